@@ -8,7 +8,7 @@ A "step" = one pass of the hot path (noising + CFG duplication + U-Net-to-tap + 
 cycle through several distinct resident batches.  Weights are seeded random tensors of the real SD1.5
 architecture (no checkpoint offline).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N > 1 runs N ranks, one per GPU: either a torch.distributed launcher started this script N times
 (WORLD_SIZE in the environment -- how the driver runs it) or the script starts the N ranks itself.  A
@@ -150,7 +150,7 @@ def cpu_model() -> str:
 def timed_steps(step, a, world, dev):
     """W untimed warm-up steps, then exactly K steps bracketed by barrier + synchronize on both sides; the score
     all_gather (the path's only collective) is inside the timed region; time = MAX over ranks.
-    Returns (seconds, scores of the first timed step, ranks seen)."""
+    Returns (seconds, scores of the first timed step, scores of the last timed step of every rank in rank order, ranks seen)."""
     import torch.distributed as dist
     first = step(0)
     for i in range(a.warmup):
@@ -171,6 +171,7 @@ def timed_steps(step, a, world, dev):
         dist.barrier()
         torch.cuda.synchronize()
     el = time.perf_counter() - t0
+    last = torch.cat([g[-1] for g in gathered]) if world > 1 else kept[-1]
     seen = 1
     if world > 1:
         tt = torch.tensor([el], dtype=torch.float64, device=dev)
@@ -179,7 +180,16 @@ def timed_steps(step, a, world, dev):
         c = torch.ones(1, dtype=torch.int64, device=dev)
         dist.all_reduce(c)
         seen = int(c.item())
-    return el, kept[0], seen
+    return el, kept[0], last, seen
+
+
+def dump_outputs(d: str, last) -> None:
+    """--dump-outputs DIR: what a caller of the timed path receives from its last step -- one float32 score per pair, every
+    rank's pairs in rank order -- as DIR/scores.npy.  Weights, latents, noise and images are all seeded, so two runs with the
+    same arguments score the same inputs and two builds can be compared output for output."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "scores.npy"), last.float().cpu().numpy())
 
 
 def roofline_fields(recs, peak, tail=None, dump=None):
@@ -410,7 +420,9 @@ def secondary(a, world, rank, dev):
                (", fp8 (e4m3) MFMA attention" if a.fp8_attention else "")
     zA, zB = zA.to(dev), zB.to(dev)
     n = [t.to(dev) for t in n]
-    el, scores, seen = timed_steps(run, a, world, dev)
+    el, scores, last, seen = timed_steps(run, a, world, dev)
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, last)
     out = {"metric": "image-pairs/sec (secondary config)", "value": round(world * a.steps * bp / el, 3), "unit": "pairs/s",
            "n_gpus": world, "n_ranks_seen": seen, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(1e3 * el / a.steps, 3),
            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": a.dtype, "data": "synthetic",
@@ -558,7 +570,9 @@ def headline(a, world, rank, dev):
             return torch.cat(parts)
         return pair_score(q, k, v, ia, ib, eng.heads, "cosine")
 
-    el, scores, seen = timed_steps(step, a, world, dev)
+    el, scores, last, seen = timed_steps(step, a, world, dev)
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, last)
     pairs_per_s = world * a.steps * bp * NS / el
     out = {
         "metric": "image-pairs/sec at 512px, SD1.5 up_blocks[0] t=600",
@@ -638,6 +652,8 @@ def main():
                     help="skip the secondary leg that scores the resident pairs through DiffSim.score_latent_pairs with no knobs")
     ap.add_argument("--no-pixels-leg", action="store_true", help="skip the pixels-in leg (VAE encoder in front) of the default run")
     ap.add_argument("--dump-launches", type=str, default=None, help="write the per-launch records of the profiled step (JSON lines)")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps, write the scores of the last timed step (all ranks, rank order) to DIR/scores.npy")
     ap.add_argument("--model", choices=["sd15", "sdxl", "dit"], default="sd15",
                     help="sd15 = the headline metric (BASELINE config[1]); sdxl / dit = secondary lines for configs[3], [4]")
     ap.add_argument("--fp8-attention", action="store_true", help="--model dit only: e4m3 MFMA attention in the DiT blocks (config 5)")
@@ -659,6 +675,8 @@ def main():
     # ---- N ranks: either a torch.distributed launcher started us (WORLD_SIZE set), or we start them ourselves -----
     if a.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         # the parent never touches the HIP runtime (not even to count devices): a rank that has no GPU says so itself
         # ("rank r needs GPU k, only n visible") and the supervisor stops the others

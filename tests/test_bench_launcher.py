@@ -7,6 +7,9 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(ROOT, "bench.py")
 
@@ -55,6 +58,9 @@ def test_mislabelled_runs_are_refused():
     else:
         assert ("visible" in r.stderr or "needs a GPU" in r.stderr) and "{" not in r.stdout
         assert "stopping the other ranks" in r.stderr
+    # no step count that would leave ms_per_step undefined
+    r = subprocess.run([sys.executable, BENCH, "--steps", "0", "--selftest-launch"], capture_output=True, text=True, env=_env(), timeout=120)
+    assert r.returncode != 0 and "--steps" in r.stderr and "{" not in r.stdout
 
 
 def test_spawn_ranks_stops_the_survivors_when_one_rank_dies(tmp_path):
@@ -114,6 +120,23 @@ def test_self_launch_eight_ranks():
     d = _line(r.stdout)
     assert d["n_gpus"] == 8 and d["n_ranks_seen"] == 8 and d["ranks_in_gather"] == list(range(8))
     assert abs(d["max_rank_s"] - 8e-3) < 1e-9          # MAX over ranks: rank 7 reports 8 ms
+
+
+@pytest.mark.gpu
+def test_dump_outputs_is_the_last_timed_step(tmp_path):
+    """--steps K times K steps and --dump-outputs DIR writes the scores the last one returned.  With one resident batch every
+    step scores the same pairs, so the dump equals the line's score_sample, which comes from the first timed step."""
+    out = tmp_path / "out"
+    r = subprocess.run([sys.executable, BENCH, "--steps", "3", "--warmup", "0", "--batch-pairs", "4", "--resident-batches", "1",
+                        "--no-profile", "--no-cpu-baseline", "--no-product-default", "--no-pixels-leg", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, env=_env(), timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _line(r.stdout)
+    assert d["steps"] == 3 and d["ms_per_step"] > 0
+    assert sorted(os.listdir(out)) == ["scores.npy"]
+    s = np.load(out / "scores.npy")
+    assert s.dtype == np.float32 and s.shape == (4,) and np.isfinite(s).all()
+    assert np.abs(s - np.array(d["score_sample"])).max() <= 1e-6          # score_sample is rounded to 6 decimals
 
 
 def _cute_tree(root, n_cls=2, n_inst=3, n_light=2, n_img=3):

@@ -1,7 +1,8 @@
 """Development probe: run the self-attention kernel on the SD1.5 level-0 shape (for rocprofv3 --pmc passes)."""
+import os
 import sys
 import torch
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from diffsim_amd import engine as E
 
 B, H, N, D = (int(x) for x in (sys.argv[1:5] if len(sys.argv) > 4 else (32, 8, 4096, 40)))

@@ -1,7 +1,8 @@
 """Development probe: the 3x3 conv GEMM on an SD1.5 level-0 / level-2 shape (for rocprofv3 --pmc passes)."""
+import os
 import sys
 import torch
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from diffsim_amd import engine as E
 
 B, H, W, Cin, Cout = (int(x) for x in (sys.argv[1:6] if len(sys.argv) > 5 else (128, 16, 16, 2560, 1280)))

@@ -3,7 +3,7 @@ import os, sys, time, tempfile
 import numpy as np
 import torch
 from PIL import Image
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from diffsim_amd import config as C, synth as S
 from diffsim_amd.diffsim import DiffSim, get_generator
 from diffsim_amd.image import load_image, process_image

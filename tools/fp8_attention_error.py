@@ -1,5 +1,5 @@
-import sys, math, torch, torch.nn.functional as F
-sys.path.insert(0, "/root/repo")
+import os, sys, math, torch, torch.nn.functional as F
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from diffsim_amd import engine as E
 for (B,H,N,D) in ((3,16,256,72),(2,4,64,32)):
     g = torch.Generator().manual_seed(1)

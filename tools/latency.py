@@ -1,6 +1,6 @@
 """Small-batch latency: eager launches vs hipGraph replay (DiffSim(use_graphs=True)).  Run on the GPU box."""
-import time, torch, sys
-sys.path.insert(0, "/root/repo")
+import os, time, torch, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from diffsim_amd import config as C, synth as S
 from diffsim_amd.diffsim import DiffSim
 cfg = C.SD15

@@ -1,8 +1,9 @@
 """Development probe: a linear GEMM (default: the tapped layer's fused q/k/v projection at 32 pairs) for --pmc passes.
 usage: lin_probe.py M N K [geglu] [res]"""
+import os
 import sys
 import torch
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from diffsim_amd import engine as E
 
 M, N, K = (int(x) for x in (sys.argv[1:4] if len(sys.argv) > 3 else (32768, 3840, 1280)))

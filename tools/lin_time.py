@@ -5,7 +5,7 @@ The hooks are NOT in the tree: apply the patch at the end of profiles/r02_linear
 import os
 import sys
 import torch
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from diffsim_amd import engine as E
 
 SHAPES = [(524288, 320, 320, False, True), (524288, 320, 320, False, False), (524288, 960, 320, False, False),

@@ -1,7 +1,7 @@
 """Development probe: per-kernel-family time of one forward at a small batch (HIP events per launch)."""
-import sys, collections
+import os, sys, collections
 import torch
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from diffsim_amd import config as C, synth as S
 from diffsim_amd.diffsim import DiffSim
 

@@ -1,8 +1,8 @@
 """Development probe: the same step N times -- q/k/v and scores must be bit-identical every time (a race in the LDS ring /
 persistent tile hand-off / attention staging / the small-batch kernel's counted-vmcnt ring would show up as a flipped bit).
     python tools/soak_determinism.py [N=200] [pairs=32] [bf16|fp16]      (pairs = 1 exercises the small-batch GEMM)"""
-import sys, torch
-sys.path.insert(0, "/root/repo")
+import os, sys, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from diffsim_amd import config as C, synth as S
 from diffsim_amd.diffsim import DiffSim
 

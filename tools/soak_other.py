@@ -1,6 +1,6 @@
 """Development probe: repeat-determinism of the VAE encoder and the DiT path (see soak_determinism.py)."""
-import sys, torch
-sys.path.insert(0, "/root/repo")
+import os, sys, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from diffsim_amd import config as C, synth as S
 from diffsim_amd.engine import VAEEncoder
 from diffsim_amd.diffsim_dit import diffsim_DiT

@@ -1,12 +1,13 @@
 """Batch-size sweep of the headline path: pairs/step in {1,2,4,8,16,32,48,64}, latents-in, bf16.
 Prints one JSON line per batch size.  Run on the GPU box: python tools/sweep_batch.py"""
 import json
+import os
 import sys
 import time
 
 import torch
 
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from diffsim_amd import config as C, synth as S
 from diffsim_amd.diffsim import DiffSim
 

@@ -1,7 +1,7 @@
 """Development probe: VAE encoder on synthetic 512 px images (for rocprofv3 --kernel-trace --stats)."""
-import sys, time
+import os, sys, time
 import torch
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from diffsim_amd import config as C, synth as S
 from diffsim_amd.engine import VAEEncoder
 
