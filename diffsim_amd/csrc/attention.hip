@@ -1016,148 +1016,6 @@ __global__ __launch_bounds__(256, (ACfg<T, D>::WPS)) void attn_kernel(const Attn
 // it is: a stream of Q in and O out.  h16; K / V images in attn_kernel's padded row-major layouts (ones column of V included).
 // The heads of a token share cache lines in Q and O (80 bytes per head at d = 40): the XCD-aware block order that keeps the
 // heads of a batch element on one XCD matters more than anything inside the loop (0.62 -> 0.46 ms at d = 40).
-#ifdef DSIM_DEVTOOLS
-// (kbench only: round 5's form of the kernel below, for interleaved A/B -- g_attn_short = 2)
-template <int D>
-__global__ __launch_bounds__(256, (D <= 80 ? 4 : 2)) void attn_short_v1_kernel(const AttnArgs p, const float scale_log2, const int qit) {
-    typedef h16 T;
-    typedef ACfg<T, D> C;
-    constexpr int KR = 96;                                   // key rows held (three 32-row MFMA blocks)
-    constexpr int CPRD = D / C::VEC;                         // real 16-byte chunks per row
-    constexpr int VOFF = KR * C::RS;                         // V image behind the K image
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, l31 = lane & 31;
-    const int nqc = (p.Nq + 128 * qit - 1) / (128 * qit);    // query chunks per (batch, head)
-    int bid = blockIdx.x;
-    if (p.xcd_remap) {          // as attn_kernel: every XCD a contiguous run of (batch, head, chunk) items -- the heads of a row share cache lines
-        const int nwg = gridDim.x, xcd = bid & 7, qq = nwg >> 3, r = nwg & 7, slot = bid >> 3;
-        bid = (xcd < r ? xcd * (qq + 1) : r * (qq + 1) + (xcd - r) * qq) + slot;
-    }
-    const int qc = bid % nqc, bh = bid / nqc;
-    const int h = bh % p.H, b = bh / p.H;
-    const size_t kvoff = (size_t)(b % p.Bkv) * p.Nk * p.ldk + h * D;
-    const T* kb = (const T*)p.k + kvoff;
-    const T* vb = (const T*)p.v + kvoff;
-    // ---- stage K and V once: zero image (padding columns, rows >= Nk), then the real chunks and V's ones column ---------
-    {
-        const u32x4 z = {0u, 0u, 0u, 0u};
-        for (int o = tid * 16; o < KR * (C::RS + C::RSV); o += 256 * 16) *reinterpret_cast<u32x4*>(smem + o) = z;
-        __syncthreads();
-        for (int idx = tid; idx < p.Nk * CPRD; idx += 256) {
-            const int r = idx / CPRD, c = idx - r * CPRD;
-            const u32x4 kk = *reinterpret_cast<const u32x4*>(kb + (size_t)r * p.ldk + c * C::VEC);
-            const u32x4 vv = *reinterpret_cast<const u32x4*>(vb + (size_t)r * p.ldk + c * C::VEC);
-            *reinterpret_cast<u32x4*>(smem + r * C::RS + c * 16) = kk;
-            *reinterpret_cast<u32x4*>(smem + VOFF + r * C::RSV + c * 16) = vv;
-        }
-        if constexpr (C::ONES)
-            for (int r = tid; r < p.Nk; r += 256) *reinterpret_cast<u32x4*>(smem + VOFF + r * C::RSV + CPRD * 16) = one_chunk<T>();
-        __syncthreads();
-    }
-    const int i16 = lane & 15, g4 = lane >> 4;
-    const char* const kfr = smem + l31 * C::RS + half * 16;
-    const char* const vfr = smem + VOFF + (4 * (g4 >> 1) + (i16 >> 2)) * C::RSV + (16 * (g4 & 1) + 4 * (i16 & 3)) * 2;
-    const int q0 = qc * 128 * qit + wave * 32 + l31;
-    QFrags<T, D> qf;
-    {
-        const int qq = q0 < p.Nq ? q0 : p.Nq - 1;
-        load_q<T, D>(qf, (const T*)p.q + ((size_t)b * p.Nq + qq) * p.ldq + h * D, half, scale_log2);
-    }
-    for (int it = 0; it < qit; ++it) {
-        const int q = q0 + it * 128;
-        if (q - l31 >= p.Nq) break;                          // wave-uniform: this wave's rows are past the end
-        // the next block's Q rows fly while this block computes
-        QFrags<T, D> qn;
-        {
-            const int qq = q + 128 < p.Nq ? q + 128 : p.Nq - 1;
-            load_q<T, D>(qn, (const T*)p.q + ((size_t)b * p.Nq + qq) * p.ldq + h * D, half, scale_log2);
-        }
-        f32x16 s[3];
-#pragma unroll
-        for (int kbk = 0; kbk < 3; ++kbk) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) s[kbk][r] = 0.f;
-#pragma unroll
-            for (int ks = 0; ks < C::NKS; ++ks) {
-                h16x8 kf;
-                lload_frag(kf, kfr + kbk * 32 * C::RS + ks * 32);
-                mma(kf, qf.f[ks], s[kbk]);
-            }
-        }
-        // keys >= Nk never count; exact row maximum over the (<= 96) keys: lane-local + one exchange between the halves
-        float m = -INFINITY;
-#pragma unroll
-        for (int kbk = 0; kbk < 3; ++kbk)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int kv = kbk * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-                if (kv >= p.Nk) s[kbk][r] = -INFINITY;
-                m = fmaxf(m, s[kbk][r]);
-            }
-        m = max_halves(m);
-        float psum = 0.f;
-#pragma unroll
-        for (int kbk = 0; kbk < 3; ++kbk)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                s[kbk][r] = __builtin_amdgcn_exp2f(s[kbk][r] - m);
-                if constexpr (!C::ONES) psum += s[kbk][r];
-            }
-        f32x16 o[C::NDB];
-#pragma unroll
-        for (int db = 0; db < C::NDB; ++db)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) o[db][r] = 0.f;
-#pragma unroll
-        for (int kbk = 0; kbk < 3; ++kbk)
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) {
-                h16x8 pf;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) pf[e] = (h16)s[kbk][8 * s2 + e];
-#pragma unroll
-                for (int db = 0; db < C::NDB; ++db) {
-                    const char* pa = vfr + (kbk * 32 + 16 * s2) * C::RSV + db * 64;
-                    const h16x4 lo = h16_ds_read_tr16_b64((pa));
-                    const h16x4 hi = h16_ds_read_tr16_b64((pa + 8 * C::RSV));
-                    h16x8 vf;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) { vf[e] = lo[e]; vf[4 + e] = hi[e]; }
-                    o[db] = H16_MFMA_32x32x16(vf, pf, o[db], 0, 0, 0);
-                }
-            }
-        float l_tot;
-        if constexpr (C::ONES) {
-            constexpr int RB = D / 32, RR = D % 32;
-            constexpr int RH = (RR >> 2) & 1, REG = (RR & 3) + 4 * (RR >> 3);
-            const float mine = o[RB][REG];
-            const float other = __shfl_xor(mine, 32);
-            l_tot = (half == RH) ? mine : other;
-        } else {
-            l_tot = psum + __shfl_xor(psum, 32);
-        }
-        const float inv = 1.0f / l_tot;
-        if (q < p.Nq) {
-            T* orow = (T*)p.out + ((size_t)b * p.Nq + q) * p.ldo + h * D;
-#pragma unroll
-            for (int db = 0; db < C::NDB; ++db)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int d = db * 32 + 8 * g + 4 * half;
-                    if (d < D) {
-                        h16x4 v4;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v4[e] = (h16)(o[db][4 * g + e] * inv);
-                        *reinterpret_cast<h16x4*>(orow + d) = v4;
-                    }
-                }
-        }
-        qf = qn;
-    }
-}
-
-#endif
-
 // Round 6 (profiles/r06_experiments.txt item 4): the loop was bound by its vector instructions (493 per 32-query block against 21
 // MFMAs; vector pipe 0.46 busy, matrix pipe 0.14), so
 //  - Q is NOT pre-scaled (24 multiplies + conversions per block): the softmax computes exp2(fma(s, c, -m c)) as packed v_pk_fma_f32;
@@ -1168,13 +1026,7 @@ __global__ __launch_bounds__(256, (D <= 80 ? 4 : 2)) void attn_short_v1_kernel(c
 //    image read the same prompt), so the 256-query level of the U-Net (d = 160: two blocks per batch element) amortises its staging
 //    over eight blocks like the others; block order [bkv][chunk][head]: the heads of a row stay neighbours on one XCD.
 template <int D, bool K80>
-__global__ __launch_bounds__(256, 2) void attn_short_kernel(const AttnArgs p, const float scale_log2, const int qit_) {
-#ifdef DSIM_DEVTOOLS
-    const int qit = qit_ & 255, abl = qit_ >> 8;        // kbench ablations: 1 = no output stores, 2 = no Q prefetch loads (timing only)
-#else
-    const int qit = qit_;
-    constexpr int abl = 0;
-#endif
+__global__ __launch_bounds__(256, 2) void attn_short_kernel(const AttnArgs p, const float scale_log2, const int qit) {
     typedef h16 T;
     typedef ACfg<T, D> C;
     constexpr int KR = 96;                                   // key rows held (three 32-row MFMA blocks)
@@ -1243,8 +1095,7 @@ __global__ __launch_bounds__(256, 2) void attn_short_kernel(const AttnArgs p, co
         if (++qblk == nqb) { qblk = 0; ++bi; }
         // the next block's Q rows fly while this block computes
         QFrags<T, D> qn;
-        if (!(abl & 2)) load_q_raw(qn, (bi < nbg ? bi : nbg - 1) * p.Bkv + bkv, qblk * 128 + wave * 32 + l31);
-        else qn = qf;
+        load_q_raw(qn, (bi < nbg ? bi : nbg - 1) * p.Bkv + bkv, qblk * 128 + wave * 32 + l31);
         if (q - l31 < p.Nq) {                               // wave-uniform: some of this wave's rows exist
             f32x16 s[3];
 #pragma unroll
@@ -1319,25 +1170,8 @@ __global__ __launch_bounds__(256, 2) void attn_short_kernel(const AttnArgs p, co
                 l_tot = psum + __shfl_xor(psum, 32);
             }
             const float inv = 1.0f / l_tot;
-            if (q < p.Nq && !(abl & 1)) {
+            if (q < p.Nq) {
                 T* orow = (T*)p.out + ((size_t)b * p.Nq + q) * p.ldo + h * D;
-#ifdef DSIM_DEVTOOLS
-                if (abl & 4) {      // kbench: the same bytes as fully coalesced 1 KB wave stores at wrong addresses (timing only)
-                    char* base = (char*)p.out + (((size_t)b * p.Nq + (q - l31)) * p.ldo) * 2 + (size_t)h * 32 * D * 2;
-                    int i = 0;
-#pragma unroll
-                    for (int db = 0; db < C::NDB; ++db)
-#pragma unroll
-                        for (int gp = 0; gp < 2; ++gp)
-                            if (db * 32 + 16 * gp < D) {
-                                u32x4 w;
-#pragma unroll
-                                for (int e = 0; e < 4; ++e) w[e] = __float_as_uint(o[db][8 * gp + e] * inv);
-                                if (i * 1024 + lane * 16 < 32 * D * 2) *reinterpret_cast<u32x4*>(base + i * 1024 + lane * 16) = w;
-                                ++i;
-                            }
-                } else
-#endif
                 store_o_rows<D>(orow, half, wide, [&](int db, int r) { return o[db][r] * inv; });
             }
         }
@@ -1469,131 +1303,148 @@ __global__ void pair_finish_kernel(const float* __restrict__ part, int n_pairs, 
 
 inline float scale_log2_of(int D) { return (1.0f / sqrtf((float)D)) * 1.4426950408889634f; }
 
-#ifdef DSIM_DEVTOOLS
-// kbench occupancy probe: g_attn_lds_pad KB of unused LDS on top of every tiled attention launch
-#define A_LAUNCH_LDS(kern, base) ([&]() { const int l_ = (base) + g_attn_lds_pad * 1024; if (g_attn_lds_pad) (void)hipFuncSetAttribute((const void*)(kern), hipFuncAttributeMaxDynamicSharedMemorySize, l_); return l_; }())
-#define DSIM_SHORT_QIT(q) ((q) | (g_attn_dbg << 8))
-#else
-#define A_LAUNCH_LDS(kern, base) (base)
-#define DSIM_SHORT_QIT(q) (q)
-#endif
+// The kernels launch_attention starts, as the profile family suffixes attention_kernel_kind names them (bench.py maps family names
+// to the symbols rocprofv3 prints):
+enum class AttnKernel {
+    P160,       // "_p160"   sdpa160_kernel (attn160.hip): 256 x 256 tokens at d = 160 on the persistent core
+    Short,      // "_short"  attn_short_kernel<D, false>: keys resident in LDS
+    ShortK80,   // "_short"  attn_short_kernel<D, true>: the same for 64 < Nk <= 80 (the 77-key prompt context)
+    Long,       // "_long"   attn_long_kernel: two query blocks per wave, pipelined
+    Q2,         // "_q2"     attn_q2_kernel<D, false>: two query blocks per wave sharing every fragment read, exact softmax
+    Q2Fast,     // "_q2fast" attn_q2_kernel<D, true>: the same with the fixed-reference softmax
+    Fast,       // "_fast"   attn_kernel<T, D, true>: the fixed-reference softmax
+    Exact,      // ""        attn_kernel<T, D, false>: the exact running maximum
+};
 
+// fewest keys that take the fixed-reference softmax: long key sequences (>= 1024 keys: the 64 x 64 and 32 x 32 self-attentions)
+// run 6 % faster on it at 4096 keys x d = 40, 10 % at 1024 keys x d = 80, 14 % at 1024 keys x d = 64 (SDXL); short ones
+// (cross-attention's 77 keys, the 16 x 16 level: 0.179 -> 0.195 ms at 256 keys x d = 160) keep the exact running maximum -- there
+// the end-of-block check costs more than the skipped maxima save
+constexpr int ATTN_FAST_MIN = 1024;
+
+// The one place that decides which kernel serves a problem: launch_attention and attention_kernel_kind both follow it.
+AttnKernel attention_kernel(const AttnArgs& a, int dtype) {
+    if (dtype == DSIM_F32) return AttnKernel::Exact;
+    if (sdpa160_applies(a)) return AttnKernel::P160;
+    // the prompt context of the cross-attentions (77 keys): keys resident in LDS, several query blocks per workgroup
+    // (round 6, interleaved A/B against the tiled kernel at 64 pairs: d = 40 0.492 -> 0.387 ms, d = 80 0.221 -> 0.199, d = 160 at
+    //  256 queries 0.112 -> 0.091, SDXL's d = 64 at 4096 / 1024 queries 0.736 -> 0.652 / 0.397 -> 0.381)
+    if ((a.D == 40 || a.D == 64 || a.D == 80 || a.D == 160) && a.Nk <= 96)
+        return a.Nk > 64 && a.Nk <= 80 ? AttnKernel::ShortK80 : AttnKernel::Short;
+    // two query blocks per wave where SD1.5's 4096-key level lives (d = 64 would spill: its K fragments and staging are wider)
+    if (a.D == 40 && a.Nk >= 2048 && a.Nk % KT == 0) return AttnKernel::Long;
+    // two query blocks per wave (attend2; d = 80 would spill 82-175 registers): halves the LDS fragment reads that bound attn_kernel;
+    // worth it from 256 queries up
+    if (a.D == 64 && a.Nk > 96 && a.Nq >= 256) return a.Nk >= ATTN_FAST_MIN ? AttnKernel::Q2Fast : AttnKernel::Q2;
+    return a.Nk >= ATTN_FAST_MIN ? AttnKernel::Fast : AttnKernel::Exact;
+}
+
+// launches the tiled kernel `kind` names (every kind but P160); the `if constexpr` guards only keep kernels from being instantiated
+// for a (T, D) that attention_kernel never sends to them, and such a pair returns DSIM_ERR_INVALID
 template <typename T, int D>
-int launch_attn_d(const AttnArgs& a, hipStream_t s) {
+int launch_attn_d(const AttnArgs& a, AttnKernel kind, hipStream_t s) {
     typedef ACfg<T, D> C;
-    const dim3 grid(((a.Nq + 127) / 128) * a.H * a.B);
-    // long key sequences (>= 1024 keys: the 64 x 64 and 32 x 32 self-attentions): the fixed-reference softmax -- 6 % faster at
-    // 4096 keys x d = 40, 10 % at 1024 keys x d = 80, 14 % at 1024 keys x d = 64 (SDXL); short ones (cross-attention's 77 keys,
-    // the 16 x 16 level: 0.179 -> 0.195 ms at 256 keys x d = 160) keep the exact running maximum -- there the end-of-block check
-    // costs more than the skipped maxima save
-    if constexpr (sizeof(T) == 2 && (D == 40 || D == 64 || D == 80 || D == 160)) {
-        // the prompt context of the cross-attentions (77 keys): keys resident in LDS, several query blocks per workgroup
-        // (round 6, interleaved A/B against the tiled kernel at 64 pairs: d = 40 0.492 -> 0.387 ms, d = 80 0.221 -> 0.199, d = 160 at
-        //  256 queries 0.112 -> 0.091, SDXL's d = 64 at 4096 / 1024 queries 0.736 -> 0.652 / 0.397 -> 0.381)
-        if (a.Nk <= 96 && g_attn_short) {
-            // TWO workgroups per CU whatever the K / V images need: the kernel is bound by the cache-line operations of its Q rows in
-            // and O rows out, and more resident workgroups only thrash that path (64 pairs, ms at 4 | 3 | 2 | 1 workgroups per CU:
-            // d = 40  0.457 | 0.426 | 0.388 | 0.447;  d = 80  0.193 | 0.181 | 0.180 | 0.191: profiles/r06_experiments.txt 4e)
-            constexpr int LDSK = 96 * (C::RS + C::RSV);
-            constexpr int LDSS = LDSK < 56 * 1024 ? 56 * 1024 : LDSK;
-#ifdef DSIM_DEVTOOLS
-            if (g_attn_short == 2) {
-                static DeviceOnce onces;
-                auto kern = attn_short_v1_kernel<D>;
-                CK_ONCE(onces, kern, LDSK);
-                const int nqb = (a.Nq + 127) / 128;
+    switch (kind) {
+        case AttnKernel::Short:
+        case AttnKernel::ShortK80:
+            if constexpr (sizeof(T) == 2 && (D == 40 || D == 64 || D == 80 || D == 160)) {
+                // TWO workgroups per CU whatever the K / V images need: the kernel is bound by the cache-line operations of its Q rows
+                // in and O rows out, and more resident workgroups only thrash that path (64 pairs, ms at 4 | 3 | 2 | 1 workgroups per CU:
+                // d = 40  0.457 | 0.426 | 0.388 | 0.447;  d = 80  0.193 | 0.181 | 0.180 | 0.191: profiles/r06_experiments.txt 4e)
+                constexpr int LDSK = 96 * (C::RS + C::RSV);
+                constexpr int LDSS = LDSK < 56 * 1024 ? 56 * 1024 : LDSK;
+                // query blocks per workgroup: as many as keep >= 8 workgroups per CU in the grid (at most 8); the 256-register d = 160
+                // instantiation (two workgroups per CU) is content with one full round.  A workgroup's blocks continue across the batch
+                // elements that share its K / V.
+                const int nqb = (a.Nq + 127) / 128, nvb = ((a.B + a.Bkv - 1) / a.Bkv) * nqb;
+                const long want = (D > 80 ? 2L : 8L) * cu_count();
                 int qit = 8;
-                while (qit > 1 && (long)((nqb + qit - 1) / qit) * a.H * a.B < 8L * cu_count()) qit >>= 1;
-                hipLaunchKernelGGL(kern, dim3(((nqb + qit - 1) / qit) * a.H * a.B), dim3(256), LDSK, s, a, scale_log2_of(D), qit);
+                while (qit > 1 && (long)((nvb + qit - 1) / qit) * a.H * a.Bkv < want) qit >>= 1;
+                const int nch = (nvb + qit - 1) / qit;
+                const dim3 g(nch * a.H * a.Bkv);
+                if (kind == AttnKernel::ShortK80) {
+                    static DeviceOnce onces;
+                    auto kern = attn_short_kernel<D, true>;
+                    CK_ONCE(onces, kern, LDSS);
+                    hipLaunchKernelGGL(kern, g, dim3(256), LDSS, s, a, scale_log2_of(D), qit);
+                } else {
+                    static DeviceOnce onces;
+                    auto kern = attn_short_kernel<D, false>;
+                    CK_ONCE(onces, kern, LDSS);
+                    hipLaunchKernelGGL(kern, g, dim3(256), LDSS, s, a, scale_log2_of(D), qit);
+                }
                 DSIM_HIP_CHECK(hipGetLastError());
                 return DSIM_OK;
             }
-#endif
-            // query blocks per workgroup: as many as keep >= 8 workgroups per CU in the grid (at most 8); the 256-register d = 160
-            // instantiation (two workgroups per CU) is content with one full round.  A workgroup's blocks continue across the batch
-            // elements that share its K / V.
-            const int nqb = (a.Nq + 127) / 128, nvb = ((a.B + a.Bkv - 1) / a.Bkv) * nqb;
-            const long want = (D > 80 ? 2L : 8L) * cu_count();
-            int qit = 8;
-            while (qit > 1 && (long)((nvb + qit - 1) / qit) * a.H * a.Bkv < want) qit >>= 1;
-            const int nch = (nvb + qit - 1) / qit;
-            const dim3 g(nch * a.H * a.Bkv);
-            if (a.Nk > 64 && a.Nk <= 80) {
-                static DeviceOnce onces;
-                auto kern = attn_short_kernel<D, true>;
-                CK_ONCE(onces, kern, LDSS);
-                hipLaunchKernelGGL(kern, g, dim3(256), LDSS, s, a, scale_log2_of(D), DSIM_SHORT_QIT(qit));
-            } else {
-                static DeviceOnce onces;
-                auto kern = attn_short_kernel<D, false>;
-                CK_ONCE(onces, kern, LDSS);
-                hipLaunchKernelGGL(kern, g, dim3(256), LDSS, s, a, scale_log2_of(D), DSIM_SHORT_QIT(qit));
-            }
-            DSIM_HIP_CHECK(hipGetLastError());
-            return DSIM_OK;
-        }
-    }
-    if constexpr (sizeof(T) == 2 && D == 40) {
-        // two query blocks per wave where SD1.5's 4096-key level lives (d = 64 would spill: its K fragments and staging are wider)
-        if (a.Nk >= 2048 && a.Nk % KT == 0 && g_attn_q2) {
-            constexpr int LDS3 = 3 * 2 * C::TILE;           // the 3-deep tile ring
+            break;
+        case AttnKernel::Long:
+            if constexpr (sizeof(T) == 2 && D == 40) {
+                constexpr int LDS3 = 3 * 2 * C::TILE;           // the 3-deep tile ring
 #ifdef DSIM_DEVTOOLS
-            switch (g_attn_dbg) {
+                switch (g_attn_dbg) {
 #define X(d) case d: { static DeviceOnce o; auto k = attn_long_kernel<D, d>; CK_ONCE(o, k, LDS3); hipLaunchKernelGGL(k, dim3(((a.Nq + 255) / 256) * a.H * a.B), dim3(256), LDS3, s, a, scale_log2_of(D)); DSIM_HIP_CHECK(hipGetLastError()); return DSIM_OK; }
-                X(8) X(32) X(64) X(96)
+                    X(8) X(32) X(64) X(96)
 #undef X
-                default: break;
-            }
+                    default: break;
+                }
 #endif
-            static DeviceOnce once2;
-            auto kern = attn_long_kernel<D, 0>;
-            CK_ONCE(once2, kern, LDS3);
-            hipLaunchKernelGGL(kern, dim3(((a.Nq + 255) / 256) * a.H * a.B), dim3(256), A_LAUNCH_LDS(kern, LDS3), s, a, scale_log2_of(D));
-            DSIM_HIP_CHECK(hipGetLastError());
-            return DSIM_OK;
-        }
-    }
-    if constexpr (sizeof(T) == 2 && D == 64) {
-        // two query blocks per wave (attend2; d = 80 would spill 82-175 registers): halves the LDS fragment reads that bound attn_kernel; worth it from 256 queries up
-        if (a.Nk > 96 && a.Nq >= 256 && g_attn_q2) {
-            const dim3 grid2(((a.Nq + 255) / 256) * a.H * a.B);
-            if (a.Nk >= g_attn_fast_min) {
-                static DeviceOnce o1;
-                auto k = attn_q2_kernel<D, true>;
-                CK_ONCE(o1, k, C::LDS);
-                hipLaunchKernelGGL(k, grid2, dim3(256), A_LAUNCH_LDS(k, C::LDS), s, a, scale_log2_of(D));
+                static DeviceOnce once2;
+                auto kern = attn_long_kernel<D, 0>;
+                CK_ONCE(once2, kern, LDS3);
+                hipLaunchKernelGGL(kern, dim3(((a.Nq + 255) / 256) * a.H * a.B), dim3(256), LDS3, s, a, scale_log2_of(D));
+                DSIM_HIP_CHECK(hipGetLastError());
+                return DSIM_OK;
+            }
+            break;
+        case AttnKernel::Q2:
+        case AttnKernel::Q2Fast:
+            if constexpr (sizeof(T) == 2 && D == 64) {
+                const dim3 grid2(((a.Nq + 255) / 256) * a.H * a.B);
+                if (kind == AttnKernel::Q2Fast) {
+                    static DeviceOnce o1;
+                    auto k = attn_q2_kernel<D, true>;
+                    CK_ONCE(o1, k, C::LDS);
+                    hipLaunchKernelGGL(k, grid2, dim3(256), C::LDS, s, a, scale_log2_of(D));
+                } else {
+                    static DeviceOnce o2;
+                    auto k = attn_q2_kernel<D, false>;
+                    CK_ONCE(o2, k, C::LDS);
+                    hipLaunchKernelGGL(k, grid2, dim3(256), C::LDS, s, a, scale_log2_of(D));
+                }
+                DSIM_HIP_CHECK(hipGetLastError());
+                return DSIM_OK;
+            }
+            break;
+        case AttnKernel::Fast:
+        case AttnKernel::Exact: {
+            const dim3 grid(((a.Nq + 127) / 128) * a.H * a.B);
+            if (kind == AttnKernel::Fast) {
+                static DeviceOnce oncef;
+                auto kern = attn_kernel<T, D, true>;
+                CK_ONCE(oncef, kern, C::LDS);
+                hipLaunchKernelGGL(kern, grid, dim3(256), C::LDS, s, a, scale_log2_of(D));
             } else {
-                static DeviceOnce o2;
-                auto k = attn_q2_kernel<D, false>;
-                CK_ONCE(o2, k, C::LDS);
-                hipLaunchKernelGGL(k, grid2, dim3(256), A_LAUNCH_LDS(k, C::LDS), s, a, scale_log2_of(D));
+                static DeviceOnce once;
+                auto kern = attn_kernel<T, D, false>;
+                CK_ONCE(once, kern, C::LDS);
+                hipLaunchKernelGGL(kern, grid, dim3(256), C::LDS, s, a, scale_log2_of(D));
             }
             DSIM_HIP_CHECK(hipGetLastError());
             return DSIM_OK;
         }
+        case AttnKernel::P160:
+            break;
     }
-    if (sizeof(T) == 2 && a.Nk >= g_attn_fast_min) {
-        static DeviceOnce oncef;
-        auto kern = attn_kernel<T, D, true>;
-        CK_ONCE(oncef, kern, C::LDS);
-        hipLaunchKernelGGL(kern, grid, dim3(256), A_LAUNCH_LDS(kern, C::LDS), s, a, scale_log2_of(D));
-    } else {
-        static DeviceOnce once;
-        auto kern = attn_kernel<T, D, false>;
-        CK_ONCE(once, kern, C::LDS);
-        hipLaunchKernelGGL(kern, grid, dim3(256), A_LAUNCH_LDS(kern, C::LDS), s, a, scale_log2_of(D));
-    }
-    DSIM_HIP_CHECK(hipGetLastError());
-    return DSIM_OK;
+    return DSIM_ERR_INVALID;
 }
 
 // head dims of the supported graphs: SD1.5 40/80/160, SDXL 64, DiT-XL/2 72, test configs 16/32/64
 #define DSIM_FOR_EACH_D(X) X(16) X(32) X(40) X(64) X(72) X(80) X(160)
 
 template <typename T>
-int launch_attn_t(const AttnArgs& a, hipStream_t s) {
+int launch_attn_t(const AttnArgs& a, AttnKernel kind, hipStream_t s) {
     switch (a.D) {
-#define X(d) case d: return launch_attn_d<T, d>(a, s);
+#define X(d) case d: return launch_attn_d<T, d>(a, kind, s);
         DSIM_FOR_EACH_D(X)
 #undef X
         default: return DSIM_ERR_INVALID;
@@ -1630,29 +1481,20 @@ int launch_tail_t(const void* q, const void* k, const void* v, const int32_t* ia
 }  // namespace
 
 #ifdef DSIM_DEVTOOLS
-int g_attn_q2 = 1;
 int g_attn_dbg = 0;
-int g_attn_lds_pad = 0;
-int g_norm_lds_pad = 0;
-int g_attn_short = 1;
-int g_attn_fast_min = 1024;
-int g_tail160 = 1;
-int g_sdpa160 = 1;
 #endif
 
-// Which kernel launch_attention picks for this problem, as the suffix of the profile family name (bench.py maps family names to
-// the symbols rocprofv3 prints): "_short" attn_short_kernel (keys resident in LDS), "_long" attn_long_kernel (two query blocks
-// per wave, pipelined), "_q2" / "_q2fast" attn_q2_kernel (two query blocks per wave sharing every fragment read; exact / fixed-reference
-// softmax), "_fast" attn_kernel with the fixed-reference softmax, "_p160" sdpa160_kernel (attn160.hip: 256 x 256 tokens at d = 160 on the
-// persistent core), "" attn_kernel with the exact running maximum.
-// Mirrors launch_attn_d's conditions (the development switches are 1 in the product).
 const char* attention_kernel_kind(const AttnArgs& a, int dtype) {
-    if (dtype == DSIM_F32) return "";
-    if (g_sdpa160 && sdpa160_applies(a)) return "_p160";
-    if ((a.D == 40 || a.D == 64 || a.D == 80 || a.D == 160) && a.Nk <= 96) return "_short";
-    if (a.D == 40 && a.Nk >= 2048 && a.Nk % KT == 0) return "_long";
-    if (a.D == 64 && a.Nk > 96 && a.Nq >= 256) return a.Nk >= g_attn_fast_min ? "_q2fast" : "_q2";
-    if (a.Nk >= g_attn_fast_min) return "_fast";
+    switch (attention_kernel(a, dtype)) {
+        case AttnKernel::P160: return "_p160";
+        case AttnKernel::Short:
+        case AttnKernel::ShortK80: return "_short";
+        case AttnKernel::Long: return "_long";
+        case AttnKernel::Q2: return "_q2";
+        case AttnKernel::Q2Fast: return "_q2fast";
+        case AttnKernel::Fast: return "_fast";
+        case AttnKernel::Exact: break;
+    }
     return "";
 }
 
@@ -1661,11 +1503,11 @@ int launch_attention(const AttnArgs& a, int dtype, hipStream_t s) {
     if (a.D % 8 || a.ldq % vec || a.ldk % vec || a.ldo % 4 || a.Nk < 1 || a.Nq < 1 || a.Bkv < 1)
         return DSIM_ERR_INVALID;
     if (dtype == DSIM_H16) {
-        if (g_sdpa160 && sdpa160_applies(a)) return launch_sdpa160(a, s);      // 256 x 256 tokens at d = 160: the persistent core (attn160.hip)
-        return launch_attn_t<h16>(a, s);
+        const AttnKernel kind = attention_kernel(a, dtype);
+        return kind == AttnKernel::P160 ? launch_sdpa160(a, s) : launch_attn_t<h16>(a, kind, s);
     }
 #ifndef DSIM_H16_IS_F16
-    if (dtype == DSIM_F32) return launch_attn_t<float>(a, s);
+    if (dtype == DSIM_F32) return launch_attn_t<float>(a, attention_kernel(a, dtype), s);
 #ifdef DSIM_HAS_F16_TWINS
     if (dtype == DSIM_F16) return launch_attention_f16(a, dtype, s);
 #endif
@@ -1689,7 +1531,7 @@ int launch_pair_score(const void* q, const void* k, const void* v, const int32_t
     if (scratch_bytes < pair_score_scratch_bytes(n_pairs, B, H, N, D)) return DSIM_ERR_WORKSPACE;
     if (n_pairs * 2 > 65535) return DSIM_ERR_INVALID;
     if (dtype == DSIM_H16) {
-        if (g_tail160 && pair_score160_applies(N, D, DSIM_H16))
+        if (pair_score160_applies(N, D, DSIM_H16))
             return launch_pair_score160(q, k, v, ia, ib, n_pairs, B, H, similarity, out, scratch, scratch_bytes, s, status);
         return launch_tail_t<h16>(q, k, v, ia, ib, n_pairs, B, H, N, D, similarity, out, scratch, s, status);
     }

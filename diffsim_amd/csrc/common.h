@@ -169,17 +169,7 @@ extern int g_gemm_exp;          // experiment mask passed to gemm_kernel
 extern int g_gemm_skinny;       // 0 = small problems through gemm_kernel as well
 extern unsigned long long* g_gemm_stamps;   // device buffer of gemm_kernel's phase stamps (-DDSIM_STAMPS builds)
 extern int g_skinny_tile;       // 0 = heuristic, else (bm << 8) | bn
-extern int g_gn_onepass;        // DSIM_GN_ONEPASS
-extern int g_ln_rows;           // DSIM_LN_ROWS
-extern int g_prep8;             // DSIM_PREP8
-extern int g_attn_q2;           // 0 = long-key attention with one query block per wave (attn_kernel)
 extern int g_attn_dbg;          // ablation mask of attn_long_kernel
-extern int g_norm_lds_pad;      // kbench occupancy probe: KB of unused LDS per GroupNorm workgroup
-extern int g_attn_lds_pad;      // kbench occupancy probe: KB of unused LDS added to the tiled attention launches
-extern int g_attn_short;        // 0 = short key sequences through attn_kernel
-extern int g_attn_fast_min;     // fewest keys that take the fixed-reference softmax of attn_kernel
-extern int g_tail160;           // 0 = the 256-token d = 160 score tail through pair_tail_kernel
-extern int g_sdpa160;           // 0 = the 256-token d = 160 self-attention through attn_kernel
 extern float* g_tail160_dbg;    // kbench: device buffer for the first unit's two attention outputs
 extern int g_tail160_exp;       // kbench: experiment mask of pair_tail160_kernel
 extern int g_ff_dbg;            // ablation mask of the fused feed-forward kernel (rowres.hip)
@@ -187,7 +177,7 @@ extern int g_rl_dbg;            // ablation mask of the row-resident Linear kern
 extern int g_rl_wpc;            // rowlin_kernel's persistent workgroups per CU (kbench occupancy probe)
 extern int g_ff_stagger;        // its wave de-phasing, in s_nop 7 units per wave index
 #else
-constexpr int g_gemm_skinny = 1, g_gemm_persistent = 1, g_force_bm = 0, g_gn_onepass = 1, g_ln_rows = 1, g_prep8 = 1, g_attn_q2 = 1, g_attn_short = 1, g_attn_fast_min = 1024, g_tail160 = 1, g_sdpa160 = 1;
+constexpr int g_gemm_skinny = 1, g_gemm_persistent = 1, g_force_bm = 0;
 #endif
 int gemm_fill_extents(GemmArgs& g, size_t es);                       // operand byte extents for the buffer descriptors
 bool gemm_skinny_applies(const GemmArgs& a);                         // small-batch kernel (gemm_skinny.hip): same arithmetic, deep ring
@@ -289,7 +279,7 @@ struct AttnArgs {
     int xcd_remap = 1;                        // 0: plain block order (micro-benchmark A/B only)
 };
 int launch_attention(const AttnArgs& a, int dtype, hipStream_t s);
-const char* attention_kernel_kind(const AttnArgs& a, int dtype);      // "_short" / "_long" / "_fast" / "": the kernel it picks
+const char* attention_kernel_kind(const AttnArgs& a, int dtype);      // "_p160" / "_short" / "_long" / "_q2" / "_q2fast" / "_fast" / "": the kernel it picks
 int launch_attention_fp8(const AttnArgs& a, hipStream_t s);      // h16 in/out, e4m3 MFMAs (attention_fp8.hip)
 size_t pair_score_scratch_bytes(int n_pairs, int B, int H, int N, int D);
 int launch_pair_score(const void* q, const void* k, const void* v, const int32_t* idx_a,

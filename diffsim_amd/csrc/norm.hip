@@ -12,16 +12,9 @@
 //   2. gn_apply : folds the slab partials in fixed order, then y = (x-mean)*rstd*gamma+beta
 //                 [*sigmoid] with 16-byte loads and stores.
 // No float atomics anywhere: results are bit-reproducible and independent of batch size.
-#include <cstdlib>
-
 #include "common.h"
 
 namespace dsim {
-// development A/B: DSIM_GN_ONEPASS=0 keeps the two-pass kernels at every level
-#ifdef DSIM_DEVTOOLS
-int g_gn_onepass = [] { const char* e = getenv("DSIM_GN_ONEPASS"); return e ? atoi(e) : 1; }();
-int g_ln_rows = [] { const char* e = getenv("DSIM_LN_ROWS"); return e ? atoi(e) : 1; }();
-#endif
 namespace {
 
 constexpr int GN_THREADS = 256;
@@ -494,7 +487,7 @@ int ln_typed(const void* x, const float* gamma, const float* beta, void* out, in
     if (C % VEC || C > 64 * 6 * VEC || M < 1) return DSIM_ERR_INVALID;
     const int S = C / VEC;
     const dim3 block(256);
-    if (!MOD && g_ln_rows && S <= 80) {      // wider rows: the wave-per-row form below already streams at > 6 TB/s
+    if (!MOD && S <= 80) {      // wider rows: the wave-per-row form below already streams at > 6 TB/s
         int LPR = 1;
         while (LPR < 64 && S % (LPR * 2) == 0) LPR *= 2;
         const int CPL = S / LPR;                       // odd by construction
@@ -712,13 +705,6 @@ int gn_onepass_slab(int C0, int C1, int B, int HW, int groups) {
     return best;
 }
 
-#ifdef DSIM_DEVTOOLS
-// (g_norm_lds_pad: kbench occupancy probe, KB of unused LDS per GroupNorm workgroup; defined in attention.hip)
-#define GN_PAD ((size_t)g_norm_lds_pad * 1024)
-#else
-#define GN_PAD ((size_t)0)
-#endif
-
 template <typename T, int NS, int UNR>
 int gn_launch(const void* x0, int C0, const void* x1, int C1, const float* gamma, const float* beta, void* out, int B,
               int HW, int groups, float eps, int silu, void* scratch, int chunks, int rb, size_t lds, hipStream_t s,
@@ -729,9 +715,9 @@ int gn_launch(const void* x0, int C0, const void* x1, int C1, const float* gamma
         hipLaunchKernelGGL(gn_fold_kernel, dim3(groups, B), dim3(GN_THREADS), 0, s, pre, pre_chunks, (C0 + C1) / 4, groups, (double*)scratch);
         chunks = 1;
     } else
-    hipLaunchKernelGGL((gn_stats_kernel<T, NS, UNR>), dim3(chunks, B), dim3(GN_THREADS), lds + GN_PAD, s, (const T*)x0, C0,
+    hipLaunchKernelGGL((gn_stats_kernel<T, NS, UNR>), dim3(chunks, B), dim3(GN_THREADS), lds, s, (const T*)x0, C0,
                        (const T*)x1, C1, HW, groups, (double*)scratch);
-    const size_t alds = (size_t)chunks * groups * 2 * sizeof(double) + GN_PAD;       // <= 32 KB
+    const size_t alds = (size_t)chunks * groups * 2 * sizeof(double);       // <= 32 KB
     if (silu)
         hipLaunchKernelGGL((gn_apply_kernel<T, true, NS, UNR>), dim3(rb, B), dim3(GN_THREADS), alds, s, (const T*)x0, C0,
                            (const T*)x1, C1, gamma, beta, (T*)out, HW, groups, eps, chunks, (const double*)scratch);
@@ -753,7 +739,7 @@ int gn_typed(const void* x0, int C0, const void* x1, int C1, const float* gamma,
         return DSIM_ERR_INVALID;
     // (precomputed statistics: whole 4-channel quads per group)
     if (pre && (x1 || groups > 64 || (C / groups) % 4)) return DSIM_ERR_INVALID;
-    if (const int CS = (g_gn_onepass && !pre) ? gn_onepass_slab<T>(C0, C1, B, HW, groups) : 0) {
+    if (const int CS = !pre ? gn_onepass_slab<T>(C0, C1, B, HW, groups) : 0) {
         const int tpr1 = CS / VEC, R1 = GN_THREADS / tpr1;
         const size_t lds1 = (size_t)R1 * CS * 2 * sizeof(float);
         if (silu)
@@ -788,7 +774,6 @@ int gn_typed(const void* x0, int C0, const void* x1, int C1, const float* gamma,
 
 // passes over the tensor the GroupNorm of this shape makes (2 = one-pass form: read + write; 3 = statistics read + read + write)
 int groupnorm_passes(int C0, int C1, int HW, int groups, int dtype) {
-    if (!g_gn_onepass) return 3;
     const int cs = dtype == DSIM_F32 ? gn_onepass_slab<float>(C0, C1, 1, HW, groups) : gn_onepass_slab<h16>(C0, C1, 1, HW, groups);   // (either 16-bit type)
     return cs ? 2 : 3;
 }

@@ -4,9 +4,6 @@
 #include "common.h"
 
 namespace dsim {
-#ifdef DSIM_DEVTOOLS
-int g_prep8 = [] { const char* e = getenv("DSIM_PREP8"); return e ? atoi(e) : 1; }();
-#endif
 namespace {
 
 __device__ __forceinline__ float ld_any(const void* p, int dt, size_t i) {
@@ -427,7 +424,7 @@ int conv_in_rows(const float* images, const float* w, const float* bias, void* o
 }
 int prep_conv_in(const float* lat, const float* noise, float sa, float sb, const float* w, const float* bias, void* out,
                  int dtype, int n_img, int Cin, int S, int Cout, int dup, hipStream_t st) {
-    if (g_prep8 && Cout % 8 == 0 && Cout / 8 <= 256) {
+    if (Cout % 8 == 0 && Cout / 8 <= 256) {
         constexpr int PP = 4;
         const int PIX = (256 / (Cout / 8)) * PP;
         const dim3 grid8((S * S + PIX - 1) / PIX, n_img);

@@ -213,8 +213,6 @@ static void bench_gemm(const char* name, int mode, int M, int N, int Cin, int H,
     HC(hipFree(A)); if (A1) HC(hipFree(A1)); HC(hipFree(Wt)); HC(hipFree(bias)); HC(hipFree(res)); HC(hipFree(out));
 }
 
-static float bf2f(unsigned short h) { unsigned u = (unsigned)h << 16; float r; memcpy(&r, &u, 4); return r; }
-
 static void bench_attn(const char* name, int B, int Bkv, int H, int Nq, int Nk, int D, int iters, Timer& t) {
     if (!want(name)) return;
     const int C = H * D;
@@ -236,140 +234,34 @@ static void bench_attn(const char* name, int B, int Bkv, int H, int Nq, int Nk, 
         a.xcd_remap = 1;
         m1.push_back(t.run([&] { st = launch_attention(a, DSIM_BF16, 0); }, iters));
     }
-    if (Nk <= 96) {                               // keys resident in LDS (attn_short_kernel; round 5's form of it) against the tiled kernel
-        std::vector<float> q1, q2, q3;
-        const size_t no = (size_t)B * Nq * C;
-        std::vector<unsigned short> h0(no), h1(no);
-        g_attn_short = 0;
-        HC(hipMemset(out, 0xff, no * 2));
-        st = launch_attention(a, DSIM_BF16, 0);
-        HC(hipMemcpy(h0.data(), out, no * 2, hipMemcpyDeviceToHost));
-        g_attn_short = 1;
-        HC(hipMemset(out, 0xff, no * 2));
-        st = launch_attention(a, DSIM_BF16, 0);
-        HC(hipMemcpy(h1.data(), out, no * 2, hipMemcpyDeviceToHost));
-        double md = 0, mx = 0; size_t nbad = 0;
-        for (size_t i = 0; i < no; ++i) {
-            const float x = bf2f(h0[i]), y = bf2f(h1[i]);
-            if (!(y - y == 0.0f)) ++nbad;
-            md = std::max(md, (double)fabsf(x - y)); mx = std::max(mx, (double)fabsf(x));
-        }
-        for (int r = 0; r < rounds; ++r) {
-            g_attn_short = 0;
-            q1.push_back(t.run([&] { st = launch_attention(a, DSIM_BF16, 0); }, iters));
-            g_attn_short = 2;
-            q3.push_back(t.run([&] { st = launch_attention(a, DSIM_BF16, 0); }, iters));
-            g_attn_short = 1;
-            q2.push_back(t.run([&] { st = launch_attention(a, DSIM_BF16, 0); }, iters));
-        }
-        if (getenv("KB_SHORTABL")) {              // ablations of the short-key kernel: 1 no output stores, 2 no Q prefetch, 3 neither, 4 the output as coalesced 1 KB stores
-            for (int m = 1; m <= 4; ++m) {
-                g_attn_dbg = m; g_attn_short = 1;
-                std::vector<float> qa;
-                for (int r = 0; r < rounds; ++r) qa.push_back(t.run([&] { st = launch_attention(a, DSIM_BF16, 0); }, iters));
-                std::sort(qa.begin(), qa.end());
-                printf("  short-key kernel ablation %d: %8.3f ms\n", m, qa[rounds / 2]);
-            }
-            g_attn_dbg = 0;
-        }
-        std::sort(q1.begin(), q1.end()); std::sort(q2.begin(), q2.end()); std::sort(q3.begin(), q3.end());
-        printf("  tiled kernel %8.3f/%8.3f ms | short-key kernel, round 5 %8.3f/%8.3f ms | short-key kernel %8.3f/%8.3f ms (min/median)   vs tiled: max |diff| %.3g of max %.3g, %zu non-finite\n",
-               q1[0], q1[rounds / 2], q3[0], q3[rounds / 2], q2[0], q2[rounds / 2], md, mx, nbad);
-    }
-    if (self && D == 160 && Nq == 256) {          // the tiled kernel against the persistent core (attn160.hip), and their outputs against each other
-        std::vector<float> q1, q2;
-        const size_t no = (size_t)B * Nq * C;
-        std::vector<unsigned short> h0(no), h1(no);
-        g_sdpa160 = 0;
-        HC(hipMemset(out, 0xff, no * 2));
-        st = launch_attention(a, DSIM_BF16, 0);
-        HC(hipMemcpy(h0.data(), out, no * 2, hipMemcpyDeviceToHost));
-        g_sdpa160 = 1;
-        HC(hipMemset(out, 0xff, no * 2));
-        st = launch_attention(a, DSIM_BF16, 0);
-        HC(hipMemcpy(h1.data(), out, no * 2, hipMemcpyDeviceToHost));
-        double md = 0, mx = 0; size_t nbad = 0, ndiff = 0;
-        for (size_t i = 0; i < no; ++i) {
-            const float x = bf2f(h0[i]), y = bf2f(h1[i]);
-            if (!(y - y == 0.0f)) ++nbad;
-            if (h0[i] != h1[i]) ++ndiff;
-            md = std::max(md, (double)fabsf(x - y)); mx = std::max(mx, (double)fabsf(x));
-        }
-        for (int r = 0; r < rounds; ++r) {
-            g_sdpa160 = 0;
-            q1.push_back(t.run([&] { st = launch_attention(a, DSIM_BF16, 0); }, iters));
-            g_sdpa160 = 1;
-            q2.push_back(t.run([&] { st = launch_attention(a, DSIM_BF16, 0); }, iters));
-        }
-        std::sort(q1.begin(), q1.end()); std::sort(q2.begin(), q2.end());
-        printf("  tiled kernel %8.4f/%8.4f ms | persistent core %8.4f/%8.4f ms (min/median)   outputs: max |diff| %.3g of max %.3g, %zu of %zu differ, %zu non-finite\n",
-               q1[0], q1[rounds / 2], q2[0], q2[rounds / 2], md, mx, ndiff, no, nbad);
-    }
-    if (Nk >= 256 && Nk < 2048) {                 // exact running maximum against the fixed-reference softmax at mid-length key sequences
-        std::vector<float> q1, q2;
-        for (int r = 0; r < rounds; ++r) {
-            g_attn_fast_min = 2048;
-            q1.push_back(t.run([&] { st = launch_attention(a, DSIM_BF16, 0); }, iters));
-            g_attn_fast_min = 256;
-            q2.push_back(t.run([&] { st = launch_attention(a, DSIM_BF16, 0); }, iters));
-        }
-        g_attn_fast_min = 1024;
-        std::sort(q1.begin(), q1.end()); std::sort(q2.begin(), q2.end());
-        printf("  running maximum %8.3f/%8.3f ms | fixed reference %8.3f/%8.3f ms (min/median)\n", q1[0], q1[rounds / 2], q2[0], q2[rounds / 2]);
-    }
-    if (Nk >= 2048 || (D == 64 && Nk > 96)) {   // one query block per wave (attn_kernel) against two (attn_long_kernel)
-        std::vector<float> q1, q2;
-        for (int r = 0; r < rounds; ++r) {
-            g_attn_q2 = 0;
-            q1.push_back(t.run([&] { st = launch_attention(a, DSIM_BF16, 0); }, iters));
-            g_attn_q2 = 1;
-            q2.push_back(t.run([&] { st = launch_attention(a, DSIM_BF16, 0); }, iters));
-        }
-        std::sort(q1.begin(), q1.end()); std::sort(q2.begin(), q2.end());
-        if (const char* e = getenv("KB_ATDBG")) {
-            std::vector<int> vals{0};
-            std::string l = e;
-            for (size_t pos = 0; pos < l.size();) {
-                size_t nx = l.find(',', pos);
-                if (nx == std::string::npos) nx = l.size();
-                vals.push_back(atoi(l.substr(pos, nx - pos).c_str()));
-                pos = nx + 1;
-            }
-            std::vector<std::vector<float>> ms(vals.size());
-            for (int r = 0; r < rounds; ++r)
-                for (size_t k = 0; k < vals.size(); ++k) {
-                    g_attn_dbg = vals[k];
-                    ms[k].push_back(t.run([&] { st = launch_attention(a, DSIM_BF16, 0); }, iters));
-                }
-            g_attn_dbg = 0;
-            printf("  attn_long ablation median ms:");
-            for (size_t k = 0; k < vals.size(); ++k) {
-                std::sort(ms[k].begin(), ms[k].end());
-                printf("  %d:%.3f", vals[k], ms[k][rounds / 2]);
-            }
-            printf("\n");
-        }
-        printf("  32 queries per wave %8.3f/%8.3f ms | 64 queries per wave %8.3f/%8.3f ms (min/median)\n", q1[0], q1[rounds / 2], q2[0], q2[rounds / 2]);
-    }
-    if (const char* e = getenv("KB_ATTNPAD")) {          // occupancy probe: KB of unused LDS per workgroup (tiled kernels)
+    if (const char* e = getenv("KB_ATDBG"); e && D == 40 && Nk >= 2048) {      // ablation masks of attn_long_kernel (its shapes only)
+        std::vector<int> vals{0};
         std::string l = e;
         for (size_t pos = 0; pos < l.size();) {
             size_t nx = l.find(',', pos);
             if (nx == std::string::npos) nx = l.size();
-            g_attn_lds_pad = atoi(l.substr(pos, nx - pos).c_str());
-            std::vector<float> qa;
-            for (int r = 0; r < rounds; ++r) qa.push_back(t.run([&] { st = launch_attention(a, DSIM_BF16, 0); }, iters));
-            std::sort(qa.begin(), qa.end());
-            printf("  +%d KB of LDS per workgroup: %8.3f ms (st=%d)\n", g_attn_lds_pad, qa[rounds / 2], st);
+            vals.push_back(atoi(l.substr(pos, nx - pos).c_str()));
             pos = nx + 1;
         }
-        g_attn_lds_pad = 0;
+        std::vector<std::vector<float>> ms(vals.size());
+        for (int r = 0; r < rounds; ++r)
+            for (size_t k = 0; k < vals.size(); ++k) {
+                g_attn_dbg = vals[k];
+                ms[k].push_back(t.run([&] { st = launch_attention(a, DSIM_BF16, 0); }, iters));
+            }
+        g_attn_dbg = 0;
+        printf("  attn_long ablation median ms:");
+        for (size_t k = 0; k < vals.size(); ++k) {
+            std::sort(ms[k].begin(), ms[k].end());
+            printf("  %d:%.3f", vals[k], ms[k][rounds / 2]);
+        }
+        printf("\n");
     }
     std::sort(m0.begin(), m0.end()); std::sort(m1.begin(), m1.end());
     const float ms = m1[rounds / 2];
     const double fl = 4.0 * B * H * (double)Nq * Nk * D;
-    printf("%-28s B=%3d H=%d Nq=%5d Nk=%5d D=%3d  plain %8.3f/%8.3f ms | xcd-aware min/median %8.3f/%8.3f ms  %7.1f TF/s  st=%d\n", name, B, H,
-           Nq, Nk, D, m0[0], m0[rounds / 2], m1[0], ms, fl / ms / 1e9, st);
+    printf("%-28s B=%3d H=%d Nq=%5d Nk=%5d D=%3d  plain %8.3f/%8.3f ms | xcd-aware min/median %8.3f/%8.3f ms  %7.1f TF/s  kind \"%s\" st=%d\n", name,
+           B, H, Nq, Nk, D, m0[0], m0[rounds / 2], m1[0], ms, fl / ms / 1e9, attention_kernel_kind(a, DSIM_BF16), st);
     HC(hipFree(q)); if (kv) HC(hipFree(kv)); HC(hipFree(out));
 }
 
@@ -419,7 +311,7 @@ static double tail_reference(const std::vector<unsigned short>& q, const std::ve
     return res * 0.5;
 }
 
-// the fused score tail at SD1.5's default tap (256 tokens x 8 heads x 160): pair_tail_kernel against pair_tail160_kernel (attn160.hip)
+// the fused score tail at SD1.5's default tap (256 tokens x 8 heads x 160): pair_tail160_kernel (attn160.hip)
 static void bench_tail(const char* name, int np, int iters, Timer& t) {
     if (!want(name)) return;
     const int B = 2, H = 8, N = 256, D = 160, C = H * D;
@@ -434,33 +326,26 @@ static void bench_tail(const char* name, int np, int iters, Timer& t) {
     HC(hipMemcpy(ia, ha.data(), np * 4, hipMemcpyHostToDevice)); HC(hipMemcpy(ib, hb.data(), np * 4, hipMemcpyHostToDevice));
     const size_t sb = pair_score_scratch_bytes(np, B, H, N, D);
     void* scratch; HC(hipMalloc(&scratch, sb));
-    float *o0, *o1;
-    HC(hipMalloc((void**)&o0, np * 4)); HC(hipMalloc((void**)&o1, np * 4));
-    int st0 = 0, st1 = 0;
+    float* o1;
+    HC(hipMalloc((void**)&o1, np * 4));
+    int st1 = 0;
     const int rounds = getenv("KB_ROUNDS") ? atoi(getenv("KB_ROUNDS")) : 5;
     for (int sim = 0; sim < 2; ++sim) {
-        std::vector<float> m0, m1;
-        for (int r = 0; r < rounds; ++r) {
-            g_tail160 = 0;
-            m0.push_back(t.run([&] { st0 = launch_pair_score(q, k, v, ia, ib, np, B, H, N, D, DSIM_BF16, sim, o0, scratch, sb, 0); }, iters));
-            g_tail160 = 1;
+        std::vector<float> m1;
+        for (int r = 0; r < rounds; ++r)
             m1.push_back(t.run([&] { st1 = launch_pair_score(q, k, v, ia, ib, np, B, H, N, D, DSIM_BF16, sim, o1, scratch, sb, 0); }, iters));
-        }
         HC(hipDeviceSynchronize());
-        std::vector<float> h0(np), h1(np);
-        HC(hipMemcpy(h0.data(), o0, np * 4, hipMemcpyDeviceToHost)); HC(hipMemcpy(h1.data(), o1, np * 4, hipMemcpyDeviceToHost));
-        double md = 0;
-        for (int i = 0; i < np; ++i) md = std::max(md, (double)fabsf(h0[i] - h1[i]) / std::max(1e-12, (double)fabsf(h0[i])));
-        std::sort(m0.begin(), m0.end()); std::sort(m1.begin(), m1.end());
+        std::vector<float> h1(np);
+        HC(hipMemcpy(h1.data(), o1, np * 4, hipMemcpyDeviceToHost));
+        std::sort(m1.begin(), m1.end());
         const double fl = 2.0 * np * B * H * 2 * 4.0 * N * N * D;
-        printf("%-20s %s pairs=%3d  tiled %8.4f/%8.4f ms %7.1f TF/s | persistent d160 %8.4f/%8.4f ms %7.1f TF/s (min/median)  max rel diff %.3g  score[0] %.6f / %.6f st=%d/%d\n",
-               name, sim ? "mse   " : "cosine", np, m0[0], m0[rounds / 2], fl / m0[rounds / 2] / 1e9, m1[0], m1[rounds / 2], fl / m1[rounds / 2] / 1e9, md,
-               h0[0], h1[0], st0, st1);
+        printf("%-20s %s pairs=%3d  persistent d160 %8.4f/%8.4f ms %7.1f TF/s (min/median)  score[0] %.6f st=%d\n",
+               name, sim ? "mse   " : "cosine", np, m1[0], m1[rounds / 2], fl / m1[rounds / 2] / 1e9, h1[0], st1);
 #ifdef DSIM_STAMPS
         if (sim == 0) {
             const int nwg = 256;
             unsigned long long* sbuf; HC(hipMalloc((void**)&sbuf, (size_t)nwg * 8 * 8 * 8)); HC(hipMemset(sbuf, 0, (size_t)nwg * 8 * 8 * 8));
-            g_tail160_dbg = (float*)sbuf; g_tail160 = 1;
+            g_tail160_dbg = (float*)sbuf;
             launch_pair_score(q, k, v, ia, ib, np, B, H, N, D, DSIM_BF16, sim, o1, scratch, sb, 0);
             HC(hipDeviceSynchronize());
             g_tail160_dbg = nullptr;
@@ -480,7 +365,7 @@ static void bench_tail(const char* name, int np, int iters, Timer& t) {
         if (getenv("KB_TAILDBG") && sim == 0) {
             // the first unit (pair 0, direction 0, b 0, head 0): both attention outputs against a host evaluation, error by key-independent position
             float* dbg; HC(hipMalloc((void**)&dbg, 2 * N * D * 4)); HC(hipMemset(dbg, 0, 2 * N * D * 4));
-            g_tail160_dbg = dbg; g_tail160 = 1;
+            g_tail160_dbg = dbg;
             launch_pair_score(q, k, v, ia, ib, np, B, H, N, D, DSIM_BF16, sim, o1, scratch, sb, 0);
             HC(hipDeviceSynchronize());
             g_tail160_dbg = nullptr;
@@ -588,7 +473,6 @@ static void bench_tail(const char* name, int np, int iters, Timer& t) {
             }
             std::vector<std::vector<float>> ms(vals.size());
             std::vector<float> sc(vals.size());
-            g_tail160 = 1;
             for (int r = 0; r < rounds; ++r)
                 for (size_t kk = 0; kk < vals.size(); ++kk) {
                     g_tail160_exp = vals[kk];
@@ -605,10 +489,10 @@ static void bench_tail(const char* name, int np, int iters, Timer& t) {
             HC(hipMemcpy(hq.data(), q, per * 2, hipMemcpyDeviceToHost)); HC(hipMemcpy(hk.data(), k, per * 2, hipMemcpyDeviceToHost));
             HC(hipMemcpy(hv.data(), v, per * 2, hipMemcpyDeviceToHost));
             const int pi = np - 1;
-            printf("   host reference pair %d: %.7f   tiled %.7f   persistent %.7f\n", pi, tail_reference(hq, hk, hv, ha[pi], hb[pi], B, H, N, D, sim), h0[pi], h1[pi]);
+            printf("   host reference pair %d: %.7f   persistent %.7f\n", pi, tail_reference(hq, hk, hv, ha[pi], hb[pi], B, H, N, D, sim), h1[pi]);
         }
     }
-    HC(hipFree(q)); HC(hipFree(k)); HC(hipFree(v)); HC(hipFree(ia)); HC(hipFree(ib)); HC(hipFree(scratch)); HC(hipFree(o0)); HC(hipFree(o1));
+    HC(hipFree(q)); HC(hipFree(k)); HC(hipFree(v)); HC(hipFree(ia)); HC(hipFree(ib)); HC(hipFree(scratch)); HC(hipFree(o1));
 }
 
 static void bench_gn(const char* name, int B, int HW, int C, int iters, Timer& t) {
@@ -620,21 +504,6 @@ static void bench_gn(const char* name, int B, int HW, int C, int iters, Timer& t
     HC(hipMalloc(&out, (size_t)B * HW * C * 2));
     HC(hipMalloc(&sc, groupnorm_scratch_bytes(B, 32)));
     int st = DSIM_OK;
-    if (const char* e = getenv("KB_NORMPAD")) {
-        std::string l = e;
-        int st2 = 0;
-        for (size_t pos = 0; pos < l.size();) {
-            size_t nx = l.find(',', pos);
-            if (nx == std::string::npos) nx = l.size();
-            g_norm_lds_pad = atoi(l.substr(pos, nx - pos).c_str());
-            std::vector<float> qa;
-            for (int r = 0; r < 5; ++r) qa.push_back(t.run([&] { st2 = launch_groupnorm(x, C, nullptr, 0, g, b, out, B, HW, 32, 1e-5f, 1, DSIM_BF16, sc, 0); }, iters));
-            std::sort(qa.begin(), qa.end());
-            printf("  %s +%d KB of LDS per workgroup: %8.4f ms (st=%d)\n", name, g_norm_lds_pad, qa[2], st2);
-            pos = nx + 1;
-        }
-        g_norm_lds_pad = 0;
-    }
     const float ms = t.run([&] { st = launch_groupnorm(x, C, nullptr, 0, g, b, out, B, HW, 32, 1e-5f, 1, DSIM_BF16, sc, 0); }, iters);
     if (getenv("KB_GN_SILU")) {      // with and without the SiLU, interleaved: is the apply pass VALU-limited?
         std::vector<float> a, c;
