@@ -40,9 +40,13 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--use_text_attn", action="store_true")
     p.add_argument("--seed", type=int, default=2333)
     # additions of this build
-    p.add_argument("--dataset", type=str, choices=["cute", "nights", "sref"], default="cute",
+    p.add_argument("--dataset", type=str, choices=["cute", "nights", "sref", "retrieval"], default="cute",
                    help="which reference loop to run: cute_main.py (class/instance/lighting tree), night_main.py (data.csv) or "
-                        "style_main.py (Sref / InstantStyle: one folder per style, 2000 sampled experiments)")
+                        "style_main.py (Sref / InstantStyle: one folder per style, 2000 sampled experiments); retrieval: every "
+                        "--query_path image against every --image_path (gallery) image, top-k rankings written to --out_path (one .txt per "
+                        "query, named by its path under --query_path)")
+    p.add_argument("--query_path", type=str, default=None, help="--dataset retrieval: folder of query images")
+    p.add_argument("--topk", type=int, default=10, help="--dataset retrieval: gallery entries ranked per query")
     p.add_argument("--experiments", type=int, default=2000, help="--dataset sref: sampled experiments (style_main.py:64)")
     p.add_argument("--model_path", type=str, default=None, help="diffusers-layout checkpoint directory (unet/, vae/, text_encoder/, tokenizer/)")
     p.add_argument("--dtype", type=str, choices=["bf16", "fp16", "fp32"], default="bf16",
@@ -203,6 +207,8 @@ def run(args) -> int:
     if rank == 0:
         print(f"=========seed {args.seed}=========")
         print(f"Experiment on {args.target_block}, layer {args.target_layer}, timestep {args.target_step}:")
+    if args.dataset == "retrieval":
+        return run_retrieval(args, scorer, layer)
     if args.dataset == "nights":
         rows = H.read_nights_csv(args.image_path)
         trip = [(r["ref"], r["left"], r["right"], r["prompt"]) for r in rows]
@@ -243,6 +249,24 @@ def run(args) -> int:
     return 0
 
 
+def run_retrieval(args, scorer, layer) -> int:
+    """--dataset retrieval: the query x gallery score matrix (retrieval.score_path_matrix) and one ranking file per query."""
+    from . import retrieval as R
+    queries, gallery = R.list_images(args.query_path), R.list_images(args.image_path)
+    try:
+        R.ranking_names(queries, args.query_path)               # two queries that would share a ranking file: refused before scoring
+    except ValueError as e:
+        raise SystemExit(str(e))
+    m, bad = R.score_path_matrix(scorer, queries, gallery, args.image_size, args.prompt, args.target_block, layer,
+                                 args.target_step, args.seed, args.similarity, return_status=True)
+    files = R.write_rankings(args.out_path, queries, gallery, m, args.topk, args.similarity, args.query_path)
+    if bad:
+        print(f"WARNING: {bad} score(s) are NaN/inf (ranked last)")
+    print(f"Score matrix {tuple(m.shape)} ({len(queries)} queries x {len(gallery)} gallery images, {args.similarity}); "
+          f"top-{min(args.topk, len(gallery))} rankings of {len(files)} queries written to {args.out_path}")
+    return 0
+
+
 def main(argv=None) -> int:
     argv = list(sys.argv[1:] if argv is None else argv)
     args = arg_parse(argv)
@@ -260,6 +284,13 @@ def main(argv=None) -> int:
                              f"(LOCAL_WORLD_SIZE / WORLD_SIZE): refusing to run a mislabelled launch")
     if args.ngpu is None:
         args.ngpu = 1
+    if args.dataset == "retrieval":
+        if args.ngpu > 1:
+            raise SystemExit("--dataset retrieval is single-GPU for now: run it with --ngpu 1")
+        if args.selftest_shard:
+            raise SystemExit("--selftest_shard checks the triplet sharding; --dataset retrieval has none")
+        if not args.query_path or not args.image_path or not args.out_path:
+            raise SystemExit("--dataset retrieval needs --query_path, --image_path (the gallery) and --out_path")
     if args.ngpu > 1 and "WORLD_SIZE" not in os.environ:
         from .parallel import spawn_ranks              # the parent never touches the GPU
         return spawn_ranks(args.ngpu, [sys.executable, "-m", "diffsim_amd"] + argv)

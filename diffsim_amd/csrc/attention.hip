@@ -1301,6 +1301,120 @@ __global__ void pair_finish_kernel(const float* __restrict__ part, int n_pairs, 
     if (status) status[p] = (sc - sc == 0.0f) ? 0 : 1;
 }
 
+// ---- score matrix ---------------------------------------------------------------------------------------------------------------
+// Every image of set A against every image of set B.  The score of (a, b) needs O_aa and O_bb, which do not depend on the partner: the
+// SELF mode computes each image's once (rounded to the compute dtype as the pair tail rounds it; f32 in the parity mode) into
+// [n][B][N][H*D], and the CROSS mode runs one attention per cell and direction -- O_ab = SDPA(Qa, Kb, Vb) against O_aa read back,
+// O_ba = SDPA(Qb, Ka, Va) against O_bb -- with the pair tail's products, reduction and partial layout [cell][dir][bh][qtile][4], so
+// pair_finish_kernel folds them.  Both modes run the same attend on the same Q fragments as pair_tail_kernel: a cell of an image
+// against itself compares bit-identical tensors, and a cell equals the pair tail's score of the same two images.
+// grid  self: (ceil(N/128), B*H, n_a + n_b);  cross: (ceil(N/128) * n_cells * 2, B*H)
+struct MatArgs {
+    const void* q[2]; const void* k[2]; const void* v[2];      // set A, set B: [n][B][N][H*D]
+    void* self[2];                                              // the sets' self outputs, same layout
+    int n_a, n_b, B, H, N;
+};
+template <typename T, int D>
+__global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void matrix_tail_kernel(const MatArgs p, float scale_log2, int mse, int self_mode,
+                                                                                     float* __restrict__ part) {
+    typedef ACfg<T, D> C;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    __shared__ float red[4][4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, l31 = lane & 31;
+    const int bh = blockIdx.y, b = bh / p.H, h = bh - b * p.H;
+    const int N = p.N, ld = p.H * D;
+    const size_t img = (size_t)p.B * N * ld;
+    const size_t boff = (size_t)b * N * ld + h * D;
+    const int qt = (N + 127) / 128;
+    int qtile, set, iq, ix, cell = 0, dir = 0;
+    if (self_mode) {
+        qtile = blockIdx.x;
+        set = (int)blockIdx.z >= p.n_a;
+        iq = ix = (int)blockIdx.z - (set ? p.n_a : 0);
+    } else {
+        qtile = blockIdx.x % qt;
+        const int cd = blockIdx.x / qt;
+        cell = cd >> 1; dir = cd & 1;
+        const int ia = cell / p.n_b, ib = cell - ia * p.n_b;
+        set = dir;
+        iq = dir ? ib : ia;
+        ix = dir ? ia : ib;
+    }
+    const T* qg = (const T*)p.q[set];
+    const T* kg = (const T*)p.k[set ^ (self_mode ? 0 : 1)];
+    const T* vg = (const T*)p.v[set ^ (self_mode ? 0 : 1)];
+    T* so = (T*)p.self[set] + iq * img + boff;
+    const int q = qtile * 128 + wave * 32 + l31;
+    const int qc = q < N ? q : N - 1;
+    QFrags<T, D> qf;
+    load_q<T, D>(qf, qg + iq * img + boff + (size_t)qc * ld, half, scale_log2);
+    OAcc<T, D> oa;
+    attend<T, D>(qf, kg + ix * img + boff, vg + ix * img + boff, ld, N, smem, oa);
+    auto& o = oa.b;
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    if (self_mode) {
+        if (q < N) {
+#pragma unroll
+            for (int db = 0; db < C::NDB; ++db)
+#pragma unroll
+                for (int r = 0; r < 16; r += 2) {
+                    T pr[2];
+                    if constexpr (sizeof(T) == 2) {
+                        const h16x2 y = __builtin_convertvector((f32x2){o[db][r], o[db][r + 1]}, h16x2);
+                        pr[0] = y[0]; pr[1] = y[1];
+                    } else {
+                        pr[0] = o[db][r]; pr[1] = o[db][r + 1];
+                    }
+#pragma unroll
+                    for (int e = 0; e < 2; ++e) {
+                        const int rr = r + e, d = db * 32 + (rr & 3) + 8 * (rr >> 2) + 4 * half;
+                        if (d < D) so[(size_t)q * ld + d] = pr[e];
+                    }
+                }
+        }
+        return;
+    }
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+    if (q < N) {
+#pragma unroll
+        for (int db = 0; db < C::NDB; ++db)
+#pragma unroll
+            for (int r = 0; r < 16; r += 2) {
+                float xv[2];
+                if constexpr (sizeof(T) == 2) {
+                    const h16x2 xp = __builtin_convertvector((f32x2){o[db][r], o[db][r + 1]}, h16x2);
+                    xv[0] = (float)xp[0]; xv[1] = (float)xp[1];
+                } else {
+                    xv[0] = o[db][r]; xv[1] = o[db][r + 1];
+                }
+#pragma unroll
+                for (int e = 0; e < 2; ++e) {
+                    const int rr = r + e, d = db * 32 + (rr & 3) + 8 * (rr >> 2) + 4 * half;
+                    if (d < D) {
+                        const float x = xv[e], y = (float)so[(size_t)q * ld + d];
+                        if (mse) { const float df = x - y; s0 = fmaf(df, df, s0); }
+                        else { s0 = fmaf(x, y, s0); s1 = fmaf(x, x, s1); s2 = fmaf(y, y, s2); }
+                    }
+                }
+            }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        s0 += __shfl_xor(s0, off);
+        s1 += __shfl_xor(s1, off);
+        s2 += __shfl_xor(s2, off);
+    }
+    if (lane == 0) { red[wave][0] = s0; red[wave][1] = s1; red[wave][2] = s2; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float* po = part + ((((size_t)cell * 2 + dir) * gridDim.y + bh) * qt + qtile) * 4;
+        po[0] = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
+        po[1] = (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]);
+        po[2] = (red[0][2] + red[1][2]) + (red[2][2] + red[3][2]);
+        po[3] = 0.f;
+    }
+}
+
 inline float scale_log2_of(int D) { return (1.0f / sqrtf((float)D)) * 1.4426950408889634f; }
 
 // The kernels launch_attention starts, as the profile family suffixes attention_kernel_kind names them (bench.py maps family names
@@ -1478,6 +1592,43 @@ int launch_tail_t(const void* q, const void* k, const void* v, const int32_t* ia
     }
 }
 
+// workspace of the tiled score matrix: [self A | self B | partials], each 256-byte aligned
+size_t mat_self_bytes(int n, int B, int H, int N, int D, int es) { return (((size_t)n * B * N * H * D * es) + 255) & ~(size_t)255; }
+size_t mat_part_bytes(long n_cells, int B, int H, int N) { return (((size_t)n_cells * 2 * B * H * ((N + 127) / 128) * 4 * sizeof(float)) + 255) & ~(size_t)255; }
+
+template <typename T, int D>
+int launch_matrix_d(const MatArgs& m, int mse, float* out, int32_t* status, float* part, hipStream_t s) {
+    typedef ACfg<T, D> C;
+    static DeviceOnce once;
+    auto kern = matrix_tail_kernel<T, D>;
+    CK_ONCE(once, kern, C::LDS);
+    const int qt = (m.N + 127) / 128;
+    hipLaunchKernelGGL(kern, dim3(qt, m.B * m.H, m.n_a + m.n_b), dim3(256), C::LDS, s, m, scale_log2_of(D), mse, 1, part);
+    hipLaunchKernelGGL(kern, dim3(qt * m.n_a * m.n_b * 2, m.B * m.H), dim3(256), C::LDS, s, m, scale_log2_of(D), mse, 0, part);
+    const int nc = m.n_a * m.n_b;
+    hipLaunchKernelGGL(pair_finish_kernel, dim3((nc + 63) / 64), dim3(64), 0, s, (const float*)part, nc, qt * m.B * m.H, mse,
+                       (double)m.B * m.H * m.N * D, out, status);
+    DSIM_HIP_CHECK(hipGetLastError());
+    return DSIM_OK;
+}
+
+template <typename T>
+int launch_matrix_t(const void* qa, const void* ka, const void* va, int n_a, const void* qb, const void* kb, const void* vb, int n_b, int B,
+                    int H, int N, int D, int mse, float* out, int32_t* status, void* scratch, hipStream_t s) {
+    MatArgs m;
+    m.q[0] = qa; m.k[0] = ka; m.v[0] = va; m.q[1] = qb; m.k[1] = kb; m.v[1] = vb;
+    m.self[0] = scratch;
+    m.self[1] = (char*)scratch + mat_self_bytes(n_a, B, H, N, D, sizeof(T));
+    m.n_a = n_a; m.n_b = n_b; m.B = B; m.H = H; m.N = N;
+    float* part = (float*)((char*)m.self[1] + mat_self_bytes(n_b, B, H, N, D, sizeof(T)));
+    switch (D) {
+#define X(d) case d: return launch_matrix_d<T, d>(m, mse, out, status, part, s);
+        DSIM_FOR_EACH_D(X)
+#undef X
+        default: return DSIM_ERR_INVALID;
+    }
+}
+
 }  // namespace
 
 #ifdef DSIM_DEVTOOLS
@@ -1540,6 +1691,39 @@ int launch_pair_score(const void* q, const void* k, const void* v, const int32_t
 #ifdef DSIM_HAS_F16_TWINS
     if (dtype == DSIM_F16)
         return launch_pair_score_f16(q, k, v, ia, ib, n_pairs, B, H, N, D, dtype, similarity, out, scratch, scratch_bytes, s, status);
+#endif
+#endif
+    return DSIM_ERR_INVALID;
+}
+
+size_t score_matrix_scratch_bytes(int n_a, int n_b, int B, int H, int N, int D, int dtype) {
+    if (n_a < 1 || n_b < 1 || B < 1 || H < 1 || N < 1 || D < 1) return 0;
+    if ((dtype == DSIM_BF16 || dtype == DSIM_F16) && pair_score160_applies(N, D, DSIM_H16))
+        return score_matrix160_scratch_bytes(n_a, n_b, B, H);           // (the fp16 persistent kernel has the bf16 one's layout)
+    const int es = dtype == DSIM_F32 ? 4 : 2;
+    return mat_self_bytes(n_a, B, H, N, D, es) + mat_self_bytes(n_b, B, H, N, D, es) + mat_part_bytes((long)n_a * n_b, B, H, N);
+}
+
+int launch_score_matrix(const void* qa, const void* ka, const void* va, int n_a, const void* qb, const void* kb, const void* vb, int n_b,
+                        int B, int H, int N, int D, int dtype, int similarity, float* out, int32_t* status, void* scratch,
+                        size_t scratch_bytes, hipStream_t s) {
+    if (n_a < 1 || n_b < 1 || B < 1 || H < 1 || N < 1 || D % 8 || (similarity != 0 && similarity != 1)) return DSIM_ERR_INVALID;
+    if (dtype != DSIM_F32 && dtype != DSIM_BF16 && dtype != DSIM_F16) return DSIM_ERR_INVALID;
+    // 32-bit grid extents and cell indices
+    const long units = (long)n_a * n_b * 2 * ((N + 127) / 128);
+    if (units >= (1l << 31) || (long)n_a * n_b * B * H * 16 >= (1l << 31) || n_a + n_b > 65535) return DSIM_ERR_INVALID;
+    if (scratch_bytes < score_matrix_scratch_bytes(n_a, n_b, B, H, N, D, dtype)) return DSIM_ERR_WORKSPACE;
+    if (dtype == DSIM_H16) {
+        if (pair_score160_applies(N, D, DSIM_H16))
+            return launch_score_matrix160(qa, ka, va, n_a, qb, kb, vb, n_b, B, H, similarity, out, status, scratch, scratch_bytes, s);
+        return launch_matrix_t<h16>(qa, ka, va, n_a, qb, kb, vb, n_b, B, H, N, D, similarity, out, status, scratch, s);
+    }
+#ifndef DSIM_H16_IS_F16
+    if (dtype == DSIM_F32)
+        return launch_matrix_t<float>(qa, ka, va, n_a, qb, kb, vb, n_b, B, H, N, D, similarity, out, status, scratch, s);
+#ifdef DSIM_HAS_F16_TWINS
+    if (dtype == DSIM_F16)
+        return launch_score_matrix_f16(qa, ka, va, n_a, qb, kb, vb, n_b, B, H, N, D, dtype, similarity, out, status, scratch, scratch_bytes, s);
 #endif
 #endif
     return DSIM_ERR_INVALID;

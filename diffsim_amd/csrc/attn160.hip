@@ -818,6 +818,330 @@ __global__ __launch_bounds__(512, 2) void sdpa160_kernel(const h16* __restrict__
     wait_vm<0>();
 }
 
+// ------------------------------------------------------------------------------------------------------------------------------------
+// The cross pass of a score MATRIX (every image of set A against every image of set B): for a cell (a, b), direction 0 is
+// O_ab = SDPA(Qa, Kb, Vb) against O_aa, direction 1 is O_ba = SDPA(Qb, Ka, Va) against O_bb.  The self outputs O_ii do not depend on
+// the partner, so the caller computes them once per image beforehand (sdpa160_kernel: the same step arithmetic as this kernel, hence
+// a cell of an image against itself compares bit-identical tensors) and a cell costs two attentions instead of the pair tail's four.
+// The kernel is sdpa160_kernel with a different unit and epilogue.  A unit is (direction, CFG half, head, partner, query image) with the
+// query image fastest: the eight consecutive units that share one partner's K / V (160 KB) run at the same time on eight workgroups
+// of ONE XCD, so that K / V is served from that XCD's L2.  The unit's self output (rounded to the compute dtype) comes back in the
+// register order of pack_o -- lane-major, as self_lanes160_kernel lays it out -- by ten inline-asm 16-byte buffer loads per lane
+// issued in step 5, two and a half steps before the epilogue uses it, counted in the hand-over waits of steps 5-7.  (Read straight
+// from the row-major output, the same data took twenty 8-byte loads whose lanes touch 32 rows each: 640 cache-line requests per wave
+// and unit against 160, and 1.85 us per step against the pair tail's 1.54.)  The products are the pair tail's: v_dot2c on packed
+// pairs, f32 per wave, per-wave partials in pair_finish160_kernel's layout [cell][dir][bh][wave].
+// sdpa160_kernel's row-major output [n][B][N][H*D] -> the lane-major order the cross pass reads: per (image, CFG half, head) and wave,
+// ten 1 KB slabs, slab j holding pack_o's register j of lanes 0..63 (the 16 bytes of d = 16 j + 4 half + {0..3, 8..11} of the lane's
+// query row 32 wave + (lane & 31)).  One thread per 16-byte output chunk; a pure permutation, so the values are sdpa160_kernel's.
+__global__ __launch_bounds__(256) void self_lanes160_kernel(const h16* __restrict__ rows, h16* __restrict__ lanes, const int n_img,
+                                                            const int B, const int H) {
+    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t total = (size_t)n_img * B * H * 8 * (2 * A_NDB) * 64;
+    if (t >= total) return;
+    const int lane = (int)(t & 63);
+    size_t r = t >> 6;
+    const int j = (int)(r % (2 * A_NDB)); r /= 2 * A_NDB;
+    const int w = (int)(r & 7); r >>= 3;
+    const int bh = (int)(r % (size_t)(B * H));
+    const size_t img = r / (size_t)(B * H);
+    const int b = bh / H, h = bh - b * H, ld = H * A_D;
+    const int row = w * 32 + (lane & 31);
+    const h16* src = rows + ((img * B + b) * A_N + row) * (size_t)ld + h * A_D + 16 * j + 4 * (lane >> 5);
+    const u32x2 lo = *reinterpret_cast<const u32x2*>(src), hi = *reinterpret_cast<const u32x2*>(src + 8);
+    const u32x4 v = {lo[0], lo[1], hi[0], hi[1]};
+    *reinterpret_cast<u32x4*>(reinterpret_cast<char*>(lanes) + t * 16) = v;
+}
+
+__global__ __launch_bounds__(512, 2) void matrix_cross160_kernel(const h16* __restrict__ qa, const h16* __restrict__ ka, const h16* __restrict__ va,
+                                                                 const h16* __restrict__ sa, const h16* __restrict__ qb, const h16* __restrict__ kb,
+                                                                 const h16* __restrict__ vb, const h16* __restrict__ sbf, const int n_a,
+                                                                 const int n_b, const int B, const int H, const float c, const int mse,
+                                                                 float* __restrict__ part) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, l31 = lane & 31;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const unsigned lbase = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem;
+    const int ld = H * A_D, rowb = ld * 2;
+    const unsigned long long imgb = (unsigned long long)B * A_N * rowb;     // bytes of one image's features
+    const int BH = B * H;
+    const int per_dir = BH * n_a * n_b, total = 2 * per_dir;
+    const int xcd = blockIdx.x & 7, wslot = blockIdx.x >> 3, g8 = (int)gridDim.x >> 6;
+    const unsigned recs = (unsigned)((A_N - 1) * rowb + A_ROWB);
+
+    auto piece_voff = [&](int pat, bool swizzle, int ln, int rb) {
+        const int f = 64 * pat + ln;
+        const int r = (f * 3277) >> 16, pos = f - r * 20;
+        const int ch = swizzle ? ((pos & ~3) | ((pos & 3) ^ (r >> 2))) : pos;
+        return r * rb + ch * 16;
+    };
+    int kv_voff[3], kv_grp[3];
+    unsigned kv_lds[3];
+    bool kv_isv[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const int pj = wave + 8 * j;
+        kv_isv[j] = pj >= 10;
+        const int p = kv_isv[j] ? pj - 10 : pj;
+        const int grp = p >= 5, pat = p - 5 * grp;
+        kv_voff[j] = piece_voff(pat, !kv_isv[j], lane, rowb);
+        kv_grp[j] = grp;
+        kv_lds[j] = (kv_isv[j] ? A_KTILE : 0) + p * 1024;
+    }
+    const bool three = wave < 4;
+    auto issue_kv = [&](const char* kp, const char* vp, int tile, int slot) {
+        const u32x4 dK = make_desc(kp, recs), dV = make_desc(vp, recs);
+        int rb = rowb;
+        unsigned lb = lbase;
+        asm volatile("" : "+s"(rb), "+s"(lb));
+        const unsigned sb = lb + slot * A_SLOT;
+        const int ts = tile * A_KT * rb;
+        dma_piece(sb + kv_lds[0], kv_voff[0], dK, ts + kv_grp[0] * 16 * rb);
+        dma_piece(sb + kv_lds[1], kv_voff[1], kv_isv[1] ? dV : dK, ts + kv_grp[1] * 16 * rb);
+        if (three) dma_piece(sb + kv_lds[2], kv_voff[2], dV, ts + kv_grp[2] * 16 * rb);
+    };
+    const unsigned qslab = lbase + A_RING + wave * A_KTILE;
+    auto issue_q = [&](const char* qp, int j) {
+        const u32x4 dQ = make_desc(qp, recs);
+        int ln = lane, rb = rowb;
+        unsigned qs = qslab;
+        asm volatile("" : "+v"(ln), "+s"(rb), "+s"(qs));
+        dma_piece(qs + j * 1024, piece_voff(j % 5, true, ln, rb), dQ, (wave * 32 + 16 * (j / 5)) * rb);
+    };
+    const int swz = (l31 >> 2) & 3;
+    const int e0 = l31 * A_ROWB + ((half ^ swz) << 4);
+    const int e1 = l31 * A_ROWB + (((2 + half) ^ swz) << 4);
+    const int vl = A_KTILE + (4 * half + ((lane & 15) >> 2)) * A_ROWB + (16 * ((lane >> 4) & 1) + 4 * (lane & 3)) * 2;
+
+    // a unit's four views: the query image's Q rows and self output, the partner's K and V (all at the unit's CFG half and head)
+    struct Unit { const char* q; const char* k; const char* v; const char* so; int pidx; };
+    auto setup = [&](int u) {
+        Unit r;
+        const int dir = u >= per_dir;
+        int t = u - dir * per_dir;
+        const int nq = dir ? n_b : n_a, np = dir ? n_a : n_b;
+        const int iq = t % nq;
+        t /= nq;
+        const int ip = t % np, bh = t / np, b = bh / H, h = bh - b * H;
+        const unsigned long long off = ((unsigned long long)b * A_N * ld + h * A_D) * 2ull;
+        const char* qs = (const char*)(dir ? qb : qa);
+        const char* ss = (const char*)(dir ? sbf : sa);
+        r.q = qs + iq * imgb + off;
+        r.so = ss + ((unsigned long long)iq * BH + bh) * (8 * A_KTILE);
+        r.k = (const char*)(dir ? ka : kb) + ip * imgb + off;
+        r.v = (const char*)(dir ? va : vb) + ip * imgb + off;
+        const int cell = dir ? ip * n_b + iq : iq * n_b + ip;
+        r.pidx = ((cell * 2 + dir) * BH + bh) * 8 + wave;
+        return r;
+    };
+    auto unit_of = [&](int it) { return ((it * g8 + (wslot >> 3)) * 8 + xcd) * 8 + (wslot & 7); };
+    h16x8 q[A_NKS];
+    auto read_q = [&]() {
+        const char* s0 = smem + A_RING + wave * A_KTILE;
+#pragma unroll
+        for (int ks = 0; ks < A_NKS; ++ks) q[ks] = *reinterpret_cast<const h16x8*>(s0 + ((ks & 1) ? e1 : e0) + (ks >> 1) * 64);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    };
+
+    int it = 0;
+    if (unit_of(0) >= total) return;
+    Unit cur = setup(unit_of(0));
+#pragma unroll
+    for (int j = 0; j < 10; ++j) issue_q(cur.q, j);
+#pragma unroll
+    for (int t = 0; t < A_NSLOT; ++t) issue_kv(cur.k, cur.v, t, t);
+    if (three) wait_vm<3 * A_NSLOT>(); else wait_vm<2 * A_NSLOT>();
+    read_q();
+    if (three) wait_vm<3 * (A_NSLOT - 1)>(); else wait_vm<2 * (A_NSLOT - 1)>();
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    h16x8 kpre[A_PRE];
+#pragma unroll
+    for (int ks = 0; ks < A_PRE; ++ks) kpre[ks] = *reinterpret_cast<const h16x8*>(smem + ((ks & 1) ? e1 : e0) + (ks >> 1) * 64);
+
+    f32x16 o[A_NDB];
+    float m_run = 0.f, l_run = 0.f;
+    const float thr = A_THR / c;
+
+    for (;;) {
+        const int un = unit_of(it + 1);
+        const bool has_next = un < total;
+        const Unit nxt = has_next ? setup(un) : cur;       // (no next unit: the look-ahead re-fetches this unit's own rows)
+        u32x4 ypk[2 * A_NDB];                              // the self output in pack_o's register order
+
+        auto step = [&](auto tc) {
+            constexpr int T = decltype(tc)::value;
+            constexpr bool FIRST = T == 0;
+            const char* sb = smem + (T & 3) * A_SLOT;
+            f32x16 s;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) s[r] = 0.f;
+            h16x8 kf[A_PRE + 1];
+#pragma unroll
+            for (int i = 0; i < A_PRE; ++i) kf[i] = kpre[i];
+#pragma unroll
+            for (int ks = 0; ks < A_NKS; ++ks) {
+                if (ks + A_PRE < A_NKS)
+                    kf[(ks + A_PRE) % (A_PRE + 1)] = *reinterpret_cast<const h16x8*>(sb + (((ks + A_PRE) & 1) ? e1 : e0) + ((ks + A_PRE) >> 1) * 64);
+                __builtin_amdgcn_sched_barrier(0);
+                s = H16_MFMA_32x32x16(kf[ks % (A_PRE + 1)], q[ks], s, 0, 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            if constexpr (T == 5) {
+                // The unit's self output, lane-major (self_lanes160_kernel): this wave's 10 KB slab, register i of every lane in the
+                // i-th kilobyte -- ten 16-byte loads per lane, each instruction one contiguous kilobyte.  Inline asm, so that hipcc does
+                // not wait for these loads with a count that ignores the DMA pieces behind them; the hand-over waits of steps 5-7 count
+                // them and the epilogue's wait names their registers.  s_nop 4: see the tail's park read-back (an SGPR operand just
+                // restored from a VGPR lane).
+                const u32x4 dS = make_desc(cur.so + (size_t)wave * A_KTILE, A_KTILE);
+                int ln = lane;
+                asm volatile("" : "+v"(ln));
+                const int po = ln * 16;
+#pragma unroll
+                for (int i = 0; i < 2 * A_NDB; ++i)
+                    asm volatile("s_nop 4\n\tbuffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(ypk[i]) : "v"(po), "s"(dS), "s"(i * 1024) : "memory");
+            }
+            const char* vb = sb + vl;
+            auto vread = [&](int j) {
+                const char* pa = vb + (j / A_NDB) * 16 * A_ROWB + (j % A_NDB) * 64;
+                const h16x4 lo = h16_ds_read_tr16_b64(pa);
+                const h16x4 hi = h16_ds_read_tr16_b64(pa + 8 * A_ROWB);
+                h16x8 vf;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) { vf[e] = lo[e]; vf[4 + e] = hi[e]; }
+                return vf;
+            };
+            h16x8 vf[A_PRE + 1];
+#pragma unroll
+            for (int j = 0; j < A_PRE; ++j) vf[j] = vread(j);
+            __builtin_amdgcn_sched_barrier(0);
+            float tmax = max16_after_mfma(s);
+            tmax = max_halves160(tmax);
+            if constexpr (FIRST) {
+                m_run = tmax;
+            } else {
+                if (!__all(tmax <= m_run + thr)) {
+                    const float mn = fmaxf(m_run, tmax);
+                    const float alpha = __builtin_amdgcn_exp2f((m_run - mn) * c);
+                    m_run = mn;
+                    l_run *= alpha;
+#pragma unroll
+                    for (int db = 0; db < A_NDB; ++db)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) o[db][r] *= alpha;
+                }
+            }
+            const float mc = -m_run * c;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) s[r] = __builtin_amdgcn_exp2f(fmaf(s[r], c, mc));
+            const float psum = (((s[0] + s[1]) + (s[2] + s[3])) + ((s[4] + s[5]) + (s[6] + s[7]))) +
+                               (((s[8] + s[9]) + (s[10] + s[11])) + ((s[12] + s[13]) + (s[14] + s[15])));
+            l_run = FIRST ? psum : l_run + psum;
+            h16x8 pf[2];
+#pragma unroll
+            for (int f = 0; f < 2; ++f)
+#pragma unroll
+                for (int e = 0; e < 8; ++e) pf[f][e] = (h16)s[8 * f + e];
+            constexpr int NPV = 2 * A_NDB;
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int j = 0; j < NPV; ++j) {
+                if (j + A_PRE < NPV) vf[(j + A_PRE) % (A_PRE + 1)] = vread(j + A_PRE);
+                if (j == NPV - A_PRE) {
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                    // Issued since the pieces of tile T + 1 (hand-over T - 3): two hand-overs' K / V pieces (3 or 2 each), their Q pieces
+                    // (two per hand-over 0-4) and -- in steps 5-7 -- the ten self-output loads of step 5.  In the first unit the
+                    // prologue's tiles stand in for hand-overs 5-7, which issue no Q pieces either.
+                    constexpr int NQ2 = (((T + 6) & 7) <= 4 ? 2 : 0) + (((T + 7) & 7) <= 4 ? 2 : 0);
+                    constexpr int NS = T >= 5 ? 2 * A_NDB : 0;
+                    if (three) wait_vm<6 + NQ2 + NS>(); else wait_vm<4 + NQ2 + NS>();
+                    __builtin_amdgcn_s_barrier();
+                    asm volatile("" ::: "memory");
+                    if constexpr (T <= 4) { issue_q(nxt.q, 2 * T); issue_q(nxt.q, 2 * T + 1); }
+                    constexpr int TN = T + A_NSLOT;
+                    if constexpr (TN < 8) issue_kv(cur.k, cur.v, TN, TN & 3);
+                    else issue_kv(nxt.k, nxt.v, TN - 8, TN & 3);
+                    const char* sn = smem + ((T + 1) & 3) * A_SLOT;
+#pragma unroll
+                    for (int ks = 0; ks < A_PRE; ++ks) kpre[ks] = *reinterpret_cast<const h16x8*>(sn + ((ks & 1) ? e1 : e0) + (ks >> 1) * 64);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                const int s2 = j / A_NDB, db = j % A_NDB;
+                if (FIRST && s2 == 0) {
+                    f32x16 z;
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) z[r] = 0.f;
+                    o[db] = H16_MFMA_32x32x16(vf[j % (A_PRE + 1)], pf[s2], z, 0, 0, 0);
+                } else {
+                    o[db] = H16_MFMA_32x32x16(vf[j % (A_PRE + 1)], pf[s2], o[db], 0, 0, 0);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        };
+        step(IC<0>{}); step(IC<1>{}); step(IC<2>{}); step(IC<3>{}); step(IC<4>{}); step(IC<5>{}); step(IC<6>{}); step(IC<7>{});
+
+        // ---- the unit's products.  The next unit's Q rows are complete in the slab (as in sdpa160_kernel): into registers first.
+        read_q();
+        {
+            u32x4 xpk[2 * A_NDB];
+            {
+                const float inv = __builtin_amdgcn_rcpf(half_sum(l_run));
+                typedef float f32x2 __attribute__((ext_vector_type(2)));
+#pragma unroll
+                for (int db = 0; db < A_NDB; ++db)
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) {
+                        const h16x2 v = __builtin_convertvector((f32x2){o[db][2 * i] * inv, o[db][2 * i + 1] * inv}, h16x2);
+                        xpk[2 * db + (i >> 2)][i & 3] = __builtin_bit_cast(unsigned, v);
+                    }
+            }
+            // issued behind the self loads: the K / V pieces of hand-overs 5-7 (2 or 3 each; 6 or more).  Loads retire in order, so
+            // vmcnt(6) has the ten self loads in; ONE statement for both wave classes names the registers it makes valid.
+            asm volatile("s_waitcnt vmcnt(6)" : "+v"(ypk[0]), "+v"(ypk[1]), "+v"(ypk[2]), "+v"(ypk[3]), "+v"(ypk[4]), "+v"(ypk[5]), "+v"(ypk[6]), "+v"(ypk[7]), "+v"(ypk[8]), "+v"(ypk[9]) :: "memory");
+            float a0[4] = {0.f, 0.f, 0.f, 0.f}, a1[4] = {0.f, 0.f, 0.f, 0.f}, a2[4] = {0.f, 0.f, 0.f, 0.f};
+            if (!mse) {
+#pragma unroll
+                for (int i = 0; i < 2 * A_NDB; ++i)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const unsigned ux = xpk[i][e], uy = ypk[i][e];
+                        const h16x2 x = __builtin_bit_cast(h16x2, ux), y = __builtin_bit_cast(h16x2, uy);
+                        a0[e] = H16_DOT2(x, y, a0[e]);
+                        a1[e] = H16_DOT2(x, x, a1[e]);
+                        a2[e] = H16_DOT2(y, y, a2[e]);
+                    }
+            } else {
+#pragma unroll
+                for (int i = 0; i < 2 * A_NDB; ++i)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const unsigned ux = xpk[i][e], uy = ypk[i][e];
+                        const h16x2 x = __builtin_bit_cast(h16x2, ux), y = __builtin_bit_cast(h16x2, uy);
+                        const float d0 = (float)x[0] - (float)y[0], d1 = (float)x[1] - (float)y[1];
+                        a0[e] = fmaf(d0, d0, a0[e]);
+                        a0[e] = fmaf(d1, d1, a0[e]);
+                    }
+            }
+            float s0 = (a0[0] + a0[1]) + (a0[2] + a0[3]);
+            float s1 = (a1[0] + a1[1]) + (a1[2] + a1[3]);
+            float s2 = (a2[0] + a2[1]) + (a2[2] + a2[3]);
+            s0 = wave_sum(s0);
+            s1 = wave_sum(s1);
+            s2 = wave_sum(s2);
+            if (lane == 0) {
+                // (x = the cross attention's output, y = the self attention's: the pair tail's order)
+                f32x4 r4 = {s0, s1, s2, 0.f};
+                *reinterpret_cast<f32x4*>(part + (size_t)cur.pidx * 4) = r4;
+            }
+        }
+        if (!has_next) break;
+        cur = nxt;
+        ++it;
+    }
+    wait_vm<0>();
+}
+
 // workgroups the launch uses: one per CU, a multiple of 16 (two directions x eight XCDs), no more than the units there are
 int tail160_grid(int n_pairs, int B, int H) {
     int g = cu_count() & ~15;
@@ -869,6 +1193,58 @@ static size_t tail160_part_bytes(int n_pairs, int B, int H) { return (((size_t)n
 size_t pair_score160_scratch_bytes(int n_pairs, int B, int H) {
     const long need = (((long)n_pairs * B * H + 7) / 8) * 16;
     return tail160_part_bytes(n_pairs, B, H) + (size_t)(need < 512 ? need : 512) * 8 * A_KTILE;
+}
+
+// ---- score matrix at the default tap: sdpa160_kernel writes every image's self output, self_lanes160_kernel reorders it lane-major,
+// matrix_cross160_kernel writes the cells' partials, pair_finish160_kernel folds them.
+// Workspace: [self A | self B | lane-major self A | lane-major self B | partials], each 256-byte aligned.
+static size_t mat160_self_bytes(int n, int B, int H) { return (((size_t)n * B * A_N * H * A_D * 2) + 255) & ~(size_t)255; }
+static size_t mat160_part_bytes(long n_cells, int B, int H) { return (((size_t)n_cells * 2 * B * H * 8 * 4 * sizeof(float)) + 255) & ~(size_t)255; }
+
+size_t score_matrix160_scratch_bytes(int n_a, int n_b, int B, int H) {
+    return 2 * (mat160_self_bytes(n_a, B, H) + mat160_self_bytes(n_b, B, H)) + mat160_part_bytes((long)n_a * n_b, B, H);
+}
+
+int launch_score_matrix160(const void* qa, const void* ka, const void* va, int n_a, const void* qb, const void* kb, const void* vb, int n_b,
+                           int B, int H, int mse, float* out, int32_t* status, void* scratch, size_t scratch_bytes, hipStream_t s) {
+    if (scratch_bytes < score_matrix160_scratch_bytes(n_a, n_b, B, H)) return DSIM_ERR_WORKSPACE;
+    // 32-bit unit and partial-slot indices
+    if ((long)n_a * n_b * B * H * 2 * 8 >= (1l << 31) || (long)(A_N - 1) * H * A_D * 2 + A_ROWB >= (1l << 31)) return DSIM_ERR_INVALID;
+    if (((size_t)qa | (size_t)ka | (size_t)va | (size_t)qb | (size_t)kb | (size_t)vb) & 15) return DSIM_ERR_INVALID;
+    char* selfa = (char*)scratch;
+    char* selfb = selfa + mat160_self_bytes(n_a, B, H);
+    char* lanea = selfb + mat160_self_bytes(n_b, B, H);
+    char* laneb = lanea + mat160_self_bytes(n_a, B, H);
+    float* part = (float*)(laneb + mat160_self_bytes(n_b, B, H));
+    const int ld = H * A_D;
+    for (int set = 0; set < 2; ++set) {
+        AttnArgs a;
+        a.q = set ? qb : qa; a.k = set ? kb : ka; a.v = set ? vb : va; a.out = set ? selfb : selfa;
+        a.ldq = a.ldk = a.ldo = ld;
+        a.B = a.Bkv = (set ? n_b : n_a) * B;
+        a.H = H; a.Nq = a.Nk = A_N; a.D = A_D;
+        if (!sdpa160_applies(a)) return DSIM_ERR_INVALID;
+        const int st = launch_sdpa160(a, s);
+        if (st != DSIM_OK) return st;
+        const size_t chunks = (size_t)a.B * H * 8 * (2 * A_NDB) * 64;
+        hipLaunchKernelGGL(self_lanes160_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, s, (const h16*)a.out,
+                           (h16*)(set ? laneb : lanea), set ? n_b : n_a, B, H);
+    }
+    int g = cu_count() & ~63;
+    if (g < 64) g = 64;
+    if (g > 512) g = 512;
+    const long need = (((long)n_a * n_b * B * H * 2 + 63) / 64) * 64;
+    if (need < g) g = (int)need;
+    static DeviceOnce once;
+    auto kern = matrix_cross160_kernel;
+    CK_ONCE(once, kern, A_LDS);
+    const float c = (1.0f / sqrtf((float)A_D)) * 1.4426950408889634f;
+    hipLaunchKernelGGL(kern, dim3(g), dim3(512), A_LDS, s, (const h16*)qa, (const h16*)ka, (const h16*)va, (const h16*)lanea, (const h16*)qb,
+                       (const h16*)kb, (const h16*)vb, (const h16*)laneb, n_a, n_b, B, H, c, mse, part);
+    hipLaunchKernelGGL(pair_finish160_kernel, dim3(n_a * n_b), dim3(64), 0, s, (const float*)part, B * H * 8, mse,
+                       (double)B * H * A_N * A_D, out, status);
+    DSIM_HIP_CHECK(hipGetLastError());
+    return DSIM_OK;
 }
 
 int launch_pair_score160(const void* q, const void* k, const void* v, const int32_t* ia, const int32_t* ib, int n_pairs, int B,

@@ -36,6 +36,10 @@
 #define launch_pair_score160 launch_pair_score160_f16
 #define sdpa160_applies sdpa160_applies_f16
 #define launch_sdpa160 launch_sdpa160_f16
+#define score_matrix_scratch_bytes score_matrix_scratch_bytes_f16
+#define launch_score_matrix launch_score_matrix_f16
+#define score_matrix160_scratch_bytes score_matrix160_scratch_bytes_f16
+#define launch_score_matrix160 launch_score_matrix160_f16
 #define ff_stream_bytes ff_stream_bytes_f16
 #define pack_ff_stream pack_ff_stream_f16
 #define launch_ff_fused launch_ff_fused_f16
@@ -295,6 +299,15 @@ int launch_pair_score160(const void* q, const void* k, const void* v, const int3
 // the same core as a plain SDPA (256 queries = 256 keys, head dim 160, 16-bit types): the U-Net's 16 x 16-level self-attentions
 bool sdpa160_applies(const AttnArgs& a);
 int launch_sdpa160(const AttnArgs& a, hipStream_t s);
+// score matrix (every image of set A against every image of set B; q, k, v of a set: [n][B][N][H*D]): the self attentions once per
+// image into the workspace, then two cross attentions per cell -- attention.hip (any shape), attn160.hip (the default tap, 16-bit)
+size_t score_matrix_scratch_bytes(int n_a, int n_b, int B, int H, int N, int D, int dtype);
+int launch_score_matrix(const void* qa, const void* ka, const void* va, int n_a, const void* qb, const void* kb, const void* vb, int n_b,
+                        int B, int H, int N, int D, int dtype, int similarity, float* out, int32_t* status, void* scratch,
+                        size_t scratch_bytes, hipStream_t s);
+size_t score_matrix160_scratch_bytes(int n_a, int n_b, int B, int H);
+int launch_score_matrix160(const void* qa, const void* ka, const void* va, int n_a, const void* qb, const void* kb, const void* vb, int n_b,
+                           int B, int H, int mse, float* out, int32_t* status, void* scratch, size_t scratch_bytes, hipStream_t s);
 
 // row-resident fused feed-forward of the 320-channel transformer blocks (h16) -- rowres.hip
 //   out = x + W2 (h * gelu(g)) + b2,  [h ; g] = W1 LN(x) + b1
@@ -333,6 +346,10 @@ int launch_attention_f16(const AttnArgs& a, int dtype, hipStream_t s);
 int launch_pair_score_f16(const void* q, const void* k, const void* v, const int32_t* idx_a, const int32_t* idx_b, int n_pairs, int B, int H,
                           int N, int D, int dtype, int similarity, float* out, void* scratch, size_t scratch_bytes, hipStream_t s,
                           int32_t* status);
+size_t score_matrix_scratch_bytes_f16(int n_a, int n_b, int B, int H, int N, int D, int dtype);
+int launch_score_matrix_f16(const void* qa, const void* ka, const void* va, int n_a, const void* qb, const void* kb, const void* vb, int n_b,
+                            int B, int H, int N, int D, int dtype, int similarity, float* out, int32_t* status, void* scratch,
+                            size_t scratch_bytes, hipStream_t s);
 #endif
 
 // Per-device once-flags for hipFuncSetAttribute(MaxDynamicSharedMemorySize) and the CU count: the attribute is a

@@ -838,6 +838,22 @@ int dsim_pair_score_status(const void* q, const void* k, const void* v, const in
                              workspace_bytes - lost, (hipStream_t)stream, status);
 }
 
+size_t dsim_score_matrix_workspace_bytes(int n_a, int n_b, int B, int H, int N, int D, int dtype) {
+    const size_t b = score_matrix_scratch_bytes(n_a, n_b, B, H, N, D, dtype);
+    return b ? b + 256 : 0;
+}
+
+int dsim_score_matrix(const void* qa, const void* ka, const void* va, int n_a, const void* qb, const void* kb, const void* vb, int n_b,
+                      int B, int H, int N, int D, int dtype, int similarity, float* out, int32_t* status, void* workspace,
+                      size_t workspace_bytes, void* stream) {
+    if (!qa || !ka || !va || !qb || !kb || !vb || !out || !workspace) return DSIM_ERR_INVALID;
+    const uintptr_t b0 = ((uintptr_t)workspace + 255) & ~(uintptr_t)255;
+    const size_t lost = b0 - (uintptr_t)workspace;
+    if (workspace_bytes < lost) return DSIM_ERR_WORKSPACE;
+    return launch_score_matrix(qa, ka, va, n_a, qb, kb, vb, n_b, B, H, N, D, dtype, similarity, out, status, (void*)b0,
+                               workspace_bytes - lost, (hipStream_t)stream);
+}
+
 // ---- single-operator entry points (tests / micro-benchmarks; these allocate and synchronise) ----
 namespace {
 struct Tmp {

@@ -316,3 +316,21 @@ class DiffSim:
             lB.append(b.to(self.noise_dtype).float())
         return self.score_latent_pairs(torch.cat(lA), torch.cat(lB), nA, nB, prompt, target_block, target_layer,
                                        target_step, similarity, unet_bp)
+
+    # ------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def score_matrix(self, paths_a: Sequence[str], paths_b: Sequence[str], img_size, prompt, target_block, target_layer,
+                     target_step, seed="2333", similarity="cosine", batch: Optional[int] = None) -> torch.Tensor:
+        """(len(paths_a), len(paths_b)) matrix of :meth:`diffsim` scores, every image pushed through the U-Net once
+        (retrieval.score_path_matrix)."""
+        from .retrieval import score_path_matrix
+        return score_path_matrix(self, paths_a, paths_b, img_size, prompt, target_block, _norm_layer(target_layer), target_step,
+                                 seed, similarity, batch)
+
+    @torch.no_grad()
+    def score_latent_matrix(self, latA, latB, noiseA, noiseB, prompt, target_block="up_blocks", target_layer=0,
+                            target_step=600, similarity="cosine", batch: Optional[int] = None) -> torch.Tensor:
+        """(n_a, n_b) matrix of :meth:`diffsim_latents` scores of (latA[i], latB[j]) (retrieval.score_latent_matrix)."""
+        from .retrieval import score_latent_matrix
+        return score_latent_matrix(self, latA, latB, noiseA, noiseB, prompt, target_block, _norm_layer(target_layer),
+                                   target_step, similarity, batch)

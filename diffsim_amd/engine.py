@@ -348,6 +348,46 @@ def pair_score(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, idx_a: torch.T
     return out
 
 
+def score_matrix_workspace_bytes(n_a: int, n_b: int, B: int, heads: int, N: int, D: int, dtype: torch.dtype) -> int:
+    return int(_lib.lib().dsim_score_matrix_workspace_bytes(n_a, n_b, B, heads, N, D, _TORCH2DSIM[dtype]))
+
+
+def score_matrix(fa, fb, heads: int, similarity: str = "cosine", return_status: bool = False):
+    """Every image of set A against every image of set B (dsim_score_matrix).  fa, fb: (q, k, v) tuples of [n][B][N][H*D]
+    device tensors of one dtype.  Returns the (n_a, n_b) f32 device tensor whose cell (i, j) is pair_score of (fa[i], fb[j]);
+    each image's self-attention is computed once.  return_status: also an int32 (n_a, n_b) tensor, 1 where the score is
+    NaN / infinite."""
+    L = _lib.lib()
+    if similarity not in ("cosine", "mse"):
+        raise ValueError(similarity)
+    (qa, ka, va), (qb, kb, vb) = fa, fb
+    _require_cuda(qa, ka, va, qb, kb, vb)
+    dt = qa.dtype
+    if dt not in _TORCH2DSIM or any(t.dtype != dt for t in (ka, va, qb, kb, vb)):
+        raise _lib.DsimError("q,k,v of both sets must share dtype float32, bfloat16 or float16")
+    if qa.ndim != 4 or any(t.shape != qa.shape for t in (ka, va)) or any(t.shape != qb.shape for t in (kb, vb)) or \
+            qa.shape[1:] != qb.shape[1:]:
+        raise _lib.DsimError("features must be [n][B][N][H*D], one geometry for both sets")
+    if not all(t.is_contiguous() for t in (qa, ka, va, qb, kb, vb)):
+        raise _lib.DsimError("features must be contiguous")
+    n_a, B, N, HD = qa.shape
+    n_b = qb.shape[0]
+    D = HD // heads
+    if D * heads != HD:
+        raise _lib.DsimError(f"H*D = {HD} is not a multiple of heads = {heads}")
+    out = torch.empty((n_a, n_b), dtype=torch.float32, device=qa.device)
+    status = torch.empty((n_a, n_b), dtype=torch.int32, device=qa.device) if return_status else None
+    with torch.cuda.device(qa.device):
+        wsb = int(L.dsim_score_matrix_workspace_bytes(n_a, n_b, B, heads, N, D, _TORCH2DSIM[dt]))
+        if wsb == 0:
+            raise _lib.DsimError(f"no score matrix for n_a={n_a} n_b={n_b} B={B} H={heads} N={N} D={D}")
+        ws = torch.empty(wsb, dtype=torch.uint8, device=qa.device)
+        _lib.check(L.dsim_score_matrix(qa.data_ptr(), ka.data_ptr(), va.data_ptr(), n_a, qb.data_ptr(), kb.data_ptr(),
+                                       vb.data_ptr(), n_b, B, heads, N, D, _TORCH2DSIM[dt], 0 if similarity == "cosine" else 1,
+                                       out.data_ptr(), _ptr(status), ws.data_ptr(), wsb, _stream_ptr()), "dsim_score_matrix")
+    return (out, status) if return_status else out
+
+
 # ---- single-operator entry points (kernel-level parity tests) -----------------------------------
 def op_linear(x, w, bias=None, residual=None, geglu=False):
     L = _lib.lib()

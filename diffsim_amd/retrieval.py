@@ -1,0 +1,187 @@
+"""Score matrices for retrieval: every query image against every gallery image.
+
+The paper ranks a whole gallery against each query (the reference's ``retrieval_vis.py`` plots such lists).  A reference call
+reseeds its generator, so the score of (query a, gallery b) depends on a only through its slot-A features (VAE draw A, noise A)
+and on b only through its slot-B features (VAE draw B, noise B).  Here every image is pushed through the U-Net once -- n_a + n_b
+forwards instead of 2 n_a n_b -- and ``engine.score_matrix`` computes each image's self-attention once and two cross attentions
+per cell.  Cell (i, j) equals what ``diffsim(paths_a[i], paths_b[j], ...)`` / ``diffsim_latents`` return for that pair.
+
+Query features are computed once and kept; the gallery runs in chunks of the adapter's engine batch (one feature batch and one
+``score_matrix`` call per chunk), and the chunk is halved until the call's workspace fits a fixed share of the free HBM.
+"""
+from __future__ import annotations
+
+import os
+from typing import List, Optional, Sequence
+
+import torch
+
+from .diffsim import get_generator
+from .engine import image_preprocess, latent_sample, score_matrix, score_matrix_workspace_bytes
+from .harness import _Adapter, _prepare, _shared_pool
+from .image import DecodePool, load_image, process_image
+
+IMAGE_EXTS = (".png", ".jpg", ".jpeg")
+WORKSPACE_SHARE = 0.25          # of the free HBM, for one score_matrix call's workspace (self outputs + partial sums)
+
+
+def list_images(root: str) -> List[str]:
+    """Every .png / .jpg / .jpeg file (either case) under root, recursively, in sorted path order."""
+    out = []
+    for d, dirs, files in os.walk(root):
+        dirs.sort()
+        out += [os.path.join(d, f) for f in sorted(files) if f.lower().endswith(IMAGE_EXTS)]
+    return sorted(out)
+
+
+def _features(ad: _Adapter, lat, noise, prompt, block, layer, step, batch: int):
+    """(q, k, v) of n latents that all sit in one slot (one noise tensor), in engine batches of `batch` images."""
+    n = lat.shape[0]
+    parts = []
+    for i0 in range(0, n, batch):
+        m = min(n, i0 + batch) - i0
+        parts.append(ad.features(lat[i0:i0 + m], noise.expand(m, *lat.shape[1:]).contiguous(), prompt, block, layer, step))
+    if len(parts) == 1:
+        return tuple(t.contiguous() for t in parts[0])
+    return tuple(torch.cat([p[i] for p in parts]) for i in range(3))
+
+
+@torch.no_grad()
+def score_latent_matrix(scorer, latA, latB, noiseA, noiseB, prompt, target_block="up_blocks", target_layer=0, target_step=600,
+                        similarity="cosine", batch: Optional[int] = None, return_status: bool = False):
+    """(n_a, n_b) f32 device tensor: query latents latA in slot A (noiseA), gallery latents latB in slot B (noiseB), any
+    scorer kind (DiffSim, diffsim_xl, diffsim_DiT).  noiseA / noiseB: (1, C, s, s), shared by every pair as in the reference.
+    batch: gallery images per chunk (None: the adapter's engine batch, 3 images per triplet of ``auto_triplets``).
+    return_status: also the number of NaN / infinite cells."""
+    ad = _Adapter(scorer)
+    dev = scorer.device
+    latA = latA.to(dev, torch.float32)
+    latB = latB.to(dev, torch.float32)
+    nA = noiseA.to(dev, torch.float32)
+    nB = noiseB.to(dev, torch.float32)
+    n_a, n_b = latA.shape[0], latB.shape[0]
+    heads = ad.heads(target_block, target_layer)
+    if batch is None:
+        batch = 3 * ad.auto_triplets(target_block, target_layer, max(n_a, n_b))
+    batch = max(1, int(batch))
+    fa = _features(ad, latA, nA, prompt, target_block, target_layer, target_step, batch)
+    out = torch.empty((n_a, n_b), dtype=torch.float32, device=dev)
+    bad = torch.zeros((), dtype=torch.int64, device=dev)
+    _, B, N, HD = fa[0].shape
+    chunk = min(batch, n_b) if n_b else 1
+    try:
+        free, _total = torch.cuda.mem_get_info(dev)
+        while chunk > 1 and score_matrix_workspace_bytes(n_a, chunk, B, heads, N, HD // heads, fa[0].dtype) > WORKSPACE_SHARE * free:
+            chunk = (chunk + 1) // 2
+    except RuntimeError:
+        pass
+    for j0 in range(0, n_b, chunk):
+        j1 = min(n_b, j0 + chunk)
+        fb = _features(ad, latB[j0:j1], nB, prompt, target_block, target_layer, target_step, batch)
+        s, st = score_matrix(fa, fb, heads, similarity, return_status=True)
+        out[:, j0:j1] = s
+        bad += st.sum()
+    return (out, int(bad)) if return_status else out
+
+
+@torch.no_grad()
+def score_path_matrix(scorer, paths_a: Sequence[str], paths_b: Sequence[str], img_size, prompt, target_block="up_blocks",
+                      target_layer=0, target_step=600, seed=2333, similarity="cosine", batch: Optional[int] = None,
+                      return_status: bool = False):
+    """The (len(paths_a), len(paths_b)) matrix of ``diffsim(paths_a[i], paths_b[j], ...)`` scores: the query images are
+    encoded with the reseeded generator's slot-A VAE draw and noise, the gallery images with the slot-B ones (the adapter's
+    draw order: VAE sample A, VAE sample B, noise A, noise B).  Through the scorer's HIP VAE fast path where it has one."""
+    ad = _Adapter(scorer)
+    dev = scorer.device
+    if not paths_a or not paths_b:
+        empty = torch.empty((len(paths_a), len(paths_b)), dtype=torch.float32, device=dev)
+        return (empty, 0) if return_status else empty
+    if ad.fast:
+        vae = ad.vae
+        sf = vae.config.scaling_factor
+        pool = getattr(scorer, "_decode", None) or _shared_pool()
+        draws = None
+        lats = ([], [])
+        chunk = 16                      # images per VAE encode (32 at 512 px keep its widest activation < 2 GiB)
+        for slot, paths in enumerate((paths_a, paths_b)):
+            for i0 in range(0, len(paths), chunk):
+                px = DecodePool.gather(pool.submit(list(paths[i0:i0 + chunk]), img_size))
+                x = image_preprocess(px.to(vae.device, non_blocking=True), ad.image_half)
+                mom = vae.moments(x)
+                if draws is None:
+                    g = get_generator(seed, "cpu")
+                    shp = (1, mom.shape[1] // 2) + tuple(mom.shape[2:])
+                    eA = torch.randn(shp, generator=g, dtype=ad.eps_dtype).float().to(vae.device)
+                    eB = torch.randn(shp, generator=g, dtype=ad.eps_dtype).float().to(vae.device)
+                    nA = torch.randn(shp, generator=g, dtype=ad.noise_draw).float()
+                    nB = torch.randn(shp, generator=g, dtype=ad.noise_draw).float()
+                    draws = (eA, eB, nA, nB)
+                lats[slot].append(latent_sample(mom, draws[slot], sf, 0, 1, ad.round16))
+        latA, latB = torch.cat(lats[0]), torch.cat(lats[1])
+        nA, nB = draws[2], draws[3]
+    else:
+        # no HIP VAE plugged in: the scorer's own prepare_image_latents per image, in the reference's draw order.  Every call
+        # reseeds, so the generator state behind slot A's draw is the same for every pair: it is taken once, behind the first
+        # query's encode, and each gallery image's slot-B draw starts from it
+        la, lb = [], []
+        nA = nB = None
+        after_a = None
+        for p in paths_a:
+            g = get_generator(seed, "cpu")
+            la.append(_prepare(scorer, ad, process_image(load_image(p), img_size), g))
+            if after_a is None:
+                after_a = g.get_state()
+        for p in paths_b:
+            g = torch.Generator("cpu")
+            g.set_state(after_a)
+            lb.append(_prepare(scorer, ad, process_image(load_image(p), img_size), g))
+            if nA is None:
+                nA = torch.randn(lb[-1].shape, generator=g, dtype=ad.noise_draw).float()
+                nB = torch.randn(lb[-1].shape, generator=g, dtype=ad.noise_draw).float()
+        latA, latB = torch.cat(la), torch.cat(lb)
+    return score_latent_matrix(scorer, latA, latB, nA, nB, prompt, target_block, target_layer, target_step, similarity, batch,
+                               return_status)
+
+
+def topk(matrix: torch.Tensor, k: int, similarity: str = "cosine"):
+    """(values, indices) of the k best gallery entries per query row: descending for cosine, ascending for mse (the
+    reference drivers' ordering rule, night_main.py:157-163).  Ties go to the lower gallery index."""
+    m = matrix.detach().float().cpu()
+    k = max(0, min(int(k), m.shape[1]))
+    # a stable sort keeps equal scores in gallery order; NaN scores rank last either way
+    key = torch.nan_to_num(-m if similarity == "cosine" else m, nan=float("inf"))
+    idx = torch.sort(key, dim=1, stable=True).indices[:, :k]
+    return torch.gather(m, 1, idx), idx
+
+
+def ranking_names(paths_a: Sequence[str], root: Optional[str] = None) -> List[str]:
+    """Ranking file name per query: ``<query path relative to root, extension dropped>.txt`` (root: the queries' common
+    folder), so that a/cat.png and b/cat.png get a/cat.txt and b/cat.txt.  Two queries that would share a file (cat.png and
+    cat.jpg in one folder) are refused rather than overwriting each other."""
+    if not paths_a:
+        return []
+    root = root if root is not None else os.path.commonpath([os.path.dirname(os.path.abspath(p)) for p in paths_a])
+    names = [os.path.splitext(os.path.relpath(os.path.abspath(p), root))[0] + ".txt" for p in paths_a]
+    seen = {}
+    for p, n in zip(paths_a, names):
+        if n in seen:
+            raise ValueError(f"queries {seen[n]} and {p} would both be ranked into {n}")
+        seen[n] = p
+    return names
+
+
+def write_rankings(out_dir: str, paths_a: Sequence[str], paths_b: Sequence[str], matrix: torch.Tensor, k: int,
+                   similarity: str = "cosine", query_root: Optional[str] = None) -> List[str]:
+    """One ranking file per query under out_dir (``ranking_names``: the query's path relative to query_root with .txt): k lines
+    ``<gallery path> <score>`` in rank order.  Returns the files."""
+    names = ranking_names(paths_a, query_root)
+    vals, idx = topk(matrix, k, similarity)
+    files = []
+    for i, name in enumerate(names):
+        fn = os.path.join(out_dir, name)
+        os.makedirs(os.path.dirname(fn), exist_ok=True)
+        with open(fn, "w") as f:
+            for v, j in zip(vals[i].tolist(), idx[i].tolist()):
+                f.write(f"{paths_b[j]} {v:.8g}\n")
+        files.append(fn)
+    return files

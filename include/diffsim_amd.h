@@ -188,6 +188,26 @@ int    dsim_pair_score_status(const void* q, const void* k, const void* v, const
                               int similarity, float* out_scores, int32_t* status, void* workspace,
                               size_t workspace_bytes, void* stream);
 
+/* ---- score matrix: every image of set A against every image of set B (retrieval: queries x gallery) --
+ * out[a][b] is what dsim_pair_score returns for the pair (image a of set A, image b of set B), but each image's
+ * self-attention O_ii = SDPA(Q_i, K_i, V_i) is computed once per call instead of once per pair: a cell costs the two
+ * cross attentions, the self attentions cost n_a + n_b.  The sets are separate tensors, so a retained query set can be
+ * scored against fresh gallery chunks without copying.
+ *   qa,ka,va    : dtype [n_a][B][N][H*D]   (set A: the query images, 16-byte aligned)
+ *   qb,kb,vb    : dtype [n_b][B][N][H*D]   (set B: the gallery images)
+ *   similarity  : 0 cosine, 1 mse
+ *   out         : device f32 [n_a][n_b]
+ *   status      : NULL, or device int32 [n_a][n_b]: 1 where the score is NaN or infinite (as dsim_pair_score_status)
+ * DSIM_ERR_INVALID for an unsupported shape or dtype, DSIM_ERR_WORKSPACE when workspace_bytes is short of
+ * dsim_score_matrix_workspace_bytes (which returns 0 for an invalid shape).  Deterministic: a cell's value does not
+ * depend on the other cells of the call. */
+size_t dsim_score_matrix_workspace_bytes(int n_a, int n_b, int B, int H, int N, int D, int dtype);
+int    dsim_score_matrix(const void* qa, const void* ka, const void* va, int n_a,
+                         const void* qb, const void* kb, const void* vb, int n_b,
+                         int B, int H, int N, int D, int dtype, int similarity,
+                         float* out, int32_t* status, void* workspace, size_t workspace_bytes,
+                         void* stream);
+
 /* ---- VAE encoder: replaces `pipe.vae.encode(image)` in
  *      DiffSim.prepare_image_latents (diffsim/diffsim.py:92-96).  Sampling
  *      z = mean + exp(0.5*clamp(logvar,-30,20))*eps and the 0.18215 scaling stay with the caller,
