@@ -6,6 +6,14 @@
 //                          flattened (B, H, N, D) tensors -- for N = 256 tokens, head dim 160, 16-bit compute types.
 //  * sdpa160_kernel      : the same core as a plain SDPA -- the U-Net's own self-attentions of that level
 //                          (/root/reference/diffsim/hacked_attn.py:74-81); described where it is defined.
+//  * matrix_cross160_kernel : the cross pass of a score matrix -- sdpa160_kernel's 8-step core with another unit and epilogue.
+//
+// The three kernels write the core out each in full: the DMA piece table, the ring's hand-overs, QK^T, the softmax and the PV.
+// They share piece_voff (the DMA piece layout), vread160 (the V^T fragment reads), the dynamic LDS declaration and the host's grid,
+// softmax-constant and partial-size helpers.  The rest stays written out because moving it into shared helpers changes the
+// instructions hipcc emits (instruction order, register assignment, VGPR count), and the counted s_waitcnt hand-overs and the
+// inline-asm loads are checked against the exact instruction sequence around them.  A fix in one kernel's core must be repeated
+// in the other two.
 //
 // Why a kernel of its own.  pair_tail_kernel<h16, 160> (attention.hip) gives a 128-query workgroup its own single-buffered
 // copy of every key tile: 50 % of its wave cycles wait for global loads or barriers and the matrix pipe is 0.2 busy.  The work
@@ -103,6 +111,29 @@ __device__ __forceinline__ float wave_sum(float x) {
            (__int_as_float(__builtin_amdgcn_readlane(v, 47)) + __int_as_float(__builtin_amdgcn_readlane(v, 63)));
 }
 
+// The three persistent kernels' LDS (A_LDS bytes): the 4-slot K / V ring, then one 10 KB Q slab per wave
+extern __shared__ __attribute__((aligned(16))) char smem[];
+
+// DMA pieces.  A piece is 1 KB = 3.2 dense rows of a 32-row image: lane ln writes LDS byte 1024 p + 16 ln and chooses its source
+// chunk (K, Q: swizzled).  The lane pattern repeats every 5 pieces = 16 rows: pat = p % 5; rb = the source's bytes per row.
+__device__ __forceinline__ int piece_voff(int pat, bool swizzle, int ln, int rb) {
+    const int f = 64 * pat + ln;
+    const int r = (f * 3277) >> 16, pos = f - r * 20;            // f / 20, f % 20 (f < 320)
+    const int ch = swizzle ? ((pos & ~3) | ((pos & 3) ^ (r >> 2))) : pos;
+    return r * rb + ch * 16;
+}
+
+// the V^T fragment of PV MFMA j = 5 s2 + db: transposed reads from vb = the slot's V tile + the lane's offset vl
+__device__ __forceinline__ h16x8 vread160(const char* vb, int j) {
+    const char* pa = vb + (j / A_NDB) * 16 * A_ROWB + (j % A_NDB) * 64;
+    const h16x4 lo = h16_ds_read_tr16_b64(pa);
+    const h16x4 hi = h16_ds_read_tr16_b64(pa + 8 * A_ROWB);
+    h16x8 vf;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { vf[e] = lo[e]; vf[4 + e] = hi[e]; }
+    return vf;
+}
+
 template <int N> struct IC { static constexpr int value = N; };
 
 // In-kernel phase stamps (-DDSIM_DEVTOOLS -DDSIM_STAMPS builds of tools/kbench only; the s_waitcnt behind each s_memtime also
@@ -152,7 +183,6 @@ __global__ __launch_bounds__(512, 2) void pair_tail160_kernel(const h16* __restr
                                                               , float* __restrict__ dbg, const int exp
 #endif
                                                               ) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, l31 = lane & 31;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const unsigned lbase = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem;
@@ -164,14 +194,6 @@ __global__ __launch_bounds__(512, 2) void pair_tail160_kernel(const h16* __restr
     const int xcd = blockIdx.x & 7, wslot = blockIdx.x >> 3, cj = wslot >> 1, dir = wslot & 1, npc = (int)gridDim.x >> 4;
     const unsigned recs = (unsigned)((A_N - 1) * rowb + A_ROWB);    // bytes of one (image, CFG half, head) view from its first element
 
-    // ---- DMA pieces.  A piece is 1 KB = 3.2 dense rows of a 32-row image: lane i writes LDS byte 1024 p + 16 i and chooses its
-    // source chunk (K, Q: swizzled).  The lane pattern repeats every 5 pieces = 16 rows.
-    auto piece_voff = [&](int pat, bool swizzle, int ln, int rb) {
-        const int f = 64 * pat + ln;
-        const int r = (f * 3277) >> 16, pos = f - r * 20;            // f / 20, f % 20 (f < 320)
-        const int ch = swizzle ? ((pos & ~3) | ((pos & 3) ^ (r >> 2))) : pos;
-        return r * rb + ch * 16;
-    };
     // K / V: this wave's pieces of a tile are j = wave, wave + 8, wave + 16 (< 20) of [K pieces 0..9 | V pieces 0..9]: waves 0-3 issue
     // three, waves 4-7 two (the two waves of a SIMD five together)
     int kv_voff[3], kv_grp[3];
@@ -350,18 +372,9 @@ __global__ __launch_bounds__(512, 2) void pair_tail160_kernel(const h16* __restr
             }
             // the first V^T fragments: their LDS latency passes under the softmax
             const char* vb = sb + vl;
-            auto vread = [&](int j) {                   // fragment of PV MFMA j = 5 s2 + db
-                const char* pa = vb + (j / A_NDB) * 16 * A_ROWB + (j % A_NDB) * 64;
-                const h16x4 lo = h16_ds_read_tr16_b64(pa);
-                const h16x4 hi = h16_ds_read_tr16_b64(pa + 8 * A_ROWB);
-                h16x8 vf;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { vf[e] = lo[e]; vf[4 + e] = hi[e]; }
-                return vf;
-            };
             h16x8 vf[A_PRE + 1];
 #pragma unroll
-            for (int j = 0; j < A_PRE; ++j) vf[j] = vread(j);
+            for (int j = 0; j < A_PRE; ++j) vf[j] = vread160(vb, j);
             __builtin_amdgcn_sched_barrier(0);
             // ---- online softmax -------------------------------------------------------------------------------------------
             // The reference point m_run moves only when some row's maximum has grown by more than A_THR (log2 units): softmax is
@@ -403,7 +416,7 @@ __global__ __launch_bounds__(512, 2) void pair_tail160_kernel(const h16* __restr
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int j = 0; j < NPV; ++j) {
-                if (j + A_PRE < NPV) vf[(j + A_PRE) % (A_PRE + 1)] = vread(j + A_PRE);
+                if (j + A_PRE < NPV) vf[(j + A_PRE) % (A_PRE + 1)] = vread160(vb, j + A_PRE);
                 if (j == NPV - A_PRE) {
                     // Waves 0-3 issue their DMA pieces right BEHIND the barrier (below), waves 4-7 -- their SIMD partners -- just in
                     // FRONT of the next one (here: the pieces of the previous hand-over).  Same work, but the two waves of a SIMD
@@ -579,7 +592,6 @@ __global__ __launch_bounds__(64) void pair_finish160_kernel(const float* __restr
 __global__ __launch_bounds__(512, 2) void sdpa160_kernel(const h16* __restrict__ qg, const h16* __restrict__ kg, const h16* __restrict__ vg,
                                                          h16* __restrict__ og, const int ldq, const int ldk, const int ldo, const int B,
                                                          const int H, const float c) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, l31 = lane & 31;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const unsigned lbase = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem;
@@ -590,12 +602,6 @@ __global__ __launch_bounds__(512, 2) void sdpa160_kernel(const h16* __restrict__
     const int xcd = blockIdx.x & 7, wslot = blockIdx.x >> 3, g8 = (int)gridDim.x >> 6;
     const unsigned recs_q = (unsigned)((A_N - 1) * rbq + A_ROWB), recs_k = (unsigned)((A_N - 1) * rbk + A_ROWB);
 
-    auto piece_voff = [&](int pat, bool swizzle, int ln, int rb) {
-        const int f = 64 * pat + ln;
-        const int r = (f * 3277) >> 16, pos = f - r * 20;
-        const int ch = swizzle ? ((pos & ~3) | ((pos & 3) ^ (r >> 2))) : pos;
-        return r * rb + ch * 16;
-    };
     int kv_voff[3], kv_grp[3];
     unsigned kv_lds[3];
     bool kv_isv[3];
@@ -697,18 +703,9 @@ __global__ __launch_bounds__(512, 2) void sdpa160_kernel(const h16* __restrict__
                 __builtin_amdgcn_sched_barrier(0);
             }
             const char* vb = sb + vl;
-            auto vread = [&](int j) {
-                const char* pa = vb + (j / A_NDB) * 16 * A_ROWB + (j % A_NDB) * 64;
-                const h16x4 lo = h16_ds_read_tr16_b64(pa);
-                const h16x4 hi = h16_ds_read_tr16_b64(pa + 8 * A_ROWB);
-                h16x8 vf;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { vf[e] = lo[e]; vf[4 + e] = hi[e]; }
-                return vf;
-            };
             h16x8 vf[A_PRE + 1];
 #pragma unroll
-            for (int j = 0; j < A_PRE; ++j) vf[j] = vread(j);
+            for (int j = 0; j < A_PRE; ++j) vf[j] = vread160(vb, j);
             __builtin_amdgcn_sched_barrier(0);
             float tmax = max16_after_mfma(s);
             tmax = max_halves160(tmax);
@@ -741,7 +738,7 @@ __global__ __launch_bounds__(512, 2) void sdpa160_kernel(const h16* __restrict__
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int j = 0; j < NPV; ++j) {
-                if (j + A_PRE < NPV) vf[(j + A_PRE) % (A_PRE + 1)] = vread(j + A_PRE);
+                if (j + A_PRE < NPV) vf[(j + A_PRE) % (A_PRE + 1)] = vread160(vb, j + A_PRE);
                 if (j == NPV - A_PRE) {
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                     // Issued since the pieces of tile T + 1 (hand-over T - 3): two hand-overs' K / V pieces (3 or 2 each) and Q pieces
@@ -859,7 +856,6 @@ __global__ __launch_bounds__(512, 2) void matrix_cross160_kernel(const h16* __re
                                                                  const h16* __restrict__ vb, const h16* __restrict__ sbf, const int n_a,
                                                                  const int n_b, const int B, const int H, const float c, const int mse,
                                                                  float* __restrict__ part) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, l31 = lane & 31;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const unsigned lbase = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem;
@@ -870,12 +866,6 @@ __global__ __launch_bounds__(512, 2) void matrix_cross160_kernel(const h16* __re
     const int xcd = blockIdx.x & 7, wslot = blockIdx.x >> 3, g8 = (int)gridDim.x >> 6;
     const unsigned recs = (unsigned)((A_N - 1) * rowb + A_ROWB);
 
-    auto piece_voff = [&](int pat, bool swizzle, int ln, int rb) {
-        const int f = 64 * pat + ln;
-        const int r = (f * 3277) >> 16, pos = f - r * 20;
-        const int ch = swizzle ? ((pos & ~3) | ((pos & 3) ^ (r >> 2))) : pos;
-        return r * rb + ch * 16;
-    };
     int kv_voff[3], kv_grp[3];
     unsigned kv_lds[3];
     bool kv_isv[3];
@@ -1003,18 +993,9 @@ __global__ __launch_bounds__(512, 2) void matrix_cross160_kernel(const h16* __re
                     asm volatile("s_nop 4\n\tbuffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(ypk[i]) : "v"(po), "s"(dS), "s"(i * 1024) : "memory");
             }
             const char* vb = sb + vl;
-            auto vread = [&](int j) {
-                const char* pa = vb + (j / A_NDB) * 16 * A_ROWB + (j % A_NDB) * 64;
-                const h16x4 lo = h16_ds_read_tr16_b64(pa);
-                const h16x4 hi = h16_ds_read_tr16_b64(pa + 8 * A_ROWB);
-                h16x8 vf;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { vf[e] = lo[e]; vf[4 + e] = hi[e]; }
-                return vf;
-            };
             h16x8 vf[A_PRE + 1];
 #pragma unroll
-            for (int j = 0; j < A_PRE; ++j) vf[j] = vread(j);
+            for (int j = 0; j < A_PRE; ++j) vf[j] = vread160(vb, j);
             __builtin_amdgcn_sched_barrier(0);
             float tmax = max16_after_mfma(s);
             tmax = max_halves160(tmax);
@@ -1047,7 +1028,7 @@ __global__ __launch_bounds__(512, 2) void matrix_cross160_kernel(const h16* __re
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int j = 0; j < NPV; ++j) {
-                if (j + A_PRE < NPV) vf[(j + A_PRE) % (A_PRE + 1)] = vread(j + A_PRE);
+                if (j + A_PRE < NPV) vf[(j + A_PRE) % (A_PRE + 1)] = vread160(vb, j + A_PRE);
                 if (j == NPV - A_PRE) {
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                     // Issued since the pieces of tile T + 1 (hand-over T - 3): two hand-overs' K / V pieces (3 or 2 each), their Q pieces
@@ -1142,15 +1123,25 @@ __global__ __launch_bounds__(512, 2) void matrix_cross160_kernel(const h16* __re
     wait_vm<0>();
 }
 
-// workgroups the launch uses: one per CU, a multiple of 16 (two directions x eight XCDs), no more than the units there are
-int tail160_grid(int n_pairs, int B, int H) {
-    int g = cu_count() & ~15;
-    if (g < 16) g = 16;
-    if (g > 512) g = 512;
-    const long need = (((long)n_pairs * B * H + 7) / 8) * 16;      // couples per XCD x 16
-    if (need < g) g = (int)need;
-    return g;
+// Workgroups of a persistent launch over `units` units, in multiples of `quantum` (16 for the pair tail: two directions x eight
+// XCDs; 64 for the 8-step kernels: eight units on each of eight XCDs).  grid160_bound is the most it ever launches, whatever the
+// device: the units rounded up, at most 512.  grid160 is what it launches here: one workgroup per CU as well.
+long grid160_bound(long units, int quantum) {
+    const long need = (units + quantum - 1) / quantum * quantum;
+    return need < 512 ? need : 512;
 }
+int grid160(long units, int quantum) {
+    int g = cu_count() & ~(quantum - 1);
+    if (g < quantum) g = quantum;
+    const long bound = grid160_bound(units, quantum);
+    return bound < g ? (int)bound : g;
+}
+
+// the softmax constant c = log2(e) / sqrt(160): the kernels compute exp2(fma(s, c, -m c)) on raw logits
+float softmax_c160() { return (1.0f / sqrtf((float)A_D)) * 1.4426950408889634f; }
+
+// per-wave partials [item][dir][bh][wave] of pair_finish160_kernel, for n items (pairs or cells), 256-byte aligned
+size_t part160_bytes(long n, int B, int H) { return (((size_t)n * 2 * B * H * 8 * 4 * sizeof(float)) + 255) & ~(size_t)255; }
 
 }  // namespace
 
@@ -1171,38 +1162,29 @@ bool sdpa160_applies(const AttnArgs& a) {
 }
 
 int launch_sdpa160(const AttnArgs& a, hipStream_t s) {
-    int g = cu_count() & ~63;
-    if (g < 64) g = 64;
-    if (g > 512) g = 512;
-    const long need = (((long)a.B * a.H + 63) / 64) * 64;
-    if (need < g) g = (int)need;
+    const int g = grid160((long)a.B * a.H, 64);
     static DeviceOnce once;
     auto kern = sdpa160_kernel;
     CK_ONCE(once, kern, A_LDS);
-    const float c = (1.0f / sqrtf((float)A_D)) * 1.4426950408889634f;
     hipLaunchKernelGGL(kern, dim3(g), dim3(512), A_LDS, s, (const h16*)a.q, (const h16*)a.k, (const h16*)a.v, (h16*)a.out, a.ldq, a.ldk,
-                       a.ldo, a.B, a.H, c);
+                       a.ldo, a.B, a.H, softmax_c160());
     DSIM_HIP_CHECK(hipGetLastError());
     return DSIM_OK;
 }
 
-static size_t tail160_part_bytes(int n_pairs, int B, int H) { return (((size_t)n_pairs * 2 * B * H * 8 * 4 * sizeof(float)) + 255) & ~(size_t)255; }
-
 // partial sums + one 80 KB park slab per workgroup (the grid is bounded by 512 workgroups whatever the device, which keeps this
 // function free of device queries)
 size_t pair_score160_scratch_bytes(int n_pairs, int B, int H) {
-    const long need = (((long)n_pairs * B * H + 7) / 8) * 16;
-    return tail160_part_bytes(n_pairs, B, H) + (size_t)(need < 512 ? need : 512) * 8 * A_KTILE;
+    return part160_bytes(n_pairs, B, H) + (size_t)grid160_bound(2l * n_pairs * B * H, 16) * 8 * A_KTILE;
 }
 
 // ---- score matrix at the default tap: sdpa160_kernel writes every image's self output, self_lanes160_kernel reorders it lane-major,
 // matrix_cross160_kernel writes the cells' partials, pair_finish160_kernel folds them.
 // Workspace: [self A | self B | lane-major self A | lane-major self B | partials], each 256-byte aligned.
 static size_t mat160_self_bytes(int n, int B, int H) { return (((size_t)n * B * A_N * H * A_D * 2) + 255) & ~(size_t)255; }
-static size_t mat160_part_bytes(long n_cells, int B, int H) { return (((size_t)n_cells * 2 * B * H * 8 * 4 * sizeof(float)) + 255) & ~(size_t)255; }
 
 size_t score_matrix160_scratch_bytes(int n_a, int n_b, int B, int H) {
-    return 2 * (mat160_self_bytes(n_a, B, H) + mat160_self_bytes(n_b, B, H)) + mat160_part_bytes((long)n_a * n_b, B, H);
+    return 2 * (mat160_self_bytes(n_a, B, H) + mat160_self_bytes(n_b, B, H)) + part160_bytes((long)n_a * n_b, B, H);
 }
 
 int launch_score_matrix160(const void* qa, const void* ka, const void* va, int n_a, const void* qb, const void* kb, const void* vb, int n_b,
@@ -1230,17 +1212,12 @@ int launch_score_matrix160(const void* qa, const void* ka, const void* va, int n
         hipLaunchKernelGGL(self_lanes160_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, s, (const h16*)a.out,
                            (h16*)(set ? laneb : lanea), set ? n_b : n_a, B, H);
     }
-    int g = cu_count() & ~63;
-    if (g < 64) g = 64;
-    if (g > 512) g = 512;
-    const long need = (((long)n_a * n_b * B * H * 2 + 63) / 64) * 64;
-    if (need < g) g = (int)need;
+    const int g = grid160((long)n_a * n_b * B * H * 2, 64);
     static DeviceOnce once;
     auto kern = matrix_cross160_kernel;
     CK_ONCE(once, kern, A_LDS);
-    const float c = (1.0f / sqrtf((float)A_D)) * 1.4426950408889634f;
     hipLaunchKernelGGL(kern, dim3(g), dim3(512), A_LDS, s, (const h16*)qa, (const h16*)ka, (const h16*)va, (const h16*)lanea, (const h16*)qb,
-                       (const h16*)kb, (const h16*)vb, (const h16*)laneb, n_a, n_b, B, H, c, mse, part);
+                       (const h16*)kb, (const h16*)vb, (const h16*)laneb, n_a, n_b, B, H, softmax_c160(), mse, part);
     hipLaunchKernelGGL(pair_finish160_kernel, dim3(n_a * n_b), dim3(64), 0, s, (const float*)part, B * H * 8, mse,
                        (double)B * H * A_N * A_D, out, status);
     DSIM_HIP_CHECK(hipGetLastError());
@@ -1250,17 +1227,17 @@ int launch_score_matrix160(const void* qa, const void* ka, const void* va, int n
 int launch_pair_score160(const void* q, const void* k, const void* v, const int32_t* ia, const int32_t* ib, int n_pairs, int B,
                          int H, int mse, float* out, void* scratch, size_t scratch_bytes, hipStream_t s, int32_t* status) {
     if (scratch_bytes < pair_score160_scratch_bytes(n_pairs, B, H)) return DSIM_ERR_WORKSPACE;
-    const int grid = tail160_grid(n_pairs, B, H);
+    const int grid = grid160(2l * n_pairs * B * H, 16);
     static DeviceOnce once;
     auto kern = pair_tail160_kernel;
     CK_ONCE(once, kern, A_LDS);
-    const float c = (1.0f / sqrtf((float)A_D)) * 1.4426950408889634f;
+    const float c = softmax_c160();
 #ifdef DSIM_DEVTOOLS
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512), A_LDS, s, (const h16*)q, (const h16*)k, (const h16*)v, ia, ib, n_pairs, B, H, c,
-                       mse, (float*)scratch, (char*)scratch + tail160_part_bytes(n_pairs, B, H), g_tail160_dbg, g_tail160_exp);
+                       mse, (float*)scratch, (char*)scratch + part160_bytes(n_pairs, B, H), g_tail160_dbg, g_tail160_exp);
 #else
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512), A_LDS, s, (const h16*)q, (const h16*)k, (const h16*)v, ia, ib, n_pairs, B, H, c,
-                       mse, (float*)scratch, (char*)scratch + tail160_part_bytes(n_pairs, B, H));
+                       mse, (float*)scratch, (char*)scratch + part160_bytes(n_pairs, B, H));
 #endif
     hipLaunchKernelGGL(pair_finish160_kernel, dim3(n_pairs), dim3(64), 0, s, (const float*)scratch, B * H * 8, mse,
                        (double)B * H * A_N * A_D, out, status);

@@ -13,7 +13,10 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "diffsim_amd", "csrc", "attn160.hip")
+sys.path.insert(0, ROOT)
+from diffsim_amd.build import CSRC, FLAGS, HIPCC  # noqa: E402
+
+SRC = os.path.join(CSRC, "attn160.hip")
 
 
 def regs_of(tok):
@@ -27,11 +30,10 @@ def regs_of(tok):
 
 def audit(flags):
     with tempfile.TemporaryDirectory() as d:
-        cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "--cuda-device-only", "-S", SRC, "-o", os.path.join(d, "a.s")] + flags
+        cmd = [HIPCC] + FLAGS + ["--cuda-device-only", "-S", SRC, "-o", os.path.join(d, "a.s")] + flags
         subprocess.run(cmd, check=True, capture_output=True)
         lines = open(os.path.join(d, "a.s")).read().split("\n")
     text = "\n".join(lines)
-    m = re.search(r"\.vgpr_spill_count:\s*(\d+)", text[text.find("pair_tail160"):] if "pair_tail160" in text else text)
     spills = [int(x) for x in re.findall(r"\.vgpr_spill_count:\s*(\d+)", text)]
     scratch = [int(x) for x in re.findall(r"\.private_segment_fixed_size:\s*(\d+)", text)]
     bad = []
