@@ -47,6 +47,10 @@ def build_parser() -> argparse.ArgumentParser:
                         "query, named by its path under --query_path)")
     p.add_argument("--query_path", type=str, default=None, help="--dataset retrieval: folder of query images")
     p.add_argument("--topk", type=int, default=10, help="--dataset retrieval: gallery entries ranked per query")
+    p.add_argument("--save_maps", action="store_true",
+                   help="--dataset retrieval: beside each ranking .txt also write <name>.npz with the similarity maps of the query "
+                        "against its top-k gallery images (gallery, score (k,), local and contrib (k, 2, h, w): direction 0 on the "
+                        "query's token grid, 1 on the gallery image's)")
     p.add_argument("--experiments", type=int, default=2000, help="--dataset sref: sampled experiments (style_main.py:64)")
     p.add_argument("--model_path", type=str, default=None, help="diffusers-layout checkpoint directory (unet/, vae/, text_encoder/, tokenizer/)")
     p.add_argument("--dtype", type=str, choices=["bf16", "fp16", "fp32"], default="bf16",
@@ -73,7 +77,11 @@ def build_parser() -> argparse.ArgumentParser:
 
 
 def arg_parse(argv=None):
-    return build_parser().parse_args(argv)
+    p = build_parser()
+    args = p.parse_args(argv)
+    if args.save_maps and args.dataset != "retrieval":
+        p.error("--save_maps writes the maps of the retrieval rankings: it needs --dataset retrieval")
+    return args
 
 
 # ---- the CUTE triplet walk (cute_main.py:48-108) ------------------------------------------------------------------
@@ -257,13 +265,30 @@ def run_retrieval(args, scorer, layer) -> int:
         R.ranking_names(queries, args.query_path)               # two queries that would share a ranking file: refused before scoring
     except ValueError as e:
         raise SystemExit(str(e))
-    m, bad = R.score_path_matrix(scorer, queries, gallery, args.image_size, args.prompt, args.target_block, layer,
-                                 args.target_step, args.seed, args.similarity, return_status=True)
+    if not args.save_maps:
+        m, bad = R.score_path_matrix(scorer, queries, gallery, args.image_size, args.prompt, args.target_block, layer,
+                                     args.target_step, args.seed, args.similarity, return_status=True)
+    elif queries and gallery:
+        # the matrix's own latents and draws, kept for the maps of each query's top-k cells
+        latA, latB, nA, nB = R._path_latents(scorer, queries, gallery, args.image_size, args.seed)
+        m, bad = R.score_latent_matrix(scorer, latA, latB, nA, nB, args.prompt, args.target_block, layer, args.target_step,
+                                       args.similarity, return_status=True)
+    else:
+        m, bad = R.score_path_matrix(scorer, queries, gallery, args.image_size, args.prompt, args.target_block, layer,
+                                     args.target_step, args.seed, args.similarity, return_status=True)
     files = R.write_rankings(args.out_path, queries, gallery, m, args.topk, args.similarity, args.query_path)
     if bad:
         print(f"WARNING: {bad} score(s) are NaN/inf (ranked last)")
     print(f"Score matrix {tuple(m.shape)} ({len(queries)} queries x {len(gallery)} gallery images, {args.similarity}); "
           f"top-{min(args.topk, len(gallery))} rankings of {len(files)} queries written to {args.out_path}")
+    if args.save_maps and queries and gallery:
+        from . import maps as M
+        _vals, idx = R.topk(m, args.topk, args.similarity)
+        k = idx.shape[1]
+        mp = M.score_latent_pair_maps(scorer, latA.repeat_interleave(k, 0), latB[idx.reshape(-1).to(latB.device)], nA, nB,
+                                      args.prompt, args.target_block, layer, args.target_step, args.similarity)
+        mfiles = M.write_map_files(args.out_path, queries, gallery, idx, mp, args.query_path)
+        print(f"Similarity maps {mp.grid[0]}x{mp.grid[1]} of the top-{k} cells of {len(mfiles)} queries written to {args.out_path}")
     return 0
 
 

@@ -1629,6 +1629,192 @@ int launch_matrix_t(const void* qa, const void* ka, const void* va, int n_a, con
     }
 }
 
+// ---- similarity maps: the score tail kept per token ------------------------------------------------------------------------------
+// The score of direction a->b splits over query tokens: cos(O_ab, O_aa) = sum_i dot_i / (|O_ab| |O_aa|) and
+// mse = sum_i sqd_i / (B H N D), where dot_i / sqd_i sum over the CFG batch, the heads and d at token i.
+// pair_map_kernel is a TWIN of pair_tail_kernel: the same grid, the same attend twice on the same Q fragments, the same rounding
+// and products; only the epilogue differs (per-token partials instead of one partial per 128 rows).  It is a copy, not a template
+// flag on pair_tail_kernel, so that the tail's device code stays as it is: a fix to one goes into the other.
+// grid (ceil(N/128), B*H, n_pairs*2); partial layout [pair][dir][comp][bh][N] f32 (comp: dot | x2 | y2, or sqd | - | -)
+template <typename T, int D>
+__global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void pair_map_kernel(const T* __restrict__ qg, const T* __restrict__ kg,
+                                                        const T* __restrict__ vg, const int32_t* __restrict__ idx_a,
+                                                        const int32_t* __restrict__ idx_b, int B, int H, int N,
+                                                        float scale_log2, int mse, float* __restrict__ part) {
+    typedef ACfg<T, D> C;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, l31 = lane & 31;
+    const int bh = blockIdx.y, b = bh / H, h = bh - b * H;
+    const int pair = blockIdx.z >> 1, dir = blockIdx.z & 1;
+    const int ia = idx_a[pair], ib = idx_b[pair];
+    const int iq = dir ? ib : ia;        // query image (also the "self" keys/values)
+    const int ix = dir ? ia : ib;        // the other image ("cross" keys/values)
+    const int ld = H * D;
+    const size_t img = (size_t)B * N * ld;
+    const int q = blockIdx.x * 128 + wave * 32 + l31;
+    const int qc = q < N ? q : N - 1;
+    const size_t boff = (size_t)b * N * ld + h * D;
+    QFrags<T, D> qf;
+    load_q<T, D>(qf, qg + iq * img + boff + (size_t)qc * ld, half, scale_log2);
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+    if constexpr (sizeof(T) == 2) {
+        typedef float f32x2 __attribute__((ext_vector_type(2)));
+        h16x2 osp[C::NDB][8];           // the self-attention's output, rounded to the compute dtype, two values per register
+        {
+            OAcc<T, D> osa;
+            attend<T, D>(qf, kg + iq * img + boff, vg + iq * img + boff, ld, N, smem, osa);
+#pragma unroll
+            for (int db = 0; db < C::NDB; ++db)
+#pragma unroll
+                for (int r = 0; r < 16; r += 2) {
+                    osp[db][r >> 1] = __builtin_convertvector((f32x2){osa.b[db][r], osa.b[db][r + 1]}, h16x2);
+                    asm volatile("" : "+v"(osp[db][r >> 1]));          // (pinned: the f32 accumulators die here, before the second attention)
+                }
+        }
+        OAcc<T, D> oxa;
+        attend<T, D>(qf, kg + ix * img + boff, vg + ix * img + boff, ld, N, smem, oxa);
+        if (q < N) {
+#pragma unroll
+            for (int db = 0; db < C::NDB; ++db)
+#pragma unroll
+                for (int r = 0; r < 16; r += 2) {
+                    const h16x2 xp = __builtin_convertvector((f32x2){oxa.b[db][r], oxa.b[db][r + 1]}, h16x2);
+#pragma unroll
+                    for (int e = 0; e < 2; ++e) {
+                        const int rr = r + e, d = db * 32 + (rr & 3) + 8 * (rr >> 2) + 4 * half;
+                        if (d < D) {
+                            const float x = (float)xp[e], y = (float)osp[db][r >> 1][e];
+                            if (mse) { const float df = x - y; s0 = fmaf(df, df, s0); }
+                            else { s0 = fmaf(x, y, s0); s1 = fmaf(x, x, s1); s2 = fmaf(y, y, s2); }
+                        }
+                    }
+                }
+        }
+    } else {
+    OAcc<T, D> osa, oxa;
+    attend<T, D>(qf, kg + iq * img + boff, vg + iq * img + boff, ld, N, smem, osa);
+    attend<T, D>(qf, kg + ix * img + boff, vg + ix * img + boff, ld, N, smem, oxa);
+    auto& os = osa.b;
+    auto& ox = oxa.b;
+    if (q < N) {
+#pragma unroll
+        for (int db = 0; db < C::NDB; ++db)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int d = db * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+                if (d < D) {
+                    const float x = ox[db][r], y = os[db][r];
+                    if (mse) { const float df = x - y; s0 = fmaf(df, df, s0); }
+                    else { s0 = fmaf(x, y, s0); s1 = fmaf(x, x, s1); s2 = fmaf(y, y, s2); }
+                }
+            }
+    }
+    }
+    // a row's d values are split between the two lane halves: fold them, then the first half stores the row (128 B per wave and
+    // component, no atomics)
+    s0 += __shfl_xor(s0, 32);
+    s1 += __shfl_xor(s1, 32);
+    s2 += __shfl_xor(s2, 32);
+    if (half == 0 && q < N) {
+        const size_t plane = (size_t)gridDim.y * N;
+        float* o = part + ((size_t)pair * 2 + dir) * 3 * plane + (size_t)bh * N + q;
+        o[0] = s0;
+        if (!mse) { o[plane] = s1; o[2 * plane] = s2; }
+    }
+}
+
+// one workgroup per pair, both directions: per token, a fixed-order f64 fold of the B*H partials; over tokens, per-thread strided
+// sums and a fixed-order tree.  local: the token's own cosine (|.| of the token's vectors) or mean squared difference; contrib: its
+// share of the direction's score, so that 0.5 (sum contrib[0] + sum contrib[1]) is the pair's score (F.cosine_similarity eps =
+// 1e-8, as pair_finish_kernel)
+// (NT threads: a template, so that it is emitted after the kernels above and leaves their code objects as they were)
+constexpr int MAP_FINISH_THREADS = 256;
+template <int NT>
+__global__ __launch_bounds__(NT) void pair_map_finish_kernel(const float* __restrict__ part, int BH, int N, int D,
+                                                                             int mse, float* __restrict__ score, float* __restrict__ local,
+                                                                             float* __restrict__ contrib, int32_t* __restrict__ status) {
+    __shared__ double red[3][NT];
+    const int p = blockIdx.x, t = threadIdx.x;
+    const size_t plane = (size_t)BH * N;
+    double res = 0.0;
+    for (int dir = 0; dir < 2; ++dir) {
+        const float* pd = part + ((size_t)p * 2 + dir) * 3 * plane;
+        float* lo = local ? local + ((size_t)p * 2 + dir) * N : nullptr;
+        float* co = contrib ? contrib + ((size_t)p * 2 + dir) * N : nullptr;
+        auto fold = [&](int comp, int i) {
+            double a = 0.0;
+            for (int j = 0; j < BH; ++j) a += pd[comp * plane + (size_t)j * N + i];
+            return a;
+        };
+        // pass 1: local, and the direction's squared norms (cosine)
+        double x2t = 0.0, y2t = 0.0;
+        for (int i = t; i < N; i += NT) {
+            const double a = fold(0, i);
+            if (mse) {
+                if (lo) lo[i] = (float)(a / ((double)BH * D));
+            } else {
+                const double x2 = fold(1, i), y2 = fold(2, i);
+                x2t += x2; y2t += y2;
+                if (lo) lo[i] = (float)(a / (fmax(sqrt(x2), 1e-8) * fmax(sqrt(y2), 1e-8)));
+            }
+        }
+        red[1][t] = x2t; red[2][t] = y2t;
+        __syncthreads();
+        for (int s = NT / 2; s > 0; s >>= 1) {
+            if (t < s) { red[1][t] += red[1][t + s]; red[2][t] += red[2][t + s]; }
+            __syncthreads();
+        }
+        const double den = mse ? (double)BH * N * D : fmax(sqrt(red[1][0]), 1e-8) * fmax(sqrt(red[2][0]), 1e-8);
+        // pass 2: contrib (the same fold again: the per-token sums are not kept), and the direction's total
+        double ct = 0.0;
+        for (int i = t; i < N; i += NT) {
+            const double c = fold(0, i) / den;
+            ct += c;
+            if (co) co[i] = (float)c;
+        }
+        __syncthreads();                 // (every thread has read red[1..2][0])
+        red[0][t] = ct;
+        __syncthreads();
+        for (int s = NT / 2; s > 0; s >>= 1) {
+            if (t < s) red[0][t] += red[0][t + s];
+            __syncthreads();
+        }
+        res += red[0][0];
+        __syncthreads();
+    }
+    if (t == 0) {
+        const float sc = (float)(res * 0.5);
+        score[p] = sc;
+        if (status) status[p] = (sc - sc == 0.0f) ? 0 : 1;
+    }
+}
+
+template <typename T, int D>
+int launch_maps_d(const void* q, const void* k, const void* v, const int32_t* ia, const int32_t* ib, int n_pairs, int B, int H, int N,
+                  int mse, float* score, float* local, float* contrib, int32_t* status, void* scratch, hipStream_t s) {
+    typedef ACfg<T, D> C;
+    static DeviceOnce once;
+    auto kern = pair_map_kernel<T, D>;
+    CK_ONCE(once, kern, C::LDS);
+    hipLaunchKernelGGL(kern, dim3((N + 127) / 128, B * H, n_pairs * 2), dim3(256), C::LDS, s, (const T*)q, (const T*)k,
+                       (const T*)v, ia, ib, B, H, N, scale_log2_of(D), mse, (float*)scratch);
+    hipLaunchKernelGGL(pair_map_finish_kernel<MAP_FINISH_THREADS>, dim3(n_pairs), dim3(MAP_FINISH_THREADS), 0, s, (const float*)scratch, B * H, N, D, mse,
+                       score, local, contrib, status);
+    DSIM_HIP_CHECK(hipGetLastError());
+    return DSIM_OK;
+}
+
+template <typename T>
+int launch_maps_t(const void* q, const void* k, const void* v, const int32_t* ia, const int32_t* ib, int n_pairs, int B, int H, int N,
+                  int D, int mse, float* score, float* local, float* contrib, int32_t* status, void* scratch, hipStream_t s) {
+    switch (D) {
+#define X(d) case d: return launch_maps_d<T, d>(q, k, v, ia, ib, n_pairs, B, H, N, mse, score, local, contrib, status, scratch, s);
+        DSIM_FOR_EACH_D(X)
+#undef X
+        default: return DSIM_ERR_INVALID;
+    }
+}
+
 }  // namespace
 
 #ifdef DSIM_DEVTOOLS
@@ -1724,6 +1910,34 @@ int launch_score_matrix(const void* qa, const void* ka, const void* va, int n_a,
 #ifdef DSIM_HAS_F16_TWINS
     if (dtype == DSIM_F16)
         return launch_score_matrix_f16(qa, ka, va, n_a, qb, kb, vb, n_b, B, H, N, D, dtype, similarity, out, status, scratch, scratch_bytes, s);
+#endif
+#endif
+    return DSIM_ERR_INVALID;
+}
+
+
+size_t pair_score_maps_scratch_bytes(int n_pairs, int B, int H, int N) {
+    if (n_pairs < 1 || B < 1 || H < 1 || N < 1) return 0;
+    return (size_t)n_pairs * 2 * 3 * B * H * N * sizeof(float);
+}
+
+// per-token maps of the score tail: pair_map_kernel at every shape and dtype (the default tap's persistent kernel keeps no
+// per-token sums)
+int launch_pair_score_maps(const void* q, const void* k, const void* v, const int32_t* ia, const int32_t* ib, int n_pairs, int B, int H,
+                           int N, int D, int dtype, int similarity, float* score, float* local, float* contrib, int32_t* status,
+                           void* scratch, size_t scratch_bytes, hipStream_t s) {
+    if (n_pairs <= 0 || B < 1 || H < 1 || D % 8 || N < 1 || (similarity != 0 && similarity != 1)) return DSIM_ERR_INVALID;
+    if (n_pairs * 2 > 65535 || B * H > 65535) return DSIM_ERR_INVALID;
+    if (scratch_bytes < pair_score_maps_scratch_bytes(n_pairs, B, H, N)) return DSIM_ERR_WORKSPACE;
+    if (dtype == DSIM_H16)
+        return launch_maps_t<h16>(q, k, v, ia, ib, n_pairs, B, H, N, D, similarity, score, local, contrib, status, scratch, s);
+#ifndef DSIM_H16_IS_F16
+    if (dtype == DSIM_F32)
+        return launch_maps_t<float>(q, k, v, ia, ib, n_pairs, B, H, N, D, similarity, score, local, contrib, status, scratch, s);
+#ifdef DSIM_HAS_F16_TWINS
+    if (dtype == DSIM_F16)
+        return launch_pair_score_maps_f16(q, k, v, ia, ib, n_pairs, B, H, N, D, dtype, similarity, score, local, contrib, status, scratch,
+                                          scratch_bytes, s);
 #endif
 #endif
     return DSIM_ERR_INVALID;

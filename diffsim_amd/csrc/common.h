@@ -40,6 +40,8 @@
 #define launch_score_matrix launch_score_matrix_f16
 #define score_matrix160_scratch_bytes score_matrix160_scratch_bytes_f16
 #define launch_score_matrix160 launch_score_matrix160_f16
+#define pair_score_maps_scratch_bytes pair_score_maps_scratch_bytes_f16
+#define launch_pair_score_maps launch_pair_score_maps_f16
 #define ff_stream_bytes ff_stream_bytes_f16
 #define pack_ff_stream pack_ff_stream_f16
 #define launch_ff_fused launch_ff_fused_f16
@@ -296,6 +298,12 @@ bool pair_score160_applies(int N, int D, int dtype);
 size_t pair_score160_scratch_bytes(int n_pairs, int B, int H);
 int launch_pair_score160(const void* q, const void* k, const void* v, const int32_t* idx_a, const int32_t* idx_b, int n_pairs, int B,
                          int H, int mse, float* out, void* scratch, size_t scratch_bytes, hipStream_t s, int32_t* status);
+// similarity maps: the score tail kept per query token (pair_map_kernel, any shape and dtype) -- attention.hip
+//   score [n_pairs]; local, contrib (each may be NULL) [n_pairs][2][N]; status (may be NULL) [n_pairs]
+size_t pair_score_maps_scratch_bytes(int n_pairs, int B, int H, int N);
+int launch_pair_score_maps(const void* q, const void* k, const void* v, const int32_t* idx_a, const int32_t* idx_b, int n_pairs, int B,
+                           int H, int N, int D, int dtype, int similarity, float* score, float* local, float* contrib, int32_t* status,
+                           void* scratch, size_t scratch_bytes, hipStream_t s);
 // the same core as a plain SDPA (256 queries = 256 keys, head dim 160, 16-bit types): the U-Net's 16 x 16-level self-attentions
 bool sdpa160_applies(const AttnArgs& a);
 int launch_sdpa160(const AttnArgs& a, hipStream_t s);
@@ -350,6 +358,9 @@ size_t score_matrix_scratch_bytes_f16(int n_a, int n_b, int B, int H, int N, int
 int launch_score_matrix_f16(const void* qa, const void* ka, const void* va, int n_a, const void* qb, const void* kb, const void* vb, int n_b,
                             int B, int H, int N, int D, int dtype, int similarity, float* out, int32_t* status, void* scratch,
                             size_t scratch_bytes, hipStream_t s);
+int launch_pair_score_maps_f16(const void* q, const void* k, const void* v, const int32_t* idx_a, const int32_t* idx_b, int n_pairs, int B,
+                               int H, int N, int D, int dtype, int similarity, float* score, float* local, float* contrib, int32_t* status,
+                               void* scratch, size_t scratch_bytes, hipStream_t s);
 #endif
 
 // Per-device once-flags for hipFuncSetAttribute(MaxDynamicSharedMemorySize) and the CU count: the attribute is a

@@ -854,6 +854,23 @@ int dsim_score_matrix(const void* qa, const void* ka, const void* va, int n_a, c
                                workspace_bytes - lost, (hipStream_t)stream);
 }
 
+size_t dsim_pair_score_maps_workspace_bytes(int n_pairs, int B, int H, int N, int D) {
+    const size_t b = pair_score_maps_scratch_bytes(n_pairs, B, H, N);
+    return b && D >= 1 ? b + 256 : 0;
+}
+
+int dsim_pair_score_maps(const void* q, const void* k, const void* v, const int32_t* idx_a, const int32_t* idx_b, int n_pairs, int B,
+                         int H, int N, int D, int dtype, int similarity, float* score, float* local, float* contrib, int32_t* status,
+                         void* workspace, size_t workspace_bytes, void* stream) {
+    if (!q || !k || !v || !idx_a || !idx_b || !score || !workspace) return DSIM_ERR_INVALID;
+    if (similarity != 0 && similarity != 1) return DSIM_ERR_INVALID;
+    const uintptr_t b0 = ((uintptr_t)workspace + 255) & ~(uintptr_t)255;
+    const size_t lost = b0 - (uintptr_t)workspace;
+    if (workspace_bytes < lost) return DSIM_ERR_WORKSPACE;
+    return launch_pair_score_maps(q, k, v, idx_a, idx_b, n_pairs, B, H, N, D, dtype, similarity, score, local, contrib, status,
+                                  (void*)b0, workspace_bytes - lost, (hipStream_t)stream);
+}
+
 // ---- single-operator entry points (tests / micro-benchmarks; these allocate and synchronise) ----
 namespace {
 struct Tmp {

@@ -250,6 +250,12 @@ class DiffSim:
         if ip_adapter:
             raise NotImplementedError("IP-Adapter mode is out of scope")
         target_layer = _norm_layer(target_layer)
+        latentsA, latentsB, noiseA, noiseB = self._path_pair_latents(image_A, image_B, img_size, seed)
+        return self.score_latent_pairs(latentsA, latentsB, noiseA, noiseB, prompt, target_block, target_layer, target_step,
+                                       similarity)
+
+    def _path_pair_latents(self, image_A, image_B, img_size, seed):
+        """(latentsA, latentsB, noiseA, noiseB) as f32 tensors: what one reference call draws for the two image files."""
         # decode + Lanczos resize of the two images on two host threads (PIL releases the GIL); same tensors as serially
         fa = self._pool.submit(lambda: process_image(load_image(image_A), img_size))
         tensor_B = process_image(load_image(image_B), img_size)
@@ -261,8 +267,7 @@ class DiffSim:
         noiseB = torch.randn(latentsB.shape, generator=generator, dtype=self.noise_dtype)
         if self.noise_dtype == torch.float16:      # the fp16 pipeline holds its latents in fp16
             latentsA, latentsB = latentsA.to(torch.float16), latentsB.to(torch.float16)
-        return self.score_latent_pairs(latentsA.float(), latentsB.float(), noiseA.float(), noiseB.float(), prompt,
-                                       target_block, target_layer, target_step, similarity)
+        return latentsA.float(), latentsB.float(), noiseA.float(), noiseB.float()
 
     @torch.no_grad()
     def score_pairs(self, pairs: Sequence[Tuple[str, str]], img_size, prompt, target_block, target_layer, target_step,
@@ -334,3 +339,21 @@ class DiffSim:
         from .retrieval import score_latent_matrix
         return score_latent_matrix(self, latA, latB, noiseA, noiseB, prompt, target_block, _norm_layer(target_layer),
                                    target_step, similarity, batch)
+
+    # ------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def similarity_maps(self, image_A, image_B, img_size, prompt, target_block, target_layer, target_step, seed="2333",
+                        similarity="cosine"):
+        """:meth:`diffsim`'s score of one image pair with its per-token terms on both images' grids: a
+        :class:`~diffsim_amd.maps.SimilarityMaps` of one pair (direction 0 on image_A's grid, 1 on image_B's)."""
+        latentsA, latentsB, noiseA, noiseB = self._path_pair_latents(image_A, image_B, img_size, seed)
+        return self.score_latent_pair_maps(latentsA, latentsB, noiseA, noiseB, prompt, target_block, target_layer, target_step,
+                                           similarity)
+
+    @torch.no_grad()
+    def score_latent_pair_maps(self, latA, latB, noiseA, noiseB, prompt, target_block="up_blocks", target_layer=0,
+                               target_step=600, similarity="cosine", batch_pairs: Optional[int] = None):
+        """Maps of the pairs of :meth:`score_latent_pairs` (maps.score_latent_pair_maps)."""
+        from .maps import score_latent_pair_maps
+        return score_latent_pair_maps(self, latA, latB, noiseA, noiseB, prompt, target_block, _norm_layer(target_layer),
+                                      target_step, similarity, batch_pairs)

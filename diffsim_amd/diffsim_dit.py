@@ -75,6 +75,10 @@ class diffsim_DiT:
     def diffsim_score(self, image_A, image_B, img_size, prompt, target_block, target_layer, target_step, similarity, seed):
         """Same contract as the reference's ``diffsim_DiT.diffsim_score`` (diffsim/diffsim_dit.py:74-142)."""
         layer = target_layer[0]
+        return self.score_latent_pairs(*self._path_pair_latents(image_A, image_B, img_size, seed), layer, target_step, similarity)
+
+    def _path_pair_latents(self, image_A, image_B, img_size, seed):
+        """(latentsA, latentsB, noiseA, noiseB) as f32 tensors: what one reference call draws for the two image files."""
         tA, tB = process_image(load_image(image_A), img_size), process_image(load_image(image_B), img_size)
         generator = get_generator(seed, "cpu")
         latentsA = self.prepare_image_latents(tA, generator)
@@ -82,5 +86,18 @@ class diffsim_DiT:
         # randn_tensor(dtype=latents.dtype): the reference draws the noise in fp16 (diffsim_dit.py:64-66)
         noiseA = torch.randn(latentsA.shape, generator=generator, dtype=latentsA.dtype)
         noiseB = torch.randn(latentsB.shape, generator=generator, dtype=latentsB.dtype)
-        return self.score_latent_pairs(latentsA.float(), latentsB.float(), noiseA.float(), noiseB.float(), layer, target_step,
-                                       similarity)
+        return latentsA.float(), latentsB.float(), noiseA.float(), noiseB.float()
+
+    @torch.no_grad()
+    def similarity_maps(self, image_A, image_B, img_size, prompt, target_block, target_layer, target_step, similarity, seed):
+        """:meth:`diffsim_score` with the per-token terms on both images' grids (a maps.SimilarityMaps of one pair)."""
+        return self.score_latent_pair_maps(*self._path_pair_latents(image_A, image_B, img_size, seed), target_layer[0],
+                                           target_step, similarity)
+
+    @torch.no_grad()
+    def score_latent_pair_maps(self, latA, latB, noiseA, noiseB, target_layer: int, target_step: int, similarity="cosine",
+                               batch_pairs: int = 32):
+        """Maps of the pairs of :meth:`score_latent_pairs` (maps.score_latent_pair_maps)."""
+        from .maps import score_latent_pair_maps
+        return score_latent_pair_maps(self, latA, latB, noiseA, noiseB, None, "none", [int(target_layer)], target_step, similarity,
+                                      batch_pairs)

@@ -111,6 +111,12 @@ class diffsim_xl:
     @torch.no_grad()
     def diffsim_score(self, image_A, image_B, img_size, prompt, target_block, target_layer, target_step, similarity, seed):
         """Same contract as the reference's ``diffsim_xl.diffsim_score`` (diffsim/diffsim_xl.py:65-155)."""
+        latentsA, latentsB, noiseA, noiseB, ctx, pooled = self._path_pair_inputs(image_A, image_B, img_size, prompt, seed)
+        return self.score_latent_pairs(latentsA, latentsB, noiseA, noiseB, ctx, pooled, target_block, target_layer, target_step,
+                                       similarity)
+
+    def _path_pair_inputs(self, image_A, image_B, img_size, prompt, seed):
+        """(latentsA, latentsB, noiseA, noiseB, ctx, pooled): what one reference call draws and encodes."""
         if self._encode_prompt is None:
             raise RuntimeError("no text encoder plugged in: pass encode_prompt=...")
         tensor_A, tensor_B = process_image(load_image(image_A), img_size), process_image(load_image(image_B), img_size)
@@ -120,5 +126,19 @@ class diffsim_xl:
         noiseA = torch.randn(latentsA.shape, generator=generator, dtype=self.noise_dtype).float()
         noiseB = torch.randn(latentsB.shape, generator=generator, dtype=self.noise_dtype).float()
         ctx, pooled = self._encode_prompt(prompt)
-        return self.score_latent_pairs(latentsA.float(), latentsB.float(), noiseA, noiseB, ctx, pooled, target_block,
-                                       target_layer, target_step, similarity)
+        return latentsA.float(), latentsB.float(), noiseA, noiseB, ctx, pooled
+
+    @torch.no_grad()
+    def similarity_maps(self, image_A, image_B, img_size, prompt, target_block, target_layer, target_step, similarity, seed):
+        """:meth:`diffsim_score` with the per-token terms on both images' grids (a maps.SimilarityMaps of one pair)."""
+        latentsA, latentsB, noiseA, noiseB, ctx, pooled = self._path_pair_inputs(image_A, image_B, img_size, prompt, seed)
+        return self.score_latent_pair_maps(latentsA, latentsB, noiseA, noiseB, ctx, pooled, target_block, target_layer,
+                                           target_step, similarity)
+
+    @torch.no_grad()
+    def score_latent_pair_maps(self, latA, latB, noiseA, noiseB, ctx, pooled, target_block, target_layer, target_step,
+                               similarity="cosine", batch_pairs: int = 8):
+        """Maps of the pairs of :meth:`score_latent_pairs` (maps.score_latent_pair_maps)."""
+        from .maps import score_latent_pair_maps
+        return score_latent_pair_maps(self, latA, latB, noiseA, noiseB, (ctx, pooled), target_block, target_layer, target_step,
+                                      similarity, batch_pairs)

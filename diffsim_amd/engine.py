@@ -348,6 +348,47 @@ def pair_score(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, idx_a: torch.T
     return out
 
 
+def pair_score_maps(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, idx_a: torch.Tensor, idx_b: torch.Tensor,
+                    heads: int, similarity: str = "cosine", return_status: bool = False):
+    """The score tail kept per query token (dsim_pair_score_maps).  q,k,v: [n_feat][B][N][H*D]; idx: int32 cuda [n_pairs].
+    Returns f32 device tensors (score (n,), local (n, 2, N), contrib (n, 2, N)): direction 0 on image idx_a[p]'s tokens,
+    direction 1 on idx_b[p]'s; local is a token's own cosine (or mean squared difference), contrib its term of the score:
+    score = 0.5 * contrib.sum((1, 2)).  return_status: also an int32 (n,) tensor, 1 where the score is NaN / infinite."""
+    L = _lib.lib()
+    _require_cuda(q, k, v, idx_a, idx_b)
+    if similarity not in ("cosine", "mse"):
+        raise ValueError(similarity)
+    if q.dtype not in (torch.float32, torch.bfloat16, torch.float16) or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise _lib.DsimError("q,k,v must share dtype float32, bfloat16 or float16")
+    if idx_a.dtype != torch.int32 or idx_b.dtype != torch.int32:
+        raise _lib.DsimError("pair indices must be int32")
+    if q.ndim != 4 or k.shape != q.shape or v.shape != q.shape:
+        raise _lib.DsimError("q,k,v must be [n_feat][B][N][H*D] of one shape")
+    if not all(t.is_contiguous() for t in (q, k, v, idx_a, idx_b)):
+        raise _lib.DsimError("features and indices must be contiguous")
+    nf, B, N, HD = q.shape
+    D = HD // heads
+    if D * heads != HD:
+        raise _lib.DsimError(f"H*D = {HD} is not a multiple of heads = {heads}")
+    n_pairs = idx_a.numel()
+    if idx_b.numel() != n_pairs:
+        raise _lib.DsimError("idx_a and idx_b must have the same length")
+    score = torch.empty(n_pairs, dtype=torch.float32, device=q.device)
+    local = torch.empty((n_pairs, 2, N), dtype=torch.float32, device=q.device)
+    contrib = torch.empty((n_pairs, 2, N), dtype=torch.float32, device=q.device)
+    status = torch.empty(n_pairs, dtype=torch.int32, device=q.device) if return_status else None
+    with torch.cuda.device(q.device):
+        wsb = int(L.dsim_pair_score_maps_workspace_bytes(n_pairs, B, heads, N, D))
+        if wsb == 0:
+            raise _lib.DsimError(f"no similarity maps for n_pairs={n_pairs} B={B} H={heads} N={N} D={D}")
+        ws = torch.empty(wsb, dtype=torch.uint8, device=q.device)
+        _lib.check(L.dsim_pair_score_maps(q.data_ptr(), k.data_ptr(), v.data_ptr(), idx_a.data_ptr(), idx_b.data_ptr(), n_pairs, B,
+                                          heads, N, D, _TORCH2DSIM[q.dtype], 0 if similarity == "cosine" else 1, score.data_ptr(),
+                                          local.data_ptr(), contrib.data_ptr(), _ptr(status), ws.data_ptr(), wsb, _stream_ptr()),
+                   "dsim_pair_score_maps")
+    return (score, local, contrib, status) if return_status else (score, local, contrib)
+
+
 def score_matrix_workspace_bytes(n_a: int, n_b: int, B: int, heads: int, N: int, D: int, dtype: torch.dtype) -> int:
     return int(_lib.lib().dsim_score_matrix_workspace_bytes(n_a, n_b, B, heads, N, D, _TORCH2DSIM[dtype]))
 

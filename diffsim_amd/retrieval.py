@@ -91,11 +91,18 @@ def score_path_matrix(scorer, paths_a: Sequence[str], paths_b: Sequence[str], im
     """The (len(paths_a), len(paths_b)) matrix of ``diffsim(paths_a[i], paths_b[j], ...)`` scores: the query images are
     encoded with the reseeded generator's slot-A VAE draw and noise, the gallery images with the slot-B ones (the adapter's
     draw order: VAE sample A, VAE sample B, noise A, noise B).  Through the scorer's HIP VAE fast path where it has one."""
-    ad = _Adapter(scorer)
-    dev = scorer.device
     if not paths_a or not paths_b:
-        empty = torch.empty((len(paths_a), len(paths_b)), dtype=torch.float32, device=dev)
+        empty = torch.empty((len(paths_a), len(paths_b)), dtype=torch.float32, device=scorer.device)
         return (empty, 0) if return_status else empty
+    latA, latB, nA, nB = _path_latents(scorer, paths_a, paths_b, img_size, seed)
+    return score_latent_matrix(scorer, latA, latB, nA, nB, prompt, target_block, target_layer, target_step, similarity, batch,
+                               return_status)
+
+
+def _path_latents(scorer, paths_a: Sequence[str], paths_b: Sequence[str], img_size, seed=2333):
+    """(latA, latB, noiseA, noiseB) of score_path_matrix: the queries' latents with the slot-A draws, the gallery's with the
+    slot-B ones, and the two noise tensors."""
+    ad = _Adapter(scorer)
     if ad.fast:
         vae = ad.vae
         sf = vae.config.scaling_factor
@@ -139,8 +146,7 @@ def score_path_matrix(scorer, paths_a: Sequence[str], paths_b: Sequence[str], im
                 nA = torch.randn(lb[-1].shape, generator=g, dtype=ad.noise_draw).float()
                 nB = torch.randn(lb[-1].shape, generator=g, dtype=ad.noise_draw).float()
         latA, latB = torch.cat(la), torch.cat(lb)
-    return score_latent_matrix(scorer, latA, latB, nA, nB, prompt, target_block, target_layer, target_step, similarity, batch,
-                               return_status)
+    return latA, latB, nA, nB
 
 
 def topk(matrix: torch.Tensor, k: int, similarity: str = "cosine"):

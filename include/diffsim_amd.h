@@ -208,6 +208,24 @@ int    dsim_score_matrix(const void* qa, const void* ka, const void* va, int n_a
                          float* out, int32_t* status, void* workspace, size_t workspace_bytes,
                          void* stream);
 
+/* ---- similarity maps: the score tail kept per query token ----------------------------------------------
+ * The score of direction a->b breaks down over a's query tokens: cos(O_ab, O_aa) = sum_i dot_i / (|O_ab| |O_aa|), and
+ * mse = sum_i sqd_i / (B H N D), where dot_i / sqd_i sum over the CFG batch, the heads and d at token i.
+ *   q,k,v, idx_a, idx_b, similarity : as dsim_pair_score
+ *   score       : device f32 [n_pairs], the pair's score (within float rounding of dsim_pair_score's)
+ *   local       : NULL, or device f32 [n_pairs][2][N]: the token's own cosine of its O_ab and O_aa vectors (over B, H, D),
+ *                 or their mean squared difference
+ *   contrib     : NULL, or device f32 [n_pairs][2][N]: the token's term of the direction's score, so that
+ *                 score[p] = 0.5 (sum_i contrib[p][0][i] + sum_i contrib[p][1][i])
+ *   status      : NULL, or device int32 [n_pairs] (as dsim_pair_score_status)
+ * Row [p][0] lies on image idx_a[p]'s token grid, row [p][1] on idx_b[p]'s.  Deterministic, and a pair's values do not
+ * depend on the other pairs of the call.  dsim_pair_score_maps_workspace_bytes returns 0 for an invalid shape. */
+size_t dsim_pair_score_maps_workspace_bytes(int n_pairs, int B, int H, int N, int D);
+int    dsim_pair_score_maps(const void* q, const void* k, const void* v, const int32_t* idx_a,
+                            const int32_t* idx_b, int n_pairs, int B, int H, int N, int D, int dtype,
+                            int similarity, float* score, float* local, float* contrib, int32_t* status,
+                            void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- VAE encoder: replaces `pipe.vae.encode(image)` in
  *      DiffSim.prepare_image_latents (diffsim/diffsim.py:92-96).  Sampling
  *      z = mean + exp(0.5*clamp(logvar,-30,20))*eps and the 0.18215 scaling stay with the caller,
