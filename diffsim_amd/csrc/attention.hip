@@ -29,6 +29,8 @@
 // h16 path: v_mfma_f32_32x32x16_bf16; fp32 parity path: v_mfma_f32_32x32x2_f32 (exact f32).
 #include "common.h"
 
+#include <type_traits>
+
 namespace dsim {
 namespace {
 
@@ -1180,20 +1182,82 @@ __global__ __launch_bounds__(256, 2) void attn_short_kernel(const AttnArgs p, co
 }
 
 // ---- fused score tail ----------------------------------------------------------------------
-// grid (ceil(N/128), B*H, n_pairs*2); partial layout [pair][dir][bh][qtile][4] f32
 // 16-bit modes (round 5): both SDPA outputs are rounded to the compute dtype before the products -- torch's SDPA returns
 // tensors of the pipeline dtype and the reference's cosine / mse consume those (diffsim.py:177-190); the products and sums stay
 // f32 per workgroup and f64 across them.  The self-attention's output then waits for the cross-attention as packed 16-bit
 // pairs (40 registers at d = 160 instead of 80), which brings d = 160 from 426 registers (one workgroup per CU) under 256: two
 // workgroups per CU.  The f32 parity mode keeps both outputs in f32.
-template <typename T, int D>
-__global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void pair_tail_kernel(const T* __restrict__ qg, const T* __restrict__ kg,
-                                                        const T* __restrict__ vg, const int32_t* __restrict__ idx_a,
-                                                        const int32_t* __restrict__ idx_b, int B, int H, int N,
-                                                        float scale_log2, int mse, float* __restrict__ part) {
+
+// attend's output in the lane's row, rounded to the compute dtype T (the 16-bit modes convert two values at a time), folded in
+// slot order: s = f(s, db, r, d, x) for every accumulator slot (db, r) whose column d is < D.  (The state goes through f by value:
+// with the current compiler, sums held by reference across the walk move the register allocation of the tail kernels.)
+template <typename T, int D, typename S, typename F>
+__device__ __forceinline__ S fold_rounded(const OAcc<T, D>& acc, int half, S s, F&& f) {
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+#pragma unroll
+    for (int db = 0; db < ACfg<T, D>::NDB; ++db)
+#pragma unroll
+        for (int r = 0; r < 16; r += 2) {
+            T v[2];
+            if constexpr (sizeof(T) == 2) {
+                const h16x2 p = __builtin_convertvector((f32x2){acc.b[db][r], acc.b[db][r + 1]}, h16x2);
+                v[0] = p[0]; v[1] = p[1];
+            } else {
+                v[0] = acc.b[db][r]; v[1] = acc.b[db][r + 1];
+            }
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                const int rr = r + e, d = db * 32 + (rr & 3) + 8 * (rr >> 2) + 4 * half;
+                if (d < D) s = f(s, db, rr, d, v[e]);
+            }
+        }
+    return s;
+}
+
+// the products of the cross output ox (rounded by fold_rounded) against the self output y(db, r, d), in f32: cosine sums
+// dot | x2 | y2 into s0 | s1 | s2, mse the squared difference into s0
+struct TailSums { float s0 = 0.f, s1 = 0.f, s2 = 0.f; };
+template <typename T, int D, typename Y>
+__device__ __forceinline__ TailSums tail_products(const OAcc<T, D>& ox, int half, int mse, Y&& y) {
+    return fold_rounded<T, D>(ox, half, TailSums{}, [&](TailSums s, int db, int r, int d, T xr) {
+        const float x = (float)xr, yv = y(db, r, d);
+        if (mse) { const float df = x - yv; s.s0 = fmaf(df, df, s.s0); }
+        else { s.s0 = fmaf(x, yv, s.s0); s.s1 = fmaf(x, x, s.s1); s.s2 = fmaf(yv, yv, s.s2); }
+        return s;
+    });
+}
+
+// a workgroup's products folded over its 4 waves (shuffles, then the waves in a fixed order) into its partial
+// o[0..3] = (s0, s1, s2, 0); every thread of the workgroup calls it
+__device__ __forceinline__ void store_block_partial(TailSums t, int lane, int wave, float* __restrict__ o) {
+    __shared__ float red[4][4];
+    float s0 = t.s0, s1 = t.s1, s2 = t.s2;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        s0 += __shfl_xor(s0, off);
+        s1 += __shfl_xor(s1, off);
+        s2 += __shfl_xor(s2, off);
+    }
+    if (lane == 0) { red[wave][0] = s0; red[wave][1] = s1; red[wave][2] = s2; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        o[0] = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
+        o[1] = (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]);
+        o[2] = (red[0][2] + red[1][2]) + (red[2][2] + red[3][2]);
+        o[3] = 0.f;
+    }
+}
+
+// One direction of a pair in a 128-query workgroup: the self and the cross attention on the same Q fragments, then their products.
+// The epilogue is pair_tail_kernel's (PER_TOKEN false: one partial per workgroup, [pair][dir][bh][qtile][4] f32) or pair_map_kernel's
+// (PER_TOKEN true: one per query token, [pair][dir][comp][bh][N] f32, comp: dot | x2 | y2, or sqd | - | -).
+// grid (ceil(N/128), B*H, n_pairs*2)
+template <typename T, int D, bool PER_TOKEN>
+__device__ __forceinline__ void pair_tail_body(const T* __restrict__ qg, const T* __restrict__ kg, const T* __restrict__ vg,
+                                               const int32_t* __restrict__ idx_a, const int32_t* __restrict__ idx_b, int B, int H, int N,
+                                               float scale_log2, int mse, float* __restrict__ part) {
     typedef ACfg<T, D> C;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    __shared__ float red[4][4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, l31 = lane & 31;
     const int bh = blockIdx.y, b = bh / H, h = bh - b * H;
     const int pair = blockIdx.z >> 1, dir = blockIdx.z & 1;
@@ -1207,7 +1271,7 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void pair_tail_kerne
     const size_t boff = (size_t)b * N * ld + h * D;
     QFrags<T, D> qf;
     load_q<T, D>(qf, qg + iq * img + boff + (size_t)qc * ld, half, scale_log2);
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+    TailSums t;
     if constexpr (sizeof(T) == 2) {
         typedef float f32x2 __attribute__((ext_vector_type(2)));
         h16x2 osp[C::NDB][8];           // the self-attention's output, rounded to the compute dtype, two values per register
@@ -1224,58 +1288,36 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void pair_tail_kerne
         }
         OAcc<T, D> oxa;
         attend<T, D>(qf, kg + ix * img + boff, vg + ix * img + boff, ld, N, smem, oxa);
-        if (q < N) {
-#pragma unroll
-            for (int db = 0; db < C::NDB; ++db)
-#pragma unroll
-                for (int r = 0; r < 16; r += 2) {
-                    const h16x2 xp = __builtin_convertvector((f32x2){oxa.b[db][r], oxa.b[db][r + 1]}, h16x2);
-#pragma unroll
-                    for (int e = 0; e < 2; ++e) {
-                        const int rr = r + e, d = db * 32 + (rr & 3) + 8 * (rr >> 2) + 4 * half;
-                        if (d < D) {
-                            const float x = (float)xp[e], y = (float)osp[db][r >> 1][e];
-                            if (mse) { const float df = x - y; s0 = fmaf(df, df, s0); }
-                            else { s0 = fmaf(x, y, s0); s1 = fmaf(x, x, s1); s2 = fmaf(y, y, s2); }
-                        }
-                    }
-                }
+        if (q < N) t = tail_products<T, D>(oxa, half, mse, [&](int db, int r, int) { return (float)osp[db][r >> 1][r & 1]; });
+    } else {
+        OAcc<T, D> osa, oxa;
+        attend<T, D>(qf, kg + iq * img + boff, vg + iq * img + boff, ld, N, smem, osa);
+        attend<T, D>(qf, kg + ix * img + boff, vg + ix * img + boff, ld, N, smem, oxa);
+        if (q < N) t = tail_products<T, D>(oxa, half, mse, [&](int db, int r, int) { return osa.b[db][r]; });
+    }
+    if constexpr (PER_TOKEN) {
+        // a row's d values are split between the two lane halves: fold them, then the first half stores the row (128 B per wave and
+        // component, no atomics)
+        const float s0 = t.s0 + __shfl_xor(t.s0, 32);
+        const float s1 = t.s1 + __shfl_xor(t.s1, 32);
+        const float s2 = t.s2 + __shfl_xor(t.s2, 32);
+        if (half == 0 && q < N) {
+            const size_t plane = (size_t)gridDim.y * N;
+            float* o = part + ((size_t)pair * 2 + dir) * 3 * plane + (size_t)bh * N + q;
+            o[0] = s0;
+            if (!mse) { o[plane] = s1; o[2 * plane] = s2; }
         }
     } else {
-    OAcc<T, D> osa, oxa;
-    attend<T, D>(qf, kg + iq * img + boff, vg + iq * img + boff, ld, N, smem, osa);
-    attend<T, D>(qf, kg + ix * img + boff, vg + ix * img + boff, ld, N, smem, oxa);
-    auto& os = osa.b;
-    auto& ox = oxa.b;
-    if (q < N) {
-#pragma unroll
-        for (int db = 0; db < C::NDB; ++db)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int d = db * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-                if (d < D) {
-                    const float x = ox[db][r], y = os[db][r];
-                    if (mse) { const float df = x - y; s0 = fmaf(df, df, s0); }
-                    else { s0 = fmaf(x, y, s0); s1 = fmaf(x, x, s1); s2 = fmaf(y, y, s2); }
-                }
-            }
+        store_block_partial(t, lane, wave, part + ((((size_t)pair * 2 + dir) * gridDim.y + bh) * gridDim.x + blockIdx.x) * 4);
     }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        s0 += __shfl_xor(s0, off);
-        s1 += __shfl_xor(s1, off);
-        s2 += __shfl_xor(s2, off);
-    }
-    if (lane == 0) { red[wave][0] = s0; red[wave][1] = s1; red[wave][2] = s2; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float* o = part + ((((size_t)pair * 2 + dir) * gridDim.y + bh) * gridDim.x + blockIdx.x) * 4;
-        o[0] = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
-        o[1] = (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]);
-        o[2] = (red[0][2] + red[1][2]) + (red[2][2] + red[3][2]);
-        o[3] = 0.f;
-    }
+}
+
+template <typename T, int D>
+__global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void pair_tail_kernel(const T* __restrict__ qg, const T* __restrict__ kg,
+                                                        const T* __restrict__ vg, const int32_t* __restrict__ idx_a,
+                                                        const int32_t* __restrict__ idx_b, int B, int H, int N,
+                                                        float scale_log2, int mse, float* __restrict__ part) {
+    pair_tail_body<T, D, false>(qg, kg, vg, idx_a, idx_b, B, H, N, scale_log2, mse, part);
 }
 
 // one thread per pair: fixed-order f64 fold of the partials, then cosine / mse and the mean of
@@ -1317,9 +1359,7 @@ struct MatArgs {
 template <typename T, int D>
 __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void matrix_tail_kernel(const MatArgs p, float scale_log2, int mse, int self_mode,
                                                                                      float* __restrict__ part) {
-    typedef ACfg<T, D> C;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    __shared__ float red[4][4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, l31 = lane & 31;
     const int bh = blockIdx.y, b = bh / p.H, h = bh - b * p.H;
     const int N = p.N, ld = p.H * D;
@@ -1350,69 +1390,13 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void matrix_tail_ker
     load_q<T, D>(qf, qg + iq * img + boff + (size_t)qc * ld, half, scale_log2);
     OAcc<T, D> oa;
     attend<T, D>(qf, kg + ix * img + boff, vg + ix * img + boff, ld, N, smem, oa);
-    auto& o = oa.b;
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
     if (self_mode) {
-        if (q < N) {
-#pragma unroll
-            for (int db = 0; db < C::NDB; ++db)
-#pragma unroll
-                for (int r = 0; r < 16; r += 2) {
-                    T pr[2];
-                    if constexpr (sizeof(T) == 2) {
-                        const h16x2 y = __builtin_convertvector((f32x2){o[db][r], o[db][r + 1]}, h16x2);
-                        pr[0] = y[0]; pr[1] = y[1];
-                    } else {
-                        pr[0] = o[db][r]; pr[1] = o[db][r + 1];
-                    }
-#pragma unroll
-                    for (int e = 0; e < 2; ++e) {
-                        const int rr = r + e, d = db * 32 + (rr & 3) + 8 * (rr >> 2) + 4 * half;
-                        if (d < D) so[(size_t)q * ld + d] = pr[e];
-                    }
-                }
-        }
+        if (q < N) fold_rounded<T, D>(oa, half, 0, [&](int, int, int, int d, T y) { so[(size_t)q * ld + d] = y; return 0; });  // (no state)
         return;
     }
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f;
-    if (q < N) {
-#pragma unroll
-        for (int db = 0; db < C::NDB; ++db)
-#pragma unroll
-            for (int r = 0; r < 16; r += 2) {
-                float xv[2];
-                if constexpr (sizeof(T) == 2) {
-                    const h16x2 xp = __builtin_convertvector((f32x2){o[db][r], o[db][r + 1]}, h16x2);
-                    xv[0] = (float)xp[0]; xv[1] = (float)xp[1];
-                } else {
-                    xv[0] = o[db][r]; xv[1] = o[db][r + 1];
-                }
-#pragma unroll
-                for (int e = 0; e < 2; ++e) {
-                    const int rr = r + e, d = db * 32 + (rr & 3) + 8 * (rr >> 2) + 4 * half;
-                    if (d < D) {
-                        const float x = xv[e], y = (float)so[(size_t)q * ld + d];
-                        if (mse) { const float df = x - y; s0 = fmaf(df, df, s0); }
-                        else { s0 = fmaf(x, y, s0); s1 = fmaf(x, x, s1); s2 = fmaf(y, y, s2); }
-                    }
-                }
-            }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        s0 += __shfl_xor(s0, off);
-        s1 += __shfl_xor(s1, off);
-        s2 += __shfl_xor(s2, off);
-    }
-    if (lane == 0) { red[wave][0] = s0; red[wave][1] = s1; red[wave][2] = s2; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float* po = part + ((((size_t)cell * 2 + dir) * gridDim.y + bh) * qt + qtile) * 4;
-        po[0] = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
-        po[1] = (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]);
-        po[2] = (red[0][2] + red[1][2]) + (red[2][2] + red[3][2]);
-        po[3] = 0.f;
-    }
+    TailSums t;
+    if (q < N) t = tail_products<T, D>(oa, half, mse, [&](int, int, int d) { return (float)so[(size_t)q * ld + d]; });
+    store_block_partial(t, lane, wave, part + ((((size_t)cell * 2 + dir) * gridDim.y + bh) * qt + qtile) * 4);
 }
 
 inline float scale_log2_of(int D) { return (1.0f / sqrtf((float)D)) * 1.4426950408889634f; }
@@ -1555,62 +1539,43 @@ int launch_attn_d(const AttnArgs& a, AttnKernel kind, hipStream_t s) {
 // head dims of the supported graphs: SD1.5 40/80/160, SDXL 64, DiT-XL/2 72, test configs 16/32/64
 #define DSIM_FOR_EACH_D(X) X(16) X(32) X(40) X(64) X(72) X(80) X(160)
 
-template <typename T>
-int launch_attn_t(const AttnArgs& a, AttnKernel kind, hipStream_t s) {
-    switch (a.D) {
-#define X(d) case d: return launch_attn_d<T, d>(a, kind, s);
+// f(std::integral_constant<int, D>()) for a head dim D of DSIM_FOR_EACH_D; DSIM_ERR_INVALID for any other
+template <typename F>
+int with_head_dim(int D, F&& f) {
+    switch (D) {
+#define X(d) case d: return f(std::integral_constant<int, d>());
         DSIM_FOR_EACH_D(X)
 #undef X
         default: return DSIM_ERR_INVALID;
     }
 }
 
-template <typename T, int D>
-int launch_tail_d(const void* q, const void* k, const void* v, const int32_t* ia, const int32_t* ib, int n_pairs,
-                  int B, int H, int N, int mse, float* out, void* scratch, hipStream_t s, int32_t* status) {
-    typedef ACfg<T, D> C;
-    static DeviceOnce once;
-    auto kern = pair_tail_kernel<T, D>;
-    CK_ONCE(once, kern, C::LDS);
-    const int qt = (N + 127) / 128;
-    hipLaunchKernelGGL(kern, dim3(qt, B * H, n_pairs * 2), dim3(256), C::LDS, s, (const T*)q, (const T*)k,
-                       (const T*)v, ia, ib, B, H, N, scale_log2_of(D), mse, (float*)scratch);
-    hipLaunchKernelGGL(pair_finish_kernel, dim3((n_pairs + 63) / 64), dim3(64), 0, s, (const float*)scratch, n_pairs,
-                       qt * B * H, mse, (double)B * H * N * D, out, status);
-    DSIM_HIP_CHECK(hipGetLastError());
-    return DSIM_OK;
+template <typename T>
+int launch_attn_t(const AttnArgs& a, AttnKernel kind, hipStream_t s) {
+    return with_head_dim(a.D, [&](auto dc) { return launch_attn_d<T, decltype(dc)::value>(a, kind, s); });
 }
 
 template <typename T>
 int launch_tail_t(const void* q, const void* k, const void* v, const int32_t* ia, const int32_t* ib, int n_pairs,
                   int B, int H, int N, int D, int mse, float* out, void* scratch, hipStream_t s, int32_t* status) {
-    switch (D) {
-#define X(d) case d: return launch_tail_d<T, d>(q, k, v, ia, ib, n_pairs, B, H, N, mse, out, scratch, s, status);
-        DSIM_FOR_EACH_D(X)
-#undef X
-        default: return DSIM_ERR_INVALID;
-    }
+    return with_head_dim(D, [&](auto dc) -> int {
+        constexpr int Dc = decltype(dc)::value, LDS = ACfg<T, Dc>::LDS;
+        static DeviceOnce once;
+        auto kern = pair_tail_kernel<T, Dc>;
+        CK_ONCE(once, kern, LDS);
+        const int qt = (N + 127) / 128;
+        hipLaunchKernelGGL(kern, dim3(qt, B * H, n_pairs * 2), dim3(256), LDS, s, (const T*)q, (const T*)k, (const T*)v, ia, ib, B, H,
+                           N, scale_log2_of(Dc), mse, (float*)scratch);
+        hipLaunchKernelGGL(pair_finish_kernel, dim3((n_pairs + 63) / 64), dim3(64), 0, s, (const float*)scratch, n_pairs,
+                           qt * B * H, mse, (double)B * H * N * Dc, out, status);
+        DSIM_HIP_CHECK(hipGetLastError());
+        return DSIM_OK;
+    });
 }
 
 // workspace of the tiled score matrix: [self A | self B | partials], each 256-byte aligned
 size_t mat_self_bytes(int n, int B, int H, int N, int D, int es) { return (((size_t)n * B * N * H * D * es) + 255) & ~(size_t)255; }
 size_t mat_part_bytes(long n_cells, int B, int H, int N) { return (((size_t)n_cells * 2 * B * H * ((N + 127) / 128) * 4 * sizeof(float)) + 255) & ~(size_t)255; }
-
-template <typename T, int D>
-int launch_matrix_d(const MatArgs& m, int mse, float* out, int32_t* status, float* part, hipStream_t s) {
-    typedef ACfg<T, D> C;
-    static DeviceOnce once;
-    auto kern = matrix_tail_kernel<T, D>;
-    CK_ONCE(once, kern, C::LDS);
-    const int qt = (m.N + 127) / 128;
-    hipLaunchKernelGGL(kern, dim3(qt, m.B * m.H, m.n_a + m.n_b), dim3(256), C::LDS, s, m, scale_log2_of(D), mse, 1, part);
-    hipLaunchKernelGGL(kern, dim3(qt * m.n_a * m.n_b * 2, m.B * m.H), dim3(256), C::LDS, s, m, scale_log2_of(D), mse, 0, part);
-    const int nc = m.n_a * m.n_b;
-    hipLaunchKernelGGL(pair_finish_kernel, dim3((nc + 63) / 64), dim3(64), 0, s, (const float*)part, nc, qt * m.B * m.H, mse,
-                       (double)m.B * m.H * m.N * D, out, status);
-    DSIM_HIP_CHECK(hipGetLastError());
-    return DSIM_OK;
-}
 
 template <typename T>
 int launch_matrix_t(const void* qa, const void* ka, const void* va, int n_a, const void* qb, const void* kb, const void* vb, int n_b, int B,
@@ -1621,118 +1586,43 @@ int launch_matrix_t(const void* qa, const void* ka, const void* va, int n_a, con
     m.self[1] = (char*)scratch + mat_self_bytes(n_a, B, H, N, D, sizeof(T));
     m.n_a = n_a; m.n_b = n_b; m.B = B; m.H = H; m.N = N;
     float* part = (float*)((char*)m.self[1] + mat_self_bytes(n_b, B, H, N, D, sizeof(T)));
-    switch (D) {
-#define X(d) case d: return launch_matrix_d<T, d>(m, mse, out, status, part, s);
-        DSIM_FOR_EACH_D(X)
-#undef X
-        default: return DSIM_ERR_INVALID;
-    }
+    return with_head_dim(D, [&](auto dc) -> int {
+        constexpr int Dc = decltype(dc)::value, LDS = ACfg<T, Dc>::LDS;
+        static DeviceOnce once;
+        auto kern = matrix_tail_kernel<T, Dc>;
+        CK_ONCE(once, kern, LDS);
+        const int qt = (N + 127) / 128, nc = n_a * n_b;
+        hipLaunchKernelGGL(kern, dim3(qt, B * H, n_a + n_b), dim3(256), LDS, s, m, scale_log2_of(Dc), mse, 1, part);
+        hipLaunchKernelGGL(kern, dim3(qt * nc * 2, B * H), dim3(256), LDS, s, m, scale_log2_of(Dc), mse, 0, part);
+        hipLaunchKernelGGL(pair_finish_kernel, dim3((nc + 63) / 64), dim3(64), 0, s, (const float*)part, nc, qt * B * H, mse,
+                           (double)B * H * N * Dc, out, status);
+        DSIM_HIP_CHECK(hipGetLastError());
+        return DSIM_OK;
+    });
 }
 
 // ---- similarity maps: the score tail kept per token ------------------------------------------------------------------------------
 // The score of direction a->b splits over query tokens: cos(O_ab, O_aa) = sum_i dot_i / (|O_ab| |O_aa|) and
 // mse = sum_i sqd_i / (B H N D), where dot_i / sqd_i sum over the CFG batch, the heads and d at token i.
-// pair_map_kernel is a TWIN of pair_tail_kernel: the same grid, the same attend twice on the same Q fragments, the same rounding
-// and products; only the epilogue differs (per-token partials instead of one partial per 128 rows).  It is a copy, not a template
-// flag on pair_tail_kernel, so that the tail's device code stays as it is: a fix to one goes into the other.
-// grid (ceil(N/128), B*H, n_pairs*2); partial layout [pair][dir][comp][bh][N] f32 (comp: dot | x2 | y2, or sqd | - | -)
+// pair_map_kernel is pair_tail_body with the per-token epilogue: pair_tail_kernel's grid, attentions, rounding and products, so that
+// a pair's map contributions sum to its score.
 template <typename T, int D>
 __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void pair_map_kernel(const T* __restrict__ qg, const T* __restrict__ kg,
                                                         const T* __restrict__ vg, const int32_t* __restrict__ idx_a,
                                                         const int32_t* __restrict__ idx_b, int B, int H, int N,
                                                         float scale_log2, int mse, float* __restrict__ part) {
-    typedef ACfg<T, D> C;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, l31 = lane & 31;
-    const int bh = blockIdx.y, b = bh / H, h = bh - b * H;
-    const int pair = blockIdx.z >> 1, dir = blockIdx.z & 1;
-    const int ia = idx_a[pair], ib = idx_b[pair];
-    const int iq = dir ? ib : ia;        // query image (also the "self" keys/values)
-    const int ix = dir ? ia : ib;        // the other image ("cross" keys/values)
-    const int ld = H * D;
-    const size_t img = (size_t)B * N * ld;
-    const int q = blockIdx.x * 128 + wave * 32 + l31;
-    const int qc = q < N ? q : N - 1;
-    const size_t boff = (size_t)b * N * ld + h * D;
-    QFrags<T, D> qf;
-    load_q<T, D>(qf, qg + iq * img + boff + (size_t)qc * ld, half, scale_log2);
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f;
-    if constexpr (sizeof(T) == 2) {
-        typedef float f32x2 __attribute__((ext_vector_type(2)));
-        h16x2 osp[C::NDB][8];           // the self-attention's output, rounded to the compute dtype, two values per register
-        {
-            OAcc<T, D> osa;
-            attend<T, D>(qf, kg + iq * img + boff, vg + iq * img + boff, ld, N, smem, osa);
-#pragma unroll
-            for (int db = 0; db < C::NDB; ++db)
-#pragma unroll
-                for (int r = 0; r < 16; r += 2) {
-                    osp[db][r >> 1] = __builtin_convertvector((f32x2){osa.b[db][r], osa.b[db][r + 1]}, h16x2);
-                    asm volatile("" : "+v"(osp[db][r >> 1]));          // (pinned: the f32 accumulators die here, before the second attention)
-                }
-        }
-        OAcc<T, D> oxa;
-        attend<T, D>(qf, kg + ix * img + boff, vg + ix * img + boff, ld, N, smem, oxa);
-        if (q < N) {
-#pragma unroll
-            for (int db = 0; db < C::NDB; ++db)
-#pragma unroll
-                for (int r = 0; r < 16; r += 2) {
-                    const h16x2 xp = __builtin_convertvector((f32x2){oxa.b[db][r], oxa.b[db][r + 1]}, h16x2);
-#pragma unroll
-                    for (int e = 0; e < 2; ++e) {
-                        const int rr = r + e, d = db * 32 + (rr & 3) + 8 * (rr >> 2) + 4 * half;
-                        if (d < D) {
-                            const float x = (float)xp[e], y = (float)osp[db][r >> 1][e];
-                            if (mse) { const float df = x - y; s0 = fmaf(df, df, s0); }
-                            else { s0 = fmaf(x, y, s0); s1 = fmaf(x, x, s1); s2 = fmaf(y, y, s2); }
-                        }
-                    }
-                }
-        }
-    } else {
-    OAcc<T, D> osa, oxa;
-    attend<T, D>(qf, kg + iq * img + boff, vg + iq * img + boff, ld, N, smem, osa);
-    attend<T, D>(qf, kg + ix * img + boff, vg + ix * img + boff, ld, N, smem, oxa);
-    auto& os = osa.b;
-    auto& ox = oxa.b;
-    if (q < N) {
-#pragma unroll
-        for (int db = 0; db < C::NDB; ++db)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int d = db * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-                if (d < D) {
-                    const float x = ox[db][r], y = os[db][r];
-                    if (mse) { const float df = x - y; s0 = fmaf(df, df, s0); }
-                    else { s0 = fmaf(x, y, s0); s1 = fmaf(x, x, s1); s2 = fmaf(y, y, s2); }
-                }
-            }
-    }
-    }
-    // a row's d values are split between the two lane halves: fold them, then the first half stores the row (128 B per wave and
-    // component, no atomics)
-    s0 += __shfl_xor(s0, 32);
-    s1 += __shfl_xor(s1, 32);
-    s2 += __shfl_xor(s2, 32);
-    if (half == 0 && q < N) {
-        const size_t plane = (size_t)gridDim.y * N;
-        float* o = part + ((size_t)pair * 2 + dir) * 3 * plane + (size_t)bh * N + q;
-        o[0] = s0;
-        if (!mse) { o[plane] = s1; o[2 * plane] = s2; }
-    }
+    pair_tail_body<T, D, true>(qg, kg, vg, idx_a, idx_b, B, H, N, scale_log2, mse, part);
 }
 
 // one workgroup per pair, both directions: per token, a fixed-order f64 fold of the B*H partials; over tokens, per-thread strided
 // sums and a fixed-order tree.  local: the token's own cosine (|.| of the token's vectors) or mean squared difference; contrib: its
 // share of the direction's score, so that 0.5 (sum contrib[0] + sum contrib[1]) is the pair's score (F.cosine_similarity eps =
 // 1e-8, as pair_finish_kernel)
-// (NT threads: a template, so that it is emitted after the kernels above and leaves their code objects as they were)
 constexpr int MAP_FINISH_THREADS = 256;
-template <int NT>
-__global__ __launch_bounds__(NT) void pair_map_finish_kernel(const float* __restrict__ part, int BH, int N, int D,
-                                                                             int mse, float* __restrict__ score, float* __restrict__ local,
+__global__ __launch_bounds__(MAP_FINISH_THREADS) void pair_map_finish_kernel(const float* __restrict__ part, int BH, int N, int D, int mse,
+                                                                             float* __restrict__ score, float* __restrict__ local,
                                                                              float* __restrict__ contrib, int32_t* __restrict__ status) {
+    constexpr int NT = MAP_FINISH_THREADS;
     __shared__ double red[3][NT];
     const int p = blockIdx.x, t = threadIdx.x;
     const size_t plane = (size_t)BH * N;
@@ -1789,30 +1679,21 @@ __global__ __launch_bounds__(NT) void pair_map_finish_kernel(const float* __rest
     }
 }
 
-template <typename T, int D>
-int launch_maps_d(const void* q, const void* k, const void* v, const int32_t* ia, const int32_t* ib, int n_pairs, int B, int H, int N,
-                  int mse, float* score, float* local, float* contrib, int32_t* status, void* scratch, hipStream_t s) {
-    typedef ACfg<T, D> C;
-    static DeviceOnce once;
-    auto kern = pair_map_kernel<T, D>;
-    CK_ONCE(once, kern, C::LDS);
-    hipLaunchKernelGGL(kern, dim3((N + 127) / 128, B * H, n_pairs * 2), dim3(256), C::LDS, s, (const T*)q, (const T*)k,
-                       (const T*)v, ia, ib, B, H, N, scale_log2_of(D), mse, (float*)scratch);
-    hipLaunchKernelGGL(pair_map_finish_kernel<MAP_FINISH_THREADS>, dim3(n_pairs), dim3(MAP_FINISH_THREADS), 0, s, (const float*)scratch, B * H, N, D, mse,
-                       score, local, contrib, status);
-    DSIM_HIP_CHECK(hipGetLastError());
-    return DSIM_OK;
-}
-
 template <typename T>
 int launch_maps_t(const void* q, const void* k, const void* v, const int32_t* ia, const int32_t* ib, int n_pairs, int B, int H, int N,
                   int D, int mse, float* score, float* local, float* contrib, int32_t* status, void* scratch, hipStream_t s) {
-    switch (D) {
-#define X(d) case d: return launch_maps_d<T, d>(q, k, v, ia, ib, n_pairs, B, H, N, mse, score, local, contrib, status, scratch, s);
-        DSIM_FOR_EACH_D(X)
-#undef X
-        default: return DSIM_ERR_INVALID;
-    }
+    return with_head_dim(D, [&](auto dc) -> int {
+        constexpr int Dc = decltype(dc)::value, LDS = ACfg<T, Dc>::LDS;
+        static DeviceOnce once;
+        auto kern = pair_map_kernel<T, Dc>;
+        CK_ONCE(once, kern, LDS);
+        hipLaunchKernelGGL(kern, dim3((N + 127) / 128, B * H, n_pairs * 2), dim3(256), LDS, s, (const T*)q, (const T*)k, (const T*)v, ia,
+                           ib, B, H, N, scale_log2_of(Dc), mse, (float*)scratch);
+        hipLaunchKernelGGL(pair_map_finish_kernel, dim3(n_pairs), dim3(MAP_FINISH_THREADS), 0, s, (const float*)scratch, B * H, N, Dc,
+                           mse, score, local, contrib, status);
+        DSIM_HIP_CHECK(hipGetLastError());
+        return DSIM_OK;
+    });
 }
 
 }  // namespace

@@ -298,7 +298,8 @@ bool pair_score160_applies(int N, int D, int dtype);
 size_t pair_score160_scratch_bytes(int n_pairs, int B, int H);
 int launch_pair_score160(const void* q, const void* k, const void* v, const int32_t* idx_a, const int32_t* idx_b, int n_pairs, int B,
                          int H, int mse, float* out, void* scratch, size_t scratch_bytes, hipStream_t s, int32_t* status);
-// similarity maps: the score tail kept per query token (pair_map_kernel, any shape and dtype) -- attention.hip
+// similarity maps: the score tail kept per query token (pair_map_kernel: pair_tail_kernel's body with a per-token epilogue, any
+// shape and dtype) -- attention.hip
 //   score [n_pairs]; local, contrib (each may be NULL) [n_pairs][2][N]; status (may be NULL) [n_pairs]
 size_t pair_score_maps_scratch_bytes(int n_pairs, int B, int H, int N);
 int launch_pair_score_maps(const void* q, const void* k, const void* v, const int32_t* idx_a, const int32_t* idx_b, int n_pairs, int B,

@@ -757,6 +757,17 @@ int dsim_unet_set_sample_size(dsim_unet* h, int side) {
     return DSIM_OK;
 }
 
+// a caller's workspace starts at its first 256-byte boundary: moves `ws` there and takes the bytes before it off `bytes`; false when
+// the buffer does not reach it
+static bool align_workspace(void*& ws, size_t& bytes) {
+    const uintptr_t b0 = ((uintptr_t)ws + 255) & ~(uintptr_t)255;
+    const size_t lost = b0 - (uintptr_t)ws;
+    if (bytes < lost) return false;
+    ws = (void*)b0;
+    bytes -= lost;
+    return true;
+}
+
 int dsim_unet_qkv(dsim_unet* h, const float* latents, const float* noise, float sqrt_abar, float sqrt_1m_abar,
                   const float* ctx, int n_images, void* q, void* k, void* v, void* workspace, size_t workspace_bytes,
                   void* stream) {
@@ -764,12 +775,9 @@ int dsim_unet_qkv(dsim_unet* h, const float* latents, const float* noise, float 
     if (!h->finalized || h->timestep < 0) return DSIM_ERR_STATE;
     Arena ar;
     ar.dry = false;
-    // align the arena base to 256 B
-    const uintptr_t b0 = ((uintptr_t)workspace + 255) & ~(uintptr_t)255;
-    const size_t lost = b0 - (uintptr_t)workspace;
-    if (workspace_bytes < lost) return DSIM_ERR_WORKSPACE;
-    ar.base = (char*)b0;
-    ar.cap = workspace_bytes - lost;
+    if (!align_workspace(workspace, workspace_bytes)) return DSIM_ERR_WORKSPACE;
+    ar.base = (char*)workspace;
+    ar.cap = workspace_bytes;
     {   // refuse up front instead of failing mid-graph
         Arena plan;
         Walk pw{h, &plan, nullptr, 2 * n_images, false};
@@ -814,28 +822,30 @@ size_t dsim_pair_score_workspace_bytes(int n_pairs, int B, int H, int N, int D) 
     return pair_score_scratch_bytes(n_pairs, B, H, N, D) + 256;
 }
 
+// status may be NULL here; dsim_pair_score_status requires it
+static int pair_score(const void* q, const void* k, const void* v, const int32_t* idx_a, const int32_t* idx_b, int n_pairs, int B,
+                      int H, int N, int D, int dtype, int similarity, float* out_scores, int32_t* status, void* workspace,
+                      size_t workspace_bytes, void* stream) {
+    if (!q || !k || !v || !idx_a || !idx_b || !out_scores || !workspace) return DSIM_ERR_INVALID;
+    if (similarity != 0 && similarity != 1) return DSIM_ERR_INVALID;
+    if (!align_workspace(workspace, workspace_bytes)) return DSIM_ERR_WORKSPACE;
+    return launch_pair_score(q, k, v, idx_a, idx_b, n_pairs, B, H, N, D, dtype, similarity, out_scores, workspace, workspace_bytes,
+                             (hipStream_t)stream, status);
+}
+
 int dsim_pair_score(const void* q, const void* k, const void* v, const int32_t* idx_a, const int32_t* idx_b, int n_pairs,
                     int B, int H, int N, int D, int dtype, int similarity, float* out_scores, void* workspace,
                     size_t workspace_bytes, void* stream) {
-    if (!q || !k || !v || !idx_a || !idx_b || !out_scores || !workspace) return DSIM_ERR_INVALID;
-    if (similarity != 0 && similarity != 1) return DSIM_ERR_INVALID;
-    const uintptr_t b0 = ((uintptr_t)workspace + 255) & ~(uintptr_t)255;
-    const size_t lost = b0 - (uintptr_t)workspace;
-    if (workspace_bytes < lost) return DSIM_ERR_WORKSPACE;
-    return launch_pair_score(q, k, v, idx_a, idx_b, n_pairs, B, H, N, D, dtype, similarity, out_scores, (void*)b0,
-                             workspace_bytes - lost, (hipStream_t)stream);
+    return pair_score(q, k, v, idx_a, idx_b, n_pairs, B, H, N, D, dtype, similarity, out_scores, nullptr, workspace, workspace_bytes,
+                      stream);
 }
 
 int dsim_pair_score_status(const void* q, const void* k, const void* v, const int32_t* idx_a, const int32_t* idx_b,
                            int n_pairs, int B, int H, int N, int D, int dtype, int similarity, float* out_scores,
                            int32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!q || !k || !v || !idx_a || !idx_b || !out_scores || !status || !workspace) return DSIM_ERR_INVALID;
-    if (similarity != 0 && similarity != 1) return DSIM_ERR_INVALID;
-    const uintptr_t b0 = ((uintptr_t)workspace + 255) & ~(uintptr_t)255;
-    const size_t lost = b0 - (uintptr_t)workspace;
-    if (workspace_bytes < lost) return DSIM_ERR_WORKSPACE;
-    return launch_pair_score(q, k, v, idx_a, idx_b, n_pairs, B, H, N, D, dtype, similarity, out_scores, (void*)b0,
-                             workspace_bytes - lost, (hipStream_t)stream, status);
+    if (!status) return DSIM_ERR_INVALID;
+    return pair_score(q, k, v, idx_a, idx_b, n_pairs, B, H, N, D, dtype, similarity, out_scores, status, workspace, workspace_bytes,
+                      stream);
 }
 
 size_t dsim_score_matrix_workspace_bytes(int n_a, int n_b, int B, int H, int N, int D, int dtype) {
@@ -847,11 +857,9 @@ int dsim_score_matrix(const void* qa, const void* ka, const void* va, int n_a, c
                       int B, int H, int N, int D, int dtype, int similarity, float* out, int32_t* status, void* workspace,
                       size_t workspace_bytes, void* stream) {
     if (!qa || !ka || !va || !qb || !kb || !vb || !out || !workspace) return DSIM_ERR_INVALID;
-    const uintptr_t b0 = ((uintptr_t)workspace + 255) & ~(uintptr_t)255;
-    const size_t lost = b0 - (uintptr_t)workspace;
-    if (workspace_bytes < lost) return DSIM_ERR_WORKSPACE;
-    return launch_score_matrix(qa, ka, va, n_a, qb, kb, vb, n_b, B, H, N, D, dtype, similarity, out, status, (void*)b0,
-                               workspace_bytes - lost, (hipStream_t)stream);
+    if (!align_workspace(workspace, workspace_bytes)) return DSIM_ERR_WORKSPACE;
+    return launch_score_matrix(qa, ka, va, n_a, qb, kb, vb, n_b, B, H, N, D, dtype, similarity, out, status, workspace,
+                               workspace_bytes, (hipStream_t)stream);
 }
 
 size_t dsim_pair_score_maps_workspace_bytes(int n_pairs, int B, int H, int N, int D) {
@@ -864,11 +872,9 @@ int dsim_pair_score_maps(const void* q, const void* k, const void* v, const int3
                          void* workspace, size_t workspace_bytes, void* stream) {
     if (!q || !k || !v || !idx_a || !idx_b || !score || !workspace) return DSIM_ERR_INVALID;
     if (similarity != 0 && similarity != 1) return DSIM_ERR_INVALID;
-    const uintptr_t b0 = ((uintptr_t)workspace + 255) & ~(uintptr_t)255;
-    const size_t lost = b0 - (uintptr_t)workspace;
-    if (workspace_bytes < lost) return DSIM_ERR_WORKSPACE;
+    if (!align_workspace(workspace, workspace_bytes)) return DSIM_ERR_WORKSPACE;
     return launch_pair_score_maps(q, k, v, idx_a, idx_b, n_pairs, B, H, N, D, dtype, similarity, score, local, contrib, status,
-                                  (void*)b0, workspace_bytes - lost, (hipStream_t)stream);
+                                  workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 // ---- single-operator entry points (tests / micro-benchmarks; these allocate and synchronise) ----
