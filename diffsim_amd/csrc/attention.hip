@@ -1214,6 +1214,23 @@ __device__ __forceinline__ S fold_rounded(const OAcc<T, D>& acc, int half, S s, 
     return s;
 }
 
+// attend's normalised output held as plain f32 values: hipcc may otherwise fuse attend's final multiply by 1/l into what consumes
+// it -- into the fp16 rounding (v_fma_mixlo_f16: one rounding instead of f32 then fp16) or into the mse difference (an fma) -- and it
+// does so in some tail kernels and not in others.  Every tail calls it on every attend output, so that pair_tail_body and
+// matrix_tail_kernel round and subtract the same f32 values and a matrix cell equals the pair tail's score bit for bit.
+template <typename T, int D>
+__device__ __forceinline__ void settle(OAcc<T, D>& acc) {
+#pragma unroll
+    for (int db = 0; db < ACfg<T, D>::NDB; ++db)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            if (db * 32 + (r & 3) + 8 * (r >> 2) >= D) continue;      // (no lane holds a column d < D in this slot)
+            float x = acc.b[db][r];
+            asm volatile("" : "+v"(x));
+            acc.b[db][r] = x;
+        }
+}
+
 // the products of the cross output ox (rounded by fold_rounded) against the self output y(db, r, d), in f32: cosine sums
 // dot | x2 | y2 into s0 | s1 | s2, mse the squared difference into s0
 struct TailSums { float s0 = 0.f, s1 = 0.f, s2 = 0.f; };
@@ -1278,6 +1295,7 @@ __device__ __forceinline__ void pair_tail_body(const T* __restrict__ qg, const T
         {
             OAcc<T, D> osa;
             attend<T, D>(qf, kg + iq * img + boff, vg + iq * img + boff, ld, N, smem, osa);
+            settle<T, D>(osa);
 #pragma unroll
             for (int db = 0; db < C::NDB; ++db)
 #pragma unroll
@@ -1288,11 +1306,14 @@ __device__ __forceinline__ void pair_tail_body(const T* __restrict__ qg, const T
         }
         OAcc<T, D> oxa;
         attend<T, D>(qf, kg + ix * img + boff, vg + ix * img + boff, ld, N, smem, oxa);
+        settle<T, D>(oxa);
         if (q < N) t = tail_products<T, D>(oxa, half, mse, [&](int db, int r, int) { return (float)osp[db][r >> 1][r & 1]; });
     } else {
         OAcc<T, D> osa, oxa;
         attend<T, D>(qf, kg + iq * img + boff, vg + iq * img + boff, ld, N, smem, osa);
         attend<T, D>(qf, kg + ix * img + boff, vg + ix * img + boff, ld, N, smem, oxa);
+        settle<T, D>(osa);
+        settle<T, D>(oxa);
         if (q < N) t = tail_products<T, D>(oxa, half, mse, [&](int db, int r, int) { return osa.b[db][r]; });
     }
     if constexpr (PER_TOKEN) {
@@ -1390,6 +1411,7 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void matrix_tail_ker
     load_q<T, D>(qf, qg + iq * img + boff + (size_t)qc * ld, half, scale_log2);
     OAcc<T, D> oa;
     attend<T, D>(qf, kg + ix * img + boff, vg + ix * img + boff, ld, N, smem, oa);
+    settle<T, D>(oa);
     if (self_mode) {
         if (q < N) fold_rounded<T, D>(oa, half, 0, [&](int, int, int, int d, T y) { so[(size_t)q * ld + d] = y; return 0; });  // (no state)
         return;

@@ -318,7 +318,8 @@ class TapView:
 
 def pair_score(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, idx_a: torch.Tensor, idx_b: torch.Tensor,
                heads: int, similarity: str = "cosine", return_status: bool = False):
-    """Fused score tail (diffsim/diffsim.py:177-197).  q,k,v: [n_feat][B][N][H*D]; idx: int32 cuda [n_pairs].
+    """Fused score tail (diffsim/diffsim.py:177-197).  q,k,v: contiguous [n_feat][B][N][H*D] of one shape; idx: contiguous int32
+    cuda [n_pairs] each, entries in [0, n_feat) (not checked: that would need a device sync).
     return_status: also return an int32 [n_pairs] tensor, 1 where the score is NaN / infinite (NaN guard)."""
     L = _lib.lib()
     _require_cuda(q, k, v, idx_a, idx_b)
@@ -328,9 +329,17 @@ def pair_score(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, idx_a: torch.T
         raise _lib.DsimError("q,k,v must share dtype float32, bfloat16 or float16")
     if idx_a.dtype != torch.int32 or idx_b.dtype != torch.int32:
         raise _lib.DsimError("pair indices must be int32")
+    if q.ndim != 4 or k.shape != q.shape or v.shape != q.shape:
+        raise _lib.DsimError("q,k,v must be [n_feat][B][N][H*D] of one shape")
+    if not all(t.is_contiguous() for t in (q, k, v, idx_a, idx_b)):
+        raise _lib.DsimError("features and indices must be contiguous")
     nf, B, N, HD = q.shape
     D = HD // heads
+    if D * heads != HD:
+        raise _lib.DsimError(f"H*D = {HD} is not a multiple of heads = {heads}")
     n_pairs = idx_a.numel()
+    if idx_b.numel() != n_pairs:
+        raise _lib.DsimError("idx_a and idx_b must have the same length")
     out = torch.empty(n_pairs, dtype=torch.float32, device=q.device)
     with torch.cuda.device(q.device):
         wsb = int(L.dsim_pair_score_workspace_bytes(n_pairs, B, heads, N, D))

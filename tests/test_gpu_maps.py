@@ -7,7 +7,8 @@ import os
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
+
+from tests._tail64 import pairs64
 
 pytestmark = pytest.mark.gpu
 
@@ -22,33 +23,8 @@ def eng():
 
 def _maps64(q, k, v, ia, ib, H, sim, out_dtype):
     """Per pair: score, local (2, N), contrib (2, N) in float64 -- float64 SDPAs on the rounded operands, their outputs rounded to
-    the pipeline dtype, then the per-token terms of cosine / mse"""
-    q, k, v = (t.cpu() for t in (q, k, v))
-    N, HD = q.shape[2], q.shape[3]
-    D = HD // H
-
-    def heads(t):
-        return t.double().view(B, N, H, D).transpose(1, 2)
-
-    def sdpa(i, j):
-        return F.scaled_dot_product_attention(heads(q[i]), heads(k[j]), heads(v[j])).to(out_dtype).double()
-
-    out = []
-    for a, b in zip(ia.tolist(), ib.tolist()):
-        loc, con, s = [], [], 0.0
-        for x_, o_ in ((sdpa(a, b), sdpa(a, a)), (sdpa(b, a), sdpa(b, b))):       # (B, H, N, D): O_ab vs O_aa, O_ba vs O_bb
-            if sim == "cosine":
-                dot = (x_ * o_).sum((0, 1, 3))
-                x2, y2 = (x_ * x_).sum((0, 1, 3)), (o_ * o_).sum((0, 1, 3))
-                loc.append(dot / (x2.sqrt().clamp_min(1e-8) * y2.sqrt().clamp_min(1e-8)))
-                con.append(dot / (x2.sum().sqrt().clamp_min(1e-8) * y2.sum().sqrt().clamp_min(1e-8)))
-            else:
-                sqd = ((x_ - o_) ** 2).sum((0, 1, 3))
-                loc.append(sqd / (B * H * D))
-                con.append(sqd / (B * H * N * D))
-            s += 0.5 * float(con[-1].sum())
-        out.append((s, torch.stack(loc), torch.stack(con)))
-    return out
+    the pipeline dtype, then the per-token terms of cosine / mse (tests/_tail64.py)"""
+    return pairs64(q, k, v, ia.cpu(), ib.cpu(), H, sim, out_dtype)
 
 
 def _feats(n, seed, dtype, N, H, D, logit_scale=1.0, correlate=0.5):

@@ -3,7 +3,8 @@ image of set B, each image's self-attention computed once.  Checked against the 
 torch (/root/reference/diffsim/diffsim.py:177-197) and against the pair path (engine.pair_score) on the same features."""
 import pytest
 import torch
-import torch.nn.functional as F
+
+from tests._tail64 import matrix64
 
 pytestmark = pytest.mark.gpu
 
@@ -18,31 +19,8 @@ def eng():
 
 def _tail64(fa, fb, H, sim, out_dtype):
     """float64 SDPAs on the rounded operands, their outputs rounded to the pipeline dtype, cosine / mse in float64:
-    the (n_a, n_b) matrix of diffsim.py:177-197 over every (a, b)"""
-    qa, ka, va = (t.cpu() for t in fa)
-    qb, kb, vb = (t.cpu() for t in fb)
-    N, HD = qa.shape[2], qa.shape[3]
-    D = HD // H
-
-    def heads(t):
-        return t.double().view(B, N, H, D).transpose(1, 2)
-
-    def sdpa(qq, kk, vv):
-        return F.scaled_dot_product_attention(heads(qq), heads(kk), heads(vv)).to(out_dtype).double()
-
-    sa = [sdpa(qa[i], ka[i], va[i]) for i in range(qa.shape[0])]
-    sb = [sdpa(qb[j], kb[j], vb[j]) for j in range(qb.shape[0])]
-    out = torch.empty(qa.shape[0], qb.shape[0], dtype=torch.float64)
-    for i in range(qa.shape[0]):
-        for j in range(qb.shape[0]):
-            o_ab, o_ba = sdpa(qa[i], kb[j], vb[j]), sdpa(qb[j], ka[i], va[i])
-            if sim == "cosine":
-                s = 0.5 * (F.cosine_similarity(o_ab.reshape(1, -1), sa[i].reshape(1, -1)) +
-                           F.cosine_similarity(o_ba.reshape(1, -1), sb[j].reshape(1, -1)))
-            else:
-                s = 0.5 * (F.mse_loss(o_ab, sa[i]) + F.mse_loss(o_ba, sb[j]))
-            out[i, j] = float(s)
-    return out
+    the (n_a, n_b) matrix of diffsim.py:177-197 over every (a, b) (tests/_tail64.py, query-chunked)"""
+    return matrix64(fa, fb, H, sim, out_dtype)
 
 
 def _feats(n, seed, dtype, N, H, D, logit_scale=1.0, correlate=0.0, base=None):
@@ -99,8 +77,6 @@ def test_fp32_matrix_matches_the_pair_path_and_float64(eng, N, H, D, na, nb):
     m = eng.score_matrix(fa, fb, H, "cosine")
     assert torch.equal(m, _pair_matrix(eng, fa, fb, H, "cosine"))      # pair_tail_kernel's attend, products and fold
     got = m.double().cpu()
-    if N > 1024:
-        return                  # (a float64 SDPA at 4096 keys materialises 2 GB of scores per call: the pair path is the check)
     want = _tail64(fa, fb, H, "cosine", torch.float32)
     assert ((got - want).abs() / want.abs().clamp_min(1e-6)).max().item() <= 1e-5, (got, want)
 
