@@ -260,6 +260,7 @@ def run(args) -> int:
 def run_retrieval(args, scorer, layer) -> int:
     """--dataset retrieval: the query x gallery score matrix (retrieval.score_path_matrix) and one ranking file per query."""
     from . import retrieval as R
+    from .inputs import path_latents
     queries, gallery = R.list_images(args.query_path), R.list_images(args.image_path)
     try:
         R.ranking_names(queries, args.query_path)               # two queries that would share a ranking file: refused before scoring
@@ -270,7 +271,8 @@ def run_retrieval(args, scorer, layer) -> int:
                                      args.target_step, args.seed, args.similarity, return_status=True)
     elif queries and gallery:
         # the matrix's own latents and draws, kept for the maps of each query's top-k cells
-        latA, latB, nA, nB = R._path_latents(scorer, queries, gallery, args.image_size, args.seed)
+        (latA,), nA, _ = path_latents(scorer, [(p,) for p in queries], (0,), args.image_size, args.seed, R.ENCODE_CHUNK)
+        (latB,), _, nB = path_latents(scorer, [(p,) for p in gallery], (1,), args.image_size, args.seed, R.ENCODE_CHUNK)
         m, bad = R.score_latent_matrix(scorer, latA, latB, nA, nB, args.prompt, args.target_block, layer, args.target_step,
                                        args.similarity, return_status=True)
     else:

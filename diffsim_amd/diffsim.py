@@ -199,6 +199,7 @@ class DiffSim:
         workspace arena of the engine (streams = 2 -> two arenas, ~0.75 GB per pair of the chunk size each).
         batch_pairs=None picks the measured optimum (profiles/r04h_batch_sweep.txt: 64 pairs per chunk, 662 pairs/s against
         603 at 16) within what fits: every activation < 2 GiB and the arenas of the streams in use inside the free HBM."""
+        from .inputs import stack_rows
         n = latA.shape[0]
         eng = self.engine(target_block, target_layer)
         out = torch.empty(n, dtype=torch.float32, device=self.device)
@@ -224,10 +225,7 @@ class DiffSim:
             i1 = min(n, i0 + batch_pairs)
             m = i1 - i0
             with torch.cuda.stream(self._streams[ci % ns] if ns > 1 else main):
-                lat = torch.stack([latA[i0:i1], latB[i0:i1]], dim=1).reshape(2 * m, *latA.shape[1:])
-                nA = noiseA[i0:i1] if noiseA.shape[0] == n else noiseA.expand(m, *noiseA.shape[1:])
-                nB = noiseB[i0:i1] if noiseB.shape[0] == n else noiseB.expand(m, *noiseB.shape[1:])
-                nz = torch.stack([nA, nB], dim=1).reshape(2 * m, *latA.shape[1:])
+                lat, nz = stack_rows([latA, latB], [noiseA, noiseB], i0, i1)
                 q, k, v = self.features(lat, nz, prompt if ns == 1 else ctx_ready, target_block, target_layer, target_step)
                 ia = torch.arange(0, 2 * m, 2, dtype=torch.int32, device=self.device)
                 out[i0:i1] = pair_score(q, k, v, ia, ia + 1, eng.heads, similarity)
@@ -273,54 +271,13 @@ class DiffSim:
     def score_pairs(self, pairs: Sequence[Tuple[str, str]], img_size, prompt, target_block, target_layer, target_step,
                     seed="2333", similarity="cosine", batch_pairs: Optional[int] = None) -> torch.Tensor:
         """Batched equivalent of calling :meth:`diffsim` once per (A, B) path pair."""
+        from .inputs import path_latents
         target_layer = _norm_layer(target_layer)
-        unet_bp = batch_pairs                 # None: score_latent_pairs picks its own chunk (64 where it fits)
-        if batch_pairs is None:
-            batch_pairs = 16                  # pairs per VAE encode: 32 images at 512 px keep its widest activation < 2 GiB
-        lA, lB = [], []
-        nA = nB = None
-        vae = self.vae
-        if vae is not None and hasattr(vae, "moments"):
-            # HIP VAE: images decoded on the host thread pool, one encode per chunk of pairs; every pair reseeds the
-            # same generator, so its four draws (vaeA, vaeB, noiseA, noiseB) are the same tensors for all pairs
-            from .engine import image_preprocess, latent_sample
-            g = get_generator(seed, "cpu")
-            eps = None
-            sf = vae.config.scaling_factor
-            nd = self.noise_dtype
-            def submit(i0):
-                return self._decode.submit([p for ab in pairs[i0:i0 + batch_pairs] for p in ab], img_size)
-            starts = list(range(0, len(pairs), batch_pairs))
-            pending = [submit(i0) for i0 in starts[:2]]          # decode + resize run two chunks ahead of the GPU
-            for ci, i0 in enumerate(starts):
-                px = DecodePool.gather(pending.pop(0))
-                if ci + 2 < len(starts):
-                    pending.append(submit(starts[ci + 2]))
-                # process_image's arithmetic and the fp16 image cast on the device (bit-identical, dsim_image_preprocess)
-                x = image_preprocess(px.to(vae.device, non_blocking=True), self.vae_dtype == torch.float16)
-                mom = vae.moments(x)
-                if eps is None:
-                    shp = (1, mom.shape[1] // 2) + tuple(mom.shape[2:])
-                    eA = torch.randn(shp, generator=g, dtype=nd).float().to(vae.device)
-                    eB = torch.randn(shp, generator=g, dtype=nd).float().to(vae.device)
-                    nA = torch.randn(shp, generator=g, dtype=nd).float()
-                    nB = torch.randn(shp, generator=g, dtype=nd).float()
-                    eps = (eA, eB)
-                lA.append(latent_sample(mom, eps[0], sf, 0, 2, nd == torch.float16))
-                lB.append(latent_sample(mom, eps[1], sf, 1, 2, nd == torch.float16))
-            return self.score_latent_pairs(torch.cat(lA), torch.cat(lB), nA, nB, prompt, target_block, target_layer,
-                                           target_step, similarity, unet_bp)
-        for pa, pb in pairs:
-            generator = get_generator(seed, "cpu")
-            a = self.prepare_image_latents(process_image(load_image(pa), img_size), self.vae, None, generator)
-            b = self.prepare_image_latents(process_image(load_image(pb), img_size), self.vae, None, generator)
-            if nA is None:   # same seed every call -> the two noise tensors are identical for every pair
-                nA = torch.randn(a.shape, generator=generator, dtype=self.noise_dtype).float()
-                nB = torch.randn(b.shape, generator=generator, dtype=self.noise_dtype).float()
-            lA.append(a.to(self.noise_dtype).float())
-            lB.append(b.to(self.noise_dtype).float())
-        return self.score_latent_pairs(torch.cat(lA), torch.cat(lB), nA, nB, prompt, target_block, target_layer,
-                                       target_step, similarity, unet_bp)
+        # batch_pairs=None: 16 pairs per VAE encode (32 images at 512 px keep its widest activation < 2 GiB), and
+        # score_latent_pairs picks its own chunk (64 where it fits)
+        (latA, latB), nA, nB = path_latents(self, list(pairs), (0, 1), img_size, seed, 16 if batch_pairs is None else batch_pairs)
+        return self.score_latent_pairs(latA, latB, nA, nB, prompt, target_block, target_layer, target_step, similarity,
+                                       batch_pairs)
 
     # ------------------------------------------------------------------------------------------
     @torch.no_grad()

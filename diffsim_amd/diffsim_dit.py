@@ -12,9 +12,8 @@ import torch
 
 from . import scheduler as sched
 from .config import DIT_XL2, DiTConfig
-from .diffsim import get_generator
 from .engine import DiTEngine, pair_score
-from .image import load_image, process_image
+from .inputs import path_latents, stack_rows
 
 
 class diffsim_DiT:
@@ -60,39 +59,24 @@ class diffsim_DiT:
         n = latA.shape[0]
         eng = self.engine(int(target_layer))
         out = torch.empty(n, dtype=torch.float32, device=self.device)
-        shp = latA.shape[1:]
         for i0 in range(0, n, batch_pairs):
             i1 = min(n, i0 + batch_pairs)
-            m = i1 - i0
-            lat = torch.stack([latA[i0:i1], latB[i0:i1]], dim=1).reshape(2 * m, *shp).float()
-            nz = torch.stack([noiseA.expand(m, *shp), noiseB.expand(m, *shp)], dim=1).reshape(2 * m, *shp).float()
-            q, k, v = self.features(lat, nz, target_layer, target_step)
-            ia = torch.arange(0, 2 * m, 2, dtype=torch.int32, device=self.device)
+            q, k, v = self.features(*stack_rows([latA, latB], [noiseA, noiseB], i0, i1), target_layer, target_step)
+            ia = torch.arange(0, 2 * (i1 - i0), 2, dtype=torch.int32, device=self.device)
             out[i0:i1] = pair_score(q, k, v, ia, ia + 1, eng.heads, similarity)
         return out
 
     @torch.no_grad()
     def diffsim_score(self, image_A, image_B, img_size, prompt, target_block, target_layer, target_step, similarity, seed):
         """Same contract as the reference's ``diffsim_DiT.diffsim_score`` (diffsim/diffsim_dit.py:74-142)."""
-        layer = target_layer[0]
-        return self.score_latent_pairs(*self._path_pair_latents(image_A, image_B, img_size, seed), layer, target_step, similarity)
-
-    def _path_pair_latents(self, image_A, image_B, img_size, seed):
-        """(latentsA, latentsB, noiseA, noiseB) as f32 tensors: what one reference call draws for the two image files."""
-        tA, tB = process_image(load_image(image_A), img_size), process_image(load_image(image_B), img_size)
-        generator = get_generator(seed, "cpu")
-        latentsA = self.prepare_image_latents(tA, generator)
-        latentsB = self.prepare_image_latents(tB, generator)
-        # randn_tensor(dtype=latents.dtype): the reference draws the noise in fp16 (diffsim_dit.py:64-66)
-        noiseA = torch.randn(latentsA.shape, generator=generator, dtype=latentsA.dtype)
-        noiseB = torch.randn(latentsB.shape, generator=generator, dtype=latentsB.dtype)
-        return latentsA.float(), latentsB.float(), noiseA.float(), noiseB.float()
+        (latA, latB), nA, nB = path_latents(self, [(image_A, image_B)], (0, 1), img_size, seed, 1, hip_vae=False)
+        return self.score_latent_pairs(latA, latB, nA, nB, target_layer[0], target_step, similarity)
 
     @torch.no_grad()
     def similarity_maps(self, image_A, image_B, img_size, prompt, target_block, target_layer, target_step, similarity, seed):
         """:meth:`diffsim_score` with the per-token terms on both images' grids (a maps.SimilarityMaps of one pair)."""
-        return self.score_latent_pair_maps(*self._path_pair_latents(image_A, image_B, img_size, seed), target_layer[0],
-                                           target_step, similarity)
+        (latA, latB), nA, nB = path_latents(self, [(image_A, image_B)], (0, 1), img_size, seed, 1, hip_vae=False)
+        return self.score_latent_pair_maps(latA, latB, nA, nB, target_layer[0], target_step, similarity)
 
     @torch.no_grad()
     def score_latent_pair_maps(self, latA, latB, noiseA, noiseB, target_layer: int, target_step: int, similarity="cosine",

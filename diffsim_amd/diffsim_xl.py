@@ -15,9 +15,8 @@ import torch
 
 from . import scheduler as sched
 from .config import SDXL, UNetConfig
-from .diffsim import get_generator
 from .engine import UNetEngine, pair_score
-from .image import load_image, process_image
+from .inputs import path_latents, stack_rows
 
 
 class diffsim_xl:
@@ -94,17 +93,12 @@ class diffsim_xl:
         n = latA.shape[0]
         eng = self.engine(target_block, target_layer)
         out = torch.empty(n, dtype=torch.float32, device=self.device)
-        shp = latA.shape[1:]
         batch_pairs = max(1, min(batch_pairs, eng.max_images() // 2))      # every activation must stay < 2 GiB
         for i0 in range(0, n, batch_pairs):
             i1 = min(n, i0 + batch_pairs)
-            m = i1 - i0
-            lat = torch.stack([latA[i0:i1], latB[i0:i1]], dim=1).reshape(2 * m, *shp).float()
-            nA = noiseA[i0:i1] if (noiseA.shape[0] == n and n > 1) else noiseA.expand(m, *shp)
-            nB = noiseB[i0:i1] if (noiseB.shape[0] == n and n > 1) else noiseB.expand(m, *shp)
-            nz = torch.stack([nA, nB], dim=1).reshape(2 * m, *shp)
+            lat, nz = stack_rows([latA, latB], [noiseA, noiseB], i0, i1)
             q, k, v = self.features(lat, nz, ctx, pooled, target_block, target_layer, target_step)
-            ia = torch.arange(0, 2 * m, 2, dtype=torch.int32, device=self.device)
+            ia = torch.arange(0, 2 * (i1 - i0), 2, dtype=torch.int32, device=self.device)
             out[i0:i1] = pair_score(q, k, v, ia, ia + 1, eng.heads, similarity)
         return out
 
@@ -119,14 +113,9 @@ class diffsim_xl:
         """(latentsA, latentsB, noiseA, noiseB, ctx, pooled): what one reference call draws and encodes."""
         if self._encode_prompt is None:
             raise RuntimeError("no text encoder plugged in: pass encode_prompt=...")
-        tensor_A, tensor_B = process_image(load_image(image_A), img_size), process_image(load_image(image_B), img_size)
-        generator = get_generator(seed, "cpu")
-        latentsA = self.prepare_image_latents(tensor_A, generator)
-        latentsB = self.prepare_image_latents(tensor_B, generator)
-        noiseA = torch.randn(latentsA.shape, generator=generator, dtype=self.noise_dtype).float()
-        noiseB = torch.randn(latentsB.shape, generator=generator, dtype=self.noise_dtype).float()
+        (latentsA, latentsB), noiseA, noiseB = path_latents(self, [(image_A, image_B)], (0, 1), img_size, seed, 1, hip_vae=False)
         ctx, pooled = self._encode_prompt(prompt)
-        return latentsA.float(), latentsB.float(), noiseA, noiseB, ctx, pooled
+        return latentsA, latentsB, noiseA, noiseB, ctx, pooled
 
     @torch.no_grad()
     def similarity_maps(self, image_A, image_B, img_size, prompt, target_block, target_layer, target_step, similarity, seed):

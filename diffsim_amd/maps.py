@@ -18,10 +18,8 @@ from typing import Optional, Sequence, Tuple
 import torch
 import torch.nn.functional as F
 
-from .diffsim import get_generator
-from .engine import image_preprocess, latent_sample, pair_score_maps
-from .harness import _Adapter, _prepare, _shared_pool
-from .image import DecodePool, load_image, process_image
+from .engine import pair_score_maps
+from .inputs import _Adapter, path_latents, stack_rows
 
 
 def grid_shape(n_tokens: int) -> Tuple[int, int]:
@@ -79,7 +77,6 @@ def score_latent_pair_maps(scorer, latA, latB, noiseA, noiseB, prompt, target_bl
     ad = _Adapter(scorer)
     dev = scorer.device
     n = latA.shape[0]
-    shp = latA.shape[1:]
     latA, latB = latA.to(dev, torch.float32), latB.to(dev, torch.float32)
     noiseA, noiseB = noiseA.to(dev, torch.float32), noiseB.to(dev, torch.float32)
     eng = ad.engine(target_block, target_layer)
@@ -93,13 +90,8 @@ def score_latent_pair_maps(scorer, latA, latB, noiseA, noiseB, prompt, target_bl
     score = local = contrib = None
     for i0 in range(0, n, batch_pairs):
         i1 = min(n, i0 + batch_pairs)
-        m = i1 - i0
-        lat = torch.stack([latA[i0:i1], latB[i0:i1]], dim=1).reshape(2 * m, *shp)
-        nA = noiseA[i0:i1] if (noiseA.shape[0] == n and n > 1) else noiseA.expand(m, *shp)
-        nB = noiseB[i0:i1] if (noiseB.shape[0] == n and n > 1) else noiseB.expand(m, *shp)
-        nz = torch.stack([nA, nB], dim=1).reshape(2 * m, *shp)
-        q, k, v = feats(lat, nz)
-        ia = torch.arange(0, 2 * m, 2, dtype=torch.int32, device=dev)
+        q, k, v = feats(*stack_rows([latA, latB], [noiseA, noiseB], i0, i1))
+        ia = torch.arange(0, 2 * (i1 - i0), 2, dtype=torch.int32, device=dev)
         s, lo, co = pair_score_maps(q, k, v, ia, ia + 1, heads, similarity)
         if score is None:
             N = lo.shape[2]
@@ -112,52 +104,6 @@ def score_latent_pair_maps(scorer, latA, latB, noiseA, noiseB, prompt, target_bl
     return SimilarityMaps(score, local, contrib)
 
 
-def path_pair_latents(scorer, pairs: Sequence[Tuple[str, str]], img_size, seed=2333):
-    """(latA, latB, noiseA, noiseB) of (A, B) path pairs as one reference call per pair would make them (each reseeds: the four
-    draws -- VAE sample A, VAE sample B, noise A, noise B -- are the same tensors for every pair).  The HIP VAE fast path where
-    the scorer has one (images decoded ahead on the host, one encode per chunk), else the scorer's prepare_image_latents."""
-    ad = _Adapter(scorer)
-    if ad.fast:
-        vae = ad.vae
-        sf = vae.config.scaling_factor
-        pool = getattr(scorer, "_decode", None) or _shared_pool()
-        chunk = 16                      # pairs per VAE encode (32 images at 512 px keep its widest activation < 2 GiB)
-        starts = list(range(0, len(pairs), chunk))
-
-        def submit(i0):
-            return pool.submit([p for ab in pairs[i0:i0 + chunk] for p in ab], img_size)
-        pending = [submit(i0) for i0 in starts[:2]]              # decode + resize run two chunks ahead of the GPU
-        draws = None
-        lA, lB = [], []
-        for ci, i0 in enumerate(starts):
-            px = DecodePool.gather(pending.pop(0))
-            if ci + 2 < len(starts):
-                pending.append(submit(starts[ci + 2]))
-            x = image_preprocess(px.to(vae.device, non_blocking=True), ad.image_half)
-            mom = vae.moments(x)
-            if draws is None:
-                g = get_generator(seed, "cpu")
-                shp = (1, mom.shape[1] // 2) + tuple(mom.shape[2:])
-                eA = torch.randn(shp, generator=g, dtype=ad.eps_dtype).float().to(vae.device)
-                eB = torch.randn(shp, generator=g, dtype=ad.eps_dtype).float().to(vae.device)
-                nA = torch.randn(shp, generator=g, dtype=ad.noise_draw).float()
-                nB = torch.randn(shp, generator=g, dtype=ad.noise_draw).float()
-                draws = (eA, eB, nA, nB)
-            lA.append(latent_sample(mom, draws[0], sf, 0, 2, ad.round16))
-            lB.append(latent_sample(mom, draws[1], sf, 1, 2, ad.round16))
-        return torch.cat(lA), torch.cat(lB), draws[2], draws[3]
-    lA, lB = [], []
-    nA = nB = None
-    for pa, pb in pairs:
-        g = get_generator(seed, "cpu")
-        lA.append(_prepare(scorer, ad, process_image(load_image(pa), img_size), g))
-        lB.append(_prepare(scorer, ad, process_image(load_image(pb), img_size), g))
-        if nA is None:
-            nA = torch.randn(lA[-1].shape, generator=g, dtype=ad.noise_draw).float()
-            nB = torch.randn(lB[-1].shape, generator=g, dtype=ad.noise_draw).float()
-    return torch.cat(lA), torch.cat(lB), nA, nB
-
-
 @torch.no_grad()
 def score_path_pair_maps(scorer, pairs: Sequence[Tuple[str, str]], img_size, prompt, target_block="up_blocks", target_layer=0,
                          target_step=600, seed=2333, similarity="cosine", batch_pairs: Optional[int] = None) -> SimilarityMaps:
@@ -165,7 +111,7 @@ def score_path_pair_maps(scorer, pairs: Sequence[Tuple[str, str]], img_size, pro
     each pair's per-token terms on both images' grids."""
     if not pairs:
         raise ValueError("no pairs to map")
-    latA, latB, nA, nB = path_pair_latents(scorer, list(pairs), img_size, seed)
+    (latA, latB), nA, nB = path_latents(scorer, list(pairs), (0, 1), img_size, seed, 16)
     return score_latent_pair_maps(scorer, latA, latB, nA, nB, prompt, target_block, target_layer, target_step, similarity,
                                   batch_pairs)
 

@@ -16,12 +16,11 @@ from typing import List, Optional, Sequence
 
 import torch
 
-from .diffsim import get_generator
-from .engine import image_preprocess, latent_sample, score_matrix, score_matrix_workspace_bytes
-from .harness import _Adapter, _prepare, _shared_pool
-from .image import DecodePool, load_image, process_image
+from .engine import score_matrix, score_matrix_workspace_bytes
+from .inputs import _Adapter, path_latents, stack_rows
 
 IMAGE_EXTS = (".png", ".jpg", ".jpeg")
+ENCODE_CHUNK = 16               # images per VAE encode, per side (32 at 512 px keep its widest activation < 2 GiB)
 WORKSPACE_SHARE = 0.25          # of the free HBM, for one score_matrix call's workspace (self outputs + partial sums)
 
 
@@ -37,10 +36,8 @@ def list_images(root: str) -> List[str]:
 def _features(ad: _Adapter, lat, noise, prompt, block, layer, step, batch: int):
     """(q, k, v) of n latents that all sit in one slot (one noise tensor), in engine batches of `batch` images."""
     n = lat.shape[0]
-    parts = []
-    for i0 in range(0, n, batch):
-        m = min(n, i0 + batch) - i0
-        parts.append(ad.features(lat[i0:i0 + m], noise.expand(m, *lat.shape[1:]).contiguous(), prompt, block, layer, step))
+    parts = [ad.features(*stack_rows([lat], [noise], i0, min(n, i0 + batch)), prompt, block, layer, step)
+             for i0 in range(0, n, batch)]
     if len(parts) == 1:
         return tuple(t.contiguous() for t in parts[0])
     return tuple(torch.cat([p[i] for p in parts]) for i in range(3))
@@ -89,64 +86,15 @@ def score_path_matrix(scorer, paths_a: Sequence[str], paths_b: Sequence[str], im
                       target_layer=0, target_step=600, seed=2333, similarity="cosine", batch: Optional[int] = None,
                       return_status: bool = False):
     """The (len(paths_a), len(paths_b)) matrix of ``diffsim(paths_a[i], paths_b[j], ...)`` scores: the query images are
-    encoded with the reseeded generator's slot-A VAE draw and noise, the gallery images with the slot-B ones (the adapter's
-    draw order: VAE sample A, VAE sample B, noise A, noise B).  Through the scorer's HIP VAE fast path where it has one."""
+    encoded with the reseeded generator's slot-A VAE draw and noise, the gallery images with the slot-B ones
+    (``inputs.path_latents``).  Through the scorer's HIP VAE fast path where it has one."""
     if not paths_a or not paths_b:
         empty = torch.empty((len(paths_a), len(paths_b)), dtype=torch.float32, device=scorer.device)
         return (empty, 0) if return_status else empty
-    latA, latB, nA, nB = _path_latents(scorer, paths_a, paths_b, img_size, seed)
+    (latA,), nA, _ = path_latents(scorer, [(p,) for p in paths_a], (0,), img_size, seed, ENCODE_CHUNK)
+    (latB,), _, nB = path_latents(scorer, [(p,) for p in paths_b], (1,), img_size, seed, ENCODE_CHUNK)
     return score_latent_matrix(scorer, latA, latB, nA, nB, prompt, target_block, target_layer, target_step, similarity, batch,
                                return_status)
-
-
-def _path_latents(scorer, paths_a: Sequence[str], paths_b: Sequence[str], img_size, seed=2333):
-    """(latA, latB, noiseA, noiseB) of score_path_matrix: the queries' latents with the slot-A draws, the gallery's with the
-    slot-B ones, and the two noise tensors."""
-    ad = _Adapter(scorer)
-    if ad.fast:
-        vae = ad.vae
-        sf = vae.config.scaling_factor
-        pool = getattr(scorer, "_decode", None) or _shared_pool()
-        draws = None
-        lats = ([], [])
-        chunk = 16                      # images per VAE encode (32 at 512 px keep its widest activation < 2 GiB)
-        for slot, paths in enumerate((paths_a, paths_b)):
-            for i0 in range(0, len(paths), chunk):
-                px = DecodePool.gather(pool.submit(list(paths[i0:i0 + chunk]), img_size))
-                x = image_preprocess(px.to(vae.device, non_blocking=True), ad.image_half)
-                mom = vae.moments(x)
-                if draws is None:
-                    g = get_generator(seed, "cpu")
-                    shp = (1, mom.shape[1] // 2) + tuple(mom.shape[2:])
-                    eA = torch.randn(shp, generator=g, dtype=ad.eps_dtype).float().to(vae.device)
-                    eB = torch.randn(shp, generator=g, dtype=ad.eps_dtype).float().to(vae.device)
-                    nA = torch.randn(shp, generator=g, dtype=ad.noise_draw).float()
-                    nB = torch.randn(shp, generator=g, dtype=ad.noise_draw).float()
-                    draws = (eA, eB, nA, nB)
-                lats[slot].append(latent_sample(mom, draws[slot], sf, 0, 1, ad.round16))
-        latA, latB = torch.cat(lats[0]), torch.cat(lats[1])
-        nA, nB = draws[2], draws[3]
-    else:
-        # no HIP VAE plugged in: the scorer's own prepare_image_latents per image, in the reference's draw order.  Every call
-        # reseeds, so the generator state behind slot A's draw is the same for every pair: it is taken once, behind the first
-        # query's encode, and each gallery image's slot-B draw starts from it
-        la, lb = [], []
-        nA = nB = None
-        after_a = None
-        for p in paths_a:
-            g = get_generator(seed, "cpu")
-            la.append(_prepare(scorer, ad, process_image(load_image(p), img_size), g))
-            if after_a is None:
-                after_a = g.get_state()
-        for p in paths_b:
-            g = torch.Generator("cpu")
-            g.set_state(after_a)
-            lb.append(_prepare(scorer, ad, process_image(load_image(p), img_size), g))
-            if nA is None:
-                nA = torch.randn(lb[-1].shape, generator=g, dtype=ad.noise_draw).float()
-                nB = torch.randn(lb[-1].shape, generator=g, dtype=ad.noise_draw).float()
-        latA, latB = torch.cat(la), torch.cat(lb)
-    return latA, latB, nA, nB
 
 
 def topk(matrix: torch.Tensor, k: int, similarity: str = "cosine"):

@@ -77,3 +77,17 @@ def test_dit_fp8_attention_mode(golden_dir):
     with pytest.raises(_lib.DsimError):                                      # fp32 handles have no fp8 mode
         diffsim_DiT(128, 600, "cuda", dit_config=C.DIT_TINY, state_dict=sd, torch_dtype=torch.float32,
                     fp8_attention=True).score_latent_pairs(zA, zB, nA, nB, 2, 600, "cosine")
+
+
+def test_dit_per_pair_noise_across_chunks():
+    """(n, C, s, s) noise, one per pair, over several engine chunks: each score equals that pair scored alone."""
+    from diffsim_amd.diffsim_dit import diffsim_DiT
+    dd = diffsim_DiT(128, 600, "cuda", dit_config=C.DIT_TINY, state_dict=S.make_state_dict(C.DIT_TINY, seed=0),
+                     torch_dtype=torch.float32)
+    g = torch.Generator().manual_seed(5)
+    latA, latB, nA, nB = (torch.randn(5, 4, 16, 16, generator=g) for _ in range(4))
+    got = dd.score_latent_pairs(latA, latB, nA, nB, 2, 600, "cosine", batch_pairs=2)
+    for i in range(5):
+        want = dd.score_latent_pairs(latA[i:i + 1], latB[i:i + 1], nA[i:i + 1], nB[i:i + 1], 2, 600, "cosine")
+        assert torch.equal(got[i:i + 1], want), i
+    assert not torch.equal(got[0:1], dd.score_latent_pairs(latA[:1], latB[:1], nA[1:2], nB[1:2], 2, 600, "cosine"))
