@@ -49,6 +49,29 @@ class VAECfgC(C.Structure):
     ]
 
 
+class GemmOpC(C.Structure):
+    """dsim_gemm_op (include/diffsim_amd.h)"""
+    _fields_ = [
+        ("mode", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("stride", C.c_int32), ("ups", C.c_int32), ("pad", C.c_int32),
+        ("A0", C.c_void_p), ("C0", C.c_int32), ("A1", C.c_void_p), ("C1", C.c_int32),
+        ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32),
+        ("w", C.c_void_p), ("wb_rows", C.c_int32), ("wb_stride", C.c_uint32),
+        ("bias", C.c_void_p), ("bias2", C.c_void_p), ("rows_per_batch", C.c_int32),
+        ("act", C.c_int32), ("gate", C.c_void_p), ("gate2", C.c_void_p),
+        ("epi", C.c_int32),
+        ("residual", C.c_void_p), ("out", C.c_void_p), ("ldo", C.c_int32),
+        ("out_split", C.c_int32), ("out_split_stride", C.c_int64),
+        ("force_big", C.c_int32),
+        ("gn_part", C.c_void_p), ("gn_hw", C.c_int32),
+        ("dtype", C.c_int32),
+    ]
+
+
+class GemmLaunchC(C.Structure):
+    """dsim_gemm_launch (include/diffsim_amd.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("bm", "bn", "kind", "geglu", "ek", "small")] + [("family", C.c_char * 128)]
+
+
 class DiTCfgC(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("input_size", "patch_size", "in_channels", "hidden_size", "depth", "num_heads",
                                           "mlp_ratio", "num_classes", "freq_dim", "compute_dtype", "tap_layer")]
@@ -116,6 +139,8 @@ SYMBOLS = {
     "dsim_op_attention_fp8": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "dsim_op_ff_fused": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp]),
     "dsim_op_ln_linear": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
+    "dsim_op_gemm": (_i, [C.POINTER(GemmOpC), C.POINTER(GemmLaunchC), _vp]),
+    "dsim_op_groupnorm_pre": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _f, _i, _i, _vp, _i, _vp]),
 }
 
 _lib = None

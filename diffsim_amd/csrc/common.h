@@ -162,6 +162,12 @@ struct GemmArgs {
 #endif
 };
 int launch_gemm(const GemmArgs& a, int dtype, hipStream_t s);
+// The instantiation the calling thread's last GEMM launch ran, written by launch_ek / launch_skinny_t where they launch (one
+// definition, in pack.hip, shared by the bf16 and fp16 objects): what dsim_op_gemm reports, so that tests see the kernel that ran.
+struct GemmLaunchRec {
+    int bm = 0, bn = 0, mode = -1, geglu = 0, ek = -1, small = 0;
+};
+extern thread_local GemmLaunchRec g_gemm_last_launch;
 // Rows per alternating block of a GEGLU-interleaved weight with N packed rows (= 8C): 16 where the 320 / 160-column GEMM tiles
 // divide N (their waves hold 160 or 80 packed rows: five or ten 16-row accumulator tiles, an odd count of 32-row blocks); 32 for
 // the 320-channel blocks, whose weights the fused feed-forward streams (32 x 32 MFMAs), and for widths the 256 / 128-column tiles serve.

@@ -106,12 +106,20 @@ struct DWalk {
         g.zero_page = h->zero_page;
         if (!run) return DSIM_OK;
         if (h->profiling) {
-            int bm, bn;
-            gemm_launch_tile(g, h->dt, &bm, &bn);
             const bool slow = act != 0 || gate != nullptr;      // the tanh-GELU / adaLN-gate epilogue template (gemm.hip EK_SLOW)
-            pbegin(std::string("gemm_") + dtn() + "_" + std::to_string(bm) + "x" + std::to_string(bn) + "_linear" +
-                       (slow ? ((act && !gate && !residual) ? "_act" : "_dit") : (residual ? "_res" : "")) + "|M" + std::to_string(M) + " N" + std::to_string(N) + " K" + std::to_string(K),
-                   2.0 * M * (double)N * K, (double)es() * ((double)M * K + (double)N * K + (double)M * N * (residual ? 2 : 1)));
+            if (slow) {
+                int bm, bn;
+                gemm_launch_tile(g, h->dt, &bm, &bn);
+                pbegin(std::string("gemm_") + dtn() + "_" + std::to_string(bm) + "x" + std::to_string(bn) + "_linear" +
+                           ((act && !gate && !residual) ? "_act" : "_dit") + "|M" + std::to_string(M) + " N" + std::to_string(N) + " K" + std::to_string(K),
+                       2.0 * M * (double)N * K, (double)es() * ((double)M * K + (double)N * K + (double)M * N * (residual ? 2 : 1)));
+            } else {
+                // plain / residual projections: gemm_family() names the kernel, the small-batch one included (the qkv projection of
+                // one image, 512 x 3456 x 1152, runs on it)
+                double fl, by;
+                const std::string nm = gemm_family(g, h->dt, &fl, &by);
+                pbegin(nm, fl, by);
+            }
         }
         const int st = launch_gemm(g, h->dt, s);
         pend();

@@ -975,6 +975,7 @@ int launch_ek(const GemmArgs& a, hipStream_t s) {
 #endif
     hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), LDS, s, g, tilesN, ntiles, tilesM, gn);
     DSIM_HIP_CHECK(hipGetLastError());
+    g_gemm_last_launch = GemmLaunchRec{BM, BN, MODE, GEGLU ? 1 : 0, EK, 0};
     return DSIM_OK;
 }
 

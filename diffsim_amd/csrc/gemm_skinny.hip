@@ -207,6 +207,7 @@ int launch_skinny_t(const GemmArgs& g, hipStream_t s) {
     const int tilesM = (g.M + SBM - 1) / SBM, tilesN = (g.N + SBN - 1) / SBN;
     hipLaunchKernelGGL(kern, dim3(tilesM * tilesN), dim3(SNW * 64), LDS, s, g, tilesN);
     DSIM_HIP_CHECK(hipGetLastError());
+    g_gemm_last_launch = GemmLaunchRec{SBM, SBN, MODE, 0, RES ? 1 : 0, 1};      // (gemm.hip EK_RES / EK_PLAIN)
     return DSIM_OK;
 }
 

@@ -4,6 +4,9 @@
 #include "common.h"
 
 namespace dsim {
+
+thread_local GemmLaunchRec g_gemm_last_launch;      // (common.h: written by gemm.hip / gemm_skinny.hip at each launch)
+
 namespace {
 
 __device__ __forceinline__ float ld_any(const void* p, int dt, size_t i) {

@@ -14,6 +14,7 @@
 // planner can never disagree with the executor.  Activations are token-major [B][HW][C] in the
 // compute dtype; the workspace is a caller-provided arena with stack discipline.
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 #include <map>
 #include <string>
@@ -931,6 +932,87 @@ int dsim_op_conv3x3(const void* x, const float* w, const float* bias, const void
     g.M = B * g.Hout * g.Wout; g.N = Cout; g.K = 9 * Cin; g.W = wp; g.bias = bias;
     g.epi = residual ? EPI_RESIDUAL : EPI_NONE; g.residual = residual; g.out = out; g.ldo = Cout; g.zero_page = zp;
     CK(launch_gemm(g, dtype, s));
+    DSIM_HIP_CHECK(hipStreamSynchronize(s));
+    return DSIM_OK;
+}
+
+int dsim_op_gemm(const dsim_gemm_op* op, dsim_gemm_launch* launched, void* stream) {
+    if (!op || !launched || !op->A0 || !op->w || !op->out) return DSIM_ERR_INVALID;
+    const int dt = op->dtype;
+    if ((dt != DSIM_F32 && dt != DSIM_BF16 && dt != DSIM_F16) || (op->mode != GEMM_LINEAR && op->mode != GEMM_CONV3)) return DSIM_ERR_INVALID;
+    if (op->M <= 0 || op->N <= 0 || op->K <= 0 || op->wb_rows < 0) return DSIM_ERR_INVALID;
+    if ((op->bias2 || op->gate2) && op->rows_per_batch <= 0) return DSIM_ERR_INVALID;
+    if ((op->bias2 && !op->bias) || (op->gate2 && !op->gate)) return DSIM_ERR_INVALID;      // the odd rows' vector replaces the even rows'
+    {
+        // rows are ldo elements apart: at least the columns one output tensor receives
+        const int ncol = op->epi == EPI_GEGLU ? op->N / 2 : op->N;
+        if (op->ldo < (op->out_split > 0 ? op->out_split : ncol)) return DSIM_ERR_INVALID;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const size_t es = dtype_size(dt);
+    const bool geglu = op->epi == EPI_GEGLU;
+    GemmArgs g;
+    g.A0 = op->A0; g.C0 = op->C0; g.A1 = op->A1; g.C1 = op->A1 ? op->C1 : 0;
+    g.mode = op->mode; g.M = op->M; g.N = op->N; g.K = op->K;
+    if (op->mode == GEMM_CONV3) {
+        if (op->pad != 0 && op->pad != 1) return DSIM_ERR_INVALID;
+        if (op->pad == 0 && (op->stride != 2 || op->ups)) return DSIM_ERR_INVALID;      // the VAE downsample's form only
+        g.Hin = op->H; g.Win = op->W; g.stride = op->stride; g.ups = op->ups ? 1 : 0; g.pad = op->pad;
+        // stride 2: ceil(H / 2) rows with padding 1, H / 2 with the right / bottom padding of the VAE (pad 0)
+        g.Hout = op->ups ? 2 * op->H : (op->stride == 2 ? (op->pad ? (op->H + 1) / 2 : op->H / 2) : op->H);
+        g.Wout = op->ups ? 2 * op->W : (op->stride == 2 ? (op->pad ? (op->W + 1) / 2 : op->W / 2) : op->W);
+        if (g.Hout <= 0 || g.Wout <= 0 || op->M % (g.Hout * g.Wout)) return DSIM_ERR_INVALID;
+    }
+    const int gblk = geglu ? geglu_block_rows(op->N) : 0;
+    const int nmat = op->wb_rows > 0 ? op->M / op->wb_rows : 1;
+    const size_t wmat = (size_t)op->N * op->K * es;
+    if (op->wb_rows > 0 && (op->M % op->wb_rows || op->wb_stride % 16 || (size_t)op->wb_stride < wmat)) return DSIM_ERR_INVALID;
+    Tmp t;
+    void* wp = t.get(op->wb_rows > 0 ? (size_t)(nmat - 1) * op->wb_stride + wmat : wmat);
+    float* bp = op->bias ? (float*)t.get((size_t)op->N * 4) : nullptr;
+    float* b2p = op->bias2 ? (float*)t.get((size_t)op->N * 4) : nullptr;
+    void* zp = t.get(256);
+    if (!wp || !zp || (op->bias && !bp) || (op->bias2 && !b2p)) return DSIM_ERR_HIP;
+    DSIM_HIP_CHECK(hipMemsetAsync(zp, 0, 256, s));
+    if (op->mode == GEMM_CONV3) {
+        CK(pack_conv3(op->w, DSIM_F32, wp, dt, op->N, op->C0, s));
+    } else {
+        for (int i = 0; i < nmat; ++i)
+            CK(pack_linear(op->w + (size_t)i * op->N * op->K, DSIM_F32, (char*)wp + (size_t)i * op->wb_stride, dt, op->N, op->K, gblk, s));
+    }
+    if (op->bias) CK(pack_vector(op->bias, DSIM_F32, bp, op->N, gblk, s));
+    if (op->bias2) CK(pack_vector(op->bias2, DSIM_F32, b2p, op->N, gblk, s));
+    g.W = wp; g.bias = bp; g.bias2 = b2p; g.rows_per_batch = op->rows_per_batch;
+    g.act = op->act; g.gate = op->gate; g.gate2 = op->gate2;
+    g.epi = op->epi;
+    if (geglu) g.geglu_blk = gblk;
+    g.residual = op->residual; g.out = op->out; g.ldo = op->ldo;
+    g.out_split = op->out_split; g.out_split_stride = op->out_split_stride;
+    g.force_big = op->force_big;
+    g.wb_rows = op->wb_rows; g.wb_stride = op->wb_rows > 0 ? op->wb_stride : 0;
+    g.gn_part = op->gn_part; g.gn_hw = op->gn_hw;
+    g.zero_page = zp;
+    double fl = 0, by = 0;
+    const std::string fam = gemm_family(g, dt, &fl, &by);
+    g_gemm_last_launch = GemmLaunchRec{};
+    CK(launch_gemm(g, dt, s));
+    DSIM_HIP_CHECK(hipStreamSynchronize(s));
+    const GemmLaunchRec& r = g_gemm_last_launch;
+    launched->bm = r.bm; launched->bn = r.bn; launched->kind = r.mode; launched->geglu = r.geglu; launched->ek = r.ek;
+    launched->small = r.small;
+    std::snprintf(launched->family, sizeof(launched->family), "%s", fam.c_str());
+    return DSIM_OK;
+}
+
+int dsim_op_groupnorm_pre(const void* x, int C, const float* gamma, const float* beta, void* out, int B, int HW, int groups,
+                          float eps, int silu, int dtype, const float* part32, int chunks, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (!x || !gamma || !beta || !out || !part32 || B <= 0 || HW <= 0 || groups <= 0 || C % groups) return DSIM_ERR_INVALID;
+    if (chunks < 1 || (long)chunks * 64 != HW) return DSIM_ERR_INVALID;        // one partial per 64 rows of each image (gn_part's layout)
+    Tmp t;
+    void* sc = t.get(groupnorm_scratch_bytes(B, groups));
+    if (!sc) return DSIM_ERR_HIP;
+    CK(launch_groupnorm_pre(x, C, gamma, beta, out, B, HW, groups, eps, silu, dtype, sc, part32, chunks, s));
     DSIM_HIP_CHECK(hipStreamSynchronize(s));
     return DSIM_OK;
 }

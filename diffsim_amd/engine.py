@@ -491,6 +491,101 @@ def op_conv3x3(x, w, bias=None, residual=None, stride=1, upsample=False):
     return out
 
 
+_GEMM_EPI = {"none": 0, "residual": 1, "geglu": 2}
+_GEMM_EK = ("plain", "residual", "dit", "act", "plain_gn", "residual_gn")
+
+
+def op_gemm(a0, w, out, *, a1=None, conv=None, bias=None, bias2=None, rows_per_batch=0, act=0, gate=None, gate2=None,
+            epi="none", residual=None, ldo=None, out_split=0, out_split_stride=0, force_big=False, wb_rows=0, wb_stride=0,
+            gn_part=None, gn_hw=0):
+    """The implicit GEMM with its whole epilogue surface as one operator (dsim_op_gemm).  Returns the launch record: the
+    instantiation that ran (bm, bn, kind "linear" / "conv3" / "conv3p", geglu, ek, small) and gemm_family()'s name for it.
+
+    linear: a0 [M][C0] (a1 [M][C1]: the K concatenation), w f32 [N][K] ([M / wb_rows][N][K] with wb_rows);
+    conv:   a0 [B][H][W][C0], conv = dict(stride=1|2, ups=0|1, pad=1|0), w f32 [N][C0][3][3].
+    N counts weight rows (GEGLU: [h ; g], 2 x the output columns).  out / residual: tensors of the compute dtype whose storage
+    holds M rows of ldo elements (out_split: N / out_split such outputs, out_split_stride BYTES apart, from out's first element).
+    bias / bias2 / gate / gate2: f32 [N] (gate: [output columns]); gn_part: f32 [M / gn_hw][gn_hw / 64][N / 4][2]."""
+    L = _lib.lib()
+    _require_cuda(a0, a1, w, out, bias, bias2, gate, gate2, residual, gn_part)
+    if a0.dtype not in _TORCH2DSIM:
+        raise _lib.DsimError("a0 must be float32, bfloat16 or float16")
+    dt = a0.dtype
+    for t, nm in ((a1, "a1"), (out, "out"), (residual, "residual")):
+        if t is not None and t.dtype != dt:
+            raise _lib.DsimError(f"{nm} must have a0's dtype {dt}")
+    for t, nm in ((w, "w"), (bias, "bias"), (bias2, "bias2"), (gate, "gate"), (gate2, "gate2"), (gn_part, "gn_part")):
+        if t is not None and t.dtype != torch.float32:
+            raise _lib.DsimError(f"{nm} must be float32")
+    if epi not in _GEMM_EPI:
+        raise ValueError(epi)
+    op = _lib.GemmOpC()
+    if conv is None:
+        if a0.ndim != 2 or (a1 is not None and (a1.ndim != 2 or a1.shape[0] != a0.shape[0])):
+            raise _lib.DsimError("linear: a0 [M][C0], a1 [M][C1]")
+        M, C0 = a0.shape
+        C1 = 0 if a1 is None else a1.shape[1]
+        K = C0 + C1
+        if w.shape[-1] != K or w.ndim != (3 if wb_rows else 2) or (wb_rows and w.shape[0] * wb_rows != M):
+            raise _lib.DsimError("linear: w must be [N][K] (with wb_rows: [M / wb_rows][N][K])")
+        N = w.shape[-2]
+        op.mode = 0
+    else:
+        if a0.ndim != 4 or a1 is not None or wb_rows or w.ndim != 4 or w.shape[1:] != (a0.shape[3], 3, 3):
+            raise _lib.DsimError("conv: a0 [B][H][W][C0], w [N][C0][3][3], no a1 / wb_rows")
+        B, H, W, C0 = a0.shape
+        stride, ups, pad = int(conv.get("stride", 1)), int(conv.get("ups", 0)), int(conv.get("pad", 1))
+        Ho = 2 * H if ups else ((H + 1) // 2 if pad else H // 2) if stride == 2 else H
+        Wo = 2 * W if ups else ((W + 1) // 2 if pad else W // 2) if stride == 2 else W
+        M, N, K, C1 = B * Ho * Wo, w.shape[0], 9 * C0, 0
+        op.mode, op.H, op.W, op.stride, op.ups, op.pad = 1, H, W, stride, ups, pad
+    ncol = N // 2 if epi == "geglu" else N
+    ldo = ncol if ldo is None else int(ldo)
+    es = out.element_size()
+    nout = N // out_split if out_split else 1
+    need = (nout - 1) * int(out_split_stride) + M * ldo * es
+    if ldo < (out_split or ncol) or out.numel() * es < need:
+        raise _lib.DsimError(f"out holds {out.numel() * es} bytes, the launch writes up to {need}")
+    if residual is not None and residual.numel() < M * ldo:
+        raise _lib.DsimError("residual must hold M rows of ldo elements")
+    for t, nm, n in ((bias, "bias", N), (bias2, "bias2", N), (gate, "gate", ncol), (gate2, "gate2", ncol)):
+        if t is not None and t.numel() != n:
+            raise _lib.DsimError(f"{nm} must have {n} elements")
+    if gn_part is not None and (gn_hw <= 0 or M % gn_hw or gn_part.numel() != (M // gn_hw) * (gn_hw // 64) * (N // 4) * 2):
+        raise _lib.DsimError("gn_part must be f32 [M / gn_hw][gn_hw / 64][N / 4][2]")
+    op.A0, op.C0, op.A1, op.C1 = a0.data_ptr(), C0, _ptr(a1), C1
+    op.M, op.N, op.K = M, N, K
+    op.w, op.wb_rows, op.wb_stride = w.data_ptr(), int(wb_rows), int(wb_stride)
+    op.bias, op.bias2, op.rows_per_batch = _ptr(bias), _ptr(bias2), int(rows_per_batch)
+    op.act, op.gate, op.gate2 = int(act), _ptr(gate), _ptr(gate2)
+    op.epi, op.residual, op.out, op.ldo = _GEMM_EPI[epi], _ptr(residual), out.data_ptr(), ldo
+    op.out_split, op.out_split_stride, op.force_big = int(out_split), int(out_split_stride), int(bool(force_big))
+    op.gn_part, op.gn_hw, op.dtype = _ptr(gn_part), int(gn_hw), _TORCH2DSIM[dt]
+    rec = _lib.GemmLaunchC()
+    with torch.cuda.device(a0.device):
+        _lib.check(L.dsim_op_gemm(C.byref(op), C.byref(rec), _stream_ptr()), "op_gemm")
+    return {"bm": rec.bm, "bn": rec.bn, "kind": ("linear", "conv3", "conv3p")[rec.kind], "geglu": bool(rec.geglu),
+            "ek": _GEMM_EK[rec.ek], "small": bool(rec.small), "family": rec.family.decode()}
+
+
+def op_groupnorm_pre(x, gamma, beta, groups, eps, silu, part32, chunks):
+    """GroupNorm (+ SiLU) of x [B][HW][C] with its statistics from a conv epilogue's gn_part (part32 f32 [B][chunks][C / 4][2])."""
+    L = _lib.lib()
+    _require_cuda(x, gamma, beta, part32)
+    if x.dtype not in (torch.bfloat16, torch.float16):
+        raise _lib.DsimError("op_groupnorm_pre takes a 16-bit input (the statistics epilogue is 16-bit only)")
+    B, HW, Cc = x.shape
+    if part32.dtype != torch.float32 or part32.numel() != B * chunks * (Cc // 4) * 2:
+        raise _lib.DsimError("part32 must be f32 [B][chunks][C / 4][2]")
+    if gamma.numel() != Cc or beta.numel() != Cc:
+        raise _lib.DsimError("gamma / beta must have C elements")
+    out = torch.empty_like(x)
+    _lib.check(L.dsim_op_groupnorm_pre(x.data_ptr(), Cc, gamma.data_ptr(), beta.data_ptr(), out.data_ptr(), B, HW, groups, float(eps),
+                                       int(silu), _TORCH2DSIM[x.dtype], part32.data_ptr(), int(chunks), _stream_ptr()),
+               "op_groupnorm_pre")
+    return out
+
+
 def op_groupnorm(x0, x1, gamma, beta, groups, eps, silu):
     """x0: [B][HW][C0], x1: optional [B][HW][C1] (channel concat)."""
     L = _lib.lib()

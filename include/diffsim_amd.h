@@ -350,6 +350,52 @@ int dsim_op_ff_fused(const void* x, const float* ln_gamma, const float* ln_beta,
 int dsim_op_ln_linear(const void* x, const float* ln_gamma, const float* ln_beta, const float* w, void* out, int M, int C,
                       int N, float eps, void* stream);
 
+/* The implicit GEMM with every epilogue field the engines use, as one operator (parity tests of each tile and epilogue).
+ *   out[m][n] = epi(sum_k A(m,k) W[n][k] + bias[n]); the A0 | A1 channel concatenation along K (linear), or the 3x3 conv of
+ *   the [M / (Hout Wout)][H][W][C0] image A0 (stride 1 | 2, ups: nearest 2x upsample folded in, pad 0: the VAE downsample's
+ *   F.pad(x, (0, 1, 0, 1)) then no padding).  N counts WEIGHT rows: 2 x the output columns for GEGLU.
+ *   w: diffusers-layout f32 -- linear [N][K] (GEGLU rows [h ; g]), conv [N][C0][3][3]; wb_rows > 0 (linear): [M / wb_rows][N][K],
+ *      matrix i multiplying rows [i wb_rows, (i + 1) wb_rows), packed wb_stride bytes apart (>= N K x element size, % 16 == 0).
+ *   bias / bias2: [N] f32 (bias2, which needs bias, for the rows with odd m / rows_per_batch > 0); act 1: tanh-GELU; gate / gate2:
+ *      f32 scales of the output columns before the residual add (gate2, which needs gate: odd m / rows_per_batch).
+ *   epi: 0 none, 1 residual ([M][ldo] in dtype), 2 GEGLU (out = h * gelu(g)).
+ *   out: [M][ldo] in dtype, ldo >= the output columns (out_split > 0: >= out_split, column run j going to out + j out_split_stride
+ *      bytes); DSIM_ERR_INVALID otherwise.
+ *   gn_part (16-bit power-of-two 3x3 convs on the 256 x 128 / 256 x 256 / 512 x 128 tiles): [M / gn_hw][gn_hw / 64][N / 4][2] f32
+ *      (sum, sum of squares) of the stored output per (64 rows, 4-channel quad).
+ * launched receives the instantiation that ran (recorded where it was launched) and family the profile name gemm_family() gives
+ * the same arguments.  Allocates and synchronises. */
+typedef struct dsim_gemm_op {
+    int mode;                                   /* 0 linear, 1 3x3 conv */
+    int H, W, stride, ups, pad;                 /* conv: stored input map, stride 1 | 2, upsample 0 | 1, pad 1 | 0 */
+    const void* A0; int C0;
+    const void* A1; int C1;
+    int M, N, K;
+    const float* w;
+    int wb_rows; unsigned wb_stride;
+    const float* bias; const float* bias2; int rows_per_batch;
+    int act; const float* gate; const float* gate2;
+    int epi;
+    const void* residual; void* out; int ldo;
+    int out_split; long long out_split_stride;
+    int force_big;
+    float* gn_part; int gn_hw;
+    int dtype;
+} dsim_gemm_op;
+typedef struct dsim_gemm_launch {
+    int bm, bn;
+    int kind;                                   /* 0 linear, 1 conv3, 2 conv3p (power-of-two output maps) */
+    int geglu;
+    int ek;                                     /* 0 plain, 1 residual, 2 DiT gate, 3 tanh-GELU only, 4 / 5 plain / residual + GN statistics */
+    int small;                                  /* 1: the small-batch kernel */
+    char family[128];                           /* gemm_family() of the same arguments */
+} dsim_gemm_launch;
+int dsim_op_gemm(const dsim_gemm_op* op, dsim_gemm_launch* launched, void* stream);
+/* GroupNorm (+ SiLU) of x [B][HW][C] whose statistics come from a conv epilogue's gn_part (part32, chunks = HW / 64 per image: any
+ * other count is DSIM_ERR_INVALID) */
+int dsim_op_groupnorm_pre(const void* x, int C, const float* gamma, const float* beta, void* out, int B, int HW, int groups,
+                          float eps, int silu, int dtype, const float* part32, int chunks, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -37,6 +37,12 @@ def _close(got, want, dtype, scale=None):
     assert torch.isfinite(got).all()
 
 
+def _f64(got, a0, w, dtype, **kw):
+    """beside _close: every element within tests/_gemm64.py's float64 bound (a0 the CPU operand, w / bias the f32 values)"""
+    from tests import _gemm64 as G
+    G.Gemm64(a0.to(dtype), w, dtype, **kw).check(got.float().cpu().reshape(-1, got.shape[-1]), "float64 bound")
+
+
 @pytest.fixture(scope="module")
 def eng():
     from diffsim_amd import engine
@@ -55,9 +61,11 @@ def test_linear(eng, dtype, M, N, K):
     want = F.linear(_q(x, dtype), _q(w, dtype), b)
     got = eng.op_linear(_dev(x, dtype), _dev(w), _dev(b))
     _close(got, want, dtype)
+    _f64(got, x, w, dtype, bias=b)
     want2 = want - b + _q(r, dtype)
     got2 = eng.op_linear(_dev(x, dtype), _dev(w), None, _dev(r, dtype))
     _close(got2, want2, dtype)
+    _f64(got2, x, w, dtype, residual=r.to(dtype))
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -73,6 +81,7 @@ def test_linear_geglu(eng, dtype, M, C):
     got = eng.op_linear(_dev(x, dtype), _dev(w), _dev(b), None, geglu=True)
     assert got.shape == (M, 4 * C)
     _close(got, want, dtype)
+    _f64(got, x, w, dtype, bias=b, epi="geglu")
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -93,9 +102,12 @@ def test_conv3x3(eng, dtype, B, H, W, Cin, Cout, stride, ups):
     r = torch.randn(want.shape, generator=g)
     got = eng.op_conv3x3(_dev(x.permute(0, 2, 3, 1), dtype), _dev(w), _dev(b), None, stride, ups)
     _close(got.float().cpu().permute(0, 3, 1, 2), want, dtype)
+    cv = dict(stride=stride, ups=int(ups))
+    _f64(got, x.permute(0, 2, 3, 1).contiguous(), w, dtype, conv=cv, bias=b)
     got2 = eng.op_conv3x3(_dev(x.permute(0, 2, 3, 1), dtype), _dev(w), _dev(b), _dev(r.permute(0, 2, 3, 1), dtype),
                           stride, ups)
     _close(got2.float().cpu().permute(0, 3, 1, 2), want + _q(r, dtype), dtype)
+    _f64(got2, x.permute(0, 2, 3, 1).contiguous(), w, dtype, conv=cv, bias=b, residual=r.permute(0, 2, 3, 1).to(dtype))
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -252,6 +264,8 @@ def test_linear_many_tiles_per_workgroup(eng, dtype, M, N, K, res):
     want = F.linear(_q(x[rows], dtype), _q(w, dtype), b) + (_q(r[rows], dtype) if res else 0)
     _close(got[rows], want, dtype)
     assert torch.isfinite(got).all()
+    from tests import _gemm64 as G
+    G.Gemm64(x.to(dtype), w, dtype, bias=b, residual=r.to(dtype) if res else None, rows=rows).check(got[rows], "float64 bound")
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -268,6 +282,7 @@ def test_conv3x3_many_tiles_per_workgroup(eng, dtype):
     want = F.conv2d(_q(x[sel], dtype).permute(0, 3, 1, 2), _q(w, dtype), b, padding=1).permute(0, 2, 3, 1) + _q(r[sel], dtype)
     _close(got[sel], want, dtype)
     assert torch.isfinite(got).all()
+    _f64(got[sel], x[sel], w, dtype, conv={}, bias=b, residual=r[sel].to(dtype))
 
 
 # ---- fp8 (e4m3) MFMA attention: the DiT mode of BASELINE config 5 ---------------------------------------------------
@@ -333,6 +348,7 @@ def test_conv3x3_vae_width_many_tiles(eng, dtype):
     want = F.conv2d(_q(x[sel], dtype).permute(0, 3, 1, 2), _q(w, dtype), b, padding=1).permute(0, 2, 3, 1) + _q(r[sel], dtype)
     _close(got[sel], want, dtype)
     assert torch.isfinite(got).all()
+    _f64(got[sel], x[sel], w, dtype, conv={}, bias=b, residual=r[sel].to(dtype))
 
 
 def test_linear_randomized_shapes(eng):
@@ -354,6 +370,7 @@ def test_linear_randomized_shapes(eng):
         got = eng.op_linear(_dev(x, dtype), _dev(w), _dev(b) if use_bias else None, _dev(r, dtype) if use_res else None)
         try:
             _close(got, want, dtype)
+            _f64(got, x, w, dtype, bias=b, residual=r.to(dtype) if use_res else None)
         except AssertionError as e:
             raise AssertionError(f"case {case}: M={M} N={N} K={K} bias={use_bias} res={use_res} {dtype}: {e}")
 
@@ -382,6 +399,8 @@ def test_conv3x3_randomized_shapes(eng):
         got = eng.op_conv3x3(_dev(x.permute(0, 2, 3, 1), dtype), _dev(w), _dev(b), _dev(r.permute(0, 2, 3, 1), dtype), stride, ups)
         try:
             _close(got.float().cpu().permute(0, 3, 1, 2), want + _q(r, dtype), dtype)
+            _f64(got, x.permute(0, 2, 3, 1).contiguous(), w, dtype, conv=dict(stride=stride, ups=int(ups)), bias=b,
+                 residual=r.permute(0, 2, 3, 1).to(dtype))
         except AssertionError as e:
             raise AssertionError(f"case {case}: B={B} H={H} W={W} Cin={Cin} Cout={Cout} stride={stride} ups={ups} {dtype}: {e}")
 
