@@ -72,6 +72,11 @@ class GemmLaunchC(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("bm", "bn", "kind", "geglu", "ek", "small")] + [("family", C.c_char * 128)]
 
 
+class TapC(C.Structure):
+    """dsim_tap (include/diffsim_amd.h): one tap of a sweep, the dsim_unet_cfg fields of the same names"""
+    _fields_ = [(n, C.c_int32) for n in ("block", "layer", "attn", "tfm")]
+
+
 class DiTCfgC(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("input_size", "patch_size", "in_channels", "hidden_size", "depth", "num_heads",
                                           "mlp_ratio", "num_classes", "freq_dim", "compute_dtype", "tap_layer")]
@@ -94,6 +99,10 @@ SYMBOLS = {
     "dsim_unet_qkv": (_i, [_vp, _vp, _vp, _f, _f, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dsim_unet_tap_shape": (_i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "dsim_unet_set_tap": (_i, [_vp, _i, _i, _i, _i]),
+    "dsim_unet_tap_shape_at": (_i, [_vp, C.POINTER(TapC), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
+    "dsim_unet_taps_workspace_bytes": (_sz, [_vp, _i, _i, C.POINTER(TapC)]),
+    "dsim_unet_qkv_taps": (_i, [_vp, _vp, _vp, _f, _f, _vp, _i, _i, C.POINTER(TapC), C.POINTER(_vp), C.POINTER(_vp),
+                                C.POINTER(_vp), _vp, _sz, _vp]),
     "dsim_unet_set_sample_size": (_i, [_vp, _i]),
     "dsim_unet_set_cfg_dedup": (_i, [_vp, _i]),
     "dsim_unet_set_fusion": (_i, [_vp, _i]),
@@ -124,6 +133,9 @@ SYMBOLS = {
     "dsim_dit_profile_get": (_i, [_vp, _i, C.c_char_p, _i, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "dsim_dit_workspace_bytes": (_sz, [_vp, _i]),
     "dsim_dit_qkv": (_i, [_vp, _vp, _vp, _f, _f, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dsim_dit_taps_workspace_bytes": (_sz, [_vp, _i, _i, C.POINTER(_i)]),
+    "dsim_dit_qkv_taps": (_i, [_vp, _vp, _vp, _f, _f, _i, _i, C.POINTER(_i), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _vp,
+                               _sz, _vp]),
     "dsim_pair_score_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "dsim_pair_score": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "dsim_pair_score_status": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),

@@ -51,6 +51,12 @@ def build_parser() -> argparse.ArgumentParser:
                    help="--dataset retrieval: beside each ranking .txt also write <name>.npz with the similarity maps of the query "
                         "against its top-k gallery images (gallery, score (k,), local and contrib (k, 2, h, w): direction 0 on the "
                         "query's token grid, 1 on the gallery image's)")
+    p.add_argument("--taps", type=str, nargs="+", default=None, metavar="SPEC",
+                   help="--dataset cute|nights|sref: score every tap from one forward per image batch instead of the one "
+                        "--target_block / --target_layer tap (which it overrides), and print one section per tap, in the given "
+                        "order, as a one-tap run prints it.  SPEC: diffsim up_blocks:0, down_blocks:2, mid_blocks:0; diffsim_xl "
+                        "up_blocks:0,1,9 (block, attention, transformer block), mid_blocks:0,5; dit blocks:13.  Layers are "
+                        "explicit (no coercion of a single value to 0).  `all`: every tap the model can name")
     p.add_argument("--experiments", type=int, default=2000, help="--dataset sref: sampled experiments (style_main.py:64)")
     p.add_argument("--model_path", type=str, default=None, help="diffusers-layout checkpoint directory (unet/, vae/, text_encoder/, tokenizer/)")
     p.add_argument("--dtype", type=str, choices=["bf16", "fp16", "fp32"], default="bf16",
@@ -79,6 +85,15 @@ def build_parser() -> argparse.ArgumentParser:
 def arg_parse(argv=None):
     p = build_parser()
     args = p.parse_args(argv)
+    if args.taps is not None:
+        if args.dataset == "retrieval" or args.save_maps:
+            p.error("--taps sweeps the triplet benchmarks (--dataset cute, nights or sref): score matrices and similarity maps "
+                    "(--dataset retrieval, --save_maps) take one tap, --target_block / --target_layer")
+        from .sweep import parse_tap_specs
+        try:
+            parse_tap_specs(args.taps, args.metric)
+        except ValueError as e:
+            p.error(f"--taps: {e}")
     if args.save_maps and args.dataset != "retrieval":
         p.error("--save_maps writes the maps of the retrieval rankings: it needs --dataset retrieval")
     return args
@@ -195,6 +210,61 @@ def _selftest_scores(trip, rank, world):
     return s_ab, s_ac, 0
 
 
+def _selftest_scores_taps(trip, rank, world, n_taps):
+    """--selftest_shard --taps: _selftest_scores per tap (a deterministic function of the file names and the tap's position),
+    the same shard, one pair of gathers per tap."""
+    import torch
+    from . import parallel as P
+
+    def fake(a, b, t):
+        s = ((sum(map(ord, os.path.basename(a))) * 31 + sum(map(ord, os.path.basename(b))) * 17) % 997) / 997.0
+        return 1.0 - s if t % 2 else s          # odd taps rank the other way: each tap's section shows its own gathered scores
+    mine = P.shard_triplets(len(trip), rank, world)
+    s_ab, s_ac = [], []
+    for t in range(n_taps):
+        loc_ab = torch.tensor([fake(trip[j][0], trip[j][1], t) for j in mine], dtype=torch.float32)
+        loc_ac = torch.tensor([fake(trip[j][0], trip[j][2], t) for j in mine], dtype=torch.float32)
+        s_ab.append(P.gather_scores(loc_ab, len(trip), rank, world))
+        s_ac.append(P.gather_scores(loc_ac, len(trip), rank, world))
+    return torch.stack(s_ab), torch.stack(s_ac), [0] * n_taps
+
+
+def cli_taps(args, scorer):
+    """--taps -> the scorer's taps (``all``: every tap of the scorer's model; the default model of --metric without a scorer)."""
+    from . import config as C
+    from .sweep import parse_tap_specs
+    cfg = getattr(scorer, "cfg", None) or {"diffsim": C.SD15, "diffsim_xl": C.SDXL, "dit": C.DIT_XL2}[args.metric]
+    try:
+        return parse_tap_specs(args.taps, args.metric, cfg)
+    except ValueError as e:
+        raise SystemExit(f"--taps: {e}")
+
+
+def _report(args, trip, rows, s_ab, s_ac, bad):
+    """The result lines of one tap (rank 0)."""
+    from . import harness as H
+    total = len(trip)
+    if bad:
+        print(f"WARNING: {bad} pair score(s) are NaN/inf (counted as wrong, as the reference's comparisons would)")
+    if args.dataset == "nights":
+        acc = H.nights_accuracy(s_ab, s_ac, [r["vote"] for r in rows], args.similarity)
+        print(f"Final validation accuracy: {acc:.2f}%")
+    else:
+        correct, correct2 = cute_counts(s_ab.cpu(), s_ac.cpu(), args.similarity)
+        if total > 0 and args.dataset == "sref":           # style_main.py:186-193
+            print(f"Total comparisons: {total}")
+            print(f"Accuracy: {correct / total * 100:.2f}%")
+            print(f"2x Accuracy: {correct2 / total * 100:.2f}%")
+        elif total > 0:                                     # cute_main.py:216-224
+            print(f"Total comparisons: {total}")
+            print(f"Total {total}; Correct {correct}; Correct 2x {correct2}")
+            print(f"Accuracy: {correct / total * 100}%")
+            print(f"2x Accuracy: {correct2 / total * 100}%")
+        else:
+            print("Total comparisons: 0")
+            print("No valid comparisons were made.")
+
+
 def run(args) -> int:
     import torch
     from . import harness as H
@@ -212,9 +282,11 @@ def run(args) -> int:
     os.environ.setdefault("DSIM_DECODE_PROCS", str(args.decode_procs))      # the scorers' DecodePool default
     scorer = None if args.selftest_shard else build_scorer(args)
     layer = args.target_layer if isinstance(args.target_layer, list) else [args.target_layer]
+    taps = cli_taps(args, scorer) if args.taps else None
     if rank == 0:
         print(f"=========seed {args.seed}=========")
-        print(f"Experiment on {args.target_block}, layer {args.target_layer}, timestep {args.target_step}:")
+        if taps is None:
+            print(f"Experiment on {args.target_block}, layer {args.target_layer}, timestep {args.target_step}:")
     if args.dataset == "retrieval":
         return run_retrieval(args, scorer, layer)
     if args.dataset == "nights":
@@ -224,32 +296,31 @@ def run(args) -> int:
         trip = sref_triplets(args.image_path, args.seed, args.prompt, args.experiments)
     else:
         trip = cute_triplets(args.image_path, args.seed)
-    if args.selftest_shard:
-        s_ab, s_ac, bad = _selftest_scores(trip, rank, world)
-    else:
-        s_ab, s_ac, bad = H.score_path_triplets(scorer, trip, args.image_size, args.target_block, layer, args.target_step, args.seed,
-                                                args.similarity, rank, world, args.batch, args.unet_batch)
-    if rank == 0:
-        total = len(trip)
-        if bad:
-            print(f"WARNING: {bad} pair score(s) are NaN/inf (counted as wrong, as the reference's comparisons would)")
-        if args.dataset == "nights":
-            acc = H.nights_accuracy(s_ab, s_ac, [r["vote"] for r in rows], args.similarity)
-            print(f"Final validation accuracy: {acc:.2f}%")
+    if args.dataset != "nights":
+        rows = None
+    if taps is not None:
+        # one forward per image batch serves every tap; then one section per tap, as a one-tap run prints it after its banner
+        from .sweep import score_path_triplets_taps, tap_label
+        if args.selftest_shard:
+            s_ab, s_ac, bad = _selftest_scores_taps(trip, rank, world, len(taps))
         else:
-            correct, correct2 = cute_counts(s_ab.cpu(), s_ac.cpu(), args.similarity)
-            if total > 0 and args.dataset == "sref":           # style_main.py:186-193
-                print(f"Total comparisons: {total}")
-                print(f"Accuracy: {correct / total * 100:.2f}%")
-                print(f"2x Accuracy: {correct2 / total * 100:.2f}%")
-            elif total > 0:                                     # cute_main.py:216-224
-                print(f"Total comparisons: {total}")
-                print(f"Total {total}; Correct {correct}; Correct 2x {correct2}")
-                print(f"Accuracy: {correct / total * 100}%")
-                print(f"2x Accuracy: {correct2 / total * 100}%")
-            else:
-                print("Total comparisons: 0")
-                print("No valid comparisons were made.")
+            s_ab, s_ac, bad = score_path_triplets_taps(scorer, trip, args.image_size, taps, args.target_step, args.seed,
+                                                       args.similarity, rank, world, args.batch, args.unet_batch,
+                                                       return_status=True)
+        if rank == 0:
+            for t, tap in enumerate(taps):
+                block, tl = tap_label(tap)
+                block = args.target_block if isinstance(tap, int) else block      # (a DiT run prints the ignored block flag)
+                print(f"Experiment on {block}, layer {tl}, timestep {args.target_step}:")
+                _report(args, trip, rows, s_ab[t], s_ac[t], bad[t])
+    else:
+        if args.selftest_shard:
+            s_ab, s_ac, bad = _selftest_scores(trip, rank, world)
+        else:
+            s_ab, s_ac, bad = H.score_path_triplets(scorer, trip, args.image_size, args.target_block, layer, args.target_step,
+                                                    args.seed, args.similarity, rank, world, args.batch, args.unet_batch)
+        if rank == 0:
+            _report(args, trip, rows, s_ab, s_ac, bad)
     if world > 1:
         import torch.distributed as dist
         dist.barrier()

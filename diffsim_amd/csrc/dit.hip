@@ -14,6 +14,7 @@
 // Kernels: patch embedding (K = 16: direct), modulated LayerNorm (norm.hip), the MFMA GEMM with bias /
 // tanh-GELU / adaLN-gate+residual epilogues (gemm.hip), flash attention with D = 72 (attention.hip).
 #include <string>
+#include <vector>
 
 #include "common.h"
 #include "store.h"
@@ -81,13 +82,19 @@ __global__ void add_table_row_kernel(const float* a, const float* table, int row
     if (i < D) out[i] = a[i] + table[(size_t)row * D + i];
 }
 
+// one tap of a walk: the block and the tensors that receive its q, k, v
+struct DTap {
+    int layer;
+    void *q = nullptr, *k = nullptr, *v = nullptr;
+};
+
 struct DWalk {
     dsim_dit* h;
     Arena* ar;
     hipStream_t s;
     int n;                  // images
     bool run;
-    void *q_out = nullptr, *k_out = nullptr, *v_out = nullptr;
+    std::vector<DTap> taps; // captured on the way; the walk ends at the deepest
     bool tapped = false;
 
     size_t es() const { return dtype_size(h->dt); }
@@ -171,17 +178,22 @@ struct DWalk {
         void* nb = alloc_act((size_t)M * D);
         void* big = alloc_act((size_t)M * (F > 3 * D ? F : 3 * D));
         void* ab = alloc_act((size_t)M * D);
-        for (int blk = 0; blk <= c.tap_layer; ++blk) {
+        int last = -1;
+        for (const DTap& t : taps) last = t.layer > last ? t.layer : last;
+        for (int blk = 0; blk <= last; ++blk) {
             const std::string b = "blocks." + std::to_string(blk) + ".";
             DGET(qw, b + "attn.qkv.weight"); DGET(qb, b + "attn.qkv.bias");
             CK(lnmod(x, modv(blk, 1), modv(blk, 0), nb, M, D, T));
-            if (blk == c.tap_layer) {
+            for (const DTap& t : taps) {
+                if (t.layer != blk) continue;
                 // the pre-hook's input is the modulated norm1 output; q/k/v = row blocks of the fused qkv Linear
                 for (int j = 0; j < 3; ++j) {
-                    void* dst = j == 0 ? q_out : (j == 1 ? k_out : v_out);
+                    void* dst = j == 0 ? t.q : (j == 1 ? t.k : t.v);
                     CK(linear(nb, D, (char*)qw->p + (size_t)j * D * D * es(), (const float*)qb->p + (size_t)j * D, dst, M, D, 0,
                               nullptr, nullptr, T));
                 }
+            }
+            if (blk == last) {
                 tapped = true;
                 return DSIM_OK;
             }
@@ -258,6 +270,7 @@ int dsim_dit_finalize(dsim_dit* h, void* stream) {
     h->finalized = true;
     Arena ar;
     DWalk w{h, &ar, s, 1, false};
+    w.taps = {DTap{h->cfg.tap_layer}};
     const int st = w.go(nullptr, nullptr, 0.f, 0.f);
     if (st != DSIM_OK) { h->finalized = false; return st; }
     return DSIM_OK;
@@ -315,6 +328,7 @@ int dsim_dit_set_tap(dsim_dit* h, int tap_layer) {
     h->cfg.tap_layer = tap_layer;
     Arena ar;                                   // every parameter up to the new tap must have been loaded: dry walk
     DWalk w{h, &ar, nullptr, 1, false};
+    w.taps = {DTap{tap_layer}};
     const int st = w.go(nullptr, nullptr, 0.f, 0.f);
     if (st != DSIM_OK) { h->cfg.tap_layer = old; return st; }
     return DSIM_OK;
@@ -350,19 +364,32 @@ int dsim_dit_profile_get(dsim_dit* h, int i, char* name, int name_cap, double* f
     return DSIM_OK;
 }
 
-size_t dsim_dit_workspace_bytes(const dsim_dit* hc, int n_images) {
-    dsim_dit* h = const_cast<dsim_dit*>(hc);
-    if (!h || !h->finalized || n_images < 1) return 0;
+// dry walk to the deepest of `taps`: peak arena bytes
+static int dit_plan(dsim_dit* h, int n_images, const std::vector<DTap>& taps, size_t* peak) {
     Arena ar;
     DWalk w{h, &ar, nullptr, n_images, false};
-    if (w.go(nullptr, nullptr, 0.f, 0.f) != DSIM_OK) return 0;
-    return ar.peak + 256;
+    w.taps = taps;
+    CK(w.go(nullptr, nullptr, 0.f, 0.f));
+    *peak = ar.peak;
+    return DSIM_OK;
 }
 
-int dsim_dit_qkv(dsim_dit* h, const float* latents, const float* noise, float sqrt_abar, float sqrt_1m_abar, int n_images,
-                 void* q, void* k, void* v, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!h || !latents || !noise || !q || !k || !v || !workspace || n_images < 1) return DSIM_ERR_INVALID;
-    if (!h->finalized || !h->cond_set) return DSIM_ERR_STATE;
+// the layers of one sweep, checked: each in [0, depth), no two alike
+static int dit_check_taps(const dsim_dit* h, int n_taps, const int* layers, std::vector<DTap>* out) {
+    if (n_taps < 1 || !layers) return DSIM_ERR_INVALID;
+    out->clear();
+    for (int i = 0; i < n_taps; ++i) {
+        if (layers[i] < 0 || layers[i] >= h->cfg.depth) return DSIM_ERR_INVALID;
+        for (int j = 0; j < i; ++j)
+            if (layers[j] == layers[i]) return DSIM_ERR_INVALID;
+        out->push_back(DTap{layers[i]});
+    }
+    return DSIM_OK;
+}
+
+// one walk to the deepest of `taps` (their outputs set), every check before the first launch
+static int dit_run(dsim_dit* h, const float* latents, const float* noise, float sqrt_abar, float sqrt_1m_abar, int n_images,
+                   const std::vector<DTap>& taps, void* workspace, size_t workspace_bytes, void* stream) {
     Arena ar;
     ar.dry = false;
     const uintptr_t b0 = ((uintptr_t)workspace + 255) & ~(uintptr_t)255;
@@ -371,15 +398,60 @@ int dsim_dit_qkv(dsim_dit* h, const float* latents, const float* noise, float sq
     ar.base = (char*)b0;
     ar.cap = workspace_bytes - lost;
     {
-        Arena plan;
-        DWalk pw{h, &plan, nullptr, n_images, false};
-        CK(pw.go(nullptr, nullptr, 0.f, 0.f));
-        if (plan.peak > ar.cap) return DSIM_ERR_WORKSPACE;
+        size_t peak;
+        CK(dit_plan(h, n_images, taps, &peak));
+        if (peak > ar.cap) return DSIM_ERR_WORKSPACE;
     }
     DWalk w{h, &ar, (hipStream_t)stream, n_images, true};
-    w.q_out = q; w.k_out = k; w.v_out = v;
+    w.taps = taps;
     CK(w.go(latents, noise, sqrt_abar, sqrt_1m_abar));
     return w.tapped && !ar.overflow ? DSIM_OK : DSIM_ERR_WORKSPACE;
+}
+
+size_t dsim_dit_workspace_bytes(const dsim_dit* hc, int n_images) {
+    dsim_dit* h = const_cast<dsim_dit*>(hc);
+    if (!h || !h->finalized || n_images < 1) return 0;
+    size_t peak;
+    if (dit_plan(h, n_images, {DTap{h->cfg.tap_layer}}, &peak) != DSIM_OK) return 0;
+    return peak + 256;
+}
+
+size_t dsim_dit_taps_workspace_bytes(const dsim_dit* hc, int n_images, int n_taps, const int* layers) {
+    dsim_dit* h = const_cast<dsim_dit*>(hc);
+    if (!h || !h->finalized || n_images < 1) return 0;
+    std::vector<DTap> taps;
+    size_t peak;
+    if (dit_check_taps(h, n_taps, layers, &taps) != DSIM_OK || dit_plan(h, n_images, taps, &peak) != DSIM_OK) return 0;
+    const dsim_dit_cfg& c = h->cfg;
+    const size_t T = (size_t)(c.input_size / c.patch_size) * (c.input_size / c.patch_size);
+    const size_t F = (size_t)c.mlp_ratio * c.hidden_size > 3 * (size_t)c.hidden_size ? (size_t)c.mlp_ratio * c.hidden_size
+                                                                                      : 3 * (size_t)c.hidden_size;
+    // the widest activation ([M][max(F, 3D)]) and a tap's q / k / v ([M][D]) must stay < 2 GiB
+    if ((size_t)n_images * 2 * T * F * dtype_size(h->dt) >= 0x7fffffffull) return 0;
+    return peak + 256;
+}
+
+int dsim_dit_qkv(dsim_dit* h, const float* latents, const float* noise, float sqrt_abar, float sqrt_1m_abar, int n_images,
+                 void* q, void* k, void* v, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!h || !latents || !noise || !q || !k || !v || !workspace || n_images < 1) return DSIM_ERR_INVALID;
+    if (!h->finalized || !h->cond_set) return DSIM_ERR_STATE;
+    DTap t{h->cfg.tap_layer};
+    t.q = q; t.k = k; t.v = v;
+    return dit_run(h, latents, noise, sqrt_abar, sqrt_1m_abar, n_images, {t}, workspace, workspace_bytes, stream);
+}
+
+int dsim_dit_qkv_taps(dsim_dit* h, const float* latents, const float* noise, float sqrt_abar, float sqrt_1m_abar, int n_images,
+                      int n_taps, const int* layers, void* const* q, void* const* k, void* const* v, void* workspace,
+                      size_t workspace_bytes, void* stream) {
+    if (!h || !latents || !noise || !q || !k || !v || !workspace || n_images < 1) return DSIM_ERR_INVALID;
+    if (!h->finalized || !h->cond_set) return DSIM_ERR_STATE;
+    std::vector<DTap> taps;
+    CK(dit_check_taps(h, n_taps, layers, &taps));
+    for (int i = 0; i < n_taps; ++i) {
+        if (!q[i] || !k[i] || !v[i]) return DSIM_ERR_INVALID;
+        taps[i].q = q[i]; taps[i].k = k[i]; taps[i].v = v[i];
+    }
+    return dit_run(h, latents, noise, sqrt_abar, sqrt_1m_abar, n_images, taps, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -13,6 +13,7 @@
 // One `walk()` serves three purposes: PLAN (dry run: peak workspace bytes), RUN (launch), so the
 // planner can never disagree with the executor.  Activations are token-major [B][HW][C] in the
 // compute dtype; the workspace is a caller-provided arena with stack discipline.
+#include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -37,6 +38,20 @@ struct dsim_unet : WeightStore {
 
 namespace {
 
+// One tap of a walk: the dsim_unet_cfg fields of the same names (tap_attn / tap_tfm -1 = the last one) and the tensors that receive
+// its q, k, v.  A walk captures every tap it passes and ends at the deepest.
+struct TapReq {
+    int block, layer, attn, tfm;
+    void *q = nullptr, *k = nullptr, *v = nullptr;
+};
+
+// the handle's own tap as a one-tap request
+static std::vector<TapReq> cfg_taps(const dsim_unet_cfg& c, void* q = nullptr, void* k = nullptr, void* v = nullptr) {
+    TapReq t{c.tap_block, c.tap_layer, c.tap_attn, c.tap_tfm};
+    t.q = q; t.k = k; t.v = v;
+    return {t};
+}
+
 // ---- the walk ----------------------------------------------------------------------------
 struct Walk {
     dsim_unet* h;
@@ -46,8 +61,9 @@ struct Walk {
     bool run;               // false: plan only
     void* gn_scratch = nullptr;
     void* ctx_t = nullptr;  // [2][L][Dc] compute dtype
-    void *q_out = nullptr, *k_out = nullptr, *v_out = nullptr;
-    bool tapped = false;
+    std::vector<TapReq> taps;   // where q, k, v are captured; the walk ends at the deepest of them
+    int n_captured = 0;
+    bool tapped = false;        // every tap captured
 
     size_t es() const { return dtype_size(h->dt); }
     size_t max_tensor = 0;      // largest single activation (bytes): the kernels address tensors with 32-bit offsets
@@ -183,23 +199,63 @@ struct Walk {
     int heads_at(int level) const { return h->cfg.heads_per_level[level] > 0 ? h->cfg.heads_per_level[level] : h->cfg.num_heads; }
     int depth_at(int level) const { return h->cfg.depth_per_level[level] > 0 ? h->cfg.depth_per_level[level] : 1; }
 
+    // the requested taps in the Transformer2DModel of (block, layer, attention j) -- indices into `taps`; nattn: attentions of the block
+    std::vector<int> site(int block, int layer, int j, int nattn) const {
+        std::vector<int> r;
+        for (int t = 0; t < (int)taps.size(); ++t) {
+            const TapReq& q = taps[t];
+            if (q.block != block) continue;
+            if (block == DSIM_TAP_MID || (q.layer == layer && j == (q.attn < 0 ? nattn - 1 : q.attn))) r.push_back(t);
+        }
+        return r;
+    }
+
+    // hacked_attn.py:61-69: to_q / to_k / to_v of the normed block input nb, no bias; written [B][N][H*D] to the tap's tensors
+    int tap_qkv(const void* nb, const Packed* qkv, int C, int M, const TapReq& t) {
+        Packed wq = *qkv, wk = *qkv, wv = *qkv;
+        wk.p = (char*)qkv->p + (size_t)C * C * es();
+        wv.p = (char*)qkv->p + (size_t)2 * C * C * es();
+        // one launch when q, k, v lie at equal distances (engine.py allocates them as one [3][...] buffer) and the width
+        // tiles by 320: the packed [3C][C] weight as one N = 3C GEMM whose column runs go to the three tensors
+        const long long qk = (const char*)t.k - (const char*)t.q, kv = (const char*)t.v - (const char*)t.k;
+        const bool bm_split = C % 320 == 0;
+        if ((h->fusion & DSIM_FUSE_TAPQKV) && qk == kv && qk >= (long long)M * C * (long long)es() && 3 * qk < 0x7fffffffll && bm_split) {
+            GemmArgs g;
+            g.A0 = nb; g.C0 = C; g.mode = GEMM_LINEAR; g.M = M; g.N = 3 * C; g.K = C;
+            g.W = qkv->p; g.epi = EPI_NONE; g.out = t.q; g.ldo = C; g.out_split = C; g.out_split_stride = qk;
+            return gemm(g);
+        }
+        CK(linear(nb, C, nullptr, 0, &wq, nullptr, nullptr, t.q, M, C, C));
+        CK(linear(nb, C, nullptr, 0, &wk, nullptr, nullptr, t.k, M, C, C));
+        return linear(nb, C, nullptr, 0, &wv, nullptr, nullptr, t.v, M, C, C);
+    }
+
     // Transformer2DModel (GroupNorm -> proj_in -> `depth` BasicTransformerBlocks -> proj_out -> +residual; the
-    // conv1x1 and the Linear form of proj_in/out are the same GEMM on token-major data).  tap_blk >= 0 stops
-    // after norm1 of that transformer block and emits q,k,v (-2 = never, -1 = the last block).
+    // conv1x1 and the Linear form of proj_in/out are the same GEMM on token-major data).  caps: the requested taps here (site()).
+    // At each tapped transformer block, norm1 and the q/k/v projection run as a walk that stops there runs them; the walk
+    // then stops if no other tap is left, or the block carries on exactly as an untapped one.
     // half_in: x holds ONE copy per image (B2 / 2 batch elements, opt-in CFG de-duplication): everything up to the first
     // cross-attention -- the first place the prompt context enters -- runs on that half batch, then the residual stream, the
     // block input and the cross-attention query are duplicated into [image][cfg] order and the rest runs as usual.
-    int transformer(const std::string& p, const Act& x, int level, int tap_blk, Act* out, bool half_in = false) {
+    int transformer(const std::string& p, const Act& x, int level, const std::vector<int>& caps, Act* out, bool half_in = false) {
         const int C = x.C, HW = x.H * x.W, M = B2 * HW, H = heads_at(level), D = C / H;
         const int Bfull = B2, Mh = (B2 / 2) * HW;
         const int L = h->cfg.ctx_len, Dc = h->cfg.cross_attention_dim;
         const int depth = depth_at(level);
-        if (tap_blk == -1) tap_blk = depth - 1;
-        if (tap_blk >= depth) return DSIM_ERR_INVALID;
-        const bool tap_here = tap_blk >= 0;
+        std::vector<int> cap_blk(caps.size());           // transformer block of each tap here
+        int last_blk = -1;
+        for (size_t i = 0; i < caps.size(); ++i) {
+            const int tb = taps[caps[i]].tfm < 0 ? depth - 1 : taps[caps[i]].tfm;
+            if (tb >= depth) return DSIM_ERR_INVALID;
+            cap_blk[i] = tb;
+            if (tb > last_blk) last_blk = tb;
+        }
+        // the walk ends in this model when it holds every tap not captured yet: after norm1 and q/k/v of block last_blk
+        const bool stop_here = !caps.empty() && n_captured + (int)caps.size() == (int)taps.size();
+        if (!stop_here) last_blk = -1;
         WGET(gnw, p + "norm.weight"); WGET(gnb, p + "norm.bias");
         WGET(piw, p + "proj_in.weight"); WGET(pib, p + "proj_in.bias");
-        if (!tap_here) { out->p = alloc_act((size_t)M * C); out->C = C; out->H = x.H; out->W = x.W; }
+        if (!stop_here) { out->p = alloc_act((size_t)M * C); out->C = C; out->H = x.H; out->W = x.W; }
         const size_t mk = ar->mark();
         void* t1 = alloc_act((size_t)M * C);
         void* hb = alloc_act((size_t)M * C);
@@ -208,7 +264,8 @@ struct Walk {
         void* xfull = half_in ? alloc_act((size_t)M * C) : nullptr;
         const void* xres = half_in ? xfull : x.p;                       // residual of proj_out: the block input, full batch
         if (half_in) {
-            if (tap_blk == 0) return DSIM_ERR_INVALID;                  // (callers never de-duplicate a tapped first block)
+            for (int tb : cap_blk)
+                if (tb == 0) return DSIM_ERR_INVALID;                   // (callers never de-duplicate a tapped first block)
             B2 = Bfull / 2;
         }
         const int M0 = half_in ? Mh : M;                                // rows of the part before the first cross-attention
@@ -226,8 +283,8 @@ struct Walk {
         const bool pre = half_in && blk == 0;            // still on the de-duplicated half batch
         const int Mx = pre ? Mh : M;
         void* hbx = pre ? hbh : hb;
-        // LayerNorm + projection as one row-resident launch where the width has one (16-bit modes, C = 320; not the tapped block, whose
-        // q, k, v go to three tensors)
+        // LayerNorm + projection as one row-resident launch where the width has one (16-bit modes, C = 320; not the block the walk ends
+        // in, whose q, k, v go to three tensors)
         auto ln_proj = [&](const void* xin, const Packed* g, const Packed* be, const std::string& key, void* o, int Mr, int N) -> int {
             const auto it = h->pk.find(key);
             if (it == h->pk.end() || !(h->fusion & DSIM_FUSE_LNPROJ)) return 1;          // 1: run the unfused chain
@@ -243,40 +300,33 @@ struct Walk {
             }
             return DSIM_OK;
         };
-        const bool tapped_here = blk == tap_blk;
+        const bool last = blk == last_blk;               // the walk ends after this block's q/k/v
+        bool cap = false;
+        for (int tb : cap_blk) cap = cap || tb == blk;
         int fq = 1;
-        if (!tapped_here && !big) {
+        if (!last && !big) {
             // qkv [M][3C]; later the GEGLU output [M][4C] unless the feed-forward runs as one launch
             const bool ff1 = h->pk.count(b + "ff.stream") && (h->fusion & DSIM_FUSE_FF);
             big = alloc_act((size_t)M * (ff1 ? 3 : 4) * C);
             ab = alloc_act((size_t)M * C);
             kvb = alloc_act((size_t)2 * L * 2 * C);
         }
-        if (!tapped_here) fq = ln_proj(hbx, l1w, l1b, b + "attn1.qkv.stream", big, Mx, 3 * C);
+        if (!last) fq = ln_proj(hbx, l1w, l1b, b + "attn1.qkv.stream", big, Mx, 3 * C);
         if (fq < 0) return fq;
-        if (fq > 0) CK(ln(hbx, l1w, l1b, nb, Mx, C));
-        if (blk == tap_blk) {
-            // hacked_attn.py:61-69: to_q / to_k / to_v, no bias; written [B][N][H*D]
-            Packed wq = *qkv, wk = *qkv, wv = *qkv;
-            wk.p = (char*)qkv->p + (size_t)C * C * es();
-            wv.p = (char*)qkv->p + (size_t)2 * C * C * es();
-            // one launch when q, k, v lie at equal distances (engine.py allocates them as one [3][...] buffer) and the width
-            // tiles by 320: the packed [3C][C] weight as one N = 3C GEMM whose column runs go to the three tensors
-            const long long qk = (const char*)k_out - (const char*)q_out, kv = (const char*)v_out - (const char*)k_out;
-            const bool bm_split = C % 320 == 0;
-            if ((h->fusion & DSIM_FUSE_TAPQKV) && qk == kv && qk >= (long long)M * C * (long long)es() && 3 * qk < 0x7fffffffll && bm_split) {
-                GemmArgs g;
-                g.A0 = nb; g.C0 = C; g.mode = GEMM_LINEAR; g.M = M; g.N = 3 * C; g.K = C;
-                g.W = qkv->p; g.epi = EPI_NONE; g.out = q_out; g.ldo = C; g.out_split = C; g.out_split_stride = qk;
-                CK(gemm(g));
-            } else {
-                CK(linear(nb, C, nullptr, 0, &wq, nullptr, nullptr, q_out, M, C, C));
-                CK(linear(nb, C, nullptr, 0, &wk, nullptr, nullptr, k_out, M, C, C));
-                CK(linear(nb, C, nullptr, 0, &wv, nullptr, nullptr, v_out, M, C, C));
+        // a tap's q/k/v come from the unfused norm1 -> projection chain: the fused launch is not bit-identical to it, so where the
+        // block carries on through that launch, the tap gets a norm1 of its own; elsewhere the two share one
+        if (fq > 0 || cap) CK(ln(hbx, l1w, l1b, nb, Mx, C));
+        if (cap) {
+            for (size_t i = 0; i < caps.size(); ++i)
+                if (cap_blk[i] == blk) {
+                    CK(tap_qkv(nb, qkv, C, M, taps[caps[i]]));
+                    ++n_captured;
+                }
+            if (last) {
+                tapped = true;
+                ar->release(mk);
+                return DSIM_OK;
             }
-            tapped = true;
-            ar->release(mk);
-            return DSIM_OK;
         }
         WGET(o1w, b + "attn1.to_out.0.weight"); WGET(o1b, b + "attn1.to_out.0.bias");
         WGET(l2w, b + "norm2.weight"); WGET(l2b, b + "norm2.bias");
@@ -376,8 +426,9 @@ struct Walk {
         // transformer up to its cross-attention query see two bit-identical batch halves.  With one time embedding for both
         // halves (SD1.5; SDXL's text_time embedding differs per half) and the tap outside that block, they are computed once
         // per image and duplicated where the prompt context first enters.  Same kernels, batch-invariant: same bits.
-        const bool dedup = h->cfg_dedup && !h->two_temb && c.down_has_attn[0] && c.layers_per_block >= 1 &&
-                           !(c.tap_block == DSIM_TAP_DOWN && c.tap_layer == 0);
+        bool tap_down0 = false;             // a requested tap in the first down block
+        for (const TapReq& t : taps) tap_down0 = tap_down0 || (t.block == DSIM_TAP_DOWN && t.layer == 0);
+        const bool dedup = h->cfg_dedup && !h->two_temb && c.down_has_attn[0] && c.layers_per_block >= 1 && !tap_down0;
         Act xh{nullptr, ch0, S, S};
         if (dedup) {
             xh.p = alloc_act((size_t)(B2 / 2) * S * S * ch0);
@@ -403,11 +454,10 @@ struct Walk {
                 }
                 x = r;
                 if (c.down_has_attn[i]) {
-                    const int ta = c.tap_attn < 0 ? c.layers_per_block - 1 : c.tap_attn;
-                    const bool tap = c.tap_block == DSIM_TAP_DOWN && c.tap_layer == i && j == ta;
                     Act t;
-                    CK(transformer(bp + "attentions." + std::to_string(j) + ".", x, i, tap ? c.tap_tfm : -2, &t, half));
-                    if (tap) return DSIM_OK;
+                    CK(transformer(bp + "attentions." + std::to_string(j) + ".", x, i, site(DSIM_TAP_DOWN, i, j, c.layers_per_block), &t,
+                                   half));
+                    if (tapped) return DSIM_OK;
                     x = t;
                 }
                 skips.push_back(x);
@@ -426,10 +476,9 @@ struct Walk {
             Act r;
             CK(resnet("mid_block.resnets.0.", x, nullptr, cm, &r));
             x = r;
-            const bool tap = c.tap_block == DSIM_TAP_MID;
             Act t;
-            CK(transformer("mid_block.attentions.0.", x, nl - 1, tap ? c.tap_tfm : -2, &t));
-            if (tap) return DSIM_OK;
+            CK(transformer("mid_block.attentions.0.", x, nl - 1, site(DSIM_TAP_MID, 0, 0, 1), &t));
+            if (tapped) return DSIM_OK;
             x = t;
             CK(resnet("mid_block.resnets.1.", x, nullptr, cm, &r));
             x = r;
@@ -447,11 +496,9 @@ struct Walk {
                 CK(resnet(bp + "resnets." + std::to_string(j) + ".", x, &sk, co, &r));
                 x = r;
                 if (c.up_has_attn[i]) {
-                    const int ta = c.tap_attn < 0 ? nres - 1 : c.tap_attn;
-                    const bool tap = c.tap_block == DSIM_TAP_UP && c.tap_layer == i && j == ta;
                     Act t;
-                    CK(transformer(bp + "attentions." + std::to_string(j) + ".", x, nl - 1 - i, tap ? c.tap_tfm : -2, &t));
-                    if (tap) return DSIM_OK;
+                    CK(transformer(bp + "attentions." + std::to_string(j) + ".", x, nl - 1 - i, site(DSIM_TAP_UP, i, j, nres), &t));
+                    if (tapped) return DSIM_OK;
                     x = t;
                 }
             }
@@ -476,7 +523,7 @@ struct Walk {
                 x = u;
             }
         }
-        return DSIM_ERR_INVALID;   // the tap was never reached: bad tap_block / tap_layer
+        return DSIM_ERR_INVALID;   // a tap was never reached: bad tap_block / tap_layer
     }
 };
 
@@ -635,6 +682,7 @@ int dsim_unet_finalize(dsim_unet* h, void* stream) {
     // make sure every parameter up to the tap exists: dry walk
     Arena ar;
     Walk w{h, &ar, s, 2, false};
+    w.taps = cfg_taps(h->cfg);
     const int st = w.go(nullptr, nullptr, 0.f, 0.f, nullptr);
     if (st != DSIM_OK) { h->finalized = false; return st; }
     return DSIM_OK;
@@ -709,19 +757,81 @@ int dsim_unet_set_conditioning(dsim_unet* h, int t, const float* text_embeds, co
     return set_cond(h, t, text_embeds, time_ids, (hipStream_t)stream);
 }
 
+// the handle's cfg with its tap fields set to `t` (tap_geometry's input for a tap other than the handle's own)
+static dsim_unet_cfg cfg_at(const dsim_unet_cfg& c, int block, int layer, int attn, int tfm) {
+    dsim_unet_cfg r = c;
+    r.tap_block = block; r.tap_layer = layer; r.tap_attn = attn; r.tap_tfm = tfm;
+    return r;
+}
+
+// The taps of one sweep, checked: tap_geometry accepts each, and no two name the same attention once -1 (the last) is resolved
+// and the mid block's unused fields are ignored.  out_bytes: the largest q / k / v tensor of n_images.
+static int check_taps(const dsim_unet* h, int n_images, int n_taps, const dsim_tap* taps, std::vector<TapReq>* out,
+                      size_t* out_bytes) {
+    if (n_taps < 1 || !taps) return DSIM_ERR_INVALID;
+    const dsim_unet_cfg& c = h->cfg;
+    std::vector<std::array<int, 4>> seen;
+    out->clear();
+    *out_bytes = 0;
+    for (int i = 0; i < n_taps; ++i) {
+        const dsim_tap& t = taps[i];
+        int n, hh, d;
+        CK(tap_geometry(cfg_at(c, t.block, t.layer, t.attn, t.tfm), &n, &hh, &d));
+        const size_t b = (size_t)2 * n_images * n * hh * d * dtype_size(h->dt);
+        if (b > *out_bytes) *out_bytes = b;
+        const int nl = c.n_levels;
+        const int level = t.block == DSIM_TAP_DOWN ? t.layer : (t.block == DSIM_TAP_MID ? nl - 1 : nl - 1 - t.layer);
+        const int depth = c.depth_per_level[level] > 0 ? c.depth_per_level[level] : 1;
+        const int nattn = t.block == DSIM_TAP_DOWN ? c.layers_per_block : c.layers_per_block + 1;
+        const std::array<int, 4> key = {t.block, t.block == DSIM_TAP_MID ? 0 : t.layer,
+                                        t.block == DSIM_TAP_MID ? 0 : (t.attn < 0 ? nattn - 1 : t.attn), t.tfm < 0 ? depth - 1 : t.tfm};
+        for (const auto& s2 : seen)
+            if (s2 == key) return DSIM_ERR_INVALID;
+        seen.push_back(key);
+        out->push_back(TapReq{t.block, t.layer, t.attn, t.tfm});
+    }
+    return DSIM_OK;
+}
+
+// dry walk to the deepest of `taps`: peak arena bytes and the largest activation
+static int plan_taps(dsim_unet* h, int n_images, const std::vector<TapReq>& taps, size_t* peak, size_t* max_tensor) {
+    Arena ar;
+    Walk w{h, &ar, nullptr, 2 * n_images, false};
+    w.taps = taps;
+    CK(w.go(nullptr, nullptr, 0.f, 0.f, nullptr));
+    *peak = ar.peak;
+    *max_tensor = w.max_tensor;
+    return DSIM_OK;
+}
+
 size_t dsim_unet_workspace_bytes(const dsim_unet* hc, int n_images) {
     dsim_unet* h = const_cast<dsim_unet*>(hc);
     if (!h || !h->finalized || n_images < 1) return 0;
-    Arena ar;
-    Walk w{h, &ar, nullptr, 2 * n_images, false};
-    if (w.go(nullptr, nullptr, 0.f, 0.f, nullptr) != DSIM_OK) return 0;
-    if (w.max_tensor >= 0x7fffffffull) return 0;      // a >= 2 GiB activation: the batch does not fit one call
-    return ar.peak + 256;
+    size_t peak, big;
+    if (plan_taps(h, n_images, cfg_taps(h->cfg), &peak, &big) != DSIM_OK) return 0;
+    if (big >= 0x7fffffffull) return 0;      // a >= 2 GiB activation: the batch does not fit one call
+    return peak + 256;
+}
+
+size_t dsim_unet_taps_workspace_bytes(const dsim_unet* hc, int n_images, int n_taps, const dsim_tap* taps) {
+    dsim_unet* h = const_cast<dsim_unet*>(hc);
+    if (!h || !h->finalized || n_images < 1) return 0;
+    std::vector<TapReq> req;
+    size_t out_bytes, peak, big;
+    if (check_taps(h, n_images, n_taps, taps, &req, &out_bytes) != DSIM_OK) return 0;
+    if (plan_taps(h, n_images, req, &peak, &big) != DSIM_OK) return 0;
+    if (big >= 0x7fffffffull || out_bytes >= 0x7fffffffull) return 0;
+    return peak + 256;
 }
 
 int dsim_unet_tap_shape(const dsim_unet* h, int* tokens, int* heads, int* head_dim) {
     if (!h || !tokens || !heads || !head_dim) return DSIM_ERR_INVALID;
     return tap_geometry(h->cfg, tokens, heads, head_dim);
+}
+
+int dsim_unet_tap_shape_at(const dsim_unet* h, const dsim_tap* tap, int* tokens, int* heads, int* head_dim) {
+    if (!h || !tap || !tokens || !heads || !head_dim) return DSIM_ERR_INVALID;
+    return tap_geometry(cfg_at(h->cfg, tap->block, tap->layer, tap->attn, tap->tfm), tokens, heads, head_dim);
 }
 
 int dsim_unet_set_tap(dsim_unet* h, int tap_block, int tap_layer, int tap_attn, int tap_tfm) {
@@ -734,6 +844,7 @@ int dsim_unet_set_tap(dsim_unet* h, int tap_block, int tap_layer, int tap_attn, 
     if (st == DSIM_OK) {             // every parameter up to the new tap must have been loaded: dry walk
         Arena ar;
         Walk w{h, &ar, nullptr, 2, false};
+        w.taps = cfg_taps(h->cfg);
         st = w.go(nullptr, nullptr, 0.f, 0.f, nullptr);
     }
     if (st != DSIM_OK) h->cfg = old;
@@ -769,27 +880,48 @@ static bool align_workspace(void*& ws, size_t& bytes) {
     return true;
 }
 
-int dsim_unet_qkv(dsim_unet* h, const float* latents, const float* noise, float sqrt_abar, float sqrt_1m_abar,
-                  const float* ctx, int n_images, void* q, void* k, void* v, void* workspace, size_t workspace_bytes,
-                  void* stream) {
-    if (!h || !latents || !noise || !ctx || !q || !k || !v || !workspace || n_images < 1) return DSIM_ERR_INVALID;
-    if (!h->finalized || h->timestep < 0) return DSIM_ERR_STATE;
+// one walk to the deepest of `taps` (their outputs set), every check before the first launch
+static int run_taps(dsim_unet* h, const float* latents, const float* noise, float sqrt_abar, float sqrt_1m_abar, const float* ctx,
+                    int n_images, const std::vector<TapReq>& taps, void* workspace, size_t workspace_bytes, void* stream) {
     Arena ar;
     ar.dry = false;
     if (!align_workspace(workspace, workspace_bytes)) return DSIM_ERR_WORKSPACE;
     ar.base = (char*)workspace;
     ar.cap = workspace_bytes;
     {   // refuse up front instead of failing mid-graph
-        Arena plan;
-        Walk pw{h, &plan, nullptr, 2 * n_images, false};
-        CK(pw.go(nullptr, nullptr, 0.f, 0.f, nullptr));
-        if (plan.peak > ar.cap) return DSIM_ERR_WORKSPACE;
+        size_t peak, big;
+        CK(plan_taps(h, n_images, taps, &peak, &big));
+        if (peak > ar.cap) return DSIM_ERR_WORKSPACE;
     }
     Walk w{h, &ar, (hipStream_t)stream, 2 * n_images, true};
-    w.q_out = q; w.k_out = k; w.v_out = v;
+    w.taps = taps;
     CK(w.go(latents, noise, sqrt_abar, sqrt_1m_abar, ctx));
     if (ar.overflow) return DSIM_ERR_WORKSPACE;
     return w.tapped ? DSIM_OK : DSIM_ERR_INVALID;
+}
+
+int dsim_unet_qkv(dsim_unet* h, const float* latents, const float* noise, float sqrt_abar, float sqrt_1m_abar,
+                  const float* ctx, int n_images, void* q, void* k, void* v, void* workspace, size_t workspace_bytes,
+                  void* stream) {
+    if (!h || !latents || !noise || !ctx || !q || !k || !v || !workspace || n_images < 1) return DSIM_ERR_INVALID;
+    if (!h->finalized || h->timestep < 0) return DSIM_ERR_STATE;
+    return run_taps(h, latents, noise, sqrt_abar, sqrt_1m_abar, ctx, n_images, cfg_taps(h->cfg, q, k, v), workspace, workspace_bytes,
+                    stream);
+}
+
+int dsim_unet_qkv_taps(dsim_unet* h, const float* latents, const float* noise, float sqrt_abar, float sqrt_1m_abar, const float* ctx,
+                       int n_images, int n_taps, const dsim_tap* taps, void* const* q, void* const* k, void* const* v, void* workspace,
+                       size_t workspace_bytes, void* stream) {
+    if (!h || !latents || !noise || !ctx || !q || !k || !v || !workspace || n_images < 1) return DSIM_ERR_INVALID;
+    if (!h->finalized || h->timestep < 0) return DSIM_ERR_STATE;
+    std::vector<TapReq> req;
+    size_t out_bytes;
+    CK(check_taps(h, n_images, n_taps, taps, &req, &out_bytes));
+    for (int i = 0; i < n_taps; ++i) {
+        if (!q[i] || !k[i] || !v[i]) return DSIM_ERR_INVALID;
+        req[i].q = q[i]; req[i].k = k[i]; req[i].v = v[i];
+    }
+    return run_taps(h, latents, noise, sqrt_abar, sqrt_1m_abar, ctx, n_images, req, workspace, workspace_bytes, stream);
 }
 
 int dsim_unet_profile(dsim_unet* h, int enable) {

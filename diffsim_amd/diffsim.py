@@ -157,6 +157,21 @@ class DiffSim:
     def features(self, latents: torch.Tensor, noise: torch.Tensor, prompt, target_block, target_layer, target_step):
         """latents/noise (n,4,s,s) -> q,k,v [n][2][N][H*D] (compute dtype, on device)."""
         eng = self.engine(target_block, target_layer)
+        return eng.qkv(*self._forward_inputs(eng, latents, noise, prompt, target_step))
+
+    @torch.no_grad()
+    def features_taps(self, latents: torch.Tensor, noise: torch.Tensor, prompt, taps, target_step):
+        """:meth:`features` at every tap of `taps` ([(target_block, layer)], layers explicit) from ONE U-Net forward: a list of
+        (q, k, v), entry i bit for bit what features() gives at taps[i] (sweep.py)."""
+        if not taps:
+            raise ValueError("no taps")
+        if self._base is None:
+            self.engine(*taps[0])
+        eng = self._base                # the sweep does not move the handle's tap
+        return eng.qkv_taps(*self._forward_inputs(eng, latents, noise, prompt, target_step), [(b, int(l)) for b, l in taps])
+
+    def _forward_inputs(self, eng, latents, noise, prompt, target_step):
+        """(latents, noise, sqrt_abar, sqrt_1m_abar, ctx) of the engine call at target_step; sets the engine's timestep."""
         t = sched.timestep_from_index(int(target_step))
         eng.set_timestep(t)
         sa, sb = sched.noise_coefficients(t)
@@ -169,10 +184,10 @@ class DiffSim:
             xt = a16.to(dev) * latents.to(dev, torch.float16) + b16.to(dev) * noise.to(dev, torch.float16)
             lat = xt.float().contiguous()
             ctx16 = self.context(prompt).to(torch.float16).float()         # the fp16 text encoder's output
-            return eng.qkv(lat, torch.zeros_like(lat), 1.0, 0.0, ctx16)
+            return lat, torch.zeros_like(lat), 1.0, 0.0, ctx16
         lat = latents.to(self.device, torch.float32).contiguous()
         nz = noise.to(self.device, torch.float32).contiguous()
-        return eng.qkv(lat, nz, sa, sb, self.context(prompt))
+        return lat, nz, sa, sb, self.context(prompt)
 
     def auto_batch_pairs(self, eng, n_pairs: int, streams: int = 2, target: int = 64) -> int:
         """Pairs per chunk when the caller names none: `target` (the sweep's optimum on a 288 GB part), capped by the 2 GiB
@@ -314,3 +329,20 @@ class DiffSim:
         from .maps import score_latent_pair_maps
         return score_latent_pair_maps(self, latA, latB, noiseA, noiseB, prompt, target_block, _norm_layer(target_layer),
                                       target_step, similarity, batch_pairs)
+
+    # ------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def score_latent_pairs_taps(self, latA, latB, noiseA, noiseB, prompt, taps, target_step=600, similarity="cosine",
+                                batch_pairs: Optional[int] = None) -> torch.Tensor:
+        """(n_taps, n) scores: row t is :meth:`score_latent_pairs` at taps[t], every tap from one forward per chunk
+        (sweep.score_latent_pairs_taps).  taps: [(target_block, layer)] with explicit layers, or "all"."""
+        from .sweep import score_latent_pairs_taps
+        return score_latent_pairs_taps(self, latA, latB, noiseA, noiseB, prompt, taps, target_step, similarity, batch_pairs)
+
+    @torch.no_grad()
+    def score_pairs_taps(self, pairs: Sequence[Tuple[str, str]], img_size, prompt, taps, target_step, seed="2333",
+                         similarity="cosine") -> torch.Tensor:
+        """(n_taps, len(pairs)) scores: row t is :meth:`score_pairs` at taps[t]; the images are decoded and encoded once for all
+        taps (sweep.score_path_pairs_taps)."""
+        from .sweep import score_path_pairs_taps
+        return score_path_pairs_taps(self, pairs, img_size, prompt, taps, target_step, similarity, seed)

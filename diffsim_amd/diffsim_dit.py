@@ -54,6 +54,18 @@ class diffsim_DiT:
                        sa, sb)
 
     @torch.no_grad()
+    def features_taps(self, latents, noise, layers, target_step: int):
+        """:meth:`features` at every block of `layers` from ONE forward: a list of (q, k, v), entry i bit for bit what features()
+        gives at layers[i] (sweep.py).  The engine's tap does not move."""
+        if not layers:
+            raise ValueError("no taps")
+        eng = self._engine if self._engine is not None else self.engine(int(layers[0]))
+        eng.set_conditioning(sched.dit_model_timestep(int(target_step)), 1, self.cfg.num_classes)
+        sa, sb = sched.noise_coefficients(int(target_step))
+        return eng.qkv_taps(latents.to(self.device, torch.float32).contiguous(), noise.to(self.device, torch.float32).contiguous(),
+                            sa, sb, [int(l) for l in layers])
+
+    @torch.no_grad()
     def score_latent_pairs(self, latA, latB, noiseA, noiseB, target_layer: int, target_step: int, similarity="cosine",
                            batch_pairs: int = 32) -> torch.Tensor:
         n = latA.shape[0]
@@ -85,3 +97,16 @@ class diffsim_DiT:
         from .maps import score_latent_pair_maps
         return score_latent_pair_maps(self, latA, latB, noiseA, noiseB, None, "none", [int(target_layer)], target_step, similarity,
                                       batch_pairs)
+
+    @torch.no_grad()
+    def score_latent_pairs_taps(self, latA, latB, noiseA, noiseB, layers, target_step: int, similarity="cosine",
+                                batch_pairs: Optional[int] = None) -> torch.Tensor:
+        """(n_taps, n) scores: row t is :meth:`score_latent_pairs` at layers[t] (sweep.score_latent_pairs_taps)."""
+        from .sweep import score_latent_pairs_taps
+        return score_latent_pairs_taps(self, latA, latB, noiseA, noiseB, None, layers, target_step, similarity, batch_pairs)
+
+    @torch.no_grad()
+    def score_pairs_taps(self, pairs, img_size, layers, target_step, similarity="cosine", seed=2333) -> torch.Tensor:
+        """(n_taps, len(pairs)) scores of (A, B) path pairs, the images encoded once for all blocks (sweep.score_path_pairs_taps)."""
+        from .sweep import score_path_pairs_taps
+        return score_path_pairs_taps(self, pairs, img_size, None, layers, target_step, similarity, seed)

@@ -70,6 +70,22 @@ class diffsim_xl:
     def features(self, latents, noise, ctx, pooled, target_block, target_layer, target_step):
         """latents / noise (n,4,s,s): any latent side s (img_size // 8), not only cfg.sample_size."""
         eng = self.engine(target_block, target_layer)
+        return eng.qkv(*self._forward_inputs(eng, latents, noise, ctx, pooled, target_step))
+
+    @torch.no_grad()
+    def features_taps(self, latents, noise, ctx, pooled, taps, target_step):
+        """:meth:`features` at every tap of `taps` ([(target_block, [b, a, t])]; mid: [a, t]) from ONE U-Net forward: a list of
+        (q, k, v), entry i bit for bit what features() gives at taps[i] (sweep.py)."""
+        if not taps:
+            raise ValueError("no taps")
+        if self._base is None:
+            self.engine(*taps[0])
+        eng = self._base                # the sweep does not move the handle's tap
+        return eng.qkv_taps(*self._forward_inputs(eng, latents, noise, ctx, pooled, target_step),
+                            [(b, [int(v) for v in l]) for b, l in taps])
+
+    def _forward_inputs(self, eng, latents, noise, ctx, pooled, target_step):
+        """(x, noise, a, b, ctx) of the engine call at target_step; sets the engine's conditioning."""
         t, a, b = sched.sdxl_step_coefficients(int(target_step))
         if self.noise_dtype == torch.float16:       # the fp16 text encoders' outputs
             ctx, pooled = ctx.to(torch.float16).float(), pooled.to(torch.float16).float()
@@ -83,9 +99,8 @@ class diffsim_xl:
             x = x + noise.to(dev, torch.float16) * sg.to(torch.float16).to(dev)  # add_noise: sigmas cast to the sample dtype
             x = x / ((sg ** 2 + 1) ** 0.5).to(dev)                              # scale_model_input: fp16 / 0-dim fp32 -> fp16
             x = x.float().contiguous()
-            return eng.qkv(x, torch.zeros_like(x), 1.0, 0.0, ctx)
-        return eng.qkv(latents.to(self.device, torch.float32).contiguous(), noise.to(self.device, torch.float32).contiguous(),
-                       a, b, ctx)
+            return x, torch.zeros_like(x), 1.0, 0.0, ctx
+        return latents.to(self.device, torch.float32).contiguous(), noise.to(self.device, torch.float32).contiguous(), a, b, ctx
 
     @torch.no_grad()
     def score_latent_pairs(self, latA, latB, noiseA, noiseB, ctx, pooled, target_block, target_layer, target_step,
@@ -131,3 +146,17 @@ class diffsim_xl:
         from .maps import score_latent_pair_maps
         return score_latent_pair_maps(self, latA, latB, noiseA, noiseB, (ctx, pooled), target_block, target_layer, target_step,
                                       similarity, batch_pairs)
+
+    @torch.no_grad()
+    def score_latent_pairs_taps(self, latA, latB, noiseA, noiseB, ctx, pooled, taps, target_step, similarity="cosine",
+                                batch_pairs: Optional[int] = None) -> torch.Tensor:
+        """(n_taps, n) scores: row t is :meth:`score_latent_pairs` at taps[t] (sweep.score_latent_pairs_taps)."""
+        from .sweep import score_latent_pairs_taps
+        return score_latent_pairs_taps(self, latA, latB, noiseA, noiseB, (ctx, pooled), taps, target_step, similarity,
+                                       batch_pairs)
+
+    @torch.no_grad()
+    def score_pairs_taps(self, pairs, img_size, prompt, taps, target_step, similarity="cosine", seed=2333) -> torch.Tensor:
+        """(n_taps, len(pairs)) scores of (A, B) path pairs, the images encoded once for all taps (sweep.score_path_pairs_taps)."""
+        from .sweep import score_path_pairs_taps
+        return score_path_pairs_taps(self, pairs, img_size, prompt, taps, target_step, similarity, seed)

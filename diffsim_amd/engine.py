@@ -6,7 +6,7 @@ libdiffsim_amd.so.  Every call passes ``tensor.data_ptr()`` and the current HIP 
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, Optional, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import torch
 
@@ -151,6 +151,7 @@ class UNetEngine:
         """Opt-in: compute the part of the graph both CFG halves share once (SD1.5 graphs; bit-identical scores)."""
         _lib.check(self.L.dsim_unet_set_cfg_dedup(self._h, int(bool(enable))), "dsim_unet_set_cfg_dedup")
         self._max_images = None
+        self.__dict__.pop("_max_images_taps", None)
         self._graphs.clear()
 
     def set_fusion(self, mask: int):
@@ -158,6 +159,7 @@ class UNetEngine:
         its own launch: the A/B switch of bench.py --fusion and of the parity tests."""
         _lib.check(self.L.dsim_unet_set_fusion(self._h, int(mask)), "dsim_unet_set_fusion")
         self._max_images = None
+        self.__dict__.pop("_max_images_taps", None)
         self._graphs.clear()
 
     def view(self, target_block: str, target_layer) -> "TapView":
@@ -235,34 +237,41 @@ class UNetEngine:
                 hi = mid
         return lo
 
-    def qkv(self, latents: torch.Tensor, noise: torch.Tensor, sqrt_abar: float, sqrt_1m_abar: float,
-            ctx: torch.Tensor, out: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None):
-        """latents/noise (n,Cin,s,s) f32 cuda; ctx (2,L,Dc) f32 cuda -> q,k,v each
-        [n][2][tokens][heads*head_dim] in the compute dtype."""
+    def _check_inputs(self, latents, noise, ctx):
         _require_cuda(latents, noise, ctx)
         if latents.dtype != torch.float32 or noise.dtype != torch.float32 or ctx.dtype != torch.float32:
             raise _lib.DsimError("latents, noise and ctx must be float32")
-        n = latents.shape[0]
         if latents.ndim != 4 or latents.shape[1] != self.cfg.in_channels or latents.shape[2] != latents.shape[3] or \
                 noise.shape != latents.shape:
             raise _lib.DsimError(f"latents and noise must be (n,{self.cfg.in_channels},s,s)")
         self.set_sample_size(int(latents.shape[2]))
         if tuple(ctx.shape) != (2, self.cfg.ctx_len, self.cfg.cross_attention_dim):
             raise _lib.DsimError("ctx must be (2, ctx_len, cross_attention_dim)")
+
+    def _arena(self, need: int) -> torch.Tensor:
+        # dsim_unet_qkv keeps no per-call state in the handle, so independent batches may be in flight on several
+        # streams at once (one host thread): each stream gets its own workspace arena
+        sid = _stream_ptr()
+        ws = self._ws_by_stream.get(sid)
+        if ws is None or ws.numel() < need:
+            self._ws_by_stream.pop(sid, None)
+            self._graphs.clear()                 # captured graphs hold the old arena's addresses
+            ws = self._ws_by_stream[sid] = torch.empty(need, dtype=torch.uint8, device=self.device)
+        self._ws = ws
+        return ws
+
+    def qkv(self, latents: torch.Tensor, noise: torch.Tensor, sqrt_abar: float, sqrt_1m_abar: float,
+            ctx: torch.Tensor, out: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None):
+        """latents/noise (n,Cin,s,s) f32 cuda; ctx (2,L,Dc) f32 cuda -> q,k,v each
+        [n][2][tokens][heads*head_dim] in the compute dtype."""
+        self._check_inputs(latents, noise, ctx)
+        n = latents.shape[0]
         with torch.cuda.device(self.device):
             need = self.workspace_bytes(n)
             if need == 0:
                 raise _lib.DsimError(f"{n} images do not fit one call (an activation would reach 2 GiB): at most "
                                      f"{self.max_images()} images per call for this graph")
-            # dsim_unet_qkv keeps no per-call state in the handle, so independent batches may be in flight on several
-            # streams at once (one host thread): each stream gets its own workspace arena
-            sid = _stream_ptr()
-            ws = self._ws_by_stream.get(sid)
-            if ws is None or ws.numel() < need:
-                self._ws_by_stream.pop(sid, None)
-                self._graphs.clear()                 # captured graphs hold the old arena's addresses
-                ws = self._ws_by_stream[sid] = torch.empty(need, dtype=torch.uint8, device=self.device)
-            self._ws = ws
+            self._arena(need)
             shape = (n, 2, self.tokens, self.heads * self.head_dim)
             if self.use_graphs and out is None and not self._profiling:
                 return self._replay(latents, noise, float(sqrt_abar), float(sqrt_1m_abar), ctx, shape)
@@ -270,6 +279,80 @@ class UNetEngine:
                 out = tuple(torch.empty((3,) + tuple(shape), dtype=self.dtype, device=self.device).unbind(0))    # one allocation: the tapped q | k | v projection is then one launch
             self._launch(latents, noise, float(sqrt_abar), float(sqrt_1m_abar), ctx, out)
         return out
+
+    # ---- tap sweeps: the q,k,v of several taps from one forward (dsim_unet_qkv_taps) -------------------------------
+    def _taps_c(self, taps):
+        """[(target_block, target_layer)] in the reference's addressing (set_tap's) -> a dsim_tap array"""
+        arr = (_lib.TapC * max(1, len(taps)))()
+        for i, tap in enumerate(taps):
+            try:
+                block, layer = tap
+                tl, ta, tt = resolve_tap(self.cfg, block, layer)
+                arr[i].block, arr[i].layer, arr[i].attn, arr[i].tfm = _lib.TAP[block], tl, ta, tt
+            except (KeyError, IndexError, TypeError, ValueError):
+                raise _lib.DsimError(f"unknown tap {tap!r}") from None
+        return arr
+
+    def tap_shape(self, target_block: str, target_layer) -> Tuple[int, int, int]:
+        """(tokens, heads, head_dim) of a tap at the current latent side; the handle's own tap does not move."""
+        n, h, d = C.c_int(), C.c_int(), C.c_int()
+        arr = self._taps_c([(target_block, target_layer)])
+        _lib.check(self.L.dsim_unet_tap_shape_at(self._h, arr, C.byref(n), C.byref(h), C.byref(d)),
+                   f"tap {target_block} {target_layer}")
+        return n.value, h.value, d.value
+
+    def taps_workspace_bytes(self, n_images: int, taps) -> int:
+        """Workspace of one qkv_taps call over n_images (0: the call is impossible -- see dsim_unet_taps_workspace_bytes)."""
+        return int(self.L.dsim_unet_taps_workspace_bytes(self._h, n_images, len(taps), self._taps_c(taps)))
+
+    def max_images_taps(self, taps, upper: int = 4096) -> int:
+        """Largest n_images one qkv_taps call over `taps` accepts (every activation and tap output < 2 GiB); cached per tap set
+        and latent side."""
+        key = (tuple((b, str(l)) for b, l in taps), self.sample_size)
+        cache = self.__dict__.setdefault("_max_images_taps", {})
+        if key not in cache:
+            fits = lambda m: self.taps_workspace_bytes(m, taps) > 0
+            if not fits(1):
+                cache[key] = 0
+            elif fits(upper):
+                cache[key] = upper
+            else:
+                lo, hi = 1, upper
+                while hi - lo > 1:
+                    mid = (lo + hi) // 2
+                    lo, hi = (mid, hi) if fits(mid) else (lo, mid)
+                cache[key] = lo
+        return cache[key]
+
+    def qkv_taps(self, latents: torch.Tensor, noise: torch.Tensor, sqrt_abar: float, sqrt_1m_abar: float, ctx: torch.Tensor,
+                 taps) -> List[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]]:
+        """qkv() at every tap of `taps` ([(target_block, target_layer)], any order, no repeats) from ONE forward to the deepest
+        of them: entry i is bit for bit what qkv() returns with the tap at taps[i].  The handle's own tap does not move.  Runs
+        eagerly (no hipGraph), on the calling stream's workspace arena."""
+        self._check_inputs(latents, noise, ctx)
+        n, nt = latents.shape[0], len(taps)
+        if nt < 1:
+            raise _lib.DsimError("qkv_taps: no taps")
+        arr = self._taps_c(taps)
+        with torch.cuda.device(self.device):
+            need = self.taps_workspace_bytes(n, taps)
+            shapes = [self.tap_shape(b, l) if need else (1, 1, 1) for b, l in taps]
+            if need:
+                ws = self._arena(need)
+            else:
+                # impossible call: dsim_unet_qkv_taps names the reason (an invalid, repeated or unloaded tap) before it enqueues
+                # anything; a workspace refusal means the batch is too large
+                ws = torch.empty(256, dtype=torch.uint8, device=self.device)
+            outs = [tuple(torch.empty((3, n, 2, t, h * d), dtype=self.dtype, device=self.device).unbind(0)) for t, h, d in shapes]
+            ptr = lambda j: (C.c_void_p * nt)(*[o[j].data_ptr() for o in outs])
+            st = self.L.dsim_unet_qkv_taps(self._h, latents.data_ptr(), noise.data_ptr(), float(sqrt_abar), float(sqrt_1m_abar),
+                                           ctx.data_ptr(), n, nt, arr, ptr(0), ptr(1), ptr(2), ws.data_ptr(),
+                                           ws.numel() if need else 0, _stream_ptr())
+            if not need and st in (0, -3):
+                raise _lib.DsimError(f"{n} images do not fit one sweep call (an activation or a tap output would reach 2 GiB): at "
+                                     f"most {self.max_images_taps(taps)} images per call for these taps")
+            _lib.check(st, "dsim_unet_qkv_taps")
+        return outs
 
     def _launch(self, latents, noise, sa, sb, ctx, out):
         q, k, v = out
@@ -888,3 +971,52 @@ class DiTEngine:
                                            k.data_ptr(), v.data_ptr(), self._ws.data_ptr(), self._ws.numel(), _stream_ptr()),
                        "dsim_dit_qkv")
         return q, k, v
+
+    # ---- tap sweeps: the q,k,v of several blocks from one forward (dsim_dit_qkv_taps) ----------------------------------
+    def taps_workspace_bytes(self, n_images: int, layers) -> int:
+        """Workspace of one qkv_taps call over n_images (0: the call is impossible -- see dsim_dit_taps_workspace_bytes)."""
+        arr = (C.c_int * max(1, len(layers)))(*[int(l) for l in layers])
+        return int(self.L.dsim_dit_taps_workspace_bytes(self._h, n_images, len(layers), arr))
+
+    def max_images_taps(self, layers, upper: int = 4096) -> int:
+        """Largest n_images one qkv_taps call accepts (every activation and tap output < 2 GiB)."""
+        fits = lambda m: self.taps_workspace_bytes(m, layers) > 0
+        if not fits(1):
+            return 0
+        lo, hi = 1, upper
+        if fits(hi):
+            return hi
+        while hi - lo > 1:
+            mid = (lo + hi) // 2
+            lo, hi = (mid, hi) if fits(mid) else (lo, mid)
+        return lo
+
+    def qkv_taps(self, latents: torch.Tensor, noise: torch.Tensor, sa: float, sb: float, layers):
+        """qkv() at every block of `layers` (any order, no repeats) from ONE forward to the deepest: entry i is bit for bit what
+        qkv() returns with the tap at layers[i].  The handle's own tap does not move."""
+        _require_cuda(latents, noise)
+        n, nt = latents.shape[0], len(layers)
+        s = self.cfg.input_size
+        if tuple(latents.shape) != (n, self.cfg.in_channels, s, s) or latents.dtype != torch.float32 or noise.shape != latents.shape:
+            raise _lib.DsimError(f"latents/noise must be float32 (n,{self.cfg.in_channels},{s},{s})")
+        if nt < 1:
+            raise _lib.DsimError("qkv_taps: no taps")
+        try:
+            arr = (C.c_int * nt)(*[int(l) for l in layers])
+        except (TypeError, ValueError):
+            raise _lib.DsimError(f"unknown taps {layers!r}") from None
+        with torch.cuda.device(self.device):
+            need = self.taps_workspace_bytes(n, layers)
+            if need and (self._ws is None or self._ws.numel() < need):
+                self._ws = None
+                self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            ws = self._ws if need else torch.empty(256, dtype=torch.uint8, device=self.device)
+            shape = (n, 2, self.tokens, self.cfg.hidden_size) if need else (1,)
+            outs = [tuple(torch.empty(shape, dtype=self.dtype, device=self.device) for _ in range(3)) for _ in range(nt)]
+            ptr = lambda j: (C.c_void_p * nt)(*[o[j].data_ptr() for o in outs])
+            st = self.L.dsim_dit_qkv_taps(self._h, latents.data_ptr(), noise.data_ptr(), float(sa), float(sb), n, nt, arr, ptr(0),
+                                          ptr(1), ptr(2), ws.data_ptr(), ws.numel() if need else 0, _stream_ptr())
+            if not need and st in (0, -3):
+                raise _lib.DsimError(f"{n} images do not fit one sweep call (an activation or a tap output would reach 2 GiB)")
+            _lib.check(st, "dsim_dit_qkv_taps")
+        return outs

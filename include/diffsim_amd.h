@@ -144,6 +144,27 @@ int  dsim_unet_tap_shape(const dsim_unet* h, int* tokens, int* heads, int* head_
  * --target_block/--target_layer sweeps (diffsim/diffsim.py:122-145, diffsim/diffsim_xl.py:88-107).
  * DSIM_ERR_MISSING_WEIGHT when a parameter needed before the new tap was never loaded (the old tap stays). */
 int  dsim_unet_set_tap(dsim_unet* h, int tap_block, int tap_layer, int tap_attn, int tap_tfm);
+
+/* ---- tap sweeps: the q,k,v of several taps from ONE forward --------------------------------------------------------
+ * A tap named per call; the fields mean what the dsim_unet_cfg fields of the same names mean (block: dsim_tap_block,
+ * layer: absolute block index, attn / tfm: -1 = the last). */
+typedef struct dsim_tap { int32_t block, layer, attn, tfm; } dsim_tap;
+/* geometry of `tap` (tokens, heads, head_dim) at the handle's current latent side; DSIM_ERR_INVALID for a tap the graph has not */
+int    dsim_unet_tap_shape_at(const dsim_unet* h, const dsim_tap* tap, int* tokens, int* heads, int* head_dim);
+/* Workspace of one dsim_unet_qkv_taps call: never more than the deepest tap's dsim_unet_workspace_bytes (the captures go to the
+ * caller's tensors).  0 when the call is impossible: an invalid, duplicate or unloaded tap, or an activation or a tap output of
+ * n_images that would reach 2 GiB. */
+size_t dsim_unet_taps_workspace_bytes(const dsim_unet* h, int n_images, int n_taps, const dsim_tap* taps);
+/* dsim_unet_qkv for n_taps taps (any order) in ONE walk to the deepest of them: q[i], k[i], v[i] receive what dsim_unet_qkv writes
+ * with its tap at taps[i], bit for bit.  At each shallower tap the walk runs that block's norm1 and q/k/v projection as a walk that
+ * stops there does (DSIM_FUSE_TAPQKV when q[i], k[i], v[i] lie at equal distances), then carries on exactly as a walk that passes
+ * the block (its own projection into its own buffer).  The handle's tap is neither read nor moved; CFG de-duplication is off when
+ * any tap lies in the first down block.  Checked before anything is enqueued: DSIM_ERR_INVALID for n_taps < 1, a duplicate or an
+ * invalid tap, DSIM_ERR_MISSING_WEIGHT for a parameter missing before the deepest tap, DSIM_ERR_WORKSPACE for a short workspace.
+ * Profile records (dsim_unet_profile) cover every launch of the call. */
+int    dsim_unet_qkv_taps(dsim_unet* h, const float* latents, const float* noise, float sqrt_abar, float sqrt_1m_abar,
+                          const float* ctx, int n_images, int n_taps, const dsim_tap* taps, void* const* q, void* const* k,
+                          void* const* v, void* workspace, size_t workspace_bytes, void* stream);
 /* Opt-in: compute what the two classifier-free-guidance halves share once.  The reference runs torch.cat([latents] * 2)
  * through the whole U-Net (diffsim_pipeline.py:208-221); conv_in, the first ResnetBlock2D and the first transformer up to its
  * cross-attention query see two bit-identical halves (one time embedding: SD1.5 graphs only; ignored for SDXL and when the tap
@@ -304,6 +325,15 @@ int    dsim_dit_set_tap(dsim_dit* h, int tap_layer);
  * q,k,v (out): compute dtype [n_images][2][tokens][heads*head_dim] */
 int    dsim_dit_qkv(dsim_dit* h, const float* latents, const float* noise, float sqrt_abar, float sqrt_1m_abar,
                     int n_images, void* q, void* k, void* v, void* workspace, size_t workspace_bytes, void* stream);
+/* Tap sweep: dsim_dit_qkv for the blocks layers[0..n_taps) (any order) in ONE walk to the deepest, q[i], k[i], v[i] bit for bit
+ * what dsim_dit_qkv writes with its tap at layers[i].  A shallower tap is captured by the three row-block projections of the tap
+ * path; the block then runs its fused qkv projection as usual.  The handle's tap is neither read nor moved.  Errors as
+ * dsim_unet_qkv_taps (a layer outside [0, depth) or a duplicate: DSIM_ERR_INVALID); the workspace query returns 0 for them and
+ * for a tap output of n_images that would reach 2 GiB. */
+size_t dsim_dit_taps_workspace_bytes(const dsim_dit* h, int n_images, int n_taps, const int* layers);
+int    dsim_dit_qkv_taps(dsim_dit* h, const float* latents, const float* noise, float sqrt_abar, float sqrt_1m_abar,
+                         int n_images, int n_taps, const int* layers, void* const* q, void* const* k, void* const* v,
+                         void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- the arithmetic either side of the VAE encoder, on the device (the host only decodes and resizes) ----
  * dsim_image_preprocess: what process_image does after its Lanczos resize (diffsim/diffsim.py:31-41): pixels u8 [n][H][W][3] ->
