@@ -103,6 +103,11 @@ SYMBOLS = {
     "dsim_unet_taps_workspace_bytes": (_sz, [_vp, _i, _i, C.POINTER(TapC)]),
     "dsim_unet_qkv_taps": (_i, [_vp, _vp, _vp, _f, _f, _vp, _i, _i, C.POINTER(TapC), C.POINTER(_vp), C.POINTER(_vp),
                                 C.POINTER(_vp), _vp, _sz, _vp]),
+    "dsim_unet_ctx_workspace_bytes": (_sz, [_vp, _i, _i]),
+    "dsim_unet_taps_ctx_workspace_bytes": (_sz, [_vp, _i, _i, _i, C.POINTER(TapC)]),
+    "dsim_unet_qkv_ctx": (_i, [_vp, _vp, _vp, _f, _f, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dsim_unet_qkv_taps_ctx": (_i, [_vp, _vp, _vp, _f, _f, _vp, _i, _vp, _i, _i, C.POINTER(TapC), C.POINTER(_vp), C.POINTER(_vp),
+                                    C.POINTER(_vp), _vp, _sz, _vp]),
     "dsim_unet_set_sample_size": (_i, [_vp, _i]),
     "dsim_unet_set_cfg_dedup": (_i, [_vp, _i]),
     "dsim_unet_set_fusion": (_i, [_vp, _i]),

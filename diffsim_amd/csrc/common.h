@@ -238,6 +238,9 @@ bool conv_in_rows_applies(int Cin, int S, int Cout);
 int conv_in_rows(const float* images, const float* w /*[27][128]*/, const float* bias, void* out, int dtype, int n_img, int S,
                  float* gn_part, hipStream_t st);
 int convert_f32_to(const float* src, void* dst, int dtype, size_t n, hipStream_t s);
+// per-element prompt contexts: dst[(2 img + cfg)][per] = ctx[clamp(index[img], 0, n_ctx - 1)][cfg][per] in the compute dtype, each
+// value converted as convert_f32_to converts it (ctx f32 [n_ctx][2][per], index int32 device [n_images], per = ctx_len * Dc)
+int gather_ctx(const float* ctx, int n_ctx, const int32_t* index, void* dst, int dtype, int n_images, size_t per, hipStream_t s);
 // out[2b], out[2b+1] = in[b]: a batch element becomes its two classifier-free-guidance copies (bytes_per_elem % 16 == 0)
 int dup_batch(const void* in, void* out, int n_batch, size_t bytes_per_elem, hipStream_t s);
 // token-major nearest-neighbour resize [B][Hin][Win][C] -> [B][Hout][Wout][C] (row_bytes = C * element size, % 16 == 0), source

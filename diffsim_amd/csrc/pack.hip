@@ -507,6 +507,27 @@ int convert_f32_to(const float* src, void* dst, int dtype, size_t n, hipStream_t
     return DSIM_OK;
 }
 
+namespace {
+// one thread per output element; the table row is clamped into [0, n_ctx), so a bad index reads a valid context, never past the table
+__global__ void gather_ctx_kernel(const float* __restrict__ ctx, int n_ctx, const int32_t* __restrict__ index, void* dst, int ddt,
+                                  size_t per, size_t total) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const size_t b = i / per, r = i - b * per;               // b = 2 img + cfg
+    const int c = min(max(index[b >> 1], 0), n_ctx - 1);
+    st_any(dst, ddt, i, ctx[((size_t)c * 2 + (b & 1)) * per + r]);
+}
+}  // namespace
+
+int gather_ctx(const float* ctx, int n_ctx, const int32_t* index, void* dst, int dtype, int n_images, size_t per, hipStream_t s) {
+    if (!ctx || !index || !dst || n_ctx < 1 || n_images < 1 || per < 1) return DSIM_ERR_INVALID;
+    const size_t total = (size_t)2 * n_images * per;
+    hipLaunchKernelGGL(gather_ctx_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, ctx, n_ctx, index, dst, dtype, per,
+                       total);
+    DSIM_HIP_CHECK(hipGetLastError());
+    return DSIM_OK;
+}
+
 // ---- host-adjacent arithmetic of the path, kept on the device so that decoded pixels are the only thing the host produces ----
 namespace {
 

@@ -60,10 +60,13 @@ struct Walk {
     int B2;                 // U-Net batch = 2 * images (CFG)
     bool run;               // false: plan only
     void* gn_scratch = nullptr;
-    void* ctx_t = nullptr;  // [2][L][Dc] compute dtype
+    void* ctx_t = nullptr;  // [2][L][Dc] compute dtype; with a context table, [B2][L][Dc] (one context per batch element)
     std::vector<TapReq> taps;   // where q, k, v are captured; the walk ends at the deepest of them
     int n_captured = 0;
     bool tapped = false;        // every tap captured
+    int n_ctx = 1;              // prompt contexts of the call: > 1 = a table of [uncond, cond] pairs, one row per image
+    const int32_t* ctx_index = nullptr;     // device int32 [images]: each image's row of the table (n_ctx > 1)
+    bool mixed() const { return n_ctx > 1; }
 
     size_t es() const { return dtype_size(h->dt); }
     size_t max_tensor = 0;      // largest single activation (bytes): the kernels address tensors with 32-bit offsets
@@ -309,7 +312,7 @@ struct Walk {
             const bool ff1 = h->pk.count(b + "ff.stream") && (h->fusion & DSIM_FUSE_FF);
             big = alloc_act((size_t)M * (ff1 ? 3 : 4) * C);
             ab = alloc_act((size_t)M * C);
-            kvb = alloc_act((size_t)2 * L * 2 * C);
+            kvb = alloc_act((size_t)(mixed() ? Bfull : 2) * L * 2 * C);
         }
         if (!last) fq = ln_proj(hbx, l1w, l1b, b + "attn1.qkv.stream", big, Mx, 3 * C);
         if (fq < 0) return fq;
@@ -345,7 +348,8 @@ struct Walk {
             CK(attn(a));
         }
         CK(linear(pre ? abh : ab, C, nullptr, 0, o1w, o1b, hbx, hbx, Mx, C, C));
-        // cross-attention against the prompt context: batch element b uses ctx[b % 2]
+        // cross-attention against the prompt context: batch element b uses ctx[b % 2]; with a context table (n_ctx > 1),
+        // ctx[index[b / 2]][b % 2], gathered per batch element in go()
         {
             const int f2 = ln_proj(hbx, l2w, l2b, b + "attn2.to_q.stream", pre ? abh : ab, Mx, C);
             if (f2 < 0) return f2;
@@ -367,12 +371,14 @@ struct Walk {
                 CK(st);
             }
         }
-        CK(linear(ctx_t, Dc, nullptr, 0, kv2, nullptr, nullptr, kvb, 2 * L, 2 * C, 2 * C));
+        // (a context table: every batch element projects its own context, B2 * L rows, and attends to its own K / V)
+        const int Bkv = mixed() ? B2 : 2;
+        CK(linear(ctx_t, Dc, nullptr, 0, kv2, nullptr, nullptr, kvb, Bkv * L, 2 * C, 2 * C));
         {
             AttnArgs a;
             a.q = ab; a.ldq = C;
             a.k = kvb; a.v = (char*)kvb + (size_t)C * es(); a.ldk = 2 * C;
-            a.out = big; a.ldo = C; a.B = B2; a.Bkv = 2; a.H = H; a.Nq = HW; a.Nk = L; a.D = D;
+            a.out = big; a.ldo = C; a.B = B2; a.Bkv = Bkv; a.H = H; a.Nq = HW; a.Nk = L; a.D = D;
             CK(attn(a));
         }
         CK(linear(big, C, nullptr, 0, o2w, o2b, hb, hb, M, C, C));
@@ -408,8 +414,20 @@ struct Walk {
         const int nl = c.n_levels, S = c.sample_size, ch0 = c.block_out_channels[0];
         const int L = c.ctx_len, Dc = c.cross_attention_dim;
         gn_scratch = ar->alloc(groupnorm_scratch_bytes(B2, c.norm_num_groups));
-        ctx_t = ar->alloc((size_t)2 * L * Dc * es());
-        if (run) CK(convert_f32_to(ctx, ctx_t, h->dt, (size_t)2 * L * Dc, s));
+        if (mixed()) {
+            // one [uncond, cond] context per image, in the [image][cfg] order of the batch: every cross-attention's K / V projection
+            // then runs on B2 * L rows (nothing before the first cross-attention depends on the prompt)
+            ctx_t = alloc_act((size_t)B2 * L * Dc);
+            if (run) {
+                pbegin(std::string("ctx_gather_") + dtn(), 0.0, (double)B2 * L * Dc * (4.0 + es()));
+                const int st = gather_ctx(ctx, n_ctx, ctx_index, ctx_t, h->dt, B2 / 2, (size_t)L * Dc, s);
+                pend();
+                CK(st);
+            }
+        } else {
+            ctx_t = ar->alloc((size_t)2 * L * Dc * es());
+            if (run) CK(convert_f32_to(ctx, ctx_t, h->dt, (size_t)2 * L * Dc, s));
+        }
         WGET(ciw, "conv_in.weight"); WGET(cib, "conv_in.bias");
         Act x{alloc_act((size_t)B2 * S * S * ch0), ch0, S, S};
         if (run) {
@@ -794,34 +812,55 @@ static int check_taps(const dsim_unet* h, int n_images, int n_taps, const dsim_t
 }
 
 // dry walk to the deepest of `taps`: peak arena bytes and the largest activation
-static int plan_taps(dsim_unet* h, int n_images, const std::vector<TapReq>& taps, size_t* peak, size_t* max_tensor) {
+static int plan_taps(dsim_unet* h, int n_images, const std::vector<TapReq>& taps, size_t* peak, size_t* max_tensor, int n_ctx = 1) {
     Arena ar;
     Walk w{h, &ar, nullptr, 2 * n_images, false};
     w.taps = taps;
+    w.n_ctx = n_ctx;
     CK(w.go(nullptr, nullptr, 0.f, 0.f, nullptr));
     *peak = ar.peak;
     *max_tensor = w.max_tensor;
     return DSIM_OK;
 }
 
-size_t dsim_unet_workspace_bytes(const dsim_unet* hc, int n_images) {
-    dsim_unet* h = const_cast<dsim_unet*>(hc);
-    if (!h || !h->finalized || n_images < 1) return 0;
+// a context table of n_ctx rows: SD1.5-family handles only.  SDXL's pooled prompt embedding enters the time embedding, which
+// reaches every resnet as a per-CFG-half bias: one prompt per call there.
+static bool ctx_table_ok(const dsim_unet* h, int n_ctx) {
+    return n_ctx == 1 || (n_ctx > 1 && !h->two_temb && !h->cfg.addition_embed);
+}
+
+static size_t workspace_bytes(dsim_unet* h, int n_images, int n_ctx) {
+    if (!h || !h->finalized || n_images < 1 || !ctx_table_ok(h, n_ctx)) return 0;
     size_t peak, big;
-    if (plan_taps(h, n_images, cfg_taps(h->cfg), &peak, &big) != DSIM_OK) return 0;
+    if (plan_taps(h, n_images, cfg_taps(h->cfg), &peak, &big, n_ctx) != DSIM_OK) return 0;
     if (big >= 0x7fffffffull) return 0;      // a >= 2 GiB activation: the batch does not fit one call
     return peak + 256;
 }
 
-size_t dsim_unet_taps_workspace_bytes(const dsim_unet* hc, int n_images, int n_taps, const dsim_tap* taps) {
-    dsim_unet* h = const_cast<dsim_unet*>(hc);
-    if (!h || !h->finalized || n_images < 1) return 0;
+static size_t taps_workspace_bytes(dsim_unet* h, int n_images, int n_ctx, int n_taps, const dsim_tap* taps) {
+    if (!h || !h->finalized || n_images < 1 || !ctx_table_ok(h, n_ctx)) return 0;
     std::vector<TapReq> req;
     size_t out_bytes, peak, big;
     if (check_taps(h, n_images, n_taps, taps, &req, &out_bytes) != DSIM_OK) return 0;
-    if (plan_taps(h, n_images, req, &peak, &big) != DSIM_OK) return 0;
+    if (plan_taps(h, n_images, req, &peak, &big, n_ctx) != DSIM_OK) return 0;
     if (big >= 0x7fffffffull || out_bytes >= 0x7fffffffull) return 0;
     return peak + 256;
+}
+
+size_t dsim_unet_workspace_bytes(const dsim_unet* hc, int n_images) {
+    return workspace_bytes(const_cast<dsim_unet*>(hc), n_images, 1);
+}
+
+size_t dsim_unet_ctx_workspace_bytes(const dsim_unet* hc, int n_images, int n_ctx) {
+    return workspace_bytes(const_cast<dsim_unet*>(hc), n_images, n_ctx);
+}
+
+size_t dsim_unet_taps_workspace_bytes(const dsim_unet* hc, int n_images, int n_taps, const dsim_tap* taps) {
+    return taps_workspace_bytes(const_cast<dsim_unet*>(hc), n_images, 1, n_taps, taps);
+}
+
+size_t dsim_unet_taps_ctx_workspace_bytes(const dsim_unet* hc, int n_images, int n_ctx, int n_taps, const dsim_tap* taps) {
+    return taps_workspace_bytes(const_cast<dsim_unet*>(hc), n_images, n_ctx, n_taps, taps);
 }
 
 int dsim_unet_tap_shape(const dsim_unet* h, int* tokens, int* heads, int* head_dim) {
@@ -882,7 +921,8 @@ static bool align_workspace(void*& ws, size_t& bytes) {
 
 // one walk to the deepest of `taps` (their outputs set), every check before the first launch
 static int run_taps(dsim_unet* h, const float* latents, const float* noise, float sqrt_abar, float sqrt_1m_abar, const float* ctx,
-                    int n_images, const std::vector<TapReq>& taps, void* workspace, size_t workspace_bytes, void* stream) {
+                    int n_images, const std::vector<TapReq>& taps, void* workspace, size_t workspace_bytes, void* stream,
+                    int n_ctx = 1, const int32_t* ctx_index = nullptr) {
     Arena ar;
     ar.dry = false;
     if (!align_workspace(workspace, workspace_bytes)) return DSIM_ERR_WORKSPACE;
@@ -890,11 +930,13 @@ static int run_taps(dsim_unet* h, const float* latents, const float* noise, floa
     ar.cap = workspace_bytes;
     {   // refuse up front instead of failing mid-graph
         size_t peak, big;
-        CK(plan_taps(h, n_images, taps, &peak, &big));
+        CK(plan_taps(h, n_images, taps, &peak, &big, n_ctx));
         if (peak > ar.cap) return DSIM_ERR_WORKSPACE;
     }
     Walk w{h, &ar, (hipStream_t)stream, 2 * n_images, true};
     w.taps = taps;
+    w.n_ctx = n_ctx;
+    w.ctx_index = ctx_index;
     CK(w.go(latents, noise, sqrt_abar, sqrt_1m_abar, ctx));
     if (ar.overflow) return DSIM_ERR_WORKSPACE;
     return w.tapped ? DSIM_OK : DSIM_ERR_INVALID;
@@ -909,10 +951,11 @@ int dsim_unet_qkv(dsim_unet* h, const float* latents, const float* noise, float 
                     stream);
 }
 
-int dsim_unet_qkv_taps(dsim_unet* h, const float* latents, const float* noise, float sqrt_abar, float sqrt_1m_abar, const float* ctx,
-                       int n_images, int n_taps, const dsim_tap* taps, void* const* q, void* const* k, void* const* v, void* workspace,
-                       size_t workspace_bytes, void* stream) {
+static int qkv_taps(dsim_unet* h, const float* latents, const float* noise, float sqrt_abar, float sqrt_1m_abar, const float* ctx,
+                    int n_ctx, const int32_t* ctx_index, int n_images, int n_taps, const dsim_tap* taps, void* const* q, void* const* k,
+                    void* const* v, void* workspace, size_t workspace_bytes, void* stream) {
     if (!h || !latents || !noise || !ctx || !q || !k || !v || !workspace || n_images < 1) return DSIM_ERR_INVALID;
+    if (n_ctx < 1 || (n_ctx > 1 && !ctx_index) || !ctx_table_ok(h, n_ctx)) return DSIM_ERR_INVALID;
     if (!h->finalized || h->timestep < 0) return DSIM_ERR_STATE;
     std::vector<TapReq> req;
     size_t out_bytes;
@@ -921,7 +964,32 @@ int dsim_unet_qkv_taps(dsim_unet* h, const float* latents, const float* noise, f
         if (!q[i] || !k[i] || !v[i]) return DSIM_ERR_INVALID;
         req[i].q = q[i]; req[i].k = k[i]; req[i].v = v[i];
     }
-    return run_taps(h, latents, noise, sqrt_abar, sqrt_1m_abar, ctx, n_images, req, workspace, workspace_bytes, stream);
+    return run_taps(h, latents, noise, sqrt_abar, sqrt_1m_abar, ctx, n_images, req, workspace, workspace_bytes, stream, n_ctx,
+                    n_ctx > 1 ? ctx_index : nullptr);
+}
+
+int dsim_unet_qkv_taps(dsim_unet* h, const float* latents, const float* noise, float sqrt_abar, float sqrt_1m_abar, const float* ctx,
+                       int n_images, int n_taps, const dsim_tap* taps, void* const* q, void* const* k, void* const* v, void* workspace,
+                       size_t workspace_bytes, void* stream) {
+    return qkv_taps(h, latents, noise, sqrt_abar, sqrt_1m_abar, ctx, 1, nullptr, n_images, n_taps, taps, q, k, v, workspace,
+                    workspace_bytes, stream);
+}
+
+int dsim_unet_qkv_ctx(dsim_unet* h, const float* latents, const float* noise, float sqrt_abar, float sqrt_1m_abar, const float* ctx,
+                      int n_ctx, const int32_t* ctx_index, int n_images, void* q, void* k, void* v, void* workspace,
+                      size_t workspace_bytes, void* stream) {
+    if (!h || !latents || !noise || !ctx || !q || !k || !v || !workspace || n_images < 1) return DSIM_ERR_INVALID;
+    if (n_ctx < 1 || (n_ctx > 1 && !ctx_index) || !ctx_table_ok(h, n_ctx)) return DSIM_ERR_INVALID;
+    if (!h->finalized || h->timestep < 0) return DSIM_ERR_STATE;
+    return run_taps(h, latents, noise, sqrt_abar, sqrt_1m_abar, ctx, n_images, cfg_taps(h->cfg, q, k, v), workspace, workspace_bytes,
+                    stream, n_ctx, n_ctx > 1 ? ctx_index : nullptr);
+}
+
+int dsim_unet_qkv_taps_ctx(dsim_unet* h, const float* latents, const float* noise, float sqrt_abar, float sqrt_1m_abar, const float* ctx,
+                           int n_ctx, const int32_t* ctx_index, int n_images, int n_taps, const dsim_tap* taps, void* const* q,
+                           void* const* k, void* const* v, void* workspace, size_t workspace_bytes, void* stream) {
+    return qkv_taps(h, latents, noise, sqrt_abar, sqrt_1m_abar, ctx, n_ctx, ctx_index, n_images, n_taps, taps, q, k, v, workspace,
+                    workspace_bytes, stream);
 }
 
 int dsim_unet_profile(dsim_unet* h, int enable) {

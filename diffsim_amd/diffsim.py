@@ -18,7 +18,7 @@ points work; the path-based ones raise.
 """
 from __future__ import annotations
 
-from typing import Callable, Dict, List, Optional, Sequence, Tuple, Union
+from typing import Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple, Union
 
 from concurrent.futures import ThreadPoolExecutor
 
@@ -49,6 +49,50 @@ def _norm_layer(target_layer) -> int:
         return 0
     # the reference indexes a ModuleList with the list itself -> TypeError; keep the error
     raise TypeError("list indices must be integers or slices, not list")
+
+
+class PromptTable(NamedTuple):
+    """The prompt contexts of one engine batch that carries a prompt per image: the distinct contexts (n_ctx, 2, L, Dc) f32 on the
+    device, in order of first appearance, and each image's row of that table."""
+    table: torch.Tensor
+    index: List[int]
+
+
+def single_prompt(prompt) -> bool:
+    """True for one prompt of the whole call (a string, a (2, L, Dc) context or a PromptTable already built), False for a sequence
+    with one entry per pair / triplet / image."""
+    return isinstance(prompt, (str, torch.Tensor, PromptTable))
+
+
+def distinct_prompts(prompts) -> Tuple[list, List[int]]:
+    """(the distinct entries of `prompts` in order of first appearance, each entry's position among them).  Strings are the same
+    prompt when equal, tensors when they are the same object."""
+    pos, firsts, index = {}, [], []
+    for p in prompts:
+        key = ("tensor", id(p)) if isinstance(p, torch.Tensor) else ("str", p)
+        if key not in pos:
+            pos[key] = len(firsts)
+            firsts.append(p)
+        index.append(pos[key])
+    return firsts, index
+
+
+def row_prompts(prompt, i0: int, i1: int, per_row: int):
+    """The prompts of rows [i0, i1) of a batched call image by image, each row's `per_row` images consecutive as
+    inputs.stack_rows lays them out; one prompt of the whole call stays as it is."""
+    if single_prompt(prompt):
+        return prompt
+    return [p for p in prompt[i0:i1] for _ in range(per_row)]
+
+
+def check_row_prompts(prompt, n_rows: int, what: str = "pairs"):
+    """A per-row prompt sequence as a list (ValueError unless it has one entry per row); one prompt of the call unchanged."""
+    if single_prompt(prompt):
+        return prompt
+    prompt = list(prompt)
+    if len(prompt) != n_rows:
+        raise ValueError(f"{len(prompt)} prompts for {n_rows} {what}: one prompt, or one per entry")
+    return prompt
 
 
 class DiffSim:
@@ -128,6 +172,28 @@ class DiffSim:
             self._ctx[prompt] = self._encode_prompt(prompt).to(self.device, torch.float32).contiguous()
         return self._ctx[prompt]
 
+    def prompt_table(self, prompts: Sequence[Union[str, torch.Tensor]]):
+        """The contexts of one engine batch from a prompt per image (strings or (2, L, Dc) tensors): the (2, L, Dc) context itself
+        when they all name one prompt, else a PromptTable of the distinct ones in order of first appearance, each encoded once
+        (through the context() cache)."""
+        firsts, index = distinct_prompts(prompts)
+        if not firsts:
+            raise ValueError("no prompts")
+        if len(firsts) == 1:
+            return self.context(firsts[0])
+        return PromptTable(torch.stack([self.context(p) for p in firsts]), index)
+
+    def _contexts(self, prompt, n: int):
+        """(ctx, ctx_index) of an engine call over n images: one prompt -> ((2, L, Dc), None); a prompt per image (n entries) or a
+        PromptTable -> (table, index), or the one context they all name."""
+        if not single_prompt(prompt):
+            prompt = self.prompt_table(check_row_prompts(prompt, n, "images"))
+        if isinstance(prompt, PromptTable):
+            if len(prompt.index) != n:
+                raise ValueError(f"a prompt table of {len(prompt.index)} images for {n} images")
+            return prompt.table, prompt.index
+        return self.context(prompt), None
+
     def prepare_image_latents(self, image, vae=None, device=None, generator=None):
         vae = vae or self.vae
         if vae is None:
@@ -155,9 +221,12 @@ class DiffSim:
     # ------------------------------------------------------------------------------------------
     @torch.no_grad()
     def features(self, latents: torch.Tensor, noise: torch.Tensor, prompt, target_block, target_layer, target_step):
-        """latents/noise (n,4,s,s) -> q,k,v [n][2][N][H*D] (compute dtype, on device)."""
+        """latents/noise (n,4,s,s) -> q,k,v [n][2][N][H*D] (compute dtype, on device).  prompt: one for every image (a string or
+        a (2, L, Dc) context), or a sequence of n, one per image: all prompts then run in ONE forward (a context table), each
+        image's rows bit for bit those of a call with its own prompt alone."""
         eng = self.engine(target_block, target_layer)
-        return eng.qkv(*self._forward_inputs(eng, latents, noise, prompt, target_step))
+        *args, idx = self._forward_inputs(eng, latents, noise, prompt, target_step)
+        return eng.qkv(*args, ctx_index=idx)
 
     @torch.no_grad()
     def features_taps(self, latents: torch.Tensor, noise: torch.Tensor, prompt, taps, target_step):
@@ -168,10 +237,12 @@ class DiffSim:
         if self._base is None:
             self.engine(*taps[0])
         eng = self._base                # the sweep does not move the handle's tap
-        return eng.qkv_taps(*self._forward_inputs(eng, latents, noise, prompt, target_step), [(b, int(l)) for b, l in taps])
+        *args, idx = self._forward_inputs(eng, latents, noise, prompt, target_step)
+        return eng.qkv_taps(*args, [(b, int(l)) for b, l in taps], ctx_index=idx)
 
     def _forward_inputs(self, eng, latents, noise, prompt, target_step):
-        """(latents, noise, sqrt_abar, sqrt_1m_abar, ctx) of the engine call at target_step; sets the engine's timestep."""
+        """(latents, noise, sqrt_abar, sqrt_1m_abar, ctx, ctx_index) of the engine call at target_step; sets the engine's
+        timestep.  ctx_index is None for one prompt, else each image's row of the context table ctx."""
         t = sched.timestep_from_index(int(target_step))
         eng.set_timestep(t)
         sa, sb = sched.noise_coefficients(t)
@@ -183,11 +254,13 @@ class DiffSim:
             a16, b16 = ac ** 0.5, (1 - ac) ** 0.5
             xt = a16.to(dev) * latents.to(dev, torch.float16) + b16.to(dev) * noise.to(dev, torch.float16)
             lat = xt.float().contiguous()
-            ctx16 = self.context(prompt).to(torch.float16).float()         # the fp16 text encoder's output
-            return lat, torch.zeros_like(lat), 1.0, 0.0, ctx16
+            ctx, idx = self._contexts(prompt, latents.shape[0])
+            ctx16 = ctx.to(torch.float16).float()         # the fp16 text encoder's output (elementwise: each context of a table alike)
+            return lat, torch.zeros_like(lat), 1.0, 0.0, ctx16, idx
         lat = latents.to(self.device, torch.float32).contiguous()
         nz = noise.to(self.device, torch.float32).contiguous()
-        return lat, nz, sa, sb, self.context(prompt)
+        ctx, idx = self._contexts(prompt, latents.shape[0])
+        return lat, nz, sa, sb, ctx, idx
 
     def auto_batch_pairs(self, eng, n_pairs: int, streams: int = 2, target: int = 64) -> int:
         """Pairs per chunk when the caller names none: `target` (the sweep's optimum on a 288 GB part), capped by the 2 GiB
@@ -209,6 +282,8 @@ class DiffSim:
                            target_step=600, similarity="cosine", batch_pairs: Optional[int] = None, streams: int = 2) -> torch.Tensor:
         """Batched latents-in scoring: pair i = (latA[i], latB[i]) -> scores (n,) f32 on device.
         noiseA/noiseB are (1,4,s,s) (shared by every pair: each reference call reseeds) or (n,4,s,s).
+        prompt: one for every pair, or a sequence of n (strings or (2, L, Dc) contexts), pair i's prompt: a chunk then runs its
+        pairs' prompts in one forward (each distinct one encoded once), and each score is bit for bit the one-prompt call's.
         Consecutive chunks of `batch_pairs` pairs are enqueued on `streams` HIP streams in turn, so the HBM-bound kernels of
         one chunk overlap the MFMA-bound kernels of the next (same kernels, same scores).  Each stream in use owns one
         workspace arena of the engine (streams = 2 -> two arenas, ~0.75 GB per pair of the chunk size each).
@@ -216,23 +291,25 @@ class DiffSim:
         603 at 16) within what fits: every activation < 2 GiB and the arenas of the streams in use inside the free HBM."""
         from .inputs import stack_rows
         n = latA.shape[0]
+        prompt = check_row_prompts(prompt, n)
         eng = self.engine(target_block, target_layer)
         out = torch.empty(n, dtype=torch.float32, device=self.device)
         if batch_pairs is None:
             batch_pairs = self.auto_batch_pairs(eng, n, streams)
-        batch_pairs = max(1, min(batch_pairs, eng.max_images() // 2))      # every activation must stay < 2 GiB
+        batch_pairs = max(1, min(batch_pairs, eng.max_images(n_ctx=1 if single_prompt(prompt) else 2) // 2))      # every activation must stay < 2 GiB
         starts = list(range(0, n, batch_pairs))
         ns = max(1, min(int(streams), len(starts)))
         if self.use_graphs or getattr(eng, "_profiling", False):
             ns = 1          # (per-launch profile brackets are only a kernel's own time when nothing overlaps it)
         main = torch.cuda.current_stream(self.device)
+        chunk_prompts = [row_prompts(prompt, i0, min(n, i0 + batch_pairs), 2) for i0 in starts]
         if ns > 1:
             if len(self._streams) < ns:
                 self._streams += [torch.cuda.Stream(device=self.device) for _ in range(ns - len(self._streams))]
             # everything the chunks share is produced on the main stream BEFORE the side streams fork from it: the prompt
-            # context and the timestep tables (set_timestep enqueues kernels; a later chunk on another stream would see
-            # "already set" on the host while those kernels are still running)
-            ctx_ready = self.context(prompt)
+            # contexts (every chunk's context table) and the timestep tables (set_timestep enqueues kernels; a later chunk on
+            # another stream would see "already set" on the host while those kernels are still running)
+            chunk_prompts = [self.context(p) if single_prompt(p) else self.prompt_table(p) for p in chunk_prompts]
             eng.set_timestep(sched.timestep_from_index(int(target_step)))
             for st in self._streams[:ns]:
                 st.wait_stream(main)
@@ -241,7 +318,7 @@ class DiffSim:
             m = i1 - i0
             with torch.cuda.stream(self._streams[ci % ns] if ns > 1 else main):
                 lat, nz = stack_rows([latA, latB], [noiseA, noiseB], i0, i1)
-                q, k, v = self.features(lat, nz, prompt if ns == 1 else ctx_ready, target_block, target_layer, target_step)
+                q, k, v = self.features(lat, nz, chunk_prompts[ci], target_block, target_layer, target_step)
                 ia = torch.arange(0, 2 * m, 2, dtype=torch.int32, device=self.device)
                 out[i0:i1] = pair_score(q, k, v, ia, ia + 1, eng.heads, similarity)
         if ns > 1:

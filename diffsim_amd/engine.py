@@ -52,6 +52,37 @@ def resolve_tap(cfg: UNetConfig, target_block: str, target_layer):
     return tl[0], tl[1], tl[2]
 
 
+def check_ctx_table(cfg: UNetConfig, ctx: torch.Tensor, ctx_index, n_images: int):
+    """The prompt contexts of one qkv / qkv_taps call, checked on the host: (n_ctx, index).  ctx is (2, L, Dc) -- one [uncond,
+    cond] pair for every image -- or a table (n_ctx, 2, L, Dc) with ctx_index, image i's row: a host sequence or tensor of n_images
+    values in [0, n_ctx).  index is None where one context serves every image (a table of one row, or (2, L, Dc)), else an int32
+    CPU tensor."""
+    L, Dc = cfg.ctx_len, cfg.cross_attention_dim
+    if ctx.ndim == 3:
+        if tuple(ctx.shape) != (2, L, Dc):
+            raise _lib.DsimError(f"ctx must be (2, {L}, {Dc}) or a table (n_ctx, 2, {L}, {Dc})")
+        n_ctx = 1
+    elif ctx.ndim == 4:
+        if tuple(ctx.shape[1:]) != (2, L, Dc) or ctx.shape[0] < 1:
+            raise _lib.DsimError(f"a context table must be (n_ctx, 2, {L}, {Dc}), got {tuple(ctx.shape)}")
+        n_ctx = int(ctx.shape[0])
+        if ctx_index is None:
+            raise _lib.DsimError("a context table needs ctx_index: each image's row")
+    else:
+        raise _lib.DsimError(f"ctx must be (2, {L}, {Dc}) or a table (n_ctx, 2, {L}, {Dc})")
+    if ctx_index is None:
+        return 1, None
+    idx = torch.as_tensor(ctx_index).reshape(-1)
+    if idx.is_floating_point() or idx.is_complex() or idx.dtype == torch.bool:
+        raise _lib.DsimError("ctx_index must hold integers")
+    idx = idx.cpu().to(torch.int64)
+    if idx.numel() != n_images:
+        raise _lib.DsimError(f"ctx_index has {idx.numel()} entries for {n_images} images")
+    if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= n_ctx):
+        raise _lib.DsimError(f"ctx_index values must lie in [0, {n_ctx})")
+    return n_ctx, (idx.to(torch.int32) if n_ctx > 1 else None)
+
+
 def _cfg_struct(cfg: UNetConfig, dtype: torch.dtype, tap_block: str, tap_layer) -> _lib.UNetCfgC:
     c = _lib.UNetCfgC()
     n = len(cfg.block_out_channels)
@@ -152,6 +183,7 @@ class UNetEngine:
         _lib.check(self.L.dsim_unet_set_cfg_dedup(self._h, int(bool(enable))), "dsim_unet_set_cfg_dedup")
         self._max_images = None
         self.__dict__.pop("_max_images_taps", None)
+        self.__dict__.pop("_max_images_ctx", None)
         self._graphs.clear()
 
     def set_fusion(self, mask: int):
@@ -160,6 +192,7 @@ class UNetEngine:
         _lib.check(self.L.dsim_unet_set_fusion(self._h, int(mask)), "dsim_unet_set_fusion")
         self._max_images = None
         self.__dict__.pop("_max_images_taps", None)
+        self.__dict__.pop("_max_images_ctx", None)
         self._graphs.clear()
 
     def view(self, target_block: str, target_layer) -> "TapView":
@@ -212,26 +245,37 @@ class UNetEngine:
             out.append((fam, fl.value, by.value, ms.value, shape) if detail else (fam, fl.value, by.value, ms.value))
         return out
 
-    def workspace_bytes(self, n_images: int) -> int:
-        return int(self.L.dsim_unet_workspace_bytes(self._h, n_images))
+    def workspace_bytes(self, n_images: int, n_ctx: int = 1) -> int:
+        """Workspace of one qkv() call over n_images with n_ctx prompt contexts (n_ctx > 1: a context table, whose per-image
+        contexts and K / V rows the arena holds too); 0 when the call is impossible."""
+        if n_ctx == 1:
+            return int(self.L.dsim_unet_workspace_bytes(self._h, n_images))
+        return int(self.L.dsim_unet_ctx_workspace_bytes(self._h, n_images, int(n_ctx)))
 
-    def max_images(self, upper: int = 4096) -> int:
+    def max_images(self, upper: int = 4096, n_ctx: int = 1) -> int:
         """Largest n_images one qkv() call accepts (every activation < 2 GiB); bisection over the dry-run planner,
-        cached (it depends on the graph only)."""
-        if getattr(self, "_max_images", None) is not None:
+        cached (it depends on the graph only, and on whether the call carries a context table)."""
+        if n_ctx == 1:
+            if getattr(self, "_max_images", None) is not None:
+                return self._max_images
+            self._max_images = self._max_images_search(upper)
             return self._max_images
-        self._max_images = self._max_images_search(upper)
-        return self._max_images
+        cache = self.__dict__.setdefault("_max_images_ctx", {})
+        key = (self.target_block, str(self.target_layer), self.sample_size)
+        if key not in cache:
+            cache[key] = self._max_images_search(upper, 2)
+        return cache[key]
 
-    def _max_images_search(self, upper: int) -> int:
-        if self.workspace_bytes(1) == 0:
+    def _max_images_search(self, upper: int, n_ctx: int = 1) -> int:
+        fits = lambda m: self.workspace_bytes(m, n_ctx) > 0
+        if not fits(1):
             return 0
         lo, hi = 1, upper
-        if self.workspace_bytes(hi):
+        if fits(hi):
             return hi
         while hi - lo > 1:
             mid = (lo + hi) // 2
-            if self.workspace_bytes(mid):
+            if fits(mid):
                 lo = mid
             else:
                 hi = mid
@@ -245,8 +289,18 @@ class UNetEngine:
                 noise.shape != latents.shape:
             raise _lib.DsimError(f"latents and noise must be (n,{self.cfg.in_channels},s,s)")
         self.set_sample_size(int(latents.shape[2]))
-        if tuple(ctx.shape) != (2, self.cfg.ctx_len, self.cfg.cross_attention_dim):
+        if ctx.ndim != 4 and tuple(ctx.shape) != (2, self.cfg.ctx_len, self.cfg.cross_attention_dim):
             raise _lib.DsimError("ctx must be (2, ctx_len, cross_attention_dim)")
+
+    def _ctx_args(self, ctx, ctx_index, n):
+        """(ctx, n_ctx, device index) of a call: one context -> ((2, L, Dc), 1, None), the existing entry points; a table of
+        several -> (table, n_ctx, int32 index uploaded on the calling stream), after the host-side checks."""
+        n_ctx, idx = check_ctx_table(self.cfg, ctx, ctx_index, n)
+        if n_ctx == 1:
+            return (ctx[0] if ctx.ndim == 4 else ctx), 1, None
+        if self.cfg.addition_embed:
+            raise _lib.DsimError("SDXL handles take one prompt per call: the pooled prompt embedding enters every resnet")
+        return ctx, n_ctx, idx.to(self.device)
 
     def _arena(self, need: int) -> torch.Tensor:
         # dsim_unet_qkv keeps no per-call state in the handle, so independent batches may be in flight on several
@@ -261,23 +315,26 @@ class UNetEngine:
         return ws
 
     def qkv(self, latents: torch.Tensor, noise: torch.Tensor, sqrt_abar: float, sqrt_1m_abar: float,
-            ctx: torch.Tensor, out: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None):
+            ctx: torch.Tensor, out: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None, ctx_index=None):
         """latents/noise (n,Cin,s,s) f32 cuda; ctx (2,L,Dc) f32 cuda -> q,k,v each
-        [n][2][tokens][heads*head_dim] in the compute dtype."""
+        [n][2][tokens][heads*head_dim] in the compute dtype.  Several prompts in one forward: ctx a table (n_ctx,2,L,Dc) f32 cuda
+        and ctx_index image i's row of it (host values in [0, n_ctx), checked here; check_ctx_table).  Image i's rows are then
+        bit for bit those of a call with ctx = table[ctx_index[i]]; a table of one row runs the one-prompt call."""
         self._check_inputs(latents, noise, ctx)
         n = latents.shape[0]
         with torch.cuda.device(self.device):
-            need = self.workspace_bytes(n)
+            ctx, n_ctx, idx = self._ctx_args(ctx, ctx_index, n)
+            need = self.workspace_bytes(n, n_ctx)
             if need == 0:
                 raise _lib.DsimError(f"{n} images do not fit one call (an activation would reach 2 GiB): at most "
-                                     f"{self.max_images()} images per call for this graph")
+                                     f"{self.max_images(n_ctx=n_ctx)} images per call for this graph")
             self._arena(need)
             shape = (n, 2, self.tokens, self.heads * self.head_dim)
             if self.use_graphs and out is None and not self._profiling:
-                return self._replay(latents, noise, float(sqrt_abar), float(sqrt_1m_abar), ctx, shape)
+                return self._replay(latents, noise, float(sqrt_abar), float(sqrt_1m_abar), ctx, shape, idx)
             if out is None:
                 out = tuple(torch.empty((3,) + tuple(shape), dtype=self.dtype, device=self.device).unbind(0))    # one allocation: the tapped q | k | v projection is then one launch
-            self._launch(latents, noise, float(sqrt_abar), float(sqrt_1m_abar), ctx, out)
+            self._launch(latents, noise, float(sqrt_abar), float(sqrt_1m_abar), ctx, out, idx)
         return out
 
     # ---- tap sweeps: the q,k,v of several taps from one forward (dsim_unet_qkv_taps) -------------------------------
@@ -301,17 +358,20 @@ class UNetEngine:
                    f"tap {target_block} {target_layer}")
         return n.value, h.value, d.value
 
-    def taps_workspace_bytes(self, n_images: int, taps) -> int:
-        """Workspace of one qkv_taps call over n_images (0: the call is impossible -- see dsim_unet_taps_workspace_bytes)."""
-        return int(self.L.dsim_unet_taps_workspace_bytes(self._h, n_images, len(taps), self._taps_c(taps)))
+    def taps_workspace_bytes(self, n_images: int, taps, n_ctx: int = 1) -> int:
+        """Workspace of one qkv_taps call over n_images (0: the call is impossible -- see dsim_unet_taps_workspace_bytes);
+        n_ctx > 1: with a context table (dsim_unet_taps_ctx_workspace_bytes)."""
+        if n_ctx == 1:
+            return int(self.L.dsim_unet_taps_workspace_bytes(self._h, n_images, len(taps), self._taps_c(taps)))
+        return int(self.L.dsim_unet_taps_ctx_workspace_bytes(self._h, n_images, int(n_ctx), len(taps), self._taps_c(taps)))
 
-    def max_images_taps(self, taps, upper: int = 4096) -> int:
-        """Largest n_images one qkv_taps call over `taps` accepts (every activation and tap output < 2 GiB); cached per tap set
-        and latent side."""
-        key = (tuple((b, str(l)) for b, l in taps), self.sample_size)
+    def max_images_taps(self, taps, upper: int = 4096, n_ctx: int = 1) -> int:
+        """Largest n_images one qkv_taps call over `taps` accepts (every activation and tap output < 2 GiB); cached per tap set,
+        latent side and whether the call carries a context table."""
+        key = (tuple((b, str(l)) for b, l in taps), self.sample_size) + ((("ctx",) if n_ctx > 1 else ()))
         cache = self.__dict__.setdefault("_max_images_taps", {})
         if key not in cache:
-            fits = lambda m: self.taps_workspace_bytes(m, taps) > 0
+            fits = lambda m: self.taps_workspace_bytes(m, taps, min(int(n_ctx), 2)) > 0
             if not fits(1):
                 cache[key] = 0
             elif fits(upper):
@@ -325,17 +385,18 @@ class UNetEngine:
         return cache[key]
 
     def qkv_taps(self, latents: torch.Tensor, noise: torch.Tensor, sqrt_abar: float, sqrt_1m_abar: float, ctx: torch.Tensor,
-                 taps) -> List[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]]:
+                 taps, ctx_index=None) -> List[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]]:
         """qkv() at every tap of `taps` ([(target_block, target_layer)], any order, no repeats) from ONE forward to the deepest
         of them: entry i is bit for bit what qkv() returns with the tap at taps[i].  The handle's own tap does not move.  Runs
-        eagerly (no hipGraph), on the calling stream's workspace arena."""
+        eagerly (no hipGraph), on the calling stream's workspace arena.  ctx / ctx_index: as qkv() takes them."""
         self._check_inputs(latents, noise, ctx)
         n, nt = latents.shape[0], len(taps)
         if nt < 1:
             raise _lib.DsimError("qkv_taps: no taps")
         arr = self._taps_c(taps)
         with torch.cuda.device(self.device):
-            need = self.taps_workspace_bytes(n, taps)
+            ctx, n_ctx, idx = self._ctx_args(ctx, ctx_index, n)
+            need = self.taps_workspace_bytes(n, taps, n_ctx)
             shapes = [self.tap_shape(b, l) if need else (1, 1, 1) for b, l in taps]
             if need:
                 ws = self._arena(need)
@@ -345,39 +406,57 @@ class UNetEngine:
                 ws = torch.empty(256, dtype=torch.uint8, device=self.device)
             outs = [tuple(torch.empty((3, n, 2, t, h * d), dtype=self.dtype, device=self.device).unbind(0)) for t, h, d in shapes]
             ptr = lambda j: (C.c_void_p * nt)(*[o[j].data_ptr() for o in outs])
-            st = self.L.dsim_unet_qkv_taps(self._h, latents.data_ptr(), noise.data_ptr(), float(sqrt_abar), float(sqrt_1m_abar),
-                                           ctx.data_ptr(), n, nt, arr, ptr(0), ptr(1), ptr(2), ws.data_ptr(),
-                                           ws.numel() if need else 0, _stream_ptr())
+            if n_ctx == 1:
+                st = self.L.dsim_unet_qkv_taps(self._h, latents.data_ptr(), noise.data_ptr(), float(sqrt_abar), float(sqrt_1m_abar),
+                                               ctx.data_ptr(), n, nt, arr, ptr(0), ptr(1), ptr(2), ws.data_ptr(),
+                                               ws.numel() if need else 0, _stream_ptr())
+            else:
+                st = self.L.dsim_unet_qkv_taps_ctx(self._h, latents.data_ptr(), noise.data_ptr(), float(sqrt_abar),
+                                                   float(sqrt_1m_abar), ctx.data_ptr(), n_ctx, idx.data_ptr(), n, nt, arr, ptr(0),
+                                                   ptr(1), ptr(2), ws.data_ptr(), ws.numel() if need else 0, _stream_ptr())
             if not need and st in (0, -3):
                 raise _lib.DsimError(f"{n} images do not fit one sweep call (an activation or a tap output would reach 2 GiB): at "
-                                     f"most {self.max_images_taps(taps)} images per call for these taps")
+                                     f"most {self.max_images_taps(taps, n_ctx=n_ctx)} images per call for these taps")
             _lib.check(st, "dsim_unet_qkv_taps")
         return outs
 
-    def _launch(self, latents, noise, sa, sb, ctx, out):
+    def _launch(self, latents, noise, sa, sb, ctx, out, idx=None):
         q, k, v = out
-        _lib.check(self.L.dsim_unet_qkv(self._h, latents.data_ptr(), noise.data_ptr(), sa, sb, ctx.data_ptr(),
-                                        latents.shape[0], q.data_ptr(), k.data_ptr(), v.data_ptr(), self._ws.data_ptr(),
-                                        self._ws.numel(), _stream_ptr()), "dsim_unet_qkv")
+        if idx is None:
+            _lib.check(self.L.dsim_unet_qkv(self._h, latents.data_ptr(), noise.data_ptr(), sa, sb, ctx.data_ptr(),
+                                            latents.shape[0], q.data_ptr(), k.data_ptr(), v.data_ptr(), self._ws.data_ptr(),
+                                            self._ws.numel(), _stream_ptr()), "dsim_unet_qkv")
+            return
+        _lib.check(self.L.dsim_unet_qkv_ctx(self._h, latents.data_ptr(), noise.data_ptr(), sa, sb, ctx.data_ptr(), ctx.shape[0],
+                                            idx.data_ptr(), latents.shape[0], q.data_ptr(), k.data_ptr(), v.data_ptr(),
+                                            self._ws.data_ptr(), self._ws.numel(), _stream_ptr()), "dsim_unet_qkv_ctx")
 
-    def _replay(self, latents, noise, sa, sb, ctx, shape):
+    def _replay(self, latents, noise, sa, sb, ctx, shape, idx=None):
         """hipGraph path for launch-bound small batches: the ~330 kernel launches of one forward are captured
-        once per (n_images, sqrt_abar, sqrt_1m_abar) over static input/output buffers and replayed as one graph
-        launch.  dsim_unet_qkv never allocates or synchronises, so plain stream capture works."""
-        key = (self.target_block, str(self.target_layer), self.sample_size, _stream_ptr(), shape[0], sa, sb)
+        once per (n_images, sqrt_abar, sqrt_1m_abar, n_ctx) over static input/output buffers and replayed as one graph
+        launch.  dsim_unet_qkv never allocates or synchronises, so plain stream capture works.  The context table and the
+        per-image index are static buffers too, refreshed before every replay like the latents: a replay never reuses the
+        prompt assignment of its capture."""
+        n_ctx = 1 if idx is None else int(ctx.shape[0])
+        key = (self.target_block, str(self.target_layer), self.sample_size, _stream_ptr(), shape[0], sa, sb, n_ctx)
         ent = self._graphs.get(key)
         if ent is None:
             st = {"lat": torch.empty_like(latents), "nz": torch.empty_like(noise), "ctx": torch.empty_like(ctx),
+                  "idx": None if idx is None else torch.empty_like(idx),
                   "out": tuple(torch.empty((3,) + tuple(shape), dtype=self.dtype, device=self.device).unbind(0))}
             st["lat"].copy_(latents), st["nz"].copy_(noise), st["ctx"].copy_(ctx)
-            self._launch(st["lat"], st["nz"], sa, sb, st["ctx"], st["out"])      # eager warm-up (code objects loaded)
+            if idx is not None:
+                st["idx"].copy_(idx)
+            self._launch(st["lat"], st["nz"], sa, sb, st["ctx"], st["out"], st["idx"])      # eager warm-up (code objects loaded)
             torch.cuda.synchronize(self.device)
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                self._launch(st["lat"], st["nz"], sa, sb, st["ctx"], st["out"])
+                self._launch(st["lat"], st["nz"], sa, sb, st["ctx"], st["out"], st["idx"])
             ent = self._graphs[key] = (g, st)
         g, st = ent
         st["lat"].copy_(latents), st["nz"].copy_(noise), st["ctx"].copy_(ctx)
+        if idx is not None:
+            st["idx"].copy_(idx)
         g.replay()
         return tuple(t.clone() for t in st["out"])
 

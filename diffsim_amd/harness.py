@@ -22,6 +22,7 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 
 from .engine import pair_score
+from .diffsim import single_prompt
 from .inputs import _Adapter, path_latents, stack_rows
 from .parallel import gather_scores, shard_triplets
 
@@ -33,7 +34,9 @@ def score_latent_triplets(scorer, lat_ref: torch.Tensor, lat_left: torch.Tensor,
     """Scores (ref,left) and (ref,right) for every triplet; ref sits in slot A (noiseA), left and
     right in slot B (noiseB) exactly as two reference calls would place them.  Returns two (n,) f32
     device tensors that are bit-identical to 2n separate ``diffsim_latents`` calls (any scorer kind).
-    batch_triplets=None: the engine batch of the measured optimum (``_Adapter.auto_triplets``)."""
+    batch_triplets=None: the engine batch of the measured optimum (``_Adapter.auto_triplets``).
+    prompt: one for every triplet, or (DiffSim) a sequence of n, triplet i's: each engine batch then carries its triplets'
+    prompts in one forward."""
     s_l, s_r, bad = _score_chunks(_Adapter(scorer), lat_ref, lat_left, lat_right, noiseA, noiseB, prompt, target_block,
                                   target_layer, target_step, similarity, batch_triplets)
     return (s_l, s_r, bad) if return_status else (s_l, s_r)
@@ -75,16 +78,18 @@ def _score_chunks(ad: _Adapter, ref, left, right, nA, nB, prompt, block, layer, 
     shared), chunked engine batches, one fused tail launch per chunk."""
     n = ref.shape[0]
     dev = ad.s.device
+    prompt = ad.rows(prompt, n)
     s_l = torch.empty(n, dtype=torch.float32, device=dev)
     s_r = torch.empty(n, dtype=torch.float32, device=dev)
     bad = torch.zeros((), dtype=torch.int32, device=dev)
     heads = ad.heads(block, layer)
     if batch_triplets is None:
-        batch_triplets = ad.auto_triplets(block, layer, n)
+        batch_triplets = ad.auto_triplets(block, layer, n, 1 if ad.kind != "sd15" or single_prompt(prompt) else 2)
     for i0 in range(0, n, batch_triplets):
         i1 = min(n, i0 + batch_triplets)
         m = i1 - i0
-        q, k, v = ad.features(*stack_rows([ref, left, right], [nA, nB, nB], i0, i1), prompt, block, layer, step)
+        q, k, v = ad.features(*stack_rows([ref, left, right], [nA, nB, nB], i0, i1), ad.chunk_prompt(prompt, i0, i1, 3), block, layer,
+                              step)
         base = torch.arange(0, 3 * m, 3, dtype=torch.int32, device=dev)
         s, st = pair_score(q, k, v, torch.cat([base, base]), torch.cat([base + 1, base + 2]), heads, similarity, return_status=True)
         bad += st.sum()
@@ -111,12 +116,13 @@ def score_path_triplets(scorer, triplets: Sequence[Tuple[str, str, str, str]], i
     dev = scorer.device
     sl, sr, order = [], [], []
     nbad = torch.zeros((), dtype=torch.int32, device=dev)
-    # prompts differ per row: group the shard by prompt so each context is encoded once
+    # prompts differ per row.  SD1.5 and DiT: the whole shard is one group, its engine batches carry their rows' prompts (a
+    # context table, each prompt encoded once); SDXL: one group per prompt (_Adapter.group_key)
     groups = {}
     for j in mine:
         groups.setdefault(ad.group_key(triplets[j][3]), []).append(j)
     for key, idxs in groups.items():
-        prompt = triplets[idxs[0]][3]
+        prompt = ad.group_prompt([triplets[j][3] for j in idxs])
         (ref, left, right), nA, nB = path_latents(scorer, [triplets[j][:3] for j in idxs], (0, 1, 1), img_size, seed,
                                                   batch_triplets)
         # (batch_triplets sizes the decode / VAE-encode chunks above; the U-Net batch is chosen by the adapter)

@@ -13,7 +13,7 @@ from typing import List, Sequence, Tuple
 
 import torch
 
-from .diffsim import DiffSim, _norm_layer, get_generator
+from .diffsim import DiffSim, _norm_layer, check_row_prompts, distinct_prompts, get_generator, row_prompts, single_prompt
 from .image import DecodePool, load_image, process_image
 
 
@@ -45,8 +45,42 @@ class _Adapter:
             self.round16 = True                                      # latents.to(dtype=float16), diffsim_xl.py:63 / diffsim_dit.py:59
         self._ctx = {}
 
+    @property
+    def mixes_prompts(self) -> bool:
+        """Whether one engine batch may carry several prompts.  SD1.5-family: yes, a context table (nothing before the first
+        cross-attention depends on the prompt).  DiT ignores the prompt (labels [1, 1000]).  SDXL: no -- its pooled prompt
+        embedding enters the time embedding of every resnet, one per CFG half."""
+        return self.kind != "xl"
+
     def group_key(self, prompt):
-        return None if self.kind == "dit" else prompt                # DiT ignores the prompt (labels [1, 1000])
+        """Rows of a path run with equal keys share engine batches: one group for the kinds that mix prompts, one per prompt
+        for SDXL."""
+        return prompt if not self.mixes_prompts else None
+
+    def group_prompt(self, prompts: Sequence):
+        """The prompt argument of one group's rows (group_key): SD1.5 the per-row list, or its one prompt when all rows share it;
+        the others the group's one prompt."""
+        if self.kind == "sd15" and len(distinct_prompts(prompts)[0]) > 1:
+            return list(prompts)
+        return prompts[0]
+
+    def rows(self, prompt, n_rows: int, what: str = "triplets"):
+        """A call's prompt argument checked against its rows: SD1.5 takes one prompt or one per row; SDXL one prompt per call (a
+        string or its (context, pooled) tuple, or a list that repeats one); DiT ignores it."""
+        if self.kind == "dit":
+            return prompt
+        if self.kind == "xl":
+            if isinstance(prompt, list):
+                prompt = check_row_prompts(prompt, n_rows, what)
+                if len(distinct_prompts(prompt)[0]) > 1:
+                    raise ValueError("SDXL takes one prompt per call: its pooled prompt embedding enters every resnet")
+                return prompt[0]
+            return prompt
+        return check_row_prompts(prompt, n_rows, what)
+
+    def chunk_prompt(self, prompt, i0: int, i1: int, per_row: int):
+        """The prompt argument of the engine batch of rows [i0, i1) (each row's per_row images consecutive)."""
+        return row_prompts(prompt, i0, i1, per_row) if self.kind == "sd15" else prompt
 
     def heads(self, block, layer):
         if self.kind == "dit":
@@ -58,17 +92,18 @@ class _Adapter:
             return self.s.engine(int(layer[0]))
         return self.s.engine(block, layer if self.kind == "xl" else _norm_layer(layer))
 
-    def auto_triplets(self, block, layer, n: int) -> int:
+    def auto_triplets(self, block, layer, n: int, n_ctx: int = 1) -> int:
         """Triplets per engine batch when the caller names none: the image count of the batch sweeps' optimum (SD1.5 and
         DiT: 128 images = 64 pairs, profiles/r04h_batch_sweep.txt; SDXL at 1024 px: 16), inside the 2 GiB activation bound
         and half of the free HBM."""
         eng = self.engine(block, layer)
         t = max(1, min((16 if self.kind == "xl" else 128) // 3, max(1, int(n))))
+        mixed = {"n_ctx": 2} if n_ctx > 1 else {}                   # (a context table: its per-image buffers count too)
         if hasattr(eng, "max_images"):
-            t = max(1, min(t, eng.max_images() // 3))
+            t = max(1, min(t, eng.max_images(**mixed) // 3))
         try:
             free, _total = torch.cuda.mem_get_info(self.s.device)
-            while t > 1 and hasattr(eng, "workspace_bytes") and eng.workspace_bytes(3 * t) > 0.5 * free:
+            while t > 1 and hasattr(eng, "workspace_bytes") and eng.workspace_bytes(3 * t, **mixed) > 0.5 * free:
                 t = (t + 1) // 2
         except Exception:
             pass

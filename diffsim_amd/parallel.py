@@ -167,6 +167,9 @@ def score_pairs_sharded(scorer, latA: torch.Tensor, latB: torch.Tensor, noiseA, 
         # per-pair noise (n,4,s,s) is sharded with the pairs; a shared (1,4,s,s) draw is passed through
         nA = noiseA[sel] if torch.is_tensor(noiseA) and noiseA.shape[0] == n and n > 1 else noiseA
         nB = noiseB[sel] if torch.is_tensor(noiseB) and noiseB.shape[0] == n and n > 1 else noiseB
+        from .diffsim import DiffSim, single_prompt
+        if isinstance(scorer, DiffSim) and not single_prompt(prompt):
+            prompt = [prompt[i] for i in idx]               # a prompt per pair is sharded with the pairs
         local = scorer.score_latent_pairs(latA[sel], latB[sel], nA, nB, prompt, **kw)
     else:
         local = torch.empty(0, dtype=torch.float32, device=scorer.device)

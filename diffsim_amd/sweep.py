@@ -20,6 +20,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import torch
 
+from .diffsim import single_prompt
 from .engine import pair_score
 from .inputs import _Adapter, path_latents, stack_rows
 from .parallel import gather_scores, shard_triplets
@@ -136,10 +137,10 @@ def _engine(ad: _Adapter, taps, side: int):
 
 
 def _features_fn(ad: _Adapter, prompt, taps, step):
-    """lat, nz -> [(q, k, v) per tap] from one forward.  diffsim_xl takes a (context, pooled) tuple or a prompt string (encoded
-    once), DiT ignores the prompt."""
+    """lat, nz, rows -> [(q, k, v) per tap] from one forward over the rows (i0, i1, images per row) of the call.  DiffSim takes
+    one prompt or one per row, diffsim_xl a (context, pooled) tuple or a prompt string (encoded once), DiT ignores the prompt."""
     if ad.kind == "sd15":
-        return lambda lat, nz: ad.s.features_taps(lat, nz, prompt, taps, step)
+        return lambda lat, nz, rows: ad.s.features_taps(lat, nz, ad.chunk_prompt(prompt, *rows), taps, step)
     if ad.kind == "xl":
         if isinstance(prompt, tuple):
             ctx, pooled = prompt
@@ -147,23 +148,24 @@ def _features_fn(ad: _Adapter, prompt, taps, step):
             if ad.s._encode_prompt is None:
                 raise RuntimeError("no text encoder plugged in: pass encode_prompt=...")
             ctx, pooled = ad.s._encode_prompt(prompt)
-        return lambda lat, nz: ad.s.features_taps(lat, nz, ctx, pooled, taps, step)
-    return lambda lat, nz: ad.s.features_taps(lat, nz, taps, step)
+        return lambda lat, nz, rows: ad.s.features_taps(lat, nz, ctx, pooled, taps, step)
+    return lambda lat, nz, rows: ad.s.features_taps(lat, nz, taps, step)
 
 
-def auto_rows(ad: _Adapter, eng, taps, shapes, n_rows: int, per_row: int) -> int:
+def auto_rows(ad: _Adapter, eng, taps, shapes, n_rows: int, per_row: int, n_ctx: int = 1) -> int:
     """Rows (pairs: 2 images, triplets: 3) per engine batch of a sweep when the caller names none: the batch sweeps' optimum
     (SD1.5 and DiT 128 images, SDXL 16: _Adapter.auto_triplets), within the 2 GiB bound of every activation and tap output, and
     with the arena plus the q/k/v of EVERY tap inside half of the free HBM (all seven SD1.5 taps of 64 pairs hold ~7 GB)."""
     m = max(1, min((16 if ad.kind == "xl" else 128) // per_row, int(n_rows)))
-    m = max(1, min(m, eng.max_images_taps(taps) // per_row))
+    mixed = {"n_ctx": 2} if n_ctx > 1 else {}          # (a context table: its per-image buffers count too)
+    m = max(1, min(m, eng.max_images_taps(taps, **mixed) // per_row))
     es = torch.empty((), dtype=ad.s.dtype).element_size()
     per_image = sum(3 * 2 * t * h * d * es for t, h, d in shapes)
     try:
         free, _total = torch.cuda.mem_get_info(ad.s.device)
     except Exception:
         return m
-    while m > 1 and eng.taps_workspace_bytes(per_row * m, taps) + per_row * m * per_image > 0.5 * free:
+    while m > 1 and eng.taps_workspace_bytes(per_row * m, taps, **mixed) + per_row * m * per_image > 0.5 * free:
         m = (m + 1) // 2
     return m
 
@@ -174,23 +176,25 @@ def score_latent_pairs_taps(scorer, latA, latB, noiseA, noiseB, prompt, taps, ta
     """(n_taps, n) f32 device tensor: row t is bit for bit what ``score_latent_pairs`` returns at taps[t] for the pairs
     (latA[i] in slot A, latB[i] in slot B), any scorer kind (DiffSim, diffsim_xl, diffsim_DiT).  One forward per chunk of
     batch_pairs pairs serves every tap (None: ``auto_rows``); results do not depend on the chunk.  noiseA / noiseB: (1, C, s, s)
-    or (n, C, s, s).  prompt: as the scorer's score_latent_pairs takes it (diffsim_xl: (context, pooled) or a prompt string;
-    DiT: ignored).  taps: a list in the scorer's tap form, or "all"."""
+    or (n, C, s, s).  prompt: as the scorer's score_latent_pairs takes it (DiffSim: one or one per pair; diffsim_xl: (context,
+    pooled) or a prompt string; DiT: ignored).  taps: a list in the scorer's tap form, or "all"."""
     ad = _Adapter(scorer)
     taps = _taps(ad, taps)
     dev = scorer.device
     n = latA.shape[0]
+    prompt = ad.rows(prompt, n, "pairs")
     latA, latB = latA.to(dev, torch.float32), latB.to(dev, torch.float32)
     noiseA, noiseB = noiseA.to(dev, torch.float32), noiseB.to(dev, torch.float32)
     eng, shapes = _engine(ad, taps, latA.shape[2])
+    mixed = {"n_ctx": 2} if ad.kind == "sd15" and not single_prompt(prompt) else {}
     if batch_pairs is None:
-        batch_pairs = auto_rows(ad, eng, taps, shapes, n, 2)
-    batch_pairs = max(1, min(int(batch_pairs), eng.max_images_taps(taps) // 2))
+        batch_pairs = auto_rows(ad, eng, taps, shapes, n, 2, **mixed)
+    batch_pairs = max(1, min(int(batch_pairs), eng.max_images_taps(taps, **mixed) // 2))
     feats = _features_fn(ad, prompt, taps, target_step)
     out = torch.empty((len(taps), n), dtype=torch.float32, device=dev)
     for i0 in range(0, n, batch_pairs):
         i1 = min(n, i0 + batch_pairs)
-        fs = feats(*stack_rows([latA, latB], [noiseA, noiseB], i0, i1))
+        fs = feats(*stack_rows([latA, latB], [noiseA, noiseB], i0, i1), (i0, i1, 2))
         ia = torch.arange(0, 2 * (i1 - i0), 2, dtype=torch.int32, device=dev)
         for t, (q, k, v) in enumerate(fs):
             out[t, i0:i1] = pair_score(q, k, v, ia, ia + 1, shapes[t][1], similarity)
@@ -211,18 +215,20 @@ def score_path_pairs_taps(scorer, pairs: Sequence[Tuple[str, str]], img_size, pr
 def _score_chunks_taps(ad: _Adapter, ref, left, right, nA, nB, prompt, taps, step, similarity, batch_triplets):
     """harness._score_chunks at every tap: (nt, n) (ref,left) and (ref,right) scores and the (nt,) NaN / inf counts."""
     n, nt, dev = ref.shape[0], len(taps), ad.s.device
+    prompt = ad.rows(prompt, n)
     eng, shapes = _engine(ad, taps, ref.shape[2])
     s_l = torch.empty((nt, n), dtype=torch.float32, device=dev)
     s_r = torch.empty((nt, n), dtype=torch.float32, device=dev)
     bad = torch.zeros(nt, dtype=torch.int32, device=dev)
+    mixed = {"n_ctx": 2} if ad.kind == "sd15" and not single_prompt(prompt) else {}
     if batch_triplets is None:
-        batch_triplets = auto_rows(ad, eng, taps, shapes, n, 3)
-    batch_triplets = max(1, min(int(batch_triplets), eng.max_images_taps(taps) // 3))
+        batch_triplets = auto_rows(ad, eng, taps, shapes, n, 3, **mixed)
+    batch_triplets = max(1, min(int(batch_triplets), eng.max_images_taps(taps, **mixed) // 3))
     feats = _features_fn(ad, prompt, taps, step)
     for i0 in range(0, n, batch_triplets):
         i1 = min(n, i0 + batch_triplets)
         m = i1 - i0
-        fs = feats(*stack_rows([ref, left, right], [nA, nB, nB], i0, i1))
+        fs = feats(*stack_rows([ref, left, right], [nA, nB, nB], i0, i1), (i0, i1, 3))
         base = torch.arange(0, 3 * m, 3, dtype=torch.int32, device=dev)
         ia, ib = torch.cat([base, base]), torch.cat([base + 1, base + 2])
         for t, (q, k, v) in enumerate(fs):
@@ -251,7 +257,7 @@ def score_path_triplets_taps(scorer, triplets: Sequence[Tuple[str, str, str, str
     for j in mine:
         groups.setdefault(ad.group_key(triplets[j][3]), []).append(j)
     for _key_, idxs in groups.items():
-        prompt = triplets[idxs[0]][3]
+        prompt = ad.group_prompt([triplets[j][3] for j in idxs])
         (ref, left, right), nA, nB = path_latents(scorer, [triplets[j][:3] for j in idxs], (0, 1, 1), img_size, seed,
                                                   batch_triplets)
         a_, b_, bad = _score_chunks_taps(ad, ref, left, right, nA, nB, prompt, taps, target_step, similarity, unet_triplets)

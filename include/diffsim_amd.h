@@ -189,6 +189,27 @@ int  dsim_unet_set_fusion(dsim_unet* h, int mask);
  * multiple of 2^(n_levels-1). */
 int  dsim_unet_set_sample_size(dsim_unet* h, int side);
 
+/* ---- many prompts in one forward: a context table ----------------------------------------------------------------------------
+ * dsim_unet_qkv / dsim_unet_qkv_taps with one prompt per IMAGE instead of one per call:
+ *   ctx       : f32 device [n_ctx][2][ctx_len][cross_attention_dim], n_ctx [uncond, cond] pairs
+ *   ctx_index : int32 device [n_images], image i's row of ctx; values must lie in [0, n_ctx).  The index stays on the device (no
+ *               check on the host side of the call); the gather kernel clamps every value into [0, n_ctx), so a bad index reads
+ *               some row of the table, never memory outside it.  Not read when n_ctx == 1 (may be NULL then).
+ * Batch element 2 i + cfg attends to ctx[ctx_index[i]][cfg].  Every cross-attention projects the K / V of each batch element's own
+ * context (2 n_images ctx_len rows instead of 2 ctx_len) and attends per element; no other layer depends on the prompt.  Row for
+ * row, the q / k / v are bit for bit those of a dsim_unet_qkv call whose ctx is that image's row.  n_ctx == 1 runs exactly the
+ * launches of dsim_unet_qkv with ctx.  Checked before anything is enqueued: DSIM_ERR_INVALID for n_ctx < 1, a NULL ctx_index with
+ * n_ctx > 1, or n_ctx > 1 on a handle with added conditioning (SDXL: the pooled prompt embedding enters every resnet through the
+ * per-CFG-half time embedding), then what dsim_unet_qkv / dsim_unet_qkv_taps check. */
+size_t dsim_unet_ctx_workspace_bytes(const dsim_unet* h, int n_images, int n_ctx);
+size_t dsim_unet_taps_ctx_workspace_bytes(const dsim_unet* h, int n_images, int n_ctx, int n_taps, const dsim_tap* taps);
+int    dsim_unet_qkv_ctx(dsim_unet* h, const float* latents, const float* noise, float sqrt_abar, float sqrt_1m_abar,
+                         const float* ctx, int n_ctx, const int32_t* ctx_index, int n_images, void* q, void* k, void* v,
+                         void* workspace, size_t workspace_bytes, void* stream);
+int    dsim_unet_qkv_taps_ctx(dsim_unet* h, const float* latents, const float* noise, float sqrt_abar, float sqrt_1m_abar,
+                              const float* ctx, int n_ctx, const int32_t* ctx_index, int n_images, int n_taps, const dsim_tap* taps,
+                              void* const* q, void* const* k, void* const* v, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- score tail: replaces diffsim/diffsim.py:177-197 (4x F.scaled_dot_product_attention,
  *      2x F.cosine_similarity or F.mse_loss, mean).  Fused: the O tensors never reach HBM. --
  *   q,k,v       : dtype [n_feat][B][N][H*D]   (features of n_feat images, B = CFG batch = 2)
