@@ -72,6 +72,15 @@ class GemmLaunchC(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("bm", "bn", "kind", "geglu", "ek", "small")] + [("family", C.c_char * 128)]
 
 
+class AttnLaunchC(C.Structure):
+    """dsim_attn_launch (include/diffsim_amd.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("kind", "D", "dtype", "k80", "qit", "grid")] + [("family", C.c_char * 64)]
+
+
+# dsim_attn_kind, by index
+ATTN_KINDS = ("P160", "Short", "ShortK80", "Long", "Q2", "Q2Fast", "Fast", "Exact", "FP8")
+
+
 class TapC(C.Structure):
     """dsim_tap (include/diffsim_amd.h): one tap of a sweep, the dsim_unet_cfg fields of the same names"""
     _fields_ = [(n, C.c_int32) for n in ("block", "layer", "attn", "tfm")]
@@ -158,6 +167,9 @@ SYMBOLS = {
     "dsim_op_ln_linear": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
     "dsim_op_gemm": (_i, [C.POINTER(GemmOpC), C.POINTER(GemmLaunchC), _vp]),
     "dsim_op_groupnorm_pre": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _f, _i, _i, _vp, _i, _vp]),
+    "dsim_op_attention_ex": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(AttnLaunchC), _vp]),
+    "dsim_attention_plan": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_i)]),
+    "dsim_op_softmax_rows": (_i, [_vp, _vp, _i, _i, _f, _i, _vp]),
 }
 
 _lib = None

@@ -1423,18 +1423,7 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void matrix_tail_ker
 
 inline float scale_log2_of(int D) { return (1.0f / sqrtf((float)D)) * 1.4426950408889634f; }
 
-// The kernels launch_attention starts, as the profile family suffixes attention_kernel_kind names them (bench.py maps family names
-// to the symbols rocprofv3 prints):
-enum class AttnKernel {
-    P160,       // "_p160"   sdpa160_kernel (attn160.hip): 256 x 256 tokens at d = 160 on the persistent core
-    Short,      // "_short"  attn_short_kernel<D, false>: keys resident in LDS
-    ShortK80,   // "_short"  attn_short_kernel<D, true>: the same for 64 < Nk <= 80 (the 77-key prompt context)
-    Long,       // "_long"   attn_long_kernel: two query blocks per wave, pipelined
-    Q2,         // "_q2"     attn_q2_kernel<D, false>: two query blocks per wave sharing every fragment read, exact softmax
-    Q2Fast,     // "_q2fast" attn_q2_kernel<D, true>: the same with the fixed-reference softmax
-    Fast,       // "_fast"   attn_kernel<T, D, true>: the fixed-reference softmax
-    Exact,      // ""        attn_kernel<T, D, false>: the exact running maximum
-};
+// (AttnKernel, the kernels launch_attention starts: common.h)
 
 // fewest keys that take the fixed-reference softmax: long key sequences (>= 1024 keys: the 64 x 64 and 32 x 32 self-attentions)
 // run 6 % faster on it at 4096 keys x d = 40, 10 % at 1024 keys x d = 80, 14 % at 1024 keys x d = 64 (SDXL); short ones
@@ -1487,11 +1476,13 @@ int launch_attn_d(const AttnArgs& a, AttnKernel kind, hipStream_t s) {
                     auto kern = attn_short_kernel<D, true>;
                     CK_ONCE(onces, kern, LDSS);
                     hipLaunchKernelGGL(kern, g, dim3(256), LDSS, s, a, scale_log2_of(D), qit);
+                    g_attn_last_launch = AttnLaunchRec{DSIM_ATTN_SHORT_K80, D, DSIM_H16, 1, qit, (int)g.x};
                 } else {
                     static DeviceOnce onces;
                     auto kern = attn_short_kernel<D, false>;
                     CK_ONCE(onces, kern, LDSS);
                     hipLaunchKernelGGL(kern, g, dim3(256), LDSS, s, a, scale_log2_of(D), qit);
+                    g_attn_last_launch = AttnLaunchRec{DSIM_ATTN_SHORT, D, DSIM_H16, 0, qit, (int)g.x};
                 }
                 DSIM_HIP_CHECK(hipGetLastError());
                 return DSIM_OK;
@@ -1511,7 +1502,9 @@ int launch_attn_d(const AttnArgs& a, AttnKernel kind, hipStream_t s) {
                 static DeviceOnce once2;
                 auto kern = attn_long_kernel<D, 0>;
                 CK_ONCE(once2, kern, LDS3);
-                hipLaunchKernelGGL(kern, dim3(((a.Nq + 255) / 256) * a.H * a.B), dim3(256), LDS3, s, a, scale_log2_of(D));
+                const dim3 gl(((a.Nq + 255) / 256) * a.H * a.B);
+                hipLaunchKernelGGL(kern, gl, dim3(256), LDS3, s, a, scale_log2_of(D));
+                g_attn_last_launch = AttnLaunchRec{DSIM_ATTN_LONG, D, DSIM_H16, 0, 0, (int)gl.x};
                 DSIM_HIP_CHECK(hipGetLastError());
                 return DSIM_OK;
             }
@@ -1525,11 +1518,13 @@ int launch_attn_d(const AttnArgs& a, AttnKernel kind, hipStream_t s) {
                     auto k = attn_q2_kernel<D, true>;
                     CK_ONCE(o1, k, C::LDS);
                     hipLaunchKernelGGL(k, grid2, dim3(256), C::LDS, s, a, scale_log2_of(D));
+                    g_attn_last_launch = AttnLaunchRec{DSIM_ATTN_Q2FAST, D, DSIM_H16, 0, 0, (int)grid2.x};
                 } else {
                     static DeviceOnce o2;
                     auto k = attn_q2_kernel<D, false>;
                     CK_ONCE(o2, k, C::LDS);
                     hipLaunchKernelGGL(k, grid2, dim3(256), C::LDS, s, a, scale_log2_of(D));
+                    g_attn_last_launch = AttnLaunchRec{DSIM_ATTN_Q2, D, DSIM_H16, 0, 0, (int)grid2.x};
                 }
                 DSIM_HIP_CHECK(hipGetLastError());
                 return DSIM_OK;
@@ -1538,16 +1533,19 @@ int launch_attn_d(const AttnArgs& a, AttnKernel kind, hipStream_t s) {
         case AttnKernel::Fast:
         case AttnKernel::Exact: {
             const dim3 grid(((a.Nq + 127) / 128) * a.H * a.B);
+            constexpr int edt = sizeof(T) == 2 ? DSIM_H16 : DSIM_F32;
             if (kind == AttnKernel::Fast) {
                 static DeviceOnce oncef;
                 auto kern = attn_kernel<T, D, true>;
                 CK_ONCE(oncef, kern, C::LDS);
                 hipLaunchKernelGGL(kern, grid, dim3(256), C::LDS, s, a, scale_log2_of(D));
+                g_attn_last_launch = AttnLaunchRec{DSIM_ATTN_FAST, D, edt, 0, 0, (int)grid.x};
             } else {
                 static DeviceOnce once;
                 auto kern = attn_kernel<T, D, false>;
                 CK_ONCE(once, kern, C::LDS);
                 hipLaunchKernelGGL(kern, grid, dim3(256), C::LDS, s, a, scale_log2_of(D));
+                g_attn_last_launch = AttnLaunchRec{DSIM_ATTN_EXACT, D, edt, 0, 0, (int)grid.x};
             }
             DSIM_HIP_CHECK(hipGetLastError());
             return DSIM_OK;
@@ -1724,24 +1722,30 @@ int launch_maps_t(const void* q, const void* k, const void* v, const int32_t* ia
 int g_attn_dbg = 0;
 #endif
 
-const char* attention_kernel_kind(const AttnArgs& a, int dtype) {
-    switch (attention_kernel(a, dtype)) {
-        case AttnKernel::P160: return "_p160";
-        case AttnKernel::Short:
-        case AttnKernel::ShortK80: return "_short";
-        case AttnKernel::Long: return "_long";
-        case AttnKernel::Q2: return "_q2";
-        case AttnKernel::Q2Fast: return "_q2fast";
-        case AttnKernel::Fast: return "_fast";
-        case AttnKernel::Exact: break;
-    }
-    return "";
+const char* attention_kernel_kind(const AttnArgs& a, int dtype) { return attn_kind_suffix((int)attention_kernel(a, dtype)); }
+
+// the arguments launch_attention refuses whatever the kernel
+static bool attention_args_ok(const AttnArgs& a, int dtype) {
+    const int vec = dtype == DSIM_F32 ? 4 : 8;
+    return !(a.D % 8 || a.ldq % vec || a.ldk % vec || a.ldo % 4 || a.Nk < 1 || a.Nq < 1 || a.Bkv < 1);
+}
+
+int attention_plan(const AttnArgs& a, int dtype) {
+    if (!attention_args_ok(a, dtype)) return DSIM_ERR_INVALID;
+#ifndef DSIM_H16_IS_F16
+#ifdef DSIM_HAS_F16_TWINS
+    if (dtype == DSIM_F16) return attention_plan_f16(a, dtype);
+#endif
+    if (dtype != DSIM_H16 && dtype != DSIM_F32) return DSIM_ERR_INVALID;
+#else
+    if (dtype != DSIM_H16) return DSIM_ERR_INVALID;
+#endif
+    const int st = with_head_dim(a.D, [](auto) { return DSIM_OK; });
+    return st != DSIM_OK ? st : (int)attention_kernel(a, dtype);
 }
 
 int launch_attention(const AttnArgs& a, int dtype, hipStream_t s) {
-    const int vec = dtype == DSIM_F32 ? 4 : 8;
-    if (a.D % 8 || a.ldq % vec || a.ldk % vec || a.ldo % 4 || a.Nk < 1 || a.Nq < 1 || a.Bkv < 1)
-        return DSIM_ERR_INVALID;
+    if (!attention_args_ok(a, dtype)) return DSIM_ERR_INVALID;
     if (dtype == DSIM_H16) {
         const AttnKernel kind = attention_kernel(a, dtype);
         return kind == AttnKernel::P160 ? launch_sdpa160(a, s) : launch_attn_t<h16>(a, kind, s);

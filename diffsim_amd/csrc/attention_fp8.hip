@@ -247,7 +247,9 @@ int launch_f8(const AttnArgs& a, hipStream_t s) {
     auto kern = attn_fp8_kernel<D>;
     CK_ONCE(once, kern, C::LDS);
     const float sl2 = (1.0f / sqrtf((float)D)) * 1.4426950408889634f;
-    hipLaunchKernelGGL(kern, dim3(((a.Nq + 127) / 128) * a.H * a.B), dim3(256), C::LDS, s, a, sl2);
+    const dim3 g(((a.Nq + 127) / 128) * a.H * a.B);
+    hipLaunchKernelGGL(kern, g, dim3(256), C::LDS, s, a, sl2);
+    g_attn_last_launch = AttnLaunchRec{DSIM_ATTN_FP8, D, DSIM_H16, 0, 0, (int)g.x};
     DSIM_HIP_CHECK(hipGetLastError());
     return DSIM_OK;
 }

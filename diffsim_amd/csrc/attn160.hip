@@ -1157,8 +1157,9 @@ bool sdpa160_applies(const AttnArgs& a) {
     if (a.D != A_D || a.Nq != A_N || a.Nk != A_N || a.Bkv != a.B || a.B < 1 || a.H < 1) return false;
     if (a.ldq % 8 || a.ldk % 8 || a.ldo % 8) return false;
     if (((size_t)a.q | (size_t)a.k | (size_t)a.v | (size_t)a.out) & 15) return false;
-    // 32-bit buffer offsets inside one (batch element, head) view
-    return (long)(A_N - 1) * a.ldq * 2 + A_ROWB < (1l << 31) && (long)(A_N - 1) * a.ldk * 2 + A_ROWB < (1l << 31);
+    // 32-bit buffer offsets inside one (batch element, head) view, of the inputs and of the output
+    return (long)(A_N - 1) * a.ldq * 2 + A_ROWB < (1l << 31) && (long)(A_N - 1) * a.ldk * 2 + A_ROWB < (1l << 31) &&
+           (long)(A_N - 1) * a.ldo * 2 + A_ROWB < (1l << 31);
 }
 
 int launch_sdpa160(const AttnArgs& a, hipStream_t s) {
@@ -1168,6 +1169,7 @@ int launch_sdpa160(const AttnArgs& a, hipStream_t s) {
     CK_ONCE(once, kern, A_LDS);
     hipLaunchKernelGGL(kern, dim3(g), dim3(512), A_LDS, s, (const h16*)a.q, (const h16*)a.k, (const h16*)a.v, (h16*)a.out, a.ldq, a.ldk,
                        a.ldo, a.B, a.H, softmax_c160());
+    g_attn_last_launch = AttnLaunchRec{DSIM_ATTN_P160, A_D, DSIM_H16, 0, 0, g};
     DSIM_HIP_CHECK(hipGetLastError());
     return DSIM_OK;
 }

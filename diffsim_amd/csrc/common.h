@@ -29,6 +29,7 @@
 #define launch_softmax_rows launch_softmax_rows_f16
 #define launch_attention launch_attention_f16
 #define attention_kernel_kind attention_kernel_kind_f16
+#define attention_plan attention_plan_f16
 #define pair_score_scratch_bytes pair_score_scratch_bytes_f16
 #define launch_pair_score launch_pair_score_f16
 #define pair_score160_applies pair_score160_applies_f16
@@ -293,8 +294,42 @@ struct AttnArgs {
     int B = 0, Bkv = 0, H = 0, Nq = 0, Nk = 0, D = 0;
     int xcd_remap = 1;                        // 0: plain block order (micro-benchmark A/B only)
 };
+// The kernels launch_attention starts (attention.hip attention_kernel() picks one), numbered as include/diffsim_amd.h's dsim_attn_kind;
+// profile family suffixes as attn_kind_suffix() names them (bench.py maps family names to the symbols rocprofv3 prints):
+enum class AttnKernel {
+    P160 = DSIM_ATTN_P160,          // "_p160"   sdpa160_kernel (attn160.hip): 256 x 256 tokens at d = 160 on the persistent core
+    Short = DSIM_ATTN_SHORT,        // "_short"  attn_short_kernel<D, false>: keys resident in LDS
+    ShortK80 = DSIM_ATTN_SHORT_K80, // "_short"  attn_short_kernel<D, true>: the same for 64 < Nk <= 80 (the 77-key prompt context)
+    Long = DSIM_ATTN_LONG,          // "_long"   attn_long_kernel: two query blocks per wave, pipelined
+    Q2 = DSIM_ATTN_Q2,              // "_q2"     attn_q2_kernel<D, false>: two query blocks per wave sharing every fragment read, exact softmax
+    Q2Fast = DSIM_ATTN_Q2FAST,      // "_q2fast" attn_q2_kernel<D, true>: the same with the fixed-reference softmax
+    Fast = DSIM_ATTN_FAST,          // "_fast"   attn_kernel<T, D, true>: the fixed-reference softmax
+    Exact = DSIM_ATTN_EXACT,        // ""        attn_kernel<T, D, false>: the exact running maximum
+};
+inline const char* attn_kind_suffix(int kind) {
+    switch (kind) {
+        case DSIM_ATTN_P160: return "_p160";
+        case DSIM_ATTN_SHORT:
+        case DSIM_ATTN_SHORT_K80: return "_short";
+        case DSIM_ATTN_LONG: return "_long";
+        case DSIM_ATTN_Q2: return "_q2";
+        case DSIM_ATTN_Q2FAST: return "_q2fast";
+        case DSIM_ATTN_FAST: return "_fast";
+        default: return "";
+    }
+}
 int launch_attention(const AttnArgs& a, int dtype, hipStream_t s);
 const char* attention_kernel_kind(const AttnArgs& a, int dtype);      // "_p160" / "_short" / "_long" / "_q2" / "_q2fast" / "_fast" / "": the kernel it picks
+// the dsim_attn_kind launch_attention would start for these arguments (host only, launches nothing); DSIM_ERR_INVALID where it
+// would refuse them
+int attention_plan(const AttnArgs& a, int dtype);
+// The attention kernel the calling thread launched last, written where launch_attn_d / launch_sdpa160 / launch_attention_fp8 launch it
+// (one definition, in pack.hip, shared by the bf16 and fp16 objects): what dsim_op_attention_ex reports, so that tests see the kernel
+// that ran rather than the one the dispatch rule names.
+struct AttnLaunchRec {
+    int kind = -1, D = 0, dtype = -1, k80 = 0, qit = 0, grid = 0;
+};
+extern thread_local AttnLaunchRec g_attn_last_launch;
 int launch_attention_fp8(const AttnArgs& a, hipStream_t s);      // h16 in/out, e4m3 MFMAs (attention_fp8.hip)
 size_t pair_score_scratch_bytes(int n_pairs, int B, int H, int N, int D);
 int launch_pair_score(const void* q, const void* k, const void* v, const int32_t* idx_a,
@@ -361,6 +396,7 @@ int launch_layernorm_mod_f16(const void* x, const float* scale2, const float* sh
                              int dtype, hipStream_t s);
 int launch_softmax_rows_f16(const void* x, void* out, int rows, int cols, float scale, int dtype, hipStream_t s);
 int launch_attention_f16(const AttnArgs& a, int dtype, hipStream_t s);
+int attention_plan_f16(const AttnArgs& a, int dtype);
 int launch_pair_score_f16(const void* q, const void* k, const void* v, const int32_t* idx_a, const int32_t* idx_b, int n_pairs, int B, int H,
                           int N, int D, int dtype, int similarity, float* out, void* scratch, size_t scratch_bytes, hipStream_t s,
                           int32_t* status);

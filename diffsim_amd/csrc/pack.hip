@@ -6,6 +6,7 @@
 namespace dsim {
 
 thread_local GemmLaunchRec g_gemm_last_launch;      // (common.h: written by gemm.hip / gemm_skinny.hip at each launch)
+thread_local AttnLaunchRec g_attn_last_launch;      // (common.h: written by attention.hip / attn160.hip / attention_fp8.hip at each launch)
 
 namespace {
 

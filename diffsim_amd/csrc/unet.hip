@@ -1298,4 +1298,56 @@ int dsim_op_attention_fp8(const void* q, int ldq, const void* k, const void* v, 
     return DSIM_OK;
 }
 
+static int attn_fp8_ok(const AttnArgs& a) {
+    // launch_attention_fp8's own refusals
+    if (!a.q || !a.k || !a.v || !a.out || a.B < 1 || a.Bkv < 1 || a.H < 1 || a.Nq < 1 || a.Nk < 1) return 0;
+    return !(a.ldq % 8 || a.ldk % 8 || a.ldo % 4) && (a.D == 72 || a.D == 32);
+}
+
+int dsim_attention_plan(const void* q, int ldq, const void* k, const void* v, int ldk, const void* out, int ldo, int B, int Bkv,
+                        int H, int Nq, int Nk, int D, int dtype, int fp8, int* kind) {
+    if (!kind) return DSIM_ERR_INVALID;
+    AttnArgs a;
+    a.q = q; a.ldq = ldq; a.k = k; a.v = v; a.ldk = ldk; a.out = (void*)out; a.ldo = ldo;
+    a.B = B; a.Bkv = Bkv; a.H = H; a.Nq = Nq; a.Nk = Nk; a.D = D;
+    if (fp8) {
+        if (dtype != DSIM_BF16 || !attn_fp8_ok(a)) return DSIM_ERR_INVALID;
+        *kind = DSIM_ATTN_FP8;
+        return DSIM_OK;
+    }
+    const int r = attention_plan(a, dtype);
+    if (r < 0) return r;
+    *kind = r;
+    return DSIM_OK;
+}
+
+int dsim_op_attention_ex(const void* q, int ldq, const void* k, const void* v, int ldk, void* out, int ldo, int B, int Bkv, int H,
+                         int Nq, int Nk, int D, int dtype, int fp8, dsim_attn_launch* launched, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    AttnArgs a;
+    a.q = q; a.ldq = ldq; a.k = k; a.v = v; a.ldk = ldk; a.out = out; a.ldo = ldo;
+    a.B = B; a.Bkv = Bkv; a.H = H; a.Nq = Nq; a.Nk = Nk; a.D = D;
+    if (fp8 && dtype != DSIM_BF16) return DSIM_ERR_INVALID;
+    g_attn_last_launch = AttnLaunchRec{};
+    CK(fp8 ? launch_attention_fp8(a, s) : launch_attention(a, dtype, s));
+    DSIM_HIP_CHECK(hipStreamSynchronize(s));
+    if (launched) {
+        const AttnLaunchRec& r = g_attn_last_launch;
+        launched->kind = r.kind; launched->D = r.D; launched->dtype = r.dtype; launched->k80 = r.k80; launched->qit = r.qit;
+        launched->grid = r.grid;
+        const char* dtn = r.dtype == DSIM_F32 ? "f32" : (r.dtype == DSIM_F16 ? "f16" : "bf16");
+        if (r.kind == DSIM_ATTN_FP8) std::snprintf(launched->family, sizeof(launched->family), "attention_fp8_d%d", r.D);
+        else std::snprintf(launched->family, sizeof(launched->family), "attention_%s_d%d%s", dtn, r.D, attn_kind_suffix(r.kind));
+    }
+    return DSIM_OK;
+}
+
+int dsim_op_softmax_rows(const void* x, void* out, int rows, int cols, float scale, int dtype, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (!x || !out) return DSIM_ERR_INVALID;
+    CK(launch_softmax_rows(x, out, rows, cols, scale, dtype, s));
+    DSIM_HIP_CHECK(hipStreamSynchronize(s));
+    return DSIM_OK;
+}
+
 }  // extern "C"

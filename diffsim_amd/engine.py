@@ -789,6 +789,60 @@ def op_attention(q, k, v, heads, fp8: bool = False):
     return out
 
 
+_PLAN_ADDR = 1 << 12     # attention_plan's default operand address: 256-byte aligned, never dereferenced
+
+
+def attention_plan(B, Bkv, heads, Nq, Nk, D, dtype, *, ldq=None, ldk=None, ldo=None, q=_PLAN_ADDR, k=_PLAN_ADDR, v=_PLAN_ADDR,
+                   out=_PLAN_ADDR, fp8=False):
+    """The kernel dsim_op_attention_ex would launch for these arguments, by its _lib.ATTN_KINDS name; host only (launches nothing, reads
+    no memory: q / k / v / out are addresses, looked at for their alignment only).  ld's default to heads * D; raises DsimError where
+    the launch would refuse the arguments."""
+    L = _lib.lib()
+    HD = heads * D
+    kind = C.c_int(-1)
+    _lib.check(L.dsim_attention_plan(int(q) or None, int(ldq or HD), int(k) or None, int(v) or None, int(ldk or HD), int(out) or None,
+                                     int(ldo or HD), B, Bkv, heads, Nq, Nk, D, _TORCH2DSIM[dtype], int(bool(fp8)), C.byref(kind)),
+               "attention_plan")
+    return _lib.ATTN_KINDS[kind.value]
+
+
+def op_attention_rows(q, q_off, ldq, k, k_off, v, v_off, ldk, out, o_off, ldo, *, B, Bkv, heads, Nq, Nk, D, fp8=False):
+    """The attention on the executors' fused-row buffers (dsim_op_attention_ex): head h of query row (b, i) is q[(b Nq + i) ldq + q_off
+    + h D ...], of key row (b', j) k[(b' Nk + j) ldk + k_off + h D ...] and v[... + v_off ...], of output row (b, i) out[(b Nq + i) ldo
+    + o_off + h D ...]; offsets and ld's count elements of the flat (contiguous) tensors, which may be the same tensor (self-attention's
+    q | k | v rows: ldq = ldk = 3C, k_off = C, v_off = 2C).  fp8: bf16 tensors, e4m3 MFMAs.  Writes out in place and returns the launch
+    record: kind (an _lib.ATTN_KINDS name), D, dtype, k80, qit, grid and family (the executors' profile family name)."""
+    L = _lib.lib()
+    _require_cuda(q, k, v, out)
+    dt = q.dtype
+    if dt not in _TORCH2DSIM or any(t.dtype != dt for t in (k, v, out)):
+        raise _lib.DsimError("q, k, v and out must share one float32 / bfloat16 / float16 dtype")
+    HD = heads * D
+    for t, off, ld, rows, nm in ((q, q_off, ldq, B * Nq, "q"), (k, k_off, ldk, Bkv * Nk, "k"), (v, v_off, ldk, Bkv * Nk, "v"),
+                                 (out, o_off, ldo, B * Nq, "out")):
+        if off < 0 or off + HD > ld or (rows - 1) * ld + off + HD > t.numel():
+            raise _lib.DsimError(f"{nm}: {rows} rows of {ld} elements from offset {off} do not fit its {t.numel()} elements")
+    es = q.element_size()
+    rec = _lib.AttnLaunchC()
+    with torch.cuda.device(q.device):
+        _lib.check(L.dsim_op_attention_ex(q.data_ptr() + q_off * es, int(ldq), k.data_ptr() + k_off * es, v.data_ptr() + v_off * es,
+                                          int(ldk), out.data_ptr() + o_off * es, int(ldo), B, Bkv, heads, Nq, Nk, D, _TORCH2DSIM[dt],
+                                          int(bool(fp8)), C.byref(rec), _stream_ptr()), "op_attention_rows")
+    return {"kind": _lib.ATTN_KINDS[rec.kind], "D": rec.D, "dtype": {0: torch.float32, 1: torch.bfloat16, 2: torch.float16}[rec.dtype],
+            "k80": bool(rec.k80), "qit": rec.qit, "grid": rec.grid, "family": rec.family.decode()}
+
+
+def op_softmax_rows(x, scale):
+    """softmax(x * scale) along the last dim of a contiguous [rows][cols] tensor (the VAE mid-block's softmax_rows_kernel)"""
+    L = _lib.lib()
+    _require_cuda(x)
+    out = torch.empty_like(x)
+    rows, cols = x.shape
+    _lib.check(L.dsim_op_softmax_rows(x.data_ptr(), out.data_ptr(), rows, cols, float(scale), _TORCH2DSIM[x.dtype], _stream_ptr()),
+               "op_softmax_rows")
+    return out
+
+
 # ---- the arithmetic either side of the VAE encoder, on the device ------------------------------------------------
 def image_preprocess(pixels_u8: torch.Tensor, to_half: bool = False) -> torch.Tensor:
     """pixels u8 cuda [n][H][W][3] (decoded + Lanczos-resized on the host) -> process_image's f32 [n][3][H][W], bit-identical

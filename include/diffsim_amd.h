@@ -389,6 +389,42 @@ int dsim_op_attention(const void* q, int ldq, const void* k, const void* v, int 
 int dsim_op_attention_fp8(const void* q, int ldq, const void* k, const void* v, int ldk, void* out,
                           int ldo, int B, int Bkv, int H, int Nq, int Nk, int D, void* stream);
 
+/* The attention kernels (what dsim_op_attention starts; DSIM_ATTN_FP8 is dsim_op_attention_fp8's):
+ *   P160       sdpa160_kernel: 256 queries x 256 keys at d = 160, B == Bkv, 16-byte aligned pointers and ld's (16-bit types)
+ *   SHORT      attn_short_kernel<D, false>: Nk <= 96 at d = 40 / 64 / 80 / 160, keys resident in LDS (16-bit types)
+ *   SHORT_K80  attn_short_kernel<D, true>: the same for 64 < Nk <= 80 (the 77-key prompt context)
+ *   LONG       attn_long_kernel: d = 40, Nk >= 2048, Nk % 64 == 0 (16-bit types)
+ *   Q2 / Q2FAST attn_q2_kernel<64, false | true>: d = 64, Nk > 96, Nq >= 256; FAST from Nk >= 1024 on (16-bit types)
+ *   FAST       attn_kernel<T, D, true>: the fixed-reference softmax, Nk >= 1024 (16-bit types)
+ *   EXACT      attn_kernel<T, D, false>: the exact running maximum (every other 16-bit problem; every f32 problem)
+ *   FP8        attn_fp8_kernel<D>: bf16 in / out, e4m3 MFMAs, D = 72 or 32 */
+typedef enum dsim_attn_kind {
+    DSIM_ATTN_P160 = 0, DSIM_ATTN_SHORT = 1, DSIM_ATTN_SHORT_K80 = 2, DSIM_ATTN_LONG = 3, DSIM_ATTN_Q2 = 4, DSIM_ATTN_Q2FAST = 5,
+    DSIM_ATTN_FAST = 6, DSIM_ATTN_EXACT = 7, DSIM_ATTN_FP8 = 8
+} dsim_attn_kind;
+/* What one attention launch ran, recorded where the kernel was launched (not derived from the dispatch rule). */
+typedef struct dsim_attn_launch {
+    int kind;                                   /* dsim_attn_kind */
+    int D;                                      /* the instantiation's head dim */
+    int dtype;                                  /* its element type: DSIM_F32, DSIM_BF16 or DSIM_F16 (FP8: DSIM_BF16, the in / out type) */
+    int k80;                                    /* 1: attn_short_kernel<D, true> */
+    int qit;                                    /* SHORT / SHORT_K80: query blocks per workgroup, else 0 */
+    int grid;                                   /* workgroups launched */
+    char family[64];                            /* the profile family the executors name it by: attention_<dtype>_d<D><suffix>, or attention_fp8_d<D> */
+} dsim_attn_launch;
+/* dsim_op_attention (fp8 = 0) or dsim_op_attention_fp8 (fp8 = 1: dtype must be DSIM_BF16) with every stride and pointer as the
+ * executors pass them (the fused q | k | v rows: ldq = ldk = 3C, k = q + C, v = q + 2C; the cross-attention's k | v rows: ldk = 2C,
+ * v = k + C); launched (may be NULL) receives the record of the kernel that ran.  Synchronises. */
+int dsim_op_attention_ex(const void* q, int ldq, const void* k, const void* v, int ldk, void* out, int ldo, int B, int Bkv, int H,
+                         int Nq, int Nk, int D, int dtype, int fp8, dsim_attn_launch* launched, void* stream);
+/* The dsim_attn_kind dsim_op_attention_ex would launch for the same arguments, into *kind.  Host code only: launches nothing and
+ * reads no pointer (it looks at their alignment), so it runs without a device.  DSIM_ERR_INVALID where the launch would refuse. */
+int dsim_attention_plan(const void* q, int ldq, const void* k, const void* v, int ldk, const void* out, int ldo, int B, int Bkv,
+                        int H, int Nq, int Nk, int D, int dtype, int fp8, int* kind);
+/* out[r][:] = softmax(x[r][:] * scale) over cols (the VAE mid-block's softmax; cols % 8 == 0 in 16-bit types, % 4 in f32; in place
+ * allowed).  Synchronises. */
+int dsim_op_softmax_rows(const void* x, void* out, int rows, int cols, float scale, int dtype, void* stream);
+
 /* One BasicTransformerBlock feed-forward as a single launch (bf16, C = 320): out = x + ff.net.2(GEGLU(ff.net.0.proj(LayerNorm(x))))
  * -- the chain /root/reference/diffsim/hacked_modules.py:118-132 runs as norm3 -> ff -> + hidden_states.  w1: [8C][C] f32 (diffusers
  * ff.net.0.proj.weight, rows [h ; g]), b1: [8C], w2: [C][4C], b2: [C]; x / out: bf16 [M][C] (out may alias x).

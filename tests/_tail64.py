@@ -27,7 +27,7 @@ def sdpa64(q, k, v, chunk=None):
     Nk = k.shape[2]
     rows = chunk or max(1, SCORE_BUDGET // (Bc * H * Nk))
     kt = (k.transpose(-1, -2) * (1.0 / D ** 0.5)).contiguous()
-    out = torch.empty(Bc, H, Nq, v.shape[3], dtype=torch.float64)
+    out = torch.empty(Bc, H, Nq, v.shape[3], dtype=torch.float64, device=q.device)
     for r0 in range(0, Nq, rows):
         s = torch.matmul(q[:, :, r0:r0 + rows], kt)
         out[:, :, r0:r0 + rows] = torch.matmul(torch.softmax(s, dim=-1), v)

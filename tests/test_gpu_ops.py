@@ -43,6 +43,25 @@ def _f64(got, a0, w, dtype, **kw):
     G.Gemm64(a0.to(dtype), w, dtype, **kw).check(got.float().cpu().reshape(-1, got.shape[-1]), "float64 bound")
 
 
+def _attn_f64(got, q, k, v, H, dtype, fp8=False):
+    """beside _close: every element within tests/_attn64.py's float64 bound for the kernel dsim_attention_plan names (q [B][Nq][H D],
+    k / v [Bkv][Nk][H D] CPU float32 values; above 2^22 query-key pairs per head, test_gpu_attn64's row subset)"""
+    from diffsim_amd import engine
+    from tests import _attn64 as A
+    from tests.test_gpu_attn64 import rows_checked
+    B, Nq, HD = q.shape
+    Bkv, Nk = k.shape[:2]
+    D = HD // H
+    tdt = torch.bfloat16 if fp8 else dtype
+    kind = engine.attention_plan(B, Bkv, H, Nq, Nk, D, tdt, fp8=fp8)
+    rows = rows_checked(Nq, Nk)
+    qh = A.heads(_q(q, tdt).double()[:, rows].cuda(), B, len(rows), H, D)
+    kh, vh = (A.expand_kv(A.heads(_q(t, tdt).double().cuda(), Bkv, Nk, H, D), B, Bkv, H) for t in (k, v))
+    ref, bound = A.ref_and_bound(qh, kh, vh, A.Spec(kind, tdt, D))
+    r = A.excess(A.heads(got.double().cuda()[:, rows], B, len(rows), H, D), ref, bound)
+    assert r <= 1.0, f"{kind} d{D}: err / bound {r:.3f}"
+
+
 @pytest.fixture(scope="module")
 def eng():
     from diffsim_amd import engine
@@ -195,6 +214,7 @@ def test_attention(eng, dtype, B, Bkv, H, Nq, Nk, D):
     want = want.transpose(1, 2).reshape(B, Nq, H * D)
     got = eng.op_attention(_dev(q, dtype), _dev(k, dtype), _dev(v, dtype), H)
     _close(got, want, dtype)
+    _attn_f64(got, q, k, v, H, dtype)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -309,6 +329,8 @@ def test_attention_fp8(eng, B, Bkv, H, Nq, Nk, D):
     assert float(err.mean()) <= 1.5e-2 * scale, (float(err.mean()), scale)
     got16 = eng.op_attention(qd, kd, vd, H).float().cpu()
     assert float((got16 - want).abs().max()) < float(err.max())            # the bf16 kernel is the accurate one
+    _attn_f64(got, q, k, v, H, torch.bfloat16, fp8=True)
+    _attn_f64(got16, q, k, v, H, torch.bfloat16)
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
@@ -424,6 +446,7 @@ def test_attention_peaked_logits(eng, dtype, D, scale):
     got = eng.op_attention(_dev(q, dtype), _dev(k, dtype), _dev(v, dtype), H)
     assert torch.isfinite(got.float()).all()
     _close(got, want, dtype)
+    _attn_f64(got, q, k, v, H, dtype)
 
 
 @pytest.mark.parametrize("M", [128, 96, 4096 + 32, 40000])
@@ -523,6 +546,7 @@ def test_attention_pipelined_kernel_takes_the_exact_fallback(eng, Nq, Nk, dtype)
         got = eng.op_attention(_dev(qq, dtype), _dev(kk, dtype), _dev(v, dtype), H)
         assert got.shape == (B, Nq, H * D)
         assert torch.isfinite(got.float()).all(), case
+        _attn_f64(got, qq, kk, v, H, dtype)
         if case == "overflow":
             assert (got.float().cpu() - want).abs().max().item() <= 5e-2 * float(want.abs().max())
         else:
@@ -559,6 +583,7 @@ def test_attention_long_keys_fixed_reference_softmax(eng, D, Nk, dtype):
                                               vh.double().view(B, Nk, H, D).transpose(1, 2)).transpose(1, 2).reshape(B, Nq, H * D).float()
         got = eng.op_attention(_dev(q, dtype), _dev(kk, dtype), _dev(v, dtype), H)
         assert torch.isfinite(got.float()).all(), case
+        _attn_f64(got, q, kk, v, H, dtype)
         if case == "overflow":
             # logits in the hundreds: the documented drift of near-tie rows under the bf16 pre-scaled Q (test_attention_peaked_logits)
             # applies to the exact form too; here the point is that the fallback ran: finite, and within 5 % of the range
