@@ -77,6 +77,19 @@ class AttnLaunchC(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("kind", "D", "dtype", "k80", "qit", "grid")] + [("family", C.c_char * 64)]
 
 
+class GnPlanC(C.Structure):
+    """dsim_gn_plan (include/diffsim_amd.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("form", "NS", "UNR", "CS", "tpr", "R", "chunks", "rb")]
+
+
+class LnPlanC(C.Structure):
+    """dsim_ln_plan (include/diffsim_amd.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("form", "LPR", "CPL", "passes", "MAXS", "RPW", "blocks")]
+
+
+GN_FORMS = ("onepass", "twopass", "pre")     # dsim_gn_plan.form, by index
+LN_FORMS = ("rows", "wave")                  # dsim_ln_plan.form, by index
+
 # dsim_attn_kind, by index
 ATTN_KINDS = ("P160", "Short", "ShortK80", "Long", "Q2", "Q2Fast", "Fast", "Exact", "FP8")
 
@@ -161,10 +174,15 @@ SYMBOLS = {
     "dsim_op_conv3x3": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "dsim_op_groupnorm": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _f, _i, _i, _vp]),
     "dsim_op_layernorm": (_i, [_vp, _vp, _vp, _vp, _i, _i, _f, _i, _vp]),
+    "dsim_op_layernorm_mod": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _vp]),
+    "dsim_groupnorm_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, C.POINTER(GnPlanC)]),
+    "dsim_layernorm_plan": (_i, [_i, _i, _i, _i, C.POINTER(LnPlanC)]),
     "dsim_op_attention": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "dsim_op_attention_fp8": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "dsim_op_ff_fused": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp]),
     "dsim_op_ln_linear": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
+    "dsim_op_ff_fused_dt": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _i, _vp]),
+    "dsim_op_ln_linear_dt": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _vp]),
     "dsim_op_gemm": (_i, [C.POINTER(GemmOpC), C.POINTER(GemmLaunchC), _vp]),
     "dsim_op_groupnorm_pre": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _f, _i, _i, _vp, _i, _vp]),
     "dsim_op_attention_ex": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(AttnLaunchC), _vp]),

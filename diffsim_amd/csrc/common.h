@@ -22,6 +22,8 @@
 #define launch_rowlin launch_rowlin_f16
 #define groupnorm_scratch_bytes groupnorm_scratch_bytes_f16
 #define groupnorm_passes groupnorm_passes_f16
+#define groupnorm_plan groupnorm_plan_f16
+#define layernorm_plan layernorm_plan_f16
 #define launch_groupnorm launch_groupnorm_f16
 #define launch_groupnorm_pre launch_groupnorm_pre_f16
 #define launch_layernorm launch_layernorm_f16
@@ -272,6 +274,10 @@ int latent_sample(const float* moments, const float* eps, float* out, int n_out,
 // norms -- norm.hip
 size_t groupnorm_scratch_bytes(int B, int groups);
 int groupnorm_passes(int C0, int C1, int HW, int groups, int dtype);    // 2 (one-pass form) or 3: algorithmic tensor passes
+// the dispatch of launch_groupnorm / launch_groupnorm_pre (pre = 1) and launch_layernorm / launch_layernorm_mod (mod = 1): the
+// function the launchers themselves call; host only, DSIM_ERR_INVALID where the launch would refuse the shape
+int groupnorm_plan(int C0, int C1, int B, int HW, int groups, int dtype, int pre, dsim_gn_plan* plan);
+int layernorm_plan(int M, int C, int dtype, int mod, dsim_ln_plan* plan);
 int launch_groupnorm(const void* x0, int C0, const void* x1, int C1, const float* gamma,
                      const float* beta, void* out, int B, int HW, int groups, float eps, int silu,
                      int dtype, void* scratch, hipStream_t s);

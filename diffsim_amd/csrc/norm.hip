@@ -469,49 +469,73 @@ __global__ __launch_bounds__(256) void layernorm_rows_kernel(const T* __restrict
     }
 }
 
+// The LayerNorm dispatch, decided in one place: ln_typed launches what this returns and layernorm_plan() reports it.
+//   form 0, layernorm_rows_kernel<T, CPL>: affine only, S = C / VEC <= 80 chunks with S / LPR (LPR = the largest power of two
+//           dividing S, at most 64) one of 1 / 3 / 5; rows per workgroup = 4 waves x passes x (64 / LPR);
+//   form 1, layernorm_kernel<T, MOD, MAXS, RPW>: every other width up to 64 * 6 * VEC; rows per workgroup = 4 x RPW.
+template <typename T>
+int ln_plan(int M, int C, bool mod, dsim_ln_plan* p) {
+    constexpr int VEC = Vec16<T>::N;
+    if (C < VEC || C % VEC || C > 64 * 6 * VEC || M < 1) return DSIM_ERR_INVALID;
+    const int S = C / VEC;
+    *p = dsim_ln_plan{};
+    if (!mod && S <= 80) {      // wider rows: the wave-per-row form below already streams at > 6 TB/s
+        int LPR = 1;
+        while (LPR < 64 && S % (LPR * 2) == 0) LPR *= 2;
+        const int CPL = S / LPR;                       // odd by construction
+        if (CPL == 1 || CPL == 3 || CPL == 5) {
+            const int rpw = 64 / LPR;
+            int passes = 4;                                             // rows per workgroup = 4 waves x passes x rpw
+            while (passes > 1 && (M + 4 * passes * rpw - 1) / (4 * passes * rpw) < 2048) passes >>= 1;
+            p->form = 0; p->LPR = LPR; p->CPL = CPL; p->passes = passes;
+            p->blocks = (M + 4 * passes * rpw - 1) / (4 * passes * rpw);
+            return DSIM_OK;
+        }
+    }
+    p->form = 1;
+    if (S <= 64) { p->MAXS = 1; p->RPW = 8; }
+    else if (S <= 128) { p->MAXS = 2; p->RPW = 2; }
+    else if (S <= 192) { p->MAXS = 3; p->RPW = 2; }
+    else { p->MAXS = 6; p->RPW = 1; }
+    p->blocks = (M + 4 * p->RPW - 1) / (4 * p->RPW);
+    return DSIM_OK;
+}
+
 template <typename T, int CPL>
-void ln_rows_launch(const void* x, const float* gamma, const float* beta, void* out, int M, int C, float eps, int LPR,
-                    hipStream_t s) {
-    const int rpw = 64 / LPR;
-    int passes = 4;                                             // rows per workgroup = 4 waves x passes x rpw
-    while (passes > 1 && (M + 4 * passes * rpw - 1) / (4 * passes * rpw) < 2048) passes >>= 1;
-    const int blocks = (M + 4 * passes * rpw - 1) / (4 * passes * rpw);
-    hipLaunchKernelGGL((layernorm_rows_kernel<T, CPL>), dim3(blocks), dim3(256), (size_t)2 * C * sizeof(float), s,
-                       (const T*)x, gamma, beta, (T*)out, M, C, eps, LPR, passes);
+void ln_rows_launch(const void* x, const float* gamma, const float* beta, void* out, int M, int C, float eps,
+                    const dsim_ln_plan& p, hipStream_t s) {
+    hipLaunchKernelGGL((layernorm_rows_kernel<T, CPL>), dim3(p.blocks), dim3(256), (size_t)2 * C * sizeof(float), s,
+                       (const T*)x, gamma, beta, (T*)out, M, C, eps, p.LPR, p.passes);
+}
+
+template <typename T, bool MOD, int MAXS, int RPW>
+void ln_wave_launch(const void* x, const float* gamma, const float* beta, void* out, int M, int C, float eps, int rpb,
+                    const dsim_ln_plan& p, hipStream_t s) {
+    hipLaunchKernelGGL((layernorm_kernel<T, MOD, MAXS, RPW>), dim3(p.blocks), dim3(256), 0, s, (const T*)x, gamma, beta,
+                       (T*)out, M, C, eps, rpb);
 }
 
 template <typename T, bool MOD>
 int ln_typed(const void* x, const float* gamma, const float* beta, void* out, int M, int C, float eps, int rpb,
              hipStream_t s) {
-    constexpr int VEC = Vec16<T>::N;
-    if (C % VEC || C > 64 * 6 * VEC || M < 1) return DSIM_ERR_INVALID;
-    const int S = C / VEC;
-    const dim3 block(256);
-    if (!MOD && S <= 80) {      // wider rows: the wave-per-row form below already streams at > 6 TB/s
-        int LPR = 1;
-        while (LPR < 64 && S % (LPR * 2) == 0) LPR *= 2;
-        const int CPL = S / LPR;                       // odd by construction
-        bool done = true;
-        switch (CPL) {
-            case 1: ln_rows_launch<T, 1>(x, gamma, beta, out, M, C, eps, LPR, s); break;
-            case 3: ln_rows_launch<T, 3>(x, gamma, beta, out, M, C, eps, LPR, s); break;
-            case 5: ln_rows_launch<T, 5>(x, gamma, beta, out, M, C, eps, LPR, s); break;
-            default: done = false;
+    dsim_ln_plan p;
+    if (ln_plan<T>(M, C, MOD, &p) != DSIM_OK) return DSIM_ERR_INVALID;
+    if (p.form == 0) {
+        if constexpr (!MOD) {
+            switch (p.CPL) {
+                case 1: ln_rows_launch<T, 1>(x, gamma, beta, out, M, C, eps, p, s); break;
+                case 3: ln_rows_launch<T, 3>(x, gamma, beta, out, M, C, eps, p, s); break;
+                default: ln_rows_launch<T, 5>(x, gamma, beta, out, M, C, eps, p, s); break;
+            }
         }
-        if (done) { DSIM_HIP_CHECK(hipGetLastError()); return DSIM_OK; }
-    }
-    if (S <= 64)
-        hipLaunchKernelGGL((layernorm_kernel<T, MOD, 1, 8>), dim3((M + 31) / 32), block, 0, s, (const T*)x, gamma, beta,
-                           (T*)out, M, C, eps, rpb);
-    else if (S <= 128)
-        hipLaunchKernelGGL((layernorm_kernel<T, MOD, 2, 2>), dim3((M + 7) / 8), block, 0, s, (const T*)x, gamma, beta,
-                           (T*)out, M, C, eps, rpb);
-    else if (S <= 192)
-        hipLaunchKernelGGL((layernorm_kernel<T, MOD, 3, 2>), dim3((M + 7) / 8), block, 0, s, (const T*)x, gamma, beta,
-                           (T*)out, M, C, eps, rpb);
+    } else if (p.MAXS == 1)
+        ln_wave_launch<T, MOD, 1, 8>(x, gamma, beta, out, M, C, eps, rpb, p, s);
+    else if (p.MAXS == 2)
+        ln_wave_launch<T, MOD, 2, 2>(x, gamma, beta, out, M, C, eps, rpb, p, s);
+    else if (p.MAXS == 3)
+        ln_wave_launch<T, MOD, 3, 2>(x, gamma, beta, out, M, C, eps, rpb, p, s);
     else
-        hipLaunchKernelGGL((layernorm_kernel<T, MOD, 6, 1>), dim3((M + 3) / 4), block, 0, s, (const T*)x, gamma, beta,
-                           (T*)out, M, C, eps, rpb);
+        ln_wave_launch<T, MOD, 6, 1>(x, gamma, beta, out, M, C, eps, rpb, p, s);
     DSIM_HIP_CHECK(hipGetLastError());
     return DSIM_OK;
 }
@@ -728,20 +752,53 @@ int gn_launch(const void* x0, int C0, const void* x1, int C1, const float* gamma
     return DSIM_OK;
 }
 
+// The GroupNorm dispatch, decided in one place: gn_typed launches what this returns and groupnorm_plan() reports it.
+//   form 0, one launch of gn_onepass_kernel: slab width CS (gn_onepass_slab), tpr = CS / VEC threads per row, R rows in flight;
+//   form 1, gn_stats_kernel + gn_apply_kernel<NS, UNR>: `chunks` statistic slabs and rb apply row blocks per image;
+//   form 2, gn_fold_kernel + gn_apply_kernel: the statistics come from a conv epilogue (chunks = 1 after the fold).
+template <typename T>
+int gn_plan(int C0, int C1, int B, int HW, int groups, bool pre, dsim_gn_plan* p) {
+    constexpr int VEC = Vec16<T>::N;
+    const int C = C0 + C1;
+    if (B < 1 || HW < 1 || groups < 1 || C < VEC) return DSIM_ERR_INVALID;
+    if (C % groups || C0 % VEC || C1 % VEC || groups > 64 || C > GN_MAX_SLOTS * GN_THREADS * VEC)
+        return DSIM_ERR_INVALID;
+    // (precomputed statistics: whole 4-channel quads per group)
+    if (pre && (C1 || groups > 64 || (C / groups) % 4)) return DSIM_ERR_INVALID;
+    *p = dsim_gn_plan{};
+    if (const int CS = !pre ? gn_onepass_slab<T>(C0, C1, B, HW, groups) : 0) {
+        p->form = 0; p->NS = 1; p->CS = CS; p->tpr = CS / VEC; p->R = GN_THREADS / p->tpr;
+        return DSIM_OK;
+    }
+    const int S = C / VEC, tpr = S < GN_THREADS ? S : GN_THREADS, R = GN_THREADS / tpr;
+    if ((size_t)R * C * 2 * sizeof(float) > 64 * 1024) return DSIM_ERR_INVALID;      // gn_stats_kernel's LDS
+    // row blocks per image of the apply pass (no effect on the numbers): about 1024 workgroups in all, so that large
+    // batches amortise each workgroup's statistics fold over more rows and small batches still fill the chip
+    int rb = HW / (R * 4);
+    const int want = (1024 + B - 1) / B;
+    if (rb > want) rb = want;
+    rb = rb < 1 ? 1 : (rb > 64 ? 64 : rb);
+    const int ns = (S + tpr - 1) / tpr;
+    p->form = pre ? 2 : 1;
+    p->NS = ns == 1 ? 1 : (ns == 2 ? 2 : GN_MAX_SLOTS);
+    p->UNR = ns == 1 ? 4 : (ns == 2 ? 2 : 1);
+    p->CS = C; p->tpr = tpr; p->R = R;
+    p->chunks = pre ? 1 : gn_chunks(HW);
+    p->rb = rb;
+    return DSIM_OK;
+}
+
 template <typename T>
 int gn_typed(const void* x0, int C0, const void* x1, int C1, const float* gamma, const float* beta,
              void* out, int B, int HW, int groups, float eps, int silu, void* scratch, hipStream_t s,
              const float* pre = nullptr, int pre_chunks = 0) {
-    constexpr int VEC = Vec16<T>::N;
-    const int C = C0 + (x1 ? C1 : 0);
     if (!x1) C1 = 0;
-    if (C % groups || C0 % VEC || C1 % VEC || groups > 64 || C > GN_MAX_SLOTS * GN_THREADS * VEC)
-        return DSIM_ERR_INVALID;
-    // (precomputed statistics: whole 4-channel quads per group)
-    if (pre && (x1 || groups > 64 || (C / groups) % 4)) return DSIM_ERR_INVALID;
-    if (const int CS = !pre ? gn_onepass_slab<T>(C0, C1, B, HW, groups) : 0) {
-        const int tpr1 = CS / VEC, R1 = GN_THREADS / tpr1;
-        const size_t lds1 = (size_t)R1 * CS * 2 * sizeof(float);
+    const int C = C0 + C1;
+    dsim_gn_plan p;
+    if (gn_plan<T>(C0, C1, B, HW, groups, pre != nullptr, &p) != DSIM_OK) return DSIM_ERR_INVALID;
+    if (p.form == 0) {
+        const int CS = p.CS;
+        const size_t lds1 = (size_t)p.R * CS * 2 * sizeof(float);
         if (silu)
             hipLaunchKernelGGL((gn_onepass_kernel<T, true, GN_OP_MAXCH>), dim3(C / CS, B), dim3(GN_THREADS), lds1, s, (const T*)x0, C0,
                                (const T*)x1, C1, gamma, beta, (T*)out, HW, groups, eps, CS);
@@ -751,31 +808,39 @@ int gn_typed(const void* x0, int C0, const void* x1, int C1, const float* gamma,
         DSIM_HIP_CHECK(hipGetLastError());
         return DSIM_OK;
     }
-    const int S = C / VEC, tpr = S < GN_THREADS ? S : GN_THREADS, R = GN_THREADS / tpr;
-    const int chunks = gn_chunks(HW);
-    const size_t lds = (size_t)R * C * 2 * sizeof(float);
-    if (lds > 64 * 1024) return DSIM_ERR_INVALID;
-    // row blocks per image of the apply pass (no effect on the numbers): about 1024 workgroups in all, so that large
-    // batches amortise each workgroup's statistics fold over more rows and small batches still fill the chip
-    int rb = HW / (R * 4);
-    const int want = (1024 + B - 1) / B;
-    if (rb > want) rb = want;
-    rb = rb < 1 ? 1 : (rb > 64 ? 64 : rb);
-    const int ns = (S + tpr - 1) / tpr;
-    if (ns == 1)
-        return gn_launch<T, 1, 4>(x0, C0, x1, C1, gamma, beta, out, B, HW, groups, eps, silu, scratch, chunks, rb, lds, s, pre, pre_chunks);
-    if (ns == 2)
-        return gn_launch<T, 2, 2>(x0, C0, x1, C1, gamma, beta, out, B, HW, groups, eps, silu, scratch, chunks, rb, lds, s, pre, pre_chunks);
-    return gn_launch<T, GN_MAX_SLOTS, 1>(x0, C0, x1, C1, gamma, beta, out, B, HW, groups, eps, silu, scratch, chunks, rb,
+    const size_t lds = (size_t)p.R * C * 2 * sizeof(float);
+    const int chunks = pre ? 0 : p.chunks;      // (gn_launch sets 1 after the fold)
+    if (p.NS == 1)
+        return gn_launch<T, 1, 4>(x0, C0, x1, C1, gamma, beta, out, B, HW, groups, eps, silu, scratch, chunks, p.rb, lds, s, pre, pre_chunks);
+    if (p.NS == 2)
+        return gn_launch<T, 2, 2>(x0, C0, x1, C1, gamma, beta, out, B, HW, groups, eps, silu, scratch, chunks, p.rb, lds, s, pre, pre_chunks);
+    return gn_launch<T, GN_MAX_SLOTS, 1>(x0, C0, x1, C1, gamma, beta, out, B, HW, groups, eps, silu, scratch, chunks, p.rb,
                                          lds, s, pre, pre_chunks);
 }
 
 }  // namespace
 
+// the kernels launch_groupnorm (pre = 0) / launch_groupnorm_pre (pre = 1) start for this shape; host only
+int groupnorm_plan(int C0, int C1, int B, int HW, int groups, int dtype, int pre, dsim_gn_plan* p) {
+    if (!p) return DSIM_ERR_INVALID;
+    if (dtype == DSIM_F32) return pre ? DSIM_ERR_INVALID : gn_plan<float>(C0, C1, B, HW, groups, false, p);
+    if (dtype == DSIM_BF16 || dtype == DSIM_F16) return gn_plan<h16>(C0, C1, B, HW, groups, pre != 0, p);   // (either 16-bit type)
+    return DSIM_ERR_INVALID;
+}
+
+// the kernel launch_layernorm (mod = 0) / launch_layernorm_mod (mod = 1) starts for this shape; host only
+int layernorm_plan(int M, int C, int dtype, int mod, dsim_ln_plan* p) {
+    if (!p) return DSIM_ERR_INVALID;
+    if (dtype == DSIM_F32) return ln_plan<float>(M, C, mod != 0, p);
+    if (dtype == DSIM_BF16 || dtype == DSIM_F16) return ln_plan<h16>(M, C, mod != 0, p);
+    return DSIM_ERR_INVALID;
+}
+
 // passes over the tensor the GroupNorm of this shape makes (2 = one-pass form: read + write; 3 = statistics read + read + write)
 int groupnorm_passes(int C0, int C1, int HW, int groups, int dtype) {
-    const int cs = dtype == DSIM_F32 ? gn_onepass_slab<float>(C0, C1, 1, HW, groups) : gn_onepass_slab<h16>(C0, C1, 1, HW, groups);   // (either 16-bit type)
-    return cs ? 2 : 3;
+    dsim_gn_plan p;
+    if (groupnorm_plan(C0, C1, 1, HW, groups, dtype, 0, &p) != DSIM_OK) return 3;
+    return p.form == 0 ? 2 : 3;
 }
 
 size_t groupnorm_scratch_bytes(int B, int groups) { return (size_t)B * 64 * groups * 2 * sizeof(double); }

@@ -1236,44 +1236,69 @@ int dsim_op_layernorm(const void* x, const float* gamma, const float* beta, void
     return DSIM_OK;
 }
 
-int dsim_op_ff_fused(const void* x, const float* ln_gamma, const float* ln_beta, const float* w1, const float* b1,
-                     const float* w2, const float* b2, void* out, int M, int C, float eps, void* stream) {
+int dsim_op_layernorm_mod(const void* x, const float* scale2, const float* shift2, void* out, int M, int C, int rows_per_batch,
+                          float eps, int dtype, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (!x || !scale2 || !shift2 || !out) return DSIM_ERR_INVALID;
+    CK(launch_layernorm_mod(x, scale2, shift2, out, M, C, rows_per_batch, eps, dtype, s));
+    DSIM_HIP_CHECK(hipStreamSynchronize(s));
+    return DSIM_OK;
+}
+
+int dsim_groupnorm_plan(int C0, int C1, int B, int HW, int groups, int dtype, int pre, dsim_gn_plan* plan) {
+    return groupnorm_plan(C0, C1, B, HW, groups, dtype, pre, plan);
+}
+
+int dsim_layernorm_plan(int M, int C, int dtype, int mod, dsim_ln_plan* plan) { return layernorm_plan(M, C, dtype, mod, plan); }
+
+int dsim_op_ff_fused_dt(const void* x, const float* ln_gamma, const float* ln_beta, const float* w1, const float* b1,
+                        const float* w2, const float* b2, void* out, int M, int C, float eps, int dtype, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     const size_t sb = ff_stream_bytes(C);
-    if (!sb || !x || !out || !w1 || !b1 || !w2 || !b2 || !ln_gamma || !ln_beta) return DSIM_ERR_INVALID;
+    if ((dtype != DSIM_BF16 && dtype != DSIM_F16) || !sb || !x || !out || !w1 || !b1 || !w2 || !b2 || !ln_gamma || !ln_beta) return DSIM_ERR_INVALID;
     Tmp t;
     void* w1p = t.get((size_t)8 * C * C * 2);
     float* b1p = (float*)t.get((size_t)8 * C * 4);
     void* w2p = t.get((size_t)4 * C * C * 2);
     void* st = t.get(sb);
     if (!w1p || !b1p || !w2p || !st) return DSIM_ERR_HIP;
-    CK(pack_linear(w1, DSIM_F32, w1p, DSIM_BF16, 8 * C, C, 32, s));
+    CK(pack_linear(w1, DSIM_F32, w1p, dtype, 8 * C, C, 32, s));
     CK(pack_vector(b1, DSIM_F32, b1p, 8 * C, 32, s));
-    CK(pack_linear(w2, DSIM_F32, w2p, DSIM_BF16, C, 4 * C, 0, s));
+    CK(pack_linear(w2, DSIM_F32, w2p, dtype, C, 4 * C, 0, s));
     CK(pack_ff_stream(w1p, w2p, st, C, s));
     FFArgs a;
-    a.x = x; a.out = out; a.ln_g = ln_gamma; a.ln_b = ln_beta; a.stream = st; a.b1 = b1p; a.b2 = b2; a.M = M; a.C = C; a.eps = eps;
+    a.x = x; a.out = out; a.ln_g = ln_gamma; a.ln_b = ln_beta; a.stream = st; a.b1 = b1p; a.b2 = b2; a.M = M; a.C = C; a.eps = eps; a.dtype = dtype;
     CK(launch_ff_fused(a, s));
+    DSIM_HIP_CHECK(hipStreamSynchronize(s));
+    return DSIM_OK;
+}
+
+int dsim_op_ff_fused(const void* x, const float* ln_gamma, const float* ln_beta, const float* w1, const float* b1,
+                     const float* w2, const float* b2, void* out, int M, int C, float eps, void* stream) {
+    return dsim_op_ff_fused_dt(x, ln_gamma, ln_beta, w1, b1, w2, b2, out, M, C, eps, DSIM_BF16, stream);
+}
+
+int dsim_op_ln_linear_dt(const void* x, const float* ln_gamma, const float* ln_beta, const float* w, void* out, int M, int C, int N,
+                         float eps, int dtype, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    const size_t sb = rowlin_stream_bytes(C, N);
+    if ((dtype != DSIM_BF16 && dtype != DSIM_F16) || !sb || !x || !out || !w || !ln_gamma != !ln_beta) return DSIM_ERR_INVALID;
+    Tmp t;
+    void* wp = t.get((size_t)N * C * 2);
+    void* st = t.get(sb);
+    if (!wp || !st) return DSIM_ERR_HIP;
+    CK(pack_linear(w, DSIM_F32, wp, dtype, N, C, 0, s));
+    CK(pack_rowlin_stream(wp, st, C, N, s));
+    RowLinArgs a;
+    a.x = x; a.out = out; a.ln_g = ln_gamma; a.ln_b = ln_beta; a.stream = st; a.M = M; a.C = C; a.N = N; a.eps = eps; a.dtype = dtype;
+    CK(launch_rowlin(a, s));
     DSIM_HIP_CHECK(hipStreamSynchronize(s));
     return DSIM_OK;
 }
 
 int dsim_op_ln_linear(const void* x, const float* ln_gamma, const float* ln_beta, const float* w, void* out, int M, int C, int N,
                       float eps, void* stream) {
-    hipStream_t s = (hipStream_t)stream;
-    const size_t sb = rowlin_stream_bytes(C, N);
-    if (!sb || !x || !out || !w || !ln_gamma != !ln_beta) return DSIM_ERR_INVALID;
-    Tmp t;
-    void* wp = t.get((size_t)N * C * 2);
-    void* st = t.get(sb);
-    if (!wp || !st) return DSIM_ERR_HIP;
-    CK(pack_linear(w, DSIM_F32, wp, DSIM_BF16, N, C, 0, s));
-    CK(pack_rowlin_stream(wp, st, C, N, s));
-    RowLinArgs a;
-    a.x = x; a.out = out; a.ln_g = ln_gamma; a.ln_b = ln_beta; a.stream = st; a.M = M; a.C = C; a.N = N; a.eps = eps;
-    CK(launch_rowlin(a, s));
-    DSIM_HIP_CHECK(hipStreamSynchronize(s));
-    return DSIM_OK;
+    return dsim_op_ln_linear_dt(x, ln_gamma, ln_beta, w, out, M, C, N, eps, DSIM_BF16, stream);
 }
 
 int dsim_op_attention(const void* q, int ldq, const void* k, const void* v, int ldk, void* out, int ldo, int B, int Bkv,

@@ -613,30 +613,32 @@ def op_linear(x, w, bias=None, residual=None, geglu=False):
 
 
 def op_ff_fused(x, ln_g, ln_b, w1, b1, w2, b2, eps=1e-5):
-    """x + ff.net.2(GEGLU(ff.net.0.proj(LayerNorm(x)))) in one launch (bf16, C = 320); w1 [8C][C], w2 [C][4C] f32."""
+    """x + ff.net.2(GEGLU(ff.net.0.proj(LayerNorm(x)))) in one launch (bf16, or fp16: the twin kernel; C = 320); w1 [8C][C],
+    w2 [C][4C] f32."""
     L = _lib.lib()
     _require_cuda(x, ln_g, ln_b, w1, b1, w2, b2)
-    if x.dtype != torch.bfloat16:          # the op-level entry point packs and launches in bf16 only (the engines run the fp16 twin)
-        raise TypeError("op_ff_fused takes a torch.bfloat16 input")
+    if x.dtype not in (torch.bfloat16, torch.float16):
+        raise TypeError("op_ff_fused takes a torch.bfloat16 or torch.float16 input")
     M, Cc = x.shape
     out = torch.empty_like(x)
-    _lib.check(L.dsim_op_ff_fused(x.data_ptr(), ln_g.data_ptr(), ln_b.data_ptr(), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(),
-                                  b2.data_ptr(), out.data_ptr(), M, Cc, float(eps), _stream_ptr()), "op_ff_fused")
+    _lib.check(L.dsim_op_ff_fused_dt(x.data_ptr(), ln_g.data_ptr(), ln_b.data_ptr(), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(),
+                                     b2.data_ptr(), out.data_ptr(), M, Cc, float(eps), _TORCH2DSIM[x.dtype], _stream_ptr()),
+               "op_ff_fused")
     return out
 
 
 def op_ln_linear(x, ln_g, ln_b, w, eps=1e-5):
-    """LayerNorm(x) W^T in one launch (bf16, C = 320, bias-free, N a multiple of 64 up to 960); w [N][C] f32; ln_g = ln_b = None
-    skips the LayerNorm."""
+    """LayerNorm(x) W^T in one launch (bf16, or fp16: the twin kernel; C = 320, bias-free, N a multiple of 64 up to 960); w [N][C]
+    f32; ln_g = ln_b = None skips the LayerNorm."""
     L = _lib.lib()
     _require_cuda(x, ln_g, ln_b, w)
-    if x.dtype != torch.bfloat16:          # as op_ff_fused: bf16 only at the op level
-        raise TypeError("op_ln_linear takes a torch.bfloat16 input")
+    if x.dtype not in (torch.bfloat16, torch.float16):
+        raise TypeError("op_ln_linear takes a torch.bfloat16 or torch.float16 input")
     M, Cc = x.shape
     N = w.shape[0]
     out = torch.empty((M, N), dtype=x.dtype, device=x.device)
-    _lib.check(L.dsim_op_ln_linear(x.data_ptr(), _ptr(ln_g), _ptr(ln_b), w.data_ptr(), out.data_ptr(), M, Cc, N, float(eps),
-                                   _stream_ptr()), "op_ln_linear")
+    _lib.check(L.dsim_op_ln_linear_dt(x.data_ptr(), _ptr(ln_g), _ptr(ln_b), w.data_ptr(), out.data_ptr(), M, Cc, N, float(eps),
+                                      _TORCH2DSIM[x.dtype], _stream_ptr()), "op_ln_linear")
     return out
 
 
@@ -769,6 +771,41 @@ def op_layernorm(x, gamma, beta, eps=1e-5):
     _lib.check(L.dsim_op_layernorm(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), out.data_ptr(), M, Cc, float(eps),
                                    _TORCH2DSIM[x.dtype], _stream_ptr()), "op_layernorm")
     return out
+
+
+def op_layernorm_mod(x, scale2, shift2, rows_per_batch, eps=1e-6, out=None):
+    """LayerNorm without affine, then y = xhat * (1 + scale2[half]) + shift2[half], half = (row // rows_per_batch) & 1 (DiT's adaLN
+    modulation); x [M][C], scale2 / shift2 f32 [2][C].  out: None (a new tensor) or a tensor to write (x itself: in place)."""
+    L = _lib.lib()
+    _require_cuda(x, scale2, shift2, out)
+    M, Cc = x.shape
+    for t, nm in ((scale2, "scale2"), (shift2, "shift2")):
+        if t.dtype != torch.float32 or t.numel() != 2 * Cc:
+            raise _lib.DsimError(f"{nm} must be f32 [2][C]")
+    out = torch.empty_like(x) if out is None else out
+    _lib.check(L.dsim_op_layernorm_mod(x.data_ptr(), scale2.data_ptr(), shift2.data_ptr(), out.data_ptr(), M, Cc, int(rows_per_batch),
+                                       float(eps), _TORCH2DSIM[x.dtype], _stream_ptr()), "op_layernorm_mod")
+    return out
+
+
+def groupnorm_plan(C0, C1, B, HW, groups, dtype, pre=False):
+    """What op_groupnorm (op_groupnorm_pre with pre) launches for this shape: dict(form "onepass" / "twopass" / "pre", NS, UNR, CS,
+    tpr, R, chunks, rb), from the function the launcher itself calls.  Host only; raises DsimError where the launch would refuse."""
+    p = _lib.GnPlanC()
+    _lib.check(_lib.lib().dsim_groupnorm_plan(int(C0), int(C1), int(B), int(HW), int(groups), _TORCH2DSIM[dtype], int(bool(pre)),
+                                              C.byref(p)), "groupnorm_plan")
+    d = {n: getattr(p, n) for n, _ in p._fields_}
+    d["form"] = _lib.GN_FORMS[p.form]
+    return d
+
+
+def layernorm_plan(M, Cc, dtype, mod=False):
+    """What op_layernorm (op_layernorm_mod with mod) launches: dict(form "rows" / "wave", LPR, CPL, passes, MAXS, RPW, blocks)."""
+    p = _lib.LnPlanC()
+    _lib.check(_lib.lib().dsim_layernorm_plan(int(M), int(Cc), _TORCH2DSIM[dtype], int(bool(mod)), C.byref(p)), "layernorm_plan")
+    d = {n: getattr(p, n) for n, _ in p._fields_}
+    d["form"] = _lib.LN_FORMS[p.form]
+    return d
 
 
 def op_attention(q, k, v, heads, fp8: bool = False):

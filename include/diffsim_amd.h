@@ -381,6 +381,30 @@ int dsim_op_groupnorm(const void* x0, int C0, const void* x1, int C1, const floa
                       int silu, int dtype, void* stream);
 int dsim_op_layernorm(const void* x, const float* gamma, const float* beta, void* out, int M,
                       int C, float eps, int dtype, void* stream);
+/* LayerNorm without affine, then the adaLN modulation y = LN(x) * (1 + scale2[half]) + shift2[half], half = (row / rows_per_batch) & 1
+ * (DiT blocks: the two CFG halves of a batch alternate every rows_per_batch rows); scale2 / shift2: f32 [2][C]; in place allowed. */
+int dsim_op_layernorm_mod(const void* x, const float* scale2, const float* shift2, void* out, int M, int C, int rows_per_batch,
+                          float eps, int dtype, void* stream);
+/* What dsim_op_groupnorm (pre = 0) / dsim_op_groupnorm_pre (pre = 1) launch for a shape: the launcher's own decision (it calls the
+ * same function).  Host code only, runs without a device; DSIM_ERR_INVALID where the launch would refuse the shape. */
+typedef struct dsim_gn_plan {
+    int form;                                   /* 0 one-pass (gn_onepass_kernel), 1 two-pass (gn_stats_kernel + gn_apply_kernel),
+                                                   2 pre (gn_fold_kernel + gn_apply_kernel) */
+    int NS, UNR;                                /* 16-byte channel slots per thread and rows in flight per thread (one-pass: 1, 0) */
+    int CS;                                     /* channels a workgroup covers: the one-pass slab width, else C */
+    int tpr, R;                                 /* threads per row and rows in flight per workgroup (R = 256 / tpr) */
+    int chunks;                                 /* statistic slabs per image (one-pass: 0; pre: 1, the folded pair) */
+    int rb;                                     /* row blocks per image of the apply pass (one-pass: 0) */
+} dsim_gn_plan;
+int dsim_groupnorm_plan(int C0, int C1, int B, int HW, int groups, int dtype, int pre, dsim_gn_plan* plan);
+/* The same for dsim_op_layernorm (mod = 0) / dsim_op_layernorm_mod (mod = 1). */
+typedef struct dsim_ln_plan {
+    int form;                                   /* 0 lanes-per-row (layernorm_rows_kernel<CPL>), 1 wave-per-row (layernorm_kernel<MAXS, RPW>) */
+    int LPR, CPL, passes;                       /* form 0: lanes per row, 16-byte chunks per lane, wave passes per workgroup (else 0) */
+    int MAXS, RPW;                              /* form 1: chunk slots per lane, rows per wave (else 0) */
+    int blocks;                                 /* workgroups */
+} dsim_ln_plan;
+int dsim_layernorm_plan(int M, int C, int dtype, int mod, dsim_ln_plan* plan);
 /* q: [B][Nq][ldq] at column offset h*D; k,v: [Bkv][Nk][ldk]; batch b reads kv batch b % Bkv */
 int dsim_op_attention(const void* q, int ldq, const void* k, const void* v, int ldk, void* out,
                       int ldo, int B, int Bkv, int H, int Nq, int Nk, int D, int dtype,
@@ -436,6 +460,13 @@ int dsim_op_ff_fused(const void* x, const float* ln_gamma, const float* ln_beta,
  * ln_gamma = ln_beta = NULL skips the LayerNorm.  Returns DSIM_ERR_INVALID for a shape the kernel does not cover.            */
 int dsim_op_ln_linear(const void* x, const float* ln_gamma, const float* ln_beta, const float* w, void* out, int M, int C,
                       int N, float eps, void* stream);
+
+/* dsim_op_ff_fused / dsim_op_ln_linear in either 16-bit compute dtype (DSIM_BF16: the two above; DSIM_F16: the fp16 twins the
+ * engines run in fp16 mode); x / out in that dtype. */
+int dsim_op_ff_fused_dt(const void* x, const float* ln_gamma, const float* ln_beta, const float* w1, const float* b1,
+                        const float* w2, const float* b2, void* out, int M, int C, float eps, int dtype, void* stream);
+int dsim_op_ln_linear_dt(const void* x, const float* ln_gamma, const float* ln_beta, const float* w, void* out, int M, int C,
+                         int N, float eps, int dtype, void* stream);
 
 /* The implicit GEMM with every epilogue field the engines use, as one operator (parity tests of each tile and epilogue).
  *   out[m][n] = epi(sum_k A(m,k) W[n][k] + bias[n]); the A0 | A1 channel concatenation along K (linear), or the 3x3 conv of

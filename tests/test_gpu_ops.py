@@ -62,6 +62,21 @@ def _attn_f64(got, q, k, v, H, dtype, fp8=False):
     assert r <= 1.0, f"{kind} d{D}: err / bound {r:.3f}"
 
 
+def _norm_f64(got, x0, x1, gamma, beta, dtype, *, groups=0, eps=1e-5, silu=False):
+    """beside _close: every element within tests/_norm64.py's float64 bound for the form engine.groupnorm_plan / layernorm_plan names
+    (x0 / x1 the device operands in the compute dtype; groups = 0: LayerNorm of x0 [M][C])"""
+    from diffsim_amd import engine
+    from tests import _norm64 as N
+    if groups:
+        B, HW, C0 = x0.shape
+        plan = engine.groupnorm_plan(C0, 0 if x1 is None else x1.shape[2], B, HW, groups, dtype)
+        ref, bound = N.gn_ref_and_bound(x0, x1, gamma.cuda(), beta.cuda(), groups, eps, silu, dtype, N.gn_n_p(plan, HW))
+    else:
+        plan = engine.layernorm_plan(x0.shape[0], x0.shape[1], dtype)
+        ref, bound = N.ln_ref_and_bound(x0, gamma.cuda(), beta.cuda(), eps, dtype, depth=N.ln_depth(plan, dtype))
+    N.check(got, ref, bound, f"float64 bound {plan}")
+
+
 @pytest.fixture(scope="module")
 def eng():
     from diffsim_amd import engine
@@ -154,6 +169,7 @@ def test_groupnorm(eng, dtype, B, HW, C0, C1, silu, eps):
     x1 = _dev(x[:, :, C0:], dtype) if C1 else None
     got = eng.op_groupnorm(x0, x1, _dev(gamma), _dev(beta), 32, eps, silu)
     _close(got, want, dtype)
+    _norm_f64(got, x0, x1, gamma, beta, dtype, groups=32, eps=eps, silu=silu)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -168,6 +184,7 @@ def test_groupnorm_group_counts(eng, dtype, B, HW, C, groups):
     want = F.group_norm(_q(x, dtype).permute(0, 2, 1), groups, gamma, beta, 1e-5).permute(0, 2, 1)
     got = eng.op_groupnorm(_dev(x, dtype), None, _dev(gamma), _dev(beta), groups, 1e-5, False)
     _close(got, want, dtype)
+    _norm_f64(got, _dev(x, dtype), None, gamma, beta, dtype, groups=groups)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -184,6 +201,7 @@ def test_layernorm(eng, dtype, M, C):
     want = F.layer_norm(_q(x, dtype), (C,), gamma, beta, 1e-5)
     got = eng.op_layernorm(_dev(x, dtype), _dev(gamma), _dev(beta))
     _close(got, want, dtype)
+    _norm_f64(got, _dev(x, dtype), None, gamma, beta, dtype)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
