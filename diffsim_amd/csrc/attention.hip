@@ -1722,6 +1722,7 @@ int launch_maps_t(const void* q, const void* k, const void* v, const int32_t* ia
 int g_attn_dbg = 0;
 #endif
 
+inline namespace DSIM_H16_NS {
 const char* attention_kernel_kind(const AttnArgs& a, int dtype) { return attn_kind_suffix((int)attention_kernel(a, dtype)); }
 
 // the arguments launch_attention refuses whatever the kernel
@@ -1732,14 +1733,12 @@ static bool attention_args_ok(const AttnArgs& a, int dtype) {
 
 int attention_plan(const AttnArgs& a, int dtype) {
     if (!attention_args_ok(a, dtype)) return DSIM_ERR_INVALID;
+    bool own = dtype == DSIM_H16;
 #ifndef DSIM_H16_IS_F16
-#ifdef DSIM_HAS_F16_TWINS
-    if (dtype == DSIM_F16) return attention_plan_f16(a, dtype);
+    own |= dtype == DSIM_F32;
+    if (dtype == DSIM_F16) return DSIM_F16_TWIN(attention_plan(a, dtype));
 #endif
-    if (dtype != DSIM_H16 && dtype != DSIM_F32) return DSIM_ERR_INVALID;
-#else
-    if (dtype != DSIM_H16) return DSIM_ERR_INVALID;
-#endif
+    if (!own) return DSIM_ERR_INVALID;
     const int st = with_head_dim(a.D, [](auto) { return DSIM_OK; });
     return st != DSIM_OK ? st : (int)attention_kernel(a, dtype);
 }
@@ -1752,9 +1751,7 @@ int launch_attention(const AttnArgs& a, int dtype, hipStream_t s) {
     }
 #ifndef DSIM_H16_IS_F16
     if (dtype == DSIM_F32) return launch_attn_t<float>(a, attention_kernel(a, dtype), s);
-#ifdef DSIM_HAS_F16_TWINS
-    if (dtype == DSIM_F16) return launch_attention_f16(a, dtype, s);
-#endif
+    if (dtype == DSIM_F16) return DSIM_F16_TWIN(launch_attention(a, dtype, s));
 #endif
     return DSIM_ERR_INVALID;
 }
@@ -1781,10 +1778,8 @@ int launch_pair_score(const void* q, const void* k, const void* v, const int32_t
     }
 #ifndef DSIM_H16_IS_F16
     if (dtype == DSIM_F32) return launch_tail_t<float>(q, k, v, ia, ib, n_pairs, B, H, N, D, similarity, out, scratch, s, status);
-#ifdef DSIM_HAS_F16_TWINS
     if (dtype == DSIM_F16)
-        return launch_pair_score_f16(q, k, v, ia, ib, n_pairs, B, H, N, D, dtype, similarity, out, scratch, scratch_bytes, s, status);
-#endif
+        return DSIM_F16_TWIN(launch_pair_score(q, k, v, ia, ib, n_pairs, B, H, N, D, dtype, similarity, out, scratch, scratch_bytes, s, status));
 #endif
     return DSIM_ERR_INVALID;
 }
@@ -1814,10 +1809,8 @@ int launch_score_matrix(const void* qa, const void* ka, const void* va, int n_a,
 #ifndef DSIM_H16_IS_F16
     if (dtype == DSIM_F32)
         return launch_matrix_t<float>(qa, ka, va, n_a, qb, kb, vb, n_b, B, H, N, D, similarity, out, status, scratch, s);
-#ifdef DSIM_HAS_F16_TWINS
     if (dtype == DSIM_F16)
-        return launch_score_matrix_f16(qa, ka, va, n_a, qb, kb, vb, n_b, B, H, N, D, dtype, similarity, out, status, scratch, scratch_bytes, s);
-#endif
+        return DSIM_F16_TWIN(launch_score_matrix(qa, ka, va, n_a, qb, kb, vb, n_b, B, H, N, D, dtype, similarity, out, status, scratch, scratch_bytes, s));
 #endif
     return DSIM_ERR_INVALID;
 }
@@ -1841,13 +1834,12 @@ int launch_pair_score_maps(const void* q, const void* k, const void* v, const in
 #ifndef DSIM_H16_IS_F16
     if (dtype == DSIM_F32)
         return launch_maps_t<float>(q, k, v, ia, ib, n_pairs, B, H, N, D, similarity, score, local, contrib, status, scratch, s);
-#ifdef DSIM_HAS_F16_TWINS
     if (dtype == DSIM_F16)
-        return launch_pair_score_maps_f16(q, k, v, ia, ib, n_pairs, B, H, N, D, dtype, similarity, score, local, contrib, status, scratch,
-                                          scratch_bytes, s);
-#endif
+        return DSIM_F16_TWIN(launch_pair_score_maps(q, k, v, ia, ib, n_pairs, B, H, N, D, dtype, similarity, score, local, contrib, status,
+                                                    scratch, scratch_bytes, s));
 #endif
     return DSIM_ERR_INVALID;
 }
+}  // namespace DSIM_H16_NS
 
 }  // namespace dsim

@@ -1150,6 +1150,7 @@ float* g_tail160_dbg = nullptr;
 int g_tail160_exp = 0;
 #endif
 
+inline namespace DSIM_H16_NS {
 bool pair_score160_applies(int N, int D, int dtype) { return N == A_N && D == A_D && dtype == DSIM_H16; }
 
 // the U-Net's 256-token, d = 160 self-attention on the persistent core: 16-bit types, one K / V per query batch element, 16-byte rows
@@ -1246,5 +1247,6 @@ int launch_pair_score160(const void* q, const void* k, const void* v, const int3
     DSIM_HIP_CHECK(hipGetLastError());
     return DSIM_OK;
 }
+}  // namespace DSIM_H16_NS
 
 }  // namespace dsim

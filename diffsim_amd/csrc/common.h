@@ -6,62 +6,20 @@
 
 #include "../../include/diffsim_amd.h"
 
-// ---- second compilation (h16 = fp16): the entry points of gemm / rowres / norm / attention .hip under an _f16 suffix ----------
-#ifdef DSIM_H16_IS_F16
-#define launch_gemm launch_gemm_f16
-#define gemm_tile_choice gemm_tile_choice_f16
-#define gemm_launch_tile gemm_launch_tile_f16
-#define gemm_band_width gemm_band_width_f16
-#define gemm_fill_extents gemm_fill_extents_f16
-#define gemm_skinny_applies gemm_skinny_applies_f16
-#define gemm_skinny_tile gemm_skinny_tile_f16
-#define launch_gemm_skinny launch_gemm_skinny_f16
-#define cu_count cu_count_f16
-#define rowlin_stream_bytes rowlin_stream_bytes_f16
-#define pack_rowlin_stream pack_rowlin_stream_f16
-#define launch_rowlin launch_rowlin_f16
-#define groupnorm_scratch_bytes groupnorm_scratch_bytes_f16
-#define groupnorm_passes groupnorm_passes_f16
-#define groupnorm_plan groupnorm_plan_f16
-#define layernorm_plan layernorm_plan_f16
-#define launch_groupnorm launch_groupnorm_f16
-#define launch_groupnorm_pre launch_groupnorm_pre_f16
-#define launch_layernorm launch_layernorm_f16
-#define launch_layernorm_mod launch_layernorm_mod_f16
-#define launch_softmax_rows launch_softmax_rows_f16
-#define launch_attention launch_attention_f16
-#define attention_kernel_kind attention_kernel_kind_f16
-#define attention_plan attention_plan_f16
-#define pair_score_scratch_bytes pair_score_scratch_bytes_f16
-#define launch_pair_score launch_pair_score_f16
-#define pair_score160_applies pair_score160_applies_f16
-#define pair_score160_scratch_bytes pair_score160_scratch_bytes_f16
-#define launch_pair_score160 launch_pair_score160_f16
-#define sdpa160_applies sdpa160_applies_f16
-#define launch_sdpa160 launch_sdpa160_f16
-#define score_matrix_scratch_bytes score_matrix_scratch_bytes_f16
-#define launch_score_matrix launch_score_matrix_f16
-#define score_matrix160_scratch_bytes score_matrix160_scratch_bytes_f16
-#define launch_score_matrix160 launch_score_matrix160_f16
-#define pair_score_maps_scratch_bytes pair_score_maps_scratch_bytes_f16
-#define launch_pair_score_maps launch_pair_score_maps_f16
-#define ff_stream_bytes ff_stream_bytes_f16
-#define pack_ff_stream pack_ff_stream_f16
-#define launch_ff_fused launch_ff_fused_f16
-#endif
-
 namespace dsim {
 
-// The 16-bit compute type.  The kernel sources (gemm / rowres / norm / attention .hip) are written against ONE 16-bit type,
-// h16, and are compiled twice (diffsim_amd/build.py): once with h16 = bf16 (compute dtype DSIM_BF16, the headline mode) and
-// once with -DDSIM_H16_IS_F16, h16 = IEEE fp16 (DSIM_F16: the arithmetic type the reference's drivers run in,
-// /root/reference/cute_main.py:31, diffsim/diffsim.py:82).  The fp16 objects carry the same entry points under an _f16
-// suffix (the #define block at the end of this header); the bf16 objects own the plain names and forward DSIM_F16 calls.
+// The 16-bit compute type.  The kernel sources gemm / gemm_skinny / rowres / attention / attn160 .hip are written against ONE
+// 16-bit type, h16, and are compiled twice (diffsim_amd/build.py): once with h16 = bf16 (compute dtype DSIM_BF16, the headline
+// mode) and once with -DDSIM_H16_IS_F16, h16 = IEEE fp16 (DSIM_F16: the arithmetic type the reference's drivers run in,
+// /root/reference/cute_main.py:31, diffsim/diffsim.py:82).  Their host entry points (h16_api.h) live in the inline namespace
+// DSIM_H16_NS, dsim::bf16 or dsim::f16: every caller names them unqualified and reaches the functions of its own compilation, and
+// the bf16 ones forward DSIM_F16 calls with DSIM_F16_TWIN (below).  The kernels stay in dsim::(anonymous namespace).
 // v_mfma_f32_16x16x32_f16 / v_mfma_f32_32x32x16_f16 take the same cycles as the bf16 forms, so tiles and schedules are shared.
 typedef __bf16 bf16_t;
 typedef _Float16 f16_t;
 #ifdef DSIM_H16_IS_F16
 typedef _Float16 h16;
+#define DSIM_H16_NS f16
 #define DSIM_H16 DSIM_F16
 #define DSIM_H16_ONE_BITS 0x3C00u
 // fixed-reference softmax (attention.hip attend<FAST>): P = exp2(s - m0) is stored in the 16-bit type; fp16 tops out at 65504, so
@@ -72,6 +30,7 @@ typedef _Float16 h16;
 #define H16_MFMA_32x32x16 __builtin_amdgcn_mfma_f32_32x32x16_f16
 #else
 typedef __bf16 h16;
+#define DSIM_H16_NS bf16
 #define DSIM_H16 DSIM_BF16
 #define DSIM_H16_ONE_BITS 0x3F80u
 #define DSIM_H16_LSUM_MAX 1e30f
@@ -164,7 +123,6 @@ struct GemmArgs {
     unsigned long long* stamps = nullptr;       // -DDSIM_STAMPS builds: per-phase cycle sums of gemm_kernel (7 words)
 #endif
 };
-int launch_gemm(const GemmArgs& a, int dtype, hipStream_t s);
 // The instantiation the calling thread's last GEMM launch ran, written by launch_ek / launch_skinny_t where they launch (one
 // definition, in pack.hip, shared by the bf16 and fp16 objects): what dsim_op_gemm reports, so that tests see the kernel that ran.
 struct GemmLaunchRec {
@@ -194,27 +152,6 @@ extern int g_ff_stagger;        // its wave de-phasing, in s_nop 7 units per wav
 #else
 constexpr int g_gemm_skinny = 1, g_gemm_persistent = 1, g_force_bm = 0;
 #endif
-int gemm_fill_extents(GemmArgs& g, size_t es);                       // operand byte extents for the buffer descriptors
-bool gemm_skinny_applies(const GemmArgs& a);                         // small-batch kernel (gemm_skinny.hip): same arithmetic, deep ring
-int launch_gemm_skinny(const GemmArgs& g /*extents filled*/, hipStream_t s);
-void gemm_skinny_tile(const GemmArgs& a, int* bm, int* bn);          // its tile for this problem
-int gemm_band_width(int tilesM, int tilesN, size_t w_tile_bytes);   // tile-order band width (L2 reuse of the weight tiles)
-void gemm_tile_choice(const GemmArgs& a, int* bm, int* bn);   // the tile the problem's shape asks for
-void gemm_launch_tile(const GemmArgs& a, int dtype, int* bm, int* bn);   // ... and the instantiation launch_gemm picks for it (dtype: DSIM_F32 or a 16-bit one)
-
-// Can launch_gemm take GemmArgs.gn_part for this problem?  (16-bit 3x3 conv on a power-of-two output map whose tile is the 256-row
-// one with 128 or 256 columns, N a multiple of it, whole images per 256 rows.)  The executors ask with the geometry of ONE image:
-// where a single image already fills the chip's tiles, every batch size runs the same tiles and the statistics are batch-invariant.
-inline bool gemm_gn_stats_tile(const GemmArgs& a, int dtype) {
-    if (dtype == DSIM_F32 || a.mode != GEMM_CONV3 || a.epi == EPI_GEGLU || a.bias2 || a.Wout <= 0) return false;
-    const int hw = a.Hout * a.Wout;
-    if ((a.Wout & (a.Wout - 1)) || (hw & (hw - 1)) || hw % 256) return false;
-    if (!a.force_big && gemm_skinny_applies(a)) return false;
-    int bm, bn;
-    gemm_launch_tile(a, dtype, &bm, &bn);
-    return ((bm == 256 && (bn == 128 || bn == 256)) || (bm == 512 && bn == 128)) && a.N % bn == 0 && hw % bm == 0;
-}
-
 // weight repack kernels -- pack.hip  (src f32/h16/f16 diffusers layout -> packed compute dtype)
 int pack_linear(const void* src, int src_dtype, void* dst, int dst_dtype, int N, int K,
                 int geglu_interleave, hipStream_t s);                       // [N][K] -> [N][K]; geglu_interleave: 0 or the block rows (16 / 32)
@@ -262,9 +199,6 @@ struct RowLinArgs {
     float eps = 1e-5f;
     int dtype = DSIM_BF16;                      // DSIM_BF16 or DSIM_F16
 };
-size_t rowlin_stream_bytes(int C, int N);       // 0: shape not covered
-int pack_rowlin_stream(const void* w_packed /*[N][C] h16*/, void* stream, int C, int N, hipStream_t s);
-int launch_rowlin(const RowLinArgs& a, hipStream_t s);
 
 // uint8 HWC pixels -> process_image's normalised NCHW f32 (half: rounded through fp16); VAE posterior sample -- pack.hip
 int image_preprocess(const unsigned char* hwc, float* out, int n, int H, int W, int half, hipStream_t s);
@@ -324,11 +258,6 @@ inline const char* attn_kind_suffix(int kind) {
         default: return "";
     }
 }
-int launch_attention(const AttnArgs& a, int dtype, hipStream_t s);
-const char* attention_kernel_kind(const AttnArgs& a, int dtype);      // "_p160" / "_short" / "_long" / "_q2" / "_q2fast" / "_fast" / "": the kernel it picks
-// the dsim_attn_kind launch_attention would start for these arguments (host only, launches nothing); DSIM_ERR_INVALID where it
-// would refuse them
-int attention_plan(const AttnArgs& a, int dtype);
 // The attention kernel the calling thread launched last, written where launch_attn_d / launch_sdpa160 / launch_attention_fp8 launch it
 // (one definition, in pack.hip, shared by the bf16 and fp16 objects): what dsim_op_attention_ex reports, so that tests see the kernel
 // that ran rather than the one the dispatch rule names.
@@ -337,36 +266,6 @@ struct AttnLaunchRec {
 };
 extern thread_local AttnLaunchRec g_attn_last_launch;
 int launch_attention_fp8(const AttnArgs& a, hipStream_t s);      // h16 in/out, e4m3 MFMAs (attention_fp8.hip)
-size_t pair_score_scratch_bytes(int n_pairs, int B, int H, int N, int D);
-int launch_pair_score(const void* q, const void* k, const void* v, const int32_t* idx_a,
-                      const int32_t* idx_b, int n_pairs, int B, int H, int N, int D, int dtype,
-                      int similarity, float* out, void* scratch, size_t scratch_bytes, hipStream_t s,
-                      int32_t* status = nullptr);
-// the score tail at SD1.5's default tap (256 tokens, head dim 160, 16-bit types): persistent workgroups, K / V streamed once per
-// 256 queries through an LDS-DMA ring -- attn160.hip
-bool pair_score160_applies(int N, int D, int dtype);
-size_t pair_score160_scratch_bytes(int n_pairs, int B, int H);
-int launch_pair_score160(const void* q, const void* k, const void* v, const int32_t* idx_a, const int32_t* idx_b, int n_pairs, int B,
-                         int H, int mse, float* out, void* scratch, size_t scratch_bytes, hipStream_t s, int32_t* status);
-// similarity maps: the score tail kept per query token (pair_map_kernel: pair_tail_kernel's body with a per-token epilogue, any
-// shape and dtype) -- attention.hip
-//   score [n_pairs]; local, contrib (each may be NULL) [n_pairs][2][N]; status (may be NULL) [n_pairs]
-size_t pair_score_maps_scratch_bytes(int n_pairs, int B, int H, int N);
-int launch_pair_score_maps(const void* q, const void* k, const void* v, const int32_t* idx_a, const int32_t* idx_b, int n_pairs, int B,
-                           int H, int N, int D, int dtype, int similarity, float* score, float* local, float* contrib, int32_t* status,
-                           void* scratch, size_t scratch_bytes, hipStream_t s);
-// the same core as a plain SDPA (256 queries = 256 keys, head dim 160, 16-bit types): the U-Net's 16 x 16-level self-attentions
-bool sdpa160_applies(const AttnArgs& a);
-int launch_sdpa160(const AttnArgs& a, hipStream_t s);
-// score matrix (every image of set A against every image of set B; q, k, v of a set: [n][B][N][H*D]): the self attentions once per
-// image into the workspace, then two cross attentions per cell -- attention.hip (any shape), attn160.hip (the default tap, 16-bit)
-size_t score_matrix_scratch_bytes(int n_a, int n_b, int B, int H, int N, int D, int dtype);
-int launch_score_matrix(const void* qa, const void* ka, const void* va, int n_a, const void* qb, const void* kb, const void* vb, int n_b,
-                        int B, int H, int N, int D, int dtype, int similarity, float* out, int32_t* status, void* scratch,
-                        size_t scratch_bytes, hipStream_t s);
-size_t score_matrix160_scratch_bytes(int n_a, int n_b, int B, int H);
-int launch_score_matrix160(const void* qa, const void* ka, const void* va, int n_a, const void* qb, const void* kb, const void* vb, int n_b,
-                           int B, int H, int mse, float* out, int32_t* status, void* scratch, size_t scratch_bytes, hipStream_t s);
 
 // row-resident fused feed-forward of the 320-channel transformer blocks (h16) -- rowres.hip
 //   out = x + W2 (h * gelu(g)) + b2,  [h ; g] = W1 LN(x) + b1
@@ -382,41 +281,37 @@ struct FFArgs {
     float eps = 1e-5f;
     int dtype = DSIM_BF16;                      // DSIM_BF16 or DSIM_F16
 };
-size_t ff_stream_bytes(int C);                  // 0: no fused kernel for this width
-// w1_packed: the GEGLU-interleaved [8C][C] h16 weight (pack_linear with geglu_interleave = 1); w2_packed: [C][4C] h16
-int pack_ff_stream(const void* w1_packed, const void* w2_packed, void* stream, int C, hipStream_t s);
-int launch_ff_fused(const FFArgs& a, hipStream_t s);
 
+// The entry points of the sources compiled once per 16-bit type, in this compilation's own namespace ...
+inline namespace DSIM_H16_NS {
+#include "h16_api.h"
+// Can launch_gemm take GemmArgs.gn_part for this problem?  (16-bit 3x3 conv on a power-of-two output map whose tile is the 256-row
+// one with 128 or 256 columns, N a multiple of it, whole images per 256 rows.)  The executors ask with the geometry of ONE image:
+// where a single image already fills the chip's tiles, every batch size runs the same tiles and the statistics are batch-invariant.
+inline bool gemm_gn_stats_tile(const GemmArgs& a, int dtype) {
+    if (dtype == DSIM_F32 || a.mode != GEMM_CONV3 || a.epi == EPI_GEGLU || a.bias2 || a.Wout <= 0) return false;
+    const int hw = a.Hout * a.Wout;
+    if ((a.Wout & (a.Wout - 1)) || (hw & (hw - 1)) || hw % 256) return false;
+    if (!a.force_big && gemm_skinny_applies(a)) return false;
+    int bm, bn;
+    gemm_launch_tile(a, dtype, &bm, &bn);
+    return ((bm == 256 && (bn == 128 || bn == 256)) || (bm == 512 && bn == 128)) && a.N % bn == 0 && hw % bm == 0;
+}
+}  // namespace DSIM_H16_NS
+// ... and, seen from the bf16 objects of the product build, their fp16 twins: DSIM_F16_TWIN(f(args)) is how a bf16 launcher forwards
+// compute dtype DSIM_F16.  tools/kbench (-DDSIM_DEVTOOLS) links no second compilation: there, as in the fp16 objects themselves,
+// which have nothing to forward, the call is DSIM_ERR_INVALID.
 #if !defined(DSIM_H16_IS_F16) && !defined(DSIM_DEVTOOLS)
-#define DSIM_HAS_F16_TWINS 1
-// the fp16 twins (same sources compiled with -DDSIM_H16_IS_F16); the plain entry points forward compute dtype DSIM_F16 to them
-int launch_gemm_f16(const GemmArgs& a, int dtype, hipStream_t s);
-int launch_rowlin_f16(const RowLinArgs& a, hipStream_t s);
-int launch_ff_fused_f16(const FFArgs& a, hipStream_t s);
-int launch_groupnorm_f16(const void* x0, int C0, const void* x1, int C1, const float* gamma, const float* beta, void* out, int B, int HW,
-                         int groups, float eps, int silu, int dtype, void* scratch, hipStream_t s);
-int launch_groupnorm_pre_f16(const void* x, int C, const float* gamma, const float* beta, void* out, int B, int HW, int groups, float eps,
-                             int silu, int dtype, void* scratch, const float* part32, int chunks, hipStream_t s);
-int launch_layernorm_f16(const void* x, const float* gamma, const float* beta, void* out, int M, int C, float eps, int dtype, hipStream_t s);
-int launch_layernorm_mod_f16(const void* x, const float* scale2, const float* shift2, void* out, int M, int C, int rows_per_batch, float eps,
-                             int dtype, hipStream_t s);
-int launch_softmax_rows_f16(const void* x, void* out, int rows, int cols, float scale, int dtype, hipStream_t s);
-int launch_attention_f16(const AttnArgs& a, int dtype, hipStream_t s);
-int attention_plan_f16(const AttnArgs& a, int dtype);
-int launch_pair_score_f16(const void* q, const void* k, const void* v, const int32_t* idx_a, const int32_t* idx_b, int n_pairs, int B, int H,
-                          int N, int D, int dtype, int similarity, float* out, void* scratch, size_t scratch_bytes, hipStream_t s,
-                          int32_t* status);
-size_t score_matrix_scratch_bytes_f16(int n_a, int n_b, int B, int H, int N, int D, int dtype);
-int launch_score_matrix_f16(const void* qa, const void* ka, const void* va, int n_a, const void* qb, const void* kb, const void* vb, int n_b,
-                            int B, int H, int N, int D, int dtype, int similarity, float* out, int32_t* status, void* scratch,
-                            size_t scratch_bytes, hipStream_t s);
-int launch_pair_score_maps_f16(const void* q, const void* k, const void* v, const int32_t* idx_a, const int32_t* idx_b, int n_pairs, int B,
-                               int H, int N, int D, int dtype, int similarity, float* score, float* local, float* contrib, int32_t* status,
-                               void* scratch, size_t scratch_bytes, hipStream_t s);
+namespace f16 {
+#include "h16_api.h"
+}
+#define DSIM_F16_TWIN(call) f16::call
+#else
+#define DSIM_F16_TWIN(call) DSIM_ERR_INVALID
 #endif
 
-// Per-device once-flags for hipFuncSetAttribute(MaxDynamicSharedMemorySize) and the CU count: the attribute is a
-// per-device property of the function, so a process that drives several devices must set it on each.
+// Per-device once-flags for hipFuncSetAttribute(MaxDynamicSharedMemorySize) and the CU count (one cache, in pack.hip): the
+// attribute is a per-device property of the function, so a process that drives several devices must set it on each.
 int cu_count();
 struct DeviceOnce {
     unsigned long long done = 0;       // bit d set: attribute applied on device d (d < 64)

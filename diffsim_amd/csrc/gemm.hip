@@ -34,6 +34,7 @@ int g_gemm_exp = 0;
 int g_gemm_skinny = 1;
 unsigned long long* g_gemm_stamps = nullptr;
 #endif
+inline namespace DSIM_H16_NS {
 // Tile choice.  Small problems: 128-row tiles, 4 waves, two workgroups per CU (160-wide when N
 // allows -- every SD channel count is a multiple of 160 -- else 128; 80-wide where 160 would leave one workgroup per CU).  h16
 // problems with enough 256-row tiles to fill the chip: 256 x 320 (or 256 x 256, or 256 x 192 for the DiT widths) tiles, 8 waves as
@@ -136,6 +137,7 @@ void gemm_launch_tile(const GemmArgs& a, int dtype, int* bm, int* bn) {
         *bn = slow ? 128 : (n80 ? 80 : ((n160 || *bn == 80) ? 160 : 128));
     }
 }
+}  // namespace DSIM_H16_NS
 
 namespace {
 
@@ -895,18 +897,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_kernel(const GemmArgs p,
 
 }  // namespace
 
-int cu_count() {
-    static int per_dev[64] = {0};      // CU count of each device this process has launched on
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    int n = __atomic_load_n(&per_dev[dev], __ATOMIC_RELAXED);
-    if (!n) {
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        __atomic_store_n(&per_dev[dev], n, __ATOMIC_RELAXED);
-    }
-    return n;
-}
-
+inline namespace DSIM_H16_NS {
 // Width (in tile columns) of the column bands the logical tile order walks (gemm_kernel setup()).  An XCD runs ~32 tiles at
 // a time; in row-major order at N = 10240 (40 tile columns) those are one activation panel x 32 different weight tiles,
 // 21 MB of weights against a 4 MiB L2: every tile re-fetched its whole weight tile over the fabric (7.1 GB per launch
@@ -943,6 +934,7 @@ int gemm_fill_extents(GemmArgs& g, size_t es) {
     g.a0_bytes = (unsigned)a0b; g.a1_bytes = (unsigned)a1b; g.w_bytes = (unsigned)wb; g.out_bytes = (unsigned)ob;
     return DSIM_OK;
 }
+}  // namespace DSIM_H16_NS
 
 namespace {
 
@@ -1091,15 +1083,15 @@ int launch_typed(const GemmArgs& a_in, hipStream_t s) {
 
 }  // namespace
 
+inline namespace DSIM_H16_NS {
 int launch_gemm(const GemmArgs& a, int dtype, hipStream_t s) {
     if (dtype == DSIM_H16) return launch_typed<h16>(a, s);
-#ifndef DSIM_H16_IS_F16            // the fp16 objects hold the fp16 kernels only; the plain names forward DSIM_F16 to them
+#ifndef DSIM_H16_IS_F16            // the fp16 objects hold the fp16 kernels only; the bf16 ones forward DSIM_F16 to them
     if (dtype == DSIM_F32) return launch_typed<float>(a, s);
-#ifdef DSIM_HAS_F16_TWINS
-    if (dtype == DSIM_F16) return launch_gemm_f16(a, dtype, s);
-#endif
+    if (dtype == DSIM_F16) return DSIM_F16_TWIN(launch_gemm(a, dtype, s));
 #endif
     return DSIM_ERR_INVALID;
 }
+}  // namespace DSIM_H16_NS
 
 }  // namespace dsim

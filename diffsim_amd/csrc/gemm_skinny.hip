@@ -232,6 +232,7 @@ int launch_skinny(const GemmArgs& g, hipStream_t s) {
 int g_skinny_tile = 0;          // kbench: 0 heuristic, else (bm << 8) | bn
 #endif
 
+inline namespace DSIM_H16_NS {
 // Tile of the small-batch kernel.  One workgroup runs per CU (the ring fills LDS) and streams (bm + bn) x 128 B per K tile through
 // its CU's L2 -> LDS path, so the tile with the smallest bm + bn that still makes ONE round (<= CUs workgroups) wins -- by less than
 // the byte count says once most CUs stream at the same time (the L2s' aggregate rate, ~8.7 TB/s, takes over).  Measured (tools/kbench
@@ -271,5 +272,6 @@ int launch_gemm_skinny(const GemmArgs& g, hipStream_t s) {
     if (g.mode == GEMM_CONV3) return g.epi == EPI_RESIDUAL ? launch_skinny<GEMM_CONV3, true>(g, s) : launch_skinny<GEMM_CONV3, false>(g, s);
     return g.epi == EPI_RESIDUAL ? launch_skinny<GEMM_LINEAR, true>(g, s) : launch_skinny<GEMM_LINEAR, false>(g, s);
 }
+}  // namespace DSIM_H16_NS
 
 }  // namespace dsim

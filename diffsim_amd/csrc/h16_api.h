@@ -1,0 +1,60 @@
+// The host entry points of the sources that are compiled once per 16-bit type (gemm / gemm_skinny / rowres / attention / attn160
+// .hip).  Declarations only and no include guard: common.h includes this file inside `inline namespace DSIM_H16_NS`, the including
+// object's own type, and the bf16 objects of the product build once more inside `namespace f16`, which declares the fp16 twins with
+// the same signatures and default arguments.  The argument structs and enums are plain dsim types (common.h, above the include).
+
+// implicit GEMM -- gemm.hip, gemm_skinny.hip
+int launch_gemm(const GemmArgs& a, int dtype, hipStream_t s);
+int gemm_fill_extents(GemmArgs& g, size_t es);                       // operand byte extents for the buffer descriptors
+bool gemm_skinny_applies(const GemmArgs& a);                         // small-batch kernel (gemm_skinny.hip): same arithmetic, deep ring
+int launch_gemm_skinny(const GemmArgs& g /*extents filled*/, hipStream_t s);
+void gemm_skinny_tile(const GemmArgs& a, int* bm, int* bn);          // its tile for this problem
+int gemm_band_width(int tilesM, int tilesN, size_t w_tile_bytes);   // tile-order band width (L2 reuse of the weight tiles)
+void gemm_tile_choice(const GemmArgs& a, int* bm, int* bn);   // the tile the problem's shape asks for
+void gemm_launch_tile(const GemmArgs& a, int dtype, int* bm, int* bn);   // ... and the instantiation launch_gemm picks for it (dtype: DSIM_F32 or a 16-bit one)
+
+// row-resident Linear and fused feed-forward -- rowres.hip
+size_t rowlin_stream_bytes(int C, int N);       // 0: shape not covered
+int pack_rowlin_stream(const void* w_packed /*[N][C] h16*/, void* stream, int C, int N, hipStream_t s);
+int launch_rowlin(const RowLinArgs& a, hipStream_t s);
+size_t ff_stream_bytes(int C);                  // 0: no fused kernel for this width
+// w1_packed: the GEGLU-interleaved [8C][C] h16 weight (pack_linear with geglu_interleave = 1); w2_packed: [C][4C] h16
+int pack_ff_stream(const void* w1_packed, const void* w2_packed, void* stream, int C, hipStream_t s);
+int launch_ff_fused(const FFArgs& a, hipStream_t s);
+
+// attention + fused score tail -- attention.hip
+int launch_attention(const AttnArgs& a, int dtype, hipStream_t s);
+const char* attention_kernel_kind(const AttnArgs& a, int dtype);      // "_p160" / "_short" / "_long" / "_q2" / "_q2fast" / "_fast" / "": the kernel it picks
+// the dsim_attn_kind launch_attention would start for these arguments (host only, launches nothing); DSIM_ERR_INVALID where it
+// would refuse them
+int attention_plan(const AttnArgs& a, int dtype);
+size_t pair_score_scratch_bytes(int n_pairs, int B, int H, int N, int D);
+int launch_pair_score(const void* q, const void* k, const void* v, const int32_t* idx_a,
+                      const int32_t* idx_b, int n_pairs, int B, int H, int N, int D, int dtype,
+                      int similarity, float* out, void* scratch, size_t scratch_bytes, hipStream_t s,
+                      int32_t* status = nullptr);
+// the score tail at SD1.5's default tap (256 tokens, head dim 160, 16-bit types): persistent workgroups, K / V streamed once per
+// 256 queries through an LDS-DMA ring -- attn160.hip
+bool pair_score160_applies(int N, int D, int dtype);
+size_t pair_score160_scratch_bytes(int n_pairs, int B, int H);
+int launch_pair_score160(const void* q, const void* k, const void* v, const int32_t* idx_a, const int32_t* idx_b, int n_pairs, int B,
+                         int H, int mse, float* out, void* scratch, size_t scratch_bytes, hipStream_t s, int32_t* status);
+// similarity maps: the score tail kept per query token (pair_map_kernel: pair_tail_kernel's body with a per-token epilogue, any
+// shape and dtype) -- attention.hip
+//   score [n_pairs]; local, contrib (each may be NULL) [n_pairs][2][N]; status (may be NULL) [n_pairs]
+size_t pair_score_maps_scratch_bytes(int n_pairs, int B, int H, int N);
+int launch_pair_score_maps(const void* q, const void* k, const void* v, const int32_t* idx_a, const int32_t* idx_b, int n_pairs, int B,
+                           int H, int N, int D, int dtype, int similarity, float* score, float* local, float* contrib, int32_t* status,
+                           void* scratch, size_t scratch_bytes, hipStream_t s);
+// the same core as a plain SDPA (256 queries = 256 keys, head dim 160, 16-bit types): the U-Net's 16 x 16-level self-attentions
+bool sdpa160_applies(const AttnArgs& a);
+int launch_sdpa160(const AttnArgs& a, hipStream_t s);
+// score matrix (every image of set A against every image of set B; q, k, v of a set: [n][B][N][H*D]): the self attentions once per
+// image into the workspace, then two cross attentions per cell -- attention.hip (any shape), attn160.hip (the default tap, 16-bit)
+size_t score_matrix_scratch_bytes(int n_a, int n_b, int B, int H, int N, int D, int dtype);
+int launch_score_matrix(const void* qa, const void* ka, const void* va, int n_a, const void* qb, const void* kb, const void* vb, int n_b,
+                        int B, int H, int N, int D, int dtype, int similarity, float* out, int32_t* status, void* scratch,
+                        size_t scratch_bytes, hipStream_t s);
+size_t score_matrix160_scratch_bytes(int n_a, int n_b, int B, int H);
+int launch_score_matrix160(const void* qa, const void* ka, const void* va, int n_a, const void* qb, const void* kb, const void* vb, int n_b,
+                           int B, int H, int mse, float* out, int32_t* status, void* scratch, size_t scratch_bytes, hipStream_t s);

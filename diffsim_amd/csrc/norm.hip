@@ -26,7 +26,8 @@ __device__ __forceinline__ float silu_fast(float y) {
 }
 
 template <typename T> struct Vec16;
-template <> struct Vec16<h16> { typedef h16x8 type; static constexpr int N = 8; };
+template <> struct Vec16<bf16_t> { typedef __attribute__((ext_vector_type(8))) bf16_t type; static constexpr int N = 8; };
+template <> struct Vec16<f16_t> { typedef __attribute__((ext_vector_type(8))) f16_t type; static constexpr int N = 8; };
 template <> struct Vec16<float> { typedef f32x4 type; static constexpr int N = 4; };
 
 __host__ __device__ inline int gn_chunks(int HW) {
@@ -824,7 +825,7 @@ int gn_typed(const void* x0, int C0, const void* x1, int C1, const float* gamma,
 int groupnorm_plan(int C0, int C1, int B, int HW, int groups, int dtype, int pre, dsim_gn_plan* p) {
     if (!p) return DSIM_ERR_INVALID;
     if (dtype == DSIM_F32) return pre ? DSIM_ERR_INVALID : gn_plan<float>(C0, C1, B, HW, groups, false, p);
-    if (dtype == DSIM_BF16 || dtype == DSIM_F16) return gn_plan<h16>(C0, C1, B, HW, groups, pre != 0, p);   // (either 16-bit type)
+    if (dtype == DSIM_BF16 || dtype == DSIM_F16) return gn_plan<bf16_t>(C0, C1, B, HW, groups, pre != 0, p);   // (either 16-bit type)
     return DSIM_ERR_INVALID;
 }
 
@@ -832,7 +833,7 @@ int groupnorm_plan(int C0, int C1, int B, int HW, int groups, int dtype, int pre
 int layernorm_plan(int M, int C, int dtype, int mod, dsim_ln_plan* p) {
     if (!p) return DSIM_ERR_INVALID;
     if (dtype == DSIM_F32) return ln_plan<float>(M, C, mod != 0, p);
-    if (dtype == DSIM_BF16 || dtype == DSIM_F16) return ln_plan<h16>(M, C, mod != 0, p);
+    if (dtype == DSIM_BF16 || dtype == DSIM_F16) return ln_plan<bf16_t>(M, C, mod != 0, p);      // (either 16-bit type)
     return DSIM_ERR_INVALID;
 }
 
@@ -850,51 +851,34 @@ size_t groupnorm_scratch_bytes(int B, int groups) { return (size_t)B * 64 * grou
 int launch_groupnorm_pre(const void* x, int C, const float* gamma, const float* beta, void* out, int B, int HW, int groups, float eps,
                          int silu, int dtype, void* scratch, const float* part32, int chunks, hipStream_t s) {
     if (!part32 || chunks < 1) return DSIM_ERR_INVALID;
-    if (dtype == DSIM_H16) return gn_typed<h16>(x, C, nullptr, 0, gamma, beta, out, B, HW, groups, eps, silu, scratch, s, part32, chunks);
-#if !defined(DSIM_H16_IS_F16) && defined(DSIM_HAS_F16_TWINS)
-    if (dtype == DSIM_F16) return launch_groupnorm_pre_f16(x, C, gamma, beta, out, B, HW, groups, eps, silu, dtype, scratch, part32, chunks, s);
-#endif
+    if (dtype == DSIM_BF16) return gn_typed<bf16_t>(x, C, nullptr, 0, gamma, beta, out, B, HW, groups, eps, silu, scratch, s, part32, chunks);
+    if (dtype == DSIM_F16) return gn_typed<f16_t>(x, C, nullptr, 0, gamma, beta, out, B, HW, groups, eps, silu, scratch, s, part32, chunks);
     return DSIM_ERR_INVALID;
 }
 
 int launch_groupnorm(const void* x0, int C0, const void* x1, int C1, const float* gamma, const float* beta,
                      void* out, int B, int HW, int groups, float eps, int silu, int dtype, void* scratch,
                      hipStream_t s) {
-    if (dtype == DSIM_H16)
-        return gn_typed<h16>(x0, C0, x1, C1, gamma, beta, out, B, HW, groups, eps, silu, scratch, s);
-#ifndef DSIM_H16_IS_F16
-    if (dtype == DSIM_F32)
-        return gn_typed<float>(x0, C0, x1, C1, gamma, beta, out, B, HW, groups, eps, silu, scratch, s);
-#ifdef DSIM_HAS_F16_TWINS
-    if (dtype == DSIM_F16)
-        return launch_groupnorm_f16(x0, C0, x1, C1, gamma, beta, out, B, HW, groups, eps, silu, dtype, scratch, s);
-#endif
-#endif
+    if (dtype == DSIM_BF16) return gn_typed<bf16_t>(x0, C0, x1, C1, gamma, beta, out, B, HW, groups, eps, silu, scratch, s);
+    if (dtype == DSIM_F16) return gn_typed<f16_t>(x0, C0, x1, C1, gamma, beta, out, B, HW, groups, eps, silu, scratch, s);
+    if (dtype == DSIM_F32) return gn_typed<float>(x0, C0, x1, C1, gamma, beta, out, B, HW, groups, eps, silu, scratch, s);
     return DSIM_ERR_INVALID;
 }
 
 int launch_layernorm(const void* x, const float* gamma, const float* beta, void* out, int M, int C, float eps,
                      int dtype, hipStream_t s) {
-    if (dtype == DSIM_H16) return ln_typed<h16, false>(x, gamma, beta, out, M, C, eps, 1, s);
-#ifndef DSIM_H16_IS_F16
+    if (dtype == DSIM_BF16) return ln_typed<bf16_t, false>(x, gamma, beta, out, M, C, eps, 1, s);
+    if (dtype == DSIM_F16) return ln_typed<f16_t, false>(x, gamma, beta, out, M, C, eps, 1, s);
     if (dtype == DSIM_F32) return ln_typed<float, false>(x, gamma, beta, out, M, C, eps, 1, s);
-#ifdef DSIM_HAS_F16_TWINS
-    if (dtype == DSIM_F16) return launch_layernorm_f16(x, gamma, beta, out, M, C, eps, dtype, s);
-#endif
-#endif
     return DSIM_ERR_INVALID;
 }
 
 int launch_layernorm_mod(const void* x, const float* scale2, const float* shift2, void* out, int M, int C,
                          int rows_per_batch, float eps, int dtype, hipStream_t s) {
     if (rows_per_batch < 1) return DSIM_ERR_INVALID;
-    if (dtype == DSIM_H16) return ln_typed<h16, true>(x, scale2, shift2, out, M, C, eps, rows_per_batch, s);
-#ifndef DSIM_H16_IS_F16
+    if (dtype == DSIM_BF16) return ln_typed<bf16_t, true>(x, scale2, shift2, out, M, C, eps, rows_per_batch, s);
+    if (dtype == DSIM_F16) return ln_typed<f16_t, true>(x, scale2, shift2, out, M, C, eps, rows_per_batch, s);
     if (dtype == DSIM_F32) return ln_typed<float, true>(x, scale2, shift2, out, M, C, eps, rows_per_batch, s);
-#ifdef DSIM_HAS_F16_TWINS
-    if (dtype == DSIM_F16) return launch_layernorm_mod_f16(x, scale2, shift2, out, M, C, rows_per_batch, eps, dtype, s);
-#endif
-#endif
     return DSIM_ERR_INVALID;
 }
 
@@ -902,16 +886,12 @@ int launch_softmax_rows(const void* x, void* out, int rows, int cols, float scal
     const int vec = dtype == DSIM_F32 ? 4 : 8;
     if (cols % vec || rows < 1) return DSIM_ERR_INVALID;
     const float sl2 = scale * 1.4426950408889634f;
-    if (dtype == DSIM_H16)
-        hipLaunchKernelGGL(softmax_rows_kernel<h16>, dim3(rows), dim3(256), 0, s, (const h16*)x, (h16*)out, cols, sl2);
-#ifndef DSIM_H16_IS_F16
+    if (dtype == DSIM_BF16)
+        hipLaunchKernelGGL(softmax_rows_kernel<bf16_t>, dim3(rows), dim3(256), 0, s, (const bf16_t*)x, (bf16_t*)out, cols, sl2);
+    else if (dtype == DSIM_F16)
+        hipLaunchKernelGGL(softmax_rows_kernel<f16_t>, dim3(rows), dim3(256), 0, s, (const f16_t*)x, (f16_t*)out, cols, sl2);
     else if (dtype == DSIM_F32)
         hipLaunchKernelGGL(softmax_rows_kernel<float>, dim3(rows), dim3(256), 0, s, (const float*)x, (float*)out, cols, sl2);
-#ifdef DSIM_HAS_F16_TWINS
-    else if (dtype == DSIM_F16)
-        return launch_softmax_rows_f16(x, out, rows, cols, scale, dtype, s);
-#endif
-#endif
     else
         return DSIM_ERR_INVALID;
     DSIM_HIP_CHECK(hipGetLastError());

@@ -8,6 +8,18 @@ namespace dsim {
 thread_local GemmLaunchRec g_gemm_last_launch;      // (common.h: written by gemm.hip / gemm_skinny.hip at each launch)
 thread_local AttnLaunchRec g_attn_last_launch;      // (common.h: written by attention.hip / attn160.hip / attention_fp8.hip at each launch)
 
+int cu_count() {      // (common.h; here, so that the bf16 and fp16 objects share one cache)
+    static int per_dev[64] = {0};      // CU count of each device this process has launched on
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+    int n = __atomic_load_n(&per_dev[dev], __ATOMIC_RELAXED);
+    if (!n) {
+        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+        __atomic_store_n(&per_dev[dev], n, __ATOMIC_RELAXED);
+    }
+    return n;
+}
+
 namespace {
 
 __device__ __forceinline__ float ld_any(const void* p, int dt, size_t i) {

@@ -551,6 +551,7 @@ int g_ff_stagger = -1;     // -1 = the product default
 int g_rl_wpc = 3;          // rowlin_kernel's persistent workgroups per CU
 #endif
 
+inline namespace DSIM_H16_NS {
 size_t ff_stream_bytes(int C) { return C == RC ? (size_t)RITER * RCHB : 0; }
 
 int pack_ff_stream(const void* w1_packed, const void* w2_packed, void* stream, int C, hipStream_t s) {
@@ -563,10 +564,7 @@ int pack_ff_stream(const void* w1_packed, const void* w2_packed, void* stream, i
 }
 
 int launch_ff_fused(const FFArgs& a, hipStream_t s) {
-#ifdef DSIM_HAS_F16_TWINS
-    if (a.dtype == DSIM_F16) return launch_ff_fused_f16(a, s);
-#endif
-    if (a.dtype != DSIM_H16) return DSIM_ERR_INVALID;
+    if (a.dtype != DSIM_H16) return a.dtype == DSIM_F16 ? DSIM_F16_TWIN(launch_ff_fused(a, s)) : DSIM_ERR_INVALID;
     if (a.C != RC || a.M < 1 || (size_t)a.M * RC * 2 >= 0x7fffffffull) return DSIM_ERR_INVALID;
     FFParams p;
     p.x = (const h16*)a.x; p.out = (h16*)a.out; p.ln_g = a.ln_g; p.ln_b = a.ln_b; p.stream = (const char*)a.stream;
@@ -609,10 +607,7 @@ int pack_rowlin_stream(const void* w_packed, void* stream, int C, int N, hipStre
 }
 
 int launch_rowlin(const RowLinArgs& a, hipStream_t s) {
-#ifdef DSIM_HAS_F16_TWINS
-    if (a.dtype == DSIM_F16) return launch_rowlin_f16(a, s);
-#endif
-    if (a.dtype != DSIM_H16) return DSIM_ERR_INVALID;
+    if (a.dtype != DSIM_H16) return a.dtype == DSIM_F16 ? DSIM_F16_TWIN(launch_rowlin(a, s)) : DSIM_ERR_INVALID;
     if (!rowlin_stream_bytes(a.C, a.N) || a.M < 1 || (size_t)a.M * a.N * 2 >= 0x7fffffffull || !a.ln_g != !a.ln_b) return DSIM_ERR_INVALID;
     RLParams p;
     p.x = (const h16*)a.x; p.out = (h16*)a.out; p.ln_g = a.ln_g; p.ln_b = a.ln_b; p.stream = (const char*)a.stream;
@@ -641,5 +636,6 @@ int launch_rowlin(const RowLinArgs& a, hipStream_t s) {
     DSIM_HIP_CHECK(hipGetLastError());
     return DSIM_OK;
 }
+}  // namespace DSIM_H16_NS
 
 }  // namespace dsim

@@ -317,7 +317,7 @@ def rowres_inputs(M, dtype, fam, device):
 def test_rowres_layernorm_isolated(M, dt, fam):
     """rowres.hip's rowlin_kernel LayerNorm stage, alone: with w the 320 x 320 identity, out = LN(x) W^T is the 16-bit LayerNorm
     itself -- every product is with 1.0 or 0.0, the f32 sum of one value and zeros is exact, and storing a 16-bit value in its own
-    type is exact -- so the output is held to the LayerNorm bound directly.  bf16, and the fp16 twin (launch_rowlin_f16)."""
+    type is exact -- so the output is held to the LayerNorm bound directly.  bf16, and the fp16 twin (f16::launch_rowlin)."""
     eng = _eng()
     dtype = DT[dt]
     t = rowres_inputs(M, dtype, fam, "cuda")
