@@ -88,20 +88,12 @@ struct DTap {
     void *q = nullptr, *k = nullptr, *v = nullptr;
 };
 
-struct DWalk {
-    dsim_dit* h;
-    Arena* ar;
-    hipStream_t s;
+struct DWalk : WalkBase<dsim_dit> {
     int n;                  // images
-    bool run;
     std::vector<DTap> taps; // captured on the way; the walk ends at the deepest
     bool tapped = false;
+    DWalk(dsim_dit* h, Arena* ar, hipStream_t s, int n, bool run) : WalkBase(h, ar, s, run), n(n) {}
 
-    size_t es() const { return dtype_size(h->dt); }
-    void* alloc_act(size_t elems) { return ar->alloc(elems * es()); }
-#define DGET(var, key)                                   \
-    const Packed* var = h->find(key);                    \
-    if (!var) return DSIM_ERR_MISSING_WEIGHT;
     const float* modv(int blk, int chunk) const { return h->mod + (((size_t)blk * 6 + chunk) * 2) * h->cfg.hidden_size; }
 
     int linear(const void* a, int K, const void* w, const float* bias, void* out, int M, int N, int act, const float* gate,
@@ -110,42 +102,17 @@ struct DWalk {
         g.A0 = a; g.C0 = K; g.mode = GEMM_LINEAR; g.M = M; g.N = N; g.K = K; g.W = w; g.bias = bias; g.act = act;
         if (gate) { g.gate = gate; g.gate2 = gate + h->cfg.hidden_size; g.rows_per_batch = T; }
         g.epi = residual ? EPI_RESIDUAL : EPI_NONE; g.residual = residual; g.out = out; g.ldo = N;
-        g.zero_page = h->zero_page;
-        if (!run) return DSIM_OK;
-        if (h->profiling) {
-            const bool slow = act != 0 || gate != nullptr;      // the tanh-GELU / adaLN-gate epilogue template (gemm.hip EK_SLOW)
-            if (slow) {
-                int bm, bn;
-                gemm_launch_tile(g, h->dt, &bm, &bn);
-                pbegin(std::string("gemm_") + dtn() + "_" + std::to_string(bm) + "x" + std::to_string(bn) + "_linear" +
-                           ((act && !gate && !residual) ? "_act" : "_dit") + "|M" + std::to_string(M) + " N" + std::to_string(N) + " K" + std::to_string(K),
-                       2.0 * M * (double)N * K, (double)es() * ((double)M * K + (double)N * K + (double)M * N * (residual ? 2 : 1)));
-            } else {
-                // plain / residual projections: gemm_family() names the kernel, the small-batch one included (the qkv projection of
-                // one image, 512 x 3456 x 1152, runs on it)
-                double fl, by;
-                const std::string nm = gemm_family(g, h->dt, &fl, &by);
-                pbegin(nm, fl, by);
-            }
+        if (run && h->profiling && (act != 0 || gate != nullptr)) {
+            // the tanh-GELU / adaLN-gate epilogue template (gemm.hip EK_SLOW): families of its own.  Plain / residual projections take
+            // gemm_family()'s name, the small-batch kernel included (the qkv projection of one image, 512 x 3456 x 1152, runs on it)
+            int bm, bn;
+            gemm_launch_tile(g, h->dt, &bm, &bn);
+            const std::string nm = std::string("gemm_") + dtn() + "_" + std::to_string(bm) + "x" + std::to_string(bn) + "_linear" +
+                                   ((act && !gate && !residual) ? "_act" : "_dit") + "|M" + std::to_string(M) + " N" + std::to_string(N) +
+                                   " K" + std::to_string(K);
+            return gemm(g, &nm, 2.0 * M * (double)N * K, (double)es() * ((double)M * K + (double)N * K + (double)M * N * (residual ? 2 : 1)));
         }
-        const int st = launch_gemm(g, h->dt, s);
-        pend();
-        return st;
-    }
-    // per-launch HIP-event brackets of a profiled forward (same record format as the U-Net executor's)
-    const char* dtn() const { return h->dt == DSIM_F32 ? "f32" : (h->dt == DSIM_F16 ? "f16" : "bf16"); }
-    void pbegin(const std::string& name, double flops, double bytes) {
-        if (!run || !h->profiling) return;
-        ProfRec r;
-        r.name = name; r.flops = flops; r.bytes = bytes;
-        (void)hipEventCreate(&r.e0);
-        (void)hipEventCreate(&r.e1);
-        (void)hipEventRecord(r.e0, s);
-        h->prof.push_back(r);
-    }
-    void pend() {
-        if (!run || !h->profiling) return;
-        (void)hipEventRecord(h->prof.back().e1, s);
+        return gemm(g);
     }
     int lnmod(const void* x, const float* scale2, const float* shift2, void* out, int M, int D, int T) {
         if (!run) return DSIM_OK;
@@ -159,7 +126,7 @@ struct DWalk {
         const dsim_dit_cfg& c = h->cfg;
         const int D = c.hidden_size, p = c.patch_size, S = c.input_size, g = S / p, T = g * g, H = c.num_heads;
         const int M = n * 2 * T, F = c.mlp_ratio * D;
-        DGET(pw, "x_embedder.proj.weight"); DGET(pb, "x_embedder.proj.bias"); DGET(pos, "pos_embed");
+        WGET(pw, "x_embedder.proj.weight"); WGET(pb, "x_embedder.proj.bias"); WGET(pos, "pos_embed");
         void* x = alloc_act((size_t)M * D);
         if (run) {
             const int K = c.in_channels * p * p;
@@ -182,7 +149,7 @@ struct DWalk {
         for (const DTap& t : taps) last = t.layer > last ? t.layer : last;
         for (int blk = 0; blk <= last; ++blk) {
             const std::string b = "blocks." + std::to_string(blk) + ".";
-            DGET(qw, b + "attn.qkv.weight"); DGET(qb, b + "attn.qkv.bias");
+            WGET(qw, b + "attn.qkv.weight"); WGET(qb, b + "attn.qkv.bias");
             CK(lnmod(x, modv(blk, 1), modv(blk, 0), nb, M, D, T));
             for (const DTap& t : taps) {
                 if (t.layer != blk) continue;
@@ -197,19 +164,16 @@ struct DWalk {
                 tapped = true;
                 return DSIM_OK;
             }
-            DGET(ow, b + "attn.proj.weight"); DGET(ob, b + "attn.proj.bias");
-            DGET(f1w, b + "mlp.fc1.weight"); DGET(f1b, b + "mlp.fc1.bias");
-            DGET(f2w, b + "mlp.fc2.weight"); DGET(f2b, b + "mlp.fc2.bias");
+            WGET(ow, b + "attn.proj.weight"); WGET(ob, b + "attn.proj.bias");
+            WGET(f1w, b + "mlp.fc1.weight"); WGET(f1b, b + "mlp.fc1.bias");
+            WGET(f2w, b + "mlp.fc2.weight"); WGET(f2b, b + "mlp.fc2.bias");
             CK(linear(nb, D, qw->p, (const float*)qb->p, big, M, 3 * D, 0, nullptr, nullptr, T));
             if (run) {
                 AttnArgs a;
                 a.q = big; a.ldq = 3 * D;
                 a.k = (char*)big + (size_t)D * es(); a.v = (char*)big + (size_t)2 * D * es(); a.ldk = 3 * D;
                 a.out = ab; a.ldo = D; a.B = n * 2; a.Bkv = n * 2; a.H = H; a.Nq = T; a.Nk = T; a.D = D / H;
-                pbegin((h->attn_mode == 1 ? std::string("attention_fp8_d") + std::to_string(a.D)
-                                           : std::string("attention_") + dtn() + "_d" + std::to_string(a.D) + attention_kernel_kind(a, h->dt)) + "|B" +
-                           std::to_string(a.B) + " H" + std::to_string(H) + " Nq" + std::to_string(T) + " Nk" + std::to_string(T),
-                       4.0 * a.B * H * (double)T * T * a.D, (double)es() * a.B * H * a.D * 4.0 * T);
+                pbegin_attn(a, h->attn_mode == 1);
                 const int st = h->attn_mode == 1 ? launch_attention_fp8(a, s) : launch_attention(a, h->dt, s);
                 pend();
                 CK(st);
@@ -229,31 +193,16 @@ extern "C" {
 
 int dsim_dit_create(const dsim_dit_cfg* cfg, dsim_dit** out) {
     if (!cfg || !out) return DSIM_ERR_INVALID;
-    if (cfg->compute_dtype != DSIM_F32 && cfg->compute_dtype != DSIM_BF16 && cfg->compute_dtype != DSIM_F16) return DSIM_ERR_INVALID;
     if (cfg->tap_layer < 0 || cfg->tap_layer >= cfg->depth || cfg->hidden_size % cfg->num_heads ||
         cfg->input_size % cfg->patch_size)
         return DSIM_ERR_INVALID;
-    if (dsim_device_count() < 1) return DSIM_ERR_NO_DEVICE;
-    dsim_dit* h = new dsim_dit();
-    h->cfg = *cfg;
-    h->dt = cfg->compute_dtype;
-    if (h->dalloc(256, &h->zero_page) != DSIM_OK || hipMemset(h->zero_page, 0, 256) != hipSuccess) {
-        dsim_dit_destroy(h);
-        return DSIM_ERR_HIP;
-    }
-    *out = h;
-    return DSIM_OK;
+    return handle_create(cfg, out);
 }
 
-void dsim_dit_destroy(dsim_dit* h) {
-    if (!h) return;
-    h->free_all();
-    delete h;
-}
+void dsim_dit_destroy(dsim_dit* h) { delete h; }
 
 int dsim_dit_load_weight(dsim_dit* h, const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim) {
-    if (!h) return DSIM_ERR_INVALID;
-    return h->add_raw(key, dev_ptr, dtype, shape, ndim);
+    return handle_load(h, key, dev_ptr, dtype, shape, ndim);
 }
 
 int dsim_dit_finalize(dsim_dit* h, void* stream) {
@@ -342,26 +291,10 @@ int dsim_dit_set_attention(dsim_dit* h, int mode) {
     return DSIM_OK;
 }
 
-int dsim_dit_profile(dsim_dit* h, int enable) {
-    if (!h) return DSIM_ERR_INVALID;
-    h->clear_profile();
-    h->profiling = enable != 0;
-    return DSIM_OK;
-}
-
-int dsim_dit_profile_count(const dsim_dit* h) { return h ? (int)h->prof.size() : 0; }
-
+int dsim_dit_profile(dsim_dit* h, int enable) { return prof_enable(h, enable); }
+int dsim_dit_profile_count(const dsim_dit* h) { return prof_count(h); }
 int dsim_dit_profile_get(dsim_dit* h, int i, char* name, int name_cap, double* flops, double* bytes, double* ms) {
-    if (!h || i < 0 || i >= (int)h->prof.size() || !name || name_cap < 2 || !flops || !bytes || !ms) return DSIM_ERR_INVALID;
-    ProfRec& r = h->prof[i];
-    if (r.e0 && r.e1) {
-        DSIM_HIP_CHECK(hipEventSynchronize(r.e1));
-        DSIM_HIP_CHECK(hipEventElapsedTime(&r.ms, r.e0, r.e1));
-    }
-    strncpy(name, r.name.c_str(), (size_t)name_cap - 1);
-    name[name_cap - 1] = 0;
-    *flops = r.flops; *bytes = r.bytes; *ms = (double)r.ms;
-    return DSIM_OK;
+    return prof_get(h, i, name, name_cap, flops, bytes, ms);
 }
 
 // dry walk to the deepest of `taps`: peak arena bytes
@@ -390,22 +323,17 @@ static int dit_check_taps(const dsim_dit* h, int n_taps, const int* layers, std:
 // one walk to the deepest of `taps` (their outputs set), every check before the first launch
 static int dit_run(dsim_dit* h, const float* latents, const float* noise, float sqrt_abar, float sqrt_1m_abar, int n_images,
                    const std::vector<DTap>& taps, void* workspace, size_t workspace_bytes, void* stream) {
-    Arena ar;
-    ar.dry = false;
-    const uintptr_t b0 = ((uintptr_t)workspace + 255) & ~(uintptr_t)255;
-    const size_t lost = b0 - (uintptr_t)workspace;
-    if (workspace_bytes < lost) return DSIM_ERR_WORKSPACE;
-    ar.base = (char*)b0;
-    ar.cap = workspace_bytes - lost;
-    {
-        size_t peak;
-        CK(dit_plan(h, n_images, taps, &peak));
-        if (peak > ar.cap) return DSIM_ERR_WORKSPACE;
-    }
-    DWalk w{h, &ar, (hipStream_t)stream, n_images, true};
-    w.taps = taps;
-    CK(w.go(latents, noise, sqrt_abar, sqrt_1m_abar));
-    return w.tapped && !ar.overflow ? DSIM_OK : DSIM_ERR_WORKSPACE;
+    bool tapped = false;
+    CK(run_in_workspace(
+        workspace, workspace_bytes, [&](size_t* peak) { return dit_plan(h, n_images, taps, peak); },
+        [&](Arena& ar) {
+            DWalk w{h, &ar, (hipStream_t)stream, n_images, true};
+            w.taps = taps;
+            const int st = w.go(latents, noise, sqrt_abar, sqrt_1m_abar);
+            tapped = w.tapped;
+            return st;
+        }));
+    return tapped ? DSIM_OK : DSIM_ERR_WORKSPACE;      // (run_taps in unet.hip returns DSIM_ERR_INVALID for a walk that reached no tap)
 }
 
 size_t dsim_dit_workspace_bytes(const dsim_dit* hc, int n_images) {

@@ -1,5 +1,6 @@
-// Shared host-side plumbing of the engine handles (U-Net, VAE): borrowed raw parameters, packed
-// device copies, the caller-provided workspace arena and the per-launch profiling record.
+// Shared host-side plumbing of the executors (U-Net, VAE, DiT): borrowed raw parameters, packed device copies, the
+// caller-provided workspace arena, the per-launch profiling record, the handle life cycle behind each dsim_<executor>_create /
+// destroy / load_weight / profile* group (handle_create ... prof_get) and the base of the three graph walks (WalkBase).
 #pragma once
 #include <cstring>
 #include <map>
@@ -76,9 +77,10 @@ struct WeightStore {
         if (it == pk.end()) { err_key = k; return nullptr; }
         return &it->second;
     }
-    void free_all() {
+    // (a handle destroyed with profile records pending releases their events too)
+    ~WeightStore() {
+        clear_profile();
         for (void* p : owned) (void)hipFree(p);
-        owned.clear();
     }
     int add_raw(const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim) {
         if (!key || !dev_ptr || !shape || ndim < 1 || ndim > 4) return DSIM_ERR_INVALID;
@@ -120,7 +122,7 @@ static inline std::string gemm_family(const GemmArgs& g, int dt, double* flops, 
            "|M" + std::to_string(g.M) + " N" + std::to_string(g.N) + " K" + std::to_string(g.K);
 }
 
-// HIP-event bracket of one launch of a profiled forward (the executors' pbegin / pend)
+// HIP-event bracket of one launch of a profiled forward (WalkBase::pbegin / pend)
 static inline void prof_begin(WeightStore* h, hipStream_t s, const std::string& name, double flops, double bytes) {
     ProfRec r;
     r.name = name; r.flops = flops; r.bytes = bytes;
@@ -142,6 +144,124 @@ static inline int prof_get(WeightStore* h, int i, char* name, int name_cap, doub
     *flops = r.flops; *bytes = r.bytes; *ms = (double)r.ms;
     return DSIM_OK;
 }
+
+// ---- handle life cycle: what dsim_unet_* / dsim_vae_* / dsim_dit_* forward to ------------------------------------------------
+// create, after the executor's own validation of cfg: H = the handle (a WeightStore with a `cfg` member)
+template <class H, class Cfg>
+static inline int handle_create(const Cfg* cfg, H** out) {
+    if (cfg->compute_dtype != DSIM_F32 && cfg->compute_dtype != DSIM_BF16 && cfg->compute_dtype != DSIM_F16) return DSIM_ERR_INVALID;
+    if (dsim_device_count() < 1) return DSIM_ERR_NO_DEVICE;
+    H* h = new H();
+    h->cfg = *cfg;
+    h->dt = cfg->compute_dtype;
+    if (h->dalloc(256, &h->zero_page) != DSIM_OK || hipMemset(h->zero_page, 0, 256) != hipSuccess) {
+        delete h;
+        return DSIM_ERR_HIP;
+    }
+    *out = h;
+    return DSIM_OK;
+}
+static inline int handle_load(WeightStore* h, const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim) {
+    return h ? h->add_raw(key, dev_ptr, dtype, shape, ndim) : DSIM_ERR_INVALID;
+}
+static inline int prof_enable(WeightStore* h, int enable) {
+    if (!h) return DSIM_ERR_INVALID;
+    h->clear_profile();
+    h->profiling = enable != 0;
+    return DSIM_OK;
+}
+static inline int prof_count(const WeightStore* h) { return h ? (int)h->prof.size() : 0; }
+
+// ---- one call on a caller's workspace ------------------------------------------------------------------------------------------
+// a caller's workspace starts at its first 256-byte boundary: moves `ws` there and takes the bytes before it off `bytes`; false when
+// the buffer does not reach it
+static inline bool align_workspace(void*& ws, size_t& bytes) {
+    const uintptr_t b0 = ((uintptr_t)ws + 255) & ~(uintptr_t)255;
+    const size_t lost = b0 - (uintptr_t)ws;
+    if (bytes < lost) return false;
+    ws = (void*)b0;
+    bytes -= lost;
+    return true;
+}
+
+// plan(&peak): the dry walk; walk(arena): the same walk launching.  Refuses up front, before the first launch, instead of failing
+// mid-graph; DSIM_OK = walked without leaving the arena.
+template <class Plan, class Run>
+static inline int run_in_workspace(void* ws, size_t bytes, Plan plan, Run walk) {
+    if (!align_workspace(ws, bytes)) return DSIM_ERR_WORKSPACE;
+    size_t peak = 0;
+    CK(plan(&peak));
+    if (peak > bytes) return DSIM_ERR_WORKSPACE;
+    Arena ar;
+    ar.dry = false;
+    ar.base = (char*)ws;
+    ar.cap = bytes;
+    CK(walk(ar));
+    return ar.overflow ? DSIM_ERR_WORKSPACE : DSIM_OK;
+}
+
+// ---- base of the executors' walks (Walk / VWalk / DWalk): one struct runs dry to plan the workspace and for real to launch ------
+#define WGET(var, key)                                   \
+    const Packed* var = h->find(key);                    \
+    if (!var) return DSIM_ERR_MISSING_WEIGHT;
+
+namespace {      // internal linkage, as the rest of this header and the walks that derive from it
+
+template <class H>
+struct WalkBase {
+    H* h;
+    Arena* ar;
+    hipStream_t s;
+    bool run;               // false: plan only
+    size_t max_tensor = 0;  // largest single activation (bytes): the kernels address tensors with 32-bit offsets
+    WalkBase(H* h_, Arena* ar_, hipStream_t s_, bool run_) : h(h_), ar(ar_), s(s_), run(run_) {}
+
+    size_t es() const { return dtype_size(h->dt); }
+    void* alloc_act(size_t elems) {
+        if (elems * es() > max_tensor) max_tensor = elems * es();
+        return ar->alloc(elems * es());
+    }
+    const char* dtn() const { return h->dt == DSIM_F32 ? "f32" : (h->dt == DSIM_F16 ? "f16" : "bf16"); }
+
+    // ---- optional per-launch HIP-event brackets (profiled forward only) --------------------
+    void pbegin(const std::string& name, double flops, double bytes) { if (run && h->profiling) prof_begin(h, s, name, flops, bytes); }
+    void pend() { if (run && h->profiling) prof_end(h, s); }
+    // the record of an attention launch; fp8: the e4m3 kernel (attention_fp8.hip), its own family
+    void pbegin_attn(const AttnArgs& a, bool fp8 = false) {
+        if (!run || !h->profiling) return;
+        // (key sequences >= 2048 run the fixed-reference instantiation attn_kernel<T, D, true>: its own family)
+        pbegin((fp8 ? std::string("attention_fp8_d") + std::to_string(a.D)
+                    : std::string("attention_") + dtn() + "_d" + std::to_string(a.D) + attention_kernel_kind(a, h->dt)) +
+                   "|B" + std::to_string(a.B) + " H" + std::to_string(a.H) + " Nq" + std::to_string(a.Nq) + " Nk" + std::to_string(a.Nk),
+               4.0 * a.B * a.H * (double)a.Nq * a.Nk * a.D, (double)es() * a.B * a.H * a.D * (2.0 * a.Nq + 2.0 * a.Nk));
+    }
+    // the record of a GroupNorm launch over B x HW x (C0 + C1); pre: statistics from the producing conv's epilogue (apply pass only)
+    void pbegin_gn(int B, int HW, int C0, int C1, int groups, bool pre = false) {
+        if (!run || !h->profiling) return;
+        const double n = (double)B * HW * (C0 + C1);
+        pbegin(std::string(pre ? "groupnorm_pre_" : "groupnorm_") + dtn() + "|B" + std::to_string(B) + " HW" + std::to_string(HW) + " C" +
+                   std::to_string(C0 + C1), 0.0,
+               (pre ? 2.0 : (double)groupnorm_passes(C0, C1, HW, groups, h->dt)) * n * es());
+    }
+
+    // family: the record's name where gemm_family() does not know it (DiT's epilogues), with its work
+    int gemm(GemmArgs& g, const std::string* family = nullptr, double flops = 0, double bytes = 0) {
+        g.zero_page = h->zero_page;
+        if (!run) return DSIM_OK;
+        if (h->profiling && family) {
+            pbegin(*family, flops, bytes);
+        } else if (h->profiling) {
+            double fl, by;
+            const std::string nm = gemm_family(g, h->dt, &fl, &by);
+            pbegin(nm, fl, by);
+        }
+        const int st = launch_gemm(g, h->dt, s);
+        pend();
+        return st;
+    }
+};
+
+}  // namespace
 
 // Repack every raw parameter into the engine's layouts.
 // ---- weight packing (finalize) ---------------------------------------------------------------

@@ -1,4 +1,4 @@
-// U-Net-to-tap graph executor and the C ABI of libdiffsim_amd.
+// U-Net-to-tap graph executor and its C ABI (dsim_unet_*; the ops' and score tails' entry points are in api.hip).
 //
 // Implements, as a sequence of hand-written gfx950 kernels on ONE HIP stream, the sub-graph of
 // diffusers' UNet2DConditionModel that the reference executes before its attention pre-hook
@@ -14,10 +14,7 @@
 // planner can never disagree with the executor.  Activations are token-major [B][HW][C] in the
 // compute dtype; the workspace is a caller-provided arena with stack discipline.
 #include <array>
-#include <cmath>
-#include <cstdio>
 #include <cstring>
-#include <map>
 #include <string>
 #include <vector>
 
@@ -53,12 +50,8 @@ static std::vector<TapReq> cfg_taps(const dsim_unet_cfg& c, void* q = nullptr, v
 }
 
 // ---- the walk ----------------------------------------------------------------------------
-struct Walk {
-    dsim_unet* h;
-    Arena* ar;
-    hipStream_t s;
+struct Walk : WalkBase<dsim_unet> {
     int B2;                 // U-Net batch = 2 * images (CFG)
-    bool run;               // false: plan only
     void* gn_scratch = nullptr;
     void* ctx_t = nullptr;  // [2][L][Dc] compute dtype; with a context table, [B2][L][Dc] (one context per batch element)
     std::vector<TapReq> taps;   // where q, k, v are captured; the walk ends at the deepest of them
@@ -68,45 +61,8 @@ struct Walk {
     const int32_t* ctx_index = nullptr;     // device int32 [images]: each image's row of the table (n_ctx > 1)
     bool mixed() const { return n_ctx > 1; }
 
-    size_t es() const { return dtype_size(h->dt); }
-    size_t max_tensor = 0;      // largest single activation (bytes): the kernels address tensors with 32-bit offsets
-    void* alloc_act(size_t elems) {
-        if (elems * es() > max_tensor) max_tensor = elems * es();
-        return ar->alloc(elems * es());
-    }
+    Walk(dsim_unet* h, Arena* ar, hipStream_t s, int B2, bool run) : WalkBase(h, ar, s, run), B2(B2) {}
 
-#define WGET(var, key)                                   \
-    const Packed* var = h->find(key);                    \
-    if (!var) return DSIM_ERR_MISSING_WEIGHT;
-
-    // ---- optional per-launch HIP-event brackets (profiled forward only) --------------------
-    void pbegin(const std::string& name, double flops, double bytes) {
-        if (!run || !h->profiling) return;
-        ProfRec r;
-        r.name = name; r.flops = flops; r.bytes = bytes;
-        (void)hipEventCreate(&r.e0);
-        (void)hipEventCreate(&r.e1);
-        (void)hipEventRecord(r.e0, s);
-        h->prof.push_back(r);
-    }
-    void pend() {
-        if (!run || !h->profiling) return;
-        (void)hipEventRecord(h->prof.back().e1, s);
-    }
-    const char* dtn() const { return h->dt == DSIM_F32 ? "f32" : (h->dt == DSIM_F16 ? "f16" : "bf16"); }
-
-    int gemm(GemmArgs& g) {
-        g.zero_page = h->zero_page;
-        if (!run) return DSIM_OK;
-        if (h->profiling) {
-            double fl, by;
-            const std::string nm = gemm_family(g, h->dt, &fl, &by);
-            pbegin(nm, fl, by);
-        }
-        const int st = launch_gemm(g, h->dt, s);
-        pend();
-        return st;
-    }
     int linear(const void* a0, int c0, const void* a1, int c1, const Packed* w, const Packed* b, const void* residual,
                void* out, int M, int N, int ldo, int epi = -1) {
         GemmArgs g;
@@ -140,10 +96,7 @@ struct Walk {
     }
     int gn(const Act& x0, const Act* x1, const Packed* g, const Packed* b, void* out, float eps, int silu) {
         if (!run) return DSIM_OK;
-        const double n = (double)B2 * x0.H * x0.W * (x0.C + (x1 ? x1->C : 0));
-        pbegin(std::string("groupnorm_") + dtn() + "|B" + std::to_string(B2) + " HW" + std::to_string(x0.H * x0.W) + " C" +
-                   std::to_string(x0.C + (x1 ? x1->C : 0)), 0.0,
-               (double)groupnorm_passes(x0.C, x1 ? x1->C : 0, x0.H * x0.W, h->cfg.norm_num_groups, h->dt) * n * es());
+        pbegin_gn(B2, x0.H * x0.W, x0.C, x1 ? x1->C : 0, h->cfg.norm_num_groups);
         const int st = launch_groupnorm(x0.p, x0.C, x1 ? x1->p : nullptr, x1 ? x1->C : 0, (const float*)g->p,
                                         (const float*)b->p, out, B2, x0.H * x0.W, h->cfg.norm_num_groups, eps, silu,
                                         h->dt, gn_scratch, s);
@@ -159,12 +112,7 @@ struct Walk {
     }
     int attn(const AttnArgs& a) {
         if (!run) return DSIM_OK;
-        // (key sequences >= 2048 run the fixed-reference instantiation attn_kernel<T, D, true>: its own family)
-        pbegin(std::string("attention_") + dtn() + "_d" + std::to_string(a.D) + attention_kernel_kind(a, h->dt) +
-                   "|B" + std::to_string(a.B) + " H" + std::to_string(a.H) +
-                   " Nq" + std::to_string(a.Nq) + " Nk" + std::to_string(a.Nk),
-               4.0 * a.B * a.H * (double)a.Nq * a.Nk * a.D,
-               (double)es() * a.B * a.H * a.D * (2.0 * a.Nq + 2.0 * a.Nk));
+        pbegin_attn(a);
         const int st = launch_attention(a, h->dt, s);
         pend();
         return st;
@@ -583,59 +531,18 @@ int tap_geometry(const dsim_unet_cfg& c, int* tokens, int* heads, int* hd) {
 // =============================================================================================
 extern "C" {
 
-int dsim_version(void) { return DSIM_ABI_VERSION; }
-
-const char* dsim_strerror(int st) {
-    switch (st) {
-        case DSIM_OK: return "ok";
-        case DSIM_ERR_INVALID: return "invalid argument or unsupported shape";
-        case DSIM_ERR_MISSING_WEIGHT: return "a parameter needed before the tap was never loaded";
-        case DSIM_ERR_WORKSPACE: return "workspace too small";
-        case DSIM_ERR_HIP: return "HIP runtime error";
-        case DSIM_ERR_STATE: return "call order violated";
-        case DSIM_ERR_NO_DEVICE: return "no HIP device";
-        default: return "unknown status";
-    }
-}
-
-int dsim_device_count(void) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-    return n;
-}
-
 int dsim_unet_create(const dsim_unet_cfg* cfg, dsim_unet** out) {
     if (!cfg || !out) return DSIM_ERR_INVALID;
     if (cfg->n_levels < 1 || cfg->n_levels > DSIM_MAX_LEVELS) return DSIM_ERR_INVALID;
-    if (cfg->compute_dtype != DSIM_F32 && cfg->compute_dtype != DSIM_BF16 && cfg->compute_dtype != DSIM_F16) return DSIM_ERR_INVALID;
     int t, hh, d;
     CK(tap_geometry(*cfg, &t, &hh, &d));
-    if (dsim_device_count() < 1) return DSIM_ERR_NO_DEVICE;
-    dsim_unet* h = new dsim_unet();
-    h->cfg = *cfg;
-    h->dt = cfg->compute_dtype;
-    if (h->dalloc(256, &h->zero_page) != DSIM_OK || hipMemset(h->zero_page, 0, 256) != hipSuccess) {
-        dsim_unet_destroy(h);
-        return DSIM_ERR_HIP;
-    }
-    *out = h;
-    return DSIM_OK;
+    return handle_create(cfg, out);
 }
 
-void dsim_unet_destroy(dsim_unet* h) {
-    if (!h) return;
-    for (void* p : h->owned) (void)hipFree(p);
-    delete h;
-}
+void dsim_unet_destroy(dsim_unet* h) { delete h; }
 
 int dsim_unet_load_weight(dsim_unet* h, const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim) {
-    if (!h || !key || !dev_ptr || !shape || ndim < 1 || ndim > 4) return DSIM_ERR_INVALID;
-    if (dtype != DSIM_F32 && dtype != DSIM_BF16 && dtype != DSIM_F16) return DSIM_ERR_INVALID;
-    if (h->finalized) return DSIM_ERR_STATE;
-    RawW w;
-    w.p = dev_ptr; w.dtype = dtype; w.shape.assign(shape, shape + ndim);
-    h->raw[key] = w;
-    return DSIM_OK;
+    return handle_load(h, key, dev_ptr, dtype, shape, ndim);
 }
 
 int dsim_unet_finalize(dsim_unet* h, void* stream) {
@@ -908,38 +815,27 @@ int dsim_unet_set_sample_size(dsim_unet* h, int side) {
     return DSIM_OK;
 }
 
-// a caller's workspace starts at its first 256-byte boundary: moves `ws` there and takes the bytes before it off `bytes`; false when
-// the buffer does not reach it
-static bool align_workspace(void*& ws, size_t& bytes) {
-    const uintptr_t b0 = ((uintptr_t)ws + 255) & ~(uintptr_t)255;
-    const size_t lost = b0 - (uintptr_t)ws;
-    if (bytes < lost) return false;
-    ws = (void*)b0;
-    bytes -= lost;
-    return true;
-}
-
 // one walk to the deepest of `taps` (their outputs set), every check before the first launch
 static int run_taps(dsim_unet* h, const float* latents, const float* noise, float sqrt_abar, float sqrt_1m_abar, const float* ctx,
                     int n_images, const std::vector<TapReq>& taps, void* workspace, size_t workspace_bytes, void* stream,
                     int n_ctx = 1, const int32_t* ctx_index = nullptr) {
-    Arena ar;
-    ar.dry = false;
-    if (!align_workspace(workspace, workspace_bytes)) return DSIM_ERR_WORKSPACE;
-    ar.base = (char*)workspace;
-    ar.cap = workspace_bytes;
-    {   // refuse up front instead of failing mid-graph
-        size_t peak, big;
-        CK(plan_taps(h, n_images, taps, &peak, &big, n_ctx));
-        if (peak > ar.cap) return DSIM_ERR_WORKSPACE;
-    }
-    Walk w{h, &ar, (hipStream_t)stream, 2 * n_images, true};
-    w.taps = taps;
-    w.n_ctx = n_ctx;
-    w.ctx_index = ctx_index;
-    CK(w.go(latents, noise, sqrt_abar, sqrt_1m_abar, ctx));
-    if (ar.overflow) return DSIM_ERR_WORKSPACE;
-    return w.tapped ? DSIM_OK : DSIM_ERR_INVALID;
+    bool tapped = false;
+    CK(run_in_workspace(
+        workspace, workspace_bytes,
+        [&](size_t* peak) {
+            size_t big;
+            return plan_taps(h, n_images, taps, peak, &big, n_ctx);
+        },
+        [&](Arena& ar) {
+            Walk w{h, &ar, (hipStream_t)stream, 2 * n_images, true};
+            w.taps = taps;
+            w.n_ctx = n_ctx;
+            w.ctx_index = ctx_index;
+            const int st = w.go(latents, noise, sqrt_abar, sqrt_1m_abar, ctx);
+            tapped = w.tapped;
+            return st;
+        }));
+    return tapped ? DSIM_OK : DSIM_ERR_INVALID;        // (a walk that reached no tap is an invalid tap here; dit_run calls it a workspace error)
 }
 
 int dsim_unet_qkv(dsim_unet* h, const float* latents, const float* noise, float sqrt_abar, float sqrt_1m_abar,
@@ -992,387 +888,10 @@ int dsim_unet_qkv_taps_ctx(dsim_unet* h, const float* latents, const float* nois
                     workspace_bytes, stream);
 }
 
-int dsim_unet_profile(dsim_unet* h, int enable) {
-    if (!h) return DSIM_ERR_INVALID;
-    for (auto& r : h->prof) {
-        if (r.e0) (void)hipEventDestroy(r.e0);
-        if (r.e1) (void)hipEventDestroy(r.e1);
-    }
-    h->prof.clear();
-    h->profiling = enable != 0;
-    return DSIM_OK;
-}
-
-int dsim_unet_profile_count(const dsim_unet* h) { return h ? (int)h->prof.size() : 0; }
-
+int dsim_unet_profile(dsim_unet* h, int enable) { return prof_enable(h, enable); }
+int dsim_unet_profile_count(const dsim_unet* h) { return prof_count(h); }
 int dsim_unet_profile_get(dsim_unet* h, int i, char* name, int name_cap, double* flops, double* bytes, double* ms) {
-    if (!h || i < 0 || i >= (int)h->prof.size() || !name || name_cap < 2 || !flops || !bytes || !ms)
-        return DSIM_ERR_INVALID;
-    ProfRec& r = h->prof[i];
-    if (r.e0 && r.e1) {
-        DSIM_HIP_CHECK(hipEventSynchronize(r.e1));
-        DSIM_HIP_CHECK(hipEventElapsedTime(&r.ms, r.e0, r.e1));
-    }
-    strncpy(name, r.name.c_str(), (size_t)name_cap - 1);
-    name[name_cap - 1] = 0;
-    *flops = r.flops; *bytes = r.bytes; *ms = (double)r.ms;
-    return DSIM_OK;
-}
-
-size_t dsim_pair_score_workspace_bytes(int n_pairs, int B, int H, int N, int D) {
-    return pair_score_scratch_bytes(n_pairs, B, H, N, D) + 256;
-}
-
-// status may be NULL here; dsim_pair_score_status requires it
-static int pair_score(const void* q, const void* k, const void* v, const int32_t* idx_a, const int32_t* idx_b, int n_pairs, int B,
-                      int H, int N, int D, int dtype, int similarity, float* out_scores, int32_t* status, void* workspace,
-                      size_t workspace_bytes, void* stream) {
-    if (!q || !k || !v || !idx_a || !idx_b || !out_scores || !workspace) return DSIM_ERR_INVALID;
-    if (similarity != 0 && similarity != 1) return DSIM_ERR_INVALID;
-    if (!align_workspace(workspace, workspace_bytes)) return DSIM_ERR_WORKSPACE;
-    return launch_pair_score(q, k, v, idx_a, idx_b, n_pairs, B, H, N, D, dtype, similarity, out_scores, workspace, workspace_bytes,
-                             (hipStream_t)stream, status);
-}
-
-int dsim_pair_score(const void* q, const void* k, const void* v, const int32_t* idx_a, const int32_t* idx_b, int n_pairs,
-                    int B, int H, int N, int D, int dtype, int similarity, float* out_scores, void* workspace,
-                    size_t workspace_bytes, void* stream) {
-    return pair_score(q, k, v, idx_a, idx_b, n_pairs, B, H, N, D, dtype, similarity, out_scores, nullptr, workspace, workspace_bytes,
-                      stream);
-}
-
-int dsim_pair_score_status(const void* q, const void* k, const void* v, const int32_t* idx_a, const int32_t* idx_b,
-                           int n_pairs, int B, int H, int N, int D, int dtype, int similarity, float* out_scores,
-                           int32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!status) return DSIM_ERR_INVALID;
-    return pair_score(q, k, v, idx_a, idx_b, n_pairs, B, H, N, D, dtype, similarity, out_scores, status, workspace, workspace_bytes,
-                      stream);
-}
-
-size_t dsim_score_matrix_workspace_bytes(int n_a, int n_b, int B, int H, int N, int D, int dtype) {
-    const size_t b = score_matrix_scratch_bytes(n_a, n_b, B, H, N, D, dtype);
-    return b ? b + 256 : 0;
-}
-
-int dsim_score_matrix(const void* qa, const void* ka, const void* va, int n_a, const void* qb, const void* kb, const void* vb, int n_b,
-                      int B, int H, int N, int D, int dtype, int similarity, float* out, int32_t* status, void* workspace,
-                      size_t workspace_bytes, void* stream) {
-    if (!qa || !ka || !va || !qb || !kb || !vb || !out || !workspace) return DSIM_ERR_INVALID;
-    if (!align_workspace(workspace, workspace_bytes)) return DSIM_ERR_WORKSPACE;
-    return launch_score_matrix(qa, ka, va, n_a, qb, kb, vb, n_b, B, H, N, D, dtype, similarity, out, status, workspace,
-                               workspace_bytes, (hipStream_t)stream);
-}
-
-size_t dsim_pair_score_maps_workspace_bytes(int n_pairs, int B, int H, int N, int D) {
-    const size_t b = pair_score_maps_scratch_bytes(n_pairs, B, H, N);
-    return b && D >= 1 ? b + 256 : 0;
-}
-
-int dsim_pair_score_maps(const void* q, const void* k, const void* v, const int32_t* idx_a, const int32_t* idx_b, int n_pairs, int B,
-                         int H, int N, int D, int dtype, int similarity, float* score, float* local, float* contrib, int32_t* status,
-                         void* workspace, size_t workspace_bytes, void* stream) {
-    if (!q || !k || !v || !idx_a || !idx_b || !score || !workspace) return DSIM_ERR_INVALID;
-    if (similarity != 0 && similarity != 1) return DSIM_ERR_INVALID;
-    if (!align_workspace(workspace, workspace_bytes)) return DSIM_ERR_WORKSPACE;
-    return launch_pair_score_maps(q, k, v, idx_a, idx_b, n_pairs, B, H, N, D, dtype, similarity, score, local, contrib, status,
-                                  workspace, workspace_bytes, (hipStream_t)stream);
-}
-
-// ---- single-operator entry points (tests / micro-benchmarks; these allocate and synchronise) ----
-namespace {
-struct Tmp {
-    std::vector<void*> v;
-    ~Tmp() { for (void* p : v) (void)hipFree(p); }
-    void* get(size_t bytes) {
-        void* p = nullptr;
-        if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) return nullptr;
-        v.push_back(p);
-        return p;
-    }
-};
-}  // namespace
-
-int dsim_op_linear(const void* x, const float* w, const float* bias, const void* residual, void* out, int M, int N,
-                   int K, int dtype, int geglu, void* stream) {
-    hipStream_t s = (hipStream_t)stream;
-    Tmp t;
-    const int NW = geglu ? 2 * N : N;
-    void* wp = t.get((size_t)NW * K * dtype_size(dtype));
-    float* bp = bias ? (float*)t.get((size_t)NW * 4) : nullptr;
-    void* zp = t.get(256);
-    if (!wp || !zp || (bias && !bp)) return DSIM_ERR_HIP;
-    DSIM_HIP_CHECK(hipMemsetAsync(zp, 0, 256, s));
-    const int gblk = geglu ? geglu_block_rows(NW) : 0;
-    CK(pack_linear(w, DSIM_F32, wp, dtype, NW, K, gblk, s));
-    if (bias) CK(pack_vector(bias, DSIM_F32, bp, NW, gblk, s));
-    GemmArgs g;
-    g.A0 = x; g.C0 = K; g.mode = GEMM_LINEAR; g.M = M; g.N = NW; g.K = K; g.W = wp; g.bias = bp;
-    g.epi = geglu ? EPI_GEGLU : (residual ? EPI_RESIDUAL : EPI_NONE);
-    if (geglu) g.geglu_blk = gblk;
-    g.residual = residual; g.out = out; g.ldo = N; g.zero_page = zp;
-    CK(launch_gemm(g, dtype, s));
-    DSIM_HIP_CHECK(hipStreamSynchronize(s));
-    return DSIM_OK;
-}
-
-int dsim_op_conv3x3(const void* x, const float* w, const float* bias, const void* residual, void* out, int B, int H,
-                    int W, int Cin, int Cout, int stride, int upsample, int dtype, void* stream) {
-    hipStream_t s = (hipStream_t)stream;
-    Tmp t;
-    void* wp = t.get((size_t)Cout * 9 * Cin * dtype_size(dtype));
-    void* zp = t.get(256);
-    if (!wp || !zp) return DSIM_ERR_HIP;
-    DSIM_HIP_CHECK(hipMemsetAsync(zp, 0, 256, s));
-    CK(pack_conv3(w, DSIM_F32, wp, dtype, Cout, Cin, s));
-    GemmArgs g;
-    g.A0 = x; g.C0 = Cin; g.mode = GEMM_CONV3; g.Hin = H; g.Win = W;
-    g.Hout = upsample ? 2 * H : (stride == 2 ? (H + 1) / 2 : H);      // stride 2, padding 1: ceil(H / 2), as the executor
-    g.Wout = upsample ? 2 * W : (stride == 2 ? (W + 1) / 2 : W);
-    g.stride = stride; g.ups = upsample ? 1 : 0;
-    g.M = B * g.Hout * g.Wout; g.N = Cout; g.K = 9 * Cin; g.W = wp; g.bias = bias;
-    g.epi = residual ? EPI_RESIDUAL : EPI_NONE; g.residual = residual; g.out = out; g.ldo = Cout; g.zero_page = zp;
-    CK(launch_gemm(g, dtype, s));
-    DSIM_HIP_CHECK(hipStreamSynchronize(s));
-    return DSIM_OK;
-}
-
-int dsim_op_gemm(const dsim_gemm_op* op, dsim_gemm_launch* launched, void* stream) {
-    if (!op || !launched || !op->A0 || !op->w || !op->out) return DSIM_ERR_INVALID;
-    const int dt = op->dtype;
-    if ((dt != DSIM_F32 && dt != DSIM_BF16 && dt != DSIM_F16) || (op->mode != GEMM_LINEAR && op->mode != GEMM_CONV3)) return DSIM_ERR_INVALID;
-    if (op->M <= 0 || op->N <= 0 || op->K <= 0 || op->wb_rows < 0) return DSIM_ERR_INVALID;
-    if ((op->bias2 || op->gate2) && op->rows_per_batch <= 0) return DSIM_ERR_INVALID;
-    if ((op->bias2 && !op->bias) || (op->gate2 && !op->gate)) return DSIM_ERR_INVALID;      // the odd rows' vector replaces the even rows'
-    {
-        // rows are ldo elements apart: at least the columns one output tensor receives
-        const int ncol = op->epi == EPI_GEGLU ? op->N / 2 : op->N;
-        if (op->ldo < (op->out_split > 0 ? op->out_split : ncol)) return DSIM_ERR_INVALID;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    const size_t es = dtype_size(dt);
-    const bool geglu = op->epi == EPI_GEGLU;
-    GemmArgs g;
-    g.A0 = op->A0; g.C0 = op->C0; g.A1 = op->A1; g.C1 = op->A1 ? op->C1 : 0;
-    g.mode = op->mode; g.M = op->M; g.N = op->N; g.K = op->K;
-    if (op->mode == GEMM_CONV3) {
-        if (op->pad != 0 && op->pad != 1) return DSIM_ERR_INVALID;
-        if (op->pad == 0 && (op->stride != 2 || op->ups)) return DSIM_ERR_INVALID;      // the VAE downsample's form only
-        g.Hin = op->H; g.Win = op->W; g.stride = op->stride; g.ups = op->ups ? 1 : 0; g.pad = op->pad;
-        // stride 2: ceil(H / 2) rows with padding 1, H / 2 with the right / bottom padding of the VAE (pad 0)
-        g.Hout = op->ups ? 2 * op->H : (op->stride == 2 ? (op->pad ? (op->H + 1) / 2 : op->H / 2) : op->H);
-        g.Wout = op->ups ? 2 * op->W : (op->stride == 2 ? (op->pad ? (op->W + 1) / 2 : op->W / 2) : op->W);
-        if (g.Hout <= 0 || g.Wout <= 0 || op->M % (g.Hout * g.Wout)) return DSIM_ERR_INVALID;
-    }
-    const int gblk = geglu ? geglu_block_rows(op->N) : 0;
-    const int nmat = op->wb_rows > 0 ? op->M / op->wb_rows : 1;
-    const size_t wmat = (size_t)op->N * op->K * es;
-    if (op->wb_rows > 0 && (op->M % op->wb_rows || op->wb_stride % 16 || (size_t)op->wb_stride < wmat)) return DSIM_ERR_INVALID;
-    Tmp t;
-    void* wp = t.get(op->wb_rows > 0 ? (size_t)(nmat - 1) * op->wb_stride + wmat : wmat);
-    float* bp = op->bias ? (float*)t.get((size_t)op->N * 4) : nullptr;
-    float* b2p = op->bias2 ? (float*)t.get((size_t)op->N * 4) : nullptr;
-    void* zp = t.get(256);
-    if (!wp || !zp || (op->bias && !bp) || (op->bias2 && !b2p)) return DSIM_ERR_HIP;
-    DSIM_HIP_CHECK(hipMemsetAsync(zp, 0, 256, s));
-    if (op->mode == GEMM_CONV3) {
-        CK(pack_conv3(op->w, DSIM_F32, wp, dt, op->N, op->C0, s));
-    } else {
-        for (int i = 0; i < nmat; ++i)
-            CK(pack_linear(op->w + (size_t)i * op->N * op->K, DSIM_F32, (char*)wp + (size_t)i * op->wb_stride, dt, op->N, op->K, gblk, s));
-    }
-    if (op->bias) CK(pack_vector(op->bias, DSIM_F32, bp, op->N, gblk, s));
-    if (op->bias2) CK(pack_vector(op->bias2, DSIM_F32, b2p, op->N, gblk, s));
-    g.W = wp; g.bias = bp; g.bias2 = b2p; g.rows_per_batch = op->rows_per_batch;
-    g.act = op->act; g.gate = op->gate; g.gate2 = op->gate2;
-    g.epi = op->epi;
-    if (geglu) g.geglu_blk = gblk;
-    g.residual = op->residual; g.out = op->out; g.ldo = op->ldo;
-    g.out_split = op->out_split; g.out_split_stride = op->out_split_stride;
-    g.force_big = op->force_big;
-    g.wb_rows = op->wb_rows; g.wb_stride = op->wb_rows > 0 ? op->wb_stride : 0;
-    g.gn_part = op->gn_part; g.gn_hw = op->gn_hw;
-    g.zero_page = zp;
-    double fl = 0, by = 0;
-    const std::string fam = gemm_family(g, dt, &fl, &by);
-    g_gemm_last_launch = GemmLaunchRec{};
-    CK(launch_gemm(g, dt, s));
-    DSIM_HIP_CHECK(hipStreamSynchronize(s));
-    const GemmLaunchRec& r = g_gemm_last_launch;
-    launched->bm = r.bm; launched->bn = r.bn; launched->kind = r.mode; launched->geglu = r.geglu; launched->ek = r.ek;
-    launched->small = r.small;
-    std::snprintf(launched->family, sizeof(launched->family), "%s", fam.c_str());
-    return DSIM_OK;
-}
-
-int dsim_op_groupnorm_pre(const void* x, int C, const float* gamma, const float* beta, void* out, int B, int HW, int groups,
-                          float eps, int silu, int dtype, const float* part32, int chunks, void* stream) {
-    hipStream_t s = (hipStream_t)stream;
-    if (!x || !gamma || !beta || !out || !part32 || B <= 0 || HW <= 0 || groups <= 0 || C % groups) return DSIM_ERR_INVALID;
-    if (chunks < 1 || (long)chunks * 64 != HW) return DSIM_ERR_INVALID;        // one partial per 64 rows of each image (gn_part's layout)
-    Tmp t;
-    void* sc = t.get(groupnorm_scratch_bytes(B, groups));
-    if (!sc) return DSIM_ERR_HIP;
-    CK(launch_groupnorm_pre(x, C, gamma, beta, out, B, HW, groups, eps, silu, dtype, sc, part32, chunks, s));
-    DSIM_HIP_CHECK(hipStreamSynchronize(s));
-    return DSIM_OK;
-}
-
-int dsim_op_groupnorm(const void* x0, int C0, const void* x1, int C1, const float* gamma, const float* beta, void* out,
-                      int B, int HW, int groups, float eps, int silu, int dtype, void* stream) {
-    hipStream_t s = (hipStream_t)stream;
-    Tmp t;
-    void* sc = t.get(groupnorm_scratch_bytes(B, groups));
-    if (!sc) return DSIM_ERR_HIP;
-    CK(launch_groupnorm(x0, C0, x1, C1, gamma, beta, out, B, HW, groups, eps, silu, dtype, sc, s));
-    DSIM_HIP_CHECK(hipStreamSynchronize(s));
-    return DSIM_OK;
-}
-
-int dsim_op_layernorm(const void* x, const float* gamma, const float* beta, void* out, int M, int C, float eps, int dtype,
-                      void* stream) {
-    hipStream_t s = (hipStream_t)stream;
-    CK(launch_layernorm(x, gamma, beta, out, M, C, eps, dtype, s));
-    DSIM_HIP_CHECK(hipStreamSynchronize(s));
-    return DSIM_OK;
-}
-
-int dsim_op_layernorm_mod(const void* x, const float* scale2, const float* shift2, void* out, int M, int C, int rows_per_batch,
-                          float eps, int dtype, void* stream) {
-    hipStream_t s = (hipStream_t)stream;
-    if (!x || !scale2 || !shift2 || !out) return DSIM_ERR_INVALID;
-    CK(launch_layernorm_mod(x, scale2, shift2, out, M, C, rows_per_batch, eps, dtype, s));
-    DSIM_HIP_CHECK(hipStreamSynchronize(s));
-    return DSIM_OK;
-}
-
-int dsim_groupnorm_plan(int C0, int C1, int B, int HW, int groups, int dtype, int pre, dsim_gn_plan* plan) {
-    return groupnorm_plan(C0, C1, B, HW, groups, dtype, pre, plan);
-}
-
-int dsim_layernorm_plan(int M, int C, int dtype, int mod, dsim_ln_plan* plan) { return layernorm_plan(M, C, dtype, mod, plan); }
-
-int dsim_op_ff_fused_dt(const void* x, const float* ln_gamma, const float* ln_beta, const float* w1, const float* b1,
-                        const float* w2, const float* b2, void* out, int M, int C, float eps, int dtype, void* stream) {
-    hipStream_t s = (hipStream_t)stream;
-    const size_t sb = ff_stream_bytes(C);
-    if ((dtype != DSIM_BF16 && dtype != DSIM_F16) || !sb || !x || !out || !w1 || !b1 || !w2 || !b2 || !ln_gamma || !ln_beta) return DSIM_ERR_INVALID;
-    Tmp t;
-    void* w1p = t.get((size_t)8 * C * C * 2);
-    float* b1p = (float*)t.get((size_t)8 * C * 4);
-    void* w2p = t.get((size_t)4 * C * C * 2);
-    void* st = t.get(sb);
-    if (!w1p || !b1p || !w2p || !st) return DSIM_ERR_HIP;
-    CK(pack_linear(w1, DSIM_F32, w1p, dtype, 8 * C, C, 32, s));
-    CK(pack_vector(b1, DSIM_F32, b1p, 8 * C, 32, s));
-    CK(pack_linear(w2, DSIM_F32, w2p, dtype, C, 4 * C, 0, s));
-    CK(pack_ff_stream(w1p, w2p, st, C, s));
-    FFArgs a;
-    a.x = x; a.out = out; a.ln_g = ln_gamma; a.ln_b = ln_beta; a.stream = st; a.b1 = b1p; a.b2 = b2; a.M = M; a.C = C; a.eps = eps; a.dtype = dtype;
-    CK(launch_ff_fused(a, s));
-    DSIM_HIP_CHECK(hipStreamSynchronize(s));
-    return DSIM_OK;
-}
-
-int dsim_op_ff_fused(const void* x, const float* ln_gamma, const float* ln_beta, const float* w1, const float* b1,
-                     const float* w2, const float* b2, void* out, int M, int C, float eps, void* stream) {
-    return dsim_op_ff_fused_dt(x, ln_gamma, ln_beta, w1, b1, w2, b2, out, M, C, eps, DSIM_BF16, stream);
-}
-
-int dsim_op_ln_linear_dt(const void* x, const float* ln_gamma, const float* ln_beta, const float* w, void* out, int M, int C, int N,
-                         float eps, int dtype, void* stream) {
-    hipStream_t s = (hipStream_t)stream;
-    const size_t sb = rowlin_stream_bytes(C, N);
-    if ((dtype != DSIM_BF16 && dtype != DSIM_F16) || !sb || !x || !out || !w || !ln_gamma != !ln_beta) return DSIM_ERR_INVALID;
-    Tmp t;
-    void* wp = t.get((size_t)N * C * 2);
-    void* st = t.get(sb);
-    if (!wp || !st) return DSIM_ERR_HIP;
-    CK(pack_linear(w, DSIM_F32, wp, dtype, N, C, 0, s));
-    CK(pack_rowlin_stream(wp, st, C, N, s));
-    RowLinArgs a;
-    a.x = x; a.out = out; a.ln_g = ln_gamma; a.ln_b = ln_beta; a.stream = st; a.M = M; a.C = C; a.N = N; a.eps = eps; a.dtype = dtype;
-    CK(launch_rowlin(a, s));
-    DSIM_HIP_CHECK(hipStreamSynchronize(s));
-    return DSIM_OK;
-}
-
-int dsim_op_ln_linear(const void* x, const float* ln_gamma, const float* ln_beta, const float* w, void* out, int M, int C, int N,
-                      float eps, void* stream) {
-    return dsim_op_ln_linear_dt(x, ln_gamma, ln_beta, w, out, M, C, N, eps, DSIM_BF16, stream);
-}
-
-int dsim_op_attention(const void* q, int ldq, const void* k, const void* v, int ldk, void* out, int ldo, int B, int Bkv,
-                      int H, int Nq, int Nk, int D, int dtype, void* stream) {
-    hipStream_t s = (hipStream_t)stream;
-    AttnArgs a;
-    a.q = q; a.ldq = ldq; a.k = k; a.v = v; a.ldk = ldk; a.out = out; a.ldo = ldo;
-    a.B = B; a.Bkv = Bkv; a.H = H; a.Nq = Nq; a.Nk = Nk; a.D = D;
-    CK(launch_attention(a, dtype, s));
-    DSIM_HIP_CHECK(hipStreamSynchronize(s));
-    return DSIM_OK;
-}
-
-int dsim_op_attention_fp8(const void* q, int ldq, const void* k, const void* v, int ldk, void* out, int ldo, int B, int Bkv,
-                          int H, int Nq, int Nk, int D, void* stream) {
-    hipStream_t s = (hipStream_t)stream;
-    AttnArgs a;
-    a.q = q; a.ldq = ldq; a.k = k; a.v = v; a.ldk = ldk; a.out = out; a.ldo = ldo;
-    a.B = B; a.Bkv = Bkv; a.H = H; a.Nq = Nq; a.Nk = Nk; a.D = D;
-    CK(launch_attention_fp8(a, s));
-    DSIM_HIP_CHECK(hipStreamSynchronize(s));
-    return DSIM_OK;
-}
-
-static int attn_fp8_ok(const AttnArgs& a) {
-    // launch_attention_fp8's own refusals
-    if (!a.q || !a.k || !a.v || !a.out || a.B < 1 || a.Bkv < 1 || a.H < 1 || a.Nq < 1 || a.Nk < 1) return 0;
-    return !(a.ldq % 8 || a.ldk % 8 || a.ldo % 4) && (a.D == 72 || a.D == 32);
-}
-
-int dsim_attention_plan(const void* q, int ldq, const void* k, const void* v, int ldk, const void* out, int ldo, int B, int Bkv,
-                        int H, int Nq, int Nk, int D, int dtype, int fp8, int* kind) {
-    if (!kind) return DSIM_ERR_INVALID;
-    AttnArgs a;
-    a.q = q; a.ldq = ldq; a.k = k; a.v = v; a.ldk = ldk; a.out = (void*)out; a.ldo = ldo;
-    a.B = B; a.Bkv = Bkv; a.H = H; a.Nq = Nq; a.Nk = Nk; a.D = D;
-    if (fp8) {
-        if (dtype != DSIM_BF16 || !attn_fp8_ok(a)) return DSIM_ERR_INVALID;
-        *kind = DSIM_ATTN_FP8;
-        return DSIM_OK;
-    }
-    const int r = attention_plan(a, dtype);
-    if (r < 0) return r;
-    *kind = r;
-    return DSIM_OK;
-}
-
-int dsim_op_attention_ex(const void* q, int ldq, const void* k, const void* v, int ldk, void* out, int ldo, int B, int Bkv, int H,
-                         int Nq, int Nk, int D, int dtype, int fp8, dsim_attn_launch* launched, void* stream) {
-    hipStream_t s = (hipStream_t)stream;
-    AttnArgs a;
-    a.q = q; a.ldq = ldq; a.k = k; a.v = v; a.ldk = ldk; a.out = out; a.ldo = ldo;
-    a.B = B; a.Bkv = Bkv; a.H = H; a.Nq = Nq; a.Nk = Nk; a.D = D;
-    if (fp8 && dtype != DSIM_BF16) return DSIM_ERR_INVALID;
-    g_attn_last_launch = AttnLaunchRec{};
-    CK(fp8 ? launch_attention_fp8(a, s) : launch_attention(a, dtype, s));
-    DSIM_HIP_CHECK(hipStreamSynchronize(s));
-    if (launched) {
-        const AttnLaunchRec& r = g_attn_last_launch;
-        launched->kind = r.kind; launched->D = r.D; launched->dtype = r.dtype; launched->k80 = r.k80; launched->qit = r.qit;
-        launched->grid = r.grid;
-        const char* dtn = r.dtype == DSIM_F32 ? "f32" : (r.dtype == DSIM_F16 ? "f16" : "bf16");
-        if (r.kind == DSIM_ATTN_FP8) std::snprintf(launched->family, sizeof(launched->family), "attention_fp8_d%d", r.D);
-        else std::snprintf(launched->family, sizeof(launched->family), "attention_%s_d%d%s", dtn, r.D, attn_kind_suffix(r.kind));
-    }
-    return DSIM_OK;
-}
-
-int dsim_op_softmax_rows(const void* x, void* out, int rows, int cols, float scale, int dtype, void* stream) {
-    hipStream_t s = (hipStream_t)stream;
-    if (!x || !out) return DSIM_ERR_INVALID;
-    CK(launch_softmax_rows(x, out, rows, cols, scale, dtype, s));
-    DSIM_HIP_CHECK(hipStreamSynchronize(s));
-    return DSIM_OK;
+    return prof_get(h, i, name, name_cap, flops, bytes, ms);
 }
 
 }  // extern "C"

@@ -57,38 +57,11 @@ __global__ void to_nchw_f32_kernel(const T* __restrict__ x, float* __restrict__ 
     out[(n * Cc + c) * HW + p] = (float)x[i];
 }
 
-struct VWalk {
-    dsim_vae* h;
-    Arena* ar;
-    hipStream_t s;
+struct VWalk : WalkBase<dsim_vae> {
     int n;                  // images
-    bool run;
     void* gn_scratch = nullptr;
+    VWalk(dsim_vae* h, Arena* ar, hipStream_t s, int n, bool run) : WalkBase(h, ar, s, run), n(n) {}
 
-    size_t es() const { return dtype_size(h->dt); }
-    void* alloc_act(size_t elems) { return ar->alloc(elems * es()); }
-
-#define VGET(var, key)                                   \
-    const Packed* var = h->find(key);                    \
-    if (!var) return DSIM_ERR_MISSING_WEIGHT;
-
-    // per-launch HIP-event brackets of a profiled encode (dsim_vae_profile_*), same record format as the U-Net executor's
-    void pbegin(const std::string& name, double flops, double bytes) { if (run && h->profiling) prof_begin(h, s, name, flops, bytes); }
-    void pend() { if (run && h->profiling) prof_end(h, s); }
-    const char* dtn() const { return h->dt == DSIM_F32 ? "f32" : (h->dt == DSIM_F16 ? "f16" : "bf16"); }
-
-    int gemm(GemmArgs& g) {
-        g.zero_page = h->zero_page;
-        if (!run) return DSIM_OK;
-        if (h->profiling) {
-            double fl, by;
-            const std::string nm = gemm_family(g, h->dt, &fl, &by);
-            pbegin(nm, fl, by);
-        }
-        const int st = launch_gemm(g, h->dt, s);
-        pend();
-        return st;
-    }
     int linear(const void* a, int K, const void* w, const float* bias, const void* residual, void* out, int M, int N) {
         GemmArgs g;
         g.A0 = a; g.C0 = K; g.mode = GEMM_LINEAR; g.M = M; g.N = N; g.K = K; g.W = w; g.bias = bias;
@@ -130,15 +103,13 @@ struct VWalk {
         if (!run) return DSIM_OK;
         const int HW = x.H * x.W;
         if (stats) {
-            pbegin(std::string("groupnorm_pre_") + dtn() + "|B" + std::to_string(n) + " HW" + std::to_string(HW) + " C" + std::to_string(x.C), 0.0,
-                   2.0 * n * HW * (double)x.C * es());
+            pbegin_gn(n, HW, x.C, 0, h->cfg.norm_num_groups, true);
             const int st = launch_groupnorm_pre(x.p, x.C, (const float*)g->p, (const float*)b->p, out, n, HW, h->cfg.norm_num_groups, 1e-6f,
                                                 silu, h->dt, gn_scratch, stats, HW / 64, s);
             pend();
             return st;
         }
-        pbegin(std::string("groupnorm_") + dtn() + "|B" + std::to_string(n) + " HW" + std::to_string(HW) + " C" + std::to_string(x.C), 0.0,
-               (double)groupnorm_passes(x.C, 0, HW, h->cfg.norm_num_groups, h->dt) * n * HW * (double)x.C * es());
+        pbegin_gn(n, HW, x.C, 0, h->cfg.norm_num_groups);
         const int st = launch_groupnorm(x.p, x.C, nullptr, 0, (const float*)g->p, (const float*)b->p, out, n, HW,
                                         h->cfg.norm_num_groups, 1e-6f, silu, h->dt, gn_scratch, s);
         pend();
@@ -148,10 +119,10 @@ struct VWalk {
     // in_stats: epilogue statistics of x (from the conv that produced it) for norm1; out_stats: receives those of this block's output
     int resnet(const std::string& p, const Act& x, int Cout, Act* out, const float* in_stats = nullptr, float** out_stats = nullptr) {
         const int Cin = x.C, M = n * x.H * x.W;
-        VGET(n1w, p + "norm1.weight"); VGET(n1b, p + "norm1.bias");
-        VGET(c1w, p + "conv1.weight"); VGET(c1b, p + "conv1.bias");
-        VGET(n2w, p + "norm2.weight"); VGET(n2b, p + "norm2.bias");
-        VGET(c2w, p + "conv2.weight"); VGET(c2b, p + "conv2.bias");
+        WGET(n1w, p + "norm1.weight"); WGET(n1b, p + "norm1.bias");
+        WGET(c1w, p + "conv1.weight"); WGET(c1b, p + "conv1.bias");
+        WGET(n2w, p + "norm2.weight"); WGET(n2b, p + "norm2.bias");
+        WGET(c2w, p + "conv2.weight"); WGET(c2b, p + "conv2.bias");
         out->p = alloc_act((size_t)M * Cout); out->C = Cout; out->H = x.H; out->W = x.W;
         // (the output's statistics buffer outlives this block's scratch: allocated before the mark)
         float* ostat = nullptr;
@@ -175,7 +146,7 @@ struct VWalk {
         CK(gn(t2, n2w, n2b, t3.p, 1, st2));
         const void* res = x.p;
         if (Cin != Cout) {
-            VGET(scw, p + "conv_shortcut.weight"); VGET(scb, p + "conv_shortcut.bias");
+            WGET(scw, p + "conv_shortcut.weight"); WGET(scb, p + "conv_shortcut.bias");
             void* sc = t2.p;                                   // t2 is dead after norm2
             CK(linear(x.p, Cin, scw->p, (const float*)scb->p, nullptr, sc, M, Cout));
             res = sc;
@@ -196,11 +167,11 @@ struct VWalk {
 
     int attention(const std::string& p, const Act& x, Act* out) {
         const int C = x.C, N = x.H * x.W, M = n * N;
-        VGET(gw, p + "group_norm.weight"); VGET(gb, p + "group_norm.bias");
-        VGET(wq, p + "to_q.weight"); VGET(bq, p + "to_q.bias");
-        VGET(wk, p + "to_k.weight"); VGET(bk, p + "to_k.bias");
-        VGET(wv, p + "to_v.weight"); VGET(bv, p + "to_v.bias");
-        VGET(wo, p + "to_out.0.weight"); VGET(bo, p + "to_out.0.bias");
+        WGET(gw, p + "group_norm.weight"); WGET(gb, p + "group_norm.bias");
+        WGET(wq, p + "to_q.weight"); WGET(bq, p + "to_q.bias");
+        WGET(wk, p + "to_k.weight"); WGET(bk, p + "to_k.bias");
+        WGET(wv, p + "to_v.weight"); WGET(bv, p + "to_v.bias");
+        WGET(wo, p + "to_out.0.weight"); WGET(bo, p + "to_out.0.bias");
         out->p = alloc_act((size_t)M * C); out->C = C; out->H = x.H; out->W = x.W;
         const size_t mk = ar->mark();
         char* t = (char*)alloc_act((size_t)M * C);
@@ -258,7 +229,7 @@ struct VWalk {
         const dsim_vae_cfg& c = h->cfg;
         const int nl = c.n_levels, ch0 = c.block_out_channels[0];
         gn_scratch = ar->alloc(groupnorm_scratch_bytes(n, c.norm_num_groups));
-        VGET(ciw, "encoder.conv_in.weight"); VGET(cib, "encoder.conv_in.bias");
+        WGET(ciw, "encoder.conv_in.weight"); WGET(cib, "encoder.conv_in.bias");
         Act x{alloc_act((size_t)n * S * S * ch0), ch0, S, S};
         float* xstat = nullptr;                 // epilogue statistics of x, when its producer made them
         const bool rows = conv_in_rows_applies(c.in_channels, S, ch0);
@@ -285,7 +256,7 @@ struct VWalk {
                 xstat = rstat;
             }
             if (i != nl - 1) {
-                VGET(dw, bp + "downsamplers.0.conv.weight"); VGET(db, bp + "downsamplers.0.conv.bias");
+                WGET(dw, bp + "downsamplers.0.conv.weight"); WGET(db, bp + "downsamplers.0.conv.bias");
                 Act d{alloc_act((size_t)n * (x.H / 2) * (x.W / 2) * co), co, x.H / 2, x.W / 2};
                 CK(conv3(x, dw, (const float*)db->p, nullptr, d.p, co, 2, 0, n, &xstat));
                 x = d;
@@ -300,8 +271,8 @@ struct VWalk {
             CK(attention("encoder.mid_block.attentions.0.", x, &r)); x = r;
             CK(resnet("encoder.mid_block.resnets.1.", x, cm, &r)); x = r;
         }
-        VGET(nw, "encoder.conv_norm_out.weight"); VGET(nb, "encoder.conv_norm_out.bias");
-        VGET(cow, "encoder.conv_out_folded.weight"); VGET(cob, "encoder.conv_out_folded.bias");
+        WGET(nw, "encoder.conv_norm_out.weight"); WGET(nb, "encoder.conv_norm_out.bias");
+        WGET(cow, "encoder.conv_out_folded.weight"); WGET(cob, "encoder.conv_out_folded.bias");
         const int Cm = 2 * c.latent_channels, M = n * x.H * x.W;
         Act t{alloc_act((size_t)M * x.C), x.C, x.H, x.W};
         CK(gn(x, nw, nb, t.p, 1));
@@ -331,28 +302,13 @@ extern "C" {
 int dsim_vae_create(const dsim_vae_cfg* cfg, dsim_vae** out) {
     if (!cfg || !out) return DSIM_ERR_INVALID;
     if (cfg->n_levels < 1 || cfg->n_levels > DSIM_MAX_LEVELS) return DSIM_ERR_INVALID;
-    if (cfg->compute_dtype != DSIM_F32 && cfg->compute_dtype != DSIM_BF16 && cfg->compute_dtype != DSIM_F16) return DSIM_ERR_INVALID;
-    if (dsim_device_count() < 1) return DSIM_ERR_NO_DEVICE;
-    dsim_vae* h = new dsim_vae();
-    h->cfg = *cfg;
-    h->dt = cfg->compute_dtype;
-    if (h->dalloc(256, &h->zero_page) != DSIM_OK || hipMemset(h->zero_page, 0, 256) != hipSuccess) {
-        dsim_vae_destroy(h);
-        return DSIM_ERR_HIP;
-    }
-    *out = h;
-    return DSIM_OK;
+    return handle_create(cfg, out);
 }
 
-void dsim_vae_destroy(dsim_vae* h) {
-    if (!h) return;
-    h->free_all();
-    delete h;
-}
+void dsim_vae_destroy(dsim_vae* h) { delete h; }
 
 int dsim_vae_load_weight(dsim_vae* h, const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim) {
-    if (!h) return DSIM_ERR_INVALID;
-    return h->add_raw(key, dev_ptr, dtype, shape, ndim);
+    return handle_load(h, key, dev_ptr, dtype, shape, ndim);
 }
 
 int dsim_vae_finalize(dsim_vae* h, void* stream) {
@@ -413,13 +369,21 @@ int dsim_vae_finalize(dsim_vae* h, void* stream) {
     return DSIM_OK;
 }
 
+// dry walk of an encode: peak arena bytes
+static int vae_plan(dsim_vae* h, int n_images, int image_size, size_t* peak) {
+    Arena ar;
+    VWalk w{h, &ar, nullptr, n_images, false};
+    CK(w.go(nullptr, image_size, nullptr));
+    *peak = ar.peak;
+    return DSIM_OK;
+}
+
 size_t dsim_vae_workspace_bytes(const dsim_vae* hc, int n_images, int image_size) {
     dsim_vae* h = const_cast<dsim_vae*>(hc);
     if (!h || !h->finalized || n_images < 1 || image_size < (1 << (h->cfg.n_levels - 1))) return 0;
-    Arena ar;
-    VWalk w{h, &ar, nullptr, n_images, false};
-    if (w.go(nullptr, image_size, nullptr) != DSIM_OK) return 0;
-    return ar.peak + 256;
+    size_t peak;
+    if (vae_plan(h, n_images, image_size, &peak) != DSIM_OK) return 0;
+    return peak + 256;
 }
 
 int dsim_vae_encode(dsim_vae* h, const float* images, int n_images, int image_size, float* moments, void* workspace,
@@ -427,31 +391,16 @@ int dsim_vae_encode(dsim_vae* h, const float* images, int n_images, int image_si
     if (!h || !images || !moments || !workspace || n_images < 1) return DSIM_ERR_INVALID;
     if (!h->finalized) return DSIM_ERR_STATE;
     if (image_size % (1 << (h->cfg.n_levels - 1))) return DSIM_ERR_INVALID;
-    Arena ar;
-    ar.dry = false;
-    const uintptr_t b0 = ((uintptr_t)workspace + 255) & ~(uintptr_t)255;
-    const size_t lost = b0 - (uintptr_t)workspace;
-    if (workspace_bytes < lost) return DSIM_ERR_WORKSPACE;
-    ar.base = (char*)b0;
-    ar.cap = workspace_bytes - lost;
-    {
-        Arena plan;
-        VWalk pw{h, &plan, nullptr, n_images, false};
-        CK(pw.go(nullptr, image_size, nullptr));
-        if (plan.peak > ar.cap) return DSIM_ERR_WORKSPACE;
-    }
-    VWalk w{h, &ar, (hipStream_t)stream, n_images, true};
-    CK(w.go(images, image_size, moments));
-    return ar.overflow ? DSIM_ERR_WORKSPACE : DSIM_OK;
+    return run_in_workspace(
+        workspace, workspace_bytes, [&](size_t* peak) { return vae_plan(h, n_images, image_size, peak); },
+        [&](Arena& ar) {
+            VWalk w{h, &ar, (hipStream_t)stream, n_images, true};
+            return w.go(images, image_size, moments);
+        });
 }
 
-int dsim_vae_profile(dsim_vae* h, int enable) {
-    if (!h) return DSIM_ERR_INVALID;
-    h->clear_profile();
-    h->profiling = enable != 0;
-    return DSIM_OK;
-}
-int dsim_vae_profile_count(const dsim_vae* h) { return h ? (int)h->prof.size() : 0; }
+int dsim_vae_profile(dsim_vae* h, int enable) { return prof_enable(h, enable); }
+int dsim_vae_profile_count(const dsim_vae* h) { return prof_count(h); }
 int dsim_vae_profile_get(dsim_vae* h, int i, char* name, int name_cap, double* flops, double* bytes, double* ms) {
     return prof_get(h, i, name, name_cap, flops, bytes, ms);
 }

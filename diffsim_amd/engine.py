@@ -109,12 +109,106 @@ def _cfg_struct(cfg: UNetConfig, dtype: torch.dtype, tap_block: str, tap_layer) 
     return c
 
 
-class UNetEngine:
+class _Handle:
+    """What the executors' Python handles share: one C handle of the dsim_<prefix>_* group (create / load_weight / finalize /
+    destroy / profile*), its workspace arenas, and the search for the largest batch a dry-run planner accepts.  A subclass sets
+    `prefix`, self.L and self.device, then calls _create_and_load."""
+
+    prefix = ""
+
+    def _fn(self, name: str):
+        return getattr(self.L, f"dsim_{self.prefix}_{name}")
+
+    def _create_and_load(self, cfg_struct, state_dict: Dict[str, torch.Tensor], keep=lambda key: True):
+        """Create the handle, lend it every parameter `keep` accepts (on the device, in a dtype the library reads) and pack them."""
+        self._h = C.c_void_p()
+        self._ws_by_stream: Dict[int, torch.Tensor] = {}      # one arena per HIP stream the handle is driven from
+        self._ws = None                                        # the arena of the latest call
+        with torch.cuda.device(self.device):
+            _lib.check(self._fn("create")(C.byref(cfg_struct), C.byref(self._h)), f"dsim_{self.prefix}_create")
+            alive = []                                         # the library borrows the tensors until finalize
+            for k, v in state_dict.items():
+                if not keep(k):
+                    continue
+                t = v.detach()
+                if t.dtype not in _TORCH2DSIM:
+                    t = t.float()
+                t = t.to(self.device).contiguous()
+                alive.append(t)
+                shp = (C.c_int64 * t.ndim)(*t.shape)
+                _lib.check(self._fn("load_weight")(self._h, k.encode(), t.data_ptr(), _TORCH2DSIM[t.dtype], shp, t.ndim),
+                           f"{self.prefix} load_weight({k})")
+            torch.cuda.synchronize(self.device)
+            _lib.check(self._fn("finalize")(self._h, _stream_ptr()), f"dsim_{self.prefix}_finalize")
+            del alive
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self._fn("destroy")(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def profile(self, enable: bool):
+        """HIP-event brackets around every launch of the following forwards (dsim_*_profile); not inside a timed region."""
+        _lib.check(self._fn("profile")(self._h, int(enable)), f"{self.prefix} profile")
+
+    def profile_records(self, detail: bool = False):
+        """[(kernel family, algorithmic flops, algorithmic bytes, ms)] of the forwards run since
+        profile(True); synchronises the device first.  detail=True appends the launch's shape string."""
+        torch.cuda.synchronize(self.device)
+        out = []
+        buf = C.create_string_buffer(160)
+        fl, by, ms = C.c_double(), C.c_double(), C.c_double()
+        for i in range(self._fn("profile_count")(self._h)):
+            _lib.check(self._fn("profile_get")(self._h, i, buf, 160, C.byref(fl), C.byref(by), C.byref(ms)),
+                       f"{self.prefix} profile_get")
+            fam, _, shape = buf.value.decode().partition("|")
+            out.append((fam, fl.value, by.value, ms.value, shape) if detail else (fam, fl.value, by.value, ms.value))
+        return out
+
+    @staticmethod
+    def _largest(fits, upper: int) -> int:
+        """Largest m in [1, upper] with fits(m), 0 if none; fits is monotone (a dry-run planner: workspace bytes > 0)."""
+        if not fits(1):
+            return 0
+        if fits(upper):
+            return upper
+        lo, hi = 1, upper
+        while hi - lo > 1:
+            mid = (lo + hi) // 2
+            lo, hi = (mid, hi) if fits(mid) else (lo, mid)
+        return lo
+
+    def _arena(self, need: int) -> torch.Tensor:
+        """The calling stream's workspace, grown to `need` bytes.  The entry points keep no per-call state in the handle, so
+        independent batches may be in flight on several streams at once (one host thread): each stream gets its own arena."""
+        sid = _stream_ptr()
+        ws = self._ws_by_stream.get(sid)
+        if ws is None or ws.numel() < need:
+            self._ws_by_stream.pop(sid, None)
+            ws = self._ws = None                            # the old arena is freed before its replacement exists
+            self._arena_replaced()
+            ws = self._ws_by_stream[sid] = torch.empty(need, dtype=torch.uint8, device=self.device)
+        self._ws = ws
+        return ws
+
+    def _arena_replaced(self):
+        """An arena is about to be freed: whatever holds its addresses goes too."""
+
+
+class UNetEngine(_Handle):
     """One handle = one (config, compute dtype, tap) triple with its own packed weights.
 
     Replaces ``self.unet(...)`` + the attention pre-hook of the reference
     (diffsim/diffsim_pipeline.py:213-221, diffsim/diffsim.py:43-56, 122-145).
     """
+
+    prefix = "unet"
 
     def __init__(self, cfg: UNetConfig, state_dict: Dict[str, torch.Tensor], dtype: torch.dtype = torch.bfloat16,
                  target_block: str = "up_blocks", target_layer: int = 0, device: str = "cuda:0"):
@@ -125,26 +219,9 @@ class UNetEngine:
             raise _lib.DsimError("no GPU visible: the DiffSim engine runs only on the HIP device")
         self.cfg, self.dtype, self.device = cfg, dtype, torch.device(device)
         self.target_block, self.target_layer = target_block, target_layer
-        self._h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            cs = _cfg_struct(cfg, dtype, target_block, target_layer)
-            _lib.check(self.L.dsim_unet_create(C.byref(cs), C.byref(self._h)), "dsim_unet_create")
-            keep = []
-            for k, v in state_dict.items():
-                t = v.detach()
-                if t.dtype not in _TORCH2DSIM:
-                    t = t.float()
-                t = t.to(self.device).contiguous()
-                keep.append(t)
-                shp = (C.c_int64 * t.ndim)(*t.shape)
-                _lib.check(self.L.dsim_unet_load_weight(self._h, k.encode(), t.data_ptr(), _TORCH2DSIM[t.dtype],
-                                                        shp, t.ndim), f"load_weight({k})")
-            torch.cuda.synchronize(self.device)
-            _lib.check(self.L.dsim_unet_finalize(self._h, _stream_ptr()), "dsim_unet_finalize")
-            del keep
+        self._create_and_load(_cfg_struct(cfg, dtype, target_block, target_layer), state_dict)
         self.sample_size = cfg.sample_size
         self._refresh_tap_shape()
-        self._ws_by_stream: Dict[int, torch.Tensor] = {}      # one arena per HIP stream the engine is driven from
         self._graphs: Dict[tuple, tuple] = {}
         self.use_graphs = False
         self._profiling = False
@@ -198,17 +275,6 @@ class UNetEngine:
     def view(self, target_block: str, target_layer) -> "TapView":
         return TapView(self, target_block, target_layer)
 
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self.L.dsim_unet_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def set_timestep(self, t: int):
         if self._t != t:
             with torch.cuda.device(self.device):
@@ -229,21 +295,7 @@ class UNetEngine:
 
     def profile(self, enable: bool):
         self._profiling = bool(enable)
-        _lib.check(self.L.dsim_unet_profile(self._h, int(enable)), "profile")
-
-    def profile_records(self, detail: bool = False):
-        """[(kernel family, algorithmic flops, algorithmic bytes, ms)] of the forwards run since
-        profile(True); synchronises the device first.  detail=True appends the launch's shape string."""
-        torch.cuda.synchronize(self.device)
-        out = []
-        buf = C.create_string_buffer(160)
-        fl, by, ms = C.c_double(), C.c_double(), C.c_double()
-        for i in range(self.L.dsim_unet_profile_count(self._h)):
-            _lib.check(self.L.dsim_unet_profile_get(self._h, i, buf, 160, C.byref(fl), C.byref(by), C.byref(ms)),
-                       "profile_get")
-            fam, _, shape = buf.value.decode().partition("|")
-            out.append((fam, fl.value, by.value, ms.value, shape) if detail else (fam, fl.value, by.value, ms.value))
-        return out
+        super().profile(enable)
 
     def workspace_bytes(self, n_images: int, n_ctx: int = 1) -> int:
         """Workspace of one qkv() call over n_images with n_ctx prompt contexts (n_ctx > 1: a context table, whose per-image
@@ -258,28 +310,13 @@ class UNetEngine:
         if n_ctx == 1:
             if getattr(self, "_max_images", None) is not None:
                 return self._max_images
-            self._max_images = self._max_images_search(upper)
+            self._max_images = self._largest(lambda m: self.workspace_bytes(m) > 0, upper)
             return self._max_images
         cache = self.__dict__.setdefault("_max_images_ctx", {})
         key = (self.target_block, str(self.target_layer), self.sample_size)
         if key not in cache:
-            cache[key] = self._max_images_search(upper, 2)
+            cache[key] = self._largest(lambda m: self.workspace_bytes(m, 2) > 0, upper)
         return cache[key]
-
-    def _max_images_search(self, upper: int, n_ctx: int = 1) -> int:
-        fits = lambda m: self.workspace_bytes(m, n_ctx) > 0
-        if not fits(1):
-            return 0
-        lo, hi = 1, upper
-        if fits(hi):
-            return hi
-        while hi - lo > 1:
-            mid = (lo + hi) // 2
-            if fits(mid):
-                lo = mid
-            else:
-                hi = mid
-        return lo
 
     def _check_inputs(self, latents, noise, ctx):
         _require_cuda(latents, noise, ctx)
@@ -302,17 +339,8 @@ class UNetEngine:
             raise _lib.DsimError("SDXL handles take one prompt per call: the pooled prompt embedding enters every resnet")
         return ctx, n_ctx, idx.to(self.device)
 
-    def _arena(self, need: int) -> torch.Tensor:
-        # dsim_unet_qkv keeps no per-call state in the handle, so independent batches may be in flight on several
-        # streams at once (one host thread): each stream gets its own workspace arena
-        sid = _stream_ptr()
-        ws = self._ws_by_stream.get(sid)
-        if ws is None or ws.numel() < need:
-            self._ws_by_stream.pop(sid, None)
-            self._graphs.clear()                 # captured graphs hold the old arena's addresses
-            ws = self._ws_by_stream[sid] = torch.empty(need, dtype=torch.uint8, device=self.device)
-        self._ws = ws
-        return ws
+    def _arena_replaced(self):
+        self._graphs.clear()                 # captured graphs hold the old arena's addresses
 
     def qkv(self, latents: torch.Tensor, noise: torch.Tensor, sqrt_abar: float, sqrt_1m_abar: float,
             ctx: torch.Tensor, out: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None, ctx_index=None):
@@ -371,17 +399,7 @@ class UNetEngine:
         key = (tuple((b, str(l)) for b, l in taps), self.sample_size) + ((("ctx",) if n_ctx > 1 else ()))
         cache = self.__dict__.setdefault("_max_images_taps", {})
         if key not in cache:
-            fits = lambda m: self.taps_workspace_bytes(m, taps, min(int(n_ctx), 2)) > 0
-            if not fits(1):
-                cache[key] = 0
-            elif fits(upper):
-                cache[key] = upper
-            else:
-                lo, hi = 1, upper
-                while hi - lo > 1:
-                    mid = (lo + hi) // 2
-                    lo, hi = (mid, hi) if fits(mid) else (lo, mid)
-                cache[key] = lo
+            cache[key] = self._largest(lambda m: self.taps_workspace_bytes(m, taps, min(int(n_ctx), 2)) > 0, upper)
         return cache[key]
 
     def qkv_taps(self, latents: torch.Tensor, noise: torch.Tensor, sqrt_abar: float, sqrt_1m_abar: float, ctx: torch.Tensor,
@@ -954,9 +972,11 @@ class _EncodeOut:
         self.latent_dist = _LatentDist(moments, sample_dtype)
 
 
-class VAEEncoder:
+class VAEEncoder(_Handle):
     """``AutoencoderKL.encode`` on the HIP engine, with the surface DiffSim.prepare_image_latents needs:
     ``vae.encode(image).latent_dist.sample(generator)`` and ``vae.config.scaling_factor``."""
+
+    prefix = "vae"
 
     def __init__(self, cfg, state_dict: Dict[str, torch.Tensor], dtype: torch.dtype = torch.bfloat16,
                  device: str = "cuda:0"):
@@ -972,34 +992,8 @@ class VAEEncoder:
             c.block_out_channels[i] = v
         c.layers_per_block, c.norm_num_groups = cfg.layers_per_block, cfg.norm_num_groups
         c.compute_dtype = _TORCH2DSIM[dtype]
-        self._h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            _lib.check(self.L.dsim_vae_create(C.byref(c), C.byref(self._h)), "dsim_vae_create")
-            keep = []
-            for k, v in state_dict.items():
-                if not (k.startswith("encoder.") or k.startswith("quant_conv.")):
-                    continue
-                t = v.detach()
-                if t.dtype not in _TORCH2DSIM:
-                    t = t.float()
-                t = t.to(self.device).contiguous()
-                keep.append(t)
-                shp = (C.c_int64 * t.ndim)(*t.shape)
-                _lib.check(self.L.dsim_vae_load_weight(self._h, k.encode(), t.data_ptr(), _TORCH2DSIM[t.dtype], shp, t.ndim),
-                           f"vae load_weight({k})")
-            torch.cuda.synchronize(self.device)
-            _lib.check(self.L.dsim_vae_finalize(self._h, _stream_ptr()), "dsim_vae_finalize")
-            del keep
-        self._ws = None
+        self._create_and_load(c, state_dict, lambda k: k.startswith("encoder.") or k.startswith("quant_conv."))
         self.sample_dtype = torch.float32      # dtype of latent_dist.sample's draw (DiffSim(noise_dtype=...) sets it)
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) is not None and self._h.value:
-                self.L.dsim_vae_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
 
     def moments(self, images: torch.Tensor) -> torch.Tensor:
         """images (n,3,S,S) in [-1,1], any float dtype/device -> moments (n, 2*latent, S/8, S/8) f32 on device."""
@@ -1018,36 +1012,20 @@ class VAEEncoder:
                 need = int(self.L.dsim_vae_workspace_bytes(self._h, m, S))
                 if need == 0:
                     raise _lib.DsimError("unsupported image size for the VAE encoder")
-                if self._ws is None or self._ws.numel() < need:
-                    self._ws = None
-                    self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+                ws = self._arena(need)
                 _lib.check(self.L.dsim_vae_encode(self._h, x[i0:i0 + m].data_ptr(), m, S, out[i0:i0 + m].data_ptr(),
-                                                  self._ws.data_ptr(), self._ws.numel(), _stream_ptr()), "dsim_vae_encode")
+                                                  ws.data_ptr(), ws.numel(), _stream_ptr()), "dsim_vae_encode")
         return out
 
     def encode(self, images: torch.Tensor) -> _EncodeOut:
         return _EncodeOut(self.moments(images), self.sample_dtype)
 
-    def profile(self, enable: bool):
-        """HIP-event brackets around every launch of the following encodes (dsim_vae_profile); not inside a timed region."""
-        _lib.check(self.L.dsim_vae_profile(self._h, int(enable)), "vae profile")
-
-    def profile_records(self, detail: bool = False):
-        """Same records as UNetEngine.profile_records."""
-        torch.cuda.synchronize(self.device)
-        out = []
-        buf = C.create_string_buffer(160)
-        fl, by, ms = C.c_double(), C.c_double(), C.c_double()
-        for i in range(self.L.dsim_vae_profile_count(self._h)):
-            _lib.check(self.L.dsim_vae_profile_get(self._h, i, buf, 160, C.byref(fl), C.byref(by), C.byref(ms)), "vae profile_get")
-            fam, _, shape = buf.value.decode().partition("|")
-            out.append((fam, fl.value, by.value, ms.value, shape) if detail else (fam, fl.value, by.value, ms.value))
-        return out
-
 
 # ---- DiT backbone (SURVEY.md section 8a row a11) ---------------------------------------------------------
-class DiTEngine:
+class DiTEngine(_Handle):
     """One handle = (DiT config, compute dtype, tapped block)."""
+
+    prefix = "dit"
 
     def __init__(self, cfg, state_dict: Dict[str, torch.Tensor], dtype: torch.dtype = torch.bfloat16, target_layer: int = 0,
                  device: str = "cuda:0"):
@@ -1063,25 +1041,7 @@ class DiTEngine:
         self.target_layer = int(target_layer)
         self.tokens = (cfg.input_size // cfg.patch_size) ** 2
         self.heads, self.head_dim = cfg.num_heads, cfg.hidden_size // cfg.num_heads
-        self._h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            _lib.check(self.L.dsim_dit_create(C.byref(c), C.byref(self._h)), "dsim_dit_create")
-            keep = []
-            for k, v in state_dict.items():
-                if k.startswith("final_layer"):
-                    continue
-                t = v.detach()
-                if t.dtype not in _TORCH2DSIM:
-                    t = t.float()
-                t = t.to(self.device).contiguous()
-                keep.append(t)
-                shp = (C.c_int64 * t.ndim)(*t.shape)
-                _lib.check(self.L.dsim_dit_load_weight(self._h, k.encode(), t.data_ptr(), _TORCH2DSIM[t.dtype], shp, t.ndim),
-                           f"dit load_weight({k})")
-            torch.cuda.synchronize(self.device)
-            _lib.check(self.L.dsim_dit_finalize(self._h, _stream_ptr()), "dsim_dit_finalize")
-            del keep
-        self._ws = None
+        self._create_and_load(c, state_dict, lambda k: not k.startswith("final_layer"))
         self._cond = None
 
     def set_tap(self, layer: int):
@@ -1093,29 +1053,6 @@ class DiTEngine:
     def set_attention(self, fp8: bool):
         """fp8 (OCP e4m3) MFMA attention in the DiT blocks (BASELINE config 5); bf16 handles only."""
         _lib.check(self.L.dsim_dit_set_attention(self._h, 1 if fp8 else 0), "dsim_dit_set_attention")
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) is not None and self._h.value:
-                self.L.dsim_dit_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
-
-    def profile(self, enable: bool):
-        _lib.check(self.L.dsim_dit_profile(self._h, int(enable)), "dit profile")
-
-    def profile_records(self, detail: bool = False):
-        """Same records as UNetEngine.profile_records."""
-        torch.cuda.synchronize(self.device)
-        out = []
-        buf = C.create_string_buffer(160)
-        fl, by, ms = C.c_double(), C.c_double(), C.c_double()
-        for i in range(self.L.dsim_dit_profile_count(self._h)):
-            _lib.check(self.L.dsim_dit_profile_get(self._h, i, buf, 160, C.byref(fl), C.byref(by), C.byref(ms)), "dit profile_get")
-            fam, _, shape = buf.value.decode().partition("|")
-            out.append((fam, fl.value, by.value, ms.value, shape) if detail else (fam, fl.value, by.value, ms.value))
-        return out
 
     def set_conditioning(self, t_model: int, y0: int, y1: int):
         if self._cond != (t_model, y0, y1):
@@ -1132,13 +1069,11 @@ class DiTEngine:
             raise _lib.DsimError(f"latents/noise must be float32 (n,{self.cfg.in_channels},{s},{s})")
         with torch.cuda.device(self.device):
             need = int(self.L.dsim_dit_workspace_bytes(self._h, n))
-            if self._ws is None or self._ws.numel() < need:
-                self._ws = None
-                self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            ws = self._arena(need)
             shape = (n, 2, self.tokens, self.cfg.hidden_size)
             q, k, v = (torch.empty(shape, dtype=self.dtype, device=self.device) for _ in range(3))
             _lib.check(self.L.dsim_dit_qkv(self._h, latents.data_ptr(), noise.data_ptr(), float(sa), float(sb), n, q.data_ptr(),
-                                           k.data_ptr(), v.data_ptr(), self._ws.data_ptr(), self._ws.numel(), _stream_ptr()),
+                                           k.data_ptr(), v.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr()),
                        "dsim_dit_qkv")
         return q, k, v
 
@@ -1150,16 +1085,7 @@ class DiTEngine:
 
     def max_images_taps(self, layers, upper: int = 4096) -> int:
         """Largest n_images one qkv_taps call accepts (every activation and tap output < 2 GiB)."""
-        fits = lambda m: self.taps_workspace_bytes(m, layers) > 0
-        if not fits(1):
-            return 0
-        lo, hi = 1, upper
-        if fits(hi):
-            return hi
-        while hi - lo > 1:
-            mid = (lo + hi) // 2
-            lo, hi = (mid, hi) if fits(mid) else (lo, mid)
-        return lo
+        return self._largest(lambda m: self.taps_workspace_bytes(m, layers) > 0, upper)
 
     def qkv_taps(self, latents: torch.Tensor, noise: torch.Tensor, sa: float, sb: float, layers):
         """qkv() at every block of `layers` (any order, no repeats) from ONE forward to the deepest: entry i is bit for bit what
@@ -1177,10 +1103,7 @@ class DiTEngine:
             raise _lib.DsimError(f"unknown taps {layers!r}") from None
         with torch.cuda.device(self.device):
             need = self.taps_workspace_bytes(n, layers)
-            if need and (self._ws is None or self._ws.numel() < need):
-                self._ws = None
-                self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-            ws = self._ws if need else torch.empty(256, dtype=torch.uint8, device=self.device)
+            ws = self._arena(need) if need else torch.empty(256, dtype=torch.uint8, device=self.device)
             shape = (n, 2, self.tokens, self.cfg.hidden_size) if need else (1,)
             outs = [tuple(torch.empty(shape, dtype=self.dtype, device=self.device) for _ in range(3)) for _ in range(nt)]
             ptr = lambda j: (C.c_void_p * nt)(*[o[j].data_ptr() for o in outs])

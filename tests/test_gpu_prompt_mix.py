@@ -157,6 +157,29 @@ def test_one_prompt_path_launches_unchanged():
     assert kv(one, 2 * L) and len(kv(mixed, 8 * L)) == len(kv(one, 2 * L)) and not kv(mixed, 2 * L)
 
 
+def test_profiled_engine_destroyed_with_records_pending():
+    """A handle destroyed while it still holds the records of a profiled forward (HIP events included) releases them with its
+    weights: closing is safe to repeat, and the next handle's features and records are its own."""
+    from diffsim_amd.diffsim import DiffSim
+    cfg = C.TINY
+    lat, nz = _images(cfg, 2)
+    ctx = _ctxs(cfg, 1)[0]
+    want = _ds(cfg, torch.bfloat16).features(lat, nz, ctx, "up_blocks", 0, 600)
+    counts = []
+    for _ in range(2):
+        ds = DiffSim(torch_dtype=torch.bfloat16, device="cuda", unet_config=cfg, state_dict=_sd(cfg))
+        eng = ds.engine("up_blocks", 0)
+        eng.profile(True)
+        got = ds.features(lat, nz, ctx, "up_blocks", 0, 600)
+        counts.append(len(eng.profile_records()))
+        eng.close()                         # records pending: never cleared by profile(False)
+        assert not eng._h.value
+        eng.close()
+        for g, w in zip(got, want):
+            assert torch.equal(g, w)
+    assert counts[0] > 0 and counts[0] == counts[1]
+
+
 def _image_files(root, n, seed):
     from PIL import Image
     g = torch.Generator().manual_seed(seed)

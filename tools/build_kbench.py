@@ -23,7 +23,7 @@ def cc(src):
     return obj
 
 
-only = [s for s in B.SOURCES if s not in ("unet.hip", "vae.hip", "dit.hip")]        # kbench calls the kernels directly
+only = [s for s in B.SOURCES if s not in ("api.hip", "unet.hip", "vae.hip", "dit.hip")]        # kbench calls the kernels directly
 with ThreadPoolExecutor(max_workers=4) as ex:
     objs = list(ex.map(cc, only + ["kbench.hip"]))
 out = os.path.join(ROOT, "tools", "kbench" + TAG)
