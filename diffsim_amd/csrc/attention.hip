@@ -1,129 +1,14 @@
-// Flash-style attention and the fused DiffSim score tail for gfx950.
+// Flash-style attention for gfx950: the U-Net / DiT attention kernels on the tiled core (attn_core.h) and their dispatch.
 //
 //  * attn_kernel     : softmax(Q K^T / sqrt(D)) V for the U-Net's self/cross attention layers
 //                      (replaces F.scaled_dot_product_attention inside diffusers' AttnProcessor2_0,
 //                      restated at /root/reference/diffsim/hacked_attn.py:74-83).
-//  * pair_tail_kernel: the DiffSim score tail -- /root/reference/diffsim/diffsim.py:177-197:
-//                      O_ab = SDPA(Qa,Kb,Vb), O_aa = SDPA(Qa,Ka,Va) (and the b<->a mirror), then
-//                      cosine (or mse) over the flattened (B,H,N,D) tensors.  Both attentions of a
-//                      direction share Q and run in one workgroup; O never leaves registers, only
-//                      three f32 partial sums per workgroup reach HBM and a second fixed-order pass
-//                      folds them (no float atomics => bit-reproducible scores).
-//
-// Tiling: a workgroup = 4 waves = 128 query rows of one (batch, head); each wave owns 32 rows and
-// sweeps the keys in 64-row tiles shared through LDS.
-//   - S^T = K Q^T is computed with K as the MFMA A operand and Q as B ("swapped QK^T"), so a lane
-//     holds one query column of S^T in its accumulator registers: the row max is a per-lane
-//     reduction over registers plus one exchange between the two lane halves, and the accumulator
-//     is directly the B operand of O^T = V^T P^T (no LDS round trip for P).
-//   - Q is pre-scaled by log2(e)/sqrt(D) and the S^T accumulators START at -m (the running row
-//     max), so P = exp2(acc) needs no subtract and no multiply: per score element the VALU does
-//     one v_exp, half a v_max3 and half a v_cvt_pk.  O is rescaled only in tiles where some row's
-//     max grew (exact: alpha == 1 for the other rows).
-//   - The softmax denominator comes out of the PV MFMAs: when the head dim leaves a spare column
-//     in the 32-wide d block (D = 40, 72, 80, 16) the staged V tile carries a column of ones, so
-//     row D of O^T accumulates sum(P) and is rescaled together with O.
-//   - V^T fragments come from the row-major V tile by ds_read_b64_tr_b16 (h16) / ds_read_b32 (f32).
-//   - h16: next tile's global loads are in flight during the current tile's compute (registers
-//     -> double-buffered LDS, one barrier per tile).  f32 parity mode: simple single buffer.
-// h16 path: v_mfma_f32_32x32x16_bf16; fp32 parity path: v_mfma_f32_32x32x2_f32 (exact f32).
-#include "common.h"
-
-#include <type_traits>
+//  * attn_q2_kernel, attn_long_kernel, attn_short_kernel: its forms for two query blocks per wave, long and short key
+//                      sequences; attention_kernel() picks one.  The fused score tails on the same core are tails.hip's.
+#include "attn_core.h"
 
 namespace dsim {
 namespace {
-
-// max over the two 32-lane halves of a wave in every lane: one v_permlane32_swap (gfx950) instead of a ds_bpermute
-// round trip through the LDS pipe -- the softmax branches on this value once per key tile
-__device__ __forceinline__ float max_halves(float x) {
-    const unsigned u = __float_as_uint(x);
-    const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);     // r[0] = lower half, r[1] = upper half, in both
-    return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-
-constexpr int KT = 64;   // kv rows per LDS tile
-
-template <typename T, int D> struct ACfg {
-    static constexpr int ES = sizeof(T);
-    static constexpr int VEC = 16 / ES;
-    static constexpr int NKS = (D + 15) / 16;     // 16-deep k steps over d (QK^T)
-    static constexpr int NDB = (D + 31) / 32;     // 32-wide output blocks over d (PV)
-    static constexpr int DPL = NDB * 32;          // LDS columns (zero padded)
-    static constexpr bool ONES = D < DPL;         // spare column -> ones column gives the row sum
-    // K tile: only the NKS*16 columns QK^T reads (h16); row stride an odd number of 16-B slots (ds_read_b128)
-    static constexpr int DPLK = (ES == 2) ? NKS * 16 : DPL;
-    static constexpr int RS = DPLK * ES + 16;
-    // h16, D = 8 (mod 16): K carries a ones column at d = D and Q carries -m there, so S^T comes out of the MFMAs
-    // already relative to the running max and the accumulators start at the constant 0 (no per-tile register fill).
-    // Any per-row reference cancels in the softmax, so -m rounded to h16 is exact as long as m itself is kept rounded.
-    static constexpr bool KONE = (ES == 2) && (D % 16 == 8);
-    // V tile row stride.  h16: the transposed reads (ds_read_b64_tr_b16) take, per 32-lane half, a
-    // 4-row x 32-column block = 4 rows x 16 dwords; they are conflict-free when the row stride is
-    // 16 or 48 dwords mod 64 (four rows tile the 64 banks).  f32: plain ds_read_b32, same as K.
-    static constexpr int RSV = (ES == 2) ? (((DPL * 2) % 256 == 64 || (DPL * 2) % 256 == 192) ? DPL * 2 : DPL * 2 + 64) : RS;
-    static constexpr int CPR = DPL / VEC;         // 16-B chunks per row
-    static constexpr int TILEK = KT * RS;
-    static constexpr int TILE = (KT * RS + KT * RSV + 1) / 2;   // average, so that 2*TILE = K tile + V tile
-    // double-buffered staging, except for the widest heads: there two tile pairs (83 KB) would leave one workgroup per
-    // CU; a single pair lets a second workgroup hide this one's load latency instead
-    static constexpr bool PIPE = sizeof(T) == 2 && DPL < 160;
-    static constexpr int LDS = (PIPE ? 4 : 2) * TILE;
-    // waves per SIMD the register budget is held to (occupancy hides the serial MFMA/VALU phases)
-    // (4 workgroups per CU need <= 40 KB of LDS each: true for d <= 48 now that the K tile is 48 columns wide)
-    static constexpr int WPS = (sizeof(T) == 2 && DPL <= 64) ? (LDS <= 40 * 1024 ? 4 : 3) : ((sizeof(T) == 2 && DPL <= 96) ? 2 : (sizeof(T) == 2 ? 2 : 1));
-};
-
-struct FragF32 { f32x4 lo, hi; };
-template <typename T> struct FragOf { typedef h16x8 type; };
-template <> struct FragOf<float> { typedef FragF32 type; };
-
-__device__ __forceinline__ void zero_frag(h16x8& f) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) f[i] = (h16)0.0f;
-}
-__device__ __forceinline__ void zero_frag(FragF32& f) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) f.lo[i] = f.hi[i] = 0.f;
-}
-// load 8 consecutive elements and pre-scale them (Q only)
-__device__ __forceinline__ void gload_frag_scaled(h16x8& f, const h16* p, float sc) {
-    const h16x8 t = *reinterpret_cast<const h16x8*>(p);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) f[i] = (h16)((float)t[i] * sc);
-}
-__device__ __forceinline__ void gload_frag_scaled(FragF32& f, const float* p, float sc) {
-    f.lo = *reinterpret_cast<const f32x4*>(p) * sc;
-    f.hi = *reinterpret_cast<const f32x4*>(p + 4) * sc;
-}
-__device__ __forceinline__ void lload_frag(h16x8& f, const char* p) { f = *reinterpret_cast<const h16x8*>(p); }
-__device__ __forceinline__ void lload_frag(FragF32& f, const char* p) {
-    f.lo = *reinterpret_cast<const f32x4*>(p);
-    f.hi = *reinterpret_cast<const f32x4*>(p + 16);
-}
-__device__ __forceinline__ void mma(const h16x8& a, const h16x8& b, f32x16& c) {
-    c = H16_MFMA_32x32x16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ void mma(const FragF32& a, const FragF32& b, f32x16& c) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) c = __builtin_amdgcn_mfma_f32_32x32x2f32(a.lo[j], b.lo[j], c, 0, 0, 0);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) c = __builtin_amdgcn_mfma_f32_32x32x2f32(a.hi[j], b.hi[j], c, 0, 0, 0);
-}
-
-// Q fragments of this wave's 32 query rows (pre-scaled by log2(e)/sqrt(D)), resident in registers.
-template <typename T, int D> struct QFrags { typename FragOf<T>::type f[ACfg<T, D>::NKS]; };
-template <typename T, int D> struct OAcc { f32x16 b[ACfg<T, D>::NDB]; };
-
-template <typename T, int D>
-__device__ __forceinline__ void load_q(QFrags<T, D>& qf, const T* qrow /*row base + h*D*/, int half, float scale_log2) {
-#pragma unroll
-    for (int ks = 0; ks < ACfg<T, D>::NKS; ++ks) {
-        const int d0 = 16 * ks + 8 * half;
-        if (d0 < D) gload_frag_scaled(qf.f[ks], qrow + d0, scale_log2);
-        else zero_frag(qf.f[ks]);
-    }
-}
 
 // One wave's 32 output rows from its O^T accumulators.  A lane owns one query row and, per 32-wide block db, the 8-byte chunks
 // d = 32 db + 8 g + 4 half + (0..3): stored as they lie, a wave instruction writes 16 bytes into each of 32 rows -- 32 cache-line
@@ -175,265 +60,6 @@ __device__ __forceinline__ void store_o_rows(h16* orow, int half, bool wide, F&&
 }
 // 16-byte row segments need 16-byte aligned rows
 __device__ __forceinline__ bool wide_rows(const AttnArgs& p) { return p.ldo % 8 == 0 && ((size_t)p.out & 15) == 0; }
-
-// Staging of one KT-row tile of K and V, split in a load half and a store half so the global loads can be
-// issued a whole tile ahead of the LDS writes.  Only the D real columns move per tile: the zero padding up
-// to DPL columns (and, with ONES, the 1.0 in column D of V) is written ONCE per attend() by tile_init.
-// Rows >= Nk of a ragged tile are never stored: they keep zeros or stale finite values, and their scores
-// are masked to -inf, so they contribute exactly 0.
-template <typename T, int D> struct StageRegs {
-    static constexpr int CPRD = D / ACfg<T, D>::VEC;                 // real 16-B chunks per row
-    static constexpr int N = (KT * CPRD + 255) / 256;
-    u32x4 k[N], v[N];
-    unsigned goff[N];       // element offset of this thread's chunk inside a tile (row * ldk + col)
-    unsigned loff[N];       // byte offset inside the K tile image; the V image uses lvoff
-    unsigned lvoff[N];
-    int row[N];             // tile row, or KT when this thread has no chunk in round i
-};
-
-template <typename T> __device__ __forceinline__ u32x4 one_chunk();
-template <> __device__ __forceinline__ u32x4 one_chunk<h16>() { u32x4 r = {DSIM_H16_ONE_BITS, 0u, 0u, 0u}; return r; }   // 1.0 in element 0
-template <> __device__ __forceinline__ u32x4 one_chunk<float>() { u32x4 r = {0x3F800000u, 0u, 0u, 0u}; return r; }
-
-template <typename T, int D>
-__device__ __forceinline__ void tile_init(StageRegs<T, D>& sr, char* lds, int ldk, int Nk, int tid) {
-    typedef ACfg<T, D> C;
-    typedef StageRegs<T, D> SR;
-    const u32x4 z = {0u, 0u, 0u, 0u};
-    // zero fill is needed for the padding columns and for the never-stored rows of a ragged last tile
-    if (D < C::DPL || (Nk % KT) != 0)
-        for (int o = tid * 16; o < C::LDS; o += 256 * 16) *reinterpret_cast<u32x4*>(lds + o) = z;
-#pragma unroll
-    for (int i = 0; i < SR::N; ++i) {
-        const int idx = tid + i * 256;
-        const int r = idx / SR::CPRD, c = idx - r * SR::CPRD;
-        sr.row[i] = idx < KT * SR::CPRD ? r : KT;
-        sr.goff[i] = (unsigned)r * (unsigned)ldk + (unsigned)c * C::VEC;
-        sr.loff[i] = (unsigned)(r * C::RS + c * 16);
-        sr.lvoff[i] = (unsigned)(C::TILEK + r * C::RSV + c * 16);
-    }
-    if constexpr (C::ONES) {
-        __syncthreads();
-        constexpr int NBUF = C::PIPE ? 2 : 1;
-        for (int i = tid; i < KT * NBUF; i += 256) {
-            const int buf = i / KT, r = i - buf * KT;
-            *reinterpret_cast<u32x4*>(lds + buf * 2 * C::TILE + C::TILEK + r * C::RSV + (D / C::VEC) * 16) = one_chunk<T>();
-            if constexpr (C::KONE)
-                *reinterpret_cast<u32x4*>(lds + buf * 2 * C::TILE + r * C::RS + (D / C::VEC) * 16) = one_chunk<T>();
-        }
-    }
-}
-
-template <typename T, int D>
-__device__ __forceinline__ void tile_load(StageRegs<T, D>& sr, const T* kb, const T* vb, int ldk, int kv0, int Nk) {
-    typedef StageRegs<T, D> SR;
-    const T* kt = kb + (size_t)kv0 * ldk;
-    const T* vt = vb + (size_t)kv0 * ldk;
-#pragma unroll
-    for (int i = 0; i < SR::N; ++i) {
-        if (kv0 + sr.row[i] < Nk && sr.row[i] < KT) {
-            sr.k[i] = *reinterpret_cast<const u32x4*>(kt + sr.goff[i]);
-            sr.v[i] = *reinterpret_cast<const u32x4*>(vt + sr.goff[i]);
-        }
-    }
-}
-template <typename T, int D>
-__device__ __forceinline__ void tile_store(char* lds, const StageRegs<T, D>& sr, int kv0, int Nk) {
-    typedef StageRegs<T, D> SR;
-#pragma unroll
-    for (int i = 0; i < SR::N; ++i) {
-        if (kv0 + sr.row[i] < Nk && sr.row[i] < KT) {
-            *reinterpret_cast<u32x4*>(lds + sr.loff[i]) = sr.k[i];
-            *reinterpret_cast<u32x4*>(lds + sr.lvoff[i]) = sr.v[i];
-        }
-    }
-}
-
-// One full attention of this wave's 32 query rows against Nk keys.  On return o[db][r] holds the
-// NORMALISED output O^T[d = db*32 + (r&3)+8(r>>2)+4*half][q = lane&31].  All 256 threads of the
-// workgroup must call it together (it contains workgroup barriers).
-// FAST: the running maximum is fixed after key tile 0 -- the later tiles compute P = exp2(S - m) without looking at their
-// scores at all (no row maximum, no re-base test, no rescale: a third of the loop's non-exp vector instructions).  Softmax is
-// invariant to the reference point, so a row whose true maximum lies above m just carries P > 1 and larger sums (f32 / h16
-// have the exponent range for it).  Only if the excess passes ~100 (log2 units) can exp2 overflow; the caller detects that from a
-// non-finite or absurd denominator and re-runs the block with FAST = false (attend_checked).
-template <typename T, int D, bool FAST = false>
-__device__ __forceinline__ void attend(const QFrags<T, D>& qfr, const T* kb, const T* vb, int ldk, int Nk, char* lds,
-                                       OAcc<T, D>& oacc, float* l_out = nullptr) {
-    typedef ACfg<T, D> C;
-    typedef typename FragOf<T>::type Frag;
-    QFrags<T, D> qloc = qfr;    // (KONE writes -m into the spare d = D slot of its own copy)
-    auto& qf = qloc.f;
-    auto& o = oacc.b;
-    const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, l31 = lane & 31;
-#pragma unroll
-    for (int db = 0; db < C::NDB; ++db)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[db][r] = 0.f;
-    float m_run = 0.f;          // running row max (log2 units); meaningful after tile 0 (KONE: a h16 value)
-    f32x16 minit;               // the S^T accumulators' start value: -m_run (KONE: 0, the maximum rides in Q's spare slot)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) minit[r] = 0.f;
-    float l_run = 0.f;          // used only when !ONES
-
-    const int ntiles = (Nk + KT - 1) / KT;
-    StageRegs<T, D> sr;
-    __syncthreads();            // a previous attend() of this workgroup may still be reading the buffers
-    tile_init<T, D>(sr, lds, ldk, Nk, tid);
-    if constexpr (C::PIPE) tile_load<T, D>(sr, kb, vb, ldk, 0, Nk);
-    __syncthreads();
-    char* const lds0 = lds;
-    for (int kt = 0; kt < ntiles; ++kt) {
-        if constexpr (C::PIPE) {
-            // buffer (kt&1) was last read in iteration kt-2; every wave has passed barrier kt-1 since
-            lds = lds0 + (kt & 1) * 2 * C::TILE;
-            tile_store<T, D>(lds, sr, kt * KT, Nk);
-            __syncthreads();
-            if (kt + 1 < ntiles) tile_load<T, D>(sr, kb, vb, ldk, (kt + 1) * KT, Nk);
-        } else {
-            __syncthreads();                               // previous tile fully consumed
-            tile_load<T, D>(sr, kb, vb, ldk, kt * KT, Nk);
-            tile_store<T, D>(lds, sr, kt * KT, Nk);
-            __syncthreads();
-        }
-
-        // ---- S'^T = K Q^T - m for the two 32-row kv blocks (accumulators start at -m) ----------
-        f32x16 s[2];
-#pragma unroll
-        for (int jb = 0; jb < 2; ++jb) {
-            s[jb] = minit;                  // -m in every register (KONE: the constant 0): the first MFMA reads it as its C operand
-            const char* krow = lds + (jb * 32 + l31) * C::RS + half * 8 * C::ES;
-#pragma unroll
-            for (int ks = 0; ks < C::NKS; ++ks) {
-                Frag kf;
-                lload_frag(kf, krow + ks * 16 * C::ES);
-                mma(kf, qf[ks], s[jb]);
-            }
-        }
-        if (kt * KT + KT > Nk) {                           // ragged last tile only
-#pragma unroll
-            for (int jb = 0; jb < 2; ++jb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int kv = kt * KT + jb * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-                    if (kv >= Nk) s[jb][r] = -INFINITY;
-                }
-        }
-        // ---- online softmax (per query column == per lane) ---------------------------------
-        float tmax = -INFINITY;
-        if (!FAST || kt == 0) {
-#pragma unroll
-            for (int jb = 0; jb < 2; ++jb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) tmax = fmaxf(tmax, s[jb][r]);
-            tmax = max_halves(tmax);
-        }
-        // tmax is relative to m_run.  Tile 0 always re-bases; later tiles only when some row's max
-        // grew (the running max settles after a few tiles) -- exact, not a threshold.
-        // (KONE re-bases only past a slack of 0.5, so that rounding m to h16 cannot leave a row just above 0 and
-        // re-trigger on every tile; P <= 1.42 there)
-        constexpr float SLACK = C::KONE ? 0.5f : 0.f;
-        if (kt == 0 || (!FAST && !__all(tmax <= SLACK))) {
-            float delta = kt == 0 ? tmax : fmaxf(tmax, 0.f);
-            if constexpr (C::KONE) {
-                if constexpr (sizeof(T) == 2) {
-                    const float m_new = (float)(h16)(m_run + delta);      // the value Q can carry exactly
-                    delta = m_new - m_run;
-                    m_run = m_new;
-                    if (half == 1) qf[C::NKS - 1][0] = (h16)(-m_new);       // d = D lives in element 0 of the upper half
-                }
-            } else {
-                m_run += delta;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) minit[r] = -m_run;
-            }
-#pragma unroll
-            for (int jb = 0; jb < 2; ++jb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) s[jb][r] -= delta;
-            if (kt != 0) {
-                const float alpha = __builtin_amdgcn_exp2f(-delta);
-                l_run *= alpha;
-#pragma unroll
-                for (int db = 0; db < C::NDB; ++db)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) o[db][r] *= alpha;
-            }
-        }
-#pragma unroll
-        for (int jb = 0; jb < 2; ++jb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) s[jb][r] = __builtin_amdgcn_exp2f(s[jb][r]);
-        if constexpr (!C::ONES) {
-            float psum = 0.f;
-#pragma unroll
-            for (int jb = 0; jb < 2; ++jb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) psum += s[jb][r];
-            l_run += psum;
-        }
-
-        // ---- O^T += V^T P^T ---------------------------------------------------------------
-        const char* vt = lds + C::TILEK;
-        if constexpr (sizeof(T) == 2) {
-            // transposed read: per 16-lane group a 4x16 block; lane 4q+p supplies row q, cols 4p..4p+3
-            const int i16 = lane & 15, g = lane >> 4;
-            const int trow = 4 * (g >> 1) + (i16 >> 2);            // 4*half + q'
-            const int tcol = 16 * (g & 1) + 4 * (i16 & 3);
-#pragma unroll
-            for (int jb = 0; jb < 2; ++jb) {
-#pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2) {
-                    h16x8 pf;
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) pf[j] = (h16)s[jb][8 * s2 + j];
-                    const char* vbase = vt + (jb * 32 + 16 * s2 + trow) * C::RSV + tcol * 2;
-#pragma unroll
-                    for (int db = 0; db < C::NDB; ++db) {
-                        const char* pa = vbase + db * 64;
-                        h16x4 lo = h16_ds_read_tr16_b64((pa));
-                        h16x4 hi = h16_ds_read_tr16_b64((pa + 8 * C::RSV));
-                        h16x8 vf;
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) { vf[j] = lo[j]; vf[4 + j] = hi[j]; }
-                        o[db] = H16_MFMA_32x32x16(vf, pf, o[db], 0, 0, 0);
-                    }
-                }
-            }
-        } else {
-#pragma unroll
-            for (int jb = 0; jb < 2; ++jb) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = jb * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-                    const char* vrow = vt + row * C::RSV + l31 * 4;
-#pragma unroll
-                    for (int db = 0; db < C::NDB; ++db) {
-                        const float a = *reinterpret_cast<const float*>(vrow + db * 128);
-                        o[db] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, s[jb][r], o[db], 0, 0, 0);
-                    }
-                }
-            }
-        }
-    }
-    float l_tot;
-    if constexpr (C::ONES) {
-        // row D of O^T = sum(P): block D/32, in-block row D%32 = (r&3)+8(r>>2)+4*half
-        constexpr int RB = D / 32, RR = D % 32;
-        constexpr int RH = (RR >> 2) & 1, REG = (RR & 3) + 4 * (RR >> 3);
-        const float mine = o[RB][REG];
-        const float other = __shfl_xor(mine, 32);
-        l_tot = (half == RH) ? mine : other;
-    } else {
-        l_tot = l_run + __shfl_xor(l_run, 32);
-    }
-    if (l_out) *l_out = l_tot;
-    const float inv = 1.0f / l_tot;
-#pragma unroll
-    for (int db = 0; db < C::NDB; ++db)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[db][r] *= inv;
-}
 
 // attend() for TWO 32-row query blocks per wave (a workgroup = 256 queries): every K and V^T fragment read from LDS feeds both
 // blocks.  attend() reads one kilobyte of fragments per MFMA -- at full MFMA rate 256 B per clock per CU, twice the LDS port -- so
@@ -1181,248 +807,6 @@ __global__ __launch_bounds__(256, 2) void attn_short_kernel(const AttnArgs p, co
     }
 }
 
-// ---- fused score tail ----------------------------------------------------------------------
-// 16-bit modes (round 5): both SDPA outputs are rounded to the compute dtype before the products -- torch's SDPA returns
-// tensors of the pipeline dtype and the reference's cosine / mse consume those (diffsim.py:177-190); the products and sums stay
-// f32 per workgroup and f64 across them.  The self-attention's output then waits for the cross-attention as packed 16-bit
-// pairs (40 registers at d = 160 instead of 80), which brings d = 160 from 426 registers (one workgroup per CU) under 256: two
-// workgroups per CU.  The f32 parity mode keeps both outputs in f32.
-
-// attend's output in the lane's row, rounded to the compute dtype T (the 16-bit modes convert two values at a time), folded in
-// slot order: s = f(s, db, r, d, x) for every accumulator slot (db, r) whose column d is < D.  (The state goes through f by value:
-// with the current compiler, sums held by reference across the walk move the register allocation of the tail kernels.)
-template <typename T, int D, typename S, typename F>
-__device__ __forceinline__ S fold_rounded(const OAcc<T, D>& acc, int half, S s, F&& f) {
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-#pragma unroll
-    for (int db = 0; db < ACfg<T, D>::NDB; ++db)
-#pragma unroll
-        for (int r = 0; r < 16; r += 2) {
-            T v[2];
-            if constexpr (sizeof(T) == 2) {
-                const h16x2 p = __builtin_convertvector((f32x2){acc.b[db][r], acc.b[db][r + 1]}, h16x2);
-                v[0] = p[0]; v[1] = p[1];
-            } else {
-                v[0] = acc.b[db][r]; v[1] = acc.b[db][r + 1];
-            }
-#pragma unroll
-            for (int e = 0; e < 2; ++e) {
-                const int rr = r + e, d = db * 32 + (rr & 3) + 8 * (rr >> 2) + 4 * half;
-                if (d < D) s = f(s, db, rr, d, v[e]);
-            }
-        }
-    return s;
-}
-
-// attend's normalised output held as plain f32 values: hipcc may otherwise fuse attend's final multiply by 1/l into what consumes
-// it -- into the fp16 rounding (v_fma_mixlo_f16: one rounding instead of f32 then fp16) or into the mse difference (an fma) -- and it
-// does so in some tail kernels and not in others.  Every tail calls it on every attend output, so that pair_tail_body and
-// matrix_tail_kernel round and subtract the same f32 values and a matrix cell equals the pair tail's score bit for bit.
-template <typename T, int D>
-__device__ __forceinline__ void settle(OAcc<T, D>& acc) {
-#pragma unroll
-    for (int db = 0; db < ACfg<T, D>::NDB; ++db)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            if (db * 32 + (r & 3) + 8 * (r >> 2) >= D) continue;      // (no lane holds a column d < D in this slot)
-            float x = acc.b[db][r];
-            asm volatile("" : "+v"(x));
-            acc.b[db][r] = x;
-        }
-}
-
-// the products of the cross output ox (rounded by fold_rounded) against the self output y(db, r, d), in f32: cosine sums
-// dot | x2 | y2 into s0 | s1 | s2, mse the squared difference into s0
-struct TailSums { float s0 = 0.f, s1 = 0.f, s2 = 0.f; };
-template <typename T, int D, typename Y>
-__device__ __forceinline__ TailSums tail_products(const OAcc<T, D>& ox, int half, int mse, Y&& y) {
-    return fold_rounded<T, D>(ox, half, TailSums{}, [&](TailSums s, int db, int r, int d, T xr) {
-        const float x = (float)xr, yv = y(db, r, d);
-        if (mse) { const float df = x - yv; s.s0 = fmaf(df, df, s.s0); }
-        else { s.s0 = fmaf(x, yv, s.s0); s.s1 = fmaf(x, x, s.s1); s.s2 = fmaf(yv, yv, s.s2); }
-        return s;
-    });
-}
-
-// a workgroup's products folded over its 4 waves (shuffles, then the waves in a fixed order) into its partial
-// o[0..3] = (s0, s1, s2, 0); every thread of the workgroup calls it
-__device__ __forceinline__ void store_block_partial(TailSums t, int lane, int wave, float* __restrict__ o) {
-    __shared__ float red[4][4];
-    float s0 = t.s0, s1 = t.s1, s2 = t.s2;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        s0 += __shfl_xor(s0, off);
-        s1 += __shfl_xor(s1, off);
-        s2 += __shfl_xor(s2, off);
-    }
-    if (lane == 0) { red[wave][0] = s0; red[wave][1] = s1; red[wave][2] = s2; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        o[0] = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
-        o[1] = (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]);
-        o[2] = (red[0][2] + red[1][2]) + (red[2][2] + red[3][2]);
-        o[3] = 0.f;
-    }
-}
-
-// One direction of a pair in a 128-query workgroup: the self and the cross attention on the same Q fragments, then their products.
-// The epilogue is pair_tail_kernel's (PER_TOKEN false: one partial per workgroup, [pair][dir][bh][qtile][4] f32) or pair_map_kernel's
-// (PER_TOKEN true: one per query token, [pair][dir][comp][bh][N] f32, comp: dot | x2 | y2, or sqd | - | -).
-// grid (ceil(N/128), B*H, n_pairs*2)
-template <typename T, int D, bool PER_TOKEN>
-__device__ __forceinline__ void pair_tail_body(const T* __restrict__ qg, const T* __restrict__ kg, const T* __restrict__ vg,
-                                               const int32_t* __restrict__ idx_a, const int32_t* __restrict__ idx_b, int B, int H, int N,
-                                               float scale_log2, int mse, float* __restrict__ part) {
-    typedef ACfg<T, D> C;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, l31 = lane & 31;
-    const int bh = blockIdx.y, b = bh / H, h = bh - b * H;
-    const int pair = blockIdx.z >> 1, dir = blockIdx.z & 1;
-    const int ia = idx_a[pair], ib = idx_b[pair];
-    const int iq = dir ? ib : ia;        // query image (also the "self" keys/values)
-    const int ix = dir ? ia : ib;        // the other image ("cross" keys/values)
-    const int ld = H * D;
-    const size_t img = (size_t)B * N * ld;
-    const int q = blockIdx.x * 128 + wave * 32 + l31;
-    const int qc = q < N ? q : N - 1;
-    const size_t boff = (size_t)b * N * ld + h * D;
-    QFrags<T, D> qf;
-    load_q<T, D>(qf, qg + iq * img + boff + (size_t)qc * ld, half, scale_log2);
-    TailSums t;
-    if constexpr (sizeof(T) == 2) {
-        typedef float f32x2 __attribute__((ext_vector_type(2)));
-        h16x2 osp[C::NDB][8];           // the self-attention's output, rounded to the compute dtype, two values per register
-        {
-            OAcc<T, D> osa;
-            attend<T, D>(qf, kg + iq * img + boff, vg + iq * img + boff, ld, N, smem, osa);
-            settle<T, D>(osa);
-#pragma unroll
-            for (int db = 0; db < C::NDB; ++db)
-#pragma unroll
-                for (int r = 0; r < 16; r += 2) {
-                    osp[db][r >> 1] = __builtin_convertvector((f32x2){osa.b[db][r], osa.b[db][r + 1]}, h16x2);
-                    asm volatile("" : "+v"(osp[db][r >> 1]));          // (pinned: the f32 accumulators die here, before the second attention)
-                }
-        }
-        OAcc<T, D> oxa;
-        attend<T, D>(qf, kg + ix * img + boff, vg + ix * img + boff, ld, N, smem, oxa);
-        settle<T, D>(oxa);
-        if (q < N) t = tail_products<T, D>(oxa, half, mse, [&](int db, int r, int) { return (float)osp[db][r >> 1][r & 1]; });
-    } else {
-        OAcc<T, D> osa, oxa;
-        attend<T, D>(qf, kg + iq * img + boff, vg + iq * img + boff, ld, N, smem, osa);
-        attend<T, D>(qf, kg + ix * img + boff, vg + ix * img + boff, ld, N, smem, oxa);
-        settle<T, D>(osa);
-        settle<T, D>(oxa);
-        if (q < N) t = tail_products<T, D>(oxa, half, mse, [&](int db, int r, int) { return osa.b[db][r]; });
-    }
-    if constexpr (PER_TOKEN) {
-        // a row's d values are split between the two lane halves: fold them, then the first half stores the row (128 B per wave and
-        // component, no atomics)
-        const float s0 = t.s0 + __shfl_xor(t.s0, 32);
-        const float s1 = t.s1 + __shfl_xor(t.s1, 32);
-        const float s2 = t.s2 + __shfl_xor(t.s2, 32);
-        if (half == 0 && q < N) {
-            const size_t plane = (size_t)gridDim.y * N;
-            float* o = part + ((size_t)pair * 2 + dir) * 3 * plane + (size_t)bh * N + q;
-            o[0] = s0;
-            if (!mse) { o[plane] = s1; o[2 * plane] = s2; }
-        }
-    } else {
-        store_block_partial(t, lane, wave, part + ((((size_t)pair * 2 + dir) * gridDim.y + bh) * gridDim.x + blockIdx.x) * 4);
-    }
-}
-
-template <typename T, int D>
-__global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void pair_tail_kernel(const T* __restrict__ qg, const T* __restrict__ kg,
-                                                        const T* __restrict__ vg, const int32_t* __restrict__ idx_a,
-                                                        const int32_t* __restrict__ idx_b, int B, int H, int N,
-                                                        float scale_log2, int mse, float* __restrict__ part) {
-    pair_tail_body<T, D, false>(qg, kg, vg, idx_a, idx_b, B, H, N, scale_log2, mse, part);
-}
-
-// one thread per pair: fixed-order f64 fold of the partials, then cosine / mse and the mean of
-// the two directions (diffsim.py:187-197; F.cosine_similarity eps = 1e-8)
-__global__ void pair_finish_kernel(const float* __restrict__ part, int n_pairs, int nblk, int mse, double count,
-                                   float* __restrict__ out, int32_t* __restrict__ status) {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n_pairs) return;
-    double res = 0.0;
-    for (int dir = 0; dir < 2; ++dir) {
-        double a = 0.0, x2 = 0.0, y2 = 0.0;
-        const float* o = part + ((size_t)p * 2 + dir) * nblk * 4;
-        for (int i = 0; i < nblk; ++i) { a += o[4 * i]; x2 += o[4 * i + 1]; y2 += o[4 * i + 2]; }
-        if (mse) res += a / count;
-        else {
-            const double nx = sqrt(x2), ny = sqrt(y2);
-            res += a / (fmax(nx, 1e-8) * fmax(ny, 1e-8));
-        }
-    }
-    const float sc = (float)(res * 0.5);
-    out[p] = sc;
-    // NaN guard: non-finite features surface here as a non-finite score; report them per pair
-    if (status) status[p] = (sc - sc == 0.0f) ? 0 : 1;
-}
-
-// ---- score matrix ---------------------------------------------------------------------------------------------------------------
-// Every image of set A against every image of set B.  The score of (a, b) needs O_aa and O_bb, which do not depend on the partner: the
-// SELF mode computes each image's once (rounded to the compute dtype as the pair tail rounds it; f32 in the parity mode) into
-// [n][B][N][H*D], and the CROSS mode runs one attention per cell and direction -- O_ab = SDPA(Qa, Kb, Vb) against O_aa read back,
-// O_ba = SDPA(Qb, Ka, Va) against O_bb -- with the pair tail's products, reduction and partial layout [cell][dir][bh][qtile][4], so
-// pair_finish_kernel folds them.  Both modes run the same attend on the same Q fragments as pair_tail_kernel: a cell of an image
-// against itself compares bit-identical tensors, and a cell equals the pair tail's score of the same two images.
-// grid  self: (ceil(N/128), B*H, n_a + n_b);  cross: (ceil(N/128) * n_cells * 2, B*H)
-struct MatArgs {
-    const void* q[2]; const void* k[2]; const void* v[2];      // set A, set B: [n][B][N][H*D]
-    void* self[2];                                              // the sets' self outputs, same layout
-    int n_a, n_b, B, H, N;
-};
-template <typename T, int D>
-__global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void matrix_tail_kernel(const MatArgs p, float scale_log2, int mse, int self_mode,
-                                                                                     float* __restrict__ part) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, l31 = lane & 31;
-    const int bh = blockIdx.y, b = bh / p.H, h = bh - b * p.H;
-    const int N = p.N, ld = p.H * D;
-    const size_t img = (size_t)p.B * N * ld;
-    const size_t boff = (size_t)b * N * ld + h * D;
-    const int qt = (N + 127) / 128;
-    int qtile, set, iq, ix, cell = 0, dir = 0;
-    if (self_mode) {
-        qtile = blockIdx.x;
-        set = (int)blockIdx.z >= p.n_a;
-        iq = ix = (int)blockIdx.z - (set ? p.n_a : 0);
-    } else {
-        qtile = blockIdx.x % qt;
-        const int cd = blockIdx.x / qt;
-        cell = cd >> 1; dir = cd & 1;
-        const int ia = cell / p.n_b, ib = cell - ia * p.n_b;
-        set = dir;
-        iq = dir ? ib : ia;
-        ix = dir ? ia : ib;
-    }
-    const T* qg = (const T*)p.q[set];
-    const T* kg = (const T*)p.k[set ^ (self_mode ? 0 : 1)];
-    const T* vg = (const T*)p.v[set ^ (self_mode ? 0 : 1)];
-    T* so = (T*)p.self[set] + iq * img + boff;
-    const int q = qtile * 128 + wave * 32 + l31;
-    const int qc = q < N ? q : N - 1;
-    QFrags<T, D> qf;
-    load_q<T, D>(qf, qg + iq * img + boff + (size_t)qc * ld, half, scale_log2);
-    OAcc<T, D> oa;
-    attend<T, D>(qf, kg + ix * img + boff, vg + ix * img + boff, ld, N, smem, oa);
-    settle<T, D>(oa);
-    if (self_mode) {
-        if (q < N) fold_rounded<T, D>(oa, half, 0, [&](int, int, int, int d, T y) { so[(size_t)q * ld + d] = y; return 0; });  // (no state)
-        return;
-    }
-    TailSums t;
-    if (q < N) t = tail_products<T, D>(oa, half, mse, [&](int, int, int d) { return (float)so[(size_t)q * ld + d]; });
-    store_block_partial(t, lane, wave, part + ((((size_t)cell * 2 + dir) * gridDim.y + bh) * qt + qtile) * 4);
-}
-
-inline float scale_log2_of(int D) { return (1.0f / sqrtf((float)D)) * 1.4426950408889634f; }
-
 // (AttnKernel, the kernels launch_attention starts: common.h)
 
 // fewest keys that take the fixed-reference softmax: long key sequences (>= 1024 keys: the 64 x 64 and 32 x 32 self-attentions)
@@ -1448,6 +832,15 @@ AttnKernel attention_kernel(const AttnArgs& a, int dtype) {
     return a.Nk >= ATTN_FAST_MIN ? AttnKernel::Fast : AttnKernel::Exact;
 }
 
+// launch_lds for an attention kernel (arguments: a, the softmax scale, then xargs) and, once it is in the stream, the thread's launch record
+// (kind, k80, qit go into the record only: a kernel that takes qit gets it once more, as its xargs)
+template <auto Kern, typename T, int D, typename... X>
+int launch_attn_rec(const AttnArgs& a, dim3 grid, int lds_bytes, hipStream_t s, int kind, int k80, int qit, X... xargs) {
+    const int st = launch_lds<Kern>(grid, dim3(256), lds_bytes, s, a, scale_log2_of(D), xargs...);
+    if (st == DSIM_OK) g_attn_last_launch = AttnLaunchRec{kind, D, sizeof(T) == 2 ? DSIM_H16 : DSIM_F32, k80, qit, (int)grid.x};
+    return st;
+}
+
 // launches the tiled kernel `kind` names (every kind but P160); the `if constexpr` guards only keep kernels from being instantiated
 // for a (T, D) that attention_kernel never sends to them, and such a pair returns DSIM_ERR_INVALID
 template <typename T, int D>
@@ -1471,84 +864,38 @@ int launch_attn_d(const AttnArgs& a, AttnKernel kind, hipStream_t s) {
                 while (qit > 1 && (long)((nvb + qit - 1) / qit) * a.H * a.Bkv < want) qit >>= 1;
                 const int nch = (nvb + qit - 1) / qit;
                 const dim3 g(nch * a.H * a.Bkv);
-                if (kind == AttnKernel::ShortK80) {
-                    static DeviceOnce onces;
-                    auto kern = attn_short_kernel<D, true>;
-                    CK_ONCE(onces, kern, LDSS);
-                    hipLaunchKernelGGL(kern, g, dim3(256), LDSS, s, a, scale_log2_of(D), qit);
-                    g_attn_last_launch = AttnLaunchRec{DSIM_ATTN_SHORT_K80, D, DSIM_H16, 1, qit, (int)g.x};
-                } else {
-                    static DeviceOnce onces;
-                    auto kern = attn_short_kernel<D, false>;
-                    CK_ONCE(onces, kern, LDSS);
-                    hipLaunchKernelGGL(kern, g, dim3(256), LDSS, s, a, scale_log2_of(D), qit);
-                    g_attn_last_launch = AttnLaunchRec{DSIM_ATTN_SHORT, D, DSIM_H16, 0, qit, (int)g.x};
-                }
-                DSIM_HIP_CHECK(hipGetLastError());
-                return DSIM_OK;
+                if (kind == AttnKernel::ShortK80) return launch_attn_rec<attn_short_kernel<D, true>, T, D>(a, g, LDSS, s, DSIM_ATTN_SHORT_K80, 1, qit, /* kernel argument: */ qit);
+                return launch_attn_rec<attn_short_kernel<D, false>, T, D>(a, g, LDSS, s, DSIM_ATTN_SHORT, 0, qit, /* kernel argument: */ qit);
             }
             break;
         case AttnKernel::Long:
             if constexpr (sizeof(T) == 2 && D == 40) {
                 constexpr int LDS3 = 3 * 2 * C::TILE;           // the 3-deep tile ring
+                const dim3 gl(((a.Nq + 255) / 256) * a.H * a.B);
 #ifdef DSIM_DEVTOOLS
                 switch (g_attn_dbg) {
-#define X(d) case d: { static DeviceOnce o; auto k = attn_long_kernel<D, d>; CK_ONCE(o, k, LDS3); hipLaunchKernelGGL(k, dim3(((a.Nq + 255) / 256) * a.H * a.B), dim3(256), LDS3, s, a, scale_log2_of(D)); DSIM_HIP_CHECK(hipGetLastError()); return DSIM_OK; }
+#define X(d) case d: return launch_attn_rec<attn_long_kernel<D, d>, T, D>(a, gl, LDS3, s, DSIM_ATTN_LONG, 0, 0);
                     X(8) X(32) X(64) X(96)
 #undef X
                     default: break;
                 }
 #endif
-                static DeviceOnce once2;
-                auto kern = attn_long_kernel<D, 0>;
-                CK_ONCE(once2, kern, LDS3);
-                const dim3 gl(((a.Nq + 255) / 256) * a.H * a.B);
-                hipLaunchKernelGGL(kern, gl, dim3(256), LDS3, s, a, scale_log2_of(D));
-                g_attn_last_launch = AttnLaunchRec{DSIM_ATTN_LONG, D, DSIM_H16, 0, 0, (int)gl.x};
-                DSIM_HIP_CHECK(hipGetLastError());
-                return DSIM_OK;
+                return launch_attn_rec<attn_long_kernel<D, 0>, T, D>(a, gl, LDS3, s, DSIM_ATTN_LONG, 0, 0);
             }
             break;
         case AttnKernel::Q2:
         case AttnKernel::Q2Fast:
             if constexpr (sizeof(T) == 2 && D == 64) {
                 const dim3 grid2(((a.Nq + 255) / 256) * a.H * a.B);
-                if (kind == AttnKernel::Q2Fast) {
-                    static DeviceOnce o1;
-                    auto k = attn_q2_kernel<D, true>;
-                    CK_ONCE(o1, k, C::LDS);
-                    hipLaunchKernelGGL(k, grid2, dim3(256), C::LDS, s, a, scale_log2_of(D));
-                    g_attn_last_launch = AttnLaunchRec{DSIM_ATTN_Q2FAST, D, DSIM_H16, 0, 0, (int)grid2.x};
-                } else {
-                    static DeviceOnce o2;
-                    auto k = attn_q2_kernel<D, false>;
-                    CK_ONCE(o2, k, C::LDS);
-                    hipLaunchKernelGGL(k, grid2, dim3(256), C::LDS, s, a, scale_log2_of(D));
-                    g_attn_last_launch = AttnLaunchRec{DSIM_ATTN_Q2, D, DSIM_H16, 0, 0, (int)grid2.x};
-                }
-                DSIM_HIP_CHECK(hipGetLastError());
-                return DSIM_OK;
+                if (kind == AttnKernel::Q2Fast) return launch_attn_rec<attn_q2_kernel<D, true>, T, D>(a, grid2, C::LDS, s, DSIM_ATTN_Q2FAST, 0, 0);
+                return launch_attn_rec<attn_q2_kernel<D, false>, T, D>(a, grid2, C::LDS, s, DSIM_ATTN_Q2, 0, 0);
             }
             break;
         case AttnKernel::Fast:
         case AttnKernel::Exact: {
             const dim3 grid(((a.Nq + 127) / 128) * a.H * a.B);
-            constexpr int edt = sizeof(T) == 2 ? DSIM_H16 : DSIM_F32;
-            if (kind == AttnKernel::Fast) {
-                static DeviceOnce oncef;
-                auto kern = attn_kernel<T, D, true>;
-                CK_ONCE(oncef, kern, C::LDS);
-                hipLaunchKernelGGL(kern, grid, dim3(256), C::LDS, s, a, scale_log2_of(D));
-                g_attn_last_launch = AttnLaunchRec{DSIM_ATTN_FAST, D, edt, 0, 0, (int)grid.x};
-            } else {
-                static DeviceOnce once;
-                auto kern = attn_kernel<T, D, false>;
-                CK_ONCE(once, kern, C::LDS);
-                hipLaunchKernelGGL(kern, grid, dim3(256), C::LDS, s, a, scale_log2_of(D));
-                g_attn_last_launch = AttnLaunchRec{DSIM_ATTN_EXACT, D, edt, 0, 0, (int)grid.x};
-            }
-            DSIM_HIP_CHECK(hipGetLastError());
-            return DSIM_OK;
+            if (kind == AttnKernel::Fast) return launch_attn_rec<attn_kernel<T, D, true>, T, D>(a, grid, C::LDS, s, DSIM_ATTN_FAST, 0, 0);
+            return launch_attn_rec<attn_kernel<T, D, false>, T, D>(a, grid, C::LDS, s, DSIM_ATTN_EXACT, 0, 0);
         }
         case AttnKernel::P160:
             break;
@@ -1556,164 +903,9 @@ int launch_attn_d(const AttnArgs& a, AttnKernel kind, hipStream_t s) {
     return DSIM_ERR_INVALID;
 }
 
-// head dims of the supported graphs: SD1.5 40/80/160, SDXL 64, DiT-XL/2 72, test configs 16/32/64
-#define DSIM_FOR_EACH_D(X) X(16) X(32) X(40) X(64) X(72) X(80) X(160)
-
-// f(std::integral_constant<int, D>()) for a head dim D of DSIM_FOR_EACH_D; DSIM_ERR_INVALID for any other
-template <typename F>
-int with_head_dim(int D, F&& f) {
-    switch (D) {
-#define X(d) case d: return f(std::integral_constant<int, d>());
-        DSIM_FOR_EACH_D(X)
-#undef X
-        default: return DSIM_ERR_INVALID;
-    }
-}
-
 template <typename T>
 int launch_attn_t(const AttnArgs& a, AttnKernel kind, hipStream_t s) {
     return with_head_dim(a.D, [&](auto dc) { return launch_attn_d<T, decltype(dc)::value>(a, kind, s); });
-}
-
-template <typename T>
-int launch_tail_t(const void* q, const void* k, const void* v, const int32_t* ia, const int32_t* ib, int n_pairs,
-                  int B, int H, int N, int D, int mse, float* out, void* scratch, hipStream_t s, int32_t* status) {
-    return with_head_dim(D, [&](auto dc) -> int {
-        constexpr int Dc = decltype(dc)::value, LDS = ACfg<T, Dc>::LDS;
-        static DeviceOnce once;
-        auto kern = pair_tail_kernel<T, Dc>;
-        CK_ONCE(once, kern, LDS);
-        const int qt = (N + 127) / 128;
-        hipLaunchKernelGGL(kern, dim3(qt, B * H, n_pairs * 2), dim3(256), LDS, s, (const T*)q, (const T*)k, (const T*)v, ia, ib, B, H,
-                           N, scale_log2_of(Dc), mse, (float*)scratch);
-        hipLaunchKernelGGL(pair_finish_kernel, dim3((n_pairs + 63) / 64), dim3(64), 0, s, (const float*)scratch, n_pairs,
-                           qt * B * H, mse, (double)B * H * N * Dc, out, status);
-        DSIM_HIP_CHECK(hipGetLastError());
-        return DSIM_OK;
-    });
-}
-
-// workspace of the tiled score matrix: [self A | self B | partials], each 256-byte aligned
-size_t mat_self_bytes(int n, int B, int H, int N, int D, int es) { return (((size_t)n * B * N * H * D * es) + 255) & ~(size_t)255; }
-size_t mat_part_bytes(long n_cells, int B, int H, int N) { return (((size_t)n_cells * 2 * B * H * ((N + 127) / 128) * 4 * sizeof(float)) + 255) & ~(size_t)255; }
-
-template <typename T>
-int launch_matrix_t(const void* qa, const void* ka, const void* va, int n_a, const void* qb, const void* kb, const void* vb, int n_b, int B,
-                    int H, int N, int D, int mse, float* out, int32_t* status, void* scratch, hipStream_t s) {
-    MatArgs m;
-    m.q[0] = qa; m.k[0] = ka; m.v[0] = va; m.q[1] = qb; m.k[1] = kb; m.v[1] = vb;
-    m.self[0] = scratch;
-    m.self[1] = (char*)scratch + mat_self_bytes(n_a, B, H, N, D, sizeof(T));
-    m.n_a = n_a; m.n_b = n_b; m.B = B; m.H = H; m.N = N;
-    float* part = (float*)((char*)m.self[1] + mat_self_bytes(n_b, B, H, N, D, sizeof(T)));
-    return with_head_dim(D, [&](auto dc) -> int {
-        constexpr int Dc = decltype(dc)::value, LDS = ACfg<T, Dc>::LDS;
-        static DeviceOnce once;
-        auto kern = matrix_tail_kernel<T, Dc>;
-        CK_ONCE(once, kern, LDS);
-        const int qt = (N + 127) / 128, nc = n_a * n_b;
-        hipLaunchKernelGGL(kern, dim3(qt, B * H, n_a + n_b), dim3(256), LDS, s, m, scale_log2_of(Dc), mse, 1, part);
-        hipLaunchKernelGGL(kern, dim3(qt * nc * 2, B * H), dim3(256), LDS, s, m, scale_log2_of(Dc), mse, 0, part);
-        hipLaunchKernelGGL(pair_finish_kernel, dim3((nc + 63) / 64), dim3(64), 0, s, (const float*)part, nc, qt * B * H, mse,
-                           (double)B * H * N * Dc, out, status);
-        DSIM_HIP_CHECK(hipGetLastError());
-        return DSIM_OK;
-    });
-}
-
-// ---- similarity maps: the score tail kept per token ------------------------------------------------------------------------------
-// The score of direction a->b splits over query tokens: cos(O_ab, O_aa) = sum_i dot_i / (|O_ab| |O_aa|) and
-// mse = sum_i sqd_i / (B H N D), where dot_i / sqd_i sum over the CFG batch, the heads and d at token i.
-// pair_map_kernel is pair_tail_body with the per-token epilogue: pair_tail_kernel's grid, attentions, rounding and products, so that
-// a pair's map contributions sum to its score.
-template <typename T, int D>
-__global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void pair_map_kernel(const T* __restrict__ qg, const T* __restrict__ kg,
-                                                        const T* __restrict__ vg, const int32_t* __restrict__ idx_a,
-                                                        const int32_t* __restrict__ idx_b, int B, int H, int N,
-                                                        float scale_log2, int mse, float* __restrict__ part) {
-    pair_tail_body<T, D, true>(qg, kg, vg, idx_a, idx_b, B, H, N, scale_log2, mse, part);
-}
-
-// one workgroup per pair, both directions: per token, a fixed-order f64 fold of the B*H partials; over tokens, per-thread strided
-// sums and a fixed-order tree.  local: the token's own cosine (|.| of the token's vectors) or mean squared difference; contrib: its
-// share of the direction's score, so that 0.5 (sum contrib[0] + sum contrib[1]) is the pair's score (F.cosine_similarity eps =
-// 1e-8, as pair_finish_kernel)
-constexpr int MAP_FINISH_THREADS = 256;
-__global__ __launch_bounds__(MAP_FINISH_THREADS) void pair_map_finish_kernel(const float* __restrict__ part, int BH, int N, int D, int mse,
-                                                                             float* __restrict__ score, float* __restrict__ local,
-                                                                             float* __restrict__ contrib, int32_t* __restrict__ status) {
-    constexpr int NT = MAP_FINISH_THREADS;
-    __shared__ double red[3][NT];
-    const int p = blockIdx.x, t = threadIdx.x;
-    const size_t plane = (size_t)BH * N;
-    double res = 0.0;
-    for (int dir = 0; dir < 2; ++dir) {
-        const float* pd = part + ((size_t)p * 2 + dir) * 3 * plane;
-        float* lo = local ? local + ((size_t)p * 2 + dir) * N : nullptr;
-        float* co = contrib ? contrib + ((size_t)p * 2 + dir) * N : nullptr;
-        auto fold = [&](int comp, int i) {
-            double a = 0.0;
-            for (int j = 0; j < BH; ++j) a += pd[comp * plane + (size_t)j * N + i];
-            return a;
-        };
-        // pass 1: local, and the direction's squared norms (cosine)
-        double x2t = 0.0, y2t = 0.0;
-        for (int i = t; i < N; i += NT) {
-            const double a = fold(0, i);
-            if (mse) {
-                if (lo) lo[i] = (float)(a / ((double)BH * D));
-            } else {
-                const double x2 = fold(1, i), y2 = fold(2, i);
-                x2t += x2; y2t += y2;
-                if (lo) lo[i] = (float)(a / (fmax(sqrt(x2), 1e-8) * fmax(sqrt(y2), 1e-8)));
-            }
-        }
-        red[1][t] = x2t; red[2][t] = y2t;
-        __syncthreads();
-        for (int s = NT / 2; s > 0; s >>= 1) {
-            if (t < s) { red[1][t] += red[1][t + s]; red[2][t] += red[2][t + s]; }
-            __syncthreads();
-        }
-        const double den = mse ? (double)BH * N * D : fmax(sqrt(red[1][0]), 1e-8) * fmax(sqrt(red[2][0]), 1e-8);
-        // pass 2: contrib (the same fold again: the per-token sums are not kept), and the direction's total
-        double ct = 0.0;
-        for (int i = t; i < N; i += NT) {
-            const double c = fold(0, i) / den;
-            ct += c;
-            if (co) co[i] = (float)c;
-        }
-        __syncthreads();                 // (every thread has read red[1..2][0])
-        red[0][t] = ct;
-        __syncthreads();
-        for (int s = NT / 2; s > 0; s >>= 1) {
-            if (t < s) red[0][t] += red[0][t + s];
-            __syncthreads();
-        }
-        res += red[0][0];
-        __syncthreads();
-    }
-    if (t == 0) {
-        const float sc = (float)(res * 0.5);
-        score[p] = sc;
-        if (status) status[p] = (sc - sc == 0.0f) ? 0 : 1;
-    }
-}
-
-template <typename T>
-int launch_maps_t(const void* q, const void* k, const void* v, const int32_t* ia, const int32_t* ib, int n_pairs, int B, int H, int N,
-                  int D, int mse, float* score, float* local, float* contrib, int32_t* status, void* scratch, hipStream_t s) {
-    return with_head_dim(D, [&](auto dc) -> int {
-        constexpr int Dc = decltype(dc)::value, LDS = ACfg<T, Dc>::LDS;
-        static DeviceOnce once;
-        auto kern = pair_map_kernel<T, Dc>;
-        CK_ONCE(once, kern, LDS);
-        hipLaunchKernelGGL(kern, dim3((N + 127) / 128, B * H, n_pairs * 2), dim3(256), LDS, s, (const T*)q, (const T*)k, (const T*)v, ia,
-                           ib, B, H, N, scale_log2_of(Dc), mse, (float*)scratch);
-        hipLaunchKernelGGL(pair_map_finish_kernel, dim3(n_pairs), dim3(MAP_FINISH_THREADS), 0, s, (const float*)scratch, B * H, N, Dc,
-                           mse, score, local, contrib, status);
-        DSIM_HIP_CHECK(hipGetLastError());
-        return DSIM_OK;
-    });
 }
 
 }  // namespace
@@ -1756,90 +948,6 @@ int launch_attention(const AttnArgs& a, int dtype, hipStream_t s) {
     return DSIM_ERR_INVALID;
 }
 
-size_t pair_score_scratch_bytes(int n_pairs, int B, int H, int N, int D) {
-    const size_t tiled = (size_t)n_pairs * 2 * B * H * ((N + 127) / 128) * 4 * sizeof(float);
-    if (pair_score160_applies(N, D, DSIM_H16)) {          // (dtype-blind: the 16-bit modes' persistent kernel needs the larger workspace)
-        const size_t pers = pair_score160_scratch_bytes(n_pairs, B, H);
-        return pers > tiled ? pers : tiled;
-    }
-    return tiled;
-}
-
-int launch_pair_score(const void* q, const void* k, const void* v, const int32_t* ia, const int32_t* ib,
-                      int n_pairs, int B, int H, int N, int D, int dtype, int similarity, float* out, void* scratch,
-                      size_t scratch_bytes, hipStream_t s, int32_t* status) {
-    if (n_pairs <= 0 || D % 8 || N < 1) return DSIM_ERR_INVALID;
-    if (scratch_bytes < pair_score_scratch_bytes(n_pairs, B, H, N, D)) return DSIM_ERR_WORKSPACE;
-    if (n_pairs * 2 > 65535) return DSIM_ERR_INVALID;
-    if (dtype == DSIM_H16) {
-        if (pair_score160_applies(N, D, DSIM_H16))
-            return launch_pair_score160(q, k, v, ia, ib, n_pairs, B, H, similarity, out, scratch, scratch_bytes, s, status);
-        return launch_tail_t<h16>(q, k, v, ia, ib, n_pairs, B, H, N, D, similarity, out, scratch, s, status);
-    }
-#ifndef DSIM_H16_IS_F16
-    if (dtype == DSIM_F32) return launch_tail_t<float>(q, k, v, ia, ib, n_pairs, B, H, N, D, similarity, out, scratch, s, status);
-    if (dtype == DSIM_F16)
-        return DSIM_F16_TWIN(launch_pair_score(q, k, v, ia, ib, n_pairs, B, H, N, D, dtype, similarity, out, scratch, scratch_bytes, s, status));
-#endif
-    return DSIM_ERR_INVALID;
-}
-
-size_t score_matrix_scratch_bytes(int n_a, int n_b, int B, int H, int N, int D, int dtype) {
-    if (n_a < 1 || n_b < 1 || B < 1 || H < 1 || N < 1 || D < 1) return 0;
-    if ((dtype == DSIM_BF16 || dtype == DSIM_F16) && pair_score160_applies(N, D, DSIM_H16))
-        return score_matrix160_scratch_bytes(n_a, n_b, B, H);           // (the fp16 persistent kernel has the bf16 one's layout)
-    const int es = dtype == DSIM_F32 ? 4 : 2;
-    return mat_self_bytes(n_a, B, H, N, D, es) + mat_self_bytes(n_b, B, H, N, D, es) + mat_part_bytes((long)n_a * n_b, B, H, N);
-}
-
-int launch_score_matrix(const void* qa, const void* ka, const void* va, int n_a, const void* qb, const void* kb, const void* vb, int n_b,
-                        int B, int H, int N, int D, int dtype, int similarity, float* out, int32_t* status, void* scratch,
-                        size_t scratch_bytes, hipStream_t s) {
-    if (n_a < 1 || n_b < 1 || B < 1 || H < 1 || N < 1 || D % 8 || (similarity != 0 && similarity != 1)) return DSIM_ERR_INVALID;
-    if (dtype != DSIM_F32 && dtype != DSIM_BF16 && dtype != DSIM_F16) return DSIM_ERR_INVALID;
-    // 32-bit grid extents and cell indices
-    const long units = (long)n_a * n_b * 2 * ((N + 127) / 128);
-    if (units >= (1l << 31) || (long)n_a * n_b * B * H * 16 >= (1l << 31) || n_a + n_b > 65535) return DSIM_ERR_INVALID;
-    if (scratch_bytes < score_matrix_scratch_bytes(n_a, n_b, B, H, N, D, dtype)) return DSIM_ERR_WORKSPACE;
-    if (dtype == DSIM_H16) {
-        if (pair_score160_applies(N, D, DSIM_H16))
-            return launch_score_matrix160(qa, ka, va, n_a, qb, kb, vb, n_b, B, H, similarity, out, status, scratch, scratch_bytes, s);
-        return launch_matrix_t<h16>(qa, ka, va, n_a, qb, kb, vb, n_b, B, H, N, D, similarity, out, status, scratch, s);
-    }
-#ifndef DSIM_H16_IS_F16
-    if (dtype == DSIM_F32)
-        return launch_matrix_t<float>(qa, ka, va, n_a, qb, kb, vb, n_b, B, H, N, D, similarity, out, status, scratch, s);
-    if (dtype == DSIM_F16)
-        return DSIM_F16_TWIN(launch_score_matrix(qa, ka, va, n_a, qb, kb, vb, n_b, B, H, N, D, dtype, similarity, out, status, scratch, scratch_bytes, s));
-#endif
-    return DSIM_ERR_INVALID;
-}
-
-
-size_t pair_score_maps_scratch_bytes(int n_pairs, int B, int H, int N) {
-    if (n_pairs < 1 || B < 1 || H < 1 || N < 1) return 0;
-    return (size_t)n_pairs * 2 * 3 * B * H * N * sizeof(float);
-}
-
-// per-token maps of the score tail: pair_map_kernel at every shape and dtype (the default tap's persistent kernel keeps no
-// per-token sums)
-int launch_pair_score_maps(const void* q, const void* k, const void* v, const int32_t* ia, const int32_t* ib, int n_pairs, int B, int H,
-                           int N, int D, int dtype, int similarity, float* score, float* local, float* contrib, int32_t* status,
-                           void* scratch, size_t scratch_bytes, hipStream_t s) {
-    if (n_pairs <= 0 || B < 1 || H < 1 || D % 8 || N < 1 || (similarity != 0 && similarity != 1)) return DSIM_ERR_INVALID;
-    if (n_pairs * 2 > 65535 || B * H > 65535) return DSIM_ERR_INVALID;
-    if (scratch_bytes < pair_score_maps_scratch_bytes(n_pairs, B, H, N)) return DSIM_ERR_WORKSPACE;
-    if (dtype == DSIM_H16)
-        return launch_maps_t<h16>(q, k, v, ia, ib, n_pairs, B, H, N, D, similarity, score, local, contrib, status, scratch, s);
-#ifndef DSIM_H16_IS_F16
-    if (dtype == DSIM_F32)
-        return launch_maps_t<float>(q, k, v, ia, ib, n_pairs, B, H, N, D, similarity, score, local, contrib, status, scratch, s);
-    if (dtype == DSIM_F16)
-        return DSIM_F16_TWIN(launch_pair_score_maps(q, k, v, ia, ib, n_pairs, B, H, N, D, dtype, similarity, score, local, contrib, status,
-                                                    scratch, scratch_bytes, s));
-#endif
-    return DSIM_ERR_INVALID;
-}
 }  // namespace DSIM_H16_NS
 
 }  // namespace dsim

@@ -243,15 +243,11 @@ __global__ __launch_bounds__(256, 2) void attn_fp8_kernel(const AttnArgs p, cons
 template <int D>
 int launch_f8(const AttnArgs& a, hipStream_t s) {
     typedef F8Cfg<D> C;
-    static DeviceOnce once;
-    auto kern = attn_fp8_kernel<D>;
-    CK_ONCE(once, kern, C::LDS);
     const float sl2 = (1.0f / sqrtf((float)D)) * 1.4426950408889634f;
     const dim3 g(((a.Nq + 127) / 128) * a.H * a.B);
-    hipLaunchKernelGGL(kern, g, dim3(256), C::LDS, s, a, sl2);
-    g_attn_last_launch = AttnLaunchRec{DSIM_ATTN_FP8, D, DSIM_H16, 0, 0, (int)g.x};
-    DSIM_HIP_CHECK(hipGetLastError());
-    return DSIM_OK;
+    const int st = launch_lds<attn_fp8_kernel<D>>(g, dim3(256), C::LDS, s, a, sl2);
+    if (st == DSIM_OK) g_attn_last_launch = AttnLaunchRec{DSIM_ATTN_FP8, D, DSIM_H16, 0, 0, (int)g.x};
+    return st;
 }
 
 }  // namespace

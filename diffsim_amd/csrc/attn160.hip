@@ -15,7 +15,7 @@
 // inline-asm loads are checked against the exact instruction sequence around them.  A fix in one kernel's core must be repeated
 // in the other two.
 //
-// Why a kernel of its own.  pair_tail_kernel<h16, 160> (attention.hip) gives a 128-query workgroup its own single-buffered
+// Why a kernel of its own.  pair_tail_kernel<h16, 160> (tails.hip) gives a 128-query workgroup its own single-buffered
 // copy of every key tile: 50 % of its wave cycles wait for global loads or barriers and the matrix pipe is 0.2 busy.  The work
 // is MFMA-bound on paper (per 32 x 32 block of S 20 MFMAs = 640 matrix cycles against ~80 vector instructions), so the
 // structure here is built around keeping K / V arriving while the MFMAs run:
@@ -1165,14 +1165,10 @@ bool sdpa160_applies(const AttnArgs& a) {
 
 int launch_sdpa160(const AttnArgs& a, hipStream_t s) {
     const int g = grid160((long)a.B * a.H, 64);
-    static DeviceOnce once;
-    auto kern = sdpa160_kernel;
-    CK_ONCE(once, kern, A_LDS);
-    hipLaunchKernelGGL(kern, dim3(g), dim3(512), A_LDS, s, (const h16*)a.q, (const h16*)a.k, (const h16*)a.v, (h16*)a.out, a.ldq, a.ldk,
-                       a.ldo, a.B, a.H, softmax_c160());
-    g_attn_last_launch = AttnLaunchRec{DSIM_ATTN_P160, A_D, DSIM_H16, 0, 0, g};
-    DSIM_HIP_CHECK(hipGetLastError());
-    return DSIM_OK;
+    const int st = launch_lds<sdpa160_kernel>(dim3(g), dim3(512), A_LDS, s, (const h16*)a.q, (const h16*)a.k, (const h16*)a.v, (h16*)a.out,
+                                              a.ldq, a.ldk, a.ldo, a.B, a.H, softmax_c160());
+    if (st == DSIM_OK) g_attn_last_launch = AttnLaunchRec{DSIM_ATTN_P160, A_D, DSIM_H16, 0, 0, g};
+    return st;
 }
 
 // partial sums + one 80 KB park slab per workgroup (the grid is bounded by 512 workgroups whatever the device, which keeps this
@@ -1216,11 +1212,10 @@ int launch_score_matrix160(const void* qa, const void* ka, const void* va, int n
                            (h16*)(set ? laneb : lanea), set ? n_b : n_a, B, H);
     }
     const int g = grid160((long)n_a * n_b * B * H * 2, 64);
-    static DeviceOnce once;
-    auto kern = matrix_cross160_kernel;
-    CK_ONCE(once, kern, A_LDS);
-    hipLaunchKernelGGL(kern, dim3(g), dim3(512), A_LDS, s, (const h16*)qa, (const h16*)ka, (const h16*)va, (const h16*)lanea, (const h16*)qb,
-                       (const h16*)kb, (const h16*)vb, (const h16*)laneb, n_a, n_b, B, H, softmax_c160(), mse, part);
+    const int st = launch_lds<matrix_cross160_kernel>(dim3(g), dim3(512), A_LDS, s, (const h16*)qa, (const h16*)ka, (const h16*)va,
+                                                      (const h16*)lanea, (const h16*)qb, (const h16*)kb, (const h16*)vb, (const h16*)laneb,
+                                                      n_a, n_b, B, H, softmax_c160(), mse, part);
+    if (st != DSIM_OK) return st;
     hipLaunchKernelGGL(pair_finish160_kernel, dim3(n_a * n_b), dim3(64), 0, s, (const float*)part, B * H * 8, mse,
                        (double)B * H * A_N * A_D, out, status);
     DSIM_HIP_CHECK(hipGetLastError());
@@ -1231,17 +1226,16 @@ int launch_pair_score160(const void* q, const void* k, const void* v, const int3
                          int H, int mse, float* out, void* scratch, size_t scratch_bytes, hipStream_t s, int32_t* status) {
     if (scratch_bytes < pair_score160_scratch_bytes(n_pairs, B, H)) return DSIM_ERR_WORKSPACE;
     const int grid = grid160(2l * n_pairs * B * H, 16);
-    static DeviceOnce once;
-    auto kern = pair_tail160_kernel;
-    CK_ONCE(once, kern, A_LDS);
     const float c = softmax_c160();
 #ifdef DSIM_DEVTOOLS
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), A_LDS, s, (const h16*)q, (const h16*)k, (const h16*)v, ia, ib, n_pairs, B, H, c,
-                       mse, (float*)scratch, (char*)scratch + part160_bytes(n_pairs, B, H), g_tail160_dbg, g_tail160_exp);
+    const int st = launch_lds<pair_tail160_kernel>(dim3(grid), dim3(512), A_LDS, s, (const h16*)q, (const h16*)k, (const h16*)v, ia, ib, n_pairs,
+                                                   B, H, c, mse, (float*)scratch, (char*)scratch + part160_bytes(n_pairs, B, H),
+                                                   g_tail160_dbg, g_tail160_exp);
 #else
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), A_LDS, s, (const h16*)q, (const h16*)k, (const h16*)v, ia, ib, n_pairs, B, H, c,
-                       mse, (float*)scratch, (char*)scratch + part160_bytes(n_pairs, B, H));
+    const int st = launch_lds<pair_tail160_kernel>(dim3(grid), dim3(512), A_LDS, s, (const h16*)q, (const h16*)k, (const h16*)v, ia, ib, n_pairs,
+                                                   B, H, c, mse, (float*)scratch, (char*)scratch + part160_bytes(n_pairs, B, H));
 #endif
+    if (st != DSIM_OK) return st;
     hipLaunchKernelGGL(pair_finish160_kernel, dim3(n_pairs), dim3(64), 0, s, (const float*)scratch, B * H * 8, mse,
                        (double)B * H * A_N * A_D, out, status);
     DSIM_HIP_CHECK(hipGetLastError());

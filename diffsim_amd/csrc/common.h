@@ -8,7 +8,7 @@
 
 namespace dsim {
 
-// The 16-bit compute type.  The kernel sources gemm / gemm_skinny / rowres / attention / attn160 .hip are written against ONE
+// The 16-bit compute type.  The kernel sources gemm / gemm_skinny / rowres / attention / tails / attn160 .hip are written against ONE
 // 16-bit type, h16, and are compiled twice (diffsim_amd/build.py): once with h16 = bf16 (compute dtype DSIM_BF16, the headline
 // mode) and once with -DDSIM_H16_IS_F16, h16 = IEEE fp16 (DSIM_F16: the arithmetic type the reference's drivers run in,
 // /root/reference/cute_main.py:31, diffsim/diffsim.py:82).  Their host entry points (h16_api.h) live in the inline namespace
@@ -22,7 +22,7 @@ typedef _Float16 h16;
 #define DSIM_H16_NS f16
 #define DSIM_H16 DSIM_F16
 #define DSIM_H16_ONE_BITS 0x3C00u
-// fixed-reference softmax (attention.hip attend<FAST>): P = exp2(s - m0) is stored in the 16-bit type; fp16 tops out at 65504, so
+// fixed-reference softmax (attn_core.h attend<FAST>): P = exp2(s - m0) is stored in the 16-bit type; fp16 tops out at 65504, so
 // a row whose sum reaches 3e4 (a single P near the limit, or thousands of keys a few units above tile 0's maximum) takes the exact
 // running-maximum form instead (in bf16 the bound is the f32 exponent range)
 #define DSIM_H16_LSUM_MAX 3.0e4f
@@ -226,7 +226,7 @@ int launch_layernorm_mod(const void* x, const float* scale2, const float* shift2
 // out[r][:] = softmax(x[r][:] * scale) over `cols` (VAE mid-block attention; in place allowed)
 int launch_softmax_rows(const void* x, void* out, int rows, int cols, float scale, int dtype, hipStream_t s);
 
-// attention + fused score tail -- attention.hip
+// attention -- attention.hip (its tiled core, which the score tails of tails.hip share: attn_core.h)
 struct AttnArgs {
     const void* q = nullptr; int ldq = 0;     // [B][Nq] rows of ldq elements, head h at column h*D
     const void* k = nullptr; const void* v = nullptr; int ldk = 0;   // [Bkv][Nk] rows
@@ -324,13 +324,18 @@ struct DeviceOnce {
         return st;
     }
 };
-#define CK_ONCE(once, kern, lds_bytes)                                                                                   \
-    do {                                                                                                                 \
-        const int _st = (once).ensure([&]() -> int {                                                                     \
-            return hipFuncSetAttribute((const void*)(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (lds_bytes)) ==  \
-                           hipSuccess ? DSIM_OK : DSIM_ERR_HIP;                                                          \
-        });                                                                                                              \
-        if (_st != DSIM_OK) return _st;                                                                                  \
-    } while (0)
+// The one way a kernel with opted-in dynamic LDS is launched: Kern's once-flag (one per instantiation, so one per kernel), the
+// attribute, the launch and its error check.  DSIM_OK means the kernel is in the stream; launch records are written after it.
+template <auto Kern, typename... A>
+int launch_lds(dim3 grid, dim3 block, int lds_bytes, hipStream_t s, A... args) {
+    static DeviceOnce once;
+    const int st = once.ensure([&]() -> int {
+        return hipFuncSetAttribute((const void*)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) == hipSuccess ? DSIM_OK
+                                                                                                                            : DSIM_ERR_HIP;
+    });
+    if (st != DSIM_OK) return st;
+    hipLaunchKernelGGL(Kern, grid, block, lds_bytes, s, args...);
+    return hipGetLastError() == hipSuccess ? DSIM_OK : DSIM_ERR_HIP;
+}
 
 }  // namespace dsim

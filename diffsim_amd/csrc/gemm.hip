@@ -943,9 +943,6 @@ int launch_ek(const GemmArgs& a, hipStream_t s) {
     constexpr int NW = WM * WN;
     constexpr int LDS = gemm_lds_bytes<T, BM, BN, GEGLU, WM, WN>();
     static_assert(LDS <= 160 * 1024, "LDS budget");
-    static DeviceOnce once;          // the LDS opt-in is a per-device attribute of the function
-    auto kern = gemm_kernel<T, BM, BN, MODE, GEGLU, WM, WN, EK>;
-    CK_ONCE(once, kern, LDS);
     const int tilesM = (a.M + BM - 1) / BM, tilesN = (a.N + BN - 1) / BN;
     GemmArgs g = a;
     const size_t es = sizeof(T);
@@ -965,10 +962,9 @@ int launch_ek(const GemmArgs& a, hipStream_t s) {
 #ifdef DSIM_DEVTOOLS
     if (g_gemm_exp >> 16) gn = std::min(tilesN, g_gemm_exp >> 16);      // kbench: KB_GEXP = gn << 16 (>= tilesN: row-major order)
 #endif
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), LDS, s, g, tilesN, ntiles, tilesM, gn);
-    DSIM_HIP_CHECK(hipGetLastError());
-    g_gemm_last_launch = GemmLaunchRec{BM, BN, MODE, GEGLU ? 1 : 0, EK, 0};
-    return DSIM_OK;
+    const int st = launch_lds<gemm_kernel<T, BM, BN, MODE, GEGLU, WM, WN, EK>>(dim3(grid), dim3(NW * 64), LDS, s, g, tilesN, ntiles, tilesM, gn);
+    if (st == DSIM_OK) g_gemm_last_launch = GemmLaunchRec{BM, BN, MODE, GEGLU ? 1 : 0, EK, 0};
+    return st;
 }
 
 template <typename T, int BM, int BN, int MODE, bool GEGLU, int WM = 4, int WN = 1, bool SLOW = false>

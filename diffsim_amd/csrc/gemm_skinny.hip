@@ -201,14 +201,10 @@ template <int MODE, bool RES, int SBM, int SBN>
 int launch_skinny_t(const GemmArgs& g, hipStream_t s) {
     constexpr int STG = (SBM + (SBN + 31) / 32 * 32) * SBK_BYTES;
     constexpr int LDS = ((144 * 1024 / STG) < 8 ? (144 * 1024 / STG) : 8) * STG;
-    static DeviceOnce once;
-    auto kern = gemm_skinny_kernel<MODE, RES, SBM, SBN>;
-    CK_ONCE(once, kern, LDS);
     const int tilesM = (g.M + SBM - 1) / SBM, tilesN = (g.N + SBN - 1) / SBN;
-    hipLaunchKernelGGL(kern, dim3(tilesM * tilesN), dim3(SNW * 64), LDS, s, g, tilesN);
-    DSIM_HIP_CHECK(hipGetLastError());
-    g_gemm_last_launch = GemmLaunchRec{SBM, SBN, MODE, 0, RES ? 1 : 0, 1};      // (gemm.hip EK_RES / EK_PLAIN)
-    return DSIM_OK;
+    const int st = launch_lds<gemm_skinny_kernel<MODE, RES, SBM, SBN>>(dim3(tilesM * tilesN), dim3(SNW * 64), LDS, s, g, tilesN);
+    if (st == DSIM_OK) g_gemm_last_launch = GemmLaunchRec{SBM, SBN, MODE, 0, RES ? 1 : 0, 1};      // (gemm.hip EK_RES / EK_PLAIN)
+    return st;
 }
 
 template <int MODE, bool RES>

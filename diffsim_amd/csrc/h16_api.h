@@ -1,5 +1,5 @@
-// The host entry points of the sources that are compiled once per 16-bit type (gemm / gemm_skinny / rowres / attention / attn160
-// .hip).  Declarations only and no include guard: common.h includes this file inside `inline namespace DSIM_H16_NS`, the including
+// The host entry points of the sources that are compiled once per 16-bit type (gemm / gemm_skinny / rowres / attention / tails /
+// attn160 .hip).  Declarations only and no include guard: common.h includes this file inside `inline namespace DSIM_H16_NS`, the including
 // object's own type, and the bf16 objects of the product build once more inside `namespace f16`, which declares the fp16 twins with
 // the same signatures and default arguments.  The argument structs and enums are plain dsim types (common.h, above the include).
 
@@ -22,7 +22,7 @@ size_t ff_stream_bytes(int C);                  // 0: no fused kernel for this w
 int pack_ff_stream(const void* w1_packed, const void* w2_packed, void* stream, int C, hipStream_t s);
 int launch_ff_fused(const FFArgs& a, hipStream_t s);
 
-// attention + fused score tail -- attention.hip
+// attention -- attention.hip; the fused score tail of any shape -- tails.hip
 int launch_attention(const AttnArgs& a, int dtype, hipStream_t s);
 const char* attention_kernel_kind(const AttnArgs& a, int dtype);      // "_p160" / "_short" / "_long" / "_q2" / "_q2fast" / "_fast" / "": the kernel it picks
 // the dsim_attn_kind launch_attention would start for these arguments (host only, launches nothing); DSIM_ERR_INVALID where it
@@ -40,7 +40,7 @@ size_t pair_score160_scratch_bytes(int n_pairs, int B, int H);
 int launch_pair_score160(const void* q, const void* k, const void* v, const int32_t* idx_a, const int32_t* idx_b, int n_pairs, int B,
                          int H, int mse, float* out, void* scratch, size_t scratch_bytes, hipStream_t s, int32_t* status);
 // similarity maps: the score tail kept per query token (pair_map_kernel: pair_tail_kernel's body with a per-token epilogue, any
-// shape and dtype) -- attention.hip
+// shape and dtype) -- tails.hip
 //   score [n_pairs]; local, contrib (each may be NULL) [n_pairs][2][N]; status (may be NULL) [n_pairs]
 size_t pair_score_maps_scratch_bytes(int n_pairs, int B, int H, int N);
 int launch_pair_score_maps(const void* q, const void* k, const void* v, const int32_t* idx_a, const int32_t* idx_b, int n_pairs, int B,
@@ -50,7 +50,7 @@ int launch_pair_score_maps(const void* q, const void* k, const void* v, const in
 bool sdpa160_applies(const AttnArgs& a);
 int launch_sdpa160(const AttnArgs& a, hipStream_t s);
 // score matrix (every image of set A against every image of set B; q, k, v of a set: [n][B][N][H*D]): the self attentions once per
-// image into the workspace, then two cross attentions per cell -- attention.hip (any shape), attn160.hip (the default tap, 16-bit)
+// image into the workspace, then two cross attentions per cell -- tails.hip (any shape), attn160.hip (the default tap, 16-bit)
 size_t score_matrix_scratch_bytes(int n_a, int n_b, int B, int H, int N, int D, int dtype);
 int launch_score_matrix(const void* qa, const void* ka, const void* va, int n_a, const void* qb, const void* kb, const void* vb, int n_b,
                         int B, int H, int N, int D, int dtype, int similarity, float* out, int32_t* status, void* scratch,

@@ -582,18 +582,13 @@ int launch_ff_fused(const FFArgs& a, hipStream_t s) {
     const int grid = ntiles < cu_count() ? ntiles : cu_count();
 #ifdef DSIM_DEVTOOLS
     switch (g_ff_dbg) {
-#define X(d) case d: { static DeviceOnce o; auto k = ff_fused_kernel<d>; CK_ONCE(o, k, RLDS); hipLaunchKernelGGL(k, dim3(grid), dim3(256), RLDS, s, p, ntiles); DSIM_HIP_CHECK(hipGetLastError()); return DSIM_OK; }
+#define X(d) case d: return launch_lds<ff_fused_kernel<d>>(dim3(grid), dim3(256), RLDS, s, p, ntiles);
         X(1) X(2) X(3) X(12) X(13) X(15) X(16) X(31)
 #undef X
         default: break;
     }
 #endif
-    static DeviceOnce once;
-    auto kern = ff_fused_kernel<0>;
-    CK_ONCE(once, kern, RLDS);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), RLDS, s, p, ntiles);
-    DSIM_HIP_CHECK(hipGetLastError());
-    return DSIM_OK;
+    return launch_lds<ff_fused_kernel<0>>(dim3(grid), dim3(256), RLDS, s, p, ntiles);
 }
 
 size_t rowlin_stream_bytes(int C, int N) { return (C == RC && N % 64 == 0 && N <= 960) ? (size_t)N / 32 * LCHB : 0; }
@@ -623,18 +618,13 @@ int launch_rowlin(const RowLinArgs& a, hipStream_t s) {
     const int grid = ntiles < wpc * cu_count() ? ntiles : wpc * cu_count();
 #ifdef DSIM_DEVTOOLS
     switch (g_rl_dbg) {
-#define X(d) case d: { static DeviceOnce o; auto k = rowlin_kernel<d>; CK_ONCE(o, k, LLDS); hipLaunchKernelGGL(k, dim3(grid), dim3(256), LLDS, s, p, ntiles); DSIM_HIP_CHECK(hipGetLastError()); return DSIM_OK; }
+#define X(d) case d: return launch_lds<rowlin_kernel<d>>(dim3(grid), dim3(256), LLDS, s, p, ntiles);
         X(1) X(2) X(4) X(8) X(10) X(15)
 #undef X
         default: break;
     }
 #endif
-    static DeviceOnce once;
-    auto kern = rowlin_kernel<0>;
-    CK_ONCE(once, kern, LLDS);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), LLDS, s, p, ntiles);
-    DSIM_HIP_CHECK(hipGetLastError());
-    return DSIM_OK;
+    return launch_lds<rowlin_kernel<0>>(dim3(grid), dim3(256), LLDS, s, p, ntiles);
 }
 }  // namespace DSIM_H16_NS
 

@@ -1,6 +1,6 @@
-"""A float64 restatement of scaled-dot-product attention (every kernel attention_kernel() in csrc/attention.hip picks, sdpa160_kernel in
-csrc/attn160.hip and attn_fp8_kernel in csrc/attention_fp8.hip) and its per-element error bound, shared by the attention tests.  Not a
-conftest: import it like tests/_gemm64.py.
+"""A float64 restatement of scaled-dot-product attention (every kernel attention_kernel() in csrc/attention.hip picks, on the tiled
+core of csrc/attn_core.h, sdpa160_kernel in csrc/attn160.hip and attn_fp8_kernel in csrc/attention_fp8.hip) and its per-element error
+bound, shared by the attention tests.  Not a conftest: import it like tests/_gemm64.py.
 
 The semantics are the models': O = softmax(q k^T / sqrt(D)) v per (batch element, head), batch element b reading K / V element b % Bkv.
 Operands are taken as the kernel sees them: q, k, v in the compute dtype (bf16 / fp16 / f32), as float64.  The reference is
@@ -13,34 +13,35 @@ THE BOUND.  Per element (query row, column d):
 
   * u_out: the output store's rounding (2^-24 f32, 2^-8 bf16, 2^-11 fp16), applied to the kernel's value, which is ref + E; fp16
     adds 2^-25 absolute (OUT_FLOOR: half its subnormal spacing, for outputs below 2^-14).
-  * T_q, the rounding of the pre-scaled Q: the tiled kernels load Q as round(c q) in the compute type (attention.hip load_q,
-    gload_frag_scaled: line 123; fp8: e4m3, attention_fp8.hip chunk_to_fp8 at line 95).  A relative error delta_p of element p moves
+  * T_q, the rounding of the pre-scaled Q: the tiled kernels load Q as round(c q) in the compute type (attn_core.h load_q /
+    gload_frag_scaled; fp8: e4m3, attn_fp8_kernel's chunk_to_fp8 of the Q row).  A relative error delta_p of element p moves
     every logit t_j by delta_p c q_p k_jp, so the output by ln2 sum_p delta_p c q_p G_pd, G_pd = sum_j w_j k_jp R_jd -- one
     deterministic term per element: T_q = ln2 sum_p err_q(c q_p) |G_pd|, err_q(x) = max(u_q |x|, the type's subnormal floor).  The
-    short-key kernel (attn_short_kernel, exp2(fma(s, c, -m c)) on raw logits: line 1136) and sdpa160_kernel (exp2(fmaf(s, c, mc)):
-    attn160.hip line 728) do NOT round Q: u_q = 0 there.
-  * T_s, the logit's f32 arithmetic: the QK^T accumulation, which in the tiled kernels starts at -m (attend: line 304, the
-    accumulators' start value; KONE, D = 8 mod 16: -m rides in Q's spare column as an exactly representable h16, lines 340-343),
+    short-key kernel (attn_short_kernel, exp2(fma(s, c, -m c)) on raw logits, its load_q_raw) and sdpa160_kernel
+    (exp2(fmaf(s, c, mc))) do NOT round Q: u_q = 0 there.
+  * T_s, the logit's f32 arithmetic: the QK^T accumulation, which in the tiled kernels starts at -m (attend: minit, the
+    accumulators' start value; KONE, D = 8 mod 16: -m rides in Q's spare column as an exactly representable h16, attend's m_new),
     so it is relative to c sum_p |q_p k_jp| + |m|: lam u32 sqrt(D + 1) of that; the exp2 (v_exp_f32, one ulp: 2 u32 / ln2 in log2
     units); the subtraction of the reference, the fma and the scale constant's own f32 rounding: 4 u32 (|t_j| + |t_max|).  Its
     effect is ln2 sum_j w_j e_j |R_jd|.
-  * T_k, T_v (fp8 only): K and V rounded to e4m3 per element (chunk_to_fp8, lines 121-122): independent, mean-zero errors, so
+  * T_k, T_v (fp8 only): K and V rounded to e4m3 per element (chunk_to_fp8 where attn_fp8_kernel stages a tile): independent,
+    mean-zero errors, so
     lam ln2 sqrt(sum_j w_j^2 R_jd^2 sum_p (c q_p err8(k_jp))^2) and lam sqrt(sum_j w_j^2 err8(v_jd)^2).
-  * T_p, P rounded to the MFMA operand type before PV (attend: line 389; attend2 and attend_pipelined2 alike; short kernel: line
-    1152; sdpa160: attn160.hip line 412 / its twins; fp8: pack4_fp8, attention_fp8.hip lines 208-209).  Where the row sum l adds the
-    ROUNDED P -- the ones column of V (ACfg ONES, line 53: D in {16, 40, 72, 80}) or the ones row of V^T (fp8) -- the rounding is a
+  * T_p, P rounded to the MFMA operand type before PV (attend: the pf fragments; attend2, attend_pipelined2, the short
+    kernel and attn160.hip's three kernels alike; fp8: pack4_fp8 into plo / phi).  Where the row sum l adds the
+    ROUNDED P -- the ones column of V (ACfg::ONES: D in {16, 40, 72, 80}) or the ones row of V^T (fp8) -- the rounding is a
     reweighting and moves O by sum_j w_j delta_j R_jd: lam u_P sqrt(sum_j w_j^2 R_jd^2).  Where l adds the unrounded f32 P (D = 32,
-    64, 160: `if constexpr (!C::ONES)` at line 367; sdpa160's psum at attn160.hip line 729) the numerator alone moves:
+    64, 160: the `if constexpr (!C::ONES)` branch of attend; sdpa160_kernel's psum) the numerator alone moves:
     lam u_P sqrt(sum_j w_j^2 v_jd^2).  P may exceed 1 under the fixed-reference softmax (tile 0's maximum: up to DSIM_H16_LSUM_MAX =
-    3e4 in fp16 before attend_checked's fallback, line 597) and under sdpa160's 8-unit rescale threshold: the error is relative all
+    3e4 in fp16 before attend_checked's fallback) and under sdpa160's 8-unit rescale threshold: the error is relative all
     the same.  f32 has no rounding here (u_P = 0).
   * T_floor: fp16's subnormal P (below 2^-14) is rounded with an absolute error up to 2^-25; the row sum in the kernel's frame is
     >= 1/2 (the row maximum's own P is ~1, attend_checked takes anything below 1/4 for a fault), so per key 2^-24 of weight:
-    lam 2^-24 sqrt(sum_j R_jd^2).  fp8's P = p 2^7 (attention_fp8.hip line 142) below e4m3's 2^-6 carries 2^-10 absolute against
+    lam 2^-24 sqrt(sum_j R_jd^2).  fp8's P = p 2^7 (attn_fp8_kernel's PSH) below e4m3's 2^-6 carries 2^-10 absolute against
     l >= 64: lam 2^-16 sqrt(sum_j R_jd^2).
-  * T_acc: the f32 PV and row-sum accumulations over Nk products plus one rescale per key tile (alpha, line 355):
+  * T_acc: the f32 PV and row-sum accumulations over Nk products plus one rescale per key tile (attend's alpha):
     lam u32 sqrt(Nk + Nk / 64 + 2) (sum_j w_j |v_jd| + |O_d|).
-  * T_div: 1 / l and the product (line 431; sdpa160's v_rcp_f32): 3 u32 |O_d|.
+  * T_div: 1 / l and the product (attend's inv; sdpa160's v_rcp_f32): 3 u32 |O_d|.
 lam = LAM = 8 as in tests/_gemm64.py (Higham and Mary, SIAM J. Sci. Comput. 41(5), 2019, Theorem 3.1): independent, mean-zero
 rounding errors sum to at most lam sqrt(n) u of their magnitudes with probability >= 1 - 2n exp(-lam^2 / 2).  It is chosen from that
 statement, not fitted to the kernels.  Second-order terms (products of two roundings, ~1e-6 relative to E) are left out.

@@ -581,7 +581,7 @@ def test_attention_pipelined_kernel_takes_the_exact_fallback(eng, Nq, Nk, dtype)
 @pytest.mark.parametrize("D", [40, 64, 80])
 def test_attention_long_keys_fixed_reference_softmax(eng, D, Nk, dtype):
     """Key sequences >= 1024 take the fixed-reference softmax (the maximum is fixed after key tile 0, later tiles never look
-    at their scores; attention.hip attend<FAST>).  (1) ordinary data; (2) the rare branch, FORCED (cdna_hip_programming.md rule
+    at their scores; attn_core.h attend<FAST>).  (1) ordinary data; (2) the rare branch, FORCED (cdna_hip_programming.md rule
     26): one key far down the sequence scores ~+40 (log2 units) above everything in tile 0 for some rows -> P up to 2^40,
     still exact after normalisation; (3) a key ~+300 above -> exp2 overflows in the fast form, the end-of-block check must
     send the workgroup through the exact running-maximum form.  All against float64 SDPA over the whole tensor."""
