@@ -84,6 +84,9 @@ static inline size_t dtype_size(int dt) { return dt == DSIM_F32 ? 4 : 2; }
 // ---------------------------------------------------------------------------------------------
 enum GemmMode { GEMM_LINEAR = 0, GEMM_CONV3 = 1, GEMM_CONV3P = 2 };   // CONV3P: gemm_kernel's instantiation for power-of-two output maps (never in GemmArgs.mode)
 enum GemmEpi { EPI_NONE = 0, EPI_RESIDUAL = 1, EPI_GEGLU = 2 };
+// gemm_kernel's compile-time epilogue kinds (what they are and why compile-time: gemm.hip, at the kernel)
+enum { EK_PLAIN = 0, EK_RES = 1, EK_SLOW = 2, EK_ACT = 3,     // EK_ACT: tanh-GELU only (DiT Mlp.fc1): no gate, no residual registers
+       EK_PLAIN_GN = 4, EK_RES_GN = 5 };                        // + GroupNorm statistics of the output from the read-back (GemmArgs.gn_part)
 
 struct GemmArgs {
     const void* A0 = nullptr;
@@ -123,11 +126,13 @@ struct GemmArgs {
     unsigned long long* stamps = nullptr;       // -DDSIM_STAMPS builds: per-phase cycle sums of gemm_kernel (7 words)
 #endif
 };
-// The instantiation the calling thread's last GEMM launch ran, written by launch_ek / launch_skinny_t where they launch (one
-// definition, in pack.hip, shared by the bf16 and fp16 objects): what dsim_op_gemm reports, so that tests see the kernel that ran.
+// One gemm_kernel / gemm_skinny_kernel (small = 1) instantiation: tile, GemmMode (GEMM_CONV3P included), GEGLU, epilogue kind EK_*.
+// gemm_plan() fills one for a problem: the plan launch_gemm follows and gemm_family(), gemm_gn_stats_tile() and tools/kbench read.
 struct GemmLaunchRec {
     int bm = 0, bn = 0, mode = -1, geglu = 0, ek = -1, small = 0;
 };
+// The instantiation the calling thread's last GEMM launch ran, written by launch_ek / launch_skinny_t from their template parameters
+// (one definition, in pack.hip, shared by the bf16 and fp16 objects): what dsim_op_gemm reports, so that tests see the kernel that ran.
 extern thread_local GemmLaunchRec g_gemm_last_launch;
 // Rows per alternating block of a GEGLU-interleaved weight with N packed rows (= 8C): 16 where the 320 / 160-column GEMM tiles
 // divide N (their waves hold 160 or 80 packed rows: five or ten 16-row accumulator tiles, an odd count of 32-row blocks); 32 for
@@ -150,8 +155,16 @@ extern int g_rl_dbg;            // ablation mask of the row-resident Linear kern
 extern int g_rl_wpc;            // rowlin_kernel's persistent workgroups per CU (kbench occupancy probe)
 extern int g_ff_stagger;        // its wave de-phasing, in s_nop 7 units per wave index
 #else
-constexpr int g_gemm_skinny = 1, g_gemm_persistent = 1, g_force_bm = 0;
+constexpr int g_gemm_skinny = 1, g_gemm_persistent = 1, g_force_bm = 0, g_gemm_exp = 0, g_skinny_tile = 0;
 #endif
+// The small-batch kernel's tiles, by bm + bn: gemm_skinny.hip compiles exactly these, gemm_plan() (gemm.hip) tries the first
+// kSkinnyChoices in this order
+constexpr int kSkinnyTiles[][2] = {{64, 64}, {64, 80}, {64, 128}, {128, 80}, {128, 128},
+#ifdef DSIM_DEVTOOLS
+                                   {128, 64}, {128, 160},      // kbench sweep only (g_skinny_tile): never the heuristic's choice
+#endif
+};
+constexpr int kSkinnyChoices = 5, kSkinnyCompiled = sizeof(kSkinnyTiles) / sizeof(kSkinnyTiles[0]);
 // weight repack kernels -- pack.hip  (src f32/h16/f16 diffusers layout -> packed compute dtype)
 int pack_linear(const void* src, int src_dtype, void* dst, int dst_dtype, int N, int K,
                 int geglu_interleave, hipStream_t s);                       // [N][K] -> [N][K]; geglu_interleave: 0 or the block rows (16 / 32)
@@ -285,17 +298,19 @@ struct FFArgs {
 // The entry points of the sources compiled once per 16-bit type, in this compilation's own namespace ...
 inline namespace DSIM_H16_NS {
 #include "h16_api.h"
-// Can launch_gemm take GemmArgs.gn_part for this problem?  (16-bit 3x3 conv on a power-of-two output map whose tile is the 256-row
-// one with 128 or 256 columns, N a multiple of it, whole images per 256 rows.)  The executors ask with the geometry of ONE image:
-// where a single image already fills the chip's tiles, every batch size runs the same tiles and the statistics are batch-invariant.
+// Can launch_gemm take GemmArgs.gn_part for this problem?  (16-bit 3x3 conv on a power-of-two output map whose tile has a
+// statistics epilogue, N a multiple of it, whole tiles per image: the plan's answer with gn_part asked for.)  The executors ask with
+// the geometry of ONE image: where a single image already fills the chip's tiles, every batch size runs the same tiles and the
+// statistics are batch-invariant.
 inline bool gemm_gn_stats_tile(const GemmArgs& a, int dtype) {
     if (dtype == DSIM_F32 || a.mode != GEMM_CONV3 || a.epi == EPI_GEGLU || a.bias2 || a.Wout <= 0) return false;
     const int hw = a.Hout * a.Wout;
     if ((a.Wout & (a.Wout - 1)) || (hw & (hw - 1)) || hw % 256) return false;
-    if (!a.force_big && gemm_skinny_applies(a)) return false;
-    int bm, bn;
-    gemm_launch_tile(a, dtype, &bm, &bn);
-    return ((bm == 256 && (bn == 128 || bn == 256)) || (bm == 512 && bn == 128)) && a.N % bn == 0 && hw % bm == 0;
+    float asked = 0.f;                          // (the plan reads gn_part and zero_page as flags, never through them)
+    GemmArgs q = a;
+    q.gn_part = &asked; q.gn_hw = hw; q.zero_page = &asked;
+    GemmLaunchRec plan;
+    return gemm_plan(q, dtype, &plan) == DSIM_OK;
 }
 }  // namespace DSIM_H16_NS
 // ... and, seen from the bf16 objects of the product build, their fp16 twins: DSIM_F16_TWIN(f(args)) is how a bf16 launcher forwards

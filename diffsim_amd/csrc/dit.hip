@@ -102,16 +102,6 @@ struct DWalk : WalkBase<dsim_dit> {
         g.A0 = a; g.C0 = K; g.mode = GEMM_LINEAR; g.M = M; g.N = N; g.K = K; g.W = w; g.bias = bias; g.act = act;
         if (gate) { g.gate = gate; g.gate2 = gate + h->cfg.hidden_size; g.rows_per_batch = T; }
         g.epi = residual ? EPI_RESIDUAL : EPI_NONE; g.residual = residual; g.out = out; g.ldo = N;
-        if (run && h->profiling && (act != 0 || gate != nullptr)) {
-            // the tanh-GELU / adaLN-gate epilogue template (gemm.hip EK_SLOW): families of its own.  Plain / residual projections take
-            // gemm_family()'s name, the small-batch kernel included (the qkv projection of one image, 512 x 3456 x 1152, runs on it)
-            int bm, bn;
-            gemm_launch_tile(g, h->dt, &bm, &bn);
-            const std::string nm = std::string("gemm_") + dtn() + "_" + std::to_string(bm) + "x" + std::to_string(bn) + "_linear" +
-                                   ((act && !gate && !residual) ? "_act" : "_dit") + "|M" + std::to_string(M) + " N" + std::to_string(N) +
-                                   " K" + std::to_string(K);
-            return gemm(g, &nm, 2.0 * M * (double)N * K, (double)es() * ((double)M * K + (double)N * K + (double)M * N * (residual ? 2 : 1)));
-        }
         return gemm(g);
     }
     int lnmod(const void* x, const float* scale2, const float* shift2, void* out, int M, int D, int T) {

@@ -24,6 +24,7 @@
 
 #include <algorithm>
 #include <type_traits>
+#include <utility>
 
 namespace dsim {
 
@@ -32,112 +33,9 @@ int g_force_bm = 0;
 int g_gemm_persistent = 1;
 int g_gemm_exp = 0;
 int g_gemm_skinny = 1;
+int g_skinny_tile = 0;          // kbench: 0 heuristic, else (bm << 8) | bn
 unsigned long long* g_gemm_stamps = nullptr;
 #endif
-inline namespace DSIM_H16_NS {
-// Tile choice.  Small problems: 128-row tiles, 4 waves, two workgroups per CU (160-wide when N
-// allows -- every SD channel count is a multiple of 160 -- else 128; 80-wide where 160 would leave one workgroup per CU).  h16
-// problems with enough 256-row tiles to fill the chip: 256 x 320 (or 256 x 256, or 256 x 192 for the DiT widths) tiles, 8 waves as
-// 4 x 2.  Every choice below was made by timing the neighbouring choice on the shapes it serves (profiles/r04_experiments.txt items
-// 12-15, profiles/r04_small_batch.txt); gemm_launch_tile() maps the result onto the instantiations that exist.
-void gemm_tile_choice(const GemmArgs& a, int* bm, int* bn) {
-    const bool geglu = a.epi == EPI_GEGLU;
-    if (geglu && a.geglu_blk == 16) {                      // 16-row [h | g] blocks: the 320 / 160-column tiles (N % 320 == 0)
-        const long tiles = (long)((a.M + 255) / 256) * (a.N / 320);
-        const bool big = g_force_bm ? g_force_bm == 256 : tiles >= 256;
-        *bm = big ? 256 : 128;
-        *bn = big ? 320 : 160;
-        return;
-    }
-#ifdef DSIM_DEVTOOLS
-    const bool n320 = !geglu && a.N % 320 == 0 && !(g_gemm_exp & 4096), n256 = a.N % 256 == 0;
-#else
-    const bool n320 = !geglu && a.N % 320 == 0, n256 = a.N % 256 == 0;
-#endif
-    // A ragged last 320-wide tile wasting <= 5 % of the columns (DiT: fused qkv N = 3456 = 10.8 tiles, Mlp.fc1 N = 4608 = 14.4) beats 256-wide tiles when the
-    // persistent grid's rounds come out shorter: the 64 x 160 wave tile is 5-10 % faster per column (profiles/r04_experiments.txt
-    // items 13, 15), a round is one tile per CU.  65536 x 3456 x 1152: 11 rounds of 320 against 14 of 256 (0.491 -> 0.467 ms);
-    // at 32768 rows 5.5 -> 6 rounds against 7: the 256-wide tiles stay (0.223 against 0.234 ms).
-    {
-        const int c320 = (a.N + 319) / 320, c256 = (a.N + 255) / 256, tm = (a.M + 255) / 256, cus = cu_count();
-#ifdef DSIM_DEVTOOLS
-        const bool allow = !(g_gemm_exp & 16384) && !(g_gemm_exp & 4096);
-#else
-        const bool allow = true;
-#endif
-        const bool act_only = a.act == 1 && !a.gate && a.epi != EPI_RESIDUAL;      // the epilogue kinds instantiated at 256 x 320
-        const long r320 = ((long)tm * c320 + cus - 1) / cus, r256 = ((long)tm * c256 + cus - 1) / cus;
-        if (allow && !geglu && a.mode == GEMM_LINEAR && !n320 && (act_only || (!a.act && !a.gate)) && (long)tm * c320 >= cus &&
-            (long)c320 * 320 * 20 <= (long)a.N * 21 && r320 * 320 * 19 <= r256 * 256 * 20 && g_force_bm != 128) {
-            *bm = 256; *bn = 320;
-            return;
-        }
-    }
-    // 192-wide: the DiT widths (1152, 3456) that neither 320 nor 256 divides; linear layers only
-    bool n192 = !geglu && a.mode == GEMM_LINEAR && !n320 && !n256 && a.N % 192 == 0;
-    // ... unless a ragged last 256-wide tile wastes at most 5 % of the columns (DiT's fused qkv, N = 3456: 13.5 tiles): the
-    // 64 x 128 wave tile reads 0.75 LDS fragments per MFMA against 0.83 for 64 x 96 (qkv projection 8.67 -> 7.83 ms per step)
-    if (n192 && (long)((a.N + 255) / 256) * 256 * 20 <= (long)a.N * 21 && (long)((a.M + 255) / 256) * ((a.N + 255) / 256) >= 256) {
-        *bm = g_force_bm == 128 ? 128 : 256;
-        *bn = g_force_bm == 128 ? 128 : 256;
-        return;
-    }
-    // 128-wide: the VAE's 128-channel 3x3 convs at 512 x 512 (N = 128 exactly)
-    const bool n128 = !geglu && a.mode == GEMM_CONV3 && a.N == 128;
-    int want256 = 0;
-    if (n128) {
-        const long tiles = (long)((a.M + 255) / 256);
-        if (tiles >= 256 && g_force_bm != 128) { *bm = 256; *bn = 128; return; }
-    }
-    if (n320 || n256 || n192) {
-        const int bnb = n320 ? 320 : (n256 ? 256 : 192);
-        const long tiles = (long)((a.M + 255) / 256) * (a.N / bnb);
-        want256 = tiles >= 256;
-    }
-    if (a.force_big) want256 = (n320 || n256 || n192);
-    if (g_force_bm == 128) want256 = 0;                       // development override (kbench A/B)
-    if (g_force_bm == 256) want256 = (n320 || n256 || n192);
-    if (want256) { *bm = 256; *bn = n320 ? 320 : (n256 ? 256 : 192); return; }
-    *bm = 128;
-    *bn = (a.N % 160 == 0 && !geglu) ? 160 : 128;
-    // 128 x 160 tiles that would leave ONE 4-wave workgroup per CU (<= CUs tiles: 4096 x 1280 = 16 batch elements at the 16 x 16
-    // level): half-width tiles put two on every CU -- conv 4096 x 1280 x 11520 0.163 -> 0.143 ms, x 23040 0.312 -> 0.281; where 128 x 160
-    // already gives two per CU they lose 35 % (profiles/r04_small_batch.txt)
-#ifdef DSIM_DEVTOOLS
-    const bool allow80 = !(g_gemm_exp & 2048);
-#else
-    const bool allow80 = true;
-#endif
-    if (allow80 && *bn == 160 && (long)((a.M + 127) / 128) * (a.N / 160) <= cu_count()) *bn = 80;
-}
-
-// The tile gemm_kernel is launched with (gemm_tile_choice + what the instantiation set allows): the f32 parity mode has
-// 128-row tiles only (its GEGLU with 16-row blocks the 160-column one whatever the size); the gated DiT epilogues exist at
-// 256 x 256, 256 x 192 and 128 x 128, the tanh-GELU-only one also at 256 x 320.  The executors name their profile families by it.
-void gemm_launch_tile(const GemmArgs& a, int dtype, int* bm, int* bn) {
-    gemm_tile_choice(a, bm, bn);
-    const bool slow = a.act != 0 || a.gate != nullptr;
-    const bool act_only = a.act == 1 && !a.gate && a.epi != EPI_RESIDUAL;
-    // N = 128 convs, 16-bit: 512-row tiles (8 waves as 8 x 1, 64 x 128 per wave: 0.375 instead of 0.5 KB of fragment reads per MFMA; -6 % at
-    // 512 x 512 x 128, profiles/r05_experiments.txt item 9) where ONE image alone makes >= 256 of them on a power-of-two map -- so the
-    // choice, and with it every partial sum of the epilogue statistics, is the same at every batch size
-    if (*bm == 256 && *bn == 128 && dtype != DSIM_F32 && a.mode == GEMM_CONV3 && !a.bias2 && g_force_bm != 256) {
-        const long hw = (long)a.Hout * a.Wout;
-        if (hw >= 512L * 256 && !(hw & (hw - 1)) && a.Wout > 0 && !(a.Wout & (a.Wout - 1)) && a.M % hw == 0) *bm = 512;
-    }
-    if (*bm == 512) return;
-    bool big = *bm == 256 && dtype != DSIM_F32;
-    if (big && slow && *bn == 320 && !act_only) big = false;
-    if (!big) {
-        // (a 320-column choice the f32 mode cannot run falls back to 160 columns, not 128: N % 320 == 0 there, and the one-launch
-        //  tapped q | k | v needs the tile width to divide out_split, a multiple of 320)
-        const bool n160 = *bn == 160 || (*bn == 320 && !slow) || (a.epi == EPI_GEGLU && a.geglu_blk == 16);
-        const bool n80 = *bn == 80 && dtype != DSIM_F32 && !slow;          // (16-bit instantiations only; f32: the 160-column tile)
-        *bm = 128;
-        *bn = slow ? 128 : (n80 ? 80 : ((n160 || *bn == 80) ? 160 : 128));
-    }
-}
-}  // namespace DSIM_H16_NS
 
 namespace {
 
@@ -229,9 +127,7 @@ constexpr int gemm_lds_bytes() {
 // BEFORE the epilogue, so its HBM latency and the epilogue's stores overlap instead of serialising per tile.
 // EK (epilogue kind): EK_PLAIN bias only; EK_RES + residual; EK_SLOW the DiT epilogues (tanh-GELU activation, adaLN
 // gate, optional residual decided at run time).  Compile-time, because a run-time residual flag makes hipcc keep
-// every prefetched residual register in scratch, and the DiT math would add its register pressure to all users.
-enum { EK_PLAIN = 0, EK_RES = 1, EK_SLOW = 2, EK_ACT = 3,     // EK_ACT: tanh-GELU only (DiT Mlp.fc1): no gate, no residual registers
-       EK_PLAIN_GN = 4, EK_RES_GN = 5 };                        // + GroupNorm statistics of the output from the read-back (GemmArgs.gn_part)
+// every prefetched residual register in scratch, and the DiT math would add its register pressure to all users.  (The enum: common.h.)
 template <typename T, int BM, int BN, int MODE, bool GEGLU, int WM, int WN, int EKT>
 __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_kernel(const GemmArgs p, const int tilesN, const int ntiles, const int tilesM,
                                                                const int gn) {
@@ -936,55 +832,25 @@ int gemm_fill_extents(GemmArgs& g, size_t es) {
 }
 }  // namespace DSIM_H16_NS
 
+// ---- the plan (gemm_plan(): the one place that decides which instantiation serves a problem) and the launch that follows it ----
 namespace {
 
-template <typename T, int BM, int BN, int MODE, bool GEGLU, int WM, int WN, int EK>
-int launch_ek(const GemmArgs& a, hipStream_t s) {
-    constexpr int NW = WM * WN;
-    constexpr int LDS = gemm_lds_bytes<T, BM, BN, GEGLU, WM, WN>();
-    static_assert(LDS <= 160 * 1024, "LDS budget");
-    const int tilesM = (a.M + BM - 1) / BM, tilesN = (a.N + BN - 1) / BN;
-    GemmArgs g = a;
-    const size_t es = sizeof(T);
-    {
-        const int st = gemm_fill_extents(g, es);
-        if (st != DSIM_OK) return st;
-    }
-#ifdef DSIM_DEVTOOLS
-    g.exp = g_gemm_exp;
-    g.stamps = g_gemm_stamps;
-#endif
-    // persistent grid: as many workgroups as stay resident (LDS-limited), a multiple of 8 so a workgroup keeps its XCD
-    const int ntiles = tilesM * tilesN;
-    const int resident = ((cu_count() * (LDS <= 80 * 1024 ? 2 : 1)) / 8) * 8;
-    const int grid = ntiles <= resident || resident < 8 || !g_gemm_persistent ? ntiles : resident;
-    int gn = gemm_band_width(tilesM, tilesN, (size_t)BN * a.K * es);
-#ifdef DSIM_DEVTOOLS
-    if (g_gemm_exp >> 16) gn = std::min(tilesN, g_gemm_exp >> 16);      // kbench: KB_GEXP = gn << 16 (>= tilesN: row-major order)
-#endif
-    const int st = launch_lds<gemm_kernel<T, BM, BN, MODE, GEGLU, WM, WN, EK>>(dim3(grid), dim3(NW * 64), LDS, s, g, tilesN, ntiles, tilesM, gn);
-    if (st == DSIM_OK) g_gemm_last_launch = GemmLaunchRec{BM, BN, MODE, GEGLU ? 1 : 0, EK, 0};
-    return st;
+// The compiled set of gemm_kernel, stated once: launch_planned() instantiates exactly the kernels it admits (is16: the 16-bit
+// type of this object; else the f32 parity mode) and gemm_plan() refuses a plan outside it
+constexpr bool gemm_compiled(bool is16, int bm, int bn, int mode, bool geglu, int ek) {
+    const bool lin = mode == GEMM_LINEAR, big = is16 && bm == 256;
+    if (geglu) return lin && ek == EK_PLAIN && (big ? bn == 320 || bn == 256 : bm == 128 && (bn == 160 || bn == 128));
+    if (ek >= EK_PLAIN_GN) return is16 && mode == GEMM_CONV3P && ((bm == 256 && (bn == 128 || bn == 256)) || (bm == 512 && bn == 128));
+    if (ek == EK_SLOW || ek == EK_ACT) return lin && (big ? bn == 256 || bn == 192 || (bn == 320 && ek == EK_ACT) : bm == 128 && bn == 128);
+    // EK_PLAIN, EK_RES
+    if (bm == 128) return mode != GEMM_CONV3P && (bn == 160 || bn == 128 || (bn == 80 && is16));
+    if (is16 && bm == 512) return bn == 128 && mode == GEMM_CONV3P;      // 8 waves as 8 x 1
+    return big && (bn == 320 || bn == 256 || bn == (lin ? 192 : 128));   // 8 waves as 4(M) x 2(N), 64-row x (BN/2)-column sub-tiles
 }
-
-template <typename T, int BM, int BN, int MODE, bool GEGLU, int WM = 4, int WN = 1, bool SLOW = false>
-int launch_one(const GemmArgs& a, hipStream_t s) {
-    if constexpr (SLOW) {
-        if (a.act == 1 && !a.gate && a.epi != EPI_RESIDUAL) return launch_ek<T, BM, BN, MODE, GEGLU, WM, WN, EK_ACT>(a, s);
-        return launch_ek<T, BM, BN, MODE, GEGLU, WM, WN, EK_SLOW>(a, s);
-    }
-    if constexpr (!GEGLU && sizeof(T) == 2 && MODE == GEMM_CONV3P && ((BM == 256 && (BN == 128 || BN == 256)) || (BM == 512 && BN == 128))) {
-        // GroupNorm statistics from the epilogue (GemmArgs.gn_part): the VAE's 512 x 512 / 256 x 256 levels on their 256-row tiles
-        if (a.gn_part) {
-            if (a.gn_hw <= 0 || a.gn_hw % BM || a.M % a.gn_hw || a.N % BN || a.bias2) return DSIM_ERR_INVALID;
-            return a.epi == EPI_RESIDUAL ? launch_ek<T, BM, BN, MODE, GEGLU, WM, WN, EK_RES_GN>(a, s)
-                                         : launch_ek<T, BM, BN, MODE, GEGLU, WM, WN, EK_PLAIN_GN>(a, s);
-        }
-    }
-    if (a.gn_part) return DSIM_ERR_INVALID;            // asked for on a tile that has no statistics epilogue (gemm_gn_stats_tile() says which)
-    if constexpr (!GEGLU)
-        if (a.epi == EPI_RESIDUAL) return launch_ek<T, BM, BN, MODE, GEGLU, WM, WN, EK_RES>(a, s);
-    return launch_ek<T, BM, BN, MODE, GEGLU, WM, WN, EK_PLAIN>(a, s);
+constexpr bool skinny_compiled(int bm, int bn) {
+    for (const auto& t : kSkinnyTiles)
+        if (t[0] == bm && t[1] == bn) return true;
+    return false;
 }
 
 int check_args(const GemmArgs& a, int BK) {
@@ -1007,15 +873,136 @@ int check_args(const GemmArgs& a, int BK) {
     return DSIM_OK;
 }
 
-template <typename T>
-int launch_typed(const GemmArgs& a_in, hipStream_t s) {
-    const int st = check_args(a_in, Traits<T>::BK);
+// Tile of the small-batch kernel.  One workgroup runs per CU (the ring fills LDS) and streams (bm + bn) x 128 B per K tile through
+// its CU's L2 -> LDS path, so the tile with the smallest bm + bn that still makes ONE round (<= CUs workgroups) wins -- by less than
+// the byte count says once most CUs stream at the same time (the L2s' aggregate rate, ~8.7 TB/s, takes over).  Measured (tools/kbench
+// KB_SKINNY=2, profiles/r04_small_batch.txt), ms at K = 11520: 1024 x 1280: 64x80 (256 workgroups) 0.094 | 64x128 (160) 0.098 | 128x64
+// 0.105 | 128x128 (80) 0.133 | 64x64 (320: two rounds) 0.143 | gemm_kernel 0.124; 2048 x 1280: 128x80 (256) 0.123 | 128x128 (160) 0.135 |
+// 64x128 (320) 0.192 | gemm_kernel 0.131; 256 / 512 x 1280: 64x64 0.072 against 0.124.
+long skinny_count(const GemmArgs& a, int bm, int bn) { return (long)((a.M + bm - 1) / bm) * ((a.N + bn - 1) / bn); }
+void skinny_tile(const GemmArgs& a, int* bm, int* bn) {
+    if (g_skinny_tile) { *bm = g_skinny_tile >> 8; *bn = g_skinny_tile & 255; return; }
+    for (int i = 0; i < kSkinnyChoices; ++i) {
+        const int* t = kSkinnyTiles[i];
+        if (skinny_count(a, t[0], t[1]) <= cu_count() && (t[1] != 80 || a.N % 80 == 0)) { *bm = t[0]; *bn = t[1]; return; }
+    }
+    *bm = 128; *bn = 128;
+}
+
+// Does the small-batch kernel take this problem?  Problems too small to fill the chip: 64 x 64 tiles behind a deep LDS ring, the same
+// arithmetic bit for bit (gemm_skinny.hip).  Plain / residual epilogues of the 16-bit modes with a K loop long enough for the
+// ring to matter, when gemm_kernel's grid (128-row tiles) would occupy at most a quarter of the CUs, or when its best tile makes
+// one round of 0.6 ... 1 workgroups per CU (2048 x 1280 x 11520: 0.132 against 0.146 ms; 4096 x 640: equal).
+bool skinny_applies(const GemmArgs& a, bool is16, bool slow) {
+    if (!is16 || !g_gemm_skinny || a.gn_part || a.wb_rows || a.force_big) return false;
+    if (a.epi == EPI_GEGLU || slow || a.out_split) return false;
+    if (a.K < 8 * 64 || a.K % 64 || a.C0 % 64 || (a.A1 && a.C1 % 64) || a.N % 8) return false;
+    const long reg_tiles = (long)((a.M + 127) / 128) * ((a.N + 159) / 160);
+    if (g_gemm_skinny == 2) return reg_tiles <= 2 * cu_count();          // kbench: widen the rule for a sweep
+    if (reg_tiles * 4 <= cu_count()) return true;
+    int bm, bn;
+    skinny_tile(a, &bm, &bn);
+    const long c = skinny_count(a, bm, bn);
+    return c * 10 >= (long)cu_count() * 6 && c <= cu_count();
+}
+
+// Tile choice.  Small problems: 128-row tiles, 4 waves, two workgroups per CU (160-wide when N
+// allows -- every SD channel count is a multiple of 160 -- else 128; 80-wide where 160 would leave one workgroup per CU).  h16
+// problems with enough 256-row tiles to fill the chip: 256 x 320 (or 256 x 256, or 256 x 192 for the DiT widths) tiles, 8 waves as
+// 4 x 2.  Every choice below was made by timing the neighbouring choice on the shapes it serves (profiles/r04_experiments.txt items
+// 12-15, profiles/r04_small_batch.txt); gemm_tile() maps the result onto the instantiations that exist.
+void tile_choice(const GemmArgs& a, bool slow, bool act_only, int* bm, int* bn) {
+    const bool geglu = a.epi == EPI_GEGLU;
+    if (geglu && a.geglu_blk == 16) {                      // 16-row [h | g] blocks: the 320 / 160-column tiles (N % 320 == 0)
+        const long tiles = (long)((a.M + 255) / 256) * (a.N / 320);
+        const bool big = g_force_bm ? g_force_bm == 256 : tiles >= 256;
+        *bm = big ? 256 : 128;
+        *bn = big ? 320 : 160;
+        return;
+    }
+    const bool n320 = !geglu && a.N % 320 == 0 && !(g_gemm_exp & 4096), n256 = a.N % 256 == 0;
+    // A ragged last 320-wide tile wasting <= 5 % of the columns (DiT: fused qkv N = 3456 = 10.8 tiles, Mlp.fc1 N = 4608 = 14.4) beats 256-wide tiles when the
+    // persistent grid's rounds come out shorter: the 64 x 160 wave tile is 5-10 % faster per column (profiles/r04_experiments.txt
+    // items 13, 15), a round is one tile per CU.  65536 x 3456 x 1152: 11 rounds of 320 against 14 of 256 (0.491 -> 0.467 ms);
+    // at 32768 rows 5.5 -> 6 rounds against 7: the 256-wide tiles stay (0.223 against 0.234 ms).
+    {
+        const int c320 = (a.N + 319) / 320, c256 = (a.N + 255) / 256, tm = (a.M + 255) / 256, cus = cu_count();
+        const bool allow = !(g_gemm_exp & 16384) && !(g_gemm_exp & 4096);
+        const long r320 = ((long)tm * c320 + cus - 1) / cus, r256 = ((long)tm * c256 + cus - 1) / cus;
+        if (allow && !geglu && a.mode == GEMM_LINEAR && !n320 && (act_only || !slow) && (long)tm * c320 >= cus &&
+            (long)c320 * 320 * 20 <= (long)a.N * 21 && r320 * 320 * 19 <= r256 * 256 * 20 && g_force_bm != 128) {
+            *bm = 256; *bn = 320;
+            return;
+        }
+    }
+    // 192-wide: the DiT widths (1152, 3456) that neither 320 nor 256 divides; linear layers only
+    bool n192 = !geglu && a.mode == GEMM_LINEAR && !n320 && !n256 && a.N % 192 == 0;
+    // ... unless a ragged last 256-wide tile wastes at most 5 % of the columns (DiT's fused qkv, N = 3456: 13.5 tiles): the
+    // 64 x 128 wave tile reads 0.75 LDS fragments per MFMA against 0.83 for 64 x 96 (qkv projection 8.67 -> 7.83 ms per step)
+    if (n192 && (long)((a.N + 255) / 256) * 256 * 20 <= (long)a.N * 21 && (long)((a.M + 255) / 256) * ((a.N + 255) / 256) >= 256) {
+        *bm = g_force_bm == 128 ? 128 : 256;
+        *bn = g_force_bm == 128 ? 128 : 256;
+        return;
+    }
+    // 128-wide: the VAE's 128-channel 3x3 convs at 512 x 512 (N = 128 exactly)
+    const bool n128 = !geglu && a.mode == GEMM_CONV3 && a.N == 128;
+    int want256 = 0;
+    if (n128) {
+        const long tiles = (long)((a.M + 255) / 256);
+        if (tiles >= 256 && g_force_bm != 128) { *bm = 256; *bn = 128; return; }
+    }
+    if (n320 || n256 || n192) {
+        const int bnb = n320 ? 320 : (n256 ? 256 : 192);
+        const long tiles = (long)((a.M + 255) / 256) * (a.N / bnb);
+        want256 = tiles >= 256;
+    }
+    if (a.force_big) want256 = (n320 || n256 || n192);
+    if (g_force_bm == 128) want256 = 0;                       // development override (kbench A/B)
+    if (g_force_bm == 256) want256 = (n320 || n256 || n192);
+    if (want256) { *bm = 256; *bn = n320 ? 320 : (n256 ? 256 : 192); return; }
+    *bm = 128;
+    *bn = (a.N % 160 == 0 && !geglu) ? 160 : 128;
+    // 128 x 160 tiles that would leave ONE 4-wave workgroup per CU (<= CUs tiles: 4096 x 1280 = 16 batch elements at the 16 x 16
+    // level): half-width tiles put two on every CU -- conv 4096 x 1280 x 11520 0.163 -> 0.143 ms, x 23040 0.312 -> 0.281; where 128 x 160
+    // already gives two per CU they lose 35 % (profiles/r04_small_batch.txt)
+    const bool allow80 = !(g_gemm_exp & 2048);
+    if (allow80 && *bn == 160 && (long)((a.M + 127) / 128) * (a.N / 160) <= cu_count()) *bn = 80;
+}
+
+// The tile gemm_kernel is launched with (tile_choice + what the instantiation set allows): the f32 parity mode has
+// 128-row tiles only (its GEGLU with 16-row blocks the 160-column one whatever the size); the gated DiT epilogues exist at
+// 256 x 256, 256 x 192 and 128 x 128, the tanh-GELU-only one also at 256 x 320.  The executors name their profile families by it.
+void gemm_tile(const GemmArgs& a, bool is16, bool slow, bool act_only, int* bm, int* bn) {
+    tile_choice(a, slow, act_only, bm, bn);
+    // N = 128 convs, 16-bit: 512-row tiles (8 waves as 8 x 1, 64 x 128 per wave: 0.375 instead of 0.5 KB of fragment reads per MFMA; -6 % at
+    // 512 x 512 x 128, profiles/r05_experiments.txt item 9) where ONE image alone makes >= 256 of them on a power-of-two map -- so the
+    // choice, and with it every partial sum of the epilogue statistics, is the same at every batch size
+    if (*bm == 256 && *bn == 128 && is16 && a.mode == GEMM_CONV3 && !a.bias2 && g_force_bm != 256) {
+        const long hw = (long)a.Hout * a.Wout;
+        if (hw >= 512L * 256 && a.lwo >= 0 && a.M % hw == 0) *bm = 512;
+    }
+    if (*bm == 512) return;
+    bool big = *bm == 256 && is16;
+    if (big && slow && *bn == 320 && !act_only) big = false;
+    if (!big) {
+        // (a 320-column choice the f32 mode cannot run falls back to 160 columns, not 128: N % 320 == 0 there, and the one-launch
+        //  tapped q | k | v needs the tile width to divide out_split, a multiple of 320)
+        const bool n160 = *bn == 160 || (*bn == 320 && !slow) || (a.epi == EPI_GEGLU && a.geglu_blk == 16);
+        const bool n80 = *bn == 80 && is16 && !slow;          // (16-bit instantiations only; f32: the 160-column tile)
+        *bm = 128;
+        *bn = slow ? 128 : (n80 ? 80 : ((n160 || *bn == 80) ? 160 : 128));
+    }
+}
+
+// The plan of launch_gemm(a_in): check, prepare (g: the copy the kernels are launched with -- what they and the decision read beside
+// the caller's arguments, derived once per launch), decide
+int plan_args(const GemmArgs& a_in, bool is16, GemmArgs* g, GemmLaunchRec* plan) {
+    const int st = check_args(a_in, is16 ? Traits<h16>::BK : Traits<float>::BK);
     if (st != DSIM_OK) return st;
-    GemmArgs a = a_in;
+    GemmArgs& a = *g;
+    a = a_in;
     a.lwo = a.lhw = -1;
-#ifdef DSIM_DEVTOOLS
     if (a.epi == EPI_GEGLU && (g_gemm_exp & 8192) && a.N % 64 == 0) a.geglu_blk = 32;      // kbench: the 256 / 128-column GEGLU tiles
-#endif
     if (a.mode == GEMM_CONV3) {          // power-of-two output maps: the kernels split the pixel index with shifts
         const int hw = a.Hout * a.Wout;
         if (a.Wout > 0 && !(a.Wout & (a.Wout - 1)) && !(hw & (hw - 1))) {
@@ -1025,61 +1012,101 @@ int launch_typed(const GemmArgs& a_in, hipStream_t s) {
         }
     }
     if (a.wb_rows == a.M) a.wb_rows = 0;        // one batch: a plain GEMM
-    if constexpr (sizeof(T) == 2) {
-        // problems too small to fill the chip: 64 x 64 tiles behind a deep LDS ring, the same arithmetic bit for bit (gemm_skinny.hip)
-        if (g_gemm_skinny && !a.gn_part && !a.wb_rows && !a.force_big && gemm_skinny_applies(a)) {
-            GemmArgs g = a;
-            const int se = gemm_fill_extents(g, sizeof(T));
-            return se != DSIM_OK ? se : launch_gemm_skinny(g, s);
-        }
-    }
+#ifdef DSIM_DEVTOOLS
+    a.exp = g_gemm_exp;
+    a.stamps = g_gemm_stamps;
+#endif
     const bool slow = a.act != 0 || a.gate != nullptr;     // DiT linears only
-    if (slow && (a.mode != GEMM_LINEAR || a.epi == EPI_GEGLU)) return DSIM_ERR_INVALID;
+    const bool act_only = a.act == 1 && !a.gate && a.epi != EPI_RESIDUAL;      // the epilogue kinds instantiated at 256 x 320
+    const bool geglu = a.epi == EPI_GEGLU;
+    const int ek = a.epi == EPI_RESIDUAL ? EK_RES : EK_PLAIN;
     int bm, bn;
-    gemm_launch_tile(a, sizeof(T) == 2 ? DSIM_H16 : DSIM_F32, &bm, &bn);
+    if (skinny_applies(a, is16, slow)) {
+        skinny_tile(a, &bm, &bn);
+        *plan = GemmLaunchRec{bm, bn, a.mode, 0, ek, 1};
+        return skinny_compiled(bm, bn) ? DSIM_OK : DSIM_ERR_INVALID;
+    }
+    if (slow && (a.mode != GEMM_LINEAR || geglu)) return DSIM_ERR_INVALID;
+    gemm_tile(a, is16, slow, act_only, &bm, &bn);
     // out_split: the epilogue picks ONE destination tensor per tile from its first column, so the tile width must divide the split
     if (a.out_split && a.out_split % bn != 0) return DSIM_ERR_INVALID;
     if (a.wb_rows % bm != 0) return DSIM_ERR_INVALID;           // a tile's rows belong to one weight batch
-    if constexpr (sizeof(T) == 2)
-        if (bm == 512) return a.lwo >= 0 && bn == 128 ? launch_one<T, 512, 128, GEMM_CONV3P, false, 8, 1>(a, s) : DSIM_ERR_INVALID;
-    const bool big = bm == 256, n160 = bn == 160;
-    (void)big;
-    if constexpr (sizeof(T) == 2) {
-        // h16, big problems: 256-row tiles, 8 waves as 4(M) x 2(N), 64-row x (BN/2)-column sub-tiles
-        if (big) {
-            if (a.epi == EPI_GEGLU)
-                return bn == 320 ? launch_one<T, 256, 320, GEMM_LINEAR, true, 4, 2>(a, s) : launch_one<T, 256, 256, GEMM_LINEAR, true, 4, 2>(a, s);
-            if (a.mode == GEMM_CONV3) {
-                // (the VAE's 128-channel levels: power-of-two maps as well -- setup()'s integer divisions were 10 % of these K = 1152 tiles)
-                if (bn == 128) return a.lwo >= 0 ? launch_one<T, 256, 128, GEMM_CONV3P, false, 4, 2>(a, s)
-                                                 : launch_one<T, 256, 128, GEMM_CONV3, false, 4, 2>(a, s);
-                // power-of-two output maps (every SD level at the sizes these tiles serve): the instantiation without the integer
-                // divisions in setup(); a run-time branch instead spilled scalar registers in the residual kernel
-                if (a.lwo >= 0) return bn == 320 ? launch_one<T, 256, 320, GEMM_CONV3P, false, 4, 2>(a, s)
-                                                 : launch_one<T, 256, 256, GEMM_CONV3P, false, 4, 2>(a, s);
-                return bn == 320 ? launch_one<T, 256, 320, GEMM_CONV3, false, 4, 2>(a, s)
-                                 : launch_one<T, 256, 256, GEMM_CONV3, false, 4, 2>(a, s);
-            }
-            if (slow && bn == 320) return launch_ek<T, 256, 320, GEMM_LINEAR, false, 4, 2, EK_ACT>(a, s);      // tanh-GELU only (DiT Mlp.fc1)
-            if (slow) return bn == 192 ? launch_one<T, 256, 192, GEMM_LINEAR, false, 4, 2, true>(a, s)
-                                       : launch_one<T, 256, 256, GEMM_LINEAR, false, 4, 2, true>(a, s);
-            if (bn == 192) return launch_one<T, 256, 192, GEMM_LINEAR, false, 4, 2>(a, s);
-            return bn == 320 ? launch_one<T, 256, 320, GEMM_LINEAR, false, 4, 2>(a, s)
-                             : launch_one<T, 256, 256, GEMM_LINEAR, false, 4, 2>(a, s);
-        }
+    // power-of-two output maps (every SD level at the sizes the 256- and 512-row tiles serve; the VAE's 128-channel levels as well --
+    // setup()'s integer divisions were 10 % of these K = 1152 tiles): the instantiation without the integer divisions in setup(); a
+    // run-time branch instead spilled scalar registers in the residual kernel
+    const int mode = a.mode == GEMM_CONV3 && bm >= 256 && a.lwo >= 0 ? GEMM_CONV3P : a.mode;
+    *plan = GemmLaunchRec{bm, bn, mode, geglu ? 1 : 0, slow ? (act_only ? EK_ACT : EK_SLOW) : ek, 0};
+    // GroupNorm statistics from the epilogue (GemmArgs.gn_part): the VAE's 512 x 512 / 256 x 256 levels on their 256- and 512-row
+    // tiles; refused on a tile that has no statistics epilogue (gemm_gn_stats_tile() asks).  (The DiT epilogues ignore it.)
+    if (a.gn_part && !slow) {
+        plan->ek += EK_PLAIN_GN;
+        if (a.gn_hw <= 0 || a.gn_hw % bm || a.M % a.gn_hw || a.N % bn || a.bias2) return DSIM_ERR_INVALID;
     }
-    if (slow) return launch_one<T, 128, 128, GEMM_LINEAR, false, 4, 1, true>(a, s);
-    if (a.epi == EPI_GEGLU) return n160 ? launch_one<T, 128, 160, GEMM_LINEAR, true>(a, s) : launch_one<T, 128, 128, GEMM_LINEAR, true>(a, s);
+    return gemm_compiled(is16, bm, bn, mode, geglu, plan->ek) ? DSIM_OK : DSIM_ERR_INVALID;
+}
+
+// g: prepared, extents filled.  WM x WN waves follow from the rows: 512 -> 8 x 1, 256 -> 4 x 2, 128 -> 4 x 1.
+template <typename T, int BM, int BN, int MODE, bool GEGLU, int EK>
+int launch_ek(const GemmArgs& g, hipStream_t s) {
+    constexpr int WM = BM == 512 ? 8 : 4, WN = BM == 256 ? 2 : 1, NW = WM * WN;
+    constexpr int LDS = gemm_lds_bytes<T, BM, BN, GEGLU, WM, WN>();
+    static_assert(LDS <= 160 * 1024, "LDS budget");
+    const int tilesM = (g.M + BM - 1) / BM, tilesN = (g.N + BN - 1) / BN;
+    // persistent grid: as many workgroups as stay resident (LDS-limited), a multiple of 8 so a workgroup keeps its XCD
+    const int ntiles = tilesM * tilesN;
+    const int resident = ((cu_count() * (LDS <= 80 * 1024 ? 2 : 1)) / 8) * 8;
+    const int grid = ntiles <= resident || resident < 8 || !g_gemm_persistent ? ntiles : resident;
+    int gn = gemm_band_width(tilesM, tilesN, (size_t)BN * g.K * sizeof(T));
+    if (g_gemm_exp >> 16) gn = std::min(tilesN, g_gemm_exp >> 16);      // kbench: KB_GEXP = gn << 16 (>= tilesN: row-major order)
+    const int st = launch_lds<gemm_kernel<T, BM, BN, MODE, GEGLU, WM, WN, EK>>(dim3(grid), dim3(NW * 64), LDS, s, g, tilesN, ntiles, tilesM, gn);
+    if (st == DSIM_OK) g_gemm_last_launch = GemmLaunchRec{BM, BN, MODE, GEGLU ? 1 : 0, EK, 0};
+    return st;
+}
+
+// One launch function per (tile, mode, GEGLU, epilogue kind) that gemm_compiled() admits, null for the rest: the only place
+// gemm_kernel is instantiated (kTiles lists every tile gemm_compiled() knows)
+typedef int (*GemmLaunchFn)(const GemmArgs&, hipStream_t);
+constexpr int kTiles[][2] = {{512, 128}, {256, 320}, {256, 256}, {256, 192}, {256, 128}, {128, 160}, {128, 128}, {128, 80}};
+constexpr int kNTiles = sizeof(kTiles) / sizeof(kTiles[0]), kNModes = 3, kNEk = 6, kNCombos = kNTiles * kNModes * 2 * kNEk;
+constexpr int combo(int tile, int mode, int geglu, int ek) { return ((tile * kNModes + mode) * 2 + geglu) * kNEk + ek; }
+template <typename T, int I>
+constexpr GemmLaunchFn launch_fn() {
+    constexpr int TILE = I / (kNModes * 2 * kNEk), MODE = I / (2 * kNEk) % kNModes, EK = I % kNEk;
+    constexpr bool GEGLU = I / kNEk % 2 != 0;
+    static_assert(combo(TILE, MODE, GEGLU, EK) == I, "combo()");
+    if constexpr (gemm_compiled(sizeof(T) == 2, kTiles[TILE][0], kTiles[TILE][1], MODE, GEGLU, EK))
+        return &launch_ek<T, kTiles[TILE][0], kTiles[TILE][1], MODE, GEGLU, EK>;
+    return nullptr;
+}
+template <typename T, int... I>
+int launch_planned(const GemmLaunchRec& p, const GemmArgs& g, hipStream_t s, std::integer_sequence<int, I...>) {
+    static constexpr GemmLaunchFn fns[] = {launch_fn<T, I>()...};
+    for (int t = 0; t < kNTiles; ++t)
+        if (kTiles[t][0] == p.bm && kTiles[t][1] == p.bn && fns[combo(t, p.mode, p.geglu, p.ek)]) return fns[combo(t, p.mode, p.geglu, p.ek)](g, s);
+    return DSIM_ERR_INVALID;
+}
+
+template <typename T>
+int launch_typed(const GemmArgs& a, hipStream_t s) {
+    GemmArgs g;
+    GemmLaunchRec p;
+    int st = plan_args(a, sizeof(T) == 2, &g, &p);
+    if (st == DSIM_OK) st = gemm_fill_extents(g, sizeof(T));
+    if (st != DSIM_OK) return st;
     if constexpr (sizeof(T) == 2)
-        if (bn == 80) return a.mode == GEMM_CONV3 ? launch_one<T, 128, 80, GEMM_CONV3, false>(a, s) : launch_one<T, 128, 80, GEMM_LINEAR, false>(a, s);
-    if (a.mode == GEMM_CONV3)
-        return n160 ? launch_one<T, 128, 160, GEMM_CONV3, false>(a, s) : launch_one<T, 128, 128, GEMM_CONV3, false>(a, s);
-    return n160 ? launch_one<T, 128, 160, GEMM_LINEAR, false>(a, s) : launch_one<T, 128, 128, GEMM_LINEAR, false>(a, s);
+        if (p.small) return launch_gemm_skinny(g, p, s);
+    return launch_planned<T>(p, g, s, std::make_integer_sequence<int, kNCombos>{});
 }
 
 }  // namespace
 
 inline namespace DSIM_H16_NS {
+int gemm_plan(const GemmArgs& a, int dtype, GemmLaunchRec* plan) {
+    if (dtype != DSIM_F32 && dtype != DSIM_BF16 && dtype != DSIM_F16) return DSIM_ERR_INVALID;
+    GemmArgs g;
+    return plan_args(a, dtype != DSIM_F32, &g, plan);
+}
+
 int launch_gemm(const GemmArgs& a, int dtype, hipStream_t s) {
     if (dtype == DSIM_H16) return launch_typed<h16>(a, s);
 #ifndef DSIM_H16_IS_F16            // the fp16 objects hold the fp16 kernels only; the bf16 ones forward DSIM_F16 to them

@@ -11,8 +11,11 @@
 //   * an 8-slot LDS ring (16 KB per K tile), seven K tiles in flight behind a counted vmcnt: a workgroup's K loop runs at its
 //     CU's L2->LDS rate instead of one memory round trip per tile;
 //   * no transpose epilogue (the problem is small): 8-byte stores straight from the D^T accumulators.
-// launch_gemm (gemm.hip) routes here when gemm_kernel's grid would leave most of the chip idle.
+// launch_gemm (gemm.hip) routes here when gemm_kernel's grid would leave most of the chip idle: gemm_plan() there holds the rule and
+// picks the tile.
 #include "common.h"
+
+#include <utility>
 
 namespace dsim {
 namespace {
@@ -203,70 +206,30 @@ int launch_skinny_t(const GemmArgs& g, hipStream_t s) {
     constexpr int LDS = ((144 * 1024 / STG) < 8 ? (144 * 1024 / STG) : 8) * STG;
     const int tilesM = (g.M + SBM - 1) / SBM, tilesN = (g.N + SBN - 1) / SBN;
     const int st = launch_lds<gemm_skinny_kernel<MODE, RES, SBM, SBN>>(dim3(tilesM * tilesN), dim3(SNW * 64), LDS, s, g, tilesN);
-    if (st == DSIM_OK) g_gemm_last_launch = GemmLaunchRec{SBM, SBN, MODE, 0, RES ? 1 : 0, 1};      // (gemm.hip EK_RES / EK_PLAIN)
+    if (st == DSIM_OK) g_gemm_last_launch = GemmLaunchRec{SBM, SBN, MODE, 0, RES ? EK_RES : EK_PLAIN, 1};
     return st;
 }
 
-template <int MODE, bool RES>
-int launch_skinny(const GemmArgs& g, hipStream_t s) {
-    int bm, bn;
-    gemm_skinny_tile(g, &bm, &bn);
-    if (bm == 128 && bn == 64) return launch_skinny_t<MODE, RES, 128, 64>(g, s);
-    if (bm == 64 && bn == 128) return launch_skinny_t<MODE, RES, 64, 128>(g, s);
-    if (bm == 128 && bn == 128) return launch_skinny_t<MODE, RES, 128, 128>(g, s);
-    if (bm == 64 && bn == 80) return launch_skinny_t<MODE, RES, 64, 80>(g, s);
-    if (bm == 128 && bn == 80) return launch_skinny_t<MODE, RES, 128, 80>(g, s);
-#ifdef DSIM_DEVTOOLS
-    if (bm == 128 && bn == 160) return launch_skinny_t<MODE, RES, 128, 160>(g, s);     // kbench sweep only (never the heuristic's choice)
-#endif
-    return launch_skinny_t<MODE, RES, 64, 64>(g, s);
+// One launch function per (tile of kSkinnyTiles, mode, residual): the only place gemm_skinny_kernel is instantiated
+typedef int (*SkinnyLaunchFn)(const GemmArgs&, hipStream_t);
+template <int I>
+constexpr SkinnyLaunchFn skinny_fn() {
+    return &launch_skinny_t<I / 2 % 2 ? GEMM_CONV3 : GEMM_LINEAR, I % 2 != 0, kSkinnyTiles[I / 4][0], kSkinnyTiles[I / 4][1]>;
+}
+template <int... I>
+int launch_skinny(const GemmLaunchRec& p, const GemmArgs& g, hipStream_t s, std::integer_sequence<int, I...>) {
+    static constexpr SkinnyLaunchFn fns[] = {skinny_fn<I>()...};
+    for (int t = 0; t < kSkinnyCompiled; ++t)
+        if (kSkinnyTiles[t][0] == p.bm && kSkinnyTiles[t][1] == p.bn)
+            return fns[t * 4 + (p.mode == GEMM_CONV3 ? 2 : 0) + (p.ek == EK_RES ? 1 : 0)](g, s);
+    return DSIM_ERR_INVALID;
 }
 
 }  // namespace
 
-#ifdef DSIM_DEVTOOLS
-int g_skinny_tile = 0;          // kbench: 0 heuristic, else (bm << 8) | bn
-#endif
-
 inline namespace DSIM_H16_NS {
-// Tile of the small-batch kernel.  One workgroup runs per CU (the ring fills LDS) and streams (bm + bn) x 128 B per K tile through
-// its CU's L2 -> LDS path, so the tile with the smallest bm + bn that still makes ONE round (<= CUs workgroups) wins -- by less than
-// the byte count says once most CUs stream at the same time (the L2s' aggregate rate, ~8.7 TB/s, takes over).  Measured (tools/kbench
-// KB_SKINNY=2, profiles/r04_small_batch.txt), ms at K = 11520: 1024 x 1280: 64x80 (256 workgroups) 0.094 | 64x128 (160) 0.098 | 128x64
-// 0.105 | 128x128 (80) 0.133 | 64x64 (320: two rounds) 0.143 | gemm_kernel 0.124; 2048 x 1280: 128x80 (256) 0.123 | 128x128 (160) 0.135 |
-// 64x128 (320) 0.192 | gemm_kernel 0.131; 256 / 512 x 1280: 64x64 0.072 against 0.124.
-static long skinny_count(const GemmArgs& a, int bm, int bn) { return (long)((a.M + bm - 1) / bm) * ((a.N + bn - 1) / bn); }
-static const int kSkinnyTiles[5][2] = {{64, 64}, {64, 80}, {64, 128}, {128, 80}, {128, 128}};      // by bm + bn
-void gemm_skinny_tile(const GemmArgs& a, int* bm, int* bn) {
-#ifdef DSIM_DEVTOOLS
-    if (g_skinny_tile) { *bm = g_skinny_tile >> 8; *bn = g_skinny_tile & 255; return; }
-#endif
-    for (const auto& t : kSkinnyTiles)
-        if (skinny_count(a, t[0], t[1]) <= cu_count() && (t[1] != 80 || a.N % 80 == 0)) { *bm = t[0]; *bn = t[1]; return; }
-    *bm = 128; *bn = 128;
-}
-
-// Does the small-batch kernel take this problem?  Plain / residual epilogues of the 16-bit modes with a K loop long enough for the
-// ring to matter, when gemm_kernel's grid (128-row tiles) would occupy at most a quarter of the CUs, or when its best tile makes
-// one round of 0.6 ... 1 workgroups per CU (2048 x 1280 x 11520: 0.132 against 0.146 ms; 4096 x 640: equal).
-bool gemm_skinny_applies(const GemmArgs& a) {
-    if (a.epi == EPI_GEGLU || a.act != 0 || a.gate != nullptr || a.out_split) return false;
-    if (a.K < 8 * 64 || a.K % 64 || a.C0 % 64 || (a.A1 && a.C1 % 64) || a.N % 8) return false;
-    const long reg_tiles = (long)((a.M + 127) / 128) * ((a.N + 159) / 160);
-#ifdef DSIM_DEVTOOLS
-    if (g_gemm_skinny == 2) return reg_tiles <= 2 * cu_count();          // kbench: widen the rule for a sweep
-#endif
-    if (reg_tiles * 4 <= cu_count()) return true;
-    int bm, bn;
-    gemm_skinny_tile(a, &bm, &bn);
-    const long c = skinny_count(a, bm, bn);
-    return c * 10 >= (long)cu_count() * 6 && c <= cu_count();
-}
-
-// a: operand extents already filled in (launch_gemm does it)
-int launch_gemm_skinny(const GemmArgs& g, hipStream_t s) {
-    if (g.mode == GEMM_CONV3) return g.epi == EPI_RESIDUAL ? launch_skinny<GEMM_CONV3, true>(g, s) : launch_skinny<GEMM_CONV3, false>(g, s);
-    return g.epi == EPI_RESIDUAL ? launch_skinny<GEMM_LINEAR, true>(g, s) : launch_skinny<GEMM_LINEAR, false>(g, s);
+int launch_gemm_skinny(const GemmArgs& g, const GemmLaunchRec& plan, hipStream_t s) {
+    return launch_skinny(plan, g, s, std::make_integer_sequence<int, 4 * kSkinnyCompiled>{});
 }
 }  // namespace DSIM_H16_NS
 

@@ -5,13 +5,13 @@
 
 // implicit GEMM -- gemm.hip, gemm_skinny.hip
 int launch_gemm(const GemmArgs& a, int dtype, hipStream_t s);
+// The instantiation launch_gemm starts for these arguments: the one place that decides it (host only, launches nothing, any of the
+// three dtypes); DSIM_ERR_INVALID where launch_gemm would refuse them
+int gemm_plan(const GemmArgs& a, int dtype, GemmLaunchRec* plan);
 int gemm_fill_extents(GemmArgs& g, size_t es);                       // operand byte extents for the buffer descriptors
-bool gemm_skinny_applies(const GemmArgs& a);                         // small-batch kernel (gemm_skinny.hip): same arithmetic, deep ring
-int launch_gemm_skinny(const GemmArgs& g /*extents filled*/, hipStream_t s);
-void gemm_skinny_tile(const GemmArgs& a, int* bm, int* bn);          // its tile for this problem
+// small-batch kernel (gemm_skinny.hip): same arithmetic, deep ring; g prepared by launch_gemm, the tile / mode / epilogue from its plan
+int launch_gemm_skinny(const GemmArgs& g, const GemmLaunchRec& plan, hipStream_t s);
 int gemm_band_width(int tilesM, int tilesN, size_t w_tile_bytes);   // tile-order band width (L2 reuse of the weight tiles)
-void gemm_tile_choice(const GemmArgs& a, int* bm, int* bn);   // the tile the problem's shape asks for
-void gemm_launch_tile(const GemmArgs& a, int dtype, int* bm, int* bn);   // ... and the instantiation launch_gemm picks for it (dtype: DSIM_F32 or a 16-bit one)
 
 // row-resident Linear and fused feed-forward -- rowres.hip
 size_t rowlin_stream_bytes(int C, int N);       // 0: shape not covered

@@ -100,26 +100,24 @@ struct WeightStore {
     }
 };
 
-// profile family of a GEMM launch = the kernel symbol launch_gemm will pick for it (one family per symbol), + its algorithmic work
+// profile family of a GEMM launch = the kernel symbol launch_gemm will pick for it (one family per symbol), composed from gemm_plan()'s
+// answer alone, + its algorithmic work.  Epilogue suffixes: _geglu | _res | _act (tanh-GELU only) | _dit (the gated DiT epilogues,
+// residual or not), + _gn for the statistics epilogue kinds.  (A problem launch_gemm refuses: "gemm_<dtype>_refused".)
 static inline std::string gemm_family(const GemmArgs& g, int dt, double* flops, double* bytes) {
-    int bm, bn;
-    gemm_launch_tile(g, dt, &bm, &bn);
-    const bool skinny = dt != DSIM_F32 && !(g.wb_rows && g.wb_rows != g.M) && !g.force_big && !g.gn_part && gemm_skinny_applies(g);      // the small-batch kernel (gemm_skinny.hip)
-    // 256-row 16-bit conv tiles on power-of-two output maps run the CONV3P instantiation (gemm.hip launch_typed)
-    const int hwo = g.Hout * g.Wout;
-    const bool conv_p2 = g.mode == GEMM_CONV3 && !skinny && dt != DSIM_F32 && (bm == 256 || bm == 512) && g.Wout > 0 &&
-                         !(g.Wout & (g.Wout - 1)) && !(hwo & (hwo - 1));
-    if (skinny) gemm_skinny_tile(g, &bm, &bn);
+    GemmLaunchRec p;
+    const bool ok = gemm_plan(g, dt, &p) == DSIM_OK;
     const char* dtn = dt == DSIM_F32 ? "f32" : (dt == DSIM_F16 ? "f16" : "bf16");
     const double e = (double)dtype_size(dt);
     const double outc = g.epi == EPI_GEGLU ? g.N / 2 : g.N;
     *flops = 2.0 * g.M * (double)g.N * g.K;
     *bytes = e * ((double)g.M * (g.mode == GEMM_CONV3 ? g.C0 : g.K) + (double)g.N * g.K * (g.wb_rows ? g.M / g.wb_rows : 1) +
                   (double)g.M * outc * (g.residual ? 2 : 1));
-    return std::string(skinny ? "gemm_small_" : "gemm_") + dtn + "_" + std::to_string(bm) + "x" + std::to_string(bn) +
-           (g.mode == GEMM_CONV3 ? (conv_p2 ? "_conv3p" : "_conv3") : "_linear") +
-           (g.epi == EPI_GEGLU ? "_geglu" : (g.epi == EPI_RESIDUAL ? "_res" : "")) + (g.gn_part ? "_gn" : "") +      // _gn: the statistics epilogue kinds
-           "|M" + std::to_string(g.M) + " N" + std::to_string(g.N) + " K" + std::to_string(g.K);
+    static const char* const kind[] = {"_linear", "_conv3", "_conv3p"};
+    static const char* const epi[] = {"", "_res", "_dit", "_act", "_gn", "_res_gn"};      // by EK_*
+    const std::string size = "|M" + std::to_string(g.M) + " N" + std::to_string(g.N) + " K" + std::to_string(g.K);
+    if (!ok) return std::string("gemm_") + dtn + "_refused" + size;
+    return std::string(p.small ? "gemm_small_" : "gemm_") + dtn + "_" + std::to_string(p.bm) + "x" + std::to_string(p.bn) + kind[p.mode] +
+           (p.geglu ? "_geglu" : epi[p.ek]) + size;
 }
 
 // HIP-event bracket of one launch of a profiled forward (WalkBase::pbegin / pend)
@@ -244,13 +242,10 @@ struct WalkBase {
                (pre ? 2.0 : (double)groupnorm_passes(C0, C1, HW, groups, h->dt)) * n * es());
     }
 
-    // family: the record's name where gemm_family() does not know it (DiT's epilogues), with its work
-    int gemm(GemmArgs& g, const std::string* family = nullptr, double flops = 0, double bytes = 0) {
+    int gemm(GemmArgs& g) {
         g.zero_page = h->zero_page;
         if (!run) return DSIM_OK;
-        if (h->profiling && family) {
-            pbegin(*family, flops, bytes);
-        } else if (h->profiling) {
+        if (h->profiling) {
             double fl, by;
             const std::string nm = gemm_family(g, h->dt, &fl, &by);
             pbegin(nm, fl, by);

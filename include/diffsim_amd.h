@@ -481,8 +481,10 @@ int dsim_op_ln_linear_dt(const void* x, const float* ln_gamma, const float* ln_b
  *      bytes); DSIM_ERR_INVALID otherwise.
  *   gn_part (16-bit power-of-two 3x3 convs on the 256 x 128 / 256 x 256 / 512 x 128 tiles): [M / gn_hw][gn_hw / 64][N / 4][2] f32
  *      (sum, sum of squares) of the stored output per (64 rows, 4-channel quad).
- * launched receives the instantiation that ran (recorded where it was launched) and family the profile name gemm_family() gives
- * the same arguments.  Allocates and synchronises. */
+ * launched receives the instantiation that ran (recorded where it was launched) and family the profile name of the instantiation
+ * planned for the same arguments (gemm_family() from gemm_plan(): "gemm[_small]_<dtype>_<bm>x<bn>_<linear | conv3 | conv3p>" +
+ * "_geglu" | "_res" | "_act" (act without gate or residual) | "_dit" (a gate, or act with a residual: no "_res" on these) | "", +
+ * "_gn" with gn_part, + "|M.. N.. K..").  Allocates and synchronises. */
 typedef struct dsim_gemm_op {
     int mode;                                   /* 0 linear, 1 3x3 conv */
     int H, W, stride, ups, pad;                 /* conv: stored input map, stride 1 | 2, upsample 0 | 1, pad 1 | 0 */
@@ -506,7 +508,7 @@ typedef struct dsim_gemm_launch {
     int geglu;
     int ek;                                     /* 0 plain, 1 residual, 2 DiT gate, 3 tanh-GELU only, 4 / 5 plain / residual + GN statistics */
     int small;                                  /* 1: the small-batch kernel */
-    char family[128];                           /* gemm_family() of the same arguments */
+    char family[128];                           /* the profile name of the planned instantiation (above) */
 } dsim_gemm_launch;
 int dsim_op_gemm(const dsim_gemm_op* op, dsim_gemm_launch* launched, void* stream);
 /* GroupNorm (+ SiLU) of x [B][HW][C] whose statistics come from a conv epilogue's gn_part (part32, chunks = HW / 64 per image: any

@@ -10,8 +10,8 @@ engine.op_gemm (dsim_op_gemm: the whole GemmArgs surface) in all three dtypes an
   * gn_part: the partial sums against float64 sums of the STORED output, op_groupnorm_pre against float64 GroupNorm + SiLU of
     the stored output and against op_groupnorm on the same input;
   * the small-batch kernel: bit for bit the rows of a large-M launch of the same problem on the regular tiles.
-test_launch_coverage then holds the launch records of the whole case list to the table of every instantiation launch_typed can
-reach on MI355X (256 CUs), and gemm_family's names to the records."""
+test_launch_coverage then holds the launch records of the whole case list to the table of every instantiation gemm_plan can
+name on MI355X (256 CUs), and gemm_family's names to the records."""
 import math
 import time
 
@@ -131,7 +131,7 @@ for _side, _c in ((512, 128), (256, 128), (256, 256)):                     # 512
             CASES[f"vae_conv{_c}_{_side}{'_res' if _res else ''}{'_gn' if _gn else ''}"] = _conv(1, _side, _side, _c, _c, res=_res, gn=_gn,
                                                                                               sub=1)
 
-# (dtype, small, bm, bn, kind, geglu, ek) of every instantiation launch_typed can reach on a 256-CU MI355X
+# (dtype, small, bm, bn, kind, geglu, ek) of every instantiation gemm_plan can name on a 256-CU MI355X
 _H16 = ([(0, 512, 128, "conv3p", 0, ek) for ek in ("plain", "residual", "plain_gn", "residual_gn")]
         + [(0, 256, bn, "conv3p", 0, ek) for bn in (128, 256) for ek in ("plain", "residual", "plain_gn", "residual_gn")]
         + [(0, 256, bn, kind, 0, ek) for bn, kind in ((320, "conv3p"), (320, "conv3"), (256, "conv3"), (128, "conv3"))
@@ -149,12 +149,11 @@ _F32 = ([(0, 128, 128, "linear", 0, ek) for ek in ("act", "dit")]
         + [(0, 128, bn, "linear", 1, "plain") for bn in (160, 128)]
         + [(0, 128, bn, kind, 0, ek) for bn in (160, 128) for kind in ("linear", "conv3") for ek in ("plain", "residual")])
 REACHABLE = {"bf16": set(_H16), "f16": set(_H16), "f32": set(_F32)}
-# Instantiations the product library compiles that no arguments reach: the small-batch 128 x 64 tile (gemm_skinny.hip launch_skinny
-# dispatches it, but gemm_skinny_tile() never picks it: kSkinnyTiles lacks it and its fallback is 128 x 128; only the -DDSIM_DEVTOOLS
-# g_skinny_tile override selects it), linear and conv3, plain and residual, in both 16-bit dtypes.  (128 x 160 small-batch tiles
-# exist in -DDSIM_DEVTOOLS builds only.)  REACHABLE was written from launch_typed / launch_skinny; tests/test_gemm64_host.py holds
+# Instantiations the product library compiles that no arguments reach: none.  gemm.hip's gemm_compiled() and common.h's kSkinnyTiles
+# state the compiled set, gemm_plan() plans inside it, and the one tile no plan of the product names (the small-batch 128 x 64) is
+# compiled, like 128 x 160, in -DDSIM_DEVTOOLS builds only, where g_skinny_tile selects it.  tests/test_gemm64_host.py holds
 # REACHABLE | UNREACHABLE to the kernel symbols of the built library, so a new instantiation cannot go unlisted.
-_UNREACHED_H16 = [(1, 128, 64, kind, 0, ek) for kind in ("linear", "conv3") for ek in ("plain", "residual")]
+_UNREACHED_H16 = []
 UNREACHABLE = {"bf16": set(_UNREACHED_H16), "f16": set(_UNREACHED_H16), "f32": set()}
 
 RECORDS = {}                 # (case, dtype) -> launch record
@@ -330,12 +329,12 @@ def test_gemm_against_float64(name, dt):
 
 
 def _family_fields(fam):
-    """(small, bm, bn, kind, geglu, residual, gn) from a gemm_family() name"""
+    """(small, bm, bn, kind, geglu, residual, gn, act, dit) from a gemm_family() name"""
     head = fam.split("|")[0].split("_")
     small = head[1] == "small"
     f = head[2:] if small else head[1:]
     bm, bn = (int(v) for v in f[1].split("x"))
-    return small, bm, bn, f[2], "geglu" in f[3:], "res" in f[3:], "gn" in f[3:]
+    return small, bm, bn, f[2], "geglu" in f[3:], "res" in f[3:], "gn" in f[3:], "act" in f[3:], "dit" in f[3:]
 
 
 def test_launch_coverage():
@@ -349,8 +348,9 @@ def test_launch_coverage():
     for (name, dt), r in RECORDS.items():
         key = (int(r["small"]), r["bm"], r["bn"], r["kind"], int(r["geglu"]), r["ek"])
         seen[dt].add(key)
-        small, bm, bn, kind, geglu, res, gn = _family_fields(r["family"])
+        small, bm, bn, kind, geglu, res, gn, act, dit = _family_fields(r["family"])
         assert (small, bm, bn, kind, geglu) == (r["small"], r["bm"], r["bn"], r["kind"], r["geglu"]), (name, dt, r)
+        assert (act, dit) == (r["ek"] == "act", r["ek"] == "dit"), (name, dt, r)
         if r["ek"] in ("plain", "residual", "plain_gn", "residual_gn"):
             assert (res, gn) == (r["ek"].startswith("residual"), r["ek"].endswith("_gn")), (name, dt, r)
     for dt in DT:

@@ -112,7 +112,8 @@ static void bench_gemm(const char* name, int mode, int M, int N, int Cin, int H,
         msv[v] = t.run([&] { st = launch_gemm(g, DSIM_BF16, 0); }, iters);
     }
     if (getenv("KB_SKINNY") && atoi(getenv("KB_SKINNY")) == 2) g_gemm_skinny = 2;      // widened applies() rule for the sweep
-    if (getenv("KB_SKINNY") && gemm_skinny_applies(g)) {      // small-batch kernel: gemm_kernel against every skinny tile (interleaved rounds)
+    GemmLaunchRec plan;
+    if (getenv("KB_SKINNY") && gemm_plan(g, DSIM_BF16, &plan) == DSIM_OK && plan.small) {      // small-batch kernel: gemm_kernel against every skinny tile (interleaved rounds)
         const int tiles[8] = {-1, (64 << 8) | 64, (128 << 8) | 64, (64 << 8) | 128, (128 << 8) | 128, (128 << 8) | 160, (64 << 8) | 80, (128 << 8) | 80};
         const int rounds = getenv("KB_ROUNDS") ? atoi(getenv("KB_ROUNDS")) : 5;
         std::vector<std::vector<float>> ms(8);
@@ -123,8 +124,7 @@ static void bench_gemm(const char* name, int mode, int M, int N, int Cin, int H,
                 ms[k].push_back(t.run([&] { st = launch_gemm(g, DSIM_BF16, 0); }, iters));
             }
         g_gemm_skinny = 1; g_skinny_tile = 0;
-        int hb, hn;
-        gemm_skinny_tile(g, &hb, &hn);
+        const int hb = plan.bm, hn = plan.bn;           // (planned above, under the sweep's rule and no tile override)
         printf("  small-batch median ms: gemm_kernel %.4f | 64x64 %.4f | 128x64 %.4f | 64x128 %.4f | 128x128 %.4f | 128x160 %.4f | 64x80 %.4f | 128x80 %.4f | heuristic %dx%d\n",
                (std::sort(ms[0].begin(), ms[0].end()), ms[0][rounds / 2]), (std::sort(ms[1].begin(), ms[1].end()), ms[1][rounds / 2]),
                (std::sort(ms[2].begin(), ms[2].end()), ms[2][rounds / 2]), (std::sort(ms[3].begin(), ms[3].end()), ms[3][rounds / 2]),
@@ -194,8 +194,8 @@ static void bench_gemm(const char* name, int mode, int M, int N, int Cin, int H,
         HC(hipFree(sb));
     }
 #endif
-    int bm, bn;
-    gemm_launch_tile(g, DSIM_BF16, &bm, &bn);
+    (void)gemm_plan(g, DSIM_BF16, &plan);               // the "auto" column's instantiation
+    const int bm = plan.bm, bn = plan.bn;
     unsigned long long csum = 0;
     {
         unsigned long long* dc;
