@@ -12,6 +12,8 @@
 //   2. gn_apply : folds the slab partials in fixed order, then y = (x-mean)*rstd*gamma+beta
 //                 [*sigmoid] with 16-byte loads and stores.
 // No float atomics anywhere: results are bit-reproducible and independent of batch size.
+#include <type_traits>
+
 #include "common.h"
 
 namespace dsim {
@@ -45,12 +47,107 @@ __device__ __forceinline__ typename Vec16<T>::type load_slot(const T* x0, int C0
                    : *reinterpret_cast<const V*>(x1 + row * C1 + (ch - C0));
 }
 
+// full 64-lane xor trees, and the one over the LPR (a power of two <= 64) adjacent lanes that share a row
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+    return v;
+}
+__device__ __forceinline__ float lpr_sum(float v, int LPR) {
+    if (LPR > 32) v += __shfl_xor(v, 32);
+    if (LPR > 16) v += __shfl_xor(v, 16);
+    if (LPR > 8) v += __shfl_xor(v, 8);
+    if (LPR > 4) v += __shfl_xor(v, 4);
+    if (LPR > 2) v += __shfl_xor(v, 2);
+    if (LPR > 1) v += __shfl_xor(v, 1);
+    return v;
+}
+
+// ---- the f64 (sum, sum of squares) folds.  Their order is what makes a batch of N score bit for bit like N single images: it
+// depends on the shape only, and it is written here once.
+// xor tree over w (a power of two <= 64) adjacent lanes
+__device__ __forceinline__ void gn_pair_tree(double& a, double& q, int w) {
+    for (int off = w >> 1; off > 0; off >>= 1) {
+        a += __shfl_xor(a, off, 64);
+        q += __shfl_xor(q, off, 64);
+    }
+}
+// the per-wave pairs through s_w, then the lead thread of nw consecutive waves sums them in wave order, from wave w0
+__device__ __forceinline__ void gn_pair_waves(double (*s_w)[2], int tid, bool lead, int w0, int nw, double& a, double& q) {
+    if ((tid & 63) == 0) { s_w[tid >> 6][0] = a; s_w[tid >> 6][1] = q; }
+    __syncthreads();
+    if (lead) {
+        a = 0.0; q = 0.0;
+        for (int k = 0; k < nw; ++k) { a += s_w[w0 + k][0]; q += s_w[w0 + k][1]; }
+    }
+}
+// Fold of the R x cpg per-channel f32 partials of each of `ngroups` groups, lds[R][stride][2]: the tg = GN_THREADS / (groups rounded
+// up to a power of two) threads of group g take a fixed strided subset each (thread t: partials t, t + tg, ...), then a fixed
+// xor-shuffle tree and, where a group is wider than a wave (fewer than 4 groups), a last serial fold of the per-wave sums.  The pair
+// of group g is thread t == 0's (a, q).  (One thread per group walking the list serially held the whole workgroup -- and, with every
+// workgroup of the launch in the same phase, the chip -- for several microseconds.)  Holds a barrier when tg > 64: uniform calls only.
+template <bool RAGGED>      // RAGGED: tg * ngroups may fall short of the workgroup (ngroups no power of two); threads past the last group idle
+__device__ __forceinline__ void gn_group_fold(const float* lds, int stride, int R, int cpg, int ngroups, int tg, int tid, int& g,
+                                              int& t, double& a, double& q) {
+    __shared__ double s_w[GN_THREADS / 64][2];
+    g = tid / tg;
+    t = tid - g * tg;
+    const int cnt = R * cpg;
+    a = 0.0; q = 0.0;
+    if (!RAGGED || g < ngroups)
+        for (int i = t; i < cnt; i += tg) {
+            const int rr = i / cpg, c = g * cpg + (i - rr * cpg);
+            const float2 pr = *reinterpret_cast<const float2*>(&lds[((size_t)rr * stride + c) * 2]);
+            a += (double)pr.x;
+            q += (double)pr.y;
+        }
+    gn_pair_tree(a, q, tg < 64 ? tg : 64);
+    if (tg > 64) gn_pair_waves(s_w, tid, t == 0, g * (tg / 64), tg / 64, a, q);
+}
+__device__ __forceinline__ void gn_mean_rstd(double a, double q, double n, float eps, float* mean, float* rstd) {
+    const double m = a / n;
+    double var = q / n - m * m;
+    if (var < 0.0) var = 0.0;
+    *mean = (float)m;
+    *rstd = (float)(1.0 / sqrt(var + (double)eps));
+}
+
+// one 16-byte vector into its channels' f32 partials
+template <typename T>
+__device__ __forceinline__ void gn_accum(const typename Vec16<T>::type& v, float (&s1)[Vec16<T>::N], float (&s2)[Vec16<T>::N]) {
+#pragma unroll
+    for (int e = 0; e < Vec16<T>::N; ++e) {
+        const float f = (float)v[e];
+        s1[e] += f;
+        s2[e] = fmaf(f, f, s2[e]);
+    }
+}
+// y = x * sc + sh [* sigmoid], rounded to T, one 16-byte store
+template <typename T, bool SILU>
+__device__ __forceinline__ void gn_out(const typename Vec16<T>::type& v, const float (&sc)[Vec16<T>::N], const float (&sh)[Vec16<T>::N],
+                                       T* dst) {
+    typename Vec16<T>::type o;
+#pragma unroll
+    for (int e = 0; e < Vec16<T>::N; ++e) {
+        float y = fmaf((float)v[e], sc[e], sh[e]);
+        if (SILU) y = silu_fast(y);
+        o[e] = (T)y;
+    }
+    *reinterpret_cast<typename Vec16<T>::type*>(dst) = o;
+}
+
 // grid (chunks, B); NS = channel slots per thread, UNR = rows in flight per thread
 template <typename T, int NS, int UNR>
 __global__ __launch_bounds__(GN_THREADS) void gn_stats_kernel(const T* __restrict__ x0, int C0,
                                                               const T* __restrict__ x1, int C1, int HW,
                                                               int groups, double* __restrict__ part) {
     constexpr int VEC = Vec16<T>::N;
+    typedef typename Vec16<T>::type V;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int C = C0 + C1, S = C / VEC;
     const int tpr = S < GN_THREADS ? S : GN_THREADS;          // threads per row
@@ -68,7 +165,6 @@ __global__ __launch_bounds__(GN_THREADS) void gn_stats_kernel(const T* __restric
 
     if (trow < R) {
         // UNR rows in flight per thread: all loads of a batch are issued before the first is consumed
-        typedef typename Vec16<T>::type V;
         int r = r0 + trow;
         for (; r + (UNR - 1) * R < r1; r += UNR * R) {
             V v[UNR][NS];
@@ -82,32 +178,15 @@ __global__ __launch_bounds__(GN_THREADS) void gn_stats_kernel(const T* __restric
 #pragma unroll
             for (int u = 0; u < UNR; ++u)
 #pragma unroll
-                for (int k = 0; k < NS; ++k) {
-                    const int slot = tcol + k * tpr;
-                    if (slot < S) {
-#pragma unroll
-                        for (int e = 0; e < VEC; ++e) {
-                            const float f = (float)v[u][k][e];
-                            s1[k][e] += f;
-                            s2[k][e] = fmaf(f, f, s2[k][e]);
-                        }
-                    }
-                }
+                for (int k = 0; k < NS; ++k)
+                    if (tcol + k * tpr < S) gn_accum<T>(v[u][k], s1[k], s2[k]);
         }
+        if constexpr (UNR > 1)      // (UNR = 1: the loop above takes every row)
         for (; r < r1; r += R) {
-            const size_t row = (size_t)b * HW + r;
 #pragma unroll
             for (int k = 0; k < NS; ++k) {
                 const int slot = tcol + k * tpr;
-                if (slot < S) {
-                    auto v = load_slot<T>(x0, C0, x1, C1, row, slot * VEC);
-#pragma unroll
-                    for (int e = 0; e < VEC; ++e) {
-                        const float f = (float)v[e];
-                        s1[k][e] += f;
-                        s2[k][e] = fmaf(f, f, s2[k][e]);
-                    }
-                }
+                if (slot < S) gn_accum<T>(load_slot<T>(x0, C0, x1, C1, (size_t)b * HW + r, slot * VEC), s1[k], s2[k]);
             }
         }
     }
@@ -127,43 +206,15 @@ __global__ __launch_bounds__(GN_THREADS) void gn_stats_kernel(const T* __restric
         }
     }
     __syncthreads();
-    // GN_THREADS / gp2 threads per group (gp2 = groups rounded up to a power of two) fold a fixed strided subset of the
-    // group's R x cpg partials in f64, then a fixed xor-shuffle tree: same order for a given shape, and no single thread
-    // walking the whole list while the workgroup waits
     int gp2 = 1;
     while (gp2 < groups) gp2 *= 2;
-    const int tg = GN_THREADS / gp2;                           // >= 4 (groups <= 64)
-    {
-        const int cpg = C / groups;
-        const int g = tid / tg, t = tid - g * tg, cnt = R * cpg;
-        double a = 0.0, q = 0.0;
-        if (g < groups)
-            for (int i = t; i < cnt; i += tg) {
-                const int rr = i / cpg, c = g * cpg + (i - rr * cpg);
-                const float2 pr = *reinterpret_cast<const float2*>(&lds[((size_t)rr * C + c) * 2]);
-                a += (double)pr.x;
-                q += (double)pr.y;
-            }
-        for (int off = tg >> 1; off > 0; off >>= 1) {          // tg <= 64 whenever groups >= 4; wider: see below
-            if (off < 64) {
-                a += __shfl_xor(a, off, 64);
-                q += __shfl_xor(q, off, 64);
-            }
-        }
-        if (tg > 64) {                                         // fewer than 4 groups: a group spans tg / 64 waves
-            __shared__ double s_w[4][2];
-            if ((tid & 63) == 0) { s_w[tid >> 6][0] = a; s_w[tid >> 6][1] = q; }
-            __syncthreads();
-            if (t == 0) {
-                a = 0.0; q = 0.0;
-                for (int k = 0; k < tg / 64; ++k) { a += s_w[g * (tg / 64) + k][0]; q += s_w[g * (tg / 64) + k][1]; }
-            }
-        }
-        if (t == 0 && g < groups) {
-            double* o = part + (((size_t)b * chunks + chunk) * groups + g) * 2;
-            o[0] = a;
-            o[1] = q;
-        }
+    int g, t;
+    double a, q;
+    gn_group_fold<true>(lds, C, R, C / groups, groups, GN_THREADS / gp2, tid, g, t, a, q);     // >= 4 threads per group (groups <= 64)
+    if (t == 0 && g < groups) {
+        double* o = part + (((size_t)b * chunks + chunk) * groups + g) * 2;
+        o[0] = a;
+        o[1] = q;
     }
 }
 
@@ -184,16 +235,9 @@ __global__ __launch_bounds__(GN_THREADS) void gn_fold_kernel(const float* __rest
             a += (double)pr.x;
             q += (double)pr.y;
         }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        a += __shfl_xor(a, off, 64);
-        q += __shfl_xor(q, off, 64);
-    }
-    if ((tid & 63) == 0) { s_w[tid >> 6][0] = a; s_w[tid >> 6][1] = q; }
-    __syncthreads();
+    gn_pair_tree(a, q, 64);
+    gn_pair_waves(s_w, tid, tid == 0, 0, GN_THREADS / 64, a, q);
     if (tid == 0) {
-        a = 0.0; q = 0.0;
-        for (int w = 0; w < GN_THREADS / 64; ++w) { a += s_w[w][0]; q += s_w[w][1]; }
         out[((size_t)b * groups + g) * 2] = a;
         out[((size_t)b * groups + g) * 2 + 1] = q;
     }
@@ -240,14 +284,7 @@ __global__ __launch_bounds__(GN_THREADS) void gn_apply_kernel(const T* __restric
             }
         a += __shfl_xor(a, 2, 64); q += __shfl_xor(q, 2, 64);
         a += __shfl_xor(a, 1, 64); q += __shfl_xor(q, 1, 64);
-        if (t == 0 && g < groups) {
-            const double n = (double)HW * cpg;
-            const double mean = a / n;
-            double var = q / n - mean * mean;
-            if (var < 0.0) var = 0.0;
-            s_mean[g] = (float)mean;
-            s_rstd[g] = (float)(1.0 / sqrt(var + (double)eps));
-        }
+        if (t == 0 && g < groups) gn_mean_rstd(a, q, (double)HW * cpg, eps, &s_mean[g], &s_rstd[g]);
     }
     __syncthreads();
     if (trow >= R) return;
@@ -285,34 +322,16 @@ __global__ __launch_bounds__(GN_THREADS) void gn_apply_kernel(const T* __restric
 #pragma unroll
             for (int k = 0; k < NS; ++k) {
                 const int slot = tcol + k * tpr;
-                if (slot < S) {
-                    V o;
-#pragma unroll
-                    for (int e = 0; e < VEC; ++e) {
-                        float y = fmaf((float)v[u][k][e], sc[k][e], sh[k][e]);
-                        if (SILU) y = silu_fast(y);
-                        o[e] = (T)y;
-                    }
-                    *reinterpret_cast<V*>(out + ((size_t)b * HW + r + u * R) * C + slot * VEC) = o;
-                }
+                if (slot < S) gn_out<T, SILU>(v[u][k], sc[k], sh[k], out + ((size_t)b * HW + r + u * R) * C + slot * VEC);
             }
     }
+    if constexpr (UNR > 1)
     for (; r < r1; r += R) {
         const size_t row = (size_t)b * HW + r;
 #pragma unroll
         for (int k = 0; k < NS; ++k) {
             const int slot = tcol + k * tpr;
-            if (slot < S) {
-                V v = load_slot<T>(x0, C0, x1, C1, row, slot * VEC);
-                V o;
-#pragma unroll
-                for (int e = 0; e < VEC; ++e) {
-                    float y = fmaf((float)v[e], sc[k][e], sh[k][e]);
-                    if (SILU) y = silu_fast(y);
-                    o[e] = (T)y;
-                }
-                *reinterpret_cast<V*>(out + row * C + slot * VEC) = o;
-            }
+            if (slot < S) gn_out<T, SILU>(load_slot<T>(x0, C0, x1, C1, row, slot * VEC), sc[k], sh[k], out + row * C + slot * VEC);
         }
     }
 }
@@ -355,9 +374,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const T* __restrict__ x,
                 sum += v[k][e];
             }
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
-        const float mean = sum / (float)C;
+        const float mean = wave_sum(sum) / (float)C;
         float sq = 0.f;
 #pragma unroll
         for (int k = 0; k < MAXS; ++k) {
@@ -367,9 +384,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const T* __restrict__ x,
                 for (int e = 0; e < VEC; ++e) { const float d = v[k][e] - mean; sq = fmaf(d, d, sq); }
             }
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o);
-        const float rstd = 1.0f / sqrtf(sq / (float)C + eps);
+        const float rstd = 1.0f / sqrtf(wave_sum(sq) / (float)C + eps);
         T* orow = out + (size_t)row * C;
 #pragma unroll
         for (int k = 0; k < MAXS; ++k) {
@@ -435,25 +450,13 @@ __global__ __launch_bounds__(256) void layernorm_rows_kernel(const T* __restrict
         for (int k = 0; k < CPL; ++k)
 #pragma unroll
             for (int e = 0; e < VEC; ++e) { v[k][e] = (float)t[k][e]; sum += v[k][e]; }
-        if (LPR > 32) sum += __shfl_xor(sum, 32);
-        if (LPR > 16) sum += __shfl_xor(sum, 16);
-        if (LPR > 8) sum += __shfl_xor(sum, 8);
-        if (LPR > 4) sum += __shfl_xor(sum, 4);
-        if (LPR > 2) sum += __shfl_xor(sum, 2);
-        if (LPR > 1) sum += __shfl_xor(sum, 1);
-        const float mean = sum * invC;
+        const float mean = lpr_sum(sum, LPR) * invC;
         float sq = 0.f;
 #pragma unroll
         for (int k = 0; k < CPL; ++k)
 #pragma unroll
             for (int e = 0; e < VEC; ++e) { v[k][e] -= mean; sq = fmaf(v[k][e], v[k][e], sq); }
-        if (LPR > 32) sq += __shfl_xor(sq, 32);
-        if (LPR > 16) sq += __shfl_xor(sq, 16);
-        if (LPR > 8) sq += __shfl_xor(sq, 8);
-        if (LPR > 4) sq += __shfl_xor(sq, 4);
-        if (LPR > 2) sq += __shfl_xor(sq, 2);
-        if (LPR > 1) sq += __shfl_xor(sq, 1);
-        const float rstd = 1.0f / sqrtf(sq * invC + eps);
+        const float rstd = 1.0f / sqrtf(lpr_sum(sq, LPR) * invC + eps);
         if (row < M) {
             T* orow = out + (size_t)row * C;
 #pragma unroll
@@ -468,77 +471,6 @@ __global__ __launch_bounds__(256) void layernorm_rows_kernel(const T* __restrict
 #pragma unroll
         for (int k = 0; k < CPL; ++k) t[k] = tn[k];
     }
-}
-
-// The LayerNorm dispatch, decided in one place: ln_typed launches what this returns and layernorm_plan() reports it.
-//   form 0, layernorm_rows_kernel<T, CPL>: affine only, S = C / VEC <= 80 chunks with S / LPR (LPR = the largest power of two
-//           dividing S, at most 64) one of 1 / 3 / 5; rows per workgroup = 4 waves x passes x (64 / LPR);
-//   form 1, layernorm_kernel<T, MOD, MAXS, RPW>: every other width up to 64 * 6 * VEC; rows per workgroup = 4 x RPW.
-template <typename T>
-int ln_plan(int M, int C, bool mod, dsim_ln_plan* p) {
-    constexpr int VEC = Vec16<T>::N;
-    if (C < VEC || C % VEC || C > 64 * 6 * VEC || M < 1) return DSIM_ERR_INVALID;
-    const int S = C / VEC;
-    *p = dsim_ln_plan{};
-    if (!mod && S <= 80) {      // wider rows: the wave-per-row form below already streams at > 6 TB/s
-        int LPR = 1;
-        while (LPR < 64 && S % (LPR * 2) == 0) LPR *= 2;
-        const int CPL = S / LPR;                       // odd by construction
-        if (CPL == 1 || CPL == 3 || CPL == 5) {
-            const int rpw = 64 / LPR;
-            int passes = 4;                                             // rows per workgroup = 4 waves x passes x rpw
-            while (passes > 1 && (M + 4 * passes * rpw - 1) / (4 * passes * rpw) < 2048) passes >>= 1;
-            p->form = 0; p->LPR = LPR; p->CPL = CPL; p->passes = passes;
-            p->blocks = (M + 4 * passes * rpw - 1) / (4 * passes * rpw);
-            return DSIM_OK;
-        }
-    }
-    p->form = 1;
-    if (S <= 64) { p->MAXS = 1; p->RPW = 8; }
-    else if (S <= 128) { p->MAXS = 2; p->RPW = 2; }
-    else if (S <= 192) { p->MAXS = 3; p->RPW = 2; }
-    else { p->MAXS = 6; p->RPW = 1; }
-    p->blocks = (M + 4 * p->RPW - 1) / (4 * p->RPW);
-    return DSIM_OK;
-}
-
-template <typename T, int CPL>
-void ln_rows_launch(const void* x, const float* gamma, const float* beta, void* out, int M, int C, float eps,
-                    const dsim_ln_plan& p, hipStream_t s) {
-    hipLaunchKernelGGL((layernorm_rows_kernel<T, CPL>), dim3(p.blocks), dim3(256), (size_t)2 * C * sizeof(float), s,
-                       (const T*)x, gamma, beta, (T*)out, M, C, eps, p.LPR, p.passes);
-}
-
-template <typename T, bool MOD, int MAXS, int RPW>
-void ln_wave_launch(const void* x, const float* gamma, const float* beta, void* out, int M, int C, float eps, int rpb,
-                    const dsim_ln_plan& p, hipStream_t s) {
-    hipLaunchKernelGGL((layernorm_kernel<T, MOD, MAXS, RPW>), dim3(p.blocks), dim3(256), 0, s, (const T*)x, gamma, beta,
-                       (T*)out, M, C, eps, rpb);
-}
-
-template <typename T, bool MOD>
-int ln_typed(const void* x, const float* gamma, const float* beta, void* out, int M, int C, float eps, int rpb,
-             hipStream_t s) {
-    dsim_ln_plan p;
-    if (ln_plan<T>(M, C, MOD, &p) != DSIM_OK) return DSIM_ERR_INVALID;
-    if (p.form == 0) {
-        if constexpr (!MOD) {
-            switch (p.CPL) {
-                case 1: ln_rows_launch<T, 1>(x, gamma, beta, out, M, C, eps, p, s); break;
-                case 3: ln_rows_launch<T, 3>(x, gamma, beta, out, M, C, eps, p, s); break;
-                default: ln_rows_launch<T, 5>(x, gamma, beta, out, M, C, eps, p, s); break;
-            }
-        }
-    } else if (p.MAXS == 1)
-        ln_wave_launch<T, MOD, 1, 8>(x, gamma, beta, out, M, C, eps, rpb, p, s);
-    else if (p.MAXS == 2)
-        ln_wave_launch<T, MOD, 2, 2>(x, gamma, beta, out, M, C, eps, rpb, p, s);
-    else if (p.MAXS == 3)
-        ln_wave_launch<T, MOD, 3, 2>(x, gamma, beta, out, M, C, eps, rpb, p, s);
-    else
-        ln_wave_launch<T, MOD, 6, 1>(x, gamma, beta, out, M, C, eps, rpb, p, s);
-    DSIM_HIP_CHECK(hipGetLastError());
-    return DSIM_OK;
 }
 
 // softmax over rows of `cols` elements (one 256-thread workgroup per row; cols % VEC == 0).  Used by
@@ -560,8 +492,7 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const T* __restrict__
 #pragma unroll
         for (int e = 0; e < VEC; ++e) m = fmaxf(m, (float)v[e]);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    m = wave_max(m);
     if (lane == 0) red[wave] = m;
     __syncthreads();
     m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
@@ -572,8 +503,7 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const T* __restrict__
 #pragma unroll
         for (int e = 0; e < VEC; ++e) sum += exp2f(fmaf((float)v[e], scale_log2, -mb));
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+    sum = wave_sum(sum);
     if (lane == 0) red[4 + wave] = sum;
     __syncthreads();
     const float inv = 1.0f / ((red[4] + red[5]) + (red[6] + red[7]));
@@ -621,14 +551,7 @@ __global__ __launch_bounds__(GN_THREADS) void gn_onepass_kernel(const T* __restr
 #pragma unroll
         for (int i = 0; i < MAXCH; ++i) {
             const int r = trow + i * R;
-            if (r < HW) {
-#pragma unroll
-                for (int e = 0; e < VEC; ++e) {
-                    const float f = (float)v[i][e];
-                    s1[e] += f;
-                    s2[e] = fmaf(f, f, s2[e]);
-                }
-            }
+            if (r < HW) gn_accum<T>(v[i], s1, s2);
         }
     }
     float* lds = reinterpret_cast<float*>(smem_op);            // [R][CS][2]
@@ -640,81 +563,152 @@ __global__ __launch_bounds__(GN_THREADS) void gn_onepass_kernel(const T* __restr
         }
     }
     __syncthreads();
-    // fold of a group's R x cpg channel partials in f64: tg = GN_THREADS / gslab threads per group take a fixed strided
-    // subset each, then a fixed xor-shuffle tree (and, for groups wider than a wave, a last serial fold of the per-wave
-    // sums).  The order depends on the shape only.  (One thread per group walking the list serially held the whole
-    // workgroup -- and, with every workgroup of the launch in the same phase, the chip -- for several microseconds.)
     const int gslab = CS / cpg;                                // whole groups in this slab (a power of two)
-    const int tg = GN_THREADS / gslab;                         // threads per group: 8 .. 256
-    {
-        const int g = tid / tg, t = tid - g * tg, cnt = R * cpg;
-        double a = 0.0, q = 0.0;
-        for (int i = t; i < cnt; i += tg) {
-            const int rr = i / cpg, c = g * cpg + (i - rr * cpg);
-            const float2 pr = *reinterpret_cast<const float2*>(&lds[((size_t)rr * CS + c) * 2]);
-            a += (double)pr.x;
-            q += (double)pr.y;
-        }
-        const int w = tg < 64 ? tg : 64;
-        for (int off = w >> 1; off > 0; off >>= 1) {
-            a += __shfl_xor(a, off, 64);
-            q += __shfl_xor(q, off, 64);
-        }
-        __shared__ double s_wsum[4][2];                        // per-wave sums when a group spans several waves
-        if (tg > 64) {
-            if ((tid & 63) == 0) { s_wsum[tid >> 6][0] = a; s_wsum[tid >> 6][1] = q; }
-            __syncthreads();
-            if (t == 0) {
-                a = 0.0; q = 0.0;
-                for (int k = 0; k < tg / 64; ++k) { a += s_wsum[g * (tg / 64) + k][0]; q += s_wsum[g * (tg / 64) + k][1]; }
-            }
-        }
-        if (t == 0) {
-            const double n = (double)HW * cpg;
-            const double mean = a / n;
-            double var = q / n - mean * mean;
-            if (var < 0.0) var = 0.0;
-            s_mean[g] = (float)mean;
-            s_rstd[g] = (float)(1.0 / sqrt(var + (double)eps));
-        }
-    }
+    int g, t;
+    double a, q;
+    gn_group_fold<false>(lds, CS, R, cpg, gslab, GN_THREADS / gslab, tid, g, t, a, q);          // 8 .. 256 threads per group
+    if (t == 0) gn_mean_rstd(a, q, (double)HW * cpg, eps, &s_mean[g], &s_rstd[g]);
     __syncthreads();
     if (!live) return;
     float sc[VEC], sh[VEC];
 #pragma unroll
     for (int e = 0; e < VEC; ++e) {
-        const int c = ch + e, g = (c - c0) / cpg;
-        const float w = gamma[c] * s_rstd[g];
+        const int c = ch + e, cg = (c - c0) / cpg;
+        const float w = gamma[c] * s_rstd[cg];
         sc[e] = w;
-        sh[e] = beta[c] - s_mean[g] * w;
+        sh[e] = beta[c] - s_mean[cg] * w;
     }
 #pragma unroll
     for (int i = 0; i < MAXCH; ++i) {
         const int r = trow + i * R;
-        if (r < HW) {
-            V o;
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) {
-                float y = fmaf((float)v[i][e], sc[e], sh[e]);
-                if (SILU) y = silu_fast(y);
-                o[e] = (T)y;
-            }
-            *reinterpret_cast<V*>(out + ((size_t)b * HW + r) * C + ch) = o;
+        if (r < HW) gn_out<T, SILU>(v[i], sc, sh, out + ((size_t)b * HW + r) * C + ch);
+    }
+}
+
+// ---- host side: one launch helper, one table per kernel family, one plan per operator.
+// Every kernel of this file runs 256 threads.  A pointer argument is cast to the kernel's parameter type (void* -> T*); any other
+// argument must already have it.
+static_assert(GN_THREADS == 256, "the LayerNorm and softmax kernels index with 256 threads");
+template <typename P, typename A>
+P kernel_arg(A a) {
+    if constexpr (std::is_pointer<P>::value) {
+        return static_cast<P>(a);
+    } else {
+        static_assert(std::is_same<P, A>::value, "scalar kernel arguments are passed in the parameter's own type");
+        return a;
+    }
+}
+template <typename... P, typename... A>
+int launch(void (*kern)(P...), dim3 grid, size_t lds, hipStream_t s, A... args) {
+    hipLaunchKernelGGL(kern, grid, dim3(GN_THREADS), lds, s, kernel_arg<P>(args)...);
+    DSIM_HIP_CHECK(hipGetLastError());
+    return DSIM_OK;
+}
+
+// f(Elem<T>{}) for the element type of `dtype`
+template <typename T> struct Elem { typedef T type; };
+template <typename F>
+int by_dtype(int dtype, F&& f) {
+    switch (dtype) {
+        case DSIM_BF16: return f(Elem<bf16_t>{});
+        case DSIM_F16: return f(Elem<f16_t>{});
+        case DSIM_F32: return f(Elem<float>{});
+    }
+    return DSIM_ERR_INVALID;
+}
+
+// The compiled kernels, each instantiation named once; the plans choose a row and the launchers start that row, so a plan
+// outside a table is DSIM_ERR_INVALID.  [2]: without / with SiLU (GroupNorm), affine / modulated (LayerNorm).
+template <typename T> struct GnTwoPass {
+    int NS, UNR;                                                // a thread's channel slots, and its rows in flight
+    decltype(&gn_stats_kernel<T, 1, 1>) stats;
+    decltype(&gn_apply_kernel<T, false, 1, 1>) apply[2];
+};
+template <typename T, int NS, int UNR>
+constexpr GnTwoPass<T> gn_two_pass() {
+    return {NS, UNR, gn_stats_kernel<T, NS, UNR>, {gn_apply_kernel<T, false, NS, UNR>, gn_apply_kernel<T, true, NS, UNR>}};
+}
+template <typename T> constexpr GnTwoPass<T> kGnTwoPass[] = {gn_two_pass<T, 1, 4>(), gn_two_pass<T, 2, 2>(), gn_two_pass<T, GN_MAX_SLOTS, 1>()};
+
+constexpr int GN_OP_MAXCH = 24;
+template <typename T> constexpr decltype(&gn_onepass_kernel<T, false, GN_OP_MAXCH>) kGnOnePass[2] = {
+    gn_onepass_kernel<T, false, GN_OP_MAXCH>, gn_onepass_kernel<T, true, GN_OP_MAXCH>};
+
+template <typename T> struct LnRows {
+    int CPL;
+    decltype(&layernorm_rows_kernel<T, 1>) kern;
+};
+template <typename T> constexpr LnRows<T> kLnRows[] = {{1, layernorm_rows_kernel<T, 1>}, {3, layernorm_rows_kernel<T, 3>}, {5, layernorm_rows_kernel<T, 5>}};
+
+template <typename T> struct LnWave {
+    int MAXS, RPW;                                              // rows up to 64 * MAXS chunks, RPW of them per wave
+    decltype(&layernorm_kernel<T, false, 1, 1>) kern[2];
+};
+template <typename T, int MAXS, int RPW>
+constexpr LnWave<T> ln_wave() { return {MAXS, RPW, {layernorm_kernel<T, false, MAXS, RPW>, layernorm_kernel<T, true, MAXS, RPW>}}; }
+template <typename T> constexpr LnWave<T> kLnWave[] = {ln_wave<T, 1, 8>(), ln_wave<T, 2, 2>(), ln_wave<T, 3, 2>(), ln_wave<T, 6, 1>()};
+
+// The LayerNorm dispatch, decided in one place: ln_typed launches what this returns and layernorm_plan() reports it.
+//   form 0, layernorm_rows_kernel<T, CPL>: affine only, S = C / VEC <= 80 chunks with S / LPR (LPR = the largest power of two
+//           dividing S, at most 64) a CPL of kLnRows; rows per workgroup = 4 waves x passes x (64 / LPR);
+//   form 1, layernorm_kernel<T, MOD, MAXS, RPW>: every other width, on the narrowest row of kLnWave; rows per workgroup = 4 x RPW.
+struct LnLaunch {
+    dsim_ln_plan p;
+    int row;                    // of kLnRows (form 0) / kLnWave (form 1)
+    size_t lds;
+};
+template <typename T>
+int ln_plan(int M, int C, bool mod, LnLaunch* l) {
+    constexpr int VEC = Vec16<T>::N;
+    if (C < VEC || C % VEC || C > 64 * 6 * VEC || M < 1) return DSIM_ERR_INVALID;
+    const int S = C / VEC;
+    *l = LnLaunch{};
+    dsim_ln_plan* p = &l->p;
+    if (!mod && S <= 80) {      // wider rows: the wave-per-row form below already streams at > 6 TB/s
+        int LPR = 1;
+        while (LPR < 64 && S % (LPR * 2) == 0) LPR *= 2;
+        const int CPL = S / LPR;                       // odd by construction
+        for (const LnRows<T>& k : kLnRows<T>) {
+            if (k.CPL != CPL) continue;
+            l->row = (int)(&k - kLnRows<T>);
+            const int rpw = 64 / LPR;
+            int passes = 4;                                             // rows per workgroup = 4 waves x passes x rpw
+            while (passes > 1 && (M + 4 * passes * rpw - 1) / (4 * passes * rpw) < 2048) passes >>= 1;
+            p->form = 0; p->LPR = LPR; p->CPL = CPL; p->passes = passes;
+            p->blocks = (M + 4 * passes * rpw - 1) / (4 * passes * rpw);
+            l->lds = (size_t)2 * C * sizeof(float);                     // gamma and beta
+            return DSIM_OK;
         }
     }
+    for (const LnWave<T>& k : kLnWave<T>) {
+        if (S > 64 * k.MAXS) continue;
+        l->row = (int)(&k - kLnWave<T>);
+        p->form = 1; p->MAXS = k.MAXS; p->RPW = k.RPW;
+        p->blocks = (M + 4 * k.RPW - 1) / (4 * k.RPW);
+        return DSIM_OK;
+    }
+    return DSIM_ERR_INVALID;
+}
+
+template <typename T, bool MOD>
+int ln_typed(const void* x, const float* gamma, const float* beta, void* out, int M, int C, float eps, int rpb,
+             hipStream_t s) {
+    LnLaunch l;
+    if (ln_plan<T>(M, C, MOD, &l) != DSIM_OK) return DSIM_ERR_INVALID;
+    const dsim_ln_plan& p = l.p;
+    if (p.form == 0) return launch(kLnRows<T>[l.row].kern, dim3(p.blocks), l.lds, s, x, gamma, beta, out, M, C, eps, p.LPR, p.passes);
+    return launch(kLnWave<T>[l.row].kern[MOD], dim3(p.blocks), l.lds, s, x, gamma, beta, out, M, C, eps, rpb);
 }
 
 // slab width (channels) of the one-pass form for this shape, or 0 when it does not apply: whole groups, 16-byte chunk
 // columns of at least 256 B per row, no slab straddling the two concat sources, at most MAXCH chunks per thread
-constexpr int GN_OP_MAXCH = 24;
 template <typename T>
-int gn_onepass_slab(int C0, int C1, int B, int HW, int groups) {
+int gn_onepass_slab(int C0, int C1, int HW, int groups) {
     constexpr int VEC = Vec16<T>::N;
     const int C = C0 + C1, cpg = C / groups;
-    // The choice depends on the SHAPE only, never on the batch: slab width sets the summation grouping, and a batch of N
-    // must score bit for bit like N single images.  Widest legal slab = longest coalesced row segments (narrower slabs
-    // with more, shorter workgroups measured slower at the 8 x 8 level: 17.7 vs 16.8 us, 29 vs 22 us at 2560 channels).
-    (void)B;
+    // The choice depends on the SHAPE only, never on the batch (which is why no batch size is passed): slab width sets the summation
+    // grouping, and a batch of N must score bit for bit like N single images.  Widest legal slab = longest coalesced row segments
+    // (narrower slabs with more, shorter workgroups measured slower at the 8 x 8 level: 17.7 vs 16.8 us, 29 vs 22 us at 2560 channels).
     int best = 0;
     for (int gs = 1; gs <= groups; gs *= 2) {                  // groups per slab
         const int CS = gs * cpg;
@@ -730,45 +724,33 @@ int gn_onepass_slab(int C0, int C1, int B, int HW, int groups) {
     return best;
 }
 
-template <typename T, int NS, int UNR>
-int gn_launch(const void* x0, int C0, const void* x1, int C1, const float* gamma, const float* beta, void* out, int B,
-              int HW, int groups, float eps, int silu, void* scratch, int chunks, int rb, size_t lds, hipStream_t s,
-              const float* pre = nullptr, int pre_chunks = 0) {
-    if (pre) {
-        // the statistics pass already happened in the producing conv's epilogue (GemmArgs.gn_part): fold its per-(wave, 4-channel quad)
-        // f32 partials into one f64 pair per (image, group), in fixed order
-        hipLaunchKernelGGL(gn_fold_kernel, dim3(groups, B), dim3(GN_THREADS), 0, s, pre, pre_chunks, (C0 + C1) / 4, groups, (double*)scratch);
-        chunks = 1;
-    } else
-    hipLaunchKernelGGL((gn_stats_kernel<T, NS, UNR>), dim3(chunks, B), dim3(GN_THREADS), lds, s, (const T*)x0, C0,
-                       (const T*)x1, C1, HW, groups, (double*)scratch);
-    const size_t alds = (size_t)chunks * groups * 2 * sizeof(double);       // <= 32 KB
-    if (silu)
-        hipLaunchKernelGGL((gn_apply_kernel<T, true, NS, UNR>), dim3(rb, B), dim3(GN_THREADS), alds, s, (const T*)x0, C0,
-                           (const T*)x1, C1, gamma, beta, (T*)out, HW, groups, eps, chunks, (const double*)scratch);
-    else
-        hipLaunchKernelGGL((gn_apply_kernel<T, false, NS, UNR>), dim3(rb, B), dim3(GN_THREADS), alds, s, (const T*)x0, C0,
-                           (const T*)x1, C1, gamma, beta, (T*)out, HW, groups, eps, chunks, (const double*)scratch);
-    DSIM_HIP_CHECK(hipGetLastError());
-    return DSIM_OK;
-}
-
 // The GroupNorm dispatch, decided in one place: gn_typed launches what this returns and groupnorm_plan() reports it.
 //   form 0, one launch of gn_onepass_kernel: slab width CS (gn_onepass_slab), tpr = CS / VEC threads per row, R rows in flight;
-//   form 1, gn_stats_kernel + gn_apply_kernel<NS, UNR>: `chunks` statistic slabs and rb apply row blocks per image;
-//   form 2, gn_fold_kernel + gn_apply_kernel: the statistics come from a conv epilogue (chunks = 1 after the fold).
+//   form 1, gn_stats_kernel + gn_apply_kernel<NS, UNR> (the row of kGnTwoPass with room for the slots a thread owns): `chunks`
+//           statistic slabs and rb apply row blocks per image;
+//   form 2, gn_fold_kernel + gn_apply_kernel: the statistics come from a conv epilogue (chunks = 1: the folded pair).
+// grid / lds: the first launch (one-pass, statistics or fold); agrid / alds: the apply pass of forms 1 and 2.
+struct GnLaunch {
+    dsim_gn_plan p;
+    int row;                    // of kGnTwoPass (forms 1 and 2)
+    dim3 grid, agrid;
+    size_t lds, alds;
+};
 template <typename T>
-int gn_plan(int C0, int C1, int B, int HW, int groups, bool pre, dsim_gn_plan* p) {
+int gn_plan(int C0, int C1, int B, int HW, int groups, bool pre, GnLaunch* l) {
     constexpr int VEC = Vec16<T>::N;
     const int C = C0 + C1;
     if (B < 1 || HW < 1 || groups < 1 || C < VEC) return DSIM_ERR_INVALID;
     if (C % groups || C0 % VEC || C1 % VEC || groups > 64 || C > GN_MAX_SLOTS * GN_THREADS * VEC)
         return DSIM_ERR_INVALID;
     // (precomputed statistics: whole 4-channel quads per group)
-    if (pre && (C1 || groups > 64 || (C / groups) % 4)) return DSIM_ERR_INVALID;
-    *p = dsim_gn_plan{};
-    if (const int CS = !pre ? gn_onepass_slab<T>(C0, C1, B, HW, groups) : 0) {
+    if (pre && (C1 || (C / groups) % 4)) return DSIM_ERR_INVALID;
+    *l = GnLaunch{};
+    dsim_gn_plan* p = &l->p;
+    if (const int CS = !pre ? gn_onepass_slab<T>(C0, C1, HW, groups) : 0) {
         p->form = 0; p->NS = 1; p->CS = CS; p->tpr = CS / VEC; p->R = GN_THREADS / p->tpr;
+        l->grid = dim3(C / CS, B);
+        l->lds = (size_t)p->R * CS * 2 * sizeof(float);
         return DSIM_OK;
     }
     const int S = C / VEC, tpr = S < GN_THREADS ? S : GN_THREADS, R = GN_THREADS / tpr;
@@ -780,61 +762,61 @@ int gn_plan(int C0, int C1, int B, int HW, int groups, bool pre, dsim_gn_plan* p
     if (rb > want) rb = want;
     rb = rb < 1 ? 1 : (rb > 64 ? 64 : rb);
     const int ns = (S + tpr - 1) / tpr;
-    p->form = pre ? 2 : 1;
-    p->NS = ns == 1 ? 1 : (ns == 2 ? 2 : GN_MAX_SLOTS);
-    p->UNR = ns == 1 ? 4 : (ns == 2 ? 2 : 1);
-    p->CS = C; p->tpr = tpr; p->R = R;
-    p->chunks = pre ? 1 : gn_chunks(HW);
-    p->rb = rb;
-    return DSIM_OK;
+    for (const GnTwoPass<T>& k : kGnTwoPass<T>) {
+        if (k.NS < ns) continue;
+        l->row = (int)(&k - kGnTwoPass<T>);
+        p->form = pre ? 2 : 1;
+        p->NS = k.NS; p->UNR = k.UNR;
+        p->CS = C; p->tpr = tpr; p->R = R;
+        p->chunks = pre ? 1 : gn_chunks(HW);
+        p->rb = rb;
+        l->grid = pre ? dim3(groups, B) : dim3(p->chunks, B);
+        l->lds = pre ? 0 : (size_t)R * C * 2 * sizeof(float);
+        l->agrid = dim3(rb, B);
+        l->alds = (size_t)p->chunks * groups * 2 * sizeof(double);      // <= 32 KB
+        return DSIM_OK;
+    }
+    return DSIM_ERR_INVALID;
 }
 
+// pre: the statistics pass already happened in the producing conv's epilogue (GemmArgs.gn_part): gn_fold_kernel folds its
+// per-(wave, 4-channel quad) f32 partials into one f64 pair per (image, group), in fixed order
 template <typename T>
 int gn_typed(const void* x0, int C0, const void* x1, int C1, const float* gamma, const float* beta,
              void* out, int B, int HW, int groups, float eps, int silu, void* scratch, hipStream_t s,
              const float* pre = nullptr, int pre_chunks = 0) {
     if (!x1) C1 = 0;
-    const int C = C0 + C1;
-    dsim_gn_plan p;
-    if (gn_plan<T>(C0, C1, B, HW, groups, pre != nullptr, &p) != DSIM_OK) return DSIM_ERR_INVALID;
-    if (p.form == 0) {
-        const int CS = p.CS;
-        const size_t lds1 = (size_t)p.R * CS * 2 * sizeof(float);
-        if (silu)
-            hipLaunchKernelGGL((gn_onepass_kernel<T, true, GN_OP_MAXCH>), dim3(C / CS, B), dim3(GN_THREADS), lds1, s, (const T*)x0, C0,
-                               (const T*)x1, C1, gamma, beta, (T*)out, HW, groups, eps, CS);
-        else
-            hipLaunchKernelGGL((gn_onepass_kernel<T, false, GN_OP_MAXCH>), dim3(C / CS, B), dim3(GN_THREADS), lds1, s, (const T*)x0, C0,
-                               (const T*)x1, C1, gamma, beta, (T*)out, HW, groups, eps, CS);
-        DSIM_HIP_CHECK(hipGetLastError());
-        return DSIM_OK;
-    }
-    const size_t lds = (size_t)p.R * C * 2 * sizeof(float);
-    const int chunks = pre ? 0 : p.chunks;      // (gn_launch sets 1 after the fold)
-    if (p.NS == 1)
-        return gn_launch<T, 1, 4>(x0, C0, x1, C1, gamma, beta, out, B, HW, groups, eps, silu, scratch, chunks, p.rb, lds, s, pre, pre_chunks);
-    if (p.NS == 2)
-        return gn_launch<T, 2, 2>(x0, C0, x1, C1, gamma, beta, out, B, HW, groups, eps, silu, scratch, chunks, p.rb, lds, s, pre, pre_chunks);
-    return gn_launch<T, GN_MAX_SLOTS, 1>(x0, C0, x1, C1, gamma, beta, out, B, HW, groups, eps, silu, scratch, chunks, p.rb,
-                                         lds, s, pre, pre_chunks);
+    GnLaunch l;
+    if (gn_plan<T>(C0, C1, B, HW, groups, pre != nullptr, &l) != DSIM_OK) return DSIM_ERR_INVALID;
+    const dsim_gn_plan& p = l.p;
+    const int si = silu ? 1 : 0;
+    if (p.form == 0) return launch(kGnOnePass<T>[si], l.grid, l.lds, s, x0, C0, x1, C1, gamma, beta, out, HW, groups, eps, p.CS);
+    const GnTwoPass<T>& k = kGnTwoPass<T>[l.row];
+    const int st = p.form == 2 ? launch(gn_fold_kernel, l.grid, l.lds, s, pre, pre_chunks, (C0 + C1) / 4, groups, scratch)
+                               : launch(k.stats, l.grid, l.lds, s, x0, C0, x1, C1, HW, groups, scratch);
+    if (st != DSIM_OK) return st;
+    return launch(k.apply[si], l.agrid, l.alds, s, x0, C0, x1, C1, gamma, beta, out, HW, groups, eps, p.chunks, scratch);
 }
 
 }  // namespace
 
 // the kernels launch_groupnorm (pre = 0) / launch_groupnorm_pre (pre = 1) start for this shape; host only
 int groupnorm_plan(int C0, int C1, int B, int HW, int groups, int dtype, int pre, dsim_gn_plan* p) {
-    if (!p) return DSIM_ERR_INVALID;
-    if (dtype == DSIM_F32) return pre ? DSIM_ERR_INVALID : gn_plan<float>(C0, C1, B, HW, groups, false, p);
-    if (dtype == DSIM_BF16 || dtype == DSIM_F16) return gn_plan<bf16_t>(C0, C1, B, HW, groups, pre != 0, p);   // (either 16-bit type)
-    return DSIM_ERR_INVALID;
+    if (!p || (dtype != DSIM_F32 && dtype != DSIM_BF16 && dtype != DSIM_F16) || (dtype == DSIM_F32 && pre)) return DSIM_ERR_INVALID;
+    GnLaunch l;
+    if ((dtype == DSIM_F32 ? gn_plan<float>(C0, C1, B, HW, groups, false, &l)
+                           : gn_plan<bf16_t>(C0, C1, B, HW, groups, pre != 0, &l)) != DSIM_OK) return DSIM_ERR_INVALID;    // (bf16_t: either 16-bit type)
+    *p = l.p;
+    return DSIM_OK;
 }
 
 // the kernel launch_layernorm (mod = 0) / launch_layernorm_mod (mod = 1) starts for this shape; host only
 int layernorm_plan(int M, int C, int dtype, int mod, dsim_ln_plan* p) {
-    if (!p) return DSIM_ERR_INVALID;
-    if (dtype == DSIM_F32) return ln_plan<float>(M, C, mod != 0, p);
-    if (dtype == DSIM_BF16 || dtype == DSIM_F16) return ln_plan<bf16_t>(M, C, mod != 0, p);      // (either 16-bit type)
-    return DSIM_ERR_INVALID;
+    if (!p || (dtype != DSIM_F32 && dtype != DSIM_BF16 && dtype != DSIM_F16)) return DSIM_ERR_INVALID;
+    LnLaunch l;
+    if ((dtype == DSIM_F32 ? ln_plan<float>(M, C, mod != 0, &l) : ln_plan<bf16_t>(M, C, mod != 0, &l)) != DSIM_OK) return DSIM_ERR_INVALID;
+    *p = l.p;                                                       // (bf16_t: either 16-bit type)
+    return DSIM_OK;
 }
 
 // passes over the tensor the GroupNorm of this shape makes (2 = one-pass form: read + write; 3 = statistics read + read + write)
@@ -850,52 +832,39 @@ size_t groupnorm_scratch_bytes(int B, int groups) { return (size_t)B * 64 * grou
 // chunks = its partial rows per image (HW / 64); 16-bit dtypes only
 int launch_groupnorm_pre(const void* x, int C, const float* gamma, const float* beta, void* out, int B, int HW, int groups, float eps,
                          int silu, int dtype, void* scratch, const float* part32, int chunks, hipStream_t s) {
-    if (!part32 || chunks < 1) return DSIM_ERR_INVALID;
-    if (dtype == DSIM_BF16) return gn_typed<bf16_t>(x, C, nullptr, 0, gamma, beta, out, B, HW, groups, eps, silu, scratch, s, part32, chunks);
-    if (dtype == DSIM_F16) return gn_typed<f16_t>(x, C, nullptr, 0, gamma, beta, out, B, HW, groups, eps, silu, scratch, s, part32, chunks);
-    return DSIM_ERR_INVALID;
+    if (!part32 || chunks < 1 || dtype == DSIM_F32) return DSIM_ERR_INVALID;
+    return by_dtype(dtype, [&](auto e) {
+        return gn_typed<typename decltype(e)::type>(x, C, nullptr, 0, gamma, beta, out, B, HW, groups, eps, silu, scratch, s, part32, chunks);
+    });
 }
 
 int launch_groupnorm(const void* x0, int C0, const void* x1, int C1, const float* gamma, const float* beta,
                      void* out, int B, int HW, int groups, float eps, int silu, int dtype, void* scratch,
                      hipStream_t s) {
-    if (dtype == DSIM_BF16) return gn_typed<bf16_t>(x0, C0, x1, C1, gamma, beta, out, B, HW, groups, eps, silu, scratch, s);
-    if (dtype == DSIM_F16) return gn_typed<f16_t>(x0, C0, x1, C1, gamma, beta, out, B, HW, groups, eps, silu, scratch, s);
-    if (dtype == DSIM_F32) return gn_typed<float>(x0, C0, x1, C1, gamma, beta, out, B, HW, groups, eps, silu, scratch, s);
-    return DSIM_ERR_INVALID;
+    return by_dtype(dtype, [&](auto e) {
+        return gn_typed<typename decltype(e)::type>(x0, C0, x1, C1, gamma, beta, out, B, HW, groups, eps, silu, scratch, s);
+    });
 }
 
 int launch_layernorm(const void* x, const float* gamma, const float* beta, void* out, int M, int C, float eps,
                      int dtype, hipStream_t s) {
-    if (dtype == DSIM_BF16) return ln_typed<bf16_t, false>(x, gamma, beta, out, M, C, eps, 1, s);
-    if (dtype == DSIM_F16) return ln_typed<f16_t, false>(x, gamma, beta, out, M, C, eps, 1, s);
-    if (dtype == DSIM_F32) return ln_typed<float, false>(x, gamma, beta, out, M, C, eps, 1, s);
-    return DSIM_ERR_INVALID;
+    return by_dtype(dtype, [&](auto e) { return ln_typed<typename decltype(e)::type, false>(x, gamma, beta, out, M, C, eps, 1, s); });
 }
 
 int launch_layernorm_mod(const void* x, const float* scale2, const float* shift2, void* out, int M, int C,
                          int rows_per_batch, float eps, int dtype, hipStream_t s) {
     if (rows_per_batch < 1) return DSIM_ERR_INVALID;
-    if (dtype == DSIM_BF16) return ln_typed<bf16_t, true>(x, scale2, shift2, out, M, C, eps, rows_per_batch, s);
-    if (dtype == DSIM_F16) return ln_typed<f16_t, true>(x, scale2, shift2, out, M, C, eps, rows_per_batch, s);
-    if (dtype == DSIM_F32) return ln_typed<float, true>(x, scale2, shift2, out, M, C, eps, rows_per_batch, s);
-    return DSIM_ERR_INVALID;
+    return by_dtype(dtype, [&](auto e) {
+        return ln_typed<typename decltype(e)::type, true>(x, scale2, shift2, out, M, C, eps, rows_per_batch, s);
+    });
 }
 
 int launch_softmax_rows(const void* x, void* out, int rows, int cols, float scale, int dtype, hipStream_t s) {
-    const int vec = dtype == DSIM_F32 ? 4 : 8;
-    if (cols % vec || rows < 1) return DSIM_ERR_INVALID;
-    const float sl2 = scale * 1.4426950408889634f;
-    if (dtype == DSIM_BF16)
-        hipLaunchKernelGGL(softmax_rows_kernel<bf16_t>, dim3(rows), dim3(256), 0, s, (const bf16_t*)x, (bf16_t*)out, cols, sl2);
-    else if (dtype == DSIM_F16)
-        hipLaunchKernelGGL(softmax_rows_kernel<f16_t>, dim3(rows), dim3(256), 0, s, (const f16_t*)x, (f16_t*)out, cols, sl2);
-    else if (dtype == DSIM_F32)
-        hipLaunchKernelGGL(softmax_rows_kernel<float>, dim3(rows), dim3(256), 0, s, (const float*)x, (float*)out, cols, sl2);
-    else
-        return DSIM_ERR_INVALID;
-    DSIM_HIP_CHECK(hipGetLastError());
-    return DSIM_OK;
+    return by_dtype(dtype, [&](auto e) {
+        typedef typename decltype(e)::type T;
+        if (cols % Vec16<T>::N || rows < 1) return (int)DSIM_ERR_INVALID;
+        return launch(softmax_rows_kernel<T>, dim3(rows), 0, s, x, out, cols, scale * 1.4426950408889634f);
+    });
 }
 
 }  // namespace dsim
