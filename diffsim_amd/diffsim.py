@@ -18,27 +18,20 @@ points work; the path-based ones raise.
 """
 from __future__ import annotations
 
-from typing import Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple, Union
+from typing import Callable, Dict, List, Optional, Sequence, Tuple, Union
 
 from concurrent.futures import ThreadPoolExecutor
 
 import torch
 
 from . import scheduler as sched
+from . import maps, retrieval, sweep
 from .config import SD15, UNetConfig
-from .engine import UNetEngine, pair_score
+from .engine import UNetEngine, _LatentDist, pair_score
 from .image import DecodePool, host_threads, load_image, process_image
-
-
-def get_generator(seed, device="cpu"):
-    if seed is not None:
-        if isinstance(seed, list):
-            generator = [torch.Generator(device).manual_seed(int(s)) for s in seed]
-        else:
-            generator = torch.Generator(device).manual_seed(int(seed))
-    else:
-        generator = None
-    return generator
+from .inputs import path_latents
+from .scorer import (PromptTable, Scorer, check_row_prompts, distinct_prompts, get_generator, row_prompts,  # noqa: F401
+                     single_prompt, stack_rows)
 
 
 def _norm_layer(target_layer) -> int:
@@ -51,51 +44,9 @@ def _norm_layer(target_layer) -> int:
     raise TypeError("list indices must be integers or slices, not list")
 
 
-class PromptTable(NamedTuple):
-    """The prompt contexts of one engine batch that carries a prompt per image: the distinct contexts (n_ctx, 2, L, Dc) f32 on the
-    device, in order of first appearance, and each image's row of that table."""
-    table: torch.Tensor
-    index: List[int]
+class DiffSim(Scorer):
+    per_row_prompts = True          # a context table: nothing before the first cross-attention depends on the prompt
 
-
-def single_prompt(prompt) -> bool:
-    """True for one prompt of the whole call (a string, a (2, L, Dc) context or a PromptTable already built), False for a sequence
-    with one entry per pair / triplet / image."""
-    return isinstance(prompt, (str, torch.Tensor, PromptTable))
-
-
-def distinct_prompts(prompts) -> Tuple[list, List[int]]:
-    """(the distinct entries of `prompts` in order of first appearance, each entry's position among them).  Strings are the same
-    prompt when equal, tensors when they are the same object."""
-    pos, firsts, index = {}, [], []
-    for p in prompts:
-        key = ("tensor", id(p)) if isinstance(p, torch.Tensor) else ("str", p)
-        if key not in pos:
-            pos[key] = len(firsts)
-            firsts.append(p)
-        index.append(pos[key])
-    return firsts, index
-
-
-def row_prompts(prompt, i0: int, i1: int, per_row: int):
-    """The prompts of rows [i0, i1) of a batched call image by image, each row's `per_row` images consecutive as
-    inputs.stack_rows lays them out; one prompt of the whole call stays as it is."""
-    if single_prompt(prompt):
-        return prompt
-    return [p for p in prompt[i0:i1] for _ in range(per_row)]
-
-
-def check_row_prompts(prompt, n_rows: int, what: str = "pairs"):
-    """A per-row prompt sequence as a list (ValueError unless it has one entry per row); one prompt of the call unchanged."""
-    if single_prompt(prompt):
-        return prompt
-    prompt = list(prompt)
-    if len(prompt) != n_rows:
-        raise ValueError(f"{len(prompt)} prompts for {n_rows} {what}: one prompt, or one per entry")
-    return prompt
-
-
-class DiffSim:
     def __init__(self, torch_dtype=torch.bfloat16, device="cuda", ip_adapter=False, *,
                  unet_config: UNetConfig = SD15, state_dict: Optional[Dict[str, torch.Tensor]] = None,
                  vae=None, encode_prompt: Optional[Callable[[str], torch.Tensor]] = None,
@@ -161,6 +112,25 @@ class DiffSim:
             self._engines[key].tokens            # moves the tap once: a missing weight raises here, not mid-run
         return self._engines[key]
 
+    # ---- the Scorer protocol: this kind's facts (scorer.py)
+    image_half = property(lambda self: self.vae_dtype == torch.float16)     # image.to(dtype=float16), diffsim.py:93
+    noise_draw = property(lambda self: self.noise_dtype)                    # randn_tensor(dtype=latents.dtype): the pipeline dtype
+    eps_dtype = property(lambda self: self.noise_dtype)                     # latent_dist.sample draws in the pipeline dtype too
+    round16 = property(lambda self: self.noise_dtype == torch.float16)      # the fp16 pipeline holds its latents in fp16
+
+    def prepare(self, tensor, generator):
+        return self.prepare_image_latents(tensor, None, None, generator).to(self.noise_draw).float()
+
+    def tap_of(self, target_block, target_layer):
+        return target_block, _norm_layer(target_layer)
+
+    @staticmethod
+    def canonical_tap(tap):
+        return tap[0], int(tap[1])
+
+    def auto_map_pairs(self, eng, n: int) -> int:
+        return self.auto_rows(eng, n, 2)                        # 64 where it fits, as score_latent_pairs on one stream
+
     def context(self, prompt: Union[str, torch.Tensor]) -> torch.Tensor:
         """[uncond, cond] prompt embeddings (2, L, Dc) f32 on the device; cached per prompt
         (the reference re-encodes the constant prompt on every call, diffsim_pipeline.py:125)."""
@@ -209,7 +179,6 @@ class DiffSim:
         batch-invariant bit for bit) and are then sampled in the reference's order -- A's draw, then B's."""
         vae = self.vae
         if vae is not None and hasattr(vae, "moments") and tensor_A.shape == tensor_B.shape:
-            from .engine import _LatentDist
             x = torch.cat([tensor_A, tensor_B]).to(vae.device).to(dtype=self.vae_dtype)
             mom = vae.moments(x)
             sf = vae.config.scaling_factor
@@ -263,19 +232,9 @@ class DiffSim:
         return lat, nz, sa, sb, ctx, idx
 
     def auto_batch_pairs(self, eng, n_pairs: int, streams: int = 2, target: int = 64) -> int:
-        """Pairs per chunk when the caller names none: `target` (the sweep's optimum on a 288 GB part), capped by the 2 GiB
-        activation bound, by the job and by the free HBM the per-stream arenas may take (half of what is free now)."""
-        bp = max(1, min(target, eng.max_images() // 2, max(1, int(n_pairs))))
-        try:
-            free, _total = torch.cuda.mem_get_info(self.device)
-        except Exception:
-            return bp
-        while bp > 1:
-            ns = max(1, min(int(streams), -(-int(n_pairs) // bp)))
-            if eng.workspace_bytes(2 * bp) * ns <= 0.5 * free:
-                break
-            bp = (bp + 1) // 2
-        return bp
+        """Pairs per chunk when the caller names none: `target` (the sweep's optimum on a 288 GB part) within what fits
+        (Scorer.auto_rows)."""
+        return self.auto_rows(eng, n_pairs, 2, streams=streams, images=2 * target)
 
     @torch.no_grad()
     def score_latent_pairs(self, latA, latB, noiseA, noiseB, prompt, target_block="up_blocks", target_layer=0,
@@ -289,7 +248,6 @@ class DiffSim:
         workspace arena of the engine (streams = 2 -> two arenas, ~0.75 GB per pair of the chunk size each).
         batch_pairs=None picks the measured optimum (profiles/r04h_batch_sweep.txt: 64 pairs per chunk, 662 pairs/s against
         603 at 16) within what fits: every activation < 2 GiB and the arenas of the streams in use inside the free HBM."""
-        from .inputs import stack_rows
         n = latA.shape[0]
         prompt = check_row_prompts(prompt, n)
         eng = self.engine(target_block, target_layer)
@@ -363,7 +321,6 @@ class DiffSim:
     def score_pairs(self, pairs: Sequence[Tuple[str, str]], img_size, prompt, target_block, target_layer, target_step,
                     seed="2333", similarity="cosine", batch_pairs: Optional[int] = None) -> torch.Tensor:
         """Batched equivalent of calling :meth:`diffsim` once per (A, B) path pair."""
-        from .inputs import path_latents
         target_layer = _norm_layer(target_layer)
         # batch_pairs=None: 16 pairs per VAE encode (32 images at 512 px keep its widest activation < 2 GiB), and
         # score_latent_pairs picks its own chunk (64 where it fits)
@@ -377,17 +334,15 @@ class DiffSim:
                      target_step, seed="2333", similarity="cosine", batch: Optional[int] = None) -> torch.Tensor:
         """(len(paths_a), len(paths_b)) matrix of :meth:`diffsim` scores, every image pushed through the U-Net once
         (retrieval.score_path_matrix)."""
-        from .retrieval import score_path_matrix
-        return score_path_matrix(self, paths_a, paths_b, img_size, prompt, target_block, _norm_layer(target_layer), target_step,
-                                 seed, similarity, batch)
+        return retrieval.score_path_matrix(self, paths_a, paths_b, img_size, prompt, target_block, _norm_layer(target_layer), target_step,
+                                           seed, similarity, batch)
 
     @torch.no_grad()
     def score_latent_matrix(self, latA, latB, noiseA, noiseB, prompt, target_block="up_blocks", target_layer=0,
                             target_step=600, similarity="cosine", batch: Optional[int] = None) -> torch.Tensor:
         """(n_a, n_b) matrix of :meth:`diffsim_latents` scores of (latA[i], latB[j]) (retrieval.score_latent_matrix)."""
-        from .retrieval import score_latent_matrix
-        return score_latent_matrix(self, latA, latB, noiseA, noiseB, prompt, target_block, _norm_layer(target_layer),
-                                   target_step, similarity, batch)
+        return retrieval.score_latent_matrix(self, latA, latB, noiseA, noiseB, prompt, target_block, _norm_layer(target_layer),
+                                             target_step, similarity, batch)
 
     # ------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -403,9 +358,8 @@ class DiffSim:
     def score_latent_pair_maps(self, latA, latB, noiseA, noiseB, prompt, target_block="up_blocks", target_layer=0,
                                target_step=600, similarity="cosine", batch_pairs: Optional[int] = None):
         """Maps of the pairs of :meth:`score_latent_pairs` (maps.score_latent_pair_maps)."""
-        from .maps import score_latent_pair_maps
-        return score_latent_pair_maps(self, latA, latB, noiseA, noiseB, prompt, target_block, _norm_layer(target_layer),
-                                      target_step, similarity, batch_pairs)
+        return maps.score_latent_pair_maps(self, latA, latB, noiseA, noiseB, prompt, target_block, _norm_layer(target_layer),
+                                           target_step, similarity, batch_pairs)
 
     # ------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -413,13 +367,11 @@ class DiffSim:
                                 batch_pairs: Optional[int] = None) -> torch.Tensor:
         """(n_taps, n) scores: row t is :meth:`score_latent_pairs` at taps[t], every tap from one forward per chunk
         (sweep.score_latent_pairs_taps).  taps: [(target_block, layer)] with explicit layers, or "all"."""
-        from .sweep import score_latent_pairs_taps
-        return score_latent_pairs_taps(self, latA, latB, noiseA, noiseB, prompt, taps, target_step, similarity, batch_pairs)
+        return sweep.score_latent_pairs_taps(self, latA, latB, noiseA, noiseB, prompt, taps, target_step, similarity, batch_pairs)
 
     @torch.no_grad()
     def score_pairs_taps(self, pairs: Sequence[Tuple[str, str]], img_size, prompt, taps, target_step, seed="2333",
                          similarity="cosine") -> torch.Tensor:
         """(n_taps, len(pairs)) scores: row t is :meth:`score_pairs` at taps[t]; the images are decoded and encoded once for all
         taps (sweep.score_path_pairs_taps)."""
-        from .sweep import score_path_pairs_taps
-        return score_path_pairs_taps(self, pairs, img_size, prompt, taps, target_step, similarity, seed)
+        return sweep.score_path_pairs_taps(self, pairs, img_size, prompt, taps, target_step, similarity, seed)

@@ -10,13 +10,21 @@ from typing import Dict, Optional
 
 import torch
 
+from . import maps, sweep
 from . import scheduler as sched
+from ._lib import DsimError
 from .config import DIT_XL2, DiTConfig
 from .engine import DiTEngine, pair_score
-from .inputs import path_latents, stack_rows
+from .inputs import path_latents
+from .scorer import Scorer
 
 
-class diffsim_DiT:
+class diffsim_DiT(Scorer):
+    """The prompt is ignored (labels [1, 1000]); the noise is drawn in the fp16 of the latents (randn_tensor(dtype=latents.dtype)):
+    the base's defaults.  A tap is the block index."""
+    canonical_tap = staticmethod(int)
+    one_tap_bound = False       # DiTEngine.qkv plans no image bound: a one-tap batch is neither capped nor halved for the free HBM
+
     def __init__(self, img_size=256, target_step=600, device="cuda", ckpt=None, *, dit_config: DiTConfig = DIT_XL2,
                  state_dict: Optional[Dict[str, torch.Tensor]] = None, vae=None, torch_dtype=torch.bfloat16,
                  fp8_attention: bool = False):
@@ -38,6 +46,25 @@ class diffsim_DiT:
                 self._engine.set_attention(True)
         self._engine.set_tap(int(layer))
         return self._engine
+
+    # ---- the Scorer protocol: this kind's facts (scorer.py)
+    def tap_of(self, target_block, target_layer):
+        return int(target_layer[0])                 # the hook on model.blocks[target_layer[0]].attn
+
+    def engine_at(self, tap):
+        return self.engine(tap)
+
+    def sweep_engine(self, taps, side: int):
+        if not taps:
+            raise DsimError("no taps")
+        eng = self._engine if self._engine is not None else self.engine(taps[0])
+        return eng, [(eng.tokens, eng.heads, eng.head_dim)] * len(taps)
+
+    def tap_features(self, lat, nz, prompt, tap, step):
+        return self.features(lat, nz, tap, step)
+
+    def taps_features(self, lat, nz, prompt, taps, step):
+        return self.features_taps(lat, nz, taps, step)
 
     def prepare_image_latents(self, image, generator=None):
         if self.vae is None:
@@ -68,14 +95,10 @@ class diffsim_DiT:
     @torch.no_grad()
     def score_latent_pairs(self, latA, latB, noiseA, noiseB, target_layer: int, target_step: int, similarity="cosine",
                            batch_pairs: int = 32) -> torch.Tensor:
-        n = latA.shape[0]
-        eng = self.engine(int(target_layer))
-        out = torch.empty(n, dtype=torch.float32, device=self.device)
-        for i0 in range(0, n, batch_pairs):
-            i1 = min(n, i0 + batch_pairs)
-            q, k, v = self.features(*stack_rows([latA, latB], [noiseA, noiseB], i0, i1), target_layer, target_step)
-            ia = torch.arange(0, 2 * (i1 - i0), 2, dtype=torch.int32, device=self.device)
-            out[i0:i1] = pair_score(q, k, v, ia, ia + 1, eng.heads, similarity)
+        out = torch.empty(latA.shape[0], dtype=torch.float32, device=self.device)
+        for i0, i1, s in self.pair_chunks(latA, latB, noiseA, noiseB, None, int(target_layer), target_step, similarity, batch_pairs,
+                                          pair_score):
+            out[i0:i1] = s
         return out
 
     @torch.no_grad()
@@ -94,19 +117,16 @@ class diffsim_DiT:
     def score_latent_pair_maps(self, latA, latB, noiseA, noiseB, target_layer: int, target_step: int, similarity="cosine",
                                batch_pairs: int = 32):
         """Maps of the pairs of :meth:`score_latent_pairs` (maps.score_latent_pair_maps)."""
-        from .maps import score_latent_pair_maps
-        return score_latent_pair_maps(self, latA, latB, noiseA, noiseB, None, "none", [int(target_layer)], target_step, similarity,
-                                      batch_pairs)
+        return maps.score_latent_pair_maps(self, latA, latB, noiseA, noiseB, None, "none", [int(target_layer)], target_step, similarity,
+                                           batch_pairs)
 
     @torch.no_grad()
     def score_latent_pairs_taps(self, latA, latB, noiseA, noiseB, layers, target_step: int, similarity="cosine",
                                 batch_pairs: Optional[int] = None) -> torch.Tensor:
         """(n_taps, n) scores: row t is :meth:`score_latent_pairs` at layers[t] (sweep.score_latent_pairs_taps)."""
-        from .sweep import score_latent_pairs_taps
-        return score_latent_pairs_taps(self, latA, latB, noiseA, noiseB, None, layers, target_step, similarity, batch_pairs)
+        return sweep.score_latent_pairs_taps(self, latA, latB, noiseA, noiseB, None, layers, target_step, similarity, batch_pairs)
 
     @torch.no_grad()
     def score_pairs_taps(self, pairs, img_size, layers, target_step, similarity="cosine", seed=2333) -> torch.Tensor:
         """(n_taps, len(pairs)) scores of (A, B) path pairs, the images encoded once for all blocks (sweep.score_path_pairs_taps)."""
-        from .sweep import score_path_pairs_taps
-        return score_path_pairs_taps(self, pairs, img_size, None, layers, target_step, similarity, seed)
+        return sweep.score_path_pairs_taps(self, pairs, img_size, None, layers, target_step, similarity, seed)

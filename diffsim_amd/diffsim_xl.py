@@ -13,13 +13,18 @@ from typing import Callable, Dict, Optional, Tuple
 
 import torch
 
+from . import maps, sweep
 from . import scheduler as sched
 from .config import SDXL, UNetConfig
 from .engine import UNetEngine, pair_score
-from .inputs import path_latents, stack_rows
+from .inputs import path_latents
+from .scorer import Scorer, check_row_prompts, distinct_prompts
 
 
-class diffsim_xl:
+class diffsim_xl(Scorer):
+    mixes_prompts = False       # the pooled prompt embedding enters the time embedding of every resnet, one per CFG half
+    engine_images = 16          # the batch sweeps' optimum at 1024 px
+
     def __init__(self, torch_dtype=torch.bfloat16, device="cuda", ip_adapter=False, *, unet_config: UNetConfig = SDXL,
                  state_dict: Optional[Dict[str, torch.Tensor]] = None, vae=None,
                  encode_prompt: Optional[Callable[[str], Tuple[torch.Tensor, torch.Tensor]]] = None,
@@ -51,6 +56,37 @@ class diffsim_xl:
             self._engines[key] = self._base.view(target_block, list(key[1]))
             self._engines[key].tokens
         return self._engines[key]
+
+    # ---- the Scorer protocol: this kind's facts (scorer.py)
+    noise_draw = property(lambda self: self.noise_dtype)        # randn_tensor(dtype=latents.dtype) of the pipeline run
+
+    @staticmethod
+    def canonical_tap(tap):
+        return tap[0], [int(v) for v in tap[1]]
+
+    def prompt_rows(self, prompt, n_rows: int, what: str = "triplets"):
+        """One prompt per call: a string, its (context, pooled) tuple, or a list that repeats one."""
+        if isinstance(prompt, list):
+            prompt = check_row_prompts(prompt, n_rows, what)
+            if len(distinct_prompts(prompt)[0]) > 1:
+                raise ValueError("SDXL takes one prompt per call: its pooled prompt embedding enters every resnet")
+            return prompt[0]
+        return prompt
+
+    def bind_prompt(self, prompt, n_rows: int, what: str = "triplets"):
+        """(context, pooled): a prompt string is encoded here, once per call and not once per engine batch."""
+        prompt = self.prompt_rows(prompt, n_rows, what)
+        if isinstance(prompt, tuple):
+            return prompt
+        if self._encode_prompt is None:
+            raise RuntimeError("no text encoder plugged in: pass encode_prompt=...")
+        return self._encode_prompt(prompt)
+
+    def tap_features(self, lat, nz, prompt, tap, step):
+        return self.features(lat, nz, *prompt, *tap, step)
+
+    def taps_features(self, lat, nz, prompt, taps, step):
+        return self.features_taps(lat, nz, *prompt, taps, step)
 
     def prepare_image_latents(self, image, generator=None):
         if self.vae is None:
@@ -105,16 +141,10 @@ class diffsim_xl:
     @torch.no_grad()
     def score_latent_pairs(self, latA, latB, noiseA, noiseB, ctx, pooled, target_block, target_layer, target_step,
                            similarity="cosine", batch_pairs: int = 8) -> torch.Tensor:
-        n = latA.shape[0]
-        eng = self.engine(target_block, target_layer)
-        out = torch.empty(n, dtype=torch.float32, device=self.device)
-        batch_pairs = max(1, min(batch_pairs, eng.max_images() // 2))      # every activation must stay < 2 GiB
-        for i0 in range(0, n, batch_pairs):
-            i1 = min(n, i0 + batch_pairs)
-            lat, nz = stack_rows([latA, latB], [noiseA, noiseB], i0, i1)
-            q, k, v = self.features(lat, nz, ctx, pooled, target_block, target_layer, target_step)
-            ia = torch.arange(0, 2 * (i1 - i0), 2, dtype=torch.int32, device=self.device)
-            out[i0:i1] = pair_score(q, k, v, ia, ia + 1, eng.heads, similarity)
+        out = torch.empty(latA.shape[0], dtype=torch.float32, device=self.device)
+        for i0, i1, s in self.pair_chunks(latA, latB, noiseA, noiseB, (ctx, pooled), (target_block, target_layer), target_step,
+                                          similarity, batch_pairs, pair_score):
+            out[i0:i1] = s
         return out
 
     @torch.no_grad()
@@ -126,10 +156,8 @@ class diffsim_xl:
 
     def _path_pair_inputs(self, image_A, image_B, img_size, prompt, seed):
         """(latentsA, latentsB, noiseA, noiseB, ctx, pooled): what one reference call draws and encodes."""
-        if self._encode_prompt is None:
-            raise RuntimeError("no text encoder plugged in: pass encode_prompt=...")
+        ctx, pooled = self.bind_prompt(prompt, 1)
         (latentsA, latentsB), noiseA, noiseB = path_latents(self, [(image_A, image_B)], (0, 1), img_size, seed, 1, hip_vae=False)
-        ctx, pooled = self._encode_prompt(prompt)
         return latentsA, latentsB, noiseA, noiseB, ctx, pooled
 
     @torch.no_grad()
@@ -143,20 +171,17 @@ class diffsim_xl:
     def score_latent_pair_maps(self, latA, latB, noiseA, noiseB, ctx, pooled, target_block, target_layer, target_step,
                                similarity="cosine", batch_pairs: int = 8):
         """Maps of the pairs of :meth:`score_latent_pairs` (maps.score_latent_pair_maps)."""
-        from .maps import score_latent_pair_maps
-        return score_latent_pair_maps(self, latA, latB, noiseA, noiseB, (ctx, pooled), target_block, target_layer, target_step,
-                                      similarity, batch_pairs)
+        return maps.score_latent_pair_maps(self, latA, latB, noiseA, noiseB, (ctx, pooled), target_block, target_layer, target_step,
+                                           similarity, batch_pairs)
 
     @torch.no_grad()
     def score_latent_pairs_taps(self, latA, latB, noiseA, noiseB, ctx, pooled, taps, target_step, similarity="cosine",
                                 batch_pairs: Optional[int] = None) -> torch.Tensor:
         """(n_taps, n) scores: row t is :meth:`score_latent_pairs` at taps[t] (sweep.score_latent_pairs_taps)."""
-        from .sweep import score_latent_pairs_taps
-        return score_latent_pairs_taps(self, latA, latB, noiseA, noiseB, (ctx, pooled), taps, target_step, similarity,
-                                       batch_pairs)
+        return sweep.score_latent_pairs_taps(self, latA, latB, noiseA, noiseB, (ctx, pooled), taps, target_step, similarity,
+                                             batch_pairs)
 
     @torch.no_grad()
     def score_pairs_taps(self, pairs, img_size, prompt, taps, target_step, similarity="cosine", seed=2333) -> torch.Tensor:
         """(n_taps, len(pairs)) scores of (A, B) path pairs, the images encoded once for all taps (sweep.score_path_pairs_taps)."""
-        from .sweep import score_path_pairs_taps
-        return score_path_pairs_taps(self, pairs, img_size, prompt, taps, target_step, similarity, seed)
+        return sweep.score_path_pairs_taps(self, pairs, img_size, prompt, taps, target_step, similarity, seed)

@@ -255,22 +255,23 @@ class UNetEngine(_Handle):
             self.sample_size = int(side)
             self._refresh_tap_shape()
 
-    def set_cfg_dedup(self, enable: bool):
-        """Opt-in: compute the part of the graph both CFG halves share once (SD1.5 graphs; bit-identical scores)."""
-        _lib.check(self.L.dsim_unet_set_cfg_dedup(self._h, int(bool(enable))), "dsim_unet_set_cfg_dedup")
+    def _graph_changed(self):
+        """The executed graph is another one: the image bounds found for the old one and the hipGraphs captured from it go."""
         self._max_images = None
         self.__dict__.pop("_max_images_taps", None)
         self.__dict__.pop("_max_images_ctx", None)
         self._graphs.clear()
 
+    def set_cfg_dedup(self, enable: bool):
+        """Opt-in: compute the part of the graph both CFG halves share once (SD1.5 graphs; bit-identical scores)."""
+        _lib.check(self.L.dsim_unet_set_cfg_dedup(self._h, int(bool(enable))), "dsim_unet_set_cfg_dedup")
+        self._graph_changed()
+
     def set_fusion(self, mask: int):
         """Which multi-operator kernels replace their unfused chains (_lib.FUSE_* bits; default all).  0 = every layer
         its own launch: the A/B switch of bench.py --fusion and of the parity tests."""
         _lib.check(self.L.dsim_unet_set_fusion(self._h, int(mask)), "dsim_unet_set_fusion")
-        self._max_images = None
-        self.__dict__.pop("_max_images_taps", None)
-        self.__dict__.pop("_max_images_ctx", None)
-        self._graphs.clear()
+        self._graph_changed()
 
     def view(self, target_block: str, target_layer) -> "TapView":
         return TapView(self, target_block, target_layer)
@@ -496,6 +497,31 @@ class TapView:
         setattr(object.__getattribute__(self, "_base"), name, value)
 
 
+_PAIR_MSGS = ("q,k,v must share dtype float32, bfloat16 or float16", "q,k,v must be [n_feat][B][N][H*D] of one shape",
+              "features and indices must be contiguous")
+
+
+def _check_features(ts, heads: int, shapes_ok: bool, msgs, idx=()):
+    """The checks every score tail makes of its feature tensors ts = (q, ...), each [n][B][N][H*D], and pair index tensors idx: one
+    dtype of the three, the caller's shape condition, contiguity, H*D against heads; msgs: the texts of the first three.  (B, N, D)."""
+    q = ts[0]
+    if q.dtype not in _TORCH2DSIM or any(t.dtype != q.dtype for t in ts):
+        raise _lib.DsimError(msgs[0])
+    if any(i.dtype != torch.int32 for i in idx):
+        raise _lib.DsimError("pair indices must be int32")
+    if q.ndim != 4 or not shapes_ok:
+        raise _lib.DsimError(msgs[1])
+    if not all(t.is_contiguous() for t in (*ts, *idx)):
+        raise _lib.DsimError(msgs[2])
+    _, B, N, HD = q.shape
+    D = HD // heads
+    if D * heads != HD:
+        raise _lib.DsimError(f"H*D = {HD} is not a multiple of heads = {heads}")
+    if idx and idx[0].numel() != idx[1].numel():
+        raise _lib.DsimError("idx_a and idx_b must have the same length")
+    return B, N, D
+
+
 def pair_score(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, idx_a: torch.Tensor, idx_b: torch.Tensor,
                heads: int, similarity: str = "cosine", return_status: bool = False):
     """Fused score tail (diffsim/diffsim.py:177-197).  q,k,v: contiguous [n_feat][B][N][H*D] of one shape; idx: contiguous int32
@@ -505,21 +531,8 @@ def pair_score(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, idx_a: torch.T
     _require_cuda(q, k, v, idx_a, idx_b)
     if similarity not in ("cosine", "mse"):
         raise ValueError(similarity)
-    if q.dtype not in (torch.float32, torch.bfloat16, torch.float16) or k.dtype != q.dtype or v.dtype != q.dtype:
-        raise _lib.DsimError("q,k,v must share dtype float32, bfloat16 or float16")
-    if idx_a.dtype != torch.int32 or idx_b.dtype != torch.int32:
-        raise _lib.DsimError("pair indices must be int32")
-    if q.ndim != 4 or k.shape != q.shape or v.shape != q.shape:
-        raise _lib.DsimError("q,k,v must be [n_feat][B][N][H*D] of one shape")
-    if not all(t.is_contiguous() for t in (q, k, v, idx_a, idx_b)):
-        raise _lib.DsimError("features and indices must be contiguous")
-    nf, B, N, HD = q.shape
-    D = HD // heads
-    if D * heads != HD:
-        raise _lib.DsimError(f"H*D = {HD} is not a multiple of heads = {heads}")
+    B, N, D = _check_features((q, k, v), heads, k.shape == q.shape == v.shape, _PAIR_MSGS, (idx_a, idx_b))
     n_pairs = idx_a.numel()
-    if idx_b.numel() != n_pairs:
-        raise _lib.DsimError("idx_a and idx_b must have the same length")
     out = torch.empty(n_pairs, dtype=torch.float32, device=q.device)
     with torch.cuda.device(q.device):
         wsb = int(L.dsim_pair_score_workspace_bytes(n_pairs, B, heads, N, D))
@@ -547,21 +560,8 @@ def pair_score_maps(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, idx_a: to
     _require_cuda(q, k, v, idx_a, idx_b)
     if similarity not in ("cosine", "mse"):
         raise ValueError(similarity)
-    if q.dtype not in (torch.float32, torch.bfloat16, torch.float16) or k.dtype != q.dtype or v.dtype != q.dtype:
-        raise _lib.DsimError("q,k,v must share dtype float32, bfloat16 or float16")
-    if idx_a.dtype != torch.int32 or idx_b.dtype != torch.int32:
-        raise _lib.DsimError("pair indices must be int32")
-    if q.ndim != 4 or k.shape != q.shape or v.shape != q.shape:
-        raise _lib.DsimError("q,k,v must be [n_feat][B][N][H*D] of one shape")
-    if not all(t.is_contiguous() for t in (q, k, v, idx_a, idx_b)):
-        raise _lib.DsimError("features and indices must be contiguous")
-    nf, B, N, HD = q.shape
-    D = HD // heads
-    if D * heads != HD:
-        raise _lib.DsimError(f"H*D = {HD} is not a multiple of heads = {heads}")
+    B, N, D = _check_features((q, k, v), heads, k.shape == q.shape == v.shape, _PAIR_MSGS, (idx_a, idx_b))
     n_pairs = idx_a.numel()
-    if idx_b.numel() != n_pairs:
-        raise _lib.DsimError("idx_a and idx_b must have the same length")
     score = torch.empty(n_pairs, dtype=torch.float32, device=q.device)
     local = torch.empty((n_pairs, 2, N), dtype=torch.float32, device=q.device)
     contrib = torch.empty((n_pairs, 2, N), dtype=torch.float32, device=q.device)
@@ -592,28 +592,20 @@ def score_matrix(fa, fb, heads: int, similarity: str = "cosine", return_status: 
         raise ValueError(similarity)
     (qa, ka, va), (qb, kb, vb) = fa, fb
     _require_cuda(qa, ka, va, qb, kb, vb)
-    dt = qa.dtype
-    if dt not in _TORCH2DSIM or any(t.dtype != dt for t in (ka, va, qb, kb, vb)):
-        raise _lib.DsimError("q,k,v of both sets must share dtype float32, bfloat16 or float16")
-    if qa.ndim != 4 or any(t.shape != qa.shape for t in (ka, va)) or any(t.shape != qb.shape for t in (kb, vb)) or \
-            qa.shape[1:] != qb.shape[1:]:
-        raise _lib.DsimError("features must be [n][B][N][H*D], one geometry for both sets")
-    if not all(t.is_contiguous() for t in (qa, ka, va, qb, kb, vb)):
-        raise _lib.DsimError("features must be contiguous")
-    n_a, B, N, HD = qa.shape
-    n_b = qb.shape[0]
-    D = HD // heads
-    if D * heads != HD:
-        raise _lib.DsimError(f"H*D = {HD} is not a multiple of heads = {heads}")
+    B, N, D = _check_features((qa, ka, va, qb, kb, vb), heads,
+                              ka.shape == qa.shape == va.shape and kb.shape == qb.shape == vb.shape and qa.shape[1:] == qb.shape[1:],
+                              ("q,k,v of both sets must share dtype float32, bfloat16 or float16",
+                               "features must be [n][B][N][H*D], one geometry for both sets", "features must be contiguous"))
+    n_a, n_b = qa.shape[0], qb.shape[0]
     out = torch.empty((n_a, n_b), dtype=torch.float32, device=qa.device)
     status = torch.empty((n_a, n_b), dtype=torch.int32, device=qa.device) if return_status else None
     with torch.cuda.device(qa.device):
-        wsb = int(L.dsim_score_matrix_workspace_bytes(n_a, n_b, B, heads, N, D, _TORCH2DSIM[dt]))
+        wsb = int(L.dsim_score_matrix_workspace_bytes(n_a, n_b, B, heads, N, D, _TORCH2DSIM[qa.dtype]))
         if wsb == 0:
             raise _lib.DsimError(f"no score matrix for n_a={n_a} n_b={n_b} B={B} H={heads} N={N} D={D}")
         ws = torch.empty(wsb, dtype=torch.uint8, device=qa.device)
         _lib.check(L.dsim_score_matrix(qa.data_ptr(), ka.data_ptr(), va.data_ptr(), n_a, qb.data_ptr(), kb.data_ptr(),
-                                       vb.data_ptr(), n_b, B, heads, N, D, _TORCH2DSIM[dt], 0 if similarity == "cosine" else 1,
+                                       vb.data_ptr(), n_b, B, heads, N, D, _TORCH2DSIM[qa.dtype], 0 if similarity == "cosine" else 1,
                                        out.data_ptr(), _ptr(status), ws.data_ptr(), wsb, _stream_ptr()), "dsim_score_matrix")
     return (out, status) if return_status else out
 

@@ -22,9 +22,9 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 
 from .engine import pair_score
-from .diffsim import single_prompt
-from .inputs import _Adapter, path_latents, stack_rows
+from .inputs import path_latents
 from .parallel import gather_scores, shard_triplets
+from .scorer import stack_rows
 
 
 @torch.no_grad()
@@ -34,12 +34,12 @@ def score_latent_triplets(scorer, lat_ref: torch.Tensor, lat_left: torch.Tensor,
     """Scores (ref,left) and (ref,right) for every triplet; ref sits in slot A (noiseA), left and
     right in slot B (noiseB) exactly as two reference calls would place them.  Returns two (n,) f32
     device tensors that are bit-identical to 2n separate ``diffsim_latents`` calls (any scorer kind).
-    batch_triplets=None: the engine batch of the measured optimum (``_Adapter.auto_triplets``).
+    batch_triplets=None: the engine batch of the measured optimum (``Scorer.auto_rows``).
     prompt: one for every triplet, or (DiffSim) a sequence of n, triplet i's: each engine batch then carries its triplets'
     prompts in one forward."""
-    s_l, s_r, bad = _score_chunks(_Adapter(scorer), lat_ref, lat_left, lat_right, noiseA, noiseB, prompt, target_block,
-                                  target_layer, target_step, similarity, batch_triplets)
-    return (s_l, s_r, bad) if return_status else (s_l, s_r)
+    s_l, s_r, bad = _score_chunks(scorer, lat_ref, lat_left, lat_right, noiseA, noiseB, prompt, target_block, target_layer,
+                                  target_step, similarity, batch_triplets)
+    return (s_l[0], s_r[0], bad[0]) if return_status else (s_l[0], s_r[0])
 
 
 def read_nights_csv(image_path: str, split: str = "val") -> List[dict]:
@@ -73,31 +73,76 @@ def cute_accuracy(s_ab: torch.Tensor, s_ac: torch.Tensor) -> float:
 
 
 @torch.no_grad()
-def _score_chunks(ad: _Adapter, ref, left, right, nA, nB, prompt, block, layer, step, similarity, batch_triplets):
-    """(ref,left) and (ref,right) scores of latent triplets: 3 forwards per triplet (the reference image's features are
-    shared), chunked engine batches, one fused tail launch per chunk."""
-    n = ref.shape[0]
-    dev = ad.s.device
-    prompt = ad.rows(prompt, n)
-    s_l = torch.empty(n, dtype=torch.float32, device=dev)
-    s_r = torch.empty(n, dtype=torch.float32, device=dev)
-    bad = torch.zeros((), dtype=torch.int32, device=dev)
-    heads = ad.heads(block, layer)
-    if batch_triplets is None:
-        batch_triplets = ad.auto_triplets(block, layer, n, 1 if ad.kind != "sd15" or single_prompt(prompt) else 2)
+def triplet_chunks(scorer, ref, left, right, nA, nB, prompt, heads, similarity, batch_triplets: int, feats):
+    """(ref,left) and (ref,right) scores of latent triplets at every tap of a forward: 3 forwards per triplet (the reference
+    image's features are shared), chunked engine batches, one fused tail launch per chunk and tap.  feats(lat, nz, prompt) ->
+    [(q, k, v) per tap] is the forward of one engine batch, heads[t] tap t's head count.  Returns the (nt, n) scores of both
+    sides and the (nt,) NaN / inf counts."""
+    n, nt, dev = ref.shape[0], len(heads), scorer.device
+    s_l = torch.empty((nt, n), dtype=torch.float32, device=dev)
+    s_r = torch.empty((nt, n), dtype=torch.float32, device=dev)
+    bad = torch.zeros(nt, dtype=torch.int32, device=dev)
     for i0 in range(0, n, batch_triplets):
         i1 = min(n, i0 + batch_triplets)
         m = i1 - i0
-        q, k, v = ad.features(*stack_rows([ref, left, right], [nA, nB, nB], i0, i1), ad.chunk_prompt(prompt, i0, i1, 3), block, layer,
-                              step)
+        fs = feats(*stack_rows([ref, left, right], [nA, nB, nB], i0, i1), scorer.chunk_prompt(prompt, i0, i1, 3))
         base = torch.arange(0, 3 * m, 3, dtype=torch.int32, device=dev)
-        s, st = pair_score(q, k, v, torch.cat([base, base]), torch.cat([base + 1, base + 2]), heads, similarity, return_status=True)
-        bad += st.sum()
-        s_l[i0:i1], s_r[i0:i1] = s[:m], s[m:]
+        ia, ib = torch.cat([base, base]), torch.cat([base + 1, base + 2])
+        for t, (q, k, v) in enumerate(fs):
+            s, st = pair_score(q, k, v, ia, ib, heads[t], similarity, return_status=True)
+            bad[t] += st.sum()
+            s_l[t, i0:i1], s_r[t, i0:i1] = s[:m], s[m:]
     return s_l, s_r, bad
 
 
+def _score_chunks(scorer, ref, left, right, nA, nB, prompt, block, layer, step, similarity, batch_triplets):
+    """triplet_chunks at the one tap (block, layer): each engine batch is one ``tap_features`` call."""
+    n = ref.shape[0]
+    tap = scorer.tap_of(block, layer)
+    prompt = scorer.bind_prompt(prompt, n)
+    eng = scorer.engine_at(tap)
+    heads = eng.heads
+    if batch_triplets is None:
+        batch_triplets = scorer.auto_rows(eng, n, 3, n_ctx=scorer.n_ctx(prompt))
+    return triplet_chunks(scorer, ref, left, right, nA, nB, prompt, [heads], similarity, batch_triplets,
+                          lambda lat, nz, p: [scorer.tap_features(lat, nz, p, tap, step)])
+
+
 @torch.no_grad()
+def path_triplet_scores(scorer, triplets: Sequence[Tuple[str, str, str, str]], img_size: int, seed, rank: int, world: int,
+                        batch_triplets: int, nt: int, score):
+    """The skeleton of the path triplet runs: whole triplets sharded over ranks (the cached reference-image features stay
+    local), grouped by ``Scorer.group_key``, each group's images through ``path_latents`` in chunks of batch_triplets and
+    its latents through score(ref, left, right, nA, nB, prompt) -> (nt, n) scores of both sides and (nt,) NaN / inf counts.
+    Returns (s_ab, s_ac), each (nt, len(triplets)) on every rank, and the (nt,) counts summed over ranks."""
+    n, dev = len(triplets), scorer.device
+    sl, sr, order = [], [], []
+    nbad = torch.zeros(nt, dtype=torch.int32, device=dev)
+    # prompts differ per row.  SD1.5 and DiT: the whole shard is one group, its engine batches carry their rows' prompts (a
+    # context table, each prompt encoded once); SDXL: one group per prompt (Scorer.group_key)
+    groups = {}
+    for j in shard_triplets(n, rank, world):
+        groups.setdefault(scorer.group_key(triplets[j][3]), []).append(j)
+    for idxs in groups.values():
+        prompt = scorer.group_prompt([triplets[j][3] for j in idxs])
+        (ref, left, right), nA, nB = path_latents(scorer, [triplets[j][:3] for j in idxs], (0, 1, 1), img_size, seed,
+                                                  batch_triplets)
+        a_, b_, bad = score(ref, left, right, nA, nB, prompt)
+        nbad += bad
+        sl.append(a_); sr.append(b_); order += idxs
+    if order:
+        inv = torch.tensor(sorted(range(len(order)), key=lambda t: order[t]), dtype=torch.long, device=dev)
+        loc_l, loc_r = torch.cat(sl, 1)[:, inv], torch.cat(sr, 1)[:, inv]
+    else:
+        loc_l = loc_r = torch.empty((nt, 0), dtype=torch.float32, device=dev)
+    all_l = torch.stack([gather_scores(loc_l[t].contiguous(), n, rank, world) for t in range(nt)])
+    all_r = torch.stack([gather_scores(loc_r[t].contiguous(), n, rank, world) for t in range(nt)])
+    if world > 1:
+        import torch.distributed as dist
+        dist.all_reduce(nbad)
+    return all_l, all_r, nbad
+
+
 def score_path_triplets(scorer, triplets: Sequence[Tuple[str, str, str, str]], img_size: int, target_block, target_layer,
                         target_step, seed=2333, similarity="cosine", rank: int = 0, world: int = 1, batch_triplets: int = 10,
                         unet_triplets: Optional[int] = None):
@@ -110,37 +155,11 @@ def score_path_triplets(scorer, triplets: Sequence[Tuple[str, str, str, str]], i
     (x-0.5)/0.5, NCHW and fp16-cast arithmetic of process_image and the posterior sampling run on the device
     (dsim_image_preprocess / dsim_latent_sample), bit-identically to the per-pair path.  Returns (s_ab, s_ac, n_nonfinite):
     length-len(triplets) f32 tensors on every rank and the number of NaN/inf pair scores (NaN guard)."""
-    n = len(triplets)
-    mine = shard_triplets(n, rank, world)
-    ad = _Adapter(scorer)
-    dev = scorer.device
-    sl, sr, order = [], [], []
-    nbad = torch.zeros((), dtype=torch.int32, device=dev)
-    # prompts differ per row.  SD1.5 and DiT: the whole shard is one group, its engine batches carry their rows' prompts (a
-    # context table, each prompt encoded once); SDXL: one group per prompt (_Adapter.group_key)
-    groups = {}
-    for j in mine:
-        groups.setdefault(ad.group_key(triplets[j][3]), []).append(j)
-    for key, idxs in groups.items():
-        prompt = ad.group_prompt([triplets[j][3] for j in idxs])
-        (ref, left, right), nA, nB = path_latents(scorer, [triplets[j][:3] for j in idxs], (0, 1, 1), img_size, seed,
-                                                  batch_triplets)
-        # (batch_triplets sizes the decode / VAE-encode chunks above; the U-Net batch is chosen by the adapter)
-        a_, b_, bad = _score_chunks(ad, ref, left, right, nA, nB, prompt, target_block, target_layer, target_step, similarity,
-                                    unet_triplets)
-        nbad += bad
-        sl.append(a_); sr.append(b_); order += idxs
-    if order:
-        inv = torch.tensor(sorted(range(len(order)), key=lambda t: order[t]), dtype=torch.long, device=dev)
-        loc_l, loc_r = torch.cat(sl)[inv], torch.cat(sr)[inv]
-    else:
-        loc_l = loc_r = torch.empty(0, dtype=torch.float32, device=dev)
-    all_l = gather_scores(loc_l, n, rank, world)
-    all_r = gather_scores(loc_r, n, rank, world)
-    if world > 1:
-        import torch.distributed as dist
-        dist.all_reduce(nbad)
-    return all_l, all_r, int(nbad)
+    # (batch_triplets sizes the decode / VAE-encode chunks; the U-Net batch is unet_triplets, or the scorer's auto_rows)
+    all_l, all_r, nbad = path_triplet_scores(
+        scorer, triplets, img_size, seed, rank, world, batch_triplets, 1,
+        lambda *lat_prompt: _score_chunks(scorer, *lat_prompt, target_block, target_layer, target_step, similarity, unet_triplets))
+    return all_l[0], all_r[0], int(nbad)
 
 
 @torch.no_grad()

@@ -19,7 +19,8 @@ import torch
 import torch.nn.functional as F
 
 from .engine import pair_score_maps
-from .inputs import _Adapter, path_latents, stack_rows
+from .inputs import path_latents
+from .retrieval import ranking_names
 
 
 def grid_shape(n_tokens: int) -> Tuple[int, int]:
@@ -58,41 +59,24 @@ class SimilarityMaps:
         return F.interpolate(m.float(), size=(int(size), int(size)), mode="bilinear", align_corners=False)
 
 
-def _features_fn(ad: _Adapter, prompt, block, layer, step):
-    """lat, nz -> (q, k, v) at the tap.  diffsim_xl also takes a (context, pooled) tuple as prompt (its score_latent_pairs
-    signature); the other kinds go through the adapter."""
-    if ad.kind == "xl" and isinstance(prompt, tuple):
-        ctx, pooled = prompt
-        return lambda lat, nz: ad.s.features(lat, nz, ctx, pooled, block, layer, step)
-    return lambda lat, nz: ad.features(lat, nz, prompt, block, layer, step)
-
-
 @torch.no_grad()
 def score_latent_pair_maps(scorer, latA, latB, noiseA, noiseB, prompt, target_block="up_blocks", target_layer=0, target_step=600,
                            similarity="cosine", batch_pairs: Optional[int] = None) -> SimilarityMaps:
     """Maps of pair i = (latA[i] in slot A, latB[i] in slot B), any scorer kind (DiffSim, diffsim_xl, diffsim_DiT): the pairs of
-    ``score_latent_pairs``, in chunks of batch_pairs (None: 64 where it fits for DiffSim, the engine batch of
-    ``auto_triplets`` otherwise) -- one feature batch and one maps launch per chunk.  noiseA / noiseB: (1, C, s, s) or (n, C, s, s).
-    DiT takes target_layer as a list ([layer]), as the adapter does."""
-    ad = _Adapter(scorer)
+    ``score_latent_pairs``, in chunks of batch_pairs (None: ``Scorer.auto_map_pairs``) -- one feature batch and one maps launch
+    per chunk.  noiseA / noiseB: (1, C, s, s) or (n, C, s, s).  target_block / target_layer: the reference's flag pair
+    (``Scorer.tap_of``; DiT: [layer])."""
     dev = scorer.device
     n = latA.shape[0]
     latA, latB = latA.to(dev, torch.float32), latB.to(dev, torch.float32)
     noiseA, noiseB = noiseA.to(dev, torch.float32), noiseB.to(dev, torch.float32)
-    eng = ad.engine(target_block, target_layer)
-    heads = eng.heads
+    tap = scorer.tap_of(target_block, target_layer)
+    prompt = scorer.bind_prompt(prompt, n, "pairs")
     if batch_pairs is None:
-        batch_pairs = scorer.auto_batch_pairs(eng, n, 1) if ad.kind == "sd15" else max(1, 3 * ad.auto_triplets(target_block, target_layer, n) // 2)
-    if hasattr(eng, "max_images"):
-        batch_pairs = min(batch_pairs, eng.max_images() // 2)          # every activation must stay < 2 GiB
-    batch_pairs = max(1, int(batch_pairs))
-    feats = _features_fn(ad, prompt, target_block, target_layer, target_step)
+        batch_pairs = scorer.auto_map_pairs(scorer.engine_at(tap), n)
     score = local = contrib = None
-    for i0 in range(0, n, batch_pairs):
-        i1 = min(n, i0 + batch_pairs)
-        q, k, v = feats(*stack_rows([latA, latB], [noiseA, noiseB], i0, i1))
-        ia = torch.arange(0, 2 * (i1 - i0), 2, dtype=torch.int32, device=dev)
-        s, lo, co = pair_score_maps(q, k, v, ia, ia + 1, heads, similarity)
+    for i0, i1, (s, lo, co) in scorer.pair_chunks(latA, latB, noiseA, noiseB, prompt, tap, target_step, similarity, batch_pairs,
+                                                  pair_score_maps):
         if score is None:
             N = lo.shape[2]
             score = torch.empty(n, dtype=torch.float32, device=dev)
@@ -118,7 +102,6 @@ def score_path_pair_maps(scorer, pairs: Sequence[Tuple[str, str]], img_size, pro
 
 def map_names(paths_a: Sequence[str], root: Optional[str] = None):
     """Map file name per query: its ranking file's name (``retrieval.ranking_names``) with .npz for .txt."""
-    from .retrieval import ranking_names
     return [n[:-len(".txt")] + ".npz" for n in ranking_names(paths_a, root)]
 
 

@@ -6,7 +6,7 @@ and on b only through its slot-B features (VAE draw B, noise B).  Here every ima
 forwards instead of 2 n_a n_b -- and ``engine.score_matrix`` computes each image's self-attention once and two cross attentions
 per cell.  Cell (i, j) equals what ``diffsim(paths_a[i], paths_b[j], ...)`` / ``diffsim_latents`` return for that pair.
 
-Query features are computed once and kept; the gallery runs in chunks of the adapter's engine batch (one feature batch and one
+Query features are computed once and kept; the gallery runs in chunks of the scorer's engine batch (one feature batch and one
 ``score_matrix`` call per chunk), and the chunk is halved until the call's workspace fits a fixed share of the free HBM.
 """
 from __future__ import annotations
@@ -17,7 +17,8 @@ from typing import List, Optional, Sequence
 import torch
 
 from .engine import score_matrix, score_matrix_workspace_bytes
-from .inputs import _Adapter, path_latents, stack_rows
+from .inputs import path_latents
+from .scorer import stack_rows
 
 IMAGE_EXTS = (".png", ".jpg", ".jpeg")
 ENCODE_CHUNK = 16               # images per VAE encode, per side (32 at 512 px keep its widest activation < 2 GiB)
@@ -33,10 +34,10 @@ def list_images(root: str) -> List[str]:
     return sorted(out)
 
 
-def _features(ad: _Adapter, lat, noise, prompt, block, layer, step, batch: int):
+def _features(scorer, lat, noise, prompt, tap, step, batch: int):
     """(q, k, v) of n latents that all sit in one slot (one noise tensor), in engine batches of `batch` images."""
     n = lat.shape[0]
-    parts = [ad.features(*stack_rows([lat], [noise], i0, min(n, i0 + batch)), prompt, block, layer, step)
+    parts = [scorer.tap_features(*stack_rows([lat], [noise], i0, min(n, i0 + batch)), prompt, tap, step)
              for i0 in range(0, n, batch)]
     if len(parts) == 1:
         return tuple(t.contiguous() for t in parts[0])
@@ -48,20 +49,22 @@ def score_latent_matrix(scorer, latA, latB, noiseA, noiseB, prompt, target_block
                         similarity="cosine", batch: Optional[int] = None, return_status: bool = False):
     """(n_a, n_b) f32 device tensor: query latents latA in slot A (noiseA), gallery latents latB in slot B (noiseB), any
     scorer kind (DiffSim, diffsim_xl, diffsim_DiT).  noiseA / noiseB: (1, C, s, s), shared by every pair as in the reference.
-    batch: gallery images per chunk (None: the adapter's engine batch, 3 images per triplet of ``auto_triplets``).
+    batch: gallery images per chunk (None: the images of the triplet engine batch, ``Scorer.auto_rows``).
     return_status: also the number of NaN / infinite cells."""
-    ad = _Adapter(scorer)
     dev = scorer.device
     latA = latA.to(dev, torch.float32)
     latB = latB.to(dev, torch.float32)
     nA = noiseA.to(dev, torch.float32)
     nB = noiseB.to(dev, torch.float32)
     n_a, n_b = latA.shape[0], latB.shape[0]
-    heads = ad.heads(target_block, target_layer)
+    tap = scorer.tap_of(target_block, target_layer)
+    prompt = scorer.bind_prompt(prompt, n_a, "queries")             # (one prompt of the call)
+    eng = scorer.engine_at(tap)
+    heads = eng.heads
     if batch is None:
-        batch = 3 * ad.auto_triplets(target_block, target_layer, max(n_a, n_b))
+        batch = 3 * scorer.auto_rows(eng, max(n_a, n_b), 3)
     batch = max(1, int(batch))
-    fa = _features(ad, latA, nA, prompt, target_block, target_layer, target_step, batch)
+    fa = _features(scorer, latA, nA, prompt, tap, target_step, batch)
     out = torch.empty((n_a, n_b), dtype=torch.float32, device=dev)
     bad = torch.zeros((), dtype=torch.int64, device=dev)
     _, B, N, HD = fa[0].shape
@@ -74,7 +77,7 @@ def score_latent_matrix(scorer, latA, latB, noiseA, noiseB, prompt, target_block
         pass
     for j0 in range(0, n_b, chunk):
         j1 = min(n_b, j0 + chunk)
-        fb = _features(ad, latB[j0:j1], nB, prompt, target_block, target_layer, target_step, batch)
+        fb = _features(scorer, latB[j0:j1], nB, prompt, tap, target_step, batch)
         s, st = score_matrix(fa, fb, heads, similarity, return_status=True)
         out[:, j0:j1] = s
         bad += st.sum()

@@ -1,0 +1,232 @@
+"""What the three scorer kinds share: the protocol the batched paths speak (pairs, triplets, score matrices, similarity maps, tap
+sweeps).  ``Scorer`` is the base of DiffSim, diffsim_xl and diffsim_DiT.  Each subclass states the per-call arithmetic of its
+reference entry point (DiffSim.diffsim, diffsim_xl.diffsim_score, diffsim_DiT.diffsim_score) as attributes and a few one-line
+methods; everything here is written against those, never against a class name.
+"""
+from __future__ import annotations
+
+from typing import List, NamedTuple, Sequence, Tuple
+
+import torch
+
+from ._lib import DsimError
+from .config import DiTConfig
+
+
+def get_generator(seed, device="cpu"):
+    if seed is not None:
+        if isinstance(seed, list):
+            generator = [torch.Generator(device).manual_seed(int(s)) for s in seed]
+        else:
+            generator = torch.Generator(device).manual_seed(int(seed))
+    else:
+        generator = None
+    return generator
+
+
+class PromptTable(NamedTuple):
+    """The prompt contexts of one engine batch that carries a prompt per image: the distinct contexts (n_ctx, 2, L, Dc) f32 on the
+    device, in order of first appearance, and each image's row of that table."""
+    table: torch.Tensor
+    index: List[int]
+
+
+def single_prompt(prompt) -> bool:
+    """True for one prompt of the whole call (a string, a (2, L, Dc) context or a PromptTable already built), False for a sequence
+    with one entry per pair / triplet / image."""
+    return isinstance(prompt, (str, torch.Tensor, PromptTable))
+
+
+def distinct_prompts(prompts) -> Tuple[list, List[int]]:
+    """(the distinct entries of `prompts` in order of first appearance, each entry's position among them).  Strings are the same
+    prompt when equal, tensors when they are the same object."""
+    pos, firsts, index = {}, [], []
+    for p in prompts:
+        key = ("tensor", id(p)) if isinstance(p, torch.Tensor) else ("str", p)
+        if key not in pos:
+            pos[key] = len(firsts)
+            firsts.append(p)
+        index.append(pos[key])
+    return firsts, index
+
+
+def row_prompts(prompt, i0: int, i1: int, per_row: int):
+    """The prompts of rows [i0, i1) of a batched call image by image, each row's `per_row` images consecutive as
+    stack_rows lays them out; one prompt of the whole call stays as it is."""
+    if single_prompt(prompt):
+        return prompt
+    return [p for p in prompt[i0:i1] for _ in range(per_row)]
+
+
+def check_row_prompts(prompt, n_rows: int, what: str = "pairs"):
+    """A per-row prompt sequence as a list (ValueError unless it has one entry per row); one prompt of the call unchanged."""
+    if single_prompt(prompt):
+        return prompt
+    prompt = list(prompt)
+    if len(prompt) != n_rows:
+        raise ValueError(f"{len(prompt)} prompts for {n_rows} {what}: one prompt, or one per entry")
+    return prompt
+
+
+def stack_rows(cols: Sequence[torch.Tensor], noises: Sequence[torch.Tensor], i0: int, i1: int):
+    """Engine batch of rows [i0, i1) of k latent columns (n, C, s, s): lat (k m, C, s, s) f32, each row's k images
+    consecutive, and nz in the same layout from the columns' noises, each (1, C, s, s) shared by every row or (n, C, s, s)
+    one per row."""
+    n, shp, m = cols[0].shape[0], cols[0].shape[1:], i1 - i0
+    lat = torch.stack([c[i0:i1] for c in cols], dim=1).reshape(len(cols) * m, *shp).float()
+    nz = torch.stack([z[i0:i1] if z.shape[0] == n else z.expand(m, *shp) for z in noises], dim=1).reshape(len(cols) * m, *shp)
+    return lat, nz
+
+
+def all_taps(cfg) -> list:
+    """Every tap the model's addressing names, in walk order: SD1.5 7, SDXL 70 (24 down, 10 mid, 36 up), DiT its depth."""
+    if isinstance(cfg, DiTConfig):
+        return list(range(cfg.depth))
+    n, lpb = len(cfg.block_out_channels), cfg.layers_per_block
+    down = [t == "CrossAttnDownBlock2D" for t in cfg.down_block_types]
+    up = [t == "CrossAttnUpBlock2D" for t in cfg.up_block_types]
+    if not cfg.sdxl_tap:        # down_blocks[:-1][l], mid, up_blocks[1:][l]; attentions[-1].transformer_blocks[-1]
+        return ([("down_blocks", l) for l in range(n - 1) if down[l]] + [("mid_blocks", 0)] +
+                [("up_blocks", l) for l in range(n - 1) if up[l + 1]])
+    taps = []                   # down_blocks[1:][b], up_blocks[:-1][b]: every attention and transformer block
+    for b in range(n - 1):
+        if down[b + 1]:
+            taps += [("down_blocks", [b, a, t]) for a in range(lpb) for t in range(cfg.depth(b + 1))]
+    taps += [("mid_blocks", [0, t]) for t in range(cfg.depth(n - 1))]
+    for b in range(n - 1):
+        if up[b]:
+            taps += [("up_blocks", [b, a, t]) for a in range(lpb + 1) for t in range(cfg.depth(n - 1 - b))]
+    return taps
+
+
+class Scorer:
+    """A subclass provides ``engine(*tap address)``, ``features`` / ``features_taps`` / ``prepare_image_latents`` with its
+    reference's signatures, and the facts and one-line methods below.  The defaults are those of the two kinds whose VAE runs in
+    fp32 and hands fp16 latents on (diffsim_xl.py:61-63, diffsim_dit.py:54-59)."""
+
+    # ---- the draw rule (inputs.path_latents): how one reference call draws and rounds an image's latents and noise
+    image_half = False                      # whether the image is cast to fp16 in front of the VAE
+    round16 = True                          # whether the sampled latents round through fp16
+    noise_draw = torch.float16              # dtype the noise is drawn in
+
+    @property
+    def eps_dtype(self):
+        """dtype the VAE sample is drawn in."""
+        return getattr(self.vae, "sample_dtype", torch.float32)
+
+    def prepare(self, tensor, generator):
+        """prepare_image_latents of one image, returned as the f32 values the pipeline carries on."""
+        return self.prepare_image_latents(tensor, generator).float()
+
+    # ---- batching facts
+    mixes_prompts = True                    # whether one engine batch may carry several prompts (group_key)
+    per_row_prompts = False                 # whether a call takes a prompt per row (a context table in the engine)
+    engine_images = 128                     # images per engine batch at the batch sweeps' optimum (profiles/r04h_batch_sweep.txt)
+    one_tap_bound = True                    # whether the engine's max_images / workspace_bytes bound a one-tap batch (auto_rows)
+
+    def group_key(self, prompt):
+        """Rows of a path run with equal keys share engine batches: one group for the kinds that mix prompts, else one per
+        prompt."""
+        return prompt if not self.mixes_prompts else None
+
+    def group_prompt(self, prompts: Sequence):
+        """The prompt argument of one group's rows (group_key): the per-row list where the kind takes one and the rows differ,
+        else the group's one prompt."""
+        if self.per_row_prompts and len(distinct_prompts(prompts)[0]) > 1:
+            return list(prompts)
+        return prompts[0]
+
+    def prompt_rows(self, prompt, n_rows: int, what: str = "triplets"):
+        """A call's prompt argument checked against its rows: one prompt or one per row where the kind takes that; a kind that
+        ignores the prompt returns it untouched."""
+        return check_row_prompts(prompt, n_rows, what) if self.per_row_prompts else prompt
+
+    def bind_prompt(self, prompt, n_rows: int, what: str = "triplets"):
+        """prompt_rows, then whatever the kind encodes once per call: what tap_features / taps_features take as `prompt`."""
+        return self.prompt_rows(prompt, n_rows, what)
+
+    def chunk_prompt(self, prompt, i0: int, i1: int, per_row: int):
+        """The prompt argument of the engine batch of rows [i0, i1) (each row's per_row images consecutive)."""
+        return row_prompts(prompt, i0, i1, per_row) if self.per_row_prompts else prompt
+
+    def n_ctx(self, prompt) -> int:
+        """2 when the engine batches of a call with this (bound) prompt carry a context table, else 1."""
+        return 2 if self.per_row_prompts and not single_prompt(prompt) else 1
+
+    def auto_rows(self, eng, n_rows: int, per_row: int, taps=None, shapes=(), n_ctx: int = 1, streams: int = 1, images=None) -> int:
+        """Rows (pairs: 2 images, triplets: 3) per engine batch when the caller names none: the batch sweeps' optimum
+        (`engine_images`), within the job and the 2 GiB bound of every activation, halved until the arenas of the `streams` in use
+        fit half of the free HBM.  taps / shapes (sweep_engine's): a sweep, whose bound covers every tap output and whose arena
+        counts with the q/k/v of EVERY tap (all seven SD1.5 taps of 64 pairs hold ~7 GB).  n_ctx > 1: a context table, whose
+        per-image buffers count too.  A kind without `one_tap_bound` gets the optimum within the job for its one-tap calls."""
+        m = max(1, min((self.engine_images if images is None else images) // per_row, max(1, int(n_rows))))
+        if not taps and not self.one_tap_bound:
+            return m
+        mixed = {"n_ctx": 2} if n_ctx > 1 else {}
+        cap = eng.max_images_taps(taps, **mixed) if taps else eng.max_images(**mixed)
+        m = max(1, min(m, cap // per_row))
+        try:
+            free, _total = torch.cuda.mem_get_info(self.device)
+        except Exception:
+            return m
+        outs = sum(3 * 2 * t * h * d for t, h, d in shapes) * torch.empty((), dtype=self.dtype).element_size()
+        while m > 1:
+            k = per_row * m
+            need = eng.taps_workspace_bytes(k, taps, **mixed) + k * outs if taps else eng.workspace_bytes(k, **mixed)
+            if need * max(1, min(int(streams), -(-int(n_rows) // m))) <= 0.5 * free:
+                break
+            m = (m + 1) // 2
+        return m
+
+    def auto_map_pairs(self, eng, n: int) -> int:
+        """Pairs per engine batch of the map paths when the caller names none: the images of the triplet batch."""
+        return max(1, 3 * self.auto_rows(eng, n, 3) // 2)
+
+    # ---- tap addressing: a tap is what engine(*tap) / features(..., *tap, step) take
+    def tap_of(self, target_block, target_layer):
+        """The reference's (--target_block, --target_layer) flag pair as the scorer's tap."""
+        return target_block, target_layer
+
+    def engine_at(self, tap):
+        return self.engine(*tap)
+
+    def canonical_taps(self, taps) -> list:
+        """A sweep's taps in the scorer's form; "all": every tap the model's addressing names."""
+        if isinstance(taps, str):
+            if taps != "all":
+                raise ValueError(f"taps={taps!r}: a list of taps or 'all'")
+            return all_taps(self.cfg)
+        return [self.canonical_tap(t) for t in taps]
+
+    def sweep_engine(self, taps, side: int):
+        """The scorer's engine (created at the first tap if the scorer has none yet; its own tap is not moved after that) and the
+        (tokens, heads, head_dim) of every tap at latent side `side`."""
+        if not taps:
+            raise DsimError("no taps")
+        if self._base is None:
+            self.engine_at(taps[0])
+        self._base.set_sample_size(int(side))
+        return self._base, [self._base.tap_shape(b, l) for b, l in taps]
+
+    # ---- one features signature; `prompt` is what bind_prompt (then chunk_prompt) returned
+    def tap_features(self, lat, nz, prompt, tap, step):
+        return self.features(lat, nz, prompt, *tap, step)
+
+    def taps_features(self, lat, nz, prompt, taps, step):
+        return self.features_taps(lat, nz, prompt, taps, step)
+
+    def pair_chunks(self, latA, latB, noiseA, noiseB, prompt, tap, step, similarity, batch_pairs: int, tail):
+        """Yields (i0, i1, tail(q, k, v, idx_a, idx_b, heads, similarity)) for the pairs (latA[i] in slot A, latB[i] in slot B) in
+        engine batches of batch_pairs; tail: engine.pair_score or engine.pair_score_maps."""
+        n = latA.shape[0]
+        eng = self.engine_at(tap)
+        heads = eng.heads
+        if self.one_tap_bound:
+            batch_pairs = min(batch_pairs, eng.max_images() // 2)               # every activation must stay < 2 GiB
+        batch_pairs = max(1, int(batch_pairs))
+        for i0 in range(0, n, batch_pairs):
+            i1 = min(n, i0 + batch_pairs)
+            q, k, v = self.tap_features(*stack_rows([latA, latB], [noiseA, noiseB], i0, i1), self.chunk_prompt(prompt, i0, i1, 2),
+                                        tap, step)
+            ia = torch.arange(0, 2 * (i1 - i0), 2, dtype=torch.int32, device=self.device)
+            yield i0, i1, tail(q, k, v, ia, ia + 1, heads, similarity)

@@ -1,5 +1,5 @@
-"""Host side of many prompts per U-Net forward: the context-table builder, the engine's argument checks and the adapter's rule
-for which scorer kinds batch across prompts.  No GPU."""
+"""Host side of many prompts per U-Net forward: the context-table builder, the engine's argument checks and the scorers' rule
+for which kinds batch across prompts.  No GPU."""
 import pytest
 import torch
 
@@ -91,26 +91,24 @@ def test_engine_host_checks():
         check_ctx_table(cfg, torch.zeros(2, L, Dc), [0, 1], 2)      # (2, L, Dc): only row 0 exists
 
 
-def test_adapter_decides_which_kinds_batch_across_prompts():
+def test_scorers_decide_which_kinds_batch_across_prompts():
     from diffsim_amd.diffsim_dit import diffsim_DiT
     from diffsim_amd.diffsim_xl import diffsim_xl
-    from diffsim_amd.inputs import _Adapter
     enc = []
-    ds, _ = _scorer(enc)
-    sd = _Adapter(ds)
+    sd, _ = _scorer(enc)
     assert sd.mixes_prompts and sd.group_key("a") is None and sd.group_key("b") is None
     assert sd.group_prompt(["a", "b", "a"]) == ["a", "b", "a"]
     assert sd.group_prompt(["a", "a"]) == "a"
     assert sd.chunk_prompt(["a", "b", "c"], 1, 3, 3) == ["b"] * 3 + ["c"] * 3
-    assert sd.rows(["a", "b"], 2) == ["a", "b"]
+    assert sd.prompt_rows(["a", "b"], 2) == ["a", "b"]
     with pytest.raises(ValueError):
-        sd.rows(["a", "b"], 3)
-    xl = _Adapter(diffsim_xl(torch.float32, "cpu", unet_config=C.SDXL_TINY, state_dict={}))
+        sd.prompt_rows(["a", "b"], 3)
+    xl = diffsim_xl(torch.float32, "cpu", unet_config=C.SDXL_TINY, state_dict={})
     assert not xl.mixes_prompts and xl.group_key("a") == "a" and xl.group_key("b") == "b"
     assert xl.group_prompt(["a", "a"]) == "a"
     assert xl.chunk_prompt("a", 0, 2, 3) == "a"
-    assert xl.rows(["a", "a"], 2) == "a"
+    assert xl.prompt_rows(["a", "a"], 2) == "a"
     with pytest.raises(ValueError, match="one prompt"):
-        xl.rows(["a", "b"], 2)
-    dit = _Adapter(diffsim_DiT(128, 600, "cpu", dit_config=C.DIT_TINY, state_dict={}, torch_dtype=torch.float32))
+        xl.prompt_rows(["a", "b"], 2)
+    dit = diffsim_DiT(128, 600, "cpu", dit_config=C.DIT_TINY, state_dict={}, torch_dtype=torch.float32)
     assert dit.mixes_prompts and dit.group_key("a") is None and dit.group_key("b") is None
