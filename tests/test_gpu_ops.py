@@ -77,6 +77,36 @@ def _norm_f64(got, x0, x1, gamma, beta, dtype, *, groups=0, eps=1e-5, silu=False
     N.check(got, ref, bound, f"float64 bound {plan}")
 
 
+def _rowres_f64(eng, got, x, lg, lb, dtype, *, w=None, ff=None):
+    """beside _close: the row-resident kernels within tests/_rowres64.py's float64 bounds (x the device operand in the compute dtype,
+    the rest CPU f32 values).  w: op_ln_linear, staged -- with the 320 x 320 identity the kernel returns its own 16-bit LayerNorm
+    (lg None: x itself), and the dense launch is the plain GEMM epilogue on that operand; ff = (w1, b1, w2, b2): op_ff_fused against
+    the chained bound.  Above 4096 rows, test_gpu_rowres64's row subsets."""
+    from tests import _gemm64 as G
+    from tests import _norm64 as N
+    from tests import _rowres64 as R
+    M = x.shape[0]
+    if ff is None:
+        from tests.test_gpu_rowres64 import lin_rows
+        operand = x if lg is None else eng.op_ln_linear(x, _dev(lg), _dev(lb), torch.eye(R.C, device="cuda"), 1e-5)
+        rows = lin_rows(M)
+        G.Gemm64(operand, w.cuda(), dtype, rows=rows).check(got if rows is None else got[rows.cuda()], "float64 bound, staged")
+    else:
+        rows = None if M <= 4096 else G.row_subset(M, 128)
+        ref, bound = R.ff_ref_and_bound(x, *(_dev(t) for t in (lg, lb) + tuple(ff)), 1e-5, dtype, rows=rows)
+        N.check(got if rows is None else got[rows.cuda()], ref, bound, "float64 bound, chained")
+
+
+def _h16_cases(cases):
+    """every case in bf16 under the id it had before the fp16 twins were tested, and again in fp16"""
+    out = []
+    for c in cases:
+        c = c if isinstance(c, tuple) else (c,)
+        name = "-".join(str(v) for v in c)
+        out += [pytest.param(*c, torch.bfloat16, id=name), pytest.param(*c, torch.float16, id=name + "-fp16")]
+    return out
+
+
 @pytest.fixture(scope="module")
 def eng():
     from diffsim_amd import engine
@@ -467,12 +497,11 @@ def test_attention_peaked_logits(eng, dtype, D, scale):
     _attn_f64(got, q, k, v, H, dtype)
 
 
-@pytest.mark.parametrize("M", [128, 96, 4096 + 32, 40000])
-def test_ff_fused_320(eng, M):
-    """LayerNorm -> GEGLU projection -> ff.net.2 -> + residual as ONE launch (row-resident kernel, bf16, C = 320) against
-    the fp32 CPU chain (hacked_modules.py:118-132) and against the three-launch HIP chain it replaces."""
+@pytest.mark.parametrize("M,dtype", _h16_cases([128, 96, 4096 + 32, 40000]))
+def test_ff_fused_320(eng, M, dtype):
+    """LayerNorm -> GEGLU projection -> ff.net.2 -> + residual as ONE launch (row-resident kernel, bf16 and its fp16 twin, C = 320)
+    against the fp32 CPU chain (hacked_modules.py:118-132), the float64 chain and the three-launch HIP chain it replaces."""
     C = 320
-    dtype = torch.bfloat16
     g = torch.Generator().manual_seed(M)
     x = torch.randn(M, C, generator=g) * 1.5 + 0.3
     lg, lb = torch.randn(C, generator=g) * 0.2 + 1.0, torch.randn(C, generator=g) * 0.1
@@ -488,6 +517,7 @@ def test_ff_fused_320(eng, M):
     xd = _dev(x, dtype)
     got = eng.op_ff_fused(xd, _dev(lg), _dev(lb), _dev(w1), _dev(b1), _dev(w2), _dev(b2))
     _close(got, want, dtype)
+    _rowres_f64(eng, got, xd, lg, lb, dtype, ff=(w1, b1, w2, b2))
     # the unfused HIP chain on the same inputs: same roundings at the same places, so the two agree much tighter than the gate
     n_h = eng.op_layernorm(xd, _dev(lg), _dev(lb), 1e-5)
     hid_h = eng.op_linear(n_h, _dev(w1), _dev(b1), None, geglu=True)
@@ -498,19 +528,22 @@ def test_ff_fused_320(eng, M):
     L = eng._lib.lib()
     x2 = xd.clone()
     ws = [_dev(t) for t in (lg, lb, w1, b1, w2, b2)]
-    eng._lib.check(L.dsim_op_ff_fused(x2.data_ptr(), ws[0].data_ptr(), ws[1].data_ptr(), ws[2].data_ptr(), ws[3].data_ptr(),
-                                      ws[4].data_ptr(), ws[5].data_ptr(), x2.data_ptr(), M, C, 1e-5, None), "ff in place")
+    ptrs = [x2.data_ptr()] + [w.data_ptr() for w in ws] + [x2.data_ptr()]
+    if dtype == torch.bfloat16:        # the entry point without a dtype argument is bf16's
+        eng._lib.check(L.dsim_op_ff_fused(*ptrs, M, C, 1e-5, None), "ff in place")
+    else:
+        eng._lib.check(L.dsim_op_ff_fused_dt(*ptrs, M, C, 1e-5, eng._TORCH2DSIM[dtype], None), "ff in place")
     assert torch.equal(x2, got)
 
 
-@pytest.mark.parametrize("M,N,ln", [(128, 960, True), (96, 320, True), (4096 + 32, 960, True), (40000, 320, True), (1000, 640, False),
-                                    (33, 64, True)])
-def test_ln_linear_320(eng, M, N, ln):
-    """LayerNorm -> bias-free Linear as ONE launch (row-resident kernel, bf16, C = 320): norm1 -> to_q|to_k|to_v (N = 960)
-    and norm2 -> attn2.to_q (N = 320) of hacked_modules.py:88-116, against the fp32 CPU chain and against the two-launch HIP
-    chain it replaces (same rounding points: the normalised row is rounded to bf16 before the GEMM in both)."""
+@pytest.mark.parametrize("M,N,ln,dtype", _h16_cases([(128, 960, True), (96, 320, True), (4096 + 32, 960, True), (40000, 320, True),
+                                                      (1000, 640, False), (33, 64, True)]))
+def test_ln_linear_320(eng, M, N, ln, dtype):
+    """LayerNorm -> bias-free Linear as ONE launch (row-resident kernel, bf16 and its fp16 twin, C = 320): norm1 -> to_q|to_k|to_v
+    (N = 960) and norm2 -> attn2.to_q (N = 320) of hacked_modules.py:88-116, against the fp32 CPU chain, against float64 stage by
+    stage, and against the two-launch HIP chain it replaces (same rounding points: the normalised row is rounded to the 16-bit type
+    before the GEMM in both)."""
     C = 320
-    dtype = torch.bfloat16
     g = torch.Generator().manual_seed(M + N)
     x = torch.randn(M, C, generator=g) * 1.5 + 0.3
     lg, lb = torch.randn(C, generator=g) * 0.2 + 1.0, torch.randn(C, generator=g) * 0.1
@@ -522,6 +555,7 @@ def test_ln_linear_320(eng, M, N, ln):
     got = eng.op_ln_linear(xd, _dev(lg) if ln else None, _dev(lb) if ln else None, _dev(w))
     assert got.shape == (M, N)
     _close(got, want, dtype)
+    _rowres_f64(eng, got, xd, lg if ln else None, lb if ln else None, dtype, w=w)
     n_h = eng.op_layernorm(xd, _dev(lg), _dev(lb), 1e-5) if ln else xd
     ref_h = eng.op_linear(n_h, _dev(w), None, None)
     d = (got.float() - ref_h.float()).abs().max().item()
