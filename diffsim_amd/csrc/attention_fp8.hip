@@ -19,14 +19,6 @@
 namespace dsim {
 namespace {
 
-// max over the two 32-lane halves of a wave in every lane: one v_permlane32_swap (gfx950) instead of a ds_bpermute
-// round trip through the LDS pipe -- the softmax branches on this value once per key tile
-__device__ __forceinline__ float max_halves(float x) {
-    const unsigned u = __float_as_uint(x);
-    const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);     // r[0] = lower half, r[1] = upper half, in both
-    return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-
 constexpr int KT8 = 64;                      // kv rows per LDS tile
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 

@@ -10,7 +10,8 @@
 //
 // The three kernels write the core out each in full: the DMA piece table, the ring's hand-overs, QK^T, the softmax and the PV.
 // They share piece_voff (the DMA piece layout), vread160 (the V^T fragment reads), the dynamic LDS declaration and the host's grid,
-// softmax-constant and partial-size helpers.  The rest stays written out because moving it into shared helpers changes the
+// softmax-constant and partial-size helpers, the lane reductions max16_after_mfma and wave_sum, and common.h's max_halves /
+// half_sum / buf_rsrc.  The rest stays written out because moving it into shared helpers changes the
 // instructions hipcc emits (instruction order, register assignment, VGPR count), and the counted s_waitcnt hand-overs and the
 // inline-asm loads are checked against the exact instruction sequence around them.  A fix in one kernel's core must be repeated
 // in the other two.
@@ -61,12 +62,6 @@ constexpr int A_NDB = A_D / 32;                 // 5 output blocks over d (PV)
 #define H16_DOT2(a, b, c) __builtin_amdgcn_fdot2_f32_bf16((a), (b), (c), false)
 #endif
 
-__device__ __forceinline__ float max_halves160(float x) {
-    const unsigned u = __float_as_uint(x);
-    const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-    return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-
 // Maximum of the 16 scores a lane holds after a QK^T chain, as ONE asm statement of v_max3_f32 (fmaxf on MFMA outputs draws a
 // canonicalising v_max(x, x) per operand from hipcc: 16 more vector instructions per step).  The statement OPENS with the 12 wait
 // states an 8-pass MFMA's result needs before a vector instruction may read it: hipcc pads that hazard for its own instructions
@@ -91,12 +86,6 @@ __device__ __forceinline__ float max16_after_mfma(const f32x16& s) {
 }
 constexpr float A_THR = 8.0f;                   // log2 units a row maximum may grow past the softmax reference before a rescale
 
-// x + (the value in the lane 32 away): one v_permlane32_swap instead of a ds_bpermute round trip
-__device__ __forceinline__ float half_sum(float x) {
-    const unsigned u = __float_as_uint(x);
-    const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
 // sum over the 64 lanes (wave-uniform result): DPP row shifts leave every 16-lane row's sum in its last lane, four readlanes add
 // the rows -- VALU only (the __shfl_xor tree is six dependent LDS round trips per value), in a fixed order
 __device__ __forceinline__ float wave_sum(float x) {
@@ -382,7 +371,7 @@ __global__ __launch_bounds__(512, 2) void pair_tail160_kernel(const h16* __restr
             // exact rule the rescale -- 80 multiplies against the step's 20 MFMAs -- ran in nearly every step: one of 32 rows
             // almost always finds a new maximum among 32 more keys.)
             float tmax = max16_after_mfma(s);
-            tmax = max_halves160(tmax);
+            tmax = max_halves(tmax);
             if constexpr (FIRST) {
                 m_run = tmax;
             } else {
@@ -470,7 +459,7 @@ __global__ __launch_bounds__(512, 2) void pair_tail160_kernel(const h16* __restr
                 pack_o(ysv);
                 int ln = lane;
                 asm volatile("" : "+v"(ln));
-                const __amdgpu_buffer_rsrc_t rP = __builtin_amdgcn_make_buffer_rsrc((void*)(park + ((size_t)blockIdx.x * 8 + wave) * A_KTILE), 0, A_KTILE, 0x00020000);
+                const __amdgpu_buffer_rsrc_t rP = buf_rsrc(park + ((size_t)blockIdx.x * 8 + wave) * A_KTILE, A_KTILE);
 #pragma unroll
                 // (the slab offset rides in the VECTOR offset: a buffer_store_dwordx4 with an SGPR soffset reads its data registers late and
                 // hipcc pads only for a constant offset: profiles/r05_experiments.txt item 3b)
@@ -708,7 +697,7 @@ __global__ __launch_bounds__(512, 2) void sdpa160_kernel(const h16* __restrict__
             for (int j = 0; j < A_PRE; ++j) vf[j] = vread160(vb, j);
             __builtin_amdgcn_sched_barrier(0);
             float tmax = max16_after_mfma(s);
-            tmax = max_halves160(tmax);
+            tmax = max_halves(tmax);
             if constexpr (FIRST) {
                 m_run = tmax;
             } else {
@@ -795,7 +784,7 @@ __global__ __launch_bounds__(512, 2) void sdpa160_kernel(const h16* __restrict__
                     const u32x2 w = {__builtin_bit_cast(unsigned, v0), __builtin_bit_cast(unsigned, v1)};
                     *reinterpret_cast<u32x2*>(slab + wrow + ((4 * db + (g ^ wsw)) << 4)) = w;
                 }
-            const __amdgpu_buffer_rsrc_t rO = __builtin_amdgcn_make_buffer_rsrc((void*)((char*)og + cur.oo), 0, 31 * rbo + A_ROWB, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rO = buf_rsrc((char*)og + cur.oo, 31 * rbo + A_ROWB);
             int ln = lane;
             asm volatile("" : "+v"(ln));
 #pragma unroll
@@ -998,7 +987,7 @@ __global__ __launch_bounds__(512, 2) void matrix_cross160_kernel(const h16* __re
             for (int j = 0; j < A_PRE; ++j) vf[j] = vread160(vb, j);
             __builtin_amdgcn_sched_barrier(0);
             float tmax = max16_after_mfma(s);
-            tmax = max_halves160(tmax);
+            tmax = max_halves(tmax);
             if constexpr (FIRST) {
                 m_run = tmax;
             } else {

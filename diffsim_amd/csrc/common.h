@@ -64,6 +64,28 @@ __device__ __forceinline__ float gelu_fast(float x) {
     const float t = x * fmaf(u, fmaf(u, 1.01426306e-3f, -0.106775724f), -2.30112134f);
     return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(t));
 }
+// The two 32-lane halves of a wave combined in every lane: one v_permlane32_swap (gfx950) instead of a ds_bpermute round trip
+// through the LDS pipe.  A row of a 32 x 32 MFMA tile lives in the lanes l and l + 32, so these finish a per-row reduction: the
+// softmax maximum (branched on once per key tile), a softmax denominator, a LayerNorm sum.
+__device__ __forceinline__ float max_halves(float x) {
+    const unsigned u = __float_as_uint(x);
+    const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);     // r[0] = lower half, r[1] = upper half, in both
+    return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
+}
+__device__ __forceinline__ float half_sum(float x) {
+    const unsigned u = __float_as_uint(x);
+    const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
+// Raw buffer descriptor over [ptr, ptr + bytes) for the __builtin_amdgcn_raw_buffer_* accesses (the last word: 32-bit data format,
+// no stride or swizzle).  An access whose offset reaches `bytes` reads zeros and stores nothing; BUF_OOB is the voffset that is
+// past the end of every buffer, the one a lane without an element passes.  (__attribute__((const)): a descriptor an instantiation
+// never uses is then dropped before inlining, as the bare builtin was; without it the gemm_kernel instantiations that rebuild
+// their output descriptor per tile come out with other register assignments.)
+constexpr unsigned BUF_OOB = 0x80000000u;
+__device__ __forceinline__ __attribute__((const)) __amdgpu_buffer_rsrc_t buf_rsrc(const void* ptr, unsigned bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc((void*)ptr, 0, (int)bytes, 0x00020000);
+}
 #endif
 
 #define DSIM_HIP_CHECK(expr)                                   \
@@ -152,10 +174,11 @@ extern float* g_tail160_dbg;    // kbench: device buffer for the first unit's tw
 extern int g_tail160_exp;       // kbench: experiment mask of pair_tail160_kernel
 extern int g_ff_dbg;            // ablation mask of the fused feed-forward kernel (rowres.hip)
 extern int g_rl_dbg;            // ablation mask of the row-resident Linear kernel (rowres.hip)
-extern int g_rl_wpc;            // rowlin_kernel's persistent workgroups per CU (kbench occupancy probe)
-extern int g_ff_stagger;        // its wave de-phasing, in s_nop 7 units per wave index
+extern int g_rl_wpc;            // rowlin_kernel's persistent workgroups per CU (kbench occupancy probe; the product's 3)
+extern int g_ff_stagger;        // the feed-forward kernel's wave de-phasing, in s_nop 7 units per wave index; -1 = the product default
 #else
 constexpr int g_gemm_skinny = 1, g_gemm_persistent = 1, g_force_bm = 0, g_gemm_exp = 0, g_skinny_tile = 0;
+constexpr int g_rl_wpc = 3, g_ff_stagger = -1;
 #endif
 // The small-batch kernel's tiles, by bm + bn: gemm_skinny.hip compiles exactly these, gemm_plan() (gemm.hip) tries the first
 // kSkinnyChoices in this order

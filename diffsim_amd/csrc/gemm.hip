@@ -159,22 +159,21 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_kernel(const GemmArgs p,
     const int lrow = lane >> 3;                                   // row inside an 8-row DMA piece
     const int wrow = wave * 8 + lrow;                             // row inside a 32-row group
     const unsigned celb = ((lane & 7) ^ ((wrow >> 1) & 7)) * 16;  // swizzled source chunk (bytes)
-    constexpr unsigned OOB = 0x80000000u;                         // voffset beyond every buffer -> DMA writes zeros
 
     // Buffer descriptors: every per-lane part of an address lives in a 32-bit voffset, the K
     // advance in a scalar soffset, so the steady-state staging costs no VALU at all, and rows that
-    // must read as zero (conv padding, ragged M/N edges) simply carry an out-of-range voffset.
-    const __amdgpu_buffer_rsrc_t rA0 = __builtin_amdgcn_make_buffer_rsrc((void*)p.A0, 0, (int)p.a0_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rA1 = __builtin_amdgcn_make_buffer_rsrc((void*)(p.A1 ? p.A1 : p.A0), 0, (int)p.a1_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rW = __builtin_amdgcn_make_buffer_rsrc((void*)p.W, 0, (int)p.w_bytes, 0x00020000);
+    // must read as zero (conv padding, ragged M/N edges) simply carry the out-of-range voffset BUF_OOB.
+    const __amdgpu_buffer_rsrc_t rA0 = buf_rsrc(p.A0, p.a0_bytes);
+    const __amdgpu_buffer_rsrc_t rA1 = buf_rsrc(p.A1 ? p.A1 : p.A0, p.a1_bytes);
+    const __amdgpu_buffer_rsrc_t rW = buf_rsrc(p.W, p.w_bytes);
 #ifdef DSIM_DEVTOOLS
     // kbench ablations (timing only, outputs wrong): KB_GEXP bit 16 = residual loads dropped, bit 32 = output stores dropped
     // (zero-record descriptors: the range check drops the access, the instruction stream stays)
-    const __amdgpu_buffer_rsrc_t rO = __builtin_amdgcn_make_buffer_rsrc(p.out, 0, (p.exp & 32) ? 0 : (int)p.out_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rR = __builtin_amdgcn_make_buffer_rsrc((void*)(p.residual ? p.residual : p.out), 0, (p.exp & 16) ? 0 : (int)p.out_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rO = buf_rsrc(p.out, (p.exp & 32) ? 0 : p.out_bytes);
+    const __amdgpu_buffer_rsrc_t rR = buf_rsrc(p.residual ? p.residual : p.out, (p.exp & 16) ? 0 : p.out_bytes);
 #else
-    const __amdgpu_buffer_rsrc_t rO = __builtin_amdgcn_make_buffer_rsrc(p.out, 0, (int)p.out_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rR = __builtin_amdgcn_make_buffer_rsrc((void*)(p.residual ? p.residual : p.out), 0, (int)p.out_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rO = buf_rsrc(p.out, p.out_bytes);
+    const __amdgpu_buffer_rsrc_t rR = buf_rsrc(p.residual ? p.residual : p.out, p.out_bytes);
 #endif
 
     // ---- per-thread state of the tile being staged ---------------------------------------------
@@ -217,11 +216,11 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_kernel(const GemmArgs p,
                 a_iy0[i] = (m < p.M) ? oy * p.stride - p.pad : -(1 << 20);
                 a_ix0[i] = ox * p.stride - p.pad;
                 a_base[i] = (unsigned)b * (unsigned)(p.Hin * p.Win);
-                a_voff[i] = OOB;
+                a_voff[i] = BUF_OOB;
             } else {
                 a_iy0[i] = a_ix0[i] = 0;
-                a_base[i] = (m < p.M) ? (unsigned)m : OOB;
-                a_voff[i] = (m < p.M) ? (unsigned)m * (unsigned)p.C0 * (unsigned)sizeof(T) + celb : OOB;
+                a_base[i] = (m < p.M) ? (unsigned)m : BUF_OOB;
+                a_voff[i] = (m < p.M) ? (unsigned)m * (unsigned)p.C0 * (unsigned)sizeof(T) + celb : BUF_OOB;
             }
         }
         // batched weights (the VAE's per-image q k^T and P v): the tile's rows belong to ONE batch (wb_rows % BM == 0)
@@ -229,7 +228,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_kernel(const GemmArgs p,
 #pragma unroll
         for (int i = 0; i < NB; ++i) {
             const int n = n0 + i * (NW * 8) + wrow;
-            b_voff[i] = (n < p.N) ? wofs + (unsigned)n * (unsigned)p.K * (unsigned)sizeof(T) + celb : OOB;
+            b_voff[i] = (n < p.N) ? wofs + (unsigned)n * (unsigned)p.K * (unsigned)sizeof(T) + celb : BUF_OOB;
         }
     };
     // B pieces this wave really issues per stage (wave-uniform): the tail piece exists only for
@@ -242,7 +241,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_kernel(const GemmArgs p,
     // does everything when there is no bias).  The per-CFG-half bias2 of SDXL's resnets keeps the register path.
     constexpr bool BDMA = sizeof(T) == 2 && BM < 512;
     static_assert(!BDMA || (BN / WN) * 4 <= 1024, "bias slot");
-    const __amdgpu_buffer_rsrc_t rBias = __builtin_amdgcn_make_buffer_rsrc((void*)(p.bias ? (const void*)p.bias : p.W), 0, p.bias ? p.N * 4 : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rBias = buf_rsrc(p.bias ? (const void*)p.bias : p.W, p.bias ? p.N * 4 : 0);
     auto bias_dma = [&](int par) {       // slice of the tile setup() last ran for, into the slot of tile parity `par`
         if (BDMA && !p.bias2)
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rBias, (__attribute__((address_space(3))) void*)(smem + 2 * STAGE + SPARE + (par * NW + wave_u) * 1024), 16,
@@ -262,13 +261,13 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_kernel(const GemmArgs p,
                     const int iy = a_iy0[i] + ky, ix = a_ix0[i] + kx;
                     const bool ok = (unsigned)iy < (unsigned)Hv && (unsigned)ix < (unsigned)Wv;
                     const unsigned pix = a_base[i] + (unsigned)((iy >> p.ups) * p.Win + (ix >> p.ups));
-                    a_voff[i] = ok ? pix * (unsigned)p.C0 * (unsigned)sizeof(T) + celb : OOB;
+                    a_voff[i] = ok ? pix * (unsigned)p.C0 * (unsigned)sizeof(T) + celb : BUF_OOB;
                 }
             }
         } else if (k0 == p.C0) {      // first K tile of the concatenated second source
 #pragma unroll
             for (int i = 0; i < NA; ++i)
-                a_voff[i] = a_base[i] != OOB ? a_base[i] * (unsigned)p.C1 * (unsigned)sizeof(T) + celb : OOB;
+                a_voff[i] = a_base[i] != BUF_OOB ? a_base[i] * (unsigned)p.C1 * (unsigned)sizeof(T) + celb : BUF_OOB;
         }
     };
     // (DMAW: the LDS destination of a DMA piece is wave-uniform -- formed from the scalar wave index, M0 is then one s_add per piece
@@ -515,7 +514,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_kernel(const GemmArgs p,
         int osel = 0;
         if (!GEGLU && EK == EK_PLAIN && MODE == GEMM_LINEAR && p.out_split) osel = __builtin_amdgcn_readfirstlane(en0 / p.out_split);
         const __amdgpu_buffer_rsrc_t rOt = (!GEGLU && EK == EK_PLAIN && MODE == GEMM_LINEAR)
-            ? __builtin_amdgcn_make_buffer_rsrc((char*)p.out + (size_t)osel * p.out_split_stride, 0, (int)p.out_bytes, 0x00020000) : rO;
+            ? buf_rsrc((char*)p.out + (size_t)osel * p.out_split_stride, p.out_bytes) : rO;
         const int nout0 = (GEGLU ? (nw0 >> 1) : nw0) - osel * p.out_split;
         const int mw0 = em0 + wm * (BM / WM);
         // Addresses of the read-back pieces (round 5).  Piece `it` of slab i sits at
@@ -540,7 +539,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_kernel(const GemmArgs p,
             for (int it = 0; it < NIT; ++it) {
                 const int idx = plane + it * 64;
                 const int row = idx / CPR, c = idx - row * CPR;
-                lp[it] = (idx < 16 * CPR && nout0 + c * VEC < Nout) ? (unsigned)(row * p.ldo + c * VEC) * (unsigned)ES : OOB;
+                lp[it] = (idx < 16 * CPR && nout0 + c * VEC < Nout) ? (unsigned)(row * p.ldo + c * VEC) * (unsigned)ES : BUF_OOB;
                 lrd[it] = (row < 16 ? row : 15) * RSO + c * 16;         // rows beyond the slab read a neighbouring row; their store is dropped
             }
         }
@@ -550,7 +549,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_kernel(const GemmArgs p,
         // reads its data registers late on gfx950, and hipcc (which pads the next VALU write of a wide store's data registers only
         // for a constant soffset) then lets e.g. the next piece's address arithmetic overwrite the first data dword -- seen as
         // address-like garbage in the first 4 bytes of 16-byte pieces, on the later-dispatched waves, timing dependent.
-        auto store_v = [&](int i, int it) -> unsigned { return lp[it] == OOB ? OOB : lp[it] + sbase + (unsigned)i * sslab; };
+        auto store_v = [&](int i, int it) -> unsigned { return lp[it] == BUF_OOB ? BUF_OOB : lp[it] + sbase + (unsigned)i * sslab; };
         // residual prefetch: slab i's 16-byte pieces are requested before slab i is transposed, so the HBM latency
         // hides under the register phase instead of serialising the stores (at most 10 pieces in flight per lane:
         // the f32 parity mode would spill with all 20)
@@ -633,7 +632,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_kernel(const GemmArgs p,
                         const h16x2 pr = __builtin_convertvector((f32x2){(float)t[e] + (float)r[e], (float)t[e + 1] + (float)r[e + 1]}, h16x2);
                         o16[e] = pr[0]; o16[e + 1] = pr[1];
                     }
-                    if (lp[it] != OOB) gn_acc(o16);
+                    if (lp[it] != BUF_OOB) gn_acc(o16);
                     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o16), rO, (int)store_v(i, it), 0, 0);
                 }
             }
@@ -697,7 +696,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_kernel(const GemmArgs p,
             for (int it = 0; it < NIT; ++it) {
                 const V16 t = *reinterpret_cast<const V16*>(wst + lrd[it]);
                 if (!SLOW && !ACT && !has_res) {         // plain projection: LDS -> HBM copy
-                    if (lp[it] != OOB) gn_acc(t);
+                    if (lp[it] != BUF_OOB) gn_acc(t);
                     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, t), rOt, (int)store_v(i, it), 0, 0);
                     continue;
                 }

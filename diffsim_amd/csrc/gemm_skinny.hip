@@ -39,16 +39,15 @@ __global__ __launch_bounds__(SNW * 64, 1) void gemm_skinny_kernel(const GemmArgs
     constexpr int TM = SBM / (16 * WLM), TN = SBN / (16 * WLN);      // 16 x 16 accumulator tiles per wave
     static_assert(SBM % (16 * WLM) == 0 && SBN % (16 * WLN) == 0 && SBM % 32 == 0, "wave tile");
     static_assert(SDEPTH >= 3 && (SDEPTH - 2) * SPW <= 63, "ring");
-    constexpr unsigned OOB = 0x80000000u;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);     // (scalar: the DMA pieces' LDS destinations need no v_readfirstlane)
     const int wm = W41 ? wave : wave >> 1, wn = W41 ? 0 : wave & 1;
     const int l15 = lane & 15, quad = lane >> 4, lrow = lane >> 3;
     const int wrow = wave * 8 + lrow;                                 // row inside a 32-row group of DMA pieces
     const unsigned celb = ((lane & 7) ^ ((wrow >> 1) & 7)) * 16;      // swizzled source chunk (gemm_kernel's LDS image)
-    const __amdgpu_buffer_rsrc_t rA0 = __builtin_amdgcn_make_buffer_rsrc((void*)p.A0, 0, (int)p.a0_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rA1 = __builtin_amdgcn_make_buffer_rsrc((void*)(p.A1 ? p.A1 : p.A0), 0, (int)p.a1_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rW = __builtin_amdgcn_make_buffer_rsrc((void*)p.W, 0, (int)p.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rA0 = buf_rsrc(p.A0, p.a0_bytes);
+    const __amdgpu_buffer_rsrc_t rA1 = buf_rsrc(p.A1 ? p.A1 : p.A0, p.a1_bytes);
+    const __amdgpu_buffer_rsrc_t rW = buf_rsrc(p.W, p.w_bytes);
 
     const int m0 = (blockIdx.x / tilesN) * SBM, n0 = (blockIdx.x % tilesN) * SBN;
     // the activation rows and the weight rows this lane stages per K tile
@@ -75,13 +74,13 @@ __global__ __launch_bounds__(SNW * 64, 1) void gemm_skinny_kernel(const GemmArgs
             a_base[i] = (unsigned)b * (unsigned)(p.Hin * p.Win);
         } else {
             a_iy0[i] = a_ix0[i] = 0;
-            a_base[i] = (m < p.M) ? (unsigned)m : OOB;
+            a_base[i] = (m < p.M) ? (unsigned)m : BUF_OOB;
         }
     }
 #pragma unroll
     for (int i = 0; i < NBP; ++i) {
         const int n = n0 + i * 32 + wrow;
-        b_voff[i] = (n < p.N && i * 32 + wrow < SBN) ? (unsigned)n * (unsigned)p.K * (unsigned)ES + celb : OOB;
+        b_voff[i] = (n < p.N && i * 32 + wrow < SBN) ? (unsigned)n * (unsigned)p.K * (unsigned)ES + celb : BUF_OOB;
     }
     auto issue = [&](int t) {
         char* sa = smem + (t % SDEPTH) * SSTAGE;
@@ -99,11 +98,11 @@ __global__ __launch_bounds__(SNW * 64, 1) void gemm_skinny_kernel(const GemmArgs
                 const int iy = a_iy0[i] + ky, ix = a_ix0[i] + kx;
                 const bool ok = (unsigned)iy < (unsigned)Hv && (unsigned)ix < (unsigned)Wv;
                 const unsigned pix = a_base[i] + (unsigned)((iy >> p.ups) * p.Win + (ix >> p.ups));
-                vo = ok ? pix * (unsigned)p.C0 * (unsigned)ES + celb : OOB;
+                vo = ok ? pix * (unsigned)p.C0 * (unsigned)ES + celb : BUF_OOB;
             } else {
                 second = k0 >= p.C0;
                 soff = (second ? k0 - p.C0 : k0) * ES;
-                vo = a_base[i] != OOB ? a_base[i] * (unsigned)(second ? p.C1 : p.C0) * (unsigned)ES + celb : OOB;
+                vo = a_base[i] != BUF_OOB ? a_base[i] * (unsigned)(second ? p.C1 : p.C0) * (unsigned)ES + celb : BUF_OOB;
             }
             auto lds = (__attribute__((address_space(3))) void*)(sa + (i * SNW + wave) * 1024);
             if (second) __builtin_amdgcn_raw_ptr_buffer_load_lds(rA1, lds, 16, (int)vo, soff, 0, 0);
@@ -167,8 +166,8 @@ __global__ __launch_bounds__(SNW * 64, 1) void gemm_skinny_kernel(const GemmArgs
         }
     }
     // ---- epilogue: gemm_kernel's rounding points (bias in f32, round to the 16-bit type, then the residual add and a second round)
-    const __amdgpu_buffer_rsrc_t rO = __builtin_amdgcn_make_buffer_rsrc(p.out, 0, (int)p.out_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rR = __builtin_amdgcn_make_buffer_rsrc((void*)(p.residual ? p.residual : p.out), 0, (int)p.out_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rO = buf_rsrc(p.out, p.out_bytes);
+    const __amdgpu_buffer_rsrc_t rR = buf_rsrc(p.residual ? p.residual : p.out, p.out_bytes);
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
         const int m = m0 + wm * (SBM / WLM) + i * 16 + l15;
@@ -176,7 +175,7 @@ __global__ __launch_bounds__(SNW * 64, 1) void gemm_skinny_kernel(const GemmArgs
         for (int j = 0; j < TN; ++j) {
             const int nb = n0 + wn * (SBN / WLN) + j * 16 + 4 * quad;
             const bool ok = m < p.M && nb < p.N;
-            const unsigned off = ok ? ((unsigned)m * (unsigned)p.ldo + (unsigned)nb) * (unsigned)ES : OOB;
+            const unsigned off = ok ? ((unsigned)m * (unsigned)p.ldo + (unsigned)nb) * (unsigned)ES : BUF_OOB;
             float v[4];
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = acc[i][j][e];

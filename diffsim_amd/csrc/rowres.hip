@@ -6,19 +6,22 @@
 // written + 1.34 GB read per layer at 32 pairs) and spent as long in the erf-GELU epilogue as in the MFMAs.
 //
 // Design: a wave owns 32 token rows for the whole chain; nothing but the weights ever crosses waves.
-//   * The wave loads its 32 x 320 rows once, normalises them in registers (a row lives in the two lanes l, l + 32)
-//     and keeps them as the 20 B-operand fragments of v_mfma_f32_32x32x16_bf16 (80 VGPRs).
+//   * The wave loads its 32 x 320 rows once, normalises them in registers (row_stats / row_norm: a row lives in the two
+//     lanes l, l + 32) and keeps them as the 20 B-operand fragments of v_mfma_f32_32x32x16_bf16 (80 VGPRs).
 //   * The hidden dimension is walked in chunks of 32: [h_c ; g_c]^T = W1_c X^T (two D^T accumulator tiles, K = 320),
 //     hid_c = h_c * gelu(g_c) stays in the accumulator layout -- column (token) on the lane, hidden index in the
 //     registers -- which IS the B operand of the second product out^T += W2_c hid_c^T (guide: "an accumulator tile as the
 //     next MFMA's operand"); its permuted k order is baked into the packed W2.  out^T (320 x 32 f32) = 160 accumulator
 //     registers.  With 1 wave per SIMD the kernel has the whole 512-register file.
-//   * Weights: one linear stream per layer, already in LDS image order (XOR-swizzled 16-byte chunks), 60 KB per
+//   * Weights: one linear stream per layer, already in LDS image order (W1: slab_chunk / slab_off below), 60 KB per
 //     iteration [W1 of chunk it | W2 of chunk it-2], copied by LDS-DMA into a 2-slot ring, one barrier per iteration
 //     (the biases and the LayerNorm affine stay in LDS for the whole kernel).  Iteration `it` runs GEMM1(it), the GELU of
 //     chunk it-1 and GEMM2(it-2): three independent register sets, so the GELU's VALU instructions and the ring's DMA
 //     issues sit in the shadow of 60 MFMAs (<= 4 single-issue fillers per MFMA: MI355X_MICROARCH.md, "HIDDEN per gap").
-//   * Epilogue: + b2 (accumulator init), D^T -> row-major through a wave-private LDS slab, + residual, 16-byte stores.
+//   * Epilogue: + b2 (accumulator init), D^T -> row-major through a wave-private LDS slab (slab_put), + residual, 16-byte
+//     stores.
+// rowlin_kernel, further down, is the same row-resident scheme for one Linear behind an optional LayerNorm: the same rows in
+// registers, the same LayerNorm, weight-slab image and transpose slab.
 // The h16 GELU here is x * sigmoid(x (a + b u + c u^2)), u = min(x^2, 64): |err| <= 2.6e-5 absolute against the erf form
 // (h16 resolution at 1.0 is 3.9e-3); the fp32 parity mode never takes this path.
 #include "common.h"
@@ -38,22 +41,37 @@ constexpr int RPIECES = RCHB / 1024;          // 60 LDS-DMA pieces: 15 per wave,
 constexpr int RPW = RPIECES / 4;
 // resident vectors (f32): b1 [8C] GEGLU-interleaved, b2 [C], LayerNorm gamma / beta [C]
 constexpr int RB1 = 0, RB2 = 8 * RC, RLG = 9 * RC, RLB = 10 * RC, RVEC = 11 * RC;
-constexpr int RSCR = 32 * 144;                // per-wave transpose slab: 32 rows x (64 cols h16 + 16 pad)
+constexpr int SLABP = 144;                    // row pitch of a wave's transpose slab: 64 columns of h16 + 16 bytes of padding
+constexpr int RSCR = 32 * SLABP;              // per-wave transpose slab of the feed-forward: 32 rows
 constexpr int RLDS = 2 * RCHB + RVEC * 4 + 4 * RSCR;     // 155392
 static_assert(RPIECES % 4 == 0 && RITER % 2 == 0, "ring geometry");
 
-// stream chunk ci, 16-byte unit u: see the layout comment at the top
+// ---- the swizzled [rows][128 B] weight slab --------------------------------------------------------------------------------
+// A block of weight rows x K = 320 (W1 of a hidden chunk: 64 rows; a rowlin block: 32 rows) lies in the stream, and so in the LDS
+// ring, as five slabs of 64 k: [rows][128 B] each, the positions of row r's eight 16-byte chunks XORed with (r >> 1) & 7, so that
+// the A-operand fragment reads -- 32 consecutive rows at one chunk -- do not all fall on the same banks.  slab_chunk() is the
+// packers' side of it (which chunk of the row-major weight lies at chunk position cpos of slab row `row`), slab_off() the
+// kernels' (the byte of a slab at which chunk c of row `row` is found).  They are inverses:
+//     slab_off(row, slab_chunk(row, cpos)) == row * 128 + cpos * 16,
+// because the XOR term is its own inverse; a change to one is a change to both.
+__device__ __forceinline__ int slab_chunk(int row, int cpos) { return cpos ^ ((row >> 1) & 7); }
+__device__ __forceinline__ int slab_off(int row, int c) { const int s = (row >> 1) & 7; return row * 128 + ((c ^ s) << 4); }
+// The 16 bytes the image of weight rows [row0, row0 + rows) of the packed [N][320] matrix w holds at chunk position cpos of row
+// `row` of slab `slab`.  (Byte o of an image is slab o / (rows * 128), row o % (rows * 128) / 128, position o % 128 / 16: the
+// packers split o themselves -- split in here, hipcc narrows the arithmetic differently and their code changes.)
+__device__ __forceinline__ u32x4 slab_image(const h16* __restrict__ w, int row0, int slab, int row, int cpos) {
+    const int cl = slab_chunk(row, cpos);
+    return *reinterpret_cast<const u32x4*>(w + (size_t)(row0 + row) * RC + 64 * slab + 8 * cl);
+}
+
+// stream chunk ci, 16-byte unit u: see the layout comment at the top (W1: the slab image of the chunk's 64 rows)
 __global__ void pack_ff_stream_kernel(const h16* __restrict__ w1p, const h16* __restrict__ w2p, char* __restrict__ stream) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= RITER * (RCHB / 16)) return;
     const int ci = i / (RCHB / 16), o = (i - ci * (RCHB / 16)) * 16;
     u32x4 v = {0u, 0u, 0u, 0u};
     if (o < RW1B) {
-        if (ci < RNCH) {
-            const int slab = o / 8192, row = (o % 8192) / 128, cpos = (o % 128) / 16;
-            const int cl = cpos ^ ((row >> 1) & 7);
-            v = *reinterpret_cast<const u32x4*>(w1p + (size_t)(64 * ci + row) * RC + 64 * slab + 8 * cl);
-        }
+        if (ci < RNCH) v = slab_image(w1p, 64 * ci, o / 8192, (o % 8192) / 128, (o % 128) / 16);
     } else {
         if (ci >= 2) {
             const int c = ci - 2, o2 = o - RW1B;
@@ -68,6 +86,60 @@ __global__ void pack_ff_stream_kernel(const h16* __restrict__ w1p, const h16* __
         }
     }
     *reinterpret_cast<u32x4*>(stream + (size_t)ci * RCHB + o) = v;
+}
+
+// ---- a wave's 32 rows in registers ------------------------------------------------------------------------------------------
+// Row l31 of the tile lives in the lanes l31 and l31 + 32 as RKS raw h16 B-operand fragments: lane (l31, half) holds the columns
+// 16 ks + 8 half .. + 7 in x[ks].  The LayerNorm is three passes over those registers (sum, centred squares, normalise): an f32
+// copy of the rows would not fit beside them in the 256 architectural VGPRs the VALU can address.  row_stats() is the first two
+// passes, row_norm() the third for one fragment; the kernels choose where the normalised fragment goes.
+__device__ __forceinline__ void row_stats(u32x4 (&x)[RKS], float eps, float& mean, float& rstd) {
+    float sum = 0.f;
+#pragma unroll
+    for (int ks = 0; ks < RKS; ++ks) {
+        const h16x8 t = __builtin_bit_cast(h16x8, x[ks]);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) sum += (float)t[j];
+    }
+    sum = half_sum(sum);
+    mean = sum * (1.0f / RC);
+    float sq = 0.f;
+#pragma unroll
+    for (int ks = 0; ks < RKS; ++ks) {
+        asm volatile("" : "+v"(x[ks]));      // (opaque: keeps hipcc from carrying the f32 conversions from pass to pass)
+        const h16x8 t = __builtin_bit_cast(h16x8, x[ks]);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { const float d = (float)t[j] - mean; sq = fmaf(d, d, sq); }
+    }
+    sq = half_sum(sq);
+    rstd = 1.0f / sqrtf(sq * (1.0f / RC) + eps);
+}
+// gamma, beta: the resident f32 [RC] vectors in LDS
+__device__ __forceinline__ h16x8 row_norm(u32x4& x, int ks, int half, float mean, float rstd, const float* gamma, const float* beta) {
+    const int c = 16 * ks + 8 * half;
+    const f32x4 g0 = *reinterpret_cast<const f32x4*>(gamma + c), g1 = *reinterpret_cast<const f32x4*>(gamma + c + 4);
+    const f32x4 b0 = *reinterpret_cast<const f32x4*>(beta + c), b1 = *reinterpret_cast<const f32x4*>(beta + c + 4);
+    asm volatile("" : "+v"(x));
+    const h16x8 t = __builtin_bit_cast(h16x8, x);
+    h16x8 y;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        y[j] = (h16)fmaf(((float)t[j] - mean) * rstd, g0[j], b0[j]);
+        y[4 + j] = (h16)fmaf(((float)t[4 + j] - mean) * rstd, g1[j], b1[j]);
+    }
+    return y;
+}
+// Epilogues: a 32 x 32 D^T accumulator tile (the lane's token on the lane, output column 8 q + 4 half + e in register 4 q + e)
+// goes to row-major through a wave-private slab of SLABP-byte rows.  This is the lane's 16 values, as h16, into the slab row
+// `srow` at the columns 32 bb .. 32 bb + 31.
+__device__ __forceinline__ void slab_put(char* srow, int bb, int half, const f32x16& a) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        h16x4 pk;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) pk[e] = (h16)a[4 * q + e];
+        *reinterpret_cast<h16x4*>(srow + (bb * 32 + 8 * q + 4 * half) * 2) = pk;
+    }
 }
 
 struct FFParams {
@@ -91,11 +163,10 @@ __global__ __launch_bounds__(256, 1) void ff_fused_kernel(const FFParams p, cons
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, half = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    constexpr unsigned OOB = 0x80000000u;
 
-    const __amdgpu_buffer_rsrc_t rX = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, (int)p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rO = __builtin_amdgcn_make_buffer_rsrc((void*)p.out, 0, (int)p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rS = __builtin_amdgcn_make_buffer_rsrc((void*)p.stream, 0, (int)p.stream_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rX = buf_rsrc(p.x, p.x_bytes);
+    const __amdgpu_buffer_rsrc_t rO = buf_rsrc(p.out, p.x_bytes);
+    const __amdgpu_buffer_rsrc_t rS = buf_rsrc(p.stream, p.stream_bytes);
 
     // ring: piece d (0..14) of this wave for stream chunk ci into the slot of parity sp; a wave copies 15 KB contiguous
     auto dma = [&](int sp, int ci, int d) {
@@ -115,10 +186,9 @@ __global__ __launch_bounds__(256, 1) void ff_fused_kernel(const FFParams p, cons
     }
 
     // per-lane LDS read offsets inside a slot
-    const int sw1 = (l31 >> 1) & 7;
     int w1off[4];
 #pragma unroll
-    for (int kk = 0; kk < 4; ++kk) w1off[kk] = l31 * 128 + (((2 * kk + half) ^ sw1) << 4);
+    for (int kk = 0; kk < 4; ++kk) w1off[kk] = slab_off(l31, 2 * kk + half);
     const int sw2 = (l31 >> 2) & 3;
     int w2off[2];
 #pragma unroll
@@ -128,7 +198,7 @@ __global__ __launch_bounds__(256, 1) void ff_fused_kernel(const FFParams p, cons
     u32x4 raw[RKS];
     auto load_rows = [&](int tile) {
         const int row = tile * 128 + wave * 32 + l31;
-        const unsigned rbase = (tile < ntiles && row < p.M) ? (unsigned)row * (RC * 2) + half * 16 : OOB;
+        const unsigned rbase = (tile < ntiles && row < p.M) ? (unsigned)row * (RC * 2) + half * 16 : BUF_OOB;
 #pragma unroll
         for (int ks = 0; ks < RKS; ++ks) raw[ks] = __builtin_amdgcn_raw_buffer_load_b128(rX, (int)(rbase + ks * 32), 0, 0);
     };
@@ -138,50 +208,12 @@ __global__ __launch_bounds__(256, 1) void ff_fused_kernel(const FFParams p, cons
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const int m0 = tile * 128 + wave * 32;
         // ---- LayerNorm in registers -> B-operand fragments ---------------------------------------
-        // three passes over the h16 registers (sum, centred squares, normalise): an f32 copy of the rows would not fit
-        // beside them in the 256 architectural VGPRs the VALU can address
         h16x8 X[RKS];
         {
-            float sum = 0.f;
+            float mean, rstd;
+            row_stats(raw, p.eps, mean, rstd);
 #pragma unroll
-            for (int ks = 0; ks < RKS; ++ks) {
-                const h16x8 t = __builtin_bit_cast(h16x8, raw[ks]);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) sum += (float)t[j];
-            }
-            {
-                const unsigned u = __float_as_uint(sum);
-                const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-                sum = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-            }
-            const float mean = sum * (1.0f / RC);
-            float sq = 0.f;
-#pragma unroll
-            for (int ks = 0; ks < RKS; ++ks) {
-                asm volatile("" : "+v"(raw[ks]));      // (opaque: keeps hipcc from carrying the f32 conversions from pass to pass)
-                const h16x8 t = __builtin_bit_cast(h16x8, raw[ks]);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) { const float d = (float)t[j] - mean; sq = fmaf(d, d, sq); }
-            }
-            {
-                const unsigned u = __float_as_uint(sq);
-                const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-                sq = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-            }
-            const float rstd = 1.0f / sqrtf(sq * (1.0f / RC) + p.eps);
-#pragma unroll
-            for (int ks = 0; ks < RKS; ++ks) {
-                const int c = 16 * ks + 8 * half;
-                const f32x4 g0 = *reinterpret_cast<const f32x4*>(vec + RLG + c), g1 = *reinterpret_cast<const f32x4*>(vec + RLG + c + 4);
-                const f32x4 b0 = *reinterpret_cast<const f32x4*>(vec + RLB + c), b1 = *reinterpret_cast<const f32x4*>(vec + RLB + c + 4);
-                asm volatile("" : "+v"(raw[ks]));
-                const h16x8 t = __builtin_bit_cast(h16x8, raw[ks]);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    X[ks][j] = (h16)fmaf(((float)t[j] - mean) * rstd, g0[j], b0[j]);
-                    X[ks][4 + j] = (h16)fmaf(((float)t[4 + j] - mean) * rstd, g1[j], b1[j]);
-                }
-            }
+            for (int ks = 0; ks < RKS; ++ks) X[ks] = row_norm(raw[ks], ks, half, mean, rstd, vec + RLG, vec + RLB);
         }
         __builtin_amdgcn_sched_barrier(0);
         // ---- out^T accumulators start at b2 ----------------------------------------------------
@@ -321,25 +353,18 @@ __global__ __launch_bounds__(256, 1) void ff_fused_kernel(const FFParams p, cons
 #pragma unroll
             for (int it = 0; it < 4; ++it) {
                 const int idx = lane + it * 64, r = idx >> 3, c = idx & 7;
-                const unsigned go = (m0 + r) < p.M ? (unsigned)(m0 + r) * (RC * 2) + (unsigned)(pp * 128 + c * 16) : OOB;
+                const unsigned go = (m0 + r) < p.M ? (unsigned)(m0 + r) * (RC * 2) + (unsigned)(pp * 128 + c * 16) : BUF_OOB;
                 res[pp][it] = __builtin_amdgcn_raw_buffer_load_b128(rX, (int)go, 0, 0);
             }
 #pragma unroll
         for (int pp = 0; pp < RNB / 2; ++pp) {
 #pragma unroll
-            for (int bb = 0; bb < 2; ++bb)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    h16x4 pk;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) pk[e] = (h16)out[2 * pp + bb][4 * q + e];
-                    *reinterpret_cast<h16x4*>(slab + l31 * 144 + (bb * 32 + 8 * q + 4 * half) * 2) = pk;
-                }
+            for (int bb = 0; bb < 2; ++bb) slab_put(slab + l31 * SLABP, bb, half, out[2 * pp + bb]);
 #pragma unroll
             for (int it = 0; it < 4; ++it) {
                 const int idx = lane + it * 64, r = idx >> 3, c = idx & 7;
-                const unsigned go = (m0 + r) < p.M ? (unsigned)(m0 + r) * (RC * 2) + (unsigned)(pp * 128 + c * 16) : OOB;
-                const h16x8 t = *reinterpret_cast<const h16x8*>(slab + r * 144 + c * 16);
+                const unsigned go = (m0 + r) < p.M ? (unsigned)(m0 + r) * (RC * 2) + (unsigned)(pp * 128 + c * 16) : BUF_OOB;
+                const h16x8 t = *reinterpret_cast<const h16x8*>(slab + r * SLABP + c * 16);
                 const h16x8 rr = __builtin_bit_cast(h16x8, res[pp][it]);
                 h16x8 o;
 #pragma unroll
@@ -358,22 +383,19 @@ __global__ __launch_bounds__(256, 1) void ff_fused_kernel(const FFParams p, cons
 // two-stage ring one 1.2 us K step of cover for activations that stream from HBM exactly once (726 TF/s, 3.0 TB/s at N = 960),
 // and the LayerNorm in front costs a full read + write of the tensor.  Here a wave keeps its 32 rows in registers
 // (normalised on arrival), the weights stream through a 2-slot LDS ring in 32-column blocks, the output leaves in
-// 128-byte row segments per pair of blocks -- HBM-bound, one pass.  Two 4-wave workgroups per CU (<= 256 registers, 66 KB
-// of LDS): one workgroup's row loads and stores sit under the other's MFMAs.
+// 128-byte row segments per pair of blocks -- HBM-bound, one pass.  Three 4-wave workgroups per CU (__launch_bounds__(256, 3):
+// <= 168 registers; LLDS = 52736 bytes of LDS each): one workgroup's row loads and stores sit under the others' MFMAs.
 constexpr int LCHB = 32 * RC * 2;              // 20480 bytes per ring slot: W rows [32 b, 32 b + 32) x K 320, five [32][128 B] slabs
 constexpr int LPW = LCHB / 1024 / 4;           // 5 DMA pieces per wave per block
 constexpr int LVEC = 2 * RC;                   // resident f32: LayerNorm gamma, beta
-constexpr int LSCR = 16 * 144;                 // per-wave transpose slab: 16 rows x (64 cols h16 + 16 pad)
+constexpr int LSCR = 16 * SLABP;               // per-wave transpose slab: 16 rows
 constexpr int LLDS = 2 * LCHB + LVEC * 4 + 4 * LSCR;      // 52736: three workgroups per CU
 
 __global__ void pack_rowlin_stream_kernel(const h16* __restrict__ wp, char* __restrict__ stream, int N) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= N / 32 * (LCHB / 16)) return;
     const int b = i / (LCHB / 16), o = (i - b * (LCHB / 16)) * 16;
-    const int slab = o / 4096, row = (o % 4096) / 128, cpos = (o % 128) / 16;
-    const int cl = cpos ^ ((row >> 1) & 7);
-    *reinterpret_cast<u32x4*>(stream + (size_t)b * LCHB + o) =
-        *reinterpret_cast<const u32x4*>(wp + (size_t)(32 * b + row) * RC + 64 * slab + 8 * cl);
+    *reinterpret_cast<u32x4*>(stream + (size_t)b * LCHB + o) = slab_image(wp, 32 * b, o / 4096, (o % 4096) / 128, (o % 128) / 16);
 }
 
 struct RLParams {
@@ -392,10 +414,9 @@ __global__ __launch_bounds__(256, 3) void rowlin_kernel(const RLParams p, const 
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, half = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    constexpr unsigned OOB = 0x80000000u;
-    const __amdgpu_buffer_rsrc_t rX = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, (int)p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rO = __builtin_amdgcn_make_buffer_rsrc((void*)p.out, 0, (int)p.out_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rS = __builtin_amdgcn_make_buffer_rsrc((void*)p.stream, 0, (int)p.stream_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rX = buf_rsrc(p.x, p.x_bytes);
+    const __amdgpu_buffer_rsrc_t rO = buf_rsrc(p.out, p.out_bytes);
+    const __amdgpu_buffer_rsrc_t rS = buf_rsrc(p.stream, p.stream_bytes);
     const int nblk = p.N / 32;                 // even
     auto dma = [&](int sp, int blk) {           // this wave's five pieces of weight block `blk` into the slot of parity sp
         char* dst = smem + sp * LCHB + wave * (LPW * 1024);
@@ -409,10 +430,9 @@ __global__ __launch_bounds__(256, 3) void rowlin_kernel(const RLParams p, const 
     if (p.ln_g)
         for (int i = tid; i < LVEC; i += 256) vec[i] = i < RC ? p.ln_g[i] : p.ln_b[i - RC];
     char* const slab = smem + 2 * LCHB + LVEC * 4 + wave * LSCR;
-    const int sw1 = (l31 >> 1) & 7;
     int woff[4];
 #pragma unroll
-    for (int kk = 0; kk < 4; ++kk) woff[kk] = l31 * 128 + (((2 * kk + half) ^ sw1) << 4);
+    for (int kk = 0; kk < 4; ++kk) woff[kk] = slab_off(l31, 2 * kk + half);
     __syncthreads();
     int blk = 0;                                // weight block the NEXT ring step consumes (wraps at nblk: same weights for every tile)
 
@@ -422,52 +442,16 @@ __global__ __launch_bounds__(256, 3) void rowlin_kernel(const RLParams p, const 
         u32x4 xr[RKS];
         {
             const int row = m0 + l31;
-            const unsigned rbase = row < p.M ? (unsigned)row * (RC * 2) + half * 16 : OOB;
+            const unsigned rbase = row < p.M ? (unsigned)row * (RC * 2) + half * 16 : BUF_OOB;
 #pragma unroll
             for (int ks = 0; ks < RKS; ++ks)
                 xr[ks] = (DBG & 4) ? u32x4{(unsigned)ks, 1u, 2u, rbase} : __builtin_amdgcn_raw_buffer_load_b128(rX, (int)(rbase + ks * 32), 0, 0);
-            if (p.ln_g) {                       // the LayerNorm of ff_fused_kernel (three passes over the h16 registers)
-                float sum = 0.f;
+            if (p.ln_g) {                       // in place, fragment by fragment
+                float mean, rstd;
+                row_stats(xr, p.eps, mean, rstd);
 #pragma unroll
                 for (int ks = 0; ks < RKS; ++ks) {
-                    const h16x8 t = __builtin_bit_cast(h16x8, xr[ks]);
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) sum += (float)t[j];
-                }
-                {
-                    const unsigned u = __float_as_uint(sum);
-                    const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-                    sum = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-                }
-                const float mean = sum * (1.0f / RC);
-                float sq = 0.f;
-#pragma unroll
-                for (int ks = 0; ks < RKS; ++ks) {
-                    asm volatile("" : "+v"(xr[ks]));
-                    const h16x8 t = __builtin_bit_cast(h16x8, xr[ks]);
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) { const float d = (float)t[j] - mean; sq = fmaf(d, d, sq); }
-                }
-                {
-                    const unsigned u = __float_as_uint(sq);
-                    const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-                    sq = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-                }
-                const float rstd = 1.0f / sqrtf(sq * (1.0f / RC) + p.eps);
-#pragma unroll
-                for (int ks = 0; ks < RKS; ++ks) {
-                    const int c = 16 * ks + 8 * half;
-                    const f32x4 g0 = *reinterpret_cast<const f32x4*>(vec + c), g1 = *reinterpret_cast<const f32x4*>(vec + c + 4);
-                    const f32x4 b0 = *reinterpret_cast<const f32x4*>(vec + RC + c), b1 = *reinterpret_cast<const f32x4*>(vec + RC + c + 4);
-                    asm volatile("" : "+v"(xr[ks]));
-                    const h16x8 t = __builtin_bit_cast(h16x8, xr[ks]);
-                    h16x8 y;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        y[j] = (h16)fmaf(((float)t[j] - mean) * rstd, g0[j], b0[j]);
-                        y[4 + j] = (h16)fmaf(((float)t[4 + j] - mean) * rstd, g1[j], b1[j]);
-                    }
-                    xr[ks] = __builtin_bit_cast(u32x4, y);
+                    xr[ks] = __builtin_bit_cast(u32x4, row_norm(xr[ks], ks, half, mean, rstd, vec, vec + RC));
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
@@ -512,22 +496,15 @@ __global__ __launch_bounds__(256, 3) void rowlin_kernel(const RLParams p, const 
 #pragma unroll
             for (int ph = 0; ph < 2; ++ph) {
                 asm volatile("" ::: "memory");       // pass 1 overwrites the slab pass 0 is read from
-                if ((l31 >> 4) == ph) {
+                if ((l31 >> 4) == ph) {      // (a loop over the pair: as two calls, hipcc assigns this kernel's registers differently)
 #pragma unroll
-                    for (int bb = 0; bb < 2; ++bb)
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) {
-                            h16x4 pk;
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) pk[e] = (h16)(bb ? a1[4 * q + e] : a0[4 * q + e]);
-                            *reinterpret_cast<u32x2*>(slab + (l31 & 15) * 144 + (bb * 32 + 8 * q + 4 * half) * 2) = __builtin_bit_cast(u32x2, pk);
-                        }
+                    for (int bb = 0; bb < 2; ++bb) slab_put(slab + (l31 & 15) * SLABP, bb, half, bb ? a1 : a0);
                 }
 #pragma unroll
                 for (int it = 0; it < 2; ++it) {
                     const int idx = lane + it * 64, r = idx >> 3, c = idx & 7, row = m0 + 16 * ph + r;
-                    const unsigned go = row < p.M ? ((unsigned)row * (unsigned)p.N + (unsigned)col0) * 2u + (unsigned)c * 16u : OOB;
-                    const u32x4 t = *reinterpret_cast<const u32x4*>(slab + r * 144 + c * 16);
+                    const unsigned go = row < p.M ? ((unsigned)row * (unsigned)p.N + (unsigned)col0) * 2u + (unsigned)c * 16u : BUF_OOB;
+                    const u32x4 t = *reinterpret_cast<const u32x4*>(slab + r * SLABP + c * 16);
                     if (!(DBG & 1) || t[0] == 0x12345u) __builtin_amdgcn_raw_buffer_store_b128(t, rO, (int)go, 0, 0);
                 }
             }
@@ -540,6 +517,13 @@ __global__ __launch_bounds__(256, 3) void rowlin_kernel(const RLParams p, const 
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+
+// The launch of either row-resident kernel: 128-row tiles, dealt to a persistent grid of at most wpc workgroups per CU
+template <auto Kern, typename P>
+int launch_rows(const P& p, int wpc, int lds, hipStream_t s) {
+    const int ntiles = (p.M + 127) / 128, cap = wpc * cu_count();
+    return launch_lds<Kern>(dim3(ntiles < cap ? ntiles : cap), dim3(256), lds, s, p, ntiles);
 }
 
 }  // namespace
@@ -574,21 +558,16 @@ int launch_ff_fused(const FFArgs& a, hipStream_t s) {
     // The four waves of a workgroup leave every ring barrier together and issue their DMA pieces and fragment reads at the same
     // instants; de-phased by one 8-wait-state unit per wave index the kernel runs 1.7 % faster (interleaved-round sweep in
     // profiles/r03_ff_fused_ablation.txt: 0 -> 1.208, 1 -> 1.187, 2 -> 1.218, 3 -> 1.246 ms).
-    p.stagger = 1;
+    p.stagger = g_ff_stagger >= 0 ? g_ff_stagger : 1;
 #ifdef DSIM_DEVTOOLS
-    if (g_ff_stagger >= 0) p.stagger = g_ff_stagger;
-#endif
-    const int ntiles = (a.M + 127) / 128;
-    const int grid = ntiles < cu_count() ? ntiles : cu_count();
-#ifdef DSIM_DEVTOOLS
-    switch (g_ff_dbg) {
-#define X(d) case d: return launch_lds<ff_fused_kernel<d>>(dim3(grid), dim3(256), RLDS, s, p, ntiles);
+    switch (g_ff_dbg) {             // tools/kbench: the ablation variant, if it is one of those compiled in
+#define X(d) case d: return launch_rows<ff_fused_kernel<d>>(p, 1, RLDS, s);
         X(1) X(2) X(3) X(12) X(13) X(15) X(16) X(31)
 #undef X
         default: break;
     }
 #endif
-    return launch_lds<ff_fused_kernel<0>>(dim3(grid), dim3(256), RLDS, s, p, ntiles);
+    return launch_rows<ff_fused_kernel<0>>(p, 1, RLDS, s);
 }
 
 size_t rowlin_stream_bytes(int C, int N) { return (C == RC && N % 64 == 0 && N <= 960) ? (size_t)N / 32 * LCHB : 0; }
@@ -609,22 +588,15 @@ int launch_rowlin(const RowLinArgs& a, hipStream_t s) {
     p.M = a.M; p.N = a.N; p.eps = a.eps;
     p.x_bytes = (unsigned)((size_t)a.M * RC * 2); p.out_bytes = (unsigned)((size_t)a.M * a.N * 2);
     p.stream_bytes = (unsigned)rowlin_stream_bytes(a.C, a.N);
-    const int ntiles = (a.M + 127) / 128;
-#ifdef DSIM_DEVTOOLS
-    const int wpc = g_rl_wpc;        // kbench occupancy probe: workgroups per CU
-#else
-    constexpr int wpc = 3;
-#endif
-    const int grid = ntiles < wpc * cu_count() ? ntiles : wpc * cu_count();
 #ifdef DSIM_DEVTOOLS
     switch (g_rl_dbg) {
-#define X(d) case d: return launch_lds<rowlin_kernel<d>>(dim3(grid), dim3(256), LLDS, s, p, ntiles);
+#define X(d) case d: return launch_rows<rowlin_kernel<d>>(p, g_rl_wpc, LLDS, s);
         X(1) X(2) X(4) X(8) X(10) X(15)
 #undef X
         default: break;
     }
 #endif
-    return launch_lds<rowlin_kernel<0>>(dim3(grid), dim3(256), LLDS, s, p, ntiles);
+    return launch_rows<rowlin_kernel<0>>(p, g_rl_wpc, LLDS, s);
 }
 }  // namespace DSIM_H16_NS
 
