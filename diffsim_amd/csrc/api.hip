@@ -390,7 +390,7 @@ int dsim_op_attention_ex(const void* q, int ldq, const void* k, const void* v, i
         const AttnLaunchRec& r = g_attn_last_launch;
         launched->kind = r.kind; launched->D = r.D; launched->dtype = r.dtype; launched->k80 = r.k80; launched->qit = r.qit;
         launched->grid = r.grid;
-        const char* dtn = r.dtype == DSIM_F32 ? "f32" : (r.dtype == DSIM_F16 ? "f16" : "bf16");
+        const char* dtn = dtype_name(r.dtype);
         if (r.kind == DSIM_ATTN_FP8) std::snprintf(launched->family, sizeof(launched->family), "attention_fp8_d%d", r.D);
         else std::snprintf(launched->family, sizeof(launched->family), "attention_%s_d%d%s", dtn, r.D, attn_kind_suffix(r.kind));
     }

@@ -95,6 +95,20 @@ __device__ __forceinline__ __attribute__((const)) __amdgpu_buffer_rsrc_t buf_rsr
     } while (0)
 
 static inline size_t dtype_size(int dt) { return dt == DSIM_F32 ? 4 : 2; }
+static inline const char* dtype_name(int dt) { return dt == DSIM_F32 ? "f32" : (dt == DSIM_F16 ? "f16" : "bf16"); }
+
+// f(Elem<T>{}) for the element type T of `dtype`: the one switch from a run-time compute dtype to the kernels' template parameter
+// (inside f: typename decltype(e)::type).  DSIM_ERR_INVALID for anything else.
+template <typename T> struct Elem { typedef T type; };
+template <typename F>
+int by_dtype(int dtype, F&& f) {
+    switch (dtype) {
+        case DSIM_BF16: return f(Elem<bf16_t>{});
+        case DSIM_F16: return f(Elem<f16_t>{});
+        case DSIM_F32: return f(Elem<float>{});
+    }
+    return DSIM_ERR_INVALID;
+}
 
 // ---------------------------------------------------------------------------------------------
 // implicit-GEMM (linear / 1x1 conv / 3x3 conv) -- gemm.hip

@@ -89,7 +89,7 @@ struct DTap {
 };
 
 struct DWalk : WalkBase<dsim_dit> {
-    int n;                  // images
+    const int n;            // images
     std::vector<DTap> taps; // captured on the way; the walk ends at the deepest
     bool tapped = false;
     DWalk(dsim_dit* h, Arena* ar, hipStream_t s, int n, bool run) : WalkBase(h, ar, s, run), n(n) {}
@@ -98,18 +98,15 @@ struct DWalk : WalkBase<dsim_dit> {
 
     int linear(const void* a, int K, const void* w, const float* bias, void* out, int M, int N, int act, const float* gate,
                const void* residual, int T) {
-        GemmArgs g;
-        g.A0 = a; g.C0 = K; g.mode = GEMM_LINEAR; g.M = M; g.N = N; g.K = K; g.W = w; g.bias = bias; g.act = act;
+        GemmArgs g = linear_args(a, K, w, bias, residual, out, M, N);
+        g.act = act;
         if (gate) { g.gate = gate; g.gate2 = gate + h->cfg.hidden_size; g.rows_per_batch = T; }
-        g.epi = residual ? EPI_RESIDUAL : EPI_NONE; g.residual = residual; g.out = out; g.ldo = N;
         return gemm(g);
     }
     int lnmod(const void* x, const float* scale2, const float* shift2, void* out, int M, int D, int T) {
-        if (!run) return DSIM_OK;
-        pbegin(std::string("layernorm_mod_") + dtn() + "|M" + std::to_string(M) + " C" + std::to_string(D), 0.0, 2.0 * M * (double)D * es());
-        const int st = launch_layernorm_mod(x, scale2, shift2, out, M, D, T, 1e-6f, h->dt, s);
-        pend();
-        return st;
+        return launch([&] { return rec(std::string("layernorm_mod_") + dtn() + "|M" + std::to_string(M) + " C" + std::to_string(D), 0.0,
+                                       2.0 * M * (double)D * es()); },
+                      [&] { return launch_layernorm_mod(x, scale2, shift2, out, M, D, T, 1e-6f, h->dt, s); });
     }
 
     int go(const float* lat, const float* noise, float sa, float sb) {
@@ -118,20 +115,16 @@ struct DWalk : WalkBase<dsim_dit> {
         const int M = n * 2 * T, F = c.mlp_ratio * D;
         WGET(pw, "x_embedder.proj.weight"); WGET(pb, "x_embedder.proj.bias"); WGET(pos, "pos_embed");
         void* x = alloc_act((size_t)M * D);
-        if (run) {
-            const int K = c.in_channels * p * p;
-            const dim3 grid((T + PE_TOK - 1) / PE_TOK, n);
-            if (h->dt == DSIM_BF16)
-                hipLaunchKernelGGL(patch_embed_kernel<bf16_t>, grid, dim3(256), PE_TOK * K * sizeof(float), s, lat, noise, sa, sb,
-                                   (const float*)pw->p, (const float*)pb->p, (const float*)pos->p, (bf16_t*)x, c.in_channels, S, p, D);
-            else if (h->dt == DSIM_F16)
-                hipLaunchKernelGGL(patch_embed_kernel<f16_t>, grid, dim3(256), PE_TOK * K * sizeof(float), s, lat, noise, sa, sb,
-                                   (const float*)pw->p, (const float*)pb->p, (const float*)pos->p, (f16_t*)x, c.in_channels, S, p, D);
-            else
-                hipLaunchKernelGGL(patch_embed_kernel<float>, grid, dim3(256), PE_TOK * K * sizeof(float), s, lat, noise, sa, sb,
-                                   (const float*)pw->p, (const float*)pb->p, (const float*)pos->p, (float*)x, c.in_channels, S, p, D);
-            DSIM_HIP_CHECK(hipGetLastError());
-        }
+        CK(launch([&] {
+            return by_dtype(h->dt, [&](auto e) {
+                typedef typename decltype(e)::type T_;
+                const int K = c.in_channels * p * p;
+                hipLaunchKernelGGL(patch_embed_kernel<T_>, dim3((T + PE_TOK - 1) / PE_TOK, n), dim3(256), PE_TOK * K * sizeof(float), s, lat,
+                                   noise, sa, sb, (const float*)pw->p, (const float*)pb->p, (const float*)pos->p, (T_*)x, c.in_channels, S, p, D);
+                DSIM_HIP_CHECK(hipGetLastError());
+                return DSIM_OK;
+            });
+        }));
         void* nb = alloc_act((size_t)M * D);
         void* big = alloc_act((size_t)M * (F > 3 * D ? F : 3 * D));
         void* ab = alloc_act((size_t)M * D);
@@ -158,16 +151,12 @@ struct DWalk : WalkBase<dsim_dit> {
             WGET(f1w, b + "mlp.fc1.weight"); WGET(f1b, b + "mlp.fc1.bias");
             WGET(f2w, b + "mlp.fc2.weight"); WGET(f2b, b + "mlp.fc2.bias");
             CK(linear(nb, D, qw->p, (const float*)qb->p, big, M, 3 * D, 0, nullptr, nullptr, T));
-            if (run) {
-                AttnArgs a;
-                a.q = big; a.ldq = 3 * D;
-                a.k = (char*)big + (size_t)D * es(); a.v = (char*)big + (size_t)2 * D * es(); a.ldk = 3 * D;
-                a.out = ab; a.ldo = D; a.B = n * 2; a.Bkv = n * 2; a.H = H; a.Nq = T; a.Nk = T; a.D = D / H;
-                pbegin_attn(a, h->attn_mode == 1);
-                const int st = h->attn_mode == 1 ? launch_attention_fp8(a, s) : launch_attention(a, h->dt, s);
-                pend();
-                CK(st);
-            }
+            AttnArgs a;
+            a.q = big; a.ldq = 3 * D;
+            a.k = (char*)big + (size_t)D * es(); a.v = (char*)big + (size_t)2 * D * es(); a.ldk = 3 * D;
+            a.out = ab; a.ldo = D; a.B = n * 2; a.Bkv = n * 2; a.H = H; a.Nq = T; a.Nk = T; a.D = D / H;
+            const bool fp8 = h->attn_mode == 1;
+            CK(launch([&] { return attn_rec(a, fp8); }, [&] { return fp8 ? launch_attention_fp8(a, s) : launch_attention(a, h->dt, s); }));
             CK(linear(ab, D, ow->p, (const float*)ob->p, x, M, D, 0, modv(blk, 2), x, T));
             CK(lnmod(x, modv(blk, 4), modv(blk, 3), nb, M, D, T));
             CK(linear(nb, D, f1w->p, (const float*)f1b->p, big, M, F, 1, nullptr, nullptr, T));

@@ -605,18 +605,6 @@ int launch(void (*kern)(P...), dim3 grid, size_t lds, hipStream_t s, A... args) 
     return DSIM_OK;
 }
 
-// f(Elem<T>{}) for the element type of `dtype`
-template <typename T> struct Elem { typedef T type; };
-template <typename F>
-int by_dtype(int dtype, F&& f) {
-    switch (dtype) {
-        case DSIM_BF16: return f(Elem<bf16_t>{});
-        case DSIM_F16: return f(Elem<f16_t>{});
-        case DSIM_F32: return f(Elem<float>{});
-    }
-    return DSIM_ERR_INVALID;
-}
-
 // The compiled kernels, each instantiation named once; the plans choose a row and the launchers start that row, so a plan
 // outside a table is DSIM_ERR_INVALID.  [2]: without / with SiLU (GroupNorm), affine / modulated (LayerNorm).
 template <typename T> struct GnTwoPass {

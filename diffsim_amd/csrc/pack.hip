@@ -424,19 +424,17 @@ int conv_in_rows(const float* images, const float* w, const float* bias, void* o
     int nseg = 8;                                         // 64-pixel segments of an image row one workgroup walks (weights loaded once)
     while ((S / 64) % nseg) nseg >>= 1;
     const dim3 grid(S / 64 / nseg, S, n_img);
-    if (dtype == DSIM_BF16) {
-        if (gn_part) hipLaunchKernelGGL((conv_in_rows_kernel<bf16_t, true>), grid, dim3(256), 0, st, images, w, bias, (bf16_t*)out, S, nseg, gn_part);
-        else hipLaunchKernelGGL((conv_in_rows_kernel<bf16_t, false>), grid, dim3(256), 0, st, images, w, bias, (bf16_t*)out, S, nseg, gn_part);
-    } else if (dtype == DSIM_F16) {
-        if (gn_part) hipLaunchKernelGGL((conv_in_rows_kernel<f16_t, true>), grid, dim3(256), 0, st, images, w, bias, (f16_t*)out, S, nseg, gn_part);
-        else hipLaunchKernelGGL((conv_in_rows_kernel<f16_t, false>), grid, dim3(256), 0, st, images, w, bias, (f16_t*)out, S, nseg, gn_part);
-    } else if (dtype == DSIM_F32) {
-        hipLaunchKernelGGL((conv_in_rows_kernel<float, false>), grid, dim3(256), 0, st, images, w, bias, (float*)out, S, nseg, gn_part);
-    } else {
-        return DSIM_ERR_INVALID;
-    }
-    DSIM_HIP_CHECK(hipGetLastError());
-    return DSIM_OK;
+    return by_dtype(dtype, [&](auto e) {
+        typedef typename decltype(e)::type T;
+        if (gn_part) {
+            if constexpr (sizeof(T) == 2)
+                hipLaunchKernelGGL((conv_in_rows_kernel<T, true>), grid, dim3(256), 0, st, images, w, bias, (T*)out, S, nseg, gn_part);
+        } else {
+            hipLaunchKernelGGL((conv_in_rows_kernel<T, false>), grid, dim3(256), 0, st, images, w, bias, (T*)out, S, nseg, gn_part);
+        }
+        DSIM_HIP_CHECK(hipGetLastError());
+        return DSIM_OK;
+    });
 }
 int prep_conv_in(const float* lat, const float* noise, float sa, float sb, const float* w, const float* bias, void* out,
                  int dtype, int n_img, int Cin, int S, int Cout, int dup, hipStream_t st) {
@@ -445,31 +443,23 @@ int prep_conv_in(const float* lat, const float* noise, float sa, float sb, const
         const int PIX = (256 / (Cout / 8)) * PP;
         const dim3 grid8((S * S + PIX - 1) / PIX, n_img);
         const size_t lds8 = (size_t)PIX * 9 * Cin * sizeof(float);
-        if (lds8 <= 48 * 1024) {
-            if (dtype == DSIM_BF16)
-                hipLaunchKernelGGL((prep_conv_in8_kernel<bf16_t, PP>), grid8, dim3(256), lds8, st, lat, noise, sa, sb, w, bias, (bf16_t*)out, Cin, S, Cout, dup);
-            else if (dtype == DSIM_F16)
-                hipLaunchKernelGGL((prep_conv_in8_kernel<f16_t, PP>), grid8, dim3(256), lds8, st, lat, noise, sa, sb, w, bias, (f16_t*)out, Cin, S, Cout, dup);
-            else if (dtype == DSIM_F32)
-                hipLaunchKernelGGL((prep_conv_in8_kernel<float, PP>), grid8, dim3(256), lds8, st, lat, noise, sa, sb, w, bias, (float*)out, Cin, S, Cout, dup);
-            else
-                return DSIM_ERR_INVALID;
-            DSIM_HIP_CHECK(hipGetLastError());
-            return DSIM_OK;
-        }
+        if (lds8 <= 48 * 1024)
+            return by_dtype(dtype, [&](auto e) {
+                typedef typename decltype(e)::type T;
+                hipLaunchKernelGGL((prep_conv_in8_kernel<T, PP>), grid8, dim3(256), lds8, st, lat, noise, sa, sb, w, bias, (T*)out, Cin, S, Cout,
+                                   dup);
+                DSIM_HIP_CHECK(hipGetLastError());
+                return DSIM_OK;
+            });
     }
     const dim3 grid((S * S + PREP_PIX - 1) / PREP_PIX, n_img), block(256);
     const size_t lds = (size_t)PREP_PIX * 9 * Cin * sizeof(float);
-    if (dtype == DSIM_BF16)
-        hipLaunchKernelGGL(prep_conv_in_kernel<bf16_t>, grid, block, lds, st, lat, noise, sa, sb, w, bias, (bf16_t*)out, Cin, S, Cout, dup);
-    else if (dtype == DSIM_F16)
-        hipLaunchKernelGGL(prep_conv_in_kernel<f16_t>, grid, block, lds, st, lat, noise, sa, sb, w, bias, (f16_t*)out, Cin, S, Cout, dup);
-    else if (dtype == DSIM_F32)
-        hipLaunchKernelGGL(prep_conv_in_kernel<float>, grid, block, lds, st, lat, noise, sa, sb, w, bias, (float*)out, Cin, S, Cout, dup);
-    else
-        return DSIM_ERR_INVALID;
-    DSIM_HIP_CHECK(hipGetLastError());
-    return DSIM_OK;
+    return by_dtype(dtype, [&](auto e) {
+        typedef typename decltype(e)::type T;
+        hipLaunchKernelGGL(prep_conv_in_kernel<T>, grid, block, lds, st, lat, noise, sa, sb, w, bias, (T*)out, Cin, S, Cout, dup);
+        DSIM_HIP_CHECK(hipGetLastError());
+        return DSIM_OK;
+    });
 }
 // out[(b * 2 + c)][i] = in[b][i] for c in {0, 1}: one batch element of `per` 16-byte chunks becomes its two CFG copies
 __global__ void dup_batch_kernel(const u32x4* __restrict__ in, u32x4* __restrict__ out, size_t per, size_t total) {

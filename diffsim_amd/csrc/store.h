@@ -1,6 +1,10 @@
 // Shared host-side plumbing of the executors (U-Net, VAE, DiT): borrowed raw parameters, packed device copies, the
 // caller-provided workspace arena, the per-launch profiling record, the handle life cycle behind each dsim_<executor>_create /
 // destroy / load_weight / profile* group (handle_create ... prof_get) and the base of the three graph walks (WalkBase).
+// WalkBase holds what every step of a walk is made of: launch() -- the one bracket around a kernel launch (nothing on a dry walk, a
+// profile record around it on a profiled one, the launch's status) --, the records of the launch kinds the walks share (gemm,
+// attention, GroupNorm), and the two GemmArgs builders (linear_args, conv3_args) each walk's linear / conv3 starts from.  An
+// activation (Act) carries its own batch count: no step reads how many batch elements it works on from anywhere else.
 #pragma once
 #include <cstring>
 #include <map>
@@ -31,7 +35,12 @@ struct Arena {
     void release(size_t m) { off = m; }
 };
 
-struct Act { void* p = nullptr; int C = 0, H = 0, W = 0; };
+// a token-major activation [B][H * W][C] in the compute dtype
+struct Act {
+    void* p = nullptr;
+    int C = 0, H = 0, W = 0, B = 0;
+    int rows() const { return B * H * W; }
+};
 
 // per-launch record of a profiled forward (dsim_*_profile_*): kernel family, algorithmic work
 // and the HIP-event bracket on the launch stream
@@ -106,7 +115,7 @@ struct WeightStore {
 static inline std::string gemm_family(const GemmArgs& g, int dt, double* flops, double* bytes) {
     GemmLaunchRec p;
     const bool ok = gemm_plan(g, dt, &p) == DSIM_OK;
-    const char* dtn = dt == DSIM_F32 ? "f32" : (dt == DSIM_F16 ? "f16" : "bf16");
+    const char* dtn = dtype_name(dt);
     const double e = (double)dtype_size(dt);
     const double outc = g.epi == EPI_GEGLU ? g.N / 2 : g.N;
     *flops = 2.0 * g.M * (double)g.N * g.K;
@@ -120,10 +129,8 @@ static inline std::string gemm_family(const GemmArgs& g, int dt, double* flops, 
            (p.geglu ? "_geglu" : epi[p.ek]) + size;
 }
 
-// HIP-event bracket of one launch of a profiled forward (WalkBase::pbegin / pend)
-static inline void prof_begin(WeightStore* h, hipStream_t s, const std::string& name, double flops, double bytes) {
-    ProfRec r;
-    r.name = name; r.flops = flops; r.bytes = bytes;
+// HIP-event bracket of one launch of a profiled forward (WalkBase::launch); r: name and work of the launch
+static inline void prof_begin(WeightStore* h, hipStream_t s, ProfRec r) {
     (void)hipEventCreate(&r.e0);
     (void)hipEventCreate(&r.e1);
     (void)hipEventRecord(r.e0, s);
@@ -219,40 +226,77 @@ struct WalkBase {
         if (elems * es() > max_tensor) max_tensor = elems * es();
         return ar->alloc(elems * es());
     }
-    const char* dtn() const { return h->dt == DSIM_F32 ? "f32" : (h->dt == DSIM_F16 ? "f16" : "bf16"); }
+    Act act(int B, int Hh, int Ww, int C) { return Act{alloc_act((size_t)B * Hh * Ww * C), C, Hh, Ww, B}; }      // a new activation on the arena
+    const char* dtn() const { return dtype_name(h->dt); }
 
-    // ---- optional per-launch HIP-event brackets (profiled forward only) --------------------
-    void pbegin(const std::string& name, double flops, double bytes) { if (run && h->profiling) prof_begin(h, s, name, flops, bytes); }
-    void pend() { if (run && h->profiling) prof_end(h, s); }
+    // ---- the launch bracket: every kernel launch of a walk goes through one of these two ------------------------------------------
+    // rec() -> ProfRec{name, flops, bytes}, called on a profiled forward only (an unprofiled one builds no string); go() launches and
+    // returns the status.  Nothing on a dry walk.
+    template <class Rec, class Go>
+    int launch(Rec&& rec, Go&& go) {
+        if (!run) return DSIM_OK;
+        if (!h->profiling) return go();
+        prof_begin(h, s, rec());
+        const int st = go();
+        prof_end(h, s);
+        return st;
+    }
+    // a launch that has no profile record
+    template <class Go>
+    int launch(Go&& go) { return run ? go() : DSIM_OK; }
+
+    static ProfRec rec(std::string name, double flops, double bytes) {
+        ProfRec r;
+        r.name = std::move(name); r.flops = flops; r.bytes = bytes;
+        return r;
+    }
     // the record of an attention launch; fp8: the e4m3 kernel (attention_fp8.hip), its own family
-    void pbegin_attn(const AttnArgs& a, bool fp8 = false) {
-        if (!run || !h->profiling) return;
-        // (key sequences >= 2048 run the fixed-reference instantiation attn_kernel<T, D, true>: its own family)
-        pbegin((fp8 ? std::string("attention_fp8_d") + std::to_string(a.D)
-                    : std::string("attention_") + dtn() + "_d" + std::to_string(a.D) + attention_kernel_kind(a, h->dt)) +
-                   "|B" + std::to_string(a.B) + " H" + std::to_string(a.H) + " Nq" + std::to_string(a.Nq) + " Nk" + std::to_string(a.Nk),
-               4.0 * a.B * a.H * (double)a.Nq * a.Nk * a.D, (double)es() * a.B * a.H * a.D * (2.0 * a.Nq + 2.0 * a.Nk));
+    // (key sequences >= 2048 run the fixed-reference instantiation attn_kernel<T, D, true>: its own family)
+    ProfRec attn_rec(const AttnArgs& a, bool fp8 = false) const {
+        return rec((fp8 ? std::string("attention_fp8_d") + std::to_string(a.D)
+                        : std::string("attention_") + dtn() + "_d" + std::to_string(a.D) + attention_kernel_kind(a, h->dt)) +
+                       "|B" + std::to_string(a.B) + " H" + std::to_string(a.H) + " Nq" + std::to_string(a.Nq) + " Nk" + std::to_string(a.Nk),
+                   4.0 * a.B * a.H * (double)a.Nq * a.Nk * a.D, (double)es() * a.B * a.H * a.D * (2.0 * a.Nq + 2.0 * a.Nk));
     }
     // the record of a GroupNorm launch over B x HW x (C0 + C1); pre: statistics from the producing conv's epilogue (apply pass only)
-    void pbegin_gn(int B, int HW, int C0, int C1, int groups, bool pre = false) {
-        if (!run || !h->profiling) return;
+    ProfRec gn_rec(int B, int HW, int C0, int C1, int groups, bool pre = false) const {
         const double n = (double)B * HW * (C0 + C1);
-        pbegin(std::string(pre ? "groupnorm_pre_" : "groupnorm_") + dtn() + "|B" + std::to_string(B) + " HW" + std::to_string(HW) + " C" +
-                   std::to_string(C0 + C1), 0.0,
-               (pre ? 2.0 : (double)groupnorm_passes(C0, C1, HW, groups, h->dt)) * n * es());
+        return rec(std::string(pre ? "groupnorm_pre_" : "groupnorm_") + dtn() + "|B" + std::to_string(B) + " HW" + std::to_string(HW) + " C" +
+                       std::to_string(C0 + C1), 0.0,
+                   (pre ? 2.0 : (double)groupnorm_passes(C0, C1, HW, groups, h->dt)) * n * es());
     }
 
     int gemm(GemmArgs& g) {
         g.zero_page = h->zero_page;
-        if (!run) return DSIM_OK;
-        if (h->profiling) {
-            double fl, by;
-            const std::string nm = gemm_family(g, h->dt, &fl, &by);
-            pbegin(nm, fl, by);
-        }
-        const int st = launch_gemm(g, h->dt, s);
-        pend();
-        return st;
+        return launch(
+            [&] {
+                ProfRec r;
+                r.name = gemm_family(g, h->dt, &r.flops, &r.bytes);
+                return r;
+            },
+            [&] { return launch_gemm(g, h->dt, s); });
+    }
+
+    // ---- GemmArgs, one builder per kind: a walk's linear / conv3 starts from these and sets only what is its own ------------------
+    // out[M][N] = a[M][K] w[N][K]^T + bias (+ residual), rows of N
+    static GemmArgs linear_args(const void* a, int K, const void* w, const float* bias, const void* residual, void* out, int M, int N) {
+        GemmArgs g;
+        g.A0 = a; g.C0 = K; g.mode = GEMM_LINEAR; g.M = M; g.N = N; g.K = K; g.W = w; g.bias = bias;
+        g.epi = residual ? EPI_RESIDUAL : EPI_NONE; g.residual = residual; g.out = out; g.ldo = N;
+        return g;
+    }
+    // 3x3 conv of x to Cout channels.  Output side: twice the input's behind the folded nearest-2x upsample; at stride 2, padding 1
+    // (the U-Net's downsamplers) (H - 1) / 2 + 1 = ceil(H / 2) rows (odd sides: --image_size 224 -> 28 -> 14 -> 7 -> 4), with the
+    // VAE's right / bottom padding only (pad = 0) H / 2
+    static GemmArgs conv3_args(const Act& x, const void* w, const float* bias, const void* residual, void* out, int Cout, int stride,
+                               int ups, int pad) {
+        const auto side = [&](int n) { return ups ? 2 * n : stride == 2 ? (pad ? (n + 1) / 2 : n / 2) : n; };
+        GemmArgs g;
+        g.A0 = x.p; g.C0 = x.C; g.mode = GEMM_CONV3; g.Hin = x.H; g.Win = x.W; g.Hout = side(x.H); g.Wout = side(x.W);
+        g.stride = stride; g.ups = ups; g.pad = pad;
+        g.M = x.B * g.Hout * g.Wout; g.N = Cout; g.K = 9 * x.C; g.W = w; g.bias = bias;
+        g.epi = residual ? EPI_RESIDUAL : EPI_NONE; g.residual = residual; g.out = out; g.ldo = Cout;
+        return g;
     }
 };
 

@@ -43,15 +43,30 @@ struct TapReq {
 };
 
 // the handle's own tap as a one-tap request
-static std::vector<TapReq> cfg_taps(const dsim_unet_cfg& c, void* q = nullptr, void* k = nullptr, void* v = nullptr) {
-    TapReq t{c.tap_block, c.tap_layer, c.tap_attn, c.tap_tfm};
-    t.q = q; t.k = k; t.v = v;
-    return {t};
-}
+static std::vector<TapReq> cfg_taps(const dsim_unet_cfg& c) { return {TapReq{c.tap_block, c.tap_layer, c.tap_attn, c.tap_tfm}}; }
 
 // ---- the walk ----------------------------------------------------------------------------
+// The rows a step of a transformer block works on: the residual stream, the attention output (which then holds the cross-attention
+// query) and their batch elements.
+struct Rows {
+    void* h = nullptr;
+    void* a = nullptr;
+    int B = 0;
+};
+// One Transformer2DModel under way: its geometry and the buffers its blocks share.  `full` is the whole batch; `half` exists under
+// CFG de-duplication only (one row set per image: the first block runs on it up to its cross-attention query, then the halves part).
+struct Tfm {
+    int C = 0, HW = 0, heads = 0;
+    Rows full, half;
+    const void* x = nullptr;    // the model's input, the residual of proj_out (de-duplicated: one copy per image ...
+    void* xfull = nullptr;      //   ... and its [image][cfg] copy, written where the halves part)
+    void* nb = nullptr;         // LayerNorm outputs
+    void* big = nullptr;        // qkv [M][3C], the cross-attention output, the GEGLU output [M][4C]
+    void* kvb = nullptr;        // the prompt context's K | V
+};
+
 struct Walk : WalkBase<dsim_unet> {
-    int B2;                 // U-Net batch = 2 * images (CFG)
+    const int B2;           // U-Net batch of the call = 2 * images (CFG); a step's own batch is its input's (Act.B)
     void* gn_scratch = nullptr;
     void* ctx_t = nullptr;  // [2][L][Dc] compute dtype; with a context table, [B2][L][Dc] (one context per batch element)
     std::vector<TapReq> taps;   // where q, k, v are captured; the walk ends at the deepest of them
@@ -65,73 +80,64 @@ struct Walk : WalkBase<dsim_unet> {
 
     int linear(const void* a0, int c0, const void* a1, int c1, const Packed* w, const Packed* b, const void* residual,
                void* out, int M, int N, int ldo, int epi = -1) {
-        GemmArgs g;
-        g.A0 = a0; g.C0 = c0; g.A1 = a1; g.C1 = a1 ? c1 : 0;
-        g.mode = GEMM_LINEAR;
-        g.M = M; g.N = N; g.K = c0 + (a1 ? c1 : 0);
-        g.W = w->p; g.bias = b ? (const float*)b->p : nullptr;
-        g.epi = epi >= 0 ? epi : (residual ? EPI_RESIDUAL : EPI_NONE);
+        GemmArgs g = linear_args(a0, c0, w->p, b ? (const float*)b->p : nullptr, residual, out, M, N);
+        if (a1) { g.A1 = a1; g.C1 = c1; g.K = c0 + c1; }
+        g.ldo = ldo;
+        if (epi >= 0) g.epi = epi;
         if (g.epi == EPI_GEGLU) g.geglu_blk = geglu_block_rows(N);       // as pack_all() interleaved it
-        g.residual = residual; g.out = out; g.ldo = ldo;
         return gemm(g);
     }
     int conv3(const Act& x, const Packed* w, const float* bias, const void* residual, void* out, int Cout, int stride,
               int ups, const float* bias_odd = nullptr) {
-        GemmArgs g;
-        if (h->two_temb && bias_odd) {
-            g.bias2 = bias_odd;
-            g.rows_per_batch = ups ? 4 * x.H * x.W : (stride == 2 ? ((x.H + 1) / 2) * ((x.W + 1) / 2) : x.H * x.W);
-        }
-        g.A0 = x.p; g.C0 = x.C; g.mode = GEMM_CONV3;
-        g.Hin = x.H; g.Win = x.W;
-        // stride 2, padding 1, kernel 3: (H - 1) / 2 + 1 rows, i.e. ceil(H / 2) (odd sides: --image_size 224 -> 28 -> 14 -> 7 -> 4)
-        g.Hout = ups ? x.H * 2 : (stride == 2 ? (x.H + 1) / 2 : x.H);
-        g.Wout = ups ? x.W * 2 : (stride == 2 ? (x.W + 1) / 2 : x.W);
-        g.stride = stride; g.ups = ups;
-        g.M = B2 * g.Hout * g.Wout; g.N = Cout; g.K = 9 * x.C;
-        g.W = w->p; g.bias = bias;
-        g.epi = residual ? EPI_RESIDUAL : EPI_NONE;
-        g.residual = residual; g.out = out; g.ldo = Cout;
+        GemmArgs g = conv3_args(x, w->p, bias, residual, out, Cout, stride, ups, 1);
+        if (h->two_temb && bias_odd) { g.bias2 = bias_odd; g.rows_per_batch = g.Hout * g.Wout; }
         return gemm(g);
     }
     int gn(const Act& x0, const Act* x1, const Packed* g, const Packed* b, void* out, float eps, int silu) {
-        if (!run) return DSIM_OK;
-        pbegin_gn(B2, x0.H * x0.W, x0.C, x1 ? x1->C : 0, h->cfg.norm_num_groups);
-        const int st = launch_groupnorm(x0.p, x0.C, x1 ? x1->p : nullptr, x1 ? x1->C : 0, (const float*)g->p,
-                                        (const float*)b->p, out, B2, x0.H * x0.W, h->cfg.norm_num_groups, eps, silu,
-                                        h->dt, gn_scratch, s);
-        pend();
-        return st;
+        const int HW = x0.H * x0.W, C1 = x1 ? x1->C : 0, groups = h->cfg.norm_num_groups;
+        return launch([&] { return gn_rec(x0.B, HW, x0.C, C1, groups); },
+                      [&] {
+                          return launch_groupnorm(x0.p, x0.C, x1 ? x1->p : nullptr, C1, (const float*)g->p, (const float*)b->p, out, x0.B, HW,
+                                                  groups, eps, silu, h->dt, gn_scratch, s);
+                      });
     }
     int ln(const void* x, const Packed* g, const Packed* b, void* out, int M, int C) {
-        if (!run) return DSIM_OK;
-        pbegin(std::string("layernorm_") + dtn() + "|M" + std::to_string(M) + " C" + std::to_string(C), 0.0, 2.0 * M * (double)C * es());
-        const int st = launch_layernorm(x, (const float*)g->p, (const float*)b->p, out, M, C, 1e-5f, h->dt, s);
-        pend();
-        return st;
+        return launch([&] { return rec(std::string("layernorm_") + dtn() + "|M" + std::to_string(M) + " C" + std::to_string(C), 0.0,
+                                       2.0 * M * (double)C * es()); },
+                      [&] { return launch_layernorm(x, (const float*)g->p, (const float*)b->p, out, M, C, 1e-5f, h->dt, s); });
     }
     int attn(const AttnArgs& a) {
-        if (!run) return DSIM_OK;
-        pbegin_attn(a);
-        const int st = launch_attention(a, h->dt, s);
-        pend();
-        return st;
+        return launch([&] { return attn_rec(a); }, [&] { return launch_attention(a, h->dt, s); });
+    }
+    // LayerNorm + projection as one row-resident launch where the width has one (16-bit modes, C = 320).  Returns 1 where it has
+    // none: the caller runs the unfused chain.
+    int ln_proj(const void* x, const Packed* g, const Packed* b, const std::string& key, void* out, int M, int C, int N) {
+        const auto it = h->pk.find(key);
+        if (it == h->pk.end() || !(h->fusion & DSIM_FUSE_LNPROJ)) return 1;
+        return launch([&] { return rec(std::string("ln_linear_") + dtn() + "|M" + std::to_string(M) + " N" + std::to_string(N) + " K" +
+                                           std::to_string(C), 2.0 * M * (double)C * N, (double)M * (C + N) * es() + (double)C * N * es()); },
+                      [&] {
+                          RowLinArgs ra;
+                          ra.x = x; ra.out = out; ra.ln_g = (const float*)g->p; ra.ln_b = (const float*)b->p; ra.stream = it->second.p;
+                          ra.M = M; ra.C = C; ra.N = N; ra.eps = 1e-5f; ra.dtype = h->dt;
+                          return launch_rowlin(ra, s);
+                      });
     }
 
     // ResnetBlock2D; x1 = skip tensor concatenated after x0 on channels
     int resnet(const std::string& p, const Act& x0, const Act* x1, int Cout, Act* out) {
-        const int Cin = x0.C + (x1 ? x1->C : 0), HW = x0.H * x0.W, M = B2 * HW;
+        const int Cin = x0.C + (x1 ? x1->C : 0), B = x0.B, H = x0.H, W = x0.W, M = x0.rows();
         WGET(n1w, p + "norm1.weight"); WGET(n1b, p + "norm1.bias");
         WGET(c1w, p + "conv1.weight"); WGET(c1b, p + "conv1.bias_eff"); WGET(c1b2, p + "conv1.bias_eff2");
         WGET(n2w, p + "norm2.weight"); WGET(n2b, p + "norm2.bias");
         WGET(c2w, p + "conv2.weight"); WGET(c2b, p + "conv2.bias");
-        out->p = alloc_act((size_t)M * Cout); out->C = Cout; out->H = x0.H; out->W = x0.W;
+        *out = act(B, H, W, Cout);
         const size_t mk = ar->mark();
-        Act t1{alloc_act((size_t)M * Cin), Cin, x0.H, x0.W};
+        const Act t1 = act(B, H, W, Cin);
         CK(gn(x0, x1, n1w, n1b, t1.p, h->cfg.norm_eps, 1));
-        Act t2{alloc_act((size_t)M * Cout), Cout, x0.H, x0.W};
+        const Act t2 = act(B, H, W, Cout);
         CK(conv3(t1, c1w, (const float*)c1b->p, nullptr, t2.p, Cout, 1, 0, (const float*)c1b2->p));
-        Act t3{alloc_act((size_t)M * Cout), Cout, x0.H, x0.W};
+        const Act t3 = act(B, H, W, Cout);
         CK(gn(t2, nullptr, n2w, n2b, t3.p, h->cfg.norm_eps, 1));
         const void* res = x0.p;
         if (Cin != Cout) {
@@ -171,9 +177,8 @@ struct Walk : WalkBase<dsim_unet> {
         const long long qk = (const char*)t.k - (const char*)t.q, kv = (const char*)t.v - (const char*)t.k;
         const bool bm_split = C % 320 == 0;
         if ((h->fusion & DSIM_FUSE_TAPQKV) && qk == kv && qk >= (long long)M * C * (long long)es() && 3 * qk < 0x7fffffffll && bm_split) {
-            GemmArgs g;
-            g.A0 = nb; g.C0 = C; g.mode = GEMM_LINEAR; g.M = M; g.N = 3 * C; g.K = C;
-            g.W = qkv->p; g.epi = EPI_NONE; g.out = t.q; g.ldo = C; g.out_split = C; g.out_split_stride = qk;
+            GemmArgs g = linear_args(nb, C, qkv->p, nullptr, nullptr, t.q, M, 3 * C);
+            g.ldo = C; g.out_split = C; g.out_split_stride = qk;
             return gemm(g);
         }
         CK(linear(nb, C, nullptr, 0, &wq, nullptr, nullptr, t.q, M, C, C));
@@ -181,18 +186,110 @@ struct Walk : WalkBase<dsim_unet> {
         return linear(nb, C, nullptr, 0, &wv, nullptr, nullptr, t.v, M, C, C);
     }
 
+    // ---- BasicTransformerBlock `b` of the model t, in its three parts (hacked_modules.py:17-136) ------------------------------------
+    // Self-attention on the rows r.  here: the taps of this block (indices into `taps`).  At a tapped block, norm1 and the q/k/v
+    // projection run as a walk that stops there runs them; `last`: the walk holds every tap after this block's -- it ends here
+    // (tapped = true), and the caller unwinds.
+    int self_attention(const std::string& b, const Tfm& t, const Rows& r, const std::vector<int>& here, bool last) {
+        const int C = t.C, M = r.B * t.HW;
+        WGET(l1w, b + "norm1.weight"); WGET(l1b, b + "norm1.bias");
+        WGET(qkv, b + "attn1.qkv");
+        // (the fused launch: not in the block the walk ends in, whose q, k, v go to three tensors)
+        const int fq = last ? 1 : ln_proj(r.h, l1w, l1b, b + "attn1.qkv.stream", t.big, M, C, 3 * C);
+        if (fq < 0) return fq;
+        // a tap's q/k/v come from the unfused norm1 -> projection chain: the fused launch is not bit-identical to it, so where the
+        // block carries on through that launch, the tap gets a norm1 of its own; elsewhere the two share one
+        if (fq > 0 || !here.empty()) CK(ln(r.h, l1w, l1b, t.nb, M, C));
+        for (int i : here) {
+            CK(tap_qkv(t.nb, qkv, C, M, taps[i]));
+            ++n_captured;
+        }
+        if (last) {
+            tapped = true;
+            return DSIM_OK;
+        }
+        WGET(o1w, b + "attn1.to_out.0.weight"); WGET(o1b, b + "attn1.to_out.0.bias");
+        if (fq > 0) CK(linear(t.nb, C, nullptr, 0, qkv, nullptr, nullptr, t.big, M, 3 * C, 3 * C));
+        AttnArgs a;
+        a.q = t.big; a.ldq = 3 * C;
+        a.k = (char*)t.big + (size_t)C * es(); a.v = (char*)t.big + (size_t)2 * C * es(); a.ldk = 3 * C;
+        a.out = r.a; a.ldo = C; a.B = r.B; a.Bkv = r.B; a.H = t.heads; a.Nq = t.HW; a.Nk = t.HW; a.D = C / t.heads;
+        CK(attn(a));
+        return linear(r.a, C, nullptr, 0, o1w, o1b, r.h, r.h, M, C, C);
+    }
+
+    // The two CFG halves part: [image] -> [image][cfg] for the residual stream, the cross-attention query and the model's input.
+    int part_halves(const Tfm& t) {
+        const int n = t.half.B;
+        const size_t per = (size_t)t.HW * t.C * es();
+        return launch([&] { return rec(std::string("cfg_duplicate_") + dtn(), 0.0, 3.0 * 3.0 * (n * t.HW) * (double)t.C * es()); },
+                      [&] {
+                          int st = dup_batch(t.half.h, t.full.h, n, per, s);
+                          if (st == DSIM_OK) st = dup_batch(t.half.a, t.full.a, n, per, s);
+                          if (st == DSIM_OK) st = dup_batch(t.x, t.xfull, n, per, s);
+                          return st;
+                      });
+    }
+
+    // Cross-attention against the prompt context: batch element b uses ctx[b % 2]; with a context table (n_ctx > 1),
+    // ctx[index[b / 2]][b % 2], gathered per batch element in go().  The query is the last thing computed on the rows r; the prompt
+    // enters after it, so `pre` (r = the de-duplicated half) parts the halves there and the rest runs on the full batch.
+    int cross_attention(const std::string& b, const Tfm& t, const Rows& r, bool pre) {
+        const int C = t.C, L = h->cfg.ctx_len, Dc = h->cfg.cross_attention_dim;
+        WGET(l2w, b + "norm2.weight"); WGET(l2b, b + "norm2.bias");
+        WGET(q2w, b + "attn2.to_q.weight"); WGET(kv2, b + "attn2.kv");
+        WGET(o2w, b + "attn2.to_out.0.weight"); WGET(o2b, b + "attn2.to_out.0.bias");
+        const int f2 = ln_proj(r.h, l2w, l2b, b + "attn2.to_q.stream", r.a, r.B * t.HW, C, C);
+        if (f2 < 0) return f2;
+        if (f2 > 0) {
+            CK(ln(r.h, l2w, l2b, t.nb, r.B * t.HW, C));
+            CK(linear(t.nb, C, nullptr, 0, q2w, nullptr, nullptr, r.a, r.B * t.HW, C, C));
+        }
+        if (pre) CK(part_halves(t));
+        const Rows& f = t.full;
+        // (a context table: every batch element projects its own context, B * L rows, and attends to its own K / V)
+        const int Bkv = mixed() ? f.B : 2;
+        CK(linear(ctx_t, Dc, nullptr, 0, kv2, nullptr, nullptr, t.kvb, Bkv * L, 2 * C, 2 * C));
+        AttnArgs a;
+        a.q = f.a; a.ldq = C;
+        a.k = t.kvb; a.v = (char*)t.kvb + (size_t)C * es(); a.ldk = 2 * C;
+        a.out = t.big; a.ldo = C; a.B = f.B; a.Bkv = Bkv; a.H = t.heads; a.Nq = t.HW; a.Nk = L; a.D = C / t.heads;
+        CK(attn(a));
+        return linear(t.big, C, nullptr, 0, o2w, o2b, f.h, f.h, f.B * t.HW, C, C);
+    }
+
+    // Feed-forward: norm3 -> Linear(C,8C) -> h*gelu(g) -> Linear(4C,C) -> + residual.  One row-resident launch where the width has
+    // one (16-bit modes, C = 320); else LayerNorm, the GEGLU GEMM (h*gelu(g) in its epilogue) and ff.net.2.
+    int feed_forward(const std::string& b, const Tfm& t) {
+        const int C = t.C, M = t.full.B * t.HW;
+        void* hb = t.full.h;
+        WGET(l3w, b + "norm3.weight"); WGET(l3b, b + "norm3.bias");
+        WGET(f1w, b + "ff.net.0.proj.weight"); WGET(f1b, b + "ff.net.0.proj.bias");
+        WGET(f2w, b + "ff.net.2.weight"); WGET(f2b, b + "ff.net.2.bias");
+        const auto fst = h->pk.find(b + "ff.stream");
+        if (fst != h->pk.end() && (h->fusion & DSIM_FUSE_FF))
+            return launch([&] { return rec(std::string("ff_fused_") + dtn() + "|M" + std::to_string(M) + " C" + std::to_string(C),
+                                           2.0 * M * (double)C * 12 * C, 2.0 * M * (double)C * es() + 12.0 * C * C * es()); },
+                          [&] {
+                              FFArgs fa;
+                              fa.x = hb; fa.out = hb; fa.ln_g = (const float*)l3w->p; fa.ln_b = (const float*)l3b->p;
+                              fa.stream = fst->second.p; fa.b1 = (const float*)f1b->p; fa.b2 = (const float*)f2b->p; fa.M = M; fa.C = C;
+                              fa.eps = 1e-5f; fa.dtype = h->dt;
+                              return launch_ff_fused(fa, s);
+                          });
+        CK(ln(hb, l3w, l3b, t.nb, M, C));
+        CK(linear(t.nb, C, nullptr, 0, f1w, f1b, nullptr, t.big, M, 8 * C, 4 * C, EPI_GEGLU));
+        return linear(t.big, 4 * C, nullptr, 0, f2w, f2b, hb, hb, M, C, C);
+    }
+
     // Transformer2DModel (GroupNorm -> proj_in -> `depth` BasicTransformerBlocks -> proj_out -> +residual; the
     // conv1x1 and the Linear form of proj_in/out are the same GEMM on token-major data).  caps: the requested taps here (site()).
-    // At each tapped transformer block, norm1 and the q/k/v projection run as a walk that stops there runs them; the walk
-    // then stops if no other tap is left, or the block carries on exactly as an untapped one.
-    // half_in: x holds ONE copy per image (B2 / 2 batch elements, opt-in CFG de-duplication): everything up to the first
-    // cross-attention -- the first place the prompt context enters -- runs on that half batch, then the residual stream, the
-    // block input and the cross-attention query are duplicated into [image][cfg] order and the rest runs as usual.
+    // The walk stops in the block that holds its last tap, or every block carries on exactly as an untapped one.
+    // half_in: x holds ONE copy per image (opt-in CFG de-duplication): everything up to the first cross-attention -- the first
+    // place the prompt context enters -- runs on that half batch, then the residual stream, the model's input and the
+    // cross-attention query are duplicated into [image][cfg] order (part_halves) and the rest runs as usual.
     int transformer(const std::string& p, const Act& x, int level, const std::vector<int>& caps, Act* out, bool half_in = false) {
-        const int C = x.C, HW = x.H * x.W, M = B2 * HW, H = heads_at(level), D = C / H;
-        const int Bfull = B2, Mh = (B2 / 2) * HW;
-        const int L = h->cfg.ctx_len, Dc = h->cfg.cross_attention_dim;
-        const int depth = depth_at(level);
+        const int C = x.C, HW = x.H * x.W, B = half_in ? 2 * x.B : x.B, M = B * HW, depth = depth_at(level);
         std::vector<int> cap_blk(caps.size());           // transformer block of each tap here
         int last_blk = -1;
         for (size_t i = 0; i < caps.size(); ++i) {
@@ -206,153 +303,43 @@ struct Walk : WalkBase<dsim_unet> {
         if (!stop_here) last_blk = -1;
         WGET(gnw, p + "norm.weight"); WGET(gnb, p + "norm.bias");
         WGET(piw, p + "proj_in.weight"); WGET(pib, p + "proj_in.bias");
-        if (!stop_here) { out->p = alloc_act((size_t)M * C); out->C = C; out->H = x.H; out->W = x.W; }
+        if (!stop_here) *out = act(B, x.H, x.W, C);
         const size_t mk = ar->mark();
-        void* t1 = alloc_act((size_t)M * C);
-        void* hb = alloc_act((size_t)M * C);
-        void* hbh = half_in ? alloc_act((size_t)Mh * C) : nullptr;      // half-batch residual stream / query / full-batch input copy
-        void* abh = half_in ? alloc_act((size_t)Mh * C) : nullptr;
-        void* xfull = half_in ? alloc_act((size_t)M * C) : nullptr;
-        const void* xres = half_in ? xfull : x.p;                       // residual of proj_out: the block input, full batch
+        Tfm t;
+        t.C = C; t.HW = HW; t.heads = heads_at(level); t.x = x.p;
+        t.nb = alloc_act((size_t)M * C);                 // first the GroupNorm's output, dead after proj_in
+        t.full.h = alloc_act((size_t)M * C); t.full.B = B;
         if (half_in) {
+            t.half.h = alloc_act((size_t)x.rows() * C); t.half.a = alloc_act((size_t)x.rows() * C); t.half.B = x.B;
+            t.xfull = alloc_act((size_t)M * C);
             for (int tb : cap_blk)
-                if (tb == 0) return DSIM_ERR_INVALID;                   // (callers never de-duplicate a tapped first block)
-            B2 = Bfull / 2;
+                if (tb == 0) return DSIM_ERR_INVALID;    // (callers never de-duplicate a tapped first block)
         }
-        const int M0 = half_in ? Mh : M;                                // rows of the part before the first cross-attention
-        void* hb0 = half_in ? hbh : hb;
-        CK(gn(x, nullptr, gnw, gnb, t1, 1e-6f, 0));
-        CK(linear(t1, C, nullptr, 0, piw, pib, nullptr, hb0, M0, C, C));
-        void* nb = t1;                                   // t1 is dead: reuse it for LayerNorm outputs
-        void* big = nullptr;
-        void* ab = nullptr;
-        void* kvb = nullptr;
+        CK(gn(x, nullptr, gnw, gnb, t.nb, 1e-6f, 0));
+        CK(linear(t.nb, C, nullptr, 0, piw, pib, nullptr, half_in ? t.half.h : t.full.h, x.rows(), C, C));
         for (int blk = 0; blk < depth; ++blk) {
-        const std::string b = p + "transformer_blocks." + std::to_string(blk) + ".";
-        WGET(l1w, b + "norm1.weight"); WGET(l1b, b + "norm1.bias");
-        WGET(qkv, b + "attn1.qkv");
-        const bool pre = half_in && blk == 0;            // still on the de-duplicated half batch
-        const int Mx = pre ? Mh : M;
-        void* hbx = pre ? hbh : hb;
-        // LayerNorm + projection as one row-resident launch where the width has one (16-bit modes, C = 320; not the block the walk ends
-        // in, whose q, k, v go to three tensors)
-        auto ln_proj = [&](const void* xin, const Packed* g, const Packed* be, const std::string& key, void* o, int Mr, int N) -> int {
-            const auto it = h->pk.find(key);
-            if (it == h->pk.end() || !(h->fusion & DSIM_FUSE_LNPROJ)) return 1;          // 1: run the unfused chain
-            if (run) {
-                RowLinArgs ra;
-                ra.x = xin; ra.out = o; ra.ln_g = (const float*)g->p; ra.ln_b = (const float*)be->p; ra.stream = it->second.p;
-                ra.M = Mr; ra.C = C; ra.N = N; ra.eps = 1e-5f; ra.dtype = h->dt;
-                pbegin(std::string("ln_linear_") + dtn() + "|M" + std::to_string(Mr) + " N" + std::to_string(N) + " K" + std::to_string(C),
-                       2.0 * Mr * (double)C * N, (double)Mr * (C + N) * es() + (double)C * N * es());
-                const int st = launch_rowlin(ra, s);
-                pend();
-                if (st != DSIM_OK) return st;
+            const std::string b = p + "transformer_blocks." + std::to_string(blk) + ".";
+            const bool pre = half_in && blk == 0, last = blk == last_blk;
+            if (!last && !t.big) {
+                // qkv [M][3C]; later the GEGLU output [M][4C] unless the feed-forward runs as one launch
+                const bool ff1 = h->pk.count(b + "ff.stream") && (h->fusion & DSIM_FUSE_FF);
+                t.big = alloc_act((size_t)M * (ff1 ? 3 : 4) * C);
+                t.full.a = alloc_act((size_t)M * C);
+                t.kvb = alloc_act((size_t)(mixed() ? B : 2) * h->cfg.ctx_len * 2 * C);
             }
-            return DSIM_OK;
-        };
-        const bool last = blk == last_blk;               // the walk ends after this block's q/k/v
-        bool cap = false;
-        for (int tb : cap_blk) cap = cap || tb == blk;
-        int fq = 1;
-        if (!last && !big) {
-            // qkv [M][3C]; later the GEGLU output [M][4C] unless the feed-forward runs as one launch
-            const bool ff1 = h->pk.count(b + "ff.stream") && (h->fusion & DSIM_FUSE_FF);
-            big = alloc_act((size_t)M * (ff1 ? 3 : 4) * C);
-            ab = alloc_act((size_t)M * C);
-            kvb = alloc_act((size_t)(mixed() ? Bfull : 2) * L * 2 * C);
-        }
-        if (!last) fq = ln_proj(hbx, l1w, l1b, b + "attn1.qkv.stream", big, Mx, 3 * C);
-        if (fq < 0) return fq;
-        // a tap's q/k/v come from the unfused norm1 -> projection chain: the fused launch is not bit-identical to it, so where the
-        // block carries on through that launch, the tap gets a norm1 of its own; elsewhere the two share one
-        if (fq > 0 || cap) CK(ln(hbx, l1w, l1b, nb, Mx, C));
-        if (cap) {
+            std::vector<int> here;
             for (size_t i = 0; i < caps.size(); ++i)
-                if (cap_blk[i] == blk) {
-                    CK(tap_qkv(nb, qkv, C, M, taps[caps[i]]));
-                    ++n_captured;
-                }
-            if (last) {
-                tapped = true;
-                ar->release(mk);
-                return DSIM_OK;
-            }
+                if (cap_blk[i] == blk) here.push_back(caps[i]);
+            const Rows& r = pre ? t.half : t.full;
+            CK(self_attention(b, t, r, here, last));
+            if (tapped) break;
+            CK(cross_attention(b, t, r, pre));
+            CK(feed_forward(b, t));
         }
-        WGET(o1w, b + "attn1.to_out.0.weight"); WGET(o1b, b + "attn1.to_out.0.bias");
-        WGET(l2w, b + "norm2.weight"); WGET(l2b, b + "norm2.bias");
-        WGET(q2w, b + "attn2.to_q.weight"); WGET(kv2, b + "attn2.kv");
-        WGET(o2w, b + "attn2.to_out.0.weight"); WGET(o2b, b + "attn2.to_out.0.bias");
-        WGET(l3w, b + "norm3.weight"); WGET(l3b, b + "norm3.bias");
-        WGET(f1w, b + "ff.net.0.proj.weight"); WGET(f1b, b + "ff.net.0.proj.bias");
-        WGET(f2w, b + "ff.net.2.weight"); WGET(f2b, b + "ff.net.2.bias");
-        // self-attention
-        if (fq > 0) CK(linear(nb, C, nullptr, 0, qkv, nullptr, nullptr, big, Mx, 3 * C, 3 * C));
-        {
-            AttnArgs a;
-            a.q = big; a.ldq = 3 * C;
-            a.k = (char*)big + (size_t)C * es(); a.v = (char*)big + (size_t)2 * C * es(); a.ldk = 3 * C;
-            a.out = pre ? abh : ab; a.ldo = C; a.B = B2; a.Bkv = B2; a.H = H; a.Nq = HW; a.Nk = HW; a.D = D;
-            CK(attn(a));
+        if (!tapped) {
+            WGET(pow_, p + "proj_out.weight"); WGET(pob, p + "proj_out.bias");
+            CK(linear(t.full.h, C, nullptr, 0, pow_, pob, half_in ? t.xfull : x.p, out->p, M, C, C));
         }
-        CK(linear(pre ? abh : ab, C, nullptr, 0, o1w, o1b, hbx, hbx, Mx, C, C));
-        // cross-attention against the prompt context: batch element b uses ctx[b % 2]; with a context table (n_ctx > 1),
-        // ctx[index[b / 2]][b % 2], gathered per batch element in go()
-        {
-            const int f2 = ln_proj(hbx, l2w, l2b, b + "attn2.to_q.stream", pre ? abh : ab, Mx, C);
-            if (f2 < 0) return f2;
-            if (f2 > 0) {
-                CK(ln(hbx, l2w, l2b, nb, Mx, C));
-                CK(linear(nb, C, nullptr, 0, q2w, nullptr, nullptr, pre ? abh : ab, Mx, C, C));
-            }
-        }
-        if (pre) {
-            // the two CFG halves part here: [image] -> [image][cfg] for the residual stream, the query and the block input
-            B2 = Bfull;
-            if (run) {
-                const size_t per = (size_t)HW * C * es();
-                pbegin(std::string("cfg_duplicate_") + dtn(), 0.0, 3.0 * 3.0 * Mh * (double)C * es());
-                int st = dup_batch(hbh, hb, Bfull / 2, per, s);
-                if (st == DSIM_OK) st = dup_batch(abh, ab, Bfull / 2, per, s);
-                if (st == DSIM_OK) st = dup_batch(x.p, xfull, Bfull / 2, per, s);
-                pend();
-                CK(st);
-            }
-        }
-        // (a context table: every batch element projects its own context, B2 * L rows, and attends to its own K / V)
-        const int Bkv = mixed() ? B2 : 2;
-        CK(linear(ctx_t, Dc, nullptr, 0, kv2, nullptr, nullptr, kvb, Bkv * L, 2 * C, 2 * C));
-        {
-            AttnArgs a;
-            a.q = ab; a.ldq = C;
-            a.k = kvb; a.v = (char*)kvb + (size_t)C * es(); a.ldk = 2 * C;
-            a.out = big; a.ldo = C; a.B = B2; a.Bkv = Bkv; a.H = H; a.Nq = HW; a.Nk = L; a.D = D;
-            CK(attn(a));
-        }
-        CK(linear(big, C, nullptr, 0, o2w, o2b, hb, hb, M, C, C));
-        // feed-forward: norm3 -> Linear(C,8C) -> h*gelu(g) -> Linear(4C,C) -> + residual.  One row-resident launch where
-        // the width has one (16-bit modes, C = 320); else LayerNorm, the GEGLU GEMM (h*gelu(g) in its epilogue) and ff.net.2.
-        const auto fst = h->pk.find(b + "ff.stream");
-        if (fst != h->pk.end() && (h->fusion & DSIM_FUSE_FF)) {
-            if (run) {
-                FFArgs fa;
-                fa.x = hb; fa.out = hb; fa.ln_g = (const float*)l3w->p; fa.ln_b = (const float*)l3b->p;
-                fa.stream = fst->second.p; fa.b1 = (const float*)f1b->p; fa.b2 = (const float*)f2b->p; fa.M = M; fa.C = C;
-                fa.eps = 1e-5f; fa.dtype = h->dt;
-                pbegin(std::string("ff_fused_") + dtn() + "|M" + std::to_string(M) + " C" + std::to_string(C),
-                       2.0 * M * (double)C * 12 * C, 2.0 * M * (double)C * es() + 12.0 * C * C * es());
-                const int st = launch_ff_fused(fa, s);
-                pend();
-                CK(st);
-            }
-        } else {
-            CK(ln(hb, l3w, l3b, nb, M, C));
-            CK(linear(nb, C, nullptr, 0, f1w, f1b, nullptr, big, M, 8 * C, 4 * C, EPI_GEGLU));
-            CK(linear(big, 4 * C, nullptr, 0, f2w, f2b, hb, hb, M, C, C));
-        }
-        }   // transformer blocks
-        WGET(pow_, p + "proj_out.weight"); WGET(pob, p + "proj_out.bias");
-        CK(linear(hb, C, nullptr, 0, pow_, pob, xres, out->p, M, C, C));
         ar->release(mk);
         return DSIM_OK;
     }
@@ -366,41 +353,34 @@ struct Walk : WalkBase<dsim_unet> {
             // one [uncond, cond] context per image, in the [image][cfg] order of the batch: every cross-attention's K / V projection
             // then runs on B2 * L rows (nothing before the first cross-attention depends on the prompt)
             ctx_t = alloc_act((size_t)B2 * L * Dc);
-            if (run) {
-                pbegin(std::string("ctx_gather_") + dtn(), 0.0, (double)B2 * L * Dc * (4.0 + es()));
-                const int st = gather_ctx(ctx, n_ctx, ctx_index, ctx_t, h->dt, B2 / 2, (size_t)L * Dc, s);
-                pend();
-                CK(st);
-            }
+            CK(launch([&] { return rec(std::string("ctx_gather_") + dtn(), 0.0, (double)B2 * L * Dc * (4.0 + es())); },
+                      [&] { return gather_ctx(ctx, n_ctx, ctx_index, ctx_t, h->dt, B2 / 2, (size_t)L * Dc, s); }));
         } else {
             ctx_t = ar->alloc((size_t)2 * L * Dc * es());
-            if (run) CK(convert_f32_to(ctx, ctx_t, h->dt, (size_t)2 * L * Dc, s));
+            CK(launch([&] { return convert_f32_to(ctx, ctx_t, h->dt, (size_t)2 * L * Dc, s); }));
         }
         WGET(ciw, "conv_in.weight"); WGET(cib, "conv_in.bias");
-        Act x{alloc_act((size_t)B2 * S * S * ch0), ch0, S, S};
-        if (run) {
-            pbegin("prep_conv_in", 2.0 * B2 * S * S * (double)ch0 * 9 * c.in_channels, (double)B2 * S * S * ch0 * es());
-            const int st = prep_conv_in(lat, noise, sa, sb, (const float*)ciw->p, (const float*)cib->p, x.p, h->dt,
-                                        B2 / 2, c.in_channels, S, ch0, 2, s);
-            pend();
-            CK(st);
-        }
+        const auto conv_in = [&](const Act& o, int dup) {
+            return prep_conv_in(lat, noise, sa, sb, (const float*)ciw->p, (const float*)cib->p, o.p, h->dt, B2 / 2, c.in_channels, S, ch0, dup, s);
+        };
+        Act x = act(B2, S, S, ch0);
+        CK(launch([&] { return rec("prep_conv_in", 2.0 * B2 * S * S * (double)ch0 * 9 * c.in_channels, (double)B2 * S * S * ch0 * es()); },
+                  [&] { return conv_in(x, 2); }));
         std::vector<Act> skips;
         skips.push_back(x);
         // Opt-in CFG de-duplication (dsim_unet_set_cfg_dedup): the reference feeds torch.cat([latents] * 2) with [negative,
         // positive] prompt embeddings (diffsim_pipeline.py:208-221), so conv_in, the first ResnetBlock2D and the first
         // transformer up to its cross-attention query see two bit-identical batch halves.  With one time embedding for both
         // halves (SD1.5; SDXL's text_time embedding differs per half) and the tap outside that block, they are computed once
-        // per image and duplicated where the prompt context first enters.  Same kernels, batch-invariant: same bits.
+        // per image -- conv_in a second time, one copy per image, and the first resnet and transformer on that half batch -- and
+        // duplicated where the prompt context first enters.  Same kernels, batch-invariant: same bits.
         bool tap_down0 = false;             // a requested tap in the first down block
         for (const TapReq& t : taps) tap_down0 = tap_down0 || (t.block == DSIM_TAP_DOWN && t.layer == 0);
         const bool dedup = h->cfg_dedup && !h->two_temb && c.down_has_attn[0] && c.layers_per_block >= 1 && !tap_down0;
-        Act xh{nullptr, ch0, S, S};
+        Act xh;
         if (dedup) {
-            xh.p = alloc_act((size_t)(B2 / 2) * S * S * ch0);
-            if (run)
-                CK(prep_conv_in(lat, noise, sa, sb, (const float*)ciw->p, (const float*)cib->p, xh.p, h->dt, B2 / 2, c.in_channels,
-                                S, ch0, 1, s));
+            xh = act(B2 / 2, S, S, ch0);
+            CK(launch([&] { return conv_in(xh, 1); }));
         }
         // ---- down path (hacked_modules.py:583-618) ---------------------------------------
         for (int i = 0; i < nl; ++i) {
@@ -409,15 +389,7 @@ struct Walk : WalkBase<dsim_unet> {
             for (int j = 0; j < c.layers_per_block; ++j) {
                 const bool half = dedup && i == 0 && j == 0;
                 Act r;
-                if (half) {
-                    const int Bfull = B2;
-                    B2 = Bfull / 2;
-                    const int st = resnet(bp + "resnets.0.", xh, nullptr, co, &r);
-                    B2 = Bfull;
-                    CK(st);
-                } else {
-                    CK(resnet(bp + "resnets." + std::to_string(j) + ".", x, nullptr, co, &r));
-                }
+                CK(resnet(bp + "resnets." + std::to_string(j) + ".", half ? xh : x, nullptr, co, &r));
                 x = r;
                 if (c.down_has_attn[i]) {
                     Act t;
@@ -430,7 +402,7 @@ struct Walk : WalkBase<dsim_unet> {
             }
             if (i != nl - 1) {
                 WGET(dw, bp + "downsamplers.0.conv.weight"); WGET(db, bp + "downsamplers.0.conv.bias");
-                Act d{alloc_act((size_t)B2 * ((x.H + 1) / 2) * ((x.W + 1) / 2) * co), co, (x.H + 1) / 2, (x.W + 1) / 2};
+                const Act d = act(x.B, (x.H + 1) / 2, (x.W + 1) / 2, co);
                 CK(conv3(x, dw, (const float*)db->p, nullptr, d.p, co, 2, 0));
                 x = d;
                 skips.push_back(x);
@@ -473,17 +445,13 @@ struct Walk : WalkBase<dsim_unet> {
                 // the upsampled size is the next skip's (diffusers' upsample_size, hacked_modules.py:531-533): twice the side
                 // except below an odd level, where the nearest-neighbour resize to the explicit size runs as its own launch
                 const int th = skips.empty() ? x.H * 2 : skips.back().H, tw = skips.empty() ? x.W * 2 : skips.back().W;
-                Act u{alloc_act((size_t)B2 * th * tw * co), co, th, tw};
+                const Act u = act(x.B, th, tw, co);
                 if (th == 2 * x.H && tw == 2 * x.W) {
                     CK(conv3(x, uw, (const float*)ub->p, nullptr, u.p, co, 1, 1));      // x2 folded into the conv's gather
                 } else {
-                    Act rz{alloc_act((size_t)B2 * th * tw * co), co, th, tw};
-                    if (run) {
-                        pbegin(std::string("resize_nearest_") + dtn(), 0.0, 2.0 * B2 * th * tw * (double)co * es());
-                        const int st = resize_nearest(x.p, rz.p, B2, x.H, x.W, th, tw, (size_t)co * es(), s);
-                        pend();
-                        CK(st);
-                    }
+                    const Act rz = act(x.B, th, tw, co);
+                    CK(launch([&] { return rec(std::string("resize_nearest_") + dtn(), 0.0, 2.0 * x.B * th * tw * (double)co * es()); },
+                              [&] { return resize_nearest(x.p, rz.p, x.B, x.H, x.W, th, tw, (size_t)co * es(), s); }));
                     CK(conv3(rz, uw, (const float*)ub->p, nullptr, u.p, co, 1, 0));
                 }
                 x = u;
@@ -817,8 +785,8 @@ int dsim_unet_set_sample_size(dsim_unet* h, int side) {
 
 // one walk to the deepest of `taps` (their outputs set), every check before the first launch
 static int run_taps(dsim_unet* h, const float* latents, const float* noise, float sqrt_abar, float sqrt_1m_abar, const float* ctx,
-                    int n_images, const std::vector<TapReq>& taps, void* workspace, size_t workspace_bytes, void* stream,
-                    int n_ctx = 1, const int32_t* ctx_index = nullptr) {
+                    int n_images, const std::vector<TapReq>& taps, void* workspace, size_t workspace_bytes, void* stream, int n_ctx,
+                    const int32_t* ctx_index) {
     bool tapped = false;
     CK(run_in_workspace(
         workspace, workspace_bytes,
@@ -838,25 +806,19 @@ static int run_taps(dsim_unet* h, const float* latents, const float* noise, floa
     return tapped ? DSIM_OK : DSIM_ERR_INVALID;        // (a walk that reached no tap is an invalid tap here; dit_run calls it a workspace error)
 }
 
-int dsim_unet_qkv(dsim_unet* h, const float* latents, const float* noise, float sqrt_abar, float sqrt_1m_abar,
-                  const float* ctx, int n_images, void* q, void* k, void* v, void* workspace, size_t workspace_bytes,
-                  void* stream) {
+// What the four dsim_unet_qkv* entry points are: the argument, context-table and state checks, the tap list, one walk.  own_tap: the
+// handle's own tap (n_taps / taps unused; q, k, v name one tensor each).
+static int qkv_call(dsim_unet* h, const float* latents, const float* noise, float sqrt_abar, float sqrt_1m_abar, const float* ctx,
+                    int n_ctx, const int32_t* ctx_index, int n_images, bool own_tap, int n_taps, const dsim_tap* taps, void* const* q,
+                    void* const* k, void* const* v, void* workspace, size_t workspace_bytes, void* stream) {
     if (!h || !latents || !noise || !ctx || !q || !k || !v || !workspace || n_images < 1) return DSIM_ERR_INVALID;
-    if (!h->finalized || h->timestep < 0) return DSIM_ERR_STATE;
-    return run_taps(h, latents, noise, sqrt_abar, sqrt_1m_abar, ctx, n_images, cfg_taps(h->cfg, q, k, v), workspace, workspace_bytes,
-                    stream);
-}
-
-static int qkv_taps(dsim_unet* h, const float* latents, const float* noise, float sqrt_abar, float sqrt_1m_abar, const float* ctx,
-                    int n_ctx, const int32_t* ctx_index, int n_images, int n_taps, const dsim_tap* taps, void* const* q, void* const* k,
-                    void* const* v, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!h || !latents || !noise || !ctx || !q || !k || !v || !workspace || n_images < 1) return DSIM_ERR_INVALID;
+    if (own_tap && (!*q || !*k || !*v)) return DSIM_ERR_INVALID;
     if (n_ctx < 1 || (n_ctx > 1 && !ctx_index) || !ctx_table_ok(h, n_ctx)) return DSIM_ERR_INVALID;
     if (!h->finalized || h->timestep < 0) return DSIM_ERR_STATE;
-    std::vector<TapReq> req;
+    std::vector<TapReq> req = cfg_taps(h->cfg);
     size_t out_bytes;
-    CK(check_taps(h, n_images, n_taps, taps, &req, &out_bytes));
-    for (int i = 0; i < n_taps; ++i) {
+    if (!own_tap) CK(check_taps(h, n_images, n_taps, taps, &req, &out_bytes));
+    for (size_t i = 0; i < req.size(); ++i) {
         if (!q[i] || !k[i] || !v[i]) return DSIM_ERR_INVALID;
         req[i].q = q[i]; req[i].k = k[i]; req[i].v = v[i];
     }
@@ -864,27 +826,31 @@ static int qkv_taps(dsim_unet* h, const float* latents, const float* noise, floa
                     n_ctx > 1 ? ctx_index : nullptr);
 }
 
+int dsim_unet_qkv(dsim_unet* h, const float* latents, const float* noise, float sqrt_abar, float sqrt_1m_abar,
+                  const float* ctx, int n_images, void* q, void* k, void* v, void* workspace, size_t workspace_bytes,
+                  void* stream) {
+    return qkv_call(h, latents, noise, sqrt_abar, sqrt_1m_abar, ctx, 1, nullptr, n_images, true, 0, nullptr, &q, &k, &v, workspace,
+                    workspace_bytes, stream);
+}
+
 int dsim_unet_qkv_taps(dsim_unet* h, const float* latents, const float* noise, float sqrt_abar, float sqrt_1m_abar, const float* ctx,
                        int n_images, int n_taps, const dsim_tap* taps, void* const* q, void* const* k, void* const* v, void* workspace,
                        size_t workspace_bytes, void* stream) {
-    return qkv_taps(h, latents, noise, sqrt_abar, sqrt_1m_abar, ctx, 1, nullptr, n_images, n_taps, taps, q, k, v, workspace,
+    return qkv_call(h, latents, noise, sqrt_abar, sqrt_1m_abar, ctx, 1, nullptr, n_images, false, n_taps, taps, q, k, v, workspace,
                     workspace_bytes, stream);
 }
 
 int dsim_unet_qkv_ctx(dsim_unet* h, const float* latents, const float* noise, float sqrt_abar, float sqrt_1m_abar, const float* ctx,
                       int n_ctx, const int32_t* ctx_index, int n_images, void* q, void* k, void* v, void* workspace,
                       size_t workspace_bytes, void* stream) {
-    if (!h || !latents || !noise || !ctx || !q || !k || !v || !workspace || n_images < 1) return DSIM_ERR_INVALID;
-    if (n_ctx < 1 || (n_ctx > 1 && !ctx_index) || !ctx_table_ok(h, n_ctx)) return DSIM_ERR_INVALID;
-    if (!h->finalized || h->timestep < 0) return DSIM_ERR_STATE;
-    return run_taps(h, latents, noise, sqrt_abar, sqrt_1m_abar, ctx, n_images, cfg_taps(h->cfg, q, k, v), workspace, workspace_bytes,
-                    stream, n_ctx, n_ctx > 1 ? ctx_index : nullptr);
+    return qkv_call(h, latents, noise, sqrt_abar, sqrt_1m_abar, ctx, n_ctx, ctx_index, n_images, true, 0, nullptr, &q, &k, &v, workspace,
+                    workspace_bytes, stream);
 }
 
 int dsim_unet_qkv_taps_ctx(dsim_unet* h, const float* latents, const float* noise, float sqrt_abar, float sqrt_1m_abar, const float* ctx,
                            int n_ctx, const int32_t* ctx_index, int n_images, int n_taps, const dsim_tap* taps, void* const* q,
                            void* const* k, void* const* v, void* workspace, size_t workspace_bytes, void* stream) {
-    return qkv_taps(h, latents, noise, sqrt_abar, sqrt_1m_abar, ctx, n_ctx, ctx_index, n_images, n_taps, taps, q, k, v, workspace,
+    return qkv_call(h, latents, noise, sqrt_abar, sqrt_1m_abar, ctx, n_ctx, ctx_index, n_images, false, n_taps, taps, q, k, v, workspace,
                     workspace_bytes, stream);
 }
 

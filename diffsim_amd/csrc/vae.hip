@@ -58,121 +58,98 @@ __global__ void to_nchw_f32_kernel(const T* __restrict__ x, float* __restrict__ 
 }
 
 struct VWalk : WalkBase<dsim_vae> {
-    int n;                  // images
+    const int n;            // images
     void* gn_scratch = nullptr;
     VWalk(dsim_vae* h, Arena* ar, hipStream_t s, int n, bool run) : WalkBase(h, ar, s, run), n(n) {}
 
     int linear(const void* a, int K, const void* w, const float* bias, const void* residual, void* out, int M, int N) {
-        GemmArgs g;
-        g.A0 = a; g.C0 = K; g.mode = GEMM_LINEAR; g.M = M; g.N = N; g.K = K; g.W = w; g.bias = bias;
-        g.epi = residual ? EPI_RESIDUAL : EPI_NONE; g.residual = residual; g.out = out; g.ldo = N;
+        GemmArgs g = linear_args(a, K, w, bias, residual, out, M, N);
         return gemm(g);
     }
     // The 128 x 128 level (one image = 64 ... 128 of the 256-row tiles): its convs ask for those tiles at EVERY batch size
     // (GemmArgs.force_big), so that the statistics can come from the epilogue there as well -- a single image then runs that level's
     // convs on half the chip (+0.1 ms of a ~12 ms encode), every pair or chunk as before
     static int big_tiles(int hw, int Cout) { return hw >= 128 * 128 && hw % 256 == 0 && Cout % 256 == 0; }
-    // GroupNorm statistics of a conv's output from its epilogue (GemmArgs.gn_part) where ONE image alone fills the chip's 256-row
-    // tiles (the 512 x 512 and 256 x 256 levels: the same tiles at every batch size, so the numbers do not depend on the batch);
+    // GroupNorm statistics of a conv's output from its epilogue (GemmArgs.gn_part): can the conv g produce them?  Where ONE image alone
+    // fills the chip's 256-row tiles (the 512 x 512 and 256 x 256 levels: the same tiles at every batch size, so the numbers do not
+    // depend on the batch; asked with the geometry of a single image).  Leaves g.force_big as the answer needs it.
+    bool epilogue_stats(GemmArgs& g) const {
+        const int hw = g.Hout * g.Wout, cpg = g.N / h->cfg.norm_num_groups;
+        g.force_big = big_tiles(hw, g.N);
+        GemmArgs one = g;
+        one.M = hw;
+        if (h->cfg.norm_num_groups == 32 && g.N % 32 == 0 && (cpg == 4 || cpg == 8 || cpg == 16) && gemm_gn_stats_tile(one, h->dt)) return true;
+        g.force_big = 0;
+        return false;
+    }
+    // the partial-sum buffer of those statistics for B images of hw pixels x C channels
+    float* alloc_stats(int B, int hw, int C) { return (float*)ar->alloc((size_t)B * (hw / 64) * (C / 4) * 2 * sizeof(float)); }
+    static void stats_to(GemmArgs& g, float* part) { g.gn_part = part; g.gn_hw = g.Hout * g.Wout; }
+
     // `stats` receives the partial buffer for the GroupNorm that consumes the output (null: that GroupNorm runs its own pass)
-    int conv3(const Act& x, const Packed* w, const float* bias, const void* residual, void* out, int Cout, int stride,
-              int pad, int batch, float** stats = nullptr) {
-        GemmArgs g;
-        g.A0 = x.p; g.C0 = x.C; g.mode = GEMM_CONV3; g.Hin = x.H; g.Win = x.W;
-        g.Hout = stride == 2 ? x.H / 2 : x.H; g.Wout = stride == 2 ? x.W / 2 : x.W;
-        g.stride = stride; g.ups = 0; g.pad = pad;
-        g.M = batch * g.Hout * g.Wout; g.N = Cout; g.K = 9 * x.C; g.W = w->p; g.bias = bias;
-        g.epi = residual ? EPI_RESIDUAL : EPI_NONE; g.residual = residual; g.out = out; g.ldo = Cout;
+    int conv3(const Act& x, const Packed* w, const float* bias, const void* residual, void* out, int Cout, int stride, int pad,
+              float** stats = nullptr) {
+        GemmArgs g = conv3_args(x, w->p, bias, residual, out, Cout, stride, 0, pad);
         if (stats) {
-            *stats = nullptr;
-            const int hw = g.Hout * g.Wout, cpg = Cout / h->cfg.norm_num_groups;
-            g.force_big = big_tiles(hw, Cout);
-            GemmArgs one = g;
-            one.M = hw;                                          // the geometry of a single image
-            if (h->cfg.norm_num_groups == 32 && Cout % 32 == 0 && (cpg == 4 || cpg == 8 || cpg == 16) && gemm_gn_stats_tile(one, h->dt)) {
-                *stats = (float*)ar->alloc((size_t)batch * (hw / 64) * (Cout / 4) * 2 * sizeof(float));
-                g.gn_part = *stats;
-                g.gn_hw = hw;
-            } else {
-                g.force_big = 0;
-            }
+            *stats = epilogue_stats(g) ? alloc_stats(x.B, g.Hout * g.Wout, Cout) : nullptr;
+            if (*stats) stats_to(g, *stats);
         }
         return gemm(g);
     }
     int gn(const Act& x, const Packed* g, const Packed* b, void* out, int silu, const float* stats = nullptr) {
-        if (!run) return DSIM_OK;
-        const int HW = x.H * x.W;
-        if (stats) {
-            pbegin_gn(n, HW, x.C, 0, h->cfg.norm_num_groups, true);
-            const int st = launch_groupnorm_pre(x.p, x.C, (const float*)g->p, (const float*)b->p, out, n, HW, h->cfg.norm_num_groups, 1e-6f,
-                                                silu, h->dt, gn_scratch, stats, HW / 64, s);
-            pend();
-            return st;
-        }
-        pbegin_gn(n, HW, x.C, 0, h->cfg.norm_num_groups);
-        const int st = launch_groupnorm(x.p, x.C, nullptr, 0, (const float*)g->p, (const float*)b->p, out, n, HW,
-                                        h->cfg.norm_num_groups, 1e-6f, silu, h->dt, gn_scratch, s);
-        pend();
-        return st;
+        const int HW = x.H * x.W, groups = h->cfg.norm_num_groups;
+        const float *gw = (const float*)g->p, *gb = (const float*)b->p;
+        return launch([&] { return gn_rec(x.B, HW, x.C, 0, groups, stats != nullptr); },
+                      [&] {
+                          return stats ? launch_groupnorm_pre(x.p, x.C, gw, gb, out, x.B, HW, groups, 1e-6f, silu, h->dt, gn_scratch, stats,
+                                                              HW / 64, s)
+                                       : launch_groupnorm(x.p, x.C, nullptr, 0, gw, gb, out, x.B, HW, groups, 1e-6f, silu, h->dt, gn_scratch, s);
+                      });
     }
 
     // in_stats: epilogue statistics of x (from the conv that produced it) for norm1; out_stats: receives those of this block's output
     int resnet(const std::string& p, const Act& x, int Cout, Act* out, const float* in_stats = nullptr, float** out_stats = nullptr) {
-        const int Cin = x.C, M = n * x.H * x.W;
+        const int Cin = x.C, B = x.B, H = x.H, W = x.W, M = x.rows();
         WGET(n1w, p + "norm1.weight"); WGET(n1b, p + "norm1.bias");
         WGET(c1w, p + "conv1.weight"); WGET(c1b, p + "conv1.bias");
         WGET(n2w, p + "norm2.weight"); WGET(n2b, p + "norm2.bias");
         WGET(c2w, p + "conv2.weight"); WGET(c2b, p + "conv2.bias");
-        out->p = alloc_act((size_t)M * Cout); out->C = Cout; out->H = x.H; out->W = x.W;
-        // (the output's statistics buffer outlives this block's scratch: allocated before the mark)
-        float* ostat = nullptr;
-        {
-            GemmArgs one;
-            one.mode = GEMM_CONV3; one.Hout = x.H; one.Wout = x.W; one.Hin = x.H; one.Win = x.W; one.C0 = Cout; one.M = x.H * x.W; one.N = Cout;
-            one.K = 9 * Cout; one.epi = EPI_RESIDUAL;
-            one.force_big = big_tiles(x.H * x.W, Cout);
-            const int cpg = Cout / h->cfg.norm_num_groups;
-            if (out_stats && h->cfg.norm_num_groups == 32 && Cout % 32 == 0 && (cpg == 4 || cpg == 8 || cpg == 16) && gemm_gn_stats_tile(one, h->dt))
-                ostat = (float*)ar->alloc((size_t)n * (x.H * x.W / 64) * (Cout / 4) * 2 * sizeof(float));
-        }
+        *out = act(B, H, W, Cout);
+        // conv2 + residual, but for its input and residual (known below).  Its epilogue statistics (for the next block's norm1) outlive
+        // this block's scratch: their buffer is allocated before the mark
+        GemmArgs c2 = conv3_args(Act{nullptr, Cout, H, W, B}, c2w->p, (const float*)c2b->p, x.p, out->p, Cout, 1, 0, 1);
+        float* ostat = out_stats && epilogue_stats(c2) ? alloc_stats(B, H * W, Cout) : nullptr;
+        if (ostat) stats_to(c2, ostat);
         const size_t mk = ar->mark();
-        Act t1{alloc_act((size_t)M * Cin), Cin, x.H, x.W};
+        const Act t1 = act(B, H, W, Cin);
         CK(gn(x, n1w, n1b, t1.p, 1, in_stats));
-        Act t2{alloc_act((size_t)M * Cout), Cout, x.H, x.W};
+        const Act t2 = act(B, H, W, Cout);
         float* st2 = nullptr;
-        CK(conv3(t1, c1w, (const float*)c1b->p, nullptr, t2.p, Cout, 1, 1, n, &st2));
-        Act t3{t1.p, Cout, x.H, x.W};
+        CK(conv3(t1, c1w, (const float*)c1b->p, nullptr, t2.p, Cout, 1, 1, &st2));
+        Act t3{t1.p, Cout, H, W, B};
         if (Cout > Cin) t3.p = alloc_act((size_t)M * Cout);
         CK(gn(t2, n2w, n2b, t3.p, 1, st2));
-        const void* res = x.p;
+        c2.A0 = t3.p;
         if (Cin != Cout) {
             WGET(scw, p + "conv_shortcut.weight"); WGET(scb, p + "conv_shortcut.bias");
             void* sc = t2.p;                                   // t2 is dead after norm2
             CK(linear(x.p, Cin, scw->p, (const float*)scb->p, nullptr, sc, M, Cout));
-            res = sc;
+            c2.residual = sc;
         }
-        {
-            // conv2 + residual; its epilogue statistics (for the next block's norm1) go to the buffer reserved above
-            GemmArgs g;
-            g.A0 = t3.p; g.C0 = t3.C; g.mode = GEMM_CONV3; g.Hin = g.Hout = x.H; g.Win = g.Wout = x.W; g.stride = 1; g.ups = 0; g.pad = 1;
-            g.M = M; g.N = Cout; g.K = 9 * t3.C; g.W = c2w->p; g.bias = (const float*)c2b->p;
-            g.epi = EPI_RESIDUAL; g.residual = res; g.out = out->p; g.ldo = Cout;
-            if (ostat) { g.gn_part = ostat; g.gn_hw = x.H * x.W; g.force_big = big_tiles(x.H * x.W, Cout); }
-            CK(gemm(g));
-        }
+        CK(gemm(c2));
         if (out_stats) *out_stats = ostat;
         ar->release(mk);
         return DSIM_OK;
     }
 
     int attention(const std::string& p, const Act& x, Act* out) {
-        const int C = x.C, N = x.H * x.W, M = n * N;
+        const int C = x.C, N = x.H * x.W, M = x.rows();
         WGET(gw, p + "group_norm.weight"); WGET(gb, p + "group_norm.bias");
         WGET(wq, p + "to_q.weight"); WGET(bq, p + "to_q.bias");
         WGET(wk, p + "to_k.weight"); WGET(bk, p + "to_k.bias");
         WGET(wv, p + "to_v.weight"); WGET(bv, p + "to_v.bias");
         WGET(wo, p + "to_out.0.weight"); WGET(bo, p + "to_out.0.bias");
-        out->p = alloc_act((size_t)M * C); out->C = C; out->H = x.H; out->W = x.W;
+        *out = act(n, x.H, x.W, C);
         const size_t mk = ar->mark();
         char* t = (char*)alloc_act((size_t)M * C);
         CK(gn(x, gw, gb, t, 0));
@@ -198,26 +175,19 @@ struct VWalk : WalkBase<dsim_vae> {
             const Packed* wrep = h->find(p + "to_v.weight_rep");
             for (int i = 0; i < gi;) {                                                                // v^T = Wv x^T
                 const int nb = (wrep && C % 256 == 0) ? std::min(gi - i, VAE_VREP) : 1;
-                GemmArgs gv;
-                gv.A0 = nb > 1 ? wrep->p : wv->p; gv.C0 = C; gv.mode = GEMM_LINEAR; gv.M = nb * C; gv.N = N; gv.K = C;
-                gv.W = t + (i0 + i) * img; gv.epi = EPI_NONE; gv.out = vT + i * img; gv.ldo = N;
+                GemmArgs gv = linear_args(nb > 1 ? wrep->p : wv->p, C, t + (i0 + i) * img, nullptr, nullptr, vT + i * img, nb * C, N);
                 if (nb > 1) { gv.wb_rows = C; gv.wb_stride = (unsigned)img; }
                 CK(gemm(gv));
                 i += nb;
             }
-            GemmArgs g;
-            g.A0 = q + i0 * img; g.C0 = C; g.mode = GEMM_LINEAR; g.M = gi * N; g.N = N; g.K = C; g.W = k + i0 * img;
-            g.epi = EPI_NONE; g.out = sc; g.ldo = N; g.wb_rows = N; g.wb_stride = (unsigned)img;
+            GemmArgs g = linear_args(q + i0 * img, C, k + i0 * img, nullptr, nullptr, sc, gi * N, N);
+            g.wb_rows = N; g.wb_stride = (unsigned)img;
             CK(gemm(g));                                                                              // S = q k^T
-            if (run) {
-                pbegin(std::string("softmax_rows_") + dtn() + "|N" + std::to_string(N), 0.0, 2.0 * gi * N * (double)N * es());
-                const int st = launch_softmax_rows(sc, sc, gi * N, N, 1.0f / sqrtf((float)C), h->dt, s);
-                pend();
-                CK(st);
-            }
-            GemmArgs o2;
-            o2.A0 = sc; o2.C0 = N; o2.mode = GEMM_LINEAR; o2.M = gi * N; o2.N = C; o2.K = N; o2.W = vT; o2.bias = (const float*)bv->p;
-            o2.epi = EPI_NONE; o2.out = o + i0 * img; o2.ldo = C; o2.wb_rows = N; o2.wb_stride = (unsigned)img;
+            CK(launch([&] { return rec(std::string("softmax_rows_") + dtn() + "|N" + std::to_string(N), 0.0,
+                                       2.0 * gi * N * (double)N * es()); },
+                      [&] { return launch_softmax_rows(sc, sc, gi * N, N, 1.0f / sqrtf((float)C), h->dt, s); }));
+            GemmArgs o2 = linear_args(sc, N, vT, (const float*)bv->p, nullptr, o + i0 * img, gi * N, C);
+            o2.wb_rows = N; o2.wb_stride = (unsigned)img;
             CK(gemm(o2));                                                                             // O = P v + b_v
         }
         CK(linear(o, C, wo->p, (const float*)bo->p, x.p, out->p, M, C));
@@ -230,20 +200,17 @@ struct VWalk : WalkBase<dsim_vae> {
         const int nl = c.n_levels, ch0 = c.block_out_channels[0];
         gn_scratch = ar->alloc(groupnorm_scratch_bytes(n, c.norm_num_groups));
         WGET(ciw, "encoder.conv_in.weight"); WGET(cib, "encoder.conv_in.bias");
-        Act x{alloc_act((size_t)n * S * S * ch0), ch0, S, S};
+        Act x = act(n, S, S, ch0);
         float* xstat = nullptr;                 // epilogue statistics of x, when its producer made them
         const bool rows = conv_in_rows_applies(c.in_channels, S, ch0);
-        if (rows && h->dt != DSIM_F32 && c.norm_num_groups == 32)       // (one 4-channel quad per group at 128 channels)
-            xstat = (float*)ar->alloc((size_t)n * (S * S / 64) * (ch0 / 4) * 2 * sizeof(float));
-        if (run) {
-            pbegin(rows ? "conv_in_rows" : "prep_conv_in", 2.0 * n * S * S * (double)ch0 * 9 * c.in_channels,
-                   (double)n * S * S * (ch0 * es() + c.in_channels * 4.0));
-            const int st = rows ? conv_in_rows(images, (const float*)ciw->p, (const float*)cib->p, x.p, h->dt, n, S, xstat, s)
-                                : prep_conv_in(images, nullptr, 1.f, 0.f, (const float*)ciw->p, (const float*)cib->p, x.p, h->dt, n,
-                                               c.in_channels, S, ch0, 1, s);
-            pend();
-            CK(st);
-        }
+        if (rows && h->dt != DSIM_F32 && c.norm_num_groups == 32) xstat = alloc_stats(n, S * S, ch0);      // (one 4-channel quad per group at 128 channels)
+        CK(launch([&] { return rec(rows ? "conv_in_rows" : "prep_conv_in", 2.0 * n * S * S * (double)ch0 * 9 * c.in_channels,
+                                   (double)n * S * S * (ch0 * es() + c.in_channels * 4.0)); },
+                  [&] {
+                      return rows ? conv_in_rows(images, (const float*)ciw->p, (const float*)cib->p, x.p, h->dt, n, S, xstat, s)
+                                  : prep_conv_in(images, nullptr, 1.f, 0.f, (const float*)ciw->p, (const float*)cib->p, x.p, h->dt, n,
+                                                 c.in_channels, S, ch0, 1, s);
+                  }));
         for (int i = 0; i < nl; ++i) {
             const int co = c.block_out_channels[i];
             const std::string bp = "encoder.down_blocks." + std::to_string(i) + ".";
@@ -257,8 +224,8 @@ struct VWalk : WalkBase<dsim_vae> {
             }
             if (i != nl - 1) {
                 WGET(dw, bp + "downsamplers.0.conv.weight"); WGET(db, bp + "downsamplers.0.conv.bias");
-                Act d{alloc_act((size_t)n * (x.H / 2) * (x.W / 2) * co), co, x.H / 2, x.W / 2};
-                CK(conv3(x, dw, (const float*)db->p, nullptr, d.p, co, 2, 0, n, &xstat));
+                const Act d = act(n, x.H / 2, x.W / 2, co);
+                CK(conv3(x, dw, (const float*)db->p, nullptr, d.p, co, 2, 0, &xstat));
                 x = d;
             } else {
                 xstat = nullptr;
@@ -273,24 +240,21 @@ struct VWalk : WalkBase<dsim_vae> {
         }
         WGET(nw, "encoder.conv_norm_out.weight"); WGET(nb, "encoder.conv_norm_out.bias");
         WGET(cow, "encoder.conv_out_folded.weight"); WGET(cob, "encoder.conv_out_folded.bias");
-        const int Cm = 2 * c.latent_channels, M = n * x.H * x.W;
-        Act t{alloc_act((size_t)M * x.C), x.C, x.H, x.W};
+        const int Cm = 2 * c.latent_channels;
+        const Act t = act(n, x.H, x.W, x.C);
         CK(gn(x, nw, nb, t.p, 1));
-        void* mo = alloc_act((size_t)M * Cm);
-        CK(conv3(t, cow, (const float*)cob->p, nullptr, mo, Cm, 1, 1, n));
-        if (run) {
-            const size_t total = (size_t)M * Cm;
-            if (h->dt == DSIM_BF16)
-                hipLaunchKernelGGL(to_nchw_f32_kernel<bf16_t>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s,
-                                   (const bf16_t*)mo, moments, x.H * x.W, Cm, total);
-            else if (h->dt == DSIM_F16)
-                hipLaunchKernelGGL(to_nchw_f32_kernel<f16_t>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s,
-                                   (const f16_t*)mo, moments, x.H * x.W, Cm, total);
-            else
-                hipLaunchKernelGGL(to_nchw_f32_kernel<float>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s,
-                                   (const float*)mo, moments, x.H * x.W, Cm, total);
-            DSIM_HIP_CHECK(hipGetLastError());
-        }
+        const Act mo = act(n, x.H, x.W, Cm);
+        CK(conv3(t, cow, (const float*)cob->p, nullptr, mo.p, Cm, 1, 1));
+        CK(launch([&] {
+            return by_dtype(h->dt, [&](auto e) {
+                typedef typename decltype(e)::type T;
+                const size_t total = (size_t)mo.rows() * Cm;
+                hipLaunchKernelGGL(to_nchw_f32_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const T*)mo.p, moments,
+                                   x.H * x.W, Cm, total);
+                DSIM_HIP_CHECK(hipGetLastError());
+                return DSIM_OK;
+            });
+        }));
         return DSIM_OK;
     }
 };
@@ -334,15 +298,11 @@ int dsim_vae_finalize(dsim_vae* h, void* stream) {
     CK(h->dalloc((size_t)Cm * K * dtype_size(h->dt), &fw.p));
     CK(h->dalloc((size_t)Cm * 4, &fb.p));
     fb.rows = Cm; fb.cols = 1;
-    if (h->dt == DSIM_BF16)
-        hipLaunchKernelGGL(fold_quant_kernel<bf16_t>, dim3((K + 255) / 256, Cm), dim3(256), 0, s, wq32, (const bf16_t*)cow->p,
-                           (bf16_t*)fw.p, Cm, K);
-    else if (h->dt == DSIM_F16)
-        hipLaunchKernelGGL(fold_quant_kernel<f16_t>, dim3((K + 255) / 256, Cm), dim3(256), 0, s, wq32, (const f16_t*)cow->p,
-                           (f16_t*)fw.p, Cm, K);
-    else
-        hipLaunchKernelGGL(fold_quant_kernel<float>, dim3((K + 255) / 256, Cm), dim3(256), 0, s, wq32, (const float*)cow->p,
-                           (float*)fw.p, Cm, K);
+    (void)by_dtype(h->dt, [&](auto e) {
+        typedef typename decltype(e)::type T;
+        hipLaunchKernelGGL(fold_quant_kernel<T>, dim3((K + 255) / 256, Cm), dim3(256), 0, s, wq32, (const T*)cow->p, (T*)fw.p, Cm, K);
+        return DSIM_OK;
+    });
     hipLaunchKernelGGL(fold_quant_bias_kernel, dim3(1), dim3(64), 0, s, wq32, (const float*)cob->p, (const float*)qb->p,
                        (float*)fb.p, Cm);
     DSIM_HIP_CHECK(hipGetLastError());

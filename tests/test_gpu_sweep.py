@@ -173,6 +173,32 @@ def test_no_repeated_prefix(dtype):
     assert 0 < eng.taps_workspace_bytes(4, taps) <= ws_deep
 
 
+def test_one_tap_calls_are_one_path():
+    """A one-tap call, a sweep over that one tap and a one-tap call with a context table of one row are one walk: the same launches
+    (family, shape, FLOPs) in the same order, and the same bits."""
+    from diffsim_amd.scorer import PromptTable
+    cfg = C.TINY
+    ds = _ds(cfg, torch.bfloat16, dedup=True)
+    la, lb, nA, nB = _pairs(cfg, 2)
+    ctx = S.make_context(cfg)
+    lat, nz = stack_rows([la, lb], [nA, nB], 0, 2)
+    table = PromptTable(ds.context(ctx)[None].contiguous(), [0] * lat.shape[0])
+    taps = [("down_blocks", l) for l in range(3)] + [("mid_blocks", 0)] + [("up_blocks", l) for l in range(3)]
+    ds.features(lat, nz, ctx, *taps[0], 600)                     # (timestep, arenas, code objects)
+    eng = ds._base
+    for tap in taps:
+        calls = {"one": lambda: ds.features(lat, nz, ctx, *tap, 600),
+                 "sweep": lambda: ds.features_taps(lat, nz, ctx, [tap], 600)[0],
+                 "table": lambda: ds.features(lat, nz, table, *tap, 600)}
+        out = {}
+        recs = {name: _recs(eng, lambda: out.__setitem__(name, fn())) for name, fn in calls.items()}
+        assert recs["one"], tap
+        assert recs["sweep"] == recs["one"], tap
+        assert recs["table"] == recs["one"], tap
+        _equal_feats(out["sweep"], out["one"], tap)
+        _equal_feats(out["table"], out["one"], tap)
+
+
 def test_contract_order_errors_and_handle_state():
     from diffsim_amd import _lib
     cfg = C.TINY
