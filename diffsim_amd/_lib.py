@@ -185,6 +185,7 @@ SYMBOLS = {
     "dsim_op_ln_linear": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
     "dsim_op_ff_fused_dt": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _i, _vp]),
     "dsim_op_ln_linear_dt": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _vp]),
+    "dsim_op_gn_linear_dt": (_i, [_vp, _vp, _vp, _i, _f, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "dsim_op_gemm": (_i, [C.POINTER(GemmOpC), C.POINTER(GemmLaunchC), _vp]),
     "dsim_op_groupnorm_pre": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _f, _i, _i, _vp, _i, _vp]),
     "dsim_op_attention_ex": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(AttnLaunchC), _vp]),

@@ -326,6 +326,31 @@ int dsim_op_ln_linear_dt(const void* x, const float* ln_gamma, const float* ln_b
     return DSIM_OK;
 }
 
+int dsim_op_gn_linear_dt(const void* x, const float* gamma, const float* beta, int groups, float eps, const float* w, const float* bias,
+                         void* out, int B, int HW, int C, int N, int dtype, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    const size_t sb = rowlin_stream_bytes(C, N);
+    if ((dtype != DSIM_BF16 && dtype != DSIM_F16) || !sb || N > C || !x || !out || !w || !gamma != !beta || B < 1 || HW < 1) return DSIM_ERR_INVALID;
+    if (gamma && (groups < 1 || HW % 128)) return DSIM_ERR_INVALID;        // a 128-row tile lies inside one image
+    Tmp t;
+    void* wp = t.get((size_t)N * C * 2);
+    void* st = t.get(sb);
+    void* sc = gamma ? t.get(groupnorm_scratch_bytes(B, groups)) : nullptr;
+    float* coef = gamma ? (float*)t.get((size_t)B * 2 * C * sizeof(float)) : nullptr;
+    if (!wp || !st || (gamma && (!sc || !coef))) return DSIM_ERR_HIP;
+    CK(pack_linear(w, DSIM_F32, wp, dtype, N, C, 0, s));
+    CK(pack_rowlin_stream(wp, st, C, N, s));
+    RowLinArgs a;
+    a.x = x; a.out = out; a.stream = st; a.M = B * HW; a.C = C; a.N = N; a.dtype = dtype; a.gn = 1; a.bias = bias; a.HW = HW;
+    if (gamma) {
+        CK(launch_groupnorm_stats(x, C, gamma, beta, B, HW, groups, eps, dtype, sc, coef, s));
+        a.coef = coef;
+    }
+    CK(launch_rowlin(a, s));
+    DSIM_HIP_CHECK(hipStreamSynchronize(s));
+    return DSIM_OK;
+}
+
 int dsim_op_ln_linear(const void* x, const float* ln_gamma, const float* ln_beta, const float* w, void* out, int M, int C, int N,
                       float eps, void* stream) {
     return dsim_op_ln_linear_dt(x, ln_gamma, ln_beta, w, out, M, C, N, eps, DSIM_BF16, stream);

@@ -238,7 +238,8 @@ int dup_batch(const void* in, void* out, int n_batch, size_t bytes_per_elem, hip
 // upsample of latent sides that are not a multiple of 2**levels (diffusers' forward_upsample_size)
 int resize_nearest(const void* in, void* out, int B, int Hin, int Win, int Hout, int Wout, size_t row_bytes, hipStream_t s);
 
-// row-resident Linear for K = 320 (optionally behind a LayerNorm): out[M][N] = LN?(x) W^T (+ bias), N % 64 == 0, N <= 960 -- rowres.hip
+// row-resident Linear for K = 320 and 640: out[M][N] = P(x) W^T (+ bias), N % 64 == 0, N <= 3 C -- rowres.hip.  P: nothing, a
+// LayerNorm (ln_g, ln_b), or -- the GroupNorm form, gn = 1, N <= C -- the per-image channel affine of launch_groupnorm_stats' table
 struct RowLinArgs {
     const void* x = nullptr;                    // [M][C] h16
     void* out = nullptr;                        // [M][N] h16
@@ -248,6 +249,10 @@ struct RowLinArgs {
     int M = 0, C = 0, N = 0;
     float eps = 1e-5f;
     int dtype = DSIM_BF16;                      // DSIM_BF16 or DSIM_F16
+    int gn = 0;                                 // the GroupNorm form: the two below, no LayerNorm
+    const float* coef = nullptr;                // [M / HW][2][C] f32 (sc, sh per image and channel); null: x enters as it is
+    const float* bias = nullptr;                // [N] f32, the accumulators' initial value; null: none
+    int HW = 0;                                 // rows per image (coef: HW % 128 == 0, M % HW == 0)
 };
 
 // uint8 HWC pixels -> process_image's normalised NCHW f32 (half: rounded through fp16); VAE posterior sample -- pack.hip
@@ -267,6 +272,10 @@ int launch_groupnorm(const void* x0, int C0, const void* x1, int C1, const float
                      int dtype, void* scratch, hipStream_t s);
 int launch_groupnorm_pre(const void* x, int C, const float* gamma, const float* beta, void* out, int B, int HW, int groups, float eps,
                          int silu, int dtype, void* scratch, const float* part32, int chunks, hipStream_t s);   // statistics from GemmArgs.gn_part
+// The statistics-only GroupNorm (16-bit dtypes): launch_groupnorm's statistics for this shape (same scratch) and no apply pass; coef =
+// the caller's table [B][2][C] f32 (16-byte aligned), (sc, sh) with y = fmaf(x, sc, sh) the bits launch_groupnorm writes (RowLinArgs.coef)
+int launch_groupnorm_stats(const void* x, int C, const float* gamma, const float* beta, int B, int HW, int groups, float eps, int dtype,
+                           void* scratch, float* coef, hipStream_t s);
 int launch_layernorm(const void* x, const float* gamma, const float* beta, void* out, int M, int C,
                      float eps, int dtype, hipStream_t s);
 // LayerNorm without affine followed by adaLN modulate: y = LN(x) * (1 + scale[half]) + shift[half], half =

@@ -11,6 +11,9 @@
 //                 per group -> one (sum, sumsq) f64 pair per (batch, slab, group).
 //   2. gn_apply : folds the slab partials in fixed order, then y = (x-mean)*rstd*gamma+beta
 //                 [*sigmoid] with 16-byte loads and stores.
+// launch_groupnorm_stats is the statistics alone: pass 1 (or the one-pass form's own partials and fold where that form serves the
+// shape), then gn_coef_kernel writes gn_apply's fold and coefficients once per image for a consumer that normalises the rows it
+// holds (rowres.hip, gn_rowlin_kernel).
 // No float atomics anywhere: results are bit-reproducible and independent of batch size.
 #include <type_traits>
 
@@ -115,6 +118,40 @@ __device__ __forceinline__ void gn_mean_rstd(double a, double q, double n, float
     if (var < 0.0) var = 0.0;
     *mean = (float)m;
     *rstd = (float)(1.0 / sqrt(var + (double)eps));
+}
+
+// The image's chunks x groups partial pairs -> s_mean / s_rstd [groups], the one fold every consumer of gn_stats_kernel's scratch
+// shares (gn_apply_kernel, gn_coef_kernel): fetched by the whole workgroup in one round trip (a per-group thread walking them
+// serially cost ~32 dependent L2 round trips before the first row was streamed), then 4 threads per group (groups <= 64) take every
+// 4th chunk and a two-step xor-shuffle adds them: fixed order per shape.  fold: chunks * groups * 2 doubles of LDS.  Holds barriers.
+__device__ __forceinline__ void gn_fold_partials(const double* __restrict__ part, int b, int chunks, int groups, double n, float eps,
+                                                 double* fold, float* s_mean, float* s_rstd) {
+    const int tid = threadIdx.x;
+    {
+        const double* src = part + (size_t)b * chunks * groups * 2;
+        const int cnt = chunks * groups * 2;
+        for (int i = tid; i < cnt; i += GN_THREADS) fold[i] = src[i];
+    }
+    __syncthreads();
+    {
+        const int g = tid >> 2, t = tid & 3;
+        double a = 0.0, q = 0.0;
+        if (g < groups)
+            for (int c = t; c < chunks; c += 4) {
+                a += fold[(c * groups + g) * 2];
+                q += fold[(c * groups + g) * 2 + 1];
+            }
+        a += __shfl_xor(a, 2, 64); q += __shfl_xor(q, 2, 64);
+        a += __shfl_xor(a, 1, 64); q += __shfl_xor(q, 1, 64);
+        if (t == 0 && g < groups) gn_mean_rstd(a, q, n, eps, &s_mean[g], &s_rstd[g]);
+    }
+    __syncthreads();
+}
+// the affine a normalised channel is written with: y = x * sc + sh
+__device__ __forceinline__ void gn_coef(float gamma, float beta, float mean, float rstd, float& sc, float& sh) {
+    const float w = gamma * rstd;
+    sc = w;
+    sh = beta - mean * w;
 }
 
 // one 16-byte vector into its channels' f32 partials
@@ -262,31 +299,8 @@ __global__ __launch_bounds__(GN_THREADS) void gn_apply_kernel(const T* __restric
     const int trow = tid / tpr, tcol = tid - trow * tpr;
     const int b = blockIdx.y;
     const int cpg = C / groups;
-    // the image's chunks x groups partial pairs: fetched by the whole workgroup in one round trip (a per-group
-    // thread walking them serially cost ~32 dependent L2 round trips before the first row was streamed), then folded
-    // by one thread per group in fixed order
     extern __shared__ __attribute__((aligned(16))) char smem_apply[];
-    double* fold = reinterpret_cast<double*>(smem_apply);
-    {
-        const double* src = part + (size_t)b * chunks * groups * 2;
-        const int cnt = chunks * groups * 2;
-        for (int i = tid; i < cnt; i += GN_THREADS) fold[i] = src[i];
-    }
-    __syncthreads();
-    {
-        // 4 threads per group (groups <= 64) take every 4th chunk, then a two-step xor-shuffle: fixed order per shape
-        const int g = tid >> 2, t = tid & 3;
-        double a = 0.0, q = 0.0;
-        if (g < groups)
-            for (int c = t; c < chunks; c += 4) {
-                a += fold[(c * groups + g) * 2];
-                q += fold[(c * groups + g) * 2 + 1];
-            }
-        a += __shfl_xor(a, 2, 64); q += __shfl_xor(q, 2, 64);
-        a += __shfl_xor(a, 1, 64); q += __shfl_xor(q, 1, 64);
-        if (t == 0 && g < groups) gn_mean_rstd(a, q, (double)HW * cpg, eps, &s_mean[g], &s_rstd[g]);
-    }
-    __syncthreads();
+    gn_fold_partials(part, b, chunks, groups, (double)HW * cpg, eps, reinterpret_cast<double*>(smem_apply), s_mean, s_rstd);
     if (trow >= R) return;
     float sc[NS][VEC], sh[NS][VEC];
 #pragma unroll
@@ -296,9 +310,7 @@ __global__ __launch_bounds__(GN_THREADS) void gn_apply_kernel(const T* __restric
         for (int e = 0; e < VEC; ++e) {
             if (slot < S) {
                 const int c = slot * VEC + e, g = c / cpg;
-                const float w = gamma[c] * s_rstd[g];
-                sc[k][e] = w;
-                sh[k][e] = beta[c] - s_mean[g] * w;
+                gn_coef(gamma[c], beta[c], s_mean[g], s_rstd[g], sc[k][e], sh[k][e]);
             } else {
                 sc[k][e] = sh[k][e] = 0.f;
             }
@@ -333,6 +345,24 @@ __global__ __launch_bounds__(GN_THREADS) void gn_apply_kernel(const T* __restric
             const int slot = tcol + k * tpr;
             if (slot < S) gn_out<T, SILU>(load_slot<T>(x0, C0, x1, C1, row, slot * VEC), sc[k], sh[k], out + row * C + slot * VEC);
         }
+    }
+}
+
+// The statistics-only GroupNorm (launch_groupnorm_stats): after the statistics pass, gn_apply_kernel's fold and coefficients once per
+// image into coef[b][2][C] f32 = (sc[c], sh[c]); the consumer (rowres.hip, gn_rowlin_kernel) applies y = fmaf(x, sc, sh) to the rows it
+// holds.  grid (B).
+__global__ __launch_bounds__(GN_THREADS) void gn_coef_kernel(const float* __restrict__ gamma, const float* __restrict__ beta, int C, int HW,
+                                                             int groups, float eps, int chunks, const double* __restrict__ part,
+                                                             float* __restrict__ coef) {
+    __shared__ float s_mean[64], s_rstd[64];
+    extern __shared__ __attribute__((aligned(16))) char smem_coef[];
+    const int b = blockIdx.x, cpg = C / groups;
+    gn_fold_partials(part, b, chunks, groups, (double)HW * cpg, eps, reinterpret_cast<double*>(smem_coef), s_mean, s_rstd);
+    for (int c = threadIdx.x; c < C; c += GN_THREADS) {
+        float sc, sh;
+        gn_coef(gamma[c], beta[c], s_mean[c / cpg], s_rstd[c / cpg], sc, sh);
+        coef[(size_t)b * 2 * C + c] = sc;
+        coef[(size_t)b * 2 * C + C + c] = sh;
     }
 }
 
@@ -522,7 +552,8 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const T* __restrict__
 // replaces two.  grid (P slabs, B); a thread owns one chunk column and every R-th row, exactly like the two-pass kernels,
 // and the statistics use the same per-channel f32 partials -> fixed-order f64 fold per group (bit-reproducible,
 // independent of the batch size).
-template <typename T, bool SILU, int MAXCH>
+// STATS: the statistics alone -- the group's pair goes to part[b][0][g][2] (the scratch layout with chunks = 1) and nothing is written.
+template <typename T, bool SILU, int MAXCH, bool STATS = false>
 __global__ __launch_bounds__(GN_THREADS) void gn_onepass_kernel(const T* __restrict__ x0, int C0, const T* __restrict__ x1,
                                                                 int C1, const float* __restrict__ gamma,
                                                                 const float* __restrict__ beta, T* __restrict__ out, int HW,
@@ -567,6 +598,14 @@ __global__ __launch_bounds__(GN_THREADS) void gn_onepass_kernel(const T* __restr
     int g, t;
     double a, q;
     gn_group_fold<false>(lds, CS, R, cpg, gslab, GN_THREADS / gslab, tid, g, t, a, q);          // 8 .. 256 threads per group
+    if constexpr (STATS) {
+        if (t == 0) {
+            double* o = reinterpret_cast<double*>(out) + ((size_t)b * groups + c0 / cpg + g) * 2;
+            o[0] = a;
+            o[1] = q;
+        }
+        return;
+    }
     if (t == 0) gn_mean_rstd(a, q, (double)HW * cpg, eps, &s_mean[g], &s_rstd[g]);
     __syncthreads();
     if (!live) return;
@@ -574,9 +613,7 @@ __global__ __launch_bounds__(GN_THREADS) void gn_onepass_kernel(const T* __restr
 #pragma unroll
     for (int e = 0; e < VEC; ++e) {
         const int c = ch + e, cg = (c - c0) / cpg;
-        const float w = gamma[c] * s_rstd[cg];
-        sc[e] = w;
-        sh[e] = beta[c] - s_mean[cg] * w;
+        gn_coef(gamma[c], beta[c], s_mean[cg], s_rstd[cg], sc[e], sh[e]);
     }
 #pragma unroll
     for (int i = 0; i < MAXCH; ++i) {
@@ -621,6 +658,7 @@ template <typename T> constexpr GnTwoPass<T> kGnTwoPass[] = {gn_two_pass<T, 1, 4
 constexpr int GN_OP_MAXCH = 24;
 template <typename T> constexpr decltype(&gn_onepass_kernel<T, false, GN_OP_MAXCH>) kGnOnePass[2] = {
     gn_onepass_kernel<T, false, GN_OP_MAXCH>, gn_onepass_kernel<T, true, GN_OP_MAXCH>};
+template <typename T> constexpr decltype(&gn_onepass_kernel<T, false, GN_OP_MAXCH>) kGnOnePassStats = gn_onepass_kernel<T, false, GN_OP_MAXCH, true>;
 
 template <typename T> struct LnRows {
     int CPL;
@@ -786,6 +824,22 @@ int gn_typed(const void* x0, int C0, const void* x1, int C1, const float* gamma,
     return launch(k.apply[si], l.agrid, l.alds, s, x0, C0, x1, C1, gamma, beta, out, HW, groups, eps, p.chunks, scratch);
 }
 
+// The statistics-only GroupNorm: the statistics of the form launch_groupnorm takes for this shape (the one-pass form's own f32 partials
+// and fold where it applies, else gn_stats_kernel) into the scratch, then gn_coef_kernel into the caller's table coef [B][2][C].
+template <typename T>
+int gn_stats_typed(const void* x, int C, const float* gamma, const float* beta, int B, int HW, int groups, float eps, void* scratch,
+                   float* coef, hipStream_t s) {
+    GnLaunch l;
+    if (gn_plan<T>(C, 0, B, HW, groups, false, &l) != DSIM_OK) return DSIM_ERR_INVALID;
+    const dsim_gn_plan& p = l.p;
+    const int chunks = p.form == 0 ? 1 : p.chunks;
+    // (the one-pass statistics kernel writes its pairs through `out`)
+    const int st = p.form == 0 ? launch(kGnOnePassStats<T>, l.grid, l.lds, s, x, C, (const void*)nullptr, 0, gamma, beta, scratch, HW, groups, eps, p.CS)
+                               : launch(kGnTwoPass<T>[l.row].stats, l.grid, l.lds, s, x, C, (const void*)nullptr, 0, HW, groups, scratch);
+    if (st != DSIM_OK) return st;
+    return launch(gn_coef_kernel, dim3(B), (size_t)chunks * groups * 2 * sizeof(double), s, gamma, beta, C, HW, groups, eps, chunks, scratch, coef);
+}
+
 }  // namespace
 
 // the kernels launch_groupnorm (pre = 0) / launch_groupnorm_pre (pre = 1) start for this shape; host only
@@ -832,6 +886,12 @@ int launch_groupnorm(const void* x0, int C0, const void* x1, int C1, const float
     return by_dtype(dtype, [&](auto e) {
         return gn_typed<typename decltype(e)::type>(x0, C0, x1, C1, gamma, beta, out, B, HW, groups, eps, silu, scratch, s);
     });
+}
+
+int launch_groupnorm_stats(const void* x, int C, const float* gamma, const float* beta, int B, int HW, int groups, float eps, int dtype,
+                           void* scratch, float* coef, hipStream_t s) {
+    if (!coef || dtype == DSIM_F32) return DSIM_ERR_INVALID;
+    return by_dtype(dtype, [&](auto e) { return gn_stats_typed<typename decltype(e)::type>(x, C, gamma, beta, B, HW, groups, eps, scratch, coef, s); });
 }
 
 int launch_layernorm(const void* x, const float* gamma, const float* beta, void* out, int M, int C, float eps,

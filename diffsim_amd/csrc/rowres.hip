@@ -59,9 +59,10 @@ __device__ __forceinline__ int slab_off(int row, int c) { const int s = (row >> 
 // The 16 bytes the image of weight rows [row0, row0 + rows) of the packed [N][320] matrix w holds at chunk position cpos of row
 // `row` of slab `slab`.  (Byte o of an image is slab o / (rows * 128), row o % (rows * 128) / 128, position o % 128 / 16: the
 // packers split o themselves -- split in here, hipcc narrows the arithmetic differently and their code changes.)
-__device__ __forceinline__ u32x4 slab_image(const h16* __restrict__ w, int row0, int slab, int row, int cpos) {
+// ldw, k0: the row pitch of w and the first of the 320 k the image covers (a K = 640 rowlin block is two images: k0 = 0, 320).
+__device__ __forceinline__ u32x4 slab_image(const h16* __restrict__ w, int row0, int slab, int row, int cpos, int ldw = RC, int k0 = 0) {
     const int cl = slab_chunk(row, cpos);
-    return *reinterpret_cast<const u32x4*>(w + (size_t)(row0 + row) * RC + 64 * slab + 8 * cl);
+    return *reinterpret_cast<const u32x4*>(w + (size_t)(row0 + row) * ldw + k0 + 64 * slab + 8 * cl);
 }
 
 // stream chunk ci, 16-byte unit u: see the layout comment at the top (W1: the slab image of the chunk's 64 rows)
@@ -89,32 +90,33 @@ __global__ void pack_ff_stream_kernel(const h16* __restrict__ w1p, const h16* __
 }
 
 // ---- a wave's 32 rows in registers ------------------------------------------------------------------------------------------
-// Row l31 of the tile lives in the lanes l31 and l31 + 32 as RKS raw h16 B-operand fragments: lane (l31, half) holds the columns
+// Row l31 of the tile lives in the lanes l31 and l31 + 32 as KS (RKS; 40 at 640 channels) raw h16 B-operand fragments: lane (l31, half) holds the columns
 // 16 ks + 8 half .. + 7 in x[ks].  The LayerNorm is three passes over those registers (sum, centred squares, normalise): an f32
 // copy of the rows would not fit beside them in the 256 architectural VGPRs the VALU can address.  row_stats() is the first two
 // passes, row_norm() the third for one fragment; the kernels choose where the normalised fragment goes.
-__device__ __forceinline__ void row_stats(u32x4 (&x)[RKS], float eps, float& mean, float& rstd) {
+template <int KS>
+__device__ __forceinline__ void row_stats(u32x4 (&x)[KS], float eps, float& mean, float& rstd) {
     float sum = 0.f;
 #pragma unroll
-    for (int ks = 0; ks < RKS; ++ks) {
+    for (int ks = 0; ks < KS; ++ks) {
         const h16x8 t = __builtin_bit_cast(h16x8, x[ks]);
 #pragma unroll
         for (int j = 0; j < 8; ++j) sum += (float)t[j];
     }
     sum = half_sum(sum);
-    mean = sum * (1.0f / RC);
+    mean = sum * (1.0f / (16 * KS));
     float sq = 0.f;
 #pragma unroll
-    for (int ks = 0; ks < RKS; ++ks) {
+    for (int ks = 0; ks < KS; ++ks) {
         asm volatile("" : "+v"(x[ks]));      // (opaque: keeps hipcc from carrying the f32 conversions from pass to pass)
         const h16x8 t = __builtin_bit_cast(h16x8, x[ks]);
 #pragma unroll
         for (int j = 0; j < 8; ++j) { const float d = (float)t[j] - mean; sq = fmaf(d, d, sq); }
     }
     sq = half_sum(sq);
-    rstd = 1.0f / sqrtf(sq * (1.0f / RC) + eps);
+    rstd = 1.0f / sqrtf(sq * (1.0f / (16 * KS)) + eps);
 }
-// gamma, beta: the resident f32 [RC] vectors in LDS
+// gamma, beta: the resident f32 [16 KS] vectors in LDS
 __device__ __forceinline__ h16x8 row_norm(u32x4& x, int ks, int half, float mean, float rstd, const float* gamma, const float* beta) {
     const int c = 16 * ks + 8 * half;
     const f32x4 g0 = *reinterpret_cast<const f32x4*>(gamma + c), g1 = *reinterpret_cast<const f32x4*>(gamma + c + 4);
@@ -377,25 +379,39 @@ __global__ __launch_bounds__(256, 1) void ff_fused_kernel(const FFParams p, cons
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-// ---- row-resident Linear (optionally behind a LayerNorm) for K = 320 -----------------------------------------------------
-// out[M][N] = LN?(x)[M][320] W^T (+ bias), N a multiple of 64: the fused to_q/to_k/to_v projection behind norm1 (N = 960) and
-// attn2.to_q behind norm2 (hacked_modules.py:88-116).  The tiled GEMM is latency-bound on these: a K of five tiles leaves its
-// two-stage ring one 1.2 us K step of cover for activations that stream from HBM exactly once (726 TF/s, 3.0 TB/s at N = 960),
-// and the LayerNorm in front costs a full read + write of the tensor.  Here a wave keeps its 32 rows in registers
-// (normalised on arrival), the weights stream through a 2-slot LDS ring in 32-column blocks, the output leaves in
-// 128-byte row segments per pair of blocks -- HBM-bound, one pass.  Three 4-wave workgroups per CU (__launch_bounds__(256, 3):
-// <= 168 registers; LLDS = 52736 bytes of LDS each): one workgroup's row loads and stores sit under the others' MFMAs.
-constexpr int LCHB = 32 * RC * 2;              // 20480 bytes per ring slot: W rows [32 b, 32 b + 32) x K 320, five [32][128 B] slabs
-constexpr int LPW = LCHB / 1024 / 4;           // 5 DMA pieces per wave per block
-constexpr int LVEC = 2 * RC;                   // resident f32: LayerNorm gamma, beta
+// ---- row-resident Linear (optionally behind a LayerNorm or a GroupNorm's per-image affine) for K = 320 and K = 640 -----------
+// out[M][N] = P(x)[M][K] W^T (+ bias), N a multiple of 64: the fused to_q/to_k/to_v projection behind norm1 (N = 3 K) and
+// attn2.to_q behind norm2 (hacked_modules.py:88-116), and proj_in behind the Transformer2DModel's GroupNorm.  The tiled GEMM is
+// latency-bound on these: a K of five tiles leaves its two-stage ring one 1.2 us K step of cover for activations that stream from
+// HBM exactly once (726 TF/s, 3.0 TB/s at N = 960), and the normalisation in front costs a full read + write of the tensor.  Here a
+// wave keeps its 32 rows in registers (normalised on arrival), the weights stream through a 2-slot LDS ring in 32-column blocks,
+// the output leaves in 128-byte row segments per pair of blocks -- HBM-bound, one pass.
+// One body (rowlin_body) behind thin kernels:
+//   rowlin_kernel<DBG>         K = 320, LayerNorm where p.ln_g.  Three 4-wave workgroups per CU (__launch_bounds__(256, 3): <= 168
+//                              registers; 52736 bytes of LDS each): one workgroup's row loads and stores sit under the others' MFMAs.
+//   rowlin640_kernel<DBG>      K = 640, the same.  A wave's rows are 40 fragments (160 registers): two workgroups per CU.  The ring
+//                              slot stays 32 columns x 320 k; a column block takes two ring steps into the same accumulator.
+//   gn_rowlin_kernel<K, DBG>   the GroupNorm form: where p.coef, y = (h16) fmaf(x, sc[b][c], sh[b][c]) on arrival -- gn_apply_kernel's
+//                              expression and rounding point (norm.hip), so the rows that enter the MFMAs are the bits the unfused
+//                              GroupNorm writes -- and an f32 bias as the accumulators' initial value.  The coefficients come from
+//                              a table [B][2][K] f32 that the statistics pass leaves (launch_groupnorm_stats), not from a fold of
+//                              the image's partials in every tile: the table is 2 K floats per tile from L2 against up to 16 KB of
+//                              f64 partials.  A 128-row tile lies inside one image (HW % 128 == 0).
+constexpr int LCHB = 32 * RC * 2;              // 20480 bytes per ring slot: W rows [32 b, 32 b + 32) x 320 k, five [32][128 B] slabs
+constexpr int LPW = LCHB / 1024 / 4;           // 5 DMA pieces per wave per ring step
 constexpr int LSCR = 16 * SLABP;               // per-wave transpose slab: 16 rows
-constexpr int LLDS = 2 * LCHB + LVEC * 4 + 4 * LSCR;      // 52736: three workgroups per CU
+// resident f32: [gamma K | beta K] (LayerNorm) or the tile's image's [sc K | sh K]; the GroupNorm form's bias [K] (N <= K there)
+constexpr int rowlin_lds(int K, bool GN) { return 2 * LCHB + 2 * K * 4 + (GN ? K * 4 : 0) + 4 * LSCR; }
+static_assert(rowlin_lds(RC, false) == 52736, "three workgroups per CU");
 
-__global__ void pack_rowlin_stream_kernel(const h16* __restrict__ wp, char* __restrict__ stream, int N) {
+// stream = the ring steps in order: column block b, then (K = 640) its k half
+__global__ void pack_rowlin_stream_kernel(const h16* __restrict__ wp, char* __restrict__ stream, int N, int K) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= N / 32 * (LCHB / 16)) return;
-    const int b = i / (LCHB / 16), o = (i - b * (LCHB / 16)) * 16;
-    *reinterpret_cast<u32x4*>(stream + (size_t)b * LCHB + o) = slab_image(wp, 32 * b, o / 4096, (o % 4096) / 128, (o % 128) / 16);
+    const int kh = K / RC;
+    if (i >= N / 32 * kh * (LCHB / 16)) return;
+    const int t = i / (LCHB / 16), o = (i - t * (LCHB / 16)) * 16;
+    *reinterpret_cast<u32x4*>(stream + (size_t)t * LCHB + o) =
+        slab_image(wp, 32 * (t / kh), o / 4096, (o % 4096) / 128, (o % 128) / 16, K, RC * (t % kh));
 }
 
 struct RLParams {
@@ -407,18 +423,24 @@ struct RLParams {
     int M, N;
     float eps;
     unsigned x_bytes, out_bytes, stream_bytes;
+    // the GroupNorm form only
+    const float* coef;      // [B][2][K] f32: sc, sh of every image; null: no prologue
+    const float* bias;      // [N] f32 or null
+    int HW;                 // rows per image
 };
 
-template <int DBG>      // DBG: kbench ablation masks (1 no output stores, 2 no MFMAs, 4 no row loads, 8 no fragment reads); 0 in the product
-__global__ __launch_bounds__(256, 3) void rowlin_kernel(const RLParams p, const int ntiles) {
+// DBG: kbench ablation masks (1 no output stores, 2 no MFMAs, 4 no row loads, 8 no fragment reads); 0 in the product
+template <int K, bool GN, int DBG>
+__device__ __forceinline__ void rowlin_body(const RLParams& p, const int ntiles) {
+    constexpr int KS = K / 16, KH = K / RC;     // fragments of a row; ring steps per column block
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, half = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const __amdgpu_buffer_rsrc_t rX = buf_rsrc(p.x, p.x_bytes);
     const __amdgpu_buffer_rsrc_t rO = buf_rsrc(p.out, p.out_bytes);
     const __amdgpu_buffer_rsrc_t rS = buf_rsrc(p.stream, p.stream_bytes);
-    const int nblk = p.N / 32;                 // even
-    auto dma = [&](int sp, int blk) {           // this wave's five pieces of weight block `blk` into the slot of parity sp
+    const int nblk = p.N / 32 * KH;            // ring steps per tile; even
+    auto dma = [&](int sp, int blk) {           // this wave's five pieces of ring step `blk` into the slot of parity sp
         char* dst = smem + sp * LCHB + wave * (LPW * 1024);
 #pragma unroll
         for (int d = 0; d < LPW; ++d)
@@ -426,51 +448,94 @@ __global__ __launch_bounds__(256, 3) void rowlin_kernel(const RLParams p, const 
                                                      blk * LCHB + wave * (LPW * 1024) + d * 1024, 0, 0);
     };
     dma(0, 0);
-    float* const vec = reinterpret_cast<float*>(smem + 2 * LCHB);         // [gamma 320 | beta 320]
-    if (p.ln_g)
-        for (int i = tid; i < LVEC; i += 256) vec[i] = i < RC ? p.ln_g[i] : p.ln_b[i - RC];
-    char* const slab = smem + 2 * LCHB + LVEC * 4 + wave * LSCR;
+    float* const vec = reinterpret_cast<float*>(smem + 2 * LCHB);         // [gamma K | beta K], or [sc K | sh K] of the tile's image
+    float* const bvec = vec + 2 * K;                                      // GN: bias [K], zeros past N and without one
+    if (GN) {
+        for (int i = tid; i < K; i += 256) bvec[i] = (p.bias && i < p.N) ? p.bias[i] : 0.f;
+    } else if (p.ln_g) {
+        for (int i = tid; i < 2 * K; i += 256) vec[i] = i < K ? p.ln_g[i] : p.ln_b[i - K];
+    }
+    char* const slab = smem + rowlin_lds(K, GN) - 4 * LSCR + wave * LSCR;
     int woff[4];
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) woff[kk] = slab_off(l31, 2 * kk + half);
     __syncthreads();
-    int blk = 0;                                // weight block the NEXT ring step consumes (wraps at nblk: same weights for every tile)
+    int blk = 0;                                // the ring step the NEXT one consumes (wraps at nblk: same weights for every tile)
 
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const int m0 = tile * 128 + wave * 32;
         // the rows live in ONE register array: raw h16 on arrival, overwritten in place by their normalised values
-        u32x4 xr[RKS];
+        u32x4 xr[KS];
         {
             const int row = m0 + l31;
-            const unsigned rbase = row < p.M ? (unsigned)row * (RC * 2) + half * 16 : BUF_OOB;
+            const unsigned rbase = row < p.M ? (unsigned)row * (K * 2) + half * 16 : BUF_OOB;
 #pragma unroll
-            for (int ks = 0; ks < RKS; ++ks)
+            for (int ks = 0; ks < KS; ++ks)
                 xr[ks] = (DBG & 4) ? u32x4{(unsigned)ks, 1u, 2u, rbase} : __builtin_amdgcn_raw_buffer_load_b128(rX, (int)(rbase + ks * 32), 0, 0);
-            if (p.ln_g) {                       // in place, fragment by fragment
+            if (GN) {
+                if (p.coef) {
+                    // the image's coefficients into LDS.  Every wave has left the previous tile's prologue: it passed that tile's
+                    // ring barriers since.
+                    const float* src = p.coef + (size_t)(tile * 128 / p.HW) * (2 * K);
+                    for (int i = tid; i < 2 * K / 4; i += 256)
+                        *reinterpret_cast<f32x4*>(vec + 4 * i) = *reinterpret_cast<const f32x4*>(src + 4 * i);
+                    __syncthreads();
+#pragma unroll
+                    for (int ks = 0; ks < KS; ++ks) {
+                        const int c = 16 * ks + 8 * half;
+                        const f32x4 s0 = *reinterpret_cast<const f32x4*>(vec + c), s1 = *reinterpret_cast<const f32x4*>(vec + c + 4);
+                        const f32x4 h0 = *reinterpret_cast<const f32x4*>(vec + K + c), h1 = *reinterpret_cast<const f32x4*>(vec + K + c + 4);
+                        const h16x8 t = __builtin_bit_cast(h16x8, xr[ks]);
+                        h16x8 y;
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                            // two roundings, f32 then h16, as gn_apply_kernel's: left to itself hipcc fuses the pair into one
+                            // v_fma_mixlo_f16, which rounds once -- other bits in about one fp16 value of 10^4
+                            float f0 = fmaf((float)t[j], s0[j], h0[j]), f1 = fmaf((float)t[4 + j], s1[j], h1[j]);
+                            asm("" : "+v"(f0), "+v"(f1));
+                            y[j] = (h16)f0;
+                            y[4 + j] = (h16)f1;
+                        }
+                        xr[ks] = __builtin_bit_cast(u32x4, y);
+                    }
+                }
+            } else if (p.ln_g) {                // in place, fragment by fragment
                 float mean, rstd;
                 row_stats(xr, p.eps, mean, rstd);
 #pragma unroll
-                for (int ks = 0; ks < RKS; ++ks) {
-                    xr[ks] = __builtin_bit_cast(u32x4, row_norm(xr[ks], ks, half, mean, rstd, vec, vec + RC));
+                for (int ks = 0; ks < KS; ++ks) {
+                    xr[ks] = __builtin_bit_cast(u32x4, row_norm(xr[ks], ks, half, mean, rstd, vec, vec + K));
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
         }
         __builtin_amdgcn_sched_barrier(0);
-        // one ring step: the 20 MFMAs of weight block `blk` (32 output columns) into `a`, fragments double-buffered by 64-wide K slab
+        // one ring step: 20 MFMAs of 32 output columns x 320 k (k half `kh` of the rows) into `a`, fragments double-buffered by
+        // 64-wide K slab.  kh == 0 starts the accumulator (GN: at the bias of the columns from `col`).
         h16x8 wf[2][2];
-        auto step = [&](int sp, f32x16& a) {
+        auto step = [&](int sp, f32x16& a, int kh, bool stored, int col) {
             // the slot's five DMA pieces must have landed; the four row-segment stores of the previous pair were issued after the
-            // pieces of an even step (vmcnt retires in issue order on gfx9): leave them in flight there
-            if (sp == 0) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+            // pieces of the step before a `stored` one (vmcnt retires in issue order on gfx9): leave them in flight there
+            if (stored) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
             const int nb = blk + 1 == nblk ? 0 : blk + 1;
             dma(sp ^ 1, nb);
             blk = nb;
             const char* slot = smem + sp * LCHB;
+            if (kh == 0) {
+                if (GN) {
 #pragma unroll
-            for (int e = 0; e < 16; ++e) a[e] = 0.f;
+                    for (int q = 0; q < 4; ++q) {
+                        const f32x4 b4 = *reinterpret_cast<const f32x4*>(bvec + col + 8 * q + 4 * half);
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) a[4 * q + e] = b4[e];
+                    }
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 16; ++e) a[e] = 0.f;
+                }
+            }
             auto ld = [&](int i, h16x8 (&w)[2]) {
 #pragma unroll
                 for (int u = 0; u < 2; ++u) {
@@ -486,7 +551,7 @@ __global__ __launch_bounds__(256, 3) void rowlin_kernel(const RLParams p, const 
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int u = 0; u < 2; ++u)
-                    if (!(DBG & 2)) a = H16_MFMA_32x32x16(wf[i & 1][u], __builtin_bit_cast(h16x8, xr[2 * i + u]), a, 0, 0, 0);
+                    if (!(DBG & 2)) a = H16_MFMA_32x32x16(wf[i & 1][u], __builtin_bit_cast(h16x8, xr[RKS * kh + 2 * i + u]), a, 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
             }
         };
@@ -510,14 +575,28 @@ __global__ __launch_bounds__(256, 3) void rowlin_kernel(const RLParams p, const 
             }
         };
         f32x16 a0, a1;
-        for (int pr = 0; pr < nblk / 2; ++pr) {
-            step(0, a0);
-            step(1, a1);
+        for (int pr = 0; pr < p.N / 64; ++pr) {
+            if (KH == 1) {
+                step(0, a0, 0, true, 64 * pr);
+                step(1, a1, 0, false, 64 * pr + 32);
+            } else {
+                step(0, a0, 0, true, 64 * pr);
+                step(1, a0, 1, false, 64 * pr);
+                step(0, a1, 0, false, 64 * pr + 32);
+                step(1, a1, 1, false, 64 * pr + 32);
+            }
             store_pair(a0, a1, 64 * pr);
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
+
+template <int DBG>
+__global__ __launch_bounds__(256, 3) void rowlin_kernel(const RLParams p, const int ntiles) { rowlin_body<RC, false, DBG>(p, ntiles); }
+template <int DBG>
+__global__ __launch_bounds__(256, 2) void rowlin640_kernel(const RLParams p, const int ntiles) { rowlin_body<2 * RC, false, DBG>(p, ntiles); }
+template <int K, int DBG>
+__global__ __launch_bounds__(256, K == RC ? 3 : 2) void gn_rowlin_kernel(const RLParams p, const int ntiles) { rowlin_body<K, true, DBG>(p, ntiles); }
 
 // The launch of either row-resident kernel: 128-row tiles, dealt to a persistent grid of at most wpc workgroups per CU
 template <auto Kern, typename P>
@@ -570,33 +649,44 @@ int launch_ff_fused(const FFArgs& a, hipStream_t s) {
     return launch_rows<ff_fused_kernel<0>>(p, 1, RLDS, s);
 }
 
-size_t rowlin_stream_bytes(int C, int N) { return (C == RC && N % 64 == 0 && N <= 960) ? (size_t)N / 32 * LCHB : 0; }
+size_t rowlin_stream_bytes(int C, int N) {
+    return ((C == RC || C == 2 * RC) && N >= 64 && N % 64 == 0 && N <= 3 * C) ? (size_t)N / 32 * (C / RC) * LCHB : 0;      // up to q|k|v
+}
 
 int pack_rowlin_stream(const void* w_packed, void* stream, int C, int N, hipStream_t s) {
     if (!rowlin_stream_bytes(C, N)) return DSIM_ERR_INVALID;
-    const int n = N / 32 * (LCHB / 16);
-    hipLaunchKernelGGL(pack_rowlin_stream_kernel, dim3((n + 255) / 256), dim3(256), 0, s, (const h16*)w_packed, (char*)stream, N);
+    const int n = N / 32 * (C / RC) * (LCHB / 16);
+    hipLaunchKernelGGL(pack_rowlin_stream_kernel, dim3((n + 255) / 256), dim3(256), 0, s, (const h16*)w_packed, (char*)stream, N, C);
     DSIM_HIP_CHECK(hipGetLastError());
     return DSIM_OK;
 }
 
 int launch_rowlin(const RowLinArgs& a, hipStream_t s) {
     if (a.dtype != DSIM_H16) return a.dtype == DSIM_F16 ? DSIM_F16_TWIN(launch_rowlin(a, s)) : DSIM_ERR_INVALID;
-    if (!rowlin_stream_bytes(a.C, a.N) || a.M < 1 || (size_t)a.M * a.N * 2 >= 0x7fffffffull || !a.ln_g != !a.ln_b) return DSIM_ERR_INVALID;
+    if (!rowlin_stream_bytes(a.C, a.N) || a.M < 1 || (size_t)a.M * a.N * 2 >= 0x7fffffffull || (size_t)a.M * a.C * 2 >= 0x7fffffffull ||
+        !a.ln_g != !a.ln_b) return DSIM_ERR_INVALID;
+    // the GroupNorm form: no LayerNorm beside it, N <= K (its bias lives in K floats of LDS), whole 128-row tiles per image
+    if (a.gn && (a.ln_g || a.N > a.C || (a.coef && (a.HW < 128 || a.HW % 128 || a.M % a.HW)))) return DSIM_ERR_INVALID;
+    if (!a.gn && (a.coef || a.bias)) return DSIM_ERR_INVALID;
     RLParams p;
     p.x = (const h16*)a.x; p.out = (h16*)a.out; p.ln_g = a.ln_g; p.ln_b = a.ln_b; p.stream = (const char*)a.stream;
     p.M = a.M; p.N = a.N; p.eps = a.eps;
-    p.x_bytes = (unsigned)((size_t)a.M * RC * 2); p.out_bytes = (unsigned)((size_t)a.M * a.N * 2);
+    p.x_bytes = (unsigned)((size_t)a.M * a.C * 2); p.out_bytes = (unsigned)((size_t)a.M * a.N * 2);
     p.stream_bytes = (unsigned)rowlin_stream_bytes(a.C, a.N);
+    p.coef = a.coef; p.bias = a.bias; p.HW = a.HW > 0 ? a.HW : 1;
+    if (a.gn)
+        return a.C == RC ? launch_rows<gn_rowlin_kernel<RC, 0>>(p, 3, rowlin_lds(RC, true), s)
+                         : launch_rows<gn_rowlin_kernel<2 * RC, 0>>(p, 2, rowlin_lds(2 * RC, true), s);
+    if (a.C != RC) return launch_rows<rowlin640_kernel<0>>(p, 2, rowlin_lds(2 * RC, false), s);
 #ifdef DSIM_DEVTOOLS
     switch (g_rl_dbg) {
-#define X(d) case d: return launch_rows<rowlin_kernel<d>>(p, g_rl_wpc, LLDS, s);
+#define X(d) case d: return launch_rows<rowlin_kernel<d>>(p, g_rl_wpc, rowlin_lds(RC, false), s);
         X(1) X(2) X(4) X(8) X(10) X(15)
 #undef X
         default: break;
     }
 #endif
-    return launch_rows<rowlin_kernel<0>>(p, g_rl_wpc, LLDS, s);
+    return launch_rows<rowlin_kernel<0>>(p, g_rl_wpc, rowlin_lds(RC, false), s);
 }
 }  // namespace DSIM_H16_NS
 

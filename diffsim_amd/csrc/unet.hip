@@ -95,6 +95,7 @@ struct Walk : WalkBase<dsim_unet> {
     }
     int gn(const Act& x0, const Act* x1, const Packed* g, const Packed* b, void* out, float eps, int silu) {
         const int HW = x0.H * x0.W, C1 = x1 ? x1->C : 0, groups = h->cfg.norm_num_groups;
+        if (run && !out) return DSIM_ERR_INVALID;
         return launch([&] { return gn_rec(x0.B, HW, x0.C, C1, groups); },
                       [&] {
                           return launch_groupnorm(x0.p, x0.C, x1 ? x1->p : nullptr, C1, (const float*)g->p, (const float*)b->p, out, x0.B, HW,
@@ -102,6 +103,7 @@ struct Walk : WalkBase<dsim_unet> {
                       });
     }
     int ln(const void* x, const Packed* g, const Packed* b, void* out, int M, int C) {
+        if (run && !out) return DSIM_ERR_INVALID;
         return launch([&] { return rec(std::string("layernorm_") + dtn() + "|M" + std::to_string(M) + " C" + std::to_string(C), 0.0,
                                        2.0 * M * (double)C * es()); },
                       [&] { return launch_layernorm(x, (const float*)g->p, (const float*)b->p, out, M, C, 1e-5f, h->dt, s); });
@@ -109,17 +111,56 @@ struct Walk : WalkBase<dsim_unet> {
     int attn(const AttnArgs& a) {
         return launch([&] { return attn_rec(a); }, [&] { return launch_attention(a, h->dt, s); });
     }
-    // LayerNorm + projection as one row-resident launch where the width has one (16-bit modes, C = 320).  Returns 1 where it has
-    // none: the caller runs the unfused chain.
-    int ln_proj(const void* x, const Packed* g, const Packed* b, const std::string& key, void* out, int M, int C, int N) {
+    // Does the level of HW-row maps take the row-resident forms that came after the 320-channel LayerNorm ones (the 640-channel
+    // LayerNorm forms, the GroupNorm form)?  Whole 128-row tiles per image: the map size decides, never the batch.
+    static bool rowres_level(int HW) { return HW % 128 == 0; }
+    // Which normalisations run inside their consumer's row-resident launch: each decided here once, for the launches below and for
+    // transformer(), which allocates the normalised-rows buffer only where one of them does not.
+    const Packed* ln_proj_stream(const std::string& key, int C, int HW) const {        // LayerNorm + projection (C = 320; C = 640 on a rowres_level)
         const auto it = h->pk.find(key);
-        if (it == h->pk.end() || !(h->fusion & DSIM_FUSE_LNPROJ)) return 1;
+        return (it == h->pk.end() || !(h->fusion & DSIM_FUSE_LNPROJ) || (C != 320 && !rowres_level(HW))) ? nullptr : &it->second;
+    }
+    const Packed* gn_proj_stream(const std::string& p, int HW) const {                 // GroupNorm + proj_in (a rowres_level)
+        const auto it = h->pk.find(p + "proj_in.stream");
+        return (it == h->pk.end() || !(h->fusion & DSIM_FUSE_LNPROJ) || !rowres_level(HW)) ? nullptr : &it->second;
+    }
+    const Packed* ff_stream(const std::string& b) const {                              // the whole feed-forward behind norm3
+        const auto it = h->pk.find(b + "ff.stream");
+        return (it == h->pk.end() || !(h->fusion & DSIM_FUSE_FF)) ? nullptr : &it->second;
+    }
+    // LayerNorm + projection as one row-resident launch where the width has one (16-bit modes).  Returns 1 where it has none: the
+    // caller runs the unfused chain.
+    int ln_proj(const void* x, const Packed* g, const Packed* b, const std::string& key, void* out, int M, int C, int N, int HW) {
+        const Packed* st = ln_proj_stream(key, C, HW);
+        if (!st) return 1;
         return launch([&] { return rec(std::string("ln_linear_") + dtn() + "|M" + std::to_string(M) + " N" + std::to_string(N) + " K" +
                                            std::to_string(C), 2.0 * M * (double)C * N, (double)M * (C + N) * es() + (double)C * N * es()); },
                       [&] {
                           RowLinArgs ra;
-                          ra.x = x; ra.out = out; ra.ln_g = (const float*)g->p; ra.ln_b = (const float*)b->p; ra.stream = it->second.p;
+                          ra.x = x; ra.out = out; ra.ln_g = (const float*)g->p; ra.ln_b = (const float*)b->p; ra.stream = st->p;
                           ra.M = M; ra.C = C; ra.N = N; ra.eps = 1e-5f; ra.dtype = h->dt;
+                          return launch_rowlin(ra, s);
+                      });
+    }
+    // GroupNorm + proj_in of a Transformer2DModel as a statistics pass and one row-resident launch that normalises the rows on arrival
+    // (16-bit modes, C = 320 / 640).  coef: the statistics pass's table, [x.B][2][C] f32.  Returns 1 where there is none: the caller
+    // runs gn() and linear().
+    int gn_proj(const std::string& p, const Act& x, const Packed* g, const Packed* b, const Packed* bias, float* coef, void* out) {
+        const int HW = x.H * x.W, C = x.C, M = x.rows(), groups = h->cfg.norm_num_groups;
+        const Packed* st = gn_proj_stream(p, HW);
+        if (!st) return 1;
+        const std::string shape = "|B" + std::to_string(x.B) + " HW" + std::to_string(HW) + " C" + std::to_string(C);
+        CK(launch([&] { return rec(std::string("groupnorm_stats_") + dtn() + shape, 0.0, (double)M * C * es()); },
+                  [&] {
+                      return launch_groupnorm_stats(x.p, C, (const float*)g->p, (const float*)b->p, x.B, HW, groups, 1e-6f, h->dt, gn_scratch,
+                                                    coef, s);
+                  }));
+        return launch([&] { return rec(std::string("gn_linear_") + dtn() + "|M" + std::to_string(M) + " N" + std::to_string(C) + " K" +
+                                           std::to_string(C), 2.0 * M * (double)C * C, 2.0 * M * (double)C * es() + (double)C * C * es()); },
+                      [&] {
+                          RowLinArgs ra;
+                          ra.x = x.p; ra.out = out; ra.stream = st->p; ra.M = M; ra.C = C; ra.N = C; ra.dtype = h->dt;
+                          ra.gn = 1; ra.coef = coef; ra.bias = (const float*)bias->p; ra.HW = HW;
                           return launch_rowlin(ra, s);
                       });
     }
@@ -195,7 +236,7 @@ struct Walk : WalkBase<dsim_unet> {
         WGET(l1w, b + "norm1.weight"); WGET(l1b, b + "norm1.bias");
         WGET(qkv, b + "attn1.qkv");
         // (the fused launch: not in the block the walk ends in, whose q, k, v go to three tensors)
-        const int fq = last ? 1 : ln_proj(r.h, l1w, l1b, b + "attn1.qkv.stream", t.big, M, C, 3 * C);
+        const int fq = last ? 1 : ln_proj(r.h, l1w, l1b, b + "attn1.qkv.stream", t.big, M, C, 3 * C, t.HW);
         if (fq < 0) return fq;
         // a tap's q/k/v come from the unfused norm1 -> projection chain: the fused launch is not bit-identical to it, so where the
         // block carries on through that launch, the tap gets a norm1 of its own; elsewhere the two share one
@@ -239,7 +280,7 @@ struct Walk : WalkBase<dsim_unet> {
         WGET(l2w, b + "norm2.weight"); WGET(l2b, b + "norm2.bias");
         WGET(q2w, b + "attn2.to_q.weight"); WGET(kv2, b + "attn2.kv");
         WGET(o2w, b + "attn2.to_out.0.weight"); WGET(o2b, b + "attn2.to_out.0.bias");
-        const int f2 = ln_proj(r.h, l2w, l2b, b + "attn2.to_q.stream", r.a, r.B * t.HW, C, C);
+        const int f2 = ln_proj(r.h, l2w, l2b, b + "attn2.to_q.stream", r.a, r.B * t.HW, C, C, t.HW);
         if (f2 < 0) return f2;
         if (f2 > 0) {
             CK(ln(r.h, l2w, l2b, t.nb, r.B * t.HW, C));
@@ -266,14 +307,13 @@ struct Walk : WalkBase<dsim_unet> {
         WGET(l3w, b + "norm3.weight"); WGET(l3b, b + "norm3.bias");
         WGET(f1w, b + "ff.net.0.proj.weight"); WGET(f1b, b + "ff.net.0.proj.bias");
         WGET(f2w, b + "ff.net.2.weight"); WGET(f2b, b + "ff.net.2.bias");
-        const auto fst = h->pk.find(b + "ff.stream");
-        if (fst != h->pk.end() && (h->fusion & DSIM_FUSE_FF))
+        if (const Packed* fst = ff_stream(b))
             return launch([&] { return rec(std::string("ff_fused_") + dtn() + "|M" + std::to_string(M) + " C" + std::to_string(C),
                                            2.0 * M * (double)C * 12 * C, 2.0 * M * (double)C * es() + 12.0 * C * C * es()); },
                           [&] {
                               FFArgs fa;
                               fa.x = hb; fa.out = hb; fa.ln_g = (const float*)l3w->p; fa.ln_b = (const float*)l3b->p;
-                              fa.stream = fst->second.p; fa.b1 = (const float*)f1b->p; fa.b2 = (const float*)f2b->p; fa.M = M; fa.C = C;
+                              fa.stream = fst->p; fa.b1 = (const float*)f1b->p; fa.b2 = (const float*)f2b->p; fa.M = M; fa.C = C;
                               fa.eps = 1e-5f; fa.dtype = h->dt;
                               return launch_ff_fused(fa, s);
                           });
@@ -307,7 +347,16 @@ struct Walk : WalkBase<dsim_unet> {
         const size_t mk = ar->mark();
         Tfm t;
         t.C = C; t.HW = HW; t.heads = heads_at(level); t.x = x.p;
-        t.nb = alloc_act((size_t)M * C);                 // first the GroupNorm's output, dead after proj_in
+        // nb: the GroupNorm's output, dead after proj_in, then the LayerNorm outputs.  A model whose every normalisation runs inside
+        // its consumer's launch (no tap here: a tap has a norm1 of its own) has none; gn() and ln() refuse a null output.
+        const bool gnp = gn_proj_stream(p, HW) != nullptr;
+        bool all_fused = gnp && caps.empty();
+        for (int blk = 0; blk < depth && all_fused; ++blk) {
+            const std::string b = p + "transformer_blocks." + std::to_string(blk) + ".";
+            all_fused = ln_proj_stream(b + "attn1.qkv.stream", C, HW) && ln_proj_stream(b + "attn2.to_q.stream", C, HW) && ff_stream(b);
+        }
+        if (!all_fused) t.nb = alloc_act((size_t)M * C);
+        float* const coef = gnp ? (float*)ar->alloc((size_t)x.B * 2 * C * sizeof(float)) : nullptr;      // the statistics pass's table
         t.full.h = alloc_act((size_t)M * C); t.full.B = B;
         if (half_in) {
             t.half.h = alloc_act((size_t)x.rows() * C); t.half.a = alloc_act((size_t)x.rows() * C); t.half.B = x.B;
@@ -315,14 +364,18 @@ struct Walk : WalkBase<dsim_unet> {
             for (int tb : cap_blk)
                 if (tb == 0) return DSIM_ERR_INVALID;    // (callers never de-duplicate a tapped first block)
         }
-        CK(gn(x, nullptr, gnw, gnb, t.nb, 1e-6f, 0));
-        CK(linear(t.nb, C, nullptr, 0, piw, pib, nullptr, half_in ? t.half.h : t.full.h, x.rows(), C, C));
+        const int fp = gn_proj(p, x, gnw, gnb, pib, coef, half_in ? t.half.h : t.full.h);
+        if (fp < 0) return fp;
+        if (fp > 0) {
+            CK(gn(x, nullptr, gnw, gnb, t.nb, 1e-6f, 0));
+            CK(linear(t.nb, C, nullptr, 0, piw, pib, nullptr, half_in ? t.half.h : t.full.h, x.rows(), C, C));
+        }
         for (int blk = 0; blk < depth; ++blk) {
             const std::string b = p + "transformer_blocks." + std::to_string(blk) + ".";
             const bool pre = half_in && blk == 0, last = blk == last_blk;
             if (!last && !t.big) {
                 // qkv [M][3C]; later the GEGLU output [M][4C] unless the feed-forward runs as one launch
-                const bool ff1 = h->pk.count(b + "ff.stream") && (h->fusion & DSIM_FUSE_FF);
+                const bool ff1 = ff_stream(b) != nullptr;
                 t.big = alloc_act((size_t)M * (ff1 ? 3 : 4) * C);
                 t.full.a = alloc_act((size_t)M * C);
                 t.kvb = alloc_act((size_t)(mixed() ? B : 2) * h->cfg.ctx_len * 2 * C);
@@ -552,9 +605,12 @@ int dsim_unet_finalize(dsim_unet* h, void* stream) {
             CK(pack_ff_stream(h->pk[k].p, w2->p, P.p, C, s));
             h->pk[b + "ff.stream"] = P;
         }
-        // LayerNorm-fronted projections of the same blocks: norm1 -> to_q|to_k|to_v and norm2 -> attn2.to_q
+        // LayerNorm-fronted projections of the same blocks: norm1 -> to_q|to_k|to_v and norm2 -> attn2.to_q; and the
+        // GroupNorm-fronted proj_in of their Transformer2DModel (N <= K: the GroupNorm form's bound)
         std::vector<std::pair<std::string, std::string>> lps;
         for (auto& kv : h->pk) {
+            if (ends_with(kv.first, "proj_in.weight") && kv.second.rows <= kv.second.cols && rowlin_stream_bytes(kv.second.cols, kv.second.rows))
+                lps.push_back({kv.first, kv.first.substr(0, kv.first.size() - strlen("weight")) + "stream"});
             if (ends_with(kv.first, "attn1.qkv") && rowlin_stream_bytes(kv.second.cols, kv.second.rows))
                 lps.push_back({kv.first, kv.first + ".stream"});
             if (ends_with(kv.first, "attn2.to_q.weight") && rowlin_stream_bytes(kv.second.cols, kv.second.rows))

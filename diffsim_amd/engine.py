@@ -688,8 +688,8 @@ def op_ff_fused(x, ln_g, ln_b, w1, b1, w2, b2, eps=1e-5):
 
 
 def op_ln_linear(x, ln_g, ln_b, w, eps=1e-5):
-    """LayerNorm(x) W^T in one launch (bf16, or fp16: the twin kernel; C = 320, bias-free, N a multiple of 64 up to 960); w [N][C]
-    f32; ln_g = ln_b = None skips the LayerNorm."""
+    """LayerNorm(x) W^T in one launch (bf16, or fp16: the twin kernel; C = 320 or 640, bias-free, N a multiple of 64 up to 3 C);
+    w [N][C] f32; ln_g = ln_b = None skips the LayerNorm."""
     L = _lib.lib()
     _require_cuda(x, ln_g, ln_b, w)
     if x.dtype not in (torch.bfloat16, torch.float16):
@@ -699,6 +699,21 @@ def op_ln_linear(x, ln_g, ln_b, w, eps=1e-5):
     out = torch.empty((M, N), dtype=x.dtype, device=x.device)
     _lib.check(L.dsim_op_ln_linear_dt(x.data_ptr(), _ptr(ln_g), _ptr(ln_b), w.data_ptr(), out.data_ptr(), M, Cc, N, float(eps),
                                       _TORCH2DSIM[x.dtype], _stream_ptr()), "op_ln_linear")
+    return out
+
+
+def op_gn_linear(x, gamma, beta, groups, w, bias=None, eps=1e-6):
+    """GroupNorm(x [B][HW][C]) W^T + bias as a statistics pass and one row-resident launch (16-bit dtypes; C = 320 or 640, N a
+    multiple of 64 up to C, HW % 128 == 0); w [N][C] f32, bias [N] f32 or None; gamma = beta = None: no normalisation."""
+    L = _lib.lib()
+    _require_cuda(x, gamma, beta, w, bias)
+    if x.dtype not in (torch.bfloat16, torch.float16):
+        raise TypeError("op_gn_linear takes a torch.bfloat16 or torch.float16 input")
+    B, HW, Cc = x.shape
+    N = w.shape[0]
+    out = torch.empty((B, HW, N), dtype=x.dtype, device=x.device)
+    _lib.check(L.dsim_op_gn_linear_dt(x.data_ptr(), _ptr(gamma), _ptr(beta), int(groups), float(eps), w.data_ptr(), _ptr(bias),
+                                      out.data_ptr(), B, HW, Cc, N, _TORCH2DSIM[x.dtype], _stream_ptr()), "op_gn_linear")
     return out
 
 

@@ -174,8 +174,11 @@ int  dsim_unet_set_cfg_dedup(dsim_unet* h, int enable);
  * launch -- the A/B switch of bench.py --fusion and of the parity tests; results agree to bf16 rounding, not bit for bit.
  * DSIM_FUSE_FF: norm3 -> ff.net.0.proj (GEGLU) -> ff.net.2 -> + residual of a 320-channel BasicTransformerBlock as one launch
  * (hacked_modules.py:118-132).
- * DSIM_FUSE_LNPROJ: the LayerNorm in front of a 320-channel block's self-attention q/k/v projection (norm1 -> to_q|to_k|to_v)
- * and of its cross-attention query (norm2 -> attn2.to_q) runs inside the projection's launch (hacked_modules.py:88-116).
+ * DSIM_FUSE_LNPROJ: the normalisation in front of a projection runs inside the projection's row-resident launch, at 320 and 640
+ * channels: the LayerNorm of a block's self-attention q/k/v projection (norm1 -> to_q|to_k|to_v) and of its cross-attention query
+ * (norm2 -> attn2.to_q) (hacked_modules.py:88-116), and the Transformer2DModel's GroupNorm -> proj_in, whose GroupNorm then is a
+ * statistics pass only (hacked_modules.py:336-339).  The 640-channel forms and the GroupNorm form engage where a level's map has
+ * HW % 128 == 0 rows -- decided by the map size, never by the batch.
  * DSIM_FUSE_TAPQKV: the tapped layer's to_q / to_k / to_v (hacked_attn.py:61-69) as ONE N = 3C launch whose column runs go to the
  * three output tensors -- taken when q, k, v lie at equal distances in memory (one [3][...] allocation); bit-identical to the
  * three launches, any compute dtype. */
@@ -480,7 +483,7 @@ int dsim_op_softmax_rows(const void* x, void* out, int rows, int cols, float sca
  * Returns DSIM_ERR_INVALID for a width the fused kernel does not cover.                                                   */
 int dsim_op_ff_fused(const void* x, const float* ln_gamma, const float* ln_beta, const float* w1, const float* b1,
                      const float* w2, const float* b2, void* out, int M, int C, float eps, void* stream);
-/* LayerNorm + bias-free Linear as a single launch (bf16, C = 320, N a multiple of 64 up to 960): out[M][N] = LayerNorm(x) W^T --
+/* LayerNorm + bias-free Linear as a single launch (bf16, C = 320 or 640, N a multiple of 64 up to 3 C): out[M][N] = LayerNorm(x) W^T --
  * norm1 -> to_q|to_k|to_v and norm2 -> attn2.to_q of /root/reference/diffsim/hacked_modules.py:88-116.  w: [N][C] f32;
  * ln_gamma = ln_beta = NULL skips the LayerNorm.  Returns DSIM_ERR_INVALID for a shape the kernel does not cover.            */
 int dsim_op_ln_linear(const void* x, const float* ln_gamma, const float* ln_beta, const float* w, void* out, int M, int C,
@@ -492,6 +495,13 @@ int dsim_op_ff_fused_dt(const void* x, const float* ln_gamma, const float* ln_be
                         const float* w2, const float* b2, void* out, int M, int C, float eps, int dtype, void* stream);
 int dsim_op_ln_linear_dt(const void* x, const float* ln_gamma, const float* ln_beta, const float* w, void* out, int M, int C,
                          int N, float eps, int dtype, void* stream);
+/* GroupNorm -> Linear (a Transformer2DModel's norm -> proj_in, hacked_modules.py:336-339) as a statistics pass and ONE row-resident
+ * launch that normalises the rows on arrival: out[B][HW][N] = GroupNorm(x[B][HW][C]) W^T + bias, bit for bit dsim_op_groupnorm
+ * followed by this operator with gamma = beta = NULL (no normalisation: the plain row-resident Linear + bias).  16-bit dtypes,
+ * C = 320 or 640, N a multiple of 64 up to C, w [N][C] f32, bias [N] f32 or NULL; with a GroupNorm HW % 128 == 0 (a 128-row tile
+ * lies inside one image).  DSIM_ERR_INVALID for anything else. */
+int dsim_op_gn_linear_dt(const void* x, const float* gamma, const float* beta, int groups, float eps, const float* w, const float* bias,
+                         void* out, int B, int HW, int C, int N, int dtype, void* stream);
 
 /* The implicit GEMM with every epilogue field the engines use, as one operator (parity tests of each tile and epilogue).
  *   out[m][n] = epi(sum_k A(m,k) W[n][k] + bias[n]); the A0 | A1 channel concatenation along K (linear), or the 3x3 conv of

@@ -603,10 +603,9 @@ static void bench_ff(const char* name, int M, int iters, Timer& t, void* zp) {
     HC(hipFree(st)); HC(hipFree(nb)); HC(hipFree(big)); HC(hipFree(out));
 }
 
-// row-resident Linear (rowres.hip) against the launches it replaces: [LayerNorm +] the 320-wide Linear (interleaved rounds)
-static void bench_rowlin(const char* name, int M, int N, bool ln, int iters, Timer& t, void* zp) {
+// row-resident Linear (rowres.hip) against the launches it replaces: [LayerNorm +] the 320- / 640-wide Linear (interleaved rounds)
+static void bench_rowlin(const char* name, int M, int N, bool ln, int iters, Timer& t, void* zp, int C = 320) {
     if (!want(name)) return;
-    const int C = 320;
     void* x = dalloc_bf16((size_t)M * C, 1);
     void* w = dalloc_bf16((size_t)N * C, 2, 0.05f);
     float* b = dalloc_f32(N, 4);
@@ -663,7 +662,7 @@ static void bench_rowlin(const char* name, int M, int N, bool ln, int iters, Tim
     float lnm = 0.f;
     if (ln) { std::sort(ml.begin(), ml.end()); lnm = ml[rounds / 2]; }
     const double fl = 2.0 * M * (double)C * N;
-    for (int wpc = 1; wpc <= 3; ++wpc) {
+    for (int wpc = 1; wpc <= 3 && C == 320; ++wpc) {        // (the K = 640 kernel: two workgroups per CU, no knob)
         g_rl_wpc = wpc;
         std::vector<float> qa;
         for (int r = 0; r < 5; ++r) qa.push_back(t.run([&] { s1 |= launch_rowlin(a, 0); }, iters));
@@ -675,6 +674,50 @@ static void bench_rowlin(const char* name, int M, int N, bool ln, int iters, Tim
            fl / mf[rounds / 2] / 1e9, lnm, mg[rounds / 2], lnm + mg[rounds / 2], d, s0, s1);
     HC(hipFree(x)); HC(hipFree(w)); HC(hipFree(b)); HC(hipFree(lg)); HC(hipFree(lb));
     HC(hipFree(st)); HC(hipFree(nb)); HC(hipFree(o1)); HC(hipFree(o2)); HC(hipFree(dd));
+}
+
+// GroupNorm -> proj_in: the statistics pass + the row-resident launch that normalises on arrival (rowres.hip, gn_rowlin_kernel)
+// against GroupNorm (statistics, apply) + the tiled Linear with bias (interleaved rounds)
+static void bench_gn_rowlin(const char* name, int B, int HW, int C, int iters, Timer& t, void* zp) {
+    if (!want(name)) return;
+    const int M = B * HW, N = C;
+    void* x = dalloc_bf16((size_t)M * C, 1);
+    void* w = dalloc_bf16((size_t)N * C, 2, 0.05f);
+    float* b = dalloc_f32(N, 4);
+    float* gg = dalloc_f32(C, 6);
+    float* gb = dalloc_f32(C, 7);
+    void *st, *nb, *o1, *o2, *sc;
+    float *dd, *coef;
+    HC(hipMalloc(&st, rowlin_stream_bytes(C, N)));
+    HC(hipMalloc(&nb, (size_t)M * C * 2));
+    HC(hipMalloc(&o1, (size_t)M * N * 2));
+    HC(hipMalloc(&o2, (size_t)M * N * 2));
+    HC(hipMalloc(&sc, groupnorm_scratch_bytes(B, 32)));
+    HC(hipMalloc((void**)&coef, (size_t)B * 2 * C * 4));
+    HC(hipMalloc(&dd, 4));
+    HC(hipMemset(dd, 0, 4));
+    int s0 = pack_rowlin_stream(w, st, C, N, 0), s1 = DSIM_OK;
+    RowLinArgs a;
+    a.x = x; a.out = o1; a.stream = st; a.M = M; a.C = C; a.N = N; a.gn = 1; a.bias = b; a.HW = HW; a.coef = coef;
+    GemmArgs g;
+    g.A0 = nb; g.C0 = C; g.M = M; g.N = N; g.K = C; g.W = w; g.bias = b; g.epi = EPI_NONE; g.out = o2; g.ldo = N; g.zero_page = zp;
+    const int rounds = getenv("KB_ROUNDS") ? atoi(getenv("KB_ROUNDS")) : 5;
+    std::vector<float> ms, mf, mn, mg;
+    for (int r = 0; r < rounds; ++r) {
+        ms.push_back(t.run([&] { s1 |= launch_groupnorm_stats(x, C, gg, gb, B, HW, 32, 1e-6f, DSIM_BF16, sc, coef, 0); }, iters));
+        mf.push_back(t.run([&] { s1 |= launch_rowlin(a, 0); }, iters));
+        mn.push_back(t.run([&] { s1 |= launch_groupnorm(x, C, nullptr, 0, gg, gb, nb, B, HW, 32, 1e-6f, 0, DSIM_BF16, sc, 0); }, iters));
+        mg.push_back(t.run([&] { s1 |= launch_gemm(g, DSIM_BF16, 0); }, iters));
+    }
+    hipLaunchKernelGGL(maxdiff_kernel, dim3(1024), dim3(256), 0, 0, (const __bf16*)o1, (const __bf16*)o2, (size_t)M * N, dd);
+    float d = 0.f;
+    HC(hipMemcpy(&d, dd, 4, hipMemcpyDeviceToHost));
+    for (auto* v : {&ms, &mf, &mn, &mg}) std::sort(v->begin(), v->end());
+    const int m = rounds / 2;
+    printf("%-26s M=%7d  stats %6.3f + gn_rowlin %6.3f = %7.3f ms | gn %6.3f + gemm %6.3f = %7.3f ms   maxdiff %.4g  st=%d/%d\n", name, M,
+           ms[m], mf[m], ms[m] + mf[m], mn[m], mg[m], mn[m] + mg[m], d, s0, s1);
+    HC(hipFree(x)); HC(hipFree(w)); HC(hipFree(b)); HC(hipFree(gg)); HC(hipFree(gb));
+    HC(hipFree(st)); HC(hipFree(nb)); HC(hipFree(o1)); HC(hipFree(o2)); HC(hipFree(sc)); HC(hipFree(coef)); HC(hipFree(dd));
 }
 
 int main(int argc, char** argv) {
@@ -691,6 +734,12 @@ int main(int argc, char** argv) {
     bench_rowlin("rowlin_64_ln_qkv", s64, 960, true, iters, t, zp);
     bench_rowlin("rowlin_64_ln_q", s64, 320, true, iters, t, zp);
     bench_rowlin("rowlin_64_q", s64, 320, false, iters, t, zp);
+    bench_rowlin("rowlin_32_640_ln_qkv", s32, 1920, true, iters, t, zp, 640);
+    bench_rowlin("rowlin_32_640_qkv", s32, 1920, false, iters, t, zp, 640);
+    bench_rowlin("rowlin_32_640_ln_q", s32, 640, true, iters, t, zp, 640);
+    bench_rowlin("rowlin_32_640_q", s32, 640, false, iters, t, zp, 640);
+    bench_gn_rowlin("gn_rowlin_64_320", B2, 4096, 320, iters, t, zp);
+    bench_gn_rowlin("gn_rowlin_32_640", B2, 1024, 640, iters, t, zp);
     // ---- 3x3 convs ----
     bench_gemm("conv3_64_320_320", GEMM_CONV3, s64, 320, 320, 64, 64, EPI_NONE, iters, t, zp);
     bench_gemm("conv3_64_320_320_res", GEMM_CONV3, s64, 320, 320, 64, 64, EPI_RESIDUAL, iters, t, zp);
