@@ -4,7 +4,7 @@
 
 Flags of the reference drivers (``/root/reference/argprocess.py:5-18``) keep their names, meaning and defaults;
 ``--dataset`` selects which of the reference's loops runs (``cute_main.py:48-226``, ``night_main.py:24-173`` or
-``style_main.py:24-196`` -- separate scripts there), ``--model_path / --dtype / --batch / --unet_batch / --ngpu / --noise_dtype`` are additions of this build (the reference
+``style_main.py:24-196`` -- separate scripts there), ``--model_path / --dtype / --batch / --unet_batch / --ngpu / --noise_dtype / --mask_path`` are additions of this build (the reference
 hard-codes NAS checkpoint paths, ``cute_main.py:25-31``, fp16 and one GPU, ``cute_main.sh:1``).
 
 Multi-GPU (``--ngpu N``): the parent starts N rank processes before anything touches the GPU; triplets are sharded
@@ -61,6 +61,11 @@ def build_parser() -> argparse.ArgumentParser:
                         "order, as a one-tap run prints it.  SPEC: diffsim up_blocks:0, down_blocks:2, mid_blocks:0; diffsim_xl "
                         "up_blocks:0,1,9 (block, attention, transformer block), mid_blocks:0,5; dit blocks:13.  Layers are "
                         "explicit (no coercion of a single value to 0).  `all`: every tap the model can name")
+    p.add_argument("--mask_path", type=str, default=None, metavar="DIR",
+                   help="--dataset cute|nights: score the masked part of each image (region scores).  The mask of "
+                        "<image_path>/rel/name.ext is <DIR>/rel/name.png, else <DIR>/rel/name.ext (any mode; area-averaged onto the "
+                        "tap's token grid, a token on at >= 128); an image without a mask file is scored whole, and the run prints "
+                        "how many were.  Implies --use_mask")
     p.add_argument("--experiments", type=int, default=2000, help="--dataset sref: sampled experiments (style_main.py:64)")
     p.add_argument("--model_path", type=str, default=None, help="diffusers-layout checkpoint directory (unet/, vae/, text_encoder/, tokenizer/)")
     p.add_argument("--dtype", type=str, choices=["bf16", "fp16", "fp32"], default="bf16",
@@ -98,6 +103,11 @@ def arg_parse(argv=None):
             parse_tap_specs(args.taps, args.metric)
         except ValueError as e:
             p.error(f"--taps: {e}")
+    if args.mask_path is not None:
+        if args.dataset not in ("cute", "nights") or args.taps is not None:
+            p.error("--mask_path scores regions on the one-tap triplet benchmarks (--dataset cute or nights): a region score matrix "
+                    "(--dataset retrieval), --dataset sref and a region sweep (--taps) are not supported")
+        args.use_mask = True
     if args.save_maps and args.dataset != "retrieval":
         p.error("--save_maps writes the maps of the retrieval rankings: it needs --dataset retrieval")
     if args.save_matches and args.dataset != "retrieval":
@@ -320,11 +330,18 @@ def run(args) -> int:
                 print(f"Experiment on {block}, layer {tl}, timestep {args.target_step}:")
                 _report(args, trip, rows, s_ab[t], s_ac[t], bad[t])
     else:
+        masks = None
+        if args.mask_path is not None:
+            from .regions import triplet_mask_paths
+            masks, missing = triplet_mask_paths(trip, args.image_path, args.mask_path)
+            if rank == 0:
+                print(f"Region scores: masks from {args.mask_path}; {missing} image(s) without a mask file are scored whole")
         if args.selftest_shard:
             s_ab, s_ac, bad = _selftest_scores(trip, rank, world)
         else:
             s_ab, s_ac, bad = H.score_path_triplets(scorer, trip, args.image_size, args.target_block, layer, args.target_step,
-                                                    args.seed, args.similarity, rank, world, args.batch, args.unet_batch)
+                                                    args.seed, args.similarity, rank, world, args.batch, args.unet_batch,
+                                                    *(() if masks is None else (masks,)))
         if rank == 0:
             _report(args, trip, rows, s_ab, s_ac, bad)
     if world > 1:

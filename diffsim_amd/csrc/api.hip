@@ -1,5 +1,5 @@
 // The C ABI of libdiffsim_amd that belongs to no executor: version / status text / device count, the fused score tails (pairs,
-// matrices, maps, alignments) with their workspace queries, and the single-operator and launch-plan entry points (dsim_op_*, dsim_*_plan) the
+// matrices, maps, alignments, regions) with their workspace queries, and the single-operator and launch-plan entry points (dsim_op_*, dsim_*_plan) the
 // tests and micro-benchmarks drive.  The executors' own groups live beside their walks: dsim_unet_* in unet.hip, dsim_vae_* in
 // vae.hip, dsim_dit_* in dit.hip.
 #include <cstdio>
@@ -91,6 +91,23 @@ int dsim_pair_score_maps(const void* q, const void* k, const void* v, const int3
     if (!align_workspace(workspace, workspace_bytes)) return DSIM_ERR_WORKSPACE;
     return launch_pair_score_maps(q, k, v, idx_a, idx_b, n_pairs, B, H, N, D, dtype, similarity, score, local, contrib, status,
                                   workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+size_t dsim_pair_score_regions_workspace_bytes(int n_feat, int n_pairs, int B, int H, int N, int D) {
+    const size_t b = pair_score_regions_scratch_bytes(n_feat, n_pairs, B, H, N, D);
+    return b ? b + 256 : 0;
+}
+
+int dsim_pair_score_regions(const void* q, const void* k, const void* v, const uint8_t* mask, int n_feat, const int32_t* idx_a,
+                            const int32_t* idx_b, int n_pairs, int B, int H, int N, int D, int dtype, int similarity, float* out_scores,
+                            int32_t* status, int32_t* counts, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!q || !k || !v || !mask || !idx_a || !idx_b || !out_scores || !workspace) return DSIM_ERR_INVALID;
+    if (dtype != DSIM_F32 && dtype != DSIM_BF16 && dtype != DSIM_F16) return DSIM_ERR_INVALID;
+    if (similarity != 0 && similarity != 1) return DSIM_ERR_INVALID;
+    if (pair_score_regions_scratch_bytes(n_feat, n_pairs, B, H, N, D) == 0) return DSIM_ERR_INVALID;
+    if (!align_workspace(workspace, workspace_bytes)) return DSIM_ERR_WORKSPACE;
+    return launch_pair_score_regions(q, k, v, mask, n_feat, idx_a, idx_b, n_pairs, B, H, N, D, dtype, similarity, out_scores, status,
+                                     counts, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 size_t dsim_pair_align_workspace_bytes(int n_pairs, int B, int H, int N, int D) {

@@ -1,7 +1,8 @@
 // The tiled attention core for gfx950: one wave's 32 query rows against any number of keys (attend), with the Q fragments, the
-// O^T accumulators and the K / V staging it works on, and the host-side head-dim dispatch.  Shared by exactly three sources: the
-// attention kernels (attention.hip), the score tails (tails.hip) and the token alignments (align.hip: the configuration, fragments,
-// MFMA wrappers and head-dim dispatch, not attend); everything here lives in their dsim::(anonymous namespace).
+// O^T accumulators and the K / V staging it works on, and the host-side head-dim dispatch.  Shared by exactly four sources: the
+// attention kernels (attention.hip), the score tails (tails.hip), the region scores (regions.hip: attend over listed rows) and the
+// token alignments (align.hip: the configuration, fragments, MFMA wrappers and head-dim dispatch, not attend); everything here
+// lives in their dsim::(anonymous namespace).
 //
 // Tiling: a workgroup = 4 waves = 128 query rows of one (batch, head); each wave owns 32 rows and
 // sweeps the keys in 64-row tiles shared through LDS.
@@ -159,16 +160,28 @@ __device__ __forceinline__ void tile_init(StageRegs<T, D>& sr, char* lds, int ld
     }
 }
 
-template <typename T, int D>
-__device__ __forceinline__ void tile_load(StageRegs<T, D>& sr, const T* kb, const T* vb, int ldk, int kv0, int Nk) {
+// Which row of K and V key position j of an attention is.  RowsInOrder: row j, the contiguous rows every kernel but the region
+// tail reads (tile_load's code for it is the code it had before there was a choice).  RowsListed: row list[j], the ascending token
+// list of a region (regions.hip) -- one index load per staged chunk pair, and the chunk's column taken back out of goff.
+struct RowsInOrder { static constexpr bool LISTED = false; };
+struct RowsListed { static constexpr bool LISTED = true; const int32_t* list; };
+
+template <typename T, int D, typename Rows = RowsInOrder>
+__device__ __forceinline__ void tile_load(StageRegs<T, D>& sr, const T* kb, const T* vb, int ldk, int kv0, int Nk, Rows rows = Rows()) {
     typedef StageRegs<T, D> SR;
     const T* kt = kb + (size_t)kv0 * ldk;
     const T* vt = vb + (size_t)kv0 * ldk;
 #pragma unroll
     for (int i = 0; i < SR::N; ++i) {
         if (kv0 + sr.row[i] < Nk && sr.row[i] < KT) {
-            sr.k[i] = *reinterpret_cast<const u32x4*>(kt + sr.goff[i]);
-            sr.v[i] = *reinterpret_cast<const u32x4*>(vt + sr.goff[i]);
+            if constexpr (Rows::LISTED) {
+                const size_t o = (size_t)rows.list[kv0 + sr.row[i]] * ldk + (sr.goff[i] - (unsigned)sr.row[i] * (unsigned)ldk);
+                sr.k[i] = *reinterpret_cast<const u32x4*>(kb + o);
+                sr.v[i] = *reinterpret_cast<const u32x4*>(vb + o);
+            } else {
+                sr.k[i] = *reinterpret_cast<const u32x4*>(kt + sr.goff[i]);
+                sr.v[i] = *reinterpret_cast<const u32x4*>(vt + sr.goff[i]);
+            }
         }
     }
 }
@@ -192,9 +205,10 @@ __device__ __forceinline__ void tile_store(char* lds, const StageRegs<T, D>& sr,
 // invariant to the reference point, so a row whose true maximum lies above m just carries P > 1 and larger sums (f32 / h16
 // have the exponent range for it).  Only if the excess passes ~100 (log2 units) can exp2 overflow; the caller detects that from a
 // non-finite or absurd denominator and re-runs the block with FAST = false (attend_checked).
-template <typename T, int D, bool FAST = false>
+// Rows: which rows of kb / vb the Nk key positions are (RowsInOrder: rows 0 .. Nk - 1).
+template <typename T, int D, bool FAST = false, typename Rows = RowsInOrder>
 __device__ __forceinline__ void attend(const QFrags<T, D>& qfr, const T* kb, const T* vb, int ldk, int Nk, char* lds,
-                                       OAcc<T, D>& oacc, float* l_out = nullptr) {
+                                       OAcc<T, D>& oacc, float* l_out = nullptr, Rows rows = Rows()) {
     typedef ACfg<T, D> C;
     typedef typename FragOf<T>::type Frag;
     QFrags<T, D> qloc = qfr;    // (KONE writes -m into the spare d = D slot of its own copy)
@@ -215,7 +229,7 @@ __device__ __forceinline__ void attend(const QFrags<T, D>& qfr, const T* kb, con
     StageRegs<T, D> sr;
     __syncthreads();            // a previous attend() of this workgroup may still be reading the buffers
     tile_init<T, D>(sr, lds, ldk, Nk, tid);
-    if constexpr (C::PIPE) tile_load<T, D>(sr, kb, vb, ldk, 0, Nk);
+    if constexpr (C::PIPE) tile_load<T, D>(sr, kb, vb, ldk, 0, Nk, rows);
     __syncthreads();
     char* const lds0 = lds;
     for (int kt = 0; kt < ntiles; ++kt) {
@@ -224,10 +238,10 @@ __device__ __forceinline__ void attend(const QFrags<T, D>& qfr, const T* kb, con
             lds = lds0 + (kt & 1) * 2 * C::TILE;
             tile_store<T, D>(lds, sr, kt * KT, Nk);
             __syncthreads();
-            if (kt + 1 < ntiles) tile_load<T, D>(sr, kb, vb, ldk, (kt + 1) * KT, Nk);
+            if (kt + 1 < ntiles) tile_load<T, D>(sr, kb, vb, ldk, (kt + 1) * KT, Nk, rows);
         } else {
             __syncthreads();                               // previous tile fully consumed
-            tile_load<T, D>(sr, kb, vb, ldk, kt * KT, Nk);
+            tile_load<T, D>(sr, kb, vb, ldk, kt * KT, Nk, rows);
             tile_store<T, D>(lds, sr, kt * KT, Nk);
             __syncthreads();
         }

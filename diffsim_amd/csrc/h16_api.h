@@ -1,5 +1,5 @@
 // The host entry points of the sources that are compiled once per 16-bit type (gemm / gemm_skinny / rowres / attention / tails /
-// attn160 .hip).  Declarations only and no include guard: common.h includes this file inside `inline namespace DSIM_H16_NS`, the including
+// align / regions / attn160 .hip).  Declarations only and no include guard: common.h includes this file inside `inline namespace DSIM_H16_NS`, the including
 // object's own type, and the bf16 objects of the product build once more inside `namespace f16`, which declares the fp16 twins with
 // the same signatures and default arguments.  The argument structs and enums are plain dsim types (common.h, above the include).
 
@@ -53,6 +53,13 @@ size_t pair_align_scratch_bytes(int n_pairs, int B, int H, int N, int D);      /
 int launch_pair_align(const void* q, const void* k, const int32_t* idx_a, const int32_t* idx_b, int n_pairs, int B, int H, int N, int D,
                       int dtype, int grid_w, int32_t* match, float* weight, float* expect, float* attn, int32_t* status, void* scratch,
                       size_t scratch_bytes, hipStream_t s);
+// region scores: the score tail restricted to a token region per feature image (mask [n_feat][N] bytes, non-zero = on): the
+// tail's arithmetic on the regions' rows, taken through ascending token lists built on the device -- regions.hip
+//   out [n_pairs]; status (may be NULL) [n_pairs]: 0, 1 non-finite, 2 empty region; counts (may be NULL) [n_feat]
+size_t pair_score_regions_scratch_bytes(int n_feat, int n_pairs, int B, int H, int N, int D);      // 0: call not served
+int launch_pair_score_regions(const void* q, const void* k, const void* v, const uint8_t* mask, int n_feat, const int32_t* idx_a,
+                              const int32_t* idx_b, int n_pairs, int B, int H, int N, int D, int dtype, int similarity, float* out,
+                              int32_t* status, int32_t* counts, void* scratch, size_t scratch_bytes, hipStream_t s);
 // the same core as a plain SDPA (256 queries = 256 keys, head dim 160, 16-bit types): the U-Net's 16 x 16-level self-attentions
 bool sdpa160_applies(const AttnArgs& a);
 int launch_sdpa160(const AttnArgs& a, hipStream_t s);

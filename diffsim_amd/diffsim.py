@@ -25,7 +25,7 @@ from concurrent.futures import ThreadPoolExecutor
 import torch
 
 from . import scheduler as sched
-from . import align, maps, retrieval, sweep
+from . import align, maps, regions, retrieval, sweep
 from .config import SD15, UNetConfig
 from .engine import UNetEngine, _LatentDist, pair_score
 from .image import DecodePool, host_threads, load_image, process_image
@@ -367,6 +367,15 @@ class DiffSim(Scorer):
         :class:`~diffsim_amd.align.Alignment` of one pair (direction 0 on image_A's grid, 1 on image_B's)."""
         return align.score_path_pair_alignment(self, [(image_A, image_B)], img_size, prompt, target_block, _norm_layer(target_layer),
                                                target_step, seed)
+
+    @torch.no_grad()
+    def region_score(self, image_A, image_B, mask_A, mask_B, img_size, prompt, target_block, target_layer, target_step,
+                     seed="2333", similarity="cosine"):
+        """:meth:`diffsim` of the masked part of each image (regions.py): the score tail over the tokens of mask_A on image_A and
+        of mask_B on image_B alone.  A mask is a path, a PIL image, a bool array on the tap's token grid, or None (the whole
+        image); full masks give :meth:`diffsim`'s score.  Returns a (1,) tensor."""
+        return regions.score_path_pair_regions(self, [(image_A, image_B)], [(mask_A, mask_B)], img_size, prompt, target_block,
+                                               _norm_layer(target_layer), target_step, seed, similarity)
 
     @torch.no_grad()
     def score_latent_pair_alignment(self, latA, latB, noiseA, noiseB, prompt, target_block="up_blocks", target_layer=0,

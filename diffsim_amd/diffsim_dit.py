@@ -10,7 +10,7 @@ from typing import Dict, Optional
 
 import torch
 
-from . import align, maps, sweep
+from . import align, maps, regions, sweep
 from . import scheduler as sched
 from ._lib import DsimError
 from .config import DIT_XL2, DiTConfig
@@ -126,6 +126,14 @@ class diffsim_DiT(Scorer):
         pair)."""
         (latA, latB), nA, nB = path_latents(self, [(image_A, image_B)], (0, 1), img_size, seed, 1, hip_vae=False)
         return self.score_latent_pair_alignment(latA, latB, nA, nB, target_layer[0], target_step)
+
+    @torch.no_grad()
+    def region_score(self, image_A, image_B, mask_A, mask_B, img_size, prompt, target_block, target_layer, target_step, seed,
+                     similarity):
+        """:meth:`diffsim_score` of the masked part of each image (regions.py); a mask is a path, a PIL image, a bool array on the
+        token grid, or None (the whole image).  Returns a (1,) tensor."""
+        return regions.score_path_pair_regions(self, [(image_A, image_B)], [(mask_A, mask_B)], img_size, None, "none",
+                                               [int(target_layer[0])], target_step, seed, similarity, batch_pairs=32, hip_vae=False)
 
     @torch.no_grad()
     def score_latent_pair_alignment(self, latA, latB, noiseA, noiseB, target_layer: int, target_step: int, batch_pairs: int = 32):

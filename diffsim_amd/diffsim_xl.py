@@ -13,7 +13,7 @@ from typing import Callable, Dict, Optional, Tuple
 
 import torch
 
-from . import align, maps, sweep
+from . import align, maps, regions, sweep
 from . import scheduler as sched
 from .config import SDXL, UNetConfig
 from .engine import UNetEngine, pair_score
@@ -180,6 +180,14 @@ class diffsim_xl(Scorer):
         pair)."""
         latentsA, latentsB, noiseA, noiseB, ctx, pooled = self._path_pair_inputs(image_A, image_B, img_size, prompt, seed)
         return self.score_latent_pair_alignment(latentsA, latentsB, noiseA, noiseB, ctx, pooled, target_block, target_layer, target_step)
+
+    @torch.no_grad()
+    def region_score(self, image_A, image_B, mask_A, mask_B, img_size, prompt, target_block, target_layer, target_step, seed,
+                     similarity):
+        """:meth:`diffsim_score` of the masked part of each image (regions.py); a mask is a path, a PIL image, a bool array on the
+        tap's token grid, or None (the whole image).  Returns a (1,) tensor."""
+        return regions.score_path_pair_regions(self, [(image_A, image_B)], [(mask_A, mask_B)], img_size, prompt, target_block,
+                                               target_layer, target_step, seed, similarity, hip_vae=False)
 
     @torch.no_grad()
     def score_latent_pair_alignment(self, latA, latB, noiseA, noiseB, ctx, pooled, target_block, target_layer, target_step,

@@ -579,6 +579,40 @@ def pair_score_maps(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, idx_a: to
     return (score, local, contrib, status) if return_status else (score, local, contrib)
 
 
+def pair_score_regions(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: torch.Tensor, idx_a: torch.Tensor,
+                       idx_b: torch.Tensor, heads: int, similarity: str = "cosine", return_status: bool = False,
+                       return_counts: bool = False):
+    """The score tail restricted to a token region per feature image (dsim_pair_score_regions).  q,k,v: [n_feat][B][N][H*D];
+    mask: bool or uint8 cuda (n_feat, N), non-zero = the token is in its image's region; idx: int32 cuda [n_pairs].  Pair p's
+    score is pair_score's on the rows of the two regions alone (ascending token order): the off tokens are neither queries nor
+    keys.  Returns the f32 (n,) scores; return_status: also an int32 (n,) tensor, 1 where the score is NaN / infinite, 2 where
+    a region of the pair is empty (score NaN); return_counts: also the int32 (n_feat,) region sizes."""
+    L = _lib.lib()
+    _require_cuda(q, k, v, mask, idx_a, idx_b)
+    if similarity not in ("cosine", "mse"):
+        raise ValueError(similarity)
+    B, N, D = _check_features((q, k, v), heads, k.shape == q.shape == v.shape, _PAIR_MSGS, (idx_a, idx_b))
+    if mask.dtype not in (torch.bool, torch.uint8):
+        raise _lib.DsimError("the region mask must be bool or uint8")
+    if tuple(mask.shape) != (q.shape[0], N):
+        raise _lib.DsimError(f"the region mask must be (n_feat, N) = ({q.shape[0]}, {N}): {tuple(mask.shape)}")
+    mask = mask.view(torch.uint8)
+    n_feat, n_pairs = q.shape[0], idx_a.numel()
+    out = torch.empty(n_pairs, dtype=torch.float32, device=q.device)
+    status = torch.empty(n_pairs, dtype=torch.int32, device=q.device) if return_status else None
+    counts = torch.empty(n_feat, dtype=torch.int32, device=q.device) if return_counts else None
+    with torch.cuda.device(q.device):
+        wsb = int(L.dsim_pair_score_regions_workspace_bytes(n_feat, n_pairs, B, heads, N, D))
+        if wsb == 0:
+            raise _lib.DsimError(f"no region scores for n_feat={n_feat} n_pairs={n_pairs} B={B} H={heads} N={N} D={D}")
+        ws = torch.empty(wsb, dtype=torch.uint8, device=q.device)
+        _lib.check(L.dsim_pair_score_regions(q.data_ptr(), k.data_ptr(), v.data_ptr(), mask.data_ptr(), n_feat, idx_a.data_ptr(),
+                                             idx_b.data_ptr(), n_pairs, B, heads, N, D, _TORCH2DSIM[q.dtype],
+                                             0 if similarity == "cosine" else 1, out.data_ptr(), _ptr(status), _ptr(counts),
+                                             ws.data_ptr(), wsb, _stream_ptr()), "dsim_pair_score_regions")
+    return out if not (return_status or return_counts) else (out,) + ((status,) if return_status else ()) + ((counts,) if return_counts else ())
+
+
 _ATTN_BYTES = (1 << 31) - 1          # dsim_pair_align refuses an attention tensor of 2 GiB or more: the pairs are chunked
 _ALIGN_PAIRS = 32767                 # ... and more pairs than its grid holds (two directions per pair, 65535 in all)
 

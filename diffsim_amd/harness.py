@@ -21,7 +21,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import torch
 
-from .engine import pair_score
+from .engine import pair_score, pair_score_regions
 from .inputs import path_latents
 from .parallel import gather_scores, shard_triplets
 from .scorer import stack_rows
@@ -73,11 +73,12 @@ def cute_accuracy(s_ab: torch.Tensor, s_ac: torch.Tensor) -> float:
 
 
 @torch.no_grad()
-def triplet_chunks(scorer, ref, left, right, nA, nB, prompt, heads, similarity, batch_triplets: int, feats):
+def triplet_chunks(scorer, ref, left, right, nA, nB, prompt, heads, similarity, batch_triplets: int, feats, masks=None):
     """(ref,left) and (ref,right) scores of latent triplets at every tap of a forward: 3 forwards per triplet (the reference
     image's features are shared), chunked engine batches, one fused tail launch per chunk and tap.  feats(lat, nz, prompt) ->
-    [(q, k, v) per tap] is the forward of one engine batch, heads[t] tap t's head count.  Returns the (nt, n) scores of both
-    sides and the (nt,) NaN / inf counts."""
+    [(q, k, v) per tap] is the forward of one engine batch, heads[t] tap t's head count.  masks: None, or the (ref, left, right)
+    token masks, each (n, N) bool on the device: the region tail (regions.py) over each chunk's rows instead of the pair tail.
+    Returns the (nt, n) scores of both sides and the (nt,) NaN / inf counts."""
     n, nt, dev = ref.shape[0], len(heads), scorer.device
     s_l = torch.empty((nt, n), dtype=torch.float32, device=dev)
     s_r = torch.empty((nt, n), dtype=torch.float32, device=dev)
@@ -89,31 +90,42 @@ def triplet_chunks(scorer, ref, left, right, nA, nB, prompt, heads, similarity, 
         base = torch.arange(0, 3 * m, 3, dtype=torch.int32, device=dev)
         ia, ib = torch.cat([base, base]), torch.cat([base + 1, base + 2])
         for t, (q, k, v) in enumerate(fs):
-            s, st = pair_score(q, k, v, ia, ib, heads[t], similarity, return_status=True)
+            if masks is None:
+                s, st = pair_score(q, k, v, ia, ib, heads[t], similarity, return_status=True)
+            else:                                           # (the chunk's mask rows lie as its images do: ref, left, right)
+                rows = torch.stack([mk[i0:i1] for mk in masks], dim=1).reshape(3 * m, -1).contiguous()
+                s, st = pair_score_regions(q, k, v, rows, ia, ib, heads[t], similarity, return_status=True)
+                st = (st != 0).to(torch.int32)
             bad[t] += st.sum()
             s_l[t, i0:i1], s_r[t, i0:i1] = s[:m], s[m:]
     return s_l, s_r, bad
 
 
-def _score_chunks(scorer, ref, left, right, nA, nB, prompt, block, layer, step, similarity, batch_triplets):
-    """triplet_chunks at the one tap (block, layer): each engine batch is one ``tap_features`` call."""
+def _score_chunks(scorer, ref, left, right, nA, nB, prompt, block, layer, step, similarity, batch_triplets, masks=None):
+    """triplet_chunks at the one tap (block, layer): each engine batch is one ``tap_features`` call.  masks: None, or one
+    (ref, left, right) triple of masks per triplet (``regions.as_token_mask``), put on the tap's token grid here."""
     n = ref.shape[0]
     tap = scorer.tap_of(block, layer)
+    if masks is not None:
+        from .regions import as_token_mask, tap_grid
+        grid = tap_grid(scorer, tap, ref.shape[-1])
+        masks = [torch.stack([as_token_mask(mk[c], grid) for mk in masks]).flatten(1).to(scorer.device) for c in range(3)]
     prompt = scorer.bind_prompt(prompt, n)
     eng = scorer.engine_at(tap)
     heads = eng.heads
     if batch_triplets is None:
         batch_triplets = scorer.auto_rows(eng, n, 3, n_ctx=scorer.n_ctx(prompt))
     return triplet_chunks(scorer, ref, left, right, nA, nB, prompt, [heads], similarity, batch_triplets,
-                          lambda lat, nz, p: [scorer.tap_features(lat, nz, p, tap, step)])
+                          lambda lat, nz, p: [scorer.tap_features(lat, nz, p, tap, step)], *(() if masks is None else (masks,)))
 
 
 @torch.no_grad()
 def path_triplet_scores(scorer, triplets: Sequence[Tuple[str, str, str, str]], img_size: int, seed, rank: int, world: int,
-                        batch_triplets: int, nt: int, score):
+                        batch_triplets: int, nt: int, score, masks=None):
     """The skeleton of the path triplet runs: whole triplets sharded over ranks (the cached reference-image features stay
     local), grouped by ``Scorer.group_key``, each group's images through ``path_latents`` in chunks of batch_triplets and
     its latents through score(ref, left, right, nA, nB, prompt) -> (nt, n) scores of both sides and (nt,) NaN / inf counts.
+    masks: None, or one entry per triplet; score then takes the group's entries as a seventh argument.
     Returns (s_ab, s_ac), each (nt, len(triplets)) on every rank, and the (nt,) counts summed over ranks."""
     n, dev = len(triplets), scorer.device
     sl, sr, order = [], [], []
@@ -127,7 +139,7 @@ def path_triplet_scores(scorer, triplets: Sequence[Tuple[str, str, str, str]], i
         prompt = scorer.group_prompt([triplets[j][3] for j in idxs])
         (ref, left, right), nA, nB = path_latents(scorer, [triplets[j][:3] for j in idxs], (0, 1, 1), img_size, seed,
                                                   batch_triplets)
-        a_, b_, bad = score(ref, left, right, nA, nB, prompt)
+        a_, b_, bad = score(ref, left, right, nA, nB, prompt, *(() if masks is None else ([masks[j] for j in idxs],)))
         nbad += bad
         sl.append(a_); sr.append(b_); order += idxs
     if order:
@@ -145,7 +157,7 @@ def path_triplet_scores(scorer, triplets: Sequence[Tuple[str, str, str, str]], i
 
 def score_path_triplets(scorer, triplets: Sequence[Tuple[str, str, str, str]], img_size: int, target_block, target_layer,
                         target_step, seed=2333, similarity="cosine", rank: int = 0, world: int = 1, batch_triplets: int = 10,
-                        unet_triplets: Optional[int] = None):
+                        unet_triplets: Optional[int] = None, masks: Optional[Sequence] = None):
     """Scores s(A,B) and s(A,C) of every (A, B, C, prompt) path triplet -- the two scorer calls per triplet the
     reference's loops make (cute_main.py:111-132, night_main.py:69-90, style_main.py:150-175) -- for all three scorer
     kinds (DiffSim, diffsim_xl, diffsim_DiT): whole triplets sharded over ranks (the cached reference-image features stay
@@ -153,12 +165,19 @@ def score_path_triplets(scorer, triplets: Sequence[Tuple[str, str, str, str]], i
 
     Host work is only decode + Lanczos resize, on a thread pool that runs two chunks ahead of the GPU; the /255,
     (x-0.5)/0.5, NCHW and fp16-cast arithmetic of process_image and the posterior sampling run on the device
-    (dsim_image_preprocess / dsim_latent_sample), bit-identically to the per-pair path.  Returns (s_ab, s_ac, n_nonfinite):
+    (dsim_image_preprocess / dsim_latent_sample), bit-identically to the per-pair path.  masks: None, or one (ref, left, right)
+    triple per triplet of mask paths, PIL images, bool arrays on the tap's token grid or None (the whole image): region scores
+    (regions.py), what ``region_score(A, B, mask_A, mask_B, ...)`` and ``region_score(A, C, mask_A, mask_C, ...)`` return;
+    with masks=None every call and launch is the unmasked run's.  Returns (s_ab, s_ac, n_nonfinite):
     length-len(triplets) f32 tensors on every rank and the number of NaN/inf pair scores (NaN guard)."""
     # (batch_triplets sizes the decode / VAE-encode chunks; the U-Net batch is unet_triplets, or the scorer's auto_rows)
+    if masks is not None and len(masks) != len(triplets):
+        raise ValueError(f"{len(masks)} mask triples for {len(triplets)} triplets")
     all_l, all_r, nbad = path_triplet_scores(
         scorer, triplets, img_size, seed, rank, world, batch_triplets, 1,
-        lambda *lat_prompt: _score_chunks(scorer, *lat_prompt, target_block, target_layer, target_step, similarity, unet_triplets))
+        lambda *lat_prompt: _score_chunks(scorer, *lat_prompt[:6], target_block, target_layer, target_step, similarity, unet_triplets,
+                                          *lat_prompt[6:]),
+        *(() if masks is None else (masks,)))
     return all_l[0], all_r[0], int(nbad)
 
 

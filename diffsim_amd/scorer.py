@@ -215,9 +215,10 @@ class Scorer:
     def taps_features(self, lat, nz, prompt, taps, step):
         return self.features_taps(lat, nz, prompt, taps, step)
 
-    def pair_chunks(self, latA, latB, noiseA, noiseB, prompt, tap, step, similarity, batch_pairs: int, tail):
+    def pair_chunks(self, latA, latB, noiseA, noiseB, prompt, tap, step, similarity, batch_pairs: int, tail, tail_of=None):
         """Yields (i0, i1, tail(q, k, v, idx_a, idx_b, heads, similarity)) for the pairs (latA[i] in slot A, latB[i] in slot B) in
-        engine batches of batch_pairs; tail: engine.pair_score or engine.pair_score_maps."""
+        engine batches of batch_pairs; tail: engine.pair_score or engine.pair_score_maps.  tail_of(i0, i1), when given, returns
+        the tail of that chunk instead (regions.py binds each chunk's mask rows, which lie as its images do: A0, B0, A1, B1, ...)."""
         n = latA.shape[0]
         eng = self.engine_at(tap)
         heads = eng.heads
@@ -229,4 +230,4 @@ class Scorer:
             q, k, v = self.tap_features(*stack_rows([latA, latB], [noiseA, noiseB], i0, i1), self.chunk_prompt(prompt, i0, i1, 2),
                                         tap, step)
             ia = torch.arange(0, 2 * (i1 - i0), 2, dtype=torch.int32, device=self.device)
-            yield i0, i1, tail(q, k, v, ia, ia + 1, heads, similarity)
+            yield i0, i1, (tail if tail_of is None else tail_of(i0, i1))(q, k, v, ia, ia + 1, heads, similarity)

@@ -296,6 +296,32 @@ int    dsim_pair_align(const void* q, const void* k, const int32_t* idx_a, const
                        int32_t* match, float* weight, float* expect, float* attn, int32_t* status,
                        void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- region scores: the score restricted to a token region per image --------------------------------------
+ * Every feature image i carries a token region R_i, a subset of its N tokens, given as a byte mask (non-zero = on).  The region
+ * score of pair p (a = idx_a[p], b = idx_b[p]) is dsim_pair_score's tail applied to the sub-tensors Q_a[:, :, R_a, :], K_a[R_a],
+ * V_a[R_a] and Q_b[R_b], K_b[R_b], V_b[R_b], rows in ascending token order:
+ *   direction a->b: O_ab = SDPA(Q_a[R_a], K_b[R_b], V_b[R_b]),  O_aa = SDPA(Q_a[R_a], K_a[R_a], V_a[R_a]), both rounded to the
+ *   pipeline dtype as dsim_pair_score rounds them; cosine over the flattened (B, H, |R_a|, D) tensors (eps 1e-8), or mse
+ *   dividing by B H |R_a| D; direction b->a is the mirror over R_b; the score is the mean of the two directions.
+ * The softmax scale stays 1/sqrt(D).  With every region full this is the pair score.  Off tokens are neither queries nor keys:
+ * their rows are never read.
+ *   q,k,v, idx_a, idx_b, similarity : as dsim_pair_score (index entries are not range-checked)
+ *   mask        : device uint8 [n_feat][N]
+ *   out_scores  : device f32 [n_pairs]
+ *   status      : NULL, or device int32 [n_pairs]: 0, 1 where the score is NaN or infinite, 2 where a region of the pair is
+ *                 empty (the score is then NaN; the other pairs of the call are not affected)
+ *   counts      : NULL, or device int32 [n_feat]: |R_i|
+ * Deterministic, no atomics.  A pair's value does not depend on the other pairs of the call, nor on anything outside its two
+ * regions: not on the off tokens' features, and not on where in the image the region's rows lie.
+ * DSIM_ERR_INVALID (workspace query: 0) for a bad dtype, similarity or head dim, n_pairs < 1, n_feat < 1, 2 n_pairs > 65535 or
+ * B H > 65535; DSIM_ERR_WORKSPACE for a short workspace; both are decided on the host before anything is enqueued. */
+size_t dsim_pair_score_regions_workspace_bytes(int n_feat, int n_pairs, int B, int H, int N, int D);
+int    dsim_pair_score_regions(const void* q, const void* k, const void* v, const uint8_t* mask /* [n_feat][N] */,
+                               int n_feat, const int32_t* idx_a, const int32_t* idx_b, int n_pairs,
+                               int B, int H, int N, int D, int dtype, int similarity,
+                               float* out_scores, int32_t* status /* NULL or [n_pairs]: 0, 1 non-finite, 2 empty region */,
+                               int32_t* counts /* NULL or [n_feat] */, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- VAE encoder: replaces `pipe.vae.encode(image)` in
  *      DiffSim.prepare_image_latents (diffsim/diffsim.py:92-96).  Sampling
  *      z = mean + exp(0.5*clamp(logvar,-30,20))*eps and the 0.18215 scaling stay with the caller,
