@@ -172,6 +172,10 @@ SYMBOLS = {
     "dsim_pair_score_maps": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dsim_pair_align_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "dsim_pair_align": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dsim_unet_text_workspace_bytes": (_sz, [_vp, _i, _i]),
+    "dsim_unet_qkv_text": (_i, [_vp, _vp, _vp, _f, _f, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dsim_text_attention_workspace_bytes": (_sz, [_i, _i, _i]),
+    "dsim_text_attention": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dsim_pair_score_regions_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
     "dsim_pair_score_regions": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dsim_op_linear": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),

@@ -4,7 +4,7 @@
 
 Flags of the reference drivers (``/root/reference/argprocess.py:5-18``) keep their names, meaning and defaults;
 ``--dataset`` selects which of the reference's loops runs (``cute_main.py:48-226``, ``night_main.py:24-173`` or
-``style_main.py:24-196`` -- separate scripts there), ``--model_path / --dtype / --batch / --unet_batch / --ngpu / --noise_dtype / --mask_path`` are additions of this build (the reference
+``style_main.py:24-196`` -- separate scripts there), ``--model_path / --dtype / --batch / --unet_batch / --ngpu / --noise_dtype / --mask_path / --text_attn / --text_threshold`` are additions of this build (the reference
 hard-codes NAS checkpoint paths, ``cute_main.py:25-31``, fp16 and one GPU, ``cute_main.sh:1``).
 
 Multi-GPU (``--ngpu N``): the parent starts N rank processes before anything touches the GPU; triplets are sharded
@@ -66,6 +66,14 @@ def build_parser() -> argparse.ArgumentParser:
                         "<image_path>/rel/name.ext is <DIR>/rel/name.png, else <DIR>/rel/name.ext (any mode; area-averaged onto the "
                         "tap's token grid, a token on at >= 128); an image without a mask file is scored whole, and the run prints "
                         "how many were.  Implies --use_mask")
+    p.add_argument("--text_attn", type=str, nargs="*", default=None, metavar="WORD",
+                   help="--dataset cute|nights, --metric diffsim|diffsim_xl: score the part of each image the prompt names "
+                        "(text-guided regions).  Each image's region is the tokens whose cross-attention to the WORDs of its row's "
+                        "prompt (no WORD: every content token of the prompt) is at least --text_threshold x the image's mean; the "
+                        "run prints the mean share of tokens on.  Implies --use_text_attn")
+    p.add_argument("--text_threshold", type=float, default=1.0,
+                   help="--text_attn: a token is in its image's region at >= this multiple of the image's mean text saliency "
+                        "(0: every token; a region with no token on is the whole image)")
     p.add_argument("--experiments", type=int, default=2000, help="--dataset sref: sampled experiments (style_main.py:64)")
     p.add_argument("--model_path", type=str, default=None, help="diffusers-layout checkpoint directory (unet/, vae/, text_encoder/, tokenizer/)")
     p.add_argument("--dtype", type=str, choices=["bf16", "fp16", "fp32"], default="bf16",
@@ -108,6 +116,15 @@ def arg_parse(argv=None):
             p.error("--mask_path scores regions on the one-tap triplet benchmarks (--dataset cute or nights): a region score matrix "
                     "(--dataset retrieval), --dataset sref and a region sweep (--taps) are not supported")
         args.use_mask = True
+    if args.text_attn is not None:
+        if args.dataset not in ("cute", "nights") or args.taps is not None or args.mask_path is not None:
+            p.error("--text_attn scores text-guided regions on the one-tap triplet benchmarks (--dataset cute or nights): "
+                    "--dataset retrieval, --dataset sref, a sweep (--taps) and mask files (--mask_path) are not supported with it")
+        if args.metric == "dit":
+            p.error("--text_attn: --metric dit has no text conditioning (a class-conditional model without cross-attention)")
+        if not (args.text_threshold >= 0.0) or args.text_threshold == float("inf"):
+            p.error("--text_threshold must be finite and >= 0")
+        args.use_text_attn = True
     if args.save_maps and args.dataset != "retrieval":
         p.error("--save_maps writes the maps of the retrieval rankings: it needs --dataset retrieval")
     if args.save_matches and args.dataset != "retrieval":
@@ -336,13 +353,22 @@ def run(args) -> int:
             masks, missing = triplet_mask_paths(trip, args.image_path, args.mask_path)
             if rank == 0:
                 print(f"Region scores: masks from {args.mask_path}; {missing} image(s) without a mask file are scored whole")
+        guide = None
+        if args.text_attn is not None and not args.selftest_shard:
+            from .textattn import TextGuide
+            guide = TextGuide(args.text_attn, args.text_threshold)
+            if rank == 0:
+                print(f"Text-guided regions: {'the words ' + ' '.join(args.text_attn) if args.text_attn else 'every content token'} "
+                      f"of each prompt, threshold {args.text_threshold:g} x the mean saliency")
         if args.selftest_shard:
             s_ab, s_ac, bad = _selftest_scores(trip, rank, world)
         else:
             s_ab, s_ac, bad = H.score_path_triplets(scorer, trip, args.image_size, args.target_block, layer, args.target_step,
                                                     args.seed, args.similarity, rank, world, args.batch, args.unet_batch,
-                                                    *(() if masks is None else (masks,)))
+                                                    *(() if masks is None else (masks,)), **({} if guide is None else {"text": guide}))
         if rank == 0:
+            if guide is not None:
+                print(f"Mean share of tokens on: {guide.on_fraction * 100:.2f}%")
             _report(args, trip, rows, s_ab, s_ac, bad)
     if world > 1:
         import torch.distributed as dist

@@ -16,7 +16,7 @@ namespace {
 // 16 bits between the inputs and Pm.  The score tail's attend pre-scales Q and rounds it to the compute dtype (load_q), so its
 // probabilities differ from these in the last bits.
 //
-// Two passes, one logit routine (align_logits: both take s from the same MFMA sequence on the same operands):
+// Two passes, one logit routine (align_logits, attn_core.h: both take s from the same MFMA sequence on the same operands):
 //   align_stats_kernel  one workgroup per (query tile, b h, pair, direction): the row's final maximum m and denominator
 //                       l = sum_j exp2(fma(s, c, -m c)) (online over the key tiles), stored as (-m c, 1 / l): the workspace,
 //                       [pair][dir][bh][N] float2, is all that reaches HBM besides the outputs;
@@ -32,22 +32,6 @@ template <typename T, int D> struct AlignRegs {
     static constexpr int N = (KT * CPRD + 255) / 256;
     u32x4 k[N];
 };
-
-// this lane's query row as un-scaled fragments (d >= D: zeros)
-template <typename T, int D>
-__device__ __forceinline__ void align_load_q(QFrags<T, D>& qf, const T* qrow, int half) {
-#pragma unroll
-    for (int ks = 0; ks < ACfg<T, D>::NKS; ++ks) {
-        const int d0 = 16 * ks + 8 * half;
-        if (d0 < D) {
-            if constexpr (sizeof(T) == 2) qf.f[ks] = *reinterpret_cast<const h16x8*>(qrow + d0);
-            else {
-                qf.f[ks].lo = *reinterpret_cast<const f32x4*>(qrow + d0);
-                qf.f[ks].hi = *reinterpret_cast<const f32x4*>(qrow + d0 + 4);
-            }
-        } else zero_frag(qf.f[ks]);
-    }
-}
 
 // the D real columns of key rows kv0 .. kv0 + 63 (those < Nk) of one (image, b, h): global -> registers, registers -> the LDS tile
 // (ACfg's K row stride; the padding columns and the never-stored rows keep the zeros of align_zero_tile or stale finite values
@@ -76,27 +60,6 @@ __device__ __forceinline__ void align_zero_tile(char* lds, int tid) {
     const u32x4 z = {0u, 0u, 0u, 0u};
     for (int o = tid * 16; o < ACfg<T, D>::TILEK; o += 256 * 16) *reinterpret_cast<u32x4*>(lds + o) = z;
 }
-
-// S^T = K Q^T of 32-key block jb of the staged tile against this wave's 32 query rows, raw (no scale, accumulators from 0):
-// s[r] = Q[lane & 31] . K[jb * 32 + (r & 3) + 8 (r >> 2) + 4 half].  The one logit routine of both passes.
-template <typename T, int D>
-__device__ __forceinline__ f32x16 align_logits(const QFrags<T, D>& qf, const char* lds, int jb, int l31, int half) {
-    typedef ACfg<T, D> C;
-    f32x16 s;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) s[r] = 0.f;
-    const char* krow = lds + (jb * 32 + l31) * C::RS + half * 8 * C::ES;
-#pragma unroll
-    for (int ks = 0; ks < C::NKS; ++ks) {
-        typename FragOf<T>::type kf;
-        lload_frag(kf, krow + ks * 16 * C::ES);
-        mma(kf, qf.f[ks], s);
-    }
-    return s;
-}
-
-// the key of accumulator slot (jb, r) in this lane's half
-__device__ __forceinline__ int align_key(int jb, int r, int half) { return jb * 32 + (r & 3) + 8 * (r >> 2) + 4 * half; }
 
 // pass 1.  grid (ceil(N/128), B*H, n_pairs*2)
 template <typename T, int D>

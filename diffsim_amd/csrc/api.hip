@@ -1,5 +1,5 @@
 // The C ABI of libdiffsim_amd that belongs to no executor: version / status text / device count, the fused score tails (pairs,
-// matrices, maps, alignments, regions) with their workspace queries, and the single-operator and launch-plan entry points (dsim_op_*, dsim_*_plan) the
+// matrices, maps, alignments, regions, text attention) with their workspace queries, and the single-operator and launch-plan entry points (dsim_op_*, dsim_*_plan) the
 // tests and micro-benchmarks drive.  The executors' own groups live beside their walks: dsim_unet_* in unet.hip, dsim_vae_* in
 // vae.hip, dsim_dit_* in dit.hip.
 #include <cstdio>
@@ -123,6 +123,21 @@ int dsim_pair_align(const void* q, const void* k, const int32_t* idx_a, const in
     if (!align_workspace(workspace, workspace_bytes)) return DSIM_ERR_WORKSPACE;
     return launch_pair_align(q, k, idx_a, idx_b, n_pairs, B, H, N, D, dtype, grid_w, match, weight, expect, attn, status, workspace,
                              workspace_bytes, (hipStream_t)stream);
+}
+
+size_t dsim_text_attention_workspace_bytes(int n_images, int N, int L) {
+    const size_t b = text_attention_scratch_bytes(n_images, N, L);
+    return b ? b + 256 : 0;
+}
+
+int dsim_text_attention(const void* xq, int ldq, const void* xk, int ldk, int n_images, int n_kv, int H, int N, int L, int D, int dtype,
+                        const float* token_weight, int n_w, float rel_threshold, float* attn, float* saliency, uint8_t* mask,
+                        int32_t* counts, int32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!xq || !xk || !workspace) return DSIM_ERR_INVALID;
+    if (text_attention_scratch_bytes(n_images, N, L) == 0) return DSIM_ERR_INVALID;
+    if (!align_workspace(workspace, workspace_bytes)) return DSIM_ERR_WORKSPACE;
+    return launch_text_attention(xq, ldq, xk, ldk, n_images, n_kv, H, N, L, D, dtype, token_weight, n_w, rel_threshold, attn, saliency,
+                                 mask, counts, status, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 // ---- single-operator entry points (tests / micro-benchmarks; these allocate and synchronise) ----

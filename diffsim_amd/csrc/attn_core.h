@@ -1,8 +1,9 @@
 // The tiled attention core for gfx950: one wave's 32 query rows against any number of keys (attend), with the Q fragments, the
-// O^T accumulators and the K / V staging it works on, and the host-side head-dim dispatch.  Shared by exactly four sources: the
-// attention kernels (attention.hip), the score tails (tails.hip), the region scores (regions.hip: attend over listed rows) and the
-// token alignments (align.hip: the configuration, fragments, MFMA wrappers and head-dim dispatch, not attend); everything here
-// lives in their dsim::(anonymous namespace).
+// O^T accumulators and the K / V staging it works on, and the host-side head-dim dispatch.  Shared by exactly five sources: the
+// attention kernels (attention.hip), the score tails (tails.hip), the region scores (regions.hip: attend over listed rows), the
+// token alignments (align.hip) and the text attention maps (textattn.hip) -- the last two take the configuration, fragments, MFMA
+// wrappers, head-dim dispatch and the un-rescaled logit routine, not attend; everything here lives in their dsim::(anonymous
+// namespace).
 //
 // Tiling: a workgroup = 4 waves = 128 query rows of one (batch, head); each wave owns 32 rows and
 // sweeps the keys in 64-row tiles shared through LDS.
@@ -383,6 +384,45 @@ __device__ __forceinline__ void attend(const QFrags<T, D>& qfr, const T* kb, con
 #pragma unroll
         for (int r = 0; r < 16; ++r) o[db][r] *= inv;
 }
+
+// ---- un-rescaled logits (align.hip, textattn.hip): S^T = K Q^T from the stored values, the softmax scale applied in f32 afterwards ----
+// this lane's query row as un-scaled fragments (d >= D: zeros)
+template <typename T, int D>
+__device__ __forceinline__ void align_load_q(QFrags<T, D>& qf, const T* qrow, int half) {
+#pragma unroll
+    for (int ks = 0; ks < ACfg<T, D>::NKS; ++ks) {
+        const int d0 = 16 * ks + 8 * half;
+        if (d0 < D) {
+            if constexpr (sizeof(T) == 2) qf.f[ks] = *reinterpret_cast<const h16x8*>(qrow + d0);
+            else {
+                qf.f[ks].lo = *reinterpret_cast<const f32x4*>(qrow + d0);
+                qf.f[ks].hi = *reinterpret_cast<const f32x4*>(qrow + d0 + 4);
+            }
+        } else zero_frag(qf.f[ks]);
+    }
+}
+
+// S^T = K Q^T of 32-key block jb of the staged tile against this wave's 32 query rows, raw (no scale, accumulators from 0):
+// s[r] = Q[lane & 31] . K[jb * 32 + (r & 3) + 8 (r >> 2) + 4 half].  The one logit routine of align.hip's two passes and of
+// text_attn_kernel (which stages up to four blocks, 128 keys).
+template <typename T, int D>
+__device__ __forceinline__ f32x16 align_logits(const QFrags<T, D>& qf, const char* lds, int jb, int l31, int half) {
+    typedef ACfg<T, D> C;
+    f32x16 s;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) s[r] = 0.f;
+    const char* krow = lds + (jb * 32 + l31) * C::RS + half * 8 * C::ES;
+#pragma unroll
+    for (int ks = 0; ks < C::NKS; ++ks) {
+        typename FragOf<T>::type kf;
+        lload_frag(kf, krow + ks * 16 * C::ES);
+        mma(kf, qf.f[ks], s);
+    }
+    return s;
+}
+
+// the key of accumulator slot (jb, r) in this lane's half
+__device__ __forceinline__ int align_key(int jb, int r, int half) { return jb * 32 + (r & 3) + 8 * (r >> 2) + 4 * half; }
 
 inline float scale_log2_of(int D) { return (1.0f / sqrtf((float)D)) * 1.4426950408889634f; }
 

@@ -1,5 +1,5 @@
 // The host entry points of the sources that are compiled once per 16-bit type (gemm / gemm_skinny / rowres / attention / tails /
-// align / regions / attn160 .hip).  Declarations only and no include guard: common.h includes this file inside `inline namespace DSIM_H16_NS`, the including
+// align / regions / textattn / attn160 .hip).  Declarations only and no include guard: common.h includes this file inside `inline namespace DSIM_H16_NS`, the including
 // object's own type, and the bf16 objects of the product build once more inside `namespace f16`, which declares the fp16 twins with
 // the same signatures and default arguments.  The argument structs and enums are plain dsim types (common.h, above the include).
 
@@ -60,6 +60,15 @@ size_t pair_score_regions_scratch_bytes(int n_feat, int n_pairs, int B, int H, i
 int launch_pair_score_regions(const void* q, const void* k, const void* v, const uint8_t* mask, int n_feat, const int32_t* idx_a,
                               const int32_t* idx_b, int n_pairs, int B, int H, int N, int D, int dtype, int similarity, float* out,
                               int32_t* status, int32_t* counts, void* scratch, size_t scratch_bytes, hipStream_t s);
+// text attention maps: the tapped block's cross-attention on the conditional CFG half, averaged over the heads; its weighted sum over
+// the prompt tokens (saliency) and the token region above rel_threshold x the image's mean saliency (text_attn_kernel,
+// text_region_kernel, any head dim and dtype, 1 <= L <= 128) -- textattn.hip
+//   xq [n_images][2][N] rows of ldq; xk [n_kv][L] rows of ldk (n_kv = 2 or 2 n_images); weight f32 [n_w][L] (n_w = 1 or n_images)
+//   attn [n_images][N][L]; saliency [n_images][N]; mask [n_images][N] bytes; counts, status [n_images]; each may be NULL
+size_t text_attention_scratch_bytes(int n_images, int N, int L);      // 0: shape not served
+int launch_text_attention(const void* xq, int ldq, const void* xk, int ldk, int n_images, int n_kv, int H, int N, int L, int D, int dtype,
+                          const float* weight, int n_w, float rel_threshold, float* attn, float* saliency, uint8_t* mask, int32_t* counts,
+                          int32_t* status, void* scratch, size_t scratch_bytes, hipStream_t s);
 // the same core as a plain SDPA (256 queries = 256 keys, head dim 160, 16-bit types): the U-Net's 16 x 16-level self-attentions
 bool sdpa160_applies(const AttnArgs& a);
 int launch_sdpa160(const AttnArgs& a, hipStream_t s);

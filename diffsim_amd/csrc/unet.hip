@@ -75,6 +75,11 @@ struct Walk : WalkBase<dsim_unet> {
     int n_ctx = 1;              // prompt contexts of the call: > 1 = a table of [uncond, cond] pairs, one row per image
     const int32_t* ctx_index = nullptr;     // device int32 [images]: each image's row of the table (n_ctx > 1)
     bool mixed() const { return n_ctx > 1; }
+    // the text request (dsim_unet_qkv_text, an own-tap walk): the walk does not stop at the tap but runs the block on to its
+    // cross-attention's query and K | V projection, written here
+    void* text_xq = nullptr;    // [B2][HW][C]
+    void* text_xkv = nullptr;   // [2 or B2][L][2C]
+    bool text = false;
 
     Walk(dsim_unet* h, Arena* ar, hipStream_t s, int B2, bool run) : WalkBase(h, ar, s, run), B2(B2) {}
 
@@ -245,11 +250,25 @@ struct Walk : WalkBase<dsim_unet> {
             CK(tap_qkv(t.nb, qkv, C, M, taps[i]));
             ++n_captured;
         }
-        if (last) {
+        if (last && !text) {
             tapped = true;
             return DSIM_OK;
         }
         WGET(o1w, b + "attn1.to_out.0.weight"); WGET(o1b, b + "attn1.to_out.0.bias");
+        if (last) {
+            // the text walk: the self-attention on the tap's own tensors (no second projection), to_out + residual, then the
+            // cross-attention's query and the prompt's K | V into the caller's tensors; the walk ends behind them
+            const TapReq& tp = taps[here.back()];
+            AttnArgs a;
+            a.q = tp.q; a.ldq = C; a.k = tp.k; a.v = tp.v; a.ldk = C;
+            a.out = r.a; a.ldo = C; a.B = r.B; a.Bkv = r.B; a.H = t.heads; a.Nq = t.HW; a.Nk = t.HW; a.D = C / t.heads;
+            CK(attn(a));
+            CK(linear(r.a, C, nullptr, 0, o1w, o1b, r.h, r.h, M, C, C));
+            CK(cross_query(b, t, r, text_xq));
+            CK(cross_kv(b, t, text_xkv));
+            tapped = true;
+            return DSIM_OK;
+        }
         if (fq > 0) CK(linear(t.nb, C, nullptr, 0, qkv, nullptr, nullptr, t.big, M, 3 * C, 3 * C));
         AttnArgs a;
         a.q = t.big; a.ldq = 3 * C;
@@ -272,25 +291,40 @@ struct Walk : WalkBase<dsim_unet> {
                       });
     }
 
+    // The query part of a cross-attention, the last thing computed on the rows r: norm2 -> attn2.to_q, as one row-resident launch
+    // where the fusion mask and the width have one, into xq ([r.B][HW][C]; cross_attention passes r.a, the text walk the caller's).
+    int cross_query(const std::string& b, const Tfm& t, const Rows& r, void* xq) {
+        const int C = t.C;
+        WGET(l2w, b + "norm2.weight"); WGET(l2b, b + "norm2.bias");
+        WGET(q2w, b + "attn2.to_q.weight");
+        const int f2 = ln_proj(r.h, l2w, l2b, b + "attn2.to_q.stream", xq, r.B * t.HW, C, C, t.HW);
+        if (f2 < 0) return f2;
+        if (f2 > 0) {
+            CK(ln(r.h, l2w, l2b, t.nb, r.B * t.HW, C));
+            CK(linear(t.nb, C, nullptr, 0, q2w, nullptr, nullptr, xq, r.B * t.HW, C, C));
+        }
+        return DSIM_OK;
+    }
+    // The prompt's K | V of a cross-attention into kvb, [2][L][2C] -- with a context table every batch element projects its own
+    // context, [B][L][2C], and attends to its own K / V
+    int cross_kv(const std::string& b, const Tfm& t, void* kvb) {
+        const int C = t.C, L = h->cfg.ctx_len, Dc = h->cfg.cross_attention_dim;
+        WGET(kv2, b + "attn2.kv");
+        const int Bkv = mixed() ? t.full.B : 2;
+        return linear(ctx_t, Dc, nullptr, 0, kv2, nullptr, nullptr, kvb, Bkv * L, 2 * C, 2 * C);
+    }
+
     // Cross-attention against the prompt context: batch element b uses ctx[b % 2]; with a context table (n_ctx > 1),
     // ctx[index[b / 2]][b % 2], gathered per batch element in go().  The query is the last thing computed on the rows r; the prompt
     // enters after it, so `pre` (r = the de-duplicated half) parts the halves there and the rest runs on the full batch.
     int cross_attention(const std::string& b, const Tfm& t, const Rows& r, bool pre) {
-        const int C = t.C, L = h->cfg.ctx_len, Dc = h->cfg.cross_attention_dim;
-        WGET(l2w, b + "norm2.weight"); WGET(l2b, b + "norm2.bias");
-        WGET(q2w, b + "attn2.to_q.weight"); WGET(kv2, b + "attn2.kv");
+        const int C = t.C, L = h->cfg.ctx_len;
         WGET(o2w, b + "attn2.to_out.0.weight"); WGET(o2b, b + "attn2.to_out.0.bias");
-        const int f2 = ln_proj(r.h, l2w, l2b, b + "attn2.to_q.stream", r.a, r.B * t.HW, C, C, t.HW);
-        if (f2 < 0) return f2;
-        if (f2 > 0) {
-            CK(ln(r.h, l2w, l2b, t.nb, r.B * t.HW, C));
-            CK(linear(t.nb, C, nullptr, 0, q2w, nullptr, nullptr, r.a, r.B * t.HW, C, C));
-        }
+        CK(cross_query(b, t, r, r.a));
         if (pre) CK(part_halves(t));
         const Rows& f = t.full;
-        // (a context table: every batch element projects its own context, B * L rows, and attends to its own K / V)
         const int Bkv = mixed() ? f.B : 2;
-        CK(linear(ctx_t, Dc, nullptr, 0, kv2, nullptr, nullptr, t.kvb, Bkv * L, 2 * C, 2 * C));
+        CK(cross_kv(b, t, t.kvb));
         AttnArgs a;
         a.q = f.a; a.ldq = C;
         a.k = t.kvb; a.v = (char*)t.kvb + (size_t)C * es(); a.ldk = 2 * C;
@@ -379,6 +413,8 @@ struct Walk : WalkBase<dsim_unet> {
                 t.big = alloc_act((size_t)M * (ff1 ? 3 : 4) * C);
                 t.full.a = alloc_act((size_t)M * C);
                 t.kvb = alloc_act((size_t)(mixed() ? B : 2) * h->cfg.ctx_len * 2 * C);
+            } else if (last && text && !t.full.a) {
+                t.full.a = alloc_act((size_t)M * C);     // the text walk's attention output (its query and K | V are the caller's)
             }
             std::vector<int> here;
             for (size_t i = 0; i < caps.size(); ++i)
@@ -743,11 +779,13 @@ static int check_taps(const dsim_unet* h, int n_images, int n_taps, const dsim_t
 }
 
 // dry walk to the deepest of `taps`: peak arena bytes and the largest activation
-static int plan_taps(dsim_unet* h, int n_images, const std::vector<TapReq>& taps, size_t* peak, size_t* max_tensor, int n_ctx = 1) {
+static int plan_taps(dsim_unet* h, int n_images, const std::vector<TapReq>& taps, size_t* peak, size_t* max_tensor, int n_ctx = 1,
+                     bool text = false) {
     Arena ar;
     Walk w{h, &ar, nullptr, 2 * n_images, false};
     w.taps = taps;
     w.n_ctx = n_ctx;
+    w.text = text;
     CK(w.go(nullptr, nullptr, 0.f, 0.f, nullptr));
     *peak = ar.peak;
     *max_tensor = w.max_tensor;
@@ -760,10 +798,10 @@ static bool ctx_table_ok(const dsim_unet* h, int n_ctx) {
     return n_ctx == 1 || (n_ctx > 1 && !h->two_temb && !h->cfg.addition_embed);
 }
 
-static size_t workspace_bytes(dsim_unet* h, int n_images, int n_ctx) {
+static size_t workspace_bytes(dsim_unet* h, int n_images, int n_ctx, bool text = false) {
     if (!h || !h->finalized || n_images < 1 || !ctx_table_ok(h, n_ctx)) return 0;
     size_t peak, big;
-    if (plan_taps(h, n_images, cfg_taps(h->cfg), &peak, &big, n_ctx) != DSIM_OK) return 0;
+    if (plan_taps(h, n_images, cfg_taps(h->cfg), &peak, &big, n_ctx, text) != DSIM_OK) return 0;
     if (big >= 0x7fffffffull) return 0;      // a >= 2 GiB activation: the batch does not fit one call
     return peak + 256;
 }
@@ -784,6 +822,10 @@ size_t dsim_unet_workspace_bytes(const dsim_unet* hc, int n_images) {
 
 size_t dsim_unet_ctx_workspace_bytes(const dsim_unet* hc, int n_images, int n_ctx) {
     return workspace_bytes(const_cast<dsim_unet*>(hc), n_images, n_ctx);
+}
+
+size_t dsim_unet_text_workspace_bytes(const dsim_unet* hc, int n_images, int n_ctx) {
+    return workspace_bytes(const_cast<dsim_unet*>(hc), n_images, n_ctx, true);
 }
 
 size_t dsim_unet_taps_workspace_bytes(const dsim_unet* hc, int n_images, int n_taps, const dsim_tap* taps) {
@@ -842,19 +884,21 @@ int dsim_unet_set_sample_size(dsim_unet* h, int side) {
 // one walk to the deepest of `taps` (their outputs set), every check before the first launch
 static int run_taps(dsim_unet* h, const float* latents, const float* noise, float sqrt_abar, float sqrt_1m_abar, const float* ctx,
                     int n_images, const std::vector<TapReq>& taps, void* workspace, size_t workspace_bytes, void* stream, int n_ctx,
-                    const int32_t* ctx_index) {
+                    const int32_t* ctx_index, void* text_xq = nullptr, void* text_xkv = nullptr) {
     bool tapped = false;
+    const bool text = text_xq != nullptr;
     CK(run_in_workspace(
         workspace, workspace_bytes,
         [&](size_t* peak) {
             size_t big;
-            return plan_taps(h, n_images, taps, peak, &big, n_ctx);
+            return plan_taps(h, n_images, taps, peak, &big, n_ctx, text);
         },
         [&](Arena& ar) {
             Walk w{h, &ar, (hipStream_t)stream, 2 * n_images, true};
             w.taps = taps;
             w.n_ctx = n_ctx;
             w.ctx_index = ctx_index;
+            w.text = text; w.text_xq = text_xq; w.text_xkv = text_xkv;
             const int st = w.go(latents, noise, sqrt_abar, sqrt_1m_abar, ctx);
             tapped = w.tapped;
             return st;
@@ -866,7 +910,8 @@ static int run_taps(dsim_unet* h, const float* latents, const float* noise, floa
 // handle's own tap (n_taps / taps unused; q, k, v name one tensor each).
 static int qkv_call(dsim_unet* h, const float* latents, const float* noise, float sqrt_abar, float sqrt_1m_abar, const float* ctx,
                     int n_ctx, const int32_t* ctx_index, int n_images, bool own_tap, int n_taps, const dsim_tap* taps, void* const* q,
-                    void* const* k, void* const* v, void* workspace, size_t workspace_bytes, void* stream) {
+                    void* const* k, void* const* v, void* workspace, size_t workspace_bytes, void* stream, void* text_xq = nullptr,
+                    void* text_xkv = nullptr) {
     if (!h || !latents || !noise || !ctx || !q || !k || !v || !workspace || n_images < 1) return DSIM_ERR_INVALID;
     if (own_tap && (!*q || !*k || !*v)) return DSIM_ERR_INVALID;
     if (n_ctx < 1 || (n_ctx > 1 && !ctx_index) || !ctx_table_ok(h, n_ctx)) return DSIM_ERR_INVALID;
@@ -879,7 +924,7 @@ static int qkv_call(dsim_unet* h, const float* latents, const float* noise, floa
         req[i].q = q[i]; req[i].k = k[i]; req[i].v = v[i];
     }
     return run_taps(h, latents, noise, sqrt_abar, sqrt_1m_abar, ctx, n_images, req, workspace, workspace_bytes, stream, n_ctx,
-                    n_ctx > 1 ? ctx_index : nullptr);
+                    n_ctx > 1 ? ctx_index : nullptr, text_xq, text_xkv);
 }
 
 int dsim_unet_qkv(dsim_unet* h, const float* latents, const float* noise, float sqrt_abar, float sqrt_1m_abar,
@@ -901,6 +946,14 @@ int dsim_unet_qkv_ctx(dsim_unet* h, const float* latents, const float* noise, fl
                       size_t workspace_bytes, void* stream) {
     return qkv_call(h, latents, noise, sqrt_abar, sqrt_1m_abar, ctx, n_ctx, ctx_index, n_images, true, 0, nullptr, &q, &k, &v, workspace,
                     workspace_bytes, stream);
+}
+
+int dsim_unet_qkv_text(dsim_unet* h, const float* latents, const float* noise, float sqrt_abar, float sqrt_1m_abar, const float* ctx,
+                       int n_ctx, const int32_t* ctx_index, int n_images, void* q, void* k, void* v, void* xq, void* xkv, void* workspace,
+                       size_t workspace_bytes, void* stream) {
+    if (!xq || !xkv) return DSIM_ERR_INVALID;
+    return qkv_call(h, latents, noise, sqrt_abar, sqrt_1m_abar, ctx, n_ctx, ctx_index, n_images, true, 0, nullptr, &q, &k, &v, workspace,
+                    workspace_bytes, stream, xq, xkv);
 }
 
 int dsim_unet_qkv_taps_ctx(dsim_unet* h, const float* latents, const float* noise, float sqrt_abar, float sqrt_1m_abar, const float* ctx,

@@ -25,7 +25,7 @@ from concurrent.futures import ThreadPoolExecutor
 import torch
 
 from . import scheduler as sched
-from . import align, maps, regions, retrieval, sweep
+from . import align, maps, regions, retrieval, sweep, textattn
 from .config import SD15, UNetConfig
 from .engine import UNetEngine, _LatentDist, pair_score
 from .image import DecodePool, host_threads, load_image, process_image
@@ -93,6 +93,9 @@ class DiffSim(Scorer):
         # DSIM_DECODE_PROCS environment default) or threads (0); started lazily, on the first path batch
         self._decode = DecodePool(decode_procs)
         self._streams: List[torch.cuda.Stream] = []          # side streams of score_latent_pairs
+        # tokenize(str) -> (1, L) ids, the tokenizer behind encode_prompt (loader.py sets it): which prompt tokens a word is,
+        # for the text-guided regions (textattn.py)
+        self.tokenize: Optional[Callable[[str], torch.Tensor]] = None
 
     # ------------------------------------------------------------------------------------------
     def engine(self, target_block: str, target_layer: int) -> UNetEngine:
@@ -196,6 +199,13 @@ class DiffSim(Scorer):
         eng = self.engine(target_block, target_layer)
         *args, idx = self._forward_inputs(eng, latents, noise, prompt, target_step)
         return eng.qkv(*args, ctx_index=idx)
+
+    @torch.no_grad()
+    def features_text(self, latents: torch.Tensor, noise: torch.Tensor, prompt, target_block, target_layer, target_step):
+        """:meth:`features` and the tapped block's cross-attention operands, (q, k, v, xq, xkv): UNetEngine.qkv_text."""
+        eng = self.engine(target_block, target_layer)
+        *args, idx = self._forward_inputs(eng, latents, noise, prompt, target_step)
+        return eng.qkv_text(*args, ctx_index=idx)
 
     @torch.no_grad()
     def features_taps(self, latents: torch.Tensor, noise: torch.Tensor, prompt, taps, target_step):
@@ -376,6 +386,22 @@ class DiffSim(Scorer):
         image); full masks give :meth:`diffsim`'s score.  Returns a (1,) tensor."""
         return regions.score_path_pair_regions(self, [(image_A, image_B)], [(mask_A, mask_B)], img_size, prompt, target_block,
                                                _norm_layer(target_layer), target_step, seed, similarity)
+
+    @torch.no_grad()
+    def text_region_score(self, image_A, image_B, img_size, prompt, target_block, target_layer, target_step, seed="2333",
+                          similarity="cosine", words=None, rel_threshold=1.0):
+        """:meth:`diffsim` of the part of each image the prompt names (textattn.py; the reference's declared and unbuilt
+        ``--use_text_attn``, argprocess.py:17): each image's region is the tokens whose text attention to `words` (None: every
+        content token of the prompt) is at least rel_threshold x the image's mean.  Returns a (1,) tensor."""
+        return textattn.score_path_pairs_text(self, [(image_A, image_B)], img_size, prompt, target_block, _norm_layer(target_layer),
+                                              target_step, seed, similarity, words, rel_threshold)
+
+    @torch.no_grad()
+    def text_attention_map(self, image_A, image_B, img_size, prompt, target_block, target_layer, target_step, seed="2333"):
+        """The text attention maps of the two images of one :meth:`diffsim` call: (2, h, w, L) f32 on the tap's token grid."""
+        latA, latB, nA, nB = self._path_pair_latents(image_A, image_B, img_size, seed)
+        return textattn.text_attention_maps(self, torch.cat([latA, latB]), torch.cat([nA, nB]), prompt, target_block,
+                                            _norm_layer(target_layer), target_step)
 
     @torch.no_grad()
     def score_latent_pair_alignment(self, latA, latB, noiseA, noiseB, prompt, target_block="up_blocks", target_layer=0,

@@ -135,6 +135,13 @@ class diffsim_DiT(Scorer):
         return regions.score_path_pair_regions(self, [(image_A, image_B)], [(mask_A, mask_B)], img_size, None, "none",
                                                [int(target_layer[0])], target_step, seed, similarity, batch_pairs=32, hip_vae=False)
 
+    def text_region_score(self, *args, **kwargs):
+        """DiT is class-conditional: it has no prompt and no cross-attention, so no text-guided regions."""
+        raise NotImplementedError("diffsim_DiT has no text conditioning (a class-conditional model without cross-attention): "
+                                  "text-guided regions need --metric diffsim or diffsim_xl")
+
+    text_attention_map = text_region_score
+
     @torch.no_grad()
     def score_latent_pair_alignment(self, latA, latB, noiseA, noiseB, target_layer: int, target_step: int, batch_pairs: int = 32):
         """Alignments of the pairs of :meth:`score_latent_pairs` (align.score_latent_pair_alignment)."""

@@ -13,7 +13,7 @@ from typing import Callable, Dict, Optional, Tuple
 
 import torch
 
-from . import align, maps, regions, sweep
+from . import align, maps, regions, sweep, textattn
 from . import scheduler as sched
 from .config import SDXL, UNetConfig
 from .engine import UNetEngine, pair_score
@@ -46,6 +46,7 @@ class diffsim_xl(Scorer):
         self.noise_dtype = noise_dtype
         self._base: Optional[UNetEngine] = None
         self._engines: Dict[tuple, object] = {}
+        self.tokenize = None        # tokenize(str) -> (1, L) ids of the first text encoder's tokenizer (loader.py sets it; textattn.py)
 
     def engine(self, target_block: str, target_layer):
         """The engine positioned at a tap; one packed weight copy serves every tap."""
@@ -88,6 +89,9 @@ class diffsim_xl(Scorer):
     def taps_features(self, lat, nz, prompt, taps, step):
         return self.features_taps(lat, nz, *prompt, taps, step)
 
+    def tap_features_text(self, lat, nz, prompt, tap, step):
+        return self.features_text(lat, nz, *prompt, *tap, step)
+
     def prepare_image_latents(self, image, generator=None):
         if self.vae is None:
             raise RuntimeError("no VAE plugged in: use score_latent_pairs")
@@ -107,6 +111,12 @@ class diffsim_xl(Scorer):
         """latents / noise (n,4,s,s): any latent side s (img_size // 8), not only cfg.sample_size."""
         eng = self.engine(target_block, target_layer)
         return eng.qkv(*self._forward_inputs(eng, latents, noise, ctx, pooled, target_step))
+
+    @torch.no_grad()
+    def features_text(self, latents, noise, ctx, pooled, target_block, target_layer, target_step):
+        """:meth:`features` and the tapped block's cross-attention operands, (q, k, v, xq, xkv): UNetEngine.qkv_text."""
+        eng = self.engine(target_block, target_layer)
+        return eng.qkv_text(*self._forward_inputs(eng, latents, noise, ctx, pooled, target_step))
 
     @torch.no_grad()
     def features_taps(self, latents, noise, ctx, pooled, taps, target_step):
@@ -188,6 +198,22 @@ class diffsim_xl(Scorer):
         tap's token grid, or None (the whole image).  Returns a (1,) tensor."""
         return regions.score_path_pair_regions(self, [(image_A, image_B)], [(mask_A, mask_B)], img_size, prompt, target_block,
                                                target_layer, target_step, seed, similarity, hip_vae=False)
+
+    @torch.no_grad()
+    def text_region_score(self, image_A, image_B, img_size, prompt, target_block, target_layer, target_step, seed, similarity,
+                          words=None, rel_threshold=1.0):
+        """:meth:`diffsim_score` of the part of each image the prompt names (textattn.py): each image's region is the tokens whose
+        text attention to `words` (None: every content token of the prompt) is at least rel_threshold x the image's mean.
+        Returns a (1,) tensor."""
+        return textattn.score_path_pairs_text(self, [(image_A, image_B)], img_size, prompt, target_block, target_layer, target_step,
+                                              seed, similarity, words, rel_threshold, hip_vae=False)
+
+    @torch.no_grad()
+    def text_attention_map(self, image_A, image_B, img_size, prompt, target_block, target_layer, target_step, seed):
+        """The text attention maps of the two images of one :meth:`diffsim_score` call: (2, h, w, L) f32 on the tap's grid."""
+        latA, latB, nA, nB, ctx, pooled = self._path_pair_inputs(image_A, image_B, img_size, prompt, seed)
+        return textattn.text_attention_maps(self, torch.cat([latA, latB]), torch.cat([nA, nB]), (ctx, pooled), target_block,
+                                            target_layer, target_step)
 
     @torch.no_grad()
     def score_latent_pair_alignment(self, latA, latB, noiseA, noiseB, ctx, pooled, target_block, target_layer, target_step,

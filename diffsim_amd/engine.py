@@ -440,6 +440,37 @@ class UNetEngine(_Handle):
             _lib.check(st, "dsim_unet_qkv_taps")
         return outs
 
+    # ---- the tapped block's cross-attention operands (dsim_unet_qkv_text) -------------------------------------------
+    def text_workspace_bytes(self, n_images: int, n_ctx: int = 1) -> int:
+        """Workspace of one qkv_text() call over n_images (0: the call is impossible, as workspace_bytes)."""
+        return int(self.L.dsim_unet_text_workspace_bytes(self._h, n_images, int(n_ctx)))
+
+    def qkv_text(self, latents: torch.Tensor, noise: torch.Tensor, sqrt_abar: float, sqrt_1m_abar: float, ctx: torch.Tensor,
+                 ctx_index=None):
+        """qkv() whose walk runs the tapped block on to its cross-attention: returns (q, k, v, xq, xkv) -- q, k, v bit for bit
+        qkv()'s; xq [n][2][tokens][heads*head_dim], the block's attn2.to_q(norm2(h + attn1(...))); xkv [n_kv][ctx_len][2*C], its
+        attn2.to_k | to_v of the prompt (n_kv = 2, [uncond, cond], for one prompt; 2n, batch element e's context in row e, with a
+        context table).  What text_attention() takes.  Runs eagerly (no hipGraph) on the calling stream's workspace arena; ctx /
+        ctx_index as qkv() takes them."""
+        self._check_inputs(latents, noise, ctx)
+        n = latents.shape[0]
+        with torch.cuda.device(self.device):
+            ctx, n_ctx, idx = self._ctx_args(ctx, ctx_index, n)
+            need = self.text_workspace_bytes(n, n_ctx)
+            if need == 0:
+                raise _lib.DsimError(f"{n} images do not fit one call (an activation would reach 2 GiB): at most "
+                                     f"{self.max_images(n_ctx=n_ctx)} images per call for this graph")
+            ws = self._arena(need)
+            C_ = self.heads * self.head_dim
+            q, k, v = torch.empty((3, n, 2, self.tokens, C_), dtype=self.dtype, device=self.device).unbind(0)   # one allocation, as qkv()
+            xq = torch.empty((n, 2, self.tokens, C_), dtype=self.dtype, device=self.device)
+            xkv = torch.empty((2 if n_ctx == 1 else 2 * n, self.cfg.ctx_len, 2 * C_), dtype=self.dtype, device=self.device)
+            _lib.check(self.L.dsim_unet_qkv_text(self._h, latents.data_ptr(), noise.data_ptr(), float(sqrt_abar), float(sqrt_1m_abar),
+                                                 ctx.data_ptr(), n_ctx, _ptr(idx), n, q.data_ptr(), k.data_ptr(), v.data_ptr(),
+                                                 xq.data_ptr(), xkv.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr()),
+                       "dsim_unet_qkv_text")
+        return q, k, v, xq, xkv
+
     def _launch(self, latents, noise, sa, sb, ctx, out, idx=None):
         q, k, v = out
         if idx is None:
@@ -611,6 +642,67 @@ def pair_score_regions(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: 
                                              0 if similarity == "cosine" else 1, out.data_ptr(), _ptr(status), _ptr(counts),
                                              ws.data_ptr(), wsb, _stream_ptr()), "dsim_pair_score_regions")
     return out if not (return_status or return_counts) else (out,) + ((status,) if return_status else ()) + ((counts,) if return_counts else ())
+
+
+TEXT_WANT = ("attn", "saliency", "mask", "counts", "status")
+
+
+def text_attention(xq: torch.Tensor, xkv: torch.Tensor, heads: int, token_weight: Optional[torch.Tensor] = None,
+                   rel_threshold: float = 1.0, want=("saliency", "mask", "counts")):
+    """Text attention maps and text-guided regions (dsim_text_attention) from UNetEngine.qkv_text's operands.  xq
+    [n][2][N][H*D], xkv [n_kv][L][2*H*D] (K in the first H*D columns), n_kv = 2 or 2n.  On the conditional CFG half of image i,
+    T_i[n][l] = the softmax over the L prompt tokens averaged over the heads, saliency s_i = T_i @ w_i with token_weight w f32
+    (L,) shared or (n, L) per image, and the region: the tokens with s_i[n] >= rel_threshold * mean(s_i), or every token when none
+    passes.  Returns a dict of the outputs named in `want`: attn f32 (n, N, L), saliency f32 (n, N), mask bool (n, N), counts
+    int32 (n,), status int32 (n,) (1: a non-finite probability).  The values do not depend on `want`."""
+    L_ = _lib.lib()
+    want = tuple(want)
+    if not want or any(w not in TEXT_WANT for w in want):
+        raise ValueError(f"want must name some of {TEXT_WANT}: {want}")
+    _require_cuda(xq, xkv)
+    if xq.dtype not in _TORCH2DSIM or xkv.dtype != xq.dtype:
+        raise _lib.DsimError("xq and xkv must share dtype float32, bfloat16 or float16")
+    if xq.ndim != 4 or xq.shape[1] != 2 or xkv.ndim != 3 or xkv.shape[2] != 2 * xq.shape[3] or xq.shape[3] % heads:
+        raise _lib.DsimError(f"xq must be [n][2][N][H*D] and xkv [n_kv][L][2*H*D]: {tuple(xq.shape)}, {tuple(xkv.shape)}")
+    if not (xq.is_contiguous() and xkv.is_contiguous()):
+        raise _lib.DsimError("xq and xkv must be contiguous")
+    n, _, N, HD = xq.shape
+    n_kv, L = int(xkv.shape[0]), int(xkv.shape[1])
+    dev = xq.device
+    needs_w = any(w in want for w in ("saliency", "mask", "counts"))
+    n_w = 1
+    if token_weight is not None:
+        token_weight = token_weight.to(device=dev, dtype=torch.float32).contiguous()
+        if token_weight.ndim == 1:
+            token_weight = token_weight[None]
+        if token_weight.ndim != 2 or token_weight.shape[1] != L or token_weight.shape[0] not in (1, n):
+            raise _lib.DsimError(f"token_weight must be ({L},) or ({n}, {L}): {tuple(token_weight.shape)}")
+        n_w = int(token_weight.shape[0])
+    elif needs_w:
+        raise _lib.DsimError("saliency and regions need token_weight")
+    out = {}
+    if "attn" in want:
+        out["attn"] = torch.empty((n, N, L), dtype=torch.float32, device=dev)
+    if "saliency" in want:
+        out["saliency"] = torch.empty((n, N), dtype=torch.float32, device=dev)
+    if "mask" in want:
+        out["mask"] = torch.empty((n, N), dtype=torch.uint8, device=dev)
+    if "counts" in want:
+        out["counts"] = torch.empty(n, dtype=torch.int32, device=dev)
+    if "status" in want:
+        out["status"] = torch.empty(n, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        wsb = int(L_.dsim_text_attention_workspace_bytes(n, N, L))
+        if wsb == 0:
+            raise _lib.DsimError(f"no text attention for n={n} N={N} L={L} (1 <= L <= 128)")
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        _lib.check(L_.dsim_text_attention(xq.data_ptr(), HD, xkv.data_ptr(), 2 * HD, n, n_kv, heads, N, L, HD // heads,
+                                          _TORCH2DSIM[xq.dtype], _ptr(token_weight), n_w, float(rel_threshold), _ptr(out.get("attn")),
+                                          _ptr(out.get("saliency")), _ptr(out.get("mask")), _ptr(out.get("counts")),
+                                          _ptr(out.get("status")), ws.data_ptr(), wsb, _stream_ptr()), "dsim_text_attention")
+    if "mask" in out:
+        out["mask"] = out["mask"].view(torch.bool)
+    return out
 
 
 _ATTN_BYTES = (1 << 31) - 1          # dsim_pair_align refuses an attention tensor of 2 GiB or more: the pairs are chunked

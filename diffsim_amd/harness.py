@@ -73,12 +73,14 @@ def cute_accuracy(s_ab: torch.Tensor, s_ac: torch.Tensor) -> float:
 
 
 @torch.no_grad()
-def triplet_chunks(scorer, ref, left, right, nA, nB, prompt, heads, similarity, batch_triplets: int, feats, masks=None):
+def triplet_chunks(scorer, ref, left, right, nA, nB, prompt, heads, similarity, batch_triplets: int, feats, masks=None, text=None):
     """(ref,left) and (ref,right) scores of latent triplets at every tap of a forward: 3 forwards per triplet (the reference
     image's features are shared), chunked engine batches, one fused tail launch per chunk and tap.  feats(lat, nz, prompt) ->
     [(q, k, v) per tap] is the forward of one engine batch, heads[t] tap t's head count.  masks: None, or the (ref, left, right)
     token masks, each (n, N) bool on the device: the region tail (regions.py) over each chunk's rows instead of the pair tail.
-    Returns the (nt, n) scores of both sides and the (nt,) NaN / inf counts."""
+    text: None, or (guide, w): a textattn.TextGuide and its bound per-triplet weights; feats then returns (q, k, v, xq, xkv) per
+    tap and the masks of the region tail are the text-guided regions of the chunk's images -- ref, left and right each their own,
+    the ref's made once per triplet.  Returns the (nt, n) scores of both sides and the (nt,) NaN / inf counts."""
     n, nt, dev = ref.shape[0], len(heads), scorer.device
     s_l = torch.empty((nt, n), dtype=torch.float32, device=dev)
     s_r = torch.empty((nt, n), dtype=torch.float32, device=dev)
@@ -89,11 +91,14 @@ def triplet_chunks(scorer, ref, left, right, nA, nB, prompt, heads, similarity, 
         fs = feats(*stack_rows([ref, left, right], [nA, nB, nB], i0, i1), scorer.chunk_prompt(prompt, i0, i1, 3))
         base = torch.arange(0, 3 * m, 3, dtype=torch.int32, device=dev)
         ia, ib = torch.cat([base, base]), torch.cat([base + 1, base + 2])
-        for t, (q, k, v) in enumerate(fs):
-            if masks is None:
+        for t, (q, k, v, *xs) in enumerate(fs):
+            if masks is None and text is None:
                 s, st = pair_score(q, k, v, ia, ib, heads[t], similarity, return_status=True)
             else:                                           # (the chunk's mask rows lie as its images do: ref, left, right)
-                rows = torch.stack([mk[i0:i1] for mk in masks], dim=1).reshape(3 * m, -1).contiguous()
+                if text is not None:
+                    rows, _counts = text[0].regions(*xs, heads[t], text[1], i0, i1, 3)
+                else:
+                    rows = torch.stack([mk[i0:i1] for mk in masks], dim=1).reshape(3 * m, -1).contiguous()
                 s, st = pair_score_regions(q, k, v, rows, ia, ib, heads[t], similarity, return_status=True)
                 st = (st != 0).to(torch.int32)
             bad[t] += st.sum()
@@ -101,11 +106,17 @@ def triplet_chunks(scorer, ref, left, right, nA, nB, prompt, heads, similarity, 
     return s_l, s_r, bad
 
 
-def _score_chunks(scorer, ref, left, right, nA, nB, prompt, block, layer, step, similarity, batch_triplets, masks=None):
+def _score_chunks(scorer, ref, left, right, nA, nB, prompt, block, layer, step, similarity, batch_triplets, masks=None, text=None):
     """triplet_chunks at the one tap (block, layer): each engine batch is one ``tap_features`` call.  masks: None, or one
-    (ref, left, right) triple of masks per triplet (``regions.as_token_mask``), put on the tap's token grid here."""
+    (ref, left, right) triple of masks per triplet (``regions.as_token_mask``), put on the tap's token grid here.  text: None, or
+    a textattn.TextGuide: each engine batch is one ``tap_features_text`` call and the regions come from the text attention maps
+    (per-row prompts give per-triplet weights)."""
     n = ref.shape[0]
     tap = scorer.tap_of(block, layer)
+    if text is not None:
+        if masks is not None:
+            raise ValueError("a text-guided region and a mask file per image: one or the other")
+        text = (text, text.bind(scorer, prompt, n))
     if masks is not None:
         from .regions import as_token_mask, tap_grid
         grid = tap_grid(scorer, tap, ref.shape[-1])
@@ -115,6 +126,9 @@ def _score_chunks(scorer, ref, left, right, nA, nB, prompt, block, layer, step, 
     heads = eng.heads
     if batch_triplets is None:
         batch_triplets = scorer.auto_rows(eng, n, 3, n_ctx=scorer.n_ctx(prompt))
+    if text is not None:
+        return triplet_chunks(scorer, ref, left, right, nA, nB, prompt, [heads], similarity, batch_triplets,
+                              lambda lat, nz, p: [scorer.tap_features_text(lat, nz, p, tap, step)], text=text)
     return triplet_chunks(scorer, ref, left, right, nA, nB, prompt, [heads], similarity, batch_triplets,
                           lambda lat, nz, p: [scorer.tap_features(lat, nz, p, tap, step)], *(() if masks is None else (masks,)))
 
@@ -157,7 +171,7 @@ def path_triplet_scores(scorer, triplets: Sequence[Tuple[str, str, str, str]], i
 
 def score_path_triplets(scorer, triplets: Sequence[Tuple[str, str, str, str]], img_size: int, target_block, target_layer,
                         target_step, seed=2333, similarity="cosine", rank: int = 0, world: int = 1, batch_triplets: int = 10,
-                        unet_triplets: Optional[int] = None, masks: Optional[Sequence] = None):
+                        unet_triplets: Optional[int] = None, masks: Optional[Sequence] = None, text=None):
     """Scores s(A,B) and s(A,C) of every (A, B, C, prompt) path triplet -- the two scorer calls per triplet the
     reference's loops make (cute_main.py:111-132, night_main.py:69-90, style_main.py:150-175) -- for all three scorer
     kinds (DiffSim, diffsim_xl, diffsim_DiT): whole triplets sharded over ranks (the cached reference-image features stay
@@ -168,15 +182,20 @@ def score_path_triplets(scorer, triplets: Sequence[Tuple[str, str, str, str]], i
     (dsim_image_preprocess / dsim_latent_sample), bit-identically to the per-pair path.  masks: None, or one (ref, left, right)
     triple per triplet of mask paths, PIL images, bool arrays on the tap's token grid or None (the whole image): region scores
     (regions.py), what ``region_score(A, B, mask_A, mask_B, ...)`` and ``region_score(A, C, mask_A, mask_C, ...)`` return;
-    with masks=None every call and launch is the unmasked run's.  Returns (s_ab, s_ac, n_nonfinite):
+    with masks=None every call and launch is the unmasked run's.  text: None, or a textattn.TextGuide (words, threshold):
+    text-guided regions instead -- ref, left and right each get the region their own text attention map gives, the ref's once per
+    triplet, a prompt per row giving weights per image; text.on_fraction is then the mean share of tokens on.  Returns
+    (s_ab, s_ac, n_nonfinite):
     length-len(triplets) f32 tensors on every rank and the number of NaN/inf pair scores (NaN guard)."""
     # (batch_triplets sizes the decode / VAE-encode chunks; the U-Net batch is unet_triplets, or the scorer's auto_rows)
     if masks is not None and len(masks) != len(triplets):
         raise ValueError(f"{len(masks)} mask triples for {len(triplets)} triplets")
+    if masks is not None and text is not None:
+        raise ValueError("a text-guided region and a mask file per image: one or the other")
     all_l, all_r, nbad = path_triplet_scores(
         scorer, triplets, img_size, seed, rank, world, batch_triplets, 1,
         lambda *lat_prompt: _score_chunks(scorer, *lat_prompt[:6], target_block, target_layer, target_step, similarity, unet_triplets,
-                                          *lat_prompt[6:]),
+                                          *lat_prompt[6:], **({} if text is None else {"text": text})),
         *(() if masks is None else (masks,)))
     return all_l[0], all_r[0], int(nbad)
 

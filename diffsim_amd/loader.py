@@ -185,9 +185,11 @@ def load_diffsim(model_path: str, dtype: str = "bf16", device: str = "cuda", noi
     ucfg = dataclasses.replace(ucfg, ctx_len=tcfg.max_positions)       # context length = the text encoder's positions (77)
     vae = VAEEncoder(vcfg, vae_sd, td, dev)                    # first GPU touch: raises DsimError without a GPU
     enc = T.CLIPTextEncoder(tcfg, te_sd, device=dev, dtype=torch.float32)
-    encode = T.make_encode_prompt(enc, LazyTokenizer(os.path.join(model_path, "tokenizer"), tcfg.max_positions))
-    return DiffSim(torch_dtype=td, device=dev, unet_config=ucfg, state_dict=unet_sd, vae=vae, encode_prompt=encode,
-                   noise_dtype=noise_dtype, **kw)
+    tok = LazyTokenizer(os.path.join(model_path, "tokenizer"), tcfg.max_positions)
+    ds = DiffSim(torch_dtype=td, device=dev, unet_config=ucfg, state_dict=unet_sd, vae=vae, encode_prompt=T.make_encode_prompt(enc, tok),
+                 noise_dtype=noise_dtype, **kw)
+    ds.tokenize = tok               # which prompt tokens a word is (textattn.prompt_token_weights)
+    return ds
 
 
 def load_diffsim_xl(model_path: str, dtype: str = "bf16", device: str = "cuda", noise_dtype=torch.float32):
@@ -204,9 +206,11 @@ def load_diffsim_xl(model_path: str, dtype: str = "bf16", device: str = "cuda", 
                            load_state_dict(os.path.join(model_path, "text_encoder")), device=dev)
     e2 = T.CLIPTextEncoder(clip_config_from_json(_json(os.path.join(model_path, "text_encoder_2")), T.OPENCLIP_BIGG),
                            load_state_dict(os.path.join(model_path, "text_encoder_2")), device=dev)
-    encode = T.make_encode_prompt_xl(e1, e2, LazyTokenizer(os.path.join(model_path, "tokenizer")),
-                                     LazyTokenizer(os.path.join(model_path, "tokenizer_2")))
-    return diffsim_xl(td, dev, unet_config=ucfg, state_dict=unet_sd, vae=vae, encode_prompt=encode, noise_dtype=noise_dtype)
+    tok = LazyTokenizer(os.path.join(model_path, "tokenizer"))
+    encode = T.make_encode_prompt_xl(e1, e2, tok, LazyTokenizer(os.path.join(model_path, "tokenizer_2")))
+    xl = diffsim_xl(td, dev, unet_config=ucfg, state_dict=unet_sd, vae=vae, encode_prompt=encode, noise_dtype=noise_dtype)
+    xl.tokenize = tok               # (both tokenizers split a prompt alike; the context's positions are theirs)
+    return xl
 
 
 def load_diffsim_dit(model_path: str, img_size: int, target_step: int, dtype: str = "bf16", device: str = "cuda",

@@ -215,10 +215,20 @@ class Scorer:
     def taps_features(self, lat, nz, prompt, taps, step):
         return self.features_taps(lat, nz, prompt, taps, step)
 
-    def pair_chunks(self, latA, latB, noiseA, noiseB, prompt, tap, step, similarity, batch_pairs: int, tail, tail_of=None):
+    def tap_features_text(self, lat, nz, prompt, tap, step):
+        """tap_features plus the tapped block's cross-attention operands, (q, k, v, xq, xkv) (UNetEngine.qkv_text): the kinds with
+        a text-conditioned U-Net provide ``features_text``."""
+        if not hasattr(self, "features_text"):
+            raise NotImplementedError(f"{type(self).__name__} has no text conditioning: no text attention maps")
+        return self.features_text(lat, nz, prompt, *tap, step)
+
+    def pair_chunks(self, latA, latB, noiseA, noiseB, prompt, tap, step, similarity, batch_pairs: int, tail, tail_of=None,
+                    text_of=None):
         """Yields (i0, i1, tail(q, k, v, idx_a, idx_b, heads, similarity)) for the pairs (latA[i] in slot A, latB[i] in slot B) in
         engine batches of batch_pairs; tail: engine.pair_score or engine.pair_score_maps.  tail_of(i0, i1), when given, returns
-        the tail of that chunk instead (regions.py binds each chunk's mask rows, which lie as its images do: A0, B0, A1, B1, ...)."""
+        the tail of that chunk instead (regions.py binds each chunk's mask rows, which lie as its images do: A0, B0, A1, B1, ...).
+        text_of(i0, i1, xq, xkv, heads), when given, does the same from the chunk's cross-attention operands (textattn.py: the
+        regions come from the text attention maps), and the features come from tap_features_text."""
         n = latA.shape[0]
         eng = self.engine_at(tap)
         heads = eng.heads
@@ -227,7 +237,12 @@ class Scorer:
         batch_pairs = max(1, int(batch_pairs))
         for i0 in range(0, n, batch_pairs):
             i1 = min(n, i0 + batch_pairs)
-            q, k, v = self.tap_features(*stack_rows([latA, latB], [noiseA, noiseB], i0, i1), self.chunk_prompt(prompt, i0, i1, 2),
-                                        tap, step)
+            rows, chunk_prompt = stack_rows([latA, latB], [noiseA, noiseB], i0, i1), self.chunk_prompt(prompt, i0, i1, 2)
+            if text_of is None:
+                q, k, v = self.tap_features(*rows, chunk_prompt, tap, step)
+                chunk_tail = tail if tail_of is None else tail_of(i0, i1)
+            else:
+                q, k, v, xq, xkv = self.tap_features_text(*rows, chunk_prompt, tap, step)
+                chunk_tail = text_of(i0, i1, xq, xkv, heads)
             ia = torch.arange(0, 2 * (i1 - i0), 2, dtype=torch.int32, device=self.device)
-            yield i0, i1, (tail if tail_of is None else tail_of(i0, i1))(q, k, v, ia, ia + 1, heads, similarity)
+            yield i0, i1, chunk_tail(q, k, v, ia, ia + 1, heads, similarity)

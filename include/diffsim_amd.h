@@ -213,6 +213,23 @@ int    dsim_unet_qkv_taps_ctx(dsim_unet* h, const float* latents, const float* n
                               const float* ctx, int n_ctx, const int32_t* ctx_index, int n_images, int n_taps, const dsim_tap* taps,
                               void* const* q, void* const* k, void* const* v, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the tapped block's cross-attention operands: what the text attention maps are made of -----------------------------------
+ * The reference declares `--use_text_attn`, "use the cross-attention results of text to guide conditional similarity"
+ * (argprocess.py:17), and builds nothing behind it.  dsim_unet_qkv_text is dsim_unet_qkv_ctx on the handle's own tap whose walk does
+ * not stop at the tap: the tapped BasicTransformerBlock runs on through its self-attention (on the captured q, k, v themselves),
+ * attn1.to_out + residual, norm2 and attn2.to_q, and the block's attn2.to_k | to_v of the prompt context:
+ *   q,k,v : as dsim_unet_qkv, bit for bit (the launches up to the tap are the same)
+ *   xq    : dtype [2 n_images][tokens][heads*head_dim]: the cross-attention query of every batch element
+ *   xkv   : dtype [n_kv][ctx_len][2*heads*head_dim], K in columns [0, C) and V in [C, 2C); n_kv = 2 ([uncond, cond]) when
+ *           n_ctx == 1, 2 n_images (batch element e's own context in row e) with a context table
+ * An image's rows do not depend on the other images of the call.  Checks, all before anything is enqueued: DSIM_ERR_INVALID for a
+ * NULL xq or xkv, then what dsim_unet_qkv_ctx checks; DSIM_ERR_WORKSPACE below dsim_unet_text_workspace_bytes (0: an impossible
+ * call, as its siblings).  SDXL handles take the call with n_ctx == 1. */
+size_t dsim_unet_text_workspace_bytes(const dsim_unet* h, int n_images, int n_ctx);
+int    dsim_unet_qkv_text(dsim_unet* h, const float* latents, const float* noise, float sqrt_abar, float sqrt_1m_abar,
+                          const float* ctx, int n_ctx, const int32_t* ctx_index, int n_images, void* q, void* k, void* v,
+                          void* xq, void* xkv, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- score tail: replaces diffsim/diffsim.py:177-197 (4x F.scaled_dot_product_attention,
  *      2x F.cosine_similarity or F.mse_loss, mean).  Fused: the O tensors never reach HBM. --
  *   q,k,v       : dtype [n_feat][B][N][H*D]   (features of n_feat images, B = CFG batch = 2)
@@ -321,6 +338,35 @@ int    dsim_pair_score_regions(const void* q, const void* k, const void* v, cons
                                int B, int H, int N, int D, int dtype, int similarity,
                                float* out_scores, int32_t* status /* NULL or [n_pairs]: 0, 1 non-finite, 2 empty region */,
                                int32_t* counts /* NULL or [n_feat] */, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- text attention maps and text-guided regions: the prompt's cross-attention picks the tokens --------------------------------
+ * What `--use_text_attn` (argprocess.py:17 of the reference) names.  For image i, on the conditional CFG half only (batch element
+ * e = 2 i + 1 of xq; context row 1 when n_kv == 2, row e when n_kv == 2 n_images):
+ *   P_h[n][l] = softmax_l(xq_h[n,:] . xk_h[l,:] / sqrt(D)),   T_i[n][l] = mean of P_h[n][l] over the H heads (ascending),
+ *   s_i[n]    = sum_l w_i[l] T_i[n][l]                         (saliency: f32 fma, l ascending),
+ *   m_i       = mean of s_i over the N tokens (summed in f64 in an order that depends on N alone),
+ *   token n is on iff (double)s_i[n] >= (double)rel_threshold * m_i; if no token passes (a threshold above every token, or
+ *   non-finite saliency) every token is on: the whole image.
+ *   xq          : dtype [n_images][2][N] rows of ldq elements, head h in columns [h D, (h + 1) D)   (dsim_unet_qkv_text's xq: ldq = H D)
+ *   xk          : dtype [n_kv][L] rows of ldk elements, likewise                                     (its xkv: ldk = 2 H D)
+ *   token_weight: device f32 [n_w][L], n_w = 1 (shared) or n_images; may be NULL when only attn / status are asked for
+ *   attn        : NULL, or device f32 [n_images][N][L]: T
+ *   saliency    : NULL, or device f32 [n_images][N]
+ *   mask        : NULL, or device uint8 [n_images][N]: 1 = on (the mask dsim_pair_score_regions takes)
+ *   counts      : NULL, or device int32 [n_images]: the mask's sum
+ *   status      : NULL, or device int32 [n_images]: 1 when any probability of the image is non-finite
+ * The logits come from the stored values without pre-scaling xq, the scale enters in f32 after the matrix product and nothing is
+ * rounded to 16 bits on the way to T (dsim_pair_align's arithmetic).  Deterministic, no atomics; an image's values do not depend on
+ * the other images of the call, nor on which outputs are requested.  All checks before anything is enqueued: DSIM_ERR_INVALID
+ * (workspace query: 0 for n_images outside [1, 65535], N < 1 or L outside [1, 128]) for a bad dtype or head dim, H < 1, n_kv not 2
+ * or 2 n_images, ldq / ldk below H D or not whole 16-byte chunks, xq / xk not 16-byte aligned, a negative or non-finite
+ * rel_threshold, and -- when saliency, mask or counts is asked for -- a NULL token_weight or n_w not 1 or n_images;
+ * DSIM_ERR_WORKSPACE for a short workspace. */
+size_t dsim_text_attention_workspace_bytes(int n_images, int N, int L);
+int    dsim_text_attention(const void* xq, int ldq, const void* xk, int ldk, int n_images, int n_kv, int H, int N, int L, int D,
+                           int dtype, const float* token_weight, int n_w, float rel_threshold,
+                           float* attn, float* saliency, uint8_t* mask, int32_t* counts, int32_t* status,
+                           void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- VAE encoder: replaces `pipe.vae.encode(image)` in
  *      DiffSim.prepare_image_latents (diffsim/diffsim.py:92-96).  Sampling
