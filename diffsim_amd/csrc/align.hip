@@ -237,18 +237,19 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void align_kernel(co
 }
 
 template <typename T>
-int launch_align_t(const void* q, const void* k, const int32_t* ia, const int32_t* ib, int n_pairs, int B, int H, int N, int D, int grid_w,
-                   int32_t* match, float* weight, float* expect, float* attn, int32_t* status, void* scratch, hipStream_t s) {
-    return with_head_dim(D, [&](auto dc) -> int {
+int launch_align_t(const PairArgs& a, int grid_w, int32_t* match, float* weight, float* expect, float* attn, int32_t* status,
+                   hipStream_t s) {
+    return with_head_dim(a.D, [&](auto dc) -> int {
         constexpr int Dc = decltype(dc)::value;
-        const int qt = (N + 127) / 128;
+        const int qt = (a.N + 127) / 128;
         const float c = scale_log2_of(Dc);
-        if (status) DSIM_HIP_CHECK(hipMemsetAsync(status, 0, (size_t)n_pairs * sizeof(int32_t), s));
-        hipLaunchKernelGGL((align_stats_kernel<T, Dc>), dim3(qt, B * H, n_pairs * 2), dim3(256), 0, s, (const T*)q, (const T*)k, ia, ib, B,
-                           H, N, c, (float2*)scratch);
+        if (status) DSIM_HIP_CHECK(hipMemsetAsync(status, 0, (size_t)a.n_pairs * sizeof(int32_t), s));
+        hipLaunchKernelGGL((align_stats_kernel<T, Dc>), dim3(qt, a.B * a.H, a.n_pairs * 2), dim3(256), 0, s, (const T*)a.q, (const T*)a.k,
+                           a.idx_a, a.idx_b, a.B, a.H, a.N, c, (float2*)a.scratch);
         DSIM_HIP_CHECK(hipGetLastError());
-        hipLaunchKernelGGL((align_kernel<T, Dc>), dim3(qt, n_pairs * 2), dim3(256), 0, s, (const T*)q, (const T*)k, ia, ib, B, H, N, c,
-                           1.0f / (float)(B * H), grid_w, (const float2*)scratch, match, weight, expect, attn, status);
+        hipLaunchKernelGGL((align_kernel<T, Dc>), dim3(qt, a.n_pairs * 2), dim3(256), 0, s, (const T*)a.q, (const T*)a.k, a.idx_a, a.idx_b,
+                           a.B, a.H, a.N, c, 1.0f / (float)(a.B * a.H), grid_w, (const float2*)a.scratch, match, weight, expect, attn,
+                           status);
         DSIM_HIP_CHECK(hipGetLastError());
         return DSIM_OK;
     });
@@ -257,35 +258,27 @@ int launch_align_t(const void* q, const void* k, const int32_t* ia, const int32_
 }  // namespace
 
 inline namespace DSIM_H16_NS {
-// the statistics of align_stats_kernel, [pair][dir][bh][N] float2; 0 for a shape align_kernel does not serve
+// the statistics of align_stats_kernel, [pair][dir][bh][N] float2; 0 for a shape the launcher does not serve
 size_t pair_align_scratch_bytes(int n_pairs, int B, int H, int N, int D) {
-    if (n_pairs < 1 || B < 1 || H < 1 || N < 1) return 0;
-    if (with_head_dim(D, [](auto) { return DSIM_OK; }) != DSIM_OK) return 0;
+    if (!pair_shape_served(n_pairs, B, H, N, D)) return 0;
     return (size_t)n_pairs * 2 * B * H * N * sizeof(float2);
 }
 
-// token alignments (align_stats_kernel, align_kernel): any head dim of DSIM_FOR_EACH_D, any N, the three dtypes
-int launch_pair_align(const void* q, const void* k, const int32_t* ia, const int32_t* ib, int n_pairs, int B, int H, int N, int D,
-                      int dtype, int grid_w, int32_t* match, float* weight, float* expect, float* attn, int32_t* status, void* scratch,
-                      size_t scratch_bytes, hipStream_t s) {
-    const size_t need = pair_align_scratch_bytes(n_pairs, B, H, N, D);
-    if (need == 0 || grid_w < 1 || N % grid_w) return DSIM_ERR_INVALID;
-    if (n_pairs * 2 > 65535 || B * H > 65535) return DSIM_ERR_INVALID;
+// token alignments (align_stats_kernel, align_kernel): any head dim of DSIM_FOR_EACH_D, any N, the three dtypes (a.v and
+// a.similarity are not used)
+int launch_pair_align(const PairArgs& a, int dtype, int grid_w, int32_t* match, float* weight, float* expect, float* attn,
+                      int32_t* status, hipStream_t s) {
+    const int st = pair_args_check(a, dtype);
+    if (st != DSIM_OK) return st;
+    if (grid_w < 1 || a.N % grid_w) return DSIM_ERR_INVALID;
     // 32-bit extents: an attention tensor stays below 2 GiB (the caller chunks the pairs); 16-byte aligned where its rows are
     // (N a multiple of 4: align_kernel stores four keys at a time)
-    if (attn && ((size_t)n_pairs * 2 * N * N * sizeof(float) >= ((size_t)1 << 31) || ((N & 3) == 0 && ((uintptr_t)attn & 15))))
+    if (attn && ((size_t)a.n_pairs * 2 * a.N * a.N * sizeof(float) >= ((size_t)1 << 31) || ((a.N & 3) == 0 && ((uintptr_t)attn & 15))))
         return DSIM_ERR_INVALID;
-    if (scratch_bytes < need) return DSIM_ERR_WORKSPACE;
-    if (dtype == DSIM_H16)
-        return launch_align_t<h16>(q, k, ia, ib, n_pairs, B, H, N, D, grid_w, match, weight, expect, attn, status, scratch, s);
-#ifndef DSIM_H16_IS_F16
-    if (dtype == DSIM_F32)
-        return launch_align_t<float>(q, k, ia, ib, n_pairs, B, H, N, D, grid_w, match, weight, expect, attn, status, scratch, s);
-    if (dtype == DSIM_F16)
-        return DSIM_F16_TWIN(launch_pair_align(q, k, ia, ib, n_pairs, B, H, N, D, dtype, grid_w, match, weight, expect, attn, status, scratch,
-                                               scratch_bytes, s));
-#endif
-    return DSIM_ERR_INVALID;
+    if (a.scratch_bytes < pair_align_scratch_bytes(a.n_pairs, a.B, a.H, a.N, a.D)) return DSIM_ERR_WORKSPACE;
+    return by_h16_dtype(
+        dtype, [&](auto e) { return launch_align_t<typename decltype(e)::type>(a, grid_w, match, weight, expect, attn, status, s); },
+        [&] { return DSIM_F16_TWIN(launch_pair_align(a, dtype, grid_w, match, weight, expect, attn, status, s)); });
 }
 }  // namespace DSIM_H16_NS
 

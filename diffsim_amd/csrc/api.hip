@@ -3,6 +3,7 @@
 // tests and micro-benchmarks drive.  The executors' own groups live beside their walks: dsim_unet_* in unet.hip, dsim_vae_* in
 // vae.hip, dsim_dit_* in dit.hip.
 #include <cstdio>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -34,108 +35,100 @@ int dsim_device_count(void) {
     return n;
 }
 
+// ---- the score tails ----
+// A workspace query adds 256 bytes to what the launcher asks for (0 stays 0: the call is not served), and an entry point's prologue
+// spends them: no required pointer NULL and no refusal of the arguments themselves (DSIM_ERR_INVALID), then the workspace aligned
+// up to 256 bytes inside that slack (DSIM_ERR_WORKSPACE).  The launchers repeat the argument checks: they are entry points too.
+static size_t with_slack(size_t bytes) { return bytes ? bytes + 256 : 0; }
+static int tail_prologue(std::initializer_list<const void*> required, int refusal, void*& workspace, size_t& workspace_bytes) {
+    for (const void* p : required)
+        if (!p) return DSIM_ERR_INVALID;
+    if (!workspace || refusal != DSIM_OK) return DSIM_ERR_INVALID;
+    return align_workspace(workspace, workspace_bytes) ? DSIM_OK : DSIM_ERR_WORKSPACE;
+}
+
 size_t dsim_pair_score_workspace_bytes(int n_pairs, int B, int H, int N, int D) {
     return pair_score_scratch_bytes(n_pairs, B, H, N, D) + 256;
 }
 
-// status may be NULL here; dsim_pair_score_status requires it
-static int pair_score(const void* q, const void* k, const void* v, const int32_t* idx_a, const int32_t* idx_b, int n_pairs, int B,
-                      int H, int N, int D, int dtype, int similarity, float* out_scores, int32_t* status, void* workspace,
-                      size_t workspace_bytes, void* stream) {
-    if (!q || !k || !v || !idx_a || !idx_b || !out_scores || !workspace) return DSIM_ERR_INVALID;
-    if (similarity != 0 && similarity != 1) return DSIM_ERR_INVALID;
-    if (!align_workspace(workspace, workspace_bytes)) return DSIM_ERR_WORKSPACE;
-    return launch_pair_score(q, k, v, idx_a, idx_b, n_pairs, B, H, N, D, dtype, similarity, out_scores, workspace, workspace_bytes,
-                             (hipStream_t)stream, status);
+// status may be NULL here; dsim_pair_score_status requires it.  (tiled = false: whether B*H rides on a grid axis is the launcher's to say)
+static int pair_score(PairArgs a, int dtype, float* out_scores, int32_t* status, void* stream) {
+    const int st = tail_prologue({a.q, a.k, a.v, a.idx_a, a.idx_b, out_scores}, pair_args_check(a, dtype, false), a.scratch, a.scratch_bytes);
+    return st != DSIM_OK ? st : launch_pair_score(a, dtype, out_scores, status, (hipStream_t)stream);
 }
 
 int dsim_pair_score(const void* q, const void* k, const void* v, const int32_t* idx_a, const int32_t* idx_b, int n_pairs,
                     int B, int H, int N, int D, int dtype, int similarity, float* out_scores, void* workspace,
                     size_t workspace_bytes, void* stream) {
-    return pair_score(q, k, v, idx_a, idx_b, n_pairs, B, H, N, D, dtype, similarity, out_scores, nullptr, workspace, workspace_bytes,
-                      stream);
+    return pair_score({q, k, v, idx_a, idx_b, n_pairs, B, H, N, D, similarity, workspace, workspace_bytes}, dtype, out_scores, nullptr, stream);
 }
 
 int dsim_pair_score_status(const void* q, const void* k, const void* v, const int32_t* idx_a, const int32_t* idx_b,
                            int n_pairs, int B, int H, int N, int D, int dtype, int similarity, float* out_scores,
                            int32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
     if (!status) return DSIM_ERR_INVALID;
-    return pair_score(q, k, v, idx_a, idx_b, n_pairs, B, H, N, D, dtype, similarity, out_scores, status, workspace, workspace_bytes,
-                      stream);
+    return pair_score({q, k, v, idx_a, idx_b, n_pairs, B, H, N, D, similarity, workspace, workspace_bytes}, dtype, out_scores, status, stream);
 }
 
 size_t dsim_score_matrix_workspace_bytes(int n_a, int n_b, int B, int H, int N, int D, int dtype) {
-    const size_t b = score_matrix_scratch_bytes(n_a, n_b, B, H, N, D, dtype);
-    return b ? b + 256 : 0;
+    return with_slack(score_matrix_scratch_bytes(n_a, n_b, B, H, N, D, dtype));
 }
 
 int dsim_score_matrix(const void* qa, const void* ka, const void* va, int n_a, const void* qb, const void* kb, const void* vb, int n_b,
                       int B, int H, int N, int D, int dtype, int similarity, float* out, int32_t* status, void* workspace,
                       size_t workspace_bytes, void* stream) {
-    if (!qa || !ka || !va || !qb || !kb || !vb || !out || !workspace) return DSIM_ERR_INVALID;
-    if (!align_workspace(workspace, workspace_bytes)) return DSIM_ERR_WORKSPACE;
+    const int st = tail_prologue({qa, ka, va, qb, kb, vb, out}, DSIM_OK, workspace, workspace_bytes);
+    if (st != DSIM_OK) return st;
     return launch_score_matrix(qa, ka, va, n_a, qb, kb, vb, n_b, B, H, N, D, dtype, similarity, out, status, workspace,
                                workspace_bytes, (hipStream_t)stream);
 }
 
 size_t dsim_pair_score_maps_workspace_bytes(int n_pairs, int B, int H, int N, int D) {
-    const size_t b = pair_score_maps_scratch_bytes(n_pairs, B, H, N);
-    return b && D >= 1 ? b + 256 : 0;
+    return D >= 1 ? with_slack(pair_score_maps_scratch_bytes(n_pairs, B, H, N)) : 0;
 }
 
 int dsim_pair_score_maps(const void* q, const void* k, const void* v, const int32_t* idx_a, const int32_t* idx_b, int n_pairs, int B,
                          int H, int N, int D, int dtype, int similarity, float* score, float* local, float* contrib, int32_t* status,
                          void* workspace, size_t workspace_bytes, void* stream) {
-    if (!q || !k || !v || !idx_a || !idx_b || !score || !workspace) return DSIM_ERR_INVALID;
-    if (similarity != 0 && similarity != 1) return DSIM_ERR_INVALID;
-    if (!align_workspace(workspace, workspace_bytes)) return DSIM_ERR_WORKSPACE;
-    return launch_pair_score_maps(q, k, v, idx_a, idx_b, n_pairs, B, H, N, D, dtype, similarity, score, local, contrib, status,
-                                  workspace, workspace_bytes, (hipStream_t)stream);
+    PairArgs a{q, k, v, idx_a, idx_b, n_pairs, B, H, N, D, similarity, workspace, workspace_bytes};
+    const int st = tail_prologue({q, k, v, idx_a, idx_b, score}, pair_args_check(a, dtype), a.scratch, a.scratch_bytes);
+    return st != DSIM_OK ? st : launch_pair_score_maps(a, dtype, score, local, contrib, status, (hipStream_t)stream);
 }
 
 size_t dsim_pair_score_regions_workspace_bytes(int n_feat, int n_pairs, int B, int H, int N, int D) {
-    const size_t b = pair_score_regions_scratch_bytes(n_feat, n_pairs, B, H, N, D);
-    return b ? b + 256 : 0;
+    return with_slack(pair_score_regions_scratch_bytes(n_feat, n_pairs, B, H, N, D));
 }
 
 int dsim_pair_score_regions(const void* q, const void* k, const void* v, const uint8_t* mask, int n_feat, const int32_t* idx_a,
                             const int32_t* idx_b, int n_pairs, int B, int H, int N, int D, int dtype, int similarity, float* out_scores,
                             int32_t* status, int32_t* counts, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!q || !k || !v || !mask || !idx_a || !idx_b || !out_scores || !workspace) return DSIM_ERR_INVALID;
-    if (dtype != DSIM_F32 && dtype != DSIM_BF16 && dtype != DSIM_F16) return DSIM_ERR_INVALID;
-    if (similarity != 0 && similarity != 1) return DSIM_ERR_INVALID;
-    if (pair_score_regions_scratch_bytes(n_feat, n_pairs, B, H, N, D) == 0) return DSIM_ERR_INVALID;
-    if (!align_workspace(workspace, workspace_bytes)) return DSIM_ERR_WORKSPACE;
-    return launch_pair_score_regions(q, k, v, mask, n_feat, idx_a, idx_b, n_pairs, B, H, N, D, dtype, similarity, out_scores, status,
-                                     counts, workspace, workspace_bytes, (hipStream_t)stream);
+    PairArgs a{q, k, v, idx_a, idx_b, n_pairs, B, H, N, D, similarity, workspace, workspace_bytes};
+    const bool served = pair_score_regions_scratch_bytes(n_feat, n_pairs, B, H, N, D) != 0;
+    const int st = tail_prologue({q, k, v, mask, idx_a, idx_b, out_scores}, served ? pair_args_check(a, dtype) : DSIM_ERR_INVALID, a.scratch,
+                                 a.scratch_bytes);
+    return st != DSIM_OK ? st : launch_pair_score_regions(a, dtype, mask, n_feat, out_scores, status, counts, (hipStream_t)stream);
 }
 
 size_t dsim_pair_align_workspace_bytes(int n_pairs, int B, int H, int N, int D) {
-    const size_t b = pair_align_scratch_bytes(n_pairs, B, H, N, D);
-    return b ? b + 256 : 0;
+    return with_slack(pair_align_scratch_bytes(n_pairs, B, H, N, D));
 }
 
 int dsim_pair_align(const void* q, const void* k, const int32_t* idx_a, const int32_t* idx_b, int n_pairs, int B, int H, int N, int D,
                     int dtype, int grid_w, int32_t* match, float* weight, float* expect, float* attn, int32_t* status, void* workspace,
                     size_t workspace_bytes, void* stream) {
-    if (!q || !k || !idx_a || !idx_b || !workspace) return DSIM_ERR_INVALID;
-    if (pair_align_scratch_bytes(n_pairs, B, H, N, D) == 0) return DSIM_ERR_INVALID;
-    if (!align_workspace(workspace, workspace_bytes)) return DSIM_ERR_WORKSPACE;
-    return launch_pair_align(q, k, idx_a, idx_b, n_pairs, B, H, N, D, dtype, grid_w, match, weight, expect, attn, status, workspace,
-                             workspace_bytes, (hipStream_t)stream);
+    PairArgs a{q, k, nullptr, idx_a, idx_b, n_pairs, B, H, N, D, 0, workspace, workspace_bytes};
+    const int st = tail_prologue({q, k, idx_a, idx_b}, pair_args_check(a, dtype), a.scratch, a.scratch_bytes);
+    return st != DSIM_OK ? st : launch_pair_align(a, dtype, grid_w, match, weight, expect, attn, status, (hipStream_t)stream);
 }
 
-size_t dsim_text_attention_workspace_bytes(int n_images, int N, int L) {
-    const size_t b = text_attention_scratch_bytes(n_images, N, L);
-    return b ? b + 256 : 0;
-}
+size_t dsim_text_attention_workspace_bytes(int n_images, int N, int L) { return with_slack(text_attention_scratch_bytes(n_images, N, L)); }
 
 int dsim_text_attention(const void* xq, int ldq, const void* xk, int ldk, int n_images, int n_kv, int H, int N, int L, int D, int dtype,
                         const float* token_weight, int n_w, float rel_threshold, float* attn, float* saliency, uint8_t* mask,
                         int32_t* counts, int32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!xq || !xk || !workspace) return DSIM_ERR_INVALID;
-    if (text_attention_scratch_bytes(n_images, N, L) == 0) return DSIM_ERR_INVALID;
-    if (!align_workspace(workspace, workspace_bytes)) return DSIM_ERR_WORKSPACE;
+    const int st = tail_prologue({xq, xk}, text_attention_scratch_bytes(n_images, N, L) ? DSIM_OK : DSIM_ERR_INVALID, workspace,
+                                 workspace_bytes);
+    if (st != DSIM_OK) return st;
     return launch_text_attention(xq, ldq, xk, ldk, n_images, n_kv, H, N, L, D, dtype, token_weight, n_w, rel_threshold, attn, saliency,
                                  mask, counts, status, workspace, workspace_bytes, (hipStream_t)stream);
 }

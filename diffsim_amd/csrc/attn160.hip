@@ -40,7 +40,7 @@
 //
 // Units are dealt so that the two directions of a (pair, CFG half, head) -- which read the same four K / V tensors -- run at
 // the same time on two workgroups of one XCD (blockIdx.x % 8 names the XCD under round-robin placement: speed only).
-#include "common.h"
+#include "tail_core.h"      // (the f64 finish arithmetic; nothing of the tiled core runs here)
 
 namespace dsim {
 namespace {
@@ -540,7 +540,7 @@ __global__ __launch_bounds__(512, 2) void pair_tail160_kernel(const h16* __restr
 }
 
 // One wave per pair: f64 fold of the per-wave partials in a fixed order (lane i adds entries i, i + 64, ...; xor tree), then
-// cosine / mse and the mean of the two directions (diffsim.py:187-197; F.cosine_similarity eps = 1e-8)
+// the two directions' values and their mean (tail_core.h's finish arithmetic)
 __global__ __launch_bounds__(64) void pair_finish160_kernel(const float* __restrict__ part, int nblk, int mse, double count,
                                                             float* __restrict__ out, int32_t* __restrict__ status) {
     const int p = blockIdx.x, lane = threadIdx.x;
@@ -558,17 +558,9 @@ __global__ __launch_bounds__(64) void pair_finish160_kernel(const float* __restr
             x2 += __shfl_xor(x2, off);
             y2 += __shfl_xor(y2, off);
         }
-        if (mse) res += a / count;
-        else {
-            const double nx = sqrt(x2), ny = sqrt(y2);
-            res += a / (fmax(nx, 1e-8) * fmax(ny, 1e-8));
-        }
+        res += direction_value(a, x2, y2, mse, count);
     }
-    if (lane == 0) {
-        const float sc = (float)(res * 0.5);
-        out[p] = sc;
-        if (status) status[p] = (sc - sc == 0.0f) ? 0 : 1;
-    }
+    if (lane == 0) store_score(res, out + p, status ? status + p : nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------------
@@ -1130,7 +1122,7 @@ int grid160(long units, int quantum) {
 float softmax_c160() { return (1.0f / sqrtf((float)A_D)) * 1.4426950408889634f; }
 
 // per-wave partials [item][dir][bh][wave] of pair_finish160_kernel, for n items (pairs or cells), 256-byte aligned
-size_t part160_bytes(long n, int B, int H) { return (((size_t)n * 2 * B * H * 8 * 4 * sizeof(float)) + 255) & ~(size_t)255; }
+size_t part160_bytes(long n, int B, int H) { return up256((size_t)n * 2 * B * H * 8 * 4 * sizeof(float)); }
 
 }  // namespace
 
@@ -1169,7 +1161,7 @@ size_t pair_score160_scratch_bytes(int n_pairs, int B, int H) {
 // ---- score matrix at the default tap: sdpa160_kernel writes every image's self output, self_lanes160_kernel reorders it lane-major,
 // matrix_cross160_kernel writes the cells' partials, pair_finish160_kernel folds them.
 // Workspace: [self A | self B | lane-major self A | lane-major self B | partials], each 256-byte aligned.
-static size_t mat160_self_bytes(int n, int B, int H) { return (((size_t)n * B * A_N * H * A_D * 2) + 255) & ~(size_t)255; }
+static size_t mat160_self_bytes(int n, int B, int H) { return up256((size_t)n * B * A_N * H * A_D * 2); }
 
 size_t score_matrix160_scratch_bytes(int n_a, int n_b, int B, int H) {
     return 2 * (mat160_self_bytes(n_a, B, H) + mat160_self_bytes(n_b, B, H)) + part160_bytes((long)n_a * n_b, B, H);
@@ -1211,22 +1203,23 @@ int launch_score_matrix160(const void* qa, const void* ka, const void* va, int n
     return DSIM_OK;
 }
 
-int launch_pair_score160(const void* q, const void* k, const void* v, const int32_t* ia, const int32_t* ib, int n_pairs, int B,
-                         int H, int mse, float* out, void* scratch, size_t scratch_bytes, hipStream_t s, int32_t* status) {
-    if (scratch_bytes < pair_score160_scratch_bytes(n_pairs, B, H)) return DSIM_ERR_WORKSPACE;
-    const int grid = grid160(2l * n_pairs * B * H, 16);
+// a: launch_pair_score's arguments, checked there (N = 256, D = 160)
+int launch_pair_score160(const PairArgs& a, float* out, int32_t* status, hipStream_t s) {
+    if (a.scratch_bytes < pair_score160_scratch_bytes(a.n_pairs, a.B, a.H)) return DSIM_ERR_WORKSPACE;
+    const int grid = grid160(2l * a.n_pairs * a.B * a.H, 16);
     const float c = softmax_c160();
+    char* park = (char*)a.scratch + part160_bytes(a.n_pairs, a.B, a.H);
 #ifdef DSIM_DEVTOOLS
-    const int st = launch_lds<pair_tail160_kernel>(dim3(grid), dim3(512), A_LDS, s, (const h16*)q, (const h16*)k, (const h16*)v, ia, ib, n_pairs,
-                                                   B, H, c, mse, (float*)scratch, (char*)scratch + part160_bytes(n_pairs, B, H),
-                                                   g_tail160_dbg, g_tail160_exp);
+    const int st = launch_lds<pair_tail160_kernel>(dim3(grid), dim3(512), A_LDS, s, (const h16*)a.q, (const h16*)a.k, (const h16*)a.v, a.idx_a,
+                                                   a.idx_b, a.n_pairs, a.B, a.H, c, a.similarity, (float*)a.scratch, park, g_tail160_dbg,
+                                                   g_tail160_exp);
 #else
-    const int st = launch_lds<pair_tail160_kernel>(dim3(grid), dim3(512), A_LDS, s, (const h16*)q, (const h16*)k, (const h16*)v, ia, ib, n_pairs,
-                                                   B, H, c, mse, (float*)scratch, (char*)scratch + part160_bytes(n_pairs, B, H));
+    const int st = launch_lds<pair_tail160_kernel>(dim3(grid), dim3(512), A_LDS, s, (const h16*)a.q, (const h16*)a.k, (const h16*)a.v, a.idx_a,
+                                                   a.idx_b, a.n_pairs, a.B, a.H, c, a.similarity, (float*)a.scratch, park);
 #endif
     if (st != DSIM_OK) return st;
-    hipLaunchKernelGGL(pair_finish160_kernel, dim3(n_pairs), dim3(64), 0, s, (const float*)scratch, B * H * 8, mse,
-                       (double)B * H * A_N * A_D, out, status);
+    hipLaunchKernelGGL(pair_finish160_kernel, dim3(a.n_pairs), dim3(64), 0, s, (const float*)a.scratch, a.B * a.H * 8, a.similarity,
+                       (double)a.B * a.H * A_N * A_D, out, status);
     DSIM_HIP_CHECK(hipGetLastError());
     return DSIM_OK;
 }

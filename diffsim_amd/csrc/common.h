@@ -109,6 +109,22 @@ int by_dtype(int dtype, F&& f) {
     }
     return DSIM_ERR_INVALID;
 }
+// The same switch in a source compiled once per 16-bit type (h16_api.h), to the types this object's kernels are instantiated for:
+// f(Elem<h16>{}) for the object's own 16-bit dtype in every object and f(Elem<float>{}) for DSIM_F32 in the bf16 objects alone -- the
+// fp16 objects instantiate no f32 kernel.  DSIM_F16 seen from a bf16 object is its twin's: twin() forwards the call, written at the
+// call site as [&] { return DSIM_F16_TWIN(launcher(args)); }.  DSIM_ERR_INVALID for anything else.
+template <typename F, typename Twin>
+int by_h16_dtype(int dtype, F&& f, Twin&& twin) {
+    if (dtype == DSIM_H16) return f(Elem<h16>{});
+#ifndef DSIM_H16_IS_F16
+    if (dtype == DSIM_F32) return f(Elem<float>{});
+    if (dtype == DSIM_F16) return twin();
+#endif
+    return DSIM_ERR_INVALID;
+}
+
+// parts of a workspace start on 256-byte boundaries
+static inline size_t up256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 
 // ---------------------------------------------------------------------------------------------
 // implicit-GEMM (linear / 1x1 conv / 3x3 conv) -- gemm.hip
@@ -326,6 +342,20 @@ struct AttnLaunchRec {
 extern thread_local AttnLaunchRec g_attn_last_launch;
 int launch_attention_fp8(const AttnArgs& a, hipStream_t s);      // h16 in/out, e4m3 MFMAs (attention_fp8.hip)
 
+// the score tails over pairs of feature images -- tails.hip, regions.hip, align.hip, attn160.hip: what launch_pair_score, _maps,
+// _regions, _align and launch_pair_score160 share; their outputs and the compute dtype travel beside it
+struct PairArgs {
+    const void* q = nullptr;                    // q, k, v: [n_feat][B][N][H*D] contiguous, the compute dtype (v: unused by the
+    const void* k = nullptr;                    //   alignments)
+    const void* v = nullptr;
+    const int32_t* idx_a = nullptr;             // device [n_pairs] each: pair p is (image idx_a[p], image idx_b[p])
+    const int32_t* idx_b = nullptr;
+    int n_pairs = 0, B = 0, H = 0, N = 0, D = 0;
+    int similarity = 0;                         // 0 cosine, 1 mse
+    void* scratch = nullptr;                    // 256-byte aligned; the launcher's *_scratch_bytes
+    size_t scratch_bytes = 0;
+};
+
 // row-resident fused feed-forward of the 320-channel transformer blocks (h16) -- rowres.hip
 //   out = x + W2 (h * gelu(g)) + b2,  [h ; g] = W1 LN(x) + b1
 struct FFArgs {
@@ -357,6 +387,13 @@ inline bool gemm_gn_stats_tile(const GemmArgs& a, int dtype) {
     q.gn_part = &asked; q.gn_hw = hw; q.zero_page = &asked;
     GemmLaunchRec plan;
     return gemm_plan(q, dtype, &plan) == DSIM_OK;
+}
+// The refusals every pair launcher makes before its own (DSIM_ERR_INVALID): a dtype outside the three, a similarity outside 0 | 1, a
+// shape pair_shape_served refuses.  tiled = false: a persistent launch, whose grid carries B*H on no axis.
+inline int pair_args_check(const PairArgs& a, int dtype, bool tiled = true) {
+    if (dtype != DSIM_F32 && dtype != DSIM_BF16 && dtype != DSIM_F16) return DSIM_ERR_INVALID;
+    if (a.similarity != 0 && a.similarity != 1) return DSIM_ERR_INVALID;
+    return pair_shape_served(a.n_pairs, a.B, a.H, a.N, a.D, tiled) ? DSIM_OK : DSIM_ERR_INVALID;
 }
 }  // namespace DSIM_H16_NS
 // ... and, seen from the bf16 objects of the product build, their fp16 twins: DSIM_F16_TWIN(f(args)) is how a bf16 launcher forwards

@@ -28,38 +28,32 @@ const char* attention_kernel_kind(const AttnArgs& a, int dtype);      // "_p160"
 // the dsim_attn_kind launch_attention would start for these arguments (host only, launches nothing); DSIM_ERR_INVALID where it
 // would refuse them
 int attention_plan(const AttnArgs& a, int dtype);
+// the pair launchers (PairArgs, common.h) serve this shape; tiled = false: for a persistent grid (pair_args_check, common.h, asks)
+bool pair_shape_served(int n_pairs, int B, int H, int N, int D, bool tiled = true);
 size_t pair_score_scratch_bytes(int n_pairs, int B, int H, int N, int D);
-int launch_pair_score(const void* q, const void* k, const void* v, const int32_t* idx_a,
-                      const int32_t* idx_b, int n_pairs, int B, int H, int N, int D, int dtype,
-                      int similarity, float* out, void* scratch, size_t scratch_bytes, hipStream_t s,
-                      int32_t* status = nullptr);
+int launch_pair_score(const PairArgs& a, int dtype, float* out, int32_t* status, hipStream_t s);      // status may be NULL
 // the score tail at SD1.5's default tap (256 tokens, head dim 160, 16-bit types): persistent workgroups, K / V streamed once per
 // 256 queries through an LDS-DMA ring -- attn160.hip
 bool pair_score160_applies(int N, int D, int dtype);
 size_t pair_score160_scratch_bytes(int n_pairs, int B, int H);
-int launch_pair_score160(const void* q, const void* k, const void* v, const int32_t* idx_a, const int32_t* idx_b, int n_pairs, int B,
-                         int H, int mse, float* out, void* scratch, size_t scratch_bytes, hipStream_t s, int32_t* status);
+int launch_pair_score160(const PairArgs& a, float* out, int32_t* status, hipStream_t s);
 // similarity maps: the score tail kept per query token (pair_map_kernel: pair_tail_kernel's body with a per-token epilogue, any
 // shape and dtype) -- tails.hip
 //   score [n_pairs]; local, contrib (each may be NULL) [n_pairs][2][N]; status (may be NULL) [n_pairs]
 size_t pair_score_maps_scratch_bytes(int n_pairs, int B, int H, int N);
-int launch_pair_score_maps(const void* q, const void* k, const void* v, const int32_t* idx_a, const int32_t* idx_b, int n_pairs, int B,
-                           int H, int N, int D, int dtype, int similarity, float* score, float* local, float* contrib, int32_t* status,
-                           void* scratch, size_t scratch_bytes, hipStream_t s);
+int launch_pair_score_maps(const PairArgs& a, int dtype, float* score, float* local, float* contrib, int32_t* status, hipStream_t s);
 // token alignments: softmax(Q_a K_b^T / sqrt(D)) averaged over the CFG halves and heads, per query token its argmax, weight and
-// soft-argmax position, and on request the probabilities (align_stats_kernel + align_kernel, any shape and dtype) -- tails.hip
+// soft-argmax position, and on request the probabilities (align_stats_kernel + align_kernel, any shape and dtype) -- align.hip
 //   match, weight [n_pairs][2][N]; expect [n_pairs][2][N][2]; attn [n_pairs][2][N][N]; status [n_pairs]; each may be NULL
 size_t pair_align_scratch_bytes(int n_pairs, int B, int H, int N, int D);      // 0: shape not served
-int launch_pair_align(const void* q, const void* k, const int32_t* idx_a, const int32_t* idx_b, int n_pairs, int B, int H, int N, int D,
-                      int dtype, int grid_w, int32_t* match, float* weight, float* expect, float* attn, int32_t* status, void* scratch,
-                      size_t scratch_bytes, hipStream_t s);
+int launch_pair_align(const PairArgs& a, int dtype, int grid_w, int32_t* match, float* weight, float* expect, float* attn,
+                      int32_t* status, hipStream_t s);
 // region scores: the score tail restricted to a token region per feature image (mask [n_feat][N] bytes, non-zero = on): the
 // tail's arithmetic on the regions' rows, taken through ascending token lists built on the device -- regions.hip
 //   out [n_pairs]; status (may be NULL) [n_pairs]: 0, 1 non-finite, 2 empty region; counts (may be NULL) [n_feat]
 size_t pair_score_regions_scratch_bytes(int n_feat, int n_pairs, int B, int H, int N, int D);      // 0: call not served
-int launch_pair_score_regions(const void* q, const void* k, const void* v, const uint8_t* mask, int n_feat, const int32_t* idx_a,
-                              const int32_t* idx_b, int n_pairs, int B, int H, int N, int D, int dtype, int similarity, float* out,
-                              int32_t* status, int32_t* counts, void* scratch, size_t scratch_bytes, hipStream_t s);
+int launch_pair_score_regions(const PairArgs& a, int dtype, const uint8_t* mask, int n_feat, float* out, int32_t* status,
+                              int32_t* counts, hipStream_t s);
 // text attention maps: the tapped block's cross-attention on the conditional CFG half, averaged over the heads; its weighted sum over
 // the prompt tokens (saliency) and the token region above rel_threshold x the image's mean saliency (text_attn_kernel,
 // text_region_kernel, any head dim and dtype, 1 <= L <= 128) -- textattn.hip

@@ -1,7 +1,8 @@
 // What the score tails share on top of the tiled attention core (attn_core.h): the rounding of attend's output to the pipeline
-// dtype, the products of a cross output against a self output, and a workgroup's partial.  Shared by tails.hip (pairs, maps,
-// matrices) and regions.hip (region scores), which must round and multiply alike to agree bit for bit; everything here lives in
-// their dsim::(anonymous namespace).
+// dtype, the products of a cross output against a self output, a workgroup's partial, the two-attention pair body (pair_tail_body:
+// tails.hip's pair and map kernels in row order, regions.hip's region tail through row lists) and the f64 finish arithmetic
+// (direction_value, store_score, pair_finish_kernel).  Shared by tails.hip (pairs, maps, matrices) and regions.hip (region scores),
+// which must round and multiply alike to agree bit for bit; everything here lives in their dsim::(anonymous namespace).
 #pragma once
 #include "attn_core.h"
 
@@ -90,6 +91,144 @@ __device__ __forceinline__ void store_block_partial(TailSums t, int lane, int wa
         o[2] = (red[0][2] + red[1][2]) + (red[2][2] + red[3][2]);
         o[3] = 0.f;
     }
+}
+
+// One direction of a pair in a 128-query workgroup: the self and the cross attention on the same Q fragments, then their products.
+// The epilogue is one partial per workgroup, [pair][dir][bh][qtile][4] f32 (PER_TOKEN false), or one per query token,
+// [pair][dir][comp][bh][N] f32, comp: dot | x2 | y2, or sqd | - | - (PER_TOKEN true).
+// Rows (attn_core.h): RowsInOrder -- query position t of an image is its row t and every image has N of them; list and cnt are not
+// read.  RowsListed -- the rows of an image i are list[i][0 .. cnt[i]), ascending: position t is row list[i][t] and the image's count
+// stands where N stood; the grid being sized for N, a workgroup past the query image's count, or of a pair with an empty image,
+// writes a zero partial and leaves as a whole before any barrier.
+// grid (ceil(N/128), B*H, n_pairs*2)
+template <typename T, int D, bool PER_TOKEN, typename Rows>
+__device__ __forceinline__ void pair_tail_body(const T* __restrict__ qg, const T* __restrict__ kg, const T* __restrict__ vg,
+                                               const int32_t* __restrict__ list, const int32_t* __restrict__ cnt,
+                                               const int32_t* __restrict__ idx_a, const int32_t* __restrict__ idx_b, int B, int H, int N,
+                                               float scale_log2, int mse, float* __restrict__ part) {
+    static_assert(!(PER_TOKEN && Rows::LISTED), "the per-token epilogue stores by row: rows in order only");
+    typedef ACfg<T, D> C;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, l31 = lane & 31;
+    const int bh = blockIdx.y, b = bh / H, h = bh - b * H;
+    const int pair = blockIdx.z >> 1, dir = blockIdx.z & 1;
+    const int ia = idx_a[pair], ib = idx_b[pair];
+    const int iq = dir ? ib : ia;        // query image (also the "self" keys/values)
+    const int ix = dir ? ia : ib;        // the other image ("cross" keys/values)
+    int nq = N, nx = N;                  // the two images' row counts
+    Rows rq, rx;
+    float* o = nullptr;                  // the workgroup's partial
+    if constexpr (Rows::LISTED) {
+        nq = cnt[iq];
+        nx = cnt[ix];
+        o = part + ((((size_t)pair * 2 + dir) * gridDim.y + bh) * gridDim.x + blockIdx.x) * 4;
+        if ((int)blockIdx.x * 128 >= nq || nx == 0) {          // (uniform over the workgroup)
+            if (threadIdx.x == 0) o[0] = o[1] = o[2] = o[3] = 0.f;
+            return;
+        }
+        rq.list = list + (size_t)iq * N;
+        rx.list = list + (size_t)ix * N;
+    }
+    const int ld = H * D;
+    const size_t img = (size_t)B * N * ld;
+    const int t = blockIdx.x * 128 + wave * 32 + l31;          // query position
+    int q = t < nq ? t : nq - 1;                               // its row (a position past the end: the last one's)
+    if constexpr (Rows::LISTED) q = rq.list[q];
+    const size_t boff = (size_t)b * N * ld + h * D;
+    QFrags<T, D> qf;
+    load_q<T, D>(qf, qg + iq * img + boff + (size_t)q * ld, half, scale_log2);
+    TailSums s;
+    if constexpr (sizeof(T) == 2) {
+        typedef float f32x2 __attribute__((ext_vector_type(2)));
+        h16x2 osp[C::NDB][8];           // the self-attention's output, rounded to the compute dtype, two values per register
+        {
+            OAcc<T, D> osa;
+            attend<T, D, false>(qf, kg + iq * img + boff, vg + iq * img + boff, ld, nq, smem, osa, nullptr, rq);
+            settle<T, D>(osa);
+#pragma unroll
+            for (int db = 0; db < C::NDB; ++db)
+#pragma unroll
+                for (int r = 0; r < 16; r += 2) {
+                    osp[db][r >> 1] = __builtin_convertvector((f32x2){osa.b[db][r], osa.b[db][r + 1]}, h16x2);
+                    asm volatile("" : "+v"(osp[db][r >> 1]));          // (pinned: the f32 accumulators die here, before the second attention)
+                }
+        }
+        OAcc<T, D> oxa;
+        attend<T, D, false>(qf, kg + ix * img + boff, vg + ix * img + boff, ld, nx, smem, oxa, nullptr, rx);
+        settle<T, D>(oxa);
+        if (t < nq) s = tail_products<T, D>(oxa, half, mse, [&](int db, int r, int) { return (float)osp[db][r >> 1][r & 1]; });
+    } else {
+        OAcc<T, D> osa, oxa;
+        attend<T, D, false>(qf, kg + iq * img + boff, vg + iq * img + boff, ld, nq, smem, osa, nullptr, rq);
+        attend<T, D, false>(qf, kg + ix * img + boff, vg + ix * img + boff, ld, nx, smem, oxa, nullptr, rx);
+        settle<T, D>(osa);
+        settle<T, D>(oxa);
+        if (t < nq) s = tail_products<T, D>(oxa, half, mse, [&](int db, int r, int) { return osa.b[db][r]; });
+    }
+    if constexpr (PER_TOKEN) {
+        // a row's d values are split between the two lane halves: fold them, then the first half stores the row (128 B per wave and
+        // component, no atomics)
+        const float s0 = s.s0 + __shfl_xor(s.s0, 32);
+        const float s1 = s.s1 + __shfl_xor(s.s1, 32);
+        const float s2 = s.s2 + __shfl_xor(s.s2, 32);
+        if (half == 0 && t < N) {
+            const size_t plane = (size_t)gridDim.y * N;
+            float* po = part + ((size_t)pair * 2 + dir) * 3 * plane + (size_t)bh * N + t;
+            po[0] = s0;
+            if (!mse) { po[plane] = s1; po[2 * plane] = s2; }
+        }
+    } else {
+        if constexpr (!Rows::LISTED) o = part + ((((size_t)pair * 2 + dir) * gridDim.y + bh) * gridDim.x + blockIdx.x) * 4;
+        store_block_partial(s, lane, wave, o);
+    }
+}
+
+// ---- the f64 finish ------------------------------------------------------------------------------------------------------------
+// A direction's value from the f64 folds of its partials (diffsim.py:187-197): mse a / count, cosine a / (|x| |y|) with
+// F.cosine_similarity's eps = 1e-8 under each norm.  The denominator alone for a caller that divides many numerators by it.
+__device__ __forceinline__ double direction_denominator(double x2, double y2, int mse, double count) {
+    if (mse) return count;
+    return fmax(sqrt(x2), 1e-8) * fmax(sqrt(y2), 1e-8);
+}
+__device__ __forceinline__ double direction_value(double a, double x2, double y2, int mse, double count) {
+    return a / direction_denominator(x2, y2, mse, count);
+}
+// the score, the mean of the two directions' values, and its status (NaN guard: non-finite features surface here as a non-finite
+// score; 1 reports it)
+__device__ __forceinline__ void store_score(double both, float* __restrict__ out, int32_t* __restrict__ status) {
+    const float sc = (float)(both * 0.5);
+    *out = sc;
+    if (status) *status = (sc - sc == 0.0f) ? 0 : 1;
+}
+
+// One thread per pair: fixed-order f64 fold of the workgroups' partials [pair][dir][nblk][4], then the two directions' values and
+// their mean.  REGIONS false: count = a direction's elements B H N D.  REGIONS true (regions.hip; the partials of the workgroups that
+// left are zeros): count = B H D, the elements per row, times the query image's own row count; a pair with an empty image: NaN and
+// status 2.  cnt, idx_a and idx_b are read only then.
+template <bool REGIONS>
+__global__ void pair_finish_kernel(const float* __restrict__ part, const int32_t* __restrict__ cnt, const int32_t* __restrict__ idx_a,
+                                   const int32_t* __restrict__ idx_b, int n_pairs, int nblk, int mse, double count,
+                                   float* __restrict__ out, int32_t* __restrict__ status) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n_pairs) return;
+    int n[2] = {1, 1};
+    if constexpr (REGIONS) {
+        n[0] = cnt[idx_a[p]];
+        n[1] = cnt[idx_b[p]];
+        if (n[0] == 0 || n[1] == 0) {
+            out[p] = __builtin_nanf("");
+            if (status) status[p] = 2;
+            return;
+        }
+    }
+    double res = 0.0;
+    for (int dir = 0; dir < 2; ++dir) {
+        double a = 0.0, x2 = 0.0, y2 = 0.0;
+        const float* o = part + ((size_t)p * 2 + dir) * nblk * 4;
+        for (int i = 0; i < nblk; ++i) { a += o[4 * i]; x2 += o[4 * i + 1]; y2 += o[4 * i + 2]; }
+        res += direction_value(a, x2, y2, mse, REGIONS ? count * n[dir] : count);
+    }
+    store_score(res, out + p, status ? status + p : nullptr);
 }
 
 }  // namespace

@@ -7,108 +7,19 @@
 //                      direction share Q and run in one workgroup; O never leaves registers, only
 //                      three f32 partial sums per workgroup reach HBM and a second fixed-order pass
 //                      folds them (no float atomics => bit-reproducible scores).
+// pair_tail_kernel and pair_map_kernel name the in-order instantiations of tail_core.h's pair_tail_body (the listed one is
+// regions.hip's); the finish arithmetic and pair_finish_kernel are tail_core.h's too.  The launchers take PairArgs (common.h).
 #include "tail_core.h"
 
 namespace dsim {
 namespace {
-
-// One direction of a pair in a 128-query workgroup: the self and the cross attention on the same Q fragments, then their products.
-// The epilogue is pair_tail_kernel's (PER_TOKEN false: one partial per workgroup, [pair][dir][bh][qtile][4] f32) or pair_map_kernel's
-// (PER_TOKEN true: one per query token, [pair][dir][comp][bh][N] f32, comp: dot | x2 | y2, or sqd | - | -).
-// grid (ceil(N/128), B*H, n_pairs*2)
-template <typename T, int D, bool PER_TOKEN>
-__device__ __forceinline__ void pair_tail_body(const T* __restrict__ qg, const T* __restrict__ kg, const T* __restrict__ vg,
-                                               const int32_t* __restrict__ idx_a, const int32_t* __restrict__ idx_b, int B, int H, int N,
-                                               float scale_log2, int mse, float* __restrict__ part) {
-    typedef ACfg<T, D> C;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, l31 = lane & 31;
-    const int bh = blockIdx.y, b = bh / H, h = bh - b * H;
-    const int pair = blockIdx.z >> 1, dir = blockIdx.z & 1;
-    const int ia = idx_a[pair], ib = idx_b[pair];
-    const int iq = dir ? ib : ia;        // query image (also the "self" keys/values)
-    const int ix = dir ? ia : ib;        // the other image ("cross" keys/values)
-    const int ld = H * D;
-    const size_t img = (size_t)B * N * ld;
-    const int q = blockIdx.x * 128 + wave * 32 + l31;
-    const int qc = q < N ? q : N - 1;
-    const size_t boff = (size_t)b * N * ld + h * D;
-    QFrags<T, D> qf;
-    load_q<T, D>(qf, qg + iq * img + boff + (size_t)qc * ld, half, scale_log2);
-    TailSums t;
-    if constexpr (sizeof(T) == 2) {
-        typedef float f32x2 __attribute__((ext_vector_type(2)));
-        h16x2 osp[C::NDB][8];           // the self-attention's output, rounded to the compute dtype, two values per register
-        {
-            OAcc<T, D> osa;
-            attend<T, D>(qf, kg + iq * img + boff, vg + iq * img + boff, ld, N, smem, osa);
-            settle<T, D>(osa);
-#pragma unroll
-            for (int db = 0; db < C::NDB; ++db)
-#pragma unroll
-                for (int r = 0; r < 16; r += 2) {
-                    osp[db][r >> 1] = __builtin_convertvector((f32x2){osa.b[db][r], osa.b[db][r + 1]}, h16x2);
-                    asm volatile("" : "+v"(osp[db][r >> 1]));          // (pinned: the f32 accumulators die here, before the second attention)
-                }
-        }
-        OAcc<T, D> oxa;
-        attend<T, D>(qf, kg + ix * img + boff, vg + ix * img + boff, ld, N, smem, oxa);
-        settle<T, D>(oxa);
-        if (q < N) t = tail_products<T, D>(oxa, half, mse, [&](int db, int r, int) { return (float)osp[db][r >> 1][r & 1]; });
-    } else {
-        OAcc<T, D> osa, oxa;
-        attend<T, D>(qf, kg + iq * img + boff, vg + iq * img + boff, ld, N, smem, osa);
-        attend<T, D>(qf, kg + ix * img + boff, vg + ix * img + boff, ld, N, smem, oxa);
-        settle<T, D>(osa);
-        settle<T, D>(oxa);
-        if (q < N) t = tail_products<T, D>(oxa, half, mse, [&](int db, int r, int) { return osa.b[db][r]; });
-    }
-    if constexpr (PER_TOKEN) {
-        // a row's d values are split between the two lane halves: fold them, then the first half stores the row (128 B per wave and
-        // component, no atomics)
-        const float s0 = t.s0 + __shfl_xor(t.s0, 32);
-        const float s1 = t.s1 + __shfl_xor(t.s1, 32);
-        const float s2 = t.s2 + __shfl_xor(t.s2, 32);
-        if (half == 0 && q < N) {
-            const size_t plane = (size_t)gridDim.y * N;
-            float* o = part + ((size_t)pair * 2 + dir) * 3 * plane + (size_t)bh * N + q;
-            o[0] = s0;
-            if (!mse) { o[plane] = s1; o[2 * plane] = s2; }
-        }
-    } else {
-        store_block_partial(t, lane, wave, part + ((((size_t)pair * 2 + dir) * gridDim.y + bh) * gridDim.x + blockIdx.x) * 4);
-    }
-}
 
 template <typename T, int D>
 __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void pair_tail_kernel(const T* __restrict__ qg, const T* __restrict__ kg,
                                                         const T* __restrict__ vg, const int32_t* __restrict__ idx_a,
                                                         const int32_t* __restrict__ idx_b, int B, int H, int N,
                                                         float scale_log2, int mse, float* __restrict__ part) {
-    pair_tail_body<T, D, false>(qg, kg, vg, idx_a, idx_b, B, H, N, scale_log2, mse, part);
-}
-
-// one thread per pair: fixed-order f64 fold of the partials, then cosine / mse and the mean of
-// the two directions (diffsim.py:187-197; F.cosine_similarity eps = 1e-8)
-__global__ void pair_finish_kernel(const float* __restrict__ part, int n_pairs, int nblk, int mse, double count,
-                                   float* __restrict__ out, int32_t* __restrict__ status) {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n_pairs) return;
-    double res = 0.0;
-    for (int dir = 0; dir < 2; ++dir) {
-        double a = 0.0, x2 = 0.0, y2 = 0.0;
-        const float* o = part + ((size_t)p * 2 + dir) * nblk * 4;
-        for (int i = 0; i < nblk; ++i) { a += o[4 * i]; x2 += o[4 * i + 1]; y2 += o[4 * i + 2]; }
-        if (mse) res += a / count;
-        else {
-            const double nx = sqrt(x2), ny = sqrt(y2);
-            res += a / (fmax(nx, 1e-8) * fmax(ny, 1e-8));
-        }
-    }
-    const float sc = (float)(res * 0.5);
-    out[p] = sc;
-    // NaN guard: non-finite features surface here as a non-finite score; report them per pair
-    if (status) status[p] = (sc - sc == 0.0f) ? 0 : 1;
+    pair_tail_body<T, D, false, RowsInOrder>(qg, kg, vg, nullptr, nullptr, idx_a, idx_b, B, H, N, scale_log2, mse, part);
 }
 
 // ---- score matrix ---------------------------------------------------------------------------------------------------------------
@@ -168,25 +79,30 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void matrix_tail_ker
     store_block_partial(t, lane, wave, part + ((((size_t)cell * 2 + dir) * gridDim.y + bh) * qt + qtile) * 4);
 }
 
+// pair_finish_kernel over n items (pairs or cells) of nblk partials per direction
+int launch_finish(const float* part, int n, int nblk, int mse, double count, float* out, int32_t* status, hipStream_t s) {
+    hipLaunchKernelGGL(pair_finish_kernel<false>, dim3((n + 63) / 64), dim3(64), 0, s, part, (const int32_t*)nullptr,
+                       (const int32_t*)nullptr, (const int32_t*)nullptr, n, nblk, mse, count, out, status);
+    DSIM_HIP_CHECK(hipGetLastError());
+    return DSIM_OK;
+}
+
 template <typename T>
-int launch_tail_t(const void* q, const void* k, const void* v, const int32_t* ia, const int32_t* ib, int n_pairs,
-                  int B, int H, int N, int D, int mse, float* out, void* scratch, hipStream_t s, int32_t* status) {
-    return with_head_dim(D, [&](auto dc) -> int {
+int launch_tail_t(const PairArgs& a, float* out, int32_t* status, hipStream_t s) {
+    return with_head_dim(a.D, [&](auto dc) -> int {
         constexpr int Dc = decltype(dc)::value, LDS = ACfg<T, Dc>::LDS;
-        const int qt = (N + 127) / 128;
-        const int st = launch_lds<pair_tail_kernel<T, Dc>>(dim3(qt, B * H, n_pairs * 2), dim3(256), LDS, s, (const T*)q, (const T*)k,
-                                                           (const T*)v, ia, ib, B, H, N, scale_log2_of(Dc), mse, (float*)scratch);
+        const int qt = (a.N + 127) / 128;
+        const int st = launch_lds<pair_tail_kernel<T, Dc>>(dim3(qt, a.B * a.H, a.n_pairs * 2), dim3(256), LDS, s, (const T*)a.q,
+                                                           (const T*)a.k, (const T*)a.v, a.idx_a, a.idx_b, a.B, a.H, a.N,
+                                                           scale_log2_of(Dc), a.similarity, (float*)a.scratch);
         if (st != DSIM_OK) return st;
-        hipLaunchKernelGGL(pair_finish_kernel, dim3((n_pairs + 63) / 64), dim3(64), 0, s, (const float*)scratch, n_pairs,
-                           qt * B * H, mse, (double)B * H * N * Dc, out, status);
-        DSIM_HIP_CHECK(hipGetLastError());
-        return DSIM_OK;
+        return launch_finish((const float*)a.scratch, a.n_pairs, qt * a.B * a.H, a.similarity, (double)a.B * a.H * a.N * Dc, out, status, s);
     });
 }
 
 // workspace of the tiled score matrix: [self A | self B | partials], each 256-byte aligned
-size_t mat_self_bytes(int n, int B, int H, int N, int D, int es) { return (((size_t)n * B * N * H * D * es) + 255) & ~(size_t)255; }
-size_t mat_part_bytes(long n_cells, int B, int H, int N) { return (((size_t)n_cells * 2 * B * H * ((N + 127) / 128) * 4 * sizeof(float)) + 255) & ~(size_t)255; }
+size_t mat_self_bytes(int n, int B, int H, int N, int D, int es) { return up256((size_t)n * B * N * H * D * es); }
+size_t mat_part_bytes(long n_cells, int B, int H, int N) { return up256((size_t)n_cells * 2 * B * H * ((N + 127) / 128) * 4 * sizeof(float)); }
 
 template <typename T>
 int launch_matrix_t(const void* qa, const void* ka, const void* va, int n_a, const void* qb, const void* kb, const void* vb, int n_b, int B,
@@ -204,10 +120,7 @@ int launch_matrix_t(const void* qa, const void* ka, const void* va, int n_a, con
         if (st != DSIM_OK) return st;
         st = launch_lds<matrix_tail_kernel<T, Dc>>(dim3(qt * nc * 2, B * H), dim3(256), LDS, s, m, scale_log2_of(Dc), mse, 0, part);
         if (st != DSIM_OK) return st;
-        hipLaunchKernelGGL(pair_finish_kernel, dim3((nc + 63) / 64), dim3(64), 0, s, (const float*)part, nc, qt * B * H, mse,
-                           (double)B * H * N * Dc, out, status);
-        DSIM_HIP_CHECK(hipGetLastError());
-        return DSIM_OK;
+        return launch_finish(part, nc, qt * B * H, mse, (double)B * H * N * Dc, out, status, s);
     });
 }
 
@@ -221,13 +134,13 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void pair_map_kernel
                                                         const T* __restrict__ vg, const int32_t* __restrict__ idx_a,
                                                         const int32_t* __restrict__ idx_b, int B, int H, int N,
                                                         float scale_log2, int mse, float* __restrict__ part) {
-    pair_tail_body<T, D, true>(qg, kg, vg, idx_a, idx_b, B, H, N, scale_log2, mse, part);
+    pair_tail_body<T, D, true, RowsInOrder>(qg, kg, vg, nullptr, nullptr, idx_a, idx_b, B, H, N, scale_log2, mse, part);
 }
 
 // one workgroup per pair, both directions: per token, a fixed-order f64 fold of the B*H partials; over tokens, per-thread strided
 // sums and a fixed-order tree.  local: the token's own cosine (|.| of the token's vectors) or mean squared difference; contrib: its
-// share of the direction's score, so that 0.5 (sum contrib[0] + sum contrib[1]) is the pair's score (F.cosine_similarity eps =
-// 1e-8, as pair_finish_kernel)
+// share of the direction's score, so that 0.5 (sum contrib[0] + sum contrib[1]) is the pair's score (tail_core.h's finish
+// arithmetic, as pair_finish_kernel)
 constexpr int MAP_FINISH_THREADS = 256;
 __global__ __launch_bounds__(MAP_FINISH_THREADS) void pair_map_finish_kernel(const float* __restrict__ part, int BH, int N, int D, int mse,
                                                                              float* __restrict__ score, float* __restrict__ local,
@@ -250,12 +163,12 @@ __global__ __launch_bounds__(MAP_FINISH_THREADS) void pair_map_finish_kernel(con
         double x2t = 0.0, y2t = 0.0;
         for (int i = t; i < N; i += NT) {
             const double a = fold(0, i);
-            if (mse) {
-                if (lo) lo[i] = (float)(a / ((double)BH * D));
+            if (mse) {                   // (mse folds no norms)
+                if (lo) lo[i] = (float)direction_value(a, 0.0, 0.0, mse, (double)BH * D);
             } else {
                 const double x2 = fold(1, i), y2 = fold(2, i);
                 x2t += x2; y2t += y2;
-                if (lo) lo[i] = (float)(a / (fmax(sqrt(x2), 1e-8) * fmax(sqrt(y2), 1e-8)));
+                if (lo) lo[i] = (float)direction_value(a, x2, y2, mse, (double)BH * D);
             }
         }
         red[1][t] = x2t; red[2][t] = y2t;
@@ -264,7 +177,7 @@ __global__ __launch_bounds__(MAP_FINISH_THREADS) void pair_map_finish_kernel(con
             if (t < s) { red[1][t] += red[1][t + s]; red[2][t] += red[2][t + s]; }
             __syncthreads();
         }
-        const double den = mse ? (double)BH * N * D : fmax(sqrt(red[1][0]), 1e-8) * fmax(sqrt(red[2][0]), 1e-8);
+        const double den = direction_denominator(red[1][0], red[2][0], mse, (double)BH * N * D);
         // pass 2: contrib (the same fold again: the per-token sums are not kept), and the direction's total
         double ct = 0.0;
         for (int i = t; i < N; i += NT) {
@@ -282,23 +195,19 @@ __global__ __launch_bounds__(MAP_FINISH_THREADS) void pair_map_finish_kernel(con
         res += red[0][0];
         __syncthreads();
     }
-    if (t == 0) {
-        const float sc = (float)(res * 0.5);
-        score[p] = sc;
-        if (status) status[p] = (sc - sc == 0.0f) ? 0 : 1;
-    }
+    if (t == 0) store_score(res, score + p, status ? status + p : nullptr);
 }
 
 template <typename T>
-int launch_maps_t(const void* q, const void* k, const void* v, const int32_t* ia, const int32_t* ib, int n_pairs, int B, int H, int N,
-                  int D, int mse, float* score, float* local, float* contrib, int32_t* status, void* scratch, hipStream_t s) {
-    return with_head_dim(D, [&](auto dc) -> int {
+int launch_maps_t(const PairArgs& a, float* score, float* local, float* contrib, int32_t* status, hipStream_t s) {
+    return with_head_dim(a.D, [&](auto dc) -> int {
         constexpr int Dc = decltype(dc)::value, LDS = ACfg<T, Dc>::LDS;
-        const int st = launch_lds<pair_map_kernel<T, Dc>>(dim3((N + 127) / 128, B * H, n_pairs * 2), dim3(256), LDS, s, (const T*)q,
-                                                          (const T*)k, (const T*)v, ia, ib, B, H, N, scale_log2_of(Dc), mse, (float*)scratch);
+        const int st = launch_lds<pair_map_kernel<T, Dc>>(dim3((a.N + 127) / 128, a.B * a.H, a.n_pairs * 2), dim3(256), LDS, s,
+                                                          (const T*)a.q, (const T*)a.k, (const T*)a.v, a.idx_a, a.idx_b, a.B, a.H, a.N,
+                                                          scale_log2_of(Dc), a.similarity, (float*)a.scratch);
         if (st != DSIM_OK) return st;
-        hipLaunchKernelGGL(pair_map_finish_kernel, dim3(n_pairs), dim3(MAP_FINISH_THREADS), 0, s, (const float*)scratch, B * H, N, Dc,
-                           mse, score, local, contrib, status);
+        hipLaunchKernelGGL(pair_map_finish_kernel, dim3(a.n_pairs), dim3(MAP_FINISH_THREADS), 0, s, (const float*)a.scratch, a.B * a.H,
+                           a.N, Dc, a.similarity, score, local, contrib, status);
         DSIM_HIP_CHECK(hipGetLastError());
         return DSIM_OK;
     });
@@ -307,6 +216,14 @@ int launch_maps_t(const void* q, const void* k, const void* v, const int32_t* ia
 }  // namespace
 
 inline namespace DSIM_H16_NS {
+// The shapes a pair launcher serves: at least one pair, image and token; two directions per pair on a 65535-wide grid axis and, for
+// the tiled kernels, B*H on another; a head dim of DSIM_FOR_EACH_D
+bool pair_shape_served(int n_pairs, int B, int H, int N, int D, bool tiled) {
+    if (n_pairs < 1 || B < 1 || H < 1 || N < 1) return false;
+    if (n_pairs > 65535 / 2 || (tiled && (long)B * H > 65535)) return false;
+    return with_head_dim(D, [](auto) { return DSIM_OK; }) == DSIM_OK;
+}
+
 size_t pair_score_scratch_bytes(int n_pairs, int B, int H, int N, int D) {
     const size_t tiled = (size_t)n_pairs * 2 * B * H * ((N + 127) / 128) * 4 * sizeof(float);
     if (pair_score160_applies(N, D, DSIM_H16)) {          // (dtype-blind: the 16-bit modes' persistent kernel needs the larger workspace)
@@ -316,23 +233,21 @@ size_t pair_score_scratch_bytes(int n_pairs, int B, int H, int N, int D) {
     return tiled;
 }
 
-int launch_pair_score(const void* q, const void* k, const void* v, const int32_t* ia, const int32_t* ib,
-                      int n_pairs, int B, int H, int N, int D, int dtype, int similarity, float* out, void* scratch,
-                      size_t scratch_bytes, hipStream_t s, int32_t* status) {
-    if (n_pairs <= 0 || D % 8 || N < 1) return DSIM_ERR_INVALID;
-    if (scratch_bytes < pair_score_scratch_bytes(n_pairs, B, H, N, D)) return DSIM_ERR_WORKSPACE;
-    if (n_pairs * 2 > 65535) return DSIM_ERR_INVALID;
-    if (dtype == DSIM_H16) {
-        if (pair_score160_applies(N, D, DSIM_H16))
-            return launch_pair_score160(q, k, v, ia, ib, n_pairs, B, H, similarity, out, scratch, scratch_bytes, s, status);
-        return launch_tail_t<h16>(q, k, v, ia, ib, n_pairs, B, H, N, D, similarity, out, scratch, s, status);
-    }
-#ifndef DSIM_H16_IS_F16
-    if (dtype == DSIM_F32) return launch_tail_t<float>(q, k, v, ia, ib, n_pairs, B, H, N, D, similarity, out, scratch, s, status);
-    if (dtype == DSIM_F16)
-        return DSIM_F16_TWIN(launch_pair_score(q, k, v, ia, ib, n_pairs, B, H, N, D, dtype, similarity, out, scratch, scratch_bytes, s, status));
-#endif
-    return DSIM_ERR_INVALID;
+// the default tap in a 16-bit mode runs the persistent kernel (attn160.hip), whose grid carries B*H on no axis
+int launch_pair_score(const PairArgs& a, int dtype, float* out, int32_t* status, hipStream_t s) {
+    const bool p160 = dtype != DSIM_F32 && pair_score160_applies(a.N, a.D, DSIM_H16);
+    const int st = pair_args_check(a, dtype, !p160);
+    if (st != DSIM_OK) return st;
+    if (a.scratch_bytes < pair_score_scratch_bytes(a.n_pairs, a.B, a.H, a.N, a.D)) return DSIM_ERR_WORKSPACE;
+    return by_h16_dtype(
+        dtype,
+        [&](auto e) {
+            typedef typename decltype(e)::type T;
+            if constexpr (sizeof(T) == 2)
+                if (p160) return launch_pair_score160(a, out, status, s);
+            return launch_tail_t<T>(a, out, status, s);
+        },
+        [&] { return DSIM_F16_TWIN(launch_pair_score(a, dtype, out, status, s)); });
 }
 
 size_t score_matrix_scratch_bytes(int n_a, int n_b, int B, int H, int N, int D, int dtype) {
@@ -352,20 +267,20 @@ int launch_score_matrix(const void* qa, const void* ka, const void* va, int n_a,
     const long units = (long)n_a * n_b * 2 * ((N + 127) / 128);
     if (units >= (1l << 31) || (long)n_a * n_b * B * H * 16 >= (1l << 31) || n_a + n_b > 65535) return DSIM_ERR_INVALID;
     if (scratch_bytes < score_matrix_scratch_bytes(n_a, n_b, B, H, N, D, dtype)) return DSIM_ERR_WORKSPACE;
-    if (dtype == DSIM_H16) {
-        if (pair_score160_applies(N, D, DSIM_H16))
-            return launch_score_matrix160(qa, ka, va, n_a, qb, kb, vb, n_b, B, H, similarity, out, status, scratch, scratch_bytes, s);
-        return launch_matrix_t<h16>(qa, ka, va, n_a, qb, kb, vb, n_b, B, H, N, D, similarity, out, status, scratch, s);
-    }
-#ifndef DSIM_H16_IS_F16
-    if (dtype == DSIM_F32)
-        return launch_matrix_t<float>(qa, ka, va, n_a, qb, kb, vb, n_b, B, H, N, D, similarity, out, status, scratch, s);
-    if (dtype == DSIM_F16)
-        return DSIM_F16_TWIN(launch_score_matrix(qa, ka, va, n_a, qb, kb, vb, n_b, B, H, N, D, dtype, similarity, out, status, scratch, scratch_bytes, s));
-#endif
-    return DSIM_ERR_INVALID;
+    return by_h16_dtype(
+        dtype,
+        [&](auto e) {
+            typedef typename decltype(e)::type T;
+            if constexpr (sizeof(T) == 2)
+                if (pair_score160_applies(N, D, DSIM_H16))
+                    return launch_score_matrix160(qa, ka, va, n_a, qb, kb, vb, n_b, B, H, similarity, out, status, scratch, scratch_bytes, s);
+            return launch_matrix_t<T>(qa, ka, va, n_a, qb, kb, vb, n_b, B, H, N, D, similarity, out, status, scratch, s);
+        },
+        [&] {
+            return DSIM_F16_TWIN(launch_score_matrix(qa, ka, va, n_a, qb, kb, vb, n_b, B, H, N, D, dtype, similarity, out, status, scratch,
+                                                     scratch_bytes, s));
+        });
 }
-
 
 size_t pair_score_maps_scratch_bytes(int n_pairs, int B, int H, int N) {
     if (n_pairs < 1 || B < 1 || H < 1 || N < 1) return 0;
@@ -374,22 +289,13 @@ size_t pair_score_maps_scratch_bytes(int n_pairs, int B, int H, int N) {
 
 // per-token maps of the score tail: pair_map_kernel at every shape and dtype (the default tap's persistent kernel keeps no
 // per-token sums)
-int launch_pair_score_maps(const void* q, const void* k, const void* v, const int32_t* ia, const int32_t* ib, int n_pairs, int B, int H,
-                           int N, int D, int dtype, int similarity, float* score, float* local, float* contrib, int32_t* status,
-                           void* scratch, size_t scratch_bytes, hipStream_t s) {
-    if (n_pairs <= 0 || B < 1 || H < 1 || D % 8 || N < 1 || (similarity != 0 && similarity != 1)) return DSIM_ERR_INVALID;
-    if (n_pairs * 2 > 65535 || B * H > 65535) return DSIM_ERR_INVALID;
-    if (scratch_bytes < pair_score_maps_scratch_bytes(n_pairs, B, H, N)) return DSIM_ERR_WORKSPACE;
-    if (dtype == DSIM_H16)
-        return launch_maps_t<h16>(q, k, v, ia, ib, n_pairs, B, H, N, D, similarity, score, local, contrib, status, scratch, s);
-#ifndef DSIM_H16_IS_F16
-    if (dtype == DSIM_F32)
-        return launch_maps_t<float>(q, k, v, ia, ib, n_pairs, B, H, N, D, similarity, score, local, contrib, status, scratch, s);
-    if (dtype == DSIM_F16)
-        return DSIM_F16_TWIN(launch_pair_score_maps(q, k, v, ia, ib, n_pairs, B, H, N, D, dtype, similarity, score, local, contrib, status,
-                                                    scratch, scratch_bytes, s));
-#endif
-    return DSIM_ERR_INVALID;
+int launch_pair_score_maps(const PairArgs& a, int dtype, float* score, float* local, float* contrib, int32_t* status, hipStream_t s) {
+    const int st = pair_args_check(a, dtype);
+    if (st != DSIM_OK) return st;
+    if (a.scratch_bytes < pair_score_maps_scratch_bytes(a.n_pairs, a.B, a.H, a.N)) return DSIM_ERR_WORKSPACE;
+    return by_h16_dtype(
+        dtype, [&](auto e) { return launch_maps_t<typename decltype(e)::type>(a, score, local, contrib, status, s); },
+        [&] { return DSIM_F16_TWIN(launch_pair_score_maps(a, dtype, score, local, contrib, status, s)); });
 }
 }  // namespace DSIM_H16_NS
 

@@ -209,26 +209,24 @@ int launch_text_attention(const void* xq, int ldq, const void* xk, int ldk, int 
     const bool region = mask || counts;
     if ((saliency || region) && (!weight || (n_w != 1 && n_w != n_images))) return DSIM_ERR_INVALID;
     if (!scratch || scratch_bytes < need) return DSIM_ERR_WORKSPACE;
-#ifndef DSIM_H16_IS_F16
-    if (dtype == DSIM_F16)
-        return DSIM_F16_TWIN(launch_text_attention(xq, ldq, xk, ldk, n_images, n_kv, H, N, L, D, dtype, weight, n_w, rel_threshold, attn,
-                                                   saliency, mask, counts, status, scratch, scratch_bytes, s));
-#endif
-    float* sal = saliency ? saliency : (region ? (float*)scratch : nullptr);
-    if (status) DSIM_HIP_CHECK(hipMemsetAsync(status, 0, (size_t)n_images * sizeof(int32_t), s));
-    int st = DSIM_ERR_INVALID;
-    if (dtype == DSIM_H16)
-        st = launch_text_attn_t<h16>(xq, ldq, xk, ldk, n_images, n_kv, H, N, L, D, weight, n_w, attn, sal, status, s);
-#ifndef DSIM_H16_IS_F16
-    else if (dtype == DSIM_F32)
-        st = launch_text_attn_t<float>(xq, ldq, xk, ldk, n_images, n_kv, H, N, L, D, weight, n_w, attn, sal, status, s);
-#endif
-    if (st != DSIM_OK) return st;
-    if (region) {
-        hipLaunchKernelGGL(text_region_kernel, dim3(n_images), dim3(256), 0, s, (const float*)sal, N, rel_threshold, mask, counts);
-        DSIM_HIP_CHECK(hipGetLastError());
-    }
-    return DSIM_OK;
+    return by_h16_dtype(
+        dtype,
+        [&](auto e) -> int {
+            float* sal = saliency ? saliency : (region ? (float*)scratch : nullptr);
+            if (status) DSIM_HIP_CHECK(hipMemsetAsync(status, 0, (size_t)n_images * sizeof(int32_t), s));
+            const int st = launch_text_attn_t<typename decltype(e)::type>(xq, ldq, xk, ldk, n_images, n_kv, H, N, L, D, weight, n_w, attn, sal,
+                                                                          status, s);
+            if (st != DSIM_OK) return st;
+            if (region) {
+                hipLaunchKernelGGL(text_region_kernel, dim3(n_images), dim3(256), 0, s, (const float*)sal, N, rel_threshold, mask, counts);
+                DSIM_HIP_CHECK(hipGetLastError());
+            }
+            return DSIM_OK;
+        },
+        [&] {
+            return DSIM_F16_TWIN(launch_text_attention(xq, ldq, xk, ldk, n_images, n_kv, H, N, L, D, dtype, weight, n_w, rel_threshold, attn,
+                                                       saliency, mask, counts, status, scratch, scratch_bytes, s));
+        });
 }
 }  // namespace DSIM_H16_NS
 

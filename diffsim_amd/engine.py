@@ -554,32 +554,44 @@ def _check_features(ts, heads: int, shapes_ok: bool, msgs, idx=()):
     return B, N, D
 
 
+def _similarity_code(similarity: str) -> int:
+    if similarity not in ("cosine", "mse"):
+        raise ValueError(similarity)
+    return 0 if similarity == "cosine" else 1
+
+
+def _i32(shape, dev, want: bool = True):
+    """an int32 output (a status, the counts) on dev, or None where the caller did not ask for it"""
+    return torch.empty(shape, dtype=torch.int32, device=dev) if want else None
+
+
+def _tail_call(dev, name: str, ws_shape, refusal: str, *args, query: Optional[str] = None):
+    """dsim_<name>(*args, workspace, bytes, stream) on dev, on a fresh workspace of dsim_<query or name>_workspace_bytes(*ws_shape)
+    bytes; 0 bytes: the library does not serve the shape, and `refusal` says which."""
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        wsb = int(getattr(L, f"dsim_{query or name}_workspace_bytes")(*ws_shape))
+        if wsb == 0:
+            raise _lib.DsimError(refusal)
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        _lib.check(getattr(L, f"dsim_{name}")(*args, ws.data_ptr(), wsb, _stream_ptr()), f"dsim_{name}")
+
+
 def pair_score(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, idx_a: torch.Tensor, idx_b: torch.Tensor,
                heads: int, similarity: str = "cosine", return_status: bool = False):
     """Fused score tail (diffsim/diffsim.py:177-197).  q,k,v: contiguous [n_feat][B][N][H*D] of one shape; idx: contiguous int32
     cuda [n_pairs] each, entries in [0, n_feat) (not checked: that would need a device sync).
     return_status: also return an int32 [n_pairs] tensor, 1 where the score is NaN / infinite (NaN guard)."""
-    L = _lib.lib()
     _require_cuda(q, k, v, idx_a, idx_b)
-    if similarity not in ("cosine", "mse"):
-        raise ValueError(similarity)
+    sim = _similarity_code(similarity)
     B, N, D = _check_features((q, k, v), heads, k.shape == q.shape == v.shape, _PAIR_MSGS, (idx_a, idx_b))
     n_pairs = idx_a.numel()
     out = torch.empty(n_pairs, dtype=torch.float32, device=q.device)
-    with torch.cuda.device(q.device):
-        wsb = int(L.dsim_pair_score_workspace_bytes(n_pairs, B, heads, N, D))
-        ws = torch.empty(wsb, dtype=torch.uint8, device=q.device)
-        if return_status:
-            status = torch.empty(n_pairs, dtype=torch.int32, device=q.device)
-            _lib.check(L.dsim_pair_score_status(q.data_ptr(), k.data_ptr(), v.data_ptr(), idx_a.data_ptr(), idx_b.data_ptr(),
-                                                n_pairs, B, heads, N, D, _TORCH2DSIM[q.dtype],
-                                                0 if similarity == "cosine" else 1, out.data_ptr(), status.data_ptr(),
-                                                ws.data_ptr(), wsb, _stream_ptr()), "dsim_pair_score_status")
-            return out, status
-        _lib.check(L.dsim_pair_score(q.data_ptr(), k.data_ptr(), v.data_ptr(), idx_a.data_ptr(), idx_b.data_ptr(),
-                                     n_pairs, B, heads, N, D, _TORCH2DSIM[q.dtype], 0 if similarity == "cosine" else 1,
-                                     out.data_ptr(), ws.data_ptr(), wsb, _stream_ptr()), "dsim_pair_score")
-    return out
+    status = _i32(n_pairs, q.device, return_status)
+    _tail_call(q.device, "pair_score_status" if return_status else "pair_score", (n_pairs, B, heads, N, D), "", q.data_ptr(),
+               k.data_ptr(), v.data_ptr(), idx_a.data_ptr(), idx_b.data_ptr(), n_pairs, B, heads, N, D, _TORCH2DSIM[q.dtype], sim,
+               out.data_ptr(), *((status.data_ptr(),) if return_status else ()), query="pair_score")
+    return (out, status) if return_status else out
 
 
 def pair_score_maps(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, idx_a: torch.Tensor, idx_b: torch.Tensor,
@@ -588,25 +600,18 @@ def pair_score_maps(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, idx_a: to
     Returns f32 device tensors (score (n,), local (n, 2, N), contrib (n, 2, N)): direction 0 on image idx_a[p]'s tokens,
     direction 1 on idx_b[p]'s; local is a token's own cosine (or mean squared difference), contrib its term of the score:
     score = 0.5 * contrib.sum((1, 2)).  return_status: also an int32 (n,) tensor, 1 where the score is NaN / infinite."""
-    L = _lib.lib()
     _require_cuda(q, k, v, idx_a, idx_b)
-    if similarity not in ("cosine", "mse"):
-        raise ValueError(similarity)
+    sim = _similarity_code(similarity)
     B, N, D = _check_features((q, k, v), heads, k.shape == q.shape == v.shape, _PAIR_MSGS, (idx_a, idx_b))
     n_pairs = idx_a.numel()
     score = torch.empty(n_pairs, dtype=torch.float32, device=q.device)
     local = torch.empty((n_pairs, 2, N), dtype=torch.float32, device=q.device)
     contrib = torch.empty((n_pairs, 2, N), dtype=torch.float32, device=q.device)
-    status = torch.empty(n_pairs, dtype=torch.int32, device=q.device) if return_status else None
-    with torch.cuda.device(q.device):
-        wsb = int(L.dsim_pair_score_maps_workspace_bytes(n_pairs, B, heads, N, D))
-        if wsb == 0:
-            raise _lib.DsimError(f"no similarity maps for n_pairs={n_pairs} B={B} H={heads} N={N} D={D}")
-        ws = torch.empty(wsb, dtype=torch.uint8, device=q.device)
-        _lib.check(L.dsim_pair_score_maps(q.data_ptr(), k.data_ptr(), v.data_ptr(), idx_a.data_ptr(), idx_b.data_ptr(), n_pairs, B,
-                                          heads, N, D, _TORCH2DSIM[q.dtype], 0 if similarity == "cosine" else 1, score.data_ptr(),
-                                          local.data_ptr(), contrib.data_ptr(), _ptr(status), ws.data_ptr(), wsb, _stream_ptr()),
-                   "dsim_pair_score_maps")
+    status = _i32(n_pairs, q.device, return_status)
+    _tail_call(q.device, "pair_score_maps", (n_pairs, B, heads, N, D),
+               f"no similarity maps for n_pairs={n_pairs} B={B} H={heads} N={N} D={D}", q.data_ptr(), k.data_ptr(), v.data_ptr(),
+               idx_a.data_ptr(), idx_b.data_ptr(), n_pairs, B, heads, N, D, _TORCH2DSIM[q.dtype], sim, score.data_ptr(), local.data_ptr(),
+               contrib.data_ptr(), _ptr(status))
     return (score, local, contrib, status) if return_status else (score, local, contrib)
 
 
@@ -618,10 +623,8 @@ def pair_score_regions(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: 
     score is pair_score's on the rows of the two regions alone (ascending token order): the off tokens are neither queries nor
     keys.  Returns the f32 (n,) scores; return_status: also an int32 (n,) tensor, 1 where the score is NaN / infinite, 2 where
     a region of the pair is empty (score NaN); return_counts: also the int32 (n_feat,) region sizes."""
-    L = _lib.lib()
     _require_cuda(q, k, v, mask, idx_a, idx_b)
-    if similarity not in ("cosine", "mse"):
-        raise ValueError(similarity)
+    sim = _similarity_code(similarity)
     B, N, D = _check_features((q, k, v), heads, k.shape == q.shape == v.shape, _PAIR_MSGS, (idx_a, idx_b))
     if mask.dtype not in (torch.bool, torch.uint8):
         raise _lib.DsimError("the region mask must be bool or uint8")
@@ -630,17 +633,12 @@ def pair_score_regions(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: 
     mask = mask.view(torch.uint8)
     n_feat, n_pairs = q.shape[0], idx_a.numel()
     out = torch.empty(n_pairs, dtype=torch.float32, device=q.device)
-    status = torch.empty(n_pairs, dtype=torch.int32, device=q.device) if return_status else None
-    counts = torch.empty(n_feat, dtype=torch.int32, device=q.device) if return_counts else None
-    with torch.cuda.device(q.device):
-        wsb = int(L.dsim_pair_score_regions_workspace_bytes(n_feat, n_pairs, B, heads, N, D))
-        if wsb == 0:
-            raise _lib.DsimError(f"no region scores for n_feat={n_feat} n_pairs={n_pairs} B={B} H={heads} N={N} D={D}")
-        ws = torch.empty(wsb, dtype=torch.uint8, device=q.device)
-        _lib.check(L.dsim_pair_score_regions(q.data_ptr(), k.data_ptr(), v.data_ptr(), mask.data_ptr(), n_feat, idx_a.data_ptr(),
-                                             idx_b.data_ptr(), n_pairs, B, heads, N, D, _TORCH2DSIM[q.dtype],
-                                             0 if similarity == "cosine" else 1, out.data_ptr(), _ptr(status), _ptr(counts),
-                                             ws.data_ptr(), wsb, _stream_ptr()), "dsim_pair_score_regions")
+    status = _i32(n_pairs, q.device, return_status)
+    counts = _i32(n_feat, q.device, return_counts)
+    _tail_call(q.device, "pair_score_regions", (n_feat, n_pairs, B, heads, N, D),
+               f"no region scores for n_feat={n_feat} n_pairs={n_pairs} B={B} H={heads} N={N} D={D}", q.data_ptr(), k.data_ptr(),
+               v.data_ptr(), mask.data_ptr(), n_feat, idx_a.data_ptr(), idx_b.data_ptr(), n_pairs, B, heads, N, D, _TORCH2DSIM[q.dtype],
+               sim, out.data_ptr(), _ptr(status), _ptr(counts))
     return out if not (return_status or return_counts) else (out,) + ((status,) if return_status else ()) + ((counts,) if return_counts else ())
 
 
@@ -655,7 +653,6 @@ def text_attention(xq: torch.Tensor, xkv: torch.Tensor, heads: int, token_weight
     (L,) shared or (n, L) per image, and the region: the tokens with s_i[n] >= rel_threshold * mean(s_i), or every token when none
     passes.  Returns a dict of the outputs named in `want`: attn f32 (n, N, L), saliency f32 (n, N), mask bool (n, N), counts
     int32 (n,), status int32 (n,) (1: a non-finite probability).  The values do not depend on `want`."""
-    L_ = _lib.lib()
     want = tuple(want)
     if not want or any(w not in TEXT_WANT for w in want):
         raise ValueError(f"want must name some of {TEXT_WANT}: {want}")
@@ -687,19 +684,13 @@ def text_attention(xq: torch.Tensor, xkv: torch.Tensor, heads: int, token_weight
         out["saliency"] = torch.empty((n, N), dtype=torch.float32, device=dev)
     if "mask" in want:
         out["mask"] = torch.empty((n, N), dtype=torch.uint8, device=dev)
-    if "counts" in want:
-        out["counts"] = torch.empty(n, dtype=torch.int32, device=dev)
-    if "status" in want:
-        out["status"] = torch.empty(n, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        wsb = int(L_.dsim_text_attention_workspace_bytes(n, N, L))
-        if wsb == 0:
-            raise _lib.DsimError(f"no text attention for n={n} N={N} L={L} (1 <= L <= 128)")
-        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-        _lib.check(L_.dsim_text_attention(xq.data_ptr(), HD, xkv.data_ptr(), 2 * HD, n, n_kv, heads, N, L, HD // heads,
-                                          _TORCH2DSIM[xq.dtype], _ptr(token_weight), n_w, float(rel_threshold), _ptr(out.get("attn")),
-                                          _ptr(out.get("saliency")), _ptr(out.get("mask")), _ptr(out.get("counts")),
-                                          _ptr(out.get("status")), ws.data_ptr(), wsb, _stream_ptr()), "dsim_text_attention")
+    for name in ("counts", "status"):
+        if name in want:
+            out[name] = _i32(n, dev)
+    _tail_call(dev, "text_attention", (n, N, L), f"no text attention for n={n} N={N} L={L} (1 <= L <= 128)", xq.data_ptr(), HD,
+               xkv.data_ptr(), 2 * HD, n, n_kv, heads, N, L, HD // heads, _TORCH2DSIM[xq.dtype], _ptr(token_weight), n_w,
+               float(rel_threshold), _ptr(out.get("attn")), _ptr(out.get("saliency")), _ptr(out.get("mask")), _ptr(out.get("counts")),
+               _ptr(out.get("status")))
     if "mask" in out:
         out["mask"] = out["mask"].view(torch.bool)
     return out
@@ -718,7 +709,6 @@ def pair_align(q: torch.Tensor, k: torch.Tensor, idx_a: torch.Tensor, idx_b: tor
     probability, and the soft-argmax (row, col) on the other image's grid, token j at (j // grid_w, j % grid_w).  grid_w None:
     the square grid of N tokens.  return_attention: also the probabilities, f32 (n, 2, N, N), computed in calls of fewer than
     2 GiB each; return_status: also an int32 (n,) tensor, 1 where a pair has a non-finite probability."""
-    L = _lib.lib()
     _require_cuda(q, k, idx_a, idx_b)
     B, N, D = _check_features((q, k), heads, k.shape == q.shape, _PAIR_MSGS, (idx_a, idx_b))
     if grid_w is None:
@@ -730,7 +720,7 @@ def pair_align(q: torch.Tensor, k: torch.Tensor, idx_a: torch.Tensor, idx_b: tor
     match = torch.empty((n_pairs, 2, N), dtype=torch.int32, device=dev)
     weight = torch.empty((n_pairs, 2, N), dtype=torch.float32, device=dev)
     expect = torch.empty((n_pairs, 2, N, 2), dtype=torch.float32, device=dev)
-    status = torch.empty(n_pairs, dtype=torch.int32, device=dev) if return_status else None
+    status = _i32(n_pairs, dev, return_status)
     attn = None
     step = _ALIGN_PAIRS
     if return_attention:
@@ -738,19 +728,13 @@ def pair_align(q: torch.Tensor, k: torch.Tensor, idx_a: torch.Tensor, idx_b: tor
         if step < 1:
             raise _lib.DsimError(f"the attention of one pair of {N} tokens does not fit 2 GiB")
         attn = torch.empty((n_pairs, 2, N, N), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        for i0 in range(0, n_pairs, step):
-            n = min(step, n_pairs - i0)
-            wsb = int(L.dsim_pair_align_workspace_bytes(n, B, heads, N, D))
-            if wsb == 0:
-                raise _lib.DsimError(f"no token alignments for n_pairs={n} B={B} H={heads} N={N} D={D}")
-            ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-            sl = slice(i0, i0 + n)
-            _lib.check(L.dsim_pair_align(q.data_ptr(), k.data_ptr(), idx_a[sl].data_ptr(), idx_b[sl].data_ptr(), n, B, heads, N, D,
-                                         _TORCH2DSIM[q.dtype], int(grid_w), match[sl].data_ptr(), weight[sl].data_ptr(),
-                                         expect[sl].data_ptr(), _ptr(None if attn is None else attn[sl]),
-                                         _ptr(None if status is None else status[sl]), ws.data_ptr(), wsb, _stream_ptr()),
-                       "dsim_pair_align")
+    for i0 in range(0, n_pairs, step):
+        n = min(step, n_pairs - i0)
+        sl = slice(i0, i0 + n)
+        _tail_call(dev, "pair_align", (n, B, heads, N, D), f"no token alignments for n_pairs={n} B={B} H={heads} N={N} D={D}",
+                   q.data_ptr(), k.data_ptr(), idx_a[sl].data_ptr(), idx_b[sl].data_ptr(), n, B, heads, N, D, _TORCH2DSIM[q.dtype],
+                   int(grid_w), match[sl].data_ptr(), weight[sl].data_ptr(), expect[sl].data_ptr(),
+                   _ptr(None if attn is None else attn[sl]), _ptr(None if status is None else status[sl]))
     return (match, weight, expect) + ((attn,) if return_attention else ()) + ((status,) if return_status else ())
 
 
@@ -763,9 +747,7 @@ def score_matrix(fa, fb, heads: int, similarity: str = "cosine", return_status: 
     device tensors of one dtype.  Returns the (n_a, n_b) f32 device tensor whose cell (i, j) is pair_score of (fa[i], fb[j]);
     each image's self-attention is computed once.  return_status: also an int32 (n_a, n_b) tensor, 1 where the score is
     NaN / infinite."""
-    L = _lib.lib()
-    if similarity not in ("cosine", "mse"):
-        raise ValueError(similarity)
+    sim = _similarity_code(similarity)
     (qa, ka, va), (qb, kb, vb) = fa, fb
     _require_cuda(qa, ka, va, qb, kb, vb)
     B, N, D = _check_features((qa, ka, va, qb, kb, vb), heads,
@@ -774,15 +756,10 @@ def score_matrix(fa, fb, heads: int, similarity: str = "cosine", return_status: 
                                "features must be [n][B][N][H*D], one geometry for both sets", "features must be contiguous"))
     n_a, n_b = qa.shape[0], qb.shape[0]
     out = torch.empty((n_a, n_b), dtype=torch.float32, device=qa.device)
-    status = torch.empty((n_a, n_b), dtype=torch.int32, device=qa.device) if return_status else None
-    with torch.cuda.device(qa.device):
-        wsb = int(L.dsim_score_matrix_workspace_bytes(n_a, n_b, B, heads, N, D, _TORCH2DSIM[qa.dtype]))
-        if wsb == 0:
-            raise _lib.DsimError(f"no score matrix for n_a={n_a} n_b={n_b} B={B} H={heads} N={N} D={D}")
-        ws = torch.empty(wsb, dtype=torch.uint8, device=qa.device)
-        _lib.check(L.dsim_score_matrix(qa.data_ptr(), ka.data_ptr(), va.data_ptr(), n_a, qb.data_ptr(), kb.data_ptr(),
-                                       vb.data_ptr(), n_b, B, heads, N, D, _TORCH2DSIM[qa.dtype], 0 if similarity == "cosine" else 1,
-                                       out.data_ptr(), _ptr(status), ws.data_ptr(), wsb, _stream_ptr()), "dsim_score_matrix")
+    status = _i32((n_a, n_b), qa.device, return_status)
+    _tail_call(qa.device, "score_matrix", (n_a, n_b, B, heads, N, D, _TORCH2DSIM[qa.dtype]),
+               f"no score matrix for n_a={n_a} n_b={n_b} B={B} H={heads} N={N} D={D}", qa.data_ptr(), ka.data_ptr(), va.data_ptr(), n_a,
+               qb.data_ptr(), kb.data_ptr(), vb.data_ptr(), n_b, B, heads, N, D, _TORCH2DSIM[qa.dtype], sim, out.data_ptr(), _ptr(status))
     return (out, status) if return_status else out
 
 

@@ -331,9 +331,10 @@ static void bench_tail(const char* name, int np, int iters, Timer& t) {
     int st1 = 0;
     const int rounds = getenv("KB_ROUNDS") ? atoi(getenv("KB_ROUNDS")) : 5;
     for (int sim = 0; sim < 2; ++sim) {
+        const PairArgs pa{q, k, v, ia, ib, np, B, H, N, D, sim, scratch, sb};
         std::vector<float> m1;
         for (int r = 0; r < rounds; ++r)
-            m1.push_back(t.run([&] { st1 = launch_pair_score(q, k, v, ia, ib, np, B, H, N, D, DSIM_BF16, sim, o1, scratch, sb, 0); }, iters));
+            m1.push_back(t.run([&] { st1 = launch_pair_score(pa, DSIM_BF16, o1, nullptr, 0); }, iters));
         HC(hipDeviceSynchronize());
         std::vector<float> h1(np);
         HC(hipMemcpy(h1.data(), o1, np * 4, hipMemcpyDeviceToHost));
@@ -346,7 +347,7 @@ static void bench_tail(const char* name, int np, int iters, Timer& t) {
             const int nwg = 256;
             unsigned long long* sbuf; HC(hipMalloc((void**)&sbuf, (size_t)nwg * 8 * 8 * 8)); HC(hipMemset(sbuf, 0, (size_t)nwg * 8 * 8 * 8));
             g_tail160_dbg = (float*)sbuf;
-            launch_pair_score(q, k, v, ia, ib, np, B, H, N, D, DSIM_BF16, sim, o1, scratch, sb, 0);
+            launch_pair_score(pa, DSIM_BF16, o1, nullptr, 0);
             HC(hipDeviceSynchronize());
             g_tail160_dbg = nullptr;
             std::vector<unsigned long long> hs((size_t)nwg * 64);
@@ -366,7 +367,7 @@ static void bench_tail(const char* name, int np, int iters, Timer& t) {
             // the first unit (pair 0, direction 0, b 0, head 0): both attention outputs against a host evaluation, error by key-independent position
             float* dbg; HC(hipMalloc((void**)&dbg, 2 * N * D * 4)); HC(hipMemset(dbg, 0, 2 * N * D * 4));
             g_tail160_dbg = dbg;
-            launch_pair_score(q, k, v, ia, ib, np, B, H, N, D, DSIM_BF16, sim, o1, scratch, sb, 0);
+            launch_pair_score(pa, DSIM_BF16, o1, nullptr, 0);
             HC(hipDeviceSynchronize());
             g_tail160_dbg = nullptr;
             std::vector<float> hd(2 * N * D);
@@ -476,7 +477,7 @@ static void bench_tail(const char* name, int np, int iters, Timer& t) {
             for (int r = 0; r < rounds; ++r)
                 for (size_t kk = 0; kk < vals.size(); ++kk) {
                     g_tail160_exp = vals[kk];
-                    ms[kk].push_back(t.run([&] { st1 = launch_pair_score(q, k, v, ia, ib, np, B, H, N, D, DSIM_BF16, sim, o1, scratch, sb, 0); }, iters));
+                    ms[kk].push_back(t.run([&] { st1 = launch_pair_score(pa, DSIM_BF16, o1, nullptr, 0); }, iters));
                     HC(hipMemcpy(&sc[kk], o1 + (np - 1), 4, hipMemcpyDeviceToHost));
                 }
             g_tail160_exp = 0;
