@@ -4,7 +4,7 @@
 
 Flags of the reference drivers (``/root/reference/argprocess.py:5-18``) keep their names, meaning and defaults;
 ``--dataset`` selects which of the reference's loops runs (``cute_main.py:48-226``, ``night_main.py:24-173`` or
-``style_main.py:24-196`` -- separate scripts there), ``--model_path / --dtype / --batch / --unet_batch / --ngpu / --noise_dtype / --mask_path / --text_attn / --text_threshold`` are additions of this build (the reference
+``style_main.py:24-196`` -- separate scripts there), ``--model_path / --dtype / --batch / --unet_batch / --ngpu / --noise_dtype / --mask_path / --query_mask_path / --gallery_mask_path / --text_attn / --text_threshold`` are additions of this build (the reference
 hard-codes NAS checkpoint paths, ``cute_main.py:25-31``, fp16 and one GPU, ``cute_main.sh:1``).
 
 Multi-GPU (``--ngpu N``): the parent starts N rank processes before anything touches the GPU; triplets are sharded
@@ -66,6 +66,14 @@ def build_parser() -> argparse.ArgumentParser:
                         "<image_path>/rel/name.ext is <DIR>/rel/name.png, else <DIR>/rel/name.ext (any mode; area-averaged onto the "
                         "tap's token grid, a token on at >= 128); an image without a mask file is scored whole, and the run prints "
                         "how many were.  Implies --use_mask")
+    p.add_argument("--query_mask_path", type=str, default=None, metavar="DIR",
+                   help="--dataset retrieval: rank by the masked part of each query image (a region score matrix).  The mask of "
+                        "<query_path>/rel/name.ext is <DIR>/rel/name.png, else <DIR>/rel/name.ext (as --mask_path reads them); a query "
+                        "without a mask file is scored whole, and the run prints how many were.  May be given without "
+                        "--gallery_mask_path: the gallery images are then whole")
+    p.add_argument("--gallery_mask_path", type=str, default=None, metavar="DIR",
+                   help="--dataset retrieval: the same for the gallery images under --image_path.  May be given without "
+                        "--query_mask_path")
     p.add_argument("--text_attn", type=str, nargs="*", default=None, metavar="WORD",
                    help="--dataset cute|nights, --metric diffsim|diffsim_xl: score the part of each image the prompt names "
                         "(text-guided regions).  Each image's region is the tokens whose cross-attention to the WORDs of its row's "
@@ -114,8 +122,20 @@ def arg_parse(argv=None):
     if args.mask_path is not None:
         if args.dataset not in ("cute", "nights") or args.taps is not None:
             p.error("--mask_path scores regions on the one-tap triplet benchmarks (--dataset cute or nights): a region score matrix "
-                    "(--dataset retrieval), --dataset sref and a region sweep (--taps) are not supported")
+                    "(--dataset retrieval) takes its masks from --query_mask_path / --gallery_mask_path; --dataset sref and a region "
+                    "sweep (--taps) are not supported")
         args.use_mask = True
+    for flag in ("query_mask_path", "gallery_mask_path"):
+        if getattr(args, flag) is None:
+            continue
+        if args.dataset != "retrieval":
+            p.error(f"--{flag} masks the images of a region score matrix: it needs --dataset retrieval (the triplet benchmarks take "
+                    "--mask_path)")
+        if args.save_maps or args.save_matches:
+            p.error(f"--{flag}: --save_maps and --save_matches write per-token outputs of whole images (their epilogue stores rows in "
+                    "order) and are not supported with region rankings")
+        if args.text_attn is not None:
+            p.error(f"--{flag}: text-guided regions (--text_attn) are not supported for --dataset retrieval")
     if args.text_attn is not None:
         if args.dataset not in ("cute", "nights") or args.taps is not None or args.mask_path is not None:
             p.error("--text_attn scores text-guided regions on the one-tap triplet benchmarks (--dataset cute or nights): "
@@ -386,7 +406,19 @@ def run_retrieval(args, scorer, layer) -> int:
         R.ranking_names(queries, args.query_path)               # two queries that would share a ranking file: refused before scoring
     except ValueError as e:
         raise SystemExit(str(e))
-    if not (args.save_maps or args.save_matches):
+    if args.query_mask_path is not None or args.gallery_mask_path is not None:
+        from .regions import mask_path_for
+        masks, missing = {}, 0
+        for side, paths, root, mdir in (("masks_a", queries, args.query_path, args.query_mask_path),
+                                        ("masks_b", gallery, args.image_path, args.gallery_mask_path)):
+            if mdir is not None:
+                masks[side] = [mask_path_for(p, root, mdir) for p in paths]
+                missing += sum(1 for f in masks[side] if f is None)
+        print(f"Region score matrix: masks from {' and '.join(d for d in (args.query_mask_path, args.gallery_mask_path) if d)}; "
+              f"{missing} image(s) without a mask file are scored whole")
+        m, bad = R.score_path_matrix(scorer, queries, gallery, args.image_size, args.prompt, args.target_block, layer,
+                                     args.target_step, args.seed, args.similarity, return_status=True, **masks)
+    elif not (args.save_maps or args.save_matches):
         m, bad = R.score_path_matrix(scorer, queries, gallery, args.image_size, args.prompt, args.target_block, layer,
                                      args.target_step, args.seed, args.similarity, return_status=True)
     elif queries and gallery:

@@ -109,6 +109,22 @@ int dsim_pair_score_regions(const void* q, const void* k, const void* v, const u
     return st != DSIM_OK ? st : launch_pair_score_regions(a, dtype, mask, n_feat, out_scores, status, counts, (hipStream_t)stream);
 }
 
+size_t dsim_score_matrix_regions_workspace_bytes(int n_a, int n_b, int B, int H, int N, int D, int dtype) {
+    return with_slack(score_matrix_regions_scratch_bytes(n_a, n_b, B, H, N, D, dtype));
+}
+
+int dsim_score_matrix_regions(const void* qa, const void* ka, const void* va, const uint8_t* mask_a, int n_a, const void* qb,
+                              const void* kb, const void* vb, const uint8_t* mask_b, int n_b, int B, int H, int N, int D, int dtype,
+                              int similarity, float* out, int32_t* status, int32_t* counts, void* workspace, size_t workspace_bytes,
+                              void* stream) {
+    const bool served = (similarity == 0 || similarity == 1) && score_matrix_regions_scratch_bytes(n_a, n_b, B, H, N, D, dtype) != 0;
+    const int st = tail_prologue({qa, ka, va, mask_a, qb, kb, vb, mask_b, out}, served ? DSIM_OK : DSIM_ERR_INVALID, workspace,
+                                 workspace_bytes);
+    if (st != DSIM_OK) return st;
+    return launch_score_matrix_regions(qa, ka, va, mask_a, n_a, qb, kb, vb, mask_b, n_b, B, H, N, D, dtype, similarity, out, status,
+                                       counts, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
 size_t dsim_pair_align_workspace_bytes(int n_pairs, int B, int H, int N, int D) {
     return with_slack(pair_align_scratch_bytes(n_pairs, B, H, N, D));
 }

@@ -1,5 +1,5 @@
 // The host entry points of the sources that are compiled once per 16-bit type (gemm / gemm_skinny / rowres / attention / tails /
-// align / regions / textattn / attn160 .hip).  Declarations only and no include guard: common.h includes this file inside `inline namespace DSIM_H16_NS`, the including
+// align / regions / region_matrix / textattn / attn160 .hip).  Declarations only and no include guard: common.h includes this file inside `inline namespace DSIM_H16_NS`, the including
 // object's own type, and the bf16 objects of the product build once more inside `namespace f16`, which declares the fp16 twins with
 // the same signatures and default arguments.  The argument structs and enums are plain dsim types (common.h, above the include).
 
@@ -54,6 +54,16 @@ int launch_pair_align(const PairArgs& a, int dtype, int grid_w, int32_t* match, 
 size_t pair_score_regions_scratch_bytes(int n_feat, int n_pairs, int B, int H, int N, int D);      // 0: call not served
 int launch_pair_score_regions(const PairArgs& a, int dtype, const uint8_t* mask, int n_feat, float* out, int32_t* status,
                               int32_t* counts, hipStream_t s);
+// the masks [n_feat][N] as ascending token lists [n_feat][N] and counts [n_feat] (also to counts, unless NULL): region_lists_kernel
+int launch_region_lists(const uint8_t* mask, int n_feat, int N, int32_t* list, int32_t* cnt, int32_t* counts, hipStream_t s);
+// region score matrix: cell (i, j) is the region score of (A_i over mask_a[i], B_j over mask_b[j]); each image's self attention over
+// its region once, at compacted positions, then one listed attention per cell and direction -- region_matrix.hip
+//   out [n_a][n_b]; status (may be NULL) [n_a][n_b]: 0, 1 non-finite, 2 empty region; counts (may be NULL) [n_a + n_b]
+size_t score_matrix_regions_scratch_bytes(int n_a, int n_b, int B, int H, int N, int D, int dtype);      // 0: call not served
+int launch_score_matrix_regions(const void* qa, const void* ka, const void* va, const uint8_t* mask_a, int n_a, const void* qb,
+                                const void* kb, const void* vb, const uint8_t* mask_b, int n_b, int B, int H, int N, int D, int dtype,
+                                int similarity, float* out, int32_t* status, int32_t* counts, void* scratch, size_t scratch_bytes,
+                                hipStream_t s);
 // text attention maps: the tapped block's cross-attention on the conditional CFG half, averaged over the heads; its weighted sum over
 // the prompt tokens (saliency) and the token region above rel_threshold x the image's mean saliency (text_attn_kernel,
 // text_region_kernel, any head dim and dtype, 1 <= L <= 128) -- textattn.hip

@@ -75,9 +75,9 @@ int launch_regions_t(const PairArgs& a, const uint8_t* mask, int n_feat, float* 
     return with_head_dim(a.D, [&](auto dc) -> int {
         constexpr int Dc = decltype(dc)::value, LDS = ACfg<T, Dc>::LDS;
         const int qt = (a.N + 127) / 128;
-        hipLaunchKernelGGL(region_lists_kernel, dim3(n_feat), dim3(LIST_THREADS), 0, s, mask, a.N, list, cnt, counts);
-        DSIM_HIP_CHECK(hipGetLastError());
-        const int st = launch_lds<region_tail_kernel<T, Dc>>(dim3(qt, a.B * a.H, a.n_pairs * 2), dim3(256), LDS, s, (const T*)a.q,
+        int st = launch_region_lists(mask, n_feat, a.N, list, cnt, counts, s);
+        if (st != DSIM_OK) return st;
+        st = launch_lds<region_tail_kernel<T, Dc>>(dim3(qt, a.B * a.H, a.n_pairs * 2), dim3(256), LDS, s, (const T*)a.q,
                                                              (const T*)a.k, (const T*)a.v, (const int32_t*)list, (const int32_t*)cnt,
                                                              a.idx_a, a.idx_b, a.B, a.H, a.N, scale_log2_of(Dc), a.similarity, part);
         if (st != DSIM_OK) return st;
@@ -91,6 +91,13 @@ int launch_regions_t(const PairArgs& a, const uint8_t* mask, int n_feat, float* 
 }  // namespace
 
 inline namespace DSIM_H16_NS {
+// region_lists_kernel over n_feat masks: the one launch site, for the region tail here and the region matrix (region_matrix.hip)
+int launch_region_lists(const uint8_t* mask, int n_feat, int N, int32_t* list, int32_t* cnt, int32_t* counts, hipStream_t s) {
+    hipLaunchKernelGGL(region_lists_kernel, dim3(n_feat), dim3(LIST_THREADS), 0, s, mask, N, list, cnt, counts);
+    DSIM_HIP_CHECK(hipGetLastError());
+    return DSIM_OK;
+}
+
 // 0 for a call launch_pair_score_regions refuses for its shape
 size_t pair_score_regions_scratch_bytes(int n_feat, int n_pairs, int B, int H, int N, int D) {
     if (n_feat < 1 || !pair_shape_served(n_pairs, B, H, N, D) || (long)n_feat * N >= (1l << 31)) return 0;

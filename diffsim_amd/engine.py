@@ -763,6 +763,42 @@ def score_matrix(fa, fb, heads: int, similarity: str = "cosine", return_status: 
     return (out, status) if return_status else out
 
 
+def score_matrix_regions_workspace_bytes(n_a: int, n_b: int, B: int, heads: int, N: int, D: int, dtype: torch.dtype) -> int:
+    return int(_lib.lib().dsim_score_matrix_regions_workspace_bytes(n_a, n_b, B, heads, N, D, _TORCH2DSIM[dtype]))
+
+
+def score_matrix_regions(fa, fb, mask_a: torch.Tensor, mask_b: torch.Tensor, heads: int, similarity: str = "cosine",
+                         return_status: bool = False, return_counts: bool = False):
+    """Every image of set A over its region against every image of set B over its region (dsim_score_matrix_regions).  fa, fb:
+    (q, k, v) tuples of [n][B][N][H*D] device tensors of one dtype; mask_a (n_a, N), mask_b (n_b, N): bool or uint8 cuda, non-zero =
+    the token is in its image's region.  Returns the (n_a, n_b) f32 device tensor whose cell (i, j) is pair_score_regions of
+    (fa[i] over mask_a[i], fb[j] over mask_b[j]); each image's self-attention over its region is computed once.  return_status:
+    also an int32 (n_a, n_b) tensor, 1 where the score is NaN / infinite, 2 where a region of the cell is empty (score NaN);
+    return_counts: also the int32 (n_a + n_b,) region sizes, set A's then set B's."""
+    sim = _similarity_code(similarity)
+    (qa, ka, va), (qb, kb, vb) = fa, fb
+    B, N, D = _check_features((qa, ka, va, qb, kb, vb), heads,
+                              ka.shape == qa.shape == va.shape and kb.shape == qb.shape == vb.shape and qa.shape[1:] == qb.shape[1:],
+                              ("q,k,v of both sets must share dtype float32, bfloat16 or float16",
+                               "features must be [n][B][N][H*D], one geometry for both sets", "features must be contiguous"))
+    n_a, n_b = qa.shape[0], qb.shape[0]
+    for name, m, n in (("mask_a", mask_a, n_a), ("mask_b", mask_b, n_b)):
+        if m.dtype not in (torch.bool, torch.uint8):
+            raise _lib.DsimError(f"the region mask {name} must be bool or uint8")
+        if tuple(m.shape) != (n, N):
+            raise _lib.DsimError(f"the region mask {name} must be (n, N) = ({n}, {N}): {tuple(m.shape)}")
+    _require_cuda(qa, ka, va, qb, kb, vb, mask_a, mask_b)          # (after the shape checks: those need no device)
+    mask_a, mask_b = mask_a.view(torch.uint8), mask_b.view(torch.uint8)
+    out = torch.empty((n_a, n_b), dtype=torch.float32, device=qa.device)
+    status = _i32((n_a, n_b), qa.device, return_status)
+    counts = _i32(n_a + n_b, qa.device, return_counts)
+    _tail_call(qa.device, "score_matrix_regions", (n_a, n_b, B, heads, N, D, _TORCH2DSIM[qa.dtype]),
+               f"no region score matrix for n_a={n_a} n_b={n_b} B={B} H={heads} N={N} D={D}", qa.data_ptr(), ka.data_ptr(), va.data_ptr(),
+               mask_a.data_ptr(), n_a, qb.data_ptr(), kb.data_ptr(), vb.data_ptr(), mask_b.data_ptr(), n_b, B, heads, N, D,
+               _TORCH2DSIM[qa.dtype], sim, out.data_ptr(), _ptr(status), _ptr(counts))
+    return out if not (return_status or return_counts) else (out,) + ((status,) if return_status else ()) + ((counts,) if return_counts else ())
+
+
 # ---- single-operator entry points (kernel-level parity tests) -----------------------------------
 def op_linear(x, w, bias=None, residual=None, geglu=False):
     L = _lib.lib()

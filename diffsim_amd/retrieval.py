@@ -8,6 +8,10 @@ per cell.  Cell (i, j) equals what ``diffsim(paths_a[i], paths_b[j], ...)`` / ``
 
 Query features are computed once and kept; the gallery runs in chunks of the scorer's engine batch (one feature batch and one
 ``score_matrix`` call per chunk), and the chunk is halved until the call's workspace fits a fixed share of the free HBM.
+
+With ``masks_a`` / ``masks_b`` every image carries a token mask on the tap's grid and the matrix is the region score matrix
+(``engine.score_matrix_regions``): cell (i, j) is ``regions.score_latent_pair_regions`` of that pair -- the masked object is
+retrieved, the background takes part in no softmax -- at the same n_a + n_b forwards.
 """
 from __future__ import annotations
 
@@ -16,7 +20,7 @@ from typing import List, Optional, Sequence
 
 import torch
 
-from .engine import score_matrix, score_matrix_workspace_bytes
+from .engine import score_matrix, score_matrix_regions, score_matrix_regions_workspace_bytes, score_matrix_workspace_bytes
 from .inputs import path_latents
 from .scorer import stack_rows
 
@@ -44,13 +48,29 @@ def _features(scorer, lat, noise, prompt, tap, step, batch: int):
     return tuple(torch.cat([p[i] for p in parts]) for i in range(3))
 
 
+def _set_masks(masks, n: int, grid, dev, name: str) -> torch.Tensor:
+    """(n, N) bool on dev: one token mask per image of a set (``regions.load_token_masks``: paths, PIL images, arrays on the grid,
+    None entries); masks None: whole images.  A mask with nothing on is the whole image, as a mask file's is."""
+    from .regions import load_token_masks
+    if masks is None:
+        return torch.ones((n, grid[0] * grid[1]), dtype=torch.bool, device=dev)
+    if len(masks) != n:
+        raise ValueError(f"{name}: {len(masks)} masks for {n} images")
+    m = load_token_masks(list(masks), grid).reshape(n, -1)
+    m = m | ~m.any(1, keepdim=True)
+    return m.to(dev).contiguous()
+
+
 @torch.no_grad()
 def score_latent_matrix(scorer, latA, latB, noiseA, noiseB, prompt, target_block="up_blocks", target_layer=0, target_step=600,
-                        similarity="cosine", batch: Optional[int] = None, return_status: bool = False):
+                        similarity="cosine", batch: Optional[int] = None, return_status: bool = False, *, masks_a=None, masks_b=None):
     """(n_a, n_b) f32 device tensor: query latents latA in slot A (noiseA), gallery latents latB in slot B (noiseB), any
     scorer kind (DiffSim, diffsim_xl, diffsim_DiT).  noiseA / noiseB: (1, C, s, s), shared by every pair as in the reference.
     batch: gallery images per chunk (None: the images of the triplet engine batch, ``Scorer.auto_rows``).
-    return_status: also the number of NaN / infinite cells."""
+    return_status: also the number of NaN / infinite cells.
+    masks_a / masks_b: one token mask per query / gallery image on the tap's grid (``regions.tap_grid``; each a path, a PIL image,
+    a bool array (h, w) or (N,), or None) -- the region score matrix; given only one, the other side is whole images; both None: the
+    score matrix."""
     dev = scorer.device
     latA = latA.to(dev, torch.float32)
     latB = latB.to(dev, torch.float32)
@@ -69,16 +89,26 @@ def score_latent_matrix(scorer, latA, latB, noiseA, noiseB, prompt, target_block
     bad = torch.zeros((), dtype=torch.int64, device=dev)
     _, B, N, HD = fa[0].shape
     chunk = min(batch, n_b) if n_b else 1
+    masked = masks_a is not None or masks_b is not None
+    if masked:
+        from .regions import tap_grid
+        grid = tap_grid(scorer, tap, latA.shape[-1])
+        masks_a, masks_b = _set_masks(masks_a, n_a, grid, dev, "masks_a"), _set_masks(masks_b, n_b, grid, dev, "masks_b")
+    workspace_bytes = score_matrix_regions_workspace_bytes if masked else score_matrix_workspace_bytes
     try:
         free, _total = torch.cuda.mem_get_info(dev)
-        while chunk > 1 and score_matrix_workspace_bytes(n_a, chunk, B, heads, N, HD // heads, fa[0].dtype) > WORKSPACE_SHARE * free:
+        while chunk > 1 and workspace_bytes(n_a, chunk, B, heads, N, HD // heads, fa[0].dtype) > WORKSPACE_SHARE * free:
             chunk = (chunk + 1) // 2
     except RuntimeError:
         pass
     for j0 in range(0, n_b, chunk):
         j1 = min(n_b, j0 + chunk)
         fb = _features(scorer, latB[j0:j1], nB, prompt, tap, target_step, batch)
-        s, st = score_matrix(fa, fb, heads, similarity, return_status=True)
+        if masked:
+            s, st = score_matrix_regions(fa, fb, masks_a, masks_b[j0:j1], heads, similarity, return_status=True)
+            st = st != 0
+        else:
+            s, st = score_matrix(fa, fb, heads, similarity, return_status=True)
         out[:, j0:j1] = s
         bad += st.sum()
     return (out, int(bad)) if return_status else out
@@ -87,17 +117,18 @@ def score_latent_matrix(scorer, latA, latB, noiseA, noiseB, prompt, target_block
 @torch.no_grad()
 def score_path_matrix(scorer, paths_a: Sequence[str], paths_b: Sequence[str], img_size, prompt, target_block="up_blocks",
                       target_layer=0, target_step=600, seed=2333, similarity="cosine", batch: Optional[int] = None,
-                      return_status: bool = False):
+                      return_status: bool = False, *, masks_a=None, masks_b=None):
     """The (len(paths_a), len(paths_b)) matrix of ``diffsim(paths_a[i], paths_b[j], ...)`` scores: the query images are
     encoded with the reseeded generator's slot-A VAE draw and noise, the gallery images with the slot-B ones
-    (``inputs.path_latents``).  Through the scorer's HIP VAE fast path where it has one."""
+    (``inputs.path_latents``).  Through the scorer's HIP VAE fast path where it has one.  masks_a / masks_b: as
+    ``score_latent_matrix`` takes them, one per path."""
     if not paths_a or not paths_b:
         empty = torch.empty((len(paths_a), len(paths_b)), dtype=torch.float32, device=scorer.device)
         return (empty, 0) if return_status else empty
     (latA,), nA, _ = path_latents(scorer, [(p,) for p in paths_a], (0,), img_size, seed, ENCODE_CHUNK)
     (latB,), _, nB = path_latents(scorer, [(p,) for p in paths_b], (1,), img_size, seed, ENCODE_CHUNK)
     return score_latent_matrix(scorer, latA, latB, nA, nB, prompt, target_block, target_layer, target_step, similarity, batch,
-                               return_status)
+                               return_status, masks_a=masks_a, masks_b=masks_b)
 
 
 def topk(matrix: torch.Tensor, k: int, similarity: str = "cosine"):

@@ -339,6 +339,29 @@ int    dsim_pair_score_regions(const void* q, const void* k, const void* v, cons
                                float* out_scores, int32_t* status /* NULL or [n_pairs]: 0, 1 non-finite, 2 empty region */,
                                int32_t* counts /* NULL or [n_feat] */, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- region score matrices: every masked query image against every masked gallery image -------------------------------------------
+ * Set A has n_a feature images and set B has n_b (q, k, v of a set: [n][B][N][H*D], as dsim_score_matrix); each image carries a
+ * byte mask [N] (non-zero = on) with region R_i.  Cell (i, j) is exactly the region score of the pair (A_i, B_j) as
+ * dsim_pair_score_regions defines it: rows in ascending token order, both SDPAs over the regions' rows only, outputs rounded to the
+ * pipeline dtype, cosine with F.cosine_similarity's eps or mse divided by B H |R_query| D, the mean of the two directions.  Each
+ * image's self-attention over its region is computed once; a cell costs one attention per direction.
+ * With all masks full it is dsim_score_matrix's cell.  A cell with an empty region on either side is NaN with status 2, and no
+ * other cell is disturbed.  Rows outside a region are never read.
+ *   out         : device f32 [n_a][n_b]
+ *   status      : NULL, or device int32 [n_a][n_b]: 0, 1 where the score is NaN or infinite, 2 where a region of the cell is empty
+ *   counts      : NULL, or device int32 [n_a + n_b]: |R_i| of set A's images, then of set B's
+ * Deterministic, no atomics; a cell depends on its two images and their regions alone.
+ * DSIM_ERR_INVALID (workspace query: 0) for a bad dtype, similarity or head dim, n_a < 1 or n_b < 1, n_a + n_b > 65535,
+ * B H > 65535, ceil(N/128) n_a n_b 2 >= 2^31, or any tensor or list of 2^31 elements or more; DSIM_ERR_WORKSPACE for a short
+ * workspace; both are decided on the host before anything is enqueued. */
+size_t dsim_score_matrix_regions_workspace_bytes(int n_a, int n_b, int B, int H, int N, int D, int dtype);
+int    dsim_score_matrix_regions(const void* qa, const void* ka, const void* va, const uint8_t* mask_a, int n_a,
+                                 const void* qb, const void* kb, const void* vb, const uint8_t* mask_b, int n_b,
+                                 int B, int H, int N, int D, int dtype, int similarity,
+                                 float* out /* [n_a][n_b] */, int32_t* status /* NULL or [n_a][n_b]: 0 | 1 | 2 */,
+                                 int32_t* counts /* NULL or [n_a + n_b] */,
+                                 void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- text attention maps and text-guided regions: the prompt's cross-attention picks the tokens --------------------------------
  * What `--use_text_attn` (argprocess.py:17 of the reference) names.  For image i, on the conditional CFG half only (batch element
  * e = 2 i + 1 of xq; context row 1 when n_kv == 2, row e when n_kv == 2 n_images):
