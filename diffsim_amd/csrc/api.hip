@@ -77,10 +77,9 @@ size_t dsim_score_matrix_workspace_bytes(int n_a, int n_b, int B, int H, int N, 
 int dsim_score_matrix(const void* qa, const void* ka, const void* va, int n_a, const void* qb, const void* kb, const void* vb, int n_b,
                       int B, int H, int N, int D, int dtype, int similarity, float* out, int32_t* status, void* workspace,
                       size_t workspace_bytes, void* stream) {
-    const int st = tail_prologue({qa, ka, va, qb, kb, vb, out}, DSIM_OK, workspace, workspace_bytes);
-    if (st != DSIM_OK) return st;
-    return launch_score_matrix(qa, ka, va, n_a, qb, kb, vb, n_b, B, H, N, D, dtype, similarity, out, status, workspace,
-                               workspace_bytes, (hipStream_t)stream);
+    MatrixArgs a{{qa, qb}, {ka, kb}, {va, vb}, {nullptr, nullptr}, n_a, n_b, B, H, N, D, similarity, workspace, workspace_bytes};
+    const int st = tail_prologue({qa, ka, va, qb, kb, vb, out}, matrix_args_check(a, dtype, false), a.scratch, a.scratch_bytes);
+    return st != DSIM_OK ? st : launch_score_matrix(a, dtype, out, status, (hipStream_t)stream);
 }
 
 size_t dsim_pair_score_maps_workspace_bytes(int n_pairs, int B, int H, int N, int D) {
@@ -117,12 +116,9 @@ int dsim_score_matrix_regions(const void* qa, const void* ka, const void* va, co
                               const void* kb, const void* vb, const uint8_t* mask_b, int n_b, int B, int H, int N, int D, int dtype,
                               int similarity, float* out, int32_t* status, int32_t* counts, void* workspace, size_t workspace_bytes,
                               void* stream) {
-    const bool served = (similarity == 0 || similarity == 1) && score_matrix_regions_scratch_bytes(n_a, n_b, B, H, N, D, dtype) != 0;
-    const int st = tail_prologue({qa, ka, va, mask_a, qb, kb, vb, mask_b, out}, served ? DSIM_OK : DSIM_ERR_INVALID, workspace,
-                                 workspace_bytes);
-    if (st != DSIM_OK) return st;
-    return launch_score_matrix_regions(qa, ka, va, mask_a, n_a, qb, kb, vb, mask_b, n_b, B, H, N, D, dtype, similarity, out, status,
-                                       counts, workspace, workspace_bytes, (hipStream_t)stream);
+    MatrixArgs a{{qa, qb}, {ka, kb}, {va, vb}, {mask_a, mask_b}, n_a, n_b, B, H, N, D, similarity, workspace, workspace_bytes};
+    const int st = tail_prologue({qa, ka, va, mask_a, qb, kb, vb, mask_b, out}, matrix_args_check(a, dtype, true), a.scratch, a.scratch_bytes);
+    return st != DSIM_OK ? st : launch_score_matrix_regions(a, dtype, out, status, counts, (hipStream_t)stream);
 }
 
 size_t dsim_pair_align_workspace_bytes(int n_pairs, int B, int H, int N, int D) {

@@ -1167,13 +1167,13 @@ size_t score_matrix160_scratch_bytes(int n_a, int n_b, int B, int H) {
     return 2 * (mat160_self_bytes(n_a, B, H) + mat160_self_bytes(n_b, B, H)) + part160_bytes((long)n_a * n_b, B, H);
 }
 
-int launch_score_matrix160(const void* qa, const void* ka, const void* va, int n_a, const void* qb, const void* kb, const void* vb, int n_b,
-                           int B, int H, int mse, float* out, int32_t* status, void* scratch, size_t scratch_bytes, hipStream_t s) {
-    if (scratch_bytes < score_matrix160_scratch_bytes(n_a, n_b, B, H)) return DSIM_ERR_WORKSPACE;
-    // 32-bit unit and partial-slot indices
-    if ((long)n_a * n_b * B * H * 2 * 8 >= (1l << 31) || (long)(A_N - 1) * H * A_D * 2 + A_ROWB >= (1l << 31)) return DSIM_ERR_INVALID;
-    if (((size_t)qa | (size_t)ka | (size_t)va | (size_t)qb | (size_t)kb | (size_t)vb) & 15) return DSIM_ERR_INVALID;
-    char* selfa = (char*)scratch;
+// m: launch_score_matrix's arguments, whose shape matrix_shape_served has passed (N = 256, D = 160: the 32-bit unit and partial-slot
+// indices, the bytes of a (batch element, head) view)
+int launch_score_matrix160(const MatrixArgs& m, float* out, int32_t* status, hipStream_t s) {
+    const int n_a = m.n_a, n_b = m.n_b, B = m.B, H = m.H;
+    if (m.scratch_bytes < score_matrix160_scratch_bytes(n_a, n_b, B, H)) return DSIM_ERR_WORKSPACE;
+    if (((size_t)m.q[0] | (size_t)m.k[0] | (size_t)m.v[0] | (size_t)m.q[1] | (size_t)m.k[1] | (size_t)m.v[1]) & 15) return DSIM_ERR_INVALID;
+    char* selfa = (char*)m.scratch;
     char* selfb = selfa + mat160_self_bytes(n_a, B, H);
     char* lanea = selfb + mat160_self_bytes(n_b, B, H);
     char* laneb = lanea + mat160_self_bytes(n_a, B, H);
@@ -1181,7 +1181,7 @@ int launch_score_matrix160(const void* qa, const void* ka, const void* va, int n
     const int ld = H * A_D;
     for (int set = 0; set < 2; ++set) {
         AttnArgs a;
-        a.q = set ? qb : qa; a.k = set ? kb : ka; a.v = set ? vb : va; a.out = set ? selfb : selfa;
+        a.q = m.q[set]; a.k = m.k[set]; a.v = m.v[set]; a.out = set ? selfb : selfa;
         a.ldq = a.ldk = a.ldo = ld;
         a.B = a.Bkv = (set ? n_b : n_a) * B;
         a.H = H; a.Nq = a.Nk = A_N; a.D = A_D;
@@ -1193,11 +1193,11 @@ int launch_score_matrix160(const void* qa, const void* ka, const void* va, int n
                            (h16*)(set ? laneb : lanea), set ? n_b : n_a, B, H);
     }
     const int g = grid160((long)n_a * n_b * B * H * 2, 64);
-    const int st = launch_lds<matrix_cross160_kernel>(dim3(g), dim3(512), A_LDS, s, (const h16*)qa, (const h16*)ka, (const h16*)va,
-                                                      (const h16*)lanea, (const h16*)qb, (const h16*)kb, (const h16*)vb, (const h16*)laneb,
-                                                      n_a, n_b, B, H, softmax_c160(), mse, part);
+    const int st = launch_lds<matrix_cross160_kernel>(dim3(g), dim3(512), A_LDS, s, (const h16*)m.q[0], (const h16*)m.k[0], (const h16*)m.v[0],
+                                                      (const h16*)lanea, (const h16*)m.q[1], (const h16*)m.k[1], (const h16*)m.v[1],
+                                                      (const h16*)laneb, n_a, n_b, B, H, softmax_c160(), m.similarity, part);
     if (st != DSIM_OK) return st;
-    hipLaunchKernelGGL(pair_finish160_kernel, dim3(n_a * n_b), dim3(64), 0, s, (const float*)part, B * H * 8, mse,
+    hipLaunchKernelGGL(pair_finish160_kernel, dim3(n_a * n_b), dim3(64), 0, s, (const float*)part, B * H * 8, m.similarity,
                        (double)B * H * A_N * A_D, out, status);
     DSIM_HIP_CHECK(hipGetLastError());
     return DSIM_OK;

@@ -356,6 +356,19 @@ struct PairArgs {
     size_t scratch_bytes = 0;
 };
 
+// the score matrices over two sets of feature images -- tails.hip, region_matrix.hip, attn160.hip: what launch_score_matrix,
+// _matrix160 and _matrix_regions share; their outputs and the compute dtype travel beside it
+struct MatrixArgs {
+    const void* q[2];                           // set A, set B, each q, k, v: [n][B][N][H*D] contiguous, the compute dtype
+    const void* k[2];
+    const void* v[2];
+    const uint8_t* mask[2];                     // device [n][N] bytes per set, non-zero = on; both null: the unmasked call
+    int n_a, n_b, B, H, N, D;
+    int similarity;                             // 0 cosine, 1 mse
+    void* scratch;                              // 256-byte aligned; the launcher's *_scratch_bytes
+    size_t scratch_bytes;
+};
+
 // row-resident fused feed-forward of the 320-channel transformer blocks (h16) -- rowres.hip
 //   out = x + W2 (h * gelu(g)) + b2,  [h ; g] = W1 LN(x) + b1
 struct FFArgs {
@@ -394,6 +407,11 @@ inline int pair_args_check(const PairArgs& a, int dtype, bool tiled = true) {
     if (dtype != DSIM_F32 && dtype != DSIM_BF16 && dtype != DSIM_F16) return DSIM_ERR_INVALID;
     if (a.similarity != 0 && a.similarity != 1) return DSIM_ERR_INVALID;
     return pair_shape_served(a.n_pairs, a.B, a.H, a.N, a.D, tiled) ? DSIM_OK : DSIM_ERR_INVALID;
+}
+// The same for the matrix launchers: a similarity outside 0 | 1, a call matrix_shape_served refuses (listed: the region matrix)
+inline int matrix_args_check(const MatrixArgs& a, int dtype, bool listed) {
+    if (a.similarity != 0 && a.similarity != 1) return DSIM_ERR_INVALID;
+    return matrix_shape_served(a.n_a, a.n_b, a.B, a.H, a.N, a.D, dtype, listed) ? DSIM_OK : DSIM_ERR_INVALID;
 }
 }  // namespace DSIM_H16_NS
 // ... and, seen from the bf16 objects of the product build, their fp16 twins: DSIM_F16_TWIN(f(args)) is how a bf16 launcher forwards

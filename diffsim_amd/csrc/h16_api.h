@@ -60,10 +60,7 @@ int launch_region_lists(const uint8_t* mask, int n_feat, int N, int32_t* list, i
 // its region once, at compacted positions, then one listed attention per cell and direction -- region_matrix.hip
 //   out [n_a][n_b]; status (may be NULL) [n_a][n_b]: 0, 1 non-finite, 2 empty region; counts (may be NULL) [n_a + n_b]
 size_t score_matrix_regions_scratch_bytes(int n_a, int n_b, int B, int H, int N, int D, int dtype);      // 0: call not served
-int launch_score_matrix_regions(const void* qa, const void* ka, const void* va, const uint8_t* mask_a, int n_a, const void* qb,
-                                const void* kb, const void* vb, const uint8_t* mask_b, int n_b, int B, int H, int N, int D, int dtype,
-                                int similarity, float* out, int32_t* status, int32_t* counts, void* scratch, size_t scratch_bytes,
-                                hipStream_t s);
+int launch_score_matrix_regions(const MatrixArgs& a, int dtype, float* out, int32_t* status, int32_t* counts, hipStream_t s);
 // text attention maps: the tapped block's cross-attention on the conditional CFG half, averaged over the heads; its weighted sum over
 // the prompt tokens (saliency) and the token region above rel_threshold x the image's mean saliency (text_attn_kernel,
 // text_region_kernel, any head dim and dtype, 1 <= L <= 128) -- textattn.hip
@@ -77,11 +74,11 @@ int launch_text_attention(const void* xq, int ldq, const void* xk, int ldk, int 
 bool sdpa160_applies(const AttnArgs& a);
 int launch_sdpa160(const AttnArgs& a, hipStream_t s);
 // score matrix (every image of set A against every image of set B; q, k, v of a set: [n][B][N][H*D]): the self attentions once per
-// image into the workspace, then two cross attentions per cell -- tails.hip (any shape), attn160.hip (the default tap, 16-bit)
-size_t score_matrix_scratch_bytes(int n_a, int n_b, int B, int H, int N, int D, int dtype);
-int launch_score_matrix(const void* qa, const void* ka, const void* va, int n_a, const void* qb, const void* kb, const void* vb, int n_b,
-                        int B, int H, int N, int D, int dtype, int similarity, float* out, int32_t* status, void* scratch,
-                        size_t scratch_bytes, hipStream_t s);
+// image into the workspace, then two cross attentions per cell -- tails.hip (any shape), attn160.hip (the default tap, 16-bit).
+// The launchers take MatrixArgs (common.h).  matrix_shape_served: the one answer to which matrix calls are served, for the workspace
+// queries (0 exactly where it refuses), the launchers and the entry points (matrix_args_check, common.h); listed: the region matrix
+bool matrix_shape_served(int n_a, int n_b, int B, int H, int N, int D, int dtype, bool listed);
+size_t score_matrix_scratch_bytes(int n_a, int n_b, int B, int H, int N, int D, int dtype);      // 0: call not served
+int launch_score_matrix(const MatrixArgs& a, int dtype, float* out, int32_t* status, hipStream_t s);
 size_t score_matrix160_scratch_bytes(int n_a, int n_b, int B, int H);
-int launch_score_matrix160(const void* qa, const void* ka, const void* va, int n_a, const void* qb, const void* kb, const void* vb, int n_b,
-                           int B, int H, int mse, float* out, int32_t* status, void* scratch, size_t scratch_bytes, hipStream_t s);
+int launch_score_matrix160(const MatrixArgs& a, float* out, int32_t* status, hipStream_t s);

@@ -81,10 +81,7 @@ int launch_regions_t(const PairArgs& a, const uint8_t* mask, int n_feat, float* 
                                                              (const T*)a.k, (const T*)a.v, (const int32_t*)list, (const int32_t*)cnt,
                                                              a.idx_a, a.idx_b, a.B, a.H, a.N, scale_log2_of(Dc), a.similarity, part);
         if (st != DSIM_OK) return st;
-        hipLaunchKernelGGL(pair_finish_kernel<true>, dim3((a.n_pairs + 63) / 64), dim3(64), 0, s, (const float*)part, (const int32_t*)cnt,
-                           a.idx_a, a.idx_b, a.n_pairs, qt * a.B * a.H, a.similarity, (double)a.B * a.H * Dc, out, status);
-        DSIM_HIP_CHECK(hipGetLastError());
-        return DSIM_OK;
+        return launch_pair_finish<true>(part, cnt, a.idx_a, a.idx_b, a.n_pairs, qt * a.B * a.H, a.similarity, (double)a.B * a.H * Dc, out, status, s);
     });
 }
 

@@ -1,8 +1,10 @@
 // What the score tails share on top of the tiled attention core (attn_core.h): the rounding of attend's output to the pipeline
 // dtype, the products of a cross output against a self output, a workgroup's partial, the two-attention pair body (pair_tail_body:
-// tails.hip's pair and map kernels in row order, regions.hip's region tail through row lists) and the f64 finish arithmetic
-// (direction_value, store_score, pair_finish_kernel).  Shared by tails.hip (pairs, maps, matrices) and regions.hip (region scores),
-// which must round and multiply alike to agree bit for bit; everything here lives in their dsim::(anonymous namespace).
+// tails.hip's pair and map kernels in row order, regions.hip's region tail through row lists), the one-attention matrix kernel
+// (matrix_tail_kernel: tails.hip's score matrix in row order, region_matrix.hip's through row lists) with its arguments and
+// workspace layout, and the f64 finish (direction_value, store_score, pair_finish_kernel, launch_pair_finish).  Shared by tails.hip
+// (pairs, maps, matrices), regions.hip (region scores) and region_matrix.hip (region matrices), which must round and multiply alike
+// to agree bit for bit; everything here lives in their dsim::(anonymous namespace).
 #pragma once
 #include "attn_core.h"
 
@@ -183,6 +185,142 @@ __device__ __forceinline__ void pair_tail_body(const T* __restrict__ qg, const T
     }
 }
 
+// ---- score matrices ------------------------------------------------------------------------------------------------------------
+// Every image of set A against every image of set B.  The score of (a, b) needs O_aa and O_bb, which do not depend on the partner:
+// they are computed once per image and read back by every cell.  The kernel arguments with the rows in order, and with listed rows:
+// the same fields and the lists and counts (the in-order kernel carries no pointer it never reads).  A struct of its own, the two
+// pointers in front of the extents: with them behind, as a derived struct puts them, hipcc groups the listed kernel's scalar argument
+// loads otherwise, and that form measured 1.3 % slower at (N, H, D) = (1024, 8, 80) (profiles/matrix_tail_refactor.json,
+// "earlier_forms").
+struct MatArgs {
+    const void* q[2]; const void* k[2]; const void* v[2];      // set A, set B: [n][B][N][H*D]
+    void* self[2];                                              // the sets' self outputs, same layout (listed: rows by compacted position)
+    int n_a, n_b, B, H, N;
+};
+struct RegMatArgs {
+    const void* q[2]; const void* k[2]; const void* v[2];
+    void* self[2];
+    const int32_t* list;                                        // [n_a + n_b][N]: set A's images at index i, set B's at n_a + j
+    const int32_t* cnt;                                         // [n_a + n_b]
+    int n_a, n_b, B, H, N;
+};
+
+// One attention of a 128-query workgroup, in one of two modes.  SELF: an image's self attention (rounded to the compute dtype as the
+// pair tail rounds it; f32 in the parity mode) into [n][B][N][H*D].  CROSS: one attention per cell and direction -- O_ab = SDPA(Qa, Kb,
+// Vb) against O_aa read back, O_ba = SDPA(Qb, Ka, Va) against O_bb -- with the pair tail's products, reduction and partial layout
+// [cell][dir][bh][qtile][4], so pair_finish_kernel folds them.  Both modes run the same attend on the same Q fragments as
+// pair_tail_body: a cell of an image against itself compares bit-identical tensors, and a cell equals the pair tail's score of the
+// same two images.
+// Rows as pair_tail_body's.  RowsInOrder: tails.hip's score matrix (matrix_tail_kernel<T, D, RowsInOrder>).  RowsListed:
+// region_matrix.hip's region matrix (its region_matrix_kernel<T, D> names that instantiation): the counts stand where N stood; SELF
+// stores at the COMPACTED position t (row t of the image's slab holds token list[t]), so that CROSS reads it back by position without
+// an index load; a SELF workgroup whose first position is at or past its image's count leaves as a whole before any barrier (its rows
+// are never written and never read), a CROSS workgroup past the query image's count, or of a cell with an empty image, writes a zero
+// partial and leaves likewise -- pair_tail_body's rule and order.
+// The shared text is the kernel itself, not an inline body under two wrapper kernels: hipcc optimises such a body as a function of
+// its own before it inlines it, and the kernels then come out in another instruction order than written directly ("Region
+// score matrices").  Each translation unit instantiates only the row order it launches.  Args is a parameter only so that the symbol
+// names the argument struct: it is MatrixKernelArgs<Rows>, nothing else.
+// grid  self: (ceil(N/128), B*H, n_a + n_b);  cross: (ceil(N/128) * n_cells * 2, B*H)
+template <typename Rows> using MatrixKernelArgs = std::conditional_t<Rows::LISTED, RegMatArgs, MatArgs>;
+template <typename T, int D, typename Rows, typename Args = MatrixKernelArgs<Rows>>
+__global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void matrix_tail_kernel(const Args p, float scale_log2, int mse, int self_mode,
+                                                                                     float* __restrict__ part) {
+    static_assert(std::is_same<Args, MatrixKernelArgs<Rows>>::value, "the in-order kernel takes MatArgs, the listed one RegMatArgs");
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, l31 = lane & 31;
+    const int bh = blockIdx.y, b = bh / p.H, h = bh - b * p.H;
+    const int N = p.N, ld = p.H * D;
+    const size_t img = (size_t)p.B * N * ld;
+    const size_t boff = (size_t)b * N * ld + h * D;
+    const int qt = (N + 127) / 128;
+    int qtile, set, iq, ix, cell = 0, dir = 0;      // iq, ix: the query image and the K / V image inside their sets
+    int fq = 0, fx = 0;                             // (listed) the same two among the n_a + n_b lists
+    float* o = nullptr;                             // the workgroup's partial (cross)
+    if (self_mode) {
+        qtile = blockIdx.x;
+        fq = fx = blockIdx.z;
+        set = fq >= p.n_a;
+        iq = ix = fq - (set ? p.n_a : 0);
+    } else {
+        qtile = blockIdx.x % qt;
+        const int cd = blockIdx.x / qt;
+        cell = cd >> 1; dir = cd & 1;
+        const int ia = cell / p.n_b, ib = cell - ia * p.n_b;
+        set = dir;
+        iq = dir ? ib : ia;
+        ix = dir ? ia : ib;
+        if constexpr (Rows::LISTED) {
+            fq = dir ? p.n_a + ib : ia;
+            fx = dir ? ia : p.n_a + ib;
+            o = part + ((((size_t)cell * 2 + dir) * gridDim.y + bh) * qt + qtile) * 4;
+        }
+    }
+    int nq = N, nx = N;                             // the two images' row counts
+    Rows rq, rx;
+    if constexpr (Rows::LISTED) {
+        nq = p.cnt[fq];
+        nx = p.cnt[fx];
+        if (qtile * 128 >= nq || nx == 0) {         // (uniform over the workgroup)
+            if (!self_mode && threadIdx.x == 0) o[0] = o[1] = o[2] = o[3] = 0.f;
+            return;
+        }
+        rq.list = p.list + (size_t)fq * N;
+        rx.list = p.list + (size_t)fx * N;
+    }
+    const T* qg = (const T*)p.q[set];
+    const T* kg = (const T*)p.k[set ^ (self_mode ? 0 : 1)];
+    const T* vg = (const T*)p.v[set ^ (self_mode ? 0 : 1)];
+    T* so = (T*)p.self[set] + iq * img + boff;
+    const int t = qtile * 128 + wave * 32 + l31;    // query position
+    int q = t < nq ? t : nq - 1;                    // its row (a position past the end: the last one's)
+    if constexpr (Rows::LISTED) q = rq.list[q];
+    QFrags<T, D> qf;
+    load_q<T, D>(qf, qg + iq * img + boff + (size_t)q * ld, half, scale_log2);
+    OAcc<T, D> oa;
+    attend<T, D, false>(qf, kg + ix * img + boff, vg + ix * img + boff, ld, nx, smem, oa, nullptr, rx);
+    settle<T, D>(oa);
+    if (self_mode) {
+        if (t < nq) fold_rounded<T, D>(oa, half, 0, [&](int, int, int, int d, T y) { so[(size_t)t * ld + d] = y; return 0; });  // (no state)
+        return;
+    }
+    TailSums s;
+    if (t < nq) s = tail_products<T, D>(oa, half, mse, [&](int, int, int d) { return (float)so[(size_t)t * ld + d]; });
+    if constexpr (!Rows::LISTED) o = part + ((((size_t)cell * 2 + dir) * gridDim.y + bh) * qt + qtile) * 4;
+    store_block_partial(s, lane, wave, o);
+}
+
+// workspace of a tiled score matrix, each part 256-byte aligned:
+//   [lists int32 [n_a + n_b][N] | counts int32 [n_a + n_b] | cell indices int32 [2][n_cells] |]   (listed only)
+//   self A | self B | partials f32 [n_cells][2][B H][qtiles][4]
+struct MatrixLayout {
+    size_t lists = 0, counts = 0, index = 0, self_a, self_b, parts;
+    MatrixLayout(const MatrixArgs& a, size_t es, bool listed) {
+        const size_t nf = (size_t)a.n_a + a.n_b, nc = (size_t)a.n_a * a.n_b, image = (size_t)a.B * a.N * a.H * a.D * es;
+        if (listed) {
+            lists = up256(nf * a.N * sizeof(int32_t));
+            counts = up256(nf * sizeof(int32_t));
+            index = up256(nc * sizeof(int32_t));
+        }
+        self_a = up256(a.n_a * image);
+        self_b = up256(a.n_b * image);
+        parts = up256(nc * 2 * a.B * a.H * ((a.N + 127) / 128) * 4 * sizeof(float));
+    }
+    size_t self_at() const { return lists + counts + 2 * index; }
+    size_t parts_at() const { return self_at() + self_a + self_b; }
+    size_t total() const { return parts_at() + parts; }
+    // the kernels' arguments (MatArgs, or RegMatArgs less its list and cnt) over a's workspace
+    template <typename Args>
+    Args kernel_args(const MatrixArgs& a) const {
+        Args m{};
+        for (int set = 0; set < 2; ++set) { m.q[set] = a.q[set]; m.k[set] = a.k[set]; m.v[set] = a.v[set]; }
+        m.self[0] = (char*)a.scratch + self_at();
+        m.self[1] = (char*)m.self[0] + self_a;
+        m.n_a = a.n_a; m.n_b = a.n_b; m.B = a.B; m.H = a.H; m.N = a.N;
+        return m;
+    }
+};
+
 // ---- the f64 finish ------------------------------------------------------------------------------------------------------------
 // A direction's value from the f64 folds of its partials (diffsim.py:187-197): mse a / count, cosine a / (|x| |y|) with
 // F.cosine_similarity's eps = 1e-8 under each norm.  The denominator alone for a caller that divides many numerators by it.
@@ -229,6 +367,16 @@ __global__ void pair_finish_kernel(const float* __restrict__ part, const int32_t
         res += direction_value(a, x2, y2, mse, REGIONS ? count * n[dir] : count);
     }
     store_score(res, out + p, status ? status + p : nullptr);
+}
+
+// pair_finish_kernel over n items (pairs or cells) of nblk partials per direction: its one launch site
+template <bool REGIONS>
+int launch_pair_finish(const float* part, const int32_t* cnt, const int32_t* idx_a, const int32_t* idx_b, int n, int nblk, int mse,
+                       double count, float* out, int32_t* status, hipStream_t s) {
+    hipLaunchKernelGGL(pair_finish_kernel<REGIONS>, dim3((n + 63) / 64), dim3(64), 0, s, part, cnt, idx_a, idx_b, n, nblk, mse, count, out,
+                       status);
+    DSIM_HIP_CHECK(hipGetLastError());
+    return DSIM_OK;
 }
 
 }  // namespace

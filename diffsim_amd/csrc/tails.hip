@@ -8,7 +8,9 @@
 //                      three f32 partial sums per workgroup reach HBM and a second fixed-order pass
 //                      folds them (no float atomics => bit-reproducible scores).
 // pair_tail_kernel and pair_map_kernel name the in-order instantiations of tail_core.h's pair_tail_body (the listed one is
-// regions.hip's); the finish arithmetic and pair_finish_kernel are tail_core.h's too.  The launchers take PairArgs (common.h).
+// regions.hip's); the score matrix launches the in-order instantiation of tail_core.h's matrix_tail_kernel (the listed one is
+// region_matrix.hip's); the finish arithmetic, pair_finish_kernel and its launch are tail_core.h's too.  The launchers take PairArgs
+// or MatrixArgs (common.h).
 #include "tail_core.h"
 
 namespace dsim {
@@ -22,71 +24,6 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void pair_tail_kerne
     pair_tail_body<T, D, false, RowsInOrder>(qg, kg, vg, nullptr, nullptr, idx_a, idx_b, B, H, N, scale_log2, mse, part);
 }
 
-// ---- score matrix ---------------------------------------------------------------------------------------------------------------
-// Every image of set A against every image of set B.  The score of (a, b) needs O_aa and O_bb, which do not depend on the partner: the
-// SELF mode computes each image's once (rounded to the compute dtype as the pair tail rounds it; f32 in the parity mode) into
-// [n][B][N][H*D], and the CROSS mode runs one attention per cell and direction -- O_ab = SDPA(Qa, Kb, Vb) against O_aa read back,
-// O_ba = SDPA(Qb, Ka, Va) against O_bb -- with the pair tail's products, reduction and partial layout [cell][dir][bh][qtile][4], so
-// pair_finish_kernel folds them.  Both modes run the same attend on the same Q fragments as pair_tail_kernel: a cell of an image
-// against itself compares bit-identical tensors, and a cell equals the pair tail's score of the same two images.
-// grid  self: (ceil(N/128), B*H, n_a + n_b);  cross: (ceil(N/128) * n_cells * 2, B*H)
-struct MatArgs {
-    const void* q[2]; const void* k[2]; const void* v[2];      // set A, set B: [n][B][N][H*D]
-    void* self[2];                                              // the sets' self outputs, same layout
-    int n_a, n_b, B, H, N;
-};
-template <typename T, int D>
-__global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void matrix_tail_kernel(const MatArgs p, float scale_log2, int mse, int self_mode,
-                                                                                     float* __restrict__ part) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, l31 = lane & 31;
-    const int bh = blockIdx.y, b = bh / p.H, h = bh - b * p.H;
-    const int N = p.N, ld = p.H * D;
-    const size_t img = (size_t)p.B * N * ld;
-    const size_t boff = (size_t)b * N * ld + h * D;
-    const int qt = (N + 127) / 128;
-    int qtile, set, iq, ix, cell = 0, dir = 0;
-    if (self_mode) {
-        qtile = blockIdx.x;
-        set = (int)blockIdx.z >= p.n_a;
-        iq = ix = (int)blockIdx.z - (set ? p.n_a : 0);
-    } else {
-        qtile = blockIdx.x % qt;
-        const int cd = blockIdx.x / qt;
-        cell = cd >> 1; dir = cd & 1;
-        const int ia = cell / p.n_b, ib = cell - ia * p.n_b;
-        set = dir;
-        iq = dir ? ib : ia;
-        ix = dir ? ia : ib;
-    }
-    const T* qg = (const T*)p.q[set];
-    const T* kg = (const T*)p.k[set ^ (self_mode ? 0 : 1)];
-    const T* vg = (const T*)p.v[set ^ (self_mode ? 0 : 1)];
-    T* so = (T*)p.self[set] + iq * img + boff;
-    const int q = qtile * 128 + wave * 32 + l31;
-    const int qc = q < N ? q : N - 1;
-    QFrags<T, D> qf;
-    load_q<T, D>(qf, qg + iq * img + boff + (size_t)qc * ld, half, scale_log2);
-    OAcc<T, D> oa;
-    attend<T, D>(qf, kg + ix * img + boff, vg + ix * img + boff, ld, N, smem, oa);
-    settle<T, D>(oa);
-    if (self_mode) {
-        if (q < N) fold_rounded<T, D>(oa, half, 0, [&](int, int, int, int d, T y) { so[(size_t)q * ld + d] = y; return 0; });  // (no state)
-        return;
-    }
-    TailSums t;
-    if (q < N) t = tail_products<T, D>(oa, half, mse, [&](int, int, int d) { return (float)so[(size_t)q * ld + d]; });
-    store_block_partial(t, lane, wave, part + ((((size_t)cell * 2 + dir) * gridDim.y + bh) * qt + qtile) * 4);
-}
-
-// pair_finish_kernel over n items (pairs or cells) of nblk partials per direction
-int launch_finish(const float* part, int n, int nblk, int mse, double count, float* out, int32_t* status, hipStream_t s) {
-    hipLaunchKernelGGL(pair_finish_kernel<false>, dim3((n + 63) / 64), dim3(64), 0, s, part, (const int32_t*)nullptr,
-                       (const int32_t*)nullptr, (const int32_t*)nullptr, n, nblk, mse, count, out, status);
-    DSIM_HIP_CHECK(hipGetLastError());
-    return DSIM_OK;
-}
-
 template <typename T>
 int launch_tail_t(const PairArgs& a, float* out, int32_t* status, hipStream_t s) {
     return with_head_dim(a.D, [&](auto dc) -> int {
@@ -96,31 +33,27 @@ int launch_tail_t(const PairArgs& a, float* out, int32_t* status, hipStream_t s)
                                                            (const T*)a.k, (const T*)a.v, a.idx_a, a.idx_b, a.B, a.H, a.N,
                                                            scale_log2_of(Dc), a.similarity, (float*)a.scratch);
         if (st != DSIM_OK) return st;
-        return launch_finish((const float*)a.scratch, a.n_pairs, qt * a.B * a.H, a.similarity, (double)a.B * a.H * a.N * Dc, out, status, s);
+        return launch_pair_finish<false>((const float*)a.scratch, nullptr, nullptr, nullptr, a.n_pairs, qt * a.B * a.H, a.similarity,
+                                         (double)a.B * a.H * a.N * Dc, out, status, s);
     });
 }
 
-// workspace of the tiled score matrix: [self A | self B | partials], each 256-byte aligned
-size_t mat_self_bytes(int n, int B, int H, int N, int D, int es) { return up256((size_t)n * B * N * H * D * es); }
-size_t mat_part_bytes(long n_cells, int B, int H, int N) { return up256((size_t)n_cells * 2 * B * H * ((N + 127) / 128) * 4 * sizeof(float)); }
-
+// score matrix: matrix_tail_kernel (tail_core.h) with the rows in order, the self mode once per image, then the cross mode once per
+// cell and direction, and the pair finish over the cells
 template <typename T>
-int launch_matrix_t(const void* qa, const void* ka, const void* va, int n_a, const void* qb, const void* kb, const void* vb, int n_b, int B,
-                    int H, int N, int D, int mse, float* out, int32_t* status, void* scratch, hipStream_t s) {
-    MatArgs m;
-    m.q[0] = qa; m.k[0] = ka; m.v[0] = va; m.q[1] = qb; m.k[1] = kb; m.v[1] = vb;
-    m.self[0] = scratch;
-    m.self[1] = (char*)scratch + mat_self_bytes(n_a, B, H, N, D, sizeof(T));
-    m.n_a = n_a; m.n_b = n_b; m.B = B; m.H = H; m.N = N;
-    float* part = (float*)((char*)m.self[1] + mat_self_bytes(n_b, B, H, N, D, sizeof(T)));
-    return with_head_dim(D, [&](auto dc) -> int {
+int launch_matrix_t(const MatrixArgs& a, float* out, int32_t* status, hipStream_t s) {
+    const MatrixLayout L(a, sizeof(T), false);
+    const MatArgs m = L.kernel_args<MatArgs>(a);
+    float* part = (float*)((char*)a.scratch + L.parts_at());
+    return with_head_dim(a.D, [&](auto dc) -> int {
         constexpr int Dc = decltype(dc)::value, LDS = ACfg<T, Dc>::LDS;
-        const int qt = (N + 127) / 128, nc = n_a * n_b;
-        int st = launch_lds<matrix_tail_kernel<T, Dc>>(dim3(qt, B * H, n_a + n_b), dim3(256), LDS, s, m, scale_log2_of(Dc), mse, 1, part);
+        constexpr auto kernel = matrix_tail_kernel<T, Dc, RowsInOrder>;
+        const int qt = (a.N + 127) / 128, nc = a.n_a * a.n_b, BH = a.B * a.H;
+        int st = launch_lds<kernel>(dim3(qt, BH, a.n_a + a.n_b), dim3(256), LDS, s, m, scale_log2_of(Dc), a.similarity, 1, part);
         if (st != DSIM_OK) return st;
-        st = launch_lds<matrix_tail_kernel<T, Dc>>(dim3(qt * nc * 2, B * H), dim3(256), LDS, s, m, scale_log2_of(Dc), mse, 0, part);
+        st = launch_lds<kernel>(dim3(qt * nc * 2, BH), dim3(256), LDS, s, m, scale_log2_of(Dc), a.similarity, 0, part);
         if (st != DSIM_OK) return st;
-        return launch_finish(part, nc, qt * B * H, mse, (double)B * H * N * Dc, out, status, s);
+        return launch_pair_finish<false>(part, nullptr, nullptr, nullptr, nc, qt * BH, a.similarity, (double)BH * a.N * Dc, out, status, s);
     });
 }
 
@@ -250,36 +183,54 @@ int launch_pair_score(const PairArgs& a, int dtype, float* out, int32_t* status,
         [&] { return DSIM_F16_TWIN(launch_pair_score(a, dtype, out, status, s)); });
 }
 
-size_t score_matrix_scratch_bytes(int n_a, int n_b, int B, int H, int N, int D, int dtype) {
-    if (n_a < 1 || n_b < 1 || B < 1 || H < 1 || N < 1 || D < 1) return 0;
-    if ((dtype == DSIM_BF16 || dtype == DSIM_F16) && pair_score160_applies(N, D, DSIM_H16))
-        return score_matrix160_scratch_bytes(n_a, n_b, B, H);           // (the fp16 persistent kernel has the bf16 one's layout)
-    const int es = dtype == DSIM_F32 ? 4 : 2;
-    return mat_self_bytes(n_a, B, H, N, D, es) + mat_self_bytes(n_b, B, H, N, D, es) + mat_part_bytes((long)n_a * n_b, B, H, N);
+// The matrix calls served, for both launchers, both workspace queries and both entry points: a dtype of the three, a head dim of
+// DSIM_FOR_EACH_D, at least one image per set, one token, one head; n_a + n_b on the self grid's 65535-wide axis and the cross grid in
+// a 32-bit extent.  Then what the kernels of the call index in 32 bits: the persistent default-tap kernels (16-bit, unmasked) their
+// per-wave partial slots and the bytes of a (batch element, head) view; the tiled kernels B*H on a 65535-wide grid axis (their
+// offsets are 64-bit), the unmasked call keeping the persistent one's bound on the partial slots; the listed call every tensor and
+// list under 2^31 elements.
+bool matrix_shape_served(int n_a, int n_b, int B, int H, int N, int D, int dtype, bool listed) {
+    if (dtype != DSIM_F32 && dtype != DSIM_BF16 && dtype != DSIM_F16) return false;
+    if (n_a < 1 || n_b < 1 || B < 1 || H < 1 || N < 1) return false;
+    if (with_head_dim(D, [](auto) { return DSIM_OK; }) != DSIM_OK) return false;
+    const long lim = 1l << 31, qt = (N + 127) / 128, nc = (long)n_a * n_b, bh = (long)B * H;
+    if ((long)n_a + n_b > 65535 || nc * 2 * qt >= lim) return false;
+    // the unmasked call's partial slots (bh < 2^27 first, so that the product cannot overflow)
+    const bool slots_ok = bh < lim / 16 && nc * bh * 16 < lim;
+    if (listed) {                                                                 // the tiled kernel over listed rows
+        if (bh > 65535) return false;
+        const long row = bh * D, mx = n_a > n_b ? n_a : n_b;                      // (row < 2^16 * 2^8)
+        if (row >= lim / N || row * N >= lim / mx) return false;                  // a set's q, k, v and self output
+        if (((long)n_a + n_b) * N >= lim) return false;                           // the lists
+        return nc * 2 * qt < lim / (bh * 4);                                      // the partials
+    } else if (dtype != DSIM_F32 && pair_score160_applies(N, D, DSIM_H16)) {      // the persistent default-tap kernels
+        return slots_ok && (long)(N - 1) * H * D * 2 + D * 2 < lim;               // a view's last row, in bytes
+    } else {                                                                      // the tiled kernel, rows in order
+        return bh <= 65535 && slots_ok;
+    }
 }
 
-int launch_score_matrix(const void* qa, const void* ka, const void* va, int n_a, const void* qb, const void* kb, const void* vb, int n_b,
-                        int B, int H, int N, int D, int dtype, int similarity, float* out, int32_t* status, void* scratch,
-                        size_t scratch_bytes, hipStream_t s) {
-    if (n_a < 1 || n_b < 1 || B < 1 || H < 1 || N < 1 || D % 8 || (similarity != 0 && similarity != 1)) return DSIM_ERR_INVALID;
-    if (dtype != DSIM_F32 && dtype != DSIM_BF16 && dtype != DSIM_F16) return DSIM_ERR_INVALID;
-    // 32-bit grid extents and cell indices
-    const long units = (long)n_a * n_b * 2 * ((N + 127) / 128);
-    if (units >= (1l << 31) || (long)n_a * n_b * B * H * 16 >= (1l << 31) || n_a + n_b > 65535) return DSIM_ERR_INVALID;
-    if (scratch_bytes < score_matrix_scratch_bytes(n_a, n_b, B, H, N, D, dtype)) return DSIM_ERR_WORKSPACE;
+size_t score_matrix_scratch_bytes(int n_a, int n_b, int B, int H, int N, int D, int dtype) {
+    if (!matrix_shape_served(n_a, n_b, B, H, N, D, dtype, false)) return 0;
+    if (dtype != DSIM_F32 && pair_score160_applies(N, D, DSIM_H16))
+        return score_matrix160_scratch_bytes(n_a, n_b, B, H);           // (the fp16 persistent kernel has the bf16 one's layout)
+    return MatrixLayout({{}, {}, {}, {}, n_a, n_b, B, H, N, D}, dtype_size(dtype), false).total();
+}
+
+// the default tap in a 16-bit mode runs the persistent kernels (attn160.hip)
+int launch_score_matrix(const MatrixArgs& a, int dtype, float* out, int32_t* status, hipStream_t s) {
+    const int st = matrix_args_check(a, dtype, false);
+    if (st != DSIM_OK) return st;
+    if (a.scratch_bytes < score_matrix_scratch_bytes(a.n_a, a.n_b, a.B, a.H, a.N, a.D, dtype)) return DSIM_ERR_WORKSPACE;
     return by_h16_dtype(
         dtype,
         [&](auto e) {
             typedef typename decltype(e)::type T;
             if constexpr (sizeof(T) == 2)
-                if (pair_score160_applies(N, D, DSIM_H16))
-                    return launch_score_matrix160(qa, ka, va, n_a, qb, kb, vb, n_b, B, H, similarity, out, status, scratch, scratch_bytes, s);
-            return launch_matrix_t<T>(qa, ka, va, n_a, qb, kb, vb, n_b, B, H, N, D, similarity, out, status, scratch, s);
+                if (pair_score160_applies(a.N, a.D, DSIM_H16)) return launch_score_matrix160(a, out, status, s);
+            return launch_matrix_t<T>(a, out, status, s);
         },
-        [&] {
-            return DSIM_F16_TWIN(launch_score_matrix(qa, ka, va, n_a, qb, kb, vb, n_b, B, H, N, D, dtype, similarity, out, status, scratch,
-                                                     scratch_bytes, s));
-        });
+        [&] { return DSIM_F16_TWIN(launch_score_matrix(a, dtype, out, status, s)); });
 }
 
 size_t pair_score_maps_scratch_bytes(int n_pairs, int B, int H, int N) {

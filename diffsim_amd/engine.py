@@ -554,6 +554,32 @@ def _check_features(ts, heads: int, shapes_ok: bool, msgs, idx=()):
     return B, N, D
 
 
+_SETS_MSGS = ("q,k,v of both sets must share dtype float32, bfloat16 or float16",
+              "features must be [n][B][N][H*D], one geometry for both sets", "features must be contiguous")
+
+
+def _check_two_sets(fa, fb, heads: int):
+    """_check_features for the two sets of (q, k, v) a matrix call takes, one geometry for both: ((qa, ka, va, qb, kb, vb), B, N, D)."""
+    (qa, ka, va), (qb, kb, vb) = fa, fb
+    ok = ka.shape == qa.shape == va.shape and kb.shape == qb.shape == vb.shape and qa.shape[1:] == qb.shape[1:]
+    ts = (qa, ka, va, qb, kb, vb)
+    return (ts, *_check_features(ts, heads, ok, _SETS_MSGS))
+
+
+def _check_region_mask(mask: torch.Tensor, n: int, N: int, what: str = "the region mask", rows: str = "n_feat"):
+    """a region mask: bool or uint8, (n, N); `what` names it and `rows` its first extent in the messages"""
+    if mask.dtype not in (torch.bool, torch.uint8):
+        raise _lib.DsimError(f"{what} must be bool or uint8")
+    if tuple(mask.shape) != (n, N):
+        raise _lib.DsimError(f"{what} must be ({rows}, N) = ({n}, {N}): {tuple(mask.shape)}")
+
+
+def _with_extras(out, *extras):
+    """out alone, or the tuple of out and the optional outputs the caller asked for (the others are None)"""
+    asked = tuple(e for e in extras if e is not None)
+    return (out,) + asked if asked else out
+
+
 def _similarity_code(similarity: str) -> int:
     if similarity not in ("cosine", "mse"):
         raise ValueError(similarity)
@@ -626,10 +652,7 @@ def pair_score_regions(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: 
     _require_cuda(q, k, v, mask, idx_a, idx_b)
     sim = _similarity_code(similarity)
     B, N, D = _check_features((q, k, v), heads, k.shape == q.shape == v.shape, _PAIR_MSGS, (idx_a, idx_b))
-    if mask.dtype not in (torch.bool, torch.uint8):
-        raise _lib.DsimError("the region mask must be bool or uint8")
-    if tuple(mask.shape) != (q.shape[0], N):
-        raise _lib.DsimError(f"the region mask must be (n_feat, N) = ({q.shape[0]}, {N}): {tuple(mask.shape)}")
+    _check_region_mask(mask, q.shape[0], N)
     mask = mask.view(torch.uint8)
     n_feat, n_pairs = q.shape[0], idx_a.numel()
     out = torch.empty(n_pairs, dtype=torch.float32, device=q.device)
@@ -639,7 +662,7 @@ def pair_score_regions(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: 
                f"no region scores for n_feat={n_feat} n_pairs={n_pairs} B={B} H={heads} N={N} D={D}", q.data_ptr(), k.data_ptr(),
                v.data_ptr(), mask.data_ptr(), n_feat, idx_a.data_ptr(), idx_b.data_ptr(), n_pairs, B, heads, N, D, _TORCH2DSIM[q.dtype],
                sim, out.data_ptr(), _ptr(status), _ptr(counts))
-    return out if not (return_status or return_counts) else (out,) + ((status,) if return_status else ()) + ((counts,) if return_counts else ())
+    return _with_extras(out, status, counts)
 
 
 TEXT_WANT = ("attn", "saliency", "mask", "counts", "status")
@@ -748,19 +771,15 @@ def score_matrix(fa, fb, heads: int, similarity: str = "cosine", return_status: 
     each image's self-attention is computed once.  return_status: also an int32 (n_a, n_b) tensor, 1 where the score is
     NaN / infinite."""
     sim = _similarity_code(similarity)
-    (qa, ka, va), (qb, kb, vb) = fa, fb
-    _require_cuda(qa, ka, va, qb, kb, vb)
-    B, N, D = _check_features((qa, ka, va, qb, kb, vb), heads,
-                              ka.shape == qa.shape == va.shape and kb.shape == qb.shape == vb.shape and qa.shape[1:] == qb.shape[1:],
-                              ("q,k,v of both sets must share dtype float32, bfloat16 or float16",
-                               "features must be [n][B][N][H*D], one geometry for both sets", "features must be contiguous"))
+    _require_cuda(*fa, *fb)
+    (qa, ka, va, qb, kb, vb), B, N, D = _check_two_sets(fa, fb, heads)
     n_a, n_b = qa.shape[0], qb.shape[0]
     out = torch.empty((n_a, n_b), dtype=torch.float32, device=qa.device)
     status = _i32((n_a, n_b), qa.device, return_status)
     _tail_call(qa.device, "score_matrix", (n_a, n_b, B, heads, N, D, _TORCH2DSIM[qa.dtype]),
                f"no score matrix for n_a={n_a} n_b={n_b} B={B} H={heads} N={N} D={D}", qa.data_ptr(), ka.data_ptr(), va.data_ptr(), n_a,
                qb.data_ptr(), kb.data_ptr(), vb.data_ptr(), n_b, B, heads, N, D, _TORCH2DSIM[qa.dtype], sim, out.data_ptr(), _ptr(status))
-    return (out, status) if return_status else out
+    return _with_extras(out, status)
 
 
 def score_matrix_regions_workspace_bytes(n_a: int, n_b: int, B: int, heads: int, N: int, D: int, dtype: torch.dtype) -> int:
@@ -776,17 +795,10 @@ def score_matrix_regions(fa, fb, mask_a: torch.Tensor, mask_b: torch.Tensor, hea
     also an int32 (n_a, n_b) tensor, 1 where the score is NaN / infinite, 2 where a region of the cell is empty (score NaN);
     return_counts: also the int32 (n_a + n_b,) region sizes, set A's then set B's."""
     sim = _similarity_code(similarity)
-    (qa, ka, va), (qb, kb, vb) = fa, fb
-    B, N, D = _check_features((qa, ka, va, qb, kb, vb), heads,
-                              ka.shape == qa.shape == va.shape and kb.shape == qb.shape == vb.shape and qa.shape[1:] == qb.shape[1:],
-                              ("q,k,v of both sets must share dtype float32, bfloat16 or float16",
-                               "features must be [n][B][N][H*D], one geometry for both sets", "features must be contiguous"))
+    (qa, ka, va, qb, kb, vb), B, N, D = _check_two_sets(fa, fb, heads)
     n_a, n_b = qa.shape[0], qb.shape[0]
-    for name, m, n in (("mask_a", mask_a, n_a), ("mask_b", mask_b, n_b)):
-        if m.dtype not in (torch.bool, torch.uint8):
-            raise _lib.DsimError(f"the region mask {name} must be bool or uint8")
-        if tuple(m.shape) != (n, N):
-            raise _lib.DsimError(f"the region mask {name} must be (n, N) = ({n}, {N}): {tuple(m.shape)}")
+    _check_region_mask(mask_a, n_a, N, "the region mask mask_a", "n")
+    _check_region_mask(mask_b, n_b, N, "the region mask mask_b", "n")
     _require_cuda(qa, ka, va, qb, kb, vb, mask_a, mask_b)          # (after the shape checks: those need no device)
     mask_a, mask_b = mask_a.view(torch.uint8), mask_b.view(torch.uint8)
     out = torch.empty((n_a, n_b), dtype=torch.float32, device=qa.device)
@@ -796,7 +808,7 @@ def score_matrix_regions(fa, fb, mask_a: torch.Tensor, mask_b: torch.Tensor, hea
                f"no region score matrix for n_a={n_a} n_b={n_b} B={B} H={heads} N={N} D={D}", qa.data_ptr(), ka.data_ptr(), va.data_ptr(),
                mask_a.data_ptr(), n_a, qb.data_ptr(), kb.data_ptr(), vb.data_ptr(), mask_b.data_ptr(), n_b, B, heads, N, D,
                _TORCH2DSIM[qa.dtype], sim, out.data_ptr(), _ptr(status), _ptr(counts))
-    return out if not (return_status or return_counts) else (out,) + ((status,) if return_status else ()) + ((counts,) if return_counts else ())
+    return _with_extras(out, status, counts)
 
 
 # ---- single-operator entry points (kernel-level parity tests) -----------------------------------
