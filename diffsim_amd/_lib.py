@@ -199,7 +199,21 @@ SYMBOLS = {
     "dsim_op_attention_ex": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(AttnLaunchC), _vp]),
     "dsim_attention_plan": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_i)]),
     "dsim_op_softmax_rows": (_i, [_vp, _vp, _i, _i, _f, _i, _vp]),
+    "dsim_op_conv_in": (_i, [_vp, _vp, _f, _f, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, C.POINTER(_i), _vp]),
+    "dsim_op_timestep_sincos": (_i, [_vp, _i, _i, _vp]),
+    "dsim_op_sincos_values": (_i, [_vp, _i, _vp, _i, _vp]),
+    "dsim_op_gemv_f32": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp]),
+    "dsim_op_pack": (_i, [_i, _vp, _i, _vp, _i, _i, _i, _i, _vp]),
+    "dsim_op_dup_batch": (_i, [_vp, _vp, _i, _sz, _vp]),
+    "dsim_op_resize_nearest": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _sz, _vp]),
+    "dsim_op_gather_ctx": (_i, [_vp, _i, _vp, _vp, _i, _i, _sz, _vp]),
+    "dsim_op_patch_embed": (_i, [_vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "dsim_op_fold_quant": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "dsim_op_to_nchw_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
 }
+
+CONV_IN_KERNELS = (None, "generic", "eight", "rows")      # dsim_conv_in_kernel, by value (0: the executors' choice, as `force`)
+PACK_KINDS = ("linear", "conv3", "conv_in", "vector")    # dsim_pack_kind, by value
 
 _lib = None
 

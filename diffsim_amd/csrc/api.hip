@@ -467,4 +467,108 @@ int dsim_op_softmax_rows(const void* x, void* out, int rows, int cols, float sca
     return DSIM_OK;
 }
 
+// ---- the input, embedding and weight-packing kernels, one operator each (pack.hip, and the shared launch functions of dit.hip / vae.hip) ----
+static bool is_dtype(int dt) { return dt == DSIM_F32 || dt == DSIM_BF16 || dt == DSIM_F16; }
+static int synced(int st, hipStream_t s) {
+    if (st != DSIM_OK) return st;
+    DSIM_HIP_CHECK(hipStreamSynchronize(s));
+    return DSIM_OK;
+}
+
+int dsim_op_conv_in(const float* lat, const float* noise, float sa, float sb, const float* w, const float* bias, void* out, int dtype,
+                    int n_img, int Cin, int S, int Cout, int dup, float* gn_part, int force, int* kernel, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (!lat || !w || !bias || !out || !is_dtype(dtype)) return DSIM_ERR_INVALID;
+    if (n_img < 1 || n_img > 65535 || Cin < 1 || S < 1 || S > 32768 || Cout < 1 || (dup != 1 && dup != 2)) return DSIM_ERR_INVALID;
+    if (force < 0 || force > CONV_IN_ROWS) return DSIM_ERR_INVALID;
+    // the walks' choice: the VAE's row kernel where it applies (no noising, one copy), else prep_conv_in()'s
+    const bool rows_ok = conv_in_rows_applies(Cin, S, Cout) && !noise && dup == 1;
+    const int kind = force ? force : (rows_ok ? (int)CONV_IN_ROWS : prep_conv_in_kind(Cin, Cout));
+    if (kind == CONV_IN_ROWS ? !rows_ok : (gn_part || !prep_conv_in_kind_applies(kind, Cin, Cout))) return DSIM_ERR_INVALID;
+    if (kind != CONV_IN_GENERIC && (uintptr_t)bias % 16) return DSIM_ERR_INVALID;       // (read as float4)
+    Tmp t;
+    float* wp = (float*)t.get((size_t)9 * Cin * Cout * 4);
+    if (!wp) return DSIM_ERR_HIP;
+    CK(pack_conv_in(w, DSIM_F32, wp, Cout, Cin, s));
+    CK(synced(kind == CONV_IN_ROWS ? conv_in_rows(lat, wp, bias, out, dtype, n_img, S, gn_part, s)
+                                   : prep_conv_in_as(kind, lat, noise, sa, sb, wp, bias, out, dtype, n_img, Cin, S, Cout, dup, s), s));
+    if (kernel) *kernel = kind;
+    return DSIM_OK;
+}
+
+int dsim_op_timestep_sincos(float* out, int dim, int t, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (!out || dim < 2 || dim % 2) return DSIM_ERR_INVALID;
+    return synced(timestep_sincos(out, dim, t, s), s);
+}
+
+int dsim_op_sincos_values(float* out, int dim, const float* vals, int count, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (!out || !vals || dim < 2 || dim % 2 || count < 1 || (long)count * dim > 0x7fffffffL) return DSIM_ERR_INVALID;
+    return synced(sincos_values(out, dim, vals, count, s), s);
+}
+
+int dsim_op_gemv_f32(const void* W, int w_dtype, const void* bias, int b_dtype, const float* x, float* y, int N, int K, int act,
+                     void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (!W || !x || !y || N < 1 || K < 1 || !is_dtype(w_dtype) || (bias && !is_dtype(b_dtype)) || (act != 0 && act != 1)) return DSIM_ERR_INVALID;
+    return synced(gemv_f32(W, w_dtype, bias, b_dtype, x, y, N, K, act, s), s);
+}
+
+int dsim_op_pack(int kind, const void* src, int src_dtype, void* dst, int dst_dtype, int rows, int cols, int geglu, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (!src || !dst || !is_dtype(src_dtype) || !is_dtype(dst_dtype) || rows < 1 || cols < 1) return DSIM_ERR_INVALID;
+    const bool f32_only = kind == DSIM_PACK_CONV_IN || kind == DSIM_PACK_VECTOR, interleaves = kind == DSIM_PACK_LINEAR || kind == DSIM_PACK_VECTOR;
+    if ((f32_only && dst_dtype != DSIM_F32) || (!interleaves && geglu)) return DSIM_ERR_INVALID;
+    if (geglu && ((geglu != 16 && geglu != 32) || rows % (2 * geglu))) return DSIM_ERR_INVALID;
+    switch (kind) {
+        case DSIM_PACK_LINEAR: return synced(pack_linear(src, src_dtype, dst, dst_dtype, rows, cols, geglu, s), s);
+        case DSIM_PACK_CONV3: return synced(pack_conv3(src, src_dtype, dst, dst_dtype, rows, cols, s), s);
+        case DSIM_PACK_CONV_IN: return synced(pack_conv_in(src, src_dtype, (float*)dst, rows, cols, s), s);
+        case DSIM_PACK_VECTOR: return cols != 1 ? DSIM_ERR_INVALID : synced(pack_vector(src, src_dtype, (float*)dst, rows, geglu, s), s);
+    }
+    return DSIM_ERR_INVALID;
+}
+
+int dsim_op_dup_batch(const void* in, void* out, int n_batch, size_t bytes_per_elem, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (!in || !out || n_batch < 1 || !bytes_per_elem) return DSIM_ERR_INVALID;
+    return synced(dup_batch(in, out, n_batch, bytes_per_elem, s), s);
+}
+
+int dsim_op_resize_nearest(const void* in, void* out, int B, int Hin, int Win, int Hout, int Wout, size_t row_bytes, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (!in || !out || !row_bytes) return DSIM_ERR_INVALID;
+    return synced(resize_nearest(in, out, B, Hin, Win, Hout, Wout, row_bytes, s), s);
+}
+
+int dsim_op_gather_ctx(const float* ctx, int n_ctx, const int32_t* index, void* dst, int dtype, int n_images, size_t per, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (!is_dtype(dtype)) return DSIM_ERR_INVALID;
+    return synced(gather_ctx(ctx, n_ctx, index, dst, dtype, n_images, per, s), s);
+}
+
+int dsim_op_patch_embed(const float* lat, const float* noise, float sa, float sb, const float* w, const float* bias, const float* pos,
+                        void* out, int dtype, int n_img, int Cin, int S, int p, int D, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    // (the kernel always noises: both lat and noise are read)
+    if (!lat || !noise || !w || !bias || !pos || !out || !is_dtype(dtype)) return DSIM_ERR_INVALID;
+    if (n_img < 1 || n_img > 65535 || Cin < 1 || p < 1 || S < p || S > 4096 || S % p || D < 1) return DSIM_ERR_INVALID;
+    if ((size_t)Cin * p * p * 8 * sizeof(float) > 48 * 1024) return DSIM_ERR_INVALID;            // its staging buffer: 8 tokens x K
+    return synced(patch_embed(lat, noise, sa, sb, w, bias, pos, out, dtype, n_img, Cin, S, p, D, s), s);
+}
+
+int dsim_op_fold_quant(const float* wq, const void* wco, const float* bco, const float* bq, void* out_w, float* out_b, int Cm, int K,
+                       int dtype, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (!wq || (!out_w && !out_b) || (out_w && !wco) || (out_b && (!bco || !bq)) || !is_dtype(dtype)) return DSIM_ERR_INVALID;
+    return synced(fold_quant(wq, wco, bco, bq, out_w, out_b, Cm, K, dtype, s), s);
+}
+
+int dsim_op_to_nchw_f32(const void* x, float* out, int n, int HW, int C, int dtype, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (!x || !out || n < 1 || HW < 1 || C < 1 || !is_dtype(dtype)) return DSIM_ERR_INVALID;
+    return synced(to_nchw_f32(x, out, n, HW, C, dtype, s), s);
+}
+
 }  // extern "C"

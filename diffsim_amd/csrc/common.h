@@ -238,6 +238,13 @@ int sincos_values(float* out, int dim, const float* vals /*device*/, int count, 
 int prep_conv_in(const float* lat, const float* noise /*nullable*/, float sa, float sb, const float* w /*[9*Cin][Cout]*/,
                  const float* bias, void* out, int dtype, int n_img, int Cin, int S, int Cout, int dup /*1|2*/,
                  hipStream_t st);
+// which direct kernel prep_conv_in launches, the one host decision: the eight-wide kernel where Cout % 8 == 0, Cout <= 2048 and its
+// staging buffer fits 48 KB, else the generic one.  prep_conv_in_as launches the named kind (DSIM_ERR_INVALID where it does not apply)
+enum { CONV_IN_GENERIC = 1, CONV_IN_EIGHT = 2, CONV_IN_ROWS = 3 };      // prep_conv_in_kernel, prep_conv_in8_kernel, conv_in_rows_kernel
+bool prep_conv_in_kind_applies(int kind, int Cin, int Cout);
+int prep_conv_in_kind(int Cin, int Cout);
+int prep_conv_in_as(int kind, const float* lat, const float* noise, float sa, float sb, const float* w, const float* bias, void* out,
+                    int dtype, int n_img, int Cin, int S, int Cout, int dup, hipStream_t st);
 // the VAE's 3 -> 128 conv_in at image resolution, one 64-pixel row segment per workgroup (bit-identical to prep_conv_in); gn_part
 // (16-bit dtypes only, nullable): the consumer's GroupNorm statistics in the conv epilogue's format (launch_groupnorm_pre)
 bool conv_in_rows_applies(int Cin, int S, int Cout);
@@ -253,6 +260,18 @@ int dup_batch(const void* in, void* out, int n_batch, size_t bytes_per_elem, hip
 // index = min(floor(dst * (float)in / out), in - 1) as F.interpolate(mode="nearest") computes it: the explicit-size
 // upsample of latent sides that are not a multiple of 2**levels (diffusers' forward_upsample_size)
 int resize_nearest(const void* in, void* out, int B, int Hin, int Win, int Hout, int Wout, size_t row_bytes, hipStream_t s);
+
+// DiT's patch embedding -- dit.hip: x_t = sa * lat + sb * noise (NCHW f32 [n_img][Cin][S][S]), the p x p patch projection with
+// w f32 [D][Cin p p], + bias + pos [T][D], written to both CFG halves out[(img * 2 + cfg)][T][D], T = (S / p)^2
+int patch_embed(const float* lat, const float* noise, float sa, float sb, const float* w, const float* bias, const float* pos, void* out,
+                int dtype, int n_img, int Cin, int S, int p, int D, hipStream_t s);
+// the VAE's quant_conv folded into conv_out -- vae.hip: out_w[Cm][K] = wq[Cm][Cm] wco[Cm][K] (wco / out_w in the compute dtype, wq f32),
+// out_b = wq bco + bq (f32; one workgroup of up to 1024 threads: Cm beyond that is DSIM_ERR_INVALID); either half may be left out
+// (out_w or out_b null)
+int fold_quant(const float* wq, const void* wco, const float* bco, const float* bq, void* out_w, float* out_b, int Cm, int K, int dtype,
+               hipStream_t s);
+// token-major [n][HW][C] in the compute dtype -> f32 NCHW [n][C][HW] -- vae.hip
+int to_nchw_f32(const void* x, float* out, int n, int HW, int C, int dtype, hipStream_t s);
 
 // row-resident Linear for K = 320 and 640: out[M][N] = P(x) W^T (+ bias), N % 64 == 0, N <= 3 C -- rowres.hip.  P: nothing, a
 // LayerNorm (ln_g, ln_b), or -- the GroupNorm form, gn = 1, N <= C -- the per-image channel affine of launch_groupnorm_stats' table

@@ -116,14 +116,8 @@ struct DWalk : WalkBase<dsim_dit> {
         WGET(pw, "x_embedder.proj.weight"); WGET(pb, "x_embedder.proj.bias"); WGET(pos, "pos_embed");
         void* x = alloc_act((size_t)M * D);
         CK(launch([&] {
-            return by_dtype(h->dt, [&](auto e) {
-                typedef typename decltype(e)::type T_;
-                const int K = c.in_channels * p * p;
-                hipLaunchKernelGGL(patch_embed_kernel<T_>, dim3((T + PE_TOK - 1) / PE_TOK, n), dim3(256), PE_TOK * K * sizeof(float), s, lat,
-                                   noise, sa, sb, (const float*)pw->p, (const float*)pb->p, (const float*)pos->p, (T_*)x, c.in_channels, S, p, D);
-                DSIM_HIP_CHECK(hipGetLastError());
-                return DSIM_OK;
-            });
+            return patch_embed(lat, noise, sa, sb, (const float*)pw->p, (const float*)pb->p, (const float*)pos->p, x, h->dt, n, c.in_channels, S,
+                               p, D, s);
         }));
         void* nb = alloc_act((size_t)M * D);
         void* big = alloc_act((size_t)M * (F > 3 * D ? F : 3 * D));
@@ -167,6 +161,20 @@ struct DWalk : WalkBase<dsim_dit> {
 };
 
 }  // namespace
+
+namespace dsim {
+int patch_embed(const float* lat, const float* noise, float sa, float sb, const float* w, const float* bias, const float* pos, void* out,
+                int dtype, int n_img, int Cin, int S, int p, int D, hipStream_t s) {
+    const int g = S / p, T = g * g, K = Cin * p * p;
+    return by_dtype(dtype, [&](auto e) {
+        typedef typename decltype(e)::type T_;
+        hipLaunchKernelGGL(patch_embed_kernel<T_>, dim3((T + PE_TOK - 1) / PE_TOK, n_img), dim3(256), PE_TOK * K * sizeof(float), s, lat, noise,
+                           sa, sb, w, bias, pos, (T_*)out, Cin, S, p, D);
+        DSIM_HIP_CHECK(hipGetLastError());
+        return DSIM_OK;
+    });
+}
+}  // namespace dsim
 
 extern "C" {
 

@@ -436,21 +436,37 @@ int conv_in_rows(const float* images, const float* w, const float* bias, void* o
         return DSIM_OK;
     });
 }
-int prep_conv_in(const float* lat, const float* noise, float sa, float sb, const float* w, const float* bias, void* out,
-                 int dtype, int n_img, int Cin, int S, int Cout, int dup, hipStream_t st) {
-    if (Cout % 8 == 0 && Cout / 8 <= 256) {
-        constexpr int PP = 4;
-        const int PIX = (256 / (Cout / 8)) * PP;
+// the eight-wide kernel's pixels per workgroup and staging bytes (PP = 4 pixels per thread); 0 where Cout has no eight-wide form
+constexpr int PREP8_PP = 4;
+static size_t prep8_lds(int Cin, int Cout, int* pix) {
+    if (Cout < 8 || Cout % 8 || Cout / 8 > 256) return 0;
+    *pix = (256 / (Cout / 8)) * PREP8_PP;
+    return (size_t)*pix * 9 * Cin * sizeof(float);
+}
+bool prep_conv_in_kind_applies(int kind, int Cin, int Cout) {
+    if (Cin < 1 || Cout < 1) return false;
+    int pix = 0;
+    const size_t lds8 = prep8_lds(Cin, Cout, &pix);
+    if (kind == CONV_IN_EIGHT) return lds8 > 0 && lds8 <= 48 * 1024;
+    return kind == CONV_IN_GENERIC && (size_t)PREP_PIX * 9 * Cin * sizeof(float) <= 64 * 1024;      // (a workgroup's whole LDS)
+}
+int prep_conv_in_kind(int Cin, int Cout) {
+    return prep_conv_in_kind_applies(CONV_IN_EIGHT, Cin, Cout) ? CONV_IN_EIGHT : CONV_IN_GENERIC;
+}
+int prep_conv_in_as(int kind, const float* lat, const float* noise, float sa, float sb, const float* w, const float* bias, void* out,
+                    int dtype, int n_img, int Cin, int S, int Cout, int dup, hipStream_t st) {
+    if (!prep_conv_in_kind_applies(kind, Cin, Cout)) return DSIM_ERR_INVALID;
+    if (kind == CONV_IN_EIGHT) {
+        int PIX = 0;
+        const size_t lds8 = prep8_lds(Cin, Cout, &PIX);
         const dim3 grid8((S * S + PIX - 1) / PIX, n_img);
-        const size_t lds8 = (size_t)PIX * 9 * Cin * sizeof(float);
-        if (lds8 <= 48 * 1024)
-            return by_dtype(dtype, [&](auto e) {
-                typedef typename decltype(e)::type T;
-                hipLaunchKernelGGL((prep_conv_in8_kernel<T, PP>), grid8, dim3(256), lds8, st, lat, noise, sa, sb, w, bias, (T*)out, Cin, S, Cout,
-                                   dup);
-                DSIM_HIP_CHECK(hipGetLastError());
-                return DSIM_OK;
-            });
+        return by_dtype(dtype, [&](auto e) {
+            typedef typename decltype(e)::type T;
+            hipLaunchKernelGGL((prep_conv_in8_kernel<T, PREP8_PP>), grid8, dim3(256), lds8, st, lat, noise, sa, sb, w, bias, (T*)out, Cin, S,
+                               Cout, dup);
+            DSIM_HIP_CHECK(hipGetLastError());
+            return DSIM_OK;
+        });
     }
     const dim3 grid((S * S + PREP_PIX - 1) / PREP_PIX, n_img), block(256);
     const size_t lds = (size_t)PREP_PIX * 9 * Cin * sizeof(float);
@@ -460,6 +476,10 @@ int prep_conv_in(const float* lat, const float* noise, float sa, float sb, const
         DSIM_HIP_CHECK(hipGetLastError());
         return DSIM_OK;
     });
+}
+int prep_conv_in(const float* lat, const float* noise, float sa, float sb, const float* w, const float* bias, void* out,
+                 int dtype, int n_img, int Cin, int S, int Cout, int dup, hipStream_t st) {
+    return prep_conv_in_as(prep_conv_in_kind(Cin, Cout), lat, noise, sa, sb, w, bias, out, dtype, n_img, Cin, S, Cout, dup, st);
 }
 // out[(b * 2 + c)][i] = in[b][i] for c in {0, 1}: one batch element of `per` 16-byte chunks becomes its two CFG copies
 __global__ void dup_batch_kernel(const u32x4* __restrict__ in, u32x4* __restrict__ out, size_t per, size_t total) {

@@ -245,21 +245,41 @@ struct VWalk : WalkBase<dsim_vae> {
         CK(gn(x, nw, nb, t.p, 1));
         const Act mo = act(n, x.H, x.W, Cm);
         CK(conv3(t, cow, (const float*)cob->p, nullptr, mo.p, Cm, 1, 1));
-        CK(launch([&] {
-            return by_dtype(h->dt, [&](auto e) {
-                typedef typename decltype(e)::type T;
-                const size_t total = (size_t)mo.rows() * Cm;
-                hipLaunchKernelGGL(to_nchw_f32_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const T*)mo.p, moments,
-                                   x.H * x.W, Cm, total);
-                DSIM_HIP_CHECK(hipGetLastError());
-                return DSIM_OK;
-            });
-        }));
+        CK(launch([&] { return to_nchw_f32(mo.p, moments, n, x.H * x.W, Cm, h->dt, s); }));
         return DSIM_OK;
     }
 };
 
 }  // namespace
+
+namespace dsim {
+int to_nchw_f32(const void* x, float* out, int n, int HW, int C, int dtype, hipStream_t s) {
+    return by_dtype(dtype, [&](auto e) {
+        typedef typename decltype(e)::type T;
+        const size_t total = (size_t)n * HW * C;
+        hipLaunchKernelGGL(to_nchw_f32_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const T*)x, out, HW, C, total);
+        DSIM_HIP_CHECK(hipGetLastError());
+        return DSIM_OK;
+    });
+}
+int fold_quant(const float* wq, const void* wco, const float* bco, const float* bq, void* out_w, float* out_b, int Cm, int K, int dtype,
+               hipStream_t s) {
+    // the bias kernel is one workgroup with a thread per output row: sized from Cm (it was 64 threads whatever Cm, rows past 64 unwritten)
+    if (Cm < 1 || Cm > 65535 || K < 1 || (out_b && Cm > 1024)) return DSIM_ERR_INVALID;
+    if (out_w)
+        CK(by_dtype(dtype, [&](auto e) {
+            typedef typename decltype(e)::type T;
+            hipLaunchKernelGGL(fold_quant_kernel<T>, dim3((K + 255) / 256, Cm), dim3(256), 0, s, wq, (const T*)wco, (T*)out_w, Cm, K);
+            DSIM_HIP_CHECK(hipGetLastError());
+            return DSIM_OK;
+        }));
+    if (out_b) {
+        hipLaunchKernelGGL(fold_quant_bias_kernel, dim3(1), dim3((Cm + 63) / 64 * 64), 0, s, wq, bco, bq, out_b, Cm);
+        DSIM_HIP_CHECK(hipGetLastError());
+    }
+    return DSIM_OK;
+}
+}  // namespace dsim
 
 extern "C" {
 
@@ -298,14 +318,7 @@ int dsim_vae_finalize(dsim_vae* h, void* stream) {
     CK(h->dalloc((size_t)Cm * K * dtype_size(h->dt), &fw.p));
     CK(h->dalloc((size_t)Cm * 4, &fb.p));
     fb.rows = Cm; fb.cols = 1;
-    (void)by_dtype(h->dt, [&](auto e) {
-        typedef typename decltype(e)::type T;
-        hipLaunchKernelGGL(fold_quant_kernel<T>, dim3((K + 255) / 256, Cm), dim3(256), 0, s, wq32, (const T*)cow->p, (T*)fw.p, Cm, K);
-        return DSIM_OK;
-    });
-    hipLaunchKernelGGL(fold_quant_bias_kernel, dim3(1), dim3(64), 0, s, wq32, (const float*)cob->p, (const float*)qb->p,
-                       (float*)fb.p, Cm);
-    DSIM_HIP_CHECK(hipGetLastError());
+    CK(fold_quant(wq32, cow->p, (const float*)cob->p, (const float*)qb->p, fw.p, (float*)fb.p, Cm, K, h->dt, s));
     h->pk["encoder.conv_out_folded.weight"] = fw;
     h->pk["encoder.conv_out_folded.bias"] = fb;
     // the mid-block attention's to_v weight, VAE_VREP copies back to back: v^T = Wv x^T of a whole group of images is then ONE launch

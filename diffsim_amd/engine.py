@@ -1014,6 +1014,179 @@ def op_layernorm_mod(x, scale2, shift2, rows_per_batch, eps=1e-6, out=None):
     return out
 
 
+# ---- the kernels in front of the models (csrc/pack.hip, the patch embedding, the VAE's fold and transpose), one operator each.
+# `out`: None (a new tensor) or the tensor to write -- the tests hand in a view of a sentinel-filled buffer they own.
+def _out(out, shape, dtype, device):
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    _require_cuda(out)
+    if out.dtype != dtype or out.numel() != math.prod(shape):
+        raise _lib.DsimError(f"out must hold {tuple(shape)} elements of {dtype}")
+    return out
+
+
+def _f32(*named):
+    for t, nm in named:
+        if t is not None and t.dtype != torch.float32:
+            raise _lib.DsimError(f"{nm} must be float32")
+
+
+def op_conv_in(lat, noise, sa, sb, w, bias, dtype, dup=1, force=0, gn_part=None, out=None):
+    """Noising + CFG copies + conv_in (dsim_op_conv_in): lat / noise f32 [n][Cin][S][S] (noise None: no noising), w f32
+    [Cout][Cin][3][3], bias f32 [Cout] -> ([n * dup][S * S][Cout] in dtype, the kernel that ran: "generic" / "eight" / "rows").
+    force: 0 the executors' choice, or 1 / 2 / 3 = that kernel; gn_part: f32 [n][S * S / 64][Cout / 4][2] to fill (row kernel)."""
+    L = _lib.lib()
+    _require_cuda(lat, noise, w, bias, gn_part)
+    _f32((lat, "lat"), (noise, "noise"), (w, "w"), (bias, "bias"), (gn_part, "gn_part"))
+    n, Cin, S, S2 = lat.shape
+    Cout = w.shape[0]
+    if S != S2 or tuple(w.shape) != (Cout, Cin, 3, 3) or bias.numel() != Cout or (noise is not None and noise.shape != lat.shape):
+        raise _lib.DsimError("conv_in: lat / noise [n][Cin][S][S], w [Cout][Cin][3][3], bias [Cout]")
+    if gn_part is not None and (S * S % 64 or Cout % 4 or gn_part.numel() != n * (S * S // 64) * (Cout // 4) * 2):
+        raise _lib.DsimError("gn_part must be f32 [n][S * S / 64][Cout / 4][2]")
+    out = _out(out, (n * dup, S * S, Cout), dtype, lat.device)
+    kernel = C.c_int(0)
+    with torch.cuda.device(lat.device):
+        _lib.check(L.dsim_op_conv_in(lat.data_ptr(), _ptr(noise), float(sa), float(sb), w.data_ptr(), bias.data_ptr(), out.data_ptr(),
+                                     _TORCH2DSIM[dtype], n, Cin, S, Cout, int(dup), _ptr(gn_part), int(force), C.byref(kernel),
+                                     _stream_ptr()), "op_conv_in")
+    return out.view(n * dup, S * S, Cout), _lib.CONV_IN_KERNELS[kernel.value]
+
+
+def op_timestep_sincos(dim, t, out=None, device="cuda"):
+    """diffusers Timesteps(dim, flip_sin_to_cos=True, downscale_freq_shift=0) of the integer t -> f32 [dim] = [cos | sin]"""
+    out = _out(out, (dim,), torch.float32, device)
+    with torch.cuda.device(out.device):
+        _lib.check(_lib.lib().dsim_op_timestep_sincos(out.data_ptr(), int(dim), int(t), _stream_ptr()), "op_timestep_sincos")
+    return out
+
+
+def op_sincos_values(dim, vals, out=None):
+    """the same embedding of each of the f32 values vals [count] -> f32 [count][dim]"""
+    _require_cuda(vals)
+    _f32((vals, "vals"))
+    out = _out(out, (vals.numel(), dim), torch.float32, vals.device)
+    with torch.cuda.device(vals.device):
+        _lib.check(_lib.lib().dsim_op_sincos_values(out.data_ptr(), int(dim), vals.data_ptr(), vals.numel(), _stream_ptr()),
+                   "op_sincos_values")
+    return out.view(vals.numel(), dim)
+
+
+def op_gemv_f32(W, bias, x, act=0, out=None):
+    """y = W act(x) + bias in f32: W [N][K] in any of the three dtypes, bias None or [N] in any, x f32 [K]; act 1: SiLU on x"""
+    _require_cuda(W, bias, x)
+    _f32((x, "x"))
+    N, K = W.shape
+    if x.numel() != K or (bias is not None and bias.numel() != N):
+        raise _lib.DsimError("gemv: W [N][K], x [K], bias [N]")
+    out = _out(out, (N,), torch.float32, W.device)
+    with torch.cuda.device(W.device):
+        _lib.check(_lib.lib().dsim_op_gemv_f32(W.data_ptr(), _TORCH2DSIM[W.dtype], _ptr(bias), _TORCH2DSIM[bias.dtype] if bias is not None else 0,
+                                               x.data_ptr(), out.data_ptr(), N, K, int(act), _stream_ptr()), "op_gemv_f32")
+    return out
+
+
+def op_pack(kind, src, dst_dtype, geglu=0, out=None):
+    """One weight pack (dsim_op_pack): kind "linear" (src [N][K]), "conv3" / "conv_in" (src [Cout][Cin][3][3]), "vector" (src [N]);
+    src in any of the three dtypes -> the packed tensor in dst_dtype (conv_in [9 Cin][Cout] and vector: float32 only)."""
+    _require_cuda(src)
+    k = _lib.PACK_KINDS.index(kind)
+    rows, cols = src.shape[0], (src.shape[1] if src.ndim > 1 else 1)
+    if src.ndim != {"linear": 2, "conv3": 4, "conv_in": 4, "vector": 1}[kind] or (src.ndim == 4 and tuple(src.shape[2:]) != (3, 3)):
+        raise _lib.DsimError(f"pack {kind}: wrong source shape {tuple(src.shape)}")
+    shape = {"linear": (rows, cols), "conv3": (rows, 9, cols), "conv_in": (9 * cols, rows), "vector": (rows,)}[kind]
+    out = _out(out, shape, dst_dtype, src.device)
+    with torch.cuda.device(src.device):
+        _lib.check(_lib.lib().dsim_op_pack(k, src.data_ptr(), _TORCH2DSIM[src.dtype], out.data_ptr(), _TORCH2DSIM[dst_dtype], rows, cols,
+                                           int(geglu), _stream_ptr()), "op_pack")
+    return out.view(shape)
+
+
+def op_dup_batch(x, out=None):
+    """[n][...] -> [2 n][...]: every batch element twice in a row (an element's bytes must be a multiple of 16)"""
+    _require_cuda(x)
+    n = x.shape[0]
+    out = _out(out, (2 * n,) + tuple(x.shape[1:]), x.dtype, x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().dsim_op_dup_batch(x.data_ptr(), out.data_ptr(), n, x[0].numel() * x.element_size(), _stream_ptr()),
+                   "op_dup_batch")
+    return out.view((2 * n,) + tuple(x.shape[1:]))
+
+
+def op_resize_nearest(x, Hout, Wout, out=None):
+    """token-major nearest resize [B][Hin][Win][C] -> [B][Hout][Wout][C], F.interpolate(mode="nearest")'s indices (C's bytes % 16 == 0)"""
+    _require_cuda(x)
+    B, Hin, Win, Cc = x.shape
+    out = _out(out, (B, Hout, Wout, Cc), x.dtype, x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().dsim_op_resize_nearest(x.data_ptr(), out.data_ptr(), B, Hin, Win, int(Hout), int(Wout), Cc * x.element_size(),
+                                                     _stream_ptr()), "op_resize_nearest")
+    return out.view(B, Hout, Wout, Cc)
+
+
+def op_gather_ctx(ctx, index, dtype, out=None):
+    """ctx f32 [n_ctx][2][per...], index int32 [n_images] -> [2 n_images][per...] in dtype; row (2 i + cfg) = ctx[clamp(index[i])][cfg]"""
+    _require_cuda(ctx, index)
+    _f32((ctx, "ctx"))
+    if index.dtype != torch.int32 or ctx.ndim < 3 or ctx.shape[1] != 2:
+        raise _lib.DsimError("gather_ctx: ctx f32 [n_ctx][2][...], index int32 [n_images]")
+    n_ctx, n = ctx.shape[0], index.numel()
+    per = ctx[0, 0].numel()
+    shape = (2 * n,) + tuple(ctx.shape[2:])
+    out = _out(out, shape, dtype, ctx.device)
+    with torch.cuda.device(ctx.device):
+        _lib.check(_lib.lib().dsim_op_gather_ctx(ctx.data_ptr(), n_ctx, index.data_ptr(), out.data_ptr(), _TORCH2DSIM[dtype], n, per,
+                                                 _stream_ptr()), "op_gather_ctx")
+    return out.view(shape)
+
+
+def op_patch_embed(lat, noise, sa, sb, w, bias, pos, p, dtype, out=None):
+    """DiT's patch embedding of the noised latent: lat / noise f32 [n][Cin][S][S], w f32 [D][Cin][p][p], bias f32 [D], pos f32 [T][D]
+    -> [2 n][T][D] in dtype (both CFG halves), T = (S / p)^2"""
+    _require_cuda(lat, noise, w, bias, pos)
+    _f32((lat, "lat"), (noise, "noise"), (w, "w"), (bias, "bias"), (pos, "pos"))
+    n, Cin, S, S2 = lat.shape
+    D = w.shape[0]
+    T = (S // p) ** 2
+    if S != S2 or noise.shape != lat.shape or w.numel() != D * Cin * p * p or bias.numel() != D or pos.numel() != T * D:
+        raise _lib.DsimError("patch_embed: lat / noise [n][Cin][S][S], w [D][Cin][p][p], bias [D], pos [T][D]")
+    out = _out(out, (2 * n, T, D), dtype, lat.device)
+    with torch.cuda.device(lat.device):
+        _lib.check(_lib.lib().dsim_op_patch_embed(lat.data_ptr(), noise.data_ptr(), float(sa), float(sb), w.data_ptr(), bias.data_ptr(),
+                                                  pos.data_ptr(), out.data_ptr(), _TORCH2DSIM[dtype], n, Cin, S, int(p), D, _stream_ptr()),
+                   "op_patch_embed")
+    return out.view(2 * n, T, D)
+
+
+def op_fold_quant(wq, wco=None, bco=None, bq=None, out_w=None, out_b=None):
+    """The VAE's quant_conv folded into conv_out: wq f32 [Cm][Cm]; with wco [Cm][K] (compute dtype) the weight wq wco in that dtype,
+    with bco / bq f32 [Cm] the bias wq bco + bq in f32 -> (weight or None, bias or None)."""
+    _require_cuda(wq, wco, bco, bq)
+    _f32((wq, "wq"), (bco, "bco"), (bq, "bq"))
+    Cm = wq.shape[0]
+    if tuple(wq.shape) != (Cm, Cm) or (wco is not None and wco.shape[0] != Cm) or any(t is not None and t.numel() != Cm for t in (bco, bq)):
+        raise _lib.DsimError("fold_quant: wq [Cm][Cm], wco [Cm][K], bco / bq [Cm]")
+    K = wco.shape[1] if wco is not None else 1
+    dt = wco.dtype if wco is not None else torch.float32
+    ow = _out(out_w, (Cm, K), dt, wq.device) if wco is not None else None
+    ob = _out(out_b, (Cm,), torch.float32, wq.device) if bco is not None else None
+    with torch.cuda.device(wq.device):
+        _lib.check(_lib.lib().dsim_op_fold_quant(wq.data_ptr(), _ptr(wco), _ptr(bco), _ptr(bq), _ptr(ow), _ptr(ob), Cm, K, _TORCH2DSIM[dt],
+                                                 _stream_ptr()), "op_fold_quant")
+    return ow, ob
+
+
+def op_to_nchw_f32(x, out=None):
+    """token-major [n][HW][C] in any of the three dtypes -> f32 [n][C][HW]"""
+    _require_cuda(x)
+    n, HW, Cc = x.shape
+    out = _out(out, (n, Cc, HW), torch.float32, x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().dsim_op_to_nchw_f32(x.data_ptr(), out.data_ptr(), n, HW, Cc, _TORCH2DSIM[x.dtype], _stream_ptr()),
+                   "op_to_nchw_f32")
+    return out.view(n, Cc, HW)
+
+
 def groupnorm_plan(C0, C1, B, HW, groups, dtype, pre=False):
     """What op_groupnorm (op_groupnorm_pre with pre) launches for this shape: dict(form "onepass" / "twopass" / "pre", NS, UNR, CS,
     tpr, R, chunks, rb), from the function the launcher itself calls.  Host only; raises DsimError where the launch would refuse."""

@@ -646,6 +646,56 @@ int dsim_op_gemm(const dsim_gemm_op* op, dsim_gemm_launch* launched, void* strea
 int dsim_op_groupnorm_pre(const void* x, int C, const float* gamma, const float* beta, void* out, int B, int HW, int groups,
                           float eps, int silu, int dtype, const float* part32, int chunks, void* stream);
 
+/* ---- the kernels in front of the models, one operator each: noising + conv_in, the time-embedding primitives, the weight packs,
+ * the data movers, DiT's patch embedding, the VAE's quant_conv fold and its output transpose.  Each validates its arguments
+ * (DSIM_ERR_INVALID), launches on the stream, synchronises, and writes only into the caller's buffers.
+ *
+ * dsim_op_conv_in: x = sa * lat + sb * noise (noise NULL: x = lat; NCHW f32 [n_img][Cin][S][S]), then the 3x3 conv with zero padding:
+ *   out[(img * dup + d)][S * S][Cout] in dtype for d < dup (dup 1 | 2: the CFG copies).  w: diffusers-layout f32 [Cout][Cin][3][3],
+ *   bias f32 [Cout] (16-byte aligned for the eight-wide and row kernels).  force: 0 the executors' choice (the row kernel where it
+ *   applies -- Cin 3, Cout 128, S % 64 == 0, no noise, dup 1 --, else what the U-Net's launch picks), or a dsim_conv_in_kernel to run;
+ *   a forced kernel that does not apply is DSIM_ERR_INVALID.  gn_part (NULL, or f32 [n_img][S * S / 64][Cout / 4][2]: the row kernel in
+ *   the 16-bit dtypes only) receives the GroupNorm partial sums of the stored values, dsim_gemm_op.gn_part's layout.  *kernel (may be
+ *   NULL) receives the dsim_conv_in_kernel that ran. */
+typedef enum dsim_conv_in_kernel {
+    DSIM_CONV_IN_GENERIC = 1,                   /* prep_conv_in_kernel: one output channel per thread, 16 pixels per workgroup */
+    DSIM_CONV_IN_EIGHT = 2,                     /* prep_conv_in8_kernel: eight channels per thread; Cout % 8 == 0, Cout <= 2048, staging <= 48 KB */
+    DSIM_CONV_IN_ROWS = 3                       /* conv_in_rows_kernel: the VAE's 3 -> 128 conv at image resolution */
+} dsim_conv_in_kernel;
+int dsim_op_conv_in(const float* lat, const float* noise, float sa, float sb, const float* w, const float* bias, void* out, int dtype,
+                    int n_img, int Cin, int S, int Cout, int dup, float* gn_part, int force, int* kernel, void* stream);
+/* diffusers Timesteps(dim, flip_sin_to_cos = True, downscale_freq_shift = 0): out f32 [dim] = [cos | sin](t f_i), f_i =
+ * exp(-ln(10000) i / (dim / 2)); dim even.  dsim_op_sincos_values: the same for count f32 values on the device, out [count][dim]. */
+int dsim_op_timestep_sincos(float* out, int dim, int t, void* stream);
+int dsim_op_sincos_values(float* out, int dim, const float* vals, int count, void* stream);
+/* y[N] = W[N][K] act(x[K]) + bias[N] in f32: W in w_dtype, bias NULL or in b_dtype, x / y f32; act 0 identity, 1 SiLU on x. */
+int dsim_op_gemv_f32(const void* W, int w_dtype, const void* bias, int b_dtype, const float* x, float* y, int N, int K, int act,
+                     void* stream);
+/* One weight pack from a checkpoint dtype into an engine layout, each value rounded once to dst_dtype:
+ *   LINEAR  [rows = N][cols = K] -> [N][K], geglu 0, or 16 / 32 (N % (2 geglu) == 0): the [h ; g] rows interleaved in blocks
+ *   CONV3   [rows = Cout][cols = Cin][3][3] -> [Cout][tap][Cin]
+ *   CONV_IN [rows = Cout][cols = Cin][3][3] -> f32 [tap * Cin + ci][Cout]          (dst_dtype must be DSIM_F32)
+ *   VECTOR  [rows = N] (cols = 1) -> f32 [N], geglu as LINEAR                      (dst_dtype must be DSIM_F32) */
+typedef enum dsim_pack_kind { DSIM_PACK_LINEAR = 0, DSIM_PACK_CONV3 = 1, DSIM_PACK_CONV_IN = 2, DSIM_PACK_VECTOR = 3 } dsim_pack_kind;
+int dsim_op_pack(int kind, const void* src, int src_dtype, void* dst, int dst_dtype, int rows, int cols, int geglu, void* stream);
+/* out[2 b], out[2 b + 1] = in[b] for b < n_batch, elements of bytes_per_elem bytes (% 16 == 0) */
+int dsim_op_dup_batch(const void* in, void* out, int n_batch, size_t bytes_per_elem, void* stream);
+/* token-major nearest resize [B][Hin][Win][row_bytes] -> [B][Hout][Wout][row_bytes] as F.interpolate(mode = "nearest"); row_bytes % 16 == 0 */
+int dsim_op_resize_nearest(const void* in, void* out, int B, int Hin, int Win, int Hout, int Wout, size_t row_bytes, void* stream);
+/* dst[(2 img + cfg)][per] = ctx[clamp(index[img], 0, n_ctx - 1)][cfg][per] in dtype; ctx f32 [n_ctx][2][per], index int32 [n_images] */
+int dsim_op_gather_ctx(const float* ctx, int n_ctx, const int32_t* index, void* dst, int dtype, int n_images, size_t per, void* stream);
+/* DiT's x_embedder + pos_embed on the noised latent: out[(img * 2 + cfg)][T][D] in dtype, T = (S / p)^2, token (ty, tx) =
+ * sum_k w[d][k] x[c][ty p + py][tx p + px] + bias[d] + pos[T][D], k = (c p + py) p + px; w f32 [D][Cin p p]; noise is required. */
+int dsim_op_patch_embed(const float* lat, const float* noise, float sa, float sb, const float* w, const float* bias, const float* pos,
+                        void* out, int dtype, int n_img, int Cin, int S, int p, int D, void* stream);
+/* The VAE's quant_conv folded into conv_out: out_w[Cm][K] = wq wco in dtype (wq f32 [Cm][Cm], wco [Cm][K] in dtype), out_b[Cm] =
+ * wq bco + bq in f32.  Either output may be NULL.  The bias launch is one workgroup sized from Cm: Cm > 1024 with out_b is
+ * DSIM_ERR_INVALID. */
+int dsim_op_fold_quant(const float* wq, const void* wco, const float* bco, const float* bq, void* out_w, float* out_b, int Cm, int K,
+                       int dtype, void* stream);
+/* token-major [n][HW][C] in dtype -> f32 NCHW [n][C][HW] */
+int dsim_op_to_nchw_f32(const void* x, float* out, int n, int HW, int C, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
