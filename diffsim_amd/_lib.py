@@ -104,6 +104,15 @@ class DiTCfgC(C.Structure):
                                           "mlp_ratio", "num_classes", "freq_dim", "compute_dtype", "tap_layer")]
 
 
+class ViTCfgC(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("image_size", "patch_size", "hidden_size", "depth", "num_heads", "mlp_dim", "act", "pre_norm",
+                                           "patch_bias", "layer_scale", "tap_input")] +
+                [("ln_eps", C.c_float), ("compute_dtype", C.c_int32), ("tap_layer", C.c_int32)])
+
+
+VIT_ACT = {"gelu": 0, "quick_gelu": 1}          # DSIM_VIT_ACT_*
+VIT_TAP_INPUT = {"norm1": 0, "block": 1}        # dsim_vit_cfg.tap_input
+
 # every symbol include/diffsim_amd.h declares: (restype, argtypes)
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 ABI_VERSION = 7          # include/diffsim_amd.h DSIM_ABI_VERSION (tests/test_host.py checks the header against it)
@@ -163,6 +172,20 @@ SYMBOLS = {
     "dsim_dit_taps_workspace_bytes": (_sz, [_vp, _i, _i, C.POINTER(_i)]),
     "dsim_dit_qkv_taps": (_i, [_vp, _vp, _vp, _f, _f, _i, _i, C.POINTER(_i), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _vp,
                                _sz, _vp]),
+    "dsim_vit_create": (_i, [C.POINTER(ViTCfgC), C.POINTER(_vp)]),
+    "dsim_vit_destroy": (None, [_vp]),
+    "dsim_vit_load_weight": (_i, [_vp, C.c_char_p, _vp, _i, C.POINTER(C.c_int64), _i]),
+    "dsim_vit_finalize": (_i, [_vp, _vp]),
+    "dsim_vit_set_tap": (_i, [_vp, _i]),
+    "dsim_vit_profile": (_i, [_vp, _i]),
+    "dsim_vit_profile_count": (_i, [_vp]),
+    "dsim_vit_profile_get": (_i, [_vp, _i, C.c_char_p, _i, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "dsim_vit_workspace_bytes": (_sz, [_vp, _i]),
+    "dsim_vit_qkv": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dsim_vit_taps_workspace_bytes": (_sz, [_vp, _i, _i, C.POINTER(_i)]),
+    "dsim_vit_qkv_taps": (_i, [_vp, _vp, _i, _i, C.POINTER(_i), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _vp, _sz, _vp]),
+    "dsim_pair_score_proj_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "dsim_pair_score_proj": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dsim_pair_score_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "dsim_pair_score": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "dsim_pair_score_status": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),

@@ -1,6 +1,6 @@
 """Command-line driver: the reference's benchmark loops on the MI355X engine.
 
-``python -m diffsim_amd --dataset cute|nights|sref --metric diffsim|diffsim_xl|dit --model_path <dir> --image_path <dir> ...``
+``python -m diffsim_amd --dataset cute|nights|sref --metric diffsim|diffsim_xl|dit|clip_cross|dino_cross --model_path <dir> --image_path <dir> ...``
 
 Flags of the reference drivers (``/root/reference/argprocess.py:5-18``) keep their names, meaning and defaults;
 ``--dataset`` selects which of the reference's loops runs (``cute_main.py:48-226``, ``night_main.py:24-173`` or
@@ -20,7 +20,8 @@ from typing import List, Optional, Tuple
 
 METRICS = ["diffsim", "diffsim_xl", "clip_i", "clip_cross", "dino", "dinov1", "dino_cross", "cute", "lpips", "gram",
            "diffeats", "clipfeats", "dinofeats", "ensemble", "dit"]
-ENGINE_METRICS = ("diffsim", "diffsim_xl", "dit")
+ENGINE_METRICS = ("diffsim", "diffsim_xl", "dit", "clip_cross", "dino_cross")
+VIT_METRICS = ("clip_cross", "dino_cross")      # DiffSim's method on a ViT tower (vit.py): no VAE, no noise, no prompt, no token grid
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -59,7 +60,7 @@ def build_parser() -> argparse.ArgumentParser:
                    help="--dataset cute|nights|sref: score every tap from one forward per image batch instead of the one "
                         "--target_block / --target_layer tap (which it overrides), and print one section per tap, in the given "
                         "order, as a one-tap run prints it.  SPEC: diffsim up_blocks:0, down_blocks:2, mid_blocks:0; diffsim_xl "
-                        "up_blocks:0,1,9 (block, attention, transformer block), mid_blocks:0,5; dit blocks:13.  Layers are "
+                        "up_blocks:0,1,9 (block, attention, transformer block), mid_blocks:0,5; dit blocks:13; clip_cross / dino_cross layers:5.  Layers are "
                         "explicit (no coercion of a single value to 0).  `all`: every tap the model can name")
     p.add_argument("--mask_path", type=str, default=None, metavar="DIR",
                    help="--dataset cute|nights: score the masked part of each image (region scores).  The mask of "
@@ -145,6 +146,18 @@ def arg_parse(argv=None):
         if not (args.text_threshold >= 0.0) or args.text_threshold == float("inf"):
             p.error("--text_threshold must be finite and >= 0")
         args.use_text_attn = True
+    if args.metric in VIT_METRICS:
+        for flag, on in (("--mask_path", args.mask_path is not None), ("--query_mask_path", args.query_mask_path is not None),
+                         ("--gallery_mask_path", args.gallery_mask_path is not None), ("--text_attn", args.text_attn is not None),
+                         ("--save_maps", args.save_maps), ("--save_matches", args.save_matches)):
+            if on:
+                p.error(f"{flag}: --metric {args.metric} has no regions, maps or alignments (its tokens are a class token and a "
+                        "patch grid: the class token is not on the grid)")
+        if args.fp8_attention:
+            p.error(f"--fp8_attention: --metric {args.metric} has no fp8 attention (--metric dit only)")
+        if args.metric == "clip_cross" and args.dataset == "retrieval":
+            p.error("--metric clip_cross --dataset retrieval: clip_cross applies the layer's out_proj in its score tail and there is "
+                    "no projected score matrix yet; --metric dino_cross ranks with the plain score matrix")
     if args.save_maps and args.dataset != "retrieval":
         p.error("--save_maps writes the maps of the retrieval rankings: it needs --dataset retrieval")
     if args.save_matches and args.dataset != "retrieval":
@@ -229,14 +242,17 @@ def build_scorer(args):
     import torch
     from . import loader
     if args.metric not in ENGINE_METRICS:
-        raise SystemExit(f"--metric {args.metric}: only the DiffSim metrics (diffsim, diffsim_xl, dit) run on this engine; the "
-                         f"competitor metrics of the reference are out of scope")
+        raise SystemExit(f"--metric {args.metric}: only the DiffSim metrics (diffsim, diffsim_xl, dit, clip_cross, dino_cross) run on "
+                         f"this engine; the competitor metrics of the reference are out of scope")
     if args.ip_adapter:
         raise SystemExit("--ip_adapter: IP-Adapter mode is out of scope of this build")
     if not args.model_path:
         raise SystemExit("--model_path is required (no checkpoint is bundled)")
     nd = torch.float16 if args.noise_dtype == "fp16" else torch.float32
     dev = "cuda:%d" % int(os.environ.get("LOCAL_RANK", "0"))
+    if args.metric in VIT_METRICS:
+        print(f"--metric {args.metric}: --image_size is not consulted (the model's image processor decides: resize, then a centre crop)")
+        return (loader.load_clip_cross if args.metric == "clip_cross" else loader.load_dino_cross)(args.model_path, args.dtype, dev)
     if args.metric == "diffsim":
         return loader.load_diffsim(args.model_path, args.dtype, dev, nd, dedup_cfg=args.dedup_cfg)
     if args.metric == "diffsim_xl":
@@ -286,7 +302,8 @@ def cli_taps(args, scorer):
     """--taps -> the scorer's taps (``all``: every tap of the scorer's model; the default model of --metric without a scorer)."""
     from . import config as C
     from .sweep import parse_tap_specs
-    cfg = getattr(scorer, "cfg", None) or {"diffsim": C.SD15, "diffsim_xl": C.SDXL, "dit": C.DIT_XL2}[args.metric]
+    cfg = getattr(scorer, "cfg", None) or {"diffsim": C.SD15, "diffsim_xl": C.SDXL, "dit": C.DIT_XL2, "clip_cross": C.CLIP_B32,
+                                           "dino_cross": C.DINOV2_S14}[args.metric]
     try:
         return parse_tap_specs(args.taps, args.metric, cfg)
     except ValueError as e:

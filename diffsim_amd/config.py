@@ -284,3 +284,86 @@ def dit_param_shapes(cfg: DiTConfig) -> Dict[str, Tuple[int, ...]]:
         out[b + "adaLN_modulation.1.weight"] = (6 * d, d)
         out[b + "adaLN_modulation.1.bias"] = (6 * d,)
     return out
+
+
+@dataclass(frozen=True)
+class ViTConfig:
+    """A ViT image tower as the reference's clip_cross / dino_cross metrics run it (metrics/clip_i.py, metrics/dino.py): HF
+    CLIPVisionModel (pre_layrnorm, quick-GELU, no patch bias, hook on the encoder layer) or Dinov2Model (LayerScale, erf-GELU, patch
+    bias, interpolated positions, hook on attention.attention)."""
+    kind: str = "clip"              # "clip" | "dinov2"
+    image_size: int = 224           # side of the processor's crop (CLIP: the only side the position table serves)
+    patch_size: int = 32
+    hidden_size: int = 768
+    depth: int = 12
+    num_heads: int = 12
+    mlp_dim: int = 3072
+    pos_grid: int = 7               # side of the stored patch position grid (DINOv2: 518 / 14 = 37, interpolated to the input's)
+    ln_eps: float = 1e-5
+
+    @property
+    def act(self) -> str:
+        return "quick_gelu" if self.kind == "clip" else "gelu"
+
+    @property
+    def pre_norm(self) -> bool:
+        return self.kind == "clip"
+
+    @property
+    def patch_bias(self) -> bool:
+        return self.kind == "dinov2"
+
+    @property
+    def layer_scale(self) -> bool:
+        return self.kind == "dinov2"
+
+    @property
+    def tap_input(self) -> str:
+        """What the reference's hook projects: the encoder layer's raw input (CLIP) or norm1's output (DINOv2)."""
+        return "block" if self.kind == "clip" else "norm1"
+
+    def tokens(self, side: int) -> int:
+        return 1 + (side // self.patch_size) ** 2
+
+
+CLIP_B32 = ViTConfig()
+CLIP_B16 = ViTConfig(patch_size=16, pos_grid=14)
+CLIP_L14 = ViTConfig(patch_size=14, hidden_size=1024, depth=24, num_heads=16, mlp_dim=4096, pos_grid=16)
+DINOV2_S14 = ViTConfig("dinov2", 224, 14, 384, 12, 6, 1536, 37, 1e-6)
+DINOV2_B14 = ViTConfig("dinov2", 224, 14, 768, 12, 12, 3072, 37, 1e-6)
+VIT_TINY_CLIP = ViTConfig("clip", 40, 8, 128, 3, 2, 256, 5, 1e-5)
+VIT_TINY_DINO = ViTConfig("dinov2", 40, 8, 128, 3, 2, 512, 5, 1e-6)
+
+
+def vit_param_shapes(cfg: ViTConfig) -> Dict[str, Tuple[int, ...]]:
+    """Parameters of a ViT tower under the engine's neutral keys (include/diffsim_amd.h; vit.neutral_state_dict maps the HF keys onto
+    them), in forward order; the position table at its stored grid."""
+    d, p = cfg.hidden_size, cfg.patch_size
+    out: Dict[str, Tuple[int, ...]] = {}
+    out["cls_token"] = (d,)
+    out["pos_embed"] = (1 + cfg.pos_grid ** 2, d)
+    out["x_embedder.proj.weight"] = (d, 3, p, p)
+    if cfg.patch_bias:
+        out["x_embedder.proj.bias"] = (d,)
+    if cfg.pre_norm:
+        out["pre_norm.weight"] = (d,)
+        out["pre_norm.bias"] = (d,)
+    for i in range(cfg.depth):
+        b = f"blocks.{i}."
+        out[b + "norm1.weight"] = (d,)
+        out[b + "norm1.bias"] = (d,)
+        out[b + "attn.qkv.weight"] = (3 * d, d)
+        out[b + "attn.qkv.bias"] = (3 * d,)
+        out[b + "attn.proj.weight"] = (d, d)
+        out[b + "attn.proj.bias"] = (d,)
+        if cfg.layer_scale:
+            out[b + "ls1"] = (d,)
+        out[b + "norm2.weight"] = (d,)
+        out[b + "norm2.bias"] = (d,)
+        out[b + "mlp.fc1.weight"] = (cfg.mlp_dim, d)
+        out[b + "mlp.fc1.bias"] = (cfg.mlp_dim,)
+        out[b + "mlp.fc2.weight"] = (d, cfg.mlp_dim)
+        out[b + "mlp.fc2.bias"] = (d,)
+        if cfg.layer_scale:
+            out[b + "ls2"] = (d,)
+    return out

@@ -620,6 +620,28 @@ def pair_score(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, idx_a: torch.T
     return (out, status) if return_status else out
 
 
+def pair_score_proj(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, idx_a: torch.Tensor, idx_b: torch.Tensor, heads: int,
+                    similarity: str = "cosine", return_status: bool = False, *, w_out: torch.Tensor, bias: torch.Tensor):
+    """The projected score tail (metrics/clip_i.py:143-159, dsim_pair_score_proj): pair_score with the hooked layer's out_proj
+    applied to every attention output before the cosine / mse.  q, k, v, idx, heads, similarity, return_status: as pair_score.
+    w_out: contiguous [C][C] in the features' dtype, C = H*D, rows = output features; bias: contiguous f32 [C]."""
+    _require_cuda(q, k, v, idx_a, idx_b, w_out, bias)
+    sim = _similarity_code(similarity)
+    B, N, D = _check_features((q, k, v), heads, k.shape == q.shape == v.shape, _PAIR_MSGS, (idx_a, idx_b))
+    Cc = heads * D
+    if w_out.dtype != q.dtype or tuple(w_out.shape) != (Cc, Cc) or bias.dtype != torch.float32 or tuple(bias.shape) != (Cc,):
+        raise _lib.DsimError(f"w_out must be {q.dtype} ({Cc}, {Cc}) and bias float32 ({Cc},)")
+    n_pairs = idx_a.numel()
+    out = torch.empty(n_pairs, dtype=torch.float32, device=q.device)
+    status = _i32(n_pairs, q.device, return_status)
+    dt = _TORCH2DSIM[q.dtype]
+    _tail_call(q.device, "pair_score_proj", (n_pairs, B, heads, N, D, dt),
+               f"the projected score tail does not serve n_pairs {n_pairs}, B {B}, H {heads}, N {N}, D {D}", q.data_ptr(), k.data_ptr(),
+               v.data_ptr(), idx_a.data_ptr(), idx_b.data_ptr(), n_pairs, B, heads, N, D, dt, sim, w_out.data_ptr(), bias.data_ptr(),
+               out.data_ptr(), _ptr(status))
+    return (out, status) if return_status else out
+
+
 def pair_score_maps(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, idx_a: torch.Tensor, idx_b: torch.Tensor,
                     heads: int, similarity: str = "cosine", return_status: bool = False):
     """The score tail kept per query token (dsim_pair_score_maps).  q,k,v: [n_feat][B][N][H*D]; idx: int32 cuda [n_pairs].
@@ -1493,4 +1515,115 @@ class DiTEngine(_Handle):
             if not need and st in (0, -3):
                 raise _lib.DsimError(f"{n} images do not fit one sweep call (an activation or a tap output would reach 2 GiB)")
             _lib.check(st, "dsim_dit_qkv_taps")
+        return outs
+
+
+# ---- ViT backbones: the reference's clip_cross / dino_cross metrics ----------------------------------------------------
+def interpolate_pos_embed(pos: torch.Tensor, grid: int) -> torch.Tensor:
+    """A stored position table (1 + g0^2, C) at a grid x grid patch grid: the class row kept, the patch rows bicubically
+    interpolated in f32 (align_corners False) as HF Dinov2Embeddings.interpolate_pos_encoding does; unchanged when g0 == grid."""
+    g0 = int(round((pos.shape[0] - 1) ** 0.5))
+    if g0 * g0 != pos.shape[0] - 1:
+        raise _lib.DsimError(f"position table of {pos.shape[0]} rows: not 1 + a square grid")
+    if g0 == grid:
+        return pos
+    patch = pos[1:].float().reshape(1, g0, g0, -1).permute(0, 3, 1, 2)
+    patch = torch.nn.functional.interpolate(patch, size=(grid, grid), mode="bicubic", align_corners=False)
+    return torch.cat([pos[:1].float(), patch.permute(0, 2, 3, 1).reshape(grid * grid, -1)]).contiguous()
+
+
+class ViTEngine(_Handle):
+    """One handle = (ViT config, compute dtype, image side, tapped layer).  state_dict: the neutral keys of config.vit_param_shapes,
+    the position table at its stored grid (interpolated here, on the host, to the side's grid -- DINOv2 only: CLIP has one side)."""
+
+    prefix = "vit"
+
+    def __init__(self, cfg, state_dict: Dict[str, torch.Tensor], dtype: torch.dtype = torch.bfloat16, target_layer: int = 0,
+                 device: str = "cuda:0", side: Optional[int] = None):
+        self.L = _lib.lib()
+        if not torch.cuda.is_available():
+            raise _lib.DsimError("no GPU visible: the ViT engine runs only on the HIP device")
+        side = cfg.image_size if side is None else int(side)
+        if side % cfg.patch_size or side < cfg.patch_size:
+            raise _lib.DsimError(f"image side {side} is not a multiple of the patch size {cfg.patch_size}")
+        grid = side // cfg.patch_size
+        if cfg.kind == "clip" and grid != cfg.pos_grid:
+            raise _lib.DsimError(f"CLIP position table serves {cfg.pos_grid * cfg.patch_size} px only (no interpolation): got {side}")
+        self.cfg, self.dtype, self.device, self.side = cfg, dtype, torch.device(device), side
+        c = _lib.ViTCfgC()
+        c.image_size = side
+        for f in ("patch_size", "hidden_size", "depth", "num_heads", "mlp_dim"):
+            setattr(c, f, getattr(cfg, f))
+        c.act, c.tap_input = _lib.VIT_ACT[cfg.act], _lib.VIT_TAP_INPUT[cfg.tap_input]
+        c.pre_norm, c.patch_bias, c.layer_scale = int(cfg.pre_norm), int(cfg.patch_bias), int(cfg.layer_scale)
+        c.ln_eps, c.compute_dtype, c.tap_layer = float(cfg.ln_eps), _TORCH2DSIM[dtype], int(target_layer)
+        self.target_layer = int(target_layer)
+        self.tokens = cfg.tokens(side)
+        self.heads, self.head_dim = cfg.num_heads, cfg.hidden_size // cfg.num_heads
+        sd = dict(state_dict)
+        sd["pos_embed"] = interpolate_pos_embed(sd["pos_embed"], grid)
+        self._create_and_load(c, sd)
+
+    def set_tap(self, layer: int):
+        """Move the tapped layer; the packed weights are shared by every --target_layer (dsim_vit_set_tap)."""
+        if int(layer) != self.target_layer:
+            _lib.check(self.L.dsim_vit_set_tap(self._h, int(layer)), "dsim_vit_set_tap")
+            self.target_layer = int(layer)
+
+    def _check_pixels(self, pixels: torch.Tensor) -> int:
+        _require_cuda(pixels)
+        n = pixels.shape[0]
+        if tuple(pixels.shape) != (n, 3, self.side, self.side) or pixels.dtype != torch.float32 or n < 1:
+            raise _lib.DsimError(f"pixels must be float32 (n,3,{self.side},{self.side}): {tuple(pixels.shape)} {pixels.dtype}")
+        return n
+
+    def workspace_bytes(self, n_images: int) -> int:
+        return int(self.L.dsim_vit_workspace_bytes(self._h, n_images))
+
+    def max_images(self, upper: int = 4096) -> int:
+        """Largest n_images one qkv call accepts (every activation < 2 GiB)."""
+        return self._largest(lambda m: self.workspace_bytes(m) > 0, upper)
+
+    def qkv(self, pixels: torch.Tensor):
+        """pixels: normalised f32 (n, 3, S, S) on the device -> q, k, v (n, 1, N, C) in the compute dtype, the class token first."""
+        n = self._check_pixels(pixels)
+        with torch.cuda.device(self.device):
+            need = self.workspace_bytes(n)
+            if not need:
+                raise _lib.DsimError(f"{n} images do not fit one call (an activation would reach 2 GiB)")
+            ws = self._arena(need)
+            shape = (n, 1, self.tokens, self.cfg.hidden_size)
+            q, k, v = (torch.empty(shape, dtype=self.dtype, device=self.device) for _ in range(3))
+            _lib.check(self.L.dsim_vit_qkv(self._h, pixels.data_ptr(), n, q.data_ptr(), k.data_ptr(), v.data_ptr(), ws.data_ptr(),
+                                           ws.numel(), _stream_ptr()), "dsim_vit_qkv")
+        return q, k, v
+
+    # ---- tap sweeps: the q,k,v of several layers from one forward (dsim_vit_qkv_taps) ---------------------------------------
+    def taps_workspace_bytes(self, n_images: int, layers) -> int:
+        arr = (C.c_int * max(1, len(layers)))(*[int(l) for l in layers])
+        return int(self.L.dsim_vit_taps_workspace_bytes(self._h, n_images, len(layers), arr))
+
+    def max_images_taps(self, layers, upper: int = 4096) -> int:
+        return self._largest(lambda m: self.taps_workspace_bytes(m, layers) > 0, upper)
+
+    def qkv_taps(self, pixels: torch.Tensor, layers):
+        """qkv() at every layer of `layers` (any order, no repeats) from ONE forward to the deepest: entry i is bit for bit what
+        qkv() returns with the tap at layers[i].  The handle's own tap does not move."""
+        n, nt = self._check_pixels(pixels), len(layers)
+        if nt < 1:
+            raise _lib.DsimError("qkv_taps: no taps")
+        try:
+            arr = (C.c_int * nt)(*[int(l) for l in layers])
+        except (TypeError, ValueError):
+            raise _lib.DsimError(f"unknown taps {layers!r}") from None
+        with torch.cuda.device(self.device):
+            need = self.taps_workspace_bytes(n, layers)
+            if not need:
+                raise _lib.DsimError(f"taps {list(layers)!r} of {n} images: an invalid or repeated layer, or an activation would reach 2 GiB")
+            ws = self._arena(need)
+            shape = (n, 1, self.tokens, self.cfg.hidden_size)
+            outs = [tuple(torch.empty(shape, dtype=self.dtype, device=self.device) for _ in range(3)) for _ in range(nt)]
+            ptr = lambda j: (C.c_void_p * nt)(*[o[j].data_ptr() for o in outs])
+            _lib.check(self.L.dsim_vit_qkv_taps(self._h, pixels.data_ptr(), n, nt, arr, ptr(0), ptr(1), ptr(2), ws.data_ptr(), ws.numel(),
+                                                _stream_ptr()), "dsim_vit_qkv_taps")
         return outs

@@ -73,14 +73,16 @@ def cute_accuracy(s_ab: torch.Tensor, s_ac: torch.Tensor) -> float:
 
 
 @torch.no_grad()
-def triplet_chunks(scorer, ref, left, right, nA, nB, prompt, heads, similarity, batch_triplets: int, feats, masks=None, text=None):
+def triplet_chunks(scorer, ref, left, right, nA, nB, prompt, heads, similarity, batch_triplets: int, feats, masks=None, text=None,
+                   tails=None):
     """(ref,left) and (ref,right) scores of latent triplets at every tap of a forward: 3 forwards per triplet (the reference
     image's features are shared), chunked engine batches, one fused tail launch per chunk and tap.  feats(lat, nz, prompt) ->
     [(q, k, v) per tap] is the forward of one engine batch, heads[t] tap t's head count.  masks: None, or the (ref, left, right)
     token masks, each (n, N) bool on the device: the region tail (regions.py) over each chunk's rows instead of the pair tail.
     text: None, or (guide, w): a textattn.TextGuide and its bound per-triplet weights; feats then returns (q, k, v, xq, xkv) per
     tap and the masks of the region tail are the text-guided regions of the chunk's images -- ref, left and right each their own,
-    the ref's made once per triplet.  Returns the (nt, n) scores of both sides and the (nt,) NaN / inf counts."""
+    the ref's made once per triplet.  tails: None, or each tap's ``Scorer.pair_tail`` (a None entry: engine.pair_score).  Returns
+    the (nt, n) scores of both sides and the (nt,) NaN / inf counts."""
     n, nt, dev = ref.shape[0], len(heads), scorer.device
     s_l = torch.empty((nt, n), dtype=torch.float32, device=dev)
     s_r = torch.empty((nt, n), dtype=torch.float32, device=dev)
@@ -93,7 +95,7 @@ def triplet_chunks(scorer, ref, left, right, nA, nB, prompt, heads, similarity, 
         ia, ib = torch.cat([base, base]), torch.cat([base + 1, base + 2])
         for t, (q, k, v, *xs) in enumerate(fs):
             if masks is None and text is None:
-                s, st = pair_score(q, k, v, ia, ib, heads[t], similarity, return_status=True)
+                s, st = ((tails[t] if tails else None) or pair_score)(q, k, v, ia, ib, heads[t], similarity, return_status=True)
             else:                                           # (the chunk's mask rows lie as its images do: ref, left, right)
                 if text is not None:
                     rows, _counts = text[0].regions(*xs, heads[t], text[1], i0, i1, 3)
@@ -130,7 +132,8 @@ def _score_chunks(scorer, ref, left, right, nA, nB, prompt, block, layer, step, 
         return triplet_chunks(scorer, ref, left, right, nA, nB, prompt, [heads], similarity, batch_triplets,
                               lambda lat, nz, p: [scorer.tap_features_text(lat, nz, p, tap, step)], text=text)
     return triplet_chunks(scorer, ref, left, right, nA, nB, prompt, [heads], similarity, batch_triplets,
-                          lambda lat, nz, p: [scorer.tap_features(lat, nz, p, tap, step)], *(() if masks is None else (masks,)))
+                          lambda lat, nz, p: [scorer.tap_features(lat, nz, p, tap, step)], *(() if masks is None else (masks,)),
+                          tails=[scorer.pair_tail(tap)])
 
 
 @torch.no_grad()

@@ -44,6 +44,10 @@ def path_latents(scorer, rows: Sequence[Tuple[str, ...]], slots: Sequence[int], 
     vae = getattr(scorer, "vae", None)
     k = len(slots)
     cols = [[] for _ in slots]
+    if not scorer.draws:            # a kind without VAE and noise: its own input tensors, and placeholders where the noises go
+        cols = [torch.cat([scorer.load_input(row[c], img_size) for row in rows]) for c in range(k)]
+        none = torch.zeros((1,) + tuple(cols[0].shape[1:]))
+        return cols, none, none
     if vae is not None and hasattr(vae, "moments") and hip_vae:    # the HIP VAE encoder: chunked, look-ahead decode
         sf = vae.config.scaling_factor
         pool = getattr(scorer, "_decode", None) or _shared_pool()
@@ -79,7 +83,7 @@ def path_latents(scorer, rows: Sequence[Tuple[str, ...]], slots: Sequence[int], 
         else:
             g = torch.Generator("cpu")
             g.set_state(state[1])
-        lat = scorer.prepare(process_image(load_image(path), img_size), g)
+        lat = scorer.prepare(scorer.load_input(path, img_size), g)
         state.setdefault(slot + 1, g.get_state())
         return lat
     for row in rows:

@@ -24,6 +24,7 @@ from typing import Callable, Dict, Optional
 import torch
 
 from . import text as T
+from ._lib import DsimError
 from .config import SD15, SDXL, VAE_SD15, DIT_XL2, DiTConfig, UNetConfig, VAEConfig
 
 
@@ -229,3 +230,38 @@ def load_diffsim_dit(model_path: str, img_size: int, target_step: int, dtype: st
                      torch.float32, dev)
     return diffsim_DiT(img_size, target_step, dev, dit_config=cfg, state_dict=sd, vae=vae, torch_dtype=td,
                        fp8_attention=fp8_attention)
+
+
+def _load_vit(model_path: str, kind: str, dtype: str, device: str):
+    """An HF-layout directory (config.json, *.safetensors, optional preprocessor_config.json) -> (ViTConfig, neutral state dict,
+    Preprocess, torch dtype, device)."""
+    from . import vit as V
+    td = _torch_dtype(dtype)
+    dev = "cuda:0" if device == "cuda" else device
+    cfg = V.vit_config_from_json(_json(model_path), kind)
+    pre = V.Preprocess.from_dir(model_path, V.CLIP_PREPROCESS if kind == "clip" else V.DINOV2_PREPROCESS)
+    if kind == "clip" and pre.crop != cfg.image_size:
+        raise ValueError(f"the preprocessor crops to {pre.crop} px but the CLIP tower's position table serves {cfg.image_size} px only")
+    if pre.crop % cfg.patch_size:
+        raise ValueError(f"the preprocessor's {pre.crop} px crop is not a multiple of the patch size {cfg.patch_size}")
+    cfg = dataclasses.replace(cfg, image_size=pre.crop)
+    sd = V.neutral_state_dict(load_state_dict(model_path), cfg)
+    return cfg, sd, pre, td, dev
+
+
+def load_clip_cross(model_path: str, dtype: str = "bf16", device: str = "cuda"):
+    """HF CLIPVisionModel / CLIPModel directory -> :class:`diffsim_amd.vit.CLIPScore` (metrics/clip_i.py:36-58)."""
+    from .vit import CLIPScore
+    cfg, sd, pre, td, dev = _load_vit(model_path, "clip", dtype, device)
+    if not torch.cuda.is_available():
+        raise DsimError("no GPU visible: the ViT engine runs only on the HIP device")
+    return CLIPScore(cfg, sd, dev, td, pre)
+
+
+def load_dino_cross(model_path: str, dtype: str = "bf16", device: str = "cuda"):
+    """HF Dinov2Model directory -> :class:`diffsim_amd.vit.Dinov2Score` (metrics/dino.py:94-109)."""
+    from .vit import Dinov2Score
+    cfg, sd, pre, td, dev = _load_vit(model_path, "dinov2", dtype, device)
+    if not torch.cuda.is_available():
+        raise DsimError("no GPU visible: the ViT engine runs only on the HIP device")
+    return Dinov2Score(cfg, sd, dev, td, pre)

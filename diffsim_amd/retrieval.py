@@ -20,6 +20,7 @@ from typing import List, Optional, Sequence
 
 import torch
 
+from ._lib import DsimError
 from .engine import score_matrix, score_matrix_regions, score_matrix_regions_workspace_bytes, score_matrix_workspace_bytes
 from .inputs import path_latents
 from .scorer import stack_rows
@@ -78,6 +79,9 @@ def score_latent_matrix(scorer, latA, latB, noiseA, noiseB, prompt, target_block
     nB = noiseB.to(dev, torch.float32)
     n_a, n_b = latA.shape[0], latB.shape[0]
     tap = scorer.tap_of(target_block, target_layer)
+    if getattr(scorer, "pair_tail", lambda tap: None)(tap) is not None:
+        raise DsimError(f"{type(scorer).__name__} scores pairs with a tail of its own (Scorer.pair_tail): there is no score matrix "
+                        "for it yet (clip_cross needs a projected matrix); score pairs or triplets instead")
     prompt = scorer.bind_prompt(prompt, n_a, "queries")             # (one prompt of the call)
     eng = scorer.engine_at(tap)
     heads = eng.heads

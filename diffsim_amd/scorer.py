@@ -10,7 +10,7 @@ from typing import List, NamedTuple, Sequence, Tuple
 import torch
 
 from ._lib import DsimError
-from .config import DiTConfig
+from .config import DiTConfig, ViTConfig
 
 
 def get_generator(seed, device="cpu"):
@@ -79,8 +79,8 @@ def stack_rows(cols: Sequence[torch.Tensor], noises: Sequence[torch.Tensor], i0:
 
 
 def all_taps(cfg) -> list:
-    """Every tap the model's addressing names, in walk order: SD1.5 7, SDXL 70 (24 down, 10 mid, 36 up), DiT its depth."""
-    if isinstance(cfg, DiTConfig):
+    """Every tap the model's addressing names, in walk order: SD1.5 7, SDXL 70 (24 down, 10 mid, 36 up), DiT and ViT their depth."""
+    if isinstance(cfg, (DiTConfig, ViTConfig)):
         return list(range(cfg.depth))
     n, lpb = len(cfg.block_out_channels), cfg.layers_per_block
     down = [t == "CrossAttnDownBlock2D" for t in cfg.down_block_types]
@@ -117,6 +117,20 @@ class Scorer:
     def prepare(self, tensor, generator):
         """prepare_image_latents of one image, returned as the f32 values the pipeline carries on."""
         return self.prepare_image_latents(tensor, generator).float()
+
+    draws = True                            # whether a call draws at all (VAE sample, noise); False: the input tensors are the
+                                            #   "latents", the noises are placeholders and tap_features ignores noise, prompt, step
+
+    def load_input(self, path, img_size):
+        """One image (a path or a PIL image) as the kind's (1, 3, S, S) f32 input tensor on the host: the reference's
+        process_image (Lanczos resize to img_size, [-1, 1]) in front of the VAE."""
+        from .image import load_image, process_image
+        return process_image(load_image(path), img_size)
+
+    def pair_tail(self, tap):
+        """The pair tail of the kind at `tap`, a callable with engine.pair_score's signature; None: engine.pair_score itself, the
+        plain DiffSim tail (the batched paths then call their own module's binding of it)."""
+        return None
 
     # ---- batching facts
     mixes_prompts = True                    # whether one engine batch may carry several prompts (group_key)

@@ -55,6 +55,10 @@ def parse_tap_specs(specs: Sequence[str], metric: str, cfg=None):
             if block != "blocks" or len(vals) != 1:
                 raise ValueError(f"tap {s!r}: DiT taps are blocks:LAYER")
             tap = vals[0]
+        elif metric in ("clip_cross", "dino_cross"):
+            if block != "layers" or len(vals) != 1:
+                raise ValueError(f"tap {s!r}: ViT taps are layers:LAYER")
+            tap = vals[0]
         elif block not in UNET_BLOCKS:
             raise ValueError(f"tap {s!r}: unknown block {block!r} (one of {', '.join(UNET_BLOCKS)})")
         elif metric == "diffsim_xl":
@@ -103,13 +107,14 @@ def score_latent_pairs_taps(scorer, latA, latB, noiseA, noiseB, prompt, taps, ta
     eng, shapes = scorer.sweep_engine(taps, latA.shape[2])
     batch_pairs = _sweep_rows(scorer, eng, taps, shapes, n, 2, prompt, batch_pairs)
     out = torch.empty((len(taps), n), dtype=torch.float32, device=dev)
+    tails = [scorer.pair_tail(t) for t in taps]
     for i0 in range(0, n, batch_pairs):
         i1 = min(n, i0 + batch_pairs)
         fs = scorer.taps_features(*stack_rows([latA, latB], [noiseA, noiseB], i0, i1), scorer.chunk_prompt(prompt, i0, i1, 2), taps,
                                   target_step)
         ia = torch.arange(0, 2 * (i1 - i0), 2, dtype=torch.int32, device=dev)
         for t, (q, k, v) in enumerate(fs):
-            out[t, i0:i1] = pair_score(q, k, v, ia, ia + 1, shapes[t][1], similarity)
+            out[t, i0:i1] = (tails[t] or pair_score)(q, k, v, ia, ia + 1, shapes[t][1], similarity)
     return out
 
 
@@ -139,7 +144,7 @@ def _score_chunks_taps(scorer, ref, left, right, nA, nB, prompt, taps, step, sim
     eng, shapes = scorer.sweep_engine(taps, ref.shape[2])
     batch_triplets = _sweep_rows(scorer, eng, taps, shapes, n, 3, prompt, batch_triplets)
     return triplet_chunks(scorer, ref, left, right, nA, nB, prompt, [h for _t, h, _d in shapes], similarity, batch_triplets,
-                          lambda lat, nz, p: scorer.taps_features(lat, nz, p, taps, step))
+                          lambda lat, nz, p: scorer.taps_features(lat, nz, p, taps, step), tails=[scorer.pair_tail(t) for t in taps])
 
 
 def score_path_triplets_taps(scorer, triplets: Sequence[Tuple[str, str, str, str]], img_size: int, taps, target_step,

@@ -12,7 +12,8 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
-from .config import DiTConfig, UNetConfig, VAEConfig, dit_param_shapes, unet_param_shapes, vae_encoder_param_shapes
+from .config import (DiTConfig, UNetConfig, VAEConfig, ViTConfig, dit_param_shapes, unet_param_shapes, vae_encoder_param_shapes,
+                     vit_param_shapes)
 
 
 def make_state_dict(cfg: UNetConfig, seed: int = 0, keys: Optional[Sequence[str]] = None
@@ -24,6 +25,8 @@ def make_state_dict(cfg: UNetConfig, seed: int = 0, keys: Optional[Sequence[str]
     Each tensor has its own generator keyed by its position, so a subset is reproducible."""
     if isinstance(cfg, DiTConfig):
         shapes = dit_param_shapes(cfg)
+    elif isinstance(cfg, ViTConfig):
+        shapes = vit_param_shapes(cfg)
     else:
         shapes = vae_encoder_param_shapes(cfg) if isinstance(cfg, VAEConfig) else unet_param_shapes(cfg)
     out: Dict[str, torch.Tensor] = {}
@@ -32,9 +35,21 @@ def make_state_dict(cfg: UNetConfig, seed: int = 0, keys: Optional[Sequence[str]
             continue
         g = torch.Generator("cpu").manual_seed(seed * 1000003 + idx)
         leaf = k.rsplit(".", 2)
-        is_norm = ".norm" in k or "conv_norm_out" in k or "group_norm" in k
-        if k == "pos_embed":
+        is_norm = ".norm" in k or "conv_norm_out" in k or "group_norm" in k or k.startswith("pre_norm.")
+        if k == "pos_embed" and len(shp) == 3:
             out[k] = dit_pos_embed(shp[2], int(round(shp[1] ** 0.5)))
+            continue
+        if isinstance(cfg, ViTConfig) and k in ("pos_embed", "cls_token"):      # learned tables: order 0.3, as trained ones are
+            out[k] = (0.3 * torch.randn(shp, generator=g)).to(torch.float32).contiguous()
+            continue
+        if isinstance(cfg, ViTConfig) and k.endswith((".ls1", ".ls2")):           # LayerScale: around 1, not constant
+            out[k] = (1.0 + 0.2 * torch.randn(shp, generator=g)).to(torch.float32).contiguous()
+            continue
+        if isinstance(cfg, ViTConfig) and k.endswith("attn.qkv.weight"):          # q and k rows with the attention gain (logits std ~2)
+            a = math.sqrt(3.0 / shp[1])
+            t = (torch.rand(shp, generator=g) * 2 - 1) * a
+            t[: 2 * shp[1]] *= 1.4
+            out[k] = t.to(torch.float32).contiguous()
             continue
         if k.endswith("adaLN_modulation.1.weight") or k.endswith("embedding_table.weight"):
             t = 0.3 * torch.randn(shp, generator=g) / (1.0 if k.endswith("table.weight") else math.sqrt(shp[1] / 8.0))

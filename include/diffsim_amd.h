@@ -479,6 +479,71 @@ int    dsim_dit_qkv_taps(dsim_dit* h, const float* latents, const float* noise, 
                          int n_images, int n_taps, const int* layers, void* const* q, void* const* k, void* const* v,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- ViT scorer backbones (additive to ABI v7): the reference's clip_cross and dino_cross metrics.  Replaces the forward of HF
+ *      CLIPVisionModel up to encoder layer L with the hook of metrics/hooks.py:3-17 on it (metrics/clip_i.py:113-141), and of HF
+ *      Dinov2Model up to layer L's attention with the hook of metrics/hooks.py:19-32 on it (metrics/dino.py:120-146): q, k, v are
+ *      the hooked layer's own q / k / v Linear layers applied to the hook's input.
+ *      Weights under one neutral naming (the Python side maps the HF keys): pos_embed [N][C] (already interpolated to the
+ *      handle's side), cls_token [C], x_embedder.proj.weight [C][3][p][p] (+ .bias with patch_bias), pre_norm.{weight,bias}
+ *      (with pre_norm), blocks.N.{norm1,norm2}.{weight,bias}, blocks.N.attn.qkv.{weight,bias} ([3C][C] = q ; k ; v),
+ *      blocks.N.attn.proj.*, blocks.N.mlp.{fc1,fc2}.*, blocks.N.{ls1,ls2} [C] (with layer_scale). ------------------------- */
+#define DSIM_VIT_ACT_GELU 0          /* erf form (F.gelu's default): DINOv2 */
+#define DSIM_VIT_ACT_QUICK_GELU 1    /* x * sigmoid(1.702 x): CLIP */
+typedef struct dsim_vit_cfg {
+    int32_t image_size;        /* side of the (square) input in pixels: 224 */
+    int32_t patch_size;        /* 32 (CLIP-B/32), 14 (DINOv2) */
+    int32_t hidden_size;       /* C: 768, 384 */
+    int32_t depth;             /* 12 */
+    int32_t num_heads;         /* 12, 6 (head dim 64) */
+    int32_t mlp_dim;           /* 3072, 1536 */
+    int32_t act;               /* DSIM_VIT_ACT_* */
+    int32_t pre_norm;          /* 1: LayerNorm on the embedded tokens (CLIP's pre_layrnorm) */
+    int32_t patch_bias;        /* 1: the patch conv has a bias (DINOv2) */
+    int32_t layer_scale;       /* 1: LayerScale vectors on both residual branches (DINOv2) */
+    int32_t tap_input;         /* 0: q/k/v from norm1's output (DINOv2's hook); 1: from the block's raw input (CLIP's hook) */
+    float   ln_eps;            /* 1e-5 (CLIP), 1e-6 (DINOv2) */
+    int32_t compute_dtype;     /* DSIM_F32, DSIM_BF16 or DSIM_F16 */
+    int32_t tap_layer;         /* block index L of the hooked layer */
+} dsim_vit_cfg;
+typedef struct dsim_vit dsim_vit;
+
+/* Life cycle, error codes and "every check before the first launch" as the dsim_dit_* calls of the same names. */
+int    dsim_vit_create(const dsim_vit_cfg* cfg, dsim_vit** out);
+void   dsim_vit_destroy(dsim_vit* h);
+int    dsim_vit_load_weight(dsim_vit* h, const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim);
+int    dsim_vit_finalize(dsim_vit* h, void* stream);
+int    dsim_vit_set_tap(dsim_vit* h, int tap_layer);        /* moves the tap without re-packing (as dsim_dit_set_tap) */
+int    dsim_vit_profile(dsim_vit* h, int enable);
+int    dsim_vit_profile_count(const dsim_vit* h);
+int    dsim_vit_profile_get(dsim_vit* h, int i, char* name, int name_cap, double* flops, double* bytes, double* ms);
+size_t dsim_vit_workspace_bytes(const dsim_vit* h, int n_images);
+/* pixels: f32 [n_images][3][S][S], already normalised (the image processor's output); q,k,v (out): compute dtype
+ * [n_images][1][N][heads*head_dim], N = 1 + (S / patch)^2, the class token first.  An image's rows do not depend on the other
+ * images of the call beyond the GEMM tile choice. */
+int    dsim_vit_qkv(dsim_vit* h, const float* pixels, int n_images, void* q, void* k, void* v, void* workspace,
+                    size_t workspace_bytes, void* stream);
+/* Tap sweep, as dsim_dit_qkv_taps: the layers (any order, no duplicates) in ONE walk to the deepest, bit for bit what
+ * dsim_vit_qkv writes with its tap at layers[i]. */
+size_t dsim_vit_taps_workspace_bytes(const dsim_vit* h, int n_images, int n_taps, const int* layers);
+int    dsim_vit_qkv_taps(dsim_vit* h, const float* pixels, int n_images, int n_taps, const int* layers, void* const* q,
+                         void* const* k, void* const* v, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- projected score tail: replaces CLIPScore.attention_calc of metrics/clip_i.py:143-159 (4x SDPA, each followed by the hooked
+ *      layer's out_proj, then 2x cosine, mean).  Arguments as dsim_pair_score_status, plus
+ *   w_out       : compute dtype [C][C], C = H*D, rows = output features (nn.Linear's weight)
+ *   bias        : f32 [C]
+ * Per pair and direction the cross and the self attention outputs are rounded to the compute dtype as dsim_pair_score rounds them
+ * and kept in the workspace; P = O w_out^T + bias with f32 accumulation, rounded to the compute dtype; the cosine (eps 1e-8) or mse
+ * (over B*N*C values) sums are f32 per workgroup and f64 across workgroups in a fixed order: deterministic, no atomics, and a
+ * pair's score does not depend on the other pairs of the call.  status may be NULL.
+ * DSIM_ERR_INVALID (workspace query: 0) for a head dim outside the supported list, a bad dtype or similarity, n_pairs < 1,
+ * 2 n_pairs > 65535, 2 B H > 65535 or C > 1024 (16 rows of C f32 values fill 64 KiB of LDS); DSIM_ERR_WORKSPACE for
+ * a short workspace; both decided on the host before anything is enqueued. */
+size_t dsim_pair_score_proj_workspace_bytes(int n_pairs, int B, int H, int N, int D, int dtype);
+int    dsim_pair_score_proj(const void* q, const void* k, const void* v, const int32_t* idx_a, const int32_t* idx_b, int n_pairs,
+                            int B, int H, int N, int D, int dtype, int similarity, const void* w_out, const float* bias,
+                            float* out_scores, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- the arithmetic either side of the VAE encoder, on the device (the host only decodes and resizes) ----
  * dsim_image_preprocess: what process_image does after its Lanczos resize (diffsim/diffsim.py:31-41): pixels u8 [n][H][W][3] ->
  *   f32 [n][3][H][W] = (p / 255 - 0.5) / 0.5 in IEEE f32, bit-identical to the numpy path; to_half = 1 additionally rounds
