@@ -201,6 +201,10 @@ SYMBOLS = {
     "dsim_text_attention": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dsim_pair_score_regions_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
     "dsim_pair_score_regions": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dsim_pair_score_maps_regions_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "dsim_pair_score_maps_regions": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dsim_pair_align_regions_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "dsim_pair_align_regions": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dsim_score_matrix_regions_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
     "dsim_score_matrix_regions": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dsim_op_linear": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),

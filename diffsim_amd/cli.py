@@ -4,7 +4,7 @@
 
 Flags of the reference drivers (``/root/reference/argprocess.py:5-18``) keep their names, meaning and defaults;
 ``--dataset`` selects which of the reference's loops runs (``cute_main.py:48-226``, ``night_main.py:24-173`` or
-``style_main.py:24-196`` -- separate scripts there), ``--model_path / --dtype / --batch / --unet_batch / --ngpu / --noise_dtype / --mask_path / --query_mask_path / --gallery_mask_path / --text_attn / --text_threshold`` are additions of this build (the reference
+``style_main.py:24-196`` -- separate scripts there), ``--model_path / --dtype / --batch / --unet_batch / --ngpu / --noise_dtype / --mask_path / --query_mask_path / --gallery_mask_path / --save_region_maps / --save_region_matches / --text_attn / --text_threshold`` are additions of this build (the reference
 hard-codes NAS checkpoint paths, ``cute_main.py:25-31``, fp16 and one GPU, ``cute_main.sh:1``).
 
 Multi-GPU (``--ngpu N``): the parent starts N rank processes before anything touches the GPU; triplets are sharded
@@ -56,6 +56,15 @@ def build_parser() -> argparse.ArgumentParser:
                    help="--dataset retrieval: beside each ranking .txt also write <name>.match.npz with the token alignments of the "
                         "query against its top-k gallery images (gallery, match and weight (k, 2, h, w), expect (k, 2, h, w, 2): "
                         "direction 0 on the query's token grid pointing into the gallery image's, 1 the other way round)")
+    p.add_argument("--save_region_maps", action="store_true",
+                   help="--dataset retrieval with --query_mask_path / --gallery_mask_path: beside each ranking .txt also write "
+                        "<name>.npz with the REGION maps of the query against its top-k gallery images: --save_maps' arrays computed "
+                        "over the masked tokens alone (the terms of the region score; zeros at the off tokens), and mask (k, 2, h, w)")
+    p.add_argument("--save_region_matches", action="store_true",
+                   help="--dataset retrieval with --query_mask_path / --gallery_mask_path: beside each ranking .txt also write "
+                        "<name>.match.npz with the REGION alignments of the query against its top-k gallery images: --save_matches' "
+                        "arrays with every softmax over the other image's masked tokens alone (off tokens: match -1, weight 0, expect "
+                        "(-1, -1)), and mask (k, 2, h, w)")
     p.add_argument("--taps", type=str, nargs="+", default=None, metavar="SPEC",
                    help="--dataset cute|nights|sref: score every tap from one forward per image batch instead of the one "
                         "--target_block / --target_layer tap (which it overrides), and print one section per tap, in the given "
@@ -111,6 +120,17 @@ def build_parser() -> argparse.ArgumentParser:
 def arg_parse(argv=None):
     p = build_parser()
     args = p.parse_args(argv)
+    region_out = [f for f, on in (("--save_region_maps", args.save_region_maps), ("--save_region_matches", args.save_region_matches)) if on]
+    for flag in region_out:
+        if args.dataset != "retrieval" or (args.query_mask_path is None and args.gallery_mask_path is None):
+            p.error(f"{flag} writes the per-token outputs of region rankings: it needs --dataset retrieval and --query_mask_path and / "
+                    "or --gallery_mask_path")
+        if args.metric in VIT_METRICS:
+            p.error(f"{flag}: --metric {args.metric} has no regions, maps or alignments (its tokens are a class token and a patch grid: "
+                    "the class token is not on the grid)")
+        if args.taps is not None or args.text_attn is not None:
+            p.error(f"{flag} takes one tap (--target_block / --target_layer) and mask files: --taps and --text_attn are not supported "
+                    "with it")
     if args.taps is not None:
         if args.dataset == "retrieval" or args.save_maps or args.save_matches:
             p.error("--taps sweeps the triplet benchmarks (--dataset cute, nights or sref): score matrices, similarity maps and "
@@ -134,7 +154,8 @@ def arg_parse(argv=None):
                     "--mask_path)")
         if args.save_maps or args.save_matches:
             p.error(f"--{flag}: --save_maps and --save_matches write per-token outputs of whole images (their epilogue stores rows in "
-                    "order) and are not supported with region rankings")
+                    "order) and are not supported with region rankings; --save_region_maps and --save_region_matches write the "
+                    "regions' own")
         if args.text_attn is not None:
             p.error(f"--{flag}: text-guided regions (--text_attn) are not supported for --dataset retrieval")
     if args.text_attn is not None:
@@ -433,8 +454,15 @@ def run_retrieval(args, scorer, layer) -> int:
                 missing += sum(1 for f in masks[side] if f is None)
         print(f"Region score matrix: masks from {' and '.join(d for d in (args.query_mask_path, args.gallery_mask_path) if d)}; "
               f"{missing} image(s) without a mask file are scored whole")
-        m, bad = R.score_path_matrix(scorer, queries, gallery, args.image_size, args.prompt, args.target_block, layer,
-                                     args.target_step, args.seed, args.similarity, return_status=True, **masks)
+        if (args.save_region_maps or args.save_region_matches) and queries and gallery:
+            # the matrix's own latents and draws, kept for the region maps / alignments of each query's top-k cells
+            (latA,), nA, _ = path_latents(scorer, [(p,) for p in queries], (0,), args.image_size, args.seed, R.ENCODE_CHUNK)
+            (latB,), _, nB = path_latents(scorer, [(p,) for p in gallery], (1,), args.image_size, args.seed, R.ENCODE_CHUNK)
+            m, bad = R.score_latent_matrix(scorer, latA, latB, nA, nB, args.prompt, args.target_block, layer, args.target_step,
+                                           args.similarity, return_status=True, **masks)
+        else:
+            m, bad = R.score_path_matrix(scorer, queries, gallery, args.image_size, args.prompt, args.target_block, layer,
+                                         args.target_step, args.seed, args.similarity, return_status=True, **masks)
     elif not (args.save_maps or args.save_matches):
         m, bad = R.score_path_matrix(scorer, queries, gallery, args.image_size, args.prompt, args.target_block, layer,
                                      args.target_step, args.seed, args.similarity, return_status=True)
@@ -468,6 +496,27 @@ def run_retrieval(args, scorer, layer) -> int:
                                            args.prompt, args.target_block, layer, args.target_step)
         afiles = A.write_match_files(args.out_path, queries, gallery, idx, al, args.query_path)
         print(f"Token alignments {al.grid[0]}x{al.grid[1]} of the top-{k} cells of {len(afiles)} queries written to {args.out_path}")
+    if (args.save_region_maps or args.save_region_matches) and queries and gallery:
+        from .regions import tap_grid
+        _vals, idx = R.topk(m, args.topk, args.similarity)
+        k = idx.shape[1]
+        cells = idx.reshape(-1)
+        # the matrix's own token masks (a missing or empty mask: the whole image), one pair of them per top-k cell
+        grid = tap_grid(scorer, scorer.tap_of(args.target_block, layer), latA.shape[-1])
+        mA = R._set_masks(masks.get("masks_a"), len(queries), grid, "cpu", "masks_a").repeat_interleave(k, 0)
+        mB = R._set_masks(masks.get("masks_b"), len(gallery), grid, "cpu", "masks_b")[cells.cpu()]
+        if args.save_region_maps:
+            from . import maps as M
+            mp = M.score_latent_pair_maps(scorer, latA.repeat_interleave(k, 0), latB[cells.to(latB.device)], nA, nB, args.prompt,
+                                          args.target_block, layer, args.target_step, args.similarity, maskA=mA, maskB=mB)
+            mfiles = M.write_map_files(args.out_path, queries, gallery, idx, mp, args.query_path)
+            print(f"Region maps {mp.grid[0]}x{mp.grid[1]} of the top-{k} cells of {len(mfiles)} queries written to {args.out_path}")
+        if args.save_region_matches:
+            from . import align as A
+            al = A.score_latent_pair_alignment(scorer, latA.repeat_interleave(k, 0), latB[cells.to(latB.device)], nA, nB, args.prompt,
+                                               args.target_block, layer, args.target_step, maskA=mA, maskB=mB)
+            afiles = A.write_match_files(args.out_path, queries, gallery, idx, al, args.query_path)
+            print(f"Region alignments {al.grid[0]}x{al.grid[1]} of the top-{k} cells of {len(afiles)} queries written to {args.out_path}")
     return 0
 
 

@@ -108,6 +108,37 @@ int dsim_pair_score_regions(const void* q, const void* k, const void* v, const u
     return st != DSIM_OK ? st : launch_pair_score_regions(a, dtype, mask, n_feat, out_scores, status, counts, (hipStream_t)stream);
 }
 
+size_t dsim_pair_score_maps_regions_workspace_bytes(int n_feat, int n_pairs, int B, int H, int N, int D) {
+    return with_slack(pair_score_maps_regions_scratch_bytes(n_feat, n_pairs, B, H, N, D));
+}
+
+int dsim_pair_score_maps_regions(const void* q, const void* k, const void* v, const uint8_t* mask, int n_feat, const int32_t* idx_a,
+                                 const int32_t* idx_b, int n_pairs, int B, int H, int N, int D, int dtype, int similarity, float* score,
+                                 float* local, float* contrib, int32_t* status, int32_t* counts, void* workspace, size_t workspace_bytes,
+                                 void* stream) {
+    PairArgs a{q, k, v, idx_a, idx_b, n_pairs, B, H, N, D, similarity, workspace, workspace_bytes};
+    const bool served = pair_score_maps_regions_scratch_bytes(n_feat, n_pairs, B, H, N, D) != 0;
+    const int st = tail_prologue({q, k, v, mask, idx_a, idx_b, score}, served ? pair_args_check(a, dtype) : DSIM_ERR_INVALID, a.scratch,
+                                 a.scratch_bytes);
+    return st != DSIM_OK ? st
+                         : launch_pair_score_maps_regions(a, dtype, mask, n_feat, score, local, contrib, status, counts, (hipStream_t)stream);
+}
+
+size_t dsim_pair_align_regions_workspace_bytes(int n_feat, int n_pairs, int B, int H, int N, int D) {
+    return with_slack(pair_align_regions_scratch_bytes(n_feat, n_pairs, B, H, N, D));
+}
+
+int dsim_pair_align_regions(const void* q, const void* k, const uint8_t* mask, int n_feat, const int32_t* idx_a, const int32_t* idx_b,
+                            int n_pairs, int B, int H, int N, int D, int dtype, int grid_w, int32_t* match, float* weight, float* expect,
+                            float* attn, int32_t* status, int32_t* counts, void* workspace, size_t workspace_bytes, void* stream) {
+    PairArgs a{q, k, nullptr, idx_a, idx_b, n_pairs, B, H, N, D, 0, workspace, workspace_bytes};
+    const bool served = pair_align_regions_scratch_bytes(n_feat, n_pairs, B, H, N, D) != 0;
+    const int st = tail_prologue({q, k, mask, idx_a, idx_b}, served ? pair_args_check(a, dtype) : DSIM_ERR_INVALID, a.scratch, a.scratch_bytes);
+    return st != DSIM_OK ? st
+                         : launch_pair_align_regions(a, dtype, mask, n_feat, grid_w, match, weight, expect, attn, status, counts,
+                                                     (hipStream_t)stream);
+}
+
 size_t dsim_score_matrix_regions_workspace_bytes(int n_a, int n_b, int B, int H, int N, int D, int dtype) {
     return with_slack(score_matrix_regions_scratch_bytes(n_a, n_b, B, H, N, D, dtype));
 }

@@ -1,9 +1,11 @@
 // What the score tails share on top of the tiled attention core (attn_core.h): the rounding of attend's output to the pipeline
 // dtype, the products of a cross output against a self output, a workgroup's partial, the two-attention pair body (pair_tail_body:
-// tails.hip's pair and map kernels in row order, regions.hip's region tail through row lists), the one-attention matrix kernel
+// tails.hip's pair and map kernels in row order, regions.hip's region tail and region_maps.hip's region map kernel through row
+// lists), the one-attention matrix kernel
 // (matrix_tail_kernel: tails.hip's score matrix in row order, region_matrix.hip's through row lists) with its arguments and
-// workspace layout, and the f64 finish (direction_value, store_score, pair_finish_kernel, launch_pair_finish).  Shared by tails.hip
-// (pairs, maps, matrices), regions.hip (region scores) and region_matrix.hip (region matrices), which must round and multiply alike
+// workspace layout, and the f64 finishes (direction_value, store_score, pair_finish_kernel, pair_map_finish_kernel and their
+// launches).  Shared by tails.hip (pairs, maps, matrices), regions.hip (region scores), region_matrix.hip (region matrices) and
+// region_maps.hip (region maps), which must round and multiply alike
 // to agree bit for bit; everything here lives in their dsim::(anonymous namespace).
 #pragma once
 #include "attn_core.h"
@@ -97,18 +99,18 @@ __device__ __forceinline__ void store_block_partial(TailSums t, int lane, int wa
 
 // One direction of a pair in a 128-query workgroup: the self and the cross attention on the same Q fragments, then their products.
 // The epilogue is one partial per workgroup, [pair][dir][bh][qtile][4] f32 (PER_TOKEN false), or one per query token,
-// [pair][dir][comp][bh][N] f32, comp: dot | x2 | y2, or sqd | - | - (PER_TOKEN true).
+// [pair][dir][comp][bh][N] f32 indexed by query POSITION, comp: dot | x2 | y2, or sqd | - | - (PER_TOKEN true).
 // Rows (attn_core.h): RowsInOrder -- query position t of an image is its row t and every image has N of them; list and cnt are not
 // read.  RowsListed -- the rows of an image i are list[i][0 .. cnt[i]), ascending: position t is row list[i][t] and the image's count
 // stands where N stood; the grid being sized for N, a workgroup past the query image's count, or of a pair with an empty image,
-// writes a zero partial and leaves as a whole before any barrier.
+// writes a zero partial and leaves as a whole before any barrier (PER_TOKEN: it writes nothing -- the positions from the count on
+// are never written, and the finish never reads them).
 // grid (ceil(N/128), B*H, n_pairs*2)
 template <typename T, int D, bool PER_TOKEN, typename Rows>
 __device__ __forceinline__ void pair_tail_body(const T* __restrict__ qg, const T* __restrict__ kg, const T* __restrict__ vg,
                                                const int32_t* __restrict__ list, const int32_t* __restrict__ cnt,
                                                const int32_t* __restrict__ idx_a, const int32_t* __restrict__ idx_b, int B, int H, int N,
                                                float scale_log2, int mse, float* __restrict__ part) {
-    static_assert(!(PER_TOKEN && Rows::LISTED), "the per-token epilogue stores by row: rows in order only");
     typedef ACfg<T, D> C;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, l31 = lane & 31;
@@ -123,9 +125,10 @@ __device__ __forceinline__ void pair_tail_body(const T* __restrict__ qg, const T
     if constexpr (Rows::LISTED) {
         nq = cnt[iq];
         nx = cnt[ix];
-        o = part + ((((size_t)pair * 2 + dir) * gridDim.y + bh) * gridDim.x + blockIdx.x) * 4;
+        if constexpr (!PER_TOKEN) o = part + ((((size_t)pair * 2 + dir) * gridDim.y + bh) * gridDim.x + blockIdx.x) * 4;
         if ((int)blockIdx.x * 128 >= nq || nx == 0) {          // (uniform over the workgroup)
-            if (threadIdx.x == 0) o[0] = o[1] = o[2] = o[3] = 0.f;
+            if constexpr (!PER_TOKEN)
+                if (threadIdx.x == 0) o[0] = o[1] = o[2] = o[3] = 0.f;
             return;
         }
         rq.list = list + (size_t)iq * N;
@@ -168,12 +171,12 @@ __device__ __forceinline__ void pair_tail_body(const T* __restrict__ qg, const T
         if (t < nq) s = tail_products<T, D>(oxa, half, mse, [&](int db, int r, int) { return osa.b[db][r]; });
     }
     if constexpr (PER_TOKEN) {
-        // a row's d values are split between the two lane halves: fold them, then the first half stores the row (128 B per wave and
-        // component, no atomics)
+        // a row's d values are split between the two lane halves: fold them, then the first half stores the row at its position
+        // t < nq (rows in order: nq = N) -- 128 B per wave and component, no atomics
         const float s0 = s.s0 + __shfl_xor(s.s0, 32);
         const float s1 = s.s1 + __shfl_xor(s.s1, 32);
         const float s2 = s.s2 + __shfl_xor(s.s2, 32);
-        if (half == 0 && t < N) {
+        if (half == 0 && t < nq) {
             const size_t plane = (size_t)gridDim.y * N;
             float* po = part + ((size_t)pair * 2 + dir) * 3 * plane + (size_t)bh * N + t;
             po[0] = s0;
@@ -375,6 +378,119 @@ int launch_pair_finish(const float* part, const int32_t* cnt, const int32_t* idx
                        double count, float* out, int32_t* status, hipStream_t s) {
     hipLaunchKernelGGL(pair_finish_kernel<REGIONS>, dim3((n + 63) / 64), dim3(64), 0, s, part, cnt, idx_a, idx_b, n, nblk, mse, count, out,
                        status);
+    DSIM_HIP_CHECK(hipGetLastError());
+    return DSIM_OK;
+}
+
+// ---- the f64 finish of the per-token partials ------------------------------------------------------------------------------------
+// one workgroup per pair, both directions: per token, a fixed-order f64 fold of the B*H partials; over tokens, per-thread strided
+// sums and a fixed-order tree.  local: the token's own cosine (|.| of the token's vectors) or mean squared difference; contrib: its
+// share of the direction's score, so that 0.5 (sum contrib[0] + sum contrib[1]) is the pair's score (the finish arithmetic above,
+// as pair_finish_kernel).
+// Rows as pair_tail_body's.  RowsInOrder (tails.hip's similarity maps): the partials' N positions are the tokens; mask, list, cnt,
+// idx_a and idx_b are not read.  RowsListed (region_maps.hip's region maps): the folds run over the positions t < cnt of the
+// direction's query image -- the same strided sums and tree, so that full masks give the in-order bits -- each result goes to token
+// list[t], and the thread that owns an off token (mask byte 0) stores its zeros: every element of local and contrib has one writer.
+// The mse count of a direction is B H D times the query image's own count, as pair_finish_kernel<true>'s.  A pair with an empty
+// image: score NaN, status 2, both maps zero.
+constexpr int MAP_FINISH_THREADS = 256;
+template <typename Rows>
+__global__ __launch_bounds__(MAP_FINISH_THREADS) void pair_map_finish_kernel(const float* __restrict__ part, const uint8_t* __restrict__ mask,
+                                                                             const int32_t* __restrict__ list, const int32_t* __restrict__ cnt,
+                                                                             const int32_t* __restrict__ idx_a, const int32_t* __restrict__ idx_b,
+                                                                             int BH, int N, int D, int mse, float* __restrict__ score,
+                                                                             float* __restrict__ local, float* __restrict__ contrib,
+                                                                             int32_t* __restrict__ status) {
+    constexpr int NT = MAP_FINISH_THREADS;
+    __shared__ double red[3][NT];
+    const int p = blockIdx.x, t = threadIdx.x;
+    const size_t plane = (size_t)BH * N;
+    int img[2] = {0, 0}, n[2] = {N, N};        // (listed) the directions' query images and their counts
+    if constexpr (Rows::LISTED) {
+        img[0] = idx_a[p]; img[1] = idx_b[p];
+        n[0] = cnt[img[0]]; n[1] = cnt[img[1]];
+        if (n[0] == 0 || n[1] == 0) {          // (uniform over the workgroup)
+            for (int i = t; i < 2 * N; i += NT) {
+                if (local) local[(size_t)p * 2 * N + i] = 0.f;
+                if (contrib) contrib[(size_t)p * 2 * N + i] = 0.f;
+            }
+            if (t == 0) {
+                score[p] = __builtin_nanf("");
+                if (status) status[p] = 2;
+            }
+            return;
+        }
+    }
+    double res = 0.0;
+    for (int dir = 0; dir < 2; ++dir) {
+        const float* pd = part + ((size_t)p * 2 + dir) * 3 * plane;
+        float* lo = local ? local + ((size_t)p * 2 + dir) * N : nullptr;
+        float* co = contrib ? contrib + ((size_t)p * 2 + dir) * N : nullptr;
+        const int nd = n[dir];
+        const int32_t* lst = nullptr;
+        if constexpr (Rows::LISTED) {
+            lst = list + (size_t)img[dir] * N;
+            const uint8_t* m = mask + (size_t)img[dir] * N;
+            for (int i = t; i < N; i += NT)
+                if (m[i] == 0) {
+                    if (lo) lo[i] = 0.f;
+                    if (co) co[i] = 0.f;
+                }
+        }
+        auto token = [&](int i) {                // the token of position i
+            if constexpr (Rows::LISTED) return (int)lst[i];
+            else return i;
+        };
+        auto fold = [&](int comp, int i) {
+            double a = 0.0;
+            for (int j = 0; j < BH; ++j) a += pd[comp * plane + (size_t)j * N + i];
+            return a;
+        };
+        // pass 1: local, and the direction's squared norms (cosine)
+        double x2t = 0.0, y2t = 0.0;
+        for (int i = t; i < nd; i += NT) {
+            const double a = fold(0, i);
+            if (mse) {                   // (mse folds no norms)
+                if (lo) lo[token(i)] = (float)direction_value(a, 0.0, 0.0, mse, (double)BH * D);
+            } else {
+                const double x2 = fold(1, i), y2 = fold(2, i);
+                x2t += x2; y2t += y2;
+                if (lo) lo[token(i)] = (float)direction_value(a, x2, y2, mse, (double)BH * D);
+            }
+        }
+        red[1][t] = x2t; red[2][t] = y2t;
+        __syncthreads();
+        for (int s = NT / 2; s > 0; s >>= 1) {
+            if (t < s) { red[1][t] += red[1][t + s]; red[2][t] += red[2][t + s]; }
+            __syncthreads();
+        }
+        const double den = direction_denominator(red[1][0], red[2][0], mse, (double)BH * nd * D);
+        // pass 2: contrib (the same fold again: the per-token sums are not kept), and the direction's total
+        double ct = 0.0;
+        for (int i = t; i < nd; i += NT) {
+            const double c = fold(0, i) / den;
+            ct += c;
+            if (co) co[token(i)] = (float)c;
+        }
+        __syncthreads();                 // (every thread has read red[1..2][0])
+        red[0][t] = ct;
+        __syncthreads();
+        for (int s = NT / 2; s > 0; s >>= 1) {
+            if (t < s) red[0][t] += red[0][t + s];
+            __syncthreads();
+        }
+        res += red[0][0];
+        __syncthreads();
+    }
+    if (t == 0) store_score(res, score + p, status ? status + p : nullptr);
+}
+
+// pair_map_finish_kernel over a's pairs at head dim D: its one launch site
+template <typename Rows>
+int launch_map_finish(const float* part, const uint8_t* mask, const int32_t* list, const int32_t* cnt, const PairArgs& a, int D,
+                      float* score, float* local, float* contrib, int32_t* status, hipStream_t s) {
+    hipLaunchKernelGGL(pair_map_finish_kernel<Rows>, dim3(a.n_pairs), dim3(MAP_FINISH_THREADS), 0, s, part, mask, list, cnt, a.idx_a, a.idx_b,
+                       a.B * a.H, a.N, D, a.similarity, score, local, contrib, status);
     DSIM_HIP_CHECK(hipGetLastError());
     return DSIM_OK;
 }

@@ -9,7 +9,7 @@
 //                      folds them (no float atomics => bit-reproducible scores).
 // pair_tail_kernel and pair_map_kernel name the in-order instantiations of tail_core.h's pair_tail_body (the listed one is
 // regions.hip's); the score matrix launches the in-order instantiation of tail_core.h's matrix_tail_kernel (the listed one is
-// region_matrix.hip's); the finish arithmetic, pair_finish_kernel and its launch are tail_core.h's too.  The launchers take PairArgs
+// region_matrix.hip's); the finish arithmetic, pair_finish_kernel, pair_map_finish_kernel and their launches are tail_core.h's too.  The launchers take PairArgs
 // or MatrixArgs (common.h).
 #include "tail_core.h"
 
@@ -61,74 +61,13 @@ int launch_matrix_t(const MatrixArgs& a, float* out, int32_t* status, hipStream_
 // The score of direction a->b splits over query tokens: cos(O_ab, O_aa) = sum_i dot_i / (|O_ab| |O_aa|) and
 // mse = sum_i sqd_i / (B H N D), where dot_i / sqd_i sum over the CFG batch, the heads and d at token i.
 // pair_map_kernel is pair_tail_body with the per-token epilogue: pair_tail_kernel's grid, attentions, rounding and products, so that
-// a pair's map contributions sum to its score.
+// a pair's map contributions sum to its score; the finish is tail_core.h's pair_map_finish_kernel with the rows in order.
 template <typename T, int D>
 __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void pair_map_kernel(const T* __restrict__ qg, const T* __restrict__ kg,
                                                         const T* __restrict__ vg, const int32_t* __restrict__ idx_a,
                                                         const int32_t* __restrict__ idx_b, int B, int H, int N,
                                                         float scale_log2, int mse, float* __restrict__ part) {
     pair_tail_body<T, D, true, RowsInOrder>(qg, kg, vg, nullptr, nullptr, idx_a, idx_b, B, H, N, scale_log2, mse, part);
-}
-
-// one workgroup per pair, both directions: per token, a fixed-order f64 fold of the B*H partials; over tokens, per-thread strided
-// sums and a fixed-order tree.  local: the token's own cosine (|.| of the token's vectors) or mean squared difference; contrib: its
-// share of the direction's score, so that 0.5 (sum contrib[0] + sum contrib[1]) is the pair's score (tail_core.h's finish
-// arithmetic, as pair_finish_kernel)
-constexpr int MAP_FINISH_THREADS = 256;
-__global__ __launch_bounds__(MAP_FINISH_THREADS) void pair_map_finish_kernel(const float* __restrict__ part, int BH, int N, int D, int mse,
-                                                                             float* __restrict__ score, float* __restrict__ local,
-                                                                             float* __restrict__ contrib, int32_t* __restrict__ status) {
-    constexpr int NT = MAP_FINISH_THREADS;
-    __shared__ double red[3][NT];
-    const int p = blockIdx.x, t = threadIdx.x;
-    const size_t plane = (size_t)BH * N;
-    double res = 0.0;
-    for (int dir = 0; dir < 2; ++dir) {
-        const float* pd = part + ((size_t)p * 2 + dir) * 3 * plane;
-        float* lo = local ? local + ((size_t)p * 2 + dir) * N : nullptr;
-        float* co = contrib ? contrib + ((size_t)p * 2 + dir) * N : nullptr;
-        auto fold = [&](int comp, int i) {
-            double a = 0.0;
-            for (int j = 0; j < BH; ++j) a += pd[comp * plane + (size_t)j * N + i];
-            return a;
-        };
-        // pass 1: local, and the direction's squared norms (cosine)
-        double x2t = 0.0, y2t = 0.0;
-        for (int i = t; i < N; i += NT) {
-            const double a = fold(0, i);
-            if (mse) {                   // (mse folds no norms)
-                if (lo) lo[i] = (float)direction_value(a, 0.0, 0.0, mse, (double)BH * D);
-            } else {
-                const double x2 = fold(1, i), y2 = fold(2, i);
-                x2t += x2; y2t += y2;
-                if (lo) lo[i] = (float)direction_value(a, x2, y2, mse, (double)BH * D);
-            }
-        }
-        red[1][t] = x2t; red[2][t] = y2t;
-        __syncthreads();
-        for (int s = NT / 2; s > 0; s >>= 1) {
-            if (t < s) { red[1][t] += red[1][t + s]; red[2][t] += red[2][t + s]; }
-            __syncthreads();
-        }
-        const double den = direction_denominator(red[1][0], red[2][0], mse, (double)BH * N * D);
-        // pass 2: contrib (the same fold again: the per-token sums are not kept), and the direction's total
-        double ct = 0.0;
-        for (int i = t; i < N; i += NT) {
-            const double c = fold(0, i) / den;
-            ct += c;
-            if (co) co[i] = (float)c;
-        }
-        __syncthreads();                 // (every thread has read red[1..2][0])
-        red[0][t] = ct;
-        __syncthreads();
-        for (int s = NT / 2; s > 0; s >>= 1) {
-            if (t < s) red[0][t] += red[0][t + s];
-            __syncthreads();
-        }
-        res += red[0][0];
-        __syncthreads();
-    }
-    if (t == 0) store_score(res, score + p, status ? status + p : nullptr);
 }
 
 template <typename T>
@@ -139,10 +78,7 @@ int launch_maps_t(const PairArgs& a, float* score, float* local, float* contrib,
                                                           (const T*)a.q, (const T*)a.k, (const T*)a.v, a.idx_a, a.idx_b, a.B, a.H, a.N,
                                                           scale_log2_of(Dc), a.similarity, (float*)a.scratch);
         if (st != DSIM_OK) return st;
-        hipLaunchKernelGGL(pair_map_finish_kernel, dim3(a.n_pairs), dim3(MAP_FINISH_THREADS), 0, s, (const float*)a.scratch, a.B * a.H,
-                           a.N, Dc, a.similarity, score, local, contrib, status);
-        DSIM_HIP_CHECK(hipGetLastError());
-        return DSIM_OK;
+        return launch_map_finish<RowsInOrder>((const float*)a.scratch, nullptr, nullptr, nullptr, a, Dc, score, local, contrib, status, s);
     });
 }
 

@@ -388,6 +388,24 @@ class DiffSim(Scorer):
                                                _norm_layer(target_layer), target_step, seed, similarity)
 
     @torch.no_grad()
+    def region_similarity_maps(self, image_A, image_B, mask_A, mask_B, img_size, prompt, target_block, target_layer, target_step,
+                               seed="2333", similarity="cosine"):
+        """:meth:`region_score` of one image pair with its per-token terms on both images' grids: a
+        :class:`~diffsim_amd.maps.SimilarityMaps` of one pair whose attentions ran over the masked tokens alone (zeros at the off
+        tokens; ``.mask`` holds the two token masks).  Masks as :meth:`region_score` takes them."""
+        return maps.score_path_pair_maps(self, [(image_A, image_B)], img_size, prompt, target_block, _norm_layer(target_layer),
+                                         target_step, seed, similarity, masks=[(mask_A, mask_B)])
+
+    @torch.no_grad()
+    def region_alignment(self, image_A, image_B, mask_A, mask_B, img_size, prompt, target_block, target_layer, target_step,
+                         seed="2333"):
+        """Which token of the other image's region each token of a region attends to: an :class:`~diffsim_amd.align.Alignment` of
+        one pair whose softmaxes ran over the other image's masked tokens alone (off tokens: match -1; ``.mask`` holds the two
+        token masks).  Masks as :meth:`region_score` takes them."""
+        return align.score_path_pair_alignment(self, [(image_A, image_B)], img_size, prompt, target_block, _norm_layer(target_layer),
+                                               target_step, seed, masks=[(mask_A, mask_B)])
+
+    @torch.no_grad()
     def text_region_score(self, image_A, image_B, img_size, prompt, target_block, target_layer, target_step, seed="2333",
                           similarity="cosine", words=None, rel_threshold=1.0):
         """:meth:`diffsim` of the part of each image the prompt names (textattn.py; the reference's declared and unbuilt

@@ -200,6 +200,21 @@ class diffsim_xl(Scorer):
                                                target_layer, target_step, seed, similarity, hip_vae=False)
 
     @torch.no_grad()
+    def region_similarity_maps(self, image_A, image_B, mask_A, mask_B, img_size, prompt, target_block, target_layer, target_step,
+                               seed, similarity):
+        """:meth:`region_score` with its per-token terms on both images' grids (a maps.SimilarityMaps of one pair over the masked
+        tokens; ``.mask`` holds the two token masks)."""
+        return maps.score_path_pair_maps(self, [(image_A, image_B)], img_size, prompt, target_block, target_layer, target_step, seed,
+                                         similarity, masks=[(mask_A, mask_B)], hip_vae=False)
+
+    @torch.no_grad()
+    def region_alignment(self, image_A, image_B, mask_A, mask_B, img_size, prompt, target_block, target_layer, target_step, seed):
+        """Which token of the other image's region each token of a region attends to (an align.Alignment of one pair over the
+        masked tokens; ``.mask`` holds the two token masks)."""
+        return align.score_path_pair_alignment(self, [(image_A, image_B)], img_size, prompt, target_block, target_layer, target_step,
+                                               seed, masks=[(mask_A, mask_B)], hip_vae=False)
+
+    @torch.no_grad()
     def text_region_score(self, image_A, image_B, img_size, prompt, target_block, target_layer, target_step, seed, similarity,
                           words=None, rel_threshold=1.0):
         """:meth:`diffsim_score` of the part of each image the prompt names (textattn.py): each image's region is the tokens whose

@@ -687,6 +687,34 @@ def pair_score_regions(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: 
     return _with_extras(out, status, counts)
 
 
+def pair_score_maps_regions(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: torch.Tensor, idx_a: torch.Tensor,
+                            idx_b: torch.Tensor, heads: int, similarity: str = "cosine", return_status: bool = False,
+                            return_counts: bool = False):
+    """The region score kept per query token (dsim_pair_score_maps_regions): pair_score_maps for pair_score_regions.  q,k,v, mask,
+    idx: as pair_score_regions.  Returns f32 device tensors (score (n,), local (n, 2, N), contrib (n, 2, N)) on the full token
+    grid: at an on token, local is the token's own cosine (or mean squared difference) inside the region attention and contrib
+    its term of the region score, score = 0.5 * contrib.sum((1, 2)); at an off token both are exactly 0.  return_status: also an
+    int32 (n,) tensor, 1 where the score is NaN / infinite, 2 where a region of the pair is empty (score NaN, maps zero);
+    return_counts: also the int32 (n_feat,) region sizes."""
+    _require_cuda(q, k, v, mask, idx_a, idx_b)
+    sim = _similarity_code(similarity)
+    B, N, D = _check_features((q, k, v), heads, k.shape == q.shape == v.shape, _PAIR_MSGS, (idx_a, idx_b))
+    _check_region_mask(mask, q.shape[0], N)
+    mask = mask.view(torch.uint8)
+    n_feat, n_pairs = q.shape[0], idx_a.numel()
+    dev = q.device
+    score = torch.empty(n_pairs, dtype=torch.float32, device=dev)
+    local = torch.empty((n_pairs, 2, N), dtype=torch.float32, device=dev)
+    contrib = torch.empty((n_pairs, 2, N), dtype=torch.float32, device=dev)
+    status = _i32(n_pairs, dev, return_status)
+    counts = _i32(n_feat, dev, return_counts)
+    _tail_call(dev, "pair_score_maps_regions", (n_feat, n_pairs, B, heads, N, D),
+               f"no region maps for n_feat={n_feat} n_pairs={n_pairs} B={B} H={heads} N={N} D={D}", q.data_ptr(), k.data_ptr(),
+               v.data_ptr(), mask.data_ptr(), n_feat, idx_a.data_ptr(), idx_b.data_ptr(), n_pairs, B, heads, N, D, _TORCH2DSIM[q.dtype],
+               sim, score.data_ptr(), local.data_ptr(), contrib.data_ptr(), _ptr(status), _ptr(counts))
+    return (score, local, contrib) + tuple(e for e in (status, counts) if e is not None)
+
+
 TEXT_WANT = ("attn", "saliency", "mask", "counts", "status")
 
 
@@ -781,6 +809,49 @@ def pair_align(q: torch.Tensor, k: torch.Tensor, idx_a: torch.Tensor, idx_b: tor
                    int(grid_w), match[sl].data_ptr(), weight[sl].data_ptr(), expect[sl].data_ptr(),
                    _ptr(None if attn is None else attn[sl]), _ptr(None if status is None else status[sl]))
     return (match, weight, expect) + ((attn,) if return_attention else ()) + ((status,) if return_status else ())
+
+
+def pair_align_regions(q: torch.Tensor, k: torch.Tensor, mask: torch.Tensor, idx_a: torch.Tensor, idx_b: torch.Tensor, heads: int,
+                       grid_w: Optional[int] = None, return_attention: bool = False, return_status: bool = False,
+                       return_counts: bool = False):
+    """Token alignments between two regions (dsim_pair_align_regions): pair_align with the softmax of query token i in R_a taken
+    over the keys j in R_b only.  q,k, idx, grid_w: as pair_align; mask: as pair_score_regions.  Returns device tensors (match
+    int32 (n, 2, N), weight f32 (n, 2, N), expect f32 (n, 2, N, 2)) on the full token grid: match and expect are token indices
+    and (row, col) coordinates of the other image's full grid.  Off query tokens carry match -1, weight 0, expect (-1, -1).
+    return_attention: also the probabilities, f32 (n, 2, N, N), zero outside R_a x R_b, computed in calls of fewer than 2 GiB
+    each; return_status: also an int32 (n,) tensor, 1 where a pair has a non-finite probability, 2 where a region of the pair is
+    empty (every row then carries the off values); return_counts: also the int32 (n_feat,) region sizes."""
+    _require_cuda(q, k, mask, idx_a, idx_b)
+    B, N, D = _check_features((q, k), heads, k.shape == q.shape, _PAIR_MSGS, (idx_a, idx_b))
+    _check_region_mask(mask, q.shape[0], N)
+    mask = mask.view(torch.uint8)
+    if grid_w is None:
+        grid_w = math.isqrt(N)
+        if grid_w * grid_w != N:
+            raise _lib.DsimError(f"{N} tokens do not form a square grid: name grid_w")
+    n_feat, n_pairs = q.shape[0], idx_a.numel()
+    dev = q.device
+    match = torch.empty((n_pairs, 2, N), dtype=torch.int32, device=dev)
+    weight = torch.empty((n_pairs, 2, N), dtype=torch.float32, device=dev)
+    expect = torch.empty((n_pairs, 2, N, 2), dtype=torch.float32, device=dev)
+    status = _i32(n_pairs, dev, return_status)
+    counts = _i32(n_feat, dev, return_counts)
+    attn = None
+    step = _ALIGN_PAIRS
+    if return_attention:
+        step = min(step, _ATTN_BYTES // (2 * N * N * 4))
+        if step < 1:
+            raise _lib.DsimError(f"the attention of one pair of {N} tokens does not fit 2 GiB")
+        attn = torch.empty((n_pairs, 2, N, N), dtype=torch.float32, device=dev)
+    for i0 in range(0, n_pairs, step):
+        n = min(step, n_pairs - i0)
+        sl = slice(i0, i0 + n)
+        _tail_call(dev, "pair_align_regions", (n_feat, n, B, heads, N, D),
+                   f"no region alignments for n_feat={n_feat} n_pairs={n} B={B} H={heads} N={N} D={D}", q.data_ptr(), k.data_ptr(),
+                   mask.data_ptr(), n_feat, idx_a[sl].data_ptr(), idx_b[sl].data_ptr(), n, B, heads, N, D, _TORCH2DSIM[q.dtype],
+                   int(grid_w), match[sl].data_ptr(), weight[sl].data_ptr(), expect[sl].data_ptr(),
+                   _ptr(None if attn is None else attn[sl]), _ptr(None if status is None else status[sl]), _ptr(counts))
+    return (match, weight, expect) + tuple(e for e in (attn, status, counts) if e is not None)
 
 
 def score_matrix_workspace_bytes(n_a: int, n_b: int, B: int, heads: int, N: int, D: int, dtype: torch.dtype) -> int:

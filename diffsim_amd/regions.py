@@ -94,6 +94,17 @@ def _flat_masks(m, n: int, grid: Tuple[int, int], name: str) -> torch.Tensor:
     return t
 
 
+def pair_token_masks(scorer, tap, latent_side: int, n: int, maskA, maskB):
+    """((h, w), (n, 2, N) bool on the scorer's device) for n pairs at a tap: maskA / maskB as ``score_latent_pair_regions`` takes
+    them, either may be None (whole images).  Row [i, 0] is image A_i's mask and [i, 1] image B_i's: a chunk's rows interleave as
+    its images do (``Scorer.pair_chunks``)."""
+    grid = tap_grid(scorer, tap, latent_side)
+    whole = torch.ones((n, grid[0] * grid[1]), dtype=torch.bool)
+    mA = whole if maskA is None else _flat_masks(maskA, n, grid, "maskA")
+    mB = whole if maskB is None else _flat_masks(maskB, n, grid, "maskB")
+    return grid, torch.stack([mA, mB], dim=1).to(scorer.device)
+
+
 @torch.no_grad()
 def score_latent_pair_regions(scorer, latA, latB, noiseA, noiseB, maskA, maskB, prompt, target_block="up_blocks", target_layer=0,
                               target_step=600, similarity="cosine", batch_pairs: Optional[int] = None) -> torch.Tensor:

@@ -362,6 +362,49 @@ int    dsim_score_matrix_regions(const void* qa, const void* ka, const void* va,
                                  int32_t* counts /* NULL or [n_a + n_b] */,
                                  void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- region maps: the region score per query token (additive to ABI v7) ---------------------------------------------------------
+ * dsim_pair_score_maps for dsim_pair_score_regions: the region tail's own attentions, rounding and products, kept per query token.
+ * Outputs lie on the full token grid.  For direction 0 (image idx_a[p] over idx_b[p]; direction 1 the mirror) and an on token i:
+ * local[p][0][i] is the token's own cosine (or its mean squared difference over the B H D values) and contrib[p][0][i] its term of
+ * the direction's value, so that 0.5 (sum contrib[p][0] + sum contrib[p][1]) is the pair's region score; the mse count of a direction
+ * is B H D times the query image's own |R|.  Off tokens: local = contrib = 0 exactly (the caller holds the mask).
+ *   q,k,v, mask, idx_a, idx_b, similarity, counts : as dsim_pair_score_regions
+ *   score       : device f32 [n_pairs]
+ *   local, contrib : NULL, or device f32 [n_pairs][2][N] each
+ *   status      : NULL, or device int32 [n_pairs]: 0, 1 where the score is NaN or infinite, 2 where a region of the pair is empty
+ *                 (score NaN, both maps all zero; the other pairs of the call are not affected)
+ * With every region full the outputs are dsim_pair_score_maps' bits.  Deterministic, no atomics; rows outside a region are never
+ * read.  Refusals as dsim_pair_score_regions, and n_feat N >= 2^31. */
+size_t dsim_pair_score_maps_regions_workspace_bytes(int n_feat, int n_pairs, int B, int H, int N, int D);
+int    dsim_pair_score_maps_regions(const void* q, const void* k, const void* v, const uint8_t* mask /* [n_feat][N] */,
+                                    int n_feat, const int32_t* idx_a, const int32_t* idx_b, int n_pairs,
+                                    int B, int H, int N, int D, int dtype, int similarity,
+                                    float* score, float* local, float* contrib,
+                                    int32_t* status /* NULL or [n_pairs]: 0, 1 non-finite, 2 empty region */,
+                                    int32_t* counts /* NULL or [n_feat] */, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- region alignments: the cross-attention of one region over the other (additive to ABI v7) -------------------------------------
+ * dsim_pair_align with the background out of the softmax.  For direction a->b and query token i in R_a,
+ * Pm[i][j] = softmax over j in R_b ONLY of Q_a[i] . K_b[j] / sqrt(D), averaged over the B CFG halves and the H heads (dsim_pair_align's
+ * arithmetic on the regions' rows in ascending token order).  Outputs lie on the full grid; for an on query token i:
+ *   match  [n_pairs][2][N] int32 : argmax over j in R_b, as the token index on b's full grid (ties: the lowest j)
+ *   weight [n_pairs][2][N] f32   : that probability
+ *   expect [n_pairs][2][N][2] f32: sum_j Pm[i][j] (j / grid_w, j % grid_w), full-grid coordinates
+ *   attn   [n_pairs][2][N][N] f32: Pm, zero outside R_a x R_b; fewer than 2 GiB per call
+ * each of which may be NULL.  Off query tokens: match -1, weight 0, expect (-1, -1).
+ *   status      : NULL, or device int32 [n_pairs]: 0, 1 where a probability is non-finite, 2 where a region of the pair is empty
+ *                 (every row of the pair then carries the off values)
+ *   counts      : NULL, or device int32 [n_feat]: |R_i|
+ * With every region full the outputs are dsim_pair_align's bits.  Deterministic, no atomics; rows outside a region are never read.
+ * Refusals as dsim_pair_align (N % grid_w, an attn of 2 GiB or more) and dsim_pair_score_regions (n_feat < 1, n_feat N >= 2^31). */
+size_t dsim_pair_align_regions_workspace_bytes(int n_feat, int n_pairs, int B, int H, int N, int D);
+int    dsim_pair_align_regions(const void* q, const void* k, const uint8_t* mask /* [n_feat][N] */, int n_feat,
+                               const int32_t* idx_a, const int32_t* idx_b, int n_pairs,
+                               int B, int H, int N, int D, int dtype, int grid_w,
+                               int32_t* match, float* weight, float* expect, float* attn,
+                               int32_t* status /* NULL or [n_pairs]: 0 | 1 | 2 */, int32_t* counts /* NULL or [n_feat] */,
+                               void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- text attention maps and text-guided regions: the prompt's cross-attention picks the tokens --------------------------------
  * What `--use_text_attn` (argprocess.py:17 of the reference) names.  For image i, on the conditional CFG half only (batch element
  * e = 2 i + 1 of xq; context row 1 when n_kv == 2, row e when n_kv == 2 n_images):
