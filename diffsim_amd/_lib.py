@@ -186,6 +186,12 @@ SYMBOLS = {
     "dsim_vit_qkv_taps": (_i, [_vp, _vp, _i, _i, C.POINTER(_i), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _vp, _sz, _vp]),
     "dsim_pair_score_proj_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
     "dsim_pair_score_proj": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dsim_attn_features_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i, _i]),
+    "dsim_attn_features": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
+    "dsim_feature_pair_score_workspace_bytes": (_sz, [_i, _i, _i]),
+    "dsim_feature_pair_score": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "dsim_feature_matrix_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "dsim_feature_matrix": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "dsim_pair_score_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "dsim_pair_score": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "dsim_pair_score_status": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),

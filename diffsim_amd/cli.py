@@ -1,6 +1,6 @@
 """Command-line driver: the reference's benchmark loops on the MI355X engine.
 
-``python -m diffsim_amd --dataset cute|nights|sref --metric diffsim|diffsim_xl|dit|clip_cross|dino_cross --model_path <dir> --image_path <dir> ...``
+``python -m diffsim_amd --dataset cute|nights|sref --metric diffsim|diffsim_xl|dit|clip_cross|dino_cross|diffeats|dinofeats --model_path <dir> --image_path <dir> ...``
 
 Flags of the reference drivers (``/root/reference/argprocess.py:5-18``) keep their names, meaning and defaults;
 ``--dataset`` selects which of the reference's loops runs (``cute_main.py:48-226``, ``night_main.py:24-173`` or
@@ -20,8 +20,9 @@ from typing import List, Optional, Tuple
 
 METRICS = ["diffsim", "diffsim_xl", "clip_i", "clip_cross", "dino", "dinov1", "dino_cross", "cute", "lpips", "gram",
            "diffeats", "clipfeats", "dinofeats", "ensemble", "dit"]
-ENGINE_METRICS = ("diffsim", "diffsim_xl", "dit", "clip_cross", "dino_cross")
+ENGINE_METRICS = ("diffsim", "diffsim_xl", "dit", "clip_cross", "dino_cross", "diffeats", "dinofeats")
 VIT_METRICS = ("clip_cross", "dino_cross")      # DiffSim's method on a ViT tower (vit.py): no VAE, no noise, no prompt, no token grid
+FEATURE_METRICS = ("diffeats", "dinofeats")     # the cosine of the tapped layer's own features (feats.py), the paper's ablation
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -120,7 +121,19 @@ def build_parser() -> argparse.ArgumentParser:
 def arg_parse(argv=None):
     p = build_parser()
     args = p.parse_args(argv)
-    region_out = [f for f, on in (("--save_region_maps", args.save_region_maps), ("--save_region_matches", args.save_region_matches)) if on]
+    if args.metric in FEATURE_METRICS:
+        if args.similarity != "cosine":
+            p.error(f"--metric {args.metric} needs --similarity cosine: its score is always a cosine, as in the reference (which "
+                    "ignores the flag), and the mse counting rule would read it backwards")
+        for flag, on in (("--mask_path", args.mask_path is not None), ("--query_mask_path", args.query_mask_path is not None),
+                         ("--gallery_mask_path", args.gallery_mask_path is not None), ("--text_attn", args.text_attn is not None),
+                         ("--save_maps", args.save_maps), ("--save_matches", args.save_matches),
+                         ("--save_region_maps", args.save_region_maps), ("--save_region_matches", args.save_region_matches),
+                         ("--fp8_attention", args.fp8_attention)):
+            if on:
+                p.error(f"{flag}: --metric {args.metric} is the plain cosine of the tapped layer's features: it has no regions, maps, "
+                        "alignments or fp8 attention")
+    region_out =[f for f, on in (("--save_region_maps", args.save_region_maps), ("--save_region_matches", args.save_region_matches)) if on]
     for flag in region_out:
         if args.dataset != "retrieval" or (args.query_mask_path is None and args.gallery_mask_path is None):
             p.error(f"{flag} writes the per-token outputs of region rankings: it needs --dataset retrieval and --query_mask_path and / "
@@ -274,6 +287,15 @@ def build_scorer(args):
     if args.metric in VIT_METRICS:
         print(f"--metric {args.metric}: --image_size is not consulted (the model's image processor decides: resize, then a centre crop)")
         return (loader.load_clip_cross if args.metric == "clip_cross" else loader.load_dino_cross)(args.model_path, args.dtype, dev)
+    if args.metric == "dinofeats":
+        from .feats import FeatureView
+        print("--metric dinofeats: --image_size is not consulted (the model's image processor decides: resize, then a centre crop)")
+        return FeatureView(loader.load_dino_cross(args.model_path, args.dtype, dev))
+    if args.metric == "diffeats":
+        from .feats import FeatureView
+        print("--metric diffeats: --target_layer N is taken literally, as in the reference (--metric diffsim turns a single value "
+              "into layer 0)")
+        return FeatureView(loader.load_diffsim(args.model_path, args.dtype, dev, nd, dedup_cfg=args.dedup_cfg))
     if args.metric == "diffsim":
         return loader.load_diffsim(args.model_path, args.dtype, dev, nd, dedup_cfg=args.dedup_cfg)
     if args.metric == "diffsim_xl":
@@ -324,7 +346,7 @@ def cli_taps(args, scorer):
     from . import config as C
     from .sweep import parse_tap_specs
     cfg = getattr(scorer, "cfg", None) or {"diffsim": C.SD15, "diffsim_xl": C.SDXL, "dit": C.DIT_XL2, "clip_cross": C.CLIP_B32,
-                                           "dino_cross": C.DINOV2_S14}[args.metric]
+                                           "dino_cross": C.DINOV2_S14, "diffeats": C.SD15, "dinofeats": C.DINOV2_S14}[args.metric]
     try:
         return parse_tap_specs(args.taps, args.metric, cfg)
     except ValueError as e:

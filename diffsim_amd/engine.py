@@ -904,6 +904,99 @@ def score_matrix_regions(fa, fb, mask_a: torch.Tensor, mask_b: torch.Tensor, hea
     return _with_extras(out, status, counts)
 
 
+# ---- feature-cosine metrics (diffeats, dinofeats): the tapped self-attention's own output, its pair cosine and Gram matrix -------
+_FEAT_IMAGES = 65535                 # dsim_attn_features carries the images on a grid axis: more are chunked
+_FEAT_PAIRS = 65535                  # ... and dsim_feature_pair_score the pairs
+_FEAT_BYTES = (1 << 31) - 1          # one call's projection slab stays under 2 GiB
+
+
+def attn_features_workspace_bytes(n: int, B: int, heads: int, N: int, D: int, dtype: torch.dtype, proj: bool) -> int:
+    return int(_lib.lib().dsim_attn_features_workspace_bytes(n, B, heads, N, D, B * N * heads * D, _TORCH2DSIM.get(dtype, -1), int(proj)))
+
+
+def attn_features(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, w_out: Optional[torch.Tensor] = None,
+                  bias: Optional[torch.Tensor] = None, minmax: bool = False):
+    """The tapped self-attention's own output per image (dsim_attn_features).  q,k,v: contiguous [n][B][N][H*D] of one shape.
+    w_out / bias (both or neither): the layer's output projection, [C][C] in the features' dtype and f32 [C], C = H*D.  minmax:
+    min-max normalise each image over all its values (metrics/diffeats.py:136-140).  Returns (feats [n][B][N][C] in q's dtype,
+    stats f32 [n][4] = sum of squares, min, max, 0); an image's rows do not depend on the other images."""
+    _require_cuda(q, k, v, *(t for t in (w_out, bias) if t is not None))
+    B, N, D = _check_features((q, k, v), heads, k.shape == q.shape == v.shape, _PAIR_MSGS)
+    Cc, n, dt = heads * D, q.shape[0], _TORCH2DSIM[q.dtype]
+    if (w_out is None) != (bias is None):
+        raise _lib.DsimError("w_out and bias come together")
+    if w_out is not None and (w_out.dtype != q.dtype or tuple(w_out.shape) != (Cc, Cc) or bias.dtype != torch.float32
+                              or tuple(bias.shape) != (Cc,) or not (w_out.is_contiguous() and bias.is_contiguous())):
+        raise _lib.DsimError(f"w_out must be contiguous {q.dtype} ({Cc}, {Cc}) and bias float32 ({Cc},)")
+    L = B * N * Cc
+    feats = torch.empty_like(q)
+    stats = torch.empty((n, 4), dtype=torch.float32, device=q.device)
+    step = max(1, min(_FEAT_IMAGES, _FEAT_BYTES // (L * q.element_size())))
+    for i0 in range(0, n, step):
+        m = min(step, n - i0)
+        sl = slice(i0, i0 + m)
+        _tail_call(q.device, "attn_features", (m, B, heads, N, D, L, dt, int(w_out is not None)),
+                   f"no attention features for n={m} B={B} H={heads} N={N} D={D}", q[sl].data_ptr(), k[sl].data_ptr(), v[sl].data_ptr(),
+                   m, B, heads, N, D, L, dt, _ptr(w_out), _ptr(bias), int(bool(minmax)), feats[sl].data_ptr(), stats[sl].data_ptr())
+    return feats, stats
+
+
+def _check_feats(feats: torch.Tensor, stats: torch.Tensor, what: str = "feats") -> int:
+    """attn_features' outputs as the consumers take them: [n][...] contiguous of the three dtypes, f32 [n][4]; the image length L"""
+    if feats.dtype not in _TORCH2DSIM or feats.ndim < 2 or not feats.is_contiguous():
+        raise _lib.DsimError(f"{what} must be contiguous [n][...] of dtype float32, bfloat16 or float16")
+    if stats.dtype != torch.float32 or tuple(stats.shape) != (feats.shape[0], 4) or not stats.is_contiguous():
+        raise _lib.DsimError(f"the stats of {what} must be contiguous float32 ({feats.shape[0]}, 4)")
+    return feats[0].numel()
+
+
+def feature_pair_score_workspace_bytes(n_pairs: int, L: int, dtype: torch.dtype) -> int:
+    return int(_lib.lib().dsim_feature_pair_score_workspace_bytes(n_pairs, L, _TORCH2DSIM.get(dtype, -1)))
+
+
+def feature_pair_score(feats: torch.Tensor, stats: torch.Tensor, idx_a: torch.Tensor, idx_b: torch.Tensor, return_status: bool = False):
+    """The cosine of the flattened features of images idx_a[p] and idx_b[p] (dsim_feature_pair_score), eps 1e-8.  feats, stats:
+    attn_features' outputs; idx: contiguous int32 cuda [n_pairs].  return_status: also an int32 [n_pairs] tensor, 1 where the score
+    is NaN / infinite."""
+    _require_cuda(feats, stats, idx_a, idx_b)
+    L = _check_feats(feats, stats)
+    if idx_a.dtype != torch.int32 or idx_b.dtype != torch.int32 or idx_a.numel() != idx_b.numel():
+        raise _lib.DsimError("pair indices must be int32 and of one length")
+    if not (idx_a.is_contiguous() and idx_b.is_contiguous()):
+        raise _lib.DsimError("features and indices must be contiguous")
+    n_pairs, dt = idx_a.numel(), _TORCH2DSIM[feats.dtype]
+    out = torch.empty(n_pairs, dtype=torch.float32, device=feats.device)
+    status = _i32(n_pairs, feats.device, return_status)
+    for i0 in range(0, n_pairs, _FEAT_PAIRS):
+        m = min(_FEAT_PAIRS, n_pairs - i0)
+        sl = slice(i0, i0 + m)
+        _tail_call(feats.device, "feature_pair_score", (m, L, dt), f"no feature pair score for n_pairs={m} L={L}", feats.data_ptr(),
+                   stats.data_ptr(), idx_a[sl].data_ptr(), idx_b[sl].data_ptr(), m, L, dt, out[sl].data_ptr(),
+                   _ptr(None if status is None else status[sl]))
+    return (out, status) if return_status else out
+
+
+def feature_matrix_workspace_bytes(n_a: int, n_b: int, L: int, dtype: torch.dtype) -> int:
+    return int(_lib.lib().dsim_feature_matrix_workspace_bytes(n_a, n_b, L, _TORCH2DSIM.get(dtype, -1)))
+
+
+def feature_matrix(fa, fb, return_status: bool = False):
+    """Every image of set A against every image of set B (dsim_feature_matrix).  fa, fb: (feats, stats) of attn_features, one
+    dtype and image length.  Returns the (n_a, n_b) f32 device tensor of cosines; a cell depends on its two images alone and is
+    close to, not bit-equal to, feature_pair_score of them.  return_status: also an int32 (n_a, n_b) tensor, 1 where NaN / infinite."""
+    (xa, sa), (xb, sb) = fa, fb
+    _require_cuda(xa, sa, xb, sb)
+    L = _check_feats(xa, sa, "set A's feats")
+    if _check_feats(xb, sb, "set B's feats") != L or xb.dtype != xa.dtype:
+        raise _lib.DsimError("both sets' features must share dtype and image length")
+    n_a, n_b, dt = xa.shape[0], xb.shape[0], _TORCH2DSIM[xa.dtype]
+    out = torch.empty((n_a, n_b), dtype=torch.float32, device=xa.device)
+    status = _i32((n_a, n_b), xa.device, return_status)
+    _tail_call(xa.device, "feature_matrix", (n_a, n_b, L, dt), f"no feature matrix for n_a={n_a} n_b={n_b} L={L}", xa.data_ptr(),
+               sa.data_ptr(), n_a, xb.data_ptr(), sb.data_ptr(), n_b, L, dt, out.data_ptr(), _ptr(status))
+    return _with_extras(out, status)
+
+
 # ---- single-operator entry points (kernel-level parity tests) -----------------------------------
 def op_linear(x, w, bias=None, residual=None, geglu=False):
     L = _lib.lib()

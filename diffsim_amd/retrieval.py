@@ -12,6 +12,9 @@ Query features are computed once and kept; the gallery runs in chunks of the sco
 With ``masks_a`` / ``masks_b`` every image carries a token mask on the tap's grid and the matrix is the region score matrix
 (``engine.score_matrix_regions``): cell (i, j) is ``regions.score_latent_pair_regions`` of that pair -- the masked object is
 retrieved, the background takes part in no softmax -- at the same n_a + n_b forwards.
+
+A scorer with a matrix tail of its own (``Scorer.matrix_tail``: the feature-cosine metrics of ``feats.py``) ranks through it: what the
+query set contributes is computed once per call, each gallery chunk's once, and one ``engine.feature_matrix`` per chunk.
 """
 from __future__ import annotations
 
@@ -79,7 +82,10 @@ def score_latent_matrix(scorer, latA, latB, noiseA, noiseB, prompt, target_block
     nB = noiseB.to(dev, torch.float32)
     n_a, n_b = latA.shape[0], latB.shape[0]
     tap = scorer.tap_of(target_block, target_layer)
-    if getattr(scorer, "pair_tail", lambda tap: None)(tap) is not None:
+    mtail = getattr(scorer, "matrix_tail", lambda tap: None)(tap)
+    if mtail is not None and (masks_a is not None or masks_b is not None):
+        raise DsimError(f"{type(scorer).__name__} ranks with a matrix tail of its own (Scorer.matrix_tail): it has no region matrix")
+    if mtail is None and getattr(scorer, "pair_tail", lambda tap: None)(tap) is not None:
         raise DsimError(f"{type(scorer).__name__} scores pairs with a tail of its own (Scorer.pair_tail): there is no score matrix "
                         "for it yet (clip_cross needs a projected matrix); score pairs or triplets instead")
     prompt = scorer.bind_prompt(prompt, n_a, "queries")             # (one prompt of the call)
@@ -99,6 +105,9 @@ def score_latent_matrix(scorer, latA, latB, noiseA, noiseB, prompt, target_block
         grid = tap_grid(scorer, tap, latA.shape[-1])
         masks_a, masks_b = _set_masks(masks_a, n_a, grid, dev, "masks_a"), _set_masks(masks_b, n_b, grid, dev, "masks_b")
     workspace_bytes = score_matrix_regions_workspace_bytes if masked else score_matrix_workspace_bytes
+    if mtail is not None:
+        workspace_bytes = mtail.workspace_bytes
+        ga = mtail.features(fa, heads)          # the query set's share of every chunk's matrix, once per call
     try:
         free, _total = torch.cuda.mem_get_info(dev)
         while chunk > 1 and workspace_bytes(n_a, chunk, B, heads, N, HD // heads, fa[0].dtype) > WORKSPACE_SHARE * free:
@@ -108,7 +117,9 @@ def score_latent_matrix(scorer, latA, latB, noiseA, noiseB, prompt, target_block
     for j0 in range(0, n_b, chunk):
         j1 = min(n_b, j0 + chunk)
         fb = _features(scorer, latB[j0:j1], nB, prompt, tap, target_step, batch)
-        if masked:
+        if mtail is not None:
+            s, st = mtail.matrix(ga, mtail.features(fb, heads))
+        elif masked:
             s, st = score_matrix_regions(fa, fb, masks_a, masks_b[j0:j1], heads, similarity, return_status=True)
             st = st != 0
         else:

@@ -132,6 +132,13 @@ class Scorer:
         plain DiffSim tail (the batched paths then call their own module's binding of it)."""
         return None
 
+    def matrix_tail(self, tap):
+        """The matrix tail of the kind at `tap` (retrieval.score_latent_matrix): an object with .features((q, k, v), heads) -> what
+        a set of images contributes, computed once per set, .matrix(fa, fb) -> ((n_a, n_b) scores, int32 status) and
+        .workspace_bytes(n_a, n_b, B, heads, N, D, dtype); None: engine.score_matrix on the sets' q, k, v (a kind with a pair tail
+        of its own and no matrix tail has no score matrix)."""
+        return None
+
     # ---- batching facts
     mixes_prompts = True                    # whether one engine batch may carry several prompts (group_key)
     per_row_prompts = False                 # whether a call takes a prompt per row (a context table in the engine)

@@ -55,7 +55,7 @@ def parse_tap_specs(specs: Sequence[str], metric: str, cfg=None):
             if block != "blocks" or len(vals) != 1:
                 raise ValueError(f"tap {s!r}: DiT taps are blocks:LAYER")
             tap = vals[0]
-        elif metric in ("clip_cross", "dino_cross"):
+        elif metric in ("clip_cross", "dino_cross", "dinofeats"):
             if block != "layers" or len(vals) != 1:
                 raise ValueError(f"tap {s!r}: ViT taps are layers:LAYER")
             tap = vals[0]

@@ -221,25 +221,29 @@ class _ViTScore(Scorer):
         return eng.qkv_taps(pixels.to(self.device, torch.float32).contiguous(), [int(l) for l in layers])
 
     @torch.no_grad()
-    def score_pixel_pairs(self, pixA, pixB, target_layer: int, similarity="cosine", batch_pairs: Optional[int] = None) -> torch.Tensor:
-        """(n,) scores of the pairs (pixA[i], pixB[i]) of preprocessed pixels, in engine batches of batch_pairs (None: auto_rows)."""
+    def score_pixel_pairs(self, pixA, pixB, target_layer: int, similarity="cosine", batch_pairs: Optional[int] = None,
+                          tail=None) -> torch.Tensor:
+        """(n,) scores of the pairs (pixA[i], pixB[i]) of preprocessed pixels, in engine batches of batch_pairs (None: auto_rows).
+        tail: None (the kind's own pair tail), or a callable with engine.pair_score's signature."""
         tap, n = int(target_layer), pixA.shape[0]
         self.side = int(pixA.shape[-1])
         if batch_pairs is None:
             batch_pairs = self.auto_rows(self.engine_at(tap), n, 2)
         none = torch.zeros((1,) + tuple(pixA.shape[1:]))
         out = torch.empty(n, dtype=torch.float32, device=self.device)
-        for i0, i1, s in self.pair_chunks(pixA, pixB, none, none, None, tap, 0, similarity, batch_pairs, self.pair_tail(tap) or pair_score):
+        for i0, i1, s in self.pair_chunks(pixA, pixB, none, none, None, tap, 0, similarity, batch_pairs,
+                                            tail or self.pair_tail(tap) or pair_score):
             out[i0:i1] = s
         return out
 
-    def _cross_score(self, images1, images2, target_layer):
+    def _cross_score(self, images1, images2, target_layer, tail_of=None):
         images1 = images1 if isinstance(images1, list) else [images1]
         images2 = images2 if isinstance(images2, list) else [images2]
         if len(images1) != len(images2):
             raise ValueError(f"Number of images1 ({len(images1)}) and images2 ({len(images2)}) should be same.")
         (pa, pb), _, _ = path_latents(self, list(zip(images1, images2)), (0, 1), None, None, len(images1))
-        return self.score_pixel_pairs(pa, pb, self.tap_of(None, target_layer))
+        tap = self.tap_of(None, target_layer)
+        return self.score_pixel_pairs(pa, pb, tap, tail=None if tail_of is None else tail_of(tap))
 
     @torch.no_grad()
     def score_pairs_taps(self, pairs, layers, similarity="cosine") -> torch.Tensor:
@@ -280,3 +284,11 @@ class Dinov2Score(_ViTScore):
     def dino_cross_score(self, images1, images2, target_layer):
         """Same contract as the reference's ``Dinov2Score.dino_cross_score``."""
         return self._cross_score(images1, images2, target_layer)
+
+    @torch.no_grad()
+    def dino_feature_score(self, images1, images2, target_layer):
+        """``dinofeats`` (metrics/dino.py:163-183): the cosine of the hooked attention's context layers, class token included
+        (feats.py).  PIL images or paths, one or a list each, as dino_cross_score takes them; a score per pair (the reference
+        flattens a whole list into ONE cosine: the same number for the single pair its drivers pass)."""
+        from .feats import FeatureView
+        return self._cross_score(images1, images2, target_layer, FeatureView(self).pair_tail)

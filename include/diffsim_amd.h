@@ -587,6 +587,47 @@ int    dsim_pair_score_proj(const void* q, const void* k, const void* v, const i
                             int B, int H, int N, int D, int dtype, int similarity, const void* w_out, const float* bias,
                             float* out_scores, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- feature-cosine metrics: the reference's `diffeats` (metrics/diffeats.py:136-205) and `dinofeats` (metrics/dino.py:163-183):
+ *      the plain cosine of the tapped self-attention's OWN output, the ablation beside the attention scores above.
+ * dsim_attn_features: per image i, O_i = SDPA(q_i, k_i, v_i) per (b, h) on the tiled attention core, rounded to the compute dtype as
+ *   dsim_pair_score rounds its outputs and merged to [B][N][C] rows, C = H*D.
+ *     q,k,v       : dtype [n][B][N][H*D] (16-byte aligned);  L = B*N*H*D, an image's elements (stated so that the call and its
+ *                   consumers below agree on it)
+ *     w_out, bias : both NULL (F = O: dinofeats, the context layer as it is), or the tapped layer's output projection, compute dtype
+ *                   [C][C] (rows = output features) and f32 [C]: F = O w_out^T + bias on the matrix cores, f32 accumulation in an
+ *                   order fixed by the tile shape, rounded once (diffeats: attn1.to_out.0; no residual, no rescale)
+ *     minmax      : non-zero: G = (F - mn) / (mx - mn) in f32, rounded to the compute dtype, mn / mx the exact minimum / maximum of
+ *                   the image's rounded F over all B N C values (diffeats.py:136-140).  mx == mn makes every value of that image NaN,
+ *                   as the reference's division does.  Zero: G = F.
+ *     feats (out) : dtype [n][B][N][C], G
+ *     stats (out) : f32 [n][4] = { sum of G^2, mn, mx, 0 } (mn, mx: of F); the sum is f32 per workgroup and f64 across workgroups in
+ *                   a fixed order
+ *   No atomics; an image's features and stats do not depend on the other images of the call.
+ * dsim_feature_pair_score: out[p] = cosine_similarity(flat G of image idx_a[p], flat G of image idx_b[p]), eps 1e-8 under each norm
+ *   (the eps arithmetic of dsim_pair_score): the dot product over L in f32 per workgroup and f64 across in a fixed order, the norms
+ *   from stats.  status: NULL, or device int32 [n_pairs], 1 where the score is NaN or infinite.  A pair's score does not depend on
+ *   the other pairs of the call.
+ * dsim_feature_matrix: out[a][b] = the same cosine of (image a of set A, image b of set B), as a Gram product on the matrix cores in
+ *   the 16-bit modes (f32: exact-f32 MFMAs): 32 x 128 tiles, K split over workgroups in 16384 elements, the f32 partials folded in
+ *   f64 in ascending K order.  No atomics.  A cell's value depends on its two images alone: not on n_a, n_b, its position or the other
+ *   cells (edge tiles are zero-padded; a NaN image poisons only its own row or column), and out[a][b] of (A, B) equals out[b][a] of
+ *   (B, A).  A matrix cell and the pair score of the same two images are NOT bit-equal: the matrix cores and the vector unit round a
+ *   long dot product differently; both are deterministic and hold the same bound against float64.
+ *     status      : NULL, or device int32 [n_a][n_b], as above
+ * Every check is made before anything is enqueued.  DSIM_ERR_INVALID (workspace query: 0) for a bad dtype, a head dim outside the
+ * supported list, n < 1, n > 65535, n_pairs > 65535, B H > 65535, L != B N H D, L % 8 != 0, L > 2^30, n_a n_b >= 2^31, or one of
+ * w_out / bias without the other; DSIM_ERR_WORKSPACE for a short workspace. */
+size_t dsim_attn_features_workspace_bytes(int n, int B, int H, int N, int D, int L, int dtype, int proj);
+int    dsim_attn_features(const void* q, const void* k, const void* v, int n, int B, int H, int N, int D, int L, int dtype,
+                          const void* w_out, const float* bias, int minmax, void* feats, float* stats, void* workspace,
+                          size_t workspace_bytes, void* stream);
+size_t dsim_feature_pair_score_workspace_bytes(int n_pairs, int L, int dtype);
+int    dsim_feature_pair_score(const void* feats, const float* stats, const int32_t* idx_a, const int32_t* idx_b, int n_pairs, int L,
+                               int dtype, float* out_scores, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+size_t dsim_feature_matrix_workspace_bytes(int n_a, int n_b, int L, int dtype);
+int    dsim_feature_matrix(const void* fa, const float* stats_a, int n_a, const void* fb, const float* stats_b, int n_b, int L,
+                           int dtype, float* out, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- the arithmetic either side of the VAE encoder, on the device (the host only decodes and resizes) ----
  * dsim_image_preprocess: what process_image does after its Lanczos resize (diffsim/diffsim.py:31-41): pixels u8 [n][H][W][3] ->
  *   f32 [n][3][H][W] = (p / 255 - 0.5) / 0.5 in IEEE f32, bit-identical to the numpy path; to_half = 1 additionally rounds
