@@ -207,6 +207,8 @@ SYMBOLS = {
     "dsim_text_attention": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dsim_pair_score_regions_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
     "dsim_pair_score_regions": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dsim_pair_score_weights_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "dsim_pair_score_weights": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dsim_pair_score_maps_regions_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
     "dsim_pair_score_maps_regions": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dsim_pair_align_regions_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),

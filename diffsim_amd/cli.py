@@ -4,7 +4,7 @@
 
 Flags of the reference drivers (``/root/reference/argprocess.py:5-18``) keep their names, meaning and defaults;
 ``--dataset`` selects which of the reference's loops runs (``cute_main.py:48-226``, ``night_main.py:24-173`` or
-``style_main.py:24-196`` -- separate scripts there), ``--model_path / --dtype / --batch / --unet_batch / --ngpu / --noise_dtype / --mask_path / --query_mask_path / --gallery_mask_path / --save_region_maps / --save_region_matches / --text_attn / --text_threshold`` are additions of this build (the reference
+``style_main.py:24-196`` -- separate scripts there), ``--model_path / --dtype / --batch / --unet_batch / --ngpu / --noise_dtype / --mask_path / --query_mask_path / --gallery_mask_path / --save_region_maps / --save_region_matches / --text_attn / --text_threshold / --soft_masks / --text_soft`` are additions of this build (the reference
 hard-codes NAS checkpoint paths, ``cute_main.py:25-31``, fp16 and one GPU, ``cute_main.sh:1``).
 
 Multi-GPU (``--ngpu N``): the parent starts N rank processes before anything touches the GPU; triplets are sharded
@@ -90,6 +90,13 @@ def build_parser() -> argparse.ArgumentParser:
                         "(text-guided regions).  Each image's region is the tokens whose cross-attention to the WORDs of its row's "
                         "prompt (no WORD: every content token of the prompt) is at least --text_threshold x the image's mean; the "
                         "run prints the mean share of tokens on.  Implies --use_text_attn")
+    p.add_argument("--soft_masks", action="store_true",
+                   help="--mask_path: soft region scores -- a mask's area average on the token grid is the token's weight (0 .. 255) "
+                        "instead of being thresholded at 128, so a partly covered token counts partly, in both attentions and in the "
+                        "sums.  Masks of 0 and 255 alone on the grid give the --mask_path scores")
+    p.add_argument("--text_soft", action="store_true",
+                   help="--text_attn: soft text-guided regions -- a token below --text_threshold x the mean saliency keeps its share of "
+                        "the threshold as a weight instead of being switched off; the run prints the mean token weight")
     p.add_argument("--text_threshold", type=float, default=1.0,
                    help="--text_attn: a token is in its image's region at >= this multiple of the image's mean text saliency "
                         "(0: every token; a region with no token on is the whole image)")
@@ -121,6 +128,17 @@ def build_parser() -> argparse.ArgumentParser:
 def arg_parse(argv=None):
     p = build_parser()
     args = p.parse_args(argv)
+    for flag, on, partner, has in (("--soft_masks", args.soft_masks, "--mask_path", args.mask_path is not None),
+                                   ("--text_soft", args.text_soft, "--text_attn", args.text_attn is not None)):
+        if not on:
+            continue
+        if not has:
+            p.error(f"{flag} weighs the tokens of {partner}: it needs {partner}")
+        if args.dataset == "retrieval" or args.taps is not None:
+            p.error(f"{flag} scores soft regions on the one-tap triplet benchmarks (--dataset cute or nights): --dataset retrieval and "
+                    "a sweep (--taps) are not supported with it (there are no soft score matrices)")
+        if args.metric in VIT_METRICS or args.metric in FEATURE_METRICS:
+            p.error(f"{flag}: --metric {args.metric} has no regions")
     if args.metric in FEATURE_METRICS:
         if args.similarity != "cosine":
             p.error(f"--metric {args.metric} needs --similarity cosine: its score is always a cosine, as in the reference (which "
@@ -433,10 +451,12 @@ def run(args) -> int:
             masks, missing = triplet_mask_paths(trip, args.image_path, args.mask_path)
             if rank == 0:
                 print(f"Region scores: masks from {args.mask_path}; {missing} image(s) without a mask file are scored whole")
+                if args.soft_masks:
+                    print("Soft regions: a mask's area average on the token grid is the token's weight")
         guide = None
         if args.text_attn is not None and not args.selftest_shard:
             from .textattn import TextGuide
-            guide = TextGuide(args.text_attn, args.text_threshold)
+            guide = TextGuide(args.text_attn, args.text_threshold, **({"soft": True} if args.text_soft else {}))
             if rank == 0:
                 print(f"Text-guided regions: {'the words ' + ' '.join(args.text_attn) if args.text_attn else 'every content token'} "
                       f"of each prompt, threshold {args.text_threshold:g} x the mean saliency")
@@ -445,10 +465,14 @@ def run(args) -> int:
         else:
             s_ab, s_ac, bad = H.score_path_triplets(scorer, trip, args.image_size, args.target_block, layer, args.target_step,
                                                     args.seed, args.similarity, rank, world, args.batch, args.unet_batch,
-                                                    *(() if masks is None else (masks,)), **({} if guide is None else {"text": guide}))
+                                                    *(() if masks is None else (masks,)), **({} if guide is None else {"text": guide}),
+                                                    **({"soft": True} if args.soft_masks else {}))
         if rank == 0:
             if guide is not None:
-                print(f"Mean share of tokens on: {guide.on_fraction * 100:.2f}%")
+                if args.text_soft:
+                    print(f"Mean token weight: {guide.on_fraction * 100:.2f}%")
+                else:
+                    print(f"Mean share of tokens on: {guide.on_fraction * 100:.2f}%")
             _report(args, trip, rows, s_ab, s_ac, bad)
     if world > 1:
         import torch.distributed as dist

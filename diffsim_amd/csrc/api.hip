@@ -108,6 +108,20 @@ int dsim_pair_score_regions(const void* q, const void* k, const void* v, const u
     return st != DSIM_OK ? st : launch_pair_score_regions(a, dtype, mask, n_feat, out_scores, status, counts, (hipStream_t)stream);
 }
 
+size_t dsim_pair_score_weights_workspace_bytes(int n_feat, int n_pairs, int B, int H, int N, int D) {
+    return with_slack(pair_score_weights_scratch_bytes(n_feat, n_pairs, B, H, N, D));
+}
+
+int dsim_pair_score_weights(const void* q, const void* k, const void* v, const uint8_t* weights, int n_feat, const int32_t* idx_a,
+                            const int32_t* idx_b, int n_pairs, int B, int H, int N, int D, int dtype, int similarity, float* out_scores,
+                            int32_t* status, int32_t* weight_sums, void* workspace, size_t workspace_bytes, void* stream) {
+    PairArgs a{q, k, v, idx_a, idx_b, n_pairs, B, H, N, D, similarity, workspace, workspace_bytes};
+    const bool served = pair_score_weights_scratch_bytes(n_feat, n_pairs, B, H, N, D) != 0;
+    const int st = tail_prologue({q, k, v, weights, idx_a, idx_b, out_scores}, served ? pair_args_check(a, dtype) : DSIM_ERR_INVALID,
+                                 a.scratch, a.scratch_bytes);
+    return st != DSIM_OK ? st : launch_pair_score_weights(a, dtype, weights, n_feat, out_scores, status, weight_sums, (hipStream_t)stream);
+}
+
 size_t dsim_pair_score_maps_regions_workspace_bytes(int n_feat, int n_pairs, int B, int H, int N, int D) {
     return with_slack(pair_score_maps_regions_scratch_bytes(n_feat, n_pairs, B, H, N, D));
 }

@@ -1,9 +1,9 @@
 // The tiled attention core for gfx950: one wave's 32 query rows against any number of keys (attend), with the Q fragments, the
-// O^T accumulators and the K / V staging it works on, and the host-side head-dim dispatch.  Shared by exactly five sources: the
+// O^T accumulators and the K / V staging it works on, and the host-side head-dim dispatch.  Shared by exactly six sources: the
 // attention kernels (attention.hip), the score tails (tails.hip), the region scores (regions.hip: attend over listed rows), the
-// token alignments (align.hip) and the text attention maps (textattn.hip) -- the last two take the configuration, fragments, MFMA
-// wrappers, head-dim dispatch and the un-rescaled logit routine, not attend; everything here lives in their dsim::(anonymous
-// namespace).
+// soft region scores (soft_regions.hip: listed rows and a bias per key), the token alignments (align.hip) and the text attention maps
+// (textattn.hip) -- the last two take the configuration, fragments, MFMA wrappers, head-dim dispatch and the un-rescaled logit
+// routine, not attend; everything here lives in their dsim::(anonymous namespace).
 //
 // Tiling: a workgroup = 4 waves = 128 query rows of one (batch, head); each wave owns 32 rows and
 // sweeps the keys in 64-row tiles shared through LDS.
@@ -164,8 +164,29 @@ __device__ __forceinline__ void tile_init(StageRegs<T, D>& sr, char* lds, int ld
 // Which row of K and V key position j of an attention is.  RowsInOrder: row j, the contiguous rows every kernel but the region
 // tail reads (tile_load's code for it is the code it had before there was a choice).  RowsListed: row list[j], the ascending token
 // list of a region (regions.hip) -- one index load per staged chunk pair, and the chunk's column taken back out of goff.
-struct RowsInOrder { static constexpr bool LISTED = false; };
-struct RowsListed { static constexpr bool LISTED = true; const int32_t* list; };
+struct RowsInOrder { static constexpr bool LISTED = false, WEIGHTED = false; struct Table {}; };
+struct RowsListed { static constexpr bool LISTED = true, WEIGHTED = false; const int32_t* list; struct Table {}; };
+
+// What attend adds to the logit of key position j before the softmax looks at it.  NoKeyBias: nothing -- every line of the hook is
+// under `if constexpr`, so an instantiation without a bias has the program text it had before there was a choice.  KeyBiasLog2:
+// lb[j], in the log2 units of the pre-scaled logits (soft_regions.hip: log2 of the key token's weight, <= 0 and finite), indexed by
+// key position; lb is 16-byte aligned and readable up to the end of the last 64-key tile.
+struct NoKeyBias { static constexpr bool BIASED = false; };
+struct KeyBiasLog2 { static constexpr bool BIASED = true; const float* lb; };
+// RowsWeighted (soft_regions.hip): RowsListed's rows, each with a byte weight m in 1 .. 255 -- lb[j] = log2(m / 255) of the image's
+// listed token j, the bias of key position j.  Table: the same for every image of a call, and the bytes themselves on the token grid
+// (the tails take a query row's weight from them).
+struct RowsWeighted {
+    static constexpr bool LISTED = true, WEIGHTED = true;
+    const int32_t* list;
+    const float* lb;
+    struct Table { const float* lb; const uint8_t* bytes; int stride; };      // lb [n_feat][stride], bytes [n_feat][N]
+};
+template <typename Rows>
+__device__ __forceinline__ auto key_bias(const Rows& rows) {
+    if constexpr (Rows::WEIGHTED) return KeyBiasLog2{rows.lb};
+    else return NoKeyBias{};
+}
 
 template <typename T, int D, typename Rows = RowsInOrder>
 __device__ __forceinline__ void tile_load(StageRegs<T, D>& sr, const T* kb, const T* vb, int ldk, int kv0, int Nk, Rows rows = Rows()) {
@@ -207,9 +228,14 @@ __device__ __forceinline__ void tile_store(char* lds, const StageRegs<T, D>& sr,
 // have the exponent range for it).  Only if the excess passes ~100 (log2 units) can exp2 overflow; the caller detects that from a
 // non-finite or absurd denominator and re-runs the block with FAST = false (attend_checked).
 // Rows: which rows of kb / vb the Nk key positions are (RowsInOrder: rows 0 .. Nk - 1).
-template <typename T, int D, bool FAST = false, typename Rows = RowsInOrder>
+// Bias: an additive term per key position (NoKeyBias: none).  KeyBiasLog2: s(q, j) += lb[j] right after the QK^T MFMAs, so the
+// ragged-tile mask, the row maximum, the re-base and the exponentials all see the biased logit and need no change.  The 32 values a
+// lane needs per tile are eight 16-byte loads, the same addresses across a lane half, from an array that stays in L2 (64 floats a
+// tile); nothing is staged in LDS, so ACfg's LDS budget and occupancy are the unbiased ones.  KONE: a bias is <= 0, it can only
+// lower a logit, so no row passes the re-base slack that would not have passed it unbiased.
+template <typename T, int D, bool FAST = false, typename Rows = RowsInOrder, typename Bias = NoKeyBias>
 __device__ __forceinline__ void attend(const QFrags<T, D>& qfr, const T* kb, const T* vb, int ldk, int Nk, char* lds,
-                                       OAcc<T, D>& oacc, float* l_out = nullptr, Rows rows = Rows()) {
+                                       OAcc<T, D>& oacc, float* l_out = nullptr, Rows rows = Rows(), Bias bias = Bias()) {
     typedef ACfg<T, D> C;
     typedef typename FragOf<T>::type Frag;
     QFrags<T, D> qloc = qfr;    // (KONE writes -m into the spare d = D slot of its own copy)
@@ -259,6 +285,18 @@ __device__ __forceinline__ void attend(const QFrags<T, D>& qfr, const T* kb, con
                 lload_frag(kf, krow + ks * 16 * C::ES);
                 mma(kf, qf[ks], s[jb]);
             }
+        }
+        if constexpr (Bias::BIASED) {
+            // slot (jb, r = 4 g + e) is key kt*KT + jb*32 + e + 8 g + 4 half: four consecutive positions per load
+            const float* lb = bias.lb + kt * KT + 4 * half;
+#pragma unroll
+            for (int jb = 0; jb < 2; ++jb)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const f32x4 b4 = *reinterpret_cast<const f32x4*>(lb + jb * 32 + 8 * g);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) s[jb][4 * g + e] += b4[e];
+                }
         }
         if (kt * KT + KT > Nk) {                           // ragged last tile only
 #pragma unroll

@@ -1,5 +1,5 @@
 // The host entry points of the sources that are compiled once per 16-bit type (gemm / gemm_skinny / rowres / attention / tails /
-// align / regions / region_matrix / region_maps / textattn / attn160 .hip).  Declarations only and no include guard: common.h includes this file inside `inline namespace DSIM_H16_NS`, the including
+// align / regions / soft_regions / region_matrix / region_maps / textattn / attn160 .hip).  Declarations only and no include guard: common.h includes this file inside `inline namespace DSIM_H16_NS`, the including
 // object's own type, and the bf16 objects of the product build once more inside `namespace f16`, which declares the fp16 twins with
 // the same signatures and default arguments.  The argument structs and enums are plain dsim types (common.h, above the include).
 
@@ -56,6 +56,12 @@ int launch_pair_score_regions(const PairArgs& a, int dtype, const uint8_t* mask,
                               int32_t* counts, hipStream_t s);
 // the masks [n_feat][N] as ascending token lists [n_feat][N] and counts [n_feat] (also to counts, unless NULL): region_lists_kernel
 int launch_region_lists(const uint8_t* mask, int n_feat, int N, int32_t* list, int32_t* cnt, int32_t* counts, hipStream_t s);
+// soft region scores: the region score with a byte weight per token (weights [n_feat][N], w = byte / 255) -- a weight-0 token is
+// dropped, a listed key's logit carries the bias ln w, a query row's terms the factor w -- soft_regions.hip
+//   out [n_pairs]; status (may be NULL) [n_pairs]: 0, 1 non-finite, 2 an image of byte sum 0; weight_sums (may be NULL) [n_feat]
+size_t pair_score_weights_scratch_bytes(int n_feat, int n_pairs, int B, int H, int N, int D);      // 0: call not served
+int launch_pair_score_weights(const PairArgs& a, int dtype, const uint8_t* weights, int n_feat, float* out, int32_t* status,
+                              int32_t* weight_sums, hipStream_t s);
 // region maps: launch_pair_score_maps' outputs for the region score -- the region tail kept per query token, on the full token grid,
 // zeros at the off tokens -- region_maps.hip
 //   score [n_pairs]; local, contrib (each may be NULL) [n_pairs][2][N]; status (may be NULL): 0, 1 non-finite, 2 empty region

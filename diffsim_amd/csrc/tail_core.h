@@ -104,13 +104,16 @@ __device__ __forceinline__ void store_block_partial(TailSums t, int lane, int wa
 // read.  RowsListed -- the rows of an image i are list[i][0 .. cnt[i]), ascending: position t is row list[i][t] and the image's count
 // stands where N stood; the grid being sized for N, a workgroup past the query image's count, or of a pair with an empty image,
 // writes a zero partial and leaves as a whole before any barrier (PER_TOKEN: it writes nothing -- the positions from the count on
-// are never written, and the finish never reads them).
+// are never written, and the finish never reads them).  RowsWeighted (soft_regions.hip) -- RowsListed, and both attends add the key
+// image's log2 weights to the logits (key_bias) and a query row's three sums are multiplied by its weight byte / 255 (wt: the
+// call's weights); with every listed byte 255 the additions are + 0.0f and the factor is 1.0f: RowsListed's bits.
 // grid (ceil(N/128), B*H, n_pairs*2)
 template <typename T, int D, bool PER_TOKEN, typename Rows>
 __device__ __forceinline__ void pair_tail_body(const T* __restrict__ qg, const T* __restrict__ kg, const T* __restrict__ vg,
                                                const int32_t* __restrict__ list, const int32_t* __restrict__ cnt,
                                                const int32_t* __restrict__ idx_a, const int32_t* __restrict__ idx_b, int B, int H, int N,
-                                               float scale_log2, int mse, float* __restrict__ part) {
+                                               float scale_log2, int mse, float* __restrict__ part,
+                                               typename Rows::Table wt = typename Rows::Table()) {
     typedef ACfg<T, D> C;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, l31 = lane & 31;
@@ -133,6 +136,10 @@ __device__ __forceinline__ void pair_tail_body(const T* __restrict__ qg, const T
         }
         rq.list = list + (size_t)iq * N;
         rx.list = list + (size_t)ix * N;
+        if constexpr (Rows::WEIGHTED) {
+            rq.lb = wt.lb + (size_t)iq * wt.stride;
+            rx.lb = wt.lb + (size_t)ix * wt.stride;
+        }
     }
     const int ld = H * D;
     const size_t img = (size_t)B * N * ld;
@@ -148,7 +155,7 @@ __device__ __forceinline__ void pair_tail_body(const T* __restrict__ qg, const T
         h16x2 osp[C::NDB][8];           // the self-attention's output, rounded to the compute dtype, two values per register
         {
             OAcc<T, D> osa;
-            attend<T, D, false>(qf, kg + iq * img + boff, vg + iq * img + boff, ld, nq, smem, osa, nullptr, rq);
+            attend<T, D, false>(qf, kg + iq * img + boff, vg + iq * img + boff, ld, nq, smem, osa, nullptr, rq, key_bias(rq));
             settle<T, D>(osa);
 #pragma unroll
             for (int db = 0; db < C::NDB; ++db)
@@ -159,16 +166,23 @@ __device__ __forceinline__ void pair_tail_body(const T* __restrict__ qg, const T
                 }
         }
         OAcc<T, D> oxa;
-        attend<T, D, false>(qf, kg + ix * img + boff, vg + ix * img + boff, ld, nx, smem, oxa, nullptr, rx);
+        attend<T, D, false>(qf, kg + ix * img + boff, vg + ix * img + boff, ld, nx, smem, oxa, nullptr, rx, key_bias(rx));
         settle<T, D>(oxa);
         if (t < nq) s = tail_products<T, D>(oxa, half, mse, [&](int db, int r, int) { return (float)osp[db][r >> 1][r & 1]; });
     } else {
         OAcc<T, D> osa, oxa;
-        attend<T, D, false>(qf, kg + iq * img + boff, vg + iq * img + boff, ld, nq, smem, osa, nullptr, rq);
-        attend<T, D, false>(qf, kg + ix * img + boff, vg + ix * img + boff, ld, nx, smem, oxa, nullptr, rx);
+        attend<T, D, false>(qf, kg + iq * img + boff, vg + iq * img + boff, ld, nq, smem, osa, nullptr, rq, key_bias(rq));
+        attend<T, D, false>(qf, kg + ix * img + boff, vg + ix * img + boff, ld, nx, smem, oxa, nullptr, rx, key_bias(rx));
         settle<T, D>(osa);
         settle<T, D>(oxa);
         if (t < nq) s = tail_products<T, D>(oxa, half, mse, [&](int db, int r, int) { return osa.b[db][r]; });
+    }
+    if constexpr (Rows::WEIGHTED) {
+        // the query row's weight on its three sums (byte 255: * 1.0f); pinned, so that the product is rounded on its own and never
+        // fused into the additions that follow
+        const float wq = (float)wt.bytes[(size_t)iq * N + q] / 255.0f;
+        s.s0 *= wq; s.s1 *= wq; s.s2 *= wq;
+        asm volatile("" : "+v"(s.s0), "+v"(s.s1), "+v"(s.s2));
     }
     if constexpr (PER_TOKEN) {
         // a row's d values are split between the two lane halves: fold them, then the first half stores the row at its position

@@ -388,6 +388,17 @@ class DiffSim(Scorer):
                                                _norm_layer(target_layer), target_step, seed, similarity)
 
     @torch.no_grad()
+    def soft_region_score(self, image_A, image_B, mask_A, mask_B, img_size, prompt, target_block, target_layer, target_step,
+                          seed="2333", similarity="cosine"):
+        """:meth:`region_score` with a weight per token instead of a bit (regions.py, ``engine.pair_score_weights``): a mask's area
+        average on the token grid is the token's weight, so a partly covered token counts partly -- as a key through a logit bias in
+        both attentions, as a query through a factor on its terms.  A mask is a path, a PIL image, a uint8 / bool / [0, 1] float
+        array on the tap's token grid, or None (the whole image); masks of 0 and 255 alone give :meth:`region_score`'s score.
+        Returns a (1,) tensor."""
+        return regions.score_path_pair_weights(self, [(image_A, image_B)], [(mask_A, mask_B)], img_size, prompt, target_block,
+                                               _norm_layer(target_layer), target_step, seed, similarity)
+
+    @torch.no_grad()
     def region_similarity_maps(self, image_A, image_B, mask_A, mask_B, img_size, prompt, target_block, target_layer, target_step,
                                seed="2333", similarity="cosine"):
         """:meth:`region_score` of one image pair with its per-token terms on both images' grids: a

@@ -200,6 +200,14 @@ class diffsim_xl(Scorer):
                                                target_layer, target_step, seed, similarity, hip_vae=False)
 
     @torch.no_grad()
+    def soft_region_score(self, image_A, image_B, mask_A, mask_B, img_size, prompt, target_block, target_layer, target_step, seed,
+                          similarity):
+        """:meth:`region_score` with a weight per token instead of a bit (``regions.score_path_pair_weights``); a mask is a path, a
+        PIL image, a uint8 / bool / [0, 1] float array on the tap's token grid, or None.  Returns a (1,) tensor."""
+        return regions.score_path_pair_weights(self, [(image_A, image_B)], [(mask_A, mask_B)], img_size, prompt, target_block,
+                                               target_layer, target_step, seed, similarity, hip_vae=False)
+
+    @torch.no_grad()
     def region_similarity_maps(self, image_A, image_B, mask_A, mask_B, img_size, prompt, target_block, target_layer, target_step,
                                seed, similarity):
         """:meth:`region_score` with its per-token terms on both images' grids (a maps.SimilarityMaps of one pair over the masked

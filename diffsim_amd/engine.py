@@ -687,6 +687,34 @@ def pair_score_regions(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: 
     return _with_extras(out, status, counts)
 
 
+def pair_score_weights(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, weights_u8: torch.Tensor, idx_a: torch.Tensor,
+                       idx_b: torch.Tensor, heads: int, similarity: str = "cosine", return_status: bool = False,
+                       return_sums: bool = False):
+    """The soft region score (dsim_pair_score_weights): pair_score_regions with a weight per token instead of a bit.  q,k,v:
+    [n_feat][B][N][H*D]; weights_u8: uint8 cuda (n_feat, N), token t of image i weighs byte / 255; idx: int32 cuda [n_pairs].  A
+    token of byte 0 is dropped as an off token is; a key of weight w enters both softmaxes with the logit bias ln w, and a query row
+    of weight w counts w times in the cosine / mse sums.  With every byte 0 or 255 it is pair_score_regions on `weights_u8 != 0`, bit
+    for bit.  Returns the f32 (n,) scores; return_status: also an int32 (n,) tensor, 1 where the score is NaN / infinite, 2 where
+    an image of the pair has no weight at all (score NaN); return_sums: also the int32 (n_feat,) byte sums."""
+    _require_cuda(q, k, v, weights_u8, idx_a, idx_b)
+    sim = _similarity_code(similarity)
+    B, N, D = _check_features((q, k, v), heads, k.shape == q.shape == v.shape, _PAIR_MSGS, (idx_a, idx_b))
+    if weights_u8.dtype != torch.uint8:
+        raise _lib.DsimError("the token weights must be uint8")
+    _check_region_mask(weights_u8, q.shape[0], N, "the token weights")
+    if not weights_u8.is_contiguous():
+        raise _lib.DsimError("the token weights must be contiguous")
+    n_feat, n_pairs = q.shape[0], idx_a.numel()
+    out = torch.empty(n_pairs, dtype=torch.float32, device=q.device)
+    status = _i32(n_pairs, q.device, return_status)
+    sums = _i32(n_feat, q.device, return_sums)
+    _tail_call(q.device, "pair_score_weights", (n_feat, n_pairs, B, heads, N, D),
+               f"no soft region scores for n_feat={n_feat} n_pairs={n_pairs} B={B} H={heads} N={N} D={D}", q.data_ptr(), k.data_ptr(),
+               v.data_ptr(), weights_u8.data_ptr(), n_feat, idx_a.data_ptr(), idx_b.data_ptr(), n_pairs, B, heads, N, D,
+               _TORCH2DSIM[q.dtype], sim, out.data_ptr(), _ptr(status), _ptr(sums))
+    return _with_extras(out, status, sums)
+
+
 def pair_score_maps_regions(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: torch.Tensor, idx_a: torch.Tensor,
                             idx_b: torch.Tensor, heads: int, similarity: str = "cosine", return_status: bool = False,
                             return_counts: bool = False):

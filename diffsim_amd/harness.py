@@ -21,7 +21,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import torch
 
-from .engine import pair_score, pair_score_regions
+from .engine import pair_score, pair_score_regions, pair_score_weights
 from .inputs import path_latents
 from .parallel import gather_scores, shard_triplets
 from .scorer import stack_rows
@@ -74,14 +74,15 @@ def cute_accuracy(s_ab: torch.Tensor, s_ac: torch.Tensor) -> float:
 
 @torch.no_grad()
 def triplet_chunks(scorer, ref, left, right, nA, nB, prompt, heads, similarity, batch_triplets: int, feats, masks=None, text=None,
-                   tails=None):
+                   tails=None, soft: bool = False):
     """(ref,left) and (ref,right) scores of latent triplets at every tap of a forward: 3 forwards per triplet (the reference
     image's features are shared), chunked engine batches, one fused tail launch per chunk and tap.  feats(lat, nz, prompt) ->
     [(q, k, v) per tap] is the forward of one engine batch, heads[t] tap t's head count.  masks: None, or the (ref, left, right)
     token masks, each (n, N) bool on the device: the region tail (regions.py) over each chunk's rows instead of the pair tail.
     text: None, or (guide, w): a textattn.TextGuide and its bound per-triplet weights; feats then returns (q, k, v, xq, xkv) per
     tap and the masks of the region tail are the text-guided regions of the chunk's images -- ref, left and right each their own,
-    the ref's made once per triplet.  tails: None, or each tap's ``Scorer.pair_tail`` (a None entry: engine.pair_score).  Returns
+    the ref's made once per triplet.  soft: the masks are (n, N) uint8 token weights (or the guide makes weights: TextGuide(soft=True))
+    and the tail is the soft region tail, engine.pair_score_weights.  tails: None, or each tap's ``Scorer.pair_tail`` (a None entry: engine.pair_score).  Returns
     the (nt, n) scores of both sides and the (nt,) NaN / inf counts."""
     n, nt, dev = ref.shape[0], len(heads), scorer.device
     s_l = torch.empty((nt, n), dtype=torch.float32, device=dev)
@@ -101,28 +102,34 @@ def triplet_chunks(scorer, ref, left, right, nA, nB, prompt, heads, similarity, 
                     rows, _counts = text[0].regions(*xs, heads[t], text[1], i0, i1, 3)
                 else:
                     rows = torch.stack([mk[i0:i1] for mk in masks], dim=1).reshape(3 * m, -1).contiguous()
-                s, st = pair_score_regions(q, k, v, rows, ia, ib, heads[t], similarity, return_status=True)
+                region_tail = pair_score_weights if soft or (text is not None and getattr(text[0], "soft", False)) else pair_score_regions
+                s, st = region_tail(q, k, v, rows, ia, ib, heads[t], similarity, return_status=True)
                 st = (st != 0).to(torch.int32)
             bad[t] += st.sum()
             s_l[t, i0:i1], s_r[t, i0:i1] = s[:m], s[m:]
     return s_l, s_r, bad
 
 
-def _score_chunks(scorer, ref, left, right, nA, nB, prompt, block, layer, step, similarity, batch_triplets, masks=None, text=None):
+def _score_chunks(scorer, ref, left, right, nA, nB, prompt, block, layer, step, similarity, batch_triplets, masks=None, text=None,
+                  soft: bool = False):
     """triplet_chunks at the one tap (block, layer): each engine batch is one ``tap_features`` call.  masks: None, or one
     (ref, left, right) triple of masks per triplet (``regions.as_token_mask``), put on the tap's token grid here.  text: None, or
     a textattn.TextGuide: each engine batch is one ``tap_features_text`` call and the regions come from the text attention maps
-    (per-row prompts give per-triplet weights)."""
+    (per-row prompts give per-triplet weights).  soft (with masks): the masks become token weights (``regions.as_token_weights``) and
+    the tail the soft region tail."""
     n = ref.shape[0]
+    if soft and masks is None:
+        raise ValueError("soft=True weighs the tokens of masks=: it needs them (a text guide is soft by TextGuide(soft=True))")
     tap = scorer.tap_of(block, layer)
     if text is not None:
         if masks is not None:
             raise ValueError("a text-guided region and a mask file per image: one or the other")
         text = (text, text.bind(scorer, prompt, n))
     if masks is not None:
-        from .regions import as_token_mask, tap_grid
+        from .regions import as_token_mask, as_token_weights, tap_grid
         grid = tap_grid(scorer, tap, ref.shape[-1])
-        masks = [torch.stack([as_token_mask(mk[c], grid) for mk in masks]).flatten(1).to(scorer.device) for c in range(3)]
+        on_grid = as_token_weights if soft else as_token_mask
+        masks = [torch.stack([on_grid(mk[c], grid) for mk in masks]).flatten(1).to(scorer.device) for c in range(3)]
     prompt = scorer.bind_prompt(prompt, n)
     eng = scorer.engine_at(tap)
     heads = eng.heads
@@ -133,7 +140,7 @@ def _score_chunks(scorer, ref, left, right, nA, nB, prompt, block, layer, step, 
                               lambda lat, nz, p: [scorer.tap_features_text(lat, nz, p, tap, step)], text=text)
     return triplet_chunks(scorer, ref, left, right, nA, nB, prompt, [heads], similarity, batch_triplets,
                           lambda lat, nz, p: [scorer.tap_features(lat, nz, p, tap, step)], *(() if masks is None else (masks,)),
-                          tails=[scorer.pair_tail(tap)])
+                          tails=[scorer.pair_tail(tap)], **({"soft": True} if soft else {}))
 
 
 @torch.no_grad()
@@ -174,7 +181,7 @@ def path_triplet_scores(scorer, triplets: Sequence[Tuple[str, str, str, str]], i
 
 def score_path_triplets(scorer, triplets: Sequence[Tuple[str, str, str, str]], img_size: int, target_block, target_layer,
                         target_step, seed=2333, similarity="cosine", rank: int = 0, world: int = 1, batch_triplets: int = 10,
-                        unet_triplets: Optional[int] = None, masks: Optional[Sequence] = None, text=None):
+                        unet_triplets: Optional[int] = None, masks: Optional[Sequence] = None, text=None, soft: bool = False):
     """Scores s(A,B) and s(A,C) of every (A, B, C, prompt) path triplet -- the two scorer calls per triplet the
     reference's loops make (cute_main.py:111-132, night_main.py:69-90, style_main.py:150-175) -- for all three scorer
     kinds (DiffSim, diffsim_xl, diffsim_DiT): whole triplets sharded over ranks (the cached reference-image features stay
@@ -185,7 +192,9 @@ def score_path_triplets(scorer, triplets: Sequence[Tuple[str, str, str, str]], i
     (dsim_image_preprocess / dsim_latent_sample), bit-identically to the per-pair path.  masks: None, or one (ref, left, right)
     triple per triplet of mask paths, PIL images, bool arrays on the tap's token grid or None (the whole image): region scores
     (regions.py), what ``region_score(A, B, mask_A, mask_B, ...)`` and ``region_score(A, C, mask_A, mask_C, ...)`` return;
-    with masks=None every call and launch is the unmasked run's.  text: None, or a textattn.TextGuide (words, threshold):
+    with masks=None every call and launch is the unmasked run's.  soft=True (with masks): soft region scores -- each mask becomes
+    byte weights on the token grid (``regions.as_token_weights``: the area average kept, not thresholded) and the tail is
+    ``engine.pair_score_weights``; with soft=False every call and launch is the hard run's.  text: None, or a textattn.TextGuide (words, threshold):
     text-guided regions instead -- ref, left and right each get the region their own text attention map gives, the ref's once per
     triplet, a prompt per row giving weights per image; text.on_fraction is then the mean share of tokens on.  Returns
     (s_ab, s_ac, n_nonfinite):
@@ -195,10 +204,12 @@ def score_path_triplets(scorer, triplets: Sequence[Tuple[str, str, str, str]], i
         raise ValueError(f"{len(masks)} mask triples for {len(triplets)} triplets")
     if masks is not None and text is not None:
         raise ValueError("a text-guided region and a mask file per image: one or the other")
+    if soft and masks is None:
+        raise ValueError("soft=True weighs the tokens of masks=: it needs them (a text guide is soft by TextGuide(soft=True))")
     all_l, all_r, nbad = path_triplet_scores(
         scorer, triplets, img_size, seed, rank, world, batch_triplets, 1,
         lambda *lat_prompt: _score_chunks(scorer, *lat_prompt[:6], target_block, target_layer, target_step, similarity, unet_triplets,
-                                          *lat_prompt[6:], **({} if text is None else {"text": text})),
+                                          *lat_prompt[6:], **({} if text is None else {"text": text}), **({"soft": True} if soft else {})),
         *(() if masks is None else (masks,)))
     return all_l[0], all_r[0], int(nbad)
 

@@ -6,7 +6,9 @@ cross-attention says which image tokens listen to which prompt tokens.  ``UNetEn
 cross-attention (two steps behind the tap, on the score's token grid), ``engine.text_attention`` turns its operands into the text
 attention map T (n, N, L) of the conditional CFG half, the saliency T @ w of the prompt tokens that matter and the region of the
 tokens at or above ``rel_threshold`` x the image's mean saliency; the text-guided score of a pair is the region score
-(regions.py, ``engine.pair_score_regions``) over those regions.  A region with no token on is the whole image.
+(regions.py, ``engine.pair_score_regions``) over those regions.  A region with no token on is the whole image.  A soft guide
+(``TextGuide(soft=True)``) keeps the saliency below the threshold as a token weight instead of cutting it (``soft_token_bytes``), and
+the score is the soft region score (``engine.pair_score_weights``).
 """
 from __future__ import annotations
 
@@ -14,7 +16,7 @@ from typing import Callable, Optional, Sequence, Tuple
 
 import torch
 
-from .engine import pair_score_regions, text_attention
+from .engine import pair_score_regions, pair_score_weights, text_attention
 from .inputs import path_latents
 from .maps import grid_shape
 from .scorer import single_prompt, stack_rows
@@ -57,11 +59,27 @@ def prompt_token_weights(tokenize: Callable[[str], torch.Tensor], prompt, words:
     return w
 
 
+def soft_token_bytes(saliency: torch.Tensor, mask: torch.Tensor, rel_threshold: float) -> torch.Tensor:
+    """The saliency (n, N) f32 as uint8 token weights, with torch ops on its device: per image
+    b = clamp(floor(255 s / (rel_threshold mean(s)) + 0.5), 0, 255) in float64 -- a token at the threshold or above, which the hard
+    rule switches on (mask, the kernel's own decision), carries 255, the others their share.  Threshold 0, or an image whose saliency
+    is non-finite or all zero: all 255, the whole image."""
+    s = saliency.double()
+    den = float(rel_threshold) * s.mean(1, keepdim=True)
+    ok = torch.isfinite(s).all(1, keepdim=True) & (den > 0)
+    full = torch.full_like(s, 255.0)
+    b = torch.where(ok, torch.floor(255.0 * s / den + 0.5).clamp(0.0, 255.0), full)
+    return torch.where(mask != 0, full, b).to(torch.uint8)
+
+
 class TextGuide:
     """What a text-guided run carries: the words (None: every content token), the threshold, or explicit token weights -- (L,) for
-    every image, or one row per pair / triplet -- and the running size of the regions it has made (``on_fraction``)."""
+    every image, or one row per pair / triplet -- and the running size of the regions it has made (``on_fraction``).  soft: the
+    regions are uint8 token weights (``soft_token_bytes``) for the soft region tail, and on_fraction is the mean weight."""
 
-    def __init__(self, words: Optional[Sequence[str]] = None, rel_threshold: float = 1.0, weights: Optional[torch.Tensor] = None):
+    def __init__(self, words: Optional[Sequence[str]] = None, rel_threshold: float = 1.0, weights: Optional[torch.Tensor] = None,
+                 soft: bool = False):
+        self.soft = bool(soft)
         self.words = list(words) if words else None
         self.rel_threshold = float(rel_threshold)
         if not (self.rel_threshold >= 0.0) or self.rel_threshold == float("inf"):
@@ -96,8 +114,16 @@ class TextGuide:
 
     def regions(self, xq, xkv, heads: int, w: torch.Tensor, i0: int, i1: int, per_row: int):
         """(mask bool (images, N), counts int32 (images,)) of the engine batch of rows [i0, i1), each row's per_row images
-        consecutive: a row's weights are its images' weights."""
+        consecutive: a row's weights are its images' weights.  A soft guide returns the uint8 token weights in the mask's place
+        (the counts stay the hard rule's)."""
         wc = w if w.ndim == 1 else w[i0:i1].repeat_interleave(per_row, 0).contiguous()
+        if self.soft:
+            out = text_attention(xq, xkv, heads, wc, self.rel_threshold, want=("saliency", "mask", "counts"))
+            b = soft_token_bytes(out["saliency"], out["mask"], self.rel_threshold)
+            on = b.sum(dtype=torch.float64) / 255.0
+            self._on = on if self._on is None else self._on + on
+            self._seen += b.numel()
+            return b, out["counts"]
         out = text_attention(xq, xkv, heads, wc, self.rel_threshold, want=("mask", "counts"))
         on = out["counts"].sum()
         self._on = on if self._on is None else self._on + on
@@ -110,10 +136,10 @@ class TextGuide:
         return float(self._on) / self._seen if self._seen else float("nan")
 
 
-def _tap_and_guide(scorer, prompt, n, target_block, target_layer, words, rel_threshold, weights):
+def _tap_and_guide(scorer, prompt, n, target_block, target_layer, words, rel_threshold, weights, soft=False):
     if not hasattr(scorer, "features_text"):
         raise NotImplementedError(f"{type(scorer).__name__} has no text conditioning: no text attention maps")
-    guide = TextGuide(words, rel_threshold, weights)
+    guide = TextGuide(words, rel_threshold, weights, soft)
     return scorer.tap_of(target_block, target_layer), guide, guide.bind(scorer, prompt, n)
 
 
@@ -151,17 +177,21 @@ def text_attention_maps(scorer, lat, noise, prompt, target_block="up_blocks", ta
 @torch.no_grad()
 def score_latent_pairs_text(scorer, latA, latB, noiseA, noiseB, prompt, target_block="up_blocks", target_layer=0, target_step=600,
                             similarity="cosine", words: Optional[Sequence[str]] = None, rel_threshold: float = 1.0,
-                            weights: Optional[torch.Tensor] = None, batch_pairs: Optional[int] = None, return_regions: bool = False):
+                            weights: Optional[torch.Tensor] = None, batch_pairs: Optional[int] = None, return_regions: bool = False,
+                            soft: bool = False):
     """Text-guided scores of pair i = (latA[i], latB[i]): each image's region from its own text attention map, then the region
     score over the two regions -- one forward (to the tapped block's cross-attention), one text-attention call and one region tail
     per chunk of batch_pairs.  prompt: one, or one per pair (then the weights are per pair too); words: the prompt words whose
     tokens count (None: every content token); weights: the (L,) or (n, L) token weights themselves (required when the prompt is a
-    context tensor).  Returns the (n,) f32 scores on the device; return_regions: also the masks (n, 2, N) bool and counts (n, 2)."""
+    context tensor).  soft: soft regions -- the saliency becomes token weights (``soft_token_bytes``) and the tail is the soft region
+    tail.  Returns the (n,) f32 scores on the device; return_regions: also the masks (n, 2, N) bool (soft: the uint8 weights) and
+    counts (n, 2)."""
     dev = scorer.device
     n = latA.shape[0]
     if n == 0:
         raise ValueError("no pairs to score")
-    tap, guide, w = _tap_and_guide(scorer, prompt, n, target_block, target_layer, words, rel_threshold, weights)
+    tap, guide, w = _tap_and_guide(scorer, prompt, n, target_block, target_layer, words, rel_threshold, weights, soft)
+    region_tail = pair_score_weights if soft else pair_score_regions
     latA, latB = latA.to(dev, torch.float32), latB.to(dev, torch.float32)
     noiseA, noiseB = noiseA.to(dev, torch.float32), noiseB.to(dev, torch.float32)
     bound = scorer.bind_prompt(prompt, n, "pairs")
@@ -172,7 +202,7 @@ def score_latent_pairs_text(scorer, latA, latB, noiseA, noiseB, prompt, target_b
     def text_of(i0, i1, xq, xkv, heads):
         mask, cnt = guide.regions(xq, xkv, heads, w, i0, i1, 2)
         masks.append(mask), counts.append(cnt)
-        return lambda q, k, v, ia, ib, heads_, sim: pair_score_regions(q, k, v, mask, ia, ib, heads_, sim)
+        return lambda q, k, v, ia, ib, heads_, sim: region_tail(q, k, v, mask, ia, ib, heads_, sim)
     score = torch.empty(n, dtype=torch.float32, device=dev)
     for i0, i1, s in scorer.pair_chunks(latA, latB, noiseA, noiseB, bound, tap, target_step, similarity, batch_pairs, None,
                                         text_of=text_of):
@@ -186,10 +216,10 @@ def score_latent_pairs_text(scorer, latA, latB, noiseA, noiseB, prompt, target_b
 def score_path_pairs_text(scorer, pairs: Sequence[Tuple[str, str]], img_size, prompt, target_block="up_blocks", target_layer=0,
                           target_step=600, seed=2333, similarity="cosine", words: Optional[Sequence[str]] = None,
                           rel_threshold: float = 1.0, weights: Optional[torch.Tensor] = None, batch_pairs: Optional[int] = None,
-                          return_regions: bool = False, hip_vae: bool = True):
+                          return_regions: bool = False, hip_vae: bool = True, soft: bool = False):
     """Text-guided scores of (A, B) path pairs with ``score_pairs``' draw order (inputs.path_latents)."""
     if not pairs:
         raise ValueError("no pairs to score")
     (latA, latB), nA, nB = path_latents(scorer, list(pairs), (0, 1), img_size, seed, 16, hip_vae=hip_vae)
     return score_latent_pairs_text(scorer, latA, latB, nA, nB, prompt, target_block, target_layer, target_step, similarity, words,
-                                   rel_threshold, weights, batch_pairs, return_regions)
+                                   rel_threshold, weights, batch_pairs, return_regions, **({"soft": True} if soft else {}))

@@ -339,6 +339,36 @@ int    dsim_pair_score_regions(const void* q, const void* k, const void* v, cons
                                float* out_scores, int32_t* status /* NULL or [n_pairs]: 0, 1 non-finite, 2 empty region */,
                                int32_t* counts /* NULL or [n_feat] */, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- soft region scores: a weight per token instead of an on/off mask (additive to ABI v7) ---------------------------------------
+ * Every feature image i carries a byte weight per token, m_i[t] in 0 .. 255, with w_i[t] = m_i[t] / 255.  For the direction a -> b,
+ * with s(t, u) = Q_a[t] . K_x[u] / sqrt(D) per (CFG half, head):
+ *   O_ab[t] = sum_u softmax_u( s(t,u) + ln w_b[u] ) V_b[u]        (a key of weight 0 takes part in no softmax)
+ *   O_aa[t] = sum_u softmax_u( s(t,u) + ln w_a[u] ) V_a[u]
+ * both rounded to the pipeline dtype exactly where dsim_pair_score and dsim_pair_score_regions round them;
+ *   cosine: sum_t w_a[t] <O_ab[t], O_aa[t]> / max(sqrt(sum_t w_a[t] |O_ab[t]|^2) sqrt(sum_t w_a[t] |O_aa[t]|^2), eps), the sums also
+ *           over both CFG halves, all heads and D, eps = 1e-8 under each norm as dsim_pair_score's;
+ *   mse:    sum_t w_a[t] |O_ab[t] - O_aa[t]|^2 / (B H D sum_t w_a[t]), sum_t w_a[t] taken exactly as (sum of bytes) / 255;
+ * the direction b -> a is the mirror and the score is the mean of the two.  The weights are fractional multiplicities: a token of
+ * byte 2c is indistinguishable from two identical tokens of byte c.  With every byte 0 or 255 this is dsim_pair_score_regions on the
+ * mask m != 0, bit for bit; with every byte 255 it is the pair score.  The biases are log2(m / 255) from a 256-entry f32 table
+ * built in double and rounded once (entry 255 is 0.0f), added to the logits in f32 before the softmax; a query row's f32 sums are
+ * multiplied by (float)m / 255.0f.
+ *   q,k,v, idx_a, idx_b, similarity : as dsim_pair_score (index entries are not range-checked)
+ *   weights     : device uint8 [n_feat][N]
+ *   out_scores  : device f32 [n_pairs]
+ *   status      : NULL, or device int32 [n_pairs]: 0, 1 where the score is NaN or infinite, 2 where an image of the pair has byte
+ *                 sum 0 (the score is then NaN; the other pairs of the call are not affected)
+ *   weight_sums : NULL, or device int32 [n_feat]: the images' byte sums
+ * Deterministic, no atomics.  A pair's value depends on its two images and their weights alone; rows of weight 0 are never read.
+ * Refusals as dsim_pair_score_regions, and N >= 2^31 / 255: DSIM_ERR_INVALID (workspace query: 0) or DSIM_ERR_WORKSPACE, decided on
+ * the host before anything is enqueued. */
+size_t dsim_pair_score_weights_workspace_bytes(int n_feat, int n_pairs, int B, int H, int N, int D);
+int    dsim_pair_score_weights(const void* q, const void* k, const void* v, const uint8_t* weights /* [n_feat][N] */,
+                               int n_feat, const int32_t* idx_a, const int32_t* idx_b, int n_pairs,
+                               int B, int H, int N, int D, int dtype, int similarity,
+                               float* out_scores, int32_t* status /* NULL or [n_pairs]: 0, 1 non-finite, 2 zero weight */,
+                               int32_t* weight_sums /* NULL or [n_feat] */, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- region score matrices: every masked query image against every masked gallery image -------------------------------------------
  * Set A has n_a feature images and set B has n_b (q, k, v of a set: [n][B][N][H*D], as dsim_score_matrix); each image carries a
  * byte mask [N] (non-zero = on) with region R_i.  Cell (i, j) is exactly the region score of the pair (A_i, B_j) as
