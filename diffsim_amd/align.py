@@ -18,7 +18,7 @@ from typing import Optional, Sequence, Tuple
 
 import torch
 
-from .engine import pair_align, pair_align_regions
+from .engine import pair_align, pair_align_regions, pair_align_weights
 from .inputs import path_latents
 from .maps import grid_shape
 from .retrieval import ranking_names
@@ -28,13 +28,19 @@ class Alignment:
     """match (int32) and weight (f32) (n, 2, h, w), expect (f32) (n, 2, h, w, 2): pair p's direction 0 lies on image A's token
     grid and points into image B's, direction 1 the other way round; grid = (h, w), token i at (i // w, i % w), and match holds
     flat token indices of the other grid.  Built from the flat (n, 2, N) / (n, 2, N, 2) tensors of ``engine.pair_align``.
-    mask: None, or for region alignments the (n, 2, h, w) bool token masks (off tokens: match -1, weight 0, expect (-1, -1))."""
+    mask: None, or for region alignments the (n, 2, h, w) bool token masks (off tokens: match -1, weight 0, expect (-1, -1)).
+    weights: None, or for soft region alignments the (n, 2, h, w) uint8 token weights; mask is then ``weights != 0``."""
 
-    def __init__(self, match: torch.Tensor, weight: torch.Tensor, expect: torch.Tensor, mask: Optional[torch.Tensor] = None):
+    def __init__(self, match: torch.Tensor, weight: torch.Tensor, expect: torch.Tensor, mask: Optional[torch.Tensor] = None,
+                 weights: Optional[torch.Tensor] = None):
         if (match.ndim != 3 or match.shape[1] != 2 or weight.shape != match.shape or expect.shape != tuple(match.shape) + (2,)):
             raise ValueError(f"alignments must be (n, 2, N), (n, 2, N) and (n, 2, N, 2): {tuple(match.shape)}, "
                              f"{tuple(weight.shape)}, {tuple(expect.shape)}")
         n, _, N = match.shape
+        if weights is not None:
+            if weights.dtype != torch.uint8 or weights.numel() != match.numel() or weights.shape[:2] != match.shape[:2]:
+                raise ValueError(f"weights must be uint8 (n, 2, N) or (n, 2, h, w) like match: {weights.dtype}, {tuple(weights.shape)}")
+            mask = weights != 0
         self.grid = grid_shape(N)
         self.match = match.reshape(n, 2, *self.grid)
         self.weight = weight.reshape(n, 2, *self.grid)
@@ -42,6 +48,7 @@ class Alignment:
         if mask is not None and (mask.dtype != torch.bool or mask.numel() != match.numel() or mask.shape[:2] != match.shape[:2]):
             raise ValueError(f"mask must be bool (n, 2, N) or (n, 2, h, w) like match: {mask.dtype}, {tuple(mask.shape)}")
         self.mask = None if mask is None else mask.reshape(n, 2, *self.grid)
+        self.weights = None if weights is None else weights.reshape(n, 2, *self.grid)
 
     def __len__(self) -> int:
         return self.match.shape[0]
@@ -50,7 +57,7 @@ class Alignment:
         """The pairs i (an index or a slice) as an alignment of their own."""
         sl = slice(i, i + 1) if isinstance(i, int) else i
         return Alignment(self.match[sl].flatten(2), self.weight[sl].flatten(2), self.expect[sl].flatten(2, 3),
-                         None if self.mask is None else self.mask[sl])
+                         None if self.mask is None else self.mask[sl], None if self.weights is None else self.weights[sl])
 
     def points(self, size: int) -> Tuple[torch.Tensor, torch.Tensor]:
         """(src, dst), each f32 (n, 2, h, w, 2): the pixel centres (x, y) of every token and of its match on size x size images
@@ -67,16 +74,28 @@ class Alignment:
 
 @torch.no_grad()
 def score_latent_pair_alignment(scorer, latA, latB, noiseA, noiseB, prompt, target_block="up_blocks", target_layer=0,
-                                target_step=600, batch_pairs: Optional[int] = None, *, maskA=None, maskB=None) -> Alignment:
+                                target_step=600, batch_pairs: Optional[int] = None, *, maskA=None, maskB=None,
+                                soft: bool = False) -> Alignment:
     """Alignments of pair i = (latA[i] in slot A, latB[i] in slot B), any scorer kind: the pairs and the features of
     ``maps.score_latent_pair_maps``, in chunks of batch_pairs (None: ``Scorer.auto_map_pairs``) -- one feature batch and one
     ``engine.pair_align`` per chunk.
     maskA / maskB: region alignments -- the masks of ``regions.score_latent_pair_regions`` (one of them None: whole images on that
-    side); the alignment then carries the masks."""
+    side); the alignment then carries the masks.
+    soft: maskA / maskB are uint8 token weights as ``regions.score_latent_pair_weights`` takes them: the soft region alignments
+    (``engine.pair_align_weights``); the alignment then carries the weights."""
     dev = scorer.device
     n = latA.shape[0]
-    tail_of = both = None
-    if maskA is not None or maskB is not None:
+    tail_of = both = wts = None
+    if soft:
+        from .regions import pair_token_weights
+        if maskA is None and maskB is None:
+            raise ValueError("soft=True weighs masks: give maskA and / or maskB")
+        grid, wts = pair_token_weights(scorer, scorer.tap_of(target_block, target_layer), latA.shape[-1], n, maskA, maskB)
+
+        def tail_of(i0, i1):
+            chunk = wts[i0:i1].reshape(2 * (i1 - i0), -1).contiguous()
+            return lambda q, k, v, ia, ib, heads, similarity: pair_align_weights(q, k, chunk, ia, ib, heads, grid[1])
+    elif maskA is not None or maskB is not None:
         from .regions import pair_token_masks
         grid, both = pair_token_masks(scorer, scorer.tap_of(target_block, target_layer), latA.shape[-1], n, maskA, maskB)
 
@@ -101,29 +120,30 @@ def score_latent_pair_alignment(scorer, latA, latB, noiseA, noiseB, prompt, targ
         match[i0:i1], weight[i0:i1], expect[i0:i1] = m, w, e
     if match is None:
         raise ValueError("no pairs to align")
-    return Alignment(match, weight, expect, both)
+    return Alignment(match, weight, expect, both, wts)
 
 
 @torch.no_grad()
 def score_path_pair_alignment(scorer, pairs: Sequence[Tuple[str, str]], img_size, prompt, target_block="up_blocks", target_layer=0,
                               target_step=600, seed=2333, batch_pairs: Optional[int] = None, *, masks=None,
-                              hip_vae: bool = True) -> Alignment:
+                              hip_vae: bool = True, soft: bool = False) -> Alignment:
     """Alignments of (A, B) path pairs, on the latents and draws one ``diffsim(A, B, ...)`` call per pair would use
     (``inputs.path_latents``, as ``maps.score_path_pair_maps``).  masks: region alignments -- one (mask_A, mask_B) per pair as
-    ``regions.score_path_pair_regions`` takes them."""
+    ``regions.score_path_pair_regions`` takes them.  soft: the masks are soft masks (``regions.as_token_weights``)."""
     if not pairs:
         raise ValueError("no pairs to align")
     (latA, latB), nA, nB = path_latents(scorer, list(pairs), (0, 1), img_size, seed, 16, hip_vae=hip_vae)
     mA = mB = None
     if masks is not None:
-        from .regions import as_token_mask, tap_grid
+        from .regions import as_token_mask, as_token_weights, tap_grid
         if len(masks) != len(pairs):
             raise ValueError(f"{len(masks)} mask pairs for {len(pairs)} pairs")
         grid = tap_grid(scorer, scorer.tap_of(target_block, target_layer), latA.shape[-1])
-        mA = torch.stack([as_token_mask(m[0], grid) for m in masks])
-        mB = torch.stack([as_token_mask(m[1], grid) for m in masks])
+        on_grid = as_token_weights if soft else as_token_mask
+        mA = torch.stack([on_grid(m[0], grid) for m in masks])
+        mB = torch.stack([on_grid(m[1], grid) for m in masks])
     return score_latent_pair_alignment(scorer, latA, latB, nA, nB, prompt, target_block, target_layer, target_step, batch_pairs,
-                                       maskA=mA, maskB=mB)
+                                       maskA=mA, maskB=mB, soft=soft)
 
 
 def match_names(paths_a: Sequence[str], root: Optional[str] = None):
@@ -135,18 +155,20 @@ def write_match_files(out_dir: str, paths_a: Sequence[str], paths_b: Sequence[st
                       query_root: Optional[str] = None):
     """One .match.npz per query beside its ranking file: gallery (the k ranked paths), match (int32) and weight (k, 2, h, w),
     expect (k, 2, h, w, 2) -- direction 0 on the query's grid, 1 on the gallery image's.  al holds the n_a * k pairs query-major
-    (idx: (n_a, k)).  Region alignments (al.mask set) also write mask (k, 2, h, w) bool."""
+    (idx: (n_a, k)).  Region alignments (al.mask set) also write mask (k, 2, h, w) bool, soft ones (al.weights set) also
+    weights (k, 2, h, w) uint8."""
     import numpy as np
     names = match_names(paths_a, query_root)
     k = idx.shape[1]
     match, weight, expect = (t.detach().cpu().numpy() for t in (al.match, al.weight, al.expect))
     mask = None if al.mask is None else al.mask.detach().cpu().numpy()
+    wts = None if al.weights is None else al.weights.detach().cpu().numpy()
     files = []
     for i, name in enumerate(names):
         fn = os.path.join(out_dir, name)
         os.makedirs(os.path.dirname(fn), exist_ok=True)
         sl = slice(i * k, (i + 1) * k)
         np.savez(fn, gallery=np.array([paths_b[j] for j in idx[i].tolist()], dtype=str), match=match[sl], weight=weight[sl],
-                 expect=expect[sl], **({} if mask is None else {"mask": mask[sl]}))
+                 expect=expect[sl], **({} if mask is None else {"mask": mask[sl]}), **({} if wts is None else {"weights": wts[sl]}))
         files.append(fn)
     return files

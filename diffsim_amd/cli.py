@@ -93,7 +93,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--soft_masks", action="store_true",
                    help="--mask_path: soft region scores -- a mask's area average on the token grid is the token's weight (0 .. 255) "
                         "instead of being thresholded at 128, so a partly covered token counts partly, in both attentions and in the "
-                        "sums.  Masks of 0 and 255 alone on the grid give the --mask_path scores")
+                        "sums.  Masks of 0 and 255 alone on the grid give the --mask_path scores.  With --dataset retrieval and "
+                        "--query_mask_path / --gallery_mask_path: the soft score matrix; the run prints the mean token weight per side")
     p.add_argument("--text_soft", action="store_true",
                    help="--text_attn: soft text-guided regions -- a token below --text_threshold x the mean saliency keeps its share of "
                         "the threshold as a weight instead of being switched off; the run prints the mean token weight")
@@ -128,17 +129,25 @@ def build_parser() -> argparse.ArgumentParser:
 def arg_parse(argv=None):
     p = build_parser()
     args = p.parse_args(argv)
-    for flag, on, partner, has in (("--soft_masks", args.soft_masks, "--mask_path", args.mask_path is not None),
+    soft_matrix = args.soft_masks and args.dataset == "retrieval"       # the soft score matrix: its masks are the two sets' own
+    for flag, on, partner, has in (("--soft_masks", args.soft_masks and not soft_matrix, "--mask_path", args.mask_path is not None),
                                    ("--text_soft", args.text_soft, "--text_attn", args.text_attn is not None)):
         if not on:
             continue
         if not has:
             p.error(f"{flag} weighs the tokens of {partner}: it needs {partner}")
         if args.dataset == "retrieval" or args.taps is not None:
-            p.error(f"{flag} scores soft regions on the one-tap triplet benchmarks (--dataset cute or nights): --dataset retrieval and "
-                    "a sweep (--taps) are not supported with it (there are no soft score matrices)")
+            p.error(f"{flag} scores soft regions on the one-tap triplet benchmarks (--dataset cute or nights): "
+                    + ("--dataset retrieval (text-guided retrieval) and " if flag == "--text_soft" else "")
+                    + "a sweep (--taps) " + ("are" if flag == "--text_soft" else "is") + " not supported with it")
         if args.metric in VIT_METRICS or args.metric in FEATURE_METRICS:
             p.error(f"{flag}: --metric {args.metric} has no regions")
+    if soft_matrix:
+        if args.query_mask_path is None and args.gallery_mask_path is None:
+            p.error("--soft_masks with --dataset retrieval weighs the tokens of --query_mask_path / --gallery_mask_path (the soft "
+                    "score matrix): it needs one of them or both (--mask_path is the triplet benchmarks')")
+        if args.metric in VIT_METRICS or args.metric in FEATURE_METRICS:
+            p.error(f"--soft_masks: --metric {args.metric} has no regions")
     if args.metric in FEATURE_METRICS:
         if args.similarity != "cosine":
             p.error(f"--metric {args.metric} needs --similarity cosine: its score is always a cosine, as in the reference (which "
@@ -498,12 +507,22 @@ def run_retrieval(args, scorer, layer) -> int:
             if mdir is not None:
                 masks[side] = [mask_path_for(p, root, mdir) for p in paths]
                 missing += sum(1 for f in masks[side] if f is None)
-        print(f"Region score matrix: masks from {' and '.join(d for d in (args.query_mask_path, args.gallery_mask_path) if d)}; "
+        print(f"{'Soft' if args.soft_masks else 'Region'} score matrix: masks from "
+              f"{' and '.join(d for d in (args.query_mask_path, args.gallery_mask_path) if d)}; "
               f"{missing} image(s) without a mask file are scored whole")
-        if (args.save_region_maps or args.save_region_matches) and queries and gallery:
+        if args.soft_masks:
+            masks["soft"] = True
+        if (args.save_region_maps or args.save_region_matches or args.soft_masks) and queries and gallery:
             # the matrix's own latents and draws, kept for the region maps / alignments of each query's top-k cells
             (latA,), nA, _ = path_latents(scorer, [(p,) for p in queries], (0,), args.image_size, args.seed, R.ENCODE_CHUNK)
             (latB,), _, nB = path_latents(scorer, [(p,) for p in gallery], (1,), args.image_size, args.seed, R.ENCODE_CHUNK)
+            if args.soft_masks:
+                from .regions import tap_grid
+                grid = tap_grid(scorer, scorer.tap_of(args.target_block, layer), latA.shape[-1])
+                for side, n, name in (("masks_a", len(queries), "query"), ("masks_b", len(gallery), "gallery")):
+                    if side in masks:
+                        masks[side] = R.set_weights(masks[side], n, grid, "cpu", side).view(n, *grid)      # (the files are read once)
+                        print(f"Mean {name} token weight: {masks[side].double().mean().item() / 2.55:.2f}%")
             m, bad = R.score_latent_matrix(scorer, latA, latB, nA, nB, args.prompt, args.target_block, layer, args.target_step,
                                            args.similarity, return_status=True, **masks)
         else:
@@ -547,22 +566,24 @@ def run_retrieval(args, scorer, layer) -> int:
         _vals, idx = R.topk(m, args.topk, args.similarity)
         k = idx.shape[1]
         cells = idx.reshape(-1)
-        # the matrix's own token masks (a missing or empty mask: the whole image), one pair of them per top-k cell
+        # the matrix's own token masks or weights (a missing or empty mask: the whole image), one pair of them per top-k cell
         grid = tap_grid(scorer, scorer.tap_of(args.target_block, layer), latA.shape[-1])
-        mA = R._set_masks(masks.get("masks_a"), len(queries), grid, "cpu", "masks_a").repeat_interleave(k, 0)
-        mB = R._set_masks(masks.get("masks_b"), len(gallery), grid, "cpu", "masks_b")[cells.cpu()]
+        set_of = R.set_weights if args.soft_masks else R._set_masks
+        soft = {"soft": True} if args.soft_masks else {}
+        mA = set_of(masks.get("masks_a"), len(queries), grid, "cpu", "masks_a").repeat_interleave(k, 0)
+        mB = set_of(masks.get("masks_b"), len(gallery), grid, "cpu", "masks_b")[cells.cpu()]
         if args.save_region_maps:
             from . import maps as M
             mp = M.score_latent_pair_maps(scorer, latA.repeat_interleave(k, 0), latB[cells.to(latB.device)], nA, nB, args.prompt,
-                                          args.target_block, layer, args.target_step, args.similarity, maskA=mA, maskB=mB)
+                                          args.target_block, layer, args.target_step, args.similarity, maskA=mA, maskB=mB, **soft)
             mfiles = M.write_map_files(args.out_path, queries, gallery, idx, mp, args.query_path)
-            print(f"Region maps {mp.grid[0]}x{mp.grid[1]} of the top-{k} cells of {len(mfiles)} queries written to {args.out_path}")
+            print(f"{'Soft region' if args.soft_masks else 'Region'} maps {mp.grid[0]}x{mp.grid[1]} of the top-{k} cells of {len(mfiles)} queries written to {args.out_path}")
         if args.save_region_matches:
             from . import align as A
             al = A.score_latent_pair_alignment(scorer, latA.repeat_interleave(k, 0), latB[cells.to(latB.device)], nA, nB, args.prompt,
-                                               args.target_block, layer, args.target_step, maskA=mA, maskB=mB)
+                                               args.target_block, layer, args.target_step, maskA=mA, maskB=mB, **soft)
             afiles = A.write_match_files(args.out_path, queries, gallery, idx, al, args.query_path)
-            print(f"Region alignments {al.grid[0]}x{al.grid[1]} of the top-{k} cells of {len(afiles)} queries written to {args.out_path}")
+            print(f"{'Soft region' if args.soft_masks else 'Region'} alignments {al.grid[0]}x{al.grid[1]} of the top-{k} cells of {len(afiles)} queries written to {args.out_path}")
     return 0
 
 

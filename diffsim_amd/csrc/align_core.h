@@ -30,7 +30,9 @@
 // The statistics are stored by position; the outputs go to the query's token list[iq][t], match is the key's token list[ix][j], the
 // coordinates are the key token's on the full grid and attn's columns are scattered to the key tokens.  The grid being sized for N, a
 // workgroup past the query image's count, or of a pair with an empty image, leaves as a whole before any barrier: its rows are never
-// written and never read (the launcher has written the off values).
+// written and never read (the launcher has written the off values).  RowsWeighted (soft_maps.hip): RowsListed, and a key of weight w
+// enters both passes with log2(w) added to the exponent, exp2(fma(s, c, -m c) + lb[j]) with m the RAW running maximum; a query token's
+// own weight does not enter.  Byte 255 adds + 0.0f: RowsListed's bits.
 #pragma once
 #include "attn_core.h"
 
@@ -93,12 +95,27 @@ __device__ __forceinline__ void align_zero_tile(char* lds, int tid) {
     for (int o = tid * 16; o < ACfg<T, D>::TILEK; o += 256 * 16) *reinterpret_cast<u32x4*>(lds + o) = z;
 }
 
+// (weighted rows) the biases of a lane's 16 keys of block jb of key tile kt: slot r = 4 g + e is key position kt*KT + jb*32 + e + 8 g +
+// 4 half (align_key), four consecutive positions per 16-byte load; lb is zero padded to whole key tiles, so a ragged tile's loads stay
+// inside the row (those logits are -inf already)
+__device__ __forceinline__ f32x16 align_key_bias(const float* __restrict__ lb, int kt, int jb, int half) {
+    f32x16 b;
+    const float* p = lb + kt * KT + jb * 32 + 4 * half;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const f32x4 b4 = *reinterpret_cast<const f32x4*>(p + 8 * g);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) b[4 * g + e] = b4[e];
+    }
+    return b;
+}
+
 // pass 1.  grid (ceil(N/128), B*H, n_pairs*2)
 template <typename T, int D, typename Rows>
 __device__ __forceinline__ void align_stats_body(const T* __restrict__ qg, const T* __restrict__ kg, const int32_t* __restrict__ list,
                                                  const int32_t* __restrict__ cnt, const int32_t* __restrict__ idx_a,
                                                  const int32_t* __restrict__ idx_b, int B, int H, int N, float c,
-                                                 float2* __restrict__ stats) {
+                                                 float2* __restrict__ stats, typename Rows::Table wt = typename Rows::Table()) {
     typedef ACfg<T, D> C;
     __shared__ __attribute__((aligned(16))) char lds[C::TILEK];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, l31 = lane & 31;
@@ -114,6 +131,7 @@ __device__ __forceinline__ void align_stats_body(const T* __restrict__ qg, const
         if ((int)blockIdx.x * 128 >= nq || nk == 0) return;          // (uniform over the workgroup)
         rq.list = list + (size_t)iq * N;
         rx.list = list + (size_t)ix * N;
+        if constexpr (Rows::WEIGHTED) rx.lb = wt.lb + (size_t)ix * wt.stride;       // the key image's biases, by key position
     }
     const int ld = H * D;
     const size_t img = (size_t)B * N * ld, boff = (size_t)b * N * ld + h * D;
@@ -155,10 +173,21 @@ __device__ __forceinline__ void align_stats_body(const T* __restrict__ qg, const
         const float alpha = __builtin_amdgcn_exp2f(mc_new - mc);        // tile 0: exp2(-inf) = 0 against l = 0
         mc = mc_new;
         float psum = 0.f;
+        if constexpr (Rows::WEIGHTED) {
+            // the raw maximum stays the reference point; a key's bias log2(w), in [-7.995, 0], joins the exponent: the maximal key's
+            // term is at least 2^-8 and none passes 1
 #pragma unroll
-        for (int jb = 0; jb < 2; ++jb)
+            for (int jb = 0; jb < 2; ++jb) {
+                const f32x16 lb = align_key_bias(rx.lb, kt, jb, half);
 #pragma unroll
-            for (int r = 0; r < 16; ++r) psum += __builtin_amdgcn_exp2f(fmaf(s[jb][r], c, mc));
+                for (int r = 0; r < 16; ++r) psum += __builtin_amdgcn_exp2f(fmaf(s[jb][r], c, mc) + lb[r]);
+            }
+        } else {
+#pragma unroll
+            for (int jb = 0; jb < 2; ++jb)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) psum += __builtin_amdgcn_exp2f(fmaf(s[jb][r], c, mc));
+        }
         l = fmaf(l, alpha, psum);
     }
     l = half_sum(l);
@@ -171,7 +200,8 @@ __device__ __forceinline__ void align_body(const T* __restrict__ qg, const T* __
                                            const int32_t* __restrict__ cnt, const int32_t* __restrict__ idx_a,
                                            const int32_t* __restrict__ idx_b, int B, int H, int N, float c, float rbh, int grid_w,
                                            const float2* __restrict__ stats, int32_t* __restrict__ match, float* __restrict__ weight,
-                                           float* __restrict__ expect, float* __restrict__ attn, int32_t* __restrict__ status) {
+                                           float* __restrict__ expect, float* __restrict__ attn, int32_t* __restrict__ status,
+                                           typename Rows::Table wt = typename Rows::Table()) {
     typedef ACfg<T, D> C;
     __shared__ __attribute__((aligned(16))) char lds[C::TILEK];
     __shared__ float2 pos[KT];             // (row, col) of the tile's keys on the other image's grid; (0, 0) past the end
@@ -188,6 +218,7 @@ __device__ __forceinline__ void align_body(const T* __restrict__ qg, const T* __
         if ((int)blockIdx.x * 128 >= nq || nk == 0) return;          // (uniform over the workgroup)
         rq.list = list + (size_t)iq * N;
         rx.list = list + (size_t)ix * N;
+        if constexpr (Rows::WEIGHTED) rx.lb = wt.lb + (size_t)ix * wt.stride;       // the key image's biases, by key position
     }
     const int BH = B * H, ld = H * D;
     const size_t img = (size_t)B * N * ld;
@@ -238,8 +269,14 @@ __device__ __forceinline__ void align_body(const T* __restrict__ qg, const T* __
 #pragma unroll
             for (int jb = 0; jb < 2; ++jb) {           // (a block at a time: 16 logits and one block's K fragments live, not 32 and two)
                 const f32x16 s = align_logits<T, D>(qf, lds, jb, l31, half);
+                if constexpr (Rows::WEIGHTED) {
+                    const f32x16 lb = align_key_bias(rx.lb, kt, jb, half);
 #pragma unroll
-                for (int r = 0; r < 16; ++r) acc[jb][r] = fmaf(__builtin_amdgcn_exp2f(fmaf(s[r], c, ml.x)), ml.y, acc[jb][r]);
+                    for (int r = 0; r < 16; ++r) acc[jb][r] = fmaf(__builtin_amdgcn_exp2f(fmaf(s[r], c, ml.x) + lb[r]), ml.y, acc[jb][r]);
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) acc[jb][r] = fmaf(__builtin_amdgcn_exp2f(fmaf(s[r], c, ml.x)), ml.y, acc[jb][r]);
+                }
                 __builtin_amdgcn_sched_barrier(0);
             }
         }

@@ -166,6 +166,54 @@ int dsim_score_matrix_regions(const void* qa, const void* ka, const void* va, co
     return st != DSIM_OK ? st : launch_score_matrix_regions(a, dtype, out, status, counts, (hipStream_t)stream);
 }
 
+size_t dsim_pair_score_maps_weights_workspace_bytes(int n_feat, int n_pairs, int B, int H, int N, int D) {
+    return with_slack(pair_score_maps_weights_scratch_bytes(n_feat, n_pairs, B, H, N, D));
+}
+
+int dsim_pair_score_maps_weights(const void* q, const void* k, const void* v, const uint8_t* weights, int n_feat, const int32_t* idx_a,
+                                 const int32_t* idx_b, int n_pairs, int B, int H, int N, int D, int dtype, int similarity, float* score,
+                                 float* local, float* contrib, int32_t* status, int32_t* weight_sums, void* workspace,
+                                 size_t workspace_bytes, void* stream) {
+    PairArgs a{q, k, v, idx_a, idx_b, n_pairs, B, H, N, D, similarity, workspace, workspace_bytes};
+    const bool served = pair_score_maps_weights_scratch_bytes(n_feat, n_pairs, B, H, N, D) != 0;
+    const int st = tail_prologue({q, k, v, weights, idx_a, idx_b, score}, served ? pair_args_check(a, dtype) : DSIM_ERR_INVALID, a.scratch,
+                                 a.scratch_bytes);
+    return st != DSIM_OK ? st
+                         : launch_pair_score_maps_weights(a, dtype, weights, n_feat, score, local, contrib, status, weight_sums,
+                                                          (hipStream_t)stream);
+}
+
+size_t dsim_pair_align_weights_workspace_bytes(int n_feat, int n_pairs, int B, int H, int N, int D) {
+    return with_slack(pair_align_weights_scratch_bytes(n_feat, n_pairs, B, H, N, D));
+}
+
+int dsim_pair_align_weights(const void* q, const void* k, const uint8_t* weights, int n_feat, const int32_t* idx_a, const int32_t* idx_b,
+                            int n_pairs, int B, int H, int N, int D, int dtype, int grid_w, int32_t* match, float* weight, float* expect,
+                            float* attn, int32_t* status, int32_t* weight_sums, void* workspace, size_t workspace_bytes, void* stream) {
+    PairArgs a{q, k, nullptr, idx_a, idx_b, n_pairs, B, H, N, D, 0, workspace, workspace_bytes};
+    const bool served = pair_align_weights_scratch_bytes(n_feat, n_pairs, B, H, N, D) != 0;
+    const int st = tail_prologue({q, k, weights, idx_a, idx_b}, served ? pair_args_check(a, dtype) : DSIM_ERR_INVALID, a.scratch,
+                                 a.scratch_bytes);
+    return st != DSIM_OK ? st
+                         : launch_pair_align_weights(a, dtype, weights, n_feat, grid_w, match, weight, expect, attn, status, weight_sums,
+                                                     (hipStream_t)stream);
+}
+
+size_t dsim_score_matrix_weights_workspace_bytes(int n_a, int n_b, int B, int H, int N, int D, int dtype) {
+    return with_slack(score_matrix_weights_scratch_bytes(n_a, n_b, B, H, N, D, dtype));
+}
+
+int dsim_score_matrix_weights(const void* qa, const void* ka, const void* va, const uint8_t* weights_a, int n_a, const void* qb,
+                              const void* kb, const void* vb, const uint8_t* weights_b, int n_b, int B, int H, int N, int D, int dtype,
+                              int similarity, float* out, int32_t* status, int32_t* weight_sums, void* workspace, size_t workspace_bytes,
+                              void* stream) {
+    MatrixArgs a{{qa, qb}, {ka, kb}, {va, vb}, {weights_a, weights_b}, n_a, n_b, B, H, N, D, similarity, workspace, workspace_bytes};
+    const bool served = score_matrix_weights_scratch_bytes(n_a, n_b, B, H, N, D, dtype) != 0;
+    const int st = tail_prologue({qa, ka, va, weights_a, qb, kb, vb, weights_b, out},
+                                 served ? matrix_args_check(a, dtype, true) : DSIM_ERR_INVALID, a.scratch, a.scratch_bytes);
+    return st != DSIM_OK ? st : launch_score_matrix_weights(a, dtype, out, status, weight_sums, (hipStream_t)stream);
+}
+
 size_t dsim_pair_align_workspace_bytes(int n_pairs, int B, int H, int N, int D) {
     return with_slack(pair_align_scratch_bytes(n_pairs, B, H, N, D));
 }

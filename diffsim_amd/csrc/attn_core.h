@@ -173,7 +173,7 @@ struct RowsListed { static constexpr bool LISTED = true, WEIGHTED = false; const
 // key position; lb is 16-byte aligned and readable up to the end of the last 64-key tile.
 struct NoKeyBias { static constexpr bool BIASED = false; };
 struct KeyBiasLog2 { static constexpr bool BIASED = true; const float* lb; };
-// RowsWeighted (soft_regions.hip): RowsListed's rows, each with a byte weight m in 1 .. 255 -- lb[j] = log2(m / 255) of the image's
+// RowsWeighted (soft_regions.hip, soft_matrix.hip): RowsListed's rows, each with a byte weight m in 1 .. 255 -- lb[j] = log2(m / 255) of the image's
 // listed token j, the bias of key position j.  Table: the same for every image of a call, and the bytes themselves on the token grid
 // (the tails take a query row's weight from them).
 struct RowsWeighted {

@@ -79,6 +79,21 @@ int launch_pair_align_regions(const PairArgs& a, int dtype, const uint8_t* mask,
 //   out [n_a][n_b]; status (may be NULL) [n_a][n_b]: 0, 1 non-finite, 2 empty region; counts (may be NULL) [n_a + n_b]
 size_t score_matrix_regions_scratch_bytes(int n_a, int n_b, int B, int H, int N, int D, int dtype);      // 0: call not served
 int launch_score_matrix_regions(const MatrixArgs& a, int dtype, float* out, int32_t* status, int32_t* counts, hipStream_t s);
+// soft score matrix: cell (i, j) is the soft region score of (A_i, B_j) with a.mask as the two sets' weight bytes -- the region
+// matrix's launches with weighted rows -- soft_matrix.hip
+//   out [n_a][n_b]; status (may be NULL) [n_a][n_b]: 0, 1 non-finite, 2 an image of byte sum 0; weight_sums (may be NULL) [n_a + n_b]
+size_t score_matrix_weights_scratch_bytes(int n_a, int n_b, int B, int H, int N, int D, int dtype);      // 0: call not served
+int launch_score_matrix_weights(const MatrixArgs& a, int dtype, float* out, int32_t* status, int32_t* weight_sums, hipStream_t s);
+// soft region maps and soft region alignments: the two region forms above with a byte weight per token (weights [n_feat][N]) -- the
+// soft tail's biased attentions per query token, the finish applying the query weight; the alignments' softmax with the key image's
+// biases -- soft_maps.hip
+//   status (may be NULL) [n_pairs]: 0, 1 non-finite, 2 an image of byte sum 0; weight_sums (may be NULL) [n_feat]
+size_t pair_score_maps_weights_scratch_bytes(int n_feat, int n_pairs, int B, int H, int N, int D);      // 0: call not served
+int launch_pair_score_maps_weights(const PairArgs& a, int dtype, const uint8_t* weights, int n_feat, float* score, float* local,
+                                   float* contrib, int32_t* status, int32_t* weight_sums, hipStream_t s);
+size_t pair_align_weights_scratch_bytes(int n_feat, int n_pairs, int B, int H, int N, int D);      // 0: call not served
+int launch_pair_align_weights(const PairArgs& a, int dtype, const uint8_t* weights, int n_feat, int grid_w, int32_t* match, float* weight,
+                              float* expect, float* attn, int32_t* status, int32_t* weight_sums, hipStream_t s);
 // text attention maps: the tapped block's cross-attention on the conditional CFG half, averaged over the heads; its weighted sum over
 // the prompt tokens (saliency) and the token region above rel_threshold x the image's mean saliency (text_attn_kernel,
 // text_region_kernel, any head dim and dtype, 1 <= L <= 128) -- textattn.hip

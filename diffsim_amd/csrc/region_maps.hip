@@ -9,7 +9,7 @@
 //                            count, or of a pair with an empty image, leaves before any barrier and writes nothing
 //   the map finish           pair_map_finish_kernel<RowsListed> (tail_core.h): the in-order finish's folds over t < cnt, scattered to
 //                            token list[t]; zeros at the off tokens; an empty region reported (NaN, status 2, zero maps)
-//   region_align_off_kernel  the off values of the alignments (match -1, weight 0, expect (-1, -1)) at every off query token and on
+//   region_align_off_kernel  (region_maps_core.h) the off values of the alignments (match -1, weight 0, expect (-1, -1)) at every off query token and on
 //                            every row of a pair with an empty image, and the status word of each pair (0, or 2 for an empty image)
 //   region_align_stats_kernel / region_align_kernel
 //                            align_core.h's two passes with listed rows: keys gathered through the key image's list, queries through
@@ -17,8 +17,7 @@
 // With every region full the outputs are dsim_pair_score_maps' and dsim_pair_align's bits.
 // The kernels are instantiated here, not in tails.hip or align.hip, for regions.hip's reason: in a translation unit of their own they
 // cannot move the register allocation or the code of the existing tails.
-#include "align_core.h"
-#include "tail_core.h"
+#include "region_maps_core.h"
 
 namespace dsim {
 namespace {
@@ -52,40 +51,6 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void region_align_ke
                                                        int32_t* __restrict__ match, float* __restrict__ weight, float* __restrict__ expect,
                                                        float* __restrict__ attn, int32_t* __restrict__ status) {
     align_body<T, D, RowsListed>(qg, kg, list, cnt, idx_a, idx_b, B, H, N, c, rbh, grid_w, stats, match, weight, expect, attn, status);
-}
-
-// One workgroup per (pair, direction): the off values at the rows region_align_kernel does not write -- the off query tokens, and
-// every token when an image of the pair is empty -- and, from direction 0's first thread, the pair's status word.  Together with
-// region_align_kernel every element of match, weight and expect has one writer.
-constexpr int OFF_THREADS = 256;
-__global__ __launch_bounds__(OFF_THREADS) void region_align_off_kernel(const uint8_t* __restrict__ mask, const int32_t* __restrict__ cnt,
-                                                                       const int32_t* __restrict__ idx_a, const int32_t* __restrict__ idx_b,
-                                                                       int N, int32_t* __restrict__ match, float* __restrict__ weight,
-                                                                       float* __restrict__ expect, int32_t* __restrict__ status) {
-    const int pd = blockIdx.x, pair = pd >> 1, dir = pd & 1;
-    const int ia = idx_a[pair], ib = idx_b[pair];
-    const bool empty = cnt[ia] == 0 || cnt[ib] == 0;
-    const uint8_t* m = mask + (size_t)(dir ? ib : ia) * N;
-    for (int i = threadIdx.x; i < N; i += OFF_THREADS) {
-        if (!empty && m[i] != 0) continue;
-        const size_t o = (size_t)pd * N + i;
-        if (match) match[o] = -1;
-        if (weight) weight[o] = 0.f;
-        if (expect) *reinterpret_cast<float2*>(expect + 2 * o) = make_float2(-1.f, -1.f);
-    }
-    if (status && dir == 0 && threadIdx.x == 0) status[pair] = empty ? 2 : 0;
-}
-
-// workspace: [lists int32 [n_feat][N] | counts int32 [n_feat] | the call's partials or statistics], each 256-byte aligned
-struct RegionLayout {
-    size_t lists, counts;
-    RegionLayout(int n_feat, int N) : lists(up256((size_t)n_feat * N * sizeof(int32_t))), counts(up256((size_t)n_feat * sizeof(int32_t))) {}
-    int32_t* list(void* ws) const { return (int32_t*)ws; }
-    int32_t* cnt(void* ws) const { return (int32_t*)((char*)ws + lists); }
-    void* rest(void* ws) const { return (char*)ws + lists + counts; }
-};
-bool region_call_served(int n_feat, int n_pairs, int B, int H, int N, int D) {
-    return n_feat >= 1 && pair_shape_served(n_pairs, B, H, N, D) && (long)n_feat * N < (1l << 31);
 }
 
 template <typename T>

@@ -8,7 +8,7 @@
 //   the lists              regions.hip's region_lists_kernel (through launch_region_lists, the one source of it) over the n_a + n_b
 //                          masks into one list array: set A's images at index i, set B's at n_a + j.  The two sets' masks arrive as
 //                          two arrays, so it is one launch per set
-//   cell_index_kernel      idx_a[c] = c / n_b, idx_b[c] = n_a + c % n_b: what the finish reads the two counts of a cell through
+//   cell_index_kernel      (matrix_cells.h) idx_a[c] = c / n_b, idx_b[c] = n_a + c % n_b: what the finish reads the two counts of a cell through
 //   region_matrix_kernel   the score matrix's kernel (tails.hip launches it with the rows in order) -- the same source text,
 //                          tail_core.h's matrix_tail_kernel: the self mode once per image, the cross mode once per cell and
 //                          direction -- instantiated with the rows taken through the lists (RowsListed): the images' counts where
@@ -17,7 +17,7 @@
 // No atomics: every output has one writer, a cell depends on its two images alone.  The grids are sized for N, the counts being on
 // the device (the worst case, as region_tail_kernel's).  A translation unit of its own for regions.hip's reason: one more attend
 // instantiation per head dim and dtype cannot move the register allocation of the kernels that exist.
-#include "tail_core.h"
+#include "matrix_cells.h"
 
 namespace dsim {
 namespace {
@@ -26,14 +26,6 @@ namespace {
 // grid  self: (ceil(N/128), B*H, n_a + n_b);  cross: (ceil(N/128) * n_cells * 2, B*H)
 template <typename T, int D>
 constexpr auto region_matrix_kernel = matrix_tail_kernel<T, D, RowsListed>;
-
-// the cells' images among the n_a + n_b lists, for pair_finish_kernel<true>
-__global__ void cell_index_kernel(int n_a, int n_b, int32_t* __restrict__ idx_a, int32_t* __restrict__ idx_b) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= n_a * n_b) return;
-    idx_a[c] = c / n_b;
-    idx_b[c] = n_a + c % n_b;
-}
 
 template <typename T>
 int launch_regmat_t(const MatrixArgs& a, float* out, int32_t* status, int32_t* counts, hipStream_t s) {

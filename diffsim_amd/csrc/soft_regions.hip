@@ -5,12 +5,12 @@
 // identical tokens of byte c.
 //
 //   the lists             regions.hip's region_lists_kernel over m != 0 (launch_region_lists, the one source of it)
-//   soft_weights_kernel   per image: the listed tokens' biases log2(m / 255) by compacted position -- from a 256-entry f32 table the host
+//   soft_weights_kernel   (soft_core.h) per image: the listed tokens' biases log2(m / 255) by compacted position -- from a 256-entry f32 table the host
 //                         builds in double and rounds once (entry 255 is 0.0f, entry 1 about -7.99), padded with zeros to whole
 //                         64-key tiles -- and the image's byte sum
 //   soft_tail_kernel      pair_tail_body (tail_core.h) with RowsWeighted: the region tail's program text, attend with KeyBiasLog2 in
 //                         both attentions (each with the key image's biases), the lane's three sums times the query row's byte / 255
-//   soft_finish_kernel    pair_finish_kernel's fold; the mse count of a direction is B H D (byte sum of the query image) / 255 in f64;
+//   soft_finish_kernel    (soft_core.h) pair_finish_kernel's fold; the mse count of a direction is B H D (byte sum of the query image) / 255 in f64;
 //                         an image of byte sum 0: NaN, status 2
 // With every byte 0 or 255 each addition is + 0.0f and each factor 1.0f, and (255 n) / 255 is n: the region score's bits.
 //
@@ -22,56 +22,10 @@
 // and a 16 KB bias array for N = 4096 beside its tiles (54 KB) would leave it two.  So no (T, D) stages the biases.
 // In its own translation unit for regions.hip's reason: one more instantiation of attend per head dim and dtype that cannot move the
 // code of the others.
-#include <cmath>
-
-#include "tail_core.h"
+#include "soft_core.h"
 
 namespace dsim {
 namespace {
-
-constexpr int SOFT_THREADS = 256;
-
-struct BiasTable { float v[256]; };
-
-// log2(m / 255) in double, rounded once to f32; entry 0 is never read (a byte 0 is not listed)
-const BiasTable& bias_table() {
-    static const BiasTable t = [] {
-        BiasTable b;
-        b.v[0] = -INFINITY;
-        for (int m = 1; m < 256; ++m) b.v[m] = (float)std::log2((double)m / 255.0);
-        return b;
-    }();
-    return t;
-}
-
-// One workgroup per feature image: lb[img][j] = tab[m[list[j]]] for j < count, 0 from there to the row's end (stride: N rounded up
-// to whole key tiles, so attend's loads of a ragged tile stay inside the row; those logits are masked after the addition), and
-// sum[img] = the image's byte sum (also to sums_out when the caller asked).  Integer sums: the order does not matter.
-__global__ __launch_bounds__(SOFT_THREADS) void soft_weights_kernel(const BiasTable tab, const uint8_t* __restrict__ w, int N, int stride,
-                                                                    const int32_t* __restrict__ list, const int32_t* __restrict__ cnt,
-                                                                    float* __restrict__ lb, int32_t* __restrict__ sum,
-                                                                    int32_t* __restrict__ sums_out) {
-    __shared__ int wtot[SOFT_THREADS / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint8_t* m = w + (size_t)blockIdx.x * N;
-    const int32_t* l = list + (size_t)blockIdx.x * N;
-    float* o = lb + (size_t)blockIdx.x * stride;
-    const int n = cnt[blockIdx.x];
-    for (int j = tid; j < stride; j += SOFT_THREADS) o[j] = j < n ? tab.v[m[l[j]]] : 0.f;
-    int acc = 0;
-    for (int t = tid; t < N; t += SOFT_THREADS) acc += m[t];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
-    if (lane == 0) wtot[wave] = acc;
-    __syncthreads();
-    if (tid == 0) {
-        int total = 0;
-#pragma unroll
-        for (int i = 0; i < SOFT_THREADS / 64; ++i) total += wtot[i];
-        sum[blockIdx.x] = total;
-        if (sums_out) sums_out[blockIdx.x] = total;
-    }
-}
 
 // One direction of a pair in a workgroup of 128 compacted query positions: pair_tail_body with weighted listed rows.
 // grid (ceil(N/128), B*H, n_pairs*2), the region tail's.  part: [pair][dir][bh][qtile][4] f32
@@ -86,36 +40,8 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void soft_tail_kerne
                                               RowsWeighted::Table{lb, w, stride});
 }
 
-// One thread per pair: pair_finish_kernel<true>'s fold with the directions' mse counts from the byte sums, count = B H D, the
-// elements per row, times (sum of the query image's bytes) / 255 in f64; a pair with an image of byte sum 0: NaN and status 2.
-__global__ void soft_finish_kernel(const float* __restrict__ part, const int32_t* __restrict__ sum, const int32_t* __restrict__ idx_a,
-                                   const int32_t* __restrict__ idx_b, int n_pairs, int nblk, int mse, double count,
-                                   float* __restrict__ out, int32_t* __restrict__ status) {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n_pairs) return;
-    const int n[2] = {sum[idx_a[p]], sum[idx_b[p]]};
-    if (n[0] == 0 || n[1] == 0) {
-        out[p] = __builtin_nanf("");
-        if (status) status[p] = 2;
-        return;
-    }
-    double res = 0.0;
-    for (int dir = 0; dir < 2; ++dir) {
-        double a = 0.0, x2 = 0.0, y2 = 0.0;
-        const float* o = part + ((size_t)p * 2 + dir) * nblk * 4;
-        for (int i = 0; i < nblk; ++i) { a += o[4 * i]; x2 += o[4 * i + 1]; y2 += o[4 * i + 2]; }
-        res += direction_value(a, x2, y2, mse, count * ((double)n[dir] / 255.0));
-    }
-    store_score(res, out + p, status ? status + p : nullptr);
-}
-
 // workspace: [lists int32 [n_feat][N] | counts int32 [n_feat] | biases f32 [n_feat][stride] | byte sums int32 [n_feat] |
-//             partials f32 [n_pairs][2][B H][qtiles][4]], each 256-byte aligned
-int soft_stride(int N) { return (N + KT - 1) / KT * KT; }
-size_t soft_list_bytes(int n_feat, int N) { return up256((size_t)n_feat * N * sizeof(int32_t)); }
-size_t soft_count_bytes(int n_feat) { return up256((size_t)n_feat * sizeof(int32_t)); }
-size_t soft_bias_bytes(int n_feat, int N) { return up256((size_t)n_feat * soft_stride(N) * sizeof(float)); }
-
+//             partials f32 [n_pairs][2][B H][qtiles][4]], each 256-byte aligned (the sizes: soft_core.h)
 template <typename T>
 int launch_weights_t(const PairArgs& a, const uint8_t* w, int n_feat, float* out, int32_t* status, int32_t* sums, hipStream_t s) {
     int32_t* list = (int32_t*)a.scratch;

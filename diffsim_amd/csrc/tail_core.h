@@ -2,7 +2,8 @@
 // dtype, the products of a cross output against a self output, a workgroup's partial, the two-attention pair body (pair_tail_body:
 // tails.hip's pair and map kernels in row order, regions.hip's region tail and region_maps.hip's region map kernel through row
 // lists), the one-attention matrix kernel
-// (matrix_tail_kernel: tails.hip's score matrix in row order, region_matrix.hip's through row lists) with its arguments and
+// (matrix_tail_kernel: tails.hip's score matrix in row order, region_matrix.hip's through row lists, soft_matrix.hip's through
+// weighted row lists) with its arguments and
 // workspace layout, and the f64 finishes (direction_value, store_score, pair_finish_kernel, pair_map_finish_kernel and their
 // launches).  Shared by tails.hip (pairs, maps, matrices), regions.hip (region scores), region_matrix.hip (region matrices) and
 // region_maps.hip (region maps), which must round and multiply alike
@@ -177,9 +178,9 @@ __device__ __forceinline__ void pair_tail_body(const T* __restrict__ qg, const T
         settle<T, D>(oxa);
         if (t < nq) s = tail_products<T, D>(oxa, half, mse, [&](int db, int r, int) { return osa.b[db][r]; });
     }
-    if constexpr (Rows::WEIGHTED) {
+    if constexpr (Rows::WEIGHTED && !PER_TOKEN) {
         // the query row's weight on its three sums (byte 255: * 1.0f); pinned, so that the product is rounded on its own and never
-        // fused into the additions that follow
+        // fused into the additions that follow.  (Per token the partials stay unweighted: pair_map_finish_kernel applies the weight.)
         const float wq = (float)wt.bytes[(size_t)iq * N + q] / 255.0f;
         s.s0 *= wq; s.s1 *= wq; s.s2 *= wq;
         asm volatile("" : "+v"(s.s0), "+v"(s.s1), "+v"(s.s2));
@@ -221,6 +222,17 @@ struct RegMatArgs {
     const int32_t* cnt;                                         // [n_a + n_b]
     int n_a, n_b, B, H, N;
 };
+// ... and with weighted rows (soft_matrix.hip): RegMatArgs, the key biases by compacted position, the sets' weight bytes and the
+// biases' row stride; the pointers in front of the extents likewise
+struct SoftMatArgs {
+    const void* q[2]; const void* k[2]; const void* v[2];
+    void* self[2];
+    const int32_t* list;
+    const int32_t* cnt;
+    const float* lb;                                            // [n_a + n_b][stride]: log2(byte / 255) of the listed tokens, zero padded
+    const uint8_t* bytes[2];                                    // set A, set B: [n][N] weight bytes on the token grid
+    int n_a, n_b, B, H, N, stride;
+};
 
 // One attention of a 128-query workgroup, in one of two modes.  SELF: an image's self attention (rounded to the compute dtype as the
 // pair tail rounds it; f32 in the parity mode) into [n][B][N][H*D].  CROSS: one attention per cell and direction -- O_ab = SDPA(Qa, Kb,
@@ -233,17 +245,20 @@ struct RegMatArgs {
 // stores at the COMPACTED position t (row t of the image's slab holds token list[t]), so that CROSS reads it back by position without
 // an index load; a SELF workgroup whose first position is at or past its image's count leaves as a whole before any barrier (its rows
 // are never written and never read), a CROSS workgroup past the query image's count, or of a cell with an empty image, writes a zero
-// partial and leaves likewise -- pair_tail_body's rule and order.
+// partial and leaves likewise -- pair_tail_body's rule and order.  RowsWeighted: soft_matrix.hip's soft matrix (arguments:
+// SoftMatArgs): RowsListed, every attend with the key image's biases (SELF: the image's own), and CROSS multiplies the lane's three
+// sums by the query row's byte / 255, pinned as pair_tail_body pins it; every byte 255: RowsListed's bits.
 // The shared text is the kernel itself, not an inline body under two wrapper kernels: hipcc optimises such a body as a function of
 // its own before it inlines it, and the kernels then come out in another instruction order than written directly ("Region
 // score matrices").  Each translation unit instantiates only the row order it launches.  Args is a parameter only so that the symbol
 // names the argument struct: it is MatrixKernelArgs<Rows>, nothing else.
 // grid  self: (ceil(N/128), B*H, n_a + n_b);  cross: (ceil(N/128) * n_cells * 2, B*H)
-template <typename Rows> using MatrixKernelArgs = std::conditional_t<Rows::LISTED, RegMatArgs, MatArgs>;
+template <typename Rows>
+using MatrixKernelArgs = std::conditional_t<Rows::WEIGHTED, SoftMatArgs, std::conditional_t<Rows::LISTED, RegMatArgs, MatArgs>>;
 template <typename T, int D, typename Rows, typename Args = MatrixKernelArgs<Rows>>
 __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void matrix_tail_kernel(const Args p, float scale_log2, int mse, int self_mode,
                                                                                      float* __restrict__ part) {
-    static_assert(std::is_same<Args, MatrixKernelArgs<Rows>>::value, "the in-order kernel takes MatArgs, the listed one RegMatArgs");
+    static_assert(std::is_same<Args, MatrixKernelArgs<Rows>>::value, "the in-order kernel takes MatArgs, the listed one RegMatArgs, the weighted one SoftMatArgs");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, l31 = lane & 31;
     const int bh = blockIdx.y, b = bh / p.H, h = bh - b * p.H;
@@ -284,6 +299,10 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void matrix_tail_ker
         }
         rq.list = p.list + (size_t)fq * N;
         rx.list = p.list + (size_t)fx * N;
+        if constexpr (Rows::WEIGHTED) {
+            rq.lb = p.lb + (size_t)fq * p.stride;
+            rx.lb = p.lb + (size_t)fx * p.stride;
+        }
     }
     const T* qg = (const T*)p.q[set];
     const T* kg = (const T*)p.k[set ^ (self_mode ? 0 : 1)];
@@ -295,7 +314,7 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void matrix_tail_ker
     QFrags<T, D> qf;
     load_q<T, D>(qf, qg + iq * img + boff + (size_t)q * ld, half, scale_log2);
     OAcc<T, D> oa;
-    attend<T, D, false>(qf, kg + ix * img + boff, vg + ix * img + boff, ld, nx, smem, oa, nullptr, rx);
+    attend<T, D, false>(qf, kg + ix * img + boff, vg + ix * img + boff, ld, nx, smem, oa, nullptr, rx, key_bias(rx));
     settle<T, D>(oa);
     if (self_mode) {
         if (t < nq) fold_rounded<T, D>(oa, half, 0, [&](int, int, int, int d, T y) { so[(size_t)t * ld + d] = y; return 0; });  // (no state)
@@ -303,6 +322,13 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void matrix_tail_ker
     }
     TailSums s;
     if (t < nq) s = tail_products<T, D>(oa, half, mse, [&](int, int, int d) { return (float)so[(size_t)t * ld + d]; });
+    if constexpr (Rows::WEIGHTED) {
+        // the query row's weight on its three sums, rounded on its own (pair_tail_body's lines; a lane past the count holds zero
+        // sums and the last listed row's byte: the product is zero, as there)
+        const float wq = (float)p.bytes[set][(size_t)iq * N + q] / 255.0f;
+        s.s0 *= wq; s.s1 *= wq; s.s2 *= wq;
+        asm volatile("" : "+v"(s.s0), "+v"(s.s1), "+v"(s.s2));
+    }
     if constexpr (!Rows::LISTED) o = part + ((((size_t)cell * 2 + dir) * gridDim.y + bh) * qt + qtile) * 4;
     store_block_partial(s, lane, wave, o);
 }
@@ -406,7 +432,9 @@ int launch_pair_finish(const float* part, const int32_t* cnt, const int32_t* idx
 // direction's query image -- the same strided sums and tree, so that full masks give the in-order bits -- each result goes to token
 // list[t], and the thread that owns an off token (mask byte 0) stores its zeros: every element of local and contrib has one writer.
 // The mse count of a direction is B H D times the query image's own count, as pair_finish_kernel<true>'s.  A pair with an empty
-// image: score NaN, status 2, both maps zero.
+// image: score NaN, status 2, both maps zero.  RowsWeighted (soft_maps.hip's soft maps): RowsListed with mask holding the weight
+// bytes; the partials arrive unweighted, local is the token's own value, and both folds apply the query token's byte / 255 in f64:
+// the squared norms and contrib carry it, the mse count is B H D (byte sum) / 255; bytes 0 / 255: factors of exactly 1, the listed bits.
 constexpr int MAP_FINISH_THREADS = 256;
 template <typename Rows>
 __global__ __launch_bounds__(MAP_FINISH_THREADS) void pair_map_finish_kernel(const float* __restrict__ part, const uint8_t* __restrict__ mask,
@@ -442,6 +470,8 @@ __global__ __launch_bounds__(MAP_FINISH_THREADS) void pair_map_finish_kernel(con
         float* co = contrib ? contrib + ((size_t)p * 2 + dir) * N : nullptr;
         const int nd = n[dir];
         const int32_t* lst = nullptr;
+        const uint8_t* wb = nullptr;             // (weighted) the query image's weight bytes
+        double wsum = 0.0;                       // (weighted) their sum / 255
         if constexpr (Rows::LISTED) {
             lst = list + (size_t)img[dir] * N;
             const uint8_t* m = mask + (size_t)img[dir] * N;
@@ -450,6 +480,19 @@ __global__ __launch_bounds__(MAP_FINISH_THREADS) void pair_map_finish_kernel(con
                     if (lo) lo[i] = 0.f;
                     if (co) co[i] = 0.f;
                 }
+            if constexpr (Rows::WEIGHTED) {
+                wb = m;
+                double bs = 0.0;                 // the byte sum: integers in f64, exact in any order
+                for (int i = t; i < N; i += NT) bs += (double)m[i];
+                red[0][t] = bs;
+                __syncthreads();
+                for (int s = NT / 2; s > 0; s >>= 1) {
+                    if (t < s) red[0][t] += red[0][t + s];
+                    __syncthreads();
+                }
+                wsum = red[0][0] / 255.0;
+                __syncthreads();
+            }
         }
         auto token = [&](int i) {                // the token of position i
             if constexpr (Rows::LISTED) return (int)lst[i];
@@ -460,6 +503,10 @@ __global__ __launch_bounds__(MAP_FINISH_THREADS) void pair_map_finish_kernel(con
             for (int j = 0; j < BH; ++j) a += pd[comp * plane + (size_t)j * N + i];
             return a;
         };
+        auto wof = [&](int i) {                  // (weighted) the weight of position i, byte / 255 in f64 (byte 255: exactly 1)
+            if constexpr (Rows::WEIGHTED) return (double)wb[lst[i]] / 255.0;
+            else return 1.0;
+        };
         // pass 1: local, and the direction's squared norms (cosine)
         double x2t = 0.0, y2t = 0.0;
         for (int i = t; i < nd; i += NT) {
@@ -468,7 +515,8 @@ __global__ __launch_bounds__(MAP_FINISH_THREADS) void pair_map_finish_kernel(con
                 if (lo) lo[token(i)] = (float)direction_value(a, 0.0, 0.0, mse, (double)BH * D);
             } else {
                 const double x2 = fold(1, i), y2 = fold(2, i);
-                x2t += x2; y2t += y2;
+                if constexpr (Rows::WEIGHTED) { const double w = wof(i); x2t += w * x2; y2t += w * y2; }
+                else { x2t += x2; y2t += y2; }
                 if (lo) lo[token(i)] = (float)direction_value(a, x2, y2, mse, (double)BH * D);
             }
         }
@@ -478,11 +526,15 @@ __global__ __launch_bounds__(MAP_FINISH_THREADS) void pair_map_finish_kernel(con
             if (t < s) { red[1][t] += red[1][t + s]; red[2][t] += red[2][t + s]; }
             __syncthreads();
         }
-        const double den = direction_denominator(red[1][0], red[2][0], mse, (double)BH * nd * D);
+        double den;
+        if constexpr (Rows::WEIGHTED) den = direction_denominator(red[1][0], red[2][0], mse, (double)BH * D * wsum);
+        else den = direction_denominator(red[1][0], red[2][0], mse, (double)BH * nd * D);
         // pass 2: contrib (the same fold again: the per-token sums are not kept), and the direction's total
         double ct = 0.0;
         for (int i = t; i < nd; i += NT) {
-            const double c = fold(0, i) / den;
+            double c;
+            if constexpr (Rows::WEIGHTED) c = wof(i) * fold(0, i) / den;
+            else c = fold(0, i) / den;
             ct += c;
             if (co) co[token(i)] = (float)c;
         }

@@ -417,6 +417,25 @@ class DiffSim(Scorer):
                                                target_step, seed, masks=[(mask_A, mask_B)])
 
     @torch.no_grad()
+    def soft_region_similarity_maps(self, image_A, image_B, mask_A, mask_B, img_size, prompt, target_block, target_layer, target_step,
+                                    seed="2333", similarity="cosine"):
+        """:meth:`soft_region_score` of one image pair with its per-token terms on both images' grids: a
+        :class:`~diffsim_amd.maps.SimilarityMaps` of one pair (``.weights`` holds the two uint8 token weights, ``.mask`` is
+        ``weights != 0``; zeros at the tokens of weight 0).  ``local`` is a token's own value, ``contrib`` carries its weight.
+        Masks as :meth:`soft_region_score` takes them."""
+        return maps.score_path_pair_maps(self, [(image_A, image_B)], img_size, prompt, target_block, _norm_layer(target_layer),
+                                         target_step, seed, similarity, masks=[(mask_A, mask_B)], soft=True)
+
+    @torch.no_grad()
+    def soft_region_alignment(self, image_A, image_B, mask_A, mask_B, img_size, prompt, target_block, target_layer, target_step,
+                              seed="2333"):
+        """:meth:`region_alignment` with soft masks: every softmax runs over the other image's tokens of weight > 0 with ln(weight)
+        added to the logits (an :class:`~diffsim_amd.align.Alignment` of one pair; ``.weights`` holds the two uint8 token weights;
+        tokens of weight 0: match -1).  Masks as :meth:`soft_region_score` takes them."""
+        return align.score_path_pair_alignment(self, [(image_A, image_B)], img_size, prompt, target_block, _norm_layer(target_layer),
+                                               target_step, seed, masks=[(mask_A, mask_B)], soft=True)
+
+    @torch.no_grad()
     def text_region_score(self, image_A, image_B, img_size, prompt, target_block, target_layer, target_step, seed="2333",
                           similarity="cosine", words=None, rel_threshold=1.0):
         """:meth:`diffsim` of the part of each image the prompt names (textattn.py; the reference's declared and unbuilt

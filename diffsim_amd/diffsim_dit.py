@@ -158,6 +158,21 @@ class diffsim_DiT(Scorer):
         return align.score_path_pair_alignment(self, [(image_A, image_B)], img_size, None, "none", [int(target_layer[0])], target_step,
                                                seed, 32, masks=[(mask_A, mask_B)], hip_vae=False)
 
+    @torch.no_grad()
+    def soft_region_similarity_maps(self, image_A, image_B, mask_A, mask_B, img_size, prompt, target_block, target_layer, target_step,
+                                    seed, similarity):
+        """:meth:`soft_region_score` with its per-token terms on both images' grids (a maps.SimilarityMaps of one pair; ``.weights``
+        holds the two uint8 token weights)."""
+        return maps.score_path_pair_maps(self, [(image_A, image_B)], img_size, None, "none", [int(target_layer[0])], target_step, seed,
+                                         similarity, 32, masks=[(mask_A, mask_B)], hip_vae=False, soft=True)
+
+    @torch.no_grad()
+    def soft_region_alignment(self, image_A, image_B, mask_A, mask_B, img_size, prompt, target_block, target_layer, target_step, seed):
+        """:meth:`region_alignment` with soft masks (an align.Alignment of one pair; ``.weights`` holds the two uint8 token
+        weights)."""
+        return align.score_path_pair_alignment(self, [(image_A, image_B)], img_size, None, "none", [int(target_layer[0])], target_step,
+                                               seed, 32, masks=[(mask_A, mask_B)], hip_vae=False, soft=True)
+
     def text_region_score(self, *args, **kwargs):
         """DiT is class-conditional: it has no prompt and no cross-attention, so no text-guided regions."""
         raise NotImplementedError("diffsim_DiT has no text conditioning (a class-conditional model without cross-attention): "

@@ -223,6 +223,21 @@ class diffsim_xl(Scorer):
                                                seed, masks=[(mask_A, mask_B)], hip_vae=False)
 
     @torch.no_grad()
+    def soft_region_similarity_maps(self, image_A, image_B, mask_A, mask_B, img_size, prompt, target_block, target_layer, target_step,
+                                    seed, similarity):
+        """:meth:`soft_region_score` with its per-token terms on both images' grids (a maps.SimilarityMaps of one pair; ``.weights``
+        holds the two uint8 token weights)."""
+        return maps.score_path_pair_maps(self, [(image_A, image_B)], img_size, prompt, target_block, target_layer, target_step, seed,
+                                         similarity, masks=[(mask_A, mask_B)], hip_vae=False, soft=True)
+
+    @torch.no_grad()
+    def soft_region_alignment(self, image_A, image_B, mask_A, mask_B, img_size, prompt, target_block, target_layer, target_step, seed):
+        """:meth:`region_alignment` with soft masks (an align.Alignment of one pair; ``.weights`` holds the two uint8 token
+        weights)."""
+        return align.score_path_pair_alignment(self, [(image_A, image_B)], img_size, prompt, target_block, target_layer, target_step,
+                                               seed, masks=[(mask_A, mask_B)], hip_vae=False, soft=True)
+
+    @torch.no_grad()
     def text_region_score(self, image_A, image_B, img_size, prompt, target_block, target_layer, target_step, seed, similarity,
                           words=None, rel_threshold=1.0):
         """:meth:`diffsim_score` of the part of each image the prompt names (textattn.py): each image's region is the tokens whose

@@ -882,6 +882,85 @@ def pair_align_regions(q: torch.Tensor, k: torch.Tensor, mask: torch.Tensor, idx
     return (match, weight, expect) + tuple(e for e in (attn, status, counts) if e is not None)
 
 
+def _check_token_weights(weights_u8: torch.Tensor, n_feat: int, N: int):
+    """pair_score_weights' checks of its weights: uint8 only, (n_feat, N), contiguous"""
+    if weights_u8.dtype != torch.uint8:
+        raise _lib.DsimError("the token weights must be uint8")
+    _check_region_mask(weights_u8, n_feat, N, "the token weights")
+    if not weights_u8.is_contiguous():
+        raise _lib.DsimError("the token weights must be contiguous")
+
+
+def pair_score_maps_weights(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, weights_u8: torch.Tensor, idx_a: torch.Tensor,
+                            idx_b: torch.Tensor, heads: int, similarity: str = "cosine", return_status: bool = False,
+                            return_sums: bool = False):
+    """The soft region score kept per query token (dsim_pair_score_maps_weights): pair_score_maps_regions for pair_score_weights.
+    q,k,v, weights_u8, idx: as pair_score_weights.  Returns f32 device tensors (score (n,), local (n, 2, N), contrib (n, 2, N)) on the
+    full token grid: at a token of weight > 0, local is the token's own cosine (or mean squared difference) inside the biased
+    attentions, not weighted by its own weight, and contrib its weighted term of the soft score, score = 0.5 * contrib.sum((1, 2));
+    at a token of weight 0 both are exactly 0.  With every byte 0 or 255 the outputs are pair_score_maps_regions' bits.
+    return_status: also an int32 (n,) tensor, 1 where the score is NaN / infinite, 2 where an image of the pair has no weight
+    (score NaN, maps zero); return_sums: also the int32 (n_feat,) byte sums."""
+    _require_cuda(q, k, v, weights_u8, idx_a, idx_b)
+    sim = _similarity_code(similarity)
+    B, N, D = _check_features((q, k, v), heads, k.shape == q.shape == v.shape, _PAIR_MSGS, (idx_a, idx_b))
+    _check_token_weights(weights_u8, q.shape[0], N)
+    n_feat, n_pairs = q.shape[0], idx_a.numel()
+    dev = q.device
+    score = torch.empty(n_pairs, dtype=torch.float32, device=dev)
+    local = torch.empty((n_pairs, 2, N), dtype=torch.float32, device=dev)
+    contrib = torch.empty((n_pairs, 2, N), dtype=torch.float32, device=dev)
+    status = _i32(n_pairs, dev, return_status)
+    sums = _i32(n_feat, dev, return_sums)
+    _tail_call(dev, "pair_score_maps_weights", (n_feat, n_pairs, B, heads, N, D),
+               f"no soft region maps for n_feat={n_feat} n_pairs={n_pairs} B={B} H={heads} N={N} D={D}", q.data_ptr(), k.data_ptr(),
+               v.data_ptr(), weights_u8.data_ptr(), n_feat, idx_a.data_ptr(), idx_b.data_ptr(), n_pairs, B, heads, N, D, _TORCH2DSIM[q.dtype],
+               sim, score.data_ptr(), local.data_ptr(), contrib.data_ptr(), _ptr(status), _ptr(sums))
+    return (score, local, contrib) + tuple(e for e in (status, sums) if e is not None)
+
+
+def pair_align_weights(q: torch.Tensor, k: torch.Tensor, weights_u8: torch.Tensor, idx_a: torch.Tensor, idx_b: torch.Tensor, heads: int,
+                       grid_w: Optional[int] = None, return_attention: bool = False, return_status: bool = False,
+                       return_sums: bool = False):
+    """Soft region alignments (dsim_pair_align_weights): pair_align_regions with the softmax of a query token taken over the keys of
+    weight > 0 with ln(weight) added to each logit.  q,k, idx, grid_w: as pair_align; weights_u8: as pair_score_weights.  A query
+    token's own weight does not enter; query tokens of weight 0 carry match -1, weight 0, expect (-1, -1).  Returns (match int32
+    (n, 2, N), weight f32 (n, 2, N), expect f32 (n, 2, N, 2)) on the full token grid.  return_attention: also the probabilities, f32
+    (n, 2, N, N), zero at rows and columns of weight 0, in calls of fewer than 2 GiB each; return_status: also an int32 (n,) tensor, 1
+    where a pair has a non-finite probability, 2 where an image of the pair has no weight; return_sums: also the int32 (n_feat,) byte
+    sums.  With every byte 0 or 255 the outputs are pair_align_regions' bits."""
+    _require_cuda(q, k, weights_u8, idx_a, idx_b)
+    B, N, D = _check_features((q, k), heads, k.shape == q.shape, _PAIR_MSGS, (idx_a, idx_b))
+    _check_token_weights(weights_u8, q.shape[0], N)
+    if grid_w is None:
+        grid_w = math.isqrt(N)
+        if grid_w * grid_w != N:
+            raise _lib.DsimError(f"{N} tokens do not form a square grid: name grid_w")
+    n_feat, n_pairs = q.shape[0], idx_a.numel()
+    dev = q.device
+    match = torch.empty((n_pairs, 2, N), dtype=torch.int32, device=dev)
+    weight = torch.empty((n_pairs, 2, N), dtype=torch.float32, device=dev)
+    expect = torch.empty((n_pairs, 2, N, 2), dtype=torch.float32, device=dev)
+    status = _i32(n_pairs, dev, return_status)
+    sums = _i32(n_feat, dev, return_sums)
+    attn = None
+    step = _ALIGN_PAIRS
+    if return_attention:
+        step = min(step, _ATTN_BYTES // (2 * N * N * 4))
+        if step < 1:
+            raise _lib.DsimError(f"the attention of one pair of {N} tokens does not fit 2 GiB")
+        attn = torch.empty((n_pairs, 2, N, N), dtype=torch.float32, device=dev)
+    for i0 in range(0, n_pairs, step):
+        n = min(step, n_pairs - i0)
+        sl = slice(i0, i0 + n)
+        _tail_call(dev, "pair_align_weights", (n_feat, n, B, heads, N, D),
+                   f"no soft region alignments for n_feat={n_feat} n_pairs={n} B={B} H={heads} N={N} D={D}", q.data_ptr(), k.data_ptr(),
+                   weights_u8.data_ptr(), n_feat, idx_a[sl].data_ptr(), idx_b[sl].data_ptr(), n, B, heads, N, D, _TORCH2DSIM[q.dtype],
+                   int(grid_w), match[sl].data_ptr(), weight[sl].data_ptr(), expect[sl].data_ptr(),
+                   _ptr(None if attn is None else attn[sl]), _ptr(None if status is None else status[sl]), _ptr(sums))
+    return (match, weight, expect) + tuple(e for e in (attn, status, sums) if e is not None)
+
+
 def score_matrix_workspace_bytes(n_a: int, n_b: int, B: int, heads: int, N: int, D: int, dtype: torch.dtype) -> int:
     return int(_lib.lib().dsim_score_matrix_workspace_bytes(n_a, n_b, B, heads, N, D, _TORCH2DSIM[dtype]))
 
@@ -930,6 +1009,38 @@ def score_matrix_regions(fa, fb, mask_a: torch.Tensor, mask_b: torch.Tensor, hea
                mask_a.data_ptr(), n_a, qb.data_ptr(), kb.data_ptr(), vb.data_ptr(), mask_b.data_ptr(), n_b, B, heads, N, D,
                _TORCH2DSIM[qa.dtype], sim, out.data_ptr(), _ptr(status), _ptr(counts))
     return _with_extras(out, status, counts)
+
+
+def score_matrix_weights_workspace_bytes(n_a: int, n_b: int, B: int, heads: int, N: int, D: int, dtype: torch.dtype) -> int:
+    return int(_lib.lib().dsim_score_matrix_weights_workspace_bytes(n_a, n_b, B, heads, N, D, _TORCH2DSIM.get(dtype, -1)))
+
+
+def score_matrix_weights(fa, fb, weights_a: torch.Tensor, weights_b: torch.Tensor, heads: int, similarity: str = "cosine",
+                         return_status: bool = False, return_sums: bool = False):
+    """The soft score matrix (dsim_score_matrix_weights): score_matrix_regions with a weight per token instead of a bit.  fa, fb:
+    (q, k, v) tuples of [n][B][N][H*D] device tensors of one dtype; weights_a (n_a, N), weights_b (n_b, N): uint8 cuda, token t of
+    an image weighs byte / 255.  Returns the (n_a, n_b) f32 device tensor whose cell (i, j) is pair_score_weights of (fa[i] under
+    weights_a[i], fb[j] under weights_b[j]), bit for bit; each image's self-attention is computed once.  return_status: also an
+    int32 (n_a, n_b) tensor, 1 where the score is NaN / infinite, 2 where an image of the cell has no weight at all (score NaN);
+    return_sums: also the int32 (n_a + n_b,) byte sums, set A's then set B's."""
+    sim = _similarity_code(similarity)
+    (qa, ka, va, qb, kb, vb), B, N, D = _check_two_sets(fa, fb, heads)
+    n_a, n_b = qa.shape[0], qb.shape[0]
+    for w, n, name in ((weights_a, n_a, "weights_a"), (weights_b, n_b, "weights_b")):
+        if w.dtype != torch.uint8:
+            raise _lib.DsimError(f"the token weights {name} must be uint8")
+        _check_region_mask(w, n, N, f"the token weights {name}", "n")
+        if not w.is_contiguous():
+            raise _lib.DsimError(f"the token weights {name} must be contiguous")
+    _require_cuda(qa, ka, va, qb, kb, vb, weights_a, weights_b)          # (after the shape checks: those need no device)
+    out = torch.empty((n_a, n_b), dtype=torch.float32, device=qa.device)
+    status = _i32((n_a, n_b), qa.device, return_status)
+    sums = _i32(n_a + n_b, qa.device, return_sums)
+    _tail_call(qa.device, "score_matrix_weights", (n_a, n_b, B, heads, N, D, _TORCH2DSIM[qa.dtype]),
+               f"no soft score matrix for n_a={n_a} n_b={n_b} B={B} H={heads} N={N} D={D}", qa.data_ptr(), ka.data_ptr(), va.data_ptr(),
+               weights_a.data_ptr(), n_a, qb.data_ptr(), kb.data_ptr(), vb.data_ptr(), weights_b.data_ptr(), n_b, B, heads, N, D,
+               _TORCH2DSIM[qa.dtype], sim, out.data_ptr(), _ptr(status), _ptr(sums))
+    return _with_extras(out, status, sums)
 
 
 # ---- feature-cosine metrics (diffeats, dinofeats): the tapped self-attention's own output, its pair cosine and Gram matrix -------

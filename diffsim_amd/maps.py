@@ -22,7 +22,7 @@ from typing import Optional, Sequence, Tuple
 import torch
 import torch.nn.functional as F
 
-from .engine import pair_score_maps, pair_score_maps_regions
+from .engine import pair_score_maps, pair_score_maps_regions, pair_score_maps_weights
 from .inputs import path_latents
 from .retrieval import ranking_names
 
@@ -38,13 +38,19 @@ def grid_shape(n_tokens: int) -> Tuple[int, int]:
 class SimilarityMaps:
     """score (n,), local and contrib (n, 2, h, w) f32 tensors: pair p's direction 0 lies on image A's token grid, direction 1 on
     image B's; grid = (h, w), token i at (i // w, i % w).  Built from the flat (n, 2, N) maps of ``engine.pair_score_maps``.
-    mask: None, or for region maps the (n, 2, h, w) bool token masks the maps were computed over (off tokens hold zeros)."""
+    mask: None, or for region maps the (n, 2, h, w) bool token masks the maps were computed over (off tokens hold zeros).
+    weights: None, or for soft region maps the (n, 2, h, w) uint8 token weights; mask is then ``weights != 0``."""
 
-    def __init__(self, score: torch.Tensor, local: torch.Tensor, contrib: torch.Tensor, mask: Optional[torch.Tensor] = None):
+    def __init__(self, score: torch.Tensor, local: torch.Tensor, contrib: torch.Tensor, mask: Optional[torch.Tensor] = None,
+                 weights: Optional[torch.Tensor] = None):
         if local.shape != contrib.shape or local.ndim != 3 or local.shape[1] != 2 or local.shape[0] != score.shape[0]:
             raise ValueError(f"maps must be (n, 2, N) with n = len(score): {tuple(local.shape)}, {tuple(contrib.shape)}, "
                              f"{tuple(score.shape)}")
         n, _, N = local.shape
+        if weights is not None:
+            if weights.dtype != torch.uint8 or weights.numel() != local.numel() or weights.shape[:2] != local.shape[:2]:
+                raise ValueError(f"weights must be uint8 (n, 2, N) or (n, 2, h, w) like the maps: {weights.dtype}, {tuple(weights.shape)}")
+            mask = weights != 0
         self.grid = grid_shape(N)
         self.score = score
         self.local = local.reshape(n, 2, *self.grid)
@@ -52,6 +58,7 @@ class SimilarityMaps:
         if mask is not None and (mask.dtype != torch.bool or mask.numel() != local.numel() or mask.shape[:2] != local.shape[:2]):
             raise ValueError(f"mask must be bool (n, 2, N) or (n, 2, h, w) like the maps: {mask.dtype}, {tuple(mask.shape)}")
         self.mask = None if mask is None else mask.reshape(n, 2, *self.grid)
+        self.weights = None if weights is None else weights.reshape(n, 2, *self.grid)
 
     def __len__(self) -> int:
         return self.score.shape[0]
@@ -60,7 +67,7 @@ class SimilarityMaps:
         """The pairs i (an index or a slice) as maps of their own."""
         sl = slice(i, i + 1) if isinstance(i, int) else i
         return SimilarityMaps(self.score[sl], self.local[sl].flatten(2), self.contrib[sl].flatten(2),
-                              None if self.mask is None else self.mask[sl])
+                              None if self.mask is None else self.mask[sl], None if self.weights is None else self.weights[sl])
 
     def upsample(self, size: int, which: str = "local") -> torch.Tensor:
         """Bilinear (n, 2, size, size) maps for overlay on the size x size image (``img_size``); which: local or contrib."""
@@ -70,17 +77,30 @@ class SimilarityMaps:
 
 @torch.no_grad()
 def score_latent_pair_maps(scorer, latA, latB, noiseA, noiseB, prompt, target_block="up_blocks", target_layer=0, target_step=600,
-                           similarity="cosine", batch_pairs: Optional[int] = None, *, maskA=None, maskB=None) -> SimilarityMaps:
+                           similarity="cosine", batch_pairs: Optional[int] = None, *, maskA=None, maskB=None,
+                           soft: bool = False) -> SimilarityMaps:
     """Maps of pair i = (latA[i] in slot A, latB[i] in slot B), any scorer kind (DiffSim, diffsim_xl, diffsim_DiT): the pairs of
     ``score_latent_pairs``, in chunks of batch_pairs (None: ``Scorer.auto_map_pairs``) -- one feature batch and one maps launch
     per chunk.  noiseA / noiseB: (1, C, s, s) or (n, C, s, s).  target_block / target_layer: the reference's flag pair
     (``Scorer.tap_of``; DiT: [layer]).
     maskA / maskB: region maps -- the masks of ``regions.score_latent_pair_regions`` ((n, h, w) or (n, N) on the tap's grid, no row
-    empty; one of them None: whole images on that side); the score is then the region score and the maps carry the masks."""
+    empty; one of them None: whole images on that side); the score is then the region score and the maps carry the masks.
+    soft: maskA / maskB are token weights, uint8 (n, h, w) or (n, N) as ``regions.score_latent_pair_weights`` takes them: the soft
+    region maps (``engine.pair_score_maps_weights``); the score is the soft region score and the maps carry the weights."""
     dev = scorer.device
     n = latA.shape[0]
-    tail, tail_of, both = pair_score_maps, None, None
-    if maskA is not None or maskB is not None:
+    tail, tail_of, both, wts = pair_score_maps, None, None, None
+    if soft:
+        from .regions import pair_token_weights
+        if maskA is None and maskB is None:
+            raise ValueError("soft=True weighs masks: give maskA and / or maskB")
+        _grid, wts = pair_token_weights(scorer, scorer.tap_of(target_block, target_layer), latA.shape[-1], n, maskA, maskB)
+
+        def tail_of(i0, i1):
+            chunk = wts[i0:i1].reshape(2 * (i1 - i0), -1).contiguous()
+            return lambda q, k, v, ia, ib, heads, sim: pair_score_maps_weights(q, k, v, chunk, ia, ib, heads, sim)
+        tail = None
+    elif maskA is not None or maskB is not None:
         from .regions import pair_token_masks          # (regions.py imports grid_shape from here)
         _grid, both = pair_token_masks(scorer, scorer.tap_of(target_block, target_layer), latA.shape[-1], n, maskA, maskB)
 
@@ -105,30 +125,31 @@ def score_latent_pair_maps(scorer, latA, latB, noiseA, noiseB, prompt, target_bl
         score[i0:i1], local[i0:i1], contrib[i0:i1] = s, lo, co
     if score is None:
         raise ValueError("no pairs to map")
-    return SimilarityMaps(score, local, contrib, both)
+    return SimilarityMaps(score, local, contrib, both, wts)
 
 
 @torch.no_grad()
 def score_path_pair_maps(scorer, pairs: Sequence[Tuple[str, str]], img_size, prompt, target_block="up_blocks", target_layer=0,
                          target_step=600, seed=2333, similarity="cosine", batch_pairs: Optional[int] = None, *, masks=None,
-                         hip_vae: bool = True) -> SimilarityMaps:
+                         hip_vae: bool = True, soft: bool = False) -> SimilarityMaps:
     """Maps of (A, B) path pairs: what one ``diffsim(A, B, ...)`` call per pair would score (``score_pairs``' draw order), with
     each pair's per-token terms on both images' grids.
     masks: region maps -- one (mask_A, mask_B) per pair as ``regions.score_path_pair_regions`` takes them (each a path, a PIL
-    image, a bool array on the token grid or None)."""
+    image, a bool array on the token grid or None).  soft: the masks are soft masks (``regions.as_token_weights``)."""
     if not pairs:
         raise ValueError("no pairs to map")
     (latA, latB), nA, nB = path_latents(scorer, list(pairs), (0, 1), img_size, seed, 16, hip_vae=hip_vae)
     mA = mB = None
     if masks is not None:
-        from .regions import as_token_mask, tap_grid
+        from .regions import as_token_mask, as_token_weights, tap_grid
         if len(masks) != len(pairs):
             raise ValueError(f"{len(masks)} mask pairs for {len(pairs)} pairs")
         grid = tap_grid(scorer, scorer.tap_of(target_block, target_layer), latA.shape[-1])
-        mA = torch.stack([as_token_mask(m[0], grid) for m in masks])
-        mB = torch.stack([as_token_mask(m[1], grid) for m in masks])
+        on_grid = as_token_weights if soft else as_token_mask
+        mA = torch.stack([on_grid(m[0], grid) for m in masks])
+        mB = torch.stack([on_grid(m[1], grid) for m in masks])
     return score_latent_pair_maps(scorer, latA, latB, nA, nB, prompt, target_block, target_layer, target_step, similarity,
-                                  batch_pairs, maskA=mA, maskB=mB)
+                                  batch_pairs, maskA=mA, maskB=mB, soft=soft)
 
 
 def map_names(paths_a: Sequence[str], root: Optional[str] = None):
@@ -140,18 +161,19 @@ def write_map_files(out_dir: str, paths_a: Sequence[str], paths_b: Sequence[str]
                     query_root: Optional[str] = None):
     """One .npz per query beside its ranking file: gallery (the k ranked paths), score (k,), local and contrib (k, 2, h, w) --
     direction 0 on the query's grid, 1 on the gallery image's.  maps holds the n_a * k pairs query-major (idx: (n_a, k)).  Region
-    maps (maps.mask set) also write mask (k, 2, h, w) bool."""
+    maps (maps.mask set) also write mask (k, 2, h, w) bool, soft region maps (maps.weights set) also weights (k, 2, h, w) uint8."""
     import numpy as np
     names = map_names(paths_a, query_root)
     k = idx.shape[1]
     score, local, contrib = (t.detach().float().cpu().numpy() for t in (maps.score, maps.local, maps.contrib))
     mask = None if maps.mask is None else maps.mask.detach().cpu().numpy()
+    wts = None if maps.weights is None else maps.weights.detach().cpu().numpy()
     files = []
     for i, name in enumerate(names):
         fn = os.path.join(out_dir, name)
         os.makedirs(os.path.dirname(fn), exist_ok=True)
         sl = slice(i * k, (i + 1) * k)
         np.savez(fn, gallery=np.array([paths_b[j] for j in idx[i].tolist()], dtype=str), score=score[sl], local=local[sl],
-                 contrib=contrib[sl], **({} if mask is None else {"mask": mask[sl]}))
+                 contrib=contrib[sl], **({} if mask is None else {"mask": mask[sl]}), **({} if wts is None else {"weights": wts[sl]}))
         files.append(fn)
     return files

@@ -163,6 +163,16 @@ def pair_token_masks(scorer, tap, latent_side: int, n: int, maskA, maskB):
     return grid, torch.stack([mA, mB], dim=1).to(scorer.device)
 
 
+def pair_token_weights(scorer, tap, latent_side: int, n: int, weightA, weightB):
+    """``pair_token_masks`` for soft masks: ((h, w), (n, 2, N) uint8 on the scorer's device); weightA / weightB as
+    ``score_latent_pair_weights`` takes them, either may be None (whole images, byte 255)."""
+    grid = tap_grid(scorer, tap, latent_side)
+    whole = torch.full((n, grid[0] * grid[1]), 255, dtype=torch.uint8)
+    wA = whole if weightA is None else _flat_weights(weightA, n, grid, "weightA")
+    wB = whole if weightB is None else _flat_weights(weightB, n, grid, "weightB")
+    return grid, torch.stack([wA, wB], dim=1).to(scorer.device)
+
+
 @torch.no_grad()
 def score_latent_pair_regions(scorer, latA, latB, noiseA, noiseB, maskA, maskB, prompt, target_block="up_blocks", target_layer=0,
                               target_step=600, similarity="cosine", batch_pairs: Optional[int] = None) -> torch.Tensor:

@@ -11,7 +11,9 @@ Query features are computed once and kept; the gallery runs in chunks of the sco
 
 With ``masks_a`` / ``masks_b`` every image carries a token mask on the tap's grid and the matrix is the region score matrix
 (``engine.score_matrix_regions``): cell (i, j) is ``regions.score_latent_pair_regions`` of that pair -- the masked object is
-retrieved, the background takes part in no softmax -- at the same n_a + n_b forwards.
+retrieved, the background takes part in no softmax -- at the same n_a + n_b forwards.  With ``soft=True`` the masks are token
+weights (``regions.as_token_weights``) and the matrix is the soft score matrix (``engine.score_matrix_weights``): cell (i, j) is
+``regions.score_latent_pair_weights`` of that pair.
 
 A scorer with a matrix tail of its own (``Scorer.matrix_tail``: the feature-cosine metrics of ``feats.py``) ranks through it: what the
 query set contributes is computed once per call, each gallery chunk's once, and one ``engine.feature_matrix`` per chunk.
@@ -24,7 +26,8 @@ from typing import List, Optional, Sequence
 import torch
 
 from ._lib import DsimError
-from .engine import score_matrix, score_matrix_regions, score_matrix_regions_workspace_bytes, score_matrix_workspace_bytes
+from .engine import (score_matrix, score_matrix_regions, score_matrix_regions_workspace_bytes, score_matrix_weights,
+                     score_matrix_weights_workspace_bytes, score_matrix_workspace_bytes)
 from .inputs import path_latents
 from .scorer import stack_rows
 
@@ -65,16 +68,33 @@ def _set_masks(masks, n: int, grid, dev, name: str) -> torch.Tensor:
     return m.to(dev).contiguous()
 
 
+def set_weights(masks, n: int, grid, dev, name: str) -> torch.Tensor:
+    """_set_masks for soft masks: (n, N) uint8 on dev, one row of token weights per image of a set (``regions.as_token_weights``:
+    paths, PIL images, arrays on the grid, None entries); masks None: whole images (255).  An image whose weights are all 0 is the
+    whole image, as an empty mask is."""
+    from .regions import as_token_weights
+    if masks is None:
+        return torch.full((n, grid[0] * grid[1]), 255, dtype=torch.uint8, device=dev)
+    if len(masks) != n:
+        raise ValueError(f"{name}: {len(masks)} masks for {n} images")
+    w = torch.stack([as_token_weights(m, grid) for m in masks]).reshape(n, -1) if n else torch.zeros((0, grid[0] * grid[1]), dtype=torch.uint8)
+    w = torch.where((w != 0).any(1, keepdim=True), w, torch.full_like(w, 255))
+    return w.to(dev).contiguous()
+
+
 @torch.no_grad()
 def score_latent_matrix(scorer, latA, latB, noiseA, noiseB, prompt, target_block="up_blocks", target_layer=0, target_step=600,
-                        similarity="cosine", batch: Optional[int] = None, return_status: bool = False, *, masks_a=None, masks_b=None):
+                        similarity="cosine", batch: Optional[int] = None, return_status: bool = False, *, masks_a=None, masks_b=None,
+                        soft: bool = False):
     """(n_a, n_b) f32 device tensor: query latents latA in slot A (noiseA), gallery latents latB in slot B (noiseB), any
     scorer kind (DiffSim, diffsim_xl, diffsim_DiT).  noiseA / noiseB: (1, C, s, s), shared by every pair as in the reference.
     batch: gallery images per chunk (None: the images of the triplet engine batch, ``Scorer.auto_rows``).
     return_status: also the number of NaN / infinite cells.
     masks_a / masks_b: one token mask per query / gallery image on the tap's grid (``regions.tap_grid``; each a path, a PIL image,
     a bool array (h, w) or (N,), or None) -- the region score matrix; given only one, the other side is whole images; both None: the
-    score matrix."""
+    score matrix.
+    soft: the masks are token weights (``regions.as_token_weights``: a mask file's area average per token, uint8 bytes, floats in
+    [0, 1]) and the matrix is the soft score matrix; an image whose weights are all 0 is the whole image."""
     dev = scorer.device
     latA = latA.to(dev, torch.float32)
     latB = latB.to(dev, torch.float32)
@@ -103,8 +123,13 @@ def score_latent_matrix(scorer, latA, latB, noiseA, noiseB, prompt, target_block
     if masked:
         from .regions import tap_grid
         grid = tap_grid(scorer, tap, latA.shape[-1])
-        masks_a, masks_b = _set_masks(masks_a, n_a, grid, dev, "masks_a"), _set_masks(masks_b, n_b, grid, dev, "masks_b")
-    workspace_bytes = score_matrix_regions_workspace_bytes if masked else score_matrix_workspace_bytes
+        set_of = set_weights if soft else _set_masks
+        masks_a, masks_b = set_of(masks_a, n_a, grid, dev, "masks_a"), set_of(masks_b, n_b, grid, dev, "masks_b")
+    elif soft:
+        raise DsimError("soft=True weighs masks: give masks_a and / or masks_b")
+    workspace_bytes = score_matrix_workspace_bytes
+    if masked:
+        workspace_bytes = score_matrix_weights_workspace_bytes if soft else score_matrix_regions_workspace_bytes
     if mtail is not None:
         workspace_bytes = mtail.workspace_bytes
         ga = mtail.features(fa, heads)          # the query set's share of every chunk's matrix, once per call
@@ -119,6 +144,9 @@ def score_latent_matrix(scorer, latA, latB, noiseA, noiseB, prompt, target_block
         fb = _features(scorer, latB[j0:j1], nB, prompt, tap, target_step, batch)
         if mtail is not None:
             s, st = mtail.matrix(ga, mtail.features(fb, heads))
+        elif masked and soft:
+            s, st = score_matrix_weights(fa, fb, masks_a, masks_b[j0:j1].contiguous(), heads, similarity, return_status=True)
+            st = st != 0
         elif masked:
             s, st = score_matrix_regions(fa, fb, masks_a, masks_b[j0:j1], heads, similarity, return_status=True)
             st = st != 0
@@ -132,18 +160,18 @@ def score_latent_matrix(scorer, latA, latB, noiseA, noiseB, prompt, target_block
 @torch.no_grad()
 def score_path_matrix(scorer, paths_a: Sequence[str], paths_b: Sequence[str], img_size, prompt, target_block="up_blocks",
                       target_layer=0, target_step=600, seed=2333, similarity="cosine", batch: Optional[int] = None,
-                      return_status: bool = False, *, masks_a=None, masks_b=None):
+                      return_status: bool = False, *, masks_a=None, masks_b=None, soft: bool = False):
     """The (len(paths_a), len(paths_b)) matrix of ``diffsim(paths_a[i], paths_b[j], ...)`` scores: the query images are
     encoded with the reseeded generator's slot-A VAE draw and noise, the gallery images with the slot-B ones
     (``inputs.path_latents``).  Through the scorer's HIP VAE fast path where it has one.  masks_a / masks_b: as
-    ``score_latent_matrix`` takes them, one per path."""
+    ``score_latent_matrix`` takes them, one per path; soft: as there."""
     if not paths_a or not paths_b:
         empty = torch.empty((len(paths_a), len(paths_b)), dtype=torch.float32, device=scorer.device)
         return (empty, 0) if return_status else empty
     (latA,), nA, _ = path_latents(scorer, [(p,) for p in paths_a], (0,), img_size, seed, ENCODE_CHUNK)
     (latB,), _, nB = path_latents(scorer, [(p,) for p in paths_b], (1,), img_size, seed, ENCODE_CHUNK)
     return score_latent_matrix(scorer, latA, latB, nA, nB, prompt, target_block, target_layer, target_step, similarity, batch,
-                               return_status, masks_a=masks_a, masks_b=masks_b)
+                               return_status, masks_a=masks_a, masks_b=masks_b, soft=soft)
 
 
 def topk(matrix: torch.Tensor, k: int, similarity: str = "cosine"):

@@ -392,6 +392,28 @@ int    dsim_score_matrix_regions(const void* qa, const void* ka, const void* va,
                                  int32_t* counts /* NULL or [n_a + n_b] */,
                                  void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- soft score matrices: every weighted query image against every weighted gallery image (additive to ABI v7) -------------------
+ * dsim_score_matrix_regions with weight bytes for the masks: set A's images carry weights_a [n_a][N], set B's weights_b [n_b][N],
+ * w = byte / 255.  Cell (i, j) is dsim_pair_score_weights of the pair (A_i, B_j), bit for bit, in every dtype and at every head
+ * dim: tokens of byte 0 are dropped, every softmax carries the key image's biases log2(byte / 255) (the same 256-entry table), a
+ * query row's f32 sums are multiplied by (float)byte / 255.0f, and the mse count of a direction is B H D (byte sum) / 255 in f64.
+ * Each image's self-attention (with its own biases) is computed once; a cell costs one attention per direction.
+ * With bytes 0 / 255 only the cell is dsim_score_matrix_regions' on m != 0, bit for bit; with every byte 255 dsim_score_matrix's
+ * tiled cell.  A cell with an image of byte sum 0 is NaN with status 2, and no other cell is disturbed.
+ *   out         : device f32 [n_a][n_b]
+ *   status      : NULL, or device int32 [n_a][n_b]: 0, 1 where the score is NaN or infinite, 2 where an image of the cell has byte sum 0
+ *   weight_sums : NULL, or device int32 [n_a + n_b]: the byte sums of set A's images, then of set B's
+ * Deterministic, no atomics; a cell depends on its two images and their weights alone; rows of weight 0 are never read.
+ * Refusals as dsim_score_matrix_regions, and N 255 >= 2^31 or (n_a + n_b) (N rounded up to 64) >= 2^31: DSIM_ERR_INVALID (workspace
+ * query: 0) or DSIM_ERR_WORKSPACE, decided on the host before anything is enqueued. */
+size_t dsim_score_matrix_weights_workspace_bytes(int n_a, int n_b, int B, int H, int N, int D, int dtype);
+int    dsim_score_matrix_weights(const void* qa, const void* ka, const void* va, const uint8_t* weights_a, int n_a,
+                                 const void* qb, const void* kb, const void* vb, const uint8_t* weights_b, int n_b,
+                                 int B, int H, int N, int D, int dtype, int similarity,
+                                 float* out /* [n_a][n_b] */, int32_t* status /* NULL or [n_a][n_b]: 0 | 1 | 2 */,
+                                 int32_t* weight_sums /* NULL or [n_a + n_b] */,
+                                 void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- region maps: the region score per query token (additive to ABI v7) ---------------------------------------------------------
  * dsim_pair_score_maps for dsim_pair_score_regions: the region tail's own attentions, rounding and products, kept per query token.
  * Outputs lie on the full token grid.  For direction 0 (image idx_a[p] over idx_b[p]; direction 1 the mirror) and an on token i:
@@ -433,6 +455,46 @@ int    dsim_pair_align_regions(const void* q, const void* k, const uint8_t* mask
                                int B, int H, int N, int D, int dtype, int grid_w,
                                int32_t* match, float* weight, float* expect, float* attn,
                                int32_t* status /* NULL or [n_pairs]: 0 | 1 | 2 */, int32_t* counts /* NULL or [n_feat] */,
+                               void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- soft region maps: the soft region score per query token (additive to ABI v7) ------------------------------------------------
+ * dsim_pair_score_maps_regions for dsim_pair_score_weights: weights [n_feat][N] bytes, w = byte / 255, in place of the mask.  For the
+ * direction a -> b and a query token t with w_a[t] > 0, both attentions are biased as in the soft score and rounded where the tails
+ * round; with dot_t, x2_t, y2_t (cosine) or sqd_t (mse) the token's sums over B, H, D:
+ *   local[t]   = the token's own value, not weighted by its own weight: dot_t / (|x_t| |y_t|) with the finish's eps rule, or
+ *                sqd_t / (B H D)
+ *   contrib[t] = its term of the direction's soft value: w_a[t] dot_t / (sqrt(sum w x2) sqrt(sum w y2)), or
+ *                w_a[t] sqd_t / (B H D sum w_a), sum w_a taken as (byte sum) / 255
+ * so that 0.5 (sum contrib[p][0] + sum contrib[p][1]) is score[p], which agrees with dsim_pair_score_weights within
+ * 1e-6 max(1, |s|).  The weight enters in f64 in the finish; the per-token partials are unweighted.  Tokens of weight 0 hold +0.0f in
+ * both maps.  With bytes 0 / 255 the three outputs are dsim_pair_score_maps_regions' bits.
+ *   status      : NULL, or device int32 [n_pairs]: 0, 1 non-finite score, 2 an image of byte sum 0 (score NaN, maps zero)
+ *   weight_sums : NULL, or device int32 [n_feat]: the images' byte sums
+ * Deterministic, no atomics, every output element has one writer.  Refusals as dsim_pair_score_maps_regions and
+ * dsim_pair_score_weights, decided before anything is enqueued. */
+size_t dsim_pair_score_maps_weights_workspace_bytes(int n_feat, int n_pairs, int B, int H, int N, int D);
+int    dsim_pair_score_maps_weights(const void* q, const void* k, const void* v, const uint8_t* weights /* [n_feat][N] */,
+                                    int n_feat, const int32_t* idx_a, const int32_t* idx_b, int n_pairs,
+                                    int B, int H, int N, int D, int dtype, int similarity,
+                                    float* score, float* local, float* contrib,
+                                    int32_t* status /* NULL or [n_pairs]: 0, 1 non-finite, 2 zero weight */,
+                                    int32_t* weight_sums /* NULL or [n_feat] */, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- soft region alignments (additive to ABI v7) -------------------------------------------------------------------------------
+ * dsim_pair_align_regions with weights for the mask: Pm[i][j] is the mean over B, H of the softmax over the listed j (w_b[j] > 0) of
+ * Q_a[i] . K_b[j] / sqrt(D) + ln w_b[j].  A query token's own weight does not enter; a token of weight 0 is an off token: match -1,
+ * weight 0, expect (-1, -1).  match, weight, expect and attn are as the region alignments', over these probabilities.  The bias is
+ * log2(byte / 255) from the soft score's table, added to the exponent's argument in f32 with the raw running maximum as the
+ * reference point.  With bytes 0 / 255 the outputs are dsim_pair_align_regions' bits.
+ *   status      : NULL, or device int32 [n_pairs]: 0, 1 non-finite probability, 2 an image of byte sum 0 (every row off)
+ *   weight_sums : NULL, or device int32 [n_feat]: the images' byte sums
+ * Refusals as dsim_pair_align_regions and dsim_pair_score_weights. */
+size_t dsim_pair_align_weights_workspace_bytes(int n_feat, int n_pairs, int B, int H, int N, int D);
+int    dsim_pair_align_weights(const void* q, const void* k, const uint8_t* weights /* [n_feat][N] */, int n_feat,
+                               const int32_t* idx_a, const int32_t* idx_b, int n_pairs,
+                               int B, int H, int N, int D, int dtype, int grid_w,
+                               int32_t* match, float* weight, float* expect, float* attn,
+                               int32_t* status /* NULL or [n_pairs]: 0 | 1 | 2 */, int32_t* weight_sums /* NULL or [n_feat] */,
                                void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- text attention maps and text-guided regions: the prompt's cross-attention picks the tokens --------------------------------
