@@ -110,6 +110,17 @@ class ViTCfgC(C.Structure):
                 [("ln_eps", C.c_float), ("compute_dtype", C.c_int32), ("tap_layer", C.c_int32)])
 
 
+class ResizeImageC(C.Structure):
+    """dsim_resize_image (include/diffsim_amd.h)"""
+    _fields_ = [("src_offset", C.c_int64), ("w", C.c_int32), ("h", C.c_int32), ("h_table", C.c_int32), ("v_table", C.c_int32),
+                ("y_first", C.c_int32), ("rows", C.c_int32), ("temp_offset", C.c_int64)]
+
+
+class ResizeTableC(C.Structure):
+    """dsim_resize_table (include/diffsim_amd.h)"""
+    _fields_ = [("offset", C.c_int64), ("in_size", C.c_int32), ("out_size", C.c_int32), ("ksize", C.c_int32), ("reserved", C.c_int32)]
+
+
 VIT_ACT = {"gelu": 0, "quick_gelu": 1}          # DSIM_VIT_ACT_*
 VIT_TAP_INPUT = {"norm1": 0, "block": 1}        # dsim_vit_cfg.tap_input
 
@@ -157,6 +168,9 @@ SYMBOLS = {
     "dsim_vae_profile_get": (_i, [_vp, _i, C.c_char_p, _i, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "dsim_image_preprocess": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "dsim_latent_sample": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _vp]),
+    "dsim_resize_u8_workspace_bytes": (_sz, [C.POINTER(ResizeImageC), _i, C.POINTER(ResizeTableC), _i, _sz, _i, _i, _i, _i, _i, _i, _sz]),
+    "dsim_resize_u8": (_i, [_vp, _sz, C.POINTER(ResizeImageC), _i, _vp, _sz, C.POINTER(ResizeTableC), _i, _i, _i, _i, _i, _i, _i, _vp,
+                            _vp, _sz, _vp]),
     "dsim_dit_create": (_i, [C.POINTER(DiTCfgC), C.POINTER(_vp)]),
     "dsim_dit_destroy": (None, [_vp]),
     "dsim_dit_load_weight": (_i, [_vp, C.c_char_p, _vp, _i, C.POINTER(C.c_int64), _i]),

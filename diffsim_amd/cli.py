@@ -4,7 +4,7 @@
 
 Flags of the reference drivers (``/root/reference/argprocess.py:5-18``) keep their names, meaning and defaults;
 ``--dataset`` selects which of the reference's loops runs (``cute_main.py:48-226``, ``night_main.py:24-173`` or
-``style_main.py:24-196`` -- separate scripts there), ``--model_path / --dtype / --batch / --unet_batch / --ngpu / --noise_dtype / --mask_path / --query_mask_path / --gallery_mask_path / --save_region_maps / --save_region_matches / --text_attn / --text_threshold / --soft_masks / --text_soft`` are additions of this build (the reference
+``style_main.py:24-196`` -- separate scripts there), ``--model_path / --dtype / --batch / --unet_batch / --ngpu / --noise_dtype / --gpu_resize / --mask_path / --query_mask_path / --gallery_mask_path / --save_region_maps / --save_region_matches / --text_attn / --text_threshold / --soft_masks / --text_soft`` are additions of this build (the reference
 hard-codes NAS checkpoint paths, ``cute_main.py:25-31``, fp16 and one GPU, ``cute_main.sh:1``).
 
 Multi-GPU (``--ngpu N``): the parent starts N rank processes before anything touches the GPU; triplets are sharded
@@ -115,6 +115,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--decode_procs", type=str, default="auto",
                    help="worker processes that decode + resize the image files ahead of the GPU: a number, 0 = threads of this "
                         "process, auto = host cores / ranks of the node")
+    p.add_argument("--gpu_resize", action="store_true", default=argparse.SUPPRESS,      # (off: _Args.gpu_resize)
+                   help="decode the image files on the host and resize them on the GPU (PIL's Lanczos / bicubic arithmetic, bit for "
+                        "bit: the same scores); images outside the served range are resized by PIL on the host")
     p.add_argument("--fp8_attention", action="store_true", help="--metric dit: e4m3 MFMA attention")
     p.add_argument("--dedup_cfg", dest="dedup_cfg", action="store_true", default=True,
                    help="--metric diffsim: compute what the two CFG halves share once per image (bit-identical scores, ~6 %% faster); the default")
@@ -126,9 +129,15 @@ def build_parser() -> argparse.ArgumentParser:
     return p
 
 
+class _Args(argparse.Namespace):
+    """The parsed flags.  An opt-in switch that is off reads False from here and is no entry of the namespace, so that an argument
+    list without it parses to exactly the namespace it parsed to before the switch existed."""
+    gpu_resize = False
+
+
 def arg_parse(argv=None):
     p = build_parser()
-    args = p.parse_args(argv)
+    args = p.parse_args(argv, namespace=_Args())
     soft_matrix = args.soft_masks and args.dataset == "retrieval"       # the soft score matrix: its masks are the two sets' own
     for flag, on, partner, has in (("--soft_masks", args.soft_masks and not soft_matrix, "--mask_path", args.mask_path is not None),
                                    ("--text_soft", args.text_soft, "--text_attn", args.text_attn is not None)):
@@ -405,6 +414,13 @@ def _report(args, trip, rows, s_ab, s_ac, bad):
             print("No valid comparisons were made.")
 
 
+def _resize_report(args, rank):
+    """--gpu_resize: how many images of this rank took the device resize and how many fell back to PIL (rank 0 prints its own)."""
+    if getattr(args, "gpu_resize", False) and rank == 0 and not args.selftest_shard:
+        from .engine import RESIZE_COUNTS
+        print(f"GPU resize: {RESIZE_COUNTS['gpu']} image(s) resized on the device, {RESIZE_COUNTS['fallback']} fell back to the host")
+
+
 def run(args) -> int:
     import torch
     from . import harness as H
@@ -421,6 +437,8 @@ def run(args) -> int:
         dist.init_process_group("nccl")
     os.environ.setdefault("DSIM_DECODE_PROCS", str(args.decode_procs))      # the scorers' DecodePool default
     scorer = None if args.selftest_shard else build_scorer(args)
+    if getattr(args, "gpu_resize", False) and scorer is not None:         # (a plain Namespace without the flag: off)
+        getattr(scorer, "scorer", scorer).gpu_resize = True         # (a FeatureView: the scorer it wraps)
     layer = args.target_layer if isinstance(args.target_layer, list) else [args.target_layer]
     taps = cli_taps(args, scorer) if args.taps else None
     if rank == 0:
@@ -428,7 +446,9 @@ def run(args) -> int:
         if taps is None:
             print(f"Experiment on {args.target_block}, layer {args.target_layer}, timestep {args.target_step}:")
     if args.dataset == "retrieval":
-        return run_retrieval(args, scorer, layer)
+        rc = run_retrieval(args, scorer, layer)
+        _resize_report(args, rank)
+        return rc
     if args.dataset == "nights":
         rows = H.read_nights_csv(args.image_path)
         trip = [(r["ref"], r["left"], r["right"], r["prompt"]) for r in rows]
@@ -483,6 +503,7 @@ def run(args) -> int:
                 else:
                     print(f"Mean share of tokens on: {guide.on_fraction * 100:.2f}%")
             _report(args, trip, rows, s_ab, s_ac, bad)
+    _resize_report(args, rank)
     if world > 1:
         import torch.distributed as dist
         dist.barrier()

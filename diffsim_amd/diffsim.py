@@ -27,7 +27,7 @@ import torch
 from . import scheduler as sched
 from . import align, maps, regions, retrieval, sweep, textattn
 from .config import SD15, UNetConfig
-from .engine import UNetEngine, _LatentDist, pair_score
+from .engine import UNetEngine, _LatentDist, image_preprocess, pair_score, resize_u8
 from .image import DecodePool, host_threads, load_image, process_image
 from .inputs import path_latents
 from .scorer import (PromptTable, Scorer, check_row_prompts, distinct_prompts, get_generator, row_prompts,  # noqa: F401
@@ -314,10 +314,17 @@ class DiffSim(Scorer):
 
     def _path_pair_latents(self, image_A, image_B, img_size, seed):
         """(latentsA, latentsB, noiseA, noiseB) as f32 tensors: what one reference call draws for the two image files."""
+        if self.gpu_resize and hasattr(self.vae, "moments"):    # decode on the host, process_image on the device: the same bits
+            px = resize_u8([f.result() for f in self._decode.submit_raw([image_A, image_B])], img_size, img_size, "lanczos",
+                           device=self.vae.device)
+            t = image_preprocess(px)
+            return self._pair_draws(t[0:1], t[1:2], seed)
         # decode + Lanczos resize of the two images on two host threads (PIL releases the GIL); same tensors as serially
         fa = self._pool.submit(lambda: process_image(load_image(image_A), img_size))
         tensor_B = process_image(load_image(image_B), img_size)
-        tensor_A = fa.result()
+        return self._pair_draws(fa.result(), tensor_B, seed)
+
+    def _pair_draws(self, tensor_A, tensor_B, seed):
         generator = get_generator(seed, "cpu")                   # reference CPU path: CPU generator
         latentsA, latentsB = self._pair_latents(tensor_A, tensor_B, generator)
         # DiffSimPipeline.step draws the noise right after prepare_latents: A's step first, then B's

@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import threading
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -1635,6 +1636,137 @@ def latent_sample(moments: torch.Tensor, eps: torch.Tensor, scaling_factor: floa
     _lib.check(L.dsim_latent_sample(moments.data_ptr(), eps.data_ptr(), out.data_ptr(), n_out, first,
                                     stride, Cc, h * w, eps.shape[0], float(scaling_factor), int(round_fp16), _stream_ptr()),
                "dsim_latent_sample")
+    return out
+
+
+# ---- PIL's resize on the device (csrc/resize.hip; tables and served range: resize.py) -----------------------------
+RESIZE_CHUNK_BYTES = 256 << 20                  # source bytes per upload, at most (a larger single image goes alone)
+RESIZE_COUNTS = {"gpu": 0, "fallback": 0}       # images resize_u8 resized on the device / on the host since the process started
+_resize_staging: Dict[str, tuple] = {}          # device -> (pinned uint8 buffer, the event after its last upload)
+_resize_lock = threading.Lock()                 # one resize_u8 at a time fills the staging buffer and moves the counts
+
+
+def _resize_stage(dev: torch.device, nbytes: int) -> torch.Tensor:
+    """The pinned upload buffer of `dev`, grown to nbytes, free to overwrite (the upload that last read it has finished)."""
+    buf, ev = _resize_staging.get(str(dev), (None, None))
+    if ev is not None:
+        ev.synchronize()
+    if buf is None or buf.numel() < nbytes:
+        buf = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, pin_memory=True)
+    _resize_staging[str(dev)] = (buf, None)
+    return buf
+
+
+def resize_u8(sources, out_w: int, out_h: int, filter: str, crop=None, device=None) -> torch.Tensor:
+    """``Image.resize((out_w, out_h), filter)`` then ``.crop`` to crop = (ox, oy, cw, ch) (None: everything) of every source: a list
+    of uint8 (h, w, 3) host arrays or tensors of any sizes -> uint8 cuda (n, ch, cw, 3), PIL's bytes.  filter: "lanczos" or
+    "bicubic".  The sources go up packed, one upload per chunk of RESIZE_CHUNK_BYTES, with the coefficient tables of the chunk
+    (resize.coeff_table, one per distinct extent) in front; dsim_resize_u8 does the rest.  A source outside resize.served is
+    resized by PIL on the host and copied into its slot.  RESIZE_COUNTS counts both kinds.  Calls from several threads take turns
+    (one pinned staging buffer per device)."""
+    import numpy as np
+    from . import resize as rz
+    L = _lib.lib()
+    if filter not in rz.FILTERS:
+        raise _lib.DsimError(f"resize_u8: filter {filter!r} (lanczos or bicubic)")
+    out_w, out_h = int(out_w), int(out_h)
+    ox, oy, cw, ch = (0, 0, out_w, out_h) if crop is None else (int(v) for v in crop)
+    if out_w < 1 or out_h < 1 or cw < 1 or ch < 1 or ox < 0 or oy < 0 or ox + cw > out_w or oy + ch > out_h:
+        raise _lib.DsimError(f"resize_u8: crop {(ox, oy, cw, ch)} outside the {out_w}x{out_h} output")
+    arrays = []
+    for s in sources:
+        a = s.numpy() if isinstance(s, torch.Tensor) else np.asarray(s)
+        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1 or a.shape[1] < 1:
+            raise _lib.DsimError("resize_u8: every source is a uint8 (h, w, 3) host array")
+        arrays.append(a)
+    if not arrays:
+        raise _lib.DsimError("resize_u8: no sources")
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    out = torch.empty((len(arrays), ch, cw, 3), dtype=torch.uint8, device=dev)
+    tstride = (cw * 3 + 15) // 16 * 16
+    chunk, chunk_bytes, first = [], 0, 0          # consecutive served sources, their bytes, the first one's slot
+
+    def flush():
+        nonlocal chunk, chunk_bytes
+        if not chunk:
+            return
+        tables, table_arrays, t_ints = {}, [], 0
+
+        def table(n_in, n_out):
+            nonlocal t_ints
+            if n_in == n_out:
+                return -1, None
+            key = (n_in, n_out)
+            if key not in tables:
+                b, k = rz.coeff_table(n_in, n_out, filter)
+                tables[key] = (len(tables), t_ints, k.shape[1], b)
+                table_arrays.extend((b, k))
+                t_ints += b.size + k.size
+            return tables[key][0], tables[key][3]
+        imgs = (_lib.ResizeImageC * len(chunk))()
+        ids = [table(a.shape[1], out_w) + table(a.shape[0], out_h) for a in chunk]
+        if not tables:                                  # every pass skipped: one table nobody reads, so that the count is >= 1
+            tables[(1, 1)] = (0, 0, 1, None)
+            table_arrays, t_ints = [np.zeros(4, np.int32)], 4
+        t_bytes = (t_ints * 4 + 15) // 16 * 16
+        temp = src_bytes = 0
+        for d, a, (ht, _, vt, vb) in zip(imgs, chunk, ids):
+            h, w, _ = a.shape
+            y0, rows = oy, ch
+            if vb is not None:
+                y0 = int(vb[oy, 0])
+                rows = int(vb[oy + ch - 1, 0] + vb[oy + ch - 1, 1]) - y0
+            d.src_offset, d.w, d.h, d.h_table, d.v_table, d.y_first, d.rows, d.temp_offset = src_bytes, w, h, ht, vt, y0, rows, temp
+            if ht >= 0:
+                temp += rows * tstride
+            src_bytes += (a.size + 15) // 16 * 16
+        tabs = (_lib.ResizeTableC * len(tables))()
+        for (n_in, n_out), (i, o, ksize, _) in tables.items():
+            tabs[i].offset, tabs[i].in_size, tabs[i].out_size, tabs[i].ksize = o, n_in, n_out, ksize
+        total = t_bytes + src_bytes
+        stage = _resize_stage(dev, total)
+        host = stage.numpy()
+        p = 0
+        for t in table_arrays:
+            host[p:p + t.size * 4] = np.ascontiguousarray(t).view(np.uint8).reshape(-1)
+            p += t.size * 4
+        for d, a in zip(imgs, chunk):
+            host[t_bytes + d.src_offset:t_bytes + d.src_offset + a.size] = a.reshape(-1)
+        up = torch.empty(total, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            up.copy_(stage[:total], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            _resize_staging[str(dev)] = (stage, ev)
+            args = (imgs, len(chunk), tabs, len(tables), t_ints, out_w, out_h, ox, oy, cw, ch, src_bytes)
+            ws_bytes = L.dsim_resize_u8_workspace_bytes(*args)
+            if ws_bytes == 0:
+                raise _lib.DsimError("dsim_resize_u8 refuses this call (include/diffsim_amd.h lists the refusals)")
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            dst = out[first:first + len(chunk)]
+            _lib.check(L.dsim_resize_u8(up.data_ptr() + t_bytes, src_bytes, imgs, len(chunk), up.data_ptr(), t_ints, tabs, len(tables),
+                                        out_w, out_h, ox, oy, cw, ch, dst.data_ptr(), ws.data_ptr(), ws_bytes, _stream_ptr()),
+                       "dsim_resize_u8")
+        RESIZE_COUNTS["gpu"] += len(chunk)
+        chunk, chunk_bytes = [], 0
+
+    with _resize_lock:
+        for i, a in enumerate(arrays):
+            h, w, _ = a.shape
+            if not rz.served(w, h, out_w, out_h):
+                from PIL import Image
+                im = Image.fromarray(np.ascontiguousarray(a)).resize((out_w, out_h), resample=getattr(Image.Resampling, filter.upper()))
+                out[i] = torch.from_numpy(np.asarray(im.crop((ox, oy, ox + cw, oy + ch))).copy()).to(dev)
+                RESIZE_COUNTS["fallback"] += 1
+                flush()
+                continue
+            if chunk and (chunk_bytes + a.size > RESIZE_CHUNK_BYTES or len(chunk) >= 32768):
+                flush()
+            if not chunk:
+                first = i
+            chunk.append(a)
+            chunk_bytes += a.size
+        flush()
     return out
 
 

@@ -98,6 +98,32 @@ class DecodePool:
         finally:
             self._free.put(w)
 
+    def _one_raw(self, path) -> np.ndarray:
+        if isinstance(path, Image.Image):                   # handed in decoded: the same open -> EXIF transpose -> RGB, here
+            return np.asarray(load_image(path))
+        if self.procs <= 0:
+            from ._decode_worker import decode_raw
+            return decode_raw(path)
+        import struct
+        w = self._free.get()
+        try:
+            w.stdin.write(f"raw\t{path}\n".encode())
+            w.stdin.flush()
+            (n,) = struct.unpack("<q", w.stdout.read(8))
+            if n == 0:
+                (m,) = struct.unpack("<q", w.stdout.read(8))
+                raise RuntimeError(f"decode worker failed on {path}: {w.stdout.read(m).decode()}")
+            h, wd = struct.unpack("<ii", w.stdout.read(8))
+            return np.frombuffer(w.stdout.read(n - 8), dtype=np.uint8).reshape(h, wd, 3)
+        finally:
+            self._free.put(w)
+
+    def submit_raw(self, paths):
+        """Decode only: futures of one uint8 (h, w, 3) array per path, at the file's own size (the resize is engine.resize_u8's)."""
+        if self.procs > 0 and self._workers is None:
+            self._start()
+        return [self._ex.submit(self._one_raw, p) for p in paths]
+
     def submit(self, paths, img_size: int):
         if self.procs > 0 and self._workers is None:
             self._start()

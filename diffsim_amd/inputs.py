@@ -13,12 +13,13 @@ from typing import List, Sequence, Tuple
 
 import torch
 
-from .engine import image_preprocess, latent_sample
+from .engine import image_preprocess, latent_sample, resize_u8
 from .image import DecodePool, load_image, process_image
 from .scorer import get_generator, stack_rows       # noqa: F401  (stack_rows: latent rows -> engine batches, the other half)
 
 
 _POOL = None
+INPUT_CHUNK = 64                # images per decode request and device resize of a kind without draws (the ViT metrics)
 
 
 def _shared_pool():
@@ -27,6 +28,21 @@ def _shared_pool():
     if _POOL is None:
         _POOL = DecodePool()
     return _POOL
+
+
+def raw_chunks(pool, rows, chunk: int):
+    """The decoded images of `rows` (tuples of paths or PIL images), `chunk` rows at a time in row-major order, as lists of uint8
+    (h, w, 3) arrays at the files' own sizes: decode-only requests to `pool`, two chunks ahead of the consumer."""
+    starts = list(range(0, len(rows), chunk))
+
+    def submit(i0):
+        return pool.submit_raw([p for row in rows[i0:i0 + chunk] for p in row])
+    pending = [submit(i0) for i0 in starts[:2]]
+    for ci in range(len(starts)):
+        arrays = [f.result() for f in pending.pop(0)]
+        if ci + 2 < len(starts):
+            pending.append(submit(starts[ci + 2]))
+        yield arrays
 
 
 def path_latents(scorer, rows: Sequence[Tuple[str, ...]], slots: Sequence[int], img_size, seed, chunk: int,
@@ -38,13 +54,22 @@ def path_latents(scorer, rows: Sequence[Tuple[str, ...]], slots: Sequence[int], 
 
     With the scorer's HIP VAE encoder (unless hip_vae=False): decode + resize run two chunks ahead on the host, and each
     chunk of `chunk` rows is one ``vae.moments`` with the columns interleaved; the four draws come from one reseeded
-    generator and ``latent_sample`` applies them on the device.  Otherwise the scorer's prepare_image_latents per image: slot
+    generator and ``latent_sample`` applies them on the device.  With ``scorer.gpu_resize`` the host only decodes: the Lanczos
+    resize is engine.resize_u8's, PIL's bytes, so the latents are the same bits (a kind without draws: its ``load_inputs``, whose f32 inputs are then returned
+    on the device -- n x 3 x S x S x 4 bytes of device memory per column set, where the host path returns host tensors).  Otherwise the scorer's prepare_image_latents per image: slot
     A from a freshly reseeded generator, slot B from its state after slot A's draw, the noises after slot B's draw.  A call
     whose columns all sit in one slot spends one extra prepare on its first image to reach the other slot's state."""
     vae = getattr(scorer, "vae", None)
     k = len(slots)
     cols = [[] for _ in slots]
+    gpu_resize = bool(getattr(scorer, "gpu_resize", False))
     if not scorer.draws:            # a kind without VAE and noise: its own input tensors, and placeholders where the noises go
+        if gpu_resize and hasattr(scorer, "load_inputs"):
+            pool = getattr(scorer, "_decode", None) or _shared_pool()
+            x = torch.cat([scorer.load_inputs(arrays) for arrays in raw_chunks(pool, rows, max(1, INPUT_CHUNK // k))])
+            cols = [x[c::k] for c in range(k)]
+            none = torch.zeros((1,) + tuple(cols[0].shape[1:]))
+            return cols, none, none
         cols = [torch.cat([scorer.load_input(row[c], img_size) for row in rows]) for c in range(k)]
         none = torch.zeros((1,) + tuple(cols[0].shape[1:]))
         return cols, none, none
@@ -55,14 +80,18 @@ def path_latents(scorer, rows: Sequence[Tuple[str, ...]], slots: Sequence[int], 
 
         def submit(i0):
             return pool.submit([p for row in rows[i0:i0 + chunk] for p in row], img_size)
-        pending = [submit(i0) for i0 in starts[:2]]              # decode + resize run two chunks ahead of the GPU
+        raw = raw_chunks(pool, rows, chunk) if gpu_resize else None
+        pending = [] if gpu_resize else [submit(i0) for i0 in starts[:2]]      # decode + resize run two chunks ahead of the GPU
         draws = None
         for ci, i0 in enumerate(starts):
-            px = DecodePool.gather(pending.pop(0))
-            if ci + 2 < len(starts):
-                pending.append(submit(starts[ci + 2]))
+            if gpu_resize:          # the host decoded only: process_image's Lanczos resize on the device too (dsim_resize_u8)
+                px = resize_u8(next(raw), img_size, img_size, "lanczos", device=vae.device)
+            else:
+                px = DecodePool.gather(pending.pop(0)).to(vae.device, non_blocking=True)
+                if ci + 2 < len(starts):
+                    pending.append(submit(starts[ci + 2]))
             # process_image's arithmetic and the fp16 image cast on the device (bit-identical, dsim_image_preprocess)
-            x = image_preprocess(px.to(vae.device, non_blocking=True), scorer.image_half)
+            x = image_preprocess(px, scorer.image_half)
             mom = vae.moments(x)
             if draws is None:
                 g = get_generator(seed, "cpu")

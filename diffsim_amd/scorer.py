@@ -121,6 +121,9 @@ class Scorer:
     draws = True                            # whether a call draws at all (VAE sample, noise); False: the input tensors are the
                                             #   "latents", the noises are placeholders and tap_features ignores noise, prompt, step
 
+    gpu_resize = False                      # files-in calls: decode on the host, PIL's resize on the device (engine.resize_u8,
+                                            #   bit for bit); False: decode and resize on the host
+
     def load_input(self, path, img_size):
         """One image (a path or a PIL image) as the kind's (1, 3, S, S) f32 input tensor on the host: the reference's
         process_image (Lanczos resize to img_size, [-1, 1]) in front of the VAE."""

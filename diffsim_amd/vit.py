@@ -79,6 +79,34 @@ class Preprocess:
         arr = (arr - self.mean) / self.std
         return torch.from_numpy(np.ascontiguousarray(arr.transpose(2, 0, 1)[None]))
 
+    def batch(self, arrays, device) -> torch.Tensor:
+        """``torch.cat([self(Image.fromarray(a)) for a in arrays])`` for uint8 (h, w, 3) RGB arrays, bit for bit, on `device`: the
+        shortest-edge rule per image, engine.resize_u8 with the centre crop as its window (images of one output size share a
+        call; the cropped-away part is never computed), then the same f32 arithmetic and HWC -> CHW there.  A `resample` other
+        than bicubic or Lanczos is resized on the host."""
+        from . import resize as rz
+        from .engine import resize_u8
+        name = rz.filter_name(self.resample)
+        if name is None:
+            return torch.cat([self(Image.fromarray(a)) for a in arrays]).to(device)
+        c, groups = self.crop, {}
+        for i, a in enumerate(arrays):
+            h, w = a.shape[:2]
+            ow, oh = rz.shortest_edge(w, h, self.resize)
+            if ow < c or oh < c:
+                raise ValueError(f"image {ow}x{oh} after the resize is smaller than the {c} px crop")
+            groups.setdefault((ow, oh), []).append(i)
+        px = torch.empty((len(arrays), c, c, 3), dtype=torch.uint8, device=device)
+        for (ow, oh), idx in groups.items():
+            got = resize_u8([arrays[i] for i in idx], ow, oh, name, ((ow - c) // 2, (oh - c) // 2, c, c), device=device)
+            if len(groups) == 1:
+                px = got
+            else:
+                px[torch.tensor(idx, device=device)] = got
+        x = px.to(torch.float32) * float(np.float32(1.0 / 255.0))
+        x = (x - torch.from_numpy(self.mean).to(device)) / torch.from_numpy(self.std).to(device)
+        return x.permute(0, 3, 1, 2).contiguous()
+
 
 CLIP_PREPROCESS = Preprocess(224, 224, CLIP_MEAN, CLIP_STD)
 DINOV2_PREPROCESS = Preprocess(256, 224, IMAGENET_MEAN, IMAGENET_STD)
@@ -201,6 +229,10 @@ class _ViTScore(Scorer):
     def load_input(self, path, img_size):
         """img_size is not consulted, as in the reference: the image processor's resize and crop decide the side."""
         return self.preprocess(load_image(path))
+
+    def load_inputs(self, arrays):
+        """load_input of many decoded images (uint8 (h, w, 3) arrays) at once, on the device: Preprocess.batch."""
+        return self.preprocess.batch(arrays, self.device)
 
     def tap_features(self, lat, nz, prompt, tap, step):
         return self.features(lat, tap)

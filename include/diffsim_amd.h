@@ -732,6 +732,49 @@ int dsim_image_preprocess(const unsigned char* pixels_hwc, float* out, int n, in
 int dsim_latent_sample(const float* moments, const float* eps, float* out, int n_out, int first, int stride, int C, int hw,
                        int eps_n, float scaling_factor, int round_fp16, void* stream);
 
+/* ---- the resize in front of it, on the device: PIL's 8-bit resampling, bit for bit ----
+ * dsim_resize_u8: `image.resize((S, S), LANCZOS)` of process_image (diffsim/diffsim.py:27-33), and the image processors' bicubic
+ *   resize + centre crop of the ViT metrics, for packed RGB u8 over a ragged batch: n images of their own sizes, one output size.
+ *   Pillow's two passes in Pillow's integer arithmetic: horizontally over the source rows the vertical pass reads, into u8, then
+ *   vertically, each as clamp((2^21 + sum_i p[min + i] k[i]) >> 22, 0, 255) in int32 with an arithmetic shift.  An axis whose
+ *   source extent equals the output extent is skipped (both: a copy).  Only the window [oy, oy + ch) x [ox, ox + cw) of the
+ *   out_h x out_w result is computed and stored: out u8 [n][ch][cw][3].
+ *     src        : device bytes; image i is u8 [h][w][3] at images[i].src_offset (a multiple of 16), src_bytes the buffer's length
+ *     images     : HOST array [n] (read and copied by the call; free on return).  The call turns it into device descriptors with one
+ *                  hipMemcpyAsync from pageable host memory, which the runtime may complete before it returns: a call can block
+ *                  the calling thread until the stream has reached that copy
+ *     table_data : device int32 [table_ints]; table t, at tables[t].offset: out_size pairs (min, n), then out_size rows of ksize
+ *                  coefficients (22-bit fixed point; those past n unread).  One table per distinct (source extent, output extent,
+ *                  filter); h_table / v_table = -1 where the pass is skipped (and only there)
+ *     tables     : HOST array [n_tables] describing table_data
+ *     y_first, rows : the source rows the vertical pass reads, [v-table min(oy), v-table min(oy+ch-1) + n(oy+ch-1)), or [oy, oy + ch)
+ *                  without a vertical pass; temp_offset (a multiple of 16, unread without a horizontal pass): where the image's
+ *                  rows x round_up(3 cw, 16) temp bytes lie in the workspace's temp area; images must not overlap there
+ *   Deterministic, no atomics, 64-bit offsets; an image's bytes do not depend on the other images of the call.
+ *   The table CONTENTS live in device memory and are the caller's contract: min >= 0, 1 <= n <= ksize, min + n <= the source extent,
+ *   min and min + n non-decreasing (the kernels clamp every window to the image's rows and columns, so a table that breaks this
+ *   gives wrong bytes, not a wild access).  Refusals, all decided on the host before anything is enqueued: DSIM_ERR_INVALID
+ *   (workspace query: 0) for n < 1 or n > 65535, an output or crop extent < 1, a crop outside the resized image, an image extent < 1,
+ *   ksize < 1, any NULL pointer, a source offset + 3 w h beyond src_bytes, a table id >= n_tables or a table beyond table_ints, a
+ *   table whose in_size / out_size are not the image's and the output's extent (or -1 where they differ), rows outside the image,
+ *   a misaligned offset, or more than ~300 source pixels per output pixel; DSIM_ERR_WORKSPACE for a short workspace. */
+typedef struct dsim_resize_image {
+    int64_t src_offset;
+    int32_t w, h;
+    int32_t h_table, v_table;
+    int32_t y_first, rows;
+    int64_t temp_offset;
+} dsim_resize_image;
+typedef struct dsim_resize_table {
+    int64_t offset;                     /* int32 index into table_data */
+    int32_t in_size, out_size, ksize, reserved;
+} dsim_resize_table;
+size_t dsim_resize_u8_workspace_bytes(const dsim_resize_image* images, int n, const dsim_resize_table* tables, int n_tables,
+                                      size_t table_ints, int out_w, int out_h, int ox, int oy, int cw, int ch, size_t src_bytes);
+int    dsim_resize_u8(const unsigned char* src, size_t src_bytes, const dsim_resize_image* images, int n, const int32_t* table_data,
+                      size_t table_ints, const dsim_resize_table* tables, int n_tables, int out_w, int out_h, int ox, int oy, int cw,
+                      int ch, unsigned char* out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- single-operator entry points (kernel-level parity tests and micro-benchmarks) -----
  * x: dtype [M][K] (or NHWC image for the conv forms); w: diffusers-layout f32 weight.      */
 int dsim_op_linear(const void* x, const float* w /*[N][K]*/, const float* bias /*[N] or NULL*/,
