@@ -233,6 +233,8 @@ SYMBOLS = {
     "dsim_pair_score_maps_weights": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dsim_pair_align_weights_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
     "dsim_pair_align_weights": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dsim_pair_region_transfer_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "dsim_pair_region_transfer": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "dsim_score_matrix_weights_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
     "dsim_score_matrix_weights": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dsim_op_linear": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),

@@ -4,7 +4,7 @@
 
 Flags of the reference drivers (``/root/reference/argprocess.py:5-18``) keep their names, meaning and defaults;
 ``--dataset`` selects which of the reference's loops runs (``cute_main.py:48-226``, ``night_main.py:24-173`` or
-``style_main.py:24-196`` -- separate scripts there), ``--model_path / --dtype / --batch / --unet_batch / --ngpu / --noise_dtype / --gpu_resize / --mask_path / --query_mask_path / --gallery_mask_path / --save_region_maps / --save_region_matches / --text_attn / --text_threshold / --soft_masks / --text_soft`` are additions of this build (the reference
+``style_main.py:24-196`` -- separate scripts there), ``--model_path / --dtype / --batch / --unet_batch / --ngpu / --noise_dtype / --gpu_resize / --mask_path / --query_mask_path / --gallery_mask_path / --save_region_maps / --save_region_matches / --text_attn / --text_threshold / --soft_masks / --text_soft / --transfer_masks / --transfer_threshold`` are additions of this build (the reference
 hard-codes NAS checkpoint paths, ``cute_main.py:25-31``, fp16 and one GPU, ``cute_main.sh:1``).
 
 Multi-GPU (``--ngpu N``): the parent starts N rank processes before anything touches the GPU; triplets are sharded
@@ -101,6 +101,15 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--text_threshold", type=float, default=1.0,
                    help="--text_attn: a token is in its image's region at >= this multiple of the image's mean text saliency "
                         "(0: every token; a region with no token on is the whole image)")
+    p.add_argument("--transfer_masks", action="store_true", default=argparse.SUPPRESS,      # (off: _Args.transfer_masks)
+                   help="--mask_path, --dataset cute|nights, --metric diffsim|diffsim_xl|dit: exemplar-guided regions -- only the "
+                        "reference image of each triplet reads its mask file; each candidate's region is the tokens whose attention mass "
+                        "into the reference's masked tokens is at least --transfer_threshold x the candidate's mean mass.  With "
+                        "--soft_masks the reference's weights and the transferred regions are soft.  The run prints how many references "
+                        "had no mask file and the mean share of tokens on")
+    p.add_argument("--transfer_threshold", type=float, default=argparse.SUPPRESS, metavar="T",      # (default: _Args.transfer_threshold)
+                   help="--transfer_masks: a candidate's token is in its region at >= this multiple of the image's mean attention mass "
+                        "(default 1.0; 0: every token; a region with no token on is the whole image)")
     p.add_argument("--experiments", type=int, default=2000, help="--dataset sref: sampled experiments (style_main.py:64)")
     p.add_argument("--model_path", type=str, default=None, help="diffusers-layout checkpoint directory (unet/, vae/, text_encoder/, tokenizer/)")
     p.add_argument("--dtype", type=str, choices=["bf16", "fp16", "fp32"], default="bf16",
@@ -133,6 +142,8 @@ class _Args(argparse.Namespace):
     """The parsed flags.  An opt-in switch that is off reads False from here and is no entry of the namespace, so that an argument
     list without it parses to exactly the namespace it parsed to before the switch existed."""
     gpu_resize = False
+    transfer_masks = False
+    transfer_threshold = 1.0
 
 
 def arg_parse(argv=None):
@@ -157,6 +168,20 @@ def arg_parse(argv=None):
                     "score matrix): it needs one of them or both (--mask_path is the triplet benchmarks')")
         if args.metric in VIT_METRICS or args.metric in FEATURE_METRICS:
             p.error(f"--soft_masks: --metric {args.metric} has no regions")
+    if "transfer_threshold" in vars(args) and not args.transfer_masks:
+        p.error("--transfer_threshold is the threshold of --transfer_masks: it needs --transfer_masks")
+    if args.transfer_masks:
+        if args.mask_path is None:
+            p.error("--transfer_masks transfers the reference images' masks of --mask_path: it needs --mask_path")
+        if args.dataset not in ("cute", "nights") or args.taps is not None:
+            p.error("--transfer_masks scores exemplar-guided regions on the one-tap triplet benchmarks (--dataset cute or nights): "
+                    "--dataset sref, --dataset retrieval and a sweep (--taps) are not supported with it")
+        if args.text_attn is not None:
+            p.error("--transfer_masks: an exemplar-guided region and a text-guided region (--text_attn), one or the other")
+        if args.metric in VIT_METRICS or args.metric in FEATURE_METRICS:
+            p.error(f"--transfer_masks: --metric {args.metric} has no regions")
+        if not (args.transfer_threshold >= 0.0) or args.transfer_threshold == float("inf"):
+            p.error("--transfer_threshold must be finite and >= 0")
     if args.metric in FEATURE_METRICS:
         if args.similarity != "cosine":
             p.error(f"--metric {args.metric} needs --similarity cosine: its score is always a cosine, as in the reference (which "
@@ -482,6 +507,16 @@ def run(args) -> int:
                 print(f"Region scores: masks from {args.mask_path}; {missing} image(s) without a mask file are scored whole")
                 if args.soft_masks:
                     print("Soft regions: a mask's area average on the token grid is the token's weight")
+        exemplar = None
+        if args.transfer_masks and masks is not None:
+            no_ref = len({t[0] for t, mk in zip(trip, masks) if mk[0] is None})
+            masks = [mk[0] for mk in masks]
+            if not args.selftest_shard:
+                from .transfer import ExemplarGuide
+                exemplar = ExemplarGuide(args.transfer_threshold, args.soft_masks)
+            if rank == 0:
+                print(f"Exemplar-guided regions: only the reference images read their masks, threshold {args.transfer_threshold:g} x the "
+                      f"mean attention mass; {no_ref} reference image(s) without a mask file make their candidates whole")
         guide = None
         if args.text_attn is not None and not args.selftest_shard:
             from .textattn import TextGuide
@@ -495,8 +530,11 @@ def run(args) -> int:
             s_ab, s_ac, bad = H.score_path_triplets(scorer, trip, args.image_size, args.target_block, layer, args.target_step,
                                                     args.seed, args.similarity, rank, world, args.batch, args.unet_batch,
                                                     *(() if masks is None else (masks,)), **({} if guide is None else {"text": guide}),
-                                                    **({"soft": True} if args.soft_masks else {}))
+                                                    **({"soft": True} if args.soft_masks else {}),
+                                                    **({} if exemplar is None else {"exemplar": exemplar}))
         if rank == 0:
+            if exemplar is not None:
+                print(f"Mean {'token weight' if args.soft_masks else 'share of tokens on'}: {exemplar.on_fraction * 100:.2f}%")
             if guide is not None:
                 if args.text_soft:
                     print(f"Mean token weight: {guide.on_fraction * 100:.2f}%")

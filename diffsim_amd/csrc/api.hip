@@ -1,5 +1,5 @@
 // The C ABI of libdiffsim_amd that belongs to no executor: version / status text / device count, the fused score tails (pairs,
-// matrices, maps, alignments, regions, text attention) with their workspace queries, and the single-operator and launch-plan entry points (dsim_op_*, dsim_*_plan) the
+// matrices, maps, alignments, regions, text attention, region transfer) with their workspace queries, and the single-operator and launch-plan entry points (dsim_op_*, dsim_*_plan) the
 // tests and micro-benchmarks drive.  The executors' own groups live beside their walks: dsim_unet_* in unet.hip, dsim_vae_* in
 // vae.hip, dsim_dit_* in dit.hip.
 #include <cstdio>
@@ -224,6 +224,20 @@ int dsim_pair_align(const void* q, const void* k, const int32_t* idx_a, const in
     PairArgs a{q, k, nullptr, idx_a, idx_b, n_pairs, B, H, N, D, 0, workspace, workspace_bytes};
     const int st = tail_prologue({q, k, idx_a, idx_b}, pair_args_check(a, dtype), a.scratch, a.scratch_bytes);
     return st != DSIM_OK ? st : launch_pair_align(a, dtype, grid_w, match, weight, expect, attn, status, (hipStream_t)stream);
+}
+
+size_t dsim_pair_region_transfer_workspace_bytes(int n_feat, int n_pairs, int B, int H, int N, int D) {
+    return with_slack(pair_region_transfer_scratch_bytes(n_feat, n_pairs, B, H, N, D));
+}
+
+int dsim_pair_region_transfer(const void* q, const void* k, const uint8_t* weights, int n_feat, const int32_t* idx_a, const int32_t* idx_b,
+                              int n_pairs, int B, int H, int N, int D, int dtype, int directions, float* mass, int32_t* status,
+                              void* workspace, size_t workspace_bytes, void* stream) {
+    PairArgs a{q, k, nullptr, idx_a, idx_b, n_pairs, B, H, N, D, 0, workspace, workspace_bytes};
+    const bool served = pair_region_transfer_scratch_bytes(n_feat, n_pairs, B, H, N, D) != 0 && directions >= 1 && directions <= 3;
+    const int st = tail_prologue({q, k, weights, idx_a, idx_b, mass}, served ? pair_args_check(a, dtype) : DSIM_ERR_INVALID, a.scratch,
+                                 a.scratch_bytes);
+    return st != DSIM_OK ? st : launch_pair_region_transfer(a, dtype, weights, n_feat, directions, mass, status, (hipStream_t)stream);
 }
 
 size_t dsim_text_attention_workspace_bytes(int n_images, int N, int L) { return with_slack(text_attention_scratch_bytes(n_images, N, L)); }

@@ -1,5 +1,5 @@
 // The host entry points of the sources that are compiled once per 16-bit type (gemm / gemm_skinny / rowres / attention / tails /
-// align / regions / soft_regions / region_matrix / region_maps / textattn / attn160 .hip).  Declarations only and no include guard: common.h includes this file inside `inline namespace DSIM_H16_NS`, the including
+// align / regions / soft_regions / region_matrix / region_maps / textattn / transfer / attn160 .hip).  Declarations only and no include guard: common.h includes this file inside `inline namespace DSIM_H16_NS`, the including
 // object's own type, and the bf16 objects of the product build once more inside `namespace f16`, which declares the fp16 twins with
 // the same signatures and default arguments.  The argument structs and enums are plain dsim types (common.h, above the include).
 
@@ -94,6 +94,13 @@ int launch_pair_score_maps_weights(const PairArgs& a, int dtype, const uint8_t* 
 size_t pair_align_weights_scratch_bytes(int n_feat, int n_pairs, int B, int H, int N, int D);      // 0: call not served
 int launch_pair_align_weights(const PairArgs& a, int dtype, const uint8_t* weights, int n_feat, int grid_w, int32_t* match, float* weight,
                               float* expect, float* attn, int32_t* status, int32_t* weight_sums, hipStream_t s);
+// region transfer: the attention mass each token sends into the other image's weighted tokens, sum_j Pm[i][j] w[j] with launch_pair_align's
+// Pm (softmax over all keys; weights [n_feat][N] bytes, w = byte / 255, in the sum only), in one pass over the keys without Pm or
+// statistics (transfer_part_kernel + transfer_fold_kernel, any shape and dtype) -- transfer.hip
+//   directions 1: rows [p][0], 2: rows [p][1], 3: both; mass [n_pairs][2][N] (rows not asked for are not written); status (may be NULL)
+size_t pair_region_transfer_scratch_bytes(int n_feat, int n_pairs, int B, int H, int N, int D);      // 0: call not served
+int launch_pair_region_transfer(const PairArgs& a, int dtype, const uint8_t* weights, int n_feat, int directions, float* mass,
+                                int32_t* status, hipStream_t s);
 // text attention maps: the tapped block's cross-attention on the conditional CFG half, averaged over the heads; its weighted sum over
 // the prompt tokens (saliency) and the token region above rel_threshold x the image's mean saliency (text_attn_kernel,
 // text_region_kernel, any head dim and dtype, 1 <= L <= 128) -- textattn.hip

@@ -25,7 +25,7 @@ from concurrent.futures import ThreadPoolExecutor
 import torch
 
 from . import scheduler as sched
-from . import align, maps, regions, retrieval, sweep, textattn
+from . import align, maps, regions, retrieval, sweep, textattn, transfer
 from .config import SD15, UNetConfig
 from .engine import UNetEngine, _LatentDist, image_preprocess, pair_score, resize_u8
 from .image import DecodePool, host_threads, load_image, process_image
@@ -450,6 +450,24 @@ class DiffSim(Scorer):
         content token of the prompt) is at least rel_threshold x the image's mean.  Returns a (1,) tensor."""
         return textattn.score_path_pairs_text(self, [(image_A, image_B)], img_size, prompt, target_block, _norm_layer(target_layer),
                                               target_step, seed, similarity, words, rel_threshold)
+
+    exemplar_regions = True                 # the kind has exemplar-guided regions (transfer.py)
+
+    @torch.no_grad()
+    def exemplar_region_score(self, image_A, image_B, mask_A, img_size, prompt, target_block, target_layer, target_step, seed="2333",
+                              similarity="cosine", rel_threshold=1.0, soft=False):
+        """:meth:`region_score` with a mask for image_A alone (transfer.py): image_B's region is the tokens whose attention mass into
+        mask_A's tokens is at least rel_threshold x the image's mean; soft: token weights on both sides.  Returns a (1,) tensor."""
+        return transfer.score_path_pairs_exemplar(self, [(image_A, image_B)], [mask_A], img_size, prompt, target_block,
+                                                  _norm_layer(target_layer), target_step, seed, similarity, None, rel_threshold, soft)
+
+    @torch.no_grad()
+    def transferred_region(self, image_A, image_B, mask_A, img_size, prompt, target_block, target_layer, target_step, seed="2333",
+                           rel_threshold=1.0, soft=False):
+        """(mass (h, w) f32, region (h, w) bool -- soft: uint8 weights) on image_B's token grid: what :meth:`exemplar_region_score`
+        transfers from mask_A."""
+        return transfer.path_transferred_region(self, image_A, image_B, mask_A, img_size, prompt, target_block,
+                                                _norm_layer(target_layer), target_step, seed, rel_threshold, soft)
 
     @torch.no_grad()
     def text_attention_map(self, image_A, image_B, img_size, prompt, target_block, target_layer, target_step, seed="2333"):

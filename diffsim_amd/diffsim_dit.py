@@ -10,7 +10,7 @@ from typing import Dict, Optional
 
 import torch
 
-from . import align, maps, regions, sweep
+from . import align, maps, regions, sweep, transfer
 from . import scheduler as sched
 from ._lib import DsimError
 from .config import DIT_XL2, DiTConfig
@@ -172,6 +172,24 @@ class diffsim_DiT(Scorer):
         weights)."""
         return align.score_path_pair_alignment(self, [(image_A, image_B)], img_size, None, "none", [int(target_layer[0])], target_step,
                                                seed, 32, masks=[(mask_A, mask_B)], hip_vae=False, soft=True)
+
+    exemplar_regions = True                 # the kind has exemplar-guided regions (transfer.py): no text is involved
+
+    @torch.no_grad()
+    def exemplar_region_score(self, image_A, image_B, mask_A, img_size, prompt, target_block, target_layer, target_step, seed="2333",
+                              similarity="cosine", rel_threshold=1.0, soft=False):
+        """:meth:`region_score` with a mask for image_A alone (transfer.py): image_B's region is the tokens whose attention mass into
+        mask_A's tokens is at least rel_threshold x the image's mean; soft: token weights on both sides.  Returns a (1,) tensor."""
+        return transfer.score_path_pairs_exemplar(self, [(image_A, image_B)], [mask_A], img_size, None, "none", [int(target_layer[0])],
+                                                  target_step, seed, similarity, 32, rel_threshold, soft, hip_vae=False)
+
+    @torch.no_grad()
+    def transferred_region(self, image_A, image_B, mask_A, img_size, prompt, target_block, target_layer, target_step, seed="2333",
+                           rel_threshold=1.0, soft=False):
+        """(mass (h, w) f32, region (h, w) bool -- soft: uint8 weights) on image_B's token grid: what :meth:`exemplar_region_score`
+        transfers from mask_A."""
+        return transfer.path_transferred_region(self, image_A, image_B, mask_A, img_size, None, "none", [int(target_layer[0])],
+                                                target_step, seed, rel_threshold, soft, 32, hip_vae=False)
 
     def text_region_score(self, *args, **kwargs):
         """DiT is class-conditional: it has no prompt and no cross-attention, so no text-guided regions."""

@@ -13,7 +13,7 @@ from typing import Callable, Dict, Optional, Tuple
 
 import torch
 
-from . import align, maps, regions, sweep, textattn
+from . import align, maps, regions, sweep, textattn, transfer
 from . import scheduler as sched
 from .config import SDXL, UNetConfig
 from .engine import UNetEngine, pair_score
@@ -245,6 +245,24 @@ class diffsim_xl(Scorer):
         Returns a (1,) tensor."""
         return textattn.score_path_pairs_text(self, [(image_A, image_B)], img_size, prompt, target_block, target_layer, target_step,
                                               seed, similarity, words, rel_threshold, hip_vae=False)
+
+    exemplar_regions = True                 # the kind has exemplar-guided regions (transfer.py)
+
+    @torch.no_grad()
+    def exemplar_region_score(self, image_A, image_B, mask_A, img_size, prompt, target_block, target_layer, target_step, seed="2333",
+                              similarity="cosine", rel_threshold=1.0, soft=False):
+        """:meth:`region_score` with a mask for image_A alone (transfer.py): image_B's region is the tokens whose attention mass into
+        mask_A's tokens is at least rel_threshold x the image's mean; soft: token weights on both sides.  Returns a (1,) tensor."""
+        return transfer.score_path_pairs_exemplar(self, [(image_A, image_B)], [mask_A], img_size, prompt, target_block, target_layer,
+                                                  target_step, seed, similarity, None, rel_threshold, soft, hip_vae=False)
+
+    @torch.no_grad()
+    def transferred_region(self, image_A, image_B, mask_A, img_size, prompt, target_block, target_layer, target_step, seed="2333",
+                           rel_threshold=1.0, soft=False):
+        """(mass (h, w) f32, region (h, w) bool -- soft: uint8 weights) on image_B's token grid: what :meth:`exemplar_region_score`
+        transfers from mask_A."""
+        return transfer.path_transferred_region(self, image_A, image_B, mask_A, img_size, prompt, target_block, target_layer,
+                                                target_step, seed, rel_threshold, soft, hip_vae=False)
 
     @torch.no_grad()
     def text_attention_map(self, image_A, image_B, img_size, prompt, target_block, target_layer, target_step, seed):

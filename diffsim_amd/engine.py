@@ -962,6 +962,32 @@ def pair_align_weights(q: torch.Tensor, k: torch.Tensor, weights_u8: torch.Tenso
     return (match, weight, expect) + tuple(e for e in (attn, status, sums) if e is not None)
 
 
+def pair_region_transfer(q: torch.Tensor, k: torch.Tensor, weights_u8: torch.Tensor, idx_a: torch.Tensor, idx_b: torch.Tensor, heads: int,
+                         directions: int = 3, return_status: bool = False):
+    """Region transfer (dsim_pair_region_transfer): the attention mass each token sends into the other image's weighted tokens,
+    sum_j Pm[i][j] w[j] with pair_align's Pm (the softmax over all keys) and w = byte / 255, without forming Pm.  q,k, idx: as
+    pair_align; weights_u8: as pair_score_weights.  Returns f32 (n, 2, N): row [p][0] on image idx_a[p]'s grid (its queries over
+    idx_b[p]'s keys and weights), row [p][1] the mirror.  directions 1: rows [p][0] only, 2: rows [p][1] only, 3: both; the rows not
+    asked for hold NaN.  return_status: also an int32 (n,) tensor, 1 where a pair has a non-finite probability."""
+    _require_cuda(q, k, weights_u8, idx_a, idx_b)
+    B, N, D = _check_features((q, k), heads, k.shape == q.shape, _PAIR_MSGS, (idx_a, idx_b))
+    _check_token_weights(weights_u8, q.shape[0], N)
+    if directions not in (1, 2, 3):
+        raise ValueError(f"directions must be 1, 2 or 3: {directions!r}")
+    n_feat, n_pairs = q.shape[0], idx_a.numel()
+    dev = q.device
+    mass = torch.full((n_pairs, 2, N), float("nan"), dtype=torch.float32, device=dev)
+    status = _i32(n_pairs, dev, return_status)
+    for i0 in range(0, n_pairs, _ALIGN_PAIRS):
+        n = min(_ALIGN_PAIRS, n_pairs - i0)
+        sl = slice(i0, i0 + n)
+        _tail_call(dev, "pair_region_transfer", (n_feat, n, B, heads, N, D),
+                   f"no region transfer for n_feat={n_feat} n_pairs={n} B={B} H={heads} N={N} D={D}", q.data_ptr(), k.data_ptr(),
+                   weights_u8.data_ptr(), n_feat, idx_a[sl].data_ptr(), idx_b[sl].data_ptr(), n, B, heads, N, D, _TORCH2DSIM[q.dtype],
+                   int(directions), mass[sl].data_ptr(), _ptr(None if status is None else status[sl]))
+    return (mass, status) if return_status else mass
+
+
 def score_matrix_workspace_bytes(n_a: int, n_b: int, B: int, heads: int, N: int, D: int, dtype: torch.dtype) -> int:
     return int(_lib.lib().dsim_score_matrix_workspace_bytes(n_a, n_b, B, heads, N, D, _TORCH2DSIM[dtype]))
 

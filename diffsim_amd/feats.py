@@ -62,6 +62,14 @@ class FeatureView:
             raise AttributeError(name)
         return getattr(self.scorer, name)
 
+    exemplar_regions = False                # (stated here: __getattr__ would answer with the wrapped scorer's)
+
+    def exemplar_region_score(self, *args, **kwargs):
+        """A feature cosine has no region tail, so no exemplar-guided regions either."""
+        raise NotImplementedError(f"{self.metric} has no exemplar-guided regions: they need --metric diffsim, diffsim_xl or dit")
+
+    transferred_region = exemplar_region_score
+
     # ---- the Scorer protocol: what this view changes (scorer.py)
     def tap_of(self, target_block, target_layer):
         """diffeats: a one-element target_layer list is its element, taken literally (diffeats.py:143-144); dinofeats: dino_cross's

@@ -74,7 +74,7 @@ def cute_accuracy(s_ab: torch.Tensor, s_ac: torch.Tensor) -> float:
 
 @torch.no_grad()
 def triplet_chunks(scorer, ref, left, right, nA, nB, prompt, heads, similarity, batch_triplets: int, feats, masks=None, text=None,
-                   tails=None, soft: bool = False):
+                   tails=None, soft: bool = False, exemplar=None):
     """(ref,left) and (ref,right) scores of latent triplets at every tap of a forward: 3 forwards per triplet (the reference
     image's features are shared), chunked engine batches, one fused tail launch per chunk and tap.  feats(lat, nz, prompt) ->
     [(q, k, v) per tap] is the forward of one engine batch, heads[t] tap t's head count.  masks: None, or the (ref, left, right)
@@ -82,7 +82,9 @@ def triplet_chunks(scorer, ref, left, right, nA, nB, prompt, heads, similarity, 
     text: None, or (guide, w): a textattn.TextGuide and its bound per-triplet weights; feats then returns (q, k, v, xq, xkv) per
     tap and the masks of the region tail are the text-guided regions of the chunk's images -- ref, left and right each their own,
     the ref's made once per triplet.  soft: the masks are (n, N) uint8 token weights (or the guide makes weights: TextGuide(soft=True))
-    and the tail is the soft region tail, engine.pair_score_weights.  tails: None, or each tap's ``Scorer.pair_tail`` (a None entry: engine.pair_score).  Returns
+    and the tail is the soft region tail, engine.pair_score_weights.  exemplar: None, or a transfer.ExemplarGuide (with masks): only the
+    ref's masks count, and left and right each get the region the ref's mask transfers to them -- one transfer launch per chunk and tap,
+    directions=2 over the chunk's (ia, ib), covers both; the guide's soft decides the tail.  tails: None, or each tap's ``Scorer.pair_tail`` (a None entry: engine.pair_score).  Returns
     the (nt, n) scores of both sides and the (nt,) NaN / inf counts."""
     n, nt, dev = ref.shape[0], len(heads), scorer.device
     s_l = torch.empty((nt, n), dtype=torch.float32, device=dev)
@@ -102,6 +104,8 @@ def triplet_chunks(scorer, ref, left, right, nA, nB, prompt, heads, similarity, 
                     rows, _counts = text[0].regions(*xs, heads[t], text[1], i0, i1, 3)
                 else:
                     rows = torch.stack([mk[i0:i1] for mk in masks], dim=1).reshape(3 * m, -1).contiguous()
+                    if exemplar is not None:
+                        rows = exemplar.regions(q, k, heads[t], rows, ia, ib).contiguous()
                 region_tail = pair_score_weights if soft or (text is not None and getattr(text[0], "soft", False)) else pair_score_regions
                 s, st = region_tail(q, k, v, rows, ia, ib, heads[t], similarity, return_status=True)
                 st = (st != 0).to(torch.int32)
@@ -111,13 +115,16 @@ def triplet_chunks(scorer, ref, left, right, nA, nB, prompt, heads, similarity, 
 
 
 def _score_chunks(scorer, ref, left, right, nA, nB, prompt, block, layer, step, similarity, batch_triplets, masks=None, text=None,
-                  soft: bool = False):
+                  soft: bool = False, exemplar=None):
     """triplet_chunks at the one tap (block, layer): each engine batch is one ``tap_features`` call.  masks: None, or one
     (ref, left, right) triple of masks per triplet (``regions.as_token_mask``), put on the tap's token grid here.  text: None, or
     a textattn.TextGuide: each engine batch is one ``tap_features_text`` call and the regions come from the text attention maps
     (per-row prompts give per-triplet weights).  soft (with masks): the masks become token weights (``regions.as_token_weights``) and
-    the tail the soft region tail."""
+    the tail the soft region tail.  exemplar: None, or a transfer.ExemplarGuide: masks then holds ONE entry per triplet, the ref's mask
+    (None: the whole image), and left and right get the regions it transfers to them (soft as the guide says)."""
     n = ref.shape[0]
+    if exemplar is not None:
+        masks, soft = _exemplar_masks(scorer, exemplar, masks, text, soft)
     if soft and masks is None:
         raise ValueError("soft=True weighs the tokens of masks=: it needs them (a text guide is soft by TextGuide(soft=True))")
     tap = scorer.tap_of(block, layer)
@@ -130,6 +137,7 @@ def _score_chunks(scorer, ref, left, right, nA, nB, prompt, block, layer, step, 
         grid = tap_grid(scorer, tap, ref.shape[-1])
         on_grid = as_token_weights if soft else as_token_mask
         masks = [torch.stack([on_grid(mk[c], grid) for mk in masks]).flatten(1).to(scorer.device) for c in range(3)]
+    ex = {} if exemplar is None else {"exemplar": exemplar}
     prompt = scorer.bind_prompt(prompt, n)
     eng = scorer.engine_at(tap)
     heads = eng.heads
@@ -140,7 +148,22 @@ def _score_chunks(scorer, ref, left, right, nA, nB, prompt, block, layer, step, 
                               lambda lat, nz, p: [scorer.tap_features_text(lat, nz, p, tap, step)], text=text)
     return triplet_chunks(scorer, ref, left, right, nA, nB, prompt, [heads], similarity, batch_triplets,
                           lambda lat, nz, p: [scorer.tap_features(lat, nz, p, tap, step)], *(() if masks is None else (masks,)),
-                          tails=[scorer.pair_tail(tap)], **({"soft": True} if soft else {}))
+                          tails=[scorer.pair_tail(tap)], **({"soft": True} if soft else {}), **ex)
+
+
+def _exemplar_masks(scorer, exemplar, masks, text, soft: bool):
+    """The checks of an exemplar-guided triplet run, and its masks as (ref, None, None) triples: (masks, the guide's soft)."""
+    from .transfer import require_exemplar_regions
+    require_exemplar_regions(scorer)
+    if text is not None:
+        raise ValueError("exemplar= and text=: an exemplar-guided region and a text-guided region, one or the other")
+    if masks is None:
+        raise ValueError("exemplar= transfers the ref's masks: it needs masks= (one entry per triplet, the ref's; None allowed)")
+    if any(isinstance(mk, (tuple, list)) and len(mk) == 3 for mk in masks):
+        raise ValueError("exemplar= takes one mask per triplet, the ref's: (ref, left, right) triples belong to a run without it")
+    if soft and not exemplar.soft:
+        raise ValueError("soft=True with a hard guide: a soft exemplar run is ExemplarGuide(soft=True)")
+    return [(mk, None, None) for mk in masks], exemplar.soft
 
 
 @torch.no_grad()
@@ -181,7 +204,8 @@ def path_triplet_scores(scorer, triplets: Sequence[Tuple[str, str, str, str]], i
 
 def score_path_triplets(scorer, triplets: Sequence[Tuple[str, str, str, str]], img_size: int, target_block, target_layer,
                         target_step, seed=2333, similarity="cosine", rank: int = 0, world: int = 1, batch_triplets: int = 10,
-                        unet_triplets: Optional[int] = None, masks: Optional[Sequence] = None, text=None, soft: bool = False):
+                        unet_triplets: Optional[int] = None, masks: Optional[Sequence] = None, text=None, soft: bool = False,
+                        exemplar=None):
     """Scores s(A,B) and s(A,C) of every (A, B, C, prompt) path triplet -- the two scorer calls per triplet the
     reference's loops make (cute_main.py:111-132, night_main.py:69-90, style_main.py:150-175) -- for all three scorer
     kinds (DiffSim, diffsim_xl, diffsim_DiT): whole triplets sharded over ranks (the cached reference-image features stay
@@ -196,12 +220,18 @@ def score_path_triplets(scorer, triplets: Sequence[Tuple[str, str, str, str]], i
     byte weights on the token grid (``regions.as_token_weights``: the area average kept, not thresholded) and the tail is
     ``engine.pair_score_weights``; with soft=False every call and launch is the hard run's.  text: None, or a textattn.TextGuide (words, threshold):
     text-guided regions instead -- ref, left and right each get the region their own text attention map gives, the ref's once per
-    triplet, a prompt per row giving weights per image; text.on_fraction is then the mean share of tokens on.  Returns
+    triplet, a prompt per row giving weights per image; text.on_fraction is then the mean share of tokens on.  exemplar: None, or a
+    transfer.ExemplarGuide (threshold, soft): exemplar-guided regions -- masks then holds one entry per triplet, the REF's mask alone
+    (None allowed), and left and right each get the region that mask transfers to them (transfer.py); exemplar.on_fraction is then the
+    mean share of tokens on; with text, or with (ref, left, right) triples, a ValueError; with exemplar=None every call and launch is
+    the run's without it.  Returns
     (s_ab, s_ac, n_nonfinite):
     length-len(triplets) f32 tensors on every rank and the number of NaN/inf pair scores (NaN guard)."""
     # (batch_triplets sizes the decode / VAE-encode chunks; the U-Net batch is unet_triplets, or the scorer's auto_rows)
     if masks is not None and len(masks) != len(triplets):
         raise ValueError(f"{len(masks)} mask triples for {len(triplets)} triplets")
+    if exemplar is not None:
+        _exemplar_masks(scorer, exemplar, masks, text, soft)
     if masks is not None and text is not None:
         raise ValueError("a text-guided region and a mask file per image: one or the other")
     if soft and masks is None:
@@ -209,7 +239,8 @@ def score_path_triplets(scorer, triplets: Sequence[Tuple[str, str, str, str]], i
     all_l, all_r, nbad = path_triplet_scores(
         scorer, triplets, img_size, seed, rank, world, batch_triplets, 1,
         lambda *lat_prompt: _score_chunks(scorer, *lat_prompt[:6], target_block, target_layer, target_step, similarity, unet_triplets,
-                                          *lat_prompt[6:], **({} if text is None else {"text": text}), **({"soft": True} if soft else {})),
+                                          *lat_prompt[6:], **({} if text is None else {"text": text}), **({"soft": True} if soft else {}),
+                                          **({} if exemplar is None else {"exemplar": exemplar})),
         *(() if masks is None else (masks,)))
     return all_l[0], all_r[0], int(nbad)
 

@@ -197,6 +197,12 @@ class _ViTScore(Scorer):
         self.side = self.preprocess.crop
         self._engines: Dict[int, ViTEngine] = {}
 
+    def exemplar_region_score(self, *args, **kwargs):
+        """The ViT metrics have no region tails, so no exemplar-guided regions either."""
+        raise NotImplementedError(f"{type(self).__name__} has no exemplar-guided regions: they need --metric diffsim, diffsim_xl or dit")
+
+    transferred_region = exemplar_region_score
+
     def engine(self, layer: int, side: Optional[int] = None) -> ViTEngine:
         side = self.side if side is None else int(side)
         eng = self._engines.get(side)

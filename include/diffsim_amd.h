@@ -526,6 +526,32 @@ int    dsim_text_attention(const void* xq, int ldq, const void* xk, int ldk, int
                            float* attn, float* saliency, uint8_t* mask, int32_t* counts, int32_t* status,
                            void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- region transfer: the attention mass a token sends into the other image's region -------------------------------------------
+ * Every feature image i carries a byte m_i[t] in 0 .. 255 per token, w = m / 255 (the soft regions' convention).  With Pm exactly
+ * as dsim_pair_align defines it (softmax over ALL keys, logits from the stored un-rescaled q and k, the scale entering in f32,
+ * nothing rounded to 16 bits, the mean over the B CFG halves and H heads), for pair p (a = idx_a[p], b = idx_b[p]):
+ *   mass[p][0][i] = sum_j Pm_ab[i][j] w_b[j]   (on a's grid: a's queries over b's keys)
+ *   mass[p][1][u] = sum_t Pm_ba[u][t] w_a[t]   (on b's grid: b's queries over a's keys)
+ * The weights enter the sum only; no bias joins the logits.  A mass lies in [0, 1] and is 1 where every key byte is 255.
+ *   q,k         : dtype [n_feat][B][N][H*D], as dsim_pair_align (no v)
+ *   weights     : device uint8 [n_feat][N]
+ *   directions  : 1: rows [p][0] only, 2: rows [p][1] only, 3: both; rows of a direction not asked for are not written
+ *   mass        : device f32 [n_pairs][2][N]
+ *   status      : NULL, or device int32 [n_pairs]: 1 where a probability of the pair (in a direction asked for) is non-finite
+ * One pass over the keys, Pm is never formed: per query row and (b, h) the online maximum and two running f32 sums,
+ * l = sum_j e_ij and num = sum_j e_ij w_j (fma) with e_ij = exp2(fma(s, c, -m c)), r_bh = num / l; mass = (sum over (b, h) ascending
+ * of r_bh) * (1 / (B H)).  The workspace holds r_bh, f32 [n_pairs][2][B H][N], folded in that fixed order by a second launch.
+ * Deterministic, no atomics; a pair's values do not depend on the other pairs of the call, on the directions asked for, or on the
+ * weights of images other than the row's key image.  All checks before anything is enqueued: DSIM_ERR_INVALID (workspace query: 0)
+ * as dsim_pair_align for the dtype, head dim and shape, for n_feat < 1 or n_feat N >= 2^31; DSIM_ERR_INVALID for directions
+ * outside 1 .. 3 and a NULL weights or mass; DSIM_ERR_WORKSPACE for a short workspace. */
+size_t dsim_pair_region_transfer_workspace_bytes(int n_feat, int n_pairs, int B, int H, int N, int D);
+int    dsim_pair_region_transfer(const void* q, const void* k, const uint8_t* weights /* [n_feat][N] */, int n_feat,
+                                 const int32_t* idx_a, const int32_t* idx_b, int n_pairs, int B, int H, int N, int D, int dtype,
+                                 int directions /* 1: rows [p][0], 2: rows [p][1], 3: both */,
+                                 float* mass /* [n_pairs][2][N] */, int32_t* status /* NULL or [n_pairs] */,
+                                 void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- VAE encoder: replaces `pipe.vae.encode(image)` in
  *      DiffSim.prepare_image_latents (diffsim/diffsim.py:92-96).  Sampling
  *      z = mean + exp(0.5*clamp(logvar,-30,20))*eps and the 0.18215 scaling stay with the caller,
