@@ -1,7 +1,8 @@
 """End-to-end parity of the HIP scoring path (through the C ABI) against the CPU oracle and the
 golden fixtures captured from the reference.  Gate (BASELINE.json north_star): scores within
 1e-4 relative in the fp32 kernel mode on identical (latent, noise seed, timestep, weights);
-the bf16 production mode reports its error against a looser, stated bound."""
+the bf16 production mode reports its error against a looser, stated bound on the score; what the 16-bit walks compute tap by tap,
+q / k / v against float64, is held in tests/test_gpu_walk64.py."""
 import json
 import os
 

@@ -18,37 +18,8 @@ def _rel(a, b):
     return abs(a - b) / max(abs(b), 1e-6)
 
 
-def _oracle_unet(R, rcfg, sd, shapes, dtype=torch.float32):
-    """Oracle U-Net without materialising random-init parameters first: meta construction + assign (the unused tail of
-    the graph gets zero tensors, which calloc never touches)."""
-    with torch.device("meta"):
-        m = R.UNet2DConditionModel(rcfg)
-    full = {k: (sd[k].to(dtype) if k in sd else torch.zeros(shp, dtype=dtype)) for k, shp in shapes.items()}
-    m.load_state_dict(full, strict=True, assign=True)
-    return m.eval()
-
-
-def _qkv_at_taps(R, unet, x, t, ctx, added, taps):
-    """q,k,v of several taps from ONE oracle forward (pre-hooks, diffsim/diffsim.py:43-56 style); stops at the last."""
-    store, hooks = {}, []
-    names = list(taps)
-    for name in names:
-        mod = unet.tap_module(*taps[name])
-
-        def hook(m, inp, name=name):
-            store[name] = m.qkv(inp[0])
-            if name == names[-1]:
-                raise R._TapReached()
-        hooks.append(mod.register_forward_pre_hook(hook))
-    try:
-        with torch.no_grad():
-            unet.forward(x, t, ctx, None, added)
-    except R._TapReached:
-        pass
-    finally:
-        for h in hooks:
-            h.remove()
-    return store
+# the oracle U-Net built without random init and its many-taps forward: shared with the per-tap float64 comparison of the 16-bit walks
+from tests._walk64 import oracle_unet as _oracle_unet, qkv_at_taps as _qkv_at_taps  # noqa: E402
 
 
 def test_sdxl_1024px_two_taps():
