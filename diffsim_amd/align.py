@@ -18,9 +18,9 @@ from typing import Optional, Sequence, Tuple
 
 import torch
 
-from .engine import pair_align, pair_align_regions, pair_align_weights
+from .engine import pair_align, pair_align_regions, pair_align_weights      # noqa: F401  (RegionKind.tail)
 from .inputs import path_latents
-from .maps import grid_shape
+from .regions import chunk_tails, grid_shape, kind_of, path_rows, tap_grid
 from .retrieval import ranking_names
 
 
@@ -85,23 +85,15 @@ def score_latent_pair_alignment(scorer, latA, latB, noiseA, noiseB, prompt, targ
     (``engine.pair_align_weights``); the alignment then carries the weights."""
     dev = scorer.device
     n = latA.shape[0]
-    tail_of = both = wts = None
-    if soft:
-        from .regions import pair_token_weights
-        if maskA is None and maskB is None:
-            raise ValueError("soft=True weighs masks: give maskA and / or maskB")
-        grid, wts = pair_token_weights(scorer, scorer.tap_of(target_block, target_layer), latA.shape[-1], n, maskA, maskB)
-
-        def tail_of(i0, i1):
-            chunk = wts[i0:i1].reshape(2 * (i1 - i0), -1).contiguous()
-            return lambda q, k, v, ia, ib, heads, similarity: pair_align_weights(q, k, chunk, ia, ib, heads, grid[1])
-    elif maskA is not None or maskB is not None:
-        from .regions import pair_token_masks
-        grid, both = pair_token_masks(scorer, scorer.tap_of(target_block, target_layer), latA.shape[-1], n, maskA, maskB)
-
-        def tail_of(i0, i1):
-            chunk = both[i0:i1].reshape(2 * (i1 - i0), -1).contiguous()
-            return lambda q, k, v, ia, ib, heads, similarity: pair_align_regions(q, k, chunk, ia, ib, heads, grid[1])
+    tail_of, carried = None, {}
+    if soft and maskA is None and maskB is None:
+        raise ValueError("soft=True weighs masks: give maskA and / or maskB")
+    if maskA is not None or maskB is not None:
+        kind = kind_of(soft)
+        grid, rows = kind.pair_rows(scorer, scorer.tap_of(target_block, target_layer), latA.shape[-1], n, maskA, maskB)
+        align_tail = kind.tail("align", globals())
+        tail_of = chunk_tails(rows, lambda chunk, q, k, v, ia, ib, heads, similarity: align_tail(q, k, chunk, ia, ib, heads, grid[1]))
+        carried = {kind.carried: rows}
     latA, latB = latA.to(dev, torch.float32), latB.to(dev, torch.float32)
     noiseA, noiseB = noiseA.to(dev, torch.float32), noiseB.to(dev, torch.float32)
     tap = scorer.tap_of(target_block, target_layer)
@@ -120,7 +112,7 @@ def score_latent_pair_alignment(scorer, latA, latB, noiseA, noiseB, prompt, targ
         match[i0:i1], weight[i0:i1], expect[i0:i1] = m, w, e
     if match is None:
         raise ValueError("no pairs to align")
-    return Alignment(match, weight, expect, both, wts)
+    return Alignment(match, weight, expect, **carried)
 
 
 @torch.no_grad()
@@ -135,13 +127,9 @@ def score_path_pair_alignment(scorer, pairs: Sequence[Tuple[str, str]], img_size
     (latA, latB), nA, nB = path_latents(scorer, list(pairs), (0, 1), img_size, seed, 16, hip_vae=hip_vae)
     mA = mB = None
     if masks is not None:
-        from .regions import as_token_mask, as_token_weights, tap_grid
         if len(masks) != len(pairs):
             raise ValueError(f"{len(masks)} mask pairs for {len(pairs)} pairs")
-        grid = tap_grid(scorer, scorer.tap_of(target_block, target_layer), latA.shape[-1])
-        on_grid = as_token_weights if soft else as_token_mask
-        mA = torch.stack([on_grid(m[0], grid) for m in masks])
-        mB = torch.stack([on_grid(m[1], grid) for m in masks])
+        mA, mB = path_rows(kind_of(soft), masks, tap_grid(scorer, scorer.tap_of(target_block, target_layer), latA.shape[-1]))
     return score_latent_pair_alignment(scorer, latA, latB, nA, nB, prompt, target_block, target_layer, target_step, batch_pairs,
                                        maskA=mA, maskB=mB, soft=soft)
 

@@ -621,13 +621,13 @@ def run_retrieval(args, scorer, layer) -> int:
         afiles = A.write_match_files(args.out_path, queries, gallery, idx, al, args.query_path)
         print(f"Token alignments {al.grid[0]}x{al.grid[1]} of the top-{k} cells of {len(afiles)} queries written to {args.out_path}")
     if (args.save_region_maps or args.save_region_matches) and queries and gallery:
-        from .regions import tap_grid
+        from .regions import kind_of, tap_grid
         _vals, idx = R.topk(m, args.topk, args.similarity)
         k = idx.shape[1]
         cells = idx.reshape(-1)
         # the matrix's own token masks or weights (a missing or empty mask: the whole image), one pair of them per top-k cell
         grid = tap_grid(scorer, scorer.tap_of(args.target_block, layer), latA.shape[-1])
-        set_of = R.set_weights if args.soft_masks else R._set_masks
+        set_of = kind_of(args.soft_masks).set_rows
         soft = {"soft": True} if args.soft_masks else {}
         mA = set_of(masks.get("masks_a"), len(queries), grid, "cpu", "masks_a").repeat_interleave(k, 0)
         mB = set_of(masks.get("masks_b"), len(gallery), grid, "cpu", "masks_b")[cells.cpu()]

@@ -25,7 +25,7 @@ from concurrent.futures import ThreadPoolExecutor
 import torch
 
 from . import scheduler as sched
-from . import align, maps, regions, retrieval, sweep, textattn, transfer
+from . import align, maps, retrieval, sweep
 from .config import SD15, UNetConfig
 from .engine import UNetEngine, _LatentDist, image_preprocess, pair_score, resize_u8
 from .image import DecodePool, host_threads, load_image, process_image
@@ -123,6 +123,12 @@ class DiffSim(Scorer):
 
     def prepare(self, tensor, generator):
         return self.prepare_image_latents(tensor, None, None, generator).to(self.noise_draw).float()
+
+    path_hip_vae = True                     # the one-pair path calls encode through the HIP VAE (scorer.py)
+    exemplar_regions = True                 # the kind has exemplar-guided regions (transfer.py)
+
+    def path_tap(self, prompt, target_block, target_layer):
+        return prompt, target_block, _norm_layer(target_layer)
 
     def tap_of(self, target_block, target_layer):
         return target_block, _norm_layer(target_layer)
@@ -377,104 +383,6 @@ class DiffSim(Scorer):
         """Maps of the pairs of :meth:`score_latent_pairs` (maps.score_latent_pair_maps)."""
         return maps.score_latent_pair_maps(self, latA, latB, noiseA, noiseB, prompt, target_block, _norm_layer(target_layer),
                                            target_step, similarity, batch_pairs)
-
-    @torch.no_grad()
-    def alignment(self, image_A, image_B, img_size, prompt, target_block, target_layer, target_step, seed="2333"):
-        """Which token of the other image each token of one :meth:`diffsim` pair attends to: an
-        :class:`~diffsim_amd.align.Alignment` of one pair (direction 0 on image_A's grid, 1 on image_B's)."""
-        return align.score_path_pair_alignment(self, [(image_A, image_B)], img_size, prompt, target_block, _norm_layer(target_layer),
-                                               target_step, seed)
-
-    @torch.no_grad()
-    def region_score(self, image_A, image_B, mask_A, mask_B, img_size, prompt, target_block, target_layer, target_step,
-                     seed="2333", similarity="cosine"):
-        """:meth:`diffsim` of the masked part of each image (regions.py): the score tail over the tokens of mask_A on image_A and
-        of mask_B on image_B alone.  A mask is a path, a PIL image, a bool array on the tap's token grid, or None (the whole
-        image); full masks give :meth:`diffsim`'s score.  Returns a (1,) tensor."""
-        return regions.score_path_pair_regions(self, [(image_A, image_B)], [(mask_A, mask_B)], img_size, prompt, target_block,
-                                               _norm_layer(target_layer), target_step, seed, similarity)
-
-    @torch.no_grad()
-    def soft_region_score(self, image_A, image_B, mask_A, mask_B, img_size, prompt, target_block, target_layer, target_step,
-                          seed="2333", similarity="cosine"):
-        """:meth:`region_score` with a weight per token instead of a bit (regions.py, ``engine.pair_score_weights``): a mask's area
-        average on the token grid is the token's weight, so a partly covered token counts partly -- as a key through a logit bias in
-        both attentions, as a query through a factor on its terms.  A mask is a path, a PIL image, a uint8 / bool / [0, 1] float
-        array on the tap's token grid, or None (the whole image); masks of 0 and 255 alone give :meth:`region_score`'s score.
-        Returns a (1,) tensor."""
-        return regions.score_path_pair_weights(self, [(image_A, image_B)], [(mask_A, mask_B)], img_size, prompt, target_block,
-                                               _norm_layer(target_layer), target_step, seed, similarity)
-
-    @torch.no_grad()
-    def region_similarity_maps(self, image_A, image_B, mask_A, mask_B, img_size, prompt, target_block, target_layer, target_step,
-                               seed="2333", similarity="cosine"):
-        """:meth:`region_score` of one image pair with its per-token terms on both images' grids: a
-        :class:`~diffsim_amd.maps.SimilarityMaps` of one pair whose attentions ran over the masked tokens alone (zeros at the off
-        tokens; ``.mask`` holds the two token masks).  Masks as :meth:`region_score` takes them."""
-        return maps.score_path_pair_maps(self, [(image_A, image_B)], img_size, prompt, target_block, _norm_layer(target_layer),
-                                         target_step, seed, similarity, masks=[(mask_A, mask_B)])
-
-    @torch.no_grad()
-    def region_alignment(self, image_A, image_B, mask_A, mask_B, img_size, prompt, target_block, target_layer, target_step,
-                         seed="2333"):
-        """Which token of the other image's region each token of a region attends to: an :class:`~diffsim_amd.align.Alignment` of
-        one pair whose softmaxes ran over the other image's masked tokens alone (off tokens: match -1; ``.mask`` holds the two
-        token masks).  Masks as :meth:`region_score` takes them."""
-        return align.score_path_pair_alignment(self, [(image_A, image_B)], img_size, prompt, target_block, _norm_layer(target_layer),
-                                               target_step, seed, masks=[(mask_A, mask_B)])
-
-    @torch.no_grad()
-    def soft_region_similarity_maps(self, image_A, image_B, mask_A, mask_B, img_size, prompt, target_block, target_layer, target_step,
-                                    seed="2333", similarity="cosine"):
-        """:meth:`soft_region_score` of one image pair with its per-token terms on both images' grids: a
-        :class:`~diffsim_amd.maps.SimilarityMaps` of one pair (``.weights`` holds the two uint8 token weights, ``.mask`` is
-        ``weights != 0``; zeros at the tokens of weight 0).  ``local`` is a token's own value, ``contrib`` carries its weight.
-        Masks as :meth:`soft_region_score` takes them."""
-        return maps.score_path_pair_maps(self, [(image_A, image_B)], img_size, prompt, target_block, _norm_layer(target_layer),
-                                         target_step, seed, similarity, masks=[(mask_A, mask_B)], soft=True)
-
-    @torch.no_grad()
-    def soft_region_alignment(self, image_A, image_B, mask_A, mask_B, img_size, prompt, target_block, target_layer, target_step,
-                              seed="2333"):
-        """:meth:`region_alignment` with soft masks: every softmax runs over the other image's tokens of weight > 0 with ln(weight)
-        added to the logits (an :class:`~diffsim_amd.align.Alignment` of one pair; ``.weights`` holds the two uint8 token weights;
-        tokens of weight 0: match -1).  Masks as :meth:`soft_region_score` takes them."""
-        return align.score_path_pair_alignment(self, [(image_A, image_B)], img_size, prompt, target_block, _norm_layer(target_layer),
-                                               target_step, seed, masks=[(mask_A, mask_B)], soft=True)
-
-    @torch.no_grad()
-    def text_region_score(self, image_A, image_B, img_size, prompt, target_block, target_layer, target_step, seed="2333",
-                          similarity="cosine", words=None, rel_threshold=1.0):
-        """:meth:`diffsim` of the part of each image the prompt names (textattn.py; the reference's declared and unbuilt
-        ``--use_text_attn``, argprocess.py:17): each image's region is the tokens whose text attention to `words` (None: every
-        content token of the prompt) is at least rel_threshold x the image's mean.  Returns a (1,) tensor."""
-        return textattn.score_path_pairs_text(self, [(image_A, image_B)], img_size, prompt, target_block, _norm_layer(target_layer),
-                                              target_step, seed, similarity, words, rel_threshold)
-
-    exemplar_regions = True                 # the kind has exemplar-guided regions (transfer.py)
-
-    @torch.no_grad()
-    def exemplar_region_score(self, image_A, image_B, mask_A, img_size, prompt, target_block, target_layer, target_step, seed="2333",
-                              similarity="cosine", rel_threshold=1.0, soft=False):
-        """:meth:`region_score` with a mask for image_A alone (transfer.py): image_B's region is the tokens whose attention mass into
-        mask_A's tokens is at least rel_threshold x the image's mean; soft: token weights on both sides.  Returns a (1,) tensor."""
-        return transfer.score_path_pairs_exemplar(self, [(image_A, image_B)], [mask_A], img_size, prompt, target_block,
-                                                  _norm_layer(target_layer), target_step, seed, similarity, None, rel_threshold, soft)
-
-    @torch.no_grad()
-    def transferred_region(self, image_A, image_B, mask_A, img_size, prompt, target_block, target_layer, target_step, seed="2333",
-                           rel_threshold=1.0, soft=False):
-        """(mass (h, w) f32, region (h, w) bool -- soft: uint8 weights) on image_B's token grid: what :meth:`exemplar_region_score`
-        transfers from mask_A."""
-        return transfer.path_transferred_region(self, image_A, image_B, mask_A, img_size, prompt, target_block,
-                                                _norm_layer(target_layer), target_step, seed, rel_threshold, soft)
-
-    @torch.no_grad()
-    def text_attention_map(self, image_A, image_B, img_size, prompt, target_block, target_layer, target_step, seed="2333"):
-        """The text attention maps of the two images of one :meth:`diffsim` call: (2, h, w, L) f32 on the tap's token grid."""
-        latA, latB, nA, nB = self._path_pair_latents(image_A, image_B, img_size, seed)
-        return textattn.text_attention_maps(self, torch.cat([latA, latB]), torch.cat([nA, nB]), prompt, target_block,
-                                            _norm_layer(target_layer), target_step)
 
     @torch.no_grad()
     def score_latent_pair_alignment(self, latA, latB, noiseA, noiseB, prompt, target_block="up_blocks", target_layer=0,

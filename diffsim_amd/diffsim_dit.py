@@ -10,7 +10,7 @@ from typing import Dict, Optional
 
 import torch
 
-from . import align, maps, regions, sweep, transfer
+from . import align, maps, sweep
 from . import scheduler as sched
 from ._lib import DsimError
 from .config import DIT_XL2, DiTConfig
@@ -48,6 +48,12 @@ class diffsim_DiT(Scorer):
         return self._engine
 
     # ---- the Scorer protocol: this kind's facts (scorer.py)
+    path_batch_pairs = 32       # the one-pair path calls' engine batch
+    exemplar_regions = True     # the kind has exemplar-guided regions (transfer.py): no text is involved
+
+    def path_tap(self, prompt, target_block, target_layer):
+        return None, "none", [int(target_layer[0])]
+
     def tap_of(self, target_block, target_layer):
         return int(target_layer[0])                 # the hook on model.blocks[target_layer[0]].attn
 
@@ -119,77 +125,6 @@ class diffsim_DiT(Scorer):
         """Maps of the pairs of :meth:`score_latent_pairs` (maps.score_latent_pair_maps)."""
         return maps.score_latent_pair_maps(self, latA, latB, noiseA, noiseB, None, "none", [int(target_layer)], target_step, similarity,
                                            batch_pairs)
-
-    @torch.no_grad()
-    def alignment(self, image_A, image_B, img_size, prompt, target_block, target_layer, target_step, seed):
-        """Which token of the other image each token of one :meth:`diffsim_score` pair attends to (an align.Alignment of one
-        pair)."""
-        (latA, latB), nA, nB = path_latents(self, [(image_A, image_B)], (0, 1), img_size, seed, 1, hip_vae=False)
-        return self.score_latent_pair_alignment(latA, latB, nA, nB, target_layer[0], target_step)
-
-    @torch.no_grad()
-    def region_score(self, image_A, image_B, mask_A, mask_B, img_size, prompt, target_block, target_layer, target_step, seed,
-                     similarity):
-        """:meth:`diffsim_score` of the masked part of each image (regions.py); a mask is a path, a PIL image, a bool array on the
-        token grid, or None (the whole image).  Returns a (1,) tensor."""
-        return regions.score_path_pair_regions(self, [(image_A, image_B)], [(mask_A, mask_B)], img_size, None, "none",
-                                               [int(target_layer[0])], target_step, seed, similarity, batch_pairs=32, hip_vae=False)
-
-    @torch.no_grad()
-    def soft_region_score(self, image_A, image_B, mask_A, mask_B, img_size, prompt, target_block, target_layer, target_step, seed,
-                          similarity):
-        """:meth:`region_score` with a weight per token instead of a bit (``regions.score_path_pair_weights``); a mask is a path, a
-        PIL image, a uint8 / bool / [0, 1] float array on the token grid, or None.  Returns a (1,) tensor."""
-        return regions.score_path_pair_weights(self, [(image_A, image_B)], [(mask_A, mask_B)], img_size, None, "none",
-                                               [int(target_layer[0])], target_step, seed, similarity, batch_pairs=32, hip_vae=False)
-
-    @torch.no_grad()
-    def region_similarity_maps(self, image_A, image_B, mask_A, mask_B, img_size, prompt, target_block, target_layer, target_step,
-                               seed, similarity):
-        """:meth:`region_score` with its per-token terms on both images' grids (a maps.SimilarityMaps of one pair over the masked
-        tokens; ``.mask`` holds the two token masks)."""
-        return maps.score_path_pair_maps(self, [(image_A, image_B)], img_size, None, "none", [int(target_layer[0])], target_step, seed,
-                                         similarity, 32, masks=[(mask_A, mask_B)], hip_vae=False)
-
-    @torch.no_grad()
-    def region_alignment(self, image_A, image_B, mask_A, mask_B, img_size, prompt, target_block, target_layer, target_step, seed):
-        """Which token of the other image's region each token of a region attends to (an align.Alignment of one pair over the
-        masked tokens; ``.mask`` holds the two token masks)."""
-        return align.score_path_pair_alignment(self, [(image_A, image_B)], img_size, None, "none", [int(target_layer[0])], target_step,
-                                               seed, 32, masks=[(mask_A, mask_B)], hip_vae=False)
-
-    @torch.no_grad()
-    def soft_region_similarity_maps(self, image_A, image_B, mask_A, mask_B, img_size, prompt, target_block, target_layer, target_step,
-                                    seed, similarity):
-        """:meth:`soft_region_score` with its per-token terms on both images' grids (a maps.SimilarityMaps of one pair; ``.weights``
-        holds the two uint8 token weights)."""
-        return maps.score_path_pair_maps(self, [(image_A, image_B)], img_size, None, "none", [int(target_layer[0])], target_step, seed,
-                                         similarity, 32, masks=[(mask_A, mask_B)], hip_vae=False, soft=True)
-
-    @torch.no_grad()
-    def soft_region_alignment(self, image_A, image_B, mask_A, mask_B, img_size, prompt, target_block, target_layer, target_step, seed):
-        """:meth:`region_alignment` with soft masks (an align.Alignment of one pair; ``.weights`` holds the two uint8 token
-        weights)."""
-        return align.score_path_pair_alignment(self, [(image_A, image_B)], img_size, None, "none", [int(target_layer[0])], target_step,
-                                               seed, 32, masks=[(mask_A, mask_B)], hip_vae=False, soft=True)
-
-    exemplar_regions = True                 # the kind has exemplar-guided regions (transfer.py): no text is involved
-
-    @torch.no_grad()
-    def exemplar_region_score(self, image_A, image_B, mask_A, img_size, prompt, target_block, target_layer, target_step, seed="2333",
-                              similarity="cosine", rel_threshold=1.0, soft=False):
-        """:meth:`region_score` with a mask for image_A alone (transfer.py): image_B's region is the tokens whose attention mass into
-        mask_A's tokens is at least rel_threshold x the image's mean; soft: token weights on both sides.  Returns a (1,) tensor."""
-        return transfer.score_path_pairs_exemplar(self, [(image_A, image_B)], [mask_A], img_size, None, "none", [int(target_layer[0])],
-                                                  target_step, seed, similarity, 32, rel_threshold, soft, hip_vae=False)
-
-    @torch.no_grad()
-    def transferred_region(self, image_A, image_B, mask_A, img_size, prompt, target_block, target_layer, target_step, seed="2333",
-                           rel_threshold=1.0, soft=False):
-        """(mass (h, w) f32, region (h, w) bool -- soft: uint8 weights) on image_B's token grid: what :meth:`exemplar_region_score`
-        transfers from mask_A."""
-        return transfer.path_transferred_region(self, image_A, image_B, mask_A, img_size, None, "none", [int(target_layer[0])],
-                                                target_step, seed, rel_threshold, soft, 32, hip_vae=False)
 
     def text_region_score(self, *args, **kwargs):
         """DiT is class-conditional: it has no prompt and no cross-attention, so no text-guided regions."""

@@ -13,11 +13,10 @@ from typing import Callable, Dict, Optional, Tuple
 
 import torch
 
-from . import align, maps, regions, sweep, textattn, transfer
+from . import align, maps, sweep
 from . import scheduler as sched
 from .config import SDXL, UNetConfig
 from .engine import UNetEngine, pair_score
-from .inputs import path_latents
 from .scorer import Scorer, check_row_prompts, distinct_prompts
 
 
@@ -60,6 +59,7 @@ class diffsim_xl(Scorer):
 
     # ---- the Scorer protocol: this kind's facts (scorer.py)
     noise_draw = property(lambda self: self.noise_dtype)        # randn_tensor(dtype=latents.dtype) of the pipeline run
+    exemplar_regions = True     # the kind has exemplar-guided regions (transfer.py)
 
     @staticmethod
     def canonical_tap(tap):
@@ -167,8 +167,7 @@ class diffsim_xl(Scorer):
     def _path_pair_inputs(self, image_A, image_B, img_size, prompt, seed):
         """(latentsA, latentsB, noiseA, noiseB, ctx, pooled): what one reference call draws and encodes."""
         ctx, pooled = self.bind_prompt(prompt, 1)
-        (latentsA, latentsB), noiseA, noiseB = path_latents(self, [(image_A, image_B)], (0, 1), img_size, seed, 1, hip_vae=False)
-        return latentsA, latentsB, noiseA, noiseB, ctx, pooled
+        return (*self._path_pair_latents(image_A, image_B, img_size, seed), ctx, pooled)
 
     @torch.no_grad()
     def similarity_maps(self, image_A, image_B, img_size, prompt, target_block, target_layer, target_step, similarity, seed):
@@ -183,93 +182,6 @@ class diffsim_xl(Scorer):
         """Maps of the pairs of :meth:`score_latent_pairs` (maps.score_latent_pair_maps)."""
         return maps.score_latent_pair_maps(self, latA, latB, noiseA, noiseB, (ctx, pooled), target_block, target_layer, target_step,
                                            similarity, batch_pairs)
-
-    @torch.no_grad()
-    def alignment(self, image_A, image_B, img_size, prompt, target_block, target_layer, target_step, seed):
-        """Which token of the other image each token of one :meth:`diffsim_score` pair attends to (an align.Alignment of one
-        pair)."""
-        latentsA, latentsB, noiseA, noiseB, ctx, pooled = self._path_pair_inputs(image_A, image_B, img_size, prompt, seed)
-        return self.score_latent_pair_alignment(latentsA, latentsB, noiseA, noiseB, ctx, pooled, target_block, target_layer, target_step)
-
-    @torch.no_grad()
-    def region_score(self, image_A, image_B, mask_A, mask_B, img_size, prompt, target_block, target_layer, target_step, seed,
-                     similarity):
-        """:meth:`diffsim_score` of the masked part of each image (regions.py); a mask is a path, a PIL image, a bool array on the
-        tap's token grid, or None (the whole image).  Returns a (1,) tensor."""
-        return regions.score_path_pair_regions(self, [(image_A, image_B)], [(mask_A, mask_B)], img_size, prompt, target_block,
-                                               target_layer, target_step, seed, similarity, hip_vae=False)
-
-    @torch.no_grad()
-    def soft_region_score(self, image_A, image_B, mask_A, mask_B, img_size, prompt, target_block, target_layer, target_step, seed,
-                          similarity):
-        """:meth:`region_score` with a weight per token instead of a bit (``regions.score_path_pair_weights``); a mask is a path, a
-        PIL image, a uint8 / bool / [0, 1] float array on the tap's token grid, or None.  Returns a (1,) tensor."""
-        return regions.score_path_pair_weights(self, [(image_A, image_B)], [(mask_A, mask_B)], img_size, prompt, target_block,
-                                               target_layer, target_step, seed, similarity, hip_vae=False)
-
-    @torch.no_grad()
-    def region_similarity_maps(self, image_A, image_B, mask_A, mask_B, img_size, prompt, target_block, target_layer, target_step,
-                               seed, similarity):
-        """:meth:`region_score` with its per-token terms on both images' grids (a maps.SimilarityMaps of one pair over the masked
-        tokens; ``.mask`` holds the two token masks)."""
-        return maps.score_path_pair_maps(self, [(image_A, image_B)], img_size, prompt, target_block, target_layer, target_step, seed,
-                                         similarity, masks=[(mask_A, mask_B)], hip_vae=False)
-
-    @torch.no_grad()
-    def region_alignment(self, image_A, image_B, mask_A, mask_B, img_size, prompt, target_block, target_layer, target_step, seed):
-        """Which token of the other image's region each token of a region attends to (an align.Alignment of one pair over the
-        masked tokens; ``.mask`` holds the two token masks)."""
-        return align.score_path_pair_alignment(self, [(image_A, image_B)], img_size, prompt, target_block, target_layer, target_step,
-                                               seed, masks=[(mask_A, mask_B)], hip_vae=False)
-
-    @torch.no_grad()
-    def soft_region_similarity_maps(self, image_A, image_B, mask_A, mask_B, img_size, prompt, target_block, target_layer, target_step,
-                                    seed, similarity):
-        """:meth:`soft_region_score` with its per-token terms on both images' grids (a maps.SimilarityMaps of one pair; ``.weights``
-        holds the two uint8 token weights)."""
-        return maps.score_path_pair_maps(self, [(image_A, image_B)], img_size, prompt, target_block, target_layer, target_step, seed,
-                                         similarity, masks=[(mask_A, mask_B)], hip_vae=False, soft=True)
-
-    @torch.no_grad()
-    def soft_region_alignment(self, image_A, image_B, mask_A, mask_B, img_size, prompt, target_block, target_layer, target_step, seed):
-        """:meth:`region_alignment` with soft masks (an align.Alignment of one pair; ``.weights`` holds the two uint8 token
-        weights)."""
-        return align.score_path_pair_alignment(self, [(image_A, image_B)], img_size, prompt, target_block, target_layer, target_step,
-                                               seed, masks=[(mask_A, mask_B)], hip_vae=False, soft=True)
-
-    @torch.no_grad()
-    def text_region_score(self, image_A, image_B, img_size, prompt, target_block, target_layer, target_step, seed, similarity,
-                          words=None, rel_threshold=1.0):
-        """:meth:`diffsim_score` of the part of each image the prompt names (textattn.py): each image's region is the tokens whose
-        text attention to `words` (None: every content token of the prompt) is at least rel_threshold x the image's mean.
-        Returns a (1,) tensor."""
-        return textattn.score_path_pairs_text(self, [(image_A, image_B)], img_size, prompt, target_block, target_layer, target_step,
-                                              seed, similarity, words, rel_threshold, hip_vae=False)
-
-    exemplar_regions = True                 # the kind has exemplar-guided regions (transfer.py)
-
-    @torch.no_grad()
-    def exemplar_region_score(self, image_A, image_B, mask_A, img_size, prompt, target_block, target_layer, target_step, seed="2333",
-                              similarity="cosine", rel_threshold=1.0, soft=False):
-        """:meth:`region_score` with a mask for image_A alone (transfer.py): image_B's region is the tokens whose attention mass into
-        mask_A's tokens is at least rel_threshold x the image's mean; soft: token weights on both sides.  Returns a (1,) tensor."""
-        return transfer.score_path_pairs_exemplar(self, [(image_A, image_B)], [mask_A], img_size, prompt, target_block, target_layer,
-                                                  target_step, seed, similarity, None, rel_threshold, soft, hip_vae=False)
-
-    @torch.no_grad()
-    def transferred_region(self, image_A, image_B, mask_A, img_size, prompt, target_block, target_layer, target_step, seed="2333",
-                           rel_threshold=1.0, soft=False):
-        """(mass (h, w) f32, region (h, w) bool -- soft: uint8 weights) on image_B's token grid: what :meth:`exemplar_region_score`
-        transfers from mask_A."""
-        return transfer.path_transferred_region(self, image_A, image_B, mask_A, img_size, prompt, target_block, target_layer,
-                                                target_step, seed, rel_threshold, soft, hip_vae=False)
-
-    @torch.no_grad()
-    def text_attention_map(self, image_A, image_B, img_size, prompt, target_block, target_layer, target_step, seed):
-        """The text attention maps of the two images of one :meth:`diffsim_score` call: (2, h, w, L) f32 on the tap's grid."""
-        latA, latB, nA, nB, ctx, pooled = self._path_pair_inputs(image_A, image_B, img_size, prompt, seed)
-        return textattn.text_attention_maps(self, torch.cat([latA, latB]), torch.cat([nA, nB]), (ctx, pooled), target_block,
-                                            target_layer, target_step)
 
     @torch.no_grad()
     def score_latent_pair_alignment(self, latA, latB, noiseA, noiseB, ctx, pooled, target_block, target_layer, target_step,

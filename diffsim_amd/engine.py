@@ -8,7 +8,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 import threading
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 
@@ -567,12 +567,32 @@ def _check_two_sets(fa, fb, heads: int):
     return (ts, *_check_features(ts, heads, ok, _SETS_MSGS))
 
 
-def _check_region_mask(mask: torch.Tensor, n: int, N: int, what: str = "the region mask", rows: str = "n_feat"):
-    """a region mask: bool or uint8, (n, N); `what` names it and `rows` its first extent in the messages"""
-    if mask.dtype not in (torch.bool, torch.uint8):
-        raise _lib.DsimError(f"{what} must be bool or uint8")
-    if tuple(mask.shape) != (n, N):
-        raise _lib.DsimError(f"{what} must be ({rows}, N) = ({n}, {N}): {tuple(mask.shape)}")
+class _TokenRows(NamedTuple):
+    """How the region tails read one byte per token and image: the two forms of every dsim_*_regions / dsim_*_weights entry pair."""
+    suffix: str                 # of the C entries and their workspace queries
+    noun: str                   # of the refusals: "no <noun> scores for ..."
+    matrix: str                 # ... and of the matrix form's
+    what: str                   # the rows in the messages of their own checks
+    arg: str                    # ... and the matrix forms' argument names, <arg>_a and <arg>_b
+    dtypes: tuple
+    dtype_rule: str
+
+
+_MASKS = _TokenRows("regions", "region", "region score matrix", "the region mask", "mask", (torch.bool, torch.uint8), "bool or uint8")
+_WEIGHTS = _TokenRows("weights", "soft region", "soft score matrix", "the token weights", "weights", (torch.uint8,), "uint8")
+
+
+def _token_rows(form: _TokenRows, rows: torch.Tensor, n: int, N: int, what: Optional[str] = None, extent: str = "n_feat"):
+    """The token rows of a region tail checked -- the form's dtypes, (n, N), contiguous: a strided row would be read as if dense --
+    and as the uint8 the library reads; `what` names them and `extent` their first extent in the messages."""
+    what = what or form.what
+    if rows.dtype not in form.dtypes:
+        raise _lib.DsimError(f"{what} must be {form.dtype_rule}")
+    if tuple(rows.shape) != (n, N):
+        raise _lib.DsimError(f"{what} must be ({extent}, N) = ({n}, {N}): {tuple(rows.shape)}")
+    if not rows.is_contiguous():
+        raise _lib.DsimError(f"{what} must be contiguous")
+    return rows.view(torch.uint8)
 
 
 def _with_extras(out, *extras):
@@ -643,25 +663,65 @@ def pair_score_proj(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, idx_a: to
     return (out, status) if return_status else out
 
 
+def _pair_checks(ts, idx_a, idx_b, heads: int, region=None, similarity: Optional[str] = None):
+    """What every per-token pair tail checks of its features ts = (q, k[, v]), its pair indices and its optional region, a
+    (_TokenRows, rows) pair: ((B, heads, N, D), the similarity's code, the region with its rows as uint8)."""
+    form, rows = region or (None, None)
+    if form is not None and not rows.is_contiguous():          # (ahead of the device requirement: it needs no device)
+        raise _lib.DsimError(f"{form.what} must be contiguous")
+    _require_cuda(*ts, rows, idx_a, idx_b)
+    sim = None if similarity is None else _similarity_code(similarity)
+    B, N, D = _check_features(ts, heads, all(t.shape == ts[0].shape for t in ts), _PAIR_MSGS, (idx_a, idx_b))
+    return (B, heads, N, D), sim, (region and (form, _token_rows(form, rows, ts[0].shape[0], N)))
+
+
+def _pair_call(name: str, refusal: str, ts, region, idx_a, idx_b, dims, *rest, extra=None):
+    """dsim_<name> over the pairs (idx_a, idx_b) of the features ts, or with a region dsim_<name>_<regions | weights>: the rows and
+    n_feat go behind the features and `extra` (the counts / sums, or None) behind `rest`.  refusal: "no ... maps" for the shape."""
+    B, H, N, D = dims
+    n, n_feat = idx_a.numel(), ts[0].shape[0]
+    shape = f"n_pairs={n} B={B} H={H} N={N} D={D}"
+    args = (idx_a.data_ptr(), idx_b.data_ptr(), n, *dims, _TORCH2DSIM[ts[0].dtype], *rest)
+    if region is None:
+        return _tail_call(ts[0].device, name, (n, *dims), f"{refusal} for {shape}", *(t.data_ptr() for t in ts), *args)
+    form, rows = region
+    _tail_call(ts[0].device, f"{name}_{form.suffix}", (n_feat, n, *dims), f"{refusal} for n_feat={n_feat} {shape}",
+               *(t.data_ptr() for t in ts), rows.data_ptr(), n_feat, *args, _ptr(extra))
+
+
+def _pair_scores(q, k, v, idx_a, idx_b, heads, similarity, return_status, region, return_extra):
+    """pair_score_regions and pair_score_weights: one score per pair over the region's rows"""
+    dims, sim, region = _pair_checks((q, k, v), idx_a, idx_b, heads, region, similarity)
+    n_pairs = idx_a.numel()
+    out = torch.empty(n_pairs, dtype=torch.float32, device=q.device)
+    status = _i32(n_pairs, q.device, return_status)
+    extra = _i32(q.shape[0], q.device, return_extra)
+    _pair_call("pair_score", f"no {region[0].noun} scores", (q, k, v), region, idx_a, idx_b, dims, sim, out.data_ptr(), _ptr(status),
+               extra=extra)
+    return _with_extras(out, status, extra)
+
+
+def _pair_maps(q, k, v, idx_a, idx_b, heads, similarity, return_status, region=None, return_extra=False):
+    """pair_score_maps and its two region forms: the score and its per-token terms on the full token grid"""
+    dims, sim, region = _pair_checks((q, k, v), idx_a, idx_b, heads, region, similarity)
+    n_pairs, N, dev = idx_a.numel(), dims[2], q.device
+    score = torch.empty(n_pairs, dtype=torch.float32, device=dev)
+    local = torch.empty((n_pairs, 2, N), dtype=torch.float32, device=dev)
+    contrib = torch.empty((n_pairs, 2, N), dtype=torch.float32, device=dev)
+    status = _i32(n_pairs, dev, return_status)
+    extra = _i32(q.shape[0], dev, return_extra)
+    _pair_call("pair_score_maps", f"no {region[0].noun} maps" if region else "no similarity maps", (q, k, v), region, idx_a, idx_b,
+               dims, sim, score.data_ptr(), local.data_ptr(), contrib.data_ptr(), _ptr(status), extra=extra)
+    return (score, local, contrib) + tuple(e for e in (status, extra) if e is not None)
+
+
 def pair_score_maps(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, idx_a: torch.Tensor, idx_b: torch.Tensor,
                     heads: int, similarity: str = "cosine", return_status: bool = False):
     """The score tail kept per query token (dsim_pair_score_maps).  q,k,v: [n_feat][B][N][H*D]; idx: int32 cuda [n_pairs].
     Returns f32 device tensors (score (n,), local (n, 2, N), contrib (n, 2, N)): direction 0 on image idx_a[p]'s tokens,
     direction 1 on idx_b[p]'s; local is a token's own cosine (or mean squared difference), contrib its term of the score:
     score = 0.5 * contrib.sum((1, 2)).  return_status: also an int32 (n,) tensor, 1 where the score is NaN / infinite."""
-    _require_cuda(q, k, v, idx_a, idx_b)
-    sim = _similarity_code(similarity)
-    B, N, D = _check_features((q, k, v), heads, k.shape == q.shape == v.shape, _PAIR_MSGS, (idx_a, idx_b))
-    n_pairs = idx_a.numel()
-    score = torch.empty(n_pairs, dtype=torch.float32, device=q.device)
-    local = torch.empty((n_pairs, 2, N), dtype=torch.float32, device=q.device)
-    contrib = torch.empty((n_pairs, 2, N), dtype=torch.float32, device=q.device)
-    status = _i32(n_pairs, q.device, return_status)
-    _tail_call(q.device, "pair_score_maps", (n_pairs, B, heads, N, D),
-               f"no similarity maps for n_pairs={n_pairs} B={B} H={heads} N={N} D={D}", q.data_ptr(), k.data_ptr(), v.data_ptr(),
-               idx_a.data_ptr(), idx_b.data_ptr(), n_pairs, B, heads, N, D, _TORCH2DSIM[q.dtype], sim, score.data_ptr(), local.data_ptr(),
-               contrib.data_ptr(), _ptr(status))
-    return (score, local, contrib, status) if return_status else (score, local, contrib)
+    return _pair_maps(q, k, v, idx_a, idx_b, heads, similarity, return_status)
 
 
 def pair_score_regions(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: torch.Tensor, idx_a: torch.Tensor,
@@ -672,20 +732,7 @@ def pair_score_regions(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: 
     score is pair_score's on the rows of the two regions alone (ascending token order): the off tokens are neither queries nor
     keys.  Returns the f32 (n,) scores; return_status: also an int32 (n,) tensor, 1 where the score is NaN / infinite, 2 where
     a region of the pair is empty (score NaN); return_counts: also the int32 (n_feat,) region sizes."""
-    _require_cuda(q, k, v, mask, idx_a, idx_b)
-    sim = _similarity_code(similarity)
-    B, N, D = _check_features((q, k, v), heads, k.shape == q.shape == v.shape, _PAIR_MSGS, (idx_a, idx_b))
-    _check_region_mask(mask, q.shape[0], N)
-    mask = mask.view(torch.uint8)
-    n_feat, n_pairs = q.shape[0], idx_a.numel()
-    out = torch.empty(n_pairs, dtype=torch.float32, device=q.device)
-    status = _i32(n_pairs, q.device, return_status)
-    counts = _i32(n_feat, q.device, return_counts)
-    _tail_call(q.device, "pair_score_regions", (n_feat, n_pairs, B, heads, N, D),
-               f"no region scores for n_feat={n_feat} n_pairs={n_pairs} B={B} H={heads} N={N} D={D}", q.data_ptr(), k.data_ptr(),
-               v.data_ptr(), mask.data_ptr(), n_feat, idx_a.data_ptr(), idx_b.data_ptr(), n_pairs, B, heads, N, D, _TORCH2DSIM[q.dtype],
-               sim, out.data_ptr(), _ptr(status), _ptr(counts))
-    return _with_extras(out, status, counts)
+    return _pair_scores(q, k, v, idx_a, idx_b, heads, similarity, return_status, (_MASKS, mask), return_counts)
 
 
 def pair_score_weights(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, weights_u8: torch.Tensor, idx_a: torch.Tensor,
@@ -697,23 +744,7 @@ def pair_score_weights(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, weight
     of weight w counts w times in the cosine / mse sums.  With every byte 0 or 255 it is pair_score_regions on `weights_u8 != 0`, bit
     for bit.  Returns the f32 (n,) scores; return_status: also an int32 (n,) tensor, 1 where the score is NaN / infinite, 2 where
     an image of the pair has no weight at all (score NaN); return_sums: also the int32 (n_feat,) byte sums."""
-    _require_cuda(q, k, v, weights_u8, idx_a, idx_b)
-    sim = _similarity_code(similarity)
-    B, N, D = _check_features((q, k, v), heads, k.shape == q.shape == v.shape, _PAIR_MSGS, (idx_a, idx_b))
-    if weights_u8.dtype != torch.uint8:
-        raise _lib.DsimError("the token weights must be uint8")
-    _check_region_mask(weights_u8, q.shape[0], N, "the token weights")
-    if not weights_u8.is_contiguous():
-        raise _lib.DsimError("the token weights must be contiguous")
-    n_feat, n_pairs = q.shape[0], idx_a.numel()
-    out = torch.empty(n_pairs, dtype=torch.float32, device=q.device)
-    status = _i32(n_pairs, q.device, return_status)
-    sums = _i32(n_feat, q.device, return_sums)
-    _tail_call(q.device, "pair_score_weights", (n_feat, n_pairs, B, heads, N, D),
-               f"no soft region scores for n_feat={n_feat} n_pairs={n_pairs} B={B} H={heads} N={N} D={D}", q.data_ptr(), k.data_ptr(),
-               v.data_ptr(), weights_u8.data_ptr(), n_feat, idx_a.data_ptr(), idx_b.data_ptr(), n_pairs, B, heads, N, D,
-               _TORCH2DSIM[q.dtype], sim, out.data_ptr(), _ptr(status), _ptr(sums))
-    return _with_extras(out, status, sums)
+    return _pair_scores(q, k, v, idx_a, idx_b, heads, similarity, return_status, (_WEIGHTS, weights_u8), return_sums)
 
 
 def pair_score_maps_regions(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: torch.Tensor, idx_a: torch.Tensor,
@@ -725,23 +756,20 @@ def pair_score_maps_regions(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, m
     its term of the region score, score = 0.5 * contrib.sum((1, 2)); at an off token both are exactly 0.  return_status: also an
     int32 (n,) tensor, 1 where the score is NaN / infinite, 2 where a region of the pair is empty (score NaN, maps zero);
     return_counts: also the int32 (n_feat,) region sizes."""
-    _require_cuda(q, k, v, mask, idx_a, idx_b)
-    sim = _similarity_code(similarity)
-    B, N, D = _check_features((q, k, v), heads, k.shape == q.shape == v.shape, _PAIR_MSGS, (idx_a, idx_b))
-    _check_region_mask(mask, q.shape[0], N)
-    mask = mask.view(torch.uint8)
-    n_feat, n_pairs = q.shape[0], idx_a.numel()
-    dev = q.device
-    score = torch.empty(n_pairs, dtype=torch.float32, device=dev)
-    local = torch.empty((n_pairs, 2, N), dtype=torch.float32, device=dev)
-    contrib = torch.empty((n_pairs, 2, N), dtype=torch.float32, device=dev)
-    status = _i32(n_pairs, dev, return_status)
-    counts = _i32(n_feat, dev, return_counts)
-    _tail_call(dev, "pair_score_maps_regions", (n_feat, n_pairs, B, heads, N, D),
-               f"no region maps for n_feat={n_feat} n_pairs={n_pairs} B={B} H={heads} N={N} D={D}", q.data_ptr(), k.data_ptr(),
-               v.data_ptr(), mask.data_ptr(), n_feat, idx_a.data_ptr(), idx_b.data_ptr(), n_pairs, B, heads, N, D, _TORCH2DSIM[q.dtype],
-               sim, score.data_ptr(), local.data_ptr(), contrib.data_ptr(), _ptr(status), _ptr(counts))
-    return (score, local, contrib) + tuple(e for e in (status, counts) if e is not None)
+    return _pair_maps(q, k, v, idx_a, idx_b, heads, similarity, return_status, (_MASKS, mask), return_counts)
+
+
+def pair_score_maps_weights(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, weights_u8: torch.Tensor, idx_a: torch.Tensor,
+                            idx_b: torch.Tensor, heads: int, similarity: str = "cosine", return_status: bool = False,
+                            return_sums: bool = False):
+    """The soft region score kept per query token (dsim_pair_score_maps_weights): pair_score_maps_regions for pair_score_weights.
+    q,k,v, weights_u8, idx: as pair_score_weights.  Returns f32 device tensors (score (n,), local (n, 2, N), contrib (n, 2, N)) on the
+    full token grid: at a token of weight > 0, local is the token's own cosine (or mean squared difference) inside the biased
+    attentions, not weighted by its own weight, and contrib its weighted term of the soft score, score = 0.5 * contrib.sum((1, 2));
+    at a token of weight 0 both are exactly 0.  With every byte 0 or 255 the outputs are pair_score_maps_regions' bits.
+    return_status: also an int32 (n,) tensor, 1 where the score is NaN / infinite, 2 where an image of the pair has no weight
+    (score NaN, maps zero); return_sums: also the int32 (n_feat,) byte sums."""
+    return _pair_maps(q, k, v, idx_a, idx_b, heads, similarity, return_status, (_WEIGHTS, weights_u8), return_sums)
 
 
 TEXT_WANT = ("attn", "saliency", "mask", "counts", "status")
@@ -802,6 +830,44 @@ _ATTN_BYTES = (1 << 31) - 1          # dsim_pair_align refuses an attention tens
 _ALIGN_PAIRS = 32767                 # ... and more pairs than its grid holds (two directions per pair, 65535 in all)
 
 
+def _align_chunks(n_pairs: int, N: int, with_attention: bool = False):
+    """The slices of n_pairs pairs that one alignment or transfer launch takes: at most _ALIGN_PAIRS, and with the (2, N, N) f32
+    attention of every pair written out, fewer than 2 GiB of it."""
+    step = _ALIGN_PAIRS
+    if with_attention:
+        step = min(step, _ATTN_BYTES // (2 * N * N * 4))
+        if step < 1:
+            raise _lib.DsimError(f"the attention of one pair of {N} tokens does not fit 2 GiB")
+    return [slice(i0, min(n_pairs, i0 + step)) for i0 in range(0, n_pairs, step)]
+
+
+def _at(t: Optional[torch.Tensor], sl: slice) -> Optional[int]:
+    return None if t is None else t[sl].data_ptr()
+
+
+def _pair_align(q, k, idx_a, idx_b, heads, grid_w, return_attention, return_status, region=None, return_extra=False):
+    """pair_align and its two region forms"""
+    dims, _, region = _pair_checks((q, k), idx_a, idx_b, heads, region)
+    N = dims[2]
+    if grid_w is None:
+        grid_w = math.isqrt(N)
+        if grid_w * grid_w != N:
+            raise _lib.DsimError(f"{N} tokens do not form a square grid: name grid_w")
+    n_pairs, dev = idx_a.numel(), q.device
+    match = torch.empty((n_pairs, 2, N), dtype=torch.int32, device=dev)
+    weight = torch.empty((n_pairs, 2, N), dtype=torch.float32, device=dev)
+    expect = torch.empty((n_pairs, 2, N, 2), dtype=torch.float32, device=dev)
+    status = _i32(n_pairs, dev, return_status)
+    extra = _i32(q.shape[0], dev, return_extra)
+    chunks = _align_chunks(n_pairs, N, return_attention)
+    attn = torch.empty((n_pairs, 2, N, N), dtype=torch.float32, device=dev) if return_attention else None
+    for sl in chunks:
+        _pair_call("pair_align", f"no {region[0].noun} alignments" if region else "no token alignments", (q, k), region, idx_a[sl],
+                   idx_b[sl], dims, int(grid_w), match[sl].data_ptr(), weight[sl].data_ptr(), expect[sl].data_ptr(), _at(attn, sl),
+                   _at(status, sl), extra=extra)
+    return (match, weight, expect) + tuple(e for e in (attn, status, extra) if e is not None)
+
+
 def pair_align(q: torch.Tensor, k: torch.Tensor, idx_a: torch.Tensor, idx_b: torch.Tensor, heads: int,
                grid_w: Optional[int] = None, return_attention: bool = False, return_status: bool = False):
     """Token alignments (dsim_pair_align): the cross-attention the score is built on, softmax(Q_a K_b^T / sqrt(D)) averaged over
@@ -811,33 +877,7 @@ def pair_align(q: torch.Tensor, k: torch.Tensor, idx_a: torch.Tensor, idx_b: tor
     probability, and the soft-argmax (row, col) on the other image's grid, token j at (j // grid_w, j % grid_w).  grid_w None:
     the square grid of N tokens.  return_attention: also the probabilities, f32 (n, 2, N, N), computed in calls of fewer than
     2 GiB each; return_status: also an int32 (n,) tensor, 1 where a pair has a non-finite probability."""
-    _require_cuda(q, k, idx_a, idx_b)
-    B, N, D = _check_features((q, k), heads, k.shape == q.shape, _PAIR_MSGS, (idx_a, idx_b))
-    if grid_w is None:
-        grid_w = math.isqrt(N)
-        if grid_w * grid_w != N:
-            raise _lib.DsimError(f"{N} tokens do not form a square grid: name grid_w")
-    n_pairs = idx_a.numel()
-    dev = q.device
-    match = torch.empty((n_pairs, 2, N), dtype=torch.int32, device=dev)
-    weight = torch.empty((n_pairs, 2, N), dtype=torch.float32, device=dev)
-    expect = torch.empty((n_pairs, 2, N, 2), dtype=torch.float32, device=dev)
-    status = _i32(n_pairs, dev, return_status)
-    attn = None
-    step = _ALIGN_PAIRS
-    if return_attention:
-        step = min(step, _ATTN_BYTES // (2 * N * N * 4))
-        if step < 1:
-            raise _lib.DsimError(f"the attention of one pair of {N} tokens does not fit 2 GiB")
-        attn = torch.empty((n_pairs, 2, N, N), dtype=torch.float32, device=dev)
-    for i0 in range(0, n_pairs, step):
-        n = min(step, n_pairs - i0)
-        sl = slice(i0, i0 + n)
-        _tail_call(dev, "pair_align", (n, B, heads, N, D), f"no token alignments for n_pairs={n} B={B} H={heads} N={N} D={D}",
-                   q.data_ptr(), k.data_ptr(), idx_a[sl].data_ptr(), idx_b[sl].data_ptr(), n, B, heads, N, D, _TORCH2DSIM[q.dtype],
-                   int(grid_w), match[sl].data_ptr(), weight[sl].data_ptr(), expect[sl].data_ptr(),
-                   _ptr(None if attn is None else attn[sl]), _ptr(None if status is None else status[sl]))
-    return (match, weight, expect) + ((attn,) if return_attention else ()) + ((status,) if return_status else ())
+    return _pair_align(q, k, idx_a, idx_b, heads, grid_w, return_attention, return_status)
 
 
 def pair_align_regions(q: torch.Tensor, k: torch.Tensor, mask: torch.Tensor, idx_a: torch.Tensor, idx_b: torch.Tensor, heads: int,
@@ -850,74 +890,7 @@ def pair_align_regions(q: torch.Tensor, k: torch.Tensor, mask: torch.Tensor, idx
     return_attention: also the probabilities, f32 (n, 2, N, N), zero outside R_a x R_b, computed in calls of fewer than 2 GiB
     each; return_status: also an int32 (n,) tensor, 1 where a pair has a non-finite probability, 2 where a region of the pair is
     empty (every row then carries the off values); return_counts: also the int32 (n_feat,) region sizes."""
-    _require_cuda(q, k, mask, idx_a, idx_b)
-    B, N, D = _check_features((q, k), heads, k.shape == q.shape, _PAIR_MSGS, (idx_a, idx_b))
-    _check_region_mask(mask, q.shape[0], N)
-    mask = mask.view(torch.uint8)
-    if grid_w is None:
-        grid_w = math.isqrt(N)
-        if grid_w * grid_w != N:
-            raise _lib.DsimError(f"{N} tokens do not form a square grid: name grid_w")
-    n_feat, n_pairs = q.shape[0], idx_a.numel()
-    dev = q.device
-    match = torch.empty((n_pairs, 2, N), dtype=torch.int32, device=dev)
-    weight = torch.empty((n_pairs, 2, N), dtype=torch.float32, device=dev)
-    expect = torch.empty((n_pairs, 2, N, 2), dtype=torch.float32, device=dev)
-    status = _i32(n_pairs, dev, return_status)
-    counts = _i32(n_feat, dev, return_counts)
-    attn = None
-    step = _ALIGN_PAIRS
-    if return_attention:
-        step = min(step, _ATTN_BYTES // (2 * N * N * 4))
-        if step < 1:
-            raise _lib.DsimError(f"the attention of one pair of {N} tokens does not fit 2 GiB")
-        attn = torch.empty((n_pairs, 2, N, N), dtype=torch.float32, device=dev)
-    for i0 in range(0, n_pairs, step):
-        n = min(step, n_pairs - i0)
-        sl = slice(i0, i0 + n)
-        _tail_call(dev, "pair_align_regions", (n_feat, n, B, heads, N, D),
-                   f"no region alignments for n_feat={n_feat} n_pairs={n} B={B} H={heads} N={N} D={D}", q.data_ptr(), k.data_ptr(),
-                   mask.data_ptr(), n_feat, idx_a[sl].data_ptr(), idx_b[sl].data_ptr(), n, B, heads, N, D, _TORCH2DSIM[q.dtype],
-                   int(grid_w), match[sl].data_ptr(), weight[sl].data_ptr(), expect[sl].data_ptr(),
-                   _ptr(None if attn is None else attn[sl]), _ptr(None if status is None else status[sl]), _ptr(counts))
-    return (match, weight, expect) + tuple(e for e in (attn, status, counts) if e is not None)
-
-
-def _check_token_weights(weights_u8: torch.Tensor, n_feat: int, N: int):
-    """pair_score_weights' checks of its weights: uint8 only, (n_feat, N), contiguous"""
-    if weights_u8.dtype != torch.uint8:
-        raise _lib.DsimError("the token weights must be uint8")
-    _check_region_mask(weights_u8, n_feat, N, "the token weights")
-    if not weights_u8.is_contiguous():
-        raise _lib.DsimError("the token weights must be contiguous")
-
-
-def pair_score_maps_weights(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, weights_u8: torch.Tensor, idx_a: torch.Tensor,
-                            idx_b: torch.Tensor, heads: int, similarity: str = "cosine", return_status: bool = False,
-                            return_sums: bool = False):
-    """The soft region score kept per query token (dsim_pair_score_maps_weights): pair_score_maps_regions for pair_score_weights.
-    q,k,v, weights_u8, idx: as pair_score_weights.  Returns f32 device tensors (score (n,), local (n, 2, N), contrib (n, 2, N)) on the
-    full token grid: at a token of weight > 0, local is the token's own cosine (or mean squared difference) inside the biased
-    attentions, not weighted by its own weight, and contrib its weighted term of the soft score, score = 0.5 * contrib.sum((1, 2));
-    at a token of weight 0 both are exactly 0.  With every byte 0 or 255 the outputs are pair_score_maps_regions' bits.
-    return_status: also an int32 (n,) tensor, 1 where the score is NaN / infinite, 2 where an image of the pair has no weight
-    (score NaN, maps zero); return_sums: also the int32 (n_feat,) byte sums."""
-    _require_cuda(q, k, v, weights_u8, idx_a, idx_b)
-    sim = _similarity_code(similarity)
-    B, N, D = _check_features((q, k, v), heads, k.shape == q.shape == v.shape, _PAIR_MSGS, (idx_a, idx_b))
-    _check_token_weights(weights_u8, q.shape[0], N)
-    n_feat, n_pairs = q.shape[0], idx_a.numel()
-    dev = q.device
-    score = torch.empty(n_pairs, dtype=torch.float32, device=dev)
-    local = torch.empty((n_pairs, 2, N), dtype=torch.float32, device=dev)
-    contrib = torch.empty((n_pairs, 2, N), dtype=torch.float32, device=dev)
-    status = _i32(n_pairs, dev, return_status)
-    sums = _i32(n_feat, dev, return_sums)
-    _tail_call(dev, "pair_score_maps_weights", (n_feat, n_pairs, B, heads, N, D),
-               f"no soft region maps for n_feat={n_feat} n_pairs={n_pairs} B={B} H={heads} N={N} D={D}", q.data_ptr(), k.data_ptr(),
-               v.data_ptr(), weights_u8.data_ptr(), n_feat, idx_a.data_ptr(), idx_b.data_ptr(), n_pairs, B, heads, N, D, _TORCH2DSIM[q.dtype],
-               sim, score.data_ptr(), local.data_ptr(), contrib.data_ptr(), _ptr(status), _ptr(sums))
-    return (score, local, contrib) + tuple(e for e in (status, sums) if e is not None)
+    return _pair_align(q, k, idx_a, idx_b, heads, grid_w, return_attention, return_status, (_MASKS, mask), return_counts)
 
 
 def pair_align_weights(q: torch.Tensor, k: torch.Tensor, weights_u8: torch.Tensor, idx_a: torch.Tensor, idx_b: torch.Tensor, heads: int,
@@ -930,36 +903,7 @@ def pair_align_weights(q: torch.Tensor, k: torch.Tensor, weights_u8: torch.Tenso
     (n, 2, N, N), zero at rows and columns of weight 0, in calls of fewer than 2 GiB each; return_status: also an int32 (n,) tensor, 1
     where a pair has a non-finite probability, 2 where an image of the pair has no weight; return_sums: also the int32 (n_feat,) byte
     sums.  With every byte 0 or 255 the outputs are pair_align_regions' bits."""
-    _require_cuda(q, k, weights_u8, idx_a, idx_b)
-    B, N, D = _check_features((q, k), heads, k.shape == q.shape, _PAIR_MSGS, (idx_a, idx_b))
-    _check_token_weights(weights_u8, q.shape[0], N)
-    if grid_w is None:
-        grid_w = math.isqrt(N)
-        if grid_w * grid_w != N:
-            raise _lib.DsimError(f"{N} tokens do not form a square grid: name grid_w")
-    n_feat, n_pairs = q.shape[0], idx_a.numel()
-    dev = q.device
-    match = torch.empty((n_pairs, 2, N), dtype=torch.int32, device=dev)
-    weight = torch.empty((n_pairs, 2, N), dtype=torch.float32, device=dev)
-    expect = torch.empty((n_pairs, 2, N, 2), dtype=torch.float32, device=dev)
-    status = _i32(n_pairs, dev, return_status)
-    sums = _i32(n_feat, dev, return_sums)
-    attn = None
-    step = _ALIGN_PAIRS
-    if return_attention:
-        step = min(step, _ATTN_BYTES // (2 * N * N * 4))
-        if step < 1:
-            raise _lib.DsimError(f"the attention of one pair of {N} tokens does not fit 2 GiB")
-        attn = torch.empty((n_pairs, 2, N, N), dtype=torch.float32, device=dev)
-    for i0 in range(0, n_pairs, step):
-        n = min(step, n_pairs - i0)
-        sl = slice(i0, i0 + n)
-        _tail_call(dev, "pair_align_weights", (n_feat, n, B, heads, N, D),
-                   f"no soft region alignments for n_feat={n_feat} n_pairs={n} B={B} H={heads} N={N} D={D}", q.data_ptr(), k.data_ptr(),
-                   weights_u8.data_ptr(), n_feat, idx_a[sl].data_ptr(), idx_b[sl].data_ptr(), n, B, heads, N, D, _TORCH2DSIM[q.dtype],
-                   int(grid_w), match[sl].data_ptr(), weight[sl].data_ptr(), expect[sl].data_ptr(),
-                   _ptr(None if attn is None else attn[sl]), _ptr(None if status is None else status[sl]), _ptr(sums))
-    return (match, weight, expect) + tuple(e for e in (attn, status, sums) if e is not None)
+    return _pair_align(q, k, idx_a, idx_b, heads, grid_w, return_attention, return_status, (_WEIGHTS, weights_u8), return_sums)
 
 
 def pair_region_transfer(q: torch.Tensor, k: torch.Tensor, weights_u8: torch.Tensor, idx_a: torch.Tensor, idx_b: torch.Tensor, heads: int,
@@ -971,20 +915,19 @@ def pair_region_transfer(q: torch.Tensor, k: torch.Tensor, weights_u8: torch.Ten
     asked for hold NaN.  return_status: also an int32 (n,) tensor, 1 where a pair has a non-finite probability."""
     _require_cuda(q, k, weights_u8, idx_a, idx_b)
     B, N, D = _check_features((q, k), heads, k.shape == q.shape, _PAIR_MSGS, (idx_a, idx_b))
-    _check_token_weights(weights_u8, q.shape[0], N)
+    _token_rows(_WEIGHTS, weights_u8, q.shape[0], N)
     if directions not in (1, 2, 3):
         raise ValueError(f"directions must be 1, 2 or 3: {directions!r}")
     n_feat, n_pairs = q.shape[0], idx_a.numel()
     dev = q.device
     mass = torch.full((n_pairs, 2, N), float("nan"), dtype=torch.float32, device=dev)
     status = _i32(n_pairs, dev, return_status)
-    for i0 in range(0, n_pairs, _ALIGN_PAIRS):
-        n = min(_ALIGN_PAIRS, n_pairs - i0)
-        sl = slice(i0, i0 + n)
+    for sl in _align_chunks(n_pairs, N):
+        n = sl.stop - sl.start
         _tail_call(dev, "pair_region_transfer", (n_feat, n, B, heads, N, D),
                    f"no region transfer for n_feat={n_feat} n_pairs={n} B={B} H={heads} N={N} D={D}", q.data_ptr(), k.data_ptr(),
                    weights_u8.data_ptr(), n_feat, idx_a[sl].data_ptr(), idx_b[sl].data_ptr(), n, B, heads, N, D, _TORCH2DSIM[q.dtype],
-                   int(directions), mass[sl].data_ptr(), _ptr(None if status is None else status[sl]))
+                   int(directions), mass[sl].data_ptr(), _at(status, sl))
     return (mass, status) if return_status else mass
 
 
@@ -992,25 +935,43 @@ def score_matrix_workspace_bytes(n_a: int, n_b: int, B: int, heads: int, N: int,
     return int(_lib.lib().dsim_score_matrix_workspace_bytes(n_a, n_b, B, heads, N, D, _TORCH2DSIM[dtype]))
 
 
+def score_matrix_regions_workspace_bytes(n_a: int, n_b: int, B: int, heads: int, N: int, D: int, dtype: torch.dtype) -> int:
+    return int(_lib.lib().dsim_score_matrix_regions_workspace_bytes(n_a, n_b, B, heads, N, D, _TORCH2DSIM[dtype]))
+
+
+def score_matrix_weights_workspace_bytes(n_a: int, n_b: int, B: int, heads: int, N: int, D: int, dtype: torch.dtype) -> int:
+    return int(_lib.lib().dsim_score_matrix_weights_workspace_bytes(n_a, n_b, B, heads, N, D, _TORCH2DSIM.get(dtype, -1)))
+
+
+def _score_matrix(fa, fb, heads, similarity, return_status, region=None, return_extra=False):
+    """score_matrix and its two region forms; region: (_TokenRows, set A's rows, set B's rows)"""
+    sim = _similarity_code(similarity)
+    if region is None:
+        _require_cuda(*fa, *fb)
+    (qa, ka, va, qb, kb, vb), B, N, D = _check_two_sets(fa, fb, heads)
+    n_a, n_b, dev, dt = qa.shape[0], qb.shape[0], qa.device, _TORCH2DSIM[qa.dtype]
+    name, noun, rows_a, rows_b = "score_matrix", "score matrix", (), ()
+    if region is not None:
+        form, rows_a, rows_b = region
+        rows_a = _token_rows(form, rows_a, n_a, N, f"{form.what} {form.arg}_a", "n")
+        rows_b = _token_rows(form, rows_b, n_b, N, f"{form.what} {form.arg}_b", "n")
+        _require_cuda(qa, ka, va, qb, kb, vb, rows_a, rows_b)          # (after the shape checks: those need no device)
+        name, noun, rows_a, rows_b = f"score_matrix_{form.suffix}", form.matrix, (rows_a.data_ptr(),), (rows_b.data_ptr(),)
+    out = torch.empty((n_a, n_b), dtype=torch.float32, device=dev)
+    status = _i32((n_a, n_b), dev, return_status)
+    extra = _i32(n_a + n_b, dev, return_extra)
+    _tail_call(dev, name, (n_a, n_b, B, heads, N, D, dt), f"no {noun} for n_a={n_a} n_b={n_b} B={B} H={heads} N={N} D={D}", qa.data_ptr(),
+               ka.data_ptr(), va.data_ptr(), *rows_a, n_a, qb.data_ptr(), kb.data_ptr(), vb.data_ptr(), *rows_b, n_b, B, heads, N, D, dt,
+               sim, out.data_ptr(), _ptr(status), *(() if region is None else (_ptr(extra),)))
+    return _with_extras(out, status, extra)
+
+
 def score_matrix(fa, fb, heads: int, similarity: str = "cosine", return_status: bool = False):
     """Every image of set A against every image of set B (dsim_score_matrix).  fa, fb: (q, k, v) tuples of [n][B][N][H*D]
     device tensors of one dtype.  Returns the (n_a, n_b) f32 device tensor whose cell (i, j) is pair_score of (fa[i], fb[j]);
     each image's self-attention is computed once.  return_status: also an int32 (n_a, n_b) tensor, 1 where the score is
     NaN / infinite."""
-    sim = _similarity_code(similarity)
-    _require_cuda(*fa, *fb)
-    (qa, ka, va, qb, kb, vb), B, N, D = _check_two_sets(fa, fb, heads)
-    n_a, n_b = qa.shape[0], qb.shape[0]
-    out = torch.empty((n_a, n_b), dtype=torch.float32, device=qa.device)
-    status = _i32((n_a, n_b), qa.device, return_status)
-    _tail_call(qa.device, "score_matrix", (n_a, n_b, B, heads, N, D, _TORCH2DSIM[qa.dtype]),
-               f"no score matrix for n_a={n_a} n_b={n_b} B={B} H={heads} N={N} D={D}", qa.data_ptr(), ka.data_ptr(), va.data_ptr(), n_a,
-               qb.data_ptr(), kb.data_ptr(), vb.data_ptr(), n_b, B, heads, N, D, _TORCH2DSIM[qa.dtype], sim, out.data_ptr(), _ptr(status))
-    return _with_extras(out, status)
-
-
-def score_matrix_regions_workspace_bytes(n_a: int, n_b: int, B: int, heads: int, N: int, D: int, dtype: torch.dtype) -> int:
-    return int(_lib.lib().dsim_score_matrix_regions_workspace_bytes(n_a, n_b, B, heads, N, D, _TORCH2DSIM[dtype]))
+    return _score_matrix(fa, fb, heads, similarity, return_status)
 
 
 def score_matrix_regions(fa, fb, mask_a: torch.Tensor, mask_b: torch.Tensor, heads: int, similarity: str = "cosine",
@@ -1021,25 +982,7 @@ def score_matrix_regions(fa, fb, mask_a: torch.Tensor, mask_b: torch.Tensor, hea
     (fa[i] over mask_a[i], fb[j] over mask_b[j]); each image's self-attention over its region is computed once.  return_status:
     also an int32 (n_a, n_b) tensor, 1 where the score is NaN / infinite, 2 where a region of the cell is empty (score NaN);
     return_counts: also the int32 (n_a + n_b,) region sizes, set A's then set B's."""
-    sim = _similarity_code(similarity)
-    (qa, ka, va, qb, kb, vb), B, N, D = _check_two_sets(fa, fb, heads)
-    n_a, n_b = qa.shape[0], qb.shape[0]
-    _check_region_mask(mask_a, n_a, N, "the region mask mask_a", "n")
-    _check_region_mask(mask_b, n_b, N, "the region mask mask_b", "n")
-    _require_cuda(qa, ka, va, qb, kb, vb, mask_a, mask_b)          # (after the shape checks: those need no device)
-    mask_a, mask_b = mask_a.view(torch.uint8), mask_b.view(torch.uint8)
-    out = torch.empty((n_a, n_b), dtype=torch.float32, device=qa.device)
-    status = _i32((n_a, n_b), qa.device, return_status)
-    counts = _i32(n_a + n_b, qa.device, return_counts)
-    _tail_call(qa.device, "score_matrix_regions", (n_a, n_b, B, heads, N, D, _TORCH2DSIM[qa.dtype]),
-               f"no region score matrix for n_a={n_a} n_b={n_b} B={B} H={heads} N={N} D={D}", qa.data_ptr(), ka.data_ptr(), va.data_ptr(),
-               mask_a.data_ptr(), n_a, qb.data_ptr(), kb.data_ptr(), vb.data_ptr(), mask_b.data_ptr(), n_b, B, heads, N, D,
-               _TORCH2DSIM[qa.dtype], sim, out.data_ptr(), _ptr(status), _ptr(counts))
-    return _with_extras(out, status, counts)
-
-
-def score_matrix_weights_workspace_bytes(n_a: int, n_b: int, B: int, heads: int, N: int, D: int, dtype: torch.dtype) -> int:
-    return int(_lib.lib().dsim_score_matrix_weights_workspace_bytes(n_a, n_b, B, heads, N, D, _TORCH2DSIM.get(dtype, -1)))
+    return _score_matrix(fa, fb, heads, similarity, return_status, (_MASKS, mask_a, mask_b), return_counts)
 
 
 def score_matrix_weights(fa, fb, weights_a: torch.Tensor, weights_b: torch.Tensor, heads: int, similarity: str = "cosine",
@@ -1050,24 +993,7 @@ def score_matrix_weights(fa, fb, weights_a: torch.Tensor, weights_b: torch.Tenso
     weights_a[i], fb[j] under weights_b[j]), bit for bit; each image's self-attention is computed once.  return_status: also an
     int32 (n_a, n_b) tensor, 1 where the score is NaN / infinite, 2 where an image of the cell has no weight at all (score NaN);
     return_sums: also the int32 (n_a + n_b,) byte sums, set A's then set B's."""
-    sim = _similarity_code(similarity)
-    (qa, ka, va, qb, kb, vb), B, N, D = _check_two_sets(fa, fb, heads)
-    n_a, n_b = qa.shape[0], qb.shape[0]
-    for w, n, name in ((weights_a, n_a, "weights_a"), (weights_b, n_b, "weights_b")):
-        if w.dtype != torch.uint8:
-            raise _lib.DsimError(f"the token weights {name} must be uint8")
-        _check_region_mask(w, n, N, f"the token weights {name}", "n")
-        if not w.is_contiguous():
-            raise _lib.DsimError(f"the token weights {name} must be contiguous")
-    _require_cuda(qa, ka, va, qb, kb, vb, weights_a, weights_b)          # (after the shape checks: those need no device)
-    out = torch.empty((n_a, n_b), dtype=torch.float32, device=qa.device)
-    status = _i32((n_a, n_b), qa.device, return_status)
-    sums = _i32(n_a + n_b, qa.device, return_sums)
-    _tail_call(qa.device, "score_matrix_weights", (n_a, n_b, B, heads, N, D, _TORCH2DSIM[qa.dtype]),
-               f"no soft score matrix for n_a={n_a} n_b={n_b} B={B} H={heads} N={N} D={D}", qa.data_ptr(), ka.data_ptr(), va.data_ptr(),
-               weights_a.data_ptr(), n_a, qb.data_ptr(), kb.data_ptr(), vb.data_ptr(), weights_b.data_ptr(), n_b, B, heads, N, D,
-               _TORCH2DSIM[qa.dtype], sim, out.data_ptr(), _ptr(status), _ptr(sums))
-    return _with_extras(out, status, sums)
+    return _score_matrix(fa, fb, heads, similarity, return_status, (_WEIGHTS, weights_a, weights_b), return_sums)
 
 
 # ---- feature-cosine metrics (diffeats, dinofeats): the tapped self-attention's own output, its pair cosine and Gram matrix -------

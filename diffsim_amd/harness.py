@@ -21,9 +21,10 @@ from typing import List, Optional, Sequence, Tuple
 
 import torch
 
-from .engine import pair_score, pair_score_regions, pair_score_weights
+from .engine import pair_score, pair_score_regions, pair_score_weights      # noqa: F401  (RegionKind.tail)
 from .inputs import path_latents
 from .parallel import gather_scores, shard_triplets
+from .regions import kind_of, tap_grid
 from .scorer import stack_rows
 
 
@@ -106,8 +107,8 @@ def triplet_chunks(scorer, ref, left, right, nA, nB, prompt, heads, similarity, 
                     rows = torch.stack([mk[i0:i1] for mk in masks], dim=1).reshape(3 * m, -1).contiguous()
                     if exemplar is not None:
                         rows = exemplar.regions(q, k, heads[t], rows, ia, ib).contiguous()
-                region_tail = pair_score_weights if soft or (text is not None and getattr(text[0], "soft", False)) else pair_score_regions
-                s, st = region_tail(q, k, v, rows, ia, ib, heads[t], similarity, return_status=True)
+                kind = kind_of(soft or (text is not None and getattr(text[0], "soft", False)))
+                s, st = kind.tail("score", globals())(q, k, v, rows, ia, ib, heads[t], similarity, return_status=True)
                 st = (st != 0).to(torch.int32)
             bad[t] += st.sum()
             s_l[t, i0:i1], s_r[t, i0:i1] = s[:m], s[m:]
@@ -133,10 +134,8 @@ def _score_chunks(scorer, ref, left, right, nA, nB, prompt, block, layer, step, 
             raise ValueError("a text-guided region and a mask file per image: one or the other")
         text = (text, text.bind(scorer, prompt, n))
     if masks is not None:
-        from .regions import as_token_mask, as_token_weights, tap_grid
         grid = tap_grid(scorer, tap, ref.shape[-1])
-        on_grid = as_token_weights if soft else as_token_mask
-        masks = [torch.stack([on_grid(mk[c], grid) for mk in masks]).flatten(1).to(scorer.device) for c in range(3)]
+        masks = [torch.stack([kind_of(soft).on_grid(mk[c], grid) for mk in masks]).flatten(1).to(scorer.device) for c in range(3)]
     ex = {} if exemplar is None else {"exemplar": exemplar}
     prompt = scorer.bind_prompt(prompt, n)
     eng = scorer.engine_at(tap)

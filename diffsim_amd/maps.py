@@ -15,24 +15,16 @@ maps then carry the masks.
 """
 from __future__ import annotations
 
-import math
 import os
 from typing import Optional, Sequence, Tuple
 
 import torch
 import torch.nn.functional as F
 
-from .engine import pair_score_maps, pair_score_maps_regions, pair_score_maps_weights
+from .engine import pair_score_maps, pair_score_maps_regions, pair_score_maps_weights      # noqa: F401  (RegionKind.tail)
 from .inputs import path_latents
+from .regions import chunk_tails, grid_shape, kind_of, path_rows, tap_grid        # noqa: F401  (grid_shape: imported from here too)
 from .retrieval import ranking_names
-
-
-def grid_shape(n_tokens: int) -> Tuple[int, int]:
-    """(h, w) of a square token grid; a non-square token count is refused."""
-    s = math.isqrt(int(n_tokens))
-    if n_tokens < 1 or s * s != n_tokens:
-        raise ValueError(f"{n_tokens} tokens do not form a square grid: maps need an h x w = s x s token grid")
-    return s, s
 
 
 class SimilarityMaps:
@@ -89,25 +81,15 @@ def score_latent_pair_maps(scorer, latA, latB, noiseA, noiseB, prompt, target_bl
     region maps (``engine.pair_score_maps_weights``); the score is the soft region score and the maps carry the weights."""
     dev = scorer.device
     n = latA.shape[0]
-    tail, tail_of, both, wts = pair_score_maps, None, None, None
-    if soft:
-        from .regions import pair_token_weights
-        if maskA is None and maskB is None:
-            raise ValueError("soft=True weighs masks: give maskA and / or maskB")
-        _grid, wts = pair_token_weights(scorer, scorer.tap_of(target_block, target_layer), latA.shape[-1], n, maskA, maskB)
-
-        def tail_of(i0, i1):
-            chunk = wts[i0:i1].reshape(2 * (i1 - i0), -1).contiguous()
-            return lambda q, k, v, ia, ib, heads, sim: pair_score_maps_weights(q, k, v, chunk, ia, ib, heads, sim)
-        tail = None
-    elif maskA is not None or maskB is not None:
-        from .regions import pair_token_masks          # (regions.py imports grid_shape from here)
-        _grid, both = pair_token_masks(scorer, scorer.tap_of(target_block, target_layer), latA.shape[-1], n, maskA, maskB)
-
-        def tail_of(i0, i1):
-            chunk = both[i0:i1].reshape(2 * (i1 - i0), -1).contiguous()
-            return lambda q, k, v, ia, ib, heads, sim: pair_score_maps_regions(q, k, v, chunk, ia, ib, heads, sim)
-        tail = None
+    tail, tail_of, carried = pair_score_maps, None, {}
+    if soft and maskA is None and maskB is None:
+        raise ValueError("soft=True weighs masks: give maskA and / or maskB")
+    if maskA is not None or maskB is not None:
+        kind = kind_of(soft)
+        _grid, rows = kind.pair_rows(scorer, scorer.tap_of(target_block, target_layer), latA.shape[-1], n, maskA, maskB)
+        maps_tail = kind.tail("maps", globals())
+        tail, tail_of = None, chunk_tails(rows, lambda chunk, q, k, v, ia, ib, heads, sim: maps_tail(q, k, v, chunk, ia, ib, heads, sim))
+        carried = {kind.carried: rows}
     latA, latB = latA.to(dev, torch.float32), latB.to(dev, torch.float32)
     noiseA, noiseB = noiseA.to(dev, torch.float32), noiseB.to(dev, torch.float32)
     tap = scorer.tap_of(target_block, target_layer)
@@ -125,7 +107,7 @@ def score_latent_pair_maps(scorer, latA, latB, noiseA, noiseB, prompt, target_bl
         score[i0:i1], local[i0:i1], contrib[i0:i1] = s, lo, co
     if score is None:
         raise ValueError("no pairs to map")
-    return SimilarityMaps(score, local, contrib, both, wts)
+    return SimilarityMaps(score, local, contrib, **carried)
 
 
 @torch.no_grad()
@@ -141,13 +123,9 @@ def score_path_pair_maps(scorer, pairs: Sequence[Tuple[str, str]], img_size, pro
     (latA, latB), nA, nB = path_latents(scorer, list(pairs), (0, 1), img_size, seed, 16, hip_vae=hip_vae)
     mA = mB = None
     if masks is not None:
-        from .regions import as_token_mask, as_token_weights, tap_grid
         if len(masks) != len(pairs):
             raise ValueError(f"{len(masks)} mask pairs for {len(pairs)} pairs")
-        grid = tap_grid(scorer, scorer.tap_of(target_block, target_layer), latA.shape[-1])
-        on_grid = as_token_weights if soft else as_token_mask
-        mA = torch.stack([on_grid(m[0], grid) for m in masks])
-        mB = torch.stack([on_grid(m[1], grid) for m in masks])
+        mA, mB = path_rows(kind_of(soft), masks, tap_grid(scorer, scorer.tap_of(target_block, target_layer), latA.shape[-1]))
     return score_latent_pair_maps(scorer, latA, latB, nA, nB, prompt, target_block, target_layer, target_step, similarity,
                                   batch_pairs, maskA=mA, maskB=mB, soft=soft)
 

@@ -26,9 +26,10 @@ from typing import List, Optional, Sequence
 import torch
 
 from ._lib import DsimError
-from .engine import (score_matrix, score_matrix_regions, score_matrix_regions_workspace_bytes, score_matrix_weights,
-                     score_matrix_weights_workspace_bytes, score_matrix_workspace_bytes)
+from .engine import (score_matrix, score_matrix_regions, score_matrix_regions_workspace_bytes, score_matrix_weights,  # noqa: F401
+                     score_matrix_weights_workspace_bytes, score_matrix_workspace_bytes)          # (RegionKind.tail finds them)
 from .inputs import path_latents
+from .regions import kind_of, tap_grid
 from .scorer import stack_rows
 
 IMAGE_EXTS = (".png", ".jpg", ".jpeg")
@@ -55,31 +56,11 @@ def _features(scorer, lat, noise, prompt, tap, step, batch: int):
     return tuple(torch.cat([p[i] for p in parts]) for i in range(3))
 
 
-def _set_masks(masks, n: int, grid, dev, name: str) -> torch.Tensor:
-    """(n, N) bool on dev: one token mask per image of a set (``regions.load_token_masks``: paths, PIL images, arrays on the grid,
-    None entries); masks None: whole images.  A mask with nothing on is the whole image, as a mask file's is."""
-    from .regions import load_token_masks
-    if masks is None:
-        return torch.ones((n, grid[0] * grid[1]), dtype=torch.bool, device=dev)
-    if len(masks) != n:
-        raise ValueError(f"{name}: {len(masks)} masks for {n} images")
-    m = load_token_masks(list(masks), grid).reshape(n, -1)
-    m = m | ~m.any(1, keepdim=True)
-    return m.to(dev).contiguous()
-
-
 def set_weights(masks, n: int, grid, dev, name: str) -> torch.Tensor:
-    """_set_masks for soft masks: (n, N) uint8 on dev, one row of token weights per image of a set (``regions.as_token_weights``:
-    paths, PIL images, arrays on the grid, None entries); masks None: whole images (255).  An image whose weights are all 0 is the
-    whole image, as an empty mask is."""
-    from .regions import as_token_weights
-    if masks is None:
-        return torch.full((n, grid[0] * grid[1]), 255, dtype=torch.uint8, device=dev)
-    if len(masks) != n:
-        raise ValueError(f"{name}: {len(masks)} masks for {n} images")
-    w = torch.stack([as_token_weights(m, grid) for m in masks]).reshape(n, -1) if n else torch.zeros((0, grid[0] * grid[1]), dtype=torch.uint8)
-    w = torch.where((w != 0).any(1, keepdim=True), w, torch.full_like(w, 255))
-    return w.to(dev).contiguous()
+    """(n, N) uint8 on dev, one row of token weights per image of a set (``regions.as_token_weights``: paths, PIL images, arrays on
+    the grid, None entries); masks None: whole images (255).  An image whose weights are all 0 is the whole image, as an empty mask
+    is (``RegionKind.set_rows`` on the soft kind)."""
+    return kind_of(True).set_rows(masks, n, grid, dev, name)
 
 
 @torch.no_grad()
@@ -120,16 +101,14 @@ def score_latent_matrix(scorer, latA, latB, noiseA, noiseB, prompt, target_block
     _, B, N, HD = fa[0].shape
     chunk = min(batch, n_b) if n_b else 1
     masked = masks_a is not None or masks_b is not None
-    if masked:
-        from .regions import tap_grid
-        grid = tap_grid(scorer, tap, latA.shape[-1])
-        set_of = set_weights if soft else _set_masks
-        masks_a, masks_b = set_of(masks_a, n_a, grid, dev, "masks_a"), set_of(masks_b, n_b, grid, dev, "masks_b")
-    elif soft:
-        raise DsimError("soft=True weighs masks: give masks_a and / or masks_b")
     workspace_bytes = score_matrix_workspace_bytes
     if masked:
-        workspace_bytes = score_matrix_weights_workspace_bytes if soft else score_matrix_regions_workspace_bytes
+        kind = kind_of(soft)
+        grid = tap_grid(scorer, tap, latA.shape[-1])
+        masks_a, masks_b = kind.set_rows(masks_a, n_a, grid, dev, "masks_a"), kind.set_rows(masks_b, n_b, grid, dev, "masks_b")
+        workspace_bytes = kind.tail("matrix_workspace_bytes", globals())
+    elif soft:
+        raise DsimError("soft=True weighs masks: give masks_a and / or masks_b")
     if mtail is not None:
         workspace_bytes = mtail.workspace_bytes
         ga = mtail.features(fa, heads)          # the query set's share of every chunk's matrix, once per call
@@ -144,11 +123,8 @@ def score_latent_matrix(scorer, latA, latB, noiseA, noiseB, prompt, target_block
         fb = _features(scorer, latB[j0:j1], nB, prompt, tap, target_step, batch)
         if mtail is not None:
             s, st = mtail.matrix(ga, mtail.features(fb, heads))
-        elif masked and soft:
-            s, st = score_matrix_weights(fa, fb, masks_a, masks_b[j0:j1].contiguous(), heads, similarity, return_status=True)
-            st = st != 0
         elif masked:
-            s, st = score_matrix_regions(fa, fb, masks_a, masks_b[j0:j1], heads, similarity, return_status=True)
+            s, st = kind.tail("matrix", globals())(fa, fb, masks_a, masks_b[j0:j1], heads, similarity, return_status=True)      # (a row slice: contiguous)
             st = st != 0
         else:
             s, st = score_matrix(fa, fb, heads, similarity, return_status=True)

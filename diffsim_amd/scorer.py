@@ -1,5 +1,5 @@
 """What the three scorer kinds share: the protocol the batched paths speak (pairs, triplets, score matrices, similarity maps, tap
-sweeps).  ``Scorer`` is the base of DiffSim, diffsim_xl and diffsim_DiT.  Each subclass states the per-call arithmetic of its
+sweeps) and the one-pair path calls over regions.  ``Scorer`` is the base of DiffSim, diffsim_xl and diffsim_DiT.  Each subclass states the per-call arithmetic of its
 reference entry point (DiffSim.diffsim, diffsim_xl.diffsim_score, diffsim_DiT.diffsim_score) as attributes and a few one-line
 methods; everything here is written against those, never against a class name.
 """
@@ -270,3 +270,139 @@ class Scorer:
                 chunk_tail = text_of(i0, i1, xq, xkv, heads)
             ia = torch.arange(0, 2 * (i1 - i0), 2, dtype=torch.int32, device=self.device)
             yield i0, i1, chunk_tail(q, k, v, ia, ia + 1, heads, similarity)
+
+    # ---- the one-pair path calls: two image files in, the per-token and region forms of the kind's one-pair score (DiffSim.diffsim,
+    #      diffsim_xl.diffsim_score, diffsim_DiT.diffsim_score) out.  Written against three facts of the kind.
+    path_hip_vae = False                    # whether the files are encoded through the HIP VAE fast path (inputs.path_latents)
+    path_batch_pairs = None                 # pairs per engine batch (None: Scorer.auto_map_pairs)
+
+    def path_tap(self, prompt, target_block, target_layer):
+        """(prompt, target_block, target_layer) as the batched module functions take the reference's flag pair from this kind"""
+        return prompt, target_block, target_layer
+
+    def _path_pair_latents(self, image_A, image_B, img_size, seed):
+        """(latentsA, latentsB, noiseA, noiseB) as f32 tensors: what one reference call draws for the two image files."""
+        from .inputs import path_latents
+        (latA, latB), nA, nB = path_latents(self, [(image_A, image_B)], (0, 1), img_size, seed, 1, hip_vae=self.path_hip_vae)
+        return latA, latB, nA, nB
+
+    @torch.no_grad()
+    def alignment(self, image_A, image_B, img_size, prompt, target_block, target_layer, target_step, seed="2333"):
+        """Which token of the other image each token of one pair attends to: an :class:`~diffsim_amd.align.Alignment` of one pair
+        (direction 0 on image_A's grid, 1 on image_B's)."""
+        from . import align
+        return align.score_path_pair_alignment(self, [(image_A, image_B)], img_size, *self.path_tap(prompt, target_block, target_layer),
+                                               target_step, seed, self.path_batch_pairs, hip_vae=self.path_hip_vae)
+
+    @torch.no_grad()
+    def region_score(self, image_A, image_B, mask_A, mask_B, img_size, prompt, target_block, target_layer, target_step,
+                     seed="2333", similarity="cosine"):
+        """The one-pair score of the masked part of each image (regions.py): the score tail over the tokens of mask_A on image_A and
+        of mask_B on image_B alone.  A mask is a path, a PIL image, a bool array on the tap's token grid, or None (the whole
+        image); full masks give the unmasked score.  Returns a (1,) tensor."""
+        from . import regions
+        return regions.score_path_pair_regions(self, [(image_A, image_B)], [(mask_A, mask_B)], img_size,
+                                               *self.path_tap(prompt, target_block, target_layer), target_step, seed, similarity,
+                                               batch_pairs=self.path_batch_pairs, hip_vae=self.path_hip_vae)
+
+    @torch.no_grad()
+    def soft_region_score(self, image_A, image_B, mask_A, mask_B, img_size, prompt, target_block, target_layer, target_step,
+                          seed="2333", similarity="cosine"):
+        """:meth:`region_score` with a weight per token instead of a bit (regions.py, ``engine.pair_score_weights``): a mask's area
+        average on the token grid is the token's weight, so a partly covered token counts partly -- as a key through a logit bias in
+        both attentions, as a query through a factor on its terms.  A mask is a path, a PIL image, a uint8 / bool / [0, 1] float
+        array on the tap's token grid, or None (the whole image); masks of 0 and 255 alone give :meth:`region_score`'s score.
+        Returns a (1,) tensor."""
+        from . import regions
+        return regions.score_path_pair_weights(self, [(image_A, image_B)], [(mask_A, mask_B)], img_size,
+                                               *self.path_tap(prompt, target_block, target_layer), target_step, seed, similarity,
+                                               batch_pairs=self.path_batch_pairs, hip_vae=self.path_hip_vae)
+
+    def _path_region_maps(self, image_A, image_B, mask_A, mask_B, img_size, prompt, target_block, target_layer, target_step, seed,
+                          similarity, **soft):
+        from . import maps
+        return maps.score_path_pair_maps(self, [(image_A, image_B)], img_size, *self.path_tap(prompt, target_block, target_layer),
+                                         target_step, seed, similarity, self.path_batch_pairs, masks=[(mask_A, mask_B)],
+                                         hip_vae=self.path_hip_vae, **soft)
+
+    def _path_region_alignment(self, image_A, image_B, mask_A, mask_B, img_size, prompt, target_block, target_layer, target_step, seed,
+                               **soft):
+        from . import align
+        return align.score_path_pair_alignment(self, [(image_A, image_B)], img_size, *self.path_tap(prompt, target_block, target_layer),
+                                               target_step, seed, self.path_batch_pairs, masks=[(mask_A, mask_B)],
+                                               hip_vae=self.path_hip_vae, **soft)
+
+    @torch.no_grad()
+    def region_similarity_maps(self, image_A, image_B, mask_A, mask_B, img_size, prompt, target_block, target_layer, target_step,
+                               seed="2333", similarity="cosine"):
+        """:meth:`region_score` of one image pair with its per-token terms on both images' grids: a
+        :class:`~diffsim_amd.maps.SimilarityMaps` of one pair whose attentions ran over the masked tokens alone (zeros at the off
+        tokens; ``.mask`` holds the two token masks).  Masks as :meth:`region_score` takes them."""
+        return self._path_region_maps(image_A, image_B, mask_A, mask_B, img_size, prompt, target_block, target_layer, target_step, seed,
+                                      similarity)
+
+    @torch.no_grad()
+    def soft_region_similarity_maps(self, image_A, image_B, mask_A, mask_B, img_size, prompt, target_block, target_layer, target_step,
+                                    seed="2333", similarity="cosine"):
+        """:meth:`soft_region_score` of one image pair with its per-token terms on both images' grids: a
+        :class:`~diffsim_amd.maps.SimilarityMaps` of one pair (``.weights`` holds the two uint8 token weights, ``.mask`` is
+        ``weights != 0``; zeros at the tokens of weight 0).  ``local`` is a token's own value, ``contrib`` carries its weight.
+        Masks as :meth:`soft_region_score` takes them."""
+        return self._path_region_maps(image_A, image_B, mask_A, mask_B, img_size, prompt, target_block, target_layer, target_step, seed,
+                                      similarity, soft=True)
+
+    @torch.no_grad()
+    def region_alignment(self, image_A, image_B, mask_A, mask_B, img_size, prompt, target_block, target_layer, target_step,
+                         seed="2333"):
+        """Which token of the other image's region each token of a region attends to: an :class:`~diffsim_amd.align.Alignment` of
+        one pair whose softmaxes ran over the other image's masked tokens alone (off tokens: match -1; ``.mask`` holds the two
+        token masks).  Masks as :meth:`region_score` takes them."""
+        return self._path_region_alignment(image_A, image_B, mask_A, mask_B, img_size, prompt, target_block, target_layer, target_step,
+                                           seed)
+
+    @torch.no_grad()
+    def soft_region_alignment(self, image_A, image_B, mask_A, mask_B, img_size, prompt, target_block, target_layer, target_step,
+                              seed="2333"):
+        """:meth:`region_alignment` with soft masks: every softmax runs over the other image's tokens of weight > 0 with ln(weight)
+        added to the logits (an :class:`~diffsim_amd.align.Alignment` of one pair; ``.weights`` holds the two uint8 token weights;
+        tokens of weight 0: match -1).  Masks as :meth:`soft_region_score` takes them."""
+        return self._path_region_alignment(image_A, image_B, mask_A, mask_B, img_size, prompt, target_block, target_layer, target_step,
+                                           seed, soft=True)
+
+    @torch.no_grad()
+    def text_region_score(self, image_A, image_B, img_size, prompt, target_block, target_layer, target_step, seed="2333",
+                          similarity="cosine", words=None, rel_threshold=1.0):
+        """The one-pair score of the part of each image the prompt names (textattn.py; the reference's declared and unbuilt
+        ``--use_text_attn``, argprocess.py:17): each image's region is the tokens whose text attention to `words` (None: every
+        content token of the prompt) is at least rel_threshold x the image's mean.  Returns a (1,) tensor."""
+        from . import textattn
+        return textattn.score_path_pairs_text(self, [(image_A, image_B)], img_size, *self.path_tap(prompt, target_block, target_layer),
+                                              target_step, seed, similarity, words, rel_threshold, hip_vae=self.path_hip_vae)
+
+    @torch.no_grad()
+    def text_attention_map(self, image_A, image_B, img_size, prompt, target_block, target_layer, target_step, seed="2333"):
+        """The text attention maps of the two images of one pair: (2, h, w, L) f32 on the tap's token grid."""
+        from . import textattn
+        latA, latB, nA, nB = self._path_pair_latents(image_A, image_B, img_size, seed)
+        return textattn.text_attention_maps(self, torch.cat([latA, latB]), torch.cat([nA, nB]),
+                                            *self.path_tap(prompt, target_block, target_layer), target_step)
+
+    @torch.no_grad()
+    def exemplar_region_score(self, image_A, image_B, mask_A, img_size, prompt, target_block, target_layer, target_step, seed="2333",
+                              similarity="cosine", rel_threshold=1.0, soft=False):
+        """:meth:`region_score` with a mask for image_A alone (transfer.py): image_B's region is the tokens whose attention mass into
+        mask_A's tokens is at least rel_threshold x the image's mean; soft: token weights on both sides.  Returns a (1,) tensor."""
+        from . import transfer
+        return transfer.score_path_pairs_exemplar(self, [(image_A, image_B)], [mask_A], img_size,
+                                                  *self.path_tap(prompt, target_block, target_layer), target_step, seed, similarity,
+                                                  self.path_batch_pairs, rel_threshold, soft, hip_vae=self.path_hip_vae)
+
+    @torch.no_grad()
+    def transferred_region(self, image_A, image_B, mask_A, img_size, prompt, target_block, target_layer, target_step, seed="2333",
+                           rel_threshold=1.0, soft=False):
+        """(mass (h, w) f32, region (h, w) bool -- soft: uint8 weights) on image_B's token grid: what :meth:`exemplar_region_score`
+        transfers from mask_A."""
+        from . import transfer
+        return transfer.path_transferred_region(self, image_A, image_B, mask_A, img_size,
+                                                *self.path_tap(prompt, target_block, target_layer), target_step, seed, rel_threshold,
+                                                soft, self.path_batch_pairs, hip_vae=self.path_hip_vae)

@@ -16,9 +16,9 @@ from typing import Callable, Optional, Sequence, Tuple
 
 import torch
 
-from .engine import pair_score_regions, pair_score_weights, text_attention
+from .engine import pair_score_regions, pair_score_weights, text_attention      # noqa: F401  (RegionKind.tail)
 from .inputs import path_latents
-from .maps import grid_shape
+from .regions import grid_shape, kind_of
 from .scorer import single_prompt, stack_rows
 
 
@@ -191,7 +191,7 @@ def score_latent_pairs_text(scorer, latA, latB, noiseA, noiseB, prompt, target_b
     if n == 0:
         raise ValueError("no pairs to score")
     tap, guide, w = _tap_and_guide(scorer, prompt, n, target_block, target_layer, words, rel_threshold, weights, soft)
-    region_tail = pair_score_weights if soft else pair_score_regions
+    region_tail = kind_of(soft).tail("score", globals())
     latA, latB = latA.to(dev, torch.float32), latB.to(dev, torch.float32)
     noiseA, noiseB = noiseA.to(dev, torch.float32), noiseB.to(dev, torch.float32)
     bound = scorer.bind_prompt(prompt, n, "pairs")

@@ -20,9 +20,9 @@ from typing import Optional, Sequence, Tuple
 
 import torch
 
-from .engine import pair_region_transfer, pair_score_regions, pair_score_weights
+from .engine import pair_region_transfer, pair_score_regions, pair_score_weights      # noqa: F401  (RegionKind.tail)
 from .inputs import path_latents
-from .regions import as_token_mask, as_token_weights, tap_grid
+from .regions import chunk_tails, kind_of, tap_grid
 from .textattn import soft_token_bytes
 
 
@@ -57,7 +57,7 @@ class ExemplarGuide:
         exemplar row is returned all on).  An image that is idx_b of several pairs keeps the last pair's region.  q, k: the chunk's
         features; ia, ib: int32 (pairs,).  return_mass: also the (pairs, N) f32 mass on the idx_b images' grids (1 where no launch was
         needed)."""
-        want = torch.uint8 if self.soft else torch.bool
+        want = kind_of(self.soft).dtype
         if rows.dtype != want or rows.ndim != 2:
             raise ValueError(f"a {'soft' if self.soft else 'hard'} guide takes (images, N) {want} rows: {rows.dtype} {tuple(rows.shape)}")
         la, lb = ia.long(), ib.long()
@@ -92,11 +92,10 @@ def require_exemplar_regions(scorer):
 def exemplar_rows(maskA, n: int, grid: Tuple[int, int], soft: bool) -> torch.Tensor:
     """The exemplars' masks on the token grid: maskA None (every exemplar whole), or n entries, each a path, a PIL image, an array on
     the grid or None (``regions.as_token_mask``; soft: ``regions.as_token_weights``).  (n, N) bool or uint8 on the CPU."""
-    on_grid = as_token_weights if soft else as_token_mask
     entries = [None] * n if maskA is None else list(maskA)
     if len(entries) != n:
         raise ValueError(f"{len(entries)} exemplar masks for {n} pairs")
-    return torch.stack([on_grid(m, grid) for m in entries]).flatten(1)
+    return torch.stack([kind_of(soft).on_grid(m, grid) for m in entries]).flatten(1)
 
 
 @torch.no_grad()
@@ -116,10 +115,10 @@ def score_latent_pairs_exemplar(scorer, latA, latB, noiseA, noiseB, maskA, promp
     guide = ExemplarGuide(rel_threshold, soft)
     tap = scorer.tap_of(target_block, target_layer)
     grid = tap_grid(scorer, tap, latA.shape[-1])
+    kind = kind_of(soft)
+    region_tail = kind.tail("score", globals())
     mA = exemplar_rows(maskA, n, grid, soft)
-    whole = torch.full_like(mA, 255) if soft else torch.ones_like(mA)
-    both = torch.stack([mA, whole], dim=1).to(dev)              # (n, 2, N): a chunk's rows interleave as its images do
-    region_tail = pair_score_weights if soft else pair_score_regions
+    both = torch.stack([mA, kind.whole_rows(*mA.shape)], dim=1).to(dev)     # (n, 2, N): a chunk's rows interleave as its images do
     latA, latB = latA.to(dev, torch.float32), latB.to(dev, torch.float32)
     noiseA, noiseB = noiseA.to(dev, torch.float32), noiseB.to(dev, torch.float32)
     prompt = scorer.bind_prompt(prompt, n, "pairs")
@@ -127,17 +126,13 @@ def score_latent_pairs_exemplar(scorer, latA, latB, noiseA, noiseB, maskA, promp
         batch_pairs = scorer.auto_map_pairs(scorer.engine_at(tap), n)
     made, masses = [], []
 
-    def tail_of(i0, i1):
-        chunk = both[i0:i1].reshape(2 * (i1 - i0), -1).contiguous()
-
-        def tail(q, k, v, ia, ib, heads, sim):
-            rows, mass = guide.regions(q, k, heads, chunk, ia, ib, return_mass=True)
-            made.append(rows), masses.append(mass)
-            return region_tail(q, k, v, rows.contiguous(), ia, ib, heads, sim)
-        return tail
+    def tail(chunk, q, k, v, ia, ib, heads, sim):
+        rows, mass = guide.regions(q, k, heads, chunk, ia, ib, return_mass=True)
+        made.append(rows), masses.append(mass)
+        return region_tail(q, k, v, rows.contiguous(), ia, ib, heads, sim)
     score = torch.empty(n, dtype=torch.float32, device=dev)
     for i0, i1, s in scorer.pair_chunks(latA, latB, noiseA, noiseB, prompt, tap, target_step, similarity, batch_pairs, None,
-                                        tail_of=tail_of):
+                                        tail_of=chunk_tails(both, tail)):
         score[i0:i1] = s
     if not return_regions:
         return score

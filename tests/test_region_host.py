@@ -281,3 +281,109 @@ def test_triplet_masks_lie_as_the_chunk_images_do(monkeypatch, tmp_path):
         R.score_latent_pair_regions(s, torch.zeros(2, 4, 16, 16), torch.zeros(2, 4, 16, 16), torch.zeros(1, 4, 16, 16),
                                     torch.zeros(1, 4, 16, 16), torch.ones(2, 4, 4, dtype=torch.bool), torch.ones(2, 4, 4, dtype=torch.bool),
                                     "p", "up_blocks", 0, 600)
+
+
+# ---- the one-pair path methods: one body on Scorer, the kinds' facts reach the module functions -----------------------------------------
+def _kinds():
+    from diffsim_amd.diffsim import DiffSim
+    from diffsim_amd.diffsim_dit import diffsim_DiT
+    from diffsim_amd.diffsim_xl import diffsim_xl
+    # (kind, the --target_layer given, (prompt, block, layer) the module functions get, hip_vae, batch_pairs)
+    return [(DiffSim, [0], ("p", "up_blocks", 0), True, None), (diffsim_xl, [0, 1, 2], ("p", "up_blocks", [0, 1, 2]), False, None),
+            (diffsim_DiT, [3], (None, "none", [3]), False, 32)]
+
+
+@pytest.mark.parametrize("which", [0, 1, 2], ids=["DiffSim", "diffsim_xl", "diffsim_DiT"])
+def test_path_methods_hand_the_kinds_facts_to_the_module_functions(monkeypatch, which):
+    """Every one-pair path method, once per kind: the prompt / block / layer, hip_vae and batch_pairs that arrive at the module
+    function are the kind's -- DiffSim: the layer through _norm_layer, the HIP VAE, no batch; diffsim_xl: the flag pair untouched,
+    no HIP VAE, no batch; diffsim_DiT: (None, "none", [layer]), no HIP VAE, 32 pairs."""
+    import inspect
+    from diffsim_amd import align, inputs, maps, regions, textattn, transfer
+    cls, layer, (prompt, block, tap_layer), hip_vae, batch = _kinds()[which]
+    log = []
+
+    def record(mod, name, result=None):
+        sig = inspect.signature(getattr(mod, name))
+
+        def fake(*a, **k):
+            bound = sig.bind(*a, **k)
+            bound.apply_defaults()
+            log.append((name, dict(bound.arguments)))
+            return result
+        monkeypatch.setattr(mod, name, fake)
+    z = torch.zeros(1, 4, 2, 2)
+    for mod, name in ((regions, "score_path_pair_regions"), (regions, "score_path_pair_weights"), (maps, "score_path_pair_maps"),
+                      (align, "score_path_pair_alignment"), (textattn, "score_path_pairs_text"), (textattn, "text_attention_maps"),
+                      (transfer, "score_path_pairs_exemplar"), (transfer, "path_transferred_region")):
+        record(mod, name)
+    record(inputs, "path_latents", ((z, z), z, z))
+    s = object.__new__(cls)
+    if hip_vae:                                                             # DiffSim draws one call's latents its own way
+        s._path_pair_latents = lambda *a: (z, z, z, z)
+    head = ("a.png", "b.png")
+    tail = (128, "p", "up_blocks", layer, 600)
+    masked = ("region_score", "soft_region_score", "region_similarity_maps", "soft_region_similarity_maps", "region_alignment",
+              "soft_region_alignment")
+    for name in masked:
+        getattr(s, name)(*head, "ma", "mb", *tail, 7, *(() if "alignment" in name else ("mse",)))
+    s.alignment(*head, *tail, 7)
+    s.exemplar_region_score(*head, "ma", *tail, 7, "mse", 1.5, True)
+    s.transferred_region(*head, "ma", *tail, 7, 1.5, True)
+    if which == 2:
+        for name in ("text_region_score", "text_attention_map"):
+            with pytest.raises(NotImplementedError, match="diffsim_DiT has no text conditioning"):
+                getattr(s, name)(*head, *tail, 7)
+    else:
+        s.text_region_score(*head, *tail, 7, "mse", ["cat"], 1.25)
+        s.text_attention_map(*head, *tail, 7)
+    want = ["score_path_pair_regions", "score_path_pair_weights", "score_path_pair_maps", "score_path_pair_maps",
+            "score_path_pair_alignment", "score_path_pair_alignment", "score_path_pair_alignment", "score_path_pairs_exemplar",
+            "path_transferred_region"] + ([] if which == 2 else ["score_path_pairs_text"] + ["path_latents"] * (not hip_vae) +
+                                          ["text_attention_maps"])
+    assert [n for n, _ in log] == want
+    for name, got in log:
+        if name == "path_latents":
+            assert got["hip_vae"] is False and got["rows"] == [head] and got["seed"] == 7 and got["img_size"] == 128
+            continue
+        assert (got["prompt"], got["target_block"], got["target_layer"]) == (prompt, block, tap_layer), name
+        assert got["target_step"] == 600 and got["scorer"] is s, name
+        if name == "text_attention_maps":
+            assert got["lat"].shape[0] == 2 and got["batch"] is None
+            continue
+        assert got["hip_vae"] is hip_vae and got["seed"] == 7 and got["img_size"] == 128, name
+        if name != "score_path_pairs_text":
+            assert got["batch_pairs"] == batch, name
+    by = lambda name: [g for n, g in log if n == name]                       # noqa: E731
+    assert all(g["pairs"] == [head] and g["masks"] == [("ma", "mb")] and g["similarity"] == "mse"
+               for n, g in log if n in ("score_path_pair_regions", "score_path_pair_weights", "score_path_pair_maps"))
+    assert [g["soft"] for g in by("score_path_pair_maps")] == [False, True]
+    assert [(g["masks"], g["soft"]) for g in by("score_path_pair_alignment")] == [([("ma", "mb")], False), ([("ma", "mb")], True), (None, False)]
+    ex, tr = by("score_path_pairs_exemplar")[0], by("path_transferred_region")[0]
+    assert ex["masks_a"] == ["ma"] and (ex["similarity"], ex["rel_threshold"], ex["soft"], ex["return_regions"]) == ("mse", 1.5, True, False)
+    assert (tr["image_A"], tr["image_B"], tr["mask_A"], tr["rel_threshold"], tr["soft"]) == (*head, "ma", 1.5, True)
+    if which != 2:
+        tx = by("score_path_pairs_text")[0]
+        assert (tx["similarity"], tx["words"], tx["rel_threshold"], tx["weights"], tx["batch_pairs"], tx["soft"]) == \
+            ("mse", ["cat"], 1.25, None, None, False)
+
+
+def test_hard_region_tails_refuse_a_strided_mask(monkeypatch):
+    """A mask that is not contiguous would be read as if dense: the four hard forms refuse it as the soft forms do, before anything
+    needs a device."""
+    from diffsim_amd import _lib, engine
+    monkeypatch.setattr(_lib, "lib", lambda: pytest.fail("the library was touched"))
+    N, H, D = 16, 2, 8
+    q, k, v = (torch.zeros(3, 2, N, H * D) for _ in range(3))
+    ia = torch.zeros(1, dtype=torch.int32)
+    m = torch.ones(3, N, dtype=torch.bool)
+    strided = m.t().contiguous().t()
+    assert strided.shape == m.shape and not strided.is_contiguous()
+    for call in (lambda mk: engine.pair_score_regions(q, k, v, mk, ia, ia, H), lambda mk: engine.pair_score_maps_regions(q, k, v, mk, ia, ia, H),
+                 lambda mk: engine.pair_align_regions(q, k, mk, ia, ia, H),
+                 lambda mk: engine.score_matrix_regions((q, k, v), (q, k, v), mk, m, H),
+                 lambda mk: engine.score_matrix_regions((q, k, v), (q, k, v), m, mk, H)):
+        with pytest.raises(_lib.DsimError, match="contiguous"):
+            call(strided)
+        with pytest.raises(_lib.DsimError, match="not on the GPU"):         # (a dense mask gets as far as the device requirement)
+            call(m)

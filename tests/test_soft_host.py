@@ -206,7 +206,8 @@ def test_accepted_argument_lists_parse_as_before():
 
 
 def test_weight_rows_are_checked_against_the_grid():
-    from diffsim_amd.regions import _flat_weights
+    from diffsim_amd.regions import SOFT
+    _flat_weights = SOFT.flat_rows
     g = torch.Generator().manual_seed(4)
     w = torch.randint(1, 256, (3, 4, 4), generator=g).to(torch.uint8)
     assert torch.equal(_flat_weights(w, 3, (4, 4), "w"), w.reshape(3, 16)) and torch.equal(_flat_weights(w.reshape(3, 16), 3, (4, 4), "w"),
