@@ -237,6 +237,12 @@ SYMBOLS = {
     "dsim_pair_region_transfer": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "dsim_score_matrix_weights_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
     "dsim_score_matrix_weights": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dsim_region_transfer_matrix_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
+    "dsim_region_transfer_matrix": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "dsim_score_matrix_cell_regions_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
+    "dsim_score_matrix_cell_regions": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dsim_score_matrix_cell_weights_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
+    "dsim_score_matrix_cell_weights": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dsim_op_linear": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "dsim_op_conv3x3": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "dsim_op_groupnorm": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _f, _i, _i, _vp]),

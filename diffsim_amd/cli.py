@@ -4,7 +4,7 @@
 
 Flags of the reference drivers (``/root/reference/argprocess.py:5-18``) keep their names, meaning and defaults;
 ``--dataset`` selects which of the reference's loops runs (``cute_main.py:48-226``, ``night_main.py:24-173`` or
-``style_main.py:24-196`` -- separate scripts there), ``--model_path / --dtype / --batch / --unet_batch / --ngpu / --noise_dtype / --gpu_resize / --mask_path / --query_mask_path / --gallery_mask_path / --save_region_maps / --save_region_matches / --text_attn / --text_threshold / --soft_masks / --text_soft / --transfer_masks / --transfer_threshold`` are additions of this build (the reference
+``style_main.py:24-196`` -- separate scripts there), ``--model_path / --dtype / --batch / --unet_batch / --ngpu / --noise_dtype / --gpu_resize / --mask_path / --query_mask_path / --gallery_mask_path / --save_region_maps / --save_region_matches / --text_attn / --text_threshold / --soft_masks / --text_soft / --transfer_masks / --transfer_threshold / --save_transfer`` are additions of this build (the reference
 hard-codes NAS checkpoint paths, ``cute_main.py:25-31``, fp16 and one GPU, ``cute_main.sh:1``).
 
 Multi-GPU (``--ngpu N``): the parent starts N rank processes before anything touches the GPU; triplets are sharded
@@ -102,7 +102,10 @@ def build_parser() -> argparse.ArgumentParser:
                    help="--text_attn: a token is in its image's region at >= this multiple of the image's mean text saliency "
                         "(0: every token; a region with no token on is the whole image)")
     p.add_argument("--transfer_masks", action="store_true", default=argparse.SUPPRESS,      # (off: _Args.transfer_masks)
-                   help="--mask_path, --dataset cute|nights, --metric diffsim|diffsim_xl|dit: exemplar-guided regions -- only the "
+                   help="--dataset retrieval with --query_mask_path: exemplar-guided retrieval -- only the queries read their mask "
+                        "files; every gallery image's region against a query is the tokens whose attention mass into the query's masked "
+                        "tokens passes --transfer_threshold, and the ranking is by the region score of each cell.  "
+                        "--mask_path, --dataset cute|nights, --metric diffsim|diffsim_xl|dit: exemplar-guided regions -- only the "
                         "reference image of each triplet reads its mask file; each candidate's region is the tokens whose attention mass "
                         "into the reference's masked tokens is at least --transfer_threshold x the candidate's mean mass.  With "
                         "--soft_masks the reference's weights and the transferred regions are soft.  The run prints how many references "
@@ -110,6 +113,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--transfer_threshold", type=float, default=argparse.SUPPRESS, metavar="T",      # (default: _Args.transfer_threshold)
                    help="--transfer_masks: a candidate's token is in its region at >= this multiple of the image's mean attention mass "
                         "(default 1.0; 0: every token; a region with no token on is the whole image)")
+    p.add_argument("--save_transfer", action="store_true", default=argparse.SUPPRESS,      # (off: _Args.save_transfer)
+                   help="--dataset retrieval with --transfer_masks: beside each ranking .txt also write <name>.transfer.npz with the "
+                        "regions the query's mask transferred to its top-k gallery images (gallery, region (k, h, w), bool or with "
+                        "--soft_masks uint8 weights, and mass (k, h, w), the attention mass on each gallery image's token grid)")
     p.add_argument("--experiments", type=int, default=2000, help="--dataset sref: sampled experiments (style_main.py:64)")
     p.add_argument("--model_path", type=str, default=None, help="diffusers-layout checkpoint directory (unet/, vae/, text_encoder/, tokenizer/)")
     p.add_argument("--dtype", type=str, choices=["bf16", "fp16", "fp32"], default="bf16",
@@ -144,6 +151,7 @@ class _Args(argparse.Namespace):
     gpu_resize = False
     transfer_masks = False
     transfer_threshold = 1.0
+    save_transfer = False
 
 
 def arg_parse(argv=None):
@@ -170,12 +178,25 @@ def arg_parse(argv=None):
             p.error(f"--soft_masks: --metric {args.metric} has no regions")
     if "transfer_threshold" in vars(args) and not args.transfer_masks:
         p.error("--transfer_threshold is the threshold of --transfer_masks: it needs --transfer_masks")
+    if args.save_transfer and not (args.transfer_masks and args.dataset == "retrieval"):
+        p.error("--save_transfer writes the transferred regions of an exemplar-guided retrieval run: it needs --transfer_masks and "
+                "--dataset retrieval")
     if args.transfer_masks:
-        if args.mask_path is None:
+        if args.dataset == "retrieval":
+            if args.query_mask_path is None:
+                p.error("--transfer_masks with --dataset retrieval transfers the query images' masks to every gallery image: it needs "
+                        "--query_mask_path (--mask_path is the triplet benchmarks')")
+            if args.gallery_mask_path is not None:
+                p.error("--transfer_masks: the gallery's regions are the transferred ones, --gallery_mask_path is not supported with it")
+            if args.save_region_maps or args.save_region_matches:
+                p.error("--transfer_masks: region maps and region alignments over transferred regions (--save_region_maps, "
+                        "--save_region_matches) are not supported")
+        elif args.mask_path is None:
             p.error("--transfer_masks transfers the reference images' masks of --mask_path: it needs --mask_path")
-        if args.dataset not in ("cute", "nights") or args.taps is not None:
-            p.error("--transfer_masks scores exemplar-guided regions on the one-tap triplet benchmarks (--dataset cute or nights): "
-                    "--dataset sref, --dataset retrieval and a sweep (--taps) are not supported with it")
+        if args.dataset not in ("cute", "nights", "retrieval") or args.taps is not None:
+            p.error("--transfer_masks scores exemplar-guided regions on the one-tap triplet benchmarks (--dataset cute or nights, with "
+                    "--mask_path) and on retrieval rankings (--dataset retrieval, with --query_mask_path): --dataset sref and a sweep "
+                    "(--taps) are not supported with it")
         if args.text_attn is not None:
             p.error("--transfer_masks: an exemplar-guided region and a text-guided region (--text_attn), one or the other")
         if args.metric in VIT_METRICS or args.metric in FEATURE_METRICS:
@@ -558,7 +579,22 @@ def run_retrieval(args, scorer, layer) -> int:
         R.ranking_names(queries, args.query_path)               # two queries that would share a ranking file: refused before scoring
     except ValueError as e:
         raise SystemExit(str(e))
-    if args.query_mask_path is not None or args.gallery_mask_path is not None:
+    exemplar = regions = None
+    if getattr(args, "transfer_masks", False):         # (a plain Namespace without the flag: off)
+        from .regions import mask_path_for
+        from .transfer import ExemplarGuide
+        exemplar = ExemplarGuide(args.transfer_threshold, args.soft_masks)
+        qmasks = [mask_path_for(p, args.query_path, args.query_mask_path) for p in queries]
+        print(f"Exemplar-guided retrieval: only the queries read their masks (from {args.query_mask_path}), threshold "
+              f"{args.transfer_threshold:g} x the mean attention mass; {sum(1 for f in qmasks if f is None)} query image(s) without a "
+              "mask file make their gallery images whole")
+        res = R.score_path_matrix(scorer, queries, gallery, args.image_size, args.prompt, args.target_block, layer, args.target_step,
+                                  args.seed, args.similarity, return_status=True, masks_a=qmasks, exemplar=exemplar,
+                                  return_regions=bool(getattr(args, "save_transfer", False) and queries and gallery))
+        (m, bad), regions = res[:2], res[2:]
+        if queries and gallery:
+            print(f"Mean {'token weight' if args.soft_masks else 'share of tokens on'}: {exemplar.on_fraction * 100:.2f}%")
+    elif args.query_mask_path is not None or args.gallery_mask_path is not None:
         from .regions import mask_path_for
         masks, missing = {}, 0
         for side, paths, root, mdir in (("masks_a", queries, args.query_path, args.query_mask_path),
@@ -604,6 +640,15 @@ def run_retrieval(args, scorer, layer) -> int:
         print(f"WARNING: {bad} score(s) are NaN/inf (ranked last)")
     print(f"Score matrix {tuple(m.shape)} ({len(queries)} queries x {len(gallery)} gallery images, {args.similarity}); "
           f"top-{min(args.topk, len(gallery))} rankings of {len(files)} queries written to {args.out_path}")
+    if regions:
+        import numpy as np
+        _vals, idx = R.topk(m, args.topk, args.similarity)
+        region, mass = (t.cpu() for t in regions)
+        for i, fn in enumerate(files):
+            np.savez(os.path.splitext(fn)[0] + ".transfer.npz", gallery=np.array([gallery[j] for j in idx[i].tolist()]),
+                     region=region[i, idx[i]].numpy(), mass=mass[i, idx[i]].numpy())
+        print(f"Transferred regions {region.shape[2]}x{region.shape[3]} of the top-{idx.shape[1]} cells of {len(files)} queries written "
+              f"to {args.out_path}")
     if args.save_maps and queries and gallery:
         from . import maps as M
         _vals, idx = R.topk(m, args.topk, args.similarity)

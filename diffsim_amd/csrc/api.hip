@@ -240,6 +240,48 @@ int dsim_pair_region_transfer(const void* q, const void* k, const uint8_t* weigh
     return st != DSIM_OK ? st : launch_pair_region_transfer(a, dtype, weights, n_feat, directions, mass, status, (hipStream_t)stream);
 }
 
+size_t dsim_region_transfer_matrix_workspace_bytes(int n_a, int n_b, int B, int H, int N, int D, int dtype) {
+    return with_slack(region_transfer_matrix_scratch_bytes(n_a, n_b, B, H, N, D, dtype));
+}
+
+int dsim_region_transfer_matrix(const void* qa, const void* ka, const uint8_t* weights_a, int n_a, const void* qb, const void* kb, int n_b,
+                                int B, int H, int N, int D, int dtype, float* mass, int32_t* status, void* workspace, size_t workspace_bytes,
+                                void* stream) {
+    MatrixArgs a{{qa, qb}, {ka, kb}, {nullptr, nullptr}, {weights_a, nullptr}, n_a, n_b, B, H, N, D, 0, workspace, workspace_bytes};
+    const bool served = region_transfer_matrix_scratch_bytes(n_a, n_b, B, H, N, D, dtype) != 0;
+    const int st = tail_prologue({qa, ka, weights_a, qb, kb, mass}, served ? DSIM_OK : DSIM_ERR_INVALID, a.scratch, a.scratch_bytes);
+    return st != DSIM_OK ? st : launch_region_transfer_matrix(a, dtype, mass, status, (hipStream_t)stream);
+}
+
+size_t dsim_score_matrix_cell_regions_workspace_bytes(int n_a, int n_b, int B, int H, int N, int D, int dtype) {
+    return with_slack(score_matrix_cell_regions_scratch_bytes(n_a, n_b, B, H, N, D, dtype));
+}
+
+int dsim_score_matrix_cell_regions(const void* qa, const void* ka, const void* va, const uint8_t* mask_a, int n_a, const void* qb,
+                                   const void* kb, const void* vb, const uint8_t* mask_b, int n_b, int B, int H, int N, int D, int dtype,
+                                   int similarity, float* out, int32_t* status, int32_t* counts, void* workspace, size_t workspace_bytes,
+                                   void* stream) {
+    MatrixArgs a{{qa, qb}, {ka, kb}, {va, vb}, {mask_a, mask_b}, n_a, n_b, B, H, N, D, similarity, workspace, workspace_bytes};
+    const bool served = score_matrix_cell_regions_scratch_bytes(n_a, n_b, B, H, N, D, dtype) != 0 && (similarity == 0 || similarity == 1);
+    const int st = tail_prologue({qa, ka, va, mask_a, qb, kb, vb, mask_b, out}, served ? DSIM_OK : DSIM_ERR_INVALID, a.scratch, a.scratch_bytes);
+    return st != DSIM_OK ? st : launch_score_matrix_cell_regions(a, dtype, out, status, counts, (hipStream_t)stream);
+}
+
+size_t dsim_score_matrix_cell_weights_workspace_bytes(int n_a, int n_b, int B, int H, int N, int D, int dtype) {
+    return with_slack(score_matrix_cell_weights_scratch_bytes(n_a, n_b, B, H, N, D, dtype));
+}
+
+int dsim_score_matrix_cell_weights(const void* qa, const void* ka, const void* va, const uint8_t* weights_a, int n_a, const void* qb,
+                                   const void* kb, const void* vb, const uint8_t* weights_b, int n_b, int B, int H, int N, int D, int dtype,
+                                   int similarity, float* out, int32_t* status, int32_t* weight_sums, void* workspace,
+                                   size_t workspace_bytes, void* stream) {
+    MatrixArgs a{{qa, qb}, {ka, kb}, {va, vb}, {weights_a, weights_b}, n_a, n_b, B, H, N, D, similarity, workspace, workspace_bytes};
+    const bool served = score_matrix_cell_weights_scratch_bytes(n_a, n_b, B, H, N, D, dtype) != 0 && (similarity == 0 || similarity == 1);
+    const int st = tail_prologue({qa, ka, va, weights_a, qb, kb, vb, weights_b, out}, served ? DSIM_OK : DSIM_ERR_INVALID, a.scratch,
+                                 a.scratch_bytes);
+    return st != DSIM_OK ? st : launch_score_matrix_cell_weights(a, dtype, out, status, weight_sums, (hipStream_t)stream);
+}
+
 size_t dsim_text_attention_workspace_bytes(int n_images, int N, int L) { return with_slack(text_attention_scratch_bytes(n_images, N, L)); }
 
 int dsim_text_attention(const void* xq, int ldq, const void* xk, int ldk, int n_images, int n_kv, int H, int N, int L, int D, int dtype,

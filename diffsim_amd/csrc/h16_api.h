@@ -101,6 +101,18 @@ int launch_pair_align_weights(const PairArgs& a, int dtype, const uint8_t* weigh
 size_t pair_region_transfer_scratch_bytes(int n_feat, int n_pairs, int B, int H, int N, int D);      // 0: call not served
 int launch_pair_region_transfer(const PairArgs& a, int dtype, const uint8_t* weights, int n_feat, int directions, float* mass,
                                 int32_t* status, hipStream_t s);
+// transfer matrix: launch_pair_region_transfer's mirror row for every cell (A_i, B_j) of two sets, a.mask[0] set A's weight bytes
+// (a.q[1], a.k[0] are what it reads) -- transfer_matrix.hip
+//   mass [n_a][n_b][N]; status (may be NULL) [n_a][n_b]
+size_t region_transfer_matrix_scratch_bytes(int n_a, int n_b, int B, int H, int N, int D, int dtype);      // 0: call not served
+int launch_region_transfer_matrix(const MatrixArgs& a, int dtype, float* mass, int32_t* status, hipStream_t s);
+// cell-region score matrices: the region / soft matrix with set B's rows per cell, a.mask[1] [n_a][n_b][N]; set A's self attention
+// once per image, set B's with the cell's cross attention in one workgroup -- cell_matrix.hip
+//   out [n_a][n_b]; status (may be NULL) [n_a][n_b]: 0, 1, 2; counts / weight_sums (may be NULL) [n_a + n_a n_b]
+size_t score_matrix_cell_regions_scratch_bytes(int n_a, int n_b, int B, int H, int N, int D, int dtype);      // 0: call not served
+int launch_score_matrix_cell_regions(const MatrixArgs& a, int dtype, float* out, int32_t* status, int32_t* counts, hipStream_t s);
+size_t score_matrix_cell_weights_scratch_bytes(int n_a, int n_b, int B, int H, int N, int D, int dtype);      // 0: call not served
+int launch_score_matrix_cell_weights(const MatrixArgs& a, int dtype, float* out, int32_t* status, int32_t* weight_sums, hipStream_t s);
 // text attention maps: the tapped block's cross-attention on the conditional CFG half, averaged over the heads; its weighted sum over
 // the prompt tokens (saliency) and the token region above rel_threshold x the image's mean saliency (text_attn_kernel,
 // text_region_kernel, any head dim and dtype, 1 <= L <= 128) -- textattn.hip

@@ -588,8 +588,9 @@ def _token_rows(form: _TokenRows, rows: torch.Tensor, n: int, N: int, what: Opti
     what = what or form.what
     if rows.dtype not in form.dtypes:
         raise _lib.DsimError(f"{what} must be {form.dtype_rule}")
-    if tuple(rows.shape) != (n, N):
-        raise _lib.DsimError(f"{what} must be ({extent}, N) = ({n}, {N}): {tuple(rows.shape)}")
+    want = (*n, N) if isinstance(n, tuple) else (n, N)          # (a tuple: the cell forms' (n_a, n_b))
+    if tuple(rows.shape) != want:
+        raise _lib.DsimError(f"{what} must be ({extent}, N) = ({', '.join(map(str, want))}): {tuple(rows.shape)}")
     if not rows.is_contiguous():
         raise _lib.DsimError(f"{what} must be contiguous")
     return rows.view(torch.uint8)
@@ -931,6 +932,31 @@ def pair_region_transfer(q: torch.Tensor, k: torch.Tensor, weights_u8: torch.Ten
     return (mass, status) if return_status else mass
 
 
+def region_transfer_matrix_workspace_bytes(n_a: int, n_b: int, B: int, heads: int, N: int, D: int, dtype: torch.dtype) -> int:
+    return int(_lib.lib().dsim_region_transfer_matrix_workspace_bytes(n_a, n_b, B, heads, N, D, _TORCH2DSIM.get(dtype, -1)))
+
+
+def region_transfer_matrix(fa, fb, weights_a: torch.Tensor, heads: int, return_status: bool = False):
+    """The transfer matrix (dsim_region_transfer_matrix): the attention mass every image of set B sends into every set-A image's
+    weighted tokens.  fa, fb: (q, k) or (q, k, v) tuples of [n][B][N][H*D] device tensors of one dtype and geometry (v is not read);
+    weights_a: uint8 cuda (n_a, N), token t of A_i weighs byte / 255.  Returns f32 (n_a, n_b, N): cell (i, j) is
+    ``pair_region_transfer(..., directions=2)[p, 1]`` of the pair (a = fa[i], b = fb[j]) -- fb[j]'s queries over fa[i]'s keys and
+    weights, on fb[j]'s grid -- bit for bit, in one launch.  return_status: also an int32 (n_a, n_b) tensor, 1 where a cell has a
+    non-finite probability."""
+    (qa, ka), (qb, kb) = fa[:2], fb[:2]
+    ok = ka.shape == qa.shape and kb.shape == qb.shape and qa.shape[1:] == qb.shape[1:]
+    B, N, D = _check_features((qa, ka, qb, kb), heads, ok, _SETS_MSGS)
+    n_a, n_b, dev, dt = qa.shape[0], qb.shape[0], qa.device, _TORCH2DSIM[qa.dtype]
+    weights_a = _token_rows(_WEIGHTS, weights_a, n_a, N, "the token weights weights_a", "n_a")
+    _require_cuda(qa, ka, qb, kb, weights_a)
+    mass = torch.empty((n_a, n_b, N), dtype=torch.float32, device=dev)
+    status = _i32((n_a, n_b), dev, return_status)
+    _tail_call(dev, "region_transfer_matrix", (n_a, n_b, B, heads, N, D, dt),
+               f"no transfer matrix for n_a={n_a} n_b={n_b} B={B} H={heads} N={N} D={D}", qa.data_ptr(), ka.data_ptr(),
+               weights_a.data_ptr(), n_a, qb.data_ptr(), kb.data_ptr(), n_b, B, heads, N, D, dt, mass.data_ptr(), _ptr(status))
+    return (mass, status) if return_status else mass
+
+
 def score_matrix_workspace_bytes(n_a: int, n_b: int, B: int, heads: int, N: int, D: int, dtype: torch.dtype) -> int:
     return int(_lib.lib().dsim_score_matrix_workspace_bytes(n_a, n_b, B, heads, N, D, _TORCH2DSIM[dtype]))
 
@@ -943,8 +969,17 @@ def score_matrix_weights_workspace_bytes(n_a: int, n_b: int, B: int, heads: int,
     return int(_lib.lib().dsim_score_matrix_weights_workspace_bytes(n_a, n_b, B, heads, N, D, _TORCH2DSIM.get(dtype, -1)))
 
 
-def _score_matrix(fa, fb, heads, similarity, return_status, region=None, return_extra=False):
-    """score_matrix and its two region forms; region: (_TokenRows, set A's rows, set B's rows)"""
+def score_matrix_cell_regions_workspace_bytes(n_a: int, n_b: int, B: int, heads: int, N: int, D: int, dtype: torch.dtype) -> int:
+    return int(_lib.lib().dsim_score_matrix_cell_regions_workspace_bytes(n_a, n_b, B, heads, N, D, _TORCH2DSIM.get(dtype, -1)))
+
+
+def score_matrix_cell_weights_workspace_bytes(n_a: int, n_b: int, B: int, heads: int, N: int, D: int, dtype: torch.dtype) -> int:
+    return int(_lib.lib().dsim_score_matrix_cell_weights_workspace_bytes(n_a, n_b, B, heads, N, D, _TORCH2DSIM.get(dtype, -1)))
+
+
+def _score_matrix(fa, fb, heads, similarity, return_status, region=None, return_extra=False, cells: bool = False):
+    """score_matrix and its two region forms; region: (_TokenRows, set A's rows, set B's rows); cells: set B's rows are
+    (n_a, n_b, N), one per cell (the cell-region forms)"""
     sim = _similarity_code(similarity)
     if region is None:
         _require_cuda(*fa, *fb)
@@ -954,12 +989,18 @@ def _score_matrix(fa, fb, heads, similarity, return_status, region=None, return_
     if region is not None:
         form, rows_a, rows_b = region
         rows_a = _token_rows(form, rows_a, n_a, N, f"{form.what} {form.arg}_a", "n")
-        rows_b = _token_rows(form, rows_b, n_b, N, f"{form.what} {form.arg}_b", "n")
+        if cells:
+            if rows_b.ndim != 3:
+                raise _lib.DsimError(f"{form.what} {form.arg}_b_cells must be (n_a, n_b, N) = ({n_a}, {n_b}, {N}): {tuple(rows_b.shape)}")
+            rows_b = _token_rows(form, rows_b, (n_a, n_b), N, f"{form.what} {form.arg}_b_cells", "n_a, n_b")
+        else:
+            rows_b = _token_rows(form, rows_b, n_b, N, f"{form.what} {form.arg}_b", "n")
         _require_cuda(qa, ka, va, qb, kb, vb, rows_a, rows_b)          # (after the shape checks: those need no device)
-        name, noun, rows_a, rows_b = f"score_matrix_{form.suffix}", form.matrix, (rows_a.data_ptr(),), (rows_b.data_ptr(),)
+        name, noun = f"score_matrix_{'cell_' if cells else ''}{form.suffix}", ("cell-" if cells else "") + form.matrix
+        rows_a, rows_b = (rows_a.data_ptr(),), (rows_b.data_ptr(),)
     out = torch.empty((n_a, n_b), dtype=torch.float32, device=dev)
     status = _i32((n_a, n_b), dev, return_status)
-    extra = _i32(n_a + n_b, dev, return_extra)
+    extra = _i32(n_a + (n_a * n_b if cells else n_b), dev, return_extra)
     _tail_call(dev, name, (n_a, n_b, B, heads, N, D, dt), f"no {noun} for n_a={n_a} n_b={n_b} B={B} H={heads} N={N} D={D}", qa.data_ptr(),
                ka.data_ptr(), va.data_ptr(), *rows_a, n_a, qb.data_ptr(), kb.data_ptr(), vb.data_ptr(), *rows_b, n_b, B, heads, N, D, dt,
                sim, out.data_ptr(), _ptr(status), *(() if region is None else (_ptr(extra),)))
@@ -994,6 +1035,26 @@ def score_matrix_weights(fa, fb, weights_a: torch.Tensor, weights_b: torch.Tenso
     int32 (n_a, n_b) tensor, 1 where the score is NaN / infinite, 2 where an image of the cell has no weight at all (score NaN);
     return_sums: also the int32 (n_a + n_b,) byte sums, set A's then set B's."""
     return _score_matrix(fa, fb, heads, similarity, return_status, (_WEIGHTS, weights_a, weights_b), return_sums)
+
+
+def score_matrix_cell_regions(fa, fb, mask_a: torch.Tensor, mask_b_cells: torch.Tensor, heads: int, similarity: str = "cosine",
+                              return_status: bool = False, return_counts: bool = False):
+    """The cell-region score matrix (dsim_score_matrix_cell_regions): score_matrix_regions with set B's masks per CELL.  fa, fb,
+    mask_a (n_a, N): as score_matrix_regions; mask_b_cells (n_a, n_b, N): bool or uint8 cuda, row [i][j] is fb[j]'s region against
+    query i.  Returns the (n_a, n_b) f32 device tensor whose cell (i, j) is pair_score_regions of (fa[i] over mask_a[i], fb[j] over
+    mask_b_cells[i][j]), bit for bit; fa[i]'s self-attention over its region is computed once, a cell costs three attentions.
+    return_status: also an int32 (n_a, n_b) tensor, 1 where the score is NaN / infinite, 2 where a region of the cell is empty
+    (score NaN); return_counts: also the int32 (n_a + n_a n_b,) region sizes, set A's then the cells' in cell order."""
+    return _score_matrix(fa, fb, heads, similarity, return_status, (_MASKS, mask_a, mask_b_cells), return_counts, cells=True)
+
+
+def score_matrix_cell_weights(fa, fb, weights_a: torch.Tensor, weights_b_cells: torch.Tensor, heads: int, similarity: str = "cosine",
+                              return_status: bool = False, return_sums: bool = False):
+    """The soft cell-region score matrix (dsim_score_matrix_cell_weights): score_matrix_weights with set B's weights per CELL,
+    weights_b_cells uint8 cuda (n_a, n_b, N).  Cell (i, j) is pair_score_weights of (fa[i] under weights_a[i], fb[j] under
+    weights_b_cells[i][j]), bit for bit.  return_status: as score_matrix_weights; return_sums: also the int32 (n_a + n_a n_b,) byte
+    sums, set A's then the cells' in cell order."""
+    return _score_matrix(fa, fb, heads, similarity, return_status, (_WEIGHTS, weights_a, weights_b_cells), return_sums, cells=True)
 
 
 # ---- feature-cosine metrics (diffeats, dinofeats): the tapped self-attention's own output, its pair cosine and Gram matrix -------

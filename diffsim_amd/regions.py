@@ -155,9 +155,11 @@ class RegionKind(NamedTuple):
     align: str
     matrix: str
     matrix_workspace_bytes: str
+    cell_matrix: str                #   the matrix whose set-B rows belong to the cell (exemplar-guided retrieval), and its query
+    cell_matrix_workspace_bytes: str
 
     def tail(self, form: str, bindings) -> Callable:
-        """The kind's engine tail of a form (score, maps, align, matrix, matrix_workspace_bytes) out of `bindings`, the calling
+        """The kind's engine tail of a form (score, maps, align, matrix, cell_matrix and the two workspace queries) out of `bindings`, the calling
         module's globals(): every module calls its own binding of an engine tail, as it does engine.pair_score's
         (``Scorer.pair_tail``), so a stand-in bound there serves that module alone."""
         return bindings[getattr(self, form)]
@@ -203,11 +205,11 @@ class RegionKind(NamedTuple):
 
 HARD = RegionKind(False, as_token_mask, torch.bool, True, "mask", "the mask of image {} has no token on (an empty region has no score)",
                   "mask", "pair_score_regions", "pair_score_maps_regions", "pair_align_regions", "score_matrix_regions",
-                  "score_matrix_regions_workspace_bytes")
+                  "score_matrix_regions_workspace_bytes", "score_matrix_cell_regions", "score_matrix_cell_regions_workspace_bytes")
 SOFT = RegionKind(True, as_token_weights, torch.uint8, 255, "weight",
                   "the weights of image {} are all 0 (an image without weight has no score)", "weights",
                   "pair_score_weights", "pair_score_maps_weights", "pair_align_weights", "score_matrix_weights",
-                  "score_matrix_weights_workspace_bytes")
+                  "score_matrix_weights_workspace_bytes", "score_matrix_cell_weights", "score_matrix_cell_weights_workspace_bytes")
 
 
 def kind_of(soft: bool) -> RegionKind:

@@ -15,6 +15,11 @@ retrieved, the background takes part in no softmax -- at the same n_a + n_b forw
 weights (``regions.as_token_weights``) and the matrix is the soft score matrix (``engine.score_matrix_weights``): cell (i, j) is
 ``regions.score_latent_pair_weights`` of that pair.
 
+In ``score_latent_matrix_exemplar`` (``score_path_matrix(exemplar=)``) only the queries carry masks, and every gallery image's region is the one the
+query's mask transfers to it -- a region per CELL: per gallery chunk one ``engine.region_transfer_matrix`` launch, the region rule
+(``transfer.region_of_mass``) on all its masses, and one cell-region matrix (``engine.score_matrix_cell_regions`` / ``_weights``).
+Cell (i, j) is ``transfer.score_latent_pairs_exemplar`` of that pair: score, region and mass.
+
 A scorer with a matrix tail of its own (``Scorer.matrix_tail``: the feature-cosine metrics of ``feats.py``) ranks through it: what the
 query set contributes is computed once per call, each gallery chunk's once, and one ``engine.feature_matrix`` per chunk.
 """
@@ -26,11 +31,14 @@ from typing import List, Optional, Sequence
 import torch
 
 from ._lib import DsimError
-from .engine import (score_matrix, score_matrix_regions, score_matrix_regions_workspace_bytes, score_matrix_weights,  # noqa: F401
+from .engine import (region_transfer_matrix_workspace_bytes, score_matrix, score_matrix_cell_regions,  # noqa: F401
+                     score_matrix_cell_regions_workspace_bytes, score_matrix_cell_weights, score_matrix_cell_weights_workspace_bytes,
+                     score_matrix_regions, score_matrix_regions_workspace_bytes, score_matrix_weights,
                      score_matrix_weights_workspace_bytes, score_matrix_workspace_bytes)          # (RegionKind.tail finds them)
 from .inputs import path_latents
 from .regions import kind_of, tap_grid
 from .scorer import stack_rows
+from .transfer import ExemplarGuide, require_exemplar_regions
 
 IMAGE_EXTS = (".png", ".jpg", ".jpeg")
 ENCODE_CHUNK = 16               # images per VAE encode, per side (32 at 512 px keep its widest activation < 2 GiB)
@@ -76,6 +84,31 @@ def score_latent_matrix(scorer, latA, latB, noiseA, noiseB, prompt, target_block
     score matrix.
     soft: the masks are token weights (``regions.as_token_weights``: a mask file's area average per token, uint8 bytes, floats in
     [0, 1]) and the matrix is the soft score matrix; an image whose weights are all 0 is the whole image."""
+    return _latent_matrix(scorer, latA, latB, noiseA, noiseB, prompt, target_block, target_layer, target_step, similarity, batch,
+                          return_status, masks_a, masks_b, soft, None, False)
+
+
+@torch.no_grad()
+def score_latent_matrix_exemplar(scorer, latA, latB, noiseA, noiseB, prompt, target_block="up_blocks", target_layer=0, target_step=600,
+                                 similarity="cosine", batch: Optional[int] = None, return_status: bool = False, *, masks_a=None,
+                                 exemplar: Optional[ExemplarGuide] = None, return_regions: bool = False):
+    """``score_latent_matrix`` with exemplar-guided regions (the matrix form of ``transfer.score_latent_pairs_exemplar``; a function
+    beside ``score_latent_matrix`` as that one is beside ``score_latent_pairs``): masks_a are the exemplars' masks (None: every
+    exemplar whole), the gallery has none, and gallery image j's region against query i is what masks_a[i] transfers to it.
+    exemplar: the ``transfer.ExemplarGuide`` with the threshold and the kind (soft: the masks are token weights and the transferred
+    regions too); None: ``ExemplarGuide()``.  Its ``on_fraction`` accumulates over the cells.  Cell (i, j) is
+    ``transfer.score_latent_pairs_exemplar`` of the pair (latA[i], latB[j]): score, region and mass, bit for bit.
+    return_regions: the result is followed by the transferred regions (n_a, n_b, h, w), bool or uint8, and the masses
+    (n_a, n_b, h, w) f32 on the gallery images' grids.  The other arguments: as ``score_latent_matrix``."""
+    require_exemplar_regions(scorer)
+    exemplar = ExemplarGuide() if exemplar is None else exemplar
+    return _latent_matrix(scorer, latA, latB, noiseA, noiseB, prompt, target_block, target_layer, target_step, similarity, batch,
+                          return_status, masks_a, None, exemplar.soft, exemplar, return_regions)
+
+
+def _latent_matrix(scorer, latA, latB, noiseA, noiseB, prompt, target_block, target_layer, target_step, similarity, batch,
+                   return_status, masks_a, masks_b, soft, exemplar, return_regions):
+    """score_latent_matrix and score_latent_matrix_exemplar: one chunked gallery loop"""
     dev = scorer.device
     latA = latA.to(dev, torch.float32)
     latB = latB.to(dev, torch.float32)
@@ -100,13 +133,21 @@ def score_latent_matrix(scorer, latA, latB, noiseA, noiseB, prompt, target_block
     bad = torch.zeros((), dtype=torch.int64, device=dev)
     _, B, N, HD = fa[0].shape
     chunk = min(batch, n_b) if n_b else 1
-    masked = masks_a is not None or masks_b is not None
+    masked = masks_a is not None or masks_b is not None or exemplar is not None
     workspace_bytes = score_matrix_workspace_bytes
+    if mtail is not None and exemplar is not None:
+        raise DsimError(f"{type(scorer).__name__} ranks with a matrix tail of its own (Scorer.matrix_tail): it has no region matrix")
     if masked:
         kind = kind_of(soft)
         grid = tap_grid(scorer, tap, latA.shape[-1])
         masks_a, masks_b = kind.set_rows(masks_a, n_a, grid, dev, "masks_a"), kind.set_rows(masks_b, n_b, grid, dev, "masks_b")
         workspace_bytes = kind.tail("matrix_workspace_bytes", globals())
+        if exemplar is not None:            # the transfer's workspace is freed before the cell matrix asks for its own: the larger of the two
+            cells_bytes = kind.tail("cell_matrix_workspace_bytes", globals())
+
+            def workspace_bytes(*shape):
+                return max(cells_bytes(*shape), region_transfer_matrix_workspace_bytes(*shape))
+            made, masses = [], []
     elif soft:
         raise DsimError("soft=True weighs masks: give masks_a and / or masks_b")
     if mtail is not None:
@@ -123,6 +164,12 @@ def score_latent_matrix(scorer, latA, latB, noiseA, noiseB, prompt, target_block
         fb = _features(scorer, latB[j0:j1], nB, prompt, tap, target_step, batch)
         if mtail is not None:
             s, st = mtail.matrix(ga, mtail.features(fb, heads))
+        elif exemplar is not None:
+            region, mass = exemplar.cell_regions(fa, fb, heads, masks_a)
+            s, st = kind.tail("cell_matrix", globals())(fa, fb, masks_a, region.contiguous(), heads, similarity, return_status=True)
+            st = st != 0
+            if return_regions:
+                made.append(region), masses.append(mass)
         elif masked:
             s, st = kind.tail("matrix", globals())(fa, fb, masks_a, masks_b[j0:j1], heads, similarity, return_status=True)      # (a row slice: contiguous)
             st = st != 0
@@ -130,22 +177,39 @@ def score_latent_matrix(scorer, latA, latB, noiseA, noiseB, prompt, target_block
             s, st = score_matrix(fa, fb, heads, similarity, return_status=True)
         out[:, j0:j1] = s
         bad += st.sum()
-    return (out, int(bad)) if return_status else out
+    res = (out, int(bad)) if return_status else (out,)
+    if return_regions:
+        res = (*res, torch.cat(made, dim=1).reshape(n_a, n_b, *grid), torch.cat(masses, dim=1).reshape(n_a, n_b, *grid))
+    return res if len(res) > 1 else res[0]
 
 
 @torch.no_grad()
 def score_path_matrix(scorer, paths_a: Sequence[str], paths_b: Sequence[str], img_size, prompt, target_block="up_blocks",
                       target_layer=0, target_step=600, seed=2333, similarity="cosine", batch: Optional[int] = None,
-                      return_status: bool = False, *, masks_a=None, masks_b=None, soft: bool = False):
+                      return_status: bool = False, *, masks_a=None, masks_b=None, soft: bool = False,
+                      exemplar: Optional[ExemplarGuide] = None, return_regions: bool = False):
     """The (len(paths_a), len(paths_b)) matrix of ``diffsim(paths_a[i], paths_b[j], ...)`` scores: the query images are
     encoded with the reseeded generator's slot-A VAE draw and noise, the gallery images with the slot-B ones
     (``inputs.path_latents``).  Through the scorer's HIP VAE fast path where it has one.  masks_a / masks_b: as
-    ``score_latent_matrix`` takes them, one per path; soft: as there."""
+    ``score_latent_matrix`` takes them, one per path; soft: as there.  exemplar: a ``transfer.ExemplarGuide`` -- the
+    exemplar-guided matrix (``score_latent_matrix_exemplar``): masks_a are the exemplars' masks and masks_b must be None;
+    return_regions (with exemplar): as there."""
+    if exemplar is not None:
+        if masks_b is not None:
+            raise DsimError("exemplar-guided matrix: the gallery's regions are the transferred ones, masks_b must be None")
+        require_exemplar_regions(scorer)
+    elif return_regions:
+        raise DsimError("return_regions returns the transferred regions: it needs exemplar=")
     if not paths_a or not paths_b:
+        if return_regions:
+            raise ValueError("no cells to return regions of")
         empty = torch.empty((len(paths_a), len(paths_b)), dtype=torch.float32, device=scorer.device)
         return (empty, 0) if return_status else empty
     (latA,), nA, _ = path_latents(scorer, [(p,) for p in paths_a], (0,), img_size, seed, ENCODE_CHUNK)
     (latB,), _, nB = path_latents(scorer, [(p,) for p in paths_b], (1,), img_size, seed, ENCODE_CHUNK)
+    if exemplar is not None:
+        return score_latent_matrix_exemplar(scorer, latA, latB, nA, nB, prompt, target_block, target_layer, target_step, similarity,
+                                            batch, return_status, masks_a=masks_a, exemplar=exemplar, return_regions=return_regions)
     return score_latent_matrix(scorer, latA, latB, nA, nB, prompt, target_block, target_layer, target_step, similarity, batch,
                                return_status, masks_a=masks_a, masks_b=masks_b, soft=soft)
 

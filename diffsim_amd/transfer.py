@@ -20,7 +20,7 @@ from typing import Optional, Sequence, Tuple
 
 import torch
 
-from .engine import pair_region_transfer, pair_score_regions, pair_score_weights      # noqa: F401  (RegionKind.tail)
+from .engine import pair_region_transfer, pair_score_regions, pair_score_weights, region_transfer_matrix      # noqa: F401  (RegionKind.tail)
 from .inputs import path_latents
 from .regions import chunk_tails, kind_of, tap_grid
 from .textattn import soft_token_bytes
@@ -72,10 +72,36 @@ class ExemplarGuide:
         region = region_of_mass(mass, full, self.rel_threshold, self.soft)
         out = bytes_ if self.soft else bytes_ != 0
         out[lb] = region
+        self.account(region)
+        return (out, mass) if return_mass else out
+
+    def account(self, region: torch.Tensor):
+        """Adds transferred regions (bool masks or uint8 weights, any shape with the tokens last) to ``on_fraction``'s running sums:
+        what ``regions`` and ``cell_regions`` both do with the regions they make.  No device read."""
         on = region.sum(dtype=torch.float64) / (255.0 if self.soft else 1.0)
         self._on = on if self._on is None else self._on + on
         self._seen += region.numel()
-        return (out, mass) if return_mass else out
+
+    def cell_regions(self, fa, fb, heads: int, rows_a: torch.Tensor):
+        """The regions of a score matrix's cells: (regions (n_a, n_b, N) bool or uint8, mass (n_a, n_b, N) f32) on the device, row
+        [i][j] what exemplar fa[i]'s row rows_a[i] transfers to gallery image fb[j] -- ``regions``' values for the pair (fa[i], fb[j]),
+        bit for bit, from one transfer-matrix launch (``engine.region_transfer_matrix``) and one pass of the region rule over the
+        (n_a n_b, N) masses with an exemplar's ``full`` repeated along its row.  fa, fb: the sets' (q, k, v); rows_a: (n_a, N) rows of
+        the guide's kind, no row empty (``RegionKind.set_rows`` makes them).  An exemplar that is fully on makes every gallery image
+        of its row whole, with mass 1, as ``regions`` does without a launch; with every exemplar fully on nothing is launched."""
+        want = kind_of(self.soft).dtype
+        if rows_a.dtype != want or rows_a.ndim != 2:
+            raise ValueError(f"a {'soft' if self.soft else 'hard'} guide takes (n_a, N) {want} rows: {rows_a.dtype} {tuple(rows_a.shape)}")
+        n_a, n_b, N = rows_a.shape[0], fb[0].shape[0], rows_a.shape[1]
+        bytes_ = rows_a if self.soft else rows_a.to(torch.uint8) * 255
+        bytes_ = torch.where((bytes_ != 0).any(1, keepdim=True), bytes_, torch.full_like(bytes_, 255))      # an empty row: the whole image
+        full = (bytes_ == 255).all(1)                            # (n_a,)
+        mass = torch.ones((n_a, n_b, N), dtype=torch.float32, device=rows_a.device)
+        if not bool(full.all()):                                 # (one device read per chunk: whether the kernel is needed)
+            mass = torch.where(full[:, None, None], mass, region_transfer_matrix(fa, fb, bytes_.contiguous(), heads))
+        region = region_of_mass(mass.reshape(n_a * n_b, N), full.repeat_interleave(n_b), self.rel_threshold, self.soft)
+        self.account(region)
+        return region.reshape(n_a, n_b, N), mass
 
     @property
     def on_fraction(self) -> float:

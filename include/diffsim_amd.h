@@ -552,6 +552,57 @@ int    dsim_pair_region_transfer(const void* q, const void* k, const uint8_t* we
                                  float* mass /* [n_pairs][2][N] */, int32_t* status /* NULL or [n_pairs] */,
                                  void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- transfer matrix: the mass every gallery image sends into every query's weighted tokens (additive to ABI v7) ------------------
+ * Set A has n_a feature images with weight bytes weights_a [n_a][N] (w = byte / 255), set B has n_b images and no weights; the sets
+ * are separate tensors, as dsim_score_matrix's.  Cell (i, j) is dsim_pair_region_transfer's mass[p][1] of the pair (a = A_i, b = B_j):
+ *   mass[i][j][u] = sum_t Pm_ba[u][t] w_a[t]   (on B_j's grid: B_j's queries over A_i's keys, weighted by A_i's bytes)
+ * bit for bit, in every dtype and at every head dim: the same logits, online maximum, l and num with the same fma order,
+ * r_bh = num / l, and the fold over (b, h) ascending times 1 / (B H).
+ *   qa,ka       : dtype [n_a][B][N][H*D];  qb,kb: dtype [n_b][B][N][H*D] (no v; the kernel reads qb and ka only)
+ *   weights_a   : device uint8 [n_a][N]
+ *   mass        : device f32 [n_a][n_b][N]
+ *   status      : NULL, or device int32 [n_a][n_b]: 1 where a probability of the cell is non-finite
+ * The workspace holds r_bh, f32 [n_a n_b][B H][N]: one direction only.  Deterministic, no atomics, one writer per element; a cell's
+ * row depends on its two images and A_i's weights alone.  All checks before anything is enqueued: DSIM_ERR_INVALID (workspace query:
+ * 0) for a bad dtype or head dim, n_a < 1 or n_b < 1, n_a + n_b > 65535, B H > 65535, ceil(N/128) n_a n_b >= 2^31, or any tensor
+ * (features, weights, masses, workspace) of 2^31 elements or more; DSIM_ERR_INVALID for a NULL pointer other than status;
+ * DSIM_ERR_WORKSPACE for a short workspace. */
+size_t dsim_region_transfer_matrix_workspace_bytes(int n_a, int n_b, int B, int H, int N, int D, int dtype);
+int    dsim_region_transfer_matrix(const void* qa, const void* ka, const uint8_t* weights_a /* [n_a][N] */, int n_a,
+                                   const void* qb, const void* kb, int n_b, int B, int H, int N, int D, int dtype,
+                                   float* mass /* [n_a][n_b][N] */, int32_t* status /* NULL or [n_a][n_b] */,
+                                   void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- cell-region score matrices: set B's region belongs to the cell, not to the image (additive to ABI v7) ------------------------
+ * dsim_score_matrix_regions / dsim_score_matrix_weights with one change: set B's masks or weights are [n_a][n_b][N], one row per
+ * cell; set A's stay [n_a][N].  Cell (i, j) is dsim_pair_score_regions (dsim_pair_score_weights) of the pair (A_i, B_j) under the
+ * rows (mask_a[i], mask_b[i][j]), bit for bit: the same lists over the non-zero bytes in ascending order, the same rounding points,
+ * the same bias table and (float)m / 255.0f factors, the same partial layout and f64 fold.  With mask_b[i][j] equal for all i it is
+ * dsim_score_matrix_regions' (dsim_score_matrix_weights') cell, bit for bit.
+ * A_i's self-attention over its region is computed once per query image; B_j's depends on the cell and runs with the cell's cross
+ * attention in one workgroup: a cell costs three attentions.
+ *   out         : device f32 [n_a][n_b]
+ *   status      : NULL, or device int32 [n_a][n_b]: 0, 1 where the score is NaN or infinite, 2 where mask_a[i] or mask_b[i][j] is
+ *                 empty (weights: has byte sum 0); such a cell is NaN and disturbs no other cell
+ *   counts / weight_sums : NULL, or device int32 [n_a + n_a n_b]: set A's region sizes (byte sums), then the cells' in cell order
+ * Deterministic, no atomics; a cell depends on its two images and its two rows alone; rows outside a region are never read.
+ * Refusals as dsim_score_matrix_regions (dsim_score_matrix_weights) with n_a + n_a n_b rows where those have n_a + n_b:
+ * DSIM_ERR_INVALID (workspace query: 0) or DSIM_ERR_WORKSPACE, decided on the host before anything is enqueued. */
+size_t dsim_score_matrix_cell_regions_workspace_bytes(int n_a, int n_b, int B, int H, int N, int D, int dtype);
+int    dsim_score_matrix_cell_regions(const void* qa, const void* ka, const void* va, const uint8_t* mask_a /* [n_a][N] */, int n_a,
+                                      const void* qb, const void* kb, const void* vb, const uint8_t* mask_b /* [n_a][n_b][N] */, int n_b,
+                                      int B, int H, int N, int D, int dtype, int similarity,
+                                      float* out /* [n_a][n_b] */, int32_t* status /* NULL or [n_a][n_b]: 0 | 1 | 2 */,
+                                      int32_t* counts /* NULL or [n_a + n_a n_b] */,
+                                      void* workspace, size_t workspace_bytes, void* stream);
+size_t dsim_score_matrix_cell_weights_workspace_bytes(int n_a, int n_b, int B, int H, int N, int D, int dtype);
+int    dsim_score_matrix_cell_weights(const void* qa, const void* ka, const void* va, const uint8_t* weights_a /* [n_a][N] */, int n_a,
+                                      const void* qb, const void* kb, const void* vb, const uint8_t* weights_b /* [n_a][n_b][N] */,
+                                      int n_b, int B, int H, int N, int D, int dtype, int similarity,
+                                      float* out /* [n_a][n_b] */, int32_t* status /* NULL or [n_a][n_b]: 0 | 1 | 2 */,
+                                      int32_t* weight_sums /* NULL or [n_a + n_a n_b] */,
+                                      void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- VAE encoder: replaces `pipe.vae.encode(image)` in
  *      DiffSim.prepare_image_latents (diffsim/diffsim.py:92-96).  Sampling
  *      z = mean + exp(0.5*clamp(logvar,-30,20))*eps and the 0.18215 scaling stay with the caller,
