@@ -290,6 +290,7 @@ static int dit_plan(dsim_dit* h, int n_images, const std::vector<DTap>& taps, si
     DWalk w{h, &ar, nullptr, n_images, false};
     w.taps = taps;
     CK(w.go(nullptr, nullptr, 0.f, 0.f));
+    if (w.max_tensor >= 0x7fffffffull) return DSIM_ERR_INVALID;      // a >= 2 GiB activation: the batch does not fit one call (32-bit tensor offsets)
     *peak = ar.peak;
     return DSIM_OK;
 }

@@ -347,6 +347,7 @@ static int vae_plan(dsim_vae* h, int n_images, int image_size, size_t* peak) {
     Arena ar;
     VWalk w{h, &ar, nullptr, n_images, false};
     CK(w.go(nullptr, image_size, nullptr));
+    if (w.max_tensor >= 0x7fffffffull) return DSIM_ERR_INVALID;      // a >= 2 GiB activation: the batch does not fit one call (32-bit tensor offsets)
     *peak = ar.peak;
     return DSIM_OK;
 }

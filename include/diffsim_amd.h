@@ -624,6 +624,8 @@ void   dsim_vae_destroy(dsim_vae* h);
 int    dsim_vae_load_weight(dsim_vae* h, const char* key, const void* dev_ptr, int dtype,
                             const int64_t* shape, int ndim);
 int    dsim_vae_finalize(dsim_vae* h, void* stream);
+/* Workspace of one dsim_vae_encode call; 0 for a call it refuses: an image size the encoder does not take, or a batch one of whose
+ * activations would reach 2 GiB (32-bit tensor offsets), which dsim_vae_encode refuses with DSIM_ERR_INVALID before it enqueues */
 size_t dsim_vae_workspace_bytes(const dsim_vae* h, int n_images, int image_size);
 /* images: f32 [n][3][S][S] in [-1,1] (process_image output); moments (out): f32 [n][2*latent][S/8][S/8]
  * = cat(mean, logvar) exactly as AutoencoderKL's quant_conv output */
@@ -671,6 +673,8 @@ int    dsim_dit_set_attention(dsim_dit* h, int mode);
 int    dsim_dit_profile(dsim_dit* h, int enable);
 int    dsim_dit_profile_count(const dsim_dit* h);
 int    dsim_dit_profile_get(dsim_dit* h, int i, char* name, int name_cap, double* flops, double* bytes, double* ms);
+/* Workspace of one dsim_dit_qkv call; 0 for a batch one of whose activations would reach 2 GiB (32-bit tensor offsets), which
+ * dsim_dit_qkv refuses with DSIM_ERR_INVALID before it enqueues anything */
 size_t dsim_dit_workspace_bytes(const dsim_dit* h, int n_images);
 /* Move the tap (the block whose attention q,k,v are emitted) without re-packing: ONE weight copy serves every
  * --target_layer of diffsim_DiT.diffsim_score (diffsim/diffsim_dit.py:100-104 hooks model.blocks[target_layer[0]].attn).
