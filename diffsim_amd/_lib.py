@@ -110,6 +110,13 @@ class ViTCfgC(C.Structure):
                 [("ln_eps", C.c_float), ("compute_dtype", C.c_int32), ("tap_layer", C.c_int32)])
 
 
+VGG_MAX_PLAN = 32        # DSIM_VGG_MAX_PLAN
+
+
+class VGGCfgC(C.Structure):
+    _fields_ = [("in_channels", C.c_int32), ("plan", C.c_int32 * VGG_MAX_PLAN), ("compute_dtype", C.c_int32)]
+
+
 class ResizeImageC(C.Structure):
     """dsim_resize_image (include/diffsim_amd.h)"""
     _fields_ = [("src_offset", C.c_int64), ("w", C.c_int32), ("h", C.c_int32), ("h_table", C.c_int32), ("v_table", C.c_int32),
@@ -198,6 +205,20 @@ SYMBOLS = {
     "dsim_vit_qkv": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dsim_vit_taps_workspace_bytes": (_sz, [_vp, _i, _i, C.POINTER(_i)]),
     "dsim_vit_qkv_taps": (_i, [_vp, _vp, _i, _i, C.POINTER(_i), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _vp, _sz, _vp]),
+    "dsim_vgg_create": (_i, [C.POINTER(VGGCfgC), C.POINTER(_vp)]),
+    "dsim_vgg_destroy": (None, [_vp]),
+    "dsim_vgg_load_weight": (_i, [_vp, C.c_char_p, _vp, _i, C.POINTER(C.c_int64), _i]),
+    "dsim_vgg_finalize": (_i, [_vp, _vp]),
+    "dsim_vgg_profile": (_i, [_vp, _i]),
+    "dsim_vgg_profile_count": (_i, [_vp]),
+    "dsim_vgg_profile_get": (_i, [_vp, _i, C.c_char_p, _i, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "dsim_vgg_out_shape": (_i, [_vp, _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
+    "dsim_vgg_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
+    "dsim_vgg_features": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "dsim_op_relu": (_i, [_vp, _sz, _i, _vp]),
+    "dsim_op_relu_pool2": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "dsim_gram_rows_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "dsim_gram_rows": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "dsim_pair_score_proj_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
     "dsim_pair_score_proj": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dsim_attn_features_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i, _i]),
@@ -206,6 +227,8 @@ SYMBOLS = {
     "dsim_feature_pair_score": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "dsim_feature_matrix_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "dsim_feature_matrix": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "dsim_feature_matrix_chunked_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "dsim_feature_matrix_chunked": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "dsim_pair_score_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "dsim_pair_score": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "dsim_pair_score_status": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),

@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libdiffsim_amd.so")
-SOURCES = ["gemm.hip", "gemm_skinny.hip", "rowres.hip", "norm.hip", "attention.hip", "tails.hip", "align.hip", "regions.hip", "soft_regions.hip", "region_matrix.hip", "soft_matrix.hip", "cell_matrix.hip", "region_maps.hip", "soft_maps.hip", "textattn.hip", "transfer.hip", "transfer_matrix.hip", "attn160.hip", "attention_fp8.hip", "pack.hip", "api.hip", "unet.hip", "vae.hip", "dit.hip", "vit.hip", "tail_proj.hip", "feats.hip", "resize.hip"]
+SOURCES = ["gemm.hip", "gemm_skinny.hip", "rowres.hip", "norm.hip", "attention.hip", "tails.hip", "align.hip", "regions.hip", "soft_regions.hip", "region_matrix.hip", "soft_matrix.hip", "cell_matrix.hip", "region_maps.hip", "soft_maps.hip", "textattn.hip", "transfer.hip", "transfer_matrix.hip", "attn160.hip", "attention_fp8.hip", "pack.hip", "api.hip", "unet.hip", "vae.hip", "dit.hip", "vit.hip", "tail_proj.hip", "feats.hip", "resize.hip", "vgg.hip"]
 # the kernel sources written against the 16-bit type h16 are compiled a second time with h16 = fp16 (csrc/common.h): the
 # compute dtype DSIM_F16, which the bf16 objects' entry points forward to their twins in namespace dsim::f16
 F16_SOURCES = ["gemm.hip", "gemm_skinny.hip", "rowres.hip", "attention.hip", "tails.hip", "align.hip", "regions.hip", "soft_regions.hip", "region_matrix.hip", "soft_matrix.hip", "cell_matrix.hip", "region_maps.hip", "soft_maps.hip", "textattn.hip", "transfer.hip", "transfer_matrix.hip", "attn160.hip", "tail_proj.hip", "feats.hip"]

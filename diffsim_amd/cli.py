@@ -1,6 +1,6 @@
 """Command-line driver: the reference's benchmark loops on the MI355X engine.
 
-``python -m diffsim_amd --dataset cute|nights|sref --metric diffsim|diffsim_xl|dit|clip_cross|dino_cross|diffeats|dinofeats --model_path <dir> --image_path <dir> ...``
+``python -m diffsim_amd --dataset cute|nights|sref --metric diffsim|diffsim_xl|dit|clip_cross|dino_cross|diffeats|dinofeats|gram --model_path <dir> --image_path <dir> ...``
 
 Flags of the reference drivers (``/root/reference/argprocess.py:5-18``) keep their names, meaning and defaults;
 ``--dataset`` selects which of the reference's loops runs (``cute_main.py:48-226``, ``night_main.py:24-173`` or
@@ -20,9 +20,10 @@ from typing import List, Optional, Tuple
 
 METRICS = ["diffsim", "diffsim_xl", "clip_i", "clip_cross", "dino", "dinov1", "dino_cross", "cute", "lpips", "gram",
            "diffeats", "clipfeats", "dinofeats", "ensemble", "dit"]
-ENGINE_METRICS = ("diffsim", "diffsim_xl", "dit", "clip_cross", "dino_cross", "diffeats", "dinofeats")
+ENGINE_METRICS = ("diffsim", "diffsim_xl", "dit", "clip_cross", "dino_cross", "diffeats", "dinofeats", "gram")
 VIT_METRICS = ("clip_cross", "dino_cross")      # DiffSim's method on a ViT tower (vit.py): no VAE, no noise, no prompt, no token grid
 FEATURE_METRICS = ("diffeats", "dinofeats")     # the cosine of the tapped layer's own features (feats.py), the paper's ablation
+GRAM_METRIC = "gram"                            # the VGG-19 Gram style baseline (gram.py): no VAE, noise, prompt, taps or tokens
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -135,6 +136,9 @@ def build_parser() -> argparse.ArgumentParser:
                    help="decode the image files on the host and resize them on the GPU (PIL's Lanczos / bicubic arithmetic, bit for "
                         "bit: the same scores); images outside the served range are resized by PIL on the host")
     p.add_argument("--fp8_attention", action="store_true", help="--metric dit: e4m3 MFMA attention")
+    p.add_argument("--gram_full", action="store_true", default=argparse.SUPPRESS,      # (off: _Args.gram_full)
+                   help="--metric gram: the cosine of the whole 512 x 512 Gram matrices instead of the reference's, which is the cosine "
+                        "of their last rows (vgg_gram.py:81 indexes a tensor with [-1])")
     p.add_argument("--dedup_cfg", dest="dedup_cfg", action="store_true", default=True,
                    help="--metric diffsim: compute what the two CFG halves share once per image (bit-identical scores, ~6 %% faster); the default")
     p.add_argument("--selftest_shard", action="store_true",
@@ -152,6 +156,7 @@ class _Args(argparse.Namespace):
     transfer_masks = False
     transfer_threshold = 1.0
     save_transfer = False
+    gram_full = False
 
 
 def arg_parse(argv=None):
@@ -203,6 +208,30 @@ def arg_parse(argv=None):
             p.error(f"--transfer_masks: --metric {args.metric} has no regions")
         if not (args.transfer_threshold >= 0.0) or args.transfer_threshold == float("inf"):
             p.error("--transfer_threshold must be finite and >= 0")
+    if args.gram_full and args.metric != GRAM_METRIC:
+        p.error("--gram_full chooses the whole Gram matrices of --metric gram: it needs --metric gram")
+    if args.metric == GRAM_METRIC:
+        if args.similarity != "cosine":
+            p.error("--metric gram needs --similarity cosine: its score is always a cosine, as in the reference, and the mse counting "
+                    "rule would read it backwards")
+        for flag, on in (("--mask_path", args.mask_path is not None), ("--query_mask_path", args.query_mask_path is not None),
+                         ("--gallery_mask_path", args.gallery_mask_path is not None), ("--soft_masks", args.soft_masks),
+                         ("--save_region_maps", args.save_region_maps), ("--save_region_matches", args.save_region_matches)):
+            if on:
+                p.error(f"{flag}: --metric gram has no regions (a Gram matrix sums over every position of the image)")
+        for flag, on in (("--save_maps", args.save_maps), ("--save_matches", args.save_matches)):
+            if on:
+                p.error(f"{flag}: --metric gram has no similarity maps or token alignments (its descriptor has no spatial axis)")
+        if args.taps is not None:
+            p.error("--taps: --metric gram has one tap, conv5_1 of VGG-19 (vgg_gram.py:39); there is nothing to sweep")
+        if args.text_attn is not None or args.text_soft:
+            p.error("--text_attn: --metric gram has no prompt and no cross-attention, so no text-guided regions")
+        if args.transfer_masks:
+            p.error("--transfer_masks: --metric gram has no regions, so no exemplar-guided ones")
+        if args.fp8_attention:
+            p.error("--fp8_attention: --metric gram has no attention (--metric dit only)")
+        if args.ngpu is not None and args.ngpu > 1:
+            p.error("--metric gram is single-GPU for now: run it with --ngpu 1")
     if args.metric in FEATURE_METRICS:
         if args.similarity != "cosine":
             p.error(f"--metric {args.metric} needs --similarity cosine: its score is always a cosine, as in the reference (which "
@@ -369,6 +398,10 @@ def build_scorer(args):
     if args.metric in VIT_METRICS:
         print(f"--metric {args.metric}: --image_size is not consulted (the model's image processor decides: resize, then a centre crop)")
         return (loader.load_clip_cross if args.metric == "clip_cross" else loader.load_dino_cross)(args.model_path, args.dtype, dev)
+    if args.metric == GRAM_METRIC:
+        print(f"--metric gram: the cosine of the {'whole Gram matrices' if args.gram_full else 'last rows of the Gram matrices (the reference)'}"
+              f" of VGG-19 conv5_1; images keep their aspect ratio at --image_size {args.image_size}")
+        return loader.load_vgg_gram(args.model_path, args.dtype, dev)
     if args.metric == "dinofeats":
         from .feats import FeatureView
         print("--metric dinofeats: --image_size is not consulted (the model's image processor decides: resize, then a centre crop)")
@@ -485,6 +518,8 @@ def run(args) -> int:
     scorer = None if args.selftest_shard else build_scorer(args)
     if getattr(args, "gpu_resize", False) and scorer is not None:         # (a plain Namespace without the flag: off)
         getattr(scorer, "scorer", scorer).gpu_resize = True         # (a FeatureView: the scorer it wraps)
+    if args.metric == GRAM_METRIC and world > 1:
+        raise SystemExit("--metric gram is single-GPU for now: run it with --ngpu 1")
     layer = args.target_layer if isinstance(args.target_layer, list) else [args.target_layer]
     taps = cli_taps(args, scorer) if args.taps else None
     if rank == 0:
@@ -547,6 +582,8 @@ def run(args) -> int:
                       f"of each prompt, threshold {args.text_threshold:g} x the mean saliency")
         if args.selftest_shard:
             s_ab, s_ac, bad = _selftest_scores(trip, rank, world)
+        elif args.metric == GRAM_METRIC:
+            s_ab, s_ac, bad = scorer.score_path_triplets(trip, args.image_size, args.gram_full)
         else:
             s_ab, s_ac, bad = H.score_path_triplets(scorer, trip, args.image_size, args.target_block, layer, args.target_step,
                                                     args.seed, args.similarity, rank, world, args.batch, args.unet_batch,
@@ -580,7 +617,9 @@ def run_retrieval(args, scorer, layer) -> int:
     except ValueError as e:
         raise SystemExit(str(e))
     exemplar = regions = None
-    if getattr(args, "transfer_masks", False):         # (a plain Namespace without the flag: off)
+    if args.metric == GRAM_METRIC:
+        m, bad = scorer.score_path_matrix(queries, gallery, args.image_size, getattr(args, "gram_full", False), return_status=True)
+    elif getattr(args, "transfer_masks", False):         # (a plain Namespace without the flag: off)
         from .regions import mask_path_for
         from .transfer import ExemplarGuide
         exemplar = ExemplarGuide(args.transfer_threshold, args.soft_masks)

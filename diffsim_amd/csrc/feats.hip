@@ -12,6 +12,7 @@
 //                         (f32 per workgroup in a fixed order, f64 across workgroups), and (x - mn) / (mx - mn) in f32, rounded.
 //  * feat_pair_dot_kernel / feat_pair_finish_kernel: a pair's dot product, f32 per workgroup, f64 across, tail_core.h's cosine finish.
 //  * gram_finish_kernel:  a cell's split-K partials folded in f64 in ascending K order, the same cosine finish.
+//                         (dsim_feature_matrix_chunked: the same two kernels with the caller's chunk in place of GRAM_KCHUNK.)
 // No atomics; an image's features and stats, a pair's score and a cell's value do not depend on what else the call carries.
 // Compiled once per 16-bit type; the C entry points live in the bf16 object.
 #include "tail_core.h"
@@ -36,7 +37,7 @@ struct FeatArgs {
     int launch_feature_pair_score(const void* feats, const float* stats, const int32_t* idx_a, const int32_t* idx_b, int n_pairs,      \
                                   int L, int dtype, float* out, int32_t* status, void* scratch, hipStream_t s);                         \
     int launch_feature_matrix(const void* fa, const float* stats_a, int n_a, const void* fb, const float* stats_b, int n_b, int L,      \
-                              int dtype, float* out, int32_t* status, void* scratch, hipStream_t s);
+                              int dtype, float* out, int32_t* status, void* scratch, hipStream_t s, int kchunk);
 inline namespace DSIM_H16_NS {
 DSIM_FEATS_API
 }
@@ -281,7 +282,9 @@ __global__ void gram_finish_kernel(const float* __restrict__ part, const float* 
 }
 
 inline int blocks_of(int L) { return (L + FCH - 1) / FCH; }
-inline int splits_of(int L) { return (L + GRAM_KCHUNK - 1) / GRAM_KCHUNK; }
+inline int splits_of(int L, int kchunk = GRAM_KCHUNK) { return (L + kchunk - 1) / kchunk; }
+// a caller's K chunk (dsim_feature_matrix_chunked): whole stages of every dtype, no longer than the default
+inline bool kchunk_ok(int kchunk) { return kchunk >= 64 && kchunk <= GRAM_KCHUNK && kchunk % 64 == 0; }
 inline bool dtype_ok(int dtype) { return dtype == DSIM_F32 || dtype == DSIM_BF16 || dtype == DSIM_F16; }
 
 // an image's length: 16-byte vectors in every dtype, 32-bit element offsets inside an image (a last block's end included)
@@ -344,10 +347,10 @@ int launch_pair_t(const void* feats, const float* stats, const int32_t* idx_a, c
 
 template <typename T>
 int launch_gram_t(const void* fa, const float* stats_a, int n_a, const void* fb, const float* stats_b, int n_b, int L, float* out,
-                  int32_t* status, void* scratch, hipStream_t s) {
-    const int splits = splits_of(L);
+                  int32_t* status, void* scratch, hipStream_t s, int kchunk) {
+    const int splits = splits_of(L, kchunk);
     hipLaunchKernelGGL((nt_gemm_kernel<T, true>), dim3((n_a + GM - 1) / GM, (n_b + GN - 1) / GN, splits), dim3(256), 0, s, (const T*)fa, n_a,
-                       (const T*)fb, n_b, L, GRAM_KCHUNK, (const float*)nullptr, (T*)nullptr, (float*)scratch);
+                       (const T*)fb, n_b, L, kchunk, (const float*)nullptr, (T*)nullptr, (float*)scratch);
     const size_t cells = (size_t)n_a * n_b;
     hipLaunchKernelGGL(gram_finish_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, (const float*)scratch, stats_a, stats_b,
                        n_a, n_b, splits, out, status);
@@ -378,11 +381,11 @@ int launch_feature_pair_score(const void* feats, const float* stats, const int32
 }
 
 int launch_feature_matrix(const void* fa, const float* stats_a, int n_a, const void* fb, const float* stats_b, int n_b, int L, int dtype,
-                          float* out, int32_t* status, void* scratch, hipStream_t s) {
+                          float* out, int32_t* status, void* scratch, hipStream_t s, int kchunk) {
     return by_h16_dtype(
         dtype,
-        [&](auto e) { return launch_gram_t<typename decltype(e)::type>(fa, stats_a, n_a, fb, stats_b, n_b, L, out, status, scratch, s); },
-        [&] { return DSIM_F16_TWIN(launch_feature_matrix(fa, stats_a, n_a, fb, stats_b, n_b, L, dtype, out, status, scratch, s)); });
+        [&](auto e) { return launch_gram_t<typename decltype(e)::type>(fa, stats_a, n_a, fb, stats_b, n_b, L, out, status, scratch, s, kchunk); },
+        [&] { return DSIM_F16_TWIN(launch_feature_matrix(fa, stats_a, n_a, fb, stats_b, n_b, L, dtype, out, status, scratch, s, kchunk)); });
 }
 }  // namespace DSIM_H16_NS
 
@@ -403,10 +406,11 @@ size_t pair_scratch(int n_pairs, int L, int dtype) {
     if (!dtype_ok(dtype) || n_pairs < 1 || n_pairs > 65535 || !length_ok(L)) return 0;
     return up256((size_t)n_pairs * blocks_of(L) * 16);
 }
-size_t matrix_scratch(int n_a, int n_b, int L, int dtype) {
-    if (!dtype_ok(dtype) || n_a < 1 || n_b < 1 || !length_ok(L)) return 0;
+size_t matrix_scratch(int n_a, int n_b, int L, int dtype, int kchunk = GRAM_KCHUNK) {
+    if (!dtype_ok(dtype) || n_a < 1 || n_b < 1 || !length_ok(L) || !kchunk_ok(kchunk)) return 0;
     if ((long)n_a * n_b >= (1l << 31) || (n_b + GN - 1) / GN > 65535) return 0;      // the cells; the column tiles' grid axis
-    return up256((size_t)splits_of(L) * n_a * n_b * sizeof(float));
+    if (splits_of(L, kchunk) > 65535) return 0;                                       // the splits' grid axis
+    return up256((size_t)splits_of(L, kchunk) * n_a * n_b * sizeof(float));
 }
 }  // namespace
 
@@ -457,7 +461,23 @@ int dsim_feature_matrix(const void* fa, const float* stats_a, int n_a, const voi
     if (need == 0) return DSIM_ERR_INVALID;
     void* scratch;
     if (!aligned_workspace(workspace, workspace_bytes, need, &scratch)) return DSIM_ERR_WORKSPACE;
-    return launch_feature_matrix(fa, stats_a, n_a, fb, stats_b, n_b, L, dtype, out, status, scratch, (hipStream_t)stream);
+    return launch_feature_matrix(fa, stats_a, n_a, fb, stats_b, n_b, L, dtype, out, status, scratch, (hipStream_t)stream, GRAM_KCHUNK);
+}
+
+size_t dsim_feature_matrix_chunked_workspace_bytes(int n_a, int n_b, int L, int dtype, int k_chunk) {
+    const size_t b = matrix_scratch(n_a, n_b, L, dtype, k_chunk);
+    return b ? b + 256 : 0;
+}
+
+int dsim_feature_matrix_chunked(const void* fa, const float* stats_a, int n_a, const void* fb, const float* stats_b, int n_b, int L,
+                                int dtype, int k_chunk, float* out, int32_t* status, void* workspace, size_t workspace_bytes,
+                                void* stream) {
+    if (!fa || !stats_a || !fb || !stats_b || !out || !workspace) return DSIM_ERR_INVALID;
+    const size_t need = matrix_scratch(n_a, n_b, L, dtype, k_chunk);
+    if (need == 0) return DSIM_ERR_INVALID;
+    void* scratch;
+    if (!aligned_workspace(workspace, workspace_bytes, need, &scratch)) return DSIM_ERR_WORKSPACE;
+    return launch_feature_matrix(fa, stats_a, n_a, fb, stats_b, n_b, L, dtype, out, status, scratch, (hipStream_t)stream, k_chunk);
 }
 
 }  // extern "C"

@@ -1133,8 +1133,9 @@ def feature_matrix_workspace_bytes(n_a: int, n_b: int, L: int, dtype: torch.dtyp
     return int(_lib.lib().dsim_feature_matrix_workspace_bytes(n_a, n_b, L, _TORCH2DSIM.get(dtype, -1)))
 
 
-def feature_matrix(fa, fb, return_status: bool = False):
-    """Every image of set A against every image of set B (dsim_feature_matrix).  fa, fb: (feats, stats) of attn_features, one
+def feature_matrix(fa, fb, return_status: bool = False, k_chunk: Optional[int] = None):
+    """Every image of set A against every image of set B (dsim_feature_matrix; k_chunk: dsim_feature_matrix_chunked, the f32 partial
+    sums ending every k_chunk elements -- for long descriptors of one sign).  fa, fb: (feats, stats) of attn_features, one
     dtype and image length.  Returns the (n_a, n_b) f32 device tensor of cosines; a cell depends on its two images alone and is
     close to, not bit-equal to, feature_pair_score of them.  return_status: also an int32 (n_a, n_b) tensor, 1 where NaN / infinite."""
     (xa, sa), (xb, sb) = fa, fb
@@ -1145,6 +1146,11 @@ def feature_matrix(fa, fb, return_status: bool = False):
     n_a, n_b, dt = xa.shape[0], xb.shape[0], _TORCH2DSIM[xa.dtype]
     out = torch.empty((n_a, n_b), dtype=torch.float32, device=xa.device)
     status = _i32((n_a, n_b), xa.device, return_status)
+    if k_chunk is not None:
+        _tail_call(xa.device, "feature_matrix_chunked", (n_a, n_b, L, dt, int(k_chunk)),
+                   f"no feature matrix for n_a={n_a} n_b={n_b} L={L} k_chunk={k_chunk}", xa.data_ptr(), sa.data_ptr(), n_a, xb.data_ptr(),
+                   sb.data_ptr(), n_b, L, dt, int(k_chunk), out.data_ptr(), _ptr(status))
+        return _with_extras(out, status)
     _tail_call(xa.device, "feature_matrix", (n_a, n_b, L, dt), f"no feature matrix for n_a={n_a} n_b={n_b} L={L}", xa.data_ptr(),
                sa.data_ptr(), n_a, xb.data_ptr(), sb.data_ptr(), n_b, L, dt, out.data_ptr(), _ptr(status))
     return _with_extras(out, status)
@@ -2075,3 +2081,101 @@ class ViTEngine(_Handle):
             _lib.check(self.L.dsim_vit_qkv_taps(self._h, pixels.data_ptr(), n, nt, arr, ptr(0), ptr(1), ptr(2), ws.data_ptr(), ws.numel(),
                                                 _stream_ptr()), "dsim_vit_qkv_taps")
         return outs
+
+
+# ---- VGG Gram style metric: the conv stack and the Gram rows (csrc/vgg.hip) ---------------------------------------------------
+class VGGEngine(_Handle):
+    """One handle = (plan, compute dtype).  plan: conv output channels and "P" / 0 for the 2x2 max-pools, e.g. config.VGG19_PLAN;
+    state_dict: the neutral keys convs.I.{weight,bias}.  One features() call is one batch of equally sized images."""
+
+    prefix = "vgg"
+
+    def __init__(self, plan, state_dict: Dict[str, torch.Tensor], dtype: torch.dtype = torch.bfloat16, device: str = "cuda:0",
+                 in_channels: int = 3):
+        self.L = _lib.lib()
+        if not torch.cuda.is_available():
+            raise _lib.DsimError("no GPU visible: the VGG engine runs only on the HIP device")
+        entries = [0 if e in ("P", "M", 0) else e for e in plan]
+        if not all(isinstance(e, int) and not isinstance(e, bool) and e >= 0 for e in entries) or len(entries) >= _lib.VGG_MAX_PLAN:
+            raise _lib.DsimError(f"bad VGG plan {list(plan)!r}: conv channels and 'P', fewer than {_lib.VGG_MAX_PLAN} entries")
+        self.plan, self.dtype, self.device = tuple(entries), dtype, torch.device(device)
+        c = _lib.VGGCfgC()
+        c.in_channels, c.compute_dtype = int(in_channels), _TORCH2DSIM.get(dtype, -1)
+        for i in range(_lib.VGG_MAX_PLAN):
+            c.plan[i] = entries[i] if i < len(entries) else -1
+        self.in_channels = int(in_channels)
+        self.channels = next((e for e in reversed(entries) if e > 0), 0)
+        self._create_and_load(c, state_dict)
+
+    def out_shape(self, H: int, W: int) -> Tuple[int, int, int]:
+        """(H', W', C) of the tap for H x W inputs"""
+        h, w, ch = C.c_int(), C.c_int(), C.c_int()
+        _lib.check(self.L.dsim_vgg_out_shape(self._h, int(H), int(W), C.byref(h), C.byref(w), C.byref(ch)), "dsim_vgg_out_shape")
+        return h.value, w.value, ch.value
+
+    def workspace_bytes(self, n_images: int, H: int, W: int) -> int:
+        return int(self.L.dsim_vgg_workspace_bytes(self._h, n_images, int(H), int(W)))
+
+    def max_images(self, H: int, W: int, upper: int = 4096) -> int:
+        """Largest n_images one features call accepts at H x W (every activation < 2 GiB)."""
+        return self._largest(lambda m: self.workspace_bytes(m, H, W) > 0, upper)
+
+    def features(self, pixels: torch.Tensor) -> torch.Tensor:
+        """pixels: normalised f32 (n, in_channels, H, W) on the device -> the last conv's output (n, H', W', C), channel-last, in the
+        compute dtype, without ReLU."""
+        _require_cuda(pixels)
+        if pixels.ndim != 4 or pixels.shape[1] != self.in_channels or pixels.dtype != torch.float32 or pixels.shape[0] < 1:
+            raise _lib.DsimError(f"pixels must be float32 (n,{self.in_channels},H,W): {tuple(pixels.shape)} {pixels.dtype}")
+        n, _, H, W = pixels.shape
+        with torch.cuda.device(self.device):
+            need = self.workspace_bytes(n, H, W)
+            if not need:
+                raise _lib.DsimError(f"{n} images of {H}x{W} do not fit one call (smaller than the pools allow, or an activation would "
+                                     "reach 2 GiB)")
+            ws = self._arena(need)
+            out = torch.empty((n,) + self.out_shape(H, W), dtype=self.dtype, device=self.device)
+            _lib.check(self.L.dsim_vgg_features(self._h, pixels.data_ptr(), n, H, W, out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                _stream_ptr()), "dsim_vgg_features")
+        return out
+
+
+def gram_rows_workspace_bytes(n: int, P: int, Cc: int, row0: int, n_rows: int, dtype: torch.dtype) -> int:
+    return int(_lib.lib().dsim_gram_rows_workspace_bytes(n, P, Cc, row0, n_rows, _TORCH2DSIM.get(dtype, -1)))
+
+
+def gram_rows(feat: torch.Tensor, row0: int = 0, n_rows: Optional[int] = None):
+    """Rows [row0, row0 + n_rows) of each image's Gram matrix (dsim_gram_rows): feat (n, ..., C) channel-last of the three dtypes ->
+    (rows f32 (n, n_rows, C), stats f32 (n, 4)), what feature_pair_score / feature_matrix take.  A negative row0 counts from the end."""
+    _require_cuda(feat)
+    if feat.dtype not in _TORCH2DSIM or feat.ndim < 3:
+        raise _lib.DsimError("feat must be contiguous (n, ..., C) of dtype float32, bfloat16 or float16")
+    n, Cc = feat.shape[0], feat.shape[-1]
+    P = feat[0].numel() // max(Cc, 1)
+    row0 = row0 + Cc if row0 < 0 else row0
+    n_rows = Cc - row0 if n_rows is None else int(n_rows)
+    dt = _TORCH2DSIM[feat.dtype]
+    out = torch.empty((n, max(n_rows, 0), Cc), dtype=torch.float32, device=feat.device)
+    stats = torch.empty((n, 4), dtype=torch.float32, device=feat.device)
+    _tail_call(feat.device, "gram_rows", (n, P, Cc, row0, n_rows, dt), f"no Gram rows for n={n} P={P} C={Cc} rows [{row0}, {row0 + n_rows})",
+               feat.data_ptr(), n, P, Cc, row0, n_rows, dt, out.data_ptr(), stats.data_ptr())
+    return out, stats
+
+
+def op_relu(x: torch.Tensor) -> torch.Tensor:
+    """relu(x) on the VGG stack's kernel (a copy; the kernel itself works in place)"""
+    _require_cuda(x)
+    out = x.clone()
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().dsim_op_relu(out.data_ptr(), out.numel(), _TORCH2DSIM.get(x.dtype, -1), _stream_ptr()), "dsim_op_relu")
+    return out
+
+
+def op_relu_pool2(x: torch.Tensor) -> torch.Tensor:
+    """maxpool2x2(relu(x)) of channel-last x (n, H, W, C), floor mode, on the VGG stack's kernel"""
+    _require_cuda(x)
+    n, H, W, Cc = x.shape
+    out = torch.empty((n, H // 2, W // 2, Cc), dtype=x.dtype, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().dsim_op_relu_pool2(x.data_ptr(), out.data_ptr(), n, H, W, Cc, _TORCH2DSIM.get(x.dtype, -1), _stream_ptr()),
+                   "dsim_op_relu_pool2")
+    return out

@@ -265,3 +265,43 @@ def load_dino_cross(model_path: str, dtype: str = "bf16", device: str = "cuda"):
     if not torch.cuda.is_available():
         raise DsimError("no GPU visible: the ViT engine runs only on the HIP device")
     return Dinov2Score(cfg, sd, dev, td, pre)
+
+
+def vgg_gram_files(model_path: str):
+    """(plan, state dict under torchvision's keys) of a VGG checkpoint: a directory with *.safetensors (as load_state_dict reads
+    them) or one .pth / .pt file (torch.load(weights_only=True)), or a .pth / .pt / .safetensors file itself.  An optional
+    config.json {"plan": [...]} beside the weights replaces VGG-19's plan (tests use a small stack)."""
+    from . import gram as G
+    folder = model_path if os.path.isdir(model_path) else os.path.dirname(model_path)
+    if os.path.isdir(model_path):
+        pth = sorted(glob.glob(os.path.join(model_path, "*.pth")) + glob.glob(os.path.join(model_path, "*.pt")))
+        if glob.glob(os.path.join(model_path, "*.safetensors")):
+            sd = load_state_dict(model_path)
+        elif len(pth) == 1:
+            sd = torch.load(pth[0], map_location="cpu", weights_only=True)
+        else:
+            raise FileNotFoundError(f"{model_path}: no *.safetensors and not exactly one .pth / .pt file ({[os.path.basename(p) for p in pth]})")
+    elif model_path.endswith(".safetensors"):
+        from safetensors.torch import load_file
+        sd = load_file(model_path, device="cpu")
+    else:
+        sd = torch.load(model_path, map_location="cpu", weights_only=True)
+    if isinstance(sd, dict) and "state_dict" in sd and not any(k.endswith("features.0.weight") for k in sd):
+        sd = sd["state_dict"]
+    j = _json(folder)
+    try:
+        plan = G.parse_plan(j["plan"]) if "plan" in j else G.VGG19_PLAN
+    except ValueError as e:
+        raise ValueError(f"{os.path.join(folder, 'config.json')}: {e}") from None
+    return plan, sd
+
+
+def load_vgg_gram(model_path: str, dtype: str = "bf16", device: str = "cuda"):
+    """torchvision VGG-19 weights (vgg19-dcbb9e9d.pth, or the same keys as safetensors) -> :class:`diffsim_amd.gram.VGGGram`
+    (metrics/vgg_gram.py:9-15)."""
+    from .gram import VGGGram
+    td = _torch_dtype(dtype)
+    plan, sd = vgg_gram_files(model_path)
+    if not torch.cuda.is_available():
+        raise DsimError("no GPU visible: the VGG engine runs only on the HIP device")
+    return VGGGram(plan, sd, "cuda:0" if device == "cuda" else device, td)

@@ -801,6 +801,75 @@ size_t dsim_feature_matrix_workspace_bytes(int n_a, int n_b, int L, int dtype);
 int    dsim_feature_matrix(const void* fa, const float* stats_a, int n_a, const void* fb, const float* stats_b, int n_b, int L,
                            int dtype, float* out, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
 
+/* dsim_feature_matrix with the caller's K chunk (additive to ABI v7): the same kernels and the same f64 fold, the f32 partial sums
+ * ending every k_chunk elements instead of every 16384 (k_chunk a multiple of 64 in [64, 16384]; 16384 is dsim_feature_matrix bit
+ * for bit, and so is any k_chunk >= L).  For long descriptors whose terms are all of one sign -- the Gram descriptors below -- where a
+ * 16384-term f32 chain rounds a cell to about 4e-6 and 1024-term chains to about 2e-7.  The workspace grows with ceil(L / k_chunk).
+ * Refusals as dsim_feature_matrix, and for a k_chunk outside the list or ceil(L / k_chunk) > 65535. */
+size_t dsim_feature_matrix_chunked_workspace_bytes(int n_a, int n_b, int L, int dtype, int k_chunk);
+int    dsim_feature_matrix_chunked(const void* fa, const float* stats_a, int n_a, const void* fb, const float* stats_b, int n_b, int L,
+                                   int dtype, int k_chunk, float* out, int32_t* status, void* workspace, size_t workspace_bytes,
+                                   void* stream);
+
+/* ---- VGG Gram style metric (additive to ABI v7): the reference's `gram` (metrics/vgg_gram.py).  Replaces torchvision's
+ *      vgg19().features run up to module '28' (conv5_1 BEFORE its ReLU), gram_matrix (G = X X^T over the spatial axis, not
+ *      normalised) and, with dsim_feature_pair_score / dsim_feature_matrix on the f32 rows, the cosine of line 81.
+ *      A conv-only stack: 3x3 convs (stride 1, padding 1, bias), a ReLU behind every conv but the last, 2x2 max-pools of stride 2 in
+ *      floor mode.  Weights under one neutral naming (the Python side maps torchvision's features.N keys): convs.I.weight
+ *      [Cout][Cin][3][3] and convs.I.bias [Cout], I = 0, 1, ... counting the plan's convs. */
+#define DSIM_VGG_MAX_PLAN 32
+typedef struct dsim_vgg_cfg {
+    int32_t in_channels;                /* 3 (1 .. 4: the first conv runs on a direct kernel from the NCHW pixels) */
+    int32_t plan[DSIM_VGG_MAX_PLAN];    /* > 0: a conv's output channels (% 8 == 0; the input channels of every conv but the first
+                                           must be a multiple of 64, the implicit GEMM's K tile); 0: a 2x2 max-pool (only behind a
+                                           conv); -1 ends it.  The first and the last entry are convs; the tap is the last conv's
+                                           output, without ReLU.  VGG-19 to conv5_1: 64,64,0,128,128,0,256 x4,0,512 x4,0,512,-1 */
+    int32_t compute_dtype;              /* DSIM_F32, DSIM_BF16 or DSIM_F16 */
+} dsim_vgg_cfg;
+typedef struct dsim_vgg dsim_vgg;
+
+/* Life cycle, error codes and "every check before the first launch" as the dsim_vit_* calls of the same names.  dsim_vgg_create:
+ * DSIM_ERR_INVALID for a plan that breaks the rules above or has no terminator, and for a dtype outside the three. */
+int    dsim_vgg_create(const dsim_vgg_cfg* cfg, dsim_vgg** out);
+void   dsim_vgg_destroy(dsim_vgg* h);
+int    dsim_vgg_load_weight(dsim_vgg* h, const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim);
+int    dsim_vgg_finalize(dsim_vgg* h, void* stream);
+int    dsim_vgg_profile(dsim_vgg* h, int enable);
+int    dsim_vgg_profile_count(const dsim_vgg* h);
+int    dsim_vgg_profile_get(dsim_vgg* h, int i, char* name, int name_cap, double* flops, double* bytes, double* ms);
+/* the tap's geometry for H x W inputs: H' = H >> pools, W' = W >> pools, C = the last conv's channels; DSIM_ERR_INVALID for an
+ * image smaller than the pools allow */
+int    dsim_vgg_out_shape(const dsim_vgg* h, int H, int W, int* out_h, int* out_w, int* out_c);
+/* One call is one batch of n equally sized images; H and W are independent and need not be even (a pool drops an odd last row or
+ * column without reading it).  pixels: f32 [n][in_channels][H][W], already normalised; out: compute dtype [n][H'][W'][C],
+ * channel-last.  The implicit GEMM addresses tensors with 32-bit offsets: a batch whose largest activation would reach 2 GiB (64
+ * channels at 512 x 768 are 50 MB per image in 16 bits) is refused with DSIM_ERR_INVALID, and dsim_vgg_workspace_bytes returns 0 for
+ * it; split the batch.  DSIM_ERR_INVALID for n < 1 or a NULL pointer, DSIM_ERR_STATE before finalize, DSIM_ERR_WORKSPACE for a short
+ * workspace: all before anything is enqueued.  The executor does not rescale: with real VGG-19 weights fp16 activations can
+ * overflow, bf16 is the mode for this metric. */
+size_t dsim_vgg_workspace_bytes(const dsim_vgg* h, int n_images, int H, int W);
+int    dsim_vgg_features(dsim_vgg* h, const float* pixels, int n_images, int H, int W, void* out, void* workspace,
+                         size_t workspace_bytes, void* stream);
+/* The stack's two element-wise kernels alone (tests): x = relu(x) in place over n_elems elements (a multiple of 16 bytes), and
+ * out [n][H/2][W/2][C] = maxpool2x2(relu(in [n][H][W][C])) (C % 8 == 0, H, W >= 2); NaN propagates through both, as in torch. */
+int    dsim_op_relu(void* x, size_t n_elems, int dtype, void* stream);
+int    dsim_op_relu_pool2(const void* in, void* out, int n, int H, int W, int C, int dtype, void* stream);
+/* dsim_gram_rows: out[i][r - row0][c] = sum_p X_i[p][r] X_i[p][c] for r in [row0, row0 + n_rows), X_i = feat[i] ([P][C],
+ *   channel-last, P = H' W'): rows of the Gram matrix of image i, both operands from the same tile.
+ *     feat        : dtype [n][P][C], 16-byte aligned, C % 8 == 0
+ *     out         : f32 [n][n_rows][C], ALWAYS f32 (Gram entries of real VGG features exceed fp16's range)
+ *     stats (out) : f32 [n][4] = { sum of out^2 (accumulated in f64), min, max, 0 }: what dsim_feature_pair_score /
+ *                   dsim_feature_matrix expect beside out as DSIM_F32 features of L = n_rows C
+ *   16-bit dtypes with n_rows >= 8 and row0 % 8 == 0 run on the matrix cores (32 x 128 tiles, f32 accumulation); f32 features and
+ *   the other row ranges (the reference's single row) on the vector unit with one fma per position, p ascending.  P is split over
+ *   workgroups in 512 positions; the f32 partials fold in ascending p order.  No atomics; an image's rows and stats do not depend
+ *   on the other images of the call.  DSIM_ERR_INVALID (workspace query: 0) for a bad dtype, n < 1, P < 1, C % 8 != 0, a row
+ *   range outside [0, C), n ceil(P / 512) > 65535, n_rows > 65535 or n_rows C > 2^30; DSIM_ERR_WORKSPACE for a short workspace;
+ *   decided on the host before anything is enqueued. */
+size_t dsim_gram_rows_workspace_bytes(int n, int P, int C, int row0, int n_rows, int dtype);
+int    dsim_gram_rows(const void* feat, int n, int P, int C, int row0, int n_rows, int dtype, float* out, float* stats,
+                      void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- the arithmetic either side of the VAE encoder, on the device (the host only decodes and resizes) ----
  * dsim_image_preprocess: what process_image does after its Lanczos resize (diffsim/diffsim.py:31-41): pixels u8 [n][H][W][3] ->
  *   f32 [n][3][H][W] = (p / 255 - 0.5) / 0.5 in IEEE f32, bit-identical to the numpy path; to_half = 1 additionally rounds
